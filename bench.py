@@ -4,13 +4,17 @@ Adam) of the ResNet-50 MIL tile classifier on a bag of 64 synthetic 299x299 IHC 
 (BASELINE.json configs[1]; `--scratch` semantics = encoder gradients on, BN frozen via freeze_bn,
 i.e. the reference loop body train/train.py:32-37).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and reports
+them (`value`, `ms_per_step`); every other figure is measured only with --full:
   roofline     : the dominant conv kernel instantiation, timed per launch with HIP events on the launch stream
   cpu_baseline : the CPU oracle (numerically the reference path) timed on this box's host cores (rank 0, N=1 only)
+  fp32_parity_mode, rccl_world1, secondary (N=1), rccl (N>1): side runs outside the timed region
+--dump-outputs DIR writes what the last timed step computed (loss, logits, a fixed sample of the updated parameters and of the
+gradients) as DIR/<name>.npy in float32, so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -567,11 +571,40 @@ def rccl_world1_side(dev, model, params, opt, x, labels, steps=10, warmup=3, use
                     "top-level figures = eager step, as_one_hip_graph = the same step with its collectives captured and replayed"}
 
 
+DUMP_SAMPLE = 1 << 21           # elements of the parameter / gradient samples (8 MB each in float32)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, loss, logits, params):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the logits of the bag and the model it left behind
+    (the updated parameters and their gradients) -- as float32 .npy files.  The trainable tensors hold tens of millions of elements,
+    so they are written as one fixed, seeded sample of positions in their concatenation (in `model.parameters()` order); a
+    gradient the step did not produce counts as zeros."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params])
+    total = flat_p.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, min(DUMP_SAMPLE, total), replace=False))
+    idx_dev = torch.from_numpy(idx).to(flat_p.device)
+    arrays = {"loss": loss.detach().float().reshape(()).cpu().numpy(),
+              "logits": logits.detach().float().cpu().numpy(),
+              "params_sample": flat_p[idx_dev].cpu().numpy(),
+              "grads_sample": flat_g[idx_dev].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline (per-launch HIP events), CPU baseline, fp32 parity mode, "
+                         "one-rank RCCL side run and the other BASELINE configs (N=1), per-bucket all-reduce times (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, parameter / gradient samples) as DIR/<name>.npy")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fused=True) instead of the one-launch HIP Adam (A/B)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -580,13 +613,15 @@ def main():
     ap.add_argument("--event-every", type=int, default=5, help="HIP-event-bracket the conv launches of every Nth timed step (1 = all)")
     ap.add_argument("--no-rccl-side", action="store_true", help="skip the one-rank RCCL side run (N=1)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other BASELINE configs (N=1)")
-    ap.add_argument("--per-layer", action="store_true", help="also print a per-geometry launch table to stderr")
+    ap.add_argument("--per-layer", action="store_true", help="also print a per-geometry launch table to stderr (with --full)")
     ap.add_argument("--eager", action="store_true", help="enqueue every step from Python (no HIP graph); the default at N > 1")
     ap.add_argument("--graph", action="store_true", help="replay the step as one HIP graph at N > 1 too (RCCL collectives captured)")
     ap.add_argument("--rccl-graph-probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse the N>1 path on a box with fewer GPUs than ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries ONE JSON line and nothing else: RCCL prints a version banner to stdout when a communicator is created, child
     # processes and libraries may print too -- file descriptor 1 points at stderr until the line itself is written
@@ -612,7 +647,7 @@ def main():
     if world > 1:
         import torch.distributed as dist
         if args.backend == "nccl":
-            rccl_log = _rccl_debug_env()
+            rccl_log = _rccl_debug_env() if args.full else None
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group("gloo")
@@ -652,10 +687,12 @@ def main():
             reducer.reduce()
         opt.step()
         loss_acc.add_(loss.detach())
-        return loss.detach()
+        return loss.detach(), out.detach()
+
+    last = [None]                                   # (loss, logits) of the latest step: what --dump-outputs writes
 
     def step():
-        step_fn(x, labels)
+        last[0] = step_fn(x, labels)
 
     gstep = None
     if use_graph:
@@ -673,7 +710,8 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
-    timer = None if args.no_launch_timing else K.LaunchTimer()
+    # the per-launch events only serve the roofline, a --full figure: a plain run times the bare steps
+    timer = K.LaunchTimer() if args.full and not args.no_launch_timing else None
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -693,7 +731,7 @@ def main():
         xs, ls = gstep.static_inputs
         for _ in range(args.steps):
             h0 = time.perf_counter()
-            gstep(xs, ls)
+            last[0] = gstep(xs, ls)
             host_by_kind["graph"][0] += time.perf_counter() - h0
             host_by_kind["graph"][1] += 1
     elif timer is not None:
@@ -720,6 +758,9 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # before any step outside the timed region (roofline, RCCL side runs) moves the model on
+        dump_outputs(args.dump_outputs, last[0][0], last[0][1], params)
 
     events_in_region = gstep is None
     if gstep is not None and timer is not None:
@@ -733,7 +774,7 @@ def main():
     # N > 1: one more step (outside the timed region, on every rank -- it is a collective) with each bucket's all-reduce and the
     # compute stream's final wait bracketed by events, so that the first multi-GPU line explains itself
     rccl_info = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         reducer.time_collectives = True
         step()
         times = reducer.collective_times()
@@ -746,7 +787,7 @@ def main():
                      "log": _parse_rccl_log(rccl_log) if rccl_log else None}
 
     if rank == 0:
-        final_loss = float(loss_acc.item()) / max(1, args.steps + args.warmup + (1 if reducer is not None else 0) + ((1 + n_event_steps) if (gstep is not None and timer is not None) else 0))
+        final_loss = float(loss_acc.item()) / max(1, args.steps + args.warmup + (1 if rccl_info is not None else 0) + ((1 + n_event_steps) if (gstep is not None and timer is not None) else 0))
         roof = roofline_from(timer.results(), timed_steps, dtype) if timer is not None else None
         if roof is not None:
             roof["event_timed_steps"] = timed_steps
@@ -754,22 +795,22 @@ def main():
         if timer is not None and args.per_layer:
             print(per_layer_table(timer.results(), timed_steps, dtype), file=sys.stderr)
         rccl_side = None
-        if world == 1 and not args.no_rccl_side:
+        if world == 1 and args.full and not args.no_rccl_side:
             try:
                 rccl_side = rccl_world1_side(dev, model, params, opt, x, labels, use_graph=use_graph)
             except Exception as e:  # noqa: BLE001 -- a side number must never take the headline line down
                 rccl_side = {"error": f"{type(e).__name__}: {e}"[:300]}
         secondary = None
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             try:
                 secondary = secondary_configs()
             except Exception as e:  # noqa: BLE001
                 secondary = {"error": f"{type(e).__name__}: {e}"[:300]}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline()
         fp32_side = None
-        if world == 1 and args.dtype == "bf16" and not args.no_fp32_side:
+        if world == 1 and args.full and args.dtype == "bf16" and not args.no_fp32_side:
             fp32_side = fp32_parity_mode_rate(dev, x, labels)
         out = {
             "metric": "tiles/sec fwd+bwd (ResNet-50 MIL, 299x299)",
@@ -781,9 +822,11 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "host_enqueue_ms_per_step": round(host_enqueue / args.steps * 1e3, 3),
             "host_enqueue_detail": {k: {"steps": v[1], "ms_per_step": round(v[0] / v[1] * 1e3, 3)} for k, v in host_by_kind.items() if v[1]},
-            "step_mode": ("one HIP graph per step (graphed.GraphedStep replay; the batch sits in the captured input buffers) for all K timed steps; `roofline` from "
-                          f"{n_event_steps} HIP-event-bracketed eager steps of the same trajectory right after the timed region"
-                          if gstep is not None else f"eager (every launch enqueued from Python; every {args.event_every}th timed step event-bracketed)"),
+            "step_mode": (("one HIP graph per step (graphed.GraphedStep replay; the batch sits in the captured input buffers) for all K timed steps"
+                           + (f"; `roofline` from {n_event_steps} HIP-event-bracketed eager steps of the same trajectory right after the timed region"
+                              if timer is not None else ""))
+                          if gstep is not None else
+                          "eager (every launch enqueued from Python" + (f"; every {args.event_every}th timed step event-bracketed)" if timer is not None else ")")),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -28,8 +28,11 @@ def _import_lines(path):
     return keep
 
 
-@pytest.mark.parametrize("driver", [d for d in DRIVERS if os.path.exists(os.path.join(REF, d))])
+# the cases are the fixed driver list, whatever this machine holds: their ids never depend on where the suite runs
+@pytest.mark.parametrize("driver", DRIVERS)
 def test_driver_imports_resolve_through_the_dropin(driver, tmp_path):
+    if not os.path.exists(os.path.join(REF, driver)):
+        pytest.skip(f"{driver} is not in the reference tree")
     lines = _import_lines(os.path.join(REF, driver))
     assert any("model" in l for l in lines)
     prog = textwrap.dedent('''
