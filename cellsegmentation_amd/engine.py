@@ -18,9 +18,10 @@ by [tensor > 0]; the kernel producing the LAST contribution to a slot applies th
 bilinear-backward epilogues), so ReLU backward never costs a separate pass, and residual
 gradients are passed as the ``add`` operand of the dgrad epilogue instead of a separate add.
 
+Each unit has a forward step ``fwd`` and a backward step ``bwd``; ``_Forward`` / ``_Backward`` hold the state of a pass.
 The whole plan is ONE torch.autograd.Function: torch only sees (inputs, parameters) -> outputs.
 """
-import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import torch
@@ -29,6 +30,9 @@ from . import _capture
 from . import kernels as K
 
 ACT_NONE, ACT_RELU, ACT_SILU = K.CS_ACT_NONE, K.CS_ACT_RELU, K.CS_ACT_SILU
+
+PACKED = True              # packed-operand conv kernels (False: first-generation igemm everywhere; tests flip it for a reference path)
+PACKED_TRAIN_BN = True     # ... also for heavy 3x3 convolutions under batch-statistics BN
 
 
 class ConvUnit:
@@ -56,6 +60,75 @@ class ConvUnit:
     def inputs(self):
         return [self.src] + ([self.res] if self.res is not None else [])
 
+    def fwd(self, f, ui):
+        x = f.t[self.src]
+        N, H, W, Cp = x.shape
+        conv = self.conv
+        Kp = K.pad_channels(conv.out_channels)
+        R, S = conv.kernel_size
+        geom = K.make_geom(N, H, W, Cp, Kp, R, S, conv.stride[0], conv.padding[0])
+        res = f.t[self.res] if self.res is not None else None
+        batch_stats = _bn_uses_batch_stats(self.bn, f.bn_train)
+        st = f.staged(ui, self, geom, batch_stats)
+        # the stem runs on a pixel-paired image (kernels.stem_*): 28 instead of 49 K chunks
+        stem = _is_paired_stem(self) and K.is_stem_geom(geom)
+        xp = wp = None
+        if ui == 0 and f.nchw_for_stem is not None:
+            if not stem:
+                raise RuntimeError("engine: the stem was expected to take the NCHW image (placeholder input would be read)")
+            xp = K.stem_pair_from_nchw(f.nchw_for_stem, f.dtype)
+        elif stem:
+            xp = K.stem_pair_input(x)
+        if stem:
+            wp = K.stem_pair_weights(st.w_khwc)
+        if batch_stats:
+            stats = f.take_stats(Kp)
+            if stem:
+                z = K.stem_fwd(geom, xp, wp, None, st.shift, ACT_NONE, stats=stats)
+            elif st.fwd_packed:
+                # halo kernel + one statistics pass over the stored z (the statistics of exactly the values bn_apply normalises)
+                z = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, None, ACT_NONE)
+                K.bn_stats(z, stats)
+            else:
+                z = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, None, ACT_NONE, stats=stats, grouped=self.grouped)
+            y, mean, rstd = f.bn_train_fwd(self.bn, z, stats, res, self.act)
+            f.aux[ui] = SimpleNamespace(geom=geom, st=st, train=True, z=z if f.save else None, mean=mean, rstd=rstd, xp=xp)
+        else:
+            # one bit per output next to a ReLU output of a pass that will run backward: the data gradient that later masks with
+            # this tensor reads 1 byte per 16 (the bf16 masks are ~1/8 of a training step's HBM traffic)
+            want_bits = f.save and self.act == ACT_RELU
+            if stem and PACKED and K.stem_fwd_packed_supported(geom, f.dtype):
+                y = K.stem_fwd_packed(geom, xp, K.stem_pack_weights(wp), st.shift, self.act)       # ring kernel, gathered rows
+            elif stem:
+                y = K.stem_fwd(geom, xp, wp, None, st.shift, self.act)
+            elif st.fwd_packed and want_bits:
+                y, f.bits[self.dst] = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, res, self.act, want_bits=True)
+            elif st.fwd_packed:
+                y = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, res, self.act)
+            elif want_bits and Kp % 32 == 0:
+                y, f.bits[self.dst] = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, res, self.act, grouped=self.grouped, want_bits=True)
+            else:
+                y = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, res, self.act, grouped=self.grouped)
+            f.aux[ui] = SimpleNamespace(geom=geom, st=st, train=False, xp=xp)
+        f.t[self.dst] = y
+
+    def bwd(self, b, ui, g):
+        a = b.aux[ui]
+        x = b.t[self.src]
+        if self.res is not None and b.requires.get(self.res, False):
+            b.contribute(self.res, g, masked=False)
+        if self.act == ACT_SILU and not a.train:
+            raise NotImplementedError(f"{self.name}: backward through a folded (eval-mode) BN + SiLU is not supported; "
+                                      "EfficientNet trains with batch statistics (efficientnet.py:308-312)")
+        dz = b.bn_bwd(ui, self, g, a, self.conv.out_channels) if a.train else g
+        if _defers(self, a, b.need, ui):
+            b.defer_wgrad(ui, self, a, x, g, dz)
+        elif b.need(ui, "weight") or b.need(ui, "bias") or (not a.train and (b.need(ui, "gamma") or b.need(ui, "beta"))):
+            b.conv_wgrad(ui, self, a, x, g, dz)
+        b.gsum_cache.pop(self.dst, None)
+        if b.requires.get(self.src, False):
+            b.grads[self.src] = b.conv_dgrad(self, a, x, dz)
+
 
 class DwConvUnit:
     """Depthwise k x k Conv2d(groups=C, bias=False) + BatchNorm2d + activation (MBConv, efficientnet.py:101-103)."""
@@ -72,6 +145,36 @@ class DwConvUnit:
     def inputs(self):
         return [self.src]
 
+    def fwd(self, f, ui):
+        x = f.t[self.src]
+        N, H, W, C = x.shape
+        conv, bn = self.conv, self.bn
+        R = conv.kernel_size[0]
+        geom = K.make_geom(N, H, W, C, C, R, R, conv.stride[0], conv.padding[0])
+        w_hwc = f.dw_hwc[ui] if ui in f.dw_hwc else conv.weight.detach()[:, 0].permute(1, 2, 0).contiguous()
+        if _bn_uses_batch_stats(bn, f.bn_train):
+            z, zstats = K.dwconv_fwd_stats(geom, x, w_hwc)
+            f.t[self.dst], mean, rstd = f.bn_train_fwd(bn, z, zstats, None, self.act)
+            f.aux[ui] = SimpleNamespace(geom=geom, train=True, z=z if f.save else None, mean=mean, rstd=rstd, w_hwc=w_hwc)
+        else:
+            scale, shift, _ = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
+            f.t[self.dst] = K.dwconv_fwd(geom, x, w_hwc, scale, shift, self.act)
+            f.aux[ui] = SimpleNamespace(geom=geom, train=False)
+
+    def bwd(self, b, ui, g):
+        a = b.aux[ui]
+        if not a.train:
+            raise NotImplementedError(f"{self.name}: backward through an eval-mode depthwise block is not supported")
+        x = b.t[self.src]
+        dz = b.bn_bwd(ui, self, g, a)
+        if b.need(ui, "weight"):
+            b.emit(ui, "weight", K.dwconv_wgrad(a.geom, x, dz, param_layout=True))
+        if b.requires.get(self.src, False):
+            b.left[self.src] -= 1
+            dx = K.dwconv_dgrad(a.geom, dz, a.w_hwc)
+            pending = b.grads.pop(self.src, None)
+            b.grads[self.src] = dx if pending is None else K.rowscale_add(dx, None, pending)
+
 
 class SEUnit:
     """torchvision SqueezeExcitation: x * sigmoid(fc2(silu(fc1(avgpool(x)))))  (efficientnet.py:105-107)."""
@@ -85,6 +188,36 @@ class SEUnit:
 
     def inputs(self):
         return [self.src]
+
+    def fwd(self, f, ui):
+        x = f.t[self.src]
+        C = x.shape[-1]
+        w1 = self.fc1.weight.detach().view(self.fc1.out_channels, C)
+        w2 = self.fc2.weight.detach().view(C, self.fc2.in_channels)
+        avg, _ = K.gap_fwd(x, with_max=False)
+        h1, u1 = K.linear_fwd(avg, w1, self.fc1.bias.detach(), K.CS_ACT_SILU, want_preact=True)
+        sc = K.linear_fwd(h1, w2, self.fc2.bias.detach(), K.CS_ACT_SIGMOID)
+        f.t[self.dst] = K.se_scale(x, sc)
+        f.aux[ui] = SimpleNamespace(avg=avg, h1=h1, u1=u1, s=sc, w1=w1, w2=w2)
+
+    def bwd(self, b, ui, g):
+        a = b.aux[ui]
+        ds = K.se_scale_bwd_ds(g, b.t[self.src])
+        want2 = b.need(ui, "w2") or b.need(ui, "b2")
+        want1 = b.need(ui, "w1") or b.need(ui, "b1")
+        dh1, dw2, db2 = K.linear_bwd(a.h1, a.w2, ds, a.s, K.CS_ACT_SIGMOID, True, want2, want2)
+        davg, dw1, db1 = K.linear_bwd(a.avg, a.w1, dh1, a.u1, K.CS_ACT_SILU, True, want1, want1)
+        if b.need(ui, "w2"):
+            b.emit(ui, "w2", dw2.view_as(self.fc2.weight))
+        if b.need(ui, "b2"):
+            b.emit(ui, "b2", db2)
+        if b.need(ui, "w1"):
+            b.emit(ui, "w1", dw1.view_as(self.fc1.weight))
+        if b.need(ui, "b1"):
+            b.emit(ui, "b1", db1)
+        if b.requires.get(self.src, False):
+            b.sole_consumer(self.src, "SE")
+            b.grads[self.src] = K.se_scale_bwd_dx(g, a.s, davg)
 
 
 class RowScaleAddUnit:
@@ -100,6 +233,21 @@ class RowScaleAddUnit:
     def inputs(self):
         return [self.a, self.b]
 
+    def fwd(self, f, ui):
+        a = f.t[self.a]
+        keep = 1.0 - self.p
+        noise = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device).bernoulli_(keep)
+        if keep > 0:
+            noise.div_(keep)
+        f.t[self.dst] = K.rowscale_add(a, noise, f.t[self.b])
+        f.aux[ui] = SimpleNamespace(noise=noise)
+
+    def bwd(self, b, ui, g):
+        if b.requires.get(self.b, False):
+            b.contribute(self.b, g, masked=True)
+        if b.requires.get(self.a, False):
+            b.contribute(self.a, K.rowscale_add(g, b.aux[ui].noise, None), masked=True)
+
 
 class PoolUnit:
     kind = "pool"
@@ -112,6 +260,18 @@ class PoolUnit:
 
     def inputs(self):
         return [self.src]
+
+    def fwd(self, f, ui):
+        x = f.t[self.src]
+        f.t[self.dst], am = K.maxpool_fwd(x, want_argmax=f.save)
+        f.aux[ui] = SimpleNamespace(argmax=am, in_hw=tuple(x.shape[1:3]))
+
+    def bwd(self, b, ui, g):
+        if b.requires.get(self.src, False):
+            b.sole_consumer(self.src, "pool")
+            a = b.aux[ui]
+            # dy is masked by [pool_out>0]; the argmax element equals pool_out, so dx is masked too
+            b.grads[self.src] = K.maxpool_bwd(g, a.argmax, None, a.in_hw)
 
 
 class UpsampleUnit:
@@ -127,6 +287,18 @@ class UpsampleUnit:
     def inputs(self):
         return [self.src]
 
+    def fwd(self, f, ui):
+        x = f.t[self.src]
+        size = tuple(f.t[self.size_like].shape[1:3]) if self.size_like is not None else tuple(self.size_fn(f.in_hw))
+        f.t[self.dst] = K.bilinear_fwd(x, size)
+        f.aux[ui] = SimpleNamespace(in_hw=tuple(x.shape[1:3]))
+
+    def bwd(self, b, ui, g):
+        if b.requires.get(self.src, False):
+            b.sole_consumer(self.src, "upsample")
+            mask = b.t[self.src] if self.src in b.plan.relu_slots else None
+            b.grads[self.src] = K.bilinear_bwd(g, b.aux[ui].in_hw, mask=mask)
+
 
 class ConcatUnit:
     kind = "cat"
@@ -139,6 +311,20 @@ class ConcatUnit:
 
     def inputs(self):
         return [self.a, self.b]
+
+    def fwd(self, f, ui):
+        a, b = f.t[self.a], f.t[self.b]
+        f.t[self.dst] = K.concat(a, b)
+        f.aux[ui] = SimpleNamespace(ca=a.shape[-1])
+
+    def bwd(self, b, ui, g):
+        na, nb = b.requires.get(self.a, False), b.requires.get(self.b, False)
+        if na or nb:
+            ga, gb = K.split(g, b.aux[ui].ca, want_a=na, want_b=nb)
+            if na:
+                b.contribute(self.a, ga, masked=True)
+            if nb:
+                b.contribute(self.b, gb, masked=True)
 
 
 class Plan:
@@ -175,6 +361,25 @@ def _pad_vec(v, n):
 
 def _bn_uses_batch_stats(bn, bn_train):
     return bn is not None and bn_train and bn.training
+
+
+def _is_paired_stem(u):
+    """Conv2d(<= 3 -> K, 7x7, stride 2, padding 3) without groups or residual: the stem the pixel-paired kernels (kernels.stem_*) run."""
+    if u.kind != "conv":
+        return False
+    c = u.conv
+    return (not u.grouped and u.res is None and c.in_channels <= 3 and c.kernel_size == (7, 7)
+            and c.stride == (2, 2) and c.padding == (3, 3))
+
+
+def _stem_takes_nchw(plan, dtype):
+    """True when the plan's input feeds exactly one unit and that unit is the pixel-paired bf16 stem: the fp32 NCHW image can go
+    straight to the paired operand (cs_stem_pair_from_nchw) and the NHWC8 tensor is never made."""
+    if not (dtype == torch.bfloat16 and len(plan.inputs) == 1 and plan.units):
+        return False
+    u = plan.units[0]
+    return (_is_paired_stem(u) and u.conv.in_channels == 3 and u.src == plan.inputs[0]
+            and plan.consumers.get(u.src, 0) == 1)
 
 
 def _packed_flags(plan, u, geom, dtype, need_bwd, batch_stats, bits, bn_train=False):
@@ -234,292 +439,213 @@ def invalidate_staged():
     _STAGE_EPOCH[0] += 1
 
 
-def _stage_weights(u, dtype, Cp, Kp, need_bwd, folded, training, geom=None, pkf=False, pkb=False):
-    """BN folding + weight staging.  Cached only for frozen parameters and for no-grad passes: a forward that will
-    be followed by an optimizer step (`training` and the parameter requires grad) always stages afresh and leaves the
-    cache invalid, because tensor version counters cannot be trusted to see the update -- torch's fused optimizers
+# How a convolution is staged: channel extents, data-gradient operand or not, packed orders, batch-statistics BN (nothing folded in).
+# The one-launch staging (kernels.StagePack) serves a layer only under the spec it recorded.
+_StageSpec = namedtuple("_StageSpec", "Cp Kp need_bwd pkf pkb batch_stats")
+
+
+class _Staged:
+    """Staged operands of one convolution: w_khwc (forward), w_chwk (data gradient, or None), [Kp] scale / rstd (None unless an
+    eval-mode BN is folded in) and shift; *_packed: that operand is in the order of the packed-operand kernels (conv_v2.hip)."""
+    __slots__ = ("w_khwc", "w_chwk", "scale", "shift", "rstd", "fwd_packed", "bwd_packed")
+
+    def __init__(self, w_khwc, w_chwk, scale, shift, rstd, pkf, pkb):
+        self.w_khwc, self.w_chwk, self.scale, self.shift, self.rstd = w_khwc, w_chwk, scale, shift, rstd
+        self.fwd_packed, self.bwd_packed = bool(pkf), bool(pkb and w_chwk is not None)
+
+
+def _stage_weights(u, dtype, spec, geom, fresh):
+    """BN folding + weight staging, layer by layer.  Cached only for frozen parameters and for no-grad passes: `fresh` (a forward
+    that will be followed by an optimizer step, of a layer whose staging depends on a trainable parameter) always stages afresh
+    and leaves the cache invalid, because tensor version counters cannot be trusted to see the update -- torch's fused optimizers
     (`Adam(fused=True)`) write the parameters without bumping `_version`."""
     conv, bn = u.conv, u.bn
     # (a batch-statistics pass folds nothing of the BatchNorm into the operands: they depend on the convolution's own tensors only, so a
     # frozen encoder under train-mode BN -- the segmentation stage -- stages once, not once per step)
-    key_t = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if (bn is not None and folded) else [])
-    key = (_STAGE_EPOCH[0], dtype, Cp, Kp, need_bwd, folded, pkf, pkb) + tuple((t._version, t.data_ptr()) if t is not None else None for t in key_t)
-    if training and any(t is not None and t.requires_grad for t in key_t):
+    fold = bn is not None and not spec.batch_stats
+    key_t = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if fold else [])
+    key = (_STAGE_EPOCH[0], dtype, spec) + tuple((t._version, t.data_ptr()) if t is not None else None for t in key_t)
+    if fresh:
         key = None
     elif u._cache is not None and u._cache[0] == key:
         return u._cache[1]
     w = conv.weight.detach()
     bias = conv.bias.detach() if conv.bias is not None else None
-    scale = shift = rstd = None
-    if folded and bn is not None and not u.grouped:
+    scale = rstd = None
+    if fold and not u.grouped:
         w_khwc, w_chwk, scale, shift, rstd = K.stage_conv_bn(w, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                             bn.eps, bias, dtype, Cp, Kp, want_bwd=need_bwd)
-        staged = _packed(SimpleNamespace(w_khwc=w_khwc, w_chwk=w_chwk, scale=scale, shift=shift, rstd=rstd), geom, pkf, pkb)
-        u._cache = (key, staged)
-        return staged
-    if folded and bn is not None:
-        scale, shift, rstd = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, bias)
+                                                             bn.eps, bias, dtype, spec.Cp, spec.Kp, want_bwd=spec.need_bwd)
     else:
         shift = bias
-    if u.grouped:
-        w_khwc, w_chwk = K.weight_prep_grouped(w, scale, dtype, want_fwd=True, want_bwd=need_bwd)
-    else:
-        w_khwc, w_chwk = K.weight_prep(w, scale, dtype, Cp, Kp, want_fwd=True, want_bwd=need_bwd)
-    staged = _packed(SimpleNamespace(w_khwc=w_khwc, w_chwk=w_chwk, scale=scale, shift=_pad_vec(shift, Kp), rstd=rstd), geom, pkf, pkb)
-    u._cache = (key, staged)
-    return staged
-
-
-def _packed(st, geom, pkf, pkb):
-    """Layer-by-layer staging path: re-order the plain operands for the packed-operand kernels (the one-launch StagePack
-    writes that order directly)."""
-    st.fwd_packed, st.bwd_packed = bool(pkf), bool(pkb and st.w_chwk is not None)
+        if fold:
+            scale, shift, rstd = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, bias)
+        if u.grouped:
+            w_khwc, w_chwk = K.weight_prep_grouped(w, scale, dtype, want_fwd=True, want_bwd=spec.need_bwd)
+        else:
+            w_khwc, w_chwk = K.weight_prep(w, scale, dtype, spec.Cp, spec.Kp, want_fwd=True, want_bwd=spec.need_bwd)
+        shift = _pad_vec(shift, spec.Kp)
+    st = _Staged(w_khwc, w_chwk, scale, shift, rstd, spec.pkf, spec.pkb)
+    # re-order the plain operands for the packed-operand kernels (the one-launch StagePack writes that order directly)
     if st.fwd_packed:
         st.w_khwc = K.pack_conv_weights(geom, st.w_khwc, dgrad=False)
     if st.bwd_packed:
         st.w_chwk = K.pack_conv_weights(geom, st.w_chwk, dgrad=True)
+    u._cache = (key, st)
     return st
 
 
-def _stem_takes_nchw(plan, dtype):
-    """True when the plan's input feeds exactly one unit and that unit is the pixel-paired bf16 stem: the fp32 NCHW image can go
-    straight to the paired operand (cs_stem_pair_from_nchw) and the NHWC8 tensor is never made."""
-    if not (STEM_PAIRED and dtype == torch.bfloat16 and len(plan.inputs) == 1 and plan.units):
-        return False
-    u = plan.units[0]
-    if u.kind != "conv" or u.src != plan.inputs[0] or plan.consumers.get(u.src, 0) != 1 or u.grouped or u.res is not None:
-        return False
-    c = u.conv
-    return c.in_channels == 3 and c.kernel_size == (7, 7) and c.stride == (2, 2) and c.padding == (3, 3)
+class _Arena:
+    """Zeroed tensors bump-allocated from one zero-filled buffer (one fill per pass); take() is None when the request does not fit."""
+
+    def __init__(self, n, dtype, device, align):
+        self.buf = torch.zeros((n,), dtype=dtype, device=device) if n else None
+        self.pos, self.align = 0, align
+
+    def take(self, n):
+        step = (n + self.align - 1) // self.align * self.align
+        if self.buf is None or self.pos + step > self.buf.numel():
+            return None
+        v = self.buf[self.pos:self.pos + n]
+        self.pos += step
+        return v
+
+
+class _Forward:
+    """State of one forward pass: slot tensors `t`, per-unit `aux` for backward, ReLU bit planes, weight staging, BN bookkeeping."""
+
+    def __init__(self, plan, feeds, dtype, bn_train, save, requires, image_hw, input_nchw):
+        self.plan, self.dtype, self.bn_train, self.save, self.requires = plan, dtype, bn_train, save, requires
+        self.t = t = dict(feeds)
+        self.nchw_for_stem = None
+        if input_nchw is not None:
+            if _stem_takes_nchw(plan, dtype):
+                self.nchw_for_stem = input_nchw
+            else:
+                t[plan.inputs[0]] = K.to_nhwc(input_nchw, dtype, K.pad_channels(3))
+        self.aux = [None] * len(plan.units)
+        self.remaining = dict(plan.consumers)
+        self.in_hw = image_hw if image_hw is not None else tuple(t[plan.inputs[0]].shape[1:3])
+        self.dev = dev = t[plan.inputs[0]].device
+        self.capturing = _capture.capturing()
+
+        # Training passes re-stage every folded Conv+BN after each optimizer update: one launch for the whole plan (the first such
+        # pass stages layer by layer and records the layout; see kernels.StagePack)
+        # (one pack per (dtype, input shape): which layers take packed operands depends on the geometry, and a ragged last batch must
+        # not evict the pack of the full batches -- a captured step keeps replaying into it)
+        self.packs = plan.__dict__.setdefault("_stage_packs", {})
+        self.pack_key = (dtype, tuple(t[plan.inputs[0]].shape))
+        pack = self.packs.get(self.pack_key) if save else None
+        self.prestaged, self.record = {}, None          # record: [(unit index, unit, _StageSpec)] for the pack built at the end
+        if save:
+            if pack is not None and pack.valid():
+                pack.launch()
+                self.prestaged = pack.by_unit
+                if self.capturing:
+                    _capture.keep(pack)
+            else:
+                self.packs.pop(self.pack_key, None)
+                while len(self.packs) >= 4:
+                    self.packs.pop(next(iter(self.packs)))
+                self.record = []
+
+        # train-mode BN bookkeeping for the whole plan in two launches instead of two per layer: one zero-filled fp64 arena for the
+        # per-channel statistics, one foreach-add for the num_batches_tracked counters (this path is host-bound: ~1000 launches/step)
+        self.bumped = []
+        if bn_train and save:
+            K.begin_pass(dev)
+        self.bits = {}       # slot -> uint8 "output > 0" bit tensor (folded Conv+BN+ReLU outputs of a pass that will run backward)
+        n_stats = sum(K.accum_words(K.pad_channels(u.conv.out_channels)) for u in plan.units
+                      if u.kind == "conv" and _bn_uses_batch_stats(u.bn, bn_train)) if bn_train else 0
+        self.stats = _Arena(n_stats, torch.float64, dev, 1)
+        self.dw_hwc = self._stage_depthwise()
+
+    def _stage_depthwise(self):
+        """{unit index: [R, S, C] filter} of every depthwise layer, restaged by one launch per pass (a permute + strided copy per
+        layer: 26 launches of 4.4 us on EfficientNet-B3)."""
+        plan = self.plan
+        units = [ui for ui, u in enumerate(plan.units) if u.kind == "dw"]
+        if not units:
+            return {}
+        ws = [plan.units[ui].conv.weight.detach() for ui in units]
+        if not all(w.is_contiguous() and w.dtype == torch.float32 and w.dim() == 4 and w.shape[1] == 1 for w in ws):
+            return {}
+        dpack = plan.__dict__.get("_dw_stage_pack")
+        if dpack is None or dpack.key != tuple(w.data_ptr() for w in ws):
+            dpack = plan.__dict__["_dw_stage_pack"] = K.DwStagePack(ws)
+        dpack.run()
+        if self.capturing:
+            _capture.keep(dpack)
+        return dict(zip(units, dpack.hwc))
+
+    def take_stats(self, C):
+        v = self.stats.take(K.accum_words(C))
+        return v if v is not None else K.new_stats(C, self.dev)
+
+    def staged(self, ui, u, geom, batch_stats):
+        """The staged operands of conv unit u: from this pass's one-launch pack when its spec matches, else layer by layer."""
+        need_bwd = self.save and self.requires.get(u.src, False)
+        pkf, pkb = _packed_flags(self.plan, u, geom, self.dtype, need_bwd, batch_stats, self.bits, self.bn_train)
+        spec = _StageSpec(geom.C, geom.K, need_bwd, pkf, pkb, batch_stats)
+        ps = (u.conv.weight, u.conv.bias) + ((u.bn.weight, u.bn.bias) if (u.bn is not None and not batch_stats) else ())
+        trainable = any(p is not None and p.requires_grad for p in ps)       # does the staging depend on a trainable parameter?
+        # A pass that will be followed by an optimizer step, or that updates BN running statistics in place, must not leave
+        # a version-keyed cache behind: fused optimizers and our own kernels write those tensors without bumping `_version`
+        # (a later no-grad pass would be served the old weights; the one-launch pack path never touches `_cache`)
+        if self.save and trainable:
+            u._cache = None
+        pre = self.prestaged.get(ui)
+        if pre is not None and pre[0] == spec:
+            return pre[1]
+        if pre is not None:
+            self.packs.pop(self.pack_key, None)       # the layout changed (other requires_grad pattern): rebuild next time
+        st = _stage_weights(u, self.dtype, spec, geom, fresh=self.save and trainable)
+        if self.capturing:
+            _capture.keep(st)               # (a cached staged set may be replaced by a later eager pass: the graph keeps this one)
+        # (a batch-statistics layer joins the one-launch staging with bn = None: its operands depend on the convolution only)
+        if self.record is not None and not u.grouped and (batch_stats or u.bn is not None) and trainable:
+            self.record.append((ui, u, spec))
+        return st
+
+    def bn_train_fwd(self, bn, z, stats, res, act):
+        """Train-mode BatchNorm of z (+ residual, activation): finalize + apply in one launch (mean / rstd derived inside)."""
+        momentum = bn.momentum if bn.momentum is not None else 0.1
+        track = bn.track_running_stats
+        y, mean, rstd = K.bn_apply_stats(z, stats, bn.eps, momentum, bn.running_mean if track else None,
+                                         bn.running_var if track else None, bn.weight.detach(), bn.bias.detach(), res, act)
+        if track and bn.num_batches_tracked is not None:
+            self.bumped.append(bn.num_batches_tracked)
+        return y, mean, rstd
+
+    def release(self, s):
+        if self.save or s in self.plan.outputs:
+            return
+        self.remaining[s] -= 1
+        if self.remaining[s] == 0:
+            self.t.pop(s, None)
+
+    def finish(self):
+        if self.bumped:
+            torch._foreach_add_(self.bumped, 1)
+        if self.record:
+            pk = K.StagePack([(u.conv, None if s.batch_stats else u.bn, s.Cp, s.Kp, s.need_bwd, s.pkf, s.pkb)
+                              for _, u, s in self.record], self.dtype)
+            # (batch statistics: the consumers expect no folded scale and no rstd)
+            pk.by_unit = {ui: (s, _Staged(w, wb, None if s.batch_stats else sc, sh, None if s.batch_stats else r, s.pkf, s.pkb))
+                          for (ui, _, s), (w, wb, sc, sh, r) in zip(self.record, pk.staged)}
+            self.packs[self.pack_key] = pk
 
 
 def forward(plan, feeds, dtype, bn_train, save, requires, image_hw=None, input_nchw=None):
     """feeds: {slot: NHWC tensor}.  Returns state with .t (slot tensors) and .aux (per unit).
     input_nchw: the network input as the contiguous fp32 [N,3,H,W] image instead (feeds then holds an UNINITIALISED placeholder of
     the NHWC8 shape for that slot): converted here -- directly into the paired stem operand where the stem takes it."""
-    t = dict(feeds)
-    nchw_for_stem = None
-    if input_nchw is not None:
-        if _stem_takes_nchw(plan, dtype):
-            nchw_for_stem = input_nchw
-        else:
-            t[plan.inputs[0]] = K.to_nhwc(input_nchw, dtype, K.pad_channels(3))
-    aux = [None] * len(plan.units)
-    remaining = dict(plan.consumers)
-    in_hw = image_hw
-    if in_hw is None:
-        in_hw = tuple(t[plan.inputs[0]].shape[1:3])
-
-    def release(s):
-        if save or s in plan.outputs:
-            return
-        remaining[s] -= 1
-        if remaining[s] == 0:
-            t.pop(s, None)
-
-    # Training passes re-stage every folded Conv+BN after each optimizer update: one launch for the whole plan (the first such
-    # pass stages layer by layer and records the layout; see kernels.StagePack)
-    # (one pack per (dtype, input shape): which layers take packed operands depends on the geometry, and a ragged last batch must not
-    # evict the pack of the full batches -- a captured step keeps replaying into it)
-    packs = plan.__dict__.setdefault("_stage_packs", {})
-    pack_key = (dtype, tuple(t[plan.inputs[0]].shape))
-    pack = packs.get(pack_key) if save else None
-    prestaged, record = {}, None
-    capturing = _capture.capturing()
-    if save:
-        if pack is not None and pack.valid():
-            pack.launch()
-            prestaged = pack.by_unit
-            if capturing:
-                _capture.keep(pack)
-        else:
-            packs.pop(pack_key, None)
-            while len(packs) >= 4:
-                packs.pop(next(iter(packs)))
-            record = []
-
-    # train-mode BN bookkeeping for the whole plan in two launches instead of two per layer: one zero-filled fp64 arena for the
-    # per-channel statistics, one foreach-add for the num_batches_tracked counters (this path is host-bound: ~1000 launches/step)
-    stats_arena, stats_pos, bumped = None, [0], []
-    if bn_train and save:
-        K.begin_pass(t[plan.inputs[0]].device)
-    bits = {}            # slot -> uint8 "output > 0" bit tensor (folded Conv+BN+ReLU outputs of a pass that will run backward)
-    if bn_train:
-        need = sum(K.accum_words(K.pad_channels(u_.conv.out_channels)) for u_ in plan.units
-                   if u_.kind == "conv" and _bn_uses_batch_stats(u_.bn, bn_train))
-        if need:
-            stats_arena = torch.zeros((need,), dtype=torch.float64, device=t[plan.inputs[0]].device)
-
-    def take_stats(C):
-        n = K.accum_words(C)
-        if stats_arena is None or stats_pos[0] + n > stats_arena.numel():
-            return K.new_stats(C, t[plan.inputs[0]].device)
-        v = stats_arena[stats_pos[0]:stats_pos[0] + n]
-        stats_pos[0] += n
-        return v
-
-    # depthwise filters: the kernels read [R, S, C]; all layers of the plan restaged from the parameters by one launch per pass
-    # (a permute + strided copy per layer: 26 launches of 4.4 us on EfficientNet-B3)
-    dw_hwc = {}
-    dw_units = [ui_ for ui_, u_ in enumerate(plan.units) if u_.kind == "dw"]
-    if dw_units:
-        ws_ = [plan.units[ui_].conv.weight.detach() for ui_ in dw_units]
-        if all(w_.is_contiguous() and w_.dtype == torch.float32 and w_.dim() == 4 and w_.shape[1] == 1 for w_ in ws_):
-            dpack = plan.__dict__.get("_dw_stage_pack")
-            if dpack is None or dpack.key != tuple(w_.data_ptr() for w_ in ws_):
-                dpack = plan.__dict__["_dw_stage_pack"] = K.DwStagePack(ws_)
-            dpack.run()
-            if capturing:
-                _capture.keep(dpack)
-            dw_hwc = dict(zip(dw_units, dpack.hwc))
-
+    f = _Forward(plan, feeds, dtype, bn_train, save, requires, image_hw, input_nchw)
     for ui, u in enumerate(plan.units):
-        if u.kind == "conv":
-            x = t[u.src]
-            N, H, W, Cp = x.shape
-            conv = u.conv
-            Kc = conv.out_channels
-            Kp = K.pad_channels(Kc)
-            R, S = conv.kernel_size
-            geom = K.make_geom(N, H, W, Cp, Kp, R, S, conv.stride[0], conv.padding[0])
-            res = t[u.res] if u.res is not None else None
-            need_bwd = save and requires.get(u.src, False)
-            batch_stats = _bn_uses_batch_stats(u.bn, bn_train)
-            pre = prestaged.get(ui)
-            pkf, pkb = _packed_flags(plan, u, geom, dtype, need_bwd, batch_stats, bits, bn_train)
-            # A pass that will be followed by an optimizer step, or that updates BN running statistics in place, must not leave
-            # a version-keyed cache behind: fused optimizers and our own kernels write those tensors without bumping `_version`
-            # (a later no-grad pass would be served the old weights; the one-launch pack path below never touches `_cache`)
-            if save and any(p_ is not None and p_.requires_grad
-                            for p_ in (conv.weight, conv.bias) + ((u.bn.weight, u.bn.bias) if (u.bn is not None and not batch_stats) else ())):
-                u._cache = None
-            if pre is not None and pre[0] == (Cp, Kp, need_bwd, pkf, pkb, batch_stats):
-                st = pre[1]
-            else:
-                if pre is not None:
-                    packs.pop(pack_key, None)       # the layout changed (other requires_grad pattern): rebuild next time
-                st = _stage_weights(u, dtype, Cp, Kp, need_bwd, folded=not batch_stats, training=save, geom=geom, pkf=pkf, pkb=pkb)
-                if capturing:
-                    _capture.keep(st)               # (a cached staged set may be replaced by a later eager pass: the graph keeps this one)
-                # (a batch-statistics layer joins the one-launch staging with bn = None: its operands depend on the convolution only)
-                if (record is not None and not u.grouped and (batch_stats or u.bn is not None)
-                        and any(p_ is not None and p_.requires_grad
-                                for p_ in (conv.weight, conv.bias) + (() if batch_stats else (u.bn.weight, u.bn.bias)))):
-                    record.append((ui, conv, None if batch_stats else u.bn, Cp, Kp, need_bwd, pkf, pkb))
-            # the stem runs on a pixel-paired image (kernels.stem_*): 28 instead of 49 K chunks
-            stem = STEM_PAIRED and K.is_stem_geom(geom) and not u.grouped and res is None and conv.in_channels <= 3
-            if ui == 0 and nchw_for_stem is not None:
-                if not stem:
-                    raise RuntimeError("engine: the stem was expected to take the NCHW image (placeholder input would be read)")
-                xp = K.stem_pair_from_nchw(nchw_for_stem, dtype)
-            else:
-                xp = K.stem_pair_input(x) if stem else None
-            wp = K.stem_pair_weights(st.w_khwc) if stem else None
-            if not batch_stats:
-                if stem and PACKED and K.stem_fwd_packed_supported(geom, dtype):
-                    y = K.stem_fwd_packed(geom, xp, K.stem_pack_weights(wp), st.shift, u.act)       # ring kernel, gathered rows
-                elif stem:
-                    y = K.stem_fwd(geom, xp, wp, None, st.shift, u.act)
-                elif getattr(st, "fwd_packed", False):
-                    if save and RELU_BITS and u.act == ACT_RELU:
-                        y, bits[u.dst] = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, res, u.act, want_bits=True)
-                    else:
-                        y = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, res, u.act)
-                elif save and RELU_BITS and u.act == ACT_RELU and Kp % 32 == 0:
-                    # one bit per output next to the ReLU output: the data gradient that later masks with this tensor reads
-                    # 1 byte per 16 (the bf16 masks are ~1/8 of a training step's HBM traffic)
-                    y, bits[u.dst] = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, res, u.act, grouped=u.grouped, want_bits=True)
-                else:
-                    y = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, res, u.act, grouped=u.grouped)
-                aux[ui] = SimpleNamespace(geom=geom, st=st, train=False, xp=xp)
-            else:
-                bn = u.bn
-                stats = take_stats(Kp)
-                if stem:
-                    z = K.stem_fwd(geom, xp, wp, None, st.shift, ACT_NONE, stats=stats)
-                elif getattr(st, "fwd_packed", False):
-                    # halo kernel + one statistics pass over the stored z (the statistics of exactly the values bn_apply normalises)
-                    z = K.conv_fwd_packed(geom, x, st.w_khwc, st.shift, None, ACT_NONE)
-                    K.bn_stats(z, stats)
-                else:
-                    z = K.conv_fwd(geom, x, st.w_khwc, None, st.shift, None, ACT_NONE, stats=stats, grouped=u.grouped)
-                M = N * geom.P * geom.Q
-                momentum = bn.momentum if bn.momentum is not None else 0.1
-                # (finalize + apply in one launch: mean / rstd are derived from the sums inside the apply pass)
-                y, mean, rstd = K.bn_apply_stats(z, stats, bn.eps, momentum, bn.running_mean if bn.track_running_stats else None,
-                                                 bn.running_var if bn.track_running_stats else None, bn.weight.detach(), bn.bias.detach(),
-                                                 res, u.act)
-                if bn.track_running_stats and bn.num_batches_tracked is not None:
-                    bumped.append(bn.num_batches_tracked)
-                aux[ui] = SimpleNamespace(geom=geom, st=st, train=True, z=z if save else None, mean=mean, rstd=rstd, xp=xp)
-            t[u.dst] = y
-        elif u.kind == "dw":
-            x = t[u.src]
-            N, H, W, C = x.shape
-            conv, bn = u.conv, u.bn
-            R = conv.kernel_size[0]
-            geom = K.make_geom(N, H, W, C, C, R, R, conv.stride[0], conv.padding[0])
-            w_hwc = dw_hwc[ui] if ui in dw_hwc else conv.weight.detach()[:, 0].permute(1, 2, 0).contiguous()
-            if _bn_uses_batch_stats(bn, bn_train):
-                z, zstats = K.dwconv_fwd_stats(geom, x, w_hwc)
-                M = N * geom.P * geom.Q
-                momentum = bn.momentum if bn.momentum is not None else 0.1
-                t[u.dst], mean, rstd = K.bn_apply_stats(z, zstats, bn.eps, momentum, bn.running_mean if bn.track_running_stats else None,
-                                                        bn.running_var if bn.track_running_stats else None, bn.weight.detach(),
-                                                        bn.bias.detach(), None, u.act)
-                if bn.track_running_stats and bn.num_batches_tracked is not None:
-                    bumped.append(bn.num_batches_tracked)
-                aux[ui] = SimpleNamespace(geom=geom, train=True, z=z if save else None, mean=mean, rstd=rstd, w_hwc=w_hwc)
-            else:
-                scale, shift, _ = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
-                t[u.dst] = K.dwconv_fwd(geom, x, w_hwc, scale, shift, u.act)
-                aux[ui] = SimpleNamespace(geom=geom, train=False)
-        elif u.kind == "se":
-            x = t[u.src]
-            C = x.shape[-1]
-            w1 = u.fc1.weight.detach().view(u.fc1.out_channels, C)
-            w2 = u.fc2.weight.detach().view(C, u.fc2.in_channels)
-            avg, _ = K.gap_fwd(x, with_max=False)
-            h1, u1 = K.linear_fwd(avg, w1, u.fc1.bias.detach(), K.CS_ACT_SILU, want_preact=True)
-            sc = K.linear_fwd(h1, w2, u.fc2.bias.detach(), K.CS_ACT_SIGMOID)
-            t[u.dst] = K.se_scale(x, sc)
-            aux[ui] = SimpleNamespace(avg=avg, h1=h1, u1=u1, s=sc, w1=w1, w2=w2)
-        elif u.kind == "sd":
-            a = t[u.a]
-            keep = 1.0 - u.p
-            noise = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device).bernoulli_(keep)
-            if keep > 0:
-                noise.div_(keep)
-            t[u.dst] = K.rowscale_add(a, noise, t[u.b])
-            aux[ui] = SimpleNamespace(noise=noise)
-        elif u.kind == "pool":
-            y, am = K.maxpool_fwd(t[u.src], want_argmax=save)
-            aux[ui] = SimpleNamespace(argmax=am, in_hw=tuple(t[u.src].shape[1:3]))
-            t[u.dst] = y
-        elif u.kind == "up":
-            x = t[u.src]
-            size = tuple(t[u.size_like].shape[1:3]) if u.size_like is not None else tuple(u.size_fn(in_hw))
-            t[u.dst] = K.bilinear_fwd(x, size)
-            aux[ui] = SimpleNamespace(in_hw=tuple(x.shape[1:3]))
-        elif u.kind == "cat":
-            a, b = t[u.a], t[u.b]
-            t[u.dst] = K.concat(a, b)
-            aux[ui] = SimpleNamespace(ca=a.shape[-1])
+        u.fwd(f, ui)
         for s in u.inputs():
-            release(s)
-    if bumped:
-        torch._foreach_add_(bumped, 1)
-    if record:
-        pk = K.StagePack([r_[1:] for r_ in record], dtype)
-        pk.by_unit = {}
-        for (ui_, _, bn_, cp_, kp_, nb_, pkf_, pkb_), (w_khwc, w_chwk, scale, shift, rstd) in zip(record, pk.staged):
-            if bn_ is None:                          # batch statistics: the consumers expect no folded scale (and no rstd)
-                scale = rstd = None
-            pk.by_unit[ui_] = ((cp_, kp_, nb_, pkf_, pkb_, bn_ is None),
-                               SimpleNamespace(w_khwc=w_khwc, w_chwk=w_chwk, scale=scale, shift=shift, rstd=rstd,
-                                               fwd_packed=bool(pkf_), bwd_packed=bool(pkb_ and nb_)))
-        packs[pack_key] = pk
-    return SimpleNamespace(t=t, aux=aux, in_hw=in_hw, bits=bits)
+            f.release(s)
+    f.finish()
+    return SimpleNamespace(t=f.t, aux=f.aux, in_hw=f.in_hw, bits=f.bits)
 
 
 def compute_requires(plan, param_needs, input_needs):
@@ -536,10 +662,6 @@ def compute_requires(plan, param_needs, input_needs):
     return requires, unit_trainable
 
 
-def _geom_key(geom):
-    return (geom.N, geom.H, geom.W, geom.C, geom.K, geom.R, geom.S, geom.stride, geom.pad)
-
-
 def _defers(u, a, need, ui):
     """Ungrouped convolutions under a BatchNorm take the batched weight-gradient path (one split-K launch + ONE fused finalize per group of
     identical geometry; the fused finalize turns the [rs][c] slabs into torch's [c][rs] order through LDS): eval-BN layers without a
@@ -554,28 +676,10 @@ def _defers(u, a, need, ui):
 
 
 def _group_key(geom, a):
-    return (_geom_key(geom), bool(a.train))
+    return ((geom.N, geom.H, geom.W, geom.C, geom.K, geom.R, geom.S, geom.stride, geom.pad), bool(a.train))
 
 
-PACKED_TRAIN_BN = os.environ.get("CELLSEG_PACKED_TRAIN_BN", "1") != "0"   # ... also for heavy 3x3 convolutions under batch-statistics BN
-PACKED = os.environ.get("CELLSEG_PACKED", "1") != "0"                # packed-operand conv kernels (0: first-generation igemm everywhere)
-RELU_BITS = os.environ.get("CELLSEG_RELU_BITS", "1") != "0"          # bit masks next to ReLU outputs (0: bf16 tensors as masks)
-STEM_PAIRED = os.environ.get("CELLSEG_STEM_PAIRED", "1") != "0"      # pixel-paired stem (0: the generic 7x7 path, for A/B runs)
 _grad_sink = None
-# batched weight gradients on a second HIP stream, concurrently with the dgrad chain: measured 2 % SLOWER on the ResNet-50 tile step
-# (6395 vs 6522 tiles/s: the groups complete late and then compete with the HBM-bound dgrads of the next stage), so opt-in only
-WGRAD_SIDE_STREAM = os.environ.get("CELLSEG_WGRAD_STREAM", "0") == "1"
-# ... or only the groups of the deep stages (destination pixels <= this many: their weight gradients AND the data gradients they would run
-# beside are launches of <= 256 workgroups that leave most of the chip idle); 0 = off.  Round 5 A/B inside the captured step.
-WGRAD_SIDE_MAX_M = int(os.environ.get("CELLSEG_WGRAD_STREAM_MAX_M", "0") or 0)
-_side_streams = {}
-
-
-def _side_stream(dev):
-    s = _side_streams.get(dev)
-    if s is None:
-        s = _side_streams[dev] = torch.cuda.Stream(device=dev)
-    return s
 
 
 def set_grad_sink(sink):
@@ -588,324 +692,213 @@ def set_grad_sink(sink):
     return prev
 
 
-def backward(plan, state, grad_feeds, param_needs, requires, use_tr_read=True):
-    """grad_feeds: {output slot: grad (already ReLU-masked where the slot is post-ReLU)}.
-    Returns ({input slot: grad}, [param grads in plan.param_list order])."""
-    t, aux = state.t, state.aux
-    grads = dict(grad_feeds)
-    gsum_cache = {}
-    sink = _grad_sink
-    # One zero-filled fp32 arena for every raw weight-gradient buffer and column-sum vector of this backward pass
-    # (a single fill kernel instead of ~2 per convolution).
-    need_w_units, arena_elems = set(), 0
-    pi_ = 0
-    for ui_, u_ in enumerate(plan.units):
-        n_ = len(u_.params())
-        if u_.kind == "conv" and any(param_needs[pi_:pi_ + n_]):
-            need_w_units.add(ui_)
-        if u_.kind == "conv" and aux[ui_] is not None:
-            arena_elems += aux[ui_].geom.C + aux[ui_].geom.K + 16
-        pi_ += n_
-    dev_ = next(iter(grad_feeds.values())).device if grad_feeds else None
-    arena = torch.zeros((arena_elems,), dtype=torch.float32, device=dev_) if (arena_elems and dev_ is not None) else None
-    arena_pos = [0]
-    main = torch.cuda.current_stream() if (dev_ is not None and dev_.type == "cuda") else None
-    side = _side_stream(dev_) if (main is not None and (WGRAD_SIDE_STREAM or WGRAD_SIDE_MAX_M > 0)) else None
-    if side is not None and arena is not None:
-        arena.record_stream(side)
+class _Backward:
+    """State of one backward pass: slot and parameter gradients, column sums left by dgrads, batched weight-gradient groups."""
 
-    def take(shape):
-        n = 1
-        for d in shape:
-            n *= d
-        n8 = (n + 7) // 8 * 8
-        if arena is None or arena_pos[0] + n8 > arena.numel():
-            return torch.zeros(shape, dtype=torch.float32, device=dev_)
-        v = arena[arena_pos[0]:arena_pos[0] + n].view(shape)
-        arena_pos[0] += n8
-        return v
-    left = dict(plan.consumers)
-    pgrads = [None] * len(plan.param_list)
-    pindex = {}
-    for i, (ui, role, _) in enumerate(plan.param_list):
-        pindex[(ui, role)] = i
+    def __init__(self, plan, state, grad_feeds, param_needs, requires, use_tr_read):
+        self.plan, self.t, self.aux, self.bits = plan, state.t, state.aux, state.bits
+        self.param_needs, self.requires, self.use_tr_read = param_needs, requires, use_tr_read
+        self.grads = dict(grad_feeds)
+        self.gsum_cache = {}
+        self.sink = _grad_sink
+        # One zero-filled fp32 arena for every raw weight-gradient buffer and column-sum vector of this backward pass
+        # (a single fill kernel instead of ~2 per convolution).
+        self.dev = next(iter(grad_feeds.values())).device if grad_feeds else None
+        n = sum(a.geom.C + a.geom.K + 16 for u, a in zip(plan.units, self.aux) if u.kind == "conv" and a is not None)
+        self.arena = _Arena(n if self.dev is not None else 0, torch.float32, self.dev, 8)
+        self.left = dict(plan.consumers)
+        self.pgrads = [None] * len(plan.param_list)
+        self.pindex = {(ui, role): i for i, (ui, role, _) in enumerate(plan.param_list)}
+        # how many layers of each geometry will ask for a batched weight gradient: a group is launched as soon as it is complete
+        # (or holds 8 layers), so its gradients are final -- and its activations released -- long before backward ends
+        self.group_total, self.group_seen, self.deferred = {}, {}, {}
+        for ui, (u, a) in enumerate(zip(plan.units, self.aux)):
+            if a is not None and _defers(u, a, self.need, ui):
+                k = _group_key(a.geom, a)
+                self.group_total[k] = self.group_total.get(k, 0) + 1
 
-    def need(ui, role):
-        i = pindex.get((ui, role))
-        return i is not None and param_needs[i]
+    def need(self, ui, role):
+        i = self.pindex.get((ui, role))
+        return i is not None and self.param_needs[i]
 
-    def emit(ui, role, g):
+    def emit(self, ui, role, g):
         """Record a finished parameter gradient (and hand it to the data-parallel sink straight away)."""
-        i = pindex[(ui, role)]
-        pgrads[i] = g if sink is None else sink.deliver(plan.param_list[i][2], g)
+        i = self.pindex[(ui, role)]
+        self.pgrads[i] = g if self.sink is None else self.sink.deliver(self.plan.param_list[i][2], g)
 
-    def grad_buffer(param, shape=None):
+    def emit_bn(self, ui, dgamma, dbeta, n=None):
+        """dgamma / dbeta where wanted (their first n channels: the padded ones are not the parameter's)."""
+        if self.need(ui, "gamma"):
+            self.emit(ui, "gamma", dgamma if n is None else dgamma[:n])
+        if self.need(ui, "beta"):
+            self.emit(ui, "beta", dbeta if n is None else dbeta[:n])
+
+    def grad_buffer(self, param):
         """Destination for a parameter gradient: the sink's bucket slice when there is one."""
-        v = sink.view_for(param) if sink is not None else None
-        if v is not None:
-            return v
-        return torch.empty_like(param) if shape is None else torch.empty(shape, dtype=torch.float32, device=param.device)
+        v = self.sink.view_for(param) if self.sink is not None else None
+        return v if v is not None else torch.empty_like(param)
 
-    # how many layers of each geometry will ask for a batched weight gradient: a group is launched as soon as it is complete
-    # (or holds 8 layers), so its gradients are final -- and its activations released -- long before backward ends
-    group_total = {}
-    for ui_, u_ in enumerate(plan.units):
-        if ui_ in need_w_units and aux[ui_] is not None and _defers(u_, aux[ui_], need, ui_):
-            k_ = _group_key(aux[ui_].geom, aux[ui_])
-            group_total[k_] = group_total.get(k_, 0) + 1
-    group_seen = {}
+    def take(self, n):
+        v = self.arena.take(n)
+        return v if v is not None else torch.zeros((n,), dtype=torch.float32, device=self.dev)
 
-    def flush(items):
-        # Weight gradients are off the critical path (the dgrad chain): optionally on a side stream (WGRAD_SIDE_STREAM)
-        if side is None:
-            return flush_on_current(items)
-        if not WGRAD_SIDE_STREAM:
-            g_ = items[0].a.geom
-            if g_.N * g_.P * g_.Q > WGRAD_SIDE_MAX_M:
-                return flush_on_current(items)
-        for it in items:
-            for t_ in (it.x, it.dz, it.a.xp, it.a.st.scale, it.a.st.rstd, getattr(it.gsum, "buf", it.gsum)):
-                if t_ is not None:
-                    t_.record_stream(side)           # allocated on the main stream, read by side-stream kernels
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            flush_on_current(items)
+    def contribute(self, slot, g, masked):
+        """Non-fused contribution (alias when first)."""
+        self.left[slot] -= 1
+        if slot in self.grads:
+            raise NotImplementedError("engine: unfused gradient accumulation is not expected for these networks")
+        if self.left[slot] == 0 and slot in self.plan.relu_slots and not masked:
+            raise NotImplementedError("engine: last contribution to a post-ReLU slot must come from a masking kernel")
+        self.grads[slot] = g
 
-    def flush_on_current(items):
+    def sole_consumer(self, slot, what):
+        """Count the one contribution to `slot` of a unit that cannot add to a gradient already there."""
+        self.left[slot] -= 1
+        if slot in self.grads:
+            raise NotImplementedError(f"engine: {what} input with several consumers")
+
+    def bn_bwd(self, ui, u, g, a, n=None):
+        """Train-mode BatchNorm backward (through the activation) -> dz; dgamma / dbeta emitted where wanted (see emit_bn)."""
+        bn, want = u.bn, self.need(ui, "gamma") or self.need(ui, "beta")
+        dz, dgamma, dbeta = K.bn_bwd(g, a.z, a.mean, a.rstd, bn.weight.detach(), want_param_grads=want, beta=bn.bias.detach(),
+                                     act=ACT_SILU if u.act == ACT_SILU else ACT_NONE)
+        self.emit_bn(ui, dgamma, dbeta, n)
+        return dz
+
+    def colsums(self, u, a, g, dz, partial):
+        """Column sums of dz for u's BN / bias gradients (eval-mode BN: those the dgrad that finished g left), else taken now as a
+        PartialColsum (`partial`) or a vector; shared with the residual slot when it receives the very same gradient tensor."""
+        cached = self.gsum_cache.pop(u.dst, None) if not a.train else None
+        if partial:
+            gsum = cached if cached is not None else K.colsum_partial(dz)
+        else:
+            gsum = K.colsum_vector(cached) if cached is not None else K.colsum(dz)
+        if not a.train and u.res is not None and self.grads.get(u.res) is g:
+            self.gsum_cache[u.res] = gsum
+        return gsum
+
+    def defer_wgrad(self, ui, u, a, x, g, dz):
+        """Weight gradients of identical-geometry layers are launched together (one batched split-K launch per shape group:
+        proportionally fewer partial slabs to write and fold)."""
+        gsum = None
+        if not a.train:
+            gsum = self.colsums(u, a, g, dz, partial=True)
+        elif self.need(ui, "bias"):
+            # the bias of a convolution in front of a batch-statistics BN: d bias = column sums of dz (analytically zero --
+            # the BN backward removes the batch mean --, the reference computes the same rounding noise: train_seg.py decoder)
+            dbias = self.grad_buffer(u.conv.bias)
+            dbias.copy_(K.colsum(dz)[:u.conv.out_channels])
+            self.emit(ui, "bias", dbias)
+        key = _group_key(a.geom, a)
+        items = self.deferred.setdefault(key, [])
+        items.append(SimpleNamespace(ui=ui, u=u, a=a, x=x, dz=dz, gsum=gsum))
+        self.group_seen[key] = self.group_seen.get(key, 0) + 1
+        if len(items) == 8 or self.group_seen[key] == self.group_total.get(key, 0):      # kernel-argument tables hold at most 8 layers
+            self.flush(self.deferred.pop(key))
+
+    def flush(self, items):
         geom = items[0].a.geom
-        n = len(items)
         convs = [it.u.conv for it in items]
         Cin = convs[0].in_channels
         train = bool(items[0].a.train)                   # (a group is all eval-BN or all batch-statistics: _group_key)
-        dws = [grad_buffer(c.weight) for c in convs]
-        dgs = None if train else [grad_buffer(it.u.bn.weight) for it in items]
-        dbs = None if train else [grad_buffer(it.u.bn.bias) for it in items]
+        dws = [self.grad_buffer(c.weight) for c in convs]
+        dgs = None if train else [self.grad_buffer(it.u.bn.weight) for it in items]
+        dbs = None if train else [self.grad_buffer(it.u.bn.bias) for it in items]
         # (single layers take the same path: its finalize folds deferred column sums, the stand-alone one does not)
-        if n == 1 and items[0].a.xp is not None:
-            slabs = K.stem_wgrad(geom, items[0].a.xp, items[0].dz, use_tr_read=use_tr_read).unsqueeze(0)     # [1, 1, K, 7, 7, 8]
+        if len(items) == 1 and items[0].a.xp is not None:
+            slabs = K.stem_wgrad(geom, items[0].a.xp, items[0].dz, use_tr_read=self.use_tr_read).unsqueeze(0)     # [1, 1, K, 7, 7, 8]
         else:
-            slabs = K.wgrad_batched(geom, [it.x for it in items], [it.dz for it in items], use_tr_read=use_tr_read)
+            slabs = K.wgrad_batched(geom, [it.x for it in items], [it.dz for it in items], use_tr_read=self.use_tr_read)
         if train:
             K.wgrad_finalize_batched(slabs, None, None, None, None, None, dws, None, None, Cin)
             for it, dw in zip(items, dws):
-                emit(it.ui, "weight", dw)
+                self.emit(it.ui, "weight", dw)
             return
         K.wgrad_finalize_batched(slabs, [c.weight.detach() for c in convs], [it.a.st.scale for it in items],
                                  [it.a.st.rstd for it in items], [it.u.bn.running_mean for it in items], [it.gsum for it in items],
                                  dws, dgs, dbs, Cin)
         for it, dw, dg, db in zip(items, dws, dgs, dbs):
-            emit(it.ui, "weight", dw)
-            if need(it.ui, "gamma"):
-                emit(it.ui, "gamma", dg)
-            if need(it.ui, "beta"):
-                emit(it.ui, "beta", db)
+            self.emit(it.ui, "weight", dw)
+            self.emit_bn(it.ui, dg, db)
 
-    def contribute(slot, g, masked):
-        """Non-fused contribution (alias when first)."""
-        left[slot] -= 1
-        if slot in grads:
-            raise NotImplementedError("engine: unfused gradient accumulation is not expected for these networks")
-        if left[slot] == 0 and slot in plan.relu_slots and not masked:
-            raise NotImplementedError("engine: last contribution to a post-ReLU slot must come from a masking kernel")
-        grads[slot] = g
+    def conv_wgrad(self, ui, u, a, x, g, dz):
+        """Weight (+ bias, + eval-mode BN) gradients of one convolution, launched now."""
+        conv, geom = u.conv, a.geom
+        want_b = self.need(ui, "bias")
+        want_bn = not a.train and (self.need(ui, "gamma") or self.need(ui, "beta"))
+        gsum = self.colsums(u, a, g, dz, partial=False) if (want_b or want_bn) else None
+        if a.xp is not None:
+            raw = K.stem_wgrad(geom, a.xp, dz, use_tr_read=self.use_tr_read)
+        elif not u.grouped and K.wgrad2_serves(geom, x.dtype):
+            raw = K.wgrad_batched(geom, [x], [dz], use_tr_read=self.use_tr_read)[0]      # wgrad_v2.hip (the batched entry routes to it)
+        else:
+            raw = K.new_wgrad_buffer(geom, x.device, u.grouped)
+            K.conv_wgrad(geom, x, dz, raw, use_tr_read=self.use_tr_read, grouped=u.grouped)
+        dw = self.grad_buffer(conv.weight)
+        dbias = self.grad_buffer(conv.bias) if want_b else None
+        dgamma, dbeta = (self.grad_buffer(u.bn.weight), self.grad_buffer(u.bn.bias)) if want_bn else (None, None)
+        dot = self.take(conv.out_channels) if want_bn else None
+        w = conv.weight.detach() if want_bn else None
+        scale, rstd = (None, None) if a.train else (a.st.scale, a.st.rstd)
+        mean = u.bn.running_mean if want_bn else None
+        if u.grouped:
+            K.wgrad_finalize_grouped(raw, w, scale, rstd, mean, gsum, dw, dgamma=dgamma, dbeta=dbeta, dot=dot)
+        else:
+            K.wgrad_finalize(raw, w, scale, rstd, mean, gsum, conv.in_channels, dw, dbias=dbias, dgamma=dgamma, dbeta=dbeta, dot=dot)
+        if self.need(ui, "weight"):
+            self.emit(ui, "weight", dw)
+        if want_b:
+            self.emit(ui, "bias", dbias)
+        if want_bn:
+            self.emit_bn(ui, dgamma, dbeta)
 
-    deferred = {}
+    def conv_dgrad(self, u, a, x, dz):
+        """Data gradient of conv unit u (packed or dense route); the one finishing the slot masks it and leaves its column sums."""
+        geom, st = a.geom, a.st
+        self.left[u.src] -= 1
+        final = self.left[u.src] == 0
+        pending = self.grads.pop(u.src, None)
+        mask = x if (u.src in self.plan.relu_slots and final) else None
+        mbits = self.bits.get(u.src) if mask is not None else None
+        if mbits is not None:
+            mask = None
+        if st.bwd_packed and geom.stride != 1:
+            if final or pending is not None:
+                raise RuntimeError(f"{u.name}: compact strided data gradient out of order (it must be the first contribution)")
+            return K.conv_dgrad_packed(geom, dz, st.w_chwk)          # kernels.CompactGrad: consumed as a strided add operand
+        if st.bwd_packed:
+            if mask is not None and a.train:
+                mbits, mask = K.positive_bits(mask), None          # (a train-mode BN + ReLU output / a concatenation of such)
+            if mask is not None:
+                raise RuntimeError(f"{u.name}: packed data-gradient operand staged but the ReLU mask is not a bit tensor")
+            if not final:
+                return K.conv_dgrad_packed(geom, dz, st.w_chwk, add=pending, mask_bits=mbits)
+            dx, self.gsum_cache[u.src] = K.conv_dgrad_packed(geom, dz, st.w_chwk, add=pending, mask_bits=mbits, want_colsum=True)
+            return dx
+        if isinstance(pending, K.CompactGrad):
+            raise RuntimeError(f"{u.name}: a compact gradient reached a data gradient that cannot add it")
+        if not final:
+            return K.conv_dgrad(geom, dz, st.w_chwk, add=pending, mask=mask, grouped=u.grouped, mask_bits=mbits)
+        # column sums of the finished gradient feed its producer's BN/bias gradients: left as per-workgroup partial
+        # rows where the launch allows it (the batched finalize folds them; one small launch less per layer)
+        cs = self.take(geom.C) if (geom.stride != 1 or u.grouped) else None
+        dx, self.gsum_cache[u.src] = K.conv_dgrad(geom, dz, st.w_chwk, add=pending, mask=mask, colsum=cs, grouped=u.grouped,
+                                                  defer_colsum=True, mask_bits=mbits)
+        return dx
+
+
+def backward(plan, state, grad_feeds, param_needs, requires, use_tr_read=True):
+    """grad_feeds: {output slot: grad (already ReLU-masked where the slot is post-ReLU)}.
+    Returns ({input slot: grad}, [param grads in plan.param_list order])."""
+    b = _Backward(plan, state, grad_feeds, param_needs, requires, use_tr_read)
     for ui in reversed(range(len(plan.units))):
         u = plan.units[ui]
-        g = grads.pop(u.dst, None)
-        a = aux[ui]
-        if g is None:
-            continue
-        if u.kind == "conv":
-            conv = u.conv
-            Kc, Cin = conv.out_channels, conv.in_channels
-            geom = a.geom
-            x = t[u.src]
-            if u.res is not None and requires.get(u.res, False):
-                contribute(u.res, g, masked=False)
-            want_w = need(ui, "weight")
-            want_b = need(ui, "bias")
-            want_bn = need(ui, "gamma") or need(ui, "beta")
-            dz = g
-            if u.act == ACT_SILU and not a.train:
-                raise NotImplementedError(f"{u.name}: backward through a folded (eval-mode) BN + SiLU is not supported; "
-                                          "EfficientNet trains with batch statistics (efficientnet.py:308-312)")
-            if a.train:
-                bn = u.bn
-                dz, dgamma, dbeta = K.bn_bwd(g, a.z, a.mean, a.rstd, bn.weight.detach(), want_param_grads=want_bn,
-                                             beta=bn.bias.detach(), act=ACT_SILU if u.act == ACT_SILU else ACT_NONE)
-                if need(ui, "gamma"):
-                    emit(ui, "gamma", dgamma[:Kc])
-                if need(ui, "beta"):
-                    emit(ui, "beta", dbeta[:Kc])
-            if _defers(u, a, need, ui):
-                # weight gradients of identical-geometry layers are launched together (one batched split-K launch per shape
-                # group: proportionally fewer partial slabs to write and fold)
-                gsum = None
-                if not a.train:
-                    gsum = gsum_cache.pop(u.dst, None)
-                    if gsum is None:
-                        gsum = K.colsum_partial(dz)
-                    if u.res is not None and grads.get(u.res) is g:
-                        gsum_cache[u.res] = gsum
-                elif want_b:
-                    # the bias of a convolution in front of a batch-statistics BN: d bias = column sums of dz (analytically zero --
-                    # the BN backward removes the batch mean --, the reference computes the same rounding noise: train_seg.py decoder)
-                    dbias = grad_buffer(conv.bias)
-                    dbias.copy_(K.colsum(dz)[:Kc])
-                    emit(ui, "bias", dbias)
-                key = _group_key(geom, a)
-                items = deferred.setdefault(key, [])
-                items.append(SimpleNamespace(ui=ui, u=u, a=a, x=x, dz=dz, gsum=gsum))
-                group_seen[key] = group_seen.get(key, 0) + 1
-                if len(items) == 8 or group_seen[key] == group_total.get(key, 0):      # kernel-argument tables hold at most 8 layers
-                    flush(deferred.pop(key))
-            elif want_w or want_b or (want_bn and not a.train):
-                gsum = None
-                if want_b or (want_bn and not a.train):
-                    gsum = K.colsum_vector(gsum_cache.pop(u.dst, None)) if not a.train else None
-                    if gsum is None:
-                        gsum = K.colsum(dz)
-                    if not a.train and u.res is not None and grads.get(u.res) is g:
-                        gsum_cache[u.res] = gsum      # the residual branch receives the very same gradient tensor
-                if a.xp is not None:
-                    raw = K.stem_wgrad(geom, a.xp, dz, use_tr_read=use_tr_read)
-                elif not u.grouped and K.wgrad2_serves(geom, x.dtype):
-                    raw = K.wgrad_batched(geom, [x], [dz], use_tr_read=use_tr_read)[0]      # wgrad_v2.hip (the batched entry routes to it)
-                else:
-                    raw = K.new_wgrad_buffer(geom, x.device, u.grouped)
-                    K.conv_wgrad(geom, x, dz, raw, use_tr_read=use_tr_read, grouped=u.grouped)
-                dw = grad_buffer(conv.weight)
-                dbias = grad_buffer(conv.bias) if want_b else None
-                dgamma = dbeta = None
-                if want_bn and not a.train:
-                    dgamma, dbeta = grad_buffer(u.bn.weight), grad_buffer(u.bn.bias)
-                dot = take((Kc,)) if dgamma is not None else None
-                if u.grouped:
-                    K.wgrad_finalize_grouped(raw, conv.weight.detach() if dgamma is not None else None, None if a.train else a.st.scale,
-                                             None if a.train else a.st.rstd, u.bn.running_mean if dgamma is not None else None, gsum, dw,
-                                             dgamma=dgamma, dbeta=dbeta, dot=dot)
-                else:
-                    K.wgrad_finalize(raw, conv.weight.detach() if dgamma is not None else None, None if a.train else a.st.scale,
-                                     None if a.train else a.st.rstd, u.bn.running_mean if dgamma is not None else None, gsum, Cin, dw,
-                                     dbias=dbias, dgamma=dgamma, dbeta=dbeta, dot=dot)
-                if want_w:
-                    emit(ui, "weight", dw)
-                if want_b:
-                    emit(ui, "bias", dbias)
-                if dgamma is not None:
-                    if need(ui, "gamma"):
-                        emit(ui, "gamma", dgamma)
-                    if need(ui, "beta"):
-                        emit(ui, "beta", dbeta)
-            gsum_cache.pop(u.dst, None)
-            if requires.get(u.src, False):
-                left[u.src] -= 1
-                final = left[u.src] == 0
-                pending = grads.pop(u.src, None)
-                mask = x if (u.src in plan.relu_slots and final) else None
-                mbits = state.bits.get(u.src) if mask is not None else None
-                if mbits is not None:
-                    mask = None
-                if getattr(a.st, "bwd_packed", False) and geom.stride != 1:
-                    if final or pending is not None:
-                        raise RuntimeError(f"{u.name}: compact strided data gradient out of order (it must be the first contribution)")
-                    dx = K.conv_dgrad_packed(geom, dz, a.st.w_chwk)          # kernels.CompactGrad: consumed as a strided add operand
-                elif getattr(a.st, "bwd_packed", False):
-                    if mask is not None and a.train:
-                        mbits, mask = K.positive_bits(mask), None          # (a train-mode BN + ReLU output / a concatenation of such)
-                    if mask is not None:
-                        raise RuntimeError(f"{u.name}: packed data-gradient operand staged but the ReLU mask is not a bit tensor")
-                    if final:
-                        dx, gsum_cache[u.src] = K.conv_dgrad_packed(geom, dz, a.st.w_chwk, add=pending, mask_bits=mbits, want_colsum=True)
-                    else:
-                        dx = K.conv_dgrad_packed(geom, dz, a.st.w_chwk, add=pending, mask_bits=mbits)
-                elif final:
-                    # column sums of the finished gradient feed its producer's BN/bias gradients: left as per-workgroup partial
-                    # rows where the launch allows it (the batched finalize folds them; one small launch less per layer)
-                    if isinstance(pending, K.CompactGrad):
-                        raise RuntimeError(f"{u.name}: a compact gradient reached a data gradient that cannot add it")
-                    cs = take((geom.C,)) if (geom.stride != 1 or u.grouped) else None
-                    dx, gsum_cache[u.src] = K.conv_dgrad(geom, dz, a.st.w_chwk, add=pending, mask=mask, colsum=cs, grouped=u.grouped,
-                                                         defer_colsum=True, mask_bits=mbits)
-                else:
-                    if isinstance(pending, K.CompactGrad):
-                        raise RuntimeError(f"{u.name}: a compact gradient reached a data gradient that cannot add it")
-                    dx = K.conv_dgrad(geom, dz, a.st.w_chwk, add=pending, mask=mask, grouped=u.grouped, mask_bits=mbits)
-                grads[u.src] = dx
-        elif u.kind == "dw":
-            if not a.train:
-                raise NotImplementedError(f"{u.name}: backward through an eval-mode depthwise block is not supported")
-            bn, x = u.bn, t[u.src]
-            want_bn = need(ui, "gamma") or need(ui, "beta")
-            dz, dgamma, dbeta = K.bn_bwd(g, a.z, a.mean, a.rstd, bn.weight.detach(), want_param_grads=want_bn, beta=bn.bias.detach(),
-                                         act=ACT_SILU if u.act == ACT_SILU else ACT_NONE)
-            if need(ui, "gamma"):
-                emit(ui, "gamma", dgamma)
-            if need(ui, "beta"):
-                emit(ui, "beta", dbeta)
-            if need(ui, "weight"):
-                emit(ui, "weight", K.dwconv_wgrad(a.geom, x, dz, param_layout=True))
-            if requires.get(u.src, False):
-                left[u.src] -= 1
-                dx = K.dwconv_dgrad(a.geom, dz, a.w_hwc)
-                pending = grads.pop(u.src, None)
-                grads[u.src] = dx if pending is None else K.rowscale_add(dx, None, pending)
-        elif u.kind == "se":
-            x = t[u.src]
-            ds = K.se_scale_bwd_ds(g, x)
-            want2 = need(ui, "w2") or need(ui, "b2")
-            want1 = need(ui, "w1") or need(ui, "b1")
-            dh1, dw2, db2 = K.linear_bwd(a.h1, a.w2, ds, a.s, K.CS_ACT_SIGMOID, True, want2, want2)
-            davg, dw1, db1 = K.linear_bwd(a.avg, a.w1, dh1, a.u1, K.CS_ACT_SILU, True, want1, want1)
-            if need(ui, "w2"):
-                emit(ui, "w2", dw2.view_as(u.fc2.weight))
-            if need(ui, "b2"):
-                emit(ui, "b2", db2)
-            if need(ui, "w1"):
-                emit(ui, "w1", dw1.view_as(u.fc1.weight))
-            if need(ui, "b1"):
-                emit(ui, "b1", db1)
-            if requires.get(u.src, False):
-                left[u.src] -= 1
-                if u.src in grads:
-                    raise NotImplementedError("engine: SE input with several consumers")
-                grads[u.src] = K.se_scale_bwd_dx(g, a.s, davg)
-        elif u.kind == "sd":
-            if requires.get(u.b, False):
-                contribute(u.b, g, masked=True)
-            if requires.get(u.a, False):
-                contribute(u.a, K.rowscale_add(g, a.noise, None), masked=True)
-        elif u.kind == "pool":
-            if requires.get(u.src, False):
-                left[u.src] -= 1
-                if u.src in grads:
-                    raise NotImplementedError("engine: pool input with several consumers")
-                # dy is masked by [pool_out>0]; the argmax element equals pool_out, so dx is masked too
-                grads[u.src] = K.maxpool_bwd(g, a.argmax, None, a.in_hw)
-        elif u.kind == "up":
-            if requires.get(u.src, False):
-                left[u.src] -= 1
-                if u.src in grads:
-                    raise NotImplementedError("engine: upsample input with several consumers")
-                mask = t[u.src] if u.src in plan.relu_slots else None
-                grads[u.src] = K.bilinear_bwd(g, a.in_hw, mask=mask)
-        elif u.kind == "cat":
-            na, nb = requires.get(u.a, False), requires.get(u.b, False)
-            if na or nb:
-                ga, gb = K.split(g, a.ca, want_a=na, want_b=nb)
-                if na:
-                    contribute(u.a, ga, masked=True)
-                if nb:
-                    contribute(u.b, gb, masked=True)
-    for items in list(deferred.values()):       # groups whose count fell short of the forecast (defensive; not expected)
-        flush(items)
-    if side is not None:
-        main.wait_stream(side)                   # every parameter gradient is final before autograd hands it on
-        for g_ in pgrads:
-            if g_ is not None:
-                g_.record_stream(main)
-    return {s: grads.get(s) for s in plan.inputs}, pgrads
+        g = b.grads.pop(u.dst, None)
+        if g is not None:
+            u.bwd(b, ui, g)
+    for items in list(b.deferred.values()):       # groups whose count fell short of the forecast (defensive; not expected)
+        b.flush(items)
+    return {s: b.grads.get(s) for s in plan.inputs}, b.pgrads
 
 
 class _PlanFunction(torch.autograd.Function):

@@ -33,7 +33,7 @@ _ALIGN = 64      # floats: every bucket slice starts on a 256-byte boundary
 
 
 class _Bucket:
-    __slots__ = ("flat", "items", "views", "ptrs", "dirty", "pending", "launched", "streams")
+    __slots__ = ("flat", "items", "views", "ptrs", "dirty", "pending", "launched")
 
     def __init__(self, n, device):
         self.flat = torch.zeros((n,), dtype=torch.float32, device=device)
@@ -43,7 +43,6 @@ class _Bucket:
         self.dirty = []          # the slice has held a gradient since it was last zero (`flat` starts as zeros)
         self.pending = 0
         self.launched = False
-        self.streams = set()     # streams whose kernels wrote gradients into this bucket since the last reduce()
 
 
 class GradReducer:
@@ -121,7 +120,6 @@ class GradReducer:
         for b in self.buckets:
             b.pending = len(b.items)
             b.launched = False
-            b.streams = set()
         self._overlap_ok = True
 
     def broadcast_parameters(self, module, src=0):
@@ -173,8 +171,6 @@ class GradReducer:
             return grad
         if grad is not view and grad.data_ptr() != vptr:
             view.copy_(grad)
-        if (_engine.WGRAD_SIDE_STREAM or _engine.WGRAD_SIDE_MAX_M > 0) and view.is_cuda:
-            b.streams.add(torch.cuda.current_stream())      # (opt-in engine mode: weight gradients finished on a side stream)
         b.pending -= 1
         if b.pending == 0 and self._overlap_ok and self._layout_final:
             self._launch(b)
@@ -200,8 +196,6 @@ class GradReducer:
             if self._stream is None:
                 self._stream = torch.cuda.Stream()
             self._stream.wait_stream(torch.cuda.current_stream())
-            for st in b.streams:
-                self._stream.wait_stream(st)
             with torch.cuda.stream(self._stream):
                 if self.time_collectives:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

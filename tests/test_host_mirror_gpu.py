@@ -332,7 +332,7 @@ def test_training_reduces_the_loss_bf16(dev):
 def test_mixed_frozen_and_train_mode_batchnorm_trains(dev):
     """a strided shortcut whose own BN is frozen (folded, packed, compact gradient) next to a conv1 whose BN uses batch
     statistics (not packed) must fall back to the dense strided data gradient instead of raising 'a compact gradient reached a
-    data gradient that cannot add it'.  Gradients equal the all-first-generation path (CELLSEG_PACKED=0 semantics)."""
+    data gradient that cannot add it'.  Gradients equal the all-first-generation path (engine.PACKED = False)."""
     from cellsegmentation_amd import engine as E
     torch.manual_seed(0)
 
