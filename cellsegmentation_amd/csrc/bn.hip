@@ -405,29 +405,27 @@ inline int fold_partial(const double* partial, int blocks, int C, double* out, h
 }
 
 // Decomposition of the reductions (bn_stats_kernel, bn_bwd_reduce_kernel): channel chunks of <= 16 / 32 / 64 8-channel groups (balanced),
-// rows per workgroup for ~CELLSEG_BN_BLOCKS workgroups in all, never fewer than 8 row steps per thread.  A thread owns one 8-channel group
+// rows per workgroup for ~kBnRedBlocks workgroups in all, never fewer than 8 row steps per thread.  A thread owns one 8-channel group
 // and every rpar-th row of its block (rpar = 256 / chunk width).  Round 5: until then a workgroup covered ALL channels of its rows --
 // 174 live threads, one row each, for EfficientNet's 6400 x 1392 tensors, 800 row blocks of 8 rows whose 2 x 1392 partial sums (as
 // many bytes as the tensor) went through a workspace and a fold launch: 19 us for a pass that moves 36 MB.  With chunks the same
 // tensor is 100 row blocks x 6 chunks with 8 rows in flight per chunk: 14 us.
 struct RedSplit { int chunks, cw, rpb; };
+constexpr int kBnRedBlocks = 1024;
 inline RedSplit red_split(long long M, int C) {
-    static const int target = cs_env_int_("CELLSEG_BN_BLOCKS", 1024);     // A/B experiments only
     const int CG = C / 8 > 0 ? C / 8 : 1;
     RedSplit s;
     // chunk width (measured on EfficientNet-B3's tensors, tools/bn_microbench.py): one chunk while it is at most 64 groups wide and the
     // rows alone give >= 800 workgroups; 16-group chunks for tensors so small that the 8-step floor leaves < 450 workgroups whatever the
     // width (fewer row blocks = fewer contributions per channel: most of those then fit the atomics budget, one launch); 32 otherwise
-    static const int forced_w = cs_env_int_("CELLSEG_BN_CW", 0);           // A/B experiments only
     int max_w = 32;
     if (CG <= 64 && M >= 800LL * 8 * (256 / CG)) max_w = 64;
     else if (M * CG < 450LL * 2048) max_w = 16;
-    if (forced_w > 0) max_w = forced_w;
     s.chunks = (CG + max_w - 1) / max_w;
     s.cw = (CG + s.chunks - 1) / s.chunks;
     s.chunks = (CG + s.cw - 1) / s.cw;
     const int rpar = 256 / s.cw;
-    long long row_blocks = target / s.chunks;
+    long long row_blocks = kBnRedBlocks / s.chunks;
     if (row_blocks < 1) row_blocks = 1;
     long long r = (M + row_blocks - 1) / row_blocks;
     const long long floor_rows = 8LL * rpar;
@@ -436,28 +434,27 @@ inline RedSplit red_split(long long M, int C) {
     return s;
 }
 
-// row block of the element-wise passes: ~CELLSEG_EW_BLOCKS (2048: 8 workgroups per compute unit) blocks, at least 16 rows each
+// row block of the element-wise passes: ~kEwBlocks (8 workgroups per compute unit) blocks, at least 16 rows each
+constexpr int kEwBlocks = 2048;
 inline int ew_rows_per_block(long long M, int C) {
-    static const int target = cs_env_int_("CELLSEG_EW_BLOCKS", 2048);       // A/B experiments only
     const int CG = C / 8 > 0 ? C / 8 : 1;
     const int rpar = 256 / (CG < 256 ? CG : 256);
-    long long r = (M + target - 1) / target;
+    long long r = (M + kEwBlocks - 1) / kEwBlocks;
     const long long floor_rows = 4LL * (rpar > 0 ? rpar : 1);              // >= 2 two-row steps per thread
     if (r < floor_rows) r = floor_rows;
     return (int)r;
 }
 
 // Decomposition of the element-wise passes (bn_apply_kernel, bn_bwd_apply_kernel): channel chunks of max_w 8-channel groups,
-// and rows per workgroup for ~CELLSEG_EW_BLOCKS workgroups in all with at least `steps` two-row steps per thread.
+// and rows per workgroup for ~kEwBlocks workgroups in all with at least `steps` two-row steps per thread.
 struct EwSplit { int chunks, cw, rpb; };
 inline EwSplit ew_split(long long M, int C, int max_w, int steps) {
-    static const int target = cs_env_int_("CELLSEG_EW_BLOCKS", 2048);       // A/B experiments only
     const int CG = C / 8 > 0 ? C / 8 : 1;
     EwSplit s;
     s.cw = CG < max_w ? CG : max_w;                  // (the last chunk may be narrower: a workgroup derives its own width)
     s.chunks = (CG + s.cw - 1) / s.cw;
     const int rpar = 256 / s.cw > 0 ? 256 / s.cw : 1;
-    long long row_blocks = target / s.chunks;
+    long long row_blocks = kEwBlocks / s.chunks;
     if (row_blocks < 1) row_blocks = 1;
     long long r = (M + row_blocks - 1) / row_blocks;
     const long long floor_rows = 2LL * steps * rpar;

@@ -23,6 +23,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <vector>
 
 namespace {
 
@@ -798,109 +799,6 @@ __global__ __launch_bounds__(256, PF ? 2 : 4) void igemm_dma_kernel(IgemmParams 
     igemm_epilogue<T, BM, BN, PF>(p, acc, smem_raw, m0, n0, slab_row0 + mtile, &er);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// Streaming variant for the HBM-bound pure-GEMM convolutions with a short contraction (1x1, C_in <= 128):
-// a PERSISTENT workgroup owns one destination-channel tile, keeps its weights resident in LDS, and walks
-// pixel tiles with the NEXT tile's LDS-DMA always in flight while the current tile is multiplied and
-// its epilogue (residual/mask loads, stores) drains -- the one-shot kernel had a single short burst
-// of loads per workgroup and then nothing outstanding (2.6 TB/s algorithmic); this keeps the memory
-// system busy.  LDS: [B: NK stages][A: 2 x NK stages][epilogue staging (BM/2 x BN fp32)].
-// ---------------------------------------------------------------------------------------------
-template <typename T, int BM, int BN, int NK>
-__global__ __launch_bounds__(256) void igemm_stream_kernel(IgemmParams p, unsigned src_bytes, unsigned wgt_bytes, int n_mtiles) {
-    constexpr int ES = (int)sizeof(T);
-    constexpr int TM = BM / 64, TN = BN / 64;
-    constexpr int AI = BM / 32, BI = BN / 32;
-    constexpr unsigned OOB = 0x80000000u;
-    constexpr int B_BYTES = NK * BN * 128;
-    constexpr int A_BYTES = NK * BM * 128;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    unsigned char* Bs_base = smem_raw;
-    unsigned char* As_base = smem_raw + B_BYTES;
-    unsigned char* epi = As_base + 2 * A_BYTES;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, hh = lane >> 5;
-    const int n0 = blockIdx.y * BN;
-
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.src), 0, src_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt), 0, wgt_bytes, 0x00020000);
-    const int lr = tid >> 3;
-    const int lc = (tid & 7) ^ ((lr >> 1) & 7);
-    const unsigned wrow_bytes = (unsigned)p.wrow_chunks * 16u;
-    const unsigned row_bytes = (unsigned)p.SC * ES;
-
-    // weights: once per workgroup
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-        const int q = ks * 8 + lc;
-#pragma unroll
-        for (int j = 0; j < BI; ++j) {
-            const int o = n0 + lr + 32 * j;
-            const unsigned vb = (o < p.NOUT && q < p.Qtot) ? (unsigned)o * wrow_bytes + (unsigned)q * 16u : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(Bs_base + ks * BN * 128 + (8 * wave + 32 * j) * 128),
-                                                     16, (int)vb, 0, 0, 0);
-        }
-    }
-    auto issue_a = [&](int tile, int buf) {
-        const long long m0 = (long long)tile * BM;
-#pragma unroll
-        for (int ks = 0; ks < NK; ++ks) {
-            const int q = ks * 8 + lc;
-#pragma unroll
-            for (int i = 0; i < AI; ++i) {
-                const long long m = m0 + lr + 32 * i;
-                const unsigned va = (m < p.M && q < p.Qtot) ? (unsigned)(m * row_bytes) + (unsigned)q * 16u : OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                    rsrc_a, (__attribute__((address_space(3))) void*)(As_base + buf * A_BYTES + ks * BM * 128 + (8 * wave + 32 * i) * 128), 16,
-                    (int)va, 0, 0, 0);
-            }
-        }
-    };
-
-    int tile = blockIdx.x;
-    if (tile < n_mtiles) issue_a(tile, 0);
-    for (int it = 0; tile < n_mtiles; tile += gridDim.x, ++it) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const int nxt = tile + gridDim.x;
-        if (nxt < n_mtiles) issue_a(nxt, (it + 1) & 1);
-
-        f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < NK; ++ks) {
-            const uint4* As = reinterpret_cast<const uint4*>(As_base + (it & 1) * A_BYTES + ks * BM * 128);
-            const uint4* Bs = reinterpret_cast<const uint4*>(Bs_base + ks * BN * 128);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int c = 2 * kk + hh;
-                uint4 a[TM], b[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a[i] = As[swz(wm * (BM / 2) + i * 32 + l31, c)];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[j] = Bs[swz(wn * (BN / 2) + j * 32 + l31, c)];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) Mma<T>::run(a[i], b[j], acc[i][j]);
-            }
-        }
-        igemm_epilogue<T, BM, BN>(p, acc, epi, (long long)tile * BM, n0, tile);
-        // the epilogue's last LDS reads (statistics fold) must finish before the next tile's first staging write
-        __syncthreads();
-    }
-}
-
 // Fold the per-workgroup partial rows: out[c] += sum_r slab[r][c] for c < ncols (row stride = stride).
 // Workgroup = 64 columns x 4 row lanes, gridDim.y row chunks.  Every result repeats bit for bit (round 5): `stats` is an exact,
 // order-independent accumulator (ex_add); a float `colsum` target is added to by ONE workgroup per column when the grid has one row
@@ -973,17 +871,25 @@ void note_variant(const char* fmt, ...) {
     cs_set_variant_(buf);
 }
 
-int g_stream_enabled = 0;   // persistent streaming kernel for short-K pure-GEMM convs: opt-in (cs_set_igemm_path(3)); measured
-                            // 5-25 % SLOWER than the one-shot kernel on MI355X (its vmcnt(0) also drains the previous tile's stores)
-const bool g_merge_classes = !cs_env_flag_("CELLSEG_NO_MERGE");   // A/B experiments only
-const bool g_uni_walk = !cs_env_flag_("CELLSEG_NO_UNI");   // A/B experiments only
-const bool g_epi_prefetch = !cs_env_flag_("CELLSEG_NO_EPI_PREFETCH");   // A/B experiments only
 int g_igemm_path = 0;   // 0 = LDS-DMA when operands < 2 GiB, 1 = always register-staged (A/B testing)
 
 int igemm_mode(const IgemmParams& p) {
     if (p.div > 1) return 2;
     if (p.R == 1 && p.S == 1 && p.mul == 1 && p.mulx == 1 && p.off0 == 0 && p.off0x == 0 && p.wkstep == 1 && p.dst_step == 1 && !p.cslab) return 0;
     return p.R * p.S <= 64 ? 1 : 2;
+}
+
+// one launch of the LDS-DMA / the register-staged kernel, noted under the instantiation's name
+template <typename T, int BM, int BN, int MODE, bool PF, bool UNI>
+void launch_dma(dim3 grid, size_t lds, hipStream_t st, const IgemmParams& p, unsigned long long src_bytes, unsigned long long wgt_bytes) {
+    note_variant("igemm_dma_kernel<%s,%d,%d,%d,%s,%s>", tname<T>(), BM, BN, MODE, PF ? "true" : "false", UNI ? "true" : "false");
+    hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, MODE, PF, UNI>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes);
+}
+
+template <typename T, int BM, int BN, int MODE>
+void launch_reg(dim3 grid, size_t lds, hipStream_t st, const IgemmParams& p) {
+    note_variant("igemm_kernel<%s,%d,%d,%d>", tname<T>(), BM, BN, MODE);
+    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, MODE>), grid, dim3(256), lds, st, p);
 }
 
 template <typename T, int BM, int BN>
@@ -1014,11 +920,10 @@ int launch_igemm(const IgemmParams& p, hipStream_t st) {
         size_t clds = (max_nk <= 1 ? 1 : 2) * one_stage;
         if (clds < epi_bytes) clds = epi_bytes;
         if (clds < red_bytes) clds = red_bytes;
-        const bool uni = g_uni_walk && q.SCc % 8 == 0;       // every class has R*S <= 4 taps here
         const unsigned long long sb = (unsigned long long)q.src_pixels * q.SC * sizeof(T);
         const unsigned long long wb = (unsigned long long)q.NOUT * q.wrow_chunks * 16ull;
-        if (uni) { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,true>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1, false, true>), dim3(b0), dim3(256), clds, st, q, (unsigned)sb, (unsigned)wb); }
-        else { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,false>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1, false, false>), dim3(b0), dim3(256), clds, st, q, (unsigned)sb, (unsigned)wb); }
+        if (q.SCc % 8 == 0) launch_dma<T, BM, BN, 1, false, true>(dim3(b0), clds, st, q, sb, wb);   // every class has R*S <= 4 taps here
+        else launch_dma<T, BM, BN, 1, false, false>(dim3(b0), clds, st, q, sb, wb);
         CS_LAUNCH_CHECK();
         return CS_OK;
     }
@@ -1026,64 +931,25 @@ int launch_igemm(const IgemmParams& p, hipStream_t st) {
     const unsigned long long wgt_bytes = (unsigned long long)p.NOUT * p.wrow_chunks * 16ull;
     const bool dma = g_igemm_path == 0 && src_bytes < 0x80000000ull && wgt_bytes < 0x80000000ull;
     const int mode = igemm_mode(p);
-    if (dma && mode == 0 && nk_host <= 2 && g_stream_enabled) {
-        // persistent streaming kernel: ~2 workgroups per CU in total, each pinned to one N tile
-        const int n_mtiles = (int)((p.M + BM - 1) / BM);
-        const int n_ntiles = (p.NOUT + BN - 1) / BN;
-        int gx = (512 + n_ntiles - 1) / n_ntiles;
-        if (gx > n_mtiles) gx = n_mtiles;
-        if (gx < 1) gx = 1;
-        dim3 sgrid(gx, n_ntiles, 1);
-        const size_t slds = (size_t)nk_host * (BN + 2 * BM) * 128 + ((size_t)BM * BN * 2 > 16384 ? (size_t)BM * BN * 2 : 16384);
-        auto raise = [&](const void* fn) -> int {
-            if (slds <= 65536) return CS_OK;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds) != hipSuccess) {
-                cs_set_error_("igemm_stream: cannot raise the dynamic LDS limit");
-                return CS_ERR_LAUNCH;
-            }
-            return CS_OK;
-        };
-        if (nk_host <= 1) {
-            if (raise(reinterpret_cast<const void*>(&igemm_stream_kernel<T, BM, BN, 1>)) != CS_OK) return CS_ERR_LAUNCH;
-            { note_variant("igemm_stream_kernel<%s,%d,%d,1>", tname<T>(), BM, BN); hipLaunchKernelGGL((igemm_stream_kernel<T, BM, BN, 1>), sgrid, dim3(256), slds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes, n_mtiles); }
-        } else {
-            if (raise(reinterpret_cast<const void*>(&igemm_stream_kernel<T, BM, BN, 2>)) != CS_OK) return CS_ERR_LAUNCH;
-            { note_variant("igemm_stream_kernel<%s,%d,%d,2>", tname<T>(), BM, BN); hipLaunchKernelGGL((igemm_stream_kernel<T, BM, BN, 2>), sgrid, dim3(256), slds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes, n_mtiles); }
-        }
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
+    // epilogue operands loaded under the main loop: bf16 only (f32 has no such instantiation), more than one K-step, something to load
+    constexpr bool BF = sizeof(T) == 2;
+    const bool pf = BF && nk_host > 1 && (p.residual || p.mask || p.bits_in) && p.dst_step == 1;
     // scalar K walk: every 1x1 launch; tap-walking launches whose tap is wave-uniform (whole 64-element K-steps per tap)
-    const bool uni1 = g_uni_walk && mode == 1 && p.SCc % 8 == 0 && p.R * p.S <= 32;
-    const bool uni0 = g_uni_walk && mode == 0;
-    if constexpr (sizeof(T) == 2) {
-        if (dma && mode != 2 && nk_host > 1 && (p.residual || p.mask || p.bits_in) && p.dst_step == 1 && g_epi_prefetch) {
-            if (mode == 0 && uni0) { note_variant("igemm_dma_kernel<%s,%d,%d,%d,true,true>", tname<T>(), BM, BN, 0); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 0, true, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-            else if (mode == 0) { note_variant("igemm_dma_kernel<%s,%d,%d,%d,true,false>", tname<T>(), BM, BN, 0); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 0, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-            else if (uni1) { note_variant("igemm_dma_kernel<%s,%d,%d,%d,true,true>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1, true, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-            else { note_variant("igemm_dma_kernel<%s,%d,%d,%d,true,false>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-            CS_LAUNCH_CHECK();
-            return CS_OK;
-        }
-    }
-    if (dma && ((mode == 0 && uni0) || uni1)) {
-        if (mode == 0) { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,true>", tname<T>(), BM, BN, 0); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 0, false, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-        else { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,true>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1, false, true>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); }
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dma) {
-        switch (mode) {
-            case 0: { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,false>", tname<T>(), BM, BN, 0); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 0>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); } break;
-            case 1: { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,false>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 1>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); } break;
-            default: { note_variant("igemm_dma_kernel<%s,%d,%d,%d,false,false>", tname<T>(), BM, BN, 2); hipLaunchKernelGGL((igemm_dma_kernel<T, BM, BN, 2>), grid, dim3(256), lds, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes); } break;
-        }
+    const bool uni1 = p.SCc % 8 == 0 && p.R * p.S <= 32;
+    if (!dma) {
+        if (mode == 0) launch_reg<T, BM, BN, 0>(grid, lds, st, p);
+        else if (mode == 1) launch_reg<T, BM, BN, 1>(grid, lds, st, p);
+        else launch_reg<T, BM, BN, 2>(grid, lds, st, p);
+    } else if (mode == 0) {
+        if (pf) launch_dma<T, BM, BN, 0, BF, true>(grid, lds, st, p, src_bytes, wgt_bytes);
+        else launch_dma<T, BM, BN, 0, false, true>(grid, lds, st, p, src_bytes, wgt_bytes);
+    } else if (mode == 1) {
+        if (pf && uni1) launch_dma<T, BM, BN, 1, BF, true>(grid, lds, st, p, src_bytes, wgt_bytes);
+        else if (pf) launch_dma<T, BM, BN, 1, BF, false>(grid, lds, st, p, src_bytes, wgt_bytes);
+        else if (uni1) launch_dma<T, BM, BN, 1, false, true>(grid, lds, st, p, src_bytes, wgt_bytes);
+        else launch_dma<T, BM, BN, 1, false, false>(grid, lds, st, p, src_bytes, wgt_bytes);
     } else {
-        switch (mode) {
-            case 0: { note_variant("igemm_kernel<%s,%d,%d,%d>", tname<T>(), BM, BN, 0); hipLaunchKernelGGL((igemm_kernel<T, BM, BN, 0>), grid, dim3(256), lds, st, p); } break;
-            case 1: { note_variant("igemm_kernel<%s,%d,%d,%d>", tname<T>(), BM, BN, 1); hipLaunchKernelGGL((igemm_kernel<T, BM, BN, 1>), grid, dim3(256), lds, st, p); } break;
-            default: { note_variant("igemm_kernel<%s,%d,%d,%d>", tname<T>(), BM, BN, 2); hipLaunchKernelGGL((igemm_kernel<T, BM, BN, 2>), grid, dim3(256), lds, st, p); } break;
-        }
+        launch_dma<T, BM, BN, 2, false, false>(grid, lds, st, p, src_bytes, wgt_bytes);
     }
     CS_LAUNCH_CHECK();
     return CS_OK;
@@ -1092,16 +958,13 @@ int launch_igemm(const IgemmParams& p, hipStream_t st) {
 // Tile choice: wide-N tiles when there are enough output channels; shrink BM when the grid
 // would not fill the 256 CUs.  Returns BM*1000+BN.
 int igemm_tile(long long M, int NOUT) {
-    static const int forced = cs_env_int_("CELLSEG_TILE", 0);   // experiments only
-    if (forced) return (NOUT <= 64 && forced % 1000 == 128) ? forced - 64 : forced;
-    static const int thr = cs_env_int_("CELLSEG_TILE_THR", 1536);   // experiments only (A/B: 384..3072 within 1 %, 1536 best)
+    constexpr long long thr = 1536;   // workgroups for the 128-high tile (A/B: 384..3072 within 1 %, 1536 best)
     const long long mt128 = (M + 127) / 128;
     // 64-wide tiles where they cut the padded width by a fifth or more (144 or 192 output channels: 192 instead of 256 columns): the
     // EfficientNet expansions at 150 x 150 / 75 x 75 ran their second 128-wide N tile 12 % / 50 % full -- and a workgroup's epilogue costs
     // the same however full its tile is (24 -> 144 @150x150: 244 us at 128 wide)
-    static const int narrow = cs_env_int_("CELLSEG_TILE_NARROW", 1);      // A/B experiments only (2 = off)
     const int p128 = (NOUT + 127) / 128 * 128, p64 = (NOUT + 63) / 64 * 64;
-    if (NOUT > 64 && !(narrow == 1 && p64 * 5 <= p128 * 4)) {
+    if (NOUT > 64 && p64 * 5 > p128 * 4) {
         const long long blocks = mt128 * ((NOUT + 127) / 128);
         return blocks >= thr ? 128128 : 64128;
     }
@@ -1115,9 +978,8 @@ int dispatch_igemm(const IgemmParams& p_in, float* colsum, double* stats, hipStr
     int tile = igemm_tile(p.M, p.NOUT);
     {
         // train-mode BN statistics of a launch with few pixel tiles: fp64 atomics from the epilogue, no fold launch
-        static const int atomic_rows = cs_env_int_("CELLSEG_STATS_ATOMIC_ROWS", 512);      // A/B experiments only (1 = never)
         const long long rows_ = (p.M + tile / 1000 - 1) / (tile / 1000);
-        if (p.slab && stats && !colsum && !p.cslab && !p.ncls && rows_ <= atomic_rows) p.stat_atomic = stats;
+        if (p.slab && stats && !colsum && !p.cslab && !p.ncls && rows_ <= 512) p.stat_atomic = stats;
     }
     if (p.cslab) tile = (p.M + 127) / 128 >= 384 ? 128064 : 64064;   // one 64-channel slab per N tile
     switch (tile) {
@@ -1157,10 +1019,10 @@ int check_geom(const CsConvGeom* g, int dtype) {
 extern "C" int cs_igemm_tile(long long M, int n_out) { return igemm_tile(M, n_out); }
 #ifdef CS_AB_SWITCHES
 extern "C" int cs_set_igemm_path(int path) {
-    // 0 = LDS-DMA (default), 1 = register-staged everywhere, 3 = LDS-DMA + persistent streaming kernel for short-K 1x1
-    const int old = g_igemm_path == 1 ? 1 : (g_stream_enabled ? 3 : 0);
-    g_igemm_path = path == 1 ? 1 : 0;
-    g_stream_enabled = path == 3 ? 1 : 0;
+    // 0 = LDS-DMA (default), 1 = register-staged everywhere
+    CS_CHECK_ARG(path == 0 || path == 1, "set_igemm_path: path must be 0 (LDS-DMA) or 1 (register-staged)");
+    const int old = g_igemm_path;
+    g_igemm_path = path;
     return old;
 }
 #endif
@@ -1224,7 +1086,7 @@ static int conv2d_fwd_impl(const CsConvGeom* g, int dtype, const void* x, const 
 // can the (up to) four parity classes of a stride-2 data gradient go out as ONE launch (conv2d_dgrad_impl)?  Then its partial column-sum
 // rows are numbered across the classes (IgemmParams::ClassOv::row0) and may be left unfolded like a stride-1 launch's.
 static bool strided_classes_merge(const CsConvGeom* g, int slab) {
-    if (g->stride != 2 || g->R * g->S > 64 || slab || g_igemm_path != 0 || !g_merge_classes) return false;
+    if (g->stride != 2 || g->R * g->S > 64 || slab || g_igemm_path != 0) return false;
     const unsigned long long sbytes = (unsigned long long)g->N * g->P * g->Q * g->K * 4ull;      // (fp32: the larger of the two dtypes)
     const unsigned long long wbytes = (unsigned long long)g->C * g->R * g->S * (unsigned long long)g->K * 4ull;
     return sbytes < 0x80000000ull && wbytes < 0x80000000ull;
@@ -1321,64 +1183,48 @@ static int conv2d_dgrad_impl(const CsConvGeom* g, int dtype, const void* dy, con
     // kh == (py+pad) mod s (same for kw), for which the source row is a + (py+pad-kh)/s.  Classes without
     // taps still run (zero K-steps) so that `add`/`mask` are applied and dx is fully written.
     const int sd = g->stride;
-    {
-        // stride 2: the (up to) four classes go out as ONE launch when the LDS-DMA kernel can take them -- four quarter-size
-        // launches (one of them with 4 taps, one with 1) never filled the chip and each paid its own ramp and column-sum fold
-        const unsigned long long esz = dtype == CS_F32 ? 4 : 2;
-        const unsigned long long sbytes = (unsigned long long)p.src_pixels * p.SC * esz, wbytes = (unsigned long long)p.NOUT * p.wrow_chunks * 16ull;
-        IgemmParams q = p;
-        int n = 0;
-        bool ok = sd == 2 && g_igemm_path == 0 && sbytes < 0x80000000ull && wbytes < 0x80000000ull && !slab && g_merge_classes;
-        long long max_m = 0;
-        for (int py = 0; ok && py < sd; ++py)
-            for (int px = 0; px < sd; ++px) {
-                const int kh0 = (py + g->pad) % sd, kw0 = (px + g->pad) % sd;
-                const int nj = kh0 < g->R ? (g->R - kh0 + sd - 1) / sd : 0;
-                const int ni = kw0 < g->S ? (g->S - kw0 + sd - 1) / sd : 0;
-                const int dh = (g->H - py + sd - 1) / sd, dw = (g->W - px + sd - 1) / sd;
-                if (dh <= 0 || dw <= 0) continue;
-                IgemmParams::ClassOv& c = q.cls[n++];
-                c.DH = dh; c.DW = dw;
-                c.off0 = (py + g->pad - kh0) / sd; c.off0x = (px + g->pad - kw0) / sd;
-                c.R = nj; c.S = ni;
-                if (nj == 0 || ni == 0) { c.R = 0; c.S = 1; }
-                c.wk0y = kh0; c.wk0x = kw0;
-                c.Qtot = c.R * c.S * p.SCc;
-                c.dst_oy = py; c.dst_ox = px;
-                c.M = (long long)g->N * dh * dw;
-                c.block0 = 0; c.row0 = 0;
-                if (c.M > max_m) max_m = c.M;
-            }
-        if (ok && n > 0) {
-            q.ncls = n;
-            q.div = 1; q.mul = 1; q.mulx = 1; q.sgn = -1; q.wkstep = sd; q.dst_step = sd;
-            q.R = 1; q.S = 2;                       // any tap-walking shape: the per-class values replace them in the kernel
-            q.Qtot = q.cls[0].Qtot;
-            q.M = max_m;                            // tile choice
-            return dtype == CS_F32 ? dispatch_igemm<float>(q, colsum, nullptr, st) : dispatch_igemm<bf16_t>(q, colsum, nullptr, st);
-        }
-    }
-    for (int py = 0; py < sd; ++py) {
+    std::vector<IgemmParams::ClassOv> cls;
+    long long max_m = 0;
+    for (int py = 0; py < sd; ++py)
         for (int px = 0; px < sd; ++px) {
-            IgemmParams c = p;
             const int kh0 = (py + g->pad) % sd, kw0 = (px + g->pad) % sd;
             const int nj = kh0 < g->R ? (g->R - kh0 + sd - 1) / sd : 0;
             const int ni = kw0 < g->S ? (g->S - kw0 + sd - 1) / sd : 0;
-            c.DH = (g->H - py + sd - 1) / sd;
-            c.DW = (g->W - px + sd - 1) / sd;
-            if (c.DH <= 0 || c.DW <= 0) continue;
-            c.div = 1; c.mul = 1; c.mulx = 1; c.sgn = -1;
-            c.off0 = (py + g->pad - kh0) / sd;
-            c.off0x = (px + g->pad - kw0) / sd;
+            const int dh = (g->H - py + sd - 1) / sd, dw = (g->W - px + sd - 1) / sd;
+            if (dh <= 0 || dw <= 0) continue;
+            IgemmParams::ClassOv c{};
+            c.DH = dh; c.DW = dw;
+            c.off0 = (py + g->pad - kh0) / sd; c.off0x = (px + g->pad - kw0) / sd;
             c.R = nj; c.S = ni;
             if (nj == 0 || ni == 0) { c.R = 0; c.S = 1; }
-            c.wk0y = kh0; c.wk0x = kw0; c.wkstep = sd;
-            c.Qtot = c.R * c.S * c.SCc;
-            c.dst_step = sd; c.dst_oy = py; c.dst_ox = px;
-            c.M = (long long)g->N * c.DH * c.DW;
-            const int rc2 = dtype == CS_F32 ? dispatch_igemm<float>(c, colsum, nullptr, st) : dispatch_igemm<bf16_t>(c, colsum, nullptr, st);
-            if (rc2 != CS_OK) return rc2;
+            c.wk0y = kh0; c.wk0x = kw0;
+            c.Qtot = c.R * c.S * p.SCc;
+            c.dst_oy = py; c.dst_ox = px;
+            c.M = (long long)g->N * dh * dw;
+            if (c.M > max_m) max_m = c.M;
+            cls.push_back(c);
         }
+    p.div = 1; p.mul = 1; p.mulx = 1; p.sgn = -1; p.wkstep = sd; p.dst_step = sd;
+    // stride 2: the (up to) four classes go out as ONE launch when the LDS-DMA kernel can take them -- four quarter-size
+    // launches (one of them with 4 taps, one with 1) never filled the chip and each paid its own ramp and column-sum fold
+    // (sized with the real element size, unlike strided_classes_merge's fp32 bound: a bf16 dy of 1 - 2 GiB merges here only)
+    const unsigned long long esz = dtype == CS_F32 ? 4 : 2;
+    const unsigned long long sbytes = (unsigned long long)p.src_pixels * p.SC * esz, wbytes = (unsigned long long)p.NOUT * p.wrow_chunks * 16ull;
+    if (sd == 2 && g_igemm_path == 0 && sbytes < 0x80000000ull && wbytes < 0x80000000ull && !slab && !cls.empty()) {
+        IgemmParams q = p;
+        q.ncls = (int)cls.size();
+        for (int i = 0; i < q.ncls; ++i) q.cls[i] = cls[i];
+        q.R = 1; q.S = 2;                       // any tap-walking shape: the per-class values replace them in the kernel
+        q.Qtot = q.cls[0].Qtot;
+        q.M = max_m;                            // tile choice
+        return dtype == CS_F32 ? dispatch_igemm<float>(q, colsum, nullptr, st) : dispatch_igemm<bf16_t>(q, colsum, nullptr, st);
+    }
+    for (const IgemmParams::ClassOv& k : cls) {
+        IgemmParams c = p;
+        c.DH = k.DH; c.DW = k.DW; c.off0 = k.off0; c.off0x = k.off0x; c.R = k.R; c.S = k.S;
+        c.wk0y = k.wk0y; c.wk0x = k.wk0x; c.Qtot = k.Qtot; c.dst_oy = k.dst_oy; c.dst_ox = k.dst_ox; c.M = k.M;
+        const int rc2 = dtype == CS_F32 ? dispatch_igemm<float>(c, colsum, nullptr, st) : dispatch_igemm<bf16_t>(c, colsum, nullptr, st);
+        if (rc2 != CS_OK) return rc2;
     }
     return CS_OK;
 }
@@ -2086,8 +1932,7 @@ __global__ __launch_bounds__(512) void wgrad_spec_kernel(WgradParams p, unsigned
 // every slice costs one extra write + read of the whole dW in fp32, so no more than needed to fill the chip
 int wgrad_splits(long long M, int KO, int QE, int BM, int n_items = 1) {
     const int tiles = cs_ceil_div(KO, BM) * cs_ceil_div(QE, 128) * (n_items > 1 ? n_items : 1);
-    static const int target = cs_env_int_("CELLSEG_WGRAD_BLOCKS", 512);   // experiments only
-    long long want = (target + tiles - 1) / tiles;
+    long long want = (512 + tiles - 1) / tiles;
     const long long max_split = (M + 63) / 64;
     if (want > max_split) want = max_split;
     if (want < 1) want = 1;
@@ -2095,9 +1940,6 @@ int wgrad_splits(long long M, int KO, int QE, int BM, int n_items = 1) {
     per = ((per + 31) / 32) * 32;
     return (int)((M + per - 1) / per);
 }
-
-const int g_wgrad_nst = cs_env_int_("CELLSEG_WGRAD_NST", 3);   // A/B experiments only
-const bool g_wgrad_dma = !cs_env_flag_("CELLSEG_WGRAD_REG");   // A/B experiments only
 
 template <typename T, int BM, int BN, bool TR>
 int launch_wgrad(WgradParams p, hipStream_t st, int n_items = 1) {
@@ -2118,15 +1960,9 @@ int launch_wgrad(WgradParams p, hipStream_t st, int n_items = 1) {
     if constexpr (sizeof(T) == 2 && TR && BN == 128) {
         const unsigned long long x_bytes = (unsigned long long)(p.M / ((long long)p.P * p.Q)) * p.H * p.W * p.C * 2ull;
         const unsigned long long g_bytes = (unsigned long long)p.M * p.KO * 2ull;
-        if (g_wgrad_dma && !p.slab && x_bytes < 0x80000000ull && g_bytes < 0x80000000ull) {
+        if (!p.slab && x_bytes < 0x80000000ull && g_bytes < 0x80000000ull) {
             const bool plain = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;
-#define CS_WGRAD_DMA(NST_, BKP_) \
-    do { \
-        constexpr size_t stage_ = (size_t)BKP_ * (BM + 128) * 2; \
-        note_variant("wgrad_dma_kernel<%d,%d,%s,%d>", BM, NST_, plain ? "true" : "false", BKP_); \
-        if (plain) hipLaunchKernelGGL((wgrad_dma_kernel<BM, NST_, true, BKP_>), grid, dim3(256), NST_ * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes); \
-        else hipLaunchKernelGGL((wgrad_dma_kernel<BM, NST_, false, BKP_>), grid, dim3(256), NST_ * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes); \
-    } while (0)
+            constexpr size_t stage_ = (size_t)32 * (BM + 128) * 2;
             // loader / consumer specialisation pays on the deep layers (tools/wgrad_ab.sh, 4 layers per launch: 256 -> 1024 @19x19 61 -> 52 us,
             // 2048 -> 512 @10x10 65 -> 56, strided 512 -> 1024 139 -> 107, 1024 -> 512 110 -> 93) and on the pixel-paired stem (106 -> 85 us);
             // the HBM-bound early layers (64 -> 256 @75x75: 146 vs 153 us) keep the four-wave kernel.  In the step: 1x1 family 1.113 -> 1.070 ms,
@@ -2134,18 +1970,15 @@ int launch_wgrad(WgradParams p, hipStream_t st, int n_items = 1) {
             static const int spec_knob = cs_env_int_("CELLSEG_WGRAD_SPEC", 0);
             const bool deep = BM == 128 && p.KO >= 256 && p.QE >= 256, stem = !plain && p.C <= 8;
             if (spec_knob == 1 || (spec_knob == 0 && (deep || stem))) {
-                constexpr size_t stage_ = (size_t)32 * (BM + 128) * 2;
                 note_variant("wgrad_spec_kernel<%d,%d,%s,%d>", BM, 4, plain ? "true" : "false", 32);
                 if (plain) hipLaunchKernelGGL((wgrad_spec_kernel<BM, 4, true, 32>), grid, dim3(512), 4 * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes);
                 else hipLaunchKernelGGL((wgrad_spec_kernel<BM, 4, false, 32>), grid, dim3(512), 4 * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes);
                 CS_LAUNCH_CHECK();
                 return CS_OK;
             }
-            if (g_wgrad_nst == 2) CS_WGRAD_DMA(2, 32);
-            else if (g_wgrad_nst == 4) CS_WGRAD_DMA(4, 32);
-            else if (g_wgrad_nst == 64) CS_WGRAD_DMA(2, 64);
-            else CS_WGRAD_DMA(3, 32);
-#undef CS_WGRAD_DMA
+            note_variant("wgrad_dma_kernel<%d,%d,%s,%d>", BM, 3, plain ? "true" : "false", 32);
+            if (plain) hipLaunchKernelGGL((wgrad_dma_kernel<BM, 3, true, 32>), grid, dim3(256), 3 * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes);
+            else hipLaunchKernelGGL((wgrad_dma_kernel<BM, 3, false, 32>), grid, dim3(256), 3 * stage_, st, p, (unsigned)x_bytes, (unsigned)g_bytes);
             CS_LAUNCH_CHECK();
             return CS_OK;
         }

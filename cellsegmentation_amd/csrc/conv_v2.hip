@@ -1516,9 +1516,11 @@ int pick_wide_tm(long long M, int n_ntiles, int ncc) {
 // of 96 px, each 3/4 of the work: measured 34.0 -> 29.3 us forward.  Elsewhere the shorter tile loses: layer2 (722 -> 963
 // workgroups: the same total work plus 241 more prologues, 31.9 -> 33.3 us) and layer4 (200 workgroups of 128 px, one per compute
 // unit; 64-px tiles re-read the 4.7 MB of weights twice as often and run into the L2 -> LDS feed, 33.4 -> 37.9 us).
+// The 1 x 4 ring configuration follows the same rule (tools/ring_tm_sweep.sh, profiles/round3_notes.md): a deep contraction is a
+// serial chain of NCC steps whose length hardly depends on the tile height, so shorter tiles do NOT buy back an under-filled grid
+// (2048 -> 512 @10x10, 200 tiles of 128 px on 512 resident workgroups: 26.0 us, 400 tiles of 64 px: 32.3 us); the one case that
+// wins is this one (1024 -> 256 @19x19: 28.6 -> 26.0 us).
 int pick_tm(long long M, int n_ntiles) {
-    static const int forced = cs_env_int_("CELLSEG_TM", 0);   // experiments only
-    if (forced >= 2 && forced <= 4) return forced;
     const long long wg4 = ((M + 127) / 128) * n_ntiles, wg3 = ((M + 95) / 96) * n_ntiles;
     return (wg4 > 256 && wg4 <= 512 && wg3 <= 512) ? 3 : 4;
 }
@@ -1542,10 +1544,7 @@ int pick_wide1_tm(long long M, int n_ntiles, int ncc) {
     return best_tiles <= cus ? best : 0;
 }
 
-const bool g_v2_off = cs_env_flag_("CELLSEG_NO_V2");     // A/B flavour only
-
 bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
-    if (g_v2_off) return false;
     if (g->groups > 1) return false;
     if (g->R != 3 || g->S != 3 || g->stride != 1 || g->pad < 0 || g->pad > 2) return false;
     const int SC = dgrad ? g->K : g->C, NOUT = dgrad ? g->C : g->K;
@@ -1626,7 +1625,7 @@ bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     return true;
 }
 // group count of a ring launch (a multiple of 8: one group per XCD slot): minimises rounds-of-residency x pixel tiles per workgroup;
-// 512 workgroups are resident at once.  *cost_out: that product, in pixel tiles (the unit of pick_ring_tm's comparison).
+// 512 workgroups are resident at once.  *cost_out: that product, in pixel tiles.
 unsigned ring_groups(unsigned n_mt, unsigned n_ntiles, unsigned long long* cost_out) {
     const unsigned cap = (n_mt + 7u) / 8u * 8u;
     unsigned best = 8u;
@@ -1640,21 +1639,7 @@ unsigned ring_groups(unsigned n_mt, unsigned n_ntiles, unsigned long long* cost_
     return best;
 }
 
-// Pixel-tile height of the 1 x 4 ring configuration (32 * TM pixels per workgroup tile; CELLSEG_RING_TM forces 2 / 3 / 4).  Measured per
-// shape (tools/ring_tm_sweep.sh, profiles/round3_notes.md): a deep contraction is a serial chain of NCC steps whose length hardly
-// depends on the tile height, so shorter tiles do NOT buy back an under-filled grid (2048 -> 512 @10x10, 200 tiles of 128 px on 512
-// resident workgroups: 26.0 us, 400 tiles of 64 px: 32.3 us).  The one case that wins is pick_tm's: all 128-px tiles resident but more
-// than one per compute unit somewhere, and the 96-px tiles still all resident (1024 -> 256 @19x19: 28.6 -> 26.0 us).
-int pick_ring_tm(long long M, int n_ntiles, int ncc) {
-    static const int forced = cs_env_int_("CELLSEG_RING_TM", 0);
-    if (forced >= 2 && forced <= 4) return forced;
-    (void)ncc;
-    const long long wg4 = ((M + 127) / 128) * n_ntiles, wg3 = ((M + 95) / 96) * n_ntiles;
-    return (wg4 > 256 && wg4 <= 512 && wg3 <= 512) ? 3 : 4;
-}
-
 bool plan_gemm(const CsConvGeom* g, int dgrad, C2Plan& pl) {
-    if (g_v2_off) return false;
     if (g->groups > 1) return false;
     if (g->R != 1 || g->S != 1 || g->pad != 0 || g->stride < 1) return false;
     // a STRIDED 1x1 data gradient is served in compact form: dx_compact[n][y][x] = W^T dy[n][y][x] on the P x Q grid (the values of
@@ -1669,10 +1654,7 @@ bool plan_gemm(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     if (!dgrad && g->stride > 1 && (DH < 2 || DW < 2)) return false;
     const int ncc = SC / 64;
     // (isolated, tools/conv_microbench.py shows the first-generation kernel ahead on >= 16 chunks -- 24.5 vs 29.1 us on 1024 -> 256 at
-    // 19 x 19 -- but inside the training step the ring kernel wins on the family: 3.37 vs 3.43 ms per step; CELLSEG_RING_MAX_NCC
-    // declines deeper contractions for A/B runs)
-    static const int max_ncc = cs_env_int_("CELLSEG_RING_MAX_NCC", 1 << 20);
-    if (ncc > max_ncc) return false;
+    // 19 x 19 -- but inside the training step the ring kernel wins on the family: 3.37 vs 3.43 ms per step)
     const long long M = (long long)g->N * DH * DW;
     const unsigned long long src_bytes = (unsigned long long)g->N * SH * SW * SC * 2ull;
     if (M >= (1ll << 31) - 512 || src_bytes >= 0x80000000ull) return false;
@@ -1700,7 +1682,8 @@ bool plan_gemm(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     const int BN = cfg == 6 ? 128 : 64;
     p.n_ntiles = cs_ceil_div(NOUT, BN);
     pl.cfg = cfg; pl.nbw = 0; pl.ncc = ncc;
-    pl.tm = cfg == 6 ? pick_ring_tm(M, p.n_ntiles, ncc) : 2;
+    static const int ring_tm = cs_env_int_("CELLSEG_RING_TM", 0);      // A/B flavour: 2 / 3 / 4 forces the ring tile height
+    pl.tm = cfg != 6 ? 2 : (ring_tm >= 2 && ring_tm <= 4) ? ring_tm : pick_tm(M, p.n_ntiles);
     pl.rows = cfg == 6 ? cs_ceil_div(M, 32 * pl.tm) : cs_ceil_div(M, 128) * 2;
     pl.t2d = 0;
     if (cfg == 6 && p.stride == 1 && !compact && ncc % 4 == 0) {      // (two chunks per stage, two stages per loop body)

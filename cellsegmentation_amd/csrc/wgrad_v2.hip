@@ -218,10 +218,8 @@ void magic(unsigned d, unsigned& mg, unsigned& sh) {
 
 struct W2Plan { int bl, xr; W2Params p; };
 
-const bool g_wgrad2_off = cs_env_flag_("CELLSEG_NO_WGRAD2");     // A/B experiments only
-
 bool plan(const CsConvGeom* g, int dtype, int n_items, W2Plan& pl) {
-    if (g_wgrad2_off || !g || dtype != CS_BF16) return false;
+    if (!g || dtype != CS_BF16) return false;
     if (g->groups > 1 || g->R != 3 || g->S != 3 || g->stride != 1 || g->pad != 1) return false;
     if (g->C % 64 || g->K % 64 || g->P != g->H || g->Q != g->W || n_items < 1 || n_items > 8) return false;
     const int Wp = g->W + 1, Hp = g->H + 1;
@@ -246,12 +244,11 @@ bool plan(const CsConvGeom* g, int dtype, int n_items, W2Plan& pl) {
     p.n_stages = (unsigned)((D + bl - 1) / bl);
     p.n_kt = g->K / 64; p.n_ct = g->C / 64;
     p.n_items = n_items;
-    // split the positions until ~CELLSEG_WGRAD2_BLOCKS workgroups exist; every split costs one write + read of |dW| in fp32 and
+    // split the positions until ~384 workgroups exist; every split costs one write + read of |dW| in fp32 and
     // a split should hold at least 4 stages (its first loads and its 144 stores per wave are not overlapped with anything)
     // (measured, bench.py: 256 / 384 / 512 / 768 / 1024 workgroups -> 0.643 / 0.572 / 0.596 / 0.575 / 0.578 ms per step for the family)
-    static const int target = cs_env_int_("CELLSEG_WGRAD2_BLOCKS", 384);
     const long long tiles = (long long)p.n_kt * p.n_ct * n_items;
-    long long want = (target + tiles - 1) / tiles;
+    long long want = (384 + tiles - 1) / tiles;
     const long long max_split = p.n_stages / 4 > 0 ? p.n_stages / 4 : 1;
     if (want > max_split) want = max_split;
     if (want < 1) want = 1;

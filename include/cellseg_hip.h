@@ -162,8 +162,8 @@ int cs_igemm_tile(long long M, int n_out);
 #ifdef CS_AB_SWITCHES
 /* A/B flavour only (`make AB=1` -> libcellseg_hip_ab.so; not part of the production ABI).  Staging path of the fwd/dgrad
  * kernel: 0 (default) = LDS-DMA (`buffer_load ... lds`) whenever both operands are < 2 GiB; 1 = register-staged everywhere
- * (the production rule for operands >= 2 GiB, forced here so that small test shapes reach it); 3 = LDS-DMA plus the
- * experimental persistent streaming kernel for short-K 1x1 convolutions.  Returns the previous setting. */
+ * (the production rule for operands >= 2 GiB, forced here so that small test shapes reach it).  Returns the previous setting;
+ * any other value returns CS_ERR_INVALID_ARG and leaves the setting as it was. */
 int cs_set_igemm_path(int path);
 #endif
 /* data gradient: dx = ( conv_transpose(dy, w) + add ) * [mask > 0]; add/mask nullable, both shaped like x.

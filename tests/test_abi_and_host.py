@@ -46,6 +46,19 @@ def test_production_library_reads_no_environment():
     assert "getenv" not in undefined and "secure_getenv" not in undefined
 
 
+def test_every_launch_knob_is_set_by_a_test_or_tool():
+    """A CELLSEG_* knob of the A/B flavour that no test or tool sets only keeps dead launch paths compiled."""
+    csrc = os.path.join(ROOT, "cellsegmentation_amd", "csrc")
+    knobs = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith(".hip"):
+            knobs |= set(re.findall(r'cs_env_(?:int|flag)_\("(CELLSEG_[A-Z0-9_]+)"', open(os.path.join(csrc, name)).read()))
+    users = "".join(open(os.path.join(d, f)).read() for top in ("tests", "tools") for d, _, files in os.walk(os.path.join(ROOT, top))
+                    for f in files if f.endswith((".py", ".sh")))
+    orphans = sorted(k for k in knobs if not re.search(rf"\b{k}\b", users))
+    assert knobs and not orphans, f"knobs that no test or tool sets: {orphans}"
+
+
 def test_argument_checks_without_gpu():
     """Entry points validate before launching: a bad geometry is refused with a message (no GPU needed)."""
     lib = _lib.load()

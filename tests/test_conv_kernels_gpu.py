@@ -52,10 +52,10 @@ def _relerr(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
-# The register-staged twin (the production rule for operands >= 2 GiB) and the experimental streaming kernel are reachable at test
-# sizes only through cs_set_igemm_path, which exists in the A/B flavour of the library (`make AB=1`): the children started by
-# test_wave_specialised_weight_gradient_on_every_shape run this file with CELLSEG_LIB_FLAVOUR=ab and get all three paths.
-_PATHS = ([(0, "lds_dma"), (1, "reg_staged"), (3, "lds_dma+stream")]
+# The register-staged twin (the production rule for operands >= 2 GiB) is reachable at test sizes only through cs_set_igemm_path,
+# which exists in the A/B flavour of the library (`make AB=1`): the children started by
+# test_wave_specialised_weight_gradient_on_every_shape run this file with CELLSEG_LIB_FLAVOUR=ab and get both paths.
+_PATHS = ([(0, "lds_dma"), (1, "reg_staged")]
           if os.environ.get("CELLSEG_LIB_FLAVOUR") == "ab" and os.environ.get("CELLSEG_TEST_IGEMM_PATHS", "all") == "all" else [(0, "lds_dma")])
 
 
@@ -329,7 +329,7 @@ def test_wave_specialised_weight_gradient_on_every_shape(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for mode in ("1", "2"):
-        # (the first child also walks the three staging paths of the first-generation kernels; the grandchildren of the packed file's own
+        # (the first child also walks both staging paths of the first-generation kernels; the grandchildren of the packed file's own
         # forced-mode test and its bag-size sweep are left to the parent run)
         env = dict(os.environ, CELLSEG_WGRAD_SPEC=mode, CELLSEG_LIB_FLAVOUR="ab", CELLSEG_TEST_IGEMM_PATHS="all" if mode == "1" else "dma")
         r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_conv_kernels_gpu.py"),
