@@ -141,6 +141,14 @@ _SIGNATURES = {
     "cs_evaluate_tile_counts": (c_int, [_P, _P, _P, _P, c_float, c_longlong, _P, _P]),
     "cs_paint_tile_masks": (c_int, [_P, c_longlong, _P, _P, c_int, c_int, c_int, _P, _P]),
     "cs_prune_excess": (c_int, [_P, c_longlong, c_int, c_longlong, _P, _P, _P]),
+    "cs_detect_quantize": (c_int, [_P, c_longlong, _P, _P]),
+    "cs_detect_blur": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P]),
+    "cs_stitch_workspace": (c_size_t, [c_int, c_int]),
+    "cs_stitch_patches": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "cs_detect_grid_size": (c_int, [c_int, c_int, c_int, c_int]),
+    "cs_detect_meanshift": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _P, _P, _P]),
+    "cs_detect_cluster_workspace": (c_size_t, [c_int, c_int]),
+    "cs_detect_cluster": (c_int, [_P, _P, c_int, c_int, c_double, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

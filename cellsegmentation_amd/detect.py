@@ -1,0 +1,200 @@
+"""Cell localisation from segmentation probability maps: the reference's ``meanshift_cluster`` (test_seg.py:319-365) and the
+stitching of ``cell_detect`` (test_seg.py:182-316), on the HIP path (csrc/detect.hip).
+
+Steps, each integer arithmetic or one correctly rounded fp64 operation, so the result is bit-exact and independent of launch order:
+
+* quantise   ``u8 = trunc(255 p)`` in fp32 (``np.uint8(255 * mask)`` of a float32 map, test_seg.py:225).
+* blur       ``method="gaussianblur"``: a separable integer Gaussian with BORDER_REFLECT_101.  Taps are ``rint(g_i 2^14)`` of the
+             fp64-normalised Gaussian, the centre tap absorbing the remainder so they sum to 2^14; int32 row pass, int64 column
+             pass, ``(s + 2^27) >> 28``.  This is within 1 LSB of a float64 Gaussian.  Agreement with cv2's own fixed-point 8-bit
+             path is NOT pinned (cv2 is not a dependency of this project, and its tables for ``ksize <= 7`` with ``sigma <= 0``
+             are not restated: those forms raise ``ValueError``).
+* seeds      one ``window_size`` window per ``tiles.get_tiles`` corner whose blurred centre is above ``thr * 255`` (fp64).
+* mean shift ``cv2.meanShift`` with ``TermCriteria(EPS, 0, 1e-5)``: cv2 rounds eps^2 to 0 and takes 100 iterations, so the loop
+             never stops on convergence; stopping at a fixed point gives the same window.  ``max_iter`` defaults to 100.
+* clusters   ``DBSCAN(eps, min_samples=1)``: connected components of ``dr^2 + dc^2 <= eps^2`` numbered by lowest point index;
+             centroid ``rint(mean)``; weight = blurred value under the centroid.
+* order      weight descending, then label descending (``np.argsort(w, kind="stable")[::-1]``).  The reference uses the default
+             (unstable) argsort, so among equal weights its order is unspecified; here it is fixed.
+
+``method="distancetransform"`` is not implemented.
+"""
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import kernels as K
+
+_ONE = 1 << 14
+_MAX_KSIZE = 31
+
+
+def gaussian_taps(ksize, sigma):
+    """int32 [ksize] taps summing to exactly 2^14 (host)."""
+    k = int(ksize)
+    if k != ksize or k < 1 or k % 2 == 0:
+        raise ValueError(f"ksize must be a positive odd integer, got {ksize!r}")
+    if k > _MAX_KSIZE:
+        raise ValueError(f"ksize {k} > {_MAX_KSIZE} is not supported")
+    sigma = float(sigma)
+    if sigma <= 0:
+        if k <= 7:
+            raise ValueError("sigma <= 0 with ksize <= 7 selects cv2's fixed kernel tables, which are not supported")
+        sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) / 2.0
+    g = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    g = g / g.sum()
+    t = np.rint(g * _ONE).astype(np.int64)
+    t[k // 2] += _ONE - int(t.sum())
+    return t.astype(np.int32)
+
+
+def _blur_taps(ksize, sigmaX, sigmaY=0.0):
+    try:
+        kx, ky = (int(v) for v in ksize)
+    except (TypeError, ValueError):
+        raise ValueError(f"ksize must be a pair (kx, ky), got {ksize!r}") from None
+    if kx == 0 or ky == 0:
+        raise ValueError("ksize (0, 0) (size derived from sigma) is not supported: pass odd kernel sizes")
+    sy = float(sigmaY) if sigmaY and float(sigmaY) > 0 else float(sigmaX)
+    return gaussian_taps(kx, sigmaX), gaussian_taps(ky, sy)
+
+
+def _ndim(x):
+    return x.dim() if torch.is_tensor(x) else np.ndim(x)
+
+
+def _device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_u8_maps(masks, what):
+    """uint8 numpy / torch [H,W] or [N,H,W] -> (device tensor [N,H,W], was_2d)."""
+    t = torch.from_numpy(np.ascontiguousarray(masks)) if isinstance(masks, np.ndarray) else masks
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
+    if t.dtype != torch.uint8:
+        raise TypeError(f"{what}: expected a uint8 mask (quantise probabilities first), got {t.dtype}")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
+    two_d = t.dim() == 2
+    if two_d:
+        t = t.unsqueeze(0)
+    if not t.is_cuda:
+        t = t.to(_device())
+    return t.contiguous(), two_d
+
+
+def quantize(probs):
+    """fp32 probabilities (numpy or torch, any shape) -> uint8 ``trunc(255 p)`` on the device, same shape."""
+    t = torch.from_numpy(np.ascontiguousarray(probs)) if isinstance(probs, np.ndarray) else probs
+    if t.dtype != torch.float32:
+        raise TypeError(f"quantize expects float32 probabilities, got {t.dtype}")
+    if not t.is_cuda:
+        t = t.to(_device())
+    return K.detect_quantize(t)
+
+
+def gaussian_blur(mask_u8, ksize, sigmaX, sigmaY=0):
+    """``cv2.GaussianBlur(mask, ksize, sigmaX, sigmaY)`` restated in integer arithmetic (module docstring).  mask_u8: uint8
+    [H, W] or [N, H, W] (numpy or torch); returns a uint8 device tensor of the same shape."""
+    tx, ty = _blur_taps(ksize, sigmaX, sigmaY)
+    t, two_d = _as_u8_maps(mask_u8, "gaussian_blur")
+    out = K.detect_blur(t, tx, ty)
+    return out[0] if two_d else out
+
+
+def stitch_patches(patches, images_grid, image_hw):
+    """Write patches uint8 [M, ph, pw] at upper-left corners images_grid [M, 2] (row, col) into a zeroed uint8 [H, W] mask; where
+    patches overlap the one with the highest index wins, as the reference's write order (test_seg.py:255-257)."""
+    p, _ = _as_u8_maps(patches, "stitch_patches")
+    if _ndim(patches) != 3:
+        raise ValueError("stitch_patches expects patches shaped [M, ph, pw]")
+    M, ph, pw = p.shape
+    H, W = (int(v) for v in image_hw)
+    grid = np.asarray(images_grid.cpu() if torch.is_tensor(images_grid) else images_grid, dtype=np.int64).reshape(-1, 2)
+    if len(grid) != M:
+        raise ValueError(f"{M} patches but {len(grid)} corners")
+    if M and (grid.min() < 0 or (grid[:, 0] + ph).max() > H or (grid[:, 1] + pw).max() > W):
+        raise ValueError("a patch does not lie inside the image")
+    corners = torch.from_numpy(grid.astype(np.int32)).to(p.device)
+    return K.stitch_patches(p, corners, H, W)
+
+
+@dataclass
+class DetectResult:
+    """Cells of N maps: ``points[offsets[n]:offsets[n+1]]`` (int64 (row, col)) are map n's cluster centroids ordered by ``weights``
+    (blurred value under the centroid) descending, then label descending; ``n_kept[n]`` = seed windows kept."""
+    points: np.ndarray
+    weights: np.ndarray
+    offsets: np.ndarray
+    n_kept: np.ndarray
+    cell_counts: object = None
+
+    def per_image(self):
+        """[(points[:count], points[count:])] per map, as ``meanshift_cluster`` returns; ``(points, [])`` without a count."""
+        out = []
+        for n in range(len(self.offsets) - 1):
+            pts = self.points[self.offsets[n]:self.offsets[n + 1]]
+            c = self.cell_counts
+            if c is not None and not np.isscalar(c):
+                c = c[n]
+            out.append((pts, []) if c is None else (pts[:int(c)], pts[int(c):]))
+        return out
+
+
+def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, force_global):
+    """src: device [N,H,W] uint8 masks or fp32 probabilities (quantised inside the blur)."""
+    tx, ty = _blur_taps(ksize, sigmaX, sigmaY)
+    if eps < 0 or not math.isfinite(eps):
+        raise ValueError("eps must be finite and non-negative")
+    if int(max_iter) < 0:
+        raise ValueError("max_iter must be non-negative")
+    N, H, W = src.shape
+    if K.detect_grid_size(H, W, interval, window_size) <= 0:
+        raise ValueError(f"window_size {window_size} does not fit a {H}x{W} map (or interval {interval} is not positive)")
+    blurred = K.detect_blur(src, tx, ty)
+    pts, n_pts = K.detect_meanshift(blurred, int(interval), int(window_size), float(thr) * 255.0, int(max_iter))
+    out_pts, out_w, out_off = K.detect_cluster(pts, n_pts, float(eps), blurred, force_global=force_global)
+    head = torch.cat([out_off, n_pts.to(torch.int64)]).cpu().numpy()        # the one synchronisation of the batch
+    offsets, n_kept = head[:N + 1], head[N + 1:]
+    total = int(offsets[-1])
+    points = out_pts[:total].cpu().numpy()
+    weights = out_w[:total].cpu().numpy().astype(np.int64)
+    return DetectResult(points, weights, offsets, n_kept, cell_counts)
+
+
+def detect_points(masks_u8, cell_counts=None, thr=0.2, window_size=16, interval=10, eps=15, ksize=(15, 15), sigmaX=3., sigmaY=0.,
+                  max_iter=100, _force_global=False):
+    """Blur, seed, mean-shift and cluster a batch of uint8 maps [N, H, W] (or one [H, W]) -> DetectResult.  cell_counts: None,
+    one count for every map, or one per map (applied by ``DetectResult.per_image``).  ``_force_global`` (tests) takes the
+    multi-launch clustering path at any size."""
+    _blur_taps(ksize, sigmaX, sigmaY)                                     # argument errors before any device work
+    t, _ = _as_u8_maps(masks_u8, "detect_points")
+    return _detect(t, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, _force_global)
+
+
+_BLUR_KEYS = {"ksize", "sigmaX", "sigmaY", "borderType"}
+
+
+def meanshift_cluster(mask, method, cell_count=None, thr_for_setting_points=0.2, window_size=16, interval=10, eps=15, **method_kwargs):
+    """test_seg.py:319-365 with its signature and return shape: (points[:cell_count], points[cell_count:]) with a count,
+    (points, []) without; points int64 [n, 2] (row, col).  mask: uint8 2-D numpy or torch."""
+    if method == "distancetransform":
+        raise NotImplementedError("meanshift_cluster: method 'distancetransform' is not implemented (use 'gaussianblur')")
+    if method != "gaussianblur":
+        raise ValueError("Smoothing method not found. ")
+    unknown = set(method_kwargs) - _BLUR_KEYS
+    if unknown:
+        raise TypeError(f"meanshift_cluster: unexpected GaussianBlur arguments {sorted(unknown)}")
+    if "ksize" not in method_kwargs or "sigmaX" not in method_kwargs:
+        raise TypeError("meanshift_cluster: gaussianblur needs ksize and sigmaX (as cv2.GaussianBlur)")
+    if method_kwargs.get("borderType", 4) != 4:
+        raise ValueError("meanshift_cluster: only BORDER_DEFAULT (BORDER_REFLECT_101) is supported")
+    if _ndim(mask) != 2:
+        raise ValueError("meanshift_cluster expects a 2-D mask")
+    res = detect_points(mask, cell_counts=cell_count, thr=thr_for_setting_points, window_size=window_size, interval=interval, eps=eps,
+                        ksize=method_kwargs["ksize"], sigmaX=method_kwargs["sigmaX"], sigmaY=method_kwargs.get("sigmaY", 0))
+    return res.per_image()[0]

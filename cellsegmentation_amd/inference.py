@@ -141,3 +141,31 @@ def inference_seg(loader, model, device, mode='train'):
                 output = K.softmax_channel_fwd(output.contiguous(), 1)
             masks.append(output.cpu().numpy())
     return np.concatenate(masks)
+
+
+def detect_cells(loader, model, device, eps=11, reg_limit=False, **blur):
+    """Cell locations per image (test_seg.py cell_detect + meanshift_cluster, one map per image): segment-mode forward, softmax
+    channel 1, quantise, then detect.detect_points with the remaining keyword arguments (thr, window_size, interval, ksize, sigmaX,
+    ...).  With reg_limit the image-mode count rint(reg) caps each image's list (test_seg.py:217-221; the model is set back to
+    segment mode afterwards).  Returns [(points, discarded)] per image, as meanshift_cluster."""
+    from . import detect as D
+    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
+    if unknown:
+        raise TypeError(f"detect_cells: unexpected arguments {sorted(unknown)}")
+    opts = {"ksize": (15, 15), "sigmaX": 3.}
+    opts.update(blur)
+    model.eval()
+    out = []
+    with torch.no_grad():
+        for i, data in enumerate(tqdm(loader, desc="cell detecting")):
+            x = data.to(device)
+            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+            counts = None
+            if reg_limit:
+                model.setmode("image")
+                counts = np.round(model(x)[1].detach()[:, 0].float().cpu().numpy()).astype(int)
+                model.setmode("segment")
+            res = D._detect(probs, counts, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10), eps, opts["ksize"],
+                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False)
+            out.extend(res.per_image())
+    return out

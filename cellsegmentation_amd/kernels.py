@@ -1041,3 +1041,76 @@ def prune_excess(labels, flag, n_excess):
     cnt = torch.zeros((1,), dtype=torch.int64, device=labels.device)
     _lib.check(_lib.load().cs_prune_excess(_p(labels), n, int(flag), int(n_excess), _p(kept), _p(cnt), _stream()), "prune_excess")
     return kept, cnt
+
+
+# ---------------------------------------------------------------- cell localisation (csrc/detect.hip; detect.py is the public API)
+def _aligned16(t):
+    """contiguous and 16-byte aligned (a view into the middle of a buffer may not be)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def detect_quantize(probs):
+    """fp32 probabilities of any shape -> uint8 trunc(255 p), same shape."""
+    p = _aligned16(probs)
+    out = torch.empty(p.shape, dtype=torch.uint8, device=p.device)
+    if p.numel():
+        _lib.check(_lib.load().cs_detect_quantize(_p(p), p.numel(), _p(out), _stream()), "detect_quantize")
+    return out
+
+
+def detect_blur(src, taps_x, taps_y):
+    """src [N,H,W] uint8 or fp32 probabilities (quantised on the way in) -> uint8 [N,H,W]; taps: host int sequences."""
+    N, H, W = src.shape
+    s = _aligned16(src)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=s.device)
+    tx = (ctypes.c_int32 * len(taps_x))(*[int(v) for v in taps_x])
+    ty = (ctypes.c_int32 * len(taps_y))(*[int(v) for v in taps_y])
+    _lib.check(_lib.load().cs_detect_blur(_p(s), int(s.dtype == torch.float32), N, H, W, tx, len(taps_x), ty, len(taps_y), _p(out), _stream()),
+               "detect_blur")
+    return out
+
+
+def stitch_patches(patches, corners, H, W):
+    """patches uint8 [M,ph,pw], corners int32 [M,2] (device) -> uint8 [H,W], the highest patch index winning overlaps."""
+    M, ph, pw = patches.shape
+    lib = _lib.load()
+    ws_bytes = lib.cs_stitch_workspace(H, W)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=patches.device)
+    out = torch.empty((H, W), dtype=torch.uint8, device=patches.device)
+    _lib.check(lib.cs_stitch_patches(_p(patches.contiguous()) if M else None, M, ph, pw, _p(corners.contiguous()) if M else None, H, W, _p(out),
+                                     _p(ws), ws_bytes, _stream()), "stitch_patches")
+    return out
+
+
+def detect_grid_size(H, W, interval, window):
+    return _lib.load().cs_detect_grid_size(int(H), int(W), int(interval), int(window))
+
+
+def detect_meanshift(blurred, interval, window, thr255, max_iter):
+    """blurred uint8 [N,H,W] -> (pts int32 [N,G,2] final window centres, n_pts int32 [N] windows kept per map)."""
+    N, H, W = blurred.shape
+    G = detect_grid_size(H, W, interval, window)
+    if G <= 0:
+        raise ValueError(f"window {window} does not fit a {H}x{W} map (or interval {interval} is not positive)")
+    pts = torch.empty((N, G, 2), dtype=torch.int32, device=blurred.device)
+    n_pts = torch.empty((N,), dtype=torch.int32, device=blurred.device)
+    _lib.check(_lib.load().cs_detect_meanshift(_p(blurred.contiguous()), N, H, W, int(interval), int(window), float(thr255), int(max_iter), _p(pts),
+                                               _p(n_pts), _stream()), "detect_meanshift")
+    return pts, n_pts
+
+
+def detect_cluster(pts, n_pts, eps, blurred, force_global=False):
+    """pts int32 [N,cap,2], n_pts int32 [N] -> (points int64 [N cap,2], weights int32 [N cap], offsets int64 [N+1]) on the device;
+    the clusters of map n are rows offsets[n]:offsets[n+1]."""
+    N, cap, _ = pts.shape
+    _, H, W = blurred.shape
+    lib = _lib.load()
+    ws_bytes = lib.cs_detect_cluster_workspace(N, cap)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=pts.device)
+    out_pts = torch.empty((N * cap, 2), dtype=torch.int64, device=pts.device)
+    out_w = torch.empty((N * cap,), dtype=torch.int32, device=pts.device)
+    out_off = torch.empty((N + 1,), dtype=torch.int64, device=pts.device)
+    _lib.check(lib.cs_detect_cluster(_p(pts.contiguous()), _p(n_pts.contiguous()), N, cap, float(eps), _p(blurred.contiguous()), H, W,
+                                     int(bool(force_global)), _p(out_pts), _p(out_w), _p(out_off), _p(ws), ws_bytes, _stream()), "detect_cluster")
+    return out_pts, out_w, out_off

@@ -474,6 +474,41 @@ int cs_paint_tile_masks(const int64_t* selected, long long n_selected, const int
 int cs_prune_excess(const int32_t* labels, long long n, int flag, long long n_excess, int64_t* kept, int64_t* kept_count,
                     void* stream);
 
+/* ---- cell localisation from segmentation probability maps (test_seg.py meanshift_cluster / cell_detect; csrc/detect.hip) ----
+ * Every step is integer arithmetic or one correctly rounded fp64 operation: bit-exact and independent of launch order.
+ * cs_detect_quantize : out[i] = (uint8) trunc(255.0f * probs[i]) (fp32, clamped to [0, 255]); probs 16-byte aligned.
+ * cs_detect_blur     : separable integer Gaussian of N maps [N][H][W], BORDER_REFLECT_101.  src is fp32 probabilities
+ *                      (src_is_f32 = 1: quantised as above on the way in) or uint8; taps_x[kx], taps_y[ky] (host arrays) are
+ *                      odd counts <= 31 of non-negative integers summing to 2^14.  Row pass int32, column pass int64,
+ *                      dst = (s + 2^27) >> 28.  src and dst 16-byte aligned.
+ * cs_stitch_patches  : out[H][W] = 0, then patch m (patches[M][ph][pw]) written at corners[m] = (row, col) (device int32
+ *                      [M][2]), the highest m winning where patches overlap (clipped at the borders);
+ *                      workspace >= cs_stitch_workspace(H, W) bytes.
+ * cs_detect_grid_size: number G of windows of get_tiles((H, W), interval, window) (-1 when the window does not fit).
+ * cs_detect_meanshift: per map n, the grid windows whose blurred centre is above thr255 (fp64 compare), in grid order, each run
+ *                      through cv2.meanShift (TermCriteria(EPS, 0, 1e-5): max_iter steps, stopping early at a fixed point);
+ *                      pts[n][k] = (row, col) of the final window centre (int32 [N][G][2]), n_pts[n] = windows kept.
+ * cs_detect_cluster  : DBSCAN(eps, min_samples=1) of pts[n][0..n_pts[n]) (int32 [N][cap][2], n_pts[n] <= cap): components of
+ *                      dr^2 + dc^2 <= eps^2, numbered by lowest point index; centroid = rint(mean); weight =
+ *                      blurred[n][centroid] (uint8 [N][H][W]); clusters of map n ordered by weight descending, then label
+ *                      descending, written to out_pts[out_off[n] ..) (int64 [N cap][2]) and out_w (int32 [N cap]);
+ *                      out_off int64 [N + 1].  Up to 2048 points per map are clustered inside one workgroup; larger maps (or
+ *                      force_global) take a multi-launch path that reads one flag back per eight rounds (the host
+ *                      synchronises with the stream there).  workspace >= cs_detect_cluster_workspace(N, cap) bytes. */
+int cs_detect_quantize(const float* probs, long long n, uint8_t* out, void* stream);
+int cs_detect_blur(const void* src, int src_is_f32, int N, int H, int W, const int32_t* taps_x, int kx, const int32_t* taps_y, int ky,
+                   uint8_t* dst, void* stream);
+size_t cs_stitch_workspace(int H, int W);
+int cs_stitch_patches(const uint8_t* patches, int M, int ph, int pw, const int32_t* corners, int H, int W, uint8_t* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int cs_detect_grid_size(int H, int W, int interval, int window);
+int cs_detect_meanshift(const uint8_t* blurred, int N, int H, int W, int interval, int window, double thr255, int max_iter,
+                        int32_t* pts, int32_t* n_pts, void* stream);
+size_t cs_detect_cluster_workspace(int N, int cap);
+int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N, int cap, double eps, const uint8_t* blurred, int H, int W,
+                      int force_global, int64_t* out_pts, int32_t* out_w, int64_t* out_off, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
