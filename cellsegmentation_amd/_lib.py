@@ -11,8 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CELLSEG_LIB_FLAVOUR=ab: the A/B build (`make AB=1`: launch-rule knobs read from CELLSEG_* and cs_set_igemm_path compiled in).
 # Only the forced-mode tests and the tools/ sweeps set it, in child processes; the product loads the production library.
 FLAVOUR = os.environ.get("CELLSEG_LIB_FLAVOUR", "")
-if FLAVOUR not in ("", "ab", "dbg"):
-    raise RuntimeError(f"CELLSEG_LIB_FLAVOUR={FLAVOUR!r}: expected unset, 'ab' or 'dbg' (`make DEBUG=1`: A/B switches + s_memtime stamps)")
+if FLAVOUR not in ("", "ab"):
+    raise RuntimeError(f"CELLSEG_LIB_FLAVOUR={FLAVOUR!r}: expected unset or 'ab'")
 LIB_PATH = os.path.join(_HERE, f"libcellseg_hip_{FLAVOUR}.so" if FLAVOUR else "libcellseg_hip.so")
 
 CS_F32, CS_BF16 = 0, 1
@@ -177,7 +177,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch, intentionally fatal
         fn.restype = restype
         fn.argtypes = argtypes
-    if FLAVOUR in ("ab", "dbg"):
+    if FLAVOUR == "ab":
         for name, (restype, argtypes) in _AB_SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype = restype

@@ -61,9 +61,6 @@ struct C2Params {
     unsigned src_bytes;
     unsigned pix_bytes;            // SC * 2
     unsigned wpk_bytes;            // whole packed weight tensor (the range check of a raw buffer covers voffset + soffset)
-#ifdef CS_DEBUG_V2
-    unsigned long long* dbg;       // diagnostic build only: s_memtime stamps [workgroup][wave][6]
-#endif
 };
 
 // n / d for n < 2^31, d >= 2: q = umulhi(n, mg) >> sh with mg = floor(2^(31+l) / d) + 1, sh = l - 1, l = ceil(log2 d)
@@ -186,9 +183,6 @@ template <int REG> __device__ __forceinline__ float vget() {
 }
 template <int I, int... Rs> __device__ __forceinline__ void acc_tile(f32x16& out, std::integer_sequence<int, Rs...>) {
     ((out[Rs] = vget<R_ACC + 16 * I + Rs>()), ...);
-}
-template <int BASE, int... Rs> __device__ __forceinline__ void dbg_tile(f32x16& out, std::integer_sequence<int, Rs...>) {
-    ((out[Rs] = vget<BASE + Rs>()), ...);
 }
 
 // One tap-step of a TM x (32 px x 32 ch) wave tile: 4*TM MFMA and 4*TM ds_read_b128, software-pipelined over the two fragment
@@ -377,6 +371,91 @@ __device__ __forceinline__ uint4 keep_bits8(const uint4& o, unsigned b) {
     return make_uint4(wds[0], wds[1], wds[2], wds[3]);
 }
 
+// ---- arithmetic shared by Epilogue (halo and wide kernels) and RingEpilogue (ring kernel).  What differs stays in the structs: LDS
+// addressing, how the residual arrives, the ring's fixed number of memory operations per epilogue, finish().
+// Row arrangement: o0 / o1 = piece `piece` of pixel 0 / 1 of the lane's quad.  compact_add_off and load_shift are written out in one
+// of the two structs each (Epilogue::res_off, RingEpilogue::prefetch): called there, they change the compiled prologue.
+
+// compact strided add operand of a data gradient (add_stride = 2): byte offset of the row destination pixel m adds -- the row of pixel
+// (y / 2, x / 2) when both coordinates are even, nothing otherwise
+__device__ __forceinline__ unsigned compact_add_off(const C2Params& p, unsigned m, unsigned n_w, unsigned piece) {
+    const unsigned yall = udivm(m, p.mg_dw, p.sh_dw);
+    const unsigned x = m - yall * (unsigned)p.DW;
+    const unsigned n = udivm(yall, p.mg_dh, p.sh_dh);
+    const unsigned y = yall - n * (unsigned)p.DH;
+    const unsigned mc = (n * (unsigned)p.AH + (y >> 1)) * (unsigned)p.AW + (x >> 1);
+    return (m < p.M && !((x | y) & 1u)) ? (mc * (unsigned)p.NOUT + n_w + 8u * piece) * 2u : OOB;
+}
+// the shift of accumulator register r (channel n_w + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)); zeros for a data gradient, without a
+// shift vector and in a wave past the channels
+template <bool DG> __device__ __forceinline__ void load_shift(const C2Params& p, int n_w, bool alive, float (&sh)[16]) {
+    const int lane = threadIdx.x & 63;
+    const int hh = lane >> 5;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!DG && p.shift && alive) s = *reinterpret_cast<const float4*>(p.shift + n_w + 8 * g + 4 * hh);
+        sh[4 * g] = s.x; sh[4 * g + 1] = s.y; sh[4 * g + 2] = s.z; sh[4 * g + 3] = s.w;
+    }
+}
+// residual / add operand words in stored arrangement, as read at the lane's two accumulator-arrangement slots: into accumulator
+// arrangement (the swap is an involution) and added to the values of the tile
+__device__ __forceinline__ void add_residual(float (&v)[16], uint4 xa, uint4 xb) {
+    swap32(xa.x, xa.z); swap32(xa.y, xa.w);
+    swap32(xb.x, xb.z); swap32(xb.y, xb.w);
+    const unsigned rw[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float lo, hi;
+        unpack2(rw[k], lo, hi);
+        v[2 * k] += lo;
+        v[2 * k + 1] += hi;
+    }
+}
+// the values of the tile -> 8 packed dwords in store order: bf16, ReLU, groups (0,1) and (2,3) swapped so that lanes 0-31 hold
+// channels 16j .. 16j+7 and lanes 32-63 channels 16j+8 .. 16j+15
+__device__ __forceinline__ void pack_tile(const float (&v)[16], bool relu, unsigned (&pk)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) pk[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
+    if (relu) {          // on the packed pairs: 8 instructions instead of 32 (cs_common.h relu_bf16x2)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pk[k] = relu_bf16x2(pk[k]);
+    }
+    swap32(pk[0], pk[2]); swap32(pk[1], pk[3]);
+    swap32(pk[4], pk[6]); swap32(pk[5], pk[7]);
+}
+// the elements whose mask bit is clear become 0; mw: lane q of the quad holds the mask dword of pixel q
+__device__ __forceinline__ void apply_mask(uint4& o0, uint4& o1, unsigned mw, unsigned piece) {
+    const unsigned w0 = quad<0x00>(mw), w1 = quad<0x55>(mw);       // broadcast lane 0 / lane 1 of the quad
+    o0 = keep_bits8(o0, w0 >> (8u * piece));
+    o1 = keep_bits8(o1, w1 >> (8u * piece));
+}
+// column sums: s1[2c], s1[2c + 1] += the channel pairs of dword c of both pixels
+__device__ __forceinline__ void add_col_sums(float (&s1)[8], const uint4& o0, const uint4& o1) {
+    const unsigned ow[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float lo, hi;
+        unpack2(ow[k], lo, hi);
+        s1[2 * (k & 3)] += lo; s1[2 * (k & 3) + 1] += hi;
+    }
+}
+// bit-plane dwords of pixel 0 / 1 of the quad, in every lane of it: byte j of a pixel's dword = channels 8j .. 8j+7 = piece j, OR-ed over
+// the quad; lane q (piece q) stores pixel q's dword
+__device__ __forceinline__ void plane_dwords(const uint4& o0, const uint4& o1, bool relu, unsigned piece, unsigned& w0, unsigned& w1) {
+    w0 = (relu ? nz_bits8(o0) : pos_bits8(o0)) << (8u * piece), w1 = (relu ? nz_bits8(o1) : pos_bits8(o1)) << (8u * piece);
+    w0 |= quad<0xb1>(w0); w1 |= quad<0xb1>(w1);       // [1,0,3,2]
+    w0 |= quad<0x4e>(w0); w1 |= quad<0x4e>(w1);       // [2,3,0,1]
+}
+// workgroup -> (pixel tile, channel tile) in XCD-aware order: id = 8 * slot + xcd, all channel tiles of one pixel tile back to back on one
+// XCD (conv_igemm.hip).  n_w: first of the 32 channels of wave column wn of a BN-channel tile, a separate call so that the halo and wide
+// kernels compute it only after their early return.
+struct WgTile {
+    unsigned slot, mtile;
+    __device__ __forceinline__ explicit WgTile(const C2Params& p) : slot(blockIdx.x >> 3), mtile((slot / (unsigned)p.n_ntiles) * 8u + (blockIdx.x & 7u)) {}
+    __device__ __forceinline__ int n_w(const C2Params& p, int BN, int wn) const { return (int)(slot % (unsigned)p.n_ntiles) * BN + wn * 32; }
+};
+
 template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue {
     const C2Params& p;
     unsigned m0w, slab_row;
@@ -387,14 +466,6 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
     uint4 rr[TM][2];           // residual / add in row arrangement
     unsigned mb[TM];           // mask words: lanes with piece 0 / 1 hold the dword of pixel q = 0 / 1
     float s1[8];
-#ifdef CS_DEBUG_V2
-    unsigned long long e_acc[4] = {0, 0, 0, 0}, e_t = 0;
-#define CS_ETICK(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); e_acc[k] += t_ - e_t; e_t = t_; } while (0)
-#define CS_ESTART() asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(e_t))
-#else
-#define CS_ETICK(k)
-#define CS_ESTART()
-#endif
     __amdgpu_buffer_rsrc_t r_dst, r_res, r_bin, r_bout;
 
     __device__ __forceinline__ Epilogue(const C2Params& p_, unsigned m0w_, int n_w_, unsigned slab_row_, bool alive_, unsigned scr_)
@@ -410,9 +481,9 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
         return scr + (unsigned)(lane & 31) * EPI_ROW + (unsigned)(2 * j + (lane >> 5)) * 16u;
     }
 
-    // byte offset of the residual / add operand's row for (32-pixel tile i, half q): the destination row itself, or -- compact strided
-    // operand of a data gradient (add_stride = 2, see RingEpilogue::add_off; the wide kernel's 1x1 form serves such layers too) -- the
-    // row of pixel (y / 2, x / 2) when both coordinates are even, nothing otherwise
+    // byte offset of the residual / add operand's row for (32-pixel tile i, half q): the destination row itself, or the compact strided
+    // operand of a data gradient (the wide kernel's 1x1 form serves such layers too).  compact_add_off written out: called here, it
+    // re-associates the address arithmetic of the halo and wide kernels' prologue
     __device__ __forceinline__ unsigned res_off(int i, int q) const {
         if constexpr (TO::kPreset) return to.row(p.M, (unsigned)p.NOUT, i, q);
         else {
@@ -430,7 +501,6 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
 
     __device__ __forceinline__ void prefetch() {
         const int lane = threadIdx.x & 63;
-        const int hh = lane >> 5;
         const unsigned out_bytes = p.M * (unsigned)p.NOUT * 2u;
         if constexpr (!TO::kPreset) to.set(m0w, alive, (unsigned)p.NOUT, (unsigned)n_w, (unsigned)(lane & 3), p.M);
         r_dst = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, out_bytes, 0x00020000);
@@ -438,12 +508,7 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
                                                   !p.residual ? 0u : p.add_stride == 2 ? (unsigned)(p.NS * p.AH * p.AW * p.NOUT) * 2u : out_bytes, 0x00020000);
         r_bin = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.bits_in), 0, p.bits_in ? out_bytes >> 4 : 0u, 0x00020000);
         r_bout = __builtin_amdgcn_make_buffer_rsrc(p.bits_out, 0, p.bits_out ? out_bytes >> 4 : 0u, 0x00020000);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!DG && p.shift && alive) s = *reinterpret_cast<const float4*>(p.shift + n_w + 8 * g + 4 * hh);
-            sh[4 * g] = s.x; sh[4 * g + 1] = s.y; sh[4 * g + 2] = s.z; sh[4 * g + 3] = s.w;
-        }
+        load_shift<DG>(p, n_w, alive, sh);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             // a NULL operand has a zero-sized buffer: the loads return zeros without touching memory
@@ -458,7 +523,6 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
     template <int I> __device__ __forceinline__ void operator()(const f32x16& acc) {
         const int lane = threadIdx.x & 63;
         const unsigned piece = (unsigned)(lane & 3);
-        CS_ESTART();
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = DG ? acc[r] : acc[r] + sh[r];
@@ -472,42 +536,19 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
             lds_put(row_lds(0), x0);
             lds_put(row_lds(1), x1);
             __builtin_amdgcn_wave_barrier();
-            uint4 xa = lds_get(acc_lds(0)), xb = lds_get(acc_lds(1));
+            const uint4 xa = lds_get(acc_lds(0)), xb = lds_get(acc_lds(1));
             __builtin_amdgcn_wave_barrier();
-            // stored arrangement -> accumulator arrangement (the swap is an involution)
-            swap32(xa.x, xa.z); swap32(xa.y, xa.w);
-            swap32(xb.x, xb.z); swap32(xb.y, xb.w);
-            const unsigned rw[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                float lo, hi;
-                unpack2(rw[k], lo, hi);
-                v[2 * k] += lo;
-                v[2 * k + 1] += hi;
-            }
+            add_residual(v, xa, xb);
         }
         unsigned pk[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pk[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-        if (!DG && p.act == CS_ACT_RELU) {          // on the packed pairs: 8 instructions instead of 32 (cs_common.h relu_bf16x2)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) pk[k] = relu_bf16x2(pk[k]);
-        }
-        // groups (0,1) and (2,3): after the swaps lanes 0-31 hold channels 16j .. 16j+7, lanes 32-63 channels 16j+8 .. 16j+15
-        swap32(pk[0], pk[2]); swap32(pk[1], pk[3]);
-        swap32(pk[4], pk[6]); swap32(pk[5], pk[7]);
+        pack_tile(v, !DG && p.act == CS_ACT_RELU, pk);
         lds_put(acc_lds(0), make_uint4(pk[0], pk[1], pk[2], pk[3]));
         lds_put(acc_lds(1), make_uint4(pk[4], pk[5], pk[6], pk[7]));
         __builtin_amdgcn_wave_barrier();
         uint4 o0 = lds_get(row_lds(0)), o1 = lds_get(row_lds(1));
         __builtin_amdgcn_wave_barrier();
-        CS_ETICK(0);
         if constexpr (DG) {
-            if (p.bits_in) {
-                const unsigned w0 = quad<0x00>(mb[I]), w1 = quad<0x55>(mb[I]);       // broadcast lane 0 / lane 1 of the quad
-                o0 = keep_bits8(o0, w0 >> (8u * piece));
-                o1 = keep_bits8(o1, w1 >> (8u * piece));
-            }
+            if (p.bits_in) apply_mask(o0, o1, mb[I], piece);
             if constexpr (I == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) s1[k] = 0.f;
@@ -515,28 +556,16 @@ template <int TM, bool PRE_RES, bool DG, typename TO = TileOffs> struct Epilogue
             if (p.slab) {                      // statistics are those of the STORED values; rows that are not stored count as zeros
                 if (to.row(p.M, (unsigned)p.NOUT, I, 0) == OOB) o0 = make_uint4(0u, 0u, 0u, 0u);
                 if (to.row(p.M, (unsigned)p.NOUT, I, 1) == OOB) o1 = make_uint4(0u, 0u, 0u, 0u);
-                const unsigned ow[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    float lo, hi;
-                    unpack2(ow[k], lo, hi);
-                    s1[2 * (k & 3)] += lo; s1[2 * (k & 3) + 1] += hi;
-                }
+                add_col_sums(s1, o0, o1);
             }
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), r_dst, to.row(p.M, (unsigned)p.NOUT, I, 0), 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), r_dst, to.row(p.M, (unsigned)p.NOUT, I, 1), 0, 0);
-        CS_ETICK(1);
         if (!DG && p.bits_out) {
-            // byte j of a pixel's dword = channels 8j .. 8j+7 = piece j; OR over the quad, then lane (piece q) stores pixel q's dword
-            const bool relu = p.act == CS_ACT_RELU;
-            unsigned w0 = (relu ? nz_bits8(o0) : pos_bits8(o0)) << (8u * piece), w1 = (relu ? nz_bits8(o1) : pos_bits8(o1)) << (8u * piece);
-            w0 |= quad<0xb1>(w0); w1 |= quad<0xb1>(w1);       // [1,0,3,2]
-            w0 |= quad<0x4e>(w0); w1 |= quad<0x4e>(w1);       // [2,3,0,1]
+            unsigned w0, w1;
+            plane_dwords(o0, o1, p.act == CS_ACT_RELU, piece, w0, w1);
             __builtin_amdgcn_raw_buffer_store_b32((lane & 1) ? w1 : w0, r_bout, to.bit(p.M, (unsigned)p.NOUT, I), 0, 0);
         }
-        CS_ETICK(2);
-        CS_ETICK(3);
     }
 
     __device__ __forceinline__ void finish() {
@@ -575,22 +604,11 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(50))) void c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, hh = lane >> 5;
-#ifdef CS_DEBUG_V2
-    unsigned long long t_stamp[6];
-#define CS_STAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_stamp[i]))
-    CS_STAMP(0);
-#else
-#define CS_STAMP(i)
-#endif
 
-    // XCD-aware tile order: id = 8*slot + xcd, all N tiles of one M tile back to back on one XCD (conv_igemm.hip)
-    const unsigned bid = blockIdx.x;
-    const unsigned slot = bid >> 3;
-    const unsigned mtile = (slot / (unsigned)p.n_ntiles) * 8u + (bid & 7u);
-    const unsigned m0 = mtile * BM;
+    const WgTile wg(p);
+    const unsigned mtile = wg.mtile, m0 = mtile * BM;
     if (T2D ? mtile >= p.n_tiles : m0 >= p.M) return;
-    const int n0 = (int)(slot % (unsigned)p.n_ntiles) * BN;
-    const int n_w = n0 + wn * 32;
+    const int n_w = wg.n_w(p, BN, wn);
     const bool alive = n_w < p.NOUT;
 
     using TOffs = std::conditional_t<T2D, TileOffs2D<TM>, TileOffs>;
@@ -658,7 +676,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(50))) void c
 
     static_assert(TM >= 2 && TM <= 4, "the register map of the main loop holds up to 4 pixel tiles per wave");
     epi.prefetch();
-    CS_STAMP(4);
     own_registers();
     vzero_seq(std::make_integer_sequence<int, 16 * TM>{});
     const unsigned hhb = (unsigned)hh * 256u;
@@ -671,7 +688,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(50))) void c
     bload4<1>(rsrc_b, bvoff, wsoff); wsoff += 4096u;
     wait_vm<8>();
     raw_barrier();
-    CS_STAMP(1);
 
     unsigned nxt_soff = 128u;                    // channel offset (bytes) of the chunk being fetched
 
@@ -720,17 +736,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(50))) void c
             }
         }
     }
-    CS_STAMP(2);
     epi.finish();
-#ifdef CS_DEBUG_V2
-    CS_STAMP(3);
-    asm volatile("s_waitcnt vmcnt(0)");
-    CS_STAMP(5);
-    if (p.dbg && lane == 0) {
-        unsigned long long* o = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 6;
-        o[0] = t_stamp[0]; o[1] = t_stamp[4]; o[2] = t_stamp[1]; o[3] = t_stamp[2]; o[4] = t_stamp[3]; o[5] = t_stamp[5];
-    }
-#endif
 }
 
 
@@ -849,14 +855,10 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
 
-    // XCD-aware tile order: id = 8*slot + xcd, all channel tiles of one pixel tile back to back on one XCD
-    const unsigned bid = blockIdx.x;
-    const unsigned slot = bid >> 3;
-    const unsigned mtile = (slot / (unsigned)p.n_ntiles) * 8u + (bid & 7u);
-    const unsigned m0 = mtile * BM;
+    const WgTile wg(p);
+    const unsigned mtile = wg.mtile, m0 = mtile * BM;
     if (m0 >= p.M) return;
-    const int n0 = (int)(slot % (unsigned)p.n_ntiles) * BN;
-    const int n_w = n0 + wave * 32;
+    const int n_w = wg.n_w(p, BN, wave);
     const bool alive = n_w < p.NOUT;
 
     Epilogue<TM, false, DG, TileOffs> epi(p, m0, n_w, mtile, alive, 0u);
@@ -910,16 +912,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
     const unsigned smem_base = lds_off(smem);
     const int NSTAGE = NTAP == 9 ? p.NCC : p.NCC / 2;
 
-#ifdef CS_DEBUG_V2
-    // diagnostic build: shader-clock stamps around the phases + the constant 100 MHz counter at both ends (in-kernel clock =
-    // delta s_memtime / delta s_memrealtime x 100 MHz); marker 3 = wide kernel (tools/stamp_probe.py)
-    unsigned long long w_t[4], w_rt[2];
-#define CS_WSTAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w_t[i]))
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w_rt[0]));
-    CS_WSTAMP(0);
-#else
-#define CS_WSTAMP(i)
-#endif
     epi.prefetch();
     asm volatile("; v[100:255] and a[128:255] are owned by the main loop" ::: "v100", "v255", "a128", "a255");
     for_n<16 * TM>([&]<int r>() { azero<W_ACC + r>(); });
@@ -932,7 +924,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
         for_n<NSLOT - 1>([&]<int k>() { bload1<k>(rsrc_b, bvoff, wsoff); wsoff += 1024u; });
         wait_vm<NSLOT - 1>();
         raw_barrier();
-        CS_WSTAMP(1);
 
         for (int cc = 0; cc < NSTAGE; ++cc) {
             const unsigned cur = (cc & 1) ? STAGE : 0u, nxt = STAGE - cur;
@@ -978,7 +969,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
         });
         wait_vm<16 + NBW>();
         raw_barrier();
-        CS_WSTAMP(1);
         unsigned cur = 0u, dst = 2u * STAGE;             // LDS stage being multiplied / being filled (two stages ahead)
         auto stage = [&]<int NB>(int cc) {
             const unsigned hhs = (unsigned)hh * 256u + cur;
@@ -1008,21 +998,12 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
     }
     // MFMA results -> VALU reads: the last MFMA needs its 16 passes (no hardware interlock on this path)
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 7");
-    CS_WSTAMP(2);
     for_n<TM>([&]<int i>() {
         const f32x16 d = acc_read_w<i>();
         epi.template operator()<i>(d);
     });
     epi.finish();
     wait_vm<0>();                     // the out-of-range tail loads are gone before the registers / LDS are released
-#ifdef CS_DEBUG_V2
-    CS_WSTAMP(3);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w_rt[1]));
-    if (p.dbg && lane == 0) {
-        unsigned long long* o = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 6;
-        o[0] = 3; o[1] = w_t[1] - w_t[0]; o[2] = w_t[2] - w_t[1]; o[3] = w_t[3] - w_t[2]; o[4] = w_t[3] - w_t[0]; o[5] = w_rt[1] - w_rt[0];
-    }
-#endif
 }
 
 // =================================================================================================
@@ -1064,9 +1045,6 @@ template <int TM, bool DG> struct RingEpilogue {
     float s1[8];
     i32x4 q_res, q_bin;
     __amdgpu_buffer_rsrc_t r_dst, r_bout, r_slab;
-#ifdef CS_DEBUG_V2
-    unsigned long long e_acc[4] = {0, 0, 0, 0}, e_t = 0;
-#endif
 
     __device__ __forceinline__ RingEpilogue(const C2Params& p_, int n_w_, bool alive_, unsigned region_) : p(p_), n_w(n_w_), alive(alive_), region(region_) {}
 
@@ -1088,19 +1066,12 @@ template <int TM, bool DG> struct RingEpilogue {
         return region + (unsigned)i * 2048u + l31 * 64u + (((2u * j + (lane >> 5)) ^ ((l31 >> 2) & 3u)) * 16u);
     }
 
-    // residual / add rows (and mask words) of 32-pixel tile I of the pixel tile that starts at `base`: fly from now on
-    // byte offset of the add operand's row for (32-pixel tile i, half q): the destination row itself, or -- compact strided operand --
-    // the row of pixel (y / 2, x / 2) when both coordinates are even, nothing otherwise
+    // byte offset of the add operand's row for (32-pixel tile i, half q): the destination row itself, or the compact strided operand
     __device__ __forceinline__ unsigned add_off(const TileOffs& t, int i, int q) const {
         if (p.add_stride == 1) return t.row(p.M, (unsigned)p.NOUT, i, q);
-        const unsigned m = t.mr + 16u * (unsigned)(2 * i + q);
-        const unsigned yall = udivm(m, p.mg_dw, p.sh_dw);
-        const unsigned x = m - yall * (unsigned)p.DW;
-        const unsigned n = udivm(yall, p.mg_dh, p.sh_dh);
-        const unsigned y = yall - n * (unsigned)p.DH;
-        const unsigned mc = (n * (unsigned)p.AH + (y >> 1)) * (unsigned)p.AW + (x >> 1);
-        return (m < p.M && !((x | y) & 1u)) ? (mc * (unsigned)p.NOUT + (unsigned)n_w + 8u * piece()) * 2u : OOB;
+        return compact_add_off(p, t.mr + 16u * (unsigned)(2 * i + q), (unsigned)n_w, piece());
     }
+    // residual / add rows (and mask words) of 32-pixel tile I of the pixel tile `t`: fly from now on
     template <int I> __device__ __forceinline__ void arm(const TileOffs& t) {
         const unsigned v0 = add_off(t, I, 0), v1 = add_off(t, I, 1);
         const unsigned lds = __builtin_amdgcn_readfirstlane(region + (unsigned)I * 2048u);
@@ -1123,14 +1094,14 @@ template <int TM, bool DG> struct RingEpilogue {
     template <int... Is> __device__ __forceinline__ void arm_all(const TileOffs& t, std::integer_sequence<int, Is...>) { (arm<Is>(t), ...); }
 
     __device__ __forceinline__ void prefetch(unsigned first_base) {
-        const int lane = threadIdx.x & 63;
-        const int hh = lane >> 5;
         const unsigned out_bytes = p.M * (unsigned)p.NOUT * 2u;
         r_dst = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, out_bytes, 0x00020000);
         r_bout = __builtin_amdgcn_make_buffer_rsrc(p.bits_out, 0, p.bits_out ? out_bytes >> 4 : 0u, 0x00020000);
         r_slab = __builtin_amdgcn_make_buffer_rsrc(p.slab, 0, p.slab ? 0x7ffffff0u : 0u, 0x00020000);
         q_res = make_rsrc(p.residual, !p.residual ? 0u : p.add_stride == 1 ? out_bytes : (unsigned)(p.NS * p.AH * p.AW * p.NOUT) * 2u);
         q_bin = make_rsrc(p.bits_in, p.bits_in ? out_bytes >> 4 : 0u);
+        // load_shift written out: called here, it merges the four conditional loads of the forward ring kernels into one branch
+        const int hh = (threadIdx.x & 63) >> 5;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1148,79 +1119,43 @@ template <int TM, bool DG> struct RingEpilogue {
     template <int I> __device__ __forceinline__ void operator()(const f32x16& acc) {
         const int lane = threadIdx.x & 63;
         const unsigned pc = piece();
-        CS_ESTART();
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = DG ? acc[r] : acc[r] + sh[r];
         if (p.residual) {
-            uint4 xa = lds_get(acc_lds(I, 0)), xb = lds_get(acc_lds(I, 1));
+            const uint4 xa = lds_get(acc_lds(I, 0)), xb = lds_get(acc_lds(I, 1));
             __builtin_amdgcn_wave_barrier();
-            swap32(xa.x, xa.z); swap32(xa.y, xa.w);
-            swap32(xb.x, xb.z); swap32(xb.y, xb.w);
-            const unsigned rw[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                float lo, hi;
-                unpack2(rw[k], lo, hi);
-                v[2 * k] += lo;
-                v[2 * k + 1] += hi;
-            }
+            add_residual(v, xa, xb);
         }
         unsigned pk[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pk[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-        if (!DG && p.act == CS_ACT_RELU) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) pk[k] = relu_bf16x2(pk[k]);
-        }
-        swap32(pk[0], pk[2]); swap32(pk[1], pk[3]);
-        swap32(pk[4], pk[6]); swap32(pk[5], pk[7]);
-        CS_ETICK(0);
+        pack_tile(v, !DG && p.act == CS_ACT_RELU, pk);
         lds_put(acc_lds(I, 0), make_uint4(pk[0], pk[1], pk[2], pk[3]));
         lds_put(acc_lds(I, 1), make_uint4(pk[4], pk[5], pk[6], pk[7]));
         __builtin_amdgcn_wave_barrier();
         uint4 o0 = lds_get(row_lds(I, 0)), o1 = lds_get(row_lds(I, 1));
         __builtin_amdgcn_wave_barrier();
         asm volatile("" : "+v"(o0.x), "+v"(o1.w));
-        CS_ETICK(1);
         if constexpr (DG) {
             if (p.bits_in) {
                 unsigned mbw;
                 asm volatile("v_mov_b32 %0, v[%c1]" : "=v"(mbw) : "i"(R_MB + I));
-                const unsigned w0 = quad<0x00>(mbw), w1 = quad<0x55>(mbw);
-                o0 = keep_bits8(o0, w0 >> (8u * pc));
-                o1 = keep_bits8(o1, w1 >> (8u * pc));
+                apply_mask(o0, o1, mbw, pc);
             }
             if constexpr (I == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) s1[k] = 0.f;
             }
-            if (p.slab) {
-                const unsigned ow[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    float lo, hi;
-                    unpack2(ow[k], lo, hi);
-                    s1[2 * (k & 3)] += lo; s1[2 * (k & 3) + 1] += hi;
-                }
-            }
+            if (p.slab) add_col_sums(s1, o0, o1);
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), r_dst, cur.row(p.M, (unsigned)p.NOUT, I, 0), 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), r_dst, cur.row(p.M, (unsigned)p.NOUT, I, 1), 0, 0);
         if constexpr (!DG) {
             // always issued (a NULL bit plane has a zero-sized buffer): the vmcnt arithmetic of the loop counts it
             unsigned w0 = 0u, w1 = 0u;
-            if (p.bits_out) {
-                const bool relu = p.act == CS_ACT_RELU;
-                w0 = (relu ? nz_bits8(o0) : pos_bits8(o0)) << (8u * pc); w1 = (relu ? nz_bits8(o1) : pos_bits8(o1)) << (8u * pc);
-                w0 |= quad<0xb1>(w0); w1 |= quad<0xb1>(w1);
-                w0 |= quad<0x4e>(w0); w1 |= quad<0x4e>(w1);
-            }
+            if (p.bits_out) plane_dwords(o0, o1, p.act == CS_ACT_RELU, pc, w0, w1);
             __builtin_amdgcn_raw_buffer_store_b32((lane & 1) ? w1 : w0, r_bout, cur.bit(p.M, (unsigned)p.NOUT, I), 0, 0);
         }
-        CS_ETICK(2);
         arm<I>(nxt);
-        CS_ETICK(3);
     }
 
     __device__ __forceinline__ void finish() {
@@ -1262,12 +1197,10 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, hh = lane >> 5;
-    // workgroup -> (output-channel tile, pixel-tile group): id = 8*slot + xcd; the channel tiles of one group sit on one XCD
-    const unsigned bid = blockIdx.x;
-    const unsigned gslot = bid >> 3;
-    const unsigned group = (gslot / (unsigned)p.n_ntiles) * 8u + (bid & 7u);
-    const int n0 = (int)(gslot % (unsigned)p.n_ntiles) * BN;
-    const int n_w = n0 + wn * 32;
+    // workgroup -> (output-channel tile, pixel-tile group): the group's first pixel tile is the workgroup's WgTile
+    const WgTile wg(p);
+    const unsigned group = wg.mtile;
+    const int n_w = wg.n_w(p, BN, wn);
     const bool alive = n_w < p.NOUT;
     if (group * BM >= p.M) return;
     const int NCC = p.NCC;
@@ -1375,33 +1308,21 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
     int c = 0;                        // chunk of the step being multiplied
     unsigned slot = 0;
     bool fin1 = false, fin2 = false;  // steps s-1 / s-2 ended with an epilogue
-#ifdef CS_DEBUG_V2
-    unsigned long long r_acc[5] = {0, 0, 0, 0, 0}, r_a, r_b;
-    unsigned r_tiles = 0, r_steps = 0;
-#define CS_RTICK(k) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_b)); r_acc[k] += r_b - r_a; r_a = r_b; } while (0)
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_a));
-#else
-#define CS_RTICK(k)
-#endif
     auto step = [&]<int CUR>() -> bool {
         issue_b.template operator()<(CUR + 2) % 3>();
         const int nfin = (int)fin1 + (int)fin2;
         if (nfin == 0) wait_vm<12>();
         else if (nfin == 1) wait_vm<12 + E>();
         else wait_vm<12 + 2 * E>();
-        CS_RTICK(0);
         raw_barrier();
-        CS_RTICK(1);
         issue_a();
         advance_fetch();
-        CS_RTICK(2);
         const unsigned sh_cur = slot * SLOT_ROWS;          // the slot, in LDS rows
         const bool fin = c == NCC - 1;
         bool more = true;
         if (!fin) {
             tap_mfma<TM, CUR, 0, 0u, 0u, true, false, true, false>(qb[0], qb[1], qb[2], qb[3], sh_cur, 0u, hhb, cf0);
             ++c;
-            CS_RTICK(3);
         } else {
             const unsigned mt_next = mt + (unsigned)n_groups;
             const bool has_next = mt_next * BM < p.M;
@@ -1419,14 +1340,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
             c = 0;
             mt = mt_next;
             more = has_next;
-            CS_RTICK(4);
-#ifdef CS_DEBUG_V2
-            ++r_tiles;
-#endif
         }
-#ifdef CS_DEBUG_V2
-        ++r_steps;
-#endif
         slot = slot == NSLOT - 1 ? 0u : slot + 1u;
         fin2 = fin1;
         fin1 = fin;
@@ -1438,14 +1352,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
         if (!step.template operator()<2>()) break;
     }
     wait_vm<0>();                     // the out-of-range tail loads (LDS-DMA among them) are gone before the LDS is released
-#ifdef CS_DEBUG_V2
-    if (p.dbg && lane == 0) {
-        unsigned long long* o = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 6;
-        o[0] = 2; o[1] = r_acc[0]; o[2] = r_acc[1]; o[3] = r_acc[2] + r_acc[3]; o[4] = r_acc[4]; o[5] = ((unsigned long long)r_steps << 32) | r_tiles;
-        if (p.act >= 200) { o[3] = r_acc[2]; o[1] = r_acc[3]; }
-        if (p.act >= 300) { o[1] = epi.e_acc[0]; o[2] = epi.e_acc[1]; o[3] = epi.e_acc[2]; o[4] = epi.e_acc[3]; }
-    }
-#endif
 }
 
 // ---- weights [ROWS][taps][COLS] bf16 (ROWS = destination channels, COLS = contraction channels, both staged layouts of
@@ -1819,15 +1725,7 @@ int launch_halo(const C2Plan& pl, hipStream_t st) {
 #undef CS_HALO_TM
 }
 
-#ifdef CS_DEBUG_V2
-unsigned long long* g_dbg_buf = nullptr;
-#endif
-
 }  // namespace
-
-#ifdef CS_DEBUG_V2
-extern "C" int cs_debug_set_stamp_buffer(void* p) { g_dbg_buf = reinterpret_cast<unsigned long long*>(p); return CS_OK; }
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 static bool plan_any(const CsConvGeom* g, int dgrad, C2Plan& pl) { return plan_halo(g, dgrad, pl) || plan_gemm(g, dgrad, pl); }
@@ -1870,9 +1768,7 @@ extern "C" int cs_conv2d_packed_partial_rows(const CsConvGeom* g, int dgrad) {
 extern "C" int cs_conv2d_fwd_packed(const CsConvGeom* g, const void* x, const void* w_packed, const float* shift, const void* residual, int act,
                                     void* y, uint8_t* positive_bits, void* stream) {
     CS_CHECK_ARG(g && x && w_packed && y, "conv2d_fwd_packed: NULL tensor");
-#ifndef CS_DEBUG_V2
     CS_CHECK_ARG(act == CS_ACT_NONE || act == CS_ACT_RELU, "conv2d_fwd_packed: activation must be none or ReLU");
-#endif
     C2Plan pl;
     if (!plan_any(g, 0, pl)) {
         cs_set_error_("conv2d_fwd_packed: geometry not served by the packed-operand kernel (ask cs_conv2d_packed_supported first)");
@@ -1881,9 +1777,6 @@ extern "C" int cs_conv2d_fwd_packed(const CsConvGeom* g, const void* x, const vo
     pl.p.src = x; pl.p.wpk = w_packed; pl.p.dst = y;
     pl.p.shift = shift; pl.p.residual = residual; pl.p.act = act;
     pl.p.bits_out = positive_bits;
-#ifdef CS_DEBUG_V2
-    pl.p.dbg = g_dbg_buf;
-#endif
     return launch_any(pl, reinterpret_cast<hipStream_t>(stream), false);
 }
 
@@ -1910,9 +1803,6 @@ extern "C" int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const
     pl.p.residual = add; pl.p.act = CS_ACT_NONE;
     pl.p.bits_in = mask_bits;
     pl.p.slab = partial_rows;
-#ifdef CS_DEBUG_V2
-    pl.p.dbg = g_dbg_buf;
-#endif
     return launch_any(pl, reinterpret_cast<hipStream_t>(stream), true);
 }
 

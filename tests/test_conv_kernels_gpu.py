@@ -360,7 +360,7 @@ def test_weight_prep_tiled_layouts(shape, dev):
 
 
 @pytest.mark.parametrize("shape", [(2, 19, 19, 64, 128, 1), (8, 38, 38, 128, 144, 1), (64, 38, 38, 32, 192, 1), (3, 21, 17, 64, 64, 3)])
-def test_conv_fwd_batch_statistics_atomic_and_slab_paths(shape, dev):
+def test_conv_fwd_batch_statistics_on_the_atomic_and_slab_paths(shape, dev):
     """cs_conv2d_fwd with `stats`: per-channel sum / sum of squares of the STORED bf16 output.  Launches with <= 512 pixel tiles add them
     with fp64 atomics from the epilogue, larger ones leave partial rows for slab_reduce (the third shape: 722 tiles); both must match the
     sums of the stored tensor."""
