@@ -8,8 +8,11 @@ namespace {
 struct Tap { int i0, i1; float w0, w1; };
 
 // ATen's align_corners source index: scale = (in-1)/(out-1) in fp32, src = scale*dst,
-// i0 = floor(src), i1 = i0 + (i0 < in-1), lambda = src - i0.
+// i0 = floor(src), i1 = i0 + (i0 < in-1), lambda = src - i0.  src is a ROUNDED fp32 product: without the pragma the compiler contracts
+// scale*dst - i0 into one fma where it inlines this into the backward kernel (and not in the forward), and the two kernels' weights
+// differ by up to an ulp of src wherever the scale is not exact (19->38, 75->150: gradients off by 4e-5 of |dy|).
 __device__ __forceinline__ Tap tap_of(int o, int in, int out) {
+#pragma clang fp contract(off)
     const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
     const float src = scale * (float)o;
     int i0 = (int)src;

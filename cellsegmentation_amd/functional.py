@@ -180,31 +180,37 @@ def mse_loss(x, t, weighted=False, reduction="mean"):
 class _Dice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, t, eps, mean):
+        # the kernels read fp32: widen / narrow here (an fp64 or bf16 p used to be read as raw floats), like the reference's `.float()`
+        # on the target; the gradient goes back in the caller's dtype and shape
         if p.ndim == 2 and t.ndim == 2:          # metrics/metrics.py:39-44: one global dice
-            p2, t2 = p.contiguous().view(1, -1), t.contiguous().view(1, -1).float()
+            p2, t2 = p.float().contiguous().view(1, -1), t.float().contiguous().view(1, -1)
         else:
-            p2 = p.contiguous().view(p.shape[0], -1)
-            t2 = t.contiguous().view(t.shape[0], -1).float()
+            p2 = p.float().contiguous().view(p.shape[0], -1)
+            t2 = t.float().contiguous().view(t.shape[0], -1)
         loss, sums = K.dice_fwd(p2, t2, eps, mean)
         ctx.save_for_backward(p2, t2, sums)
-        ctx.eps, ctx.mean, ctx.shape = eps, mean, p.shape
+        ctx.eps, ctx.mean, ctx.shape, ctx.dtype = eps, mean, p.shape, p.dtype
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
         p2, t2, sums = ctx.saved_tensors
         dp = K.dice_bwd(p2, t2, sums, ctx.eps, ctx.mean)
-        return (dp * g).view(ctx.shape), None, None, None
+        return (dp * g).view(ctx.shape).to(ctx.dtype), None, None, None
 
 
 def dice_loss(p, t, eps=1e-6, reduction="mean"):
+    """1 - dice, mean | sum over samples (train/losses.py:52-62).  p: any floating dtype (fp64 / bf16 / fp16 are cast to fp32 on the way
+    in, the gradient comes back in p's dtype and shape), contiguous or not; t: any dtype (bool / uint8 / int64 masks included), cast
+    to fp32 like the reference's `.float()`.  Two 2-D operands are one global sample."""
     return _Dice.apply(p, t, eps, reduction == "mean")
 
 
 class _SoftmaxChannel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, ch):
-        logits = logits.contiguous()
+        ctx.dtype = logits.dtype
+        logits = logits.float().contiguous()
         ctx.save_for_backward(logits)
         ctx.ch = ch
         return K.softmax_channel_fwd(logits, ch)
@@ -212,9 +218,11 @@ class _SoftmaxChannel(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (logits,) = ctx.saved_tensors
-        return K.softmax_channel_bwd(logits, g.contiguous(), ctx.ch), None
+        return K.softmax_channel_bwd(logits, g.float().contiguous(), ctx.ch).to(ctx.dtype), None
 
 
 def softmax_channel(logits_nchw, ch=1):
-    """F.softmax(logits, dim=1)[:, ch] for NCHW fp32 logits (train/train.py:189)."""
+    """F.softmax(logits, dim=1)[:, ch] for NCHW logits (train/train.py:189).  The kernel reads fp32: logits of another floating dtype
+    (fp64, bf16) are cast to fp32 on the way in (they used to be read as raw floats); the result is fp32 and the gradient comes back
+    in the logits' dtype.  Non-contiguous logits are packed first."""
     return _SoftmaxChannel.apply(logits_nchw, ch)

@@ -21,6 +21,13 @@ def _code(dtype):
     raise TypeError(f"unsupported activation dtype {dtype}; use torch.float32 or torch.bfloat16")
 
 
+def _f32(*tensors):
+    """the loss kernels read `const float*` only: any other dtype would be read as raw bits"""
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"this kernel reads torch.float32 only, got {t.dtype}; cast on the way in (functional.py does)")
+
+
 def chunk(dtype):
     """Elements per 16-byte chunk."""
     return 4 if dtype == torch.float32 else 8
@@ -949,6 +956,7 @@ def mse(x, t, weighted=False, mean=True, want_grad=True):
 def dice_fwd(p, t, eps=1e-6, mean=True):
     """p, t: [N, HW] fp32 contiguous. returns loss[1], sums: the per-sample (sum p t, sum p^2, sum t^2) as an exact accumulator of
     accum_words(3 N) opaque words (cleared by the call, read by dice_bwd)"""
+    _f32(p, t)
     N, HW = p.shape
     sums = torch.empty((accum_words(3 * N),), dtype=torch.float64, device=p.device)
     loss = torch.empty((1,), dtype=torch.float32, device=p.device)
@@ -962,6 +970,7 @@ def dice_sums_values(sums, N):
 
 
 def dice_bwd(p, t, sums, eps=1e-6, mean=True):
+    _f32(p, t)
     N, HW = p.shape
     dp = torch.empty_like(p)
     _lib.check(_lib.load().cs_dice_bwd(_p(p), _p(t), _p(sums), N, HW, eps, 1 if mean else 0, _p(dp), _stream()), "dice_bwd")
@@ -970,6 +979,7 @@ def dice_bwd(p, t, sums, eps=1e-6, mean=True):
 
 def softmax_channel_fwd(logits, ch=1):
     """logits [N,C,H,W] fp32 -> softmax over C, channel ch: [N,H,W]"""
+    _f32(logits)
     N, C, H, W = logits.shape
     pc = torch.empty((N, H, W), dtype=torch.float32, device=logits.device)
     _lib.check(_lib.load().cs_softmax_channel_fwd(_p(logits), _p(pc), N, C, H * W, ch, _stream()), "softmax_channel_fwd")
@@ -977,6 +987,7 @@ def softmax_channel_fwd(logits, ch=1):
 
 
 def softmax_channel_bwd(logits, dpc, ch=1):
+    _f32(logits, dpc)
     N, C, H, W = logits.shape
     dl = torch.empty_like(logits)
     _lib.check(_lib.load().cs_softmax_channel_bwd(_p(logits), _p(dpc), _p(dl), N, C, H * W, ch, _stream()), "softmax_channel_bwd")

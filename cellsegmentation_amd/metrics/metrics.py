@@ -34,11 +34,14 @@ class _DiceCoef(torch.autograd.Function):
 
 
 def dice_coef(batch_inputs, batch_targets, epsilon=1e-6):
+    """Per-sample dice (one global value for two 2-D operands), fp32.  Inputs and targets must share a dtype (the reference's
+    assertion); any floating dtype is accepted: the kernel reads fp32, so fp64 / bf16 operands are cast on the way in (two fp64 tensors
+    pass the assertion and used to be read as raw floats) and the gradient comes back in the inputs' dtype and shape."""
     assert batch_inputs.dtype == batch_targets.dtype, "Input & target vectors should have same dtype. "
     if batch_inputs.ndim == 2 and batch_targets.ndim == 2:
-        p = batch_inputs.contiguous().view(1, -1)
-        t = batch_targets.contiguous().view(1, -1).float()
+        p = batch_inputs.float().contiguous().view(1, -1)
+        t = batch_targets.float().contiguous().view(1, -1)
         return _DiceCoef.apply(p, t, epsilon)[0]
-    p = batch_inputs.contiguous().view(batch_inputs.size()[0], -1)
-    t = batch_targets.contiguous().view(batch_targets.size()[0], -1).float()
+    p = batch_inputs.float().contiguous().view(batch_inputs.size()[0], -1)
+    t = batch_targets.float().contiguous().view(batch_targets.size()[0], -1)
     return _DiceCoef.apply(p, t, epsilon)
