@@ -27,9 +27,11 @@ SHAPES = [
     (2, 37, 37, 3, 64, 7, 2, 3),
     (2, 13, 13, 24, 40, 3, 1, 1),
     (2, 11, 11, 40, 24, 5, 2, 2),
-    (8, 80, 80, 32, 128, 1, 1, 0),    # M=51200: 128x128 tile path
-    (8, 80, 80, 16, 64, 3, 1, 1),     # 128x64 tile path
+    (8, 80, 80, 32, 128, 1, 1, 0),    # M=51200: 400 workgroups of 128 rows < 1536, so the 64x128 tile (dgrad into 32 channels: 64x64)
+    (8, 80, 80, 16, 64, 3, 1, 1),     # 400 < 1536: the 64x64 tile.  The 128-row tiles are tested in test_igemm_exact_gpu.py
 ]
+# forward tile of the two large shapes, asserted below so that the comments above cannot go stale again
+FWD_TILE = {(8, 80, 80, 32, 128, 1, 1, 0): (64, 128), (8, 80, 80, 16, 64, 3, 1, 1): (64, 64)}
 
 
 def _q(t, dtype):
@@ -91,6 +93,10 @@ def test_conv_fwd_dgrad_wgrad(shape, dtype, dev, igemm_path):
     sc = torch.ones(Kp); sc[:Cout] = scale
     sh = torch.zeros(Kp); sh[:Cout] = shift
     y_plain = K.conv_fwd(geom, xd, w_khwc)
+    if shape in FWD_TILE:
+        from cellsegmentation_amd import _lib
+        variant = (_lib.load().cs_last_conv_variant() or b"").decode()
+        assert variant.split("<")[1].split(",")[1:3] == [str(v) for v in FWD_TILE[shape]], variant
     y_full = K.conv_fwd(geom, xd, w_khwc, sc.to(dev), sh.to(dev), _nhwc(res, dtype, dev, Kp), K.CS_ACT_RELU)
     torch.cuda.synchronize()
     e1 = _relerr(_from_nhwc(y_plain, Cout), ref)
@@ -322,8 +328,9 @@ def test_wgrad_finalize_batched_folds_partial_column_sums(K_, Cin, R, nsplit, n,
 
 def test_wave_specialised_weight_gradient_on_every_shape(dev):
     """wgrad_spec_kernel (4 loader + 4 consumer waves) is selected by rule for the deep layers only; CELLSEG_WGRAD_SPEC=1 forces it for
-    every LDS-DMA weight gradient, =2 forces the four-wave kernel.  Both extremes must pass this file's parity tests and the exact
-    integer-data test of the packed kernels' file (the knob is read once per process: child interpreters)."""
+    every LDS-DMA weight gradient, =2 forces the four-wave kernel.  Both extremes must pass this file's parity tests, the exact
+    integer-data test of the packed kernels' file and the exact first-generation table of test_igemm_exact_gpu.py (the knob is read once
+    per process: child interpreters)."""
     import os
     import subprocess
     import sys
@@ -333,7 +340,8 @@ def test_wave_specialised_weight_gradient_on_every_shape(dev):
         # forced-mode test and its bag-size sweep are left to the parent run)
         env = dict(os.environ, CELLSEG_WGRAD_SPEC=mode, CELLSEG_LIB_FLAVOUR="ab", CELLSEG_TEST_IGEMM_PATHS="all" if mode == "1" else "dma")
         r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_conv_kernels_gpu.py"),
-                            os.path.join(root, "tests", "test_conv_packed_gpu.py"), "-m", "gpu", "-x", "-q",
+                            os.path.join(root, "tests", "test_conv_packed_gpu.py"), os.path.join(root, "tests", "test_igemm_exact_gpu.py"),
+                            "-m", "gpu", "-x", "-q",
                             "-k", "not wave_specialised and not wide_kernel_forced and not first_generation_over"],
                            capture_output=True, text=True, timeout=1200, env=env, cwd=root)
         assert r.returncode == 0, (mode, (r.stdout + r.stderr)[-3000:])

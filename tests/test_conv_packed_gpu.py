@@ -12,6 +12,8 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from conv_ref import sparse_pm1 as _sparse_pm1  # noqa: E402
+
 from cellsegmentation_amd import kernels as K  # noqa: E402
 
 BF = torch.bfloat16
@@ -206,17 +208,6 @@ def test_one_launch_staging_writes_the_packed_operands_bit_exactly(shape, dev):
     assert torch.equal(w_b.view(-1).view(torch.int16), ref_b.view(-1).view(torch.int16)[: w_b.numel()])
     assert float((scale - scale_ref).abs().max()) < 1e-6
     assert torch.equal(u_f.view(torch.int16), w_khwc.view(torch.int16)) and torch.equal(u_b.view(torch.int16), w_chwk.view(torch.int16))
-
-
-def _sparse_pm1(shape, per_row, g):
-    """[rows, ...] tensor with `per_row` entries of +-1 / +-2 per leading index, zeros elsewhere."""
-    rows = shape[0]
-    flat = int(torch.tensor(shape[1:]).prod())
-    w = torch.zeros((rows, flat))
-    for r in range(rows):
-        idx = torch.randperm(flat, generator=g)[:per_row]
-        w[r, idx] = torch.randint(1, 3, (per_row,), generator=g).float() * (torch.randint(0, 2, (per_row,), generator=g).float() * 2 - 1)
-    return w.view(shape)
 
 
 @pytest.mark.parametrize("shape", SHAPES)

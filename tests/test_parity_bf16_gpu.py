@@ -110,7 +110,7 @@ BIT_SHAPES = [
     (2, 19, 19, 64, 128, 1, 1, 0),     # single K-step forward; data gradient contracts 128 channels (two K-steps: prefetched epilogue)
     (2, 19, 19, 128, 64, 1, 1, 0),     # two K-steps forward; single K-step data gradient
     (2, 19, 19, 64, 64, 3, 1, 1),      # tap-walking launches
-    (8, 40, 40, 32, 128, 1, 1, 0),     # 128x128 tiles
+    (8, 40, 40, 32, 128, 1, 1, 0),     # M = 12800: 100 workgroups of 128 rows < 1536, so 64x128 tiles (data gradient: 64x64)
 ]
 
 
