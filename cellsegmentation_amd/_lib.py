@@ -25,7 +25,7 @@ class CsConvGeom(Structure):
 
 
 class CsStageDesc(Structure):
-    """One layer of cs_stage_conv_bn_multi (include/cellseg_hip.h)."""
+    """One layer of cs_stage_conv_bn_one / cs_stage_conv_bn_multi (include/cellseg_hip.h)."""
     _fields_ = ([(n, c_void_p) for n in ("w", "gamma", "beta", "mean", "var", "conv_bias", "w_khwc", "w_chwk", "scale", "shift", "rstd")]
                 + [("eps", c_float)] + [(n, c_int32) for n in ("K", "Cin", "R", "S", "Cp", "Kp", "block0", "fwd_packed", "bwd_packed")])
 
@@ -49,7 +49,7 @@ _SIGNATURES = {
     "cs_bn_fold": (c_int, [_P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, _P]),
     "cs_stage_conv_bn_blocks": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "cs_stage_conv_bn_multi": (c_int, [_P, c_int, c_int, c_int, _P]),
-    "cs_stage_conv_bn": (c_int, [_P, _P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "cs_stage_conv_bn_one": (c_int, [POINTER(CsStageDesc), c_int, _P]),
     "cs_weight_prep": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "cs_conv2d_fwd": (c_int, [POINTER(CsConvGeom), c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "cs_conv2d_stats_workspace": (c_size_t, [c_longlong, c_int]),

@@ -64,161 +64,14 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
     if (rstd) rstd[c] = r;
 }
 
-// ---- weights: fp32 [K][Cin][R][S] (x scale[k]) -> T [K][R][S][Cp] and/or T [Cin][R][S][Kp] ------
-template <typename T>
-__global__ void weight_prep_kernel(const float* __restrict__ w, const float* __restrict__ scale, int K, int Cin, int R,
-                                   int S, int Cp, int Kp, T* __restrict__ w_khwc, T* __restrict__ w_chwk) {
-    const int RS = R * S;
-    if (w_khwc) {
-        const long long total = (long long)Kp * RS * Cp;
-        for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-             idx += (long long)gridDim.x * blockDim.x) {
-            const int c = (int)(idx % Cp);
-            const int rs = (int)((idx / Cp) % RS);
-            const int k = (int)(idx / ((long long)Cp * RS));
-            float v = 0.f;
-            if (c < Cin && k < K) {
-                v = w[((long long)k * Cin + c) * RS + rs];
-                if (scale) v *= scale[k];
-            }
-            w_khwc[idx] = from_f32<T>(v);
-        }
-    }
-    if (w_chwk) {
-        const long long total = (long long)Cp * RS * Kp;
-        for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-             idx += (long long)gridDim.x * blockDim.x) {
-            const int k = (int)(idx % Kp);
-            const int rs = (int)((idx / Kp) % RS);
-            const int c = (int)(idx / ((long long)Kp * RS));
-            float v = 0.f;
-            if (k < K && c < Cin) {
-                v = w[((long long)k * Cin + c) * RS + rs];
-                if (scale) v *= scale[k];
-            }
-            w_chwk[idx] = from_f32<T>(v);
-        }
-    }
-}
-
-// The same for bf16 through an LDS tile (round 3): the kernel above reads w with a stride of R*S floats between neighbouring lanes (a wave
-// touches 9x the bytes it uses for a 3x3 filter) -- 21 us per layer and 0.3 ms per step on the segmentation decoder, whose 50 M trainable
-// weights are re-staged every step.  Workgroup = 32 filters x 64 input channels x all taps: contiguous reads (64 * R*S floats per filter),
-// contiguous 128-byte / 64-byte runs on the way out.
-constexpr int kWpTK = 32, kWpTC = 64;
-template <int RS>
-__global__ __launch_bounds__(256) void weight_prep_tiled_kernel(const float* __restrict__ w, const float* __restrict__ scale, int K, int Cin,
-                                                                int Cp, int Kp, bf16_t* __restrict__ w_khwc, bf16_t* __restrict__ w_chwk) {
-    extern __shared__ bf16_t wt[];                       // [kWpTK][RS][kWpTC + 2]
-    const int k0 = blockIdx.y * kWpTK, c0 = blockIdx.x * kWpTC;
-    constexpr int pitch = kWpTC + 2;
-    const int cw = (Cin - c0) < kWpTC ? (Cin - c0) : kWpTC;          // may be <= 0 in the padding columns of Cp
-    const int run = cw > 0 ? cw * RS : 0;
-    constexpr int ROW = kWpTC * RS, TOTAL = kWpTK * ROW;             // flat walk over the tile: 8 independent loads in flight per thread
-    static_assert(TOTAL % (256 * 8) == 0, "tile walk");
-    for (int e0 = threadIdx.x; e0 < TOTAL; e0 += 256 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e = e0 + u * 256;
-            const int kk = e / ROW, i = e - kk * ROW;
-            const int k = k0 + kk;
-            v[u] = (k < K && i < run) ? w[((long long)k * Cin + c0) * RS + i] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e = e0 + u * 256;
-            const int kk = e / ROW, i = e - kk * ROW;
-            const int cl = i / RS, rs = i - cl * RS;
-            const int k = k0 + kk;
-            const float sc = (scale && k < K) ? scale[k] : 1.f;
-            wt[(kk * RS + rs) * pitch + cl] = from_f32<bf16_t>(v[u] * sc);
-        }
-    }
-    __syncthreads();
-    if (w_khwc) {
-        // [k][rs][c0 .. c0+63]: one 128-byte run per (k, rs)
-        for (int i = threadIdx.x; i < kWpTK * RS * (kWpTC / 2); i += 256) {
-            const int cp = i % (kWpTC / 2), krs = i / (kWpTC / 2);
-            const int kk = krs / RS, rs = krs - kk * RS;
-            const int k = k0 + kk, c = c0 + 2 * cp;
-            if (k < Kp && c < Cp)
-                *reinterpret_cast<unsigned*>(w_khwc + ((long long)k * RS + rs) * Cp + c) = *reinterpret_cast<const unsigned*>(&wt[(kk * RS + rs) * pitch + 2 * cp]);
-        }
-    }
-    if (w_chwk) {
-        // [c][rs][k0 .. k0+31]: one 64-byte run per (c, rs)
-        for (int i = threadIdx.x; i < kWpTC * RS * (kWpTK / 2); i += 256) {
-            const int kp = i % (kWpTK / 2), crs = i / (kWpTK / 2);
-            const int cl = crs / RS, rs = crs - cl * RS;
-            const int c = c0 + cl, k = k0 + 2 * kp;
-            if (c < Cp && k < Kp) {
-                union { bf16_t h[2]; unsigned u; } cv;
-                cv.h[0] = wt[((2 * kp) * RS + rs) * pitch + cl];
-                cv.h[1] = wt[((2 * kp + 1) * RS + rs) * pitch + cl];
-                *reinterpret_cast<unsigned*>(w_chwk + ((long long)c * RS + rs) * Kp + k) = cv.u;
-            }
-        }
-    }
-}
-
-// ---- fused staging for an eval-mode Conv+BN: BN fold + both weight layouts in ONE launch.  Every thread recomputes
-// scale[k] = gamma[k]/sqrt(var[k]+eps) for its element (cheap), workgroup 0 also writes scale/shift/rstd.
-template <typename T>
-__global__ void stage_conv_bn_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                     const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                     const float* __restrict__ conv_bias, int K, int Cin, int R, int S, int Cp, int Kp,
-                                     T* __restrict__ w_khwc, T* __restrict__ w_chwk, float* __restrict__ scale,
-                                     float* __restrict__ shift, float* __restrict__ rstd) {
-    const int RS = R * S;
-    if (blockIdx.x == 0) {
-        for (int k = threadIdx.x; k < Kp; k += blockDim.x) {
-            float r = 0.f, sc = 0.f, sh = 0.f;
-            if (k < K) {
-                r = 1.0f / sqrtf(var[k] + eps);
-                sc = (gamma ? gamma[k] : 1.f) * r;
-                sh = (beta ? beta[k] : 0.f) + ((conv_bias ? conv_bias[k] : 0.f) - mean[k]) * sc;
-            }
-            scale[k] = sc; shift[k] = sh; rstd[k] = r;
-        }
-    }
-    const long long t1 = w_khwc ? (long long)Kp * RS * Cp : 0;
-    const long long t2 = w_chwk ? (long long)Cp * RS * Kp : 0;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < t1 + t2; idx += (long long)gridDim.x * blockDim.x) {
-        int k, c, rs;
-        const bool first = idx < t1;
-        if (first) {
-            c = (int)(idx % Cp); rs = (int)((idx / Cp) % RS); k = (int)(idx / ((long long)Cp * RS));
-        } else {
-            const long long j = idx - t1;
-            k = (int)(j % Kp); rs = (int)((j / Kp) % RS); c = (int)(j / ((long long)Kp * RS));
-        }
-        float v = 0.f;
-        if (k < K && c < Cin) v = w[((long long)k * Cin + c) * RS + rs] * ((gamma ? gamma[k] : 1.f) * (1.0f / sqrtf(var[k] + eps)));
-        if (first) w_khwc[idx] = from_f32<T>(v);
-        else w_chwk[idx - t1] = from_f32<T>(v);
-    }
-}
-
-// ---- every layer of a network in one launch: workgroup -> layer by binary search over the block0 prefix table
+// ---- weight staging of an ungrouped convolution: fp32 w[K][Cin][R][S] x (gamma[k] / sqrt(var[k] + eps)) -> T w_khwc [Kp][R][S][Cp]
+// and / or T w_chwk [Cp][R][S][Kp] (padding zero-filled), either one optionally in the MFMA-fragment order of csrc/conv_v2.hip, plus the
+// folded scale / shift / rstd rows.  ONE body for every route (cs_weight_prep, cs_stage_conv_bn_one, cs_stage_conv_bn_multi): workgroup
+// b of the nb workgroups that share layer d.
 constexpr int kStageElemsPerBlock = 2048;      // 256 threads x 8 staged elements
 
 template <typename T>
-__global__ __launch_bounds__(256) void stage_conv_bn_multi_kernel(const CsStageDesc* __restrict__ desc, int n) {
-    __shared__ int which_s;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = n - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (desc[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-        which_s = lo;
-    }
-    __syncthreads();
-    const int which = which_s;
-    const CsStageDesc d = desc[which];
-    const int nb = (which + 1 < n ? desc[which + 1].block0 : (int)gridDim.x) - d.block0;
-    const int b = (int)blockIdx.x - d.block0;
+__device__ __forceinline__ void stage_layer_body(const CsStageDesc& d, const int b, const int nb) {
     const int RS = d.R * d.S;
     if (b == 0) {
         for (int k = threadIdx.x; k < d.Kp; k += blockDim.x) {
@@ -228,7 +81,9 @@ __global__ __launch_bounds__(256) void stage_conv_bn_multi_kernel(const CsStageD
                 sc = (d.gamma ? d.gamma[k] : 1.f) * r;
                 sh = (d.beta ? d.beta[k] : 0.f) + ((d.conv_bias ? d.conv_bias[k] : 0.f) - (d.mean ? d.mean[k] : 0.f)) * sc;
             }
-            d.scale[k] = sc; d.shift[k] = sh; d.rstd[k] = r;
+            if (d.scale) d.scale[k] = sc;
+            if (d.shift) d.shift[k] = sh;
+            if (d.rstd) d.rstd[k] = r;
         }
     }
     T* w_khwc = reinterpret_cast<T*>(d.w_khwc);
@@ -344,6 +199,31 @@ __global__ __launch_bounds__(256) void stage_conv_bn_multi_kernel(const CsStageD
         if (first) w_khwc[j] = from_f32<T>(v);
         else w_chwk[j] = from_f32<T>(v);
     }
+}
+
+// every layer of a network in one launch: workgroup -> layer by binary search over the block0 prefix table
+template <typename T>
+__global__ __launch_bounds__(256) void stage_conv_bn_multi_kernel(const CsStageDesc* __restrict__ desc, int n) {
+    __shared__ int which_s;
+    if (threadIdx.x == 0) {
+        int lo = 0, hi = n - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (desc[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+        }
+        which_s = lo;
+    }
+    __syncthreads();
+    const int which = which_s;
+    const CsStageDesc d = desc[which];
+    const int nb = (which + 1 < n ? desc[which + 1].block0 : (int)gridDim.x) - d.block0;
+    stage_layer_body<T>(d, (int)blockIdx.x - d.block0, nb);
+}
+
+// one layer: the descriptor is the kernel argument (no device table, nothing to copy: the launch may be captured)
+template <typename T>
+__global__ __launch_bounds__(256) void stage_conv_bn_one_kernel(const CsStageDesc d) {
+    stage_layer_body<T>(d, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- grouped weights: fp32 [K][Cg][R][S] (x scale[k]) -> slab-dense T [K][R][S][64] and T [C][R][S][64]
@@ -537,36 +417,6 @@ extern "C" int cs_bn_fold(const float* gamma, const float* beta, const float* me
     CS_CHECK_ARG(mean && var && C > 0, "bn_fold: NULL statistics");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, st, gamma, beta, mean, var, eps, conv_bias, scale, shift, rstd, C);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
-extern "C" int cs_weight_prep(const float* w, const float* scale, int dtype, int K, int Cin, int R, int S, int Cp, int Kp,
-                              void* w_khwc, void* w_chwk, void* stream) {
-    CS_CHECK_ARG(w && (w_khwc || w_chwk), "weight_prep: NULL tensor");
-    CS_CHECK_ARG(K > 0 && Cin > 0 && R > 0 && S > 0 && Cp >= Cin && Kp >= K, "weight_prep: bad extents");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long t1 = (long long)Kp * R * S * Cp, t2 = (long long)Cp * R * S * Kp;
-    const long long total = t1 > t2 ? t1 : t2;
-    const size_t tile_lds = (size_t)kWpTK * R * S * (kWpTC + 2) * sizeof(bf16_t);
-    static const int untiled = cs_env_int_("CELLSEG_WPREP_UNTILED", 0);      // A/B experiments only
-    if (!untiled && dtype == CS_BF16 && (R * S == 9 || R * S == 1) && Cp % 2 == 0 && Kp % 2 == 0 && total >= (1 << 21)) {   // (smaller tensors: too few tiles to fill the chip, 10 vs 20 us)
-        const dim3 tgrid((unsigned)((Cp + kWpTC - 1) / kWpTC), (unsigned)((Kp + kWpTK - 1) / kWpTK));
-        if (R * S == 9)
-            hipLaunchKernelGGL(weight_prep_tiled_kernel<9>, tgrid, dim3(256), tile_lds, st, w, scale, K, Cin, Cp, Kp, (bf16_t*)w_khwc, (bf16_t*)w_chwk);
-        else
-            hipLaunchKernelGGL(weight_prep_tiled_kernel<1>, tgrid, dim3(256), tile_lds, st, w, scale, K, Cin, Cp, Kp, (bf16_t*)w_khwc, (bf16_t*)w_chwk);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(weight_prep_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, scale, K, Cin, R, S, Cp, Kp,
-                           (float*)w_khwc, (float*)w_chwk);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(weight_prep_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, scale, K, Cin, R, S, Cp, Kp,
-                           (bf16_t*)w_khwc, (bf16_t*)w_chwk);
-    else
-        CS_CHECK_ARG(false, "weight_prep: bad dtype");
     CS_LAUNCH_CHECK();
     return CS_OK;
 }
@@ -843,25 +693,6 @@ extern "C" int cs_wgrad_finalize_grouped(const float* dw_slab, int nsplit, const
                            dbeta, dot_ws, 0, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int cs_stage_conv_bn(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
-                                const float* conv_bias, int dtype, int K, int Cin, int R, int S, int Cp, int Kp, void* w_khwc,
-                                void* w_chwk, float* scale, float* shift, float* rstd, void* stream) {
-    CS_CHECK_ARG(w && mean && var && scale && shift && rstd && (w_khwc || w_chwk), "stage_conv_bn: NULL tensor");
-    CS_CHECK_ARG(K > 0 && Cin > 0 && R > 0 && S > 0 && Cp >= Cin && Kp >= K, "stage_conv_bn: bad extents");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long total = (w_khwc ? (long long)Kp * R * S * Cp : 0) + (w_chwk ? (long long)Cp * R * S * Kp : 0);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(stage_conv_bn_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, gamma, beta, mean, var, eps,
-                           conv_bias, K, Cin, R, S, Cp, Kp, (float*)w_khwc, (float*)w_chwk, scale, shift, rstd);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(stage_conv_bn_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, gamma, beta, mean, var, eps,
-                           conv_bias, K, Cin, R, S, Cp, Kp, (bf16_t*)w_khwc, (bf16_t*)w_chwk, scale, shift, rstd);
-    else
-        CS_CHECK_ARG(false, "stage_conv_bn: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
 extern "C" int cs_stage_conv_bn_blocks(int K, int Cin, int R, int S, int Cp, int Kp, int want_fwd, int want_bwd) {
     if (K <= 0 || Cin <= 0 || R <= 0 || S <= 0 || Cp < Cin || Kp < K) return 0;
     const long long total = (want_fwd ? (long long)Kp * R * S * Cp : 0) + (want_bwd ? (long long)Cp * R * S * Kp : 0);
@@ -869,6 +700,32 @@ extern "C" int cs_stage_conv_bn_blocks(int K, int Cin, int R, int S, int Cp, int
     if (b < 1) b = 1;
     if (b > 4096) b = 4096;
     return (int)b;
+}
+
+extern "C" int cs_stage_conv_bn_one(const CsStageDesc* host_desc, int dtype, void* stream) {
+    CS_CHECK_ARG(host_desc, "stage_conv_bn_one: NULL descriptor");
+    const CsStageDesc& d = *host_desc;
+    CS_CHECK_ARG(d.w && (d.w_khwc || d.w_chwk), "stage_conv_bn_one: NULL tensor");
+    CS_CHECK_ARG(!d.mean == !d.var, "stage_conv_bn_one: mean and var come together (both NULL: no BatchNorm is folded)");
+    const int nb = cs_stage_conv_bn_blocks(d.K, d.Cin, d.R, d.S, d.Cp, d.Kp, d.w_khwc != nullptr, d.w_chwk != nullptr);
+    CS_CHECK_ARG(nb >= 1, "stage_conv_bn_one: bad extents");
+    CS_CHECK_ARG(!(d.fwd_packed && d.w_khwc) || (d.Kp % 32 == 0 && d.Cp % 64 == 0), "stage_conv_bn_one: packed forward operand needs Kp % 32 == 0 and Cp % 64 == 0");
+    CS_CHECK_ARG(!(d.bwd_packed && d.w_chwk) || (d.Cp % 32 == 0 && d.Kp % 64 == 0), "stage_conv_bn_one: packed data-gradient operand needs Cp % 32 == 0 and Kp % 64 == 0");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == CS_F32) hipLaunchKernelGGL(stage_conv_bn_one_kernel<float>, dim3(nb), dim3(256), 0, st, d);
+    else if (dtype == CS_BF16) hipLaunchKernelGGL(stage_conv_bn_one_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, d);
+    else CS_CHECK_ARG(false, "stage_conv_bn_one: bad dtype");
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+// (cs_stage_conv_bn_one with gamma = scale, nothing else folded and no vectors out: w * (scale * 1.f) is w * scale exactly)
+extern "C" int cs_weight_prep(const float* w, const float* scale, int dtype, int K, int Cin, int R, int S, int Cp, int Kp,
+                              void* w_khwc, void* w_chwk, void* stream) {
+    CsStageDesc d{};
+    d.w = w; d.gamma = scale; d.w_khwc = w_khwc; d.w_chwk = w_chwk;
+    d.K = K; d.Cin = Cin; d.R = R; d.S = S; d.Cp = Cp; d.Kp = Kp;
+    return cs_stage_conv_bn_one(&d, dtype, stream);
 }
 
 extern "C" int cs_stage_conv_bn_multi(const CsStageDesc* desc, int n, int total_blocks, int dtype, void* stream) {

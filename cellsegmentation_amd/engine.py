@@ -351,14 +351,6 @@ class Plan:
         return [t for _, _, t in self.param_list]
 
 
-def _pad_vec(v, n):
-    if v is None or v.numel() == n:
-        return v
-    out = torch.zeros((n,), dtype=v.dtype, device=v.device)
-    out[: v.numel()] = v
-    return out
-
-
 def _bn_uses_batch_stats(bn, bn_train):
     return bn is not None and bn_train and bn.training
 
@@ -454,7 +446,7 @@ class _Staged:
         self.fwd_packed, self.bwd_packed = bool(pkf), bool(pkb and w_chwk is not None)
 
 
-def _stage_weights(u, dtype, spec, geom, fresh):
+def _stage_weights(u, dtype, spec, fresh):
     """BN folding + weight staging, layer by layer.  Cached only for frozen parameters and for no-grad passes: `fresh` (a forward
     that will be followed by an optimizer step, of a layer whose staging depends on a trainable parameter) always stages afresh
     and leaves the cache invalid, because tensor version counters cannot be trusted to see the update -- torch's fused optimizers
@@ -469,27 +461,22 @@ def _stage_weights(u, dtype, spec, geom, fresh):
         key = None
     elif u._cache is not None and u._cache[0] == key:
         return u._cache[1]
-    w = conv.weight.detach()
-    bias = conv.bias.detach() if conv.bias is not None else None
-    scale = rstd = None
-    if fold and not u.grouped:
-        w_khwc, w_chwk, scale, shift, rstd = K.stage_conv_bn(w, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                             bn.eps, bias, dtype, spec.Cp, spec.Kp, want_bwd=spec.need_bwd)
-    else:
-        shift = bias
+    if u.grouped:
+        w = conv.weight.detach()
+        scale = rstd = None
+        shift = conv.bias.detach() if conv.bias is not None else None
         if fold:
-            scale, shift, rstd = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, bias)
-        if u.grouped:
-            w_khwc, w_chwk = K.weight_prep_grouped(w, scale, dtype, want_fwd=True, want_bwd=spec.need_bwd)
-        else:
-            w_khwc, w_chwk = K.weight_prep(w, scale, dtype, spec.Cp, spec.Kp, want_fwd=True, want_bwd=spec.need_bwd)
-        shift = _pad_vec(shift, spec.Kp)
+            scale, shift, rstd = K.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, shift)
+        w_khwc, w_chwk = K.weight_prep_grouped(w, scale, dtype, want_fwd=True, want_bwd=spec.need_bwd)
+    else:
+        # one launch: BN fold, both operands, packed order where the packed-operand kernels take them (as kernels.StagePack does)
+        w_khwc, w_chwk, scale, shift, rstd = K.stage_layer(conv, bn if fold else None, dtype, spec.Cp, spec.Kp, want_bwd=spec.need_bwd,
+                                                           fwd_packed=spec.pkf, bwd_packed=spec.pkb)
+        if not fold:                        # nothing folded: no scale, no rstd, a shift only where the convolution has a bias
+            scale = rstd = None
+            if conv.bias is None:
+                shift = None
     st = _Staged(w_khwc, w_chwk, scale, shift, rstd, spec.pkf, spec.pkb)
-    # re-order the plain operands for the packed-operand kernels (the one-launch StagePack writes that order directly)
-    if st.fwd_packed:
-        st.w_khwc = K.pack_conv_weights(geom, st.w_khwc, dgrad=False)
-    if st.bwd_packed:
-        st.w_chwk = K.pack_conv_weights(geom, st.w_chwk, dgrad=True)
     u._cache = (key, st)
     return st
 
@@ -598,7 +585,7 @@ class _Forward:
             return pre[1]
         if pre is not None:
             self.packs.pop(self.pack_key, None)       # the layout changed (other requires_grad pattern): rebuild next time
-        st = _stage_weights(u, self.dtype, spec, geom, fresh=self.save and trainable)
+        st = _stage_weights(u, self.dtype, spec, fresh=self.save and trainable)
         if self.capturing:
             _capture.keep(st)               # (a cached staged set may be replaced by a later eager pass: the graph keeps this one)
         # (a batch-statistics layer joins the one-launch staging with bn = None: its operands depend on the convolution only)

@@ -88,24 +88,51 @@ def bn_fold(gamma, beta, mean, var, eps, conv_bias=None):
     return out[0], out[1], out[2]
 
 
-def stage_conv_bn(w, gamma, beta, mean, var, eps, conv_bias, dtype, Cp, Kp, want_bwd=False):
-    """Fused BN fold + weight staging. Returns w_khwc, w_chwk, scale, shift, rstd (the last three [Kp])."""
-    K_, Cin, R, S = w.shape
-    w_khwc = torch.empty((Kp, R, S, Cp), dtype=dtype, device=w.device)
-    w_chwk = torch.empty((Cp, R, S, Kp), dtype=dtype, device=w.device) if want_bwd else None
-    vec = torch.empty((3, Kp), dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().cs_stage_conv_bn(_p(w), _p(gamma), _p(beta), _p(mean), _p(var), eps, _p(conv_bias), _code(dtype), K_, Cin, R, S,
-                                            Cp, Kp, _p(w_khwc), _p(w_chwk), _p(vec[0]), _p(vec[1]), _p(vec[2]), _stream()), "stage_conv_bn")
+def _stage_desc(d, conv, bn, Cp, Kp, want_bwd, fwd_packed, bwd_packed, dtype):
+    """Fill the CsStageDesc `d` for one ungrouped Conv2d and allocate what it writes.  bn: the eval-mode BatchNorm2d folded into
+    the operands, or None (scale 1, shift = the convolution's bias or 0).  *_packed: that operand is written in the MFMA-fragment
+    order of the packed-operand kernels (conv_v2.hip).  Returns (w_khwc, w_chwk or None, scale, shift, rstd), the last three [Kp]."""
+    K_, Cin, R, S = conv.weight.shape
+    dev = conv.weight.device
+    bwd_packed = bool(bwd_packed and want_bwd)
+    if (fwd_packed and (Kp % 32 or Cp % 64)) or (bwd_packed and (Cp % 32 or Kp % 64)):
+        raise ValueError("weight staging: packed layouts need 32-row tiles and 64-channel chunks")
+    w_khwc = torch.empty((Kp, R, S, Cp), dtype=dtype, device=dev)
+    w_chwk = torch.empty((Cp, R, S, Kp), dtype=dtype, device=dev) if want_bwd else None
+    vec = torch.empty((3, Kp), dtype=torch.float32, device=dev)
+
+    def ptr(t):
+        return None if t is None else _p(t).value
+
+    d.w, d.conv_bias = ptr(conv.weight), ptr(conv.bias)
+    if bn is not None:
+        d.gamma, d.beta, d.mean, d.var = ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var)
+    else:
+        d.gamma = d.beta = d.mean = d.var = None
+    d.w_khwc, d.w_chwk = ptr(w_khwc), ptr(w_chwk)
+    d.scale, d.shift, d.rstd = ptr(vec[0]), ptr(vec[1]), ptr(vec[2])
+    d.eps = float(bn.eps) if bn is not None else 0.0
+    d.K, d.Cin, d.R, d.S, d.Cp, d.Kp, d.block0 = K_, Cin, R, S, Cp, Kp, 0
+    d.fwd_packed, d.bwd_packed = int(bool(fwd_packed)), int(bwd_packed)
     return w_khwc, w_chwk, vec[0], vec[1], vec[2]
+
+
+def stage_layer(conv, bn, dtype, Cp, Kp, want_bwd=False, fwd_packed=False, bwd_packed=False):
+    """BN fold (bn = None: nothing folded) + both weight operands of ONE ungrouped Conv2d, plain or packed, in one launch whose
+    descriptor travels as the kernel argument (no device table, no copy: it may run inside a stream capture).
+    Returns w_khwc, w_chwk, scale, shift, rstd as _stage_desc does."""
+    d = _lib.CsStageDesc()
+    staged = _stage_desc(d, conv, bn, Cp, Kp, want_bwd, fwd_packed, bwd_packed, dtype)
+    _lib.check(_lib.load().cs_stage_conv_bn_one(ctypes.byref(d), _code(dtype), _stream()), "stage_conv_bn_one")
+    return staged
 
 
 class StagePack:
     """Every Conv2d(+eval-mode BatchNorm2d) of a network staged by ONE launch (cs_stage_conv_bn_multi).
 
-    layers: [(conv, bn, Cp, Kp, want_bwd, fwd_packed, bwd_packed)]; bn = None for a layer whose BatchNorm runs on batch statistics
-    (scale 1, shift = the convolution's bias or 0).  The staging buffers and the device descriptor table are
-    allocated once and rewritten by every launch(); valid() tells whether the parameter tensors are still the ones the table
-    points at.  *_packed: the operand is written in the MFMA-fragment order of the packed-operand kernels (conv_v2.hip)."""
+    layers: [(conv, bn, Cp, Kp, want_bwd, fwd_packed, bwd_packed)] as _stage_desc takes them; bn = None for a layer whose BatchNorm
+    runs on batch statistics.  The staging buffers and the device descriptor table are allocated once and rewritten by every
+    launch(); valid() tells whether the parameter tensors are still the ones the table points at."""
 
     def __init__(self, layers, dtype):
         lib = _lib.load()
@@ -113,31 +140,13 @@ class StagePack:
         self.dtype, self.layers, self.staged = dtype, layers, []
         arr = (_lib.CsStageDesc * len(layers))()
         block = 0
-        for i, (conv, bn, Cp, Kp, want_bwd, pkf, pkb) in enumerate(layers):
-            K_, Cin, R, S = conv.weight.shape
-            w_khwc = torch.empty((Kp, R, S, Cp), dtype=dtype, device=dev)
-            w_chwk = torch.empty((Cp, R, S, Kp), dtype=dtype, device=dev) if want_bwd else None
-            vec = torch.empty((3, Kp), dtype=torch.float32, device=dev)
-            d = arr[i]
-            d.w = conv.weight.data_ptr()
-            if bn is not None:
-                d.gamma, d.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                d.mean, d.var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            else:                                   # a layer whose BatchNorm runs on batch statistics: nothing of it is folded
-                d.gamma = d.beta = d.mean = d.var = None
-            d.conv_bias = conv.bias.data_ptr() if conv.bias is not None else None
-            d.w_khwc, d.w_chwk = w_khwc.data_ptr(), (w_chwk.data_ptr() if want_bwd else None)
-            d.scale, d.shift, d.rstd = vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr()
-            d.eps = float(bn.eps) if bn is not None else 0.0
-            d.K, d.Cin, d.R, d.S, d.Cp, d.Kp, d.block0 = K_, Cin, R, S, Cp, Kp, block
-            d.fwd_packed, d.bwd_packed = int(bool(pkf)), int(bool(pkb and want_bwd))
-            if (pkf and (Kp % 32 or Cp % 64)) or (pkb and want_bwd and (Cp % 32 or Kp % 64)):
-                raise ValueError("StagePack: packed layouts need 32-row tiles and 64-channel chunks")
-            nb = lib.cs_stage_conv_bn_blocks(K_, Cin, R, S, Cp, Kp, 1, 1 if want_bwd else 0)
+        for d, (conv, bn, Cp, Kp, want_bwd, pkf, pkb) in zip(arr, layers):
+            self.staged.append(_stage_desc(d, conv, bn, Cp, Kp, want_bwd, pkf, pkb, dtype))
+            nb = lib.cs_stage_conv_bn_blocks(d.K, d.Cin, d.R, d.S, Cp, Kp, 1, 1 if want_bwd else 0)
             if nb < 1:
                 raise ValueError("StagePack: bad layer extents")
+            d.block0 = block
             block += nb
-            self.staged.append((w_khwc, w_chwk, vec[0], vec[1], vec[2]))
         self.total_blocks = block
         self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         self.key = self._key()

@@ -111,37 +111,38 @@ int cs_bn_bwd_apply(const void* dy, const void* z, int dtype, const float* mean,
                     const float* gamma, const float* beta, int act, const double* sums, long long M, int C, void* dz,
                     float* dgamma, float* dbeta, void* stream);
 
-/* ---- weight staging -------------------------------------------------------------------------
- * w[K][Cin][R][S] fp32 (torch Conv2d.weight) times optional per-K `scale` ->
+/* ---- weight staging of an ungrouped convolution ---------------------------------------------
+ * w[K][Cin][R][S] fp32 (torch Conv2d.weight) times the per-K scale of a folded eval-mode BatchNorm2d, gamma/sqrt(var + eps), ->
  *   w_khwc [Kp][R][S][Cp]  (forward operand)   if non-NULL
  *   w_chwk [Cp][R][S][Kp]  (dgrad operand)     if non-NULL
- * Cp/Kp = stored (padded) channel counts; padded rows/columns are zero-filled. */
-int cs_weight_prep(const float* w, const float* scale, int dtype, int K, int Cin, int R, int S, int Cp, int Kp,
-                   void* w_khwc, void* w_chwk, void* stream);
-
-/* cs_bn_fold + cs_weight_prep in one launch for an eval-mode Conv2d+BatchNorm2d (scale/shift/rstd are [Kp]). */
-int cs_stage_conv_bn(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
-                     const float* conv_bias, int dtype, int K, int Cin, int R, int S, int Cp, int Kp, void* w_khwc,
-                     void* w_chwk, float* scale, float* shift, float* rstd, void* stream);
-
-/* The same for EVERY eval-mode Conv2d+BatchNorm2d of a network in ONE launch (a training step re-stages all ~53 layers of a
- * ResNet-50 after each optimizer update: 53 launches of ~7 us otherwise).  `desc` is a DEVICE array of n descriptors, built once
- * by the host for a fixed set of parameter / staging buffers; block0 = prefix sum of cs_stage_conv_bn_blocks() over the layers,
- * total_blocks = the sum. */
+ * Cp/Kp = stored (padded) channel counts; padded rows/columns are zero-filled.  One descriptor per layer; ONE kernel body serves
+ * every entry below, so their outputs agree bit for bit. */
 typedef struct CsStageDesc {
-    const float *w, *gamma, *beta, *mean, *var, *conv_bias;   /* gamma / beta / conv_bias nullable; mean == var == NULL: no BatchNorm is folded
-                                                                 * (train-mode BN layers: scale = 1, shift = conv_bias or 0) */
+    const float *w, *gamma, *beta, *mean, *var, *conv_bias;   /* gamma / beta / conv_bias nullable; mean == var == NULL: no statistics are folded
+                                                                 * (rstd = 1; a train-mode BN layer passes gamma = beta = NULL too:
+                                                                 * scale = 1, shift = conv_bias or 0) */
     void *w_khwc, *w_chwk;                                     /* either nullable */
-    float *scale, *shift, *rstd;                               /* [Kp] */
+    float *scale, *shift, *rstd;                               /* [Kp], rows k >= K zero; each nullable (not wanted) in cs_stage_conv_bn_one */
     float eps;
     int32_t K, Cin, R, S, Cp, Kp;
-    int32_t block0;
-    /* nonzero: write that operand in the MFMA-fragment order cs_conv2d_fwd_packed / cs_conv2d_dgrad_packed read (what
-     * cs_pack_conv_weights produces from the plain layout; needs Kp % 32 == 0 and Cp % 64 == 0 for fwd, Cp % 32 == 0 and
-     * Kp % 64 == 0 for bwd) instead of w_khwc / w_chwk order; the buffer sizes are the same */
+    int32_t block0;                                            /* cs_stage_conv_bn_multi only: first workgroup of this layer */
+    /* nonzero: write that operand in the MFMA-fragment order cs_conv2d_fwd_packed / cs_conv2d_dgrad_packed read instead of
+     * w_khwc / w_chwk order (needs Kp % 32 == 0 and Cp % 64 == 0 for fwd, Cp % 32 == 0 and Kp % 64 == 0 for bwd); the buffer
+     * sizes are the same.  cs_pack_conv_weights, the independent implementation of that order, gives the same bits from the plain
+     * operand. */
     int32_t fwd_packed, bwd_packed;
 } CsStageDesc;
+/* Workgroups that stage one layer (both launch shapes below size their grids with it); 0 for bad extents. */
 int cs_stage_conv_bn_blocks(int K, int Cin, int R, int S, int Cp, int Kp, int want_fwd, int want_bwd);
+/* One layer in one launch: BN fold (scale/shift/rstd as cs_bn_fold computes them) + both operands, plain or packed.  `host_desc` is
+ * read on the HOST and travels as the kernel argument: no device table, no copy, so the call may sit inside a stream capture. */
+int cs_stage_conv_bn_one(const CsStageDesc* host_desc, int dtype, void* stream);
+/* The plain operands only, times an optional per-K `scale`: cs_stage_conv_bn_one with gamma = scale and nothing else set. */
+int cs_weight_prep(const float* w, const float* scale, int dtype, int K, int Cin, int R, int S, int Cp, int Kp,
+                   void* w_khwc, void* w_chwk, void* stream);
+/* EVERY layer of a network in ONE launch (a training step re-stages all ~53 layers of a ResNet-50 after each optimizer update:
+ * 53 launches of ~7 us otherwise).  `desc` is a DEVICE array of n descriptors, built once by the host for a fixed set of
+ * parameter / staging buffers; block0 = prefix sum of cs_stage_conv_bn_blocks() over the layers, total_blocks = the sum. */
 int cs_stage_conv_bn_multi(const CsStageDesc* desc, int n, int total_blocks, int dtype, void* stream);
 
 /* ---- convolution family (implicit GEMM on MFMA) ---------------------------------------------
@@ -406,9 +407,12 @@ int cs_segmented_topk(const float* probs, const int32_t* groups, const int32_t* 
  * tile in LDS), weights streamed to registers in MFMA-fragment order and a register-direct epilogue.  CS_BF16 only.
  *   cs_conv2d_packed_supported : 1 when the geometry is served (3x3, stride 1, channel counts multiples of 64, operand < 2 GiB, ...);
  *                                otherwise use cs_conv2d_fwd / cs_conv2d_dgrad with the plain staged weights.  dgrad: 0 = forward, 1 = data gradient.
- *   cs_pack_conv_weights       : staged weights (w_khwc for forward, w_chwk for the data gradient, as cs_weight_prep /
- *                                cs_stage_conv_bn* write them) -> fragment order [32-row tile][64-ch chunk][tap][16-deep step][lane][8],
- *                                cs_conv2d_packed_weight_bytes() bytes; the data-gradient form mirrors the taps.
+ *   cs_pack_conv_weights       : plain staged weights (w_khwc for forward, w_chwk for the data gradient, as cs_weight_prep /
+ *                                cs_stage_conv_bn_* write them) -> fragment order [32-row tile][64-ch chunk][tap][16-deep step][lane][8],
+ *                                cs_conv2d_packed_weight_bytes() bytes; the data-gradient form mirrors the taps.  A second launch per
+ *                                operand: the staging entries write this order themselves (CsStageDesc.fwd_packed / bwd_packed).
+ *                                This one packs what they do not stage (the stem's 256-column operand) and is the independent
+ *                                statement of the order that the tests hold them against.
  *   cs_conv2d_fwd_packed       : y = act(conv(x, w) + shift[k] + residual); positive_bits (nullable) as cs_conv2d_fwd_bits.
  *   cs_conv2d_dgrad_packed     : dx = (conv_transpose(dy, w) + add) masked by mask_bits (nullable, as cs_conv2d_dgrad_bits);
  *                                partial_rows (nullable): fp32 [cs_conv2d_packed_partial_rows(g, 1)][2][C] per-workgroup column

@@ -185,3 +185,20 @@ def assert_exact_domain(stored=(), abs_sums=(), stats_of=None, colsum_of=None, h
         assert _is_multiple_of(d, unit), "exact domain: column sums of non-integers"
         assert TILE_ROWS * float(d.abs().max()) < LIMIT, f"exact domain: 128 * max |dx| = {TILE_ROWS * float(d.abs().max())} reaches 2^24"
         assert float(d.abs().sum(dim=(0, 2, 3)).max()) < LIMIT, "exact domain: a column sum reaches 2^24 (fp32 result vector)"
+
+
+# ------------------------------------------------------------------------------------------------ staged weight operands
+def staged_operands(w, scale, dtype, Cp, Kp):
+    """The plain staged operands of w[K][C][R][S] (fp32) from their definition, in torch on w's device: every element is the fp32
+    product w * scale[k] (scale None: w itself) rounded once to `dtype`, laid out as w_khwc [Kp][R][S][Cp] and w_chwk [Cp][R][S][Kp]
+    with exact zeros in the padding.  One IEEE multiplication and one round-to-nearest-even: a kernel owes the same bits."""
+    K, C = w.shape[:2]
+    v = (w if scale is None else w * scale[:, None, None, None]).to(dtype)
+    v = F.pad(v, (0, 0, 0, 0, 0, Cp - C, 0, Kp - K))
+    return v.permute(0, 2, 3, 1).contiguous(), v.permute(1, 2, 3, 0).contiguous()
+
+
+def same_bits(a, b):
+    """bit equality of two tensors of one dtype and element count (0.0 and -0.0 differ, equal NaN patterns agree)"""
+    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    return a.dtype == b.dtype and a.numel() == b.numel() and torch.equal(a.reshape(-1).view(it), b.reshape(-1).view(it))

@@ -350,8 +350,8 @@ def test_wave_specialised_weight_gradient_on_every_shape(dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(70, 100, 3, 72, 104), (600, 520, 3, 608, 520), (512, 1024, 3, 512, 1024), (128, 96, 1, 128, 96), (40, 328, 5, 40, 328), (2048, 1024, 1, 2048, 1024), (2050, 1030, 1, 2056, 1032)])
 def test_weight_prep_tiled_layouts(shape, dev):
-    """The LDS-tiled bf16 weight staging (prep.hip weight_prep_tiled_kernel) against a permute: both layouts, padded channels zero,
-    per-filter scale applied before the rounding."""
+    """The bf16 weight staging of large tensors (prep.hip: the LDS tile of the staging body for unpadded layers, element by element
+    for padded ones) against a permute: both layouts, padded channels zero, per-filter scale applied before the rounding."""
     Kc, Cin, R, Kp, Cp = shape
     g = torch.Generator().manual_seed(Kc * 13 + Cin)
     w = torch.randn((Kc, Cin, R, R), generator=g)

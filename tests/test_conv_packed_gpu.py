@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from conv_ref import sparse_pm1 as _sparse_pm1  # noqa: E402
+from conv_ref import sparse_pm1 as _sparse_pm1, staged_operands as _staged_operands  # noqa: E402
 
 from cellsegmentation_amd import kernels as K  # noqa: E402
 
@@ -186,8 +186,10 @@ def test_compact_strided_gradient(shape, dev):
 
 @pytest.mark.parametrize("shape", [(128, 64, 3), (64, 256, 1), (256, 128, 3), (512, 2048, 1), (64, 64, 3)])
 def test_one_launch_staging_writes_the_packed_operands_bit_exactly(shape, dev):
-    """cs_stage_conv_bn_multi (LDS-tiled path for unpadded packed layers) against the two-step route: fold + stage with
-    cs_stage_conv_bn, then cs_pack_conv_weights -- the same arithmetic, so the packed operands must be identical bit for bit."""
+    """cs_stage_conv_bn_multi (LDS-tiled path for unpadded packed layers) against the operands' definition.  K.weight_prep runs the
+    same kernel body as the launch under test, so it is no reference: the plain operands come from torch (conv_ref.staged_operands:
+    one fp32 product, one rounding to bf16), the packed ones from cs_pack_conv_weights -- the independent statement of the packed
+    order -- applied to that reference.  The multi launch and K.weight_prep must both give those bits."""
     Kc, C, R = shape
     torch.manual_seed(Kc + C + R)
     conv = torch.nn.Conv2d(C, Kc, R, 1, R // 2, bias=False).to(dev)
@@ -201,13 +203,15 @@ def test_one_launch_staging_writes_the_packed_operands_bit_exactly(shape, dev):
     geom = K.make_geom(2, 19, 19, C, Kc, R, R, 1, R // 2)
     scale_ref = bn.weight.detach() * (1.0 / torch.sqrt(bn.running_var + bn.eps))          # the kernels' own expression
     w_khwc, w_chwk = K.weight_prep(conv.weight.detach(), scale_ref, BF, C, Kc, want_fwd=True, want_bwd=True)
-    ref_f = K.pack_conv_weights(geom, w_khwc, dgrad=False)
-    ref_b = K.pack_conv_weights(geom, w_chwk, dgrad=True)
+    t_khwc, t_chwk = _staged_operands(conv.weight.detach(), scale_ref, BF, C, Kc)
+    ref_f = K.pack_conv_weights(geom, t_khwc, dgrad=False)
+    ref_b = K.pack_conv_weights(geom, t_chwk, dgrad=True)
     torch.cuda.synchronize()
     assert torch.equal(w_f.view(-1).view(torch.int16), ref_f.view(-1).view(torch.int16)[: w_f.numel()])
     assert torch.equal(w_b.view(-1).view(torch.int16), ref_b.view(-1).view(torch.int16)[: w_b.numel()])
     assert float((scale - scale_ref).abs().max()) < 1e-6
-    assert torch.equal(u_f.view(torch.int16), w_khwc.view(torch.int16)) and torch.equal(u_b.view(torch.int16), w_chwk.view(torch.int16))
+    assert torch.equal(u_f.view(torch.int16), t_khwc.view(torch.int16)) and torch.equal(u_b.view(torch.int16), t_chwk.view(torch.int16))
+    assert torch.equal(w_khwc.view(torch.int16), t_khwc.view(torch.int16)) and torch.equal(w_chwk.view(torch.int16), t_chwk.view(torch.int16))
 
 
 @pytest.mark.parametrize("shape", SHAPES)

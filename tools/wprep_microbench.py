@@ -1,5 +1,4 @@
-"""Timing of cs_weight_prep (fp32 [K][C][R][S] -> bf16 [K][R][S][C] and [C][R][S][K]) on the segmentation decoder's layers.
-CELLSEG_WPREP_UNTILED=1 selects the element-per-thread kernel for A/B."""
+"""Timing of cs_weight_prep (fp32 [K][C][R][S] -> bf16 [K][R][S][C] and [C][R][S][K]) on the segmentation decoder's layers."""
 import os
 import sys
 
