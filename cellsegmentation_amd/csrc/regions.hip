@@ -1,0 +1,384 @@
+// Small-region clean-up of binary masks (utils/image_processing.py:14-17 remove_small_regions = skimage remove_small_objects, then
+// remove_small_holes; both are scipy.ndimage.label + an area filter):
+//   label     every pixel gets the lowest row-major index of its component of EQUAL-VALUED neighbours (4- or 8-neighbourhood), so
+//             one pass labels the foreground components and the background components at once:
+//               tiles   a 64 x 64 tile per workgroup, union-find in LDS, flattened; the tile-local pixel count of every tile-local
+//                       root is left in the area array at the root's slot (0 elsewhere)
+//               borders one thread per pixel of a tile's first row / first column unites across the tile edge (and, with
+//                       connectivity 2, across the corner) with global atomicMin hooks
+//               flatten every pixel takes its root; a tile-local root that is no longer a root adds its count to the root's slot
+//   filter    out = the other value where the pixel has the wanted value and area[root] < threshold (strict), else the input
+//   number    scipy's numbering of the foreground: 1 + the number of foreground roots with a lower index in the same image
+// Hooks only ever lower a label and a label is always an index of the same component, so the root of a component is its lowest
+// index whatever order the hooks land in; areas are integer sums.  The result does not depend on launch order.  Every union loop
+// lowers max(a, b) in each turn that does not end it, so it is bounded by the index range; nothing waits on another thread.
+// The number of launches depends on (N, H, W) only and nothing synchronises with the host.
+#include <stdio.h>
+#include "cs_common.h"
+
+namespace {
+
+constexpr int kT = 64;                 // tile edge
+constexpr int kTP = kT * kT;           // pixels per tile
+constexpr int kPer = kTP / 256;        // pixels per thread of the tile kernel
+constexpr int kNB = 1024;              // pixels per block of the numbering kernels
+
+__device__ __forceinline__ int find_lds(const int* lab, int x) {
+    int q;
+    while ((q = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != x) x = q;
+    return x;
+}
+__device__ __forceinline__ void unite_lds(int* lab, int a, int b) {
+    for (;;) {
+        a = find_lds(lab, a);
+        b = find_lds(lab, b);
+        if (a == b) return;
+        const int hi = max(a, b), lo = min(a, b);
+        const int old = atomicMin(lab + hi, lo);
+        if (old == hi) return;         // hi was a root and now hangs below lo
+        a = old;                       // hi had a parent already: that parent and lo are still to be united
+        b = lo;
+    }
+}
+__device__ __forceinline__ int find_global(const int32_t* lab, int x) {
+    int q;
+    while ((q = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != x) x = q;
+    return x;
+}
+__device__ __forceinline__ void unite_global(int32_t* lab, int a, int b) {
+    for (;;) {
+        a = find_global(lab, a);
+        b = find_global(lab, b);
+        if (a == b) return;
+        const int hi = max(a, b), lo = min(a, b);
+        const int old = __hip_atomic_fetch_min(lab + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == hi) return;
+        a = old;
+        b = lo;
+    }
+}
+
+// grid (tiles across, tiles down, N).  val: 0 / 1 = the pixel's value, 2 = outside the image.
+template <int CONN>
+__global__ __launch_bounds__(256) void tile_label_kernel(const uint8_t* __restrict__ m, int H, int W, int32_t* __restrict__ lab_g,
+                                                         int32_t* __restrict__ cnt_g) {
+    __shared__ int lab[kTP];
+    __shared__ int cnt[kTP];
+    __shared__ uint8_t val[kTP];
+    const int c0 = blockIdx.x * kT, r0 = blockIdx.y * kT;
+    const long long img = (long long)blockIdx.z * H * W;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        const int r = r0 + (i >> 6), c = c0 + (i & 63);
+        val[i] = (r < H && c < W) ? (uint8_t)(m[img + (long long)r * W + c] != 0) : (uint8_t)2;
+        lab[i] = i;
+        cnt[i] = 0;
+    }
+    __syncthreads();
+    for (int k = 0; k < kPer; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        const int ly = i >> 6, lx = i & 63;
+        const int v = val[i];
+        if (v == 2) continue;
+        if (lx > 0 && val[i - 1] == v) unite_lds(lab, i, i - 1);
+        if (ly > 0) {
+            if (val[i - kT] == v) unite_lds(lab, i, i - kT);
+            if (CONN == 2) {
+                if (lx > 0 && val[i - kT - 1] == v) unite_lds(lab, i, i - kT - 1);
+                if (lx < kT - 1 && val[i - kT + 1] == v) unite_lds(lab, i, i - kT + 1);
+            }
+        }
+    }
+    __syncthreads();
+    int root[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        root[k] = val[i] == 2 ? -1 : find_lds(lab, i);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        // a wave covers one tile row: where the whole row lies in one component, one add of 64 instead of 64 adds of 1
+        const int first = __builtin_amdgcn_readfirstlane(root[k]);
+        if (__all(root[k] == first)) {
+            if (first >= 0 && (threadIdx.x & 63) == 0) atomicAdd(cnt + first, 64);
+        } else if (root[k] >= 0) {
+            atomicAdd(cnt + root[k], 1);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        if (root[k] < 0) continue;
+        const int i = threadIdx.x + 256 * k;
+        const long long p = img + (long long)(r0 + (i >> 6)) * W + c0 + (i & 63);
+        lab_g[p] = (int32_t)(img + (long long)(r0 + (root[k] >> 6)) * W + c0 + (root[k] & 63));
+        cnt_g[p] = root[k] == i ? cnt[i] : 0;
+    }
+}
+
+// One thread per pixel of every tile's first row (rows 64, 128, ...) and first column (columns 64, 128, ...).
+template <int CONN>
+__global__ __launch_bounds__(256) void border_kernel(const uint8_t* __restrict__ m, int N, int H, int W, int32_t* __restrict__ lab) {
+    const long long n_row = (long long)((H - 1) / kT) * W, n_col = (long long)((W - 1) / kT) * H;
+    const long long per = n_row + n_col, total = per * N;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
+        const long long n = g / per;
+        long long e = g - n * per;
+        const long long base = n * H * W;
+        auto join = [&](long long p, long long q, bool v) {
+            if ((m[q] != 0) == v) unite_global(lab, (int)p, (int)q);
+        };
+        if (e < n_row) {
+            const int r = ((int)(e / W) + 1) * kT, c = (int)(e % W);
+            const long long p = base + (long long)r * W + c;
+            const bool v = m[p] != 0;
+            join(p, p - W, v);
+            if (CONN == 2) {
+                if (c > 0) join(p, p - W - 1, v);
+                if (c < W - 1) join(p, p - W + 1, v);
+            }
+        } else {
+            e -= n_row;
+            const int c = ((int)(e / H) + 1) * kT, r = (int)(e % H);
+            const long long p = base + (long long)r * W + c;
+            const bool v = m[p] != 0;
+            join(p, p - 1, v);
+            if (CONN == 2) {
+                if (r > 0) join(p, p - W - 1, v);
+                if (r < H - 1) join(p, p + W - 1, v);
+            }
+        }
+    }
+}
+
+// lab[p] = root; the count a tile left at p moves to the root's slot (nothing is ever added to a slot that is not a root)
+__global__ __launch_bounds__(256) void flatten_kernel(long long total, int32_t* __restrict__ lab, int32_t* __restrict__ cnt) {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+        const int root = find_global(lab, (int)p);
+        __hip_atomic_store(lab + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int c = cnt[p];
+        if (c != 0 && root != (int)p) atomicAdd(cnt + root, c);
+    }
+}
+
+__global__ __launch_bounds__(256) void filter_kernel(const uint8_t* m, long long total, const int32_t* __restrict__ lab,
+                                                     const int32_t* __restrict__ cnt, int value, int min_area, uint8_t* out) {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+        const int v = m[p] != 0;
+        out[p] = (uint8_t)((v == value && cnt[lab[p]] < min_area) ? 1 - value : v);
+    }
+}
+
+__global__ __launch_bounds__(256) void spread_kernel(const uint8_t* __restrict__ m, long long total, const int32_t* __restrict__ lab,
+                                                     const int32_t* __restrict__ table, int foreground_only, int32_t* __restrict__ out) {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256)
+        out[p] = (foreground_only && m[p] == 0) ? 0 : table[lab[p]];
+}
+
+// ---- scipy's numbering: grid (blocks per image, N), kNB pixels per block --------------------------------------------------------
+__device__ __forceinline__ bool is_fg_root(const uint8_t* m, const int32_t* lab, long long HW, long long i, long long base) {
+    return i < HW && m[base + i] != 0 && lab[base + i] == (int32_t)(base + i);
+}
+
+__global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab, long long HW,
+                                                           int32_t* __restrict__ blk) {
+    __shared__ int wsum[kNB / 64];
+    const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
+    const unsigned long long bal = __ballot(is_fg_root(m, lab, HW, i, blockIdx.y * HW));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kNB / 64; ++w) t += wsum[w];
+        blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// one workgroup per image: blk[n][0..B) -> its exclusive prefix sums, in place
+__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B) {
+    __shared__ int part[1024];
+    int32_t* blk = blk_all + (long long)blockIdx.x * B;
+    const int seg = (B + 1023) / 1024;
+    const int lo = min((int)threadIdx.x * seg, B), hi = min(lo + seg, B);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += blk[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;
+    for (int i = lo; i < hi; ++i) {
+        const int v = blk[i];
+        blk[i] = run;
+        run += v;
+    }
+}
+
+__global__ __launch_bounds__(kNB) void number_assign_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab, long long HW,
+                                                            const int32_t* __restrict__ blk, int32_t* __restrict__ num) {
+    __shared__ int wsum[kNB / 64];
+    const long long base = blockIdx.y * HW;
+    const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
+    const bool root = is_fg_root(m, lab, HW, i, base);
+    const unsigned long long bal = __ballot(root);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) wsum[wv] = __popcll(bal);
+    __syncthreads();
+    if (!root) return;
+    int off = blk[(long long)blockIdx.y * gridDim.x + blockIdx.x];
+    for (int w = 0; w < wv; ++w) off += wsum[w];
+    num[base + i] = off + __popcll(bal & ((1ull << lane) - 1ull)) + 1;
+}
+
+__global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ p, long long n, float thr, uint8_t* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) out[i] = (uint8_t)(p[i] > thr);
+}
+
+__global__ __launch_bounds__(256) void hsv_gate_kernel(const uint8_t* __restrict__ rgb, const uint8_t* mask, long long n, int v_max,
+                                                       uint8_t* out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const uint8_t* px = rgb + 3 * i;
+        const int v = max(max((int)px[0], (int)px[1]), (int)px[2]);
+        out[i] = (uint8_t)(mask[i] != 0 && v <= v_max);
+    }
+}
+
+inline unsigned grid_for(long long n) {
+    long long b = (n + 255) / 256;
+    if (b < 1) b = 1;
+    return (unsigned)(b > 16384 ? 16384 : b);
+}
+inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline long long blocks_per_image(int H, int W) { return ((long long)H * W + kNB - 1) / kNB; }
+
+struct Ws {
+    int32_t *lab, *cnt, *blk;
+};
+
+bool sizes_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31); }
+
+// labels and areas of `m` into ws.lab / ws.cnt (cnt holds the area at every root's slot)
+int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws& ws, hipStream_t st) {
+    const dim3 tiles(cs_ceil_div(W, kT), cs_ceil_div(H, kT), N);
+    const long long total = (long long)N * H * W;
+    const long long edges = ((long long)((H - 1) / kT) * W + (long long)((W - 1) / kT) * H) * N;
+    if (connectivity == 2) {
+        hipLaunchKernelGGL(tile_label_kernel<2>, tiles, dim3(256), 0, st, m, H, W, ws.lab, ws.cnt);
+        CS_LAUNCH_CHECK();
+        if (edges > 0) hipLaunchKernelGGL(border_kernel<2>, dim3(grid_for(edges)), dim3(256), 0, st, m, N, H, W, ws.lab);
+    } else {
+        hipLaunchKernelGGL(tile_label_kernel<1>, tiles, dim3(256), 0, st, m, H, W, ws.lab, ws.cnt);
+        CS_LAUNCH_CHECK();
+        if (edges > 0) hipLaunchKernelGGL(border_kernel<1>, dim3(grid_for(edges)), dim3(256), 0, st, m, N, H, W, ws.lab);
+    }
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(flatten_kernel, dim3(grid_for(total)), dim3(256), 0, st, total, ws.lab, ws.cnt);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+int carve(const char* what, int N, int H, int W, int connectivity, const void* in, const void* out, void* workspace, size_t bytes, Ws* ws) {
+    static thread_local char msg[160];
+    auto fail = [&](const char* why) {
+        snprintf(msg, sizeof(msg), "%s: %s", what, why);
+        cs_set_error_(msg);
+        return CS_ERR_INVALID_ARG;
+    };
+    if (!in || !out || !workspace) return fail("NULL argument");
+    if (!sizes_ok(N, H, W)) return fail("need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    if (connectivity != 1 && connectivity != 2) return fail("connectivity must be 1 or 2");
+    if (bytes < cs_regions_workspace(N, H, W)) return fail("workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("misaligned workspace");
+    const size_t t = (size_t)N * H * W;
+    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+    ws->lab = reinterpret_cast<int32_t*>(w);  w += align16(t * 4);
+    ws->cnt = reinterpret_cast<int32_t*>(w);  w += align16(t * 4);
+    ws->blk = reinterpret_cast<int32_t*>(w);
+    return CS_OK;
+}
+
+}  // namespace
+
+// workspace: lab, cnt (int32 N H W each), blk (int32 N ceil(H W / 1024))
+extern "C" size_t cs_regions_workspace(int N, int H, int W) {
+    if (!sizes_ok(N, H, W)) return 0;
+    const size_t t = (size_t)N * H * W;
+    return 2 * align16(t * 4) + align16((size_t)N * blocks_per_image(H, W) * 4);
+}
+
+extern "C" int cs_regions_label(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* labels, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_label", N, H, W, connectivity, mask, labels, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    const long long HW = (long long)H * W;
+    const int B = (int)blocks_per_image(H, W);
+    hipLaunchKernelGGL(number_count_kernel, dim3(B, N), dim3(kNB), 0, st, mask, ws.lab, HW, ws.blk);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(number_scan_kernel, dim3(N), dim3(1024), 0, st, ws.blk, B);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(number_assign_kernel, dim3(B, N), dim3(kNB), 0, st, mask, ws.lab, HW, ws.blk, ws.cnt);   // cnt: number of every root
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spread_kernel, dim3(grid_for(N * HW)), dim3(256), 0, st, mask, N * HW, ws.lab, ws.cnt, 1, labels);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_areas(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* areas, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_areas", N, H, W, connectivity, mask, areas, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    const long long total = (long long)N * H * W;
+    hipLaunchKernelGGL(spread_kernel, dim3(grid_for(total)), dim3(256), 0, st, mask, total, ws.lab, ws.cnt, 0, areas);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_filter(const uint8_t* mask, int N, int H, int W, int connectivity, int value, int min_area, uint8_t* out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_filter", N, H, W, connectivity, mask, out, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    CS_CHECK_ARG((value == 0 || value == 1) && min_area >= 0, "regions_filter: value must be 0 or 1 and min_area non-negative");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    const long long total = (long long)N * H * W;
+    hipLaunchKernelGGL(filter_kernel, dim3(grid_for(total)), dim3(256), 0, st, mask, total, ws.lab, ws.cnt, value, min_area, out);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_remove_small(const uint8_t* mask, int N, int H, int W, int min_object_size, int hole_area_threshold,
+                                       int connectivity, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = cs_regions_filter(mask, N, H, W, connectivity, 1, min_object_size, out, workspace, workspace_bytes, stream);
+    if (rc != CS_OK) return rc;
+    return cs_regions_filter(out, N, H, W, connectivity, 0, hole_area_threshold, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cs_regions_threshold(const float* probs, long long n, float threshold, uint8_t* out, void* stream) {
+    CS_CHECK_ARG(probs && out && n > 0, "regions_threshold: bad arguments");
+    hipLaunchKernelGGL(threshold_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), probs, n, threshold, out);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_hsv_gate(const uint8_t* images_hwc, const uint8_t* mask, long long n_pixels, int v_max, uint8_t* out,
+                                   void* stream) {
+    CS_CHECK_ARG(images_hwc && mask && out && n_pixels > 0, "regions_hsv_gate: bad arguments");
+    hipLaunchKernelGGL(hsv_gate_kernel, dim3(grid_for(n_pixels)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), images_hwc, mask,
+                       n_pixels, v_max, out);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}

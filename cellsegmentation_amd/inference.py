@@ -169,3 +169,26 @@ def detect_cells(loader, model, device, eps=11, reg_limit=False, **blur):
                             opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False)
             out.extend(res.per_image())
     return out
+
+
+def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):
+    """Cleaned binary masks per image (test_seg.py:515-527): segment-mode forward, softmax channel 1, ``> threshold`` (compared in
+    float32, as numpy does for a float32 map), ``remove_small_regions(., 300, 100)``.  With reg_limit the map of an image whose
+    image-mode count rint(reg) is 0 is zeroed first (:518-524; the model is set back to segment mode afterwards).  Returns a device
+    ``torch.bool`` tensor [len(dataset), H, W], ready for ``metrics.dice_coef``."""
+    from . import regions as Rg
+    mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
+    model.eval()
+    out = []
+    with torch.no_grad():
+        for i, data in enumerate(tqdm(loader, desc="image segmenting")):
+            x = data.to(device)
+            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+            if reg_limit:
+                model.setmode("image")
+                counts = torch.round(model(x)[1].detach()[:, 0].float())
+                model.setmode("segment")
+                probs = probs * (counts != 0).to(probs.dtype)[:, None, None]
+            classes = Rg.threshold(probs, threshold)
+            out.append(Rg.remove_small_regions(classes, mo, ho, out=classes))
+    return torch.cat(out) if out else torch.zeros((0,), dtype=torch.bool, device=device)

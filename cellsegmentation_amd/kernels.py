@@ -1134,3 +1134,78 @@ def detect_cluster(pts, n_pts, eps, blurred, force_global=False):
     _lib.check(lib.cs_detect_cluster(_p(pts.contiguous()), _p(n_pts.contiguous()), N, cap, float(eps), _p(blurred.contiguous()), H, W,
                                      int(bool(force_global)), _p(out_pts), _p(out_w), _p(out_off), _p(ws), ws_bytes, _stream()), "detect_cluster")
     return out_pts, out_w, out_off
+
+
+# ---------------------------------------------------------------- small-region clean-up (csrc/regions.hip; regions.py is the public API)
+def regions_workspace(N, H, W, device):
+    """the caller-owned scratch of one cs_regions_* call on [N,H,W] (reusable by later calls of the same shape)"""
+    ws_bytes = _lib.load().cs_regions_workspace(N, H, W)
+    if ws_bytes == 0:
+        raise ValueError(f"regions: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels, got {(N, H, W)}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+
+
+def _regions_args(mask, ws):
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise TypeError("regions kernels read uint8 [N,H,W] masks")
+    N, H, W = mask.shape
+    if ws is None:
+        ws = regions_workspace(N, H, W, mask.device)
+    return N, H, W, ws
+
+
+def regions_label(mask, connectivity=1, out=None, ws=None):
+    """uint8 [N,H,W] -> int32 [N,H,W] scipy.ndimage.label per image"""
+    N, H, W, ws = _regions_args(mask, ws)
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().cs_regions_label(_p(mask), N, H, W, int(connectivity), _p(out), _p(ws), ws.numel(), _stream()), "regions_label")
+    return out
+
+
+def regions_areas(mask, connectivity=1, out=None, ws=None):
+    """uint8 [N,H,W] -> int32 [N,H,W]: the area of the component of equal-valued pixels under every pixel"""
+    N, H, W, ws = _regions_args(mask, ws)
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().cs_regions_areas(_p(mask), N, H, W, int(connectivity), _p(out), _p(ws), ws.numel(), _stream()), "regions_areas")
+    return out
+
+
+def regions_filter(mask, value, min_area, connectivity=1, out=None, ws=None):
+    """components of `value` (0 / 1) smaller than min_area flipped; out may be mask itself"""
+    N, H, W, ws = _regions_args(mask, ws)
+    if out is None:
+        out = torch.empty_like(mask)
+    _lib.check(_lib.load().cs_regions_filter(_p(mask), N, H, W, int(connectivity), int(value), int(min_area), _p(out), _p(ws), ws.numel(),
+                                             _stream()), "regions_filter")
+    return out
+
+
+def regions_remove_small(mask, min_object_size, hole_area_threshold, connectivity=1, out=None, ws=None):
+    """remove_small_objects then remove_small_holes of the result; out may be mask itself"""
+    N, H, W, ws = _regions_args(mask, ws)
+    if out is None:
+        out = torch.empty_like(mask)
+    _lib.check(_lib.load().cs_regions_remove_small(_p(mask), N, H, W, int(min_object_size), int(hole_area_threshold), int(connectivity), _p(out),
+                                                   _p(ws), ws.numel(), _stream()), "regions_remove_small")
+    return out
+
+
+def regions_threshold(probs, threshold):
+    """fp32 probabilities of any shape -> uint8 (probs > float32(threshold)), same shape"""
+    _f32(probs)
+    out = torch.empty(probs.shape, dtype=torch.uint8, device=probs.device)
+    if probs.numel():
+        _lib.check(_lib.load().cs_regions_threshold(_p(probs), probs.numel(), float(threshold), _p(out), _stream()), "regions_threshold")
+    return out
+
+
+def regions_hsv_gate(images_hwc, mask, v_max=170):
+    """images uint8 [..., 3], mask uint8 [...] -> uint8 (mask != 0) & (max over the 3 channels <= v_max)"""
+    if images_hwc.dtype != torch.uint8 or mask.dtype != torch.uint8 or tuple(images_hwc.shape) != tuple(mask.shape) + (3,):
+        raise TypeError("regions_hsv_gate: expected uint8 images [..., 3] and a uint8 mask of the leading shape")
+    out = torch.empty_like(mask)
+    if mask.numel():
+        _lib.check(_lib.load().cs_regions_hsv_gate(_p(images_hwc), _p(mask), mask.numel(), int(v_max), _p(out), _stream()), "regions_hsv_gate")
+    return out

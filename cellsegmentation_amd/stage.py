@@ -3,8 +3,9 @@
 * ``make_train_data``  -- dataset/dataset.py:166-201 (label assignment, shuffle, pos/neg re-balancing of the selected tiles)
 * ``evaluate_tile``    -- evaluate.py:8-27 (+ metrics/metrics.py:7-16 ``calc_err``)
 * ``rank``             -- the tile ranking inside train_seg.py:234-249
-* ``generate_masks``   -- utils/image_processing.py:79-98 (square painting only; the HSV / small-region clean-up and the PNG
-                          writing stay on the CPU as in the reference)
+* ``generate_masks``   -- utils/image_processing.py:79-111 (square painting and, with ``preprocess=``, the clean-up below; only
+                          the PNG writing stays on the host)
+* ``preprocess_masks`` -- utils/image_processing.py:114-124 (HSV value gate + small-region clean-up, ``regions.py``)
 
 Index bookkeeping that is O(#images) stays in numpy on the host (as in ``inference.selection_plan``); everything that is
 O(#tiles) or O(#pixels) runs in HIP kernels (`csrc/topk.hip`).  The shuffle of ``make_train_data`` is an explicit permutation:
@@ -47,9 +48,34 @@ def rank(tile_idx, tiles_grid, probs, threshold, device=None):
     return tiles[sel], p.cpu().numpy()[sel], np.asarray(tile_idx)[sel]
 
 
-def generate_masks(n_images, image_size, tile_size, tile_idx, tiles_grid, selected, device=None):
-    """utils/image_processing.py:90-98: uint8 [n_images, H, W] DEVICE tensor with a tile_size^2 square of ones for every selected
-    tile (`selected` = indices into tile_idx / tiles_grid, e.g. the positions `rank` kept)."""
+def preprocess_masks(images_u8, masks, min_object_size=400, hole_area_threshold=120, device=None):
+    """utils/image_processing.py:114-124, batched: ``mask & (V <= 170)`` with V the HSV value of the image, then
+    ``remove_small_regions(., 400, 120)``.  images_u8: uint8 [H, W, 3] or [N, H, W, 3] (numpy or torch; cv2's 8-bit V is the channel
+    maximum, so the channel order does not matter); masks: uint8 or bool of the leading shape.  Returns a device ``torch.bool``
+    tensor of the masks' shape."""
+    from . import regions
+    mo, ho = regions._check_size(min_object_size, "min_object_size"), regions._check_size(hole_area_threshold, "hole_area_threshold")
+    img = torch.from_numpy(np.ascontiguousarray(images_u8)) if isinstance(images_u8, np.ndarray) else images_u8
+    msk = torch.from_numpy(np.ascontiguousarray(masks)) if isinstance(masks, np.ndarray) else masks
+    if not (torch.is_tensor(img) and torch.is_tensor(msk)):
+        raise TypeError("preprocess_masks: expected numpy arrays or torch tensors")
+    if img.dtype != torch.uint8 or msk.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"preprocess_masks: expected uint8 images and uint8 / bool masks, got {img.dtype} and {msk.dtype}")
+    if msk.dim() not in (2, 3) or msk.numel() == 0 or tuple(img.shape) != tuple(msk.shape) + (3,):
+        raise ValueError(f"preprocess_masks: images {tuple(img.shape)} do not match masks {tuple(msk.shape)} + (3,)")
+    if device is None:
+        device = msk.device if msk.is_cuda else (img.device if img.is_cuda else torch.device("cuda"))
+    img = img.to(device).contiguous()
+    msk = msk.to(device).contiguous()
+    gated = K.regions_hsv_gate(img, msk.view(torch.uint8) if msk.dtype == torch.bool else msk, 170).view(torch.bool)
+    return regions.remove_small_regions(gated, mo, ho, out=gated)
+
+
+def generate_masks(n_images, image_size, tile_size, tile_idx, tiles_grid, selected, device=None, preprocess=None, min_object_size=400,
+                   hole_area_threshold=120):
+    """utils/image_processing.py:90-102: uint8 [n_images, H, W] DEVICE tensor with a tile_size^2 square of ones for every selected
+    tile (`selected` = indices into tile_idx / tiles_grid, e.g. the positions `rank` kept).  preprocess: the dataset's images,
+    uint8 [n_images, H, W, 3] -- the painted masks then go through ``preprocess_masks`` (:100-102; still uint8 0/1)."""
     if device is None:
         device = torch.device("cuda")
     H, W = image_size
@@ -57,7 +83,10 @@ def generate_masks(n_images, image_size, tile_size, tile_idx, tiles_grid, select
     xy = torch.from_numpy(np.ascontiguousarray(np.asarray(tiles_grid, dtype=np.int32).reshape(-1, 2))).to(device)
     sel = selected if torch.is_tensor(selected) else torch.from_numpy(np.asarray(selected, dtype=np.int64))
     sel = sel.to(device=device, dtype=torch.int64).contiguous()
-    return K.paint_tile_masks(sel, sel.numel(), groups, xy, tile_size, n_images, H, W)
+    masks = K.paint_tile_masks(sel, sel.numel(), groups, xy, tile_size, n_images, H, W)
+    if preprocess is None:
+        return masks
+    return preprocess_masks(preprocess, masks, min_object_size, hole_area_threshold, device=device).view(torch.uint8)
 
 
 def evaluate_tile(valset, probs, tiles_per_pos, threshold, device=None):

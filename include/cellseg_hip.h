@@ -513,6 +513,34 @@ int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N, int cap, 
                       int force_global, int64_t* out_pts, int32_t* out_w, int64_t* out_off, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- small-region clean-up of binary masks (utils/image_processing.py:14-17 remove_small_regions; csrc/regions.hip) ---------
+ * Masks are uint8 [N][H][W], non-zero = foreground, N images that share nothing; 0 < N <= 65535 and N H W < 2^31 per call.
+ * connectivity 1 = 4-neighbourhood, 2 = 8-neighbourhood, for the foreground and the background alike.  Integer work only:
+ * bit-exact and independent of launch order; a fixed number of launches for a given (N, H, W), no host synchronisation.
+ * Every call takes a 16-byte aligned workspace of cs_regions_workspace bytes (0 for sizes a call would refuse).
+ * cs_regions_label       : scipy.ndimage.label per image -- labels int32 [N][H][W], 0 = background, component number = 1 + the
+ *                          number of components of the image whose lowest row-major pixel index is smaller.
+ * cs_regions_areas       : areas int32 [N][H][W] = pixel count of the component of EQUAL-VALUED pixels the pixel lies in
+ *                          (foreground components under foreground pixels, background components under background pixels).
+ * cs_regions_filter      : out = 1 - value where the pixel has `value` (0 or 1) and its component's area < min_area (strict),
+ *                          else the input as 0/1: value 1 = remove_small_objects(min_size), value 0 = remove_small_holes
+ *                          (area_threshold; background components that touch the border included).  out may be mask.
+ * cs_regions_remove_small: the filter with (1, min_object_size), then with (0, hole_area_threshold) on its result.  out may be mask.
+ * cs_regions_threshold   : out[i] = probs[i] > threshold, compared in fp32 (numpy's compare of a float32 array with a Python float).
+ * cs_regions_hsv_gate    : out[i] = mask[i] != 0 && max(images_hwc[i][0..3)) <= v_max -- the V-channel gate of preprocess_masks
+ *                          (image_processing.py:117-120, v_max = 170) on uint8 [..][3] pixels.  out may be mask. */
+size_t cs_regions_workspace(int N, int H, int W);
+int cs_regions_label(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* labels, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cs_regions_areas(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* areas, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cs_regions_filter(const uint8_t* mask, int N, int H, int W, int connectivity, int value, int min_area, uint8_t* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int cs_regions_remove_small(const uint8_t* mask, int N, int H, int W, int min_object_size, int hole_area_threshold, int connectivity,
+                            uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+int cs_regions_threshold(const float* probs, long long n, float threshold, uint8_t* out, void* stream);
+int cs_regions_hsv_gate(const uint8_t* images_hwc, const uint8_t* mask, long long n_pixels, int v_max, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
