@@ -928,18 +928,6 @@ inline int dw_tile_items(long long items, int chunks, int cgt) {
     if (per < 4 * npl) per = 4 * npl;
     return (int)per;
 }
-// Which launches take the tiled kernels: measured per EfficientNet-B3 layer (tools/dw_microbench.py, profiles/round3_notes.md).
-// Both families are VALU-bound, not L1-bound as assumed (k = 5 layers: 25 multiply-adds + the bf16 unpacking per output element run
-// at 0.45-0.8 TB/s either way), so the tile only pays where it removes work: every stride-2 data gradient (2-3x: 286 -> 176, 186 ->
-// 62, 39 -> 18, 52 -> 25 us), the 3x3 stride-1 forwards (180 -> 138, 58 -> 47, 56 -> 34, 77 -> 49 us) and the narrow early layers.
-inline bool dw_tiled_geometry(const CsConvGeom* g, int kind /* 0 forward, 1 data gradient */) {
-    static const int off = cs_env_int_("CELLSEG_DW_UNTILED", 0);      // A/B experiments only: 1 = the element-per-thread kernels
-    if (off || !((g->R == 3 || g->R == 5) && (g->stride == 1 || g->stride == 2) && g->pad == (g->R - 1) / 2)) return false;
-    if (off == 2) return true;                                        // (2 = tiled wherever the geometry allows)
-    if (kind == 1) return g->stride == 2 || g->C <= 48;
-    return g->R == 3 && (g->stride == 1 || g->C >= 288);
-}
-
 inline int grid_ew(long long total) {
     long long b = (total + 255) / 256;
     if (b > 16384) b = 16384;
@@ -953,120 +941,60 @@ inline int grid_ew(long long total) {
     if (dtype == CS_F32) { F32; } else if (dtype == CS_BF16) { BF16; }                 \
     else { cs_set_error_(NAME ": bad dtype"); return CS_ERR_INVALID_ARG; }
 
-// launch of dw_tile_kernel<T, R, ST, STATS, FLIP> on (source x [N][H][W][C]) -> (y [N][P][Q][C])
-template <typename T, bool STATS, bool FLIP>
-static void launch_dw_tile(int R, int ST, hipStream_t st, const void* x, const float* w, const float* scale, const float* shift, int act,
-                           void* y, double* partial, int N, int H, int W, int C, int pad, int P, int Q, int* rows_out) {
-    int chunks, cgt;
-    dw_tile_shape(C, chunks, cgt);
-    const long long items = (long long)N * P * ((Q + 1) / 2);
-    const int per = dw_tile_items(items, chunks, cgt);
-    dim3 grid((unsigned)((items + per - 1) / per), (unsigned)chunks);
-    if (rows_out) *rows_out = (int)grid.x;
-#define CS_DW_TILE(R_, S_)                                                                                                      \
-    hipLaunchKernelGGL((dw_tile_kernel<T, R_, S_, STATS, FLIP>), grid, dim3(256), 0, st, (const T*)x, w, scale, shift, act, (T*)y, partial, \
-                       N, H, W, C, pad, P, Q, per, cgt)
-    if (R == 3 && ST == 1) CS_DW_TILE(3, 1);
-    else if (R == 3) CS_DW_TILE(3, 2);
-    else if (ST == 1) CS_DW_TILE(5, 1);
-    else CS_DW_TILE(5, 2);
-#undef CS_DW_TILE
+// ---- One launch plan per depthwise call.  dw_plan is the only place that decides which kernel family serves a (geometry, dtype, kind)
+// and with which grid; the launchers below and the workspace queries all read the same DwPlan, so a query cannot disagree with the
+// launch it sizes.  The routing table and the measurement behind each exception: DESIGN.md, "Depthwise routing".
+enum DwKind { DW_FWD, DW_DGRAD, DW_WGRAD };
+enum DwFamily { DW_STRIP, DW_TILE, DW_S2BLOCK, DW_ELEMENT };
+struct DwPlan {
+    DwFamily family;
+    dim3 grid;
+    int per;                  // work items per workgroup (0: the kernel walks a grid stride)
+    int lanes;                // channel pairs (strips: cpt) / channel groups (tile, 2 x 2 block: cgt) per workgroup; 0: fixed by the kernel
+    int ts;                   // strip length (strips only)
+    int rows;                 // partial rows the launch writes: statistics rows of a forward, slabs of a weight gradient; 0: none
+    bool flip;                // stride-1 data gradient as the mirrored-filter convolution (source dy, destination dx)
+    int H, W, pad, P, Q;      // what the strip / tile kernels see: source H x W -> destination P x Q (swapped and pad' = R - 1 - pad when flip)
+};
+
+// A/B experiments only: CELLSEG_DW_UNTILED = 1 the element-per-thread kernels, 2 = tiled wherever the geometry allows
+static bool dw_tiled_geometry(const CsConvGeom* g, DwKind kind) {
+    static const int off = cs_env_int_("CELLSEG_DW_UNTILED", 0);
+    if (off || !((g->R == 3 || g->R == 5) && (g->stride == 1 || g->stride == 2) && g->pad == (g->R - 1) / 2)) return false;
+    if (off == 2) return true;
+    if (kind == DW_DGRAD) return g->stride == 2 || g->C <= 48;
+    return g->R == 3 && (g->stride == 1 || g->C >= 288);
 }
-// ---- strip kernels (bf16): geometry of a launch over (source N x H x W) -> (destination N x P x Q)
-struct DwStrip { int ts, per, chunks, cpt; unsigned nblk; };
+// strips: bf16, 3x3 / 5x5, stride 1 / 2, tensors below 1 GiB (kDwRowOut / kDwColOut).  A/B experiments only: CELLSEG_DW_NOSTRIP
 static bool dw_strip_ok(int R, int stride, long long src_elems, long long dst_elems, int dtype) {
-    static const int off = cs_env_int_("CELLSEG_DW_NOSTRIP", 0);      // A/B experiments only
+    static const int off = cs_env_int_("CELLSEG_DW_NOSTRIP", 0);
     return !off && dtype == CS_BF16 && (R == 3 || R == 5) && (stride == 1 || stride == 2) && src_elems * 2 < (1ll << 30) && dst_elems * 2 < (1ll << 30);
 }
-// strip length: the one of the two instantiated per stride that wastes fewer columns; `blocks_target` workgroups in all
-static DwStrip dw_strip_plan(int N, int P, int Q, int C, int stride, long long blocks_target, long long rows_cap) {
-    DwStrip d;
-    const int a = stride == 1 ? 8 : 4, b = 5;
-    const int wa = (Q + a - 1) / a * a, wb = (Q + b - 1) / b * b;
-    d.ts = wb < wa ? b : a;
-    dw_strip_shape(C, d.chunks, d.cpt);
-    const long long items = (long long)N * P * ((Q + d.ts - 1) / d.ts);
-    long long blocks = blocks_target / d.chunks;
-    if (blocks < 1) blocks = 1;
-    if (rows_cap > 0 && blocks > rows_cap) blocks = rows_cap;
-    long long p_ = (items + blocks - 1) / blocks;
-    const int npl = 256 / d.cpt;
-    if (p_ < 2 * npl) p_ = 2 * npl;
-    d.per = (int)p_;
-    d.nblk = (unsigned)((items + p_ - 1) / p_);
-    return d;
-}
-// forward launches that stay on the channel-tiled kernel: the 144-channel 3x3 stride-2 layer at 150 x 150 (194 vs 231 us, tools/dw_microbench.py)
+// forward launches that stay on the channel-tiled kernel: 3x3 stride 2 with at most 144 channels -- where dw_tiled_geometry admits
+// them, which for a stride-2 forward takes C >= 288 or CELLSEG_DW_UNTILED=2: in the production library this never holds
 static bool dw_strip_fwd_ok(const CsConvGeom* g, int dtype) {
-    if (g->stride == 2 && g->R == 3 && g->C <= 144 && dw_tiled_geometry(g, 0)) return false;
+    if (g->stride == 2 && g->R == 3 && g->C <= 144 && dw_tiled_geometry(g, DW_FWD)) return false;
     return dw_strip_ok(g->R, g->stride, (long long)g->N * g->H * g->W * g->C, (long long)g->N * g->P * g->Q * g->C, dtype);
 }
-static DwStrip dw_strip_plan_conv(int N, int P, int Q, int C, int stride) {
-    return dw_strip_plan(N, P, Q, C, stride, 4096, 2048);            // (partial statistics rows: at most 2048 per launch)
+// strips over (N x p.P x p.Q): the strip length of the two instantiated per stride that wastes fewer columns; ~4096 workgroups in all,
+// at most `rows_cap` of them along x (one partial row each), at least 2 items per item lane
+static void dw_strip_plan(DwPlan& p, int N, int C, int stride, long long rows_cap) {
+    const int a = stride == 1 ? 8 : 4, b = 5;
+    const int wa = (p.Q + a - 1) / a * a, wb = (p.Q + b - 1) / b * b;
+    p.ts = wb < wa ? b : a;
+    int chunks;
+    dw_strip_shape(C, chunks, p.lanes);
+    const long long items = (long long)N * p.P * ((p.Q + p.ts - 1) / p.ts);
+    long long blocks = 4096 / chunks;
+    if (blocks < 1) blocks = 1;
+    if (blocks > rows_cap) blocks = rows_cap;
+    long long per = (items + blocks - 1) / blocks;
+    const int npl = 256 / p.lanes;
+    if (per < 2 * npl) per = 2 * npl;
+    p.per = (int)per;
+    p.grid = dim3((unsigned)((items + per - 1) / per), (unsigned)chunks);
 }
-template <bool STATS, bool FLIP>
-static void launch_dw_strip(int R, int ST, hipStream_t st, const void* x, const float* w, const float* scale, const float* shift, int act,
-                            void* y, double* partial, int N, int H, int W, int C, int pad, int P, int Q, int* rows_out) {
-    const DwStrip d = dw_strip_plan_conv(N, P, Q, C, ST);
-    if (rows_out) *rows_out = (int)d.nblk;
-    const unsigned xb = (unsigned)((long long)N * H * W * C * 2), yb = (unsigned)((long long)N * P * Q * C * 2);
-#define CS_DW_CS(R_, S_, T_)                                                                                                              \
-    hipLaunchKernelGGL((dw_conv_strip_kernel<R_, S_, T_, STATS, FLIP>), dim3(d.nblk, (unsigned)d.chunks), dim3(256), 0, st, (const bf16_t*)x, w, \
-                       scale, shift, act, (bf16_t*)y, partial, N, H, W, C, pad, P, Q, d.per, d.cpt, xb, yb)
-    if (R == 3) {
-        if (ST == 1) { if (d.ts == 8) CS_DW_CS(3, 1, 8); else CS_DW_CS(3, 1, 5); }
-        else { if (d.ts == 4) CS_DW_CS(3, 2, 4); else CS_DW_CS(3, 2, 5); }
-    } else {
-        if (ST == 1) { if (d.ts == 8) CS_DW_CS(5, 1, 8); else CS_DW_CS(5, 1, 5); }
-        else { if (d.ts == 4) CS_DW_CS(5, 2, 4); else CS_DW_CS(5, 2, 5); }
-    }
-#undef CS_DW_CS
-}
-
-static int dw_tile_rows(const CsConvGeom* g) {
-    int chunks, cgt;
-    dw_tile_shape(g->C, chunks, cgt);
-    const long long items = (long long)g->N * g->P * ((g->Q + 1) / 2);
-    const int per = dw_tile_items(items, chunks, cgt);
-    return (int)((items + per - 1) / per);
-}
-
-static int check_dw(const CsConvGeom* g, const char* what) {
-    if (!g || g->R != g->S || g->R < 1 || g->C % 8 != 0 || g->K != g->C || g->stride < 1 ||
-        g->P != (g->H + 2 * g->pad - g->R) / g->stride + 1 || g->Q != (g->W + 2 * g->pad - g->S) / g->stride + 1) {
-        cs_set_error_(what);
-        return CS_ERR_INVALID_ARG;
-    }
-    return CS_OK;
-}
-
-extern "C" int cs_dwconv_fwd(const CsConvGeom* g, int dtype, const void* x, const float* w_hwc, const float* scale, const float* shift,
-                             int act, void* y, void* stream) {
-    int rc = check_dw(g, "dwconv_fwd: bad geometry (square filter, K == C, C % 8 == 0 required)");
-    if (rc) return rc;
-    CS_CHECK_ARG(x && w_hwc && y, "dwconv_fwd: NULL tensor");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dw_strip_fwd_ok(g, dtype)) {
-        launch_dw_strip<false, false>(g->R, g->stride, st, x, w_hwc, scale, shift, act, y, nullptr, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, nullptr);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dw_tiled_geometry(g, 0) && (dtype == CS_F32 || dtype == CS_BF16)) {
-        if (dtype == CS_F32) launch_dw_tile<float, false, false>(g->R, g->stride, st, x, w_hwc, scale, shift, act, y, nullptr, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, nullptr);
-        else launch_dw_tile<bf16_t, false, false>(g->R, g->stride, st, x, w_hwc, scale, shift, act, y, nullptr, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, nullptr);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    const int grid = grid_ew((long long)g->N * g->P * g->Q * (g->C / 8));
-    CS_T_SWITCH(dtype, "dwconv_fwd",
-                hipLaunchKernelGGL(dw_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, w_hwc, scale, shift, act, (float*)y,
-                                   g->N, g->H, g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q),
-                hipLaunchKernelGGL(dw_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, w_hwc, scale, shift, act,
-                                   (bf16_t*)y, g->N, g->H, g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
+// workgroups of the element-per-thread statistics forward (one partial row each): a multiple of CG / gcd(CG, 256), at most ~1024
 static int dw_stats_grid(const CsConvGeom* g) {
     const int CG = g->C / 8;
     int a = CG, b = 256;
@@ -1078,90 +1006,11 @@ static int dw_stats_grid(const CsConvGeom* g) {
     if (grid < m) grid = m;
     return (int)grid;
 }
-
-extern "C" size_t cs_dwconv_fwd_stats_workspace(const CsConvGeom* g) {
-    if (!g || g->C <= 0 || g->C % 8) return 0;
-    size_t strip_rows = 0;                               // (the dtype is not known here: room for whichever kernel serves the call)
-    if (dw_strip_fwd_ok(g, CS_BF16))
-        strip_rows = dw_strip_plan_conv(g->N, g->P, g->Q, g->C, g->stride).nblk;
-    const size_t other_rows = dw_tiled_geometry(g, 0) ? (size_t)dw_tile_rows(g) : (size_t)dw_stats_grid(g);
-    return (strip_rows > other_rows ? strip_rows : other_rows) * 2 * (size_t)g->C * sizeof(double);
-}
-extern "C" int cs_dwconv_fwd_stats(const CsConvGeom* g, int dtype, const void* x, const float* w_hwc, void* y, double* partial,
-                                   int* partial_rows, void* stream) {
-    int rc = check_dw(g, "dwconv_fwd_stats: bad geometry (square filter, K == C, C % 8 == 0 required)");
-    if (rc) return rc;
-    CS_CHECK_ARG(x && w_hwc && y && partial && partial_rows, "dwconv_fwd_stats: NULL argument");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dw_strip_fwd_ok(g, dtype)) {
-        launch_dw_strip<true, false>(g->R, g->stride, st, x, w_hwc, nullptr, nullptr, CS_ACT_NONE, y, partial, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, partial_rows);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dw_tiled_geometry(g, 0) && (dtype == CS_F32 || dtype == CS_BF16)) {
-        if (dtype == CS_F32) launch_dw_tile<float, true, false>(g->R, g->stride, st, x, w_hwc, nullptr, nullptr, CS_ACT_NONE, y, partial, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, partial_rows);
-        else launch_dw_tile<bf16_t, true, false>(g->R, g->stride, st, x, w_hwc, nullptr, nullptr, CS_ACT_NONE, y, partial, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, partial_rows);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    CS_CHECK_ARG((size_t)2 * g->C * sizeof(float) <= 65536, "dwconv_fwd_stats: too many channels for the LDS fold");
-    const int grid = dw_stats_grid(g);
-    const size_t lds = (size_t)2 * g->C * sizeof(float);
-    *partial_rows = grid;
-    CS_T_SWITCH(dtype, "dwconv_fwd_stats",
-                hipLaunchKernelGGL(dw_fwd_stats_kernel<float>, dim3(grid), dim3(256), lds, st, (const float*)x, w_hwc, (float*)y, partial, g->N,
-                                   g->H, g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q),
-                hipLaunchKernelGGL(dw_fwd_stats_kernel<bf16_t>, dim3(grid), dim3(256), lds, st, (const bf16_t*)x, w_hwc, (bf16_t*)y, partial,
-                                   g->N, g->H, g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
-extern "C" int cs_dwconv_dgrad(const CsConvGeom* g, int dtype, const void* dy, const float* w_hwc, void* dx, void* stream) {
-    int rc = check_dw(g, "dwconv_dgrad: bad geometry");
-    if (rc) return rc;
-    CS_CHECK_ARG(dy && w_hwc && dx, "dwconv_dgrad: NULL tensor");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (g->stride == 1 && g->pad <= g->R - 1 && dw_strip_ok(g->R, 1, (long long)g->N * g->P * g->Q * g->C, (long long)g->N * g->H * g->W * g->C, dtype)) {
-        // the gradient of a stride-1 convolution is the same convolution with the filter mirrored (source dy, destination dx)
-        launch_dw_strip<false, true>(g->R, 1, st, dy, w_hwc, nullptr, nullptr, CS_ACT_NONE, dx, nullptr, g->N, g->P, g->Q, g->C, g->R - 1 - g->pad, g->H, g->W, nullptr);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dw_tiled_geometry(g, 1) && (dtype == CS_F32 || dtype == CS_BF16)) {
-        if (g->stride == 1) {
-            // the gradient of a stride-1 "same" convolution is the same convolution with the filter mirrored (source dy, destination dx)
-            if (dtype == CS_F32) launch_dw_tile<float, false, true>(g->R, 1, st, dy, w_hwc, nullptr, nullptr, CS_ACT_NONE, dx, nullptr, g->N, g->P, g->Q, g->C, g->R - 1 - g->pad, g->H, g->W, nullptr);
-            else launch_dw_tile<bf16_t, false, true>(g->R, 1, st, dy, w_hwc, nullptr, nullptr, CS_ACT_NONE, dx, nullptr, g->N, g->P, g->Q, g->C, g->R - 1 - g->pad, g->H, g->W, nullptr);
-        } else {
-            int chunks, cgt;
-            dw_tile_shape(g->C, chunks, cgt);
-            const long long items = (long long)g->N * ((g->H + 1) / 2) * ((g->W + 1) / 2);
-            const int per = dw_tile_items(items, chunks, cgt);
-            dim3 grid((unsigned)((items + per - 1) / per), (unsigned)chunks);
-#define CS_DW_S2(T_, R_) hipLaunchKernelGGL((dw_dgrad_s2_kernel<T_, R_>), grid, dim3(256), 0, st, (const T_*)dy, w_hwc, (T_*)dx, g->N, g->H, g->W, g->C, g->P, g->Q, per, cgt)
-            if (dtype == CS_F32) { if (g->R == 3) CS_DW_S2(float, 3); else CS_DW_S2(float, 5); }
-            else { if (g->R == 3) CS_DW_S2(bf16_t, 3); else CS_DW_S2(bf16_t, 5); }
-#undef CS_DW_S2
-        }
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    const int grid = grid_ew((long long)g->N * g->H * g->W * (g->C / 8));
-    CS_T_SWITCH(dtype, "dwconv_dgrad",
-                hipLaunchKernelGGL(dw_dgrad_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, w_hwc, (float*)dx, g->N, g->H,
-                                   g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q),
-                hipLaunchKernelGGL(dw_dgrad_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, w_hwc, (bf16_t*)dx, g->N, g->H,
-                                   g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
-// output-row slabs of the weight gradient: ~1024 workgroups in total (no atomics, so parallelism is free), <= 256 partial rows
-static void dw_wgrad_split(const CsConvGeom* g, int& rows_per_block, unsigned& nslab) {
+// output-row slabs of the element-per-thread weight gradient: ~1024 workgroups in total (no atomics, so parallelism is free)
+static void dw_wgrad_split(DwPlan& p, const CsConvGeom* g) {
     const long long rows = (long long)g->N * g->P;
-    const int chunks = (g->C / 8 + 63) / 64 * ((g->R * g->R + kDwTaps - 1) / kDwTaps);
-    long long slabs = 1024 / chunks;
+    const int chunks = (g->C / 8 + 63) / 64, tgroups = (g->R * g->R + kDwTaps - 1) / kDwTaps;
+    long long slabs = 1024 / (chunks * tgroups);
     if (slabs < 1) slabs = 1;
     // every slab is one fp32 partial row of R*R*C floats for the fold: at most 32 MiB of them, at least 256
     long long cap = (32ll << 20) / ((long long)g->R * g->R * g->C * 4);
@@ -1170,29 +1019,196 @@ static void dw_wgrad_split(const CsConvGeom* g, int& rows_per_block, unsigned& n
     long long rpb = (rows + slabs - 1) / slabs;
     const long long min_rows = (64 + g->Q - 1) / g->Q;           // >= 64 pixels per workgroup
     if (rpb < min_rows) rpb = min_rows;
-    rows_per_block = (int)rpb;
-    nslab = (unsigned)((rows + rpb - 1) / rpb);
+    p.per = (int)rpb * g->Q;                                     // pixels per workgroup
+    p.rows = (int)((rows + rpb - 1) / rpb);
+    p.grid = dim3((unsigned)p.rows, (unsigned)chunks, (unsigned)tgroups);
 }
 
-// strip weight gradient: the same planning as the strip convolutions (dw_strip_plan); partial rows: at most 32 MiB, at least 128 rows
-static DwStrip dw_strip_plan_wgrad(const CsConvGeom* g) {
-    long long cap = (32ll << 20) / ((long long)g->R * g->R * g->C * 4);
-    if (cap < 128) cap = 128;
-    return dw_strip_plan(g->N, g->P, g->Q, g->C, g->stride, 4096, cap);
-}
-static bool dw_strip_wgrad_ok(const CsConvGeom* g, int dtype) {
-    return dw_strip_ok(g->R, g->stride, (long long)g->N * g->H * g->W * g->C, (long long)g->N * g->P * g->Q * g->C, dtype);
+static DwPlan dw_plan(const CsConvGeom* g, int dtype, DwKind kind) {
+    DwPlan p = {};
+    p.H = g->H; p.W = g->W; p.pad = g->pad; p.P = g->P; p.Q = g->Q;
+    const long long in = (long long)g->N * g->H * g->W * g->C, out = (long long)g->N * g->P * g->Q * g->C;
+    if (kind == DW_FWD)
+        p.family = dw_strip_fwd_ok(g, dtype) ? DW_STRIP : dw_tiled_geometry(g, kind) ? DW_TILE : DW_ELEMENT;
+    else if (kind == DW_WGRAD)
+        p.family = dw_strip_ok(g->R, g->stride, in, out, dtype) ? DW_STRIP : DW_ELEMENT;
+    else if (g->stride == 1 && g->pad <= g->R - 1 && dw_strip_ok(g->R, 1, out, in, dtype))
+        p.family = DW_STRIP;
+    else
+        p.family = !dw_tiled_geometry(g, kind) ? DW_ELEMENT : g->stride == 1 ? DW_TILE : DW_S2BLOCK;
+    if (kind == DW_DGRAD && (p.family == DW_STRIP || p.family == DW_TILE)) {
+        // the gradient of a stride-1 convolution is the same convolution with the filter mirrored (source dy, destination dx)
+        p.flip = true;
+        p.H = g->P; p.W = g->Q; p.pad = g->R - 1 - g->pad; p.P = g->H; p.Q = g->W;
+    }
+    if (p.family == DW_STRIP) {
+        // partial rows: statistics at most 2048 per launch; weight gradient at most 32 MiB of them, at least 128
+        long long cap = kind == DW_WGRAD ? (32ll << 20) / ((long long)g->R * g->R * g->C * 4) : 2048;
+        if (cap < 128) cap = 128;
+        dw_strip_plan(p, g->N, g->C, g->stride, cap);
+        p.rows = kind == DW_DGRAD ? 0 : (int)p.grid.x;
+    } else if (p.family == DW_TILE || p.family == DW_S2BLOCK) {
+        // items: two neighbouring output columns (tile) / a 2 x 2 block of input pixels (stride-2 data gradient)
+        int chunks;
+        dw_tile_shape(g->C, chunks, p.lanes);
+        const long long items = p.family == DW_TILE ? (long long)g->N * p.P * ((p.Q + 1) / 2) : (long long)g->N * ((g->H + 1) / 2) * ((g->W + 1) / 2);
+        p.per = dw_tile_items(items, chunks, p.lanes);
+        p.grid = dim3((unsigned)((items + p.per - 1) / p.per), (unsigned)chunks);
+        p.rows = kind == DW_FWD ? (int)p.grid.x : 0;
+    } else if (kind == DW_WGRAD) {
+        dw_wgrad_split(p, g);
+    } else {
+        p.grid = dim3((unsigned)grid_ew((kind == DW_FWD ? out : in) / 8));
+        p.rows = kind == DW_FWD ? dw_stats_grid(g) : 0;        // (the statistics forward runs dim3(rows) workgroups instead of `grid`)
+    }
+    return p;
 }
 
+// the instantiation a launch reached, for cs_last_conv_variant(): the kernel's template name as a profiler prints it, then the launch shape
+static void dw_note_variant(const DwPlan& p, const CsConvGeom* g, int dtype, DwKind kind, bool stats, dim3 grid) {
+    const char* t = dtype == CS_F32 ? "f32" : "bf16";
+    const char* tf[2] = {"false", "true"};
+    char k[64], buf[128];
+    if (p.family == DW_STRIP && kind == DW_WGRAD) snprintf(k, sizeof(k), "dw_wgrad_strip_kernel<%d,%d,%d>", g->R, g->stride, p.ts);
+    else if (p.family == DW_STRIP) snprintf(k, sizeof(k), "dw_conv_strip_kernel<%d,%d,%d,%s,%s>", g->R, g->stride, p.ts, tf[stats], tf[p.flip]);
+    else if (p.family == DW_TILE) snprintf(k, sizeof(k), "dw_tile_kernel<%s,%d,%d,%s,%s>", t, g->R, g->stride, tf[stats], tf[p.flip]);
+    else if (p.family == DW_S2BLOCK) snprintf(k, sizeof(k), "dw_dgrad_s2_kernel<%s,%d>", t, g->R);
+    else snprintf(k, sizeof(k), "%s<%s>", kind == DW_WGRAD ? "dw_wgrad_kernel" : kind == DW_DGRAD ? "dw_dgrad_kernel" : stats ? "dw_fwd_stats_kernel" : "dw_fwd_kernel", t);
+    snprintf(buf, sizeof(buf), "%s grid=(%u,%u,%u) per=%d lanes=%d", k, grid.x, grid.y, grid.z, p.per, p.lanes);
+    cs_set_variant_(buf);
+}
+
+// ---- launchers: one per family, each switching (R, stride, TS) and the element type once
+template <int V> struct DwInt { static constexpr int v = V; };
+template <typename T> struct DwType { using type = T; };
+// f(DwType<T>) for the element type of `dtype` (validated by the caller)
+template <typename F> static void dw_for_type(int dtype, F f) { if (dtype == CS_F32) f(DwType<float>{}); else f(DwType<bf16_t>{}); }
+// f(DwInt<R>, DwInt<ST>) over the instantiated filter sizes and strides
+template <typename F> static void dw_for_rs(int R, int ST, F f) {
+    if (R == 3 && ST == 1) f(DwInt<3>{}, DwInt<1>{});
+    else if (R == 3) f(DwInt<3>{}, DwInt<2>{});
+    else if (ST == 1) f(DwInt<5>{}, DwInt<1>{});
+    else f(DwInt<5>{}, DwInt<2>{});
+}
+// f(DwInt<R>, DwInt<ST>, DwInt<TS>): strip lengths {8, 5} at stride 1, {4, 5} at stride 2
+template <typename F> static void dw_for_rst(int R, int ST, int ts, F f) {
+    dw_for_rs(R, ST, [&](auto r, auto s) {
+        if (ts == 5) f(r, s, DwInt<5>{}); else f(r, s, DwInt<(decltype(s)::v == 1 ? 8 : 4)>{});
+    });
+}
+
+struct DwOperands { const void* x; const float *w, *scale, *shift; int act; void* y; double* partial; };
+template <bool STATS, bool FLIP>
+static void launch_dw_strip(const DwPlan& p, const CsConvGeom* g, hipStream_t st, const DwOperands& o) {
+    const unsigned xb = (unsigned)((long long)g->N * p.H * p.W * g->C * 2), yb = (unsigned)((long long)g->N * p.P * p.Q * g->C * 2);
+    dw_for_rst(g->R, g->stride, p.ts, [&](auto r, auto s, auto t) {
+        hipLaunchKernelGGL((dw_conv_strip_kernel<decltype(r)::v, decltype(s)::v, decltype(t)::v, STATS, FLIP>), p.grid, dim3(256), 0, st,
+                           (const bf16_t*)o.x, o.w, o.scale, o.shift, o.act, (bf16_t*)o.y, o.partial, g->N, p.H, p.W, g->C, p.pad, p.P, p.Q,
+                           p.per, p.lanes, xb, yb);
+    });
+}
+template <bool STATS, bool FLIP>
+static void launch_dw_tile(const DwPlan& p, const CsConvGeom* g, int dtype, hipStream_t st, const DwOperands& o) {
+    dw_for_type(dtype, [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        dw_for_rs(g->R, g->stride, [&](auto r, auto s) {
+            hipLaunchKernelGGL((dw_tile_kernel<T, decltype(r)::v, decltype(s)::v, STATS, FLIP>), p.grid, dim3(256), 0, st, (const T*)o.x, o.w,
+                               o.scale, o.shift, o.act, (T*)o.y, o.partial, g->N, p.H, p.W, g->C, p.pad, p.P, p.Q, p.per, p.lanes);
+        });
+    });
+}
+
+static int check_dw(const CsConvGeom* g, const char* what) {
+    if (!g || g->R != g->S || g->R < 1 || g->C % 8 != 0 || g->K != g->C || g->stride < 1 ||
+        g->P != (g->H + 2 * g->pad - g->R) / g->stride + 1 || g->Q != (g->W + 2 * g->pad - g->S) / g->stride + 1) {
+        cs_set_error_(what);
+        return CS_ERR_INVALID_ARG;
+    }
+    return CS_OK;
+}
+
+// forward, with the statistics of the stored output as `partial` rows when partial != nullptr
+static int dw_forward(const CsConvGeom* g, int dtype, const DwOperands& o, int* partial_rows, void* stream) {
+    int rc = check_dw(g, "dwconv_fwd: bad geometry (square filter, K == C, C % 8 == 0 required)");
+    if (rc) return rc;
+    const bool stats = o.partial != nullptr;
+    CS_CHECK_ARG(o.x && o.w && o.y && stats == (partial_rows != nullptr), "dwconv_fwd: NULL argument");
+    CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_fwd: bad dtype");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const DwPlan p = dw_plan(g, dtype, DW_FWD);
+    dim3 grid = p.grid;
+    if (p.family == DW_STRIP) {
+        if (stats) launch_dw_strip<true, false>(p, g, st, o); else launch_dw_strip<false, false>(p, g, st, o);
+    } else if (p.family == DW_TILE) {
+        if (stats) launch_dw_tile<true, false>(p, g, dtype, st, o); else launch_dw_tile<false, false>(p, g, dtype, st, o);
+    } else {
+        const size_t lds = (size_t)2 * g->C * sizeof(float);
+        CS_CHECK_ARG(!stats || lds <= 65536, "dwconv_fwd_stats: too many channels for the LDS fold");
+        if (stats) grid = dim3((unsigned)p.rows);
+        dw_for_type(dtype, [&](auto tc) {
+            using T = typename decltype(tc)::type;
+            if (stats)
+                hipLaunchKernelGGL(dw_fwd_stats_kernel<T>, grid, dim3(256), lds, st, (const T*)o.x, o.w, (T*)o.y, o.partial, g->N, g->H, g->W,
+                                   g->C, g->R, g->stride, g->pad, g->P, g->Q);
+            else
+                hipLaunchKernelGGL(dw_fwd_kernel<T>, grid, dim3(256), 0, st, (const T*)o.x, o.w, o.scale, o.shift, o.act, (T*)o.y, g->N, g->H,
+                                   g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q);
+        });
+    }
+    if (stats) *partial_rows = p.rows;
+    CS_LAUNCH_CHECK();
+    dw_note_variant(p, g, dtype, DW_FWD, stats, grid);
+    return CS_OK;
+}
+extern "C" int cs_dwconv_fwd(const CsConvGeom* g, int dtype, const void* x, const float* w_hwc, const float* scale, const float* shift,
+                             int act, void* y, void* stream) {
+    return dw_forward(g, dtype, DwOperands{x, w_hwc, scale, shift, act, y, nullptr}, nullptr, stream);
+}
+extern "C" int cs_dwconv_fwd_stats(const CsConvGeom* g, int dtype, const void* x, const float* w_hwc, void* y, double* partial,
+                                   int* partial_rows, void* stream) {
+    CS_CHECK_ARG(partial && partial_rows, "dwconv_fwd_stats: NULL argument");
+    return dw_forward(g, dtype, DwOperands{x, w_hwc, nullptr, nullptr, CS_ACT_NONE, y, partial}, partial_rows, stream);
+}
+
+extern "C" int cs_dwconv_dgrad(const CsConvGeom* g, int dtype, const void* dy, const float* w_hwc, void* dx, void* stream) {
+    int rc = check_dw(g, "dwconv_dgrad: bad geometry");
+    if (rc) return rc;
+    CS_CHECK_ARG(dy && w_hwc && dx, "dwconv_dgrad: NULL tensor");
+    CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_dgrad: bad dtype");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const DwPlan p = dw_plan(g, dtype, DW_DGRAD);
+    const DwOperands o = {dy, w_hwc, nullptr, nullptr, CS_ACT_NONE, dx, nullptr};
+    if (p.family == DW_STRIP) launch_dw_strip<false, true>(p, g, st, o);
+    else if (p.family == DW_TILE) launch_dw_tile<false, true>(p, g, dtype, st, o);
+    else
+        dw_for_type(dtype, [&](auto tc) {
+            using T = typename decltype(tc)::type;
+            if (p.family == DW_ELEMENT)
+                hipLaunchKernelGGL(dw_dgrad_kernel<T>, p.grid, dim3(256), 0, st, (const T*)dy, w_hwc, (T*)dx, g->N, g->H, g->W, g->C, g->R,
+                                   g->stride, g->pad, g->P, g->Q);
+            else
+                dw_for_rs(g->R, 2, [&](auto r, auto) {
+                    hipLaunchKernelGGL((dw_dgrad_s2_kernel<T, decltype(r)::v>), p.grid, dim3(256), 0, st, (const T*)dy, w_hwc, (T*)dx, g->N, g->H,
+                                       g->W, g->C, g->P, g->Q, p.per, p.lanes);
+                });
+        });
+    CS_LAUNCH_CHECK();
+    dw_note_variant(p, g, dtype, DW_DGRAD, false, p.grid);
+    return CS_OK;
+}
+
+// room for whichever kernel serves the call: the signatures carry no dtype, so the larger of the two dtypes' plans
+static size_t dw_plan_rows(const CsConvGeom* g, DwKind kind) {
+    const int a = dw_plan(g, CS_F32, kind).rows, b = dw_plan(g, CS_BF16, kind).rows;
+    return (size_t)(a > b ? a : b);
+}
+extern "C" size_t cs_dwconv_fwd_stats_workspace(const CsConvGeom* g) {
+    if (!g || g->C <= 0 || g->C % 8) return 0;
+    return dw_plan_rows(g, DW_FWD) * 2 * (size_t)g->C * sizeof(double);
+}
 extern "C" size_t cs_dwconv_wgrad_workspace(const CsConvGeom* g) {
     if (!g || check_dw(g, "dwconv_wgrad_workspace: bad geometry")) return 0;
-    int rpb; unsigned nslab;
-    dw_wgrad_split(g, rpb, nslab);
-    if ((g->R == 3 || g->R == 5) && (g->stride == 1 || g->stride == 2)) {      // (either kernel may serve the call: room for both)
-        const unsigned nblk = dw_strip_plan_wgrad(g).nblk;
-        if (nblk > nslab) nslab = nblk;
-    }
-    return (size_t)nslab * g->R * g->R * g->C * sizeof(float);
+    return dw_plan_rows(g, DW_WGRAD) * g->R * g->R * g->C * sizeof(float);
 }
 
 static int dwconv_wgrad_impl(const CsConvGeom* g, int dtype, const void* x, const void* dy, float* dw_hwc, float* workspace, int chan, void* stream) {
@@ -1201,43 +1217,24 @@ static int dwconv_wgrad_impl(const CsConvGeom* g, int dtype, const void* x, cons
     CS_CHECK_ARG(x && dy && dw_hwc && workspace, "dwconv_wgrad: NULL tensor (workspace: cs_dwconv_wgrad_workspace bytes)");
     CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_wgrad: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int ncols = g->R * g->R * g->C;
-    if (dw_strip_wgrad_ok(g, dtype)) {
-        const DwStrip d_ = dw_strip_plan_wgrad(g);
-        const int ts = d_.ts, per = d_.per, sch = d_.chunks, cpt = d_.cpt;
-        const unsigned nblk = d_.nblk;
+    const DwPlan p = dw_plan(g, dtype, DW_WGRAD);
+    if (p.family == DW_STRIP) {
         const unsigned xb = (unsigned)((long long)g->N * g->H * g->W * g->C * 2), yb = (unsigned)((long long)g->N * g->P * g->Q * g->C * 2);
-#define CS_DW_STRIP(R_, S_, T_)                                                                                                          \
-    hipLaunchKernelGGL((dw_wgrad_strip_kernel<R_, S_, T_>), dim3(nblk, (unsigned)sch), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, \
-                       workspace, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, per, cpt, xb, yb)
-        if (g->R == 3) {
-            if (g->stride == 1) { if (ts == 8) CS_DW_STRIP(3, 1, 8); else CS_DW_STRIP(3, 1, 5); }
-            else { if (ts == 4) CS_DW_STRIP(3, 2, 4); else CS_DW_STRIP(3, 2, 5); }
-        } else {
-            if (g->stride == 1) { if (ts == 8) CS_DW_STRIP(5, 1, 8); else CS_DW_STRIP(5, 1, 5); }
-            else { if (ts == 4) CS_DW_STRIP(5, 2, 4); else CS_DW_STRIP(5, 2, 5); }
-        }
-#undef CS_DW_STRIP
-        CS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(dw_wgrad_fold_kernel, dim3((unsigned)((ncols + 15) / 16)), dim3(256), 0, st, workspace, (int)nblk, ncols, dw_hwc, chan);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    int rpb; unsigned nslab;
-    dw_wgrad_split(g, rpb, nslab);
-    const int chunks = (g->C / 8 + 63) / 64;
-    const int tgroups = (g->R * g->R + kDwTaps - 1) / kDwTaps;
-    dim3 grid(nslab, (unsigned)chunks, (unsigned)tgroups);
-    const int ppb = rpb * g->Q;
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(dw_wgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const float*)dy, workspace, g->N, g->H, g->W, g->C,
-                           g->R, g->stride, g->pad, g->P, g->Q, ppb);
-    else
-        hipLaunchKernelGGL(dw_wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, workspace, g->N, g->H, g->W,
-                           g->C, g->R, g->stride, g->pad, g->P, g->Q, ppb);
+        dw_for_rst(g->R, g->stride, p.ts, [&](auto r, auto s, auto t) {
+            hipLaunchKernelGGL((dw_wgrad_strip_kernel<decltype(r)::v, decltype(s)::v, decltype(t)::v>), p.grid, dim3(256), 0, st, (const bf16_t*)x,
+                               (const bf16_t*)dy, workspace, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, p.per, p.lanes, xb, yb);
+        });
+    } else
+        dw_for_type(dtype, [&](auto tc) {
+            using T = typename decltype(tc)::type;
+            hipLaunchKernelGGL(dw_wgrad_kernel<T>, p.grid, dim3(256), 0, st, (const T*)x, (const T*)dy, workspace, g->N, g->H, g->W, g->C, g->R,
+                               g->stride, g->pad, g->P, g->Q, p.per);
+        });
     CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dw_wgrad_fold_kernel, dim3((unsigned)((ncols + 15) / 16)), dim3(256), 0, st, workspace, (int)nslab, ncols, dw_hwc, chan);
+    const int ncols = g->R * g->R * g->C;
+    hipLaunchKernelGGL(dw_wgrad_fold_kernel, dim3((unsigned)((ncols + 15) / 16)), dim3(256), 0, st, workspace, p.rows, ncols, dw_hwc, chan);
     CS_LAUNCH_CHECK();
+    dw_note_variant(p, g, dtype, DW_WGRAD, false, p.grid);
     return CS_OK;
 }
 

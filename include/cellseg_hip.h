@@ -315,15 +315,16 @@ int cs_dwconv_fwd(const CsConvGeom* g, int dtype, const void* x, const float* w_
 /* Depthwise forward for train-mode BN: y = raw conv output, and the per-channel sum / sum of squares of the stored y as
  * *partial_rows per-workgroup rows partial[r][2][C] (fp64, cs_dwconv_fwd_stats_workspace(g) bytes); cs_bn_partial_fold adds the
  * rows into the exact accumulator `stats` (cs_bn_accum_words(C) zeroed words) -- together they replace cs_dwconv_fwd + cs_bn_stats
- * (one pass over y less). */
+ * (one pass over y less).  The query takes no dtype: it returns room for the launch plan of either dtype, the same plan the call
+ * itself launches from, so *partial_rows rows always fit. */
 size_t cs_dwconv_fwd_stats_workspace(const CsConvGeom* g);
 int cs_dwconv_fwd_stats(const CsConvGeom* g, int dtype, const void* x, const float* w_hwc, void* y, double* partial,
                         int* partial_rows, void* stream);
 int cs_bn_partial_fold(const double* partial, int rows, int C, double* stats, void* stream);
 int cs_dwconv_dgrad(const CsConvGeom* g, int dtype, const void* dy, const float* w_hwc, void* dx, void* stream);
-/* dw_hwc[R][S][C] fp32 += ... (zeroed by the caller) */
-/* workspace: cs_dwconv_wgrad_workspace(g) bytes of per-workgroup partial rows (folded by a second kernel: no atomics, dw_hwc is
- * overwritten, not accumulated into) */
+/* dw_hwc[R][S][C] fp32.  workspace: cs_dwconv_wgrad_workspace(g) bytes of per-workgroup partial rows [R*S*C] fp32 (folded by a
+ * second kernel: no atomics, dw_hwc is overwritten, not accumulated into); like the statistics query, room for the launch plan of
+ * either dtype */
 size_t cs_dwconv_wgrad_workspace(const CsConvGeom* g);
 int cs_dwconv_wgrad(const CsConvGeom* g, int dtype, const void* x, const void* dy, float* dw_hwc, float* workspace, void* stream);
 /* the same with the result in the parameter's own layout [C][1][R][S] (nn.Conv2d(groups = C).weight, model/efficientnet.py:97-103) */

@@ -221,16 +221,18 @@ def test_depthwise_tiled_kernels_everywhere_the_geometry_allows(dev):
     """Three generations of depthwise kernels share the entry points: the strip kernels serve every bf16 3x3 / 5x5 launch, the launch
     rule (csrc/dwse.hip: dw_tiled_geometry) sends part of what is left to the channel-tiled kernels, the rest goes to the
     element-per-thread ones.  CELLSEG_DW_NOSTRIP=1 switches the strips off; CELLSEG_DW_UNTILED=2 then forces the tiled kernels wherever
-    the geometry allows, =1 the element-per-thread kernels.  Every combination must pass the same per-op parity test (the knobs are
-    read once per process: child interpreters)."""
+    the geometry allows, =1 the element-per-thread kernels.  Every combination must pass the same per-op parity test and the exact-value
+    test of tests/test_depthwise_routes_gpu.py (not its ledger: that describes production routing; the knobs are read once per process:
+    child interpreters)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for mode in ("2", "1", "0"):
         env = dict(os.environ, CELLSEG_DW_UNTILED=mode, CELLSEG_DW_NOSTRIP="1", CELLSEG_LIB_FLAVOUR="ab")
-        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_efficientnet_gpu.py"), "-m", "gpu", "-x", "-q",
-                            "-k", "test_depthwise_conv"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_efficientnet_gpu.py"),
+                            os.path.join(root, "tests", "test_depthwise_routes_gpu.py"), "-m", "gpu", "-x", "-q",
+                            "-k", "test_depthwise_conv or test_dw_exact_values"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
         assert r.returncode == 0, (mode, (r.stdout + r.stderr)[-3000:])
 
 
