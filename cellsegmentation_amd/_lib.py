@@ -149,6 +149,9 @@ _SIGNATURES = {
     "cs_detect_meanshift": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _P, _P, _P]),
     "cs_detect_cluster_workspace": (c_size_t, [c_int, c_int]),
     "cs_detect_cluster": (c_int, [_P, _P, c_int, c_int, c_double, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cs_detect_edt_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cs_detect_edt_sq": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "cs_detect_edt_smooth": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_regions_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_label": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_regions_areas": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

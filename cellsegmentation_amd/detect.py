@@ -17,7 +17,18 @@ Steps, each integer arithmetic or one correctly rounded fp64 operation, so the r
 * order      weight descending, then label descending (``np.argsort(w, kind="stable")[::-1]``).  The reference uses the default
              (unstable) argsort, so among equal weights its order is unspecified; here it is fixed.
 
-``method="distancetransform"`` is not implemented.
+``method="distancetransform"`` (test_seg.py:325-329) replaces the blur step of ``detect_points`` / ``inference.detect_cells``:
+
+* threshold  foreground = ``u8 > thr_for_dt`` (default 10), background everything else.
+* distance   ``D2`` = exact squared Euclidean distance to the nearest background pixel of the map (int32; 0 on background; ``-1``
+             everywhere in a map without any background).  Maps with ``H^2 + W^2 >= 2^31`` raise ``ValueError``.  Pinned against
+             ``scipy.ndimage.distance_transform_edt`` (tests/golden/edt_vectors.npz).
+* normalise  ``M = max D2`` of the map itself (never of the batch); all zeros where ``M <= 0``; otherwise ``255 sqrt(D2 / M)`` rounded
+             half to even, decided by the integer comparison ``4 255^2 D2 <> (2k + 1)^2 M``.  cv2 computes the distance in float32
+             and normalises in floating point; agreement with cv2's own rounding is NOT pinned (cv2 is not a dependency).
+
+``meanshift_cluster`` itself still refuses ``"distancetransform"``; ``detect_points(mask, cell_counts=c,
+method="distancetransform").per_image()[0]`` returns the pair it would.
 """
 import math
 from dataclasses import dataclass
@@ -106,6 +117,54 @@ def gaussian_blur(mask_u8, ksize, sigmaX, sigmaY=0):
     return out[0] if two_d else out
 
 
+_METHODS = ("gaussianblur", "distancetransform")
+
+
+def _check_method(method):
+    if method not in _METHODS:
+        raise ValueError("Smoothing method not found. ")
+
+
+def _dt_threshold(thr_for_dt):
+    """``u8 > thr`` for a real threshold is ``u8 > floor(thr)``; clamped to what an int32 holds (-1: all foreground)."""
+    t = float(thr_for_dt)
+    if not math.isfinite(t):
+        raise ValueError(f"thr_for_dt must be finite, got {thr_for_dt!r}")
+    return int(min(max(math.floor(t), -1), 255))
+
+
+def _check_dt_shape(shape):
+    H, W = (int(v) for v in shape[-2:])
+    if H * H + W * W >= 1 << 31:
+        raise ValueError(f"distance transform: H^2 + W^2 must stay below 2^31, got a {H}x{W} map")
+
+
+def _dt_maps(mask_u8, thr_for_dt, what):
+    thr = _dt_threshold(thr_for_dt)
+    if hasattr(mask_u8, "shape") and len(mask_u8.shape) >= 2:
+        _check_dt_shape(mask_u8.shape)                                    # before the map is copied anywhere
+    t, two_d = _as_u8_maps(mask_u8, what)
+    return t, two_d, thr
+
+
+def distance_transform_sq(mask_u8, thr_for_dt=10):
+    """Exact squared Euclidean distance of every pixel with ``mask > thr_for_dt`` to the nearest pixel without (module docstring);
+    ``-1`` everywhere in a map that has no such pixel.  mask_u8: uint8 [H, W] or [N, H, W] (numpy or torch); returns an int32
+    device tensor of the same shape."""
+    t, two_d, thr = _dt_maps(mask_u8, thr_for_dt, "distance_transform_sq")
+    out = K.detect_edt_sq(t, thr)
+    return out[0] if two_d else out
+
+
+def distance_smooth(mask_u8, thr_for_dt=10):
+    """The ``"distancetransform"`` smoothing (test_seg.py:325-329): threshold, exact distance transform, min-max normalisation of
+    every map to 0..255, rounded half to even in integer arithmetic (module docstring).  Returns a uint8 device tensor of the
+    same shape as mask_u8."""
+    t, two_d, thr = _dt_maps(mask_u8, thr_for_dt, "distance_smooth")
+    out = K.detect_edt_smooth(t, thr)
+    return out[0] if two_d else out
+
+
 def stitch_patches(patches, images_grid, image_hw):
     """Write patches uint8 [M, ph, pw] at upper-left corners images_grid [M, 2] (row, col) into a zeroed uint8 [H, W] mask; where
     patches overlap the one with the highest index wins, as the reference's write order (test_seg.py:255-257)."""
@@ -126,7 +185,7 @@ def stitch_patches(patches, images_grid, image_hw):
 @dataclass
 class DetectResult:
     """Cells of N maps: ``points[offsets[n]:offsets[n+1]]`` (int64 (row, col)) are map n's cluster centroids ordered by ``weights``
-    (blurred value under the centroid) descending, then label descending; ``n_kept[n]`` = seed windows kept."""
+    (smoothed value under the centroid) descending, then label descending; ``n_kept[n]`` = seed windows kept."""
     points: np.ndarray
     weights: np.ndarray
     offsets: np.ndarray
@@ -145,9 +204,15 @@ class DetectResult:
         return out
 
 
-def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, force_global):
-    """src: device [N,H,W] uint8 masks or fp32 probabilities (quantised inside the blur)."""
-    tx, ty = _blur_taps(ksize, sigmaX, sigmaY)
+def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, force_global, method="gaussianblur",
+            thr_for_dt=10):
+    """src: device [N,H,W] uint8 masks or fp32 probabilities (quantised inside the smoothing kernel)."""
+    _check_method(method)
+    if method == "gaussianblur":
+        tx, ty = _blur_taps(ksize, sigmaX, sigmaY)
+    else:
+        dt_thr = _dt_threshold(thr_for_dt)
+        _check_dt_shape(src.shape)
     if eps < 0 or not math.isfinite(eps):
         raise ValueError("eps must be finite and non-negative")
     if int(max_iter) < 0:
@@ -155,7 +220,7 @@ def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, si
     N, H, W = src.shape
     if K.detect_grid_size(H, W, interval, window_size) <= 0:
         raise ValueError(f"window_size {window_size} does not fit a {H}x{W} map (or interval {interval} is not positive)")
-    blurred = K.detect_blur(src, tx, ty)
+    blurred = K.detect_blur(src, tx, ty) if method == "gaussianblur" else K.detect_edt_smooth(src, dt_thr)
     pts, n_pts = K.detect_meanshift(blurred, int(interval), int(window_size), float(thr) * 255.0, int(max_iter))
     out_pts, out_w, out_off = K.detect_cluster(pts, n_pts, float(eps), blurred, force_global=force_global)
     head = torch.cat([out_off, n_pts.to(torch.int64)]).cpu().numpy()        # the one synchronisation of the batch
@@ -167,13 +232,18 @@ def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, si
 
 
 def detect_points(masks_u8, cell_counts=None, thr=0.2, window_size=16, interval=10, eps=15, ksize=(15, 15), sigmaX=3., sigmaY=0.,
-                  max_iter=100, _force_global=False):
-    """Blur, seed, mean-shift and cluster a batch of uint8 maps [N, H, W] (or one [H, W]) -> DetectResult.  cell_counts: None,
-    one count for every map, or one per map (applied by ``DetectResult.per_image``).  ``_force_global`` (tests) takes the
-    multi-launch clustering path at any size."""
-    _blur_taps(ksize, sigmaX, sigmaY)                                     # argument errors before any device work
-    t, _ = _as_u8_maps(masks_u8, "detect_points")
-    return _detect(t, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, _force_global)
+                  max_iter=100, _force_global=False, method="gaussianblur", thr_for_dt=10):
+    """Smooth, seed, mean-shift and cluster a batch of uint8 maps [N, H, W] (or one [H, W]) -> DetectResult.  cell_counts: None,
+    one count for every map, or one per map (applied by ``DetectResult.per_image``).  ``method="distancetransform"`` smooths by
+    ``distance_smooth(., thr_for_dt)`` instead of the blur (ksize, sigmaX and sigmaY are then not consulted).  ``_force_global``
+    (tests) takes the multi-launch clustering path at any size."""
+    _check_method(method)                                                 # argument errors before any device work
+    if method == "gaussianblur":
+        _blur_taps(ksize, sigmaX, sigmaY)
+        t, _ = _as_u8_maps(masks_u8, "detect_points")
+    else:
+        t, _, _ = _dt_maps(masks_u8, thr_for_dt, "detect_points")
+    return _detect(t, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, _force_global, method, thr_for_dt)
 
 
 _BLUR_KEYS = {"ksize", "sigmaX", "sigmaY", "borderType"}

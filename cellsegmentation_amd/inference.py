@@ -143,12 +143,14 @@ def inference_seg(loader, model, device, mode='train'):
     return np.concatenate(masks)
 
 
-def detect_cells(loader, model, device, eps=11, reg_limit=False, **blur):
+def detect_cells(loader, model, device, eps=11, reg_limit=False, method="gaussianblur", thr_for_dt=10, **blur):
     """Cell locations per image (test_seg.py cell_detect + meanshift_cluster, one map per image): segment-mode forward, softmax
     channel 1, quantise, then detect.detect_points with the remaining keyword arguments (thr, window_size, interval, ksize, sigmaX,
-    ...).  With reg_limit the image-mode count rint(reg) caps each image's list (test_seg.py:217-221; the model is set back to
-    segment mode afterwards).  Returns [(points, discarded)] per image, as meanshift_cluster."""
+    ...).  method="distancetransform" smooths by the exact distance transform of ``u8 > thr_for_dt`` instead of the blur (ksize and
+    sigma are then not consulted); either way the fp32 probabilities go straight into the smoothing kernel.  With reg_limit the
+    image-mode count rint(reg) caps each image's list (test_seg.py:217-221; the model is set back to segment mode afterwards).  Returns [(points, discarded)] per image, as meanshift_cluster."""
     from . import detect as D
+    D._check_method(method)
     unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
     if unknown:
         raise TypeError(f"detect_cells: unexpected arguments {sorted(unknown)}")
@@ -166,7 +168,7 @@ def detect_cells(loader, model, device, eps=11, reg_limit=False, **blur):
                 counts = np.round(model(x)[1].detach()[:, 0].float().cpu().numpy()).astype(int)
                 model.setmode("segment")
             res = D._detect(probs, counts, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10), eps, opts["ksize"],
-                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False)
+                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
             out.extend(res.per_image())
     return out
 

@@ -1136,6 +1136,32 @@ def detect_cluster(pts, n_pts, eps, blurred, force_global=False):
     return out_pts, out_w, out_off
 
 
+def _detect_edt(src, thr, smooth):
+    N, H, W = src.shape
+    lib = _lib.load()
+    ws_bytes = lib.cs_detect_edt_workspace(N, H, W, int(smooth))
+    if ws_bytes == 0:
+        raise ValueError(f"distance transform: a call takes 0 < N <= 65535 maps with H^2 + W^2 < 2^31, got {(N, H, W)}")
+    s = _aligned16(src)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=s.device)
+    out = torch.empty((N, H, W), dtype=torch.uint8 if smooth else torch.int32, device=s.device)
+    fn = lib.cs_detect_edt_smooth if smooth else lib.cs_detect_edt_sq
+    _lib.check(fn(_p(s), int(s.dtype == torch.float32), N, H, W, int(thr), _p(out), _p(ws), ws_bytes, _stream()),
+               "detect_edt_smooth" if smooth else "detect_edt_sq")
+    return out
+
+
+def detect_edt_sq(src, thr=10):
+    """src [N,H,W] uint8 or fp32 probabilities (quantised on the way in); foreground = u8 > thr -> int32 [N,H,W] exact squared
+    Euclidean distance to the nearest background pixel of the map (-1 everywhere in a map without background)."""
+    return _detect_edt(src, thr, False)
+
+
+def detect_edt_smooth(src, thr=10):
+    """src as detect_edt_sq -> uint8 [N,H,W] = 255 sqrt(D2 / max D2 of the map), rounded half to even in integer arithmetic."""
+    return _detect_edt(src, thr, True)
+
+
 # ---------------------------------------------------------------- small-region clean-up (csrc/regions.hip; regions.py is the public API)
 def regions_workspace(N, H, W, device):
     """the caller-owned scratch of one cs_regions_* call on [N,H,W] (reusable by later calls of the same shape)"""

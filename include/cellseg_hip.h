@@ -499,7 +499,15 @@ int cs_prune_excess(const int32_t* labels, long long n, int flag, long long n_ex
  *                      descending, written to out_pts[out_off[n] ..) (int64 [N cap][2]) and out_w (int32 [N cap]);
  *                      out_off int64 [N + 1].  Up to 2048 points per map are clustered inside one workgroup; larger maps (or
  *                      force_global) take a multi-launch path that reads one flag back per eight rounds (the host
- *                      synchronises with the stream there).  workspace >= cs_detect_cluster_workspace(N, cap) bytes. */
+ *                      synchronises with the stream there).  workspace >= cs_detect_cluster_workspace(N, cap) bytes.
+ * cs_detect_edt_sq   : the smoothing of method="distancetransform" (test_seg.py:325-329), first half.  src as for cs_detect_blur
+ *                      (fp32 needs 4-byte alignment only); foreground = u8 > thr.  d2 int32 [N][H][W] = exact squared Euclidean
+ *                      distance to the nearest background pixel of the same map (0 on background; -1 everywhere in a map without
+ *                      background).  Needs H^2 + W^2 < 2^31 and N <= 65535.  Three launches, no host synchronisation.
+ * cs_detect_edt_smooth: dst uint8 [N][H][W] = 255 sqrt(d2 / M) rounded half to even, M = the map's own maximum of d2 (all zeros
+ *                      where M <= 0), decided by the integer comparison 4 255^2 d2 <> (2k + 1)^2 M: no float decides a value.
+ *                      Four launches.  Both take a 16-byte aligned workspace of cs_detect_edt_workspace(N, H, W, smooth) bytes
+ *                      (smooth = 1 for cs_detect_edt_smooth; 0 for sizes a call would refuse). */
 int cs_detect_quantize(const float* probs, long long n, uint8_t* out, void* stream);
 int cs_detect_blur(const void* src, int src_is_f32, int N, int H, int W, const int32_t* taps_x, int kx, const int32_t* taps_y, int ky,
                    uint8_t* dst, void* stream);
@@ -513,6 +521,11 @@ size_t cs_detect_cluster_workspace(int N, int cap);
 int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N, int cap, double eps, const uint8_t* blurred, int H, int W,
                       int force_global, int64_t* out_pts, int32_t* out_w, int64_t* out_off, void* workspace,
                       size_t workspace_bytes, void* stream);
+size_t cs_detect_edt_workspace(int N, int H, int W, int smooth);
+int cs_detect_edt_sq(const void* src, int src_is_f32, int N, int H, int W, int thr, int32_t* d2, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cs_detect_edt_smooth(const void* src, int src_is_f32, int N, int H, int W, int thr, uint8_t* dst, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- small-region clean-up of binary masks (utils/image_processing.py:14-17 remove_small_regions; csrc/regions.hip) ---------
  * Masks are uint8 [N][H][W], non-zero = foreground, N images that share nothing; 0 < N <= 65535 and N H W < 2^31 per call.

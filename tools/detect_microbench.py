@@ -1,8 +1,10 @@
-"""Cell localisation timing: 128 probability maps of 299^2 (quantise + blur + mean shift + clustering, one batch) and one stitched
-4096^2 mask, device-event timed after warm-up, next to the numpy restatement (tests/detect_ref.py) on the host for the same work.
-Checks that the GPU outputs equal the restatement.
+"""Cell localisation timing: 128 probability maps of 299^2 (quantise + smoothing + mean shift + clustering, one batch) and one
+stitched 4096^2 mask, device-event timed after warm-up, next to the numpy restatement (tests/detect_ref.py, tests/edt_ref.py) on the
+host for the same work.  Checks that the GPU outputs equal the restatement.  --method picks the smoothing: the Gaussian blur, the
+exact distance transform, or both on the same maps in one run (the blur is then the yardstick of the distance form); the distance
+form is also timed on its worst case, a 4096^2 map that is all foreground but one pixel (smoothing kernels alone).
 
-    python tools/detect_microbench.py [--reps 5] [--host-maps 128] [--json PATH]
+    python tools/detect_microbench.py [--method both] [--reps 5] [--host-maps 128] [--json PATH]
 """
 import argparse
 import json
@@ -18,7 +20,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import detect_ref as R  # noqa: E402
+import edt_ref as E  # noqa: E402
 from cellsegmentation_amd import detect as D  # noqa: E402
+from cellsegmentation_amd import kernels as K  # noqa: E402
 
 
 def blob_probs(n, H, W, density, seed):
@@ -51,31 +55,44 @@ def time_dev(fn, reps):
     return float(np.median(ts)), ts
 
 
+def host_detect(method, mask):
+    return R.detect(mask, None, eps=11)[0] if method == "gaussianblur" else E.detect(mask, None, eps=11)[0]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=["gaussianblur", "distancetransform", "both"], default="gaussianblur")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-maps", type=int, default=128, help="maps of the batch also run (and checked) on the host")
     ap.add_argument("--json", default=None, help="also write the results to this file")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {}
+    methods = ["gaussianblur", "distancetransform"] if args.method == "both" else [args.method]
     # ---- 128 maps of 299^2
     probs = blob_probs(128, 299, 299, 1 / 1500, seed=1)
     pd = torch.from_numpy(probs).to(dev)
+    taps = D.gaussian_taps(15, 3.)
 
-    def gpu_batch():
-        return D._detect(pd, None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False)
-    ms, ts = time_dev(gpu_batch, args.reps)
-    out = gpu_batch()
-    t0 = time.perf_counter()
-    ok = True
-    for i in range(args.host_maps):
-        want = R.detect(R.quantize(probs[i]), None, eps=11)[0]
-        ok &= bool(np.array_equal(out.points[out.offsets[i]:out.offsets[i + 1]], want))
-    host_ms = (time.perf_counter() - t0) * 1e3
-    res["batch128_299"] = {"device_ms": ms, "device_ms_all": ts, "host_ms": host_ms, "host_maps": args.host_maps,
-                           "cells": int(out.offsets[-1]), "windows_kept": int(out.n_kept.sum()), "equal_to_host": ok}
-    print(json.dumps({"batch128_299": res["batch128_299"]}), flush=True)
+    for method in methods:
+        def gpu_batch():
+            return D._detect(pd, None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False, method)
+
+        def gpu_smooth():
+            return K.detect_blur(pd, taps, taps) if method == "gaussianblur" else K.detect_edt_smooth(pd, 10)
+        ms, ts = time_dev(gpu_batch, args.reps)
+        sm_ms, _ = time_dev(gpu_smooth, args.reps)
+        out = gpu_batch()
+        t0 = time.perf_counter()
+        ok = True
+        for i in range(args.host_maps):
+            want = host_detect(method, R.quantize(probs[i]))
+            ok &= bool(np.array_equal(out.points[out.offsets[i]:out.offsets[i + 1]], want))
+        host_ms = (time.perf_counter() - t0) * 1e3
+        key = "batch128_299" if method == "gaussianblur" else "batch128_299_dt"
+        res[key] = {"method": method, "device_ms": ms, "device_ms_all": ts, "smoothing_ms": sm_ms, "host_ms": host_ms,
+                    "host_maps": args.host_maps, "cells": int(out.offsets[-1]), "windows_kept": int(out.n_kept.sum()), "equal_to_host": ok}
+        print(json.dumps({key: res[key]}), flush=True)
     # ---- one stitched 4096^2 mask: 299^2 patches overlapping by 16 px, border-aligned last row / column
     H = W = 4096
     step = 299 - 16
@@ -87,18 +104,36 @@ def main():
     pq = D.quantize(torch.from_numpy(patches).to(dev))
     whole = D.stitch_patches(pq, grid, (H, W))
 
-    def gpu_whole():
-        return D._detect(whole[None], None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False)
-    ms, ts = time_dev(gpu_whole, args.reps)
-    out = gpu_whole()
-    t0 = time.perf_counter()
     mask = R.stitch(R.quantize(patches), grid, (H, W))
-    want = R.detect(mask, None, eps=11)[0]
-    host_ms = (time.perf_counter() - t0) * 1e3
-    ok = bool(np.array_equal(whole.cpu().numpy(), mask)) and bool(np.array_equal(out.points, want))
-    res["stitched_4096"] = {"device_ms": ms, "device_ms_all": ts, "host_ms": host_ms, "patches": len(grid), "cells": int(out.offsets[-1]),
-                            "windows_kept": int(out.n_kept.sum()), "equal_to_host": ok}
-    print(json.dumps({"stitched_4096": res["stitched_4096"]}), flush=True)
+    stitched_ok = bool(np.array_equal(whole.cpu().numpy(), mask))
+    for method in methods:
+        def gpu_whole():
+            return D._detect(whole[None], None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False, method)
+
+        def gpu_smooth():
+            return K.detect_blur(whole[None], taps, taps) if method == "gaussianblur" else K.detect_edt_smooth(whole[None], 10)
+        ms, ts = time_dev(gpu_whole, args.reps)
+        sm_ms, _ = time_dev(gpu_smooth, args.reps)
+        out = gpu_whole()
+        t0 = time.perf_counter()
+        want = host_detect(method, mask)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        ok = stitched_ok and bool(np.array_equal(out.points, want))
+        key = "stitched_4096" if method == "gaussianblur" else "stitched_4096_dt"
+        res[key] = {"method": method, "device_ms": ms, "device_ms_all": ts, "smoothing_ms": sm_ms, "host_ms": host_ms, "patches": len(grid),
+                    "cells": int(out.offsets[-1]), "windows_kept": int(out.n_kept.sum()), "equal_to_host": ok}
+        print(json.dumps({key: res[key]}), flush=True)
+    if "distancetransform" in methods:
+        # ---- the distance form's worst case: every pixel's row search runs to the one background pixel's column
+        worst = torch.full((1, H, W), 255, dtype=torch.uint8, device=dev)
+        worst[0, H // 2, W // 2] = 0
+        ms, ts = time_dev(lambda: K.detect_edt_smooth(worst, 10), args.reps)
+        yy, xx = np.mgrid[0:H, 0:W]
+        d2 = (yy - H // 2) ** 2 + (xx - W // 2) ** 2
+        ok = bool(np.array_equal(K.detect_edt_sq(worst, 10)[0].cpu().numpy(), d2))
+        ok &= bool(np.array_equal(K.detect_edt_smooth(worst, 10)[0].cpu().numpy(), E.normalise(d2)))
+        res["worst_4096_dt"] = {"method": "distancetransform", "smoothing_ms": ms, "smoothing_ms_all": ts, "equal_to_host": ok}
+        print(json.dumps({"worst_4096_dt": res["worst_4096_dt"]}), flush=True)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
