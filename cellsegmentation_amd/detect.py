@@ -191,6 +191,8 @@ class DetectResult:
     offsets: np.ndarray
     n_kept: np.ndarray
     cell_counts: object = None
+    device_points: object = None      # the clustering kernel's own points / offsets, still on the device (filled by _detect):
+    device_offsets: object = None     # score() reads these, so the detections are not uploaded again
 
     def per_image(self):
         """[(points[:count], points[count:])] per map, as ``meanshift_cluster`` returns; ``(points, [])`` without a count."""
@@ -202,6 +204,35 @@ class DetectResult:
                 c = c[n]
             out.append((pts, []) if c is None else (pts[:int(c)], pts[int(c):]))
         return out
+
+    def score(self, points, offsets=None, gt_xy=False, radius=16, return_match=False):
+        """Precision, recall and F1 of every map's kept detections -- ``per_image()[n][0]``, i.e. ``cell_counts`` applied as the
+        limit -- against annotated points (score.score_points, test_seg.py:120-141) -> score.ScoreResult.  points: a sequence of one
+        ``[k, 2]`` array per map, an ``[N, k, 2]`` array, one ``[k, 2]`` array for a single map, or a concatenated ``[G, 2]`` array
+        with ``offsets`` [N + 1].  ``gt_xy``: the annotations are (x, y) while the detections are (row, col)."""
+        from . import score as S
+        N = len(self.offsets) - 1
+        radius2 = S.radius_squared(radius)
+        if offsets is None:
+            if isinstance(points, (list, tuple)):
+                if len(points) != N:
+                    raise ValueError(f"{N} maps but {len(points)} point arrays")
+                points, offsets = S.ragged(points)
+            elif _ndim(points) == 3:
+                if points.shape[0] != N or points.shape[2] != 2:
+                    raise ValueError(f"expected annotations shaped [{N}, k, 2], got {tuple(points.shape)}")
+                offsets = np.arange(N + 1, dtype=np.int64) * int(points.shape[1])
+                points = points.reshape(-1, 2)
+            elif N != 1:
+                raise ValueError(f"{N} maps: pass one point array per map, or offsets")
+        prepared = S._prepare(points, offsets, N, gt_xy)
+        limits = S._limits(self.cell_counts, N)
+        if self.device_points is None:
+            hat, off = torch.from_numpy(np.ascontiguousarray(self.points, dtype=np.int64)), torch.from_numpy(np.ascontiguousarray(self.offsets, dtype=np.int64))
+            hat, off = hat.reshape(-1, 2).to(_device()), off.to(_device())
+        else:
+            hat, off = self.device_points, self.device_offsets
+        return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
 
 
 def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, force_global, method="gaussianblur",
@@ -228,7 +259,7 @@ def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, si
     total = int(offsets[-1])
     points = out_pts[:total].cpu().numpy()
     weights = out_w[:total].cpu().numpy().astype(np.int64)
-    return DetectResult(points, weights, offsets, n_kept, cell_counts)
+    return DetectResult(points, weights, offsets, n_kept, cell_counts, out_pts, out_off)
 
 
 def detect_points(masks_u8, cell_counts=None, thr=0.2, window_size=16, interval=10, eps=15, ksize=(15, 15), sigmaX=3., sigmaY=0.,

@@ -194,3 +194,67 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
             classes = Rg.threshold(probs, threshold)
             out.append(Rg.remove_small_regions(classes, mo, ho, out=classes))
     return torch.cat(out) if out else torch.zeros((0,), dtype=torch.bool, device=device)
+
+
+def _batch_points(points, n):
+    """the annotations of a batch as the loader yields them -> a list of n [k, 2] arrays: a list of per-image arrays, or the
+    [n, k, 2] tensor the default collate makes of equally long lists (batch size 1 in the reference)"""
+    if isinstance(points, (list, tuple)):
+        per = list(points)
+    else:
+        if points.ndim != 3:
+            raise ValueError(f"evaluate_detection: expected annotations shaped [n, k, 2], got {tuple(points.shape)}")
+        per = [points[i] for i in range(points.shape[0])]
+    if len(per) != n:
+        raise ValueError(f"evaluate_detection: {n} images but {len(per)} annotation arrays")
+    return per
+
+
+def evaluate_detection(loader, model, device, threshold=0.5, eps=11, reg_limit=False, method="gaussianblur", thr_for_dt=10,
+                       min_object_size=300, hole_area_threshold=100, radius=16, **blur):
+    """The evaluation loop of test_seg.py ``test()`` (:511-543) with its localisation block (:530-536) active, a batch at a time
+    on the device.  The loader yields ``(images, masks, points, ...)`` as ``PointTestset`` does: masks uint8 0 / 255 [n, H, W],
+    points a list of [k, 2] (x, y) arrays or one [n, k, 2] tensor.  Per batch: one segment-mode forward and softmax channel 1; the
+    image-mode count rint(reg) (always, it is the ``count`` column; with reg_limit a count of 0 zeroes the map and the count caps
+    the detection list); detect._detect and DetectResult.score against the annotations within ``radius``; ``> threshold``,
+    remove_small_regions and dice_coef against ``mask / 255``.  Returns a dict of numpy arrays ``count, tp, fp, fn, p, r, f1,
+    dice`` (the columns of center.csv) and ``mean`` = the averages (p, r, f1, dice) that ``MetricGroup.avg()`` prints.  The model
+    is left in segment mode."""
+    from . import detect as D
+    from . import metrics as M
+    from . import regions as Rg
+    from . import score as S
+    D._check_method(method)
+    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
+    if unknown:
+        raise TypeError(f"evaluate_detection: unexpected arguments {sorted(unknown)}")
+    opts = {"ksize": (15, 15), "sigmaX": 3.}
+    opts.update(blur)
+    mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
+    S.radius_squared(radius)
+    model.setmode("segment")
+    model.eval()
+    cols = {k: [] for k in ("count", "tp", "fp", "fn", "p", "r", "f1", "dice")}
+    with torch.no_grad():
+        for i, batch in enumerate(tqdm(loader, desc="testing")):
+            images, masks, points = batch[0], batch[1], batch[2]
+            x = images.to(device)
+            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+            model.setmode("image")
+            reg = torch.round(model(x)[1].detach()[:, 0].float())
+            model.setmode("segment")
+            counts = reg.cpu().numpy().astype(int)
+            if reg_limit:
+                probs = probs * (reg != 0).to(probs.dtype)[:, None, None]
+            res = D._detect(probs, counts if reg_limit else None, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10),
+                            eps, opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
+            sc = res.score(_batch_points(points, x.shape[0]), gt_xy=True, radius=radius)
+            classes = Rg.threshold(probs, threshold)
+            classes = Rg.remove_small_regions(classes, mo, ho, out=classes)
+            truth = torch.as_tensor(masks).to(device=device, dtype=torch.float32) / 255
+            dice = M.dice_coef(classes.float(), truth.reshape(classes.shape))
+            for k, v in zip(cols, (counts, sc.tp, sc.fp, sc.fn, sc.precision, sc.recall, sc.f1, dice.cpu().numpy().astype(np.float64))):
+                cols[k].append(v)
+    out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
+    out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "dice"))
+    return out

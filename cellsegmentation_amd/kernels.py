@@ -1235,3 +1235,56 @@ def regions_hsv_gate(images_hwc, mask, v_max=170):
     if mask.numel():
         _lib.check(_lib.load().cs_regions_hsv_gate(_p(images_hwc), _p(mask), mask.numel(), int(v_max), _p(out), _stream()), "regions_hsv_gate")
     return out
+
+
+# ---------------------------------------------------------------- detections against annotations (csrc/score.hip; score.py is the public API)
+def score_workspace(N, total_gt, device):
+    """the caller-owned scratch of one cs_score_points call on N images with total_gt annotations in all"""
+    ws_bytes = _lib.load().cs_score_workspace(int(N), int(total_gt))
+    if ws_bytes == 0:
+        raise ValueError(f"score_points: a call takes 0 < N <= 65535 images, got {N}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+
+
+def score_points(hat, hat_off, gt, gt_off, limits=None, radius2=256, want_match=False, force_block=False, ws=None):
+    """hat int64 [T,2] with hat_off int64 [N+1] (detect_cluster's points and offsets as they are), gt int32 [G,2] with gt_off int64
+    [N+1], limits int32 [N] or None (Python's [:c] per image) -> (counts int32 [N,3] = tp, fp, fn; match int32 [T] or None) on the
+    device.  match: the annotation index within the image, -1 = false positive, -2 = not scored (beyond the limit, or a row of hat
+    that hat_off does not cover).  force_block (tests): the 256-thread path for images of at most 64 annotations too."""
+    def need(t, what, dtype, tail):
+        if not torch.is_tensor(t):
+            raise TypeError(f"score_points: {what} must be a torch tensor")
+        if t.dtype != dtype:
+            raise TypeError(f"score_points: {what} must be {dtype}, got {t.dtype}")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"score_points: {what} must be shaped [n{''.join(f', {v}' for v in tail)}], got {tuple(t.shape)}")
+        if not t.is_cuda or t.device != hat_off.device:
+            raise ValueError(f"score_points: {what} must live on the device of hat_off")
+        return t.contiguous()
+
+    if not torch.is_tensor(hat_off) or not hat_off.is_cuda:
+        raise ValueError("score_points: hat_off must be a device tensor")
+    hat_off = need(hat_off, "hat_off", torch.int64, ())
+    N = hat_off.numel() - 1
+    if N < 1 or N > 65535:
+        raise ValueError(f"score_points: a call takes 0 < N <= 65535 images, got {N}")
+    hat = need(hat, "hat", torch.int64, (2,))
+    gt = need(gt, "gt", torch.int32, (2,))
+    gt_off = need(gt_off, "gt_off", torch.int64, ())
+    if gt_off.numel() != N + 1:
+        raise ValueError(f"score_points: {N + 1} detection offsets but {gt_off.numel()} annotation offsets")
+    if limits is not None:
+        limits = need(limits, "limits", torch.int32, ())
+        if limits.numel() != N:
+            raise ValueError(f"score_points: {N} images but {limits.numel()} limits")
+    radius2 = int(radius2)
+    if radius2 < 0 or radius2 >= 1 << 31:
+        raise ValueError(f"score_points: radius2 must be in [0, 2^31), got {radius2}")
+    if ws is None:
+        ws = score_workspace(N, gt.shape[0], hat.device)
+    counts = torch.empty((N, 3), dtype=torch.int32, device=hat.device)
+    match = torch.full((hat.shape[0],), -2, dtype=torch.int32, device=hat.device) if want_match else None
+    _lib.check(_lib.load().cs_score_points(_p(hat) if hat.numel() else None, _p(hat_off), _p(limits), _p(gt) if gt.numel() else None, _p(gt_off),
+                                           N, radius2, int(bool(force_block)), _p(counts), _p(match) if want_match and match.numel() else None,
+                                           _p(ws), ws.numel(), _stream()), "score_points")
+    return counts, match

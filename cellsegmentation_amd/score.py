@@ -1,0 +1,213 @@
+"""Detected cell centres against annotated ones: the reference's ``get_prf1`` (test_seg.py:120-141) with ``euclid_dist`` and
+``precision_recall`` (metrics/metrics.py:56-66), on the HIP path (csrc/score.hip), for a whole batch in one launch.
+
+Per image, in the order of the detections: a detection takes the nearest annotation that no earlier detection has taken (the
+lowest index among equally near ones, as the reference's strict ``<``) and keeps it when the distance is ``<= radius``; otherwise
+it is a false positive, also when a nearer annotation is already taken.  ``tp`` = matches, ``fp`` = detections - tp, ``fn`` =
+annotations left over.  Coordinates are integers, so the kernel compares squared distances in integers (``d2 <= floor(radius^2)``)
+and no float decides anything; the ratios are formed on the host in float64 exactly as ``precision_recall`` forms them.
+
+The result depends on the order of the detections.  ``detect.detect_points`` fixes that order (weight descending, then label
+descending), and ``DetectResult.score`` scores the device-resident detections of a batch without copying them back.
+"""
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import kernels as K
+
+_I32 = (-(1 << 31), (1 << 31) - 1)
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def precision_recall(tp, fp, fn, return_f1=False):
+    """metrics/metrics.py:60-66 for scalars or integer arrays, in float64: ``p = 1 if tp + fp == 0 else tp / (tp + fp)``,
+    ``r = 1 if tp + fn == 0 else tp / (tp + fn)`` and, with return_f1, ``f1 = 0 if p + r == 0 else 2 p r / (p + r)``."""
+    a = [np.asarray(v) for v in (tp, fp, fn)]
+    for v in a:
+        if v.dtype.kind not in "iu":
+            raise TypeError(f"precision_recall: counts must be integers, got {v.dtype}")
+        if v.size and int(v.min()) < 0:
+            raise ValueError("precision_recall: counts must be non-negative")
+    tp, fp, fn = (v.astype(np.float64) for v in a)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(tp + fp == 0, 1.0, tp / (tp + fp))
+        r = np.where(tp + fn == 0, 1.0, tp / (tp + fn))
+        if not return_f1:
+            return p[()], r[()]
+        f1 = np.where(p + r == 0, 0.0, (2 * p * r) / (p + r))
+    return p[()], r[()], f1[()]
+
+
+@dataclass
+class ScoreResult:
+    """Per image (arrays of length N): ``tp``, ``fp``, ``fn`` int64; ``precision``, ``recall``, ``f1`` float64.  ``match`` (int32,
+    one entry per detection row, or None): the index of the annotation taken within the detection's own image, -1 for a false
+    positive, -2 for a detection that was not scored (beyond its image's limit)."""
+    tp: np.ndarray
+    fp: np.ndarray
+    fn: np.ndarray
+    precision: np.ndarray
+    recall: np.ndarray
+    f1: np.ndarray
+    match: object = None
+
+
+def radius_squared(radius):
+    """``floor(radius^2)`` of a non-negative number, below 2^31: integer d2 <= it exactly where sqrt(d2) <= radius."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"radius must be a number, got {radius!r}")
+    r = float(radius)
+    if not math.isfinite(r) or r < 0:
+        raise ValueError(f"radius must be finite and non-negative, got {radius!r}")
+    r2 = math.floor(r * r)
+    if r2 >= 1 << 31:
+        raise ValueError(f"radius^2 must stay below 2^31, got radius {radius!r}")
+    return int(r2)
+
+
+def _points(x, what):
+    """-> ([n, 2] integer numpy array or torch tensor, is_torch); an empty 1-D array (``np.asarray([])``) is no points."""
+    if not torch.is_tensor(x):
+        x = np.asarray(x)
+        if x.size == 0 and x.ndim <= 2:
+            return np.zeros((0, 2), np.int64), False
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError(f"{what}: expected points shaped [n, 2], got shape {tuple(x.shape)}")
+    if torch.is_tensor(x):
+        if x.dtype not in _INT_DTYPES:
+            raise TypeError(f"{what}: expected integer coordinates, got {x.dtype}")
+        return x, True
+    if x.dtype.kind not in "iu":
+        raise TypeError(f"{what}: expected integer coordinates, got {x.dtype}")
+    if x.dtype == np.uint64 and x.size and int(x.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: a coordinate does not fit int64")
+    return x, False
+
+
+def _offsets(off, n_points, n_images, what):
+    """offsets (None = one image; numpy / sequence / torch, host or device) -> (host int64 array or None, device tensor or None)"""
+    if off is None:
+        return np.asarray([0, n_points], np.int64), None
+    if torch.is_tensor(off):
+        if off.dtype not in _INT_DTYPES or off.dim() != 1:
+            raise TypeError(f"{what}: expected a 1-D integer tensor")
+        if off.is_cuda:
+            if n_images is not None and off.numel() != n_images + 1:
+                raise ValueError(f"{what}: expected {n_images + 1} offsets, got {off.numel()}")
+            return None, off.to(torch.int64)
+        off = off.numpy()
+    off = np.asarray(off)
+    if off.ndim != 1 or off.dtype.kind not in "iu" or len(off) < 2:
+        raise ValueError(f"{what}: expected a 1-D integer sequence of N + 1 offsets")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != n_points or np.any(np.diff(off) < 0):
+        raise ValueError(f"{what}: offsets must rise from 0 to the number of points ({n_points})")
+    if n_images is not None and len(off) != n_images + 1:
+        raise ValueError(f"{what}: expected {n_images + 1} offsets, got {len(off)}")
+    return off, None
+
+
+def ragged(per_image):
+    """a sequence of N per-image point arrays ([k, 2], or empty) -> (points [sum k, 2], offsets int64 [N + 1]), on the host"""
+    arrs = []
+    for i, a in enumerate(per_image):
+        a, is_torch = _points(a, f"points of image {i}")
+        arrs.append(a.cpu().numpy() if is_torch else a)
+    off = np.zeros(len(arrs) + 1, np.int64)
+    if arrs:
+        np.cumsum([len(a) for a in arrs], out=off[1:])
+    pts = np.concatenate([a.astype(np.int64) for a in arrs]) if arrs else np.zeros((0, 2), np.int64)
+    return pts, off
+
+
+def _limits(limits, n_images):
+    """None, one count or one per image -> host int32 [N] (or a device tensor as given) with Python's [:c] meaning kept"""
+    if limits is None:
+        return None
+    if torch.is_tensor(limits) and limits.is_cuda:
+        if limits.dtype not in _INT_DTYPES or limits.dim() != 1 or limits.numel() != n_images:
+            raise ValueError(f"limits: expected {n_images} integers")
+        return limits
+    lim = np.asarray(limits.numpy() if torch.is_tensor(limits) else limits)
+    if lim.dtype.kind not in "iu":
+        raise TypeError(f"limits: expected integers, got {lim.dtype}")
+    if lim.ndim == 0:
+        lim = np.full(n_images, int(lim))
+    if lim.shape != (n_images,):
+        raise ValueError(f"limits: expected one count or {n_images} counts, got shape {lim.shape}")
+    return np.clip(lim.astype(np.int64), *_I32).astype(np.int32)          # clipping keeps the slice's meaning: n_hat < 2^31
+
+
+def _prepare(points, offsets, n_images, gt_xy):
+    """annotations -> (gt host int32 array or device tensor [G, 2] (row, col), offsets host / device); no device work"""
+    gt, gt_torch = _points(points, "points")
+    gt_off, gt_off_dev = _offsets(offsets, gt.shape[0], n_images, "offsets")
+    if gt_torch and gt.is_cuda:
+        gt = gt.flip(1) if gt_xy else gt
+        return gt, gt_off, gt_off_dev
+    g = gt.numpy() if gt_torch else gt
+    if g.size and (int(g.min()) < _I32[0] or int(g.max()) > _I32[1]):
+        raise ValueError("points: an annotation coordinate does not fit int32")
+    g = g.astype(np.int32)
+    return np.ascontiguousarray(g[:, ::-1] if gt_xy else g), gt_off, gt_off_dev
+
+
+def _run(hat_dev, hat_off_dev, n_hat_rows, prepared, limits, radius2, return_match, force_block=False):
+    """device detections + prepared annotations -> ScoreResult (one copy of the counts to the host, one of match if asked for)"""
+    dev = hat_dev.device
+    gt, gt_off, gt_off_dev = prepared
+
+    def up(x, dtype):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return t.to(device=dev, dtype=dtype).contiguous()
+
+    counts, match = K.score_points(hat_dev, hat_off_dev, up(gt, torch.int32), gt_off_dev.to(dev) if gt_off is None else up(gt_off, torch.int64),
+                                   None if limits is None else up(limits, torch.int32), radius2, want_match=return_match,
+                                   force_block=force_block)
+    c = counts.cpu().numpy().astype(np.int64)
+    if c.min(initial=0) < 0:
+        raise ValueError("score_points: the offsets do not describe the point arrays")
+    p, r, f1 = precision_recall(c[:, 0], c[:, 1], c[:, 2], return_f1=True)
+    m = match[:n_hat_rows].cpu().numpy() if return_match else None
+    return ScoreResult(c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy(), p, r, f1, m)
+
+
+def _device(*xs):
+    for x in xs:
+        if torch.is_tensor(x) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def score_points(points_hat, points, hat_offsets=None, offsets=None, limits=None, radius=16, gt_xy=False, return_match=False,
+                 _force_block=False):
+    """Score detections ``points_hat`` against annotations ``points`` -> ScoreResult.
+
+    One pair of ``[n, 2]`` integer arrays, or ragged batches: image n owns ``points_hat[hat_offsets[n]:hat_offsets[n + 1]]`` and
+    ``points[offsets[n]:offsets[n + 1]]``.  numpy or torch, on the host or the device.  Both sides use the same coordinate
+    convention, unless ``gt_xy``: then the annotations are (x, y) as ``PointTestset`` reads them while the detections are
+    (row, col).  ``limits``: None, one count or one per image, applied to every image's detections as Python's slice ``[:c]``
+    (what ``DetectResult.per_image`` does with a regression count); detections beyond it are not scored.  ``radius``: a
+    non-negative number, the reference's CELL_RADIUS_PXS = 16.  ``_force_block`` (tests) takes the 256-thread path at any size."""
+    radius2 = radius_squared(radius)
+    hat, hat_torch = _points(points_hat, "points_hat")
+    hat_off, hat_off_dev = _offsets(hat_offsets, hat.shape[0], None, "hat_offsets")
+    n_images = (len(hat_off) if hat_off is not None else hat_off_dev.numel()) - 1
+    if n_images > 65535:
+        raise ValueError(f"score_points: a call takes at most 65535 images, got {n_images}")
+    prepared = _prepare(points, offsets, n_images, gt_xy)
+    lim = _limits(limits, n_images)
+    dev = _device(points_hat, points, hat_offsets, offsets)
+    hat_dev = (hat if hat_torch else torch.from_numpy(np.ascontiguousarray(hat.astype(np.int64)))).to(device=dev, dtype=torch.int64).contiguous()
+    off_dev = hat_off_dev.to(dev) if hat_off is None else torch.from_numpy(hat_off).to(dev)
+    return _run(hat_dev, off_dev, hat.shape[0], prepared, lim, radius2, return_match, _force_block)
+
+
+def get_prf1(points_hat, points):
+    """test_seg.py:120-141 with its signature and return: ``(p, r, f1, tp, fp, fn)`` of one image, radius 16, both point lists in
+    the same coordinate convention; ``np.asarray([])`` is an empty list."""
+    res = score_points(points_hat, points)
+    return float(res.precision[0]), float(res.recall[0]), float(res.f1[0]), int(res.tp[0]), int(res.fp[0]), int(res.fn[0])

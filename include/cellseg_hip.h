@@ -555,6 +555,25 @@ int cs_regions_remove_small(const uint8_t* mask, int N, int H, int W, int min_ob
 int cs_regions_threshold(const float* probs, long long n, float threshold, uint8_t* out, void* stream);
 int cs_regions_hsv_gate(const uint8_t* images_hwc, const uint8_t* mask, long long n_pixels, int v_max, uint8_t* out, void* stream);
 
+/* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
+ * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of
+ * cs_detect_cluster as they are; gt int32 [G][2] with gt_off int64 [N + 1] are the annotations, in the same coordinate convention.
+ * Per image, in the order of the detections: a detection takes the annotation of smallest dr^2 + dc^2 among those no earlier
+ * detection has taken (the lowest index among equals) and keeps it when that is <= radius2 (0 <= radius2 < 2^31); otherwise it is
+ * a false positive, also when a nearer annotation is already taken.  Integer comparisons only: bit-exact and independent of
+ * scheduling.  A detection whose coordinate does not fit int32 matches nothing.
+ * hat_limit (int32 [N], or NULL) applies Python's slice [:c] to image n's detections: c >= 0 keeps min(c, n_hat), c < 0 keeps
+ * max(n_hat + c, 0); the rest are not scored (they are no false positives) and get match = -2.
+ * counts int32 [N][3] = (tp, fp, fn): matches, detections scored - tp, annotations left untaken.  match (int32 [hat_off[N]], or
+ * NULL): the annotation index within the detection's own image, -1 for a false positive.  An image whose offsets do not describe
+ * 0 <= n < 2^31 points, or whose flags would not fit the workspace, reports counts (-1, -1, -1).
+ * flags bit 0 forces the 256-thread block path on images of at most 64 annotations, which one wave scores otherwise (tests).
+ * One launch, no host synchronisation.  workspace: 16-byte aligned, >= cs_score_workspace(N, total_gt) bytes with
+ * total_gt >= gt_off[N] (0 for an N a call would refuse); its contents on entry do not matter. */
+size_t cs_score_workspace(int N, long long total_gt);
+int cs_score_points(const int64_t* hat, const int64_t* hat_off, const int32_t* hat_limit, const int32_t* gt, const int64_t* gt_off, int N,
+                    int radius2, int flags, int32_t* counts, int32_t* match, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
