@@ -122,6 +122,9 @@ _SIGNATURES = {
     "cs_concat_channels": (c_int, [_P, _P, c_int, _P, c_longlong, c_int, c_int, _P]),
     "cs_split_channels": (c_int, [_P, c_int, _P, _P, c_longlong, c_int, c_int, _P]),
     "cs_tile_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_longlong, c_int, POINTER(c_float), POINTER(c_float), c_int, _P, _P]),
+    "cs_stage_augmented_workspace": (c_size_t, [c_longlong]),
+    "cs_stage_augmented": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_int, POINTER(c_float),
+                                   POINTER(c_float), c_int, _P, _P, c_size_t, _P]),
     "cs_dice_fwd": (c_int, [_P, _P, c_int, c_longlong, c_float, c_int, _P, _P, _P]),
     "cs_dice_bwd": (c_int, [_P, _P, _P, c_int, c_longlong, c_float, c_int, _P, _P]),
     "cs_softmax_channel_fwd": (c_int, [_P, _P, c_int, c_int, c_longlong, c_int, _P]),

@@ -1288,3 +1288,54 @@ def score_points(hat, hat_off, gt, gt_off, limits=None, radius2=256, want_match=
                                            N, radius2, int(bool(force_block)), _p(counts), _p(match) if want_match and match.numel() else None,
                                            _p(ws), ws.numel(), _stream()), "score_points")
     return counts, match
+
+
+# ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
+def stage_augmented_workspace(n_tiles, device):
+    """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""
+    ws_bytes = _lib.load().cs_stage_augmented_workspace(int(n_tiles))
+    if ws_bytes == 0:
+        raise ValueError(f"stage_augmented: a call takes 0 < T < 2^31 tiles, got {n_tiles}")
+    return torch.empty((ws_bytes // 8,), dtype=torch.float64, device=device)
+
+
+def stage_augmented(images_u8, tile_img, tile_rc, th, tw, flips=None, ops=None, factors=None, has_contrast=False, dtype=torch.bfloat16,
+                    mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), out=None, ws=None):
+    """Device operands as they are (nothing is validated against the images here: augment.py does that on the host): images_u8 uint8
+    [n,H,W,3], tile_img int32 [T], tile_rc int32 [T,2], flips int8 [T] or None, ops int8 [T,4] with factors float32 [T,4] or None ->
+    NHWC [T,th,tw,8] dtype.  has_contrast: some record holds op code 1 (the mean reduction runs, into ws).  Enqueues 1 or 3 stream
+    operations and never synchronises: with out (and ws) given it can be captured into a graph."""
+    def need(t, what, dt, shape):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise TypeError(f"stage_augmented: {what} must be a {dt} tensor shaped {list(shape)}")
+        return t
+
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise TypeError("stage_augmented expects uint8 images shaped [n, H, W, 3]")
+    n, H, W, _ = images_u8.shape
+    T = int(tile_img.numel()) if torch.is_tensor(tile_img) else -1
+    need(tile_img, "tile_img", torch.int32, (T,))
+    need(tile_rc, "tile_rc", torch.int32, (T, 2))
+    if flips is not None:
+        need(flips, "flips", torch.int8, (T,))
+    if (ops is None) != (factors is None):
+        raise TypeError("stage_augmented: ops and factors come together")
+    if ops is not None:
+        need(ops, "ops", torch.int8, (T, 4))
+        need(factors, "factors", torch.float32, (T, 4))
+    if has_contrast and ops is None:
+        raise ValueError("stage_augmented: has_contrast without a jitter record")
+    code = _code(dtype)
+    if out is None:
+        out = torch.empty((T, th, tw, 8), dtype=dtype, device=images_u8.device)
+    elif out.dtype != dtype or tuple(out.shape) != (T, th, tw, 8):
+        raise TypeError(f"stage_augmented: out must be {dtype} shaped {[T, th, tw, 8]}")
+    if has_contrast and ws is None:
+        ws = stage_augmented_workspace(T, images_u8.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _lib.check(_lib.load().cs_stage_augmented(_p(images_u8), n, H, W, _p(tile_img), _p(tile_rc), _p(flips), _p(ops), _p(factors),
+                                              int(bool(has_contrast)), T, int(th), int(tw), m, s, code, _p(out),
+                                              _p(ws) if has_contrast else None, ws.numel() * 8 if has_contrast else 0, _stream()),
+               "stage_augmented")
+    return out

@@ -255,12 +255,15 @@ class MILResNet(nn.Module):
         return plan
 
     # ------------------------------------------------------------------ forward
+    def _is_staged(self, x):
+        return x.dim() == 4 and x.shape[-1] == 8 and x.shape[1] != 3 and x.dtype == self.compute_dtype
+
     def _trunk(self, x, bn_train, with_skips):
         if not x.is_cuda:
             raise RuntimeError("cellsegmentation_amd models run on the GPU only (HIP kernels, no CPU fallback); "
                                "move the model and its input to a cuda device")
-        if x.dim() == 4 and x.shape[-1] == 8 and x.shape[1] != 3 and x.dtype == self.compute_dtype:
-            xh = x                      # already staged NHWC tiles (cellsegmentation_amd.tiles.gather_tiles)
+        if self._is_staged(x):
+            xh = x                      # already staged NHWC tiles (cellsegmentation_amd.tiles.gather_tiles, augment.stage_*)
         elif x.dim() == 4 and x.shape[1] == 3 and not x.requires_grad:
             # the image as it comes from the loader: the engine converts it (straight into the paired stem operand for bf16)
             return E.run_plan(self._encoder_plan(with_skips), [], self.compute_dtype, bn_train, self.use_tr_read, input_nchw=x.float())
@@ -297,7 +300,7 @@ class MILResNet(nn.Module):
             feat = HF.gap_avgmax(x4, self.feature_dim)
             return self._image_branch(self.fc_image_cls, feat), self._image_branch(self.fc_image_reg, feat)
         elif self.mode == "segment":
-            cfg_hw = tuple(x.shape[-2:])
+            cfg_hw = tuple(x.shape[1:3]) if self._is_staged(x) else tuple(x.shape[-2:])      # staged input is NHWC
             (o,) = E.run_plan(self._decoder_plan(), [x4, x3, x2, x1], self.compute_dtype, self.training, self.use_tr_read, image_hw=cfg_hw)
             return HF.to_nchw(o, 2)
         else:

@@ -351,6 +351,27 @@ int cs_tile_gather(const uint8_t* images, int n_images, int H, int W, const int3
                    long long n_tiles, int size, const float* host_mean3, const float* host_std3, int dtype, void* out,
                    void* stream);
 
+/* cs_tile_gather with the reference's training augmentations (csrc/augment.hip): th x tw tiles (a whole image is one tile),
+ * per tile  crop -> /255 in fp32 -> colour ops on the un-flipped crop -> flip -> (v - mean) / std,  out[n_tiles][th][tw][8].
+ * flips (device int8 [n_tiles], NULL = none): the reference's transformIDX, bit 0 = horizontal, bit 1 = vertical:
+ *   out[y][x] = crop[bit 1 ? th-1-y : y][bit 0 ? tw-1-x : x].
+ * jitter_ops / jitter_factors (device int8 / float [n_tiles][4], both or neither; 4- and 16-byte aligned): a ColorJitter record,
+ * four op codes in application order (0 brightness, 1 contrast, 2 saturation, 3 hue, anything else = unused slot) with their
+ * factors, the float-image arithmetic of torchvision 0.11.2 with gray = 0.2989 r + 0.587 g + 0.114 b and
+ * blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1): brightness blend(x, 0, f); contrast blend(x, m, f) with m the mean of gray over
+ * the tile as the ops in front of it left it, m = fp32(sum_fp64 / (th tw)); saturation blend(x, gray(x), f); hue rgb -> hsv,
+ * h <- h + f - floor(h + f), hsv -> rgb.  The caller keeps a code from repeating within a record and the factors finite.
+ * has_contrast: 1 = some record holds a contrast op: the call zeroes the workspace and runs the mean reduction in front of the
+ * apply kernel (3 stream operations instead of 1); 0 = none does (one found is skipped) and workspace may be NULL.
+ * workspace: 8-byte aligned, >= cs_stage_augmented_workspace(n_tiles) bytes (0 for an n_tiles a call would refuse).
+ * The sum is order-independent (exact-limb accumulation): two calls give the same bits.  Never synchronises.  Without flips and
+ * jitter the output equals cs_tile_gather's bit for bit.  The caller guarantees tiles lie inside the image. */
+size_t cs_stage_augmented_workspace(long long n_tiles);
+int cs_stage_augmented(const uint8_t* images, int n_images, int H, int W, const int32_t* tile_img, const int32_t* tile_rc,
+                       const int8_t* flips, const int8_t* jitter_ops, const float* jitter_factors, int has_contrast,
+                       long long n_tiles, int th, int tw, const float* host_mean3, const float* host_std3, int dtype, void* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- heads: Linear (resnet.py:126,137,140,150), losses (train/train.py:34,80-83) ------------- */
 /* y[M][N] = act( x[M][K] @ w[N][K]^T + b[N] )  (fp32; b nullable; preact nullable: the value before act) */
 int cs_linear_fwd(const float* x, const float* w, const float* b, float* y, float* preact, int M, int N, int K, int act,
