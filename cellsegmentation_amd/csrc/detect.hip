@@ -14,6 +14,7 @@
 //             atomicMax; smoothed = 255 sqrt(D2 / M) rounded half to even, decided by 4 255^2 D2 <> (2k + 1)^2 M in int64
 // Every step is integer arithmetic or one correctly rounded fp64 operation, so the result does not depend on launch order.
 #include "cs_common.h"
+#include "cs_block.h"
 
 namespace {
 
@@ -178,14 +179,11 @@ __device__ __forceinline__ int axis_origin(int k, int n0, int len, int interval,
 __global__ __launch_bounds__(1024) void seed_kernel(const uint8_t* __restrict__ blurred, Grid g, double thr255, int32_t* __restrict__ pts,
                                                     int32_t* __restrict__ n_pts) {
     __shared__ int wsum[16];
-    __shared__ int carry;
     const int G = g.nr * g.nc;
     const uint8_t* img = blurred + (long long)blockIdx.x * g.H * g.W;
     int32_t* out = pts + (long long)blockIdx.x * G * 2;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
     const int half = g.window / 2;
+    int carry = 0;
     for (int base = 0; base < G; base += 1024) {
         const int k = base + threadIdx.x;
         int r = 0, c = 0, keep = 0;
@@ -194,23 +192,13 @@ __global__ __launch_bounds__(1024) void seed_kernel(const uint8_t* __restrict__ 
             c = axis_origin(k % g.nc, g.n0c, g.W, g.interval, g.window);
             keep = (double)img[(long long)(r + half) * g.W + c + half] > thr255;
         }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int off = carry;
-        for (int w = 0; w < wv; ++w) off += wsum[w];
+        int total;
+        const int at = carry + block_rank<1024>(keep, wsum, total);
         if (keep) {
-            out[2 * (off + before)] = r;
-            out[2 * (off + before) + 1] = c;
+            out[2 * at] = r;
+            out[2 * at + 1] = c;
         }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t = 0;
-            for (int w = 0; w < 16; ++w) t += wsum[w];
-            carry += t;
-        }
-        __syncthreads();
+        carry += total;
     }
     if (threadIdx.x == 0) n_pts[blockIdx.x] = carry;
 }
@@ -312,18 +300,13 @@ __global__ __launch_bounds__(1024) void cluster_lds_kernel(const int32_t* __rest
     }
     if (threadIdx.x == 0) changed = 0;
     __syncthreads();
-    auto root = [&](int l) {
-        int q;
-        while ((q = __hip_atomic_load(&lab[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != l) l = q;
-        return l;
-    };
     for (;;) {
         bool hooked = false;
         for (int i = threadIdx.x; i < n; i += 1024) {
             const int ir = pr[i], ic = pc[i];
             for (int j = i + 1; j < n; ++j) {
                 if (!linked(ir, ic, pr[j], pc[j], eps2)) continue;
-                const int a = root(i), b = root(j);
+                const int a = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, i), b = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, j);
                 if (a != b) {
                     atomicMin(&lab[max(a, b)], min(a, b));
                     hooked = true;
@@ -333,7 +316,7 @@ __global__ __launch_bounds__(1024) void cluster_lds_kernel(const int32_t* __rest
         if (hooked) changed = 1;
         __syncthreads();
         for (int i = threadIdx.x; i < n; i += 1024) {
-            const int r = root(i);
+            const int r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, i);
             __hip_atomic_store(&lab[i], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         __syncthreads();
@@ -354,12 +337,6 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(const int32_t* __rest
     const long long total = (long long)N * cap;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) lab[i] = (int)(i % cap);
     if (blockIdx.x == 0 && threadIdx.x < 2) state[threadIdx.x] = 0;
-}
-
-__device__ __forceinline__ int root_global(const int32_t* lab, int l) {
-    int q;
-    while ((q = __hip_atomic_load(lab + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != l) l = q;
-    return l;
 }
 
 __global__ __launch_bounds__(256) void cluster_hook_kernel(const int32_t* __restrict__ pts, const int32_t* __restrict__ n_pts, int cap,
@@ -388,7 +365,7 @@ __global__ __launch_bounds__(256) void cluster_hook_kernel(const int32_t* __rest
         for (int jj = 0; jj < jn; ++jj) {
             const int j = j0 + jj;
             if (j <= i || !linked(ir, ic, tr[jj], tc[jj], eps2)) continue;
-            const int a = root_global(lab, i), b = root_global(lab, j);
+            const int a = uf_find<__HIP_MEMORY_SCOPE_AGENT>(lab, i), b = uf_find<__HIP_MEMORY_SCOPE_AGENT>(lab, j);
             if (a != b) {
                 __hip_atomic_fetch_min(lab + max(a, b), min(a, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 hooked = true;
@@ -408,7 +385,7 @@ __global__ __launch_bounds__(256) void cluster_jump_kernel(const int32_t* __rest
         const int img = (int)(g / cap), i = (int)(g % cap);
         if (i >= min(n_pts[img], cap)) continue;
         int32_t* lab = lab_all + (long long)img * cap;
-        __hip_atomic_store(lab + i, root_global(lab, i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(lab + i, uf_find<__HIP_MEMORY_SCOPE_AGENT>(lab, i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -423,31 +400,18 @@ __global__ __launch_bounds__(1024) void cluster_ids_kernel(const int32_t* __rest
                                                            int32_t* __restrict__ cid_all, int32_t* __restrict__ n_clu,
                                                            unsigned long long* __restrict__ sums) {
     __shared__ int wsum[16];
-    __shared__ int carry;
     const int n = min(n_pts[blockIdx.x], cap);
     const int32_t* lab = lab_all + (long long)blockIdx.x * cap;
     int32_t* cid = cid_all + (long long)blockIdx.x * cap;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    int nc = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
-        const int is_root = i < n && lab[i] == i;
-        const unsigned long long bal = __ballot(is_root);
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int off = carry;
-        for (int w = 0; w < wv; ++w) off += wsum[w];
-        if (is_root) cid[i] = off + __popcll(bal & ((1ull << lane) - 1ull));
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t = 0;
-            for (int w = 0; w < 16; ++w) t += wsum[w];
-            carry += t;
-        }
-        __syncthreads();
+        const bool is_root = i < n && lab[i] == i;
+        int total;
+        const int before = block_rank<1024>(is_root, wsum, total);
+        if (is_root) cid[i] = nc + before;
+        nc += total;
     }
-    const int nc = carry;
     unsigned long long* s = sums + (long long)blockIdx.x * cap * 3;
     for (int k = threadIdx.x; k < 3 * nc; k += 1024) s[k] = 0;
     if (threadIdx.x == 0) n_clu[blockIdx.x] = nc;
@@ -472,24 +436,13 @@ __global__ __launch_bounds__(256) void cluster_accum_kernel(const int32_t* __res
 // single workgroup: off[0] = 0, off[i + 1] = off[i] + n_clu[i]
 __global__ __launch_bounds__(256) void cluster_offsets_kernel(const int32_t* __restrict__ n_clu, int N, int64_t* __restrict__ off) {
     __shared__ long long part[256];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) { carry = 0; off[0] = 0; }
-    __syncthreads();
+    long long carry = 0, total;
+    if (threadIdx.x == 0) off[0] = 0;
     for (int b0 = 0; b0 < N; b0 += 256) {
         const int i = b0 + threadIdx.x;
-        const long long v = i < N ? n_clu[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int s = 1; s < 256; s <<= 1) {
-            const long long add = threadIdx.x >= s ? part[threadIdx.x - s] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < N) off[i + 1] = carry + part[threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x == 255) carry += part[255];
-        __syncthreads();
+        const long long incl = block_scan_incl<256, long long>(i < N ? n_clu[i] : 0, part, total);
+        if (i < N) off[i + 1] = carry + incl;
+        carry += total;
     }
 }
 

@@ -15,6 +15,7 @@
 // The number of launches depends on (N, H, W) only and nothing synchronises with the host.
 #include <stdio.h>
 #include "cs_common.h"
+#include "cs_block.h"
 
 namespace {
 
@@ -23,40 +24,7 @@ constexpr int kTP = kT * kT;           // pixels per tile
 constexpr int kPer = kTP / 256;        // pixels per thread of the tile kernel
 constexpr int kNB = 1024;              // pixels per block of the numbering kernels
 
-__device__ __forceinline__ int find_lds(const int* lab, int x) {
-    int q;
-    while ((q = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != x) x = q;
-    return x;
-}
-__device__ __forceinline__ void unite_lds(int* lab, int a, int b) {
-    for (;;) {
-        a = find_lds(lab, a);
-        b = find_lds(lab, b);
-        if (a == b) return;
-        const int hi = max(a, b), lo = min(a, b);
-        const int old = atomicMin(lab + hi, lo);
-        if (old == hi) return;         // hi was a root and now hangs below lo
-        a = old;                       // hi had a parent already: that parent and lo are still to be united
-        b = lo;
-    }
-}
-__device__ __forceinline__ int find_global(const int32_t* lab, int x) {
-    int q;
-    while ((q = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != x) x = q;
-    return x;
-}
-__device__ __forceinline__ void unite_global(int32_t* lab, int a, int b) {
-    for (;;) {
-        a = find_global(lab, a);
-        b = find_global(lab, b);
-        if (a == b) return;
-        const int hi = max(a, b), lo = min(a, b);
-        const int old = __hip_atomic_fetch_min(lab + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == hi) return;
-        a = old;
-        b = lo;
-    }
-}
+constexpr int kLds = __HIP_MEMORY_SCOPE_WORKGROUP, kGlobal = __HIP_MEMORY_SCOPE_AGENT;   // where the labels of a union-find live
 
 // grid (tiles across, tiles down, N).  val: 0 / 1 = the pixel's value, 2 = outside the image.
 template <int CONN>
@@ -81,12 +49,12 @@ __global__ __launch_bounds__(256) void tile_label_kernel(const uint8_t* __restri
         const int ly = i >> 6, lx = i & 63;
         const int v = val[i];
         if (v == 2) continue;
-        if (lx > 0 && val[i - 1] == v) unite_lds(lab, i, i - 1);
+        if (lx > 0 && val[i - 1] == v) uf_unite<kLds>(lab, i, i - 1);
         if (ly > 0) {
-            if (val[i - kT] == v) unite_lds(lab, i, i - kT);
+            if (val[i - kT] == v) uf_unite<kLds>(lab, i, i - kT);
             if (CONN == 2) {
-                if (lx > 0 && val[i - kT - 1] == v) unite_lds(lab, i, i - kT - 1);
-                if (lx < kT - 1 && val[i - kT + 1] == v) unite_lds(lab, i, i - kT + 1);
+                if (lx > 0 && val[i - kT - 1] == v) uf_unite<kLds>(lab, i, i - kT - 1);
+                if (lx < kT - 1 && val[i - kT + 1] == v) uf_unite<kLds>(lab, i, i - kT + 1);
             }
         }
     }
@@ -95,7 +63,7 @@ __global__ __launch_bounds__(256) void tile_label_kernel(const uint8_t* __restri
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
         const int i = threadIdx.x + 256 * k;
-        root[k] = val[i] == 2 ? -1 : find_lds(lab, i);
+        root[k] = val[i] == 2 ? -1 : uf_find<kLds>(lab, i);
     }
     __syncthreads();
 #pragma unroll
@@ -129,7 +97,7 @@ __global__ __launch_bounds__(256) void border_kernel(const uint8_t* __restrict__
         long long e = g - n * per;
         const long long base = n * H * W;
         auto join = [&](long long p, long long q, bool v) {
-            if ((m[q] != 0) == v) unite_global(lab, (int)p, (int)q);
+            if ((m[q] != 0) == v) uf_unite<kGlobal>(lab, (int)p, (int)q);
         };
         if (e < n_row) {
             const int r = ((int)(e / W) + 1) * kT, c = (int)(e % W);
@@ -157,7 +125,7 @@ __global__ __launch_bounds__(256) void border_kernel(const uint8_t* __restrict__
 // lab[p] = root; the count a tile left at p moves to the root's slot (nothing is ever added to a slot that is not a root)
 __global__ __launch_bounds__(256) void flatten_kernel(long long total, int32_t* __restrict__ lab, int32_t* __restrict__ cnt) {
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
-        const int root = find_global(lab, (int)p);
+        const int root = uf_find<kGlobal>(lab, (int)p);
         __hip_atomic_store(lab + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int c = cnt[p];
         if (c != 0 && root != (int)p) atomicAdd(cnt + root, c);
@@ -187,14 +155,9 @@ __global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __rest
                                                            int32_t* __restrict__ blk) {
     __shared__ int wsum[kNB / 64];
     const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
-    const unsigned long long bal = __ballot(is_fg_root(m, lab, HW, i, blockIdx.y * HW));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kNB / 64; ++w) t += wsum[w];
-        blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] = t;
-    }
+    int total;
+    block_rank<kNB>(is_fg_root(m, lab, HW, i, blockIdx.y * HW), wsum, total);
+    if (threadIdx.x == 0) blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 // one workgroup per image: blk[n][0..B) -> its exclusive prefix sums, in place
@@ -205,15 +168,8 @@ __global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__
     const int lo = min((int)threadIdx.x * seg, B), hi = min(lo + seg, B);
     int s = 0;
     for (int i = lo; i < hi; ++i) s += blk[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
+    int total;
+    int run = block_scan_incl<1024>(s, part, total) - s;
     for (int i = lo; i < hi; ++i) {
         const int v = blk[i];
         blk[i] = run;
@@ -227,14 +183,10 @@ __global__ __launch_bounds__(kNB) void number_assign_kernel(const uint8_t* __res
     const long long base = blockIdx.y * HW;
     const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
     const bool root = is_fg_root(m, lab, HW, i, base);
-    const unsigned long long bal = __ballot(root);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) wsum[wv] = __popcll(bal);
-    __syncthreads();
+    int total;
+    const int before = block_rank<kNB>(root, wsum, total);
     if (!root) return;
-    int off = blk[(long long)blockIdx.y * gridDim.x + blockIdx.x];
-    for (int w = 0; w < wv; ++w) off += wsum[w];
-    num[base + i] = off + __popcll(bal & ((1ull << lane) - 1ull)) + 1;
+    num[base + i] = blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] + before + 1;
 }
 
 __global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ p, long long n, float thr, uint8_t* __restrict__ out) {

@@ -7,6 +7,7 @@
 // original order like numpy's lexsort).  Then a 3-kernel stream compaction (count / scan / write)
 // evaluates the reference's wrap-around predicate literally and emits order[index].
 #include "cs_common.h"
+#include "cs_block.h"
 
 namespace {
 
@@ -139,27 +140,15 @@ __global__ __launch_bounds__(256) void sel_count_kernel(SelPred q, long long T, 
 
 // single workgroup exclusive scan of block counts (nb <= a few thousand)
 __global__ __launch_bounds__(256) void sel_scan_kernel(int32_t* __restrict__ block_cnt, int nb, int64_t* __restrict__ out_count) {
-    __shared__ long long carry;
     __shared__ int part[256];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    long long carry = 0;
     for (int b0 = 0; b0 < nb; b0 += 256) {
         const int i = b0 + threadIdx.x;
         const int v = i < nb ? block_cnt[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        // Hillis-Steele inclusive scan in LDS
-        for (int off = 1; off < 256; off <<= 1) {
-            const int add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const long long excl = carry + part[threadIdx.x] - v;
-        if (i < nb) block_cnt[i] = (int32_t)excl;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += part[255];
-        __syncthreads();
+        int total;
+        const int incl = block_scan_incl<256>(v, part, total);
+        if (i < nb) block_cnt[i] = (int32_t)(carry + incl - v);
+        carry += total;
     }
     if (threadIdx.x == 0) *out_count = carry;
 }
@@ -176,18 +165,24 @@ __global__ __launch_bounds__(256) void sel_write_kernel(SelPred q, long long T, 
         c += f[e];
     }
     __shared__ int part[256];
-    part[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    long long w = (long long)block_off[blockIdx.x] + part[threadIdx.x] - c;
+    int total;
+    long long w = (long long)block_off[blockIdx.x] + block_scan_incl<256>(c, part, total) - c;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
         if (f[e]) out_idx[w++] = order[base + e];
+}
+
+// stream compaction of the positions where `q` holds, in position order: count per block, scan of the counts, write
+int launch_select(const SelPred& q, long long T, int32_t* block_cnt, const int64_t* order, int64_t* out_idx, int64_t* out_count,
+                  hipStream_t st) {
+    const int nb = (int)((T + kItems - 1) / kItems);
+    hipLaunchKernelGGL(sel_count_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, nb, out_count);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sel_write_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt, order, out_idx);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
 }
 
 }  // namespace
@@ -211,15 +206,7 @@ extern "C" int cs_segmented_topk(const float* probs, const int32_t* groups, cons
     int32_t* block_cnt = reinterpret_cast<int32_t*>(order + T);
     const int rc = launch_run_sort(probs, seg_offsets, n_groups, max_run, order, st);
     if (rc != CS_OK) return rc;
-    const int nb = (int)((T + kItems - 1) / kItems);
-    const SelPred q{groups, k_per_tile, nullptr, nullptr, 0.f};
-    hipLaunchKernelGGL(sel_count_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, nb, out_count);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sel_write_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt, order, out_idx);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return launch_select(SelPred{groups, k_per_tile, nullptr, nullptr, 0.f}, T, block_cnt, order, out_idx, out_count, st);
 }
 
 // ---- the steps either side of the top-k --------------------------------------------------------------
@@ -269,10 +256,8 @@ __global__ __launch_bounds__(256) void paint_tiles_kernel(const int64_t* __restr
 // order.  One workgroup walks the array in chunks of 2048 carrying both running counts (arrays here are <= a few 100k entries).
 __global__ __launch_bounds__(256) void prune_kernel(const int32_t* __restrict__ label, long long n, int flag, long long n_excess,
                                                     int64_t* __restrict__ kept, int64_t* __restrict__ kept_count) {
-    __shared__ int part_f[256], part_k[256];
-    __shared__ long long carry_f, carry_k;
-    if (threadIdx.x == 0) { carry_f = 0; carry_k = 0; }
-    __syncthreads();
+    __shared__ int part[256];
+    long long carry_f = 0, carry_k = 0;
     for (long long base = 0; base < n; base += 2048) {
         int isf[8], cf = 0;
 #pragma unroll
@@ -281,15 +266,8 @@ __global__ __launch_bounds__(256) void prune_kernel(const int32_t* __restrict__ 
             isf[e] = (i < n) && (label[i] == flag);
             cf += isf[e];
         }
-        part_f[threadIdx.x] = cf;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int add = threadIdx.x >= off ? part_f[threadIdx.x - off] : 0;
-            __syncthreads();
-            part_f[threadIdx.x] += add;
-            __syncthreads();
-        }
-        long long rank = carry_f + part_f[threadIdx.x] - cf;      // flagged entries before this thread's first position
+        int total_f, total_k;
+        long long rank = carry_f + block_scan_incl<256>(cf, part, total_f) - cf;      // flagged entries before this thread's first position
         int keep[8], ck = 0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -298,21 +276,12 @@ __global__ __launch_bounds__(256) void prune_kernel(const int32_t* __restrict__ 
             rank += isf[e];
             ck += keep[e];
         }
-        part_k[threadIdx.x] = ck;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int add = threadIdx.x >= off ? part_k[threadIdx.x - off] : 0;
-            __syncthreads();
-            part_k[threadIdx.x] += add;
-            __syncthreads();
-        }
-        long long w = carry_k + part_k[threadIdx.x] - ck;
+        long long w = carry_k + block_scan_incl<256>(ck, part, total_k) - ck;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             if (keep[e]) kept[w++] = base + (long long)threadIdx.x * 8 + e;
-        __syncthreads();
-        if (threadIdx.x == 255) { carry_f += part_f[255]; carry_k += part_k[255]; }
-        __syncthreads();
+        carry_f += total_f;
+        carry_k += total_k;
     }
     if (threadIdx.x == 0) *kept_count = carry_k;
 }
@@ -330,17 +299,8 @@ extern "C" int cs_threshold_select(const float* probs, const int64_t* order, lon
                                    int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream) {
     CS_CHECK_ARG(probs && order && out_idx && out_count && workspace && T > 0, "threshold_select: bad arguments");
     CS_CHECK_ARG(workspace_bytes >= cs_segmented_topk_workspace(T), "threshold_select: workspace too small (cs_segmented_topk_workspace)");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int32_t* block_cnt = reinterpret_cast<int32_t*>(workspace);
-    const int nb = (int)((T + kItems - 1) / kItems);
-    const SelPred q{nullptr, nullptr, probs, order, threshold};
-    hipLaunchKernelGGL(sel_count_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, nb, out_count);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sel_write_kernel, dim3(nb), dim3(256), 0, st, q, T, block_cnt, order, out_idx);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return launch_select(SelPred{nullptr, nullptr, probs, order, threshold}, T, reinterpret_cast<int32_t*>(workspace), order, out_idx, out_count,
+                         reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int cs_evaluate_tile_counts(const float* probs, const int64_t* order, const int32_t* groups, const int64_t* pos_from,

@@ -1003,16 +1003,21 @@ def softmax_channel_bwd(logits, dpc, ch=1):
     return dl
 
 
-def segmented_topk(probs, groups, k_per_tile, seg_offsets, max_run):
-    """Device-side order[index] of inference.py:31-43. Returns (out_idx[T] int64, count[1] int64)."""
+def _select_buffers(probs):
+    """(lib, T, workspace, out_idx[T] int64, count[1] int64) of one compaction over the T tiles of probs"""
     T = probs.numel()
     lib = _lib.load()
-    ws_bytes = lib.cs_segmented_topk_workspace(T)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=probs.device)
+    ws = torch.empty((lib.cs_segmented_topk_workspace(T),), dtype=torch.uint8, device=probs.device)
     out = torch.empty((T,), dtype=torch.int64, device=probs.device)
     cnt = torch.zeros((1,), dtype=torch.int64, device=probs.device)
+    return lib, T, ws, out, cnt
+
+
+def segmented_topk(probs, groups, k_per_tile, seg_offsets, max_run):
+    """Device-side order[index] of inference.py:31-43. Returns (out_idx[T] int64, count[1] int64)."""
+    lib, T, ws, out, cnt = _select_buffers(probs)
     _lib.check(lib.cs_segmented_topk(_p(probs), _p(groups), _p(k_per_tile), _p(seg_offsets), seg_offsets.numel() - 1,
-                                     int(max_run), T, _p(out), _p(cnt), _p(ws), ws_bytes, _stream()), "segmented_topk")
+                                     int(max_run), T, _p(out), _p(cnt), _p(ws), ws.numel(), _stream()), "segmented_topk")
     return out, cnt
 
 
@@ -1028,13 +1033,8 @@ def segmented_order(probs, seg_offsets, max_run):
 
 def threshold_select(probs, order, threshold):
     """order[probs[order] > threshold] -> (out_idx[T] int64, count[1] int64)."""
-    T = probs.numel()
-    lib = _lib.load()
-    ws_bytes = lib.cs_segmented_topk_workspace(T)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=probs.device)
-    out = torch.empty((T,), dtype=torch.int64, device=probs.device)
-    cnt = torch.zeros((1,), dtype=torch.int64, device=probs.device)
-    _lib.check(lib.cs_threshold_select(_p(probs), _p(order), T, float(threshold), _p(out), _p(cnt), _p(ws), ws_bytes, _stream()), "threshold_select")
+    lib, T, ws, out, cnt = _select_buffers(probs)
+    _lib.check(lib.cs_threshold_select(_p(probs), _p(order), T, float(threshold), _p(out), _p(cnt), _p(ws), ws.numel(), _stream()), "threshold_select")
     return out, cnt
 
 
