@@ -7,6 +7,8 @@
 //   m  = m + (1 - beta1) * (g' - m)      (lerp, as torch)
 //   v  = beta2 * v + (1 - beta2) * g'^2
 //   p  = p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+// SGD with momentum (second half of the file): what the drivers train with whenever a scheduler is given (train_tile.py:280-303,
+// train_seg.py:289-312, train_image.py:483-508: optim.SGD(lr, momentum=0.9, weight_decay=1e-4)), on the same tables and chunk list.
 #include "cs_common.h"
 #include <math.h>
 
@@ -144,4 +146,114 @@ extern "C" int cs_adam_step_dev(const CsAdamTensor* tensors_dev, const void* con
                        reinterpret_cast<const float2*>(coef_dev));
     CS_LAUNCH_CHECK();
     return CS_OK;
+}
+
+// ---- SGD (torch.optim.SGD, single-tensor form) -------------------------------------------------------------------------------
+//   g' = g + weight_decay * p
+//   momentum != 0:  first step of the tensor: buf = g'       later: buf = momentum * buf + (1 - dampening) * g'
+//                   nesterov: g' = g' + momentum * buf       otherwise: g' = buf
+//   p  = p - lr * g'
+// 20 B per parameter (read p, g, buf; write p, buf); 16 B on a tensor's first step (buf is only written), 12 B without momentum.
+namespace {
+
+enum { kSgdPlain = 0, kSgdFirst = 1, kSgdLater = 2 };      // no buffer / buf = g' / buf = momentum * buf + omd * g'
+
+template <int kMode>
+__device__ __forceinline__ void sgd1(float& p, float& b, float g, float lr, float mom, float omd, float wd, bool nesterov) {
+    g = g + wd * p;
+    if (kMode != kSgdPlain) {
+        b = kMode == kSgdFirst ? g : mom * b + omd * g;
+        g = nesterov ? g + mom * b : b;
+    }
+    p = p - lr * g;
+}
+
+// one chunk [begin, end) of one tensor; `buf` is neither read nor written in kSgdPlain and only written in kSgdFirst
+template <int kMode>
+__device__ __forceinline__ void sgd_chunk(float* __restrict__ p, float* __restrict__ buf, const float* __restrict__ g, long long begin, long long end,
+                                          float lr, float mom, float omd, float wd, bool nesterov) {
+    unsigned long long bits = ((unsigned long long)p) | ((unsigned long long)g);
+    if (kMode != kSgdPlain) bits |= (unsigned long long)buf;
+    const long long end4 = (bits & 15ull) == 0ull ? begin + ((end - begin) & ~3ll) : begin;      // unaligned: the scalar loop takes everything
+    for (long long i = begin + 4ll * threadIdx.x; i < end4; i += 1024) {
+        float4 pp = *reinterpret_cast<const float4*>(p + i), bb = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kMode == kSgdLater) bb = *reinterpret_cast<const float4*>(buf + i);
+        const float4 gg = *reinterpret_cast<const float4*>(g + i);
+        sgd1<kMode>(pp.x, bb.x, gg.x, lr, mom, omd, wd, nesterov);
+        sgd1<kMode>(pp.y, bb.y, gg.y, lr, mom, omd, wd, nesterov);
+        sgd1<kMode>(pp.z, bb.z, gg.z, lr, mom, omd, wd, nesterov);
+        sgd1<kMode>(pp.w, bb.w, gg.w, lr, mom, omd, wd, nesterov);
+        *reinterpret_cast<float4*>(p + i) = pp;
+        if (kMode != kSgdPlain) *reinterpret_cast<float4*>(buf + i) = bb;
+    }
+    for (long long i = end4 + threadIdx.x; i < end; i += 256) {
+        float pp = p[i], bb = 0.f;
+        if (kMode == kSgdLater) bb = buf[i];
+        sgd1<kMode>(pp, bb, g[i], lr, mom, omd, wd, nesterov);
+        p[i] = pp;
+        if (kMode != kSgdPlain) buf[i] = bb;
+    }
+}
+
+// `hyper` (capturable form, cs_sgd_step_dev): (lr, momentum) as two doubles in device memory, rounded to fp32 here as the host form
+// rounds its arguments; NULL: the two by-value arguments.  A tensor without a buffer takes the plain update whatever the momentum.
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const CsSgdTensor* __restrict__ tensors, AdamGrads grads, const int2* __restrict__ chunks, int t0,
+                                                        float lr, float mom, float omd, float wd, int nesterov, int first,
+                                                        const double* __restrict__ hyper) {
+    const int2 ch = chunks[blockIdx.x];                      // (tensor index, first element / kAdamChunk)
+    const CsSgdTensor t = tensors[ch.x];
+    if (hyper) {
+        lr = (float)hyper[0];
+        mom = (float)hyper[1];
+    }
+    const float* const* gt = grads.g;
+    const float* __restrict__ g = gt[ch.x - t0];
+    const long long begin = (long long)ch.y * kAdamChunk;
+    long long end = begin + kAdamChunk;
+    if (end > t.n) end = t.n;
+    if (t.buf == nullptr) sgd_chunk<kSgdPlain>(t.p, nullptr, g, begin, end, lr, mom, omd, wd, false);
+    else if (first) sgd_chunk<kSgdFirst>(t.p, t.buf, g, begin, end, lr, mom, omd, wd, nesterov != 0);
+    else sgd_chunk<kSgdLater>(t.p, t.buf, g, begin, end, lr, mom, omd, wd, nesterov != 0);
+}
+
+int sgd_launch(const char* who, const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+               double lr, double momentum, double dampening, double weight_decay, int nesterov, int first, const double* hyper_dev, void* stream) {
+    AdamGrads gr{};
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!grads_host[i]) {
+            cs_set_error_(who);
+            return CS_ERR_INVALID_ARG;
+        }
+        gr.g[i] = reinterpret_cast<const float*>(grads_host[i]);
+    }
+    // the scalars as torch forms them: python doubles, 1 - dampening in double, each rounded to fp32 once
+    hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tensors_dev, gr,
+                       reinterpret_cast<const int2*>(chunks_dev), t0, (float)lr, (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov,
+                       first, hyper_dev);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+}  // namespace
+
+extern "C" int cs_sgd_step(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+                           double lr, double momentum, double dampening, double weight_decay, int nesterov, int first, void* stream) {
+    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1,
+                 "sgd_step: 1..320 tensors per call, device tables, a HOST array of gradient pointers");
+    CS_CHECK_ARG(lr >= 0.0 && momentum >= 0.0 && weight_decay >= 0.0, "sgd_step: lr, momentum and weight_decay >= 0");
+    CS_CHECK_ARG(!nesterov || (momentum > 0.0 && dampening == 0.0), "sgd_step: nesterov requires momentum > 0 and dampening == 0");
+    return sgd_launch("sgd_step: NULL gradient", tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks, lr, momentum, dampening, weight_decay,
+                      nesterov, first, nullptr, stream);
+}
+
+extern "C" int cs_sgd_step_dev(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+                               const double* hyper_dev, double dampening, double weight_decay, int nesterov, int first, void* stream) {
+    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && hyper_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1,
+                 "sgd_step_dev: 1..320 tensors per call, device tables (tensors, chunks, the (lr, momentum) doubles), a HOST array of gradient "
+                 "pointers");
+    CS_CHECK_ARG(weight_decay >= 0.0, "sgd_step_dev: weight_decay >= 0");
+    // (momentum > 0 cannot be checked here: it lives on the device; a tensor without a buffer takes the plain update)
+    CS_CHECK_ARG(!nesterov || dampening == 0.0, "sgd_step_dev: nesterov requires dampening == 0");
+    return sgd_launch("sgd_step_dev: NULL gradient", tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks, 0.0, 0.0, dampening, weight_decay,
+                      nesterov, first, hyper_dev, stream);
 }

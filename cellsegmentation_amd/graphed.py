@@ -8,10 +8,13 @@ current stream with caller-owned buffers and no host synchronisation, so a whole
 
 Constraints (torch's graph-capture rules): fixed input shapes (use the eager step for a ragged last batch), no `.item()` /
 `.cpu()` inside the step, an optimizer that supports capture (`cellsegmentation_amd.optim.Adam(..., capturable=True)` -- the
-one-launch HIP Adam with its step counts on the device --, `torch.optim.Adam(..., capturable=True)`, SGD).  Parameters, BN
-running statistics and optimizer state are updated in place by the replay exactly as by the eager step.  Host code of the step
-does not run at a replay: a learning-rate scheduler is stepped by the caller after the call, and what it changed reaches the
-captured launches through a `pre_replay` hook (`optimizer.sync_hyper` of the HIP Adam).
+one-launch HIP Adam with its step counts on the device --, `torch.optim.Adam(..., capturable=True)`,
+`cellsegmentation_amd.optim.SGD(..., capturable=True)` -- the one-launch HIP SGD reading `lr` and momentum from device memory).
+`torch.optim.SGD` captures too, but passes `lr` and momentum as launch scalars: every replay uses the values of the capture, so a
+scheduler (OneCycleLR moves both at every iteration) is silently frozen.  Parameters, BN running statistics and optimizer state
+are updated in place by the replay exactly as by the eager step.  Host code of the step does not run at a replay: a learning-rate
+scheduler is stepped by the caller after the call, and what it changed reaches the captured launches through a `pre_replay` hook
+(`optimizer.sync_hyper` of the HIP Adam and the HIP SGD).
 
 Round 5: the ResNet-50 tile step of train/train.py:29-42 (`--scratch`) is captured too (bench.py's headline; bit-for-bit equality
 with eager steps in tests/test_graphed_gpu.py): 6.0 ms of host work per step leave the critical path.

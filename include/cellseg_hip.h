@@ -261,6 +261,23 @@ int cs_adam_step(const CsAdamTensor* tensors_dev, const void* const* grads_host,
 int cs_adam_step_dev(const CsAdamTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev,
                      int n_chunks, float* const* steps_dev, float* coef_dev, const double* lr_dev, double lr, double beta1, double beta2,
                      double eps, double weight_decay, void* stream);
+/* torch.optim.SGD's update (what the drivers train with when a scheduler is given: train_tile.py:280-303, train_seg.py:289-312,
+ * train_image.py:483-508 -- momentum 0.9, weight_decay 1e-4), single-tensor form, on the same machinery: tensors_dev / grads_host /
+ * chunks_dev as for cs_adam_step, cs_adam_chunk_elems() elements per chunk, at most cs_adam_max_tensors() tensors per call.
+ *   g' = g + weight_decay * p;   buf = first ? g' : momentum * buf + (1 - dampening) * g';   g' = nesterov ? g' + momentum * buf : buf;
+ *   p = p - lr * g'
+ *   buf      : NULL for a tensor that takes the plain update p = p - lr * g' (momentum 0)
+ *   first    : not 0 when the tensors of this launch have no momentum history yet (buf is written, not read)
+ *   nesterov : requires momentum > 0 and dampening == 0, as in torch
+ * The scalars are rounded to fp32 once, from double: (float)lr, (float)momentum, (float)(1 - dampening), (float)weight_decay. */
+typedef struct CsSgdTensor { float* p; float* buf; long long n; } CsSgdTensor;
+int cs_sgd_step(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+                double lr, double momentum, double dampening, double weight_decay, int nesterov, int first, void* stream);
+/* The same update with hyper_dev[0] = lr and hyper_dev[1] = momentum read from DEVICE memory (two doubles, rounded to fp32 in the
+ * kernel) by every workgroup: a launch captured into a HIP graph takes the values a scheduler wrote there since the last replay
+ * (OneCycleLR moves both at every iteration).  dampening, weight_decay, nesterov and first are launch arguments, fixed at capture. */
+int cs_sgd_step_dev(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+                    const double* hyper_dev, double dampening, double weight_decay, int nesterov, int first, void* stream);
 
 /* Per-sample, per-channel sums of an NHWC tensor [N][HW][C]: out[n][c] = scale * sum_p a[n][p][c] (* b[n][p][c] when b != NULL),
  * fp32 [N][C], overwritten.  The two reductions of a squeeze-excitation block (torchvision SqueezeExcitation as used by
