@@ -117,7 +117,7 @@ _SIGNATURES = {
     "cs_dw_weights_hwc_multi": (c_int, [_P, c_int, ctypes.c_longlong, _P]),
     "cs_dwconv_wgrad_workspace": (ctypes.c_size_t, [POINTER(CsConvGeom)]),
     "cs_se_scale": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, _P]),
-    "cs_se_scale_bwd": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "cs_se_scale_bwd_dx": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cs_rowscale_add": (c_int, [_P, c_int, _P, _P, _P, c_int, c_longlong, _P]),
     "cs_bilinear_ac_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "cs_bilinear_ac_bwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -10,7 +10,7 @@ extern "C" void cs_set_error_(const char* msg) {
     strncpy(g_err, msg ? msg : "", sizeof(g_err) - 1);
     g_err[sizeof(g_err) - 1] = '\0';
 }
-extern "C" int cs_abi_version(void) { return 9; }   // 3: packed-operand convolutions (conv_v2), packed layouts in CsStageDesc; 4: round-3 entry points (cs_adam_step, cs_sample_sum, ...); 5: cs_set_igemm_path left the production library (A/B flavour only), CS_BN_BWD_* flags; 6: cs_adam_step_dev (device step counts: capturable); 7: cell localisation (cs_detect_*, cs_stitch_*); 8: cs_stage_conv_bn_one replaces cs_stage_conv_bn (one staging body; scale/shift/rstd of CsStageDesc nullable); 9: small-region clean-up (cs_regions_*); pure additions since, version unchanged: cs_score_*, cs_augment_*, cs_sgd_step / cs_sgd_step_dev
+extern "C" int cs_abi_version(void) { return 10; }   // 3: packed-operand convolutions (conv_v2), packed layouts in CsStageDesc; 4: round-3 entry points (cs_adam_step, cs_sample_sum, ...); 5: cs_set_igemm_path left the production library (A/B flavour only), CS_BN_BWD_* flags; 6: cs_adam_step_dev (device step counts: capturable); 7: cell localisation (cs_detect_*, cs_stitch_*); 8: cs_stage_conv_bn_one replaces cs_stage_conv_bn (one staging body; scale/shift/rstd of CsStageDesc nullable); 9: small-region clean-up (cs_regions_*); pure additions since, version unchanged: cs_score_*, cs_augment_*, cs_sgd_step / cs_sgd_step_dev; 10: cs_se_scale_bwd (two phases, the first on float atomics) became cs_se_scale_bwd_dx; the squeeze-excitation sums are cs_sample_sum
 extern "C" const char* cs_last_error(void) { return g_err; }
 
 // name of the conv-family kernel instantiation the calling thread launched last (set by the launchers)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include "../../include/cellseg_hip.h"
 
@@ -27,10 +28,6 @@ template <> struct Elem<bf16_t> {
     static constexpr int kChunk = 8;
     static constexpr int kDtype = CS_BF16;
 };
-
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t lo16) {
-    return __uint_as_float(lo16 << 16);
-}
 
 // 8 consecutive elements -> 8 floats (p must be 16-byte aligned for bf16, 32 for the pair of float4s
 // is NOT required: two independent 16-byte loads).
@@ -131,7 +128,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // Accumulator of a C-channel tensor: cs_bn_accum_words(C) = 6 C + 1 zero-initialised 8-byte words,
 //   word (2 * limb + which) * C + c   limb 0..2 (units 2^-80, 2^-40, 2^0) of sum `which` (0: first sum, 1: second sum) of channel c
 //   word 6 C                          sticky flag: a contribution was NaN / infinite / >= 2^40 -> every total reads as NaN
-constexpr int kExLimbs = 3;
 __host__ __device__ inline long long ex_words(int C) { return 6LL * C + 1; }
 __device__ __forceinline__ void ex_add(void* acc, int C, int which, int c, double t) {
     double* w = reinterpret_cast<double*>(acc);
@@ -156,12 +152,6 @@ __device__ __forceinline__ double ex_read(const void* acc, int C, int which, int
     return reinterpret_cast<const unsigned long long*>(w)[6LL * C] ? __longlong_as_double(0x7ff8000000000000LL) : v;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // ---- host side error plumbing (cs_api.cpp owns the storage) ----
 extern "C" void cs_set_error_(const char* msg);
 extern "C" void cs_set_variant_(const char* name);
@@ -184,6 +174,26 @@ int cs_wgrad2_launch_(const CsConvGeom* g, int dtype, const void* const* x_tab, 
             return CS_ERR_LAUNCH;                       \
         }                                               \
     } while (0)
+
+// Launch for the element type of `dtype`: launch(CsType<T>{}) with T = float / bf16_t, then the launch check.  Any other code:
+// "<name>: bad dtype", CS_ERR_INVALID_ARG, nothing launched.  The body names the type once:
+//     return cs_launch_typed(dtype, "se_scale", [&](auto tc) {
+//         using T = typename decltype(tc)::type;
+//         hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, st, (const T*)x, s, (T*)y, N, HW, C);
+//     });
+template <typename T> struct CsType { using type = T; };
+template <typename F> static inline int cs_launch_typed(int dtype, const char* name, F launch) {
+    if (dtype == CS_F32) launch(CsType<float>{});
+    else if (dtype == CS_BF16) launch(CsType<bf16_t>{});
+    else {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "%s: bad dtype", name);
+        cs_set_error_(msg);
+        return CS_ERR_INVALID_ARG;
+    }
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
 
 static inline int cs_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 

@@ -7,7 +7,7 @@
 // here: element-per-thread (8 channels = one 16-byte access per thread; fp32 and odd geometries), channel-tiled (round 3, first half:
 // the stride-2 data gradient per 2 x 2 block and one forward launch rule) and STRIPS (round 3, second half: bf16, k in {3, 5}, stride
 // in {1, 2}: forward + statistics, stride-1 data gradient, weight gradient) -- see the comments at each family.
-#include "cs_common.h"
+#include "cs_rows.h"
 
 namespace {
 
@@ -216,114 +216,66 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const T* __restrict__ x, 
     }
 }
 
-// ds[n,c] = sum_p dy[n,p,c] * x[n,p,c]   (workgroup = (64 channel groups x 4 pixel lanes), one image)
-template <typename T>
-__global__ __launch_bounds__(256) void se_ds_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ ds, int HW, int C,
-                                                    int slab) {
-    // grid = (channel-group chunks, N, pixel slabs): partial sums combined with one atomic per channel (ds zeroed by launcher)
-    const int CG = C / 8;
-    const int n = blockIdx.y;
-    const int cg = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int part = threadIdx.x >> 6;
-    const int p0 = blockIdx.z * slab;
-    int p1 = p0 + slab;
-    if (p1 > HW) p1 = HW;
-    __shared__ float red[4][64][8];
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    if (cg < CG) {
-        for (int p = p0 + part; p < p1; p += 4) {
-            float g[8], v[8];
-            const long long o = ((long long)n * HW + p) * C + cg * 8;
-            load8<T>(dy + o, g);
-            load8<T>(x + o, v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += g[e] * v[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[part][threadIdx.x & 63][e] = acc[e];
-    __syncthreads();
-    if (part == 0 && cg < CG) {
-        const int l = threadIdx.x & 63;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) atomicAdd(ds + (long long)n * C + cg * 8 + e, red[0][l][e] + red[1][l][e] + red[2][l][e] + red[3][l][e]);
-    }
-}
-
-// out[n][c] += scale * sum over this workgroup's rows of a (* b): grid = (row blocks of ONE sample, N); a thread keeps one
-// 8-channel group and every rpar-th row (the BN reductions' layout: all 256 lanes busy for any channel count -- the 64-group x 4-lane
-// workgroups of se_ds_kernel / gap_fwd_kernel idle 72 % of their lanes on a 144-channel tensor), two rows in flight; LDS fold, one
-// float atomic per (workgroup, channel) into the zeroed output.
+// scale * sum over this workgroup's rows of a (* b): grid = (row blocks of ONE sample, N, channel chunks of <= cw groups), the placement
+// of cs_rows.h over the sample's HW rows (all 256 lanes busy for any channel count -- the 64-group x 4-lane workgroups of
+// gap_fwd_kernel idle 72 % of their lanes on a 144-channel tensor), two rows in flight; LDS fold, plain stores.
 template <typename T, bool PROD>
 __global__ __launch_bounds__(256) void sample_rowsum_kernel(const T* __restrict__ a, const T* __restrict__ b, float* __restrict__ partial,
                                                             int HW, int C, int rows_per_block, int cw, float* __restrict__ out, float scale) {
     __shared__ float red[256][8];
-    const int CG = C / 8;
     const int n = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block;
-    if (r1 > HW) r1 = HW;
     const T* an = a + (long long)n * HW * C;
     const T* bn = PROD ? b + (long long)n * HW * C : nullptr;
-    {
-        // grid = (row blocks of one sample, N, channel chunks of <= cw groups)
-        const int cg0 = blockIdx.z * cw;
-        const int width = (CG - cg0) < cw ? (CG - cg0) : cw;
-        const int rpar = 256 / width;
-        const int cg = cg0 + (int)(threadIdx.x % width);
-        const int rr = threadIdx.x / width;
-        const bool live = rr < rpar;
-        float acc[8];
+    const RowLane<int> L(blockIdx.x, blockIdx.z, cw, C / 8, rows_per_block, HW);
+    float acc[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        if (live) {
-            int r = r0 + rr;
-            for (; r + rpar < r1; r += 2 * rpar) {
-                float v0[8], v1[8];
-                load8<T>(an + (long long)r * C + cg * 8, v0);
-                load8<T>(an + (long long)(r + rpar) * C + cg * 8, v1);
-                if constexpr (PROD) {
-                    float w0[8], w1[8];
-                    load8<T>(bn + (long long)r * C + cg * 8, w0);
-                    load8<T>(bn + (long long)(r + rpar) * C + cg * 8, w1);
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    if (L.live) {
+        const int cg = L.cg, rpar = L.rpar, r1 = L.r1;
+        int r = L.r0 + L.rr;
+        for (; r + rpar < r1; r += 2 * rpar) {
+            float v0[8], v1[8];
+            load8<T>(an + (long long)r * C + cg * 8, v0);
+            load8<T>(an + (long long)(r + rpar) * C + cg * 8, v1);
+            if constexpr (PROD) {
+                float w0[8], w1[8];
+                load8<T>(bn + (long long)r * C + cg * 8, w0);
+                load8<T>(bn + (long long)(r + rpar) * C + cg * 8, w1);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += v0[e] * w0[e] + v1[e] * w1[e];
-                } else {
+                for (int e = 0; e < 8; ++e) acc[e] += v0[e] * w0[e] + v1[e] * w1[e];
+            } else {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += v0[e] + v1[e];
-                }
-            }
-            if (r < r1) {
-                float v0[8];
-                load8<T>(an + (long long)r * C + cg * 8, v0);
-                if constexpr (PROD) {
-                    float w0[8];
-                    load8<T>(bn + (long long)r * C + cg * 8, w0);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += v0[e] * w0[e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += v0[e];
-                }
+                for (int e = 0; e < 8; ++e) acc[e] += v0[e] + v1[e];
             }
         }
-        __syncthreads();
+        if (r < r1) {
+            float v0[8];
+            load8<T>(an + (long long)r * C + cg * 8, v0);
+            if constexpr (PROD) {
+                float w0[8];
+                load8<T>(bn + (long long)r * C + cg * 8, w0);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = live ? acc[e] : 0.f;
-        __syncthreads();
-        // one partial row per workgroup, plain stores (no atomics: the fold below adds them in a fixed order, so the eval forward of an
-        // EfficientNet -- and with it the adaptive top-k -- repeats bit for bit; a first version with float atomics did not)
-        float* prow = partial + ((long long)n * gridDim.x + blockIdx.x) * C;
-        for (int idx = threadIdx.x; idx < width * 8; idx += 256) {
-            const int cl = idx >> 3, e = idx & 7;
-            float t = 0.f;
-            for (int q = 0; q < rpar; ++q) t += red[q * width + cl][e];
-            // `out`: the launch has ONE row block per sample (small maps) and leaves the scaled sums themselves -- no fold launch
-            if (out) out[(long long)n * C + (cg0 + cl) * 8 + e] = t * scale;
-            else prow[(cg0 + cl) * 8 + e] = t;
+                for (int e = 0; e < 8; ++e) acc[e] += v0[e] * w0[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += v0[e];
+            }
         }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = L.live ? acc[e] : 0.f;
+    __syncthreads();
+    // one partial row per workgroup, plain stores (no atomics: the fold below adds them in a fixed order, so the eval forward of an
+    // EfficientNet -- and with it the adaptive top-k -- repeats bit for bit; a first version with float atomics did not)
+    float* prow = partial + ((long long)n * gridDim.x + blockIdx.x) * C;
+    for (int idx = threadIdx.x; idx < L.width * 8; idx += 256) {
+        const int cl = idx >> 3, e = idx & 7;
+        float t = 0.f;
+        for (int q = 0; q < L.rpar; ++q) t += red[q * L.width + cl][e];
+        // `out`: the launch has ONE row block per sample (small maps) and leaves the scaled sums themselves -- no fold launch
+        if (out) out[(long long)n * C + (L.cg0 + cl) * 8 + e] = t * scale;
+        else prow[(L.cg0 + cl) * 8 + e] = t;
     }
 }
 
@@ -937,10 +889,6 @@ inline int grid_ew(long long total) {
 
 }  // namespace
 
-#define CS_T_SWITCH(dtype, NAME, F32, BF16)                                            \
-    if (dtype == CS_F32) { F32; } else if (dtype == CS_BF16) { BF16; }                 \
-    else { cs_set_error_(NAME ": bad dtype"); return CS_ERR_INVALID_ARG; }
-
 // ---- One launch plan per depthwise call.  dw_plan is the only place that decides which kernel family serves a (geometry, dtype, kind)
 // and with which grid; the launchers below and the workspace queries all read the same DwPlan, so a query cannot disagree with the
 // launch it sizes.  The routing table and the measurement behind each exception: DESIGN.md, "Depthwise routing".
@@ -1078,11 +1026,9 @@ static void dw_note_variant(const DwPlan& p, const CsConvGeom* g, int dtype, DwK
     cs_set_variant_(buf);
 }
 
-// ---- launchers: one per family, each switching (R, stride, TS) and the element type once
+// ---- launchers: one per family, each switching (R, stride, TS) once; the element type through cs_launch_typed, which also rejects
+// any other dtype code and checks the launch
 template <int V> struct DwInt { static constexpr int v = V; };
-template <typename T> struct DwType { using type = T; };
-// f(DwType<T>) for the element type of `dtype` (validated by the caller)
-template <typename F> static void dw_for_type(int dtype, F f) { if (dtype == CS_F32) f(DwType<float>{}); else f(DwType<bf16_t>{}); }
 // f(DwInt<R>, DwInt<ST>) over the instantiated filter sizes and strides
 template <typename F> static void dw_for_rs(int R, int ST, F f) {
     if (R == 3 && ST == 1) f(DwInt<3>{}, DwInt<1>{});
@@ -1108,8 +1054,8 @@ static void launch_dw_strip(const DwPlan& p, const CsConvGeom* g, hipStream_t st
     });
 }
 template <bool STATS, bool FLIP>
-static void launch_dw_tile(const DwPlan& p, const CsConvGeom* g, int dtype, hipStream_t st, const DwOperands& o) {
-    dw_for_type(dtype, [&](auto tc) {
+static int launch_dw_tile(const DwPlan& p, const CsConvGeom* g, int dtype, const char* name, hipStream_t st, const DwOperands& o) {
+    return cs_launch_typed(dtype, name, [&](auto tc) {
         using T = typename decltype(tc)::type;
         dw_for_rs(g->R, g->stride, [&](auto r, auto s) {
             hipLaunchKernelGGL((dw_tile_kernel<T, decltype(r)::v, decltype(s)::v, STATS, FLIP>), p.grid, dim3(256), 0, st, (const T*)o.x, o.w,
@@ -1133,19 +1079,19 @@ static int dw_forward(const CsConvGeom* g, int dtype, const DwOperands& o, int* 
     if (rc) return rc;
     const bool stats = o.partial != nullptr;
     CS_CHECK_ARG(o.x && o.w && o.y && stats == (partial_rows != nullptr), "dwconv_fwd: NULL argument");
-    CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_fwd: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const DwPlan p = dw_plan(g, dtype, DW_FWD);
     dim3 grid = p.grid;
     if (p.family == DW_STRIP) {
         if (stats) launch_dw_strip<true, false>(p, g, st, o); else launch_dw_strip<false, false>(p, g, st, o);
+        CS_LAUNCH_CHECK();
     } else if (p.family == DW_TILE) {
-        if (stats) launch_dw_tile<true, false>(p, g, dtype, st, o); else launch_dw_tile<false, false>(p, g, dtype, st, o);
+        rc = stats ? launch_dw_tile<true, false>(p, g, dtype, "dwconv_fwd", st, o) : launch_dw_tile<false, false>(p, g, dtype, "dwconv_fwd", st, o);
     } else {
         const size_t lds = (size_t)2 * g->C * sizeof(float);
         CS_CHECK_ARG(!stats || lds <= 65536, "dwconv_fwd_stats: too many channels for the LDS fold");
         if (stats) grid = dim3((unsigned)p.rows);
-        dw_for_type(dtype, [&](auto tc) {
+        rc = cs_launch_typed(dtype, "dwconv_fwd", [&](auto tc) {
             using T = typename decltype(tc)::type;
             if (stats)
                 hipLaunchKernelGGL(dw_fwd_stats_kernel<T>, grid, dim3(256), lds, st, (const T*)o.x, o.w, (T*)o.y, o.partial, g->N, g->H, g->W,
@@ -1155,8 +1101,8 @@ static int dw_forward(const CsConvGeom* g, int dtype, const DwOperands& o, int* 
                                    g->W, g->C, g->R, g->stride, g->pad, g->P, g->Q);
         });
     }
+    if (rc) return rc;
     if (stats) *partial_rows = p.rows;
-    CS_LAUNCH_CHECK();
     dw_note_variant(p, g, dtype, DW_FWD, stats, grid);
     return CS_OK;
 }
@@ -1174,14 +1120,16 @@ extern "C" int cs_dwconv_dgrad(const CsConvGeom* g, int dtype, const void* dy, c
     int rc = check_dw(g, "dwconv_dgrad: bad geometry");
     if (rc) return rc;
     CS_CHECK_ARG(dy && w_hwc && dx, "dwconv_dgrad: NULL tensor");
-    CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_dgrad: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const DwPlan p = dw_plan(g, dtype, DW_DGRAD);
     const DwOperands o = {dy, w_hwc, nullptr, nullptr, CS_ACT_NONE, dx, nullptr};
-    if (p.family == DW_STRIP) launch_dw_strip<false, true>(p, g, st, o);
-    else if (p.family == DW_TILE) launch_dw_tile<false, true>(p, g, dtype, st, o);
-    else
-        dw_for_type(dtype, [&](auto tc) {
+    if (p.family == DW_STRIP) {
+        launch_dw_strip<false, true>(p, g, st, o);
+        CS_LAUNCH_CHECK();
+    } else if (p.family == DW_TILE) {
+        rc = launch_dw_tile<false, true>(p, g, dtype, "dwconv_dgrad", st, o);
+    } else {
+        rc = cs_launch_typed(dtype, "dwconv_dgrad", [&](auto tc) {
             using T = typename decltype(tc)::type;
             if (p.family == DW_ELEMENT)
                 hipLaunchKernelGGL(dw_dgrad_kernel<T>, p.grid, dim3(256), 0, st, (const T*)dy, w_hwc, (T*)dx, g->N, g->H, g->W, g->C, g->R,
@@ -1192,7 +1140,8 @@ extern "C" int cs_dwconv_dgrad(const CsConvGeom* g, int dtype, const void* dy, c
                                        g->W, g->C, g->P, g->Q, p.per, p.lanes);
                 });
         });
-    CS_LAUNCH_CHECK();
+    }
+    if (rc) return rc;
     dw_note_variant(p, g, dtype, DW_DGRAD, false, p.grid);
     return CS_OK;
 }
@@ -1215,7 +1164,6 @@ static int dwconv_wgrad_impl(const CsConvGeom* g, int dtype, const void* x, cons
     int rc = check_dw(g, "dwconv_wgrad: bad geometry");
     if (rc) return rc;
     CS_CHECK_ARG(x && dy && dw_hwc && workspace, "dwconv_wgrad: NULL tensor (workspace: cs_dwconv_wgrad_workspace bytes)");
-    CS_CHECK_ARG(dtype == CS_F32 || dtype == CS_BF16, "dwconv_wgrad: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const DwPlan p = dw_plan(g, dtype, DW_WGRAD);
     if (p.family == DW_STRIP) {
@@ -1224,13 +1172,15 @@ static int dwconv_wgrad_impl(const CsConvGeom* g, int dtype, const void* x, cons
             hipLaunchKernelGGL((dw_wgrad_strip_kernel<decltype(r)::v, decltype(s)::v, decltype(t)::v>), p.grid, dim3(256), 0, st, (const bf16_t*)x,
                                (const bf16_t*)dy, workspace, g->N, g->H, g->W, g->C, g->pad, g->P, g->Q, p.per, p.lanes, xb, yb);
         });
-    } else
-        dw_for_type(dtype, [&](auto tc) {
+        CS_LAUNCH_CHECK();
+    } else {
+        rc = cs_launch_typed(dtype, "dwconv_wgrad", [&](auto tc) {
             using T = typename decltype(tc)::type;
             hipLaunchKernelGGL(dw_wgrad_kernel<T>, p.grid, dim3(256), 0, st, (const T*)x, (const T*)dy, workspace, g->N, g->H, g->W, g->C, g->R,
                                g->stride, g->pad, g->P, g->Q, p.per);
         });
-    CS_LAUNCH_CHECK();
+        if (rc) return rc;
+    }
     const int ncols = g->R * g->R * g->C;
     hipLaunchKernelGGL(dw_wgrad_fold_kernel, dim3((unsigned)((ncols + 15) / 16)), dim3(256), 0, st, workspace, p.rows, ncols, dw_hwc, chan);
     CS_LAUNCH_CHECK();
@@ -1269,55 +1219,51 @@ extern "C" int cs_dw_weights_hwc_multi(const CsDwStageDesc* desc_dev, int n, lon
     return CS_OK;
 }
 
-static void sample_rowsum_shape(int N, int HW, int C, int& rpb, int& nblk, int& cw) {
+// rows per workgroup / row blocks per sample (rpb, nblk) and the channel chunks of the per-sample row sums
+static RowSplit sample_rowsum_shape(int N, int HW, int C, int& nblk) {
     const int CG = C / 8;
+    RowSplit s;
     if (HW <= 512) {
         // small maps (EfficientNet stages 4-7 at 299 x 299: 19 x 19 and 10 x 10): ONE workgroup per (sample, chunk of <= 32 channel groups)
         // walks all rows -- no partial rows, no fold launch (7.6-9.8 us for squeeze + fold of 13-18 MB tensors, half of it the second launch)
         const int chunks = (CG + 31) / 32;
-        cw = (CG + chunks - 1) / chunks;
-        rpb = HW;
-        nblk = 1;
-        return;
+        s.cw = (CG + chunks - 1) / chunks;
+        s.rpb = HW;
+    } else {
+        // ~2048 workgroups over the N samples, at least 8 row steps per thread, at most 64 partial rows per sample
+        s.cw = CG < 256 ? CG : 256;
+        const int rpar = 256 / s.cw;
+        int per_sample = 2048 / (N > 0 ? N : 1);
+        if (per_sample < 1) per_sample = 1;
+        if (per_sample > 64) per_sample = 64;
+        s.rpb = (HW + per_sample - 1) / per_sample;
+        if (s.rpb < 8 * rpar) s.rpb = 8 * rpar;
     }
-    // ~2048 workgroups over the N samples, at least 8 row steps per thread, at most 64 partial rows per sample
-    cw = CG < 256 ? CG : 256;
-    const int rpar = 256 / cw;
-    int per_sample = 2048 / (N > 0 ? N : 1);
-    if (per_sample < 1) per_sample = 1;
-    if (per_sample > 64) per_sample = 64;
-    rpb = (HW + per_sample - 1) / per_sample;
-    if (rpb < 8 * rpar) rpb = 8 * rpar;
-    nblk = (HW + rpb - 1) / rpb;
+    s.chunks = (CG + s.cw - 1) / s.cw;
+    nblk = (int)s.row_blocks(HW);
+    return s;
 }
 
 extern "C" size_t cs_sample_sum_workspace(int N, int HW, int C) {
     if (N <= 0 || HW <= 0 || C <= 0 || C % 8) return 0;
-    int rpb, nblk, cw;
-    sample_rowsum_shape(N, HW, C, rpb, nblk, cw);
+    int nblk;
+    sample_rowsum_shape(N, HW, C, nblk);
     return (size_t)N * nblk * C * sizeof(float);
 }
 
 extern "C" int cs_sample_sum(const void* a, const void* b, int dtype, float scale, float* out, float* workspace, int N, int HW, int C, void* stream) {
     CS_CHECK_ARG(a && out && workspace && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "sample_sum: bad arguments (workspace: cs_sample_sum_workspace bytes)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rpb, nblk, cw;
-    sample_rowsum_shape(N, HW, C, rpb, nblk, cw);
-    const int CG = C / 8;
-    dim3 grid((unsigned)nblk, (unsigned)N, (unsigned)((CG + cw - 1) / cw));
+    int nblk;
+    const RowSplit sp = sample_rowsum_shape(N, HW, C, nblk);
+    const dim3 grid((unsigned)nblk, (unsigned)N, (unsigned)sp.chunks);
     float* direct = nblk == 1 ? out : nullptr;
-    if (dtype == CS_F32) {
-        if (b) hipLaunchKernelGGL((sample_rowsum_kernel<float, true>), grid, dim3(256), 0, st, (const float*)a, (const float*)b, workspace, HW, C, rpb, cw, direct, scale);
-        else hipLaunchKernelGGL((sample_rowsum_kernel<float, false>), grid, dim3(256), 0, st, (const float*)a, (const float*)nullptr, workspace, HW, C, rpb, cw, direct, scale);
-    } else if (dtype == CS_BF16) {
-        if (b) hipLaunchKernelGGL((sample_rowsum_kernel<bf16_t, true>), grid, dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, workspace, HW, C, rpb, cw, direct, scale);
-        else hipLaunchKernelGGL((sample_rowsum_kernel<bf16_t, false>), grid, dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)nullptr, workspace, HW, C, rpb, cw, direct, scale);
-    } else {
-        cs_set_error_("sample_sum: bad dtype");
-        return CS_ERR_INVALID_ARG;
-    }
-    CS_LAUNCH_CHECK();
-    if (direct) return CS_OK;
+    const int rc = cs_launch_typed(dtype, "sample_sum", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        if (b) hipLaunchKernelGGL((sample_rowsum_kernel<T, true>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, workspace, HW, C, sp.rpb, sp.cw, direct, scale);
+        else hipLaunchKernelGGL((sample_rowsum_kernel<T, false>), grid, dim3(256), 0, st, (const T*)a, (const T*)nullptr, workspace, HW, C, sp.rpb, sp.cw, direct, scale);
+    });
+    if (rc || direct) return rc;
     const long long total = (long long)N * C;
     hipLaunchKernelGGL(sample_rowsum_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, workspace, scale, out, nblk, C, total);
     CS_LAUNCH_CHECK();
@@ -1328,37 +1274,21 @@ extern "C" int cs_se_scale(const void* x, int dtype, const float* s, void* y, in
     CS_CHECK_ARG(x && s && y && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "se_scale: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew((long long)N * HW * (C / 8));
-    CS_T_SWITCH(dtype, "se_scale",
-                hipLaunchKernelGGL(se_scale_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, s, (float*)y, N, HW, C),
-                hipLaunchKernelGGL(se_scale_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, s, (bf16_t*)y, N, HW, C));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "se_scale", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(se_scale_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, s, (T*)y, N, HW, C);
+    });
 }
 
-extern "C" int cs_se_scale_bwd(const void* dy, const void* x, int dtype, const float* s, const float* davg, float* ds, void* dx, int N,
-                               int HW, int C, int phase, void* stream) {
-    /* phase 0: ds[n,c] = sum_p dy*x ; phase 1: dx = dy*s + davg/HW */
-    CS_CHECK_ARG(dy && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "se_scale_bwd: bad arguments");
+// dx = dy * s + davg / HW (davg nullable); ds = sum_p dy * x is cs_sample_sum(dy, x)
+extern "C" int cs_se_scale_bwd_dx(const void* dy, int dtype, const float* s, const float* davg, void* dx, int N, int HW, int C, void* stream) {
+    CS_CHECK_ARG(dy && s && dx && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "se_scale_bwd_dx: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (phase == 0) {
-        CS_CHECK_ARG(x && ds, "se_scale_bwd: phase 0 needs x and ds");
-        int slabs = (HW + 511) / 512;
-        if (slabs > 64) slabs = 64;
-        const int slab = (HW + slabs - 1) / slabs;
-        if (hipMemsetAsync(ds, 0, sizeof(float) * (size_t)N * C, st) != hipSuccess) { cs_set_error_("se_scale_bwd: memset failed"); return CS_ERR_LAUNCH; }
-        dim3 grid((C / 8 + 63) / 64, N, (HW + slab - 1) / slab);
-        CS_T_SWITCH(dtype, "se_scale_bwd",
-                    hipLaunchKernelGGL(se_ds_kernel<float>, grid, dim3(256), 0, st, (const float*)dy, (const float*)x, ds, HW, C, slab),
-                    hipLaunchKernelGGL(se_ds_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, ds, HW, C, slab));
-    } else {
-        CS_CHECK_ARG(s && dx, "se_scale_bwd: phase 1 needs s and dx");
-        const int grid = grid_ew((long long)N * HW * (C / 8));
-        CS_T_SWITCH(dtype, "se_scale_bwd",
-                    hipLaunchKernelGGL(se_dx_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, s, davg, (float*)dx, N, HW, C),
-                    hipLaunchKernelGGL(se_dx_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, s, davg, (bf16_t*)dx, N, HW, C));
-    }
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    const int grid = grid_ew((long long)N * HW * (C / 8));
+    return cs_launch_typed(dtype, "se_scale_bwd_dx", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(se_dx_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)dy, s, davg, (T*)dx, N, HW, C);
+    });
 }
 
 extern "C" int cs_rowscale_add(const void* a, int dtype, const float* row_scale, const void* b, void* y, int N, long long per_row,
@@ -1367,11 +1297,8 @@ extern "C" int cs_rowscale_add(const void* a, int dtype, const float* row_scale,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total8 = (long long)N * per_row / 8;
     const int grid = grid_ew(total8);
-    CS_T_SWITCH(dtype, "rowscale_add",
-                hipLaunchKernelGGL(rowscale_add_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)a, row_scale, (const float*)b,
-                                   (float*)y, per_row, total8),
-                hipLaunchKernelGGL(rowscale_add_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)a, row_scale, (const bf16_t*)b,
-                                   (bf16_t*)y, per_row, total8));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "rowscale_add", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(rowscale_add_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)a, row_scale, (const T*)b, (T*)y, per_row, total8);
+    });
 }

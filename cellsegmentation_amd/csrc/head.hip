@@ -87,11 +87,6 @@ __device__ __forceinline__ void linear_dx_body(unsigned block, const float* __re
     acc = wave_sum(acc);
     if (lane == 0) dx[wave] = acc;
 }
-__global__ __launch_bounds__(256) void linear_dx_kernel(const float* __restrict__ dy, const float* __restrict__ y,
-                                                        const float* __restrict__ w, float* __restrict__ dx, int M, int N,
-                                                        int K, int act) {
-    linear_dx_body(blockIdx.x, dy, y, w, dx, M, N, K, act);
-}
 
 // dw[n][k] = sum_m g[m][n] x[m][k];  db[n] = sum_m g[m][n] (k == 0 thread)
 __device__ __forceinline__ void linear_dw_body(unsigned block, const float* __restrict__ dy, const float* __restrict__ y,
@@ -109,12 +104,6 @@ __device__ __forceinline__ void linear_dw_body(unsigned block, const float* __re
     }
     dw[idx] = accumulate ? dw[idx] + acc : acc;
     if (db && k == 0) db[n] = accumulate ? db[n] + accb : accb;
-}
-__global__ __launch_bounds__(256) void linear_dw_kernel(const float* __restrict__ dy, const float* __restrict__ y,
-                                                        const float* __restrict__ x, float* __restrict__ dw,
-                                                        float* __restrict__ db, int M, int N, int K, int act,
-                                                        int accumulate) {
-    linear_dw_body(blockIdx.x, dy, y, x, dw, db, M, N, K, act, accumulate);
 }
 
 // ---- Round 3: the three Linear products as 64 x 64 LDS tiles (4 x 4 outputs per thread).  The one-output-per-thread / per-wave

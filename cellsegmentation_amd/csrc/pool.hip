@@ -1,6 +1,7 @@
 // Pooling kernels (HBM-bound, 16-byte vector access, 8 channels per thread):
 //   MaxPool2d(3,2,1)                         model/resnet.py:114
 //   AdaptiveAvgPool2d(1)+AdaptiveMaxPool2d(1) model/resnet.py:122-123,130-131,266,274
+// (the average alone -- the squeeze of squeeze-excitation -- is cs_sample_sum, dwse.hip: all lanes busy at any channel count, fixed-order fold)
 #include "cs_common.h"
 
 namespace {
@@ -197,41 +198,6 @@ __global__ __launch_bounds__(256) void gap_fwd_kernel(const T* __restrict__ x, f
     }
 }
 
-// Average only (the SE squeeze, HW up to 150*150): many workgroups per image, each reduces a slab of pixels and adds its
-// partial mean with one atomic per channel (feat zeroed by the launcher).  grid = (channel-group chunks, N, pixel slabs).
-template <typename T>
-__global__ __launch_bounds__(256) void gap_avg_split_kernel(const T* __restrict__ x, float* __restrict__ feat, int HW, int C, int slab) {
-    const int CG = C / 8;
-    const int n = blockIdx.y;
-    const int cg = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int part = threadIdx.x >> 6;
-    const int p0 = blockIdx.z * slab;
-    int p1 = p0 + slab;
-    if (p1 > HW) p1 = HW;
-    __shared__ float red[4][64][8];
-    float sum[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sum[e] = 0.f;
-    if (cg < CG) {
-        for (int p = p0 + part; p < p1; p += 4) {
-            float v[8];
-            load8<T>(x + ((long long)n * HW + p) * C + cg * 8, v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum[e] += v[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[part][threadIdx.x & 63][e] = sum[e];
-    __syncthreads();
-    if (part == 0 && cg < CG) {
-        const int l = threadIdx.x & 63;
-        const float inv = 1.f / (float)HW;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            atomicAdd(feat + (long long)n * C + cg * 8 + e, (red[0][l][e] + red[1][l][e] + red[2][l][e] + red[3][l][e]) * inv);
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void gap_bwd_kernel(const float* __restrict__ dfeat, const int32_t* __restrict__ amax,
                                                       const T* __restrict__ x, T* __restrict__ dx, int N, int HW, int C,
@@ -282,14 +248,10 @@ extern "C" int cs_maxpool3x3s2_fwd(const void* x, int dtype, void* y, uint8_t* a
     CS_CHECK_ARG(P == (H + 2 - 3) / 2 + 1 && Q == (W + 2 - 3) / 2 + 1, "maxpool_fwd: P/Q do not match H/W");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)N * P * Q * (C / 8);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)x, (float*)y, argmax, N, H, W, C, P, Q);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, argmax, N, H, W, C, P, Q);
-    else
-        CS_CHECK_ARG(false, "maxpool_fwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "maxpool_fwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)x, (T*)y, argmax, N, H, W, C, P, Q);
+    });
 }
 
 extern "C" int cs_maxpool3x3s2_bwd(const void* dy, const uint8_t* argmax, const void* y_mask, int dtype, void* dx, int N,
@@ -299,14 +261,10 @@ extern "C" int cs_maxpool3x3s2_bwd(const void* dy, const uint8_t* argmax, const 
     CS_CHECK_ARG(P == (H + 2 - 3) / 2 + 1 && Q == (W + 2 - 3) / 2 + 1, "maxpool_bwd: P/Q do not match H/W");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(maxpool_bwd_block_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, argmax, (const float*)y_mask, (float*)dx, N, H, W, C, P, Q);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(maxpool_bwd_block_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)dy, argmax, (const bf16_t*)y_mask, (bf16_t*)dx, N, H, W, C, P, Q);
-    else
-        CS_CHECK_ARG(false, "maxpool_bwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "maxpool_bwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(maxpool_bwd_block_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)dy, argmax, (const T*)y_mask, (T*)dx, N, H, W, C, P, Q);
+    });
 }
 
 extern "C" int cs_gap_avgmax_fwd(const void* x, int dtype, float* feat, int32_t* argmax, int N, int HW, int C, int with_max,
@@ -315,29 +273,10 @@ extern "C" int cs_gap_avgmax_fwd(const void* x, int dtype, float* feat, int32_t*
     CS_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C % 8 == 0, "gap_fwd: bad extents");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((C / 8 + 63) / 64, N);
-    if (!with_max && HW >= 1024) {
-        int slabs = (HW + 511) / 512;
-        if (slabs > 64) slabs = 64;
-        const int slab = (HW + slabs - 1) / slabs;
-        if (hipMemsetAsync(feat, 0, sizeof(float) * (size_t)N * C, st) != hipSuccess) { cs_set_error_("gap_fwd: memset failed"); return CS_ERR_LAUNCH; }
-        dim3 g3((C / 8 + 63) / 64, N, (HW + slab - 1) / slab);
-        if (dtype == CS_F32)
-            hipLaunchKernelGGL(gap_avg_split_kernel<float>, g3, dim3(256), 0, st, (const float*)x, feat, HW, C, slab);
-        else if (dtype == CS_BF16)
-            hipLaunchKernelGGL(gap_avg_split_kernel<bf16_t>, g3, dim3(256), 0, st, (const bf16_t*)x, feat, HW, C, slab);
-        else
-            CS_CHECK_ARG(false, "gap_fwd: bad dtype");
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(gap_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, feat, argmax, HW, C, with_max);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(gap_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, feat, argmax, HW, C, with_max);
-    else
-        CS_CHECK_ARG(false, "gap_fwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "gap_fwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(gap_fwd_kernel<T>, grid, dim3(256), 0, st, (const T*)x, feat, argmax, HW, C, with_max);
+    });
 }
 
 extern "C" int cs_gap_avgmax_bwd(const float* dfeat, const int32_t* argmax, const void* x, int dtype, void* dx, int N, int HW,
@@ -347,12 +286,8 @@ extern "C" int cs_gap_avgmax_bwd(const float* dfeat, const int32_t* argmax, cons
     CS_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C % 8 == 0, "gap_bwd: bad extents");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)N * HW * (C / 8);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(gap_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, dfeat, argmax, (const float*)x, (float*)dx, N, HW, C, relu_mask, with_max);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(gap_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, dfeat, argmax, (const bf16_t*)x, (bf16_t*)dx, N, HW, C, relu_mask, with_max);
-    else
-        CS_CHECK_ARG(false, "gap_bwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "gap_bwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(gap_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, dfeat, argmax, (const T*)x, (T*)dx, N, HW, C, relu_mask, with_max);
+    });
 }

@@ -387,14 +387,10 @@ extern "C" int cs_nchw_to_nhwc(const float* x, void* y, int dtype, int N, int C,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int groups = Cp / 8 > 0 ? Cp / 8 : 1;
     const long long total = (long long)N * H * W * groups;
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, (float*)y, N, C, H * W, Cp);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, (bf16_t*)y, N, C, H * W, Cp);
-    else
-        CS_CHECK_ARG(false, "nchw_to_nhwc: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "nchw_to_nhwc", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, (T*)y, N, C, H * W, Cp);
+    });
 }
 
 extern "C" int cs_nhwc_to_nchw(const void* y, int dtype, float* x, int N, int C, int H, int W, int Cp, void* stream) {
@@ -402,14 +398,10 @@ extern "C" int cs_nhwc_to_nchw(const void* y, int dtype, float* x, int N, int C,
     CS_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && Cp >= C, "nhwc_to_nchw: bad extents");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)N * H * W * ((C + 7) / 8);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)y, x, N, C, H * W, Cp);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16_t*)y, x, N, C, H * W, Cp);
-    else
-        CS_CHECK_ARG(false, "nhwc_to_nchw: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "nhwc_to_nchw", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const T*)y, x, N, C, H * W, Cp);
+    });
 }
 
 extern "C" int cs_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps,
@@ -638,11 +630,10 @@ extern "C" int cs_colsum_partial(const void* g, int dtype, long long M, int C, f
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int rows = colsum_rows_per_block(M);
     const int blocks = (int)((M + rows - 1) / rows);
-    if (dtype == CS_F32) hipLaunchKernelGGL((colsum_kernel<float, true>), dim3(blocks), dim3(256), 0, st, (const float*)g, M, C, partial, rows);
-    else if (dtype == CS_BF16) hipLaunchKernelGGL((colsum_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)g, M, C, partial, rows);
-    else CS_CHECK_ARG(false, "colsum_partial: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "colsum_partial", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL((colsum_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)g, M, C, partial, rows);
+    });
 }
 
 extern "C" int cs_colsum(const void* g, int dtype, long long M, int C, float* out, void* stream) {
@@ -654,14 +645,10 @@ extern "C" int cs_colsum(const void* g, int dtype, long long M, int C, float* ou
     long long rows = (M + 511) / 512;
     if (rows < 64) rows = 64;
     const int blocks = (int)((M + rows - 1) / rows);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL((colsum_kernel<float, false>), dim3(blocks), dim3(256), 0, st, (const float*)g, M, C, out, (int)rows);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL((colsum_kernel<bf16_t, false>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)g, M, C, out, (int)rows);
-    else
-        CS_CHECK_ARG(false, "colsum: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "colsum", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL((colsum_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)g, M, C, out, (int)rows);
+    });
 }
 
 extern "C" int cs_weight_prep_grouped(const float* w, const float* scale, int dtype, int K, int Cg, int R, int S, void* w_khwc,
@@ -670,16 +657,11 @@ extern "C" int cs_weight_prep_grouped(const float* w, const float* scale, int dt
     CS_CHECK_ARG(K > 0 && K % 64 == 0 && Cg > 0 && 64 % Cg == 0 && R > 0 && S > 0, "weight_prep_grouped: need K % 64 == 0 and Cg | 64");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)K * R * S * 64;
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(weight_prep_grouped_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, scale, K, Cg, R, S,
-                           (float*)w_khwc, (float*)w_chwk);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(weight_prep_grouped_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, scale, K, Cg, R, S,
-                           (bf16_t*)w_khwc, (bf16_t*)w_chwk);
-    else
-        CS_CHECK_ARG(false, "weight_prep_grouped: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "weight_prep_grouped", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(weight_prep_grouped_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, st, w, scale, K, Cg, R, S,
+                           (T*)w_khwc, (T*)w_chwk);
+    });
 }
 
 extern "C" int cs_wgrad_finalize_grouped(const float* dw_slab, int nsplit, const float* w, const float* scale, const float* rstd,
@@ -712,11 +694,10 @@ extern "C" int cs_stage_conv_bn_one(const CsStageDesc* host_desc, int dtype, voi
     CS_CHECK_ARG(!(d.fwd_packed && d.w_khwc) || (d.Kp % 32 == 0 && d.Cp % 64 == 0), "stage_conv_bn_one: packed forward operand needs Kp % 32 == 0 and Cp % 64 == 0");
     CS_CHECK_ARG(!(d.bwd_packed && d.w_chwk) || (d.Cp % 32 == 0 && d.Kp % 64 == 0), "stage_conv_bn_one: packed data-gradient operand needs Cp % 32 == 0 and Kp % 64 == 0");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == CS_F32) hipLaunchKernelGGL(stage_conv_bn_one_kernel<float>, dim3(nb), dim3(256), 0, st, d);
-    else if (dtype == CS_BF16) hipLaunchKernelGGL(stage_conv_bn_one_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, d);
-    else CS_CHECK_ARG(false, "stage_conv_bn_one: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "stage_conv_bn_one", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(stage_conv_bn_one_kernel<T>, dim3(nb), dim3(256), 0, st, d);
+    });
 }
 
 // (cs_stage_conv_bn_one with gamma = scale, nothing else folded and no vectors out: w * (scale * 1.f) is w * scale exactly)
@@ -731,11 +712,10 @@ extern "C" int cs_weight_prep(const float* w, const float* scale, int dtype, int
 extern "C" int cs_stage_conv_bn_multi(const CsStageDesc* desc, int n, int total_blocks, int dtype, void* stream) {
     CS_CHECK_ARG(desc && n >= 1 && total_blocks >= n, "stage_conv_bn_multi: need a device descriptor table and >= 1 workgroup per layer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == CS_F32) hipLaunchKernelGGL(stage_conv_bn_multi_kernel<float>, dim3(total_blocks), dim3(256), 0, st, desc, n);
-    else if (dtype == CS_BF16) hipLaunchKernelGGL(stage_conv_bn_multi_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, st, desc, n);
-    else CS_CHECK_ARG(false, "stage_conv_bn_multi: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "stage_conv_bn_multi", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(stage_conv_bn_multi_kernel<T>, dim3(total_blocks), dim3(256), 0, st, desc, n);
+    });
 }
 
 extern "C" int cs_wgrad_finalize_batched(const float* const* tables /* HOST: 9 consecutive tables of n pointers */, const int* gsum_rows,

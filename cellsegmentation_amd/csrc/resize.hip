@@ -137,14 +137,10 @@ extern "C" int cs_bilinear_ac_fwd(const void* x, int dtype, void* y, int N, int 
     CS_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && C > 0 && C % 8 == 0, "bilinear_fwd: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew((long long)N * P * Q * (C / 8));
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(bilinear_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, P, Q);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(bilinear_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, H, W, C, P, Q);
-    else
-        CS_CHECK_ARG(false, "bilinear_fwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "bilinear_fwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(bilinear_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, P, Q);
+    });
 }
 
 extern "C" int cs_bilinear_ac_bwd(const void* dy, const void* mask, int dtype, void* dx, int N, int H, int W, int C, int P, int Q,
@@ -152,42 +148,30 @@ extern "C" int cs_bilinear_ac_bwd(const void* dy, const void* mask, int dtype, v
     CS_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && C > 0 && C % 8 == 0, "bilinear_bwd: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew((long long)N * H * W * (C / 8));
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(bilinear_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, (const float*)mask, (float*)dx, N, H, W, C, P, Q);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(bilinear_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)mask, (bf16_t*)dx, N, H, W, C, P, Q);
-    else
-        CS_CHECK_ARG(false, "bilinear_bwd: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "bilinear_bwd", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(bilinear_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)dy, (const T*)mask, (T*)dx, N, H, W, C, P, Q);
+    });
 }
 
 extern "C" int cs_concat_channels(const void* a, const void* b, int dtype, void* out, long long M, int Ca, int Cb, void* stream) {
     CS_CHECK_ARG(a && b && out && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0, "concat: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew(M * ((Ca + Cb) / 8));
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(concat_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)a, (float*)b, (float*)out, M, Ca, Cb, 0);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(concat_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (bf16_t*)a, (bf16_t*)b, (bf16_t*)out, M, Ca, Cb, 0);
-    else
-        CS_CHECK_ARG(false, "concat: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "concat", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(concat_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)a, (T*)b, (T*)out, M, Ca, Cb, 0);
+    });
 }
 
 extern "C" int cs_split_channels(const void* whole, int dtype, void* a, void* b, long long M, int Ca, int Cb, void* stream) {
     CS_CHECK_ARG(whole && (a || b) && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0, "split: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew(M * ((Ca + Cb) / 8));
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(concat_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)a, (float*)b, (float*)whole, M, Ca, Cb, 1);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(concat_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (bf16_t*)a, (bf16_t*)b, (bf16_t*)whole, M, Ca, Cb, 1);
-    else
-        CS_CHECK_ARG(false, "split: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "split", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(concat_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)a, (T*)b, (T*)whole, M, Ca, Cb, 1);
+    });
 }
 
 // =============================================================================================
@@ -230,14 +214,9 @@ extern "C" int cs_tile_gather(const uint8_t* images, int n_images, int H, int W,
     CS_CHECK_ARG(n_images > 0 && H > 0 && W > 0 && n_tiles > 0 && size > 0 && size <= H && size <= W, "tile_gather: bad extents");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = grid_ew(n_tiles * size * size);
-    if (dtype == CS_F32)
-        hipLaunchKernelGGL(tile_gather_kernel<float>, dim3(grid), dim3(256), 0, st, images, tile_img, tile_rc, n_tiles, H, W, size,
-                           host_mean3[0], host_mean3[1], host_mean3[2], host_std3[0], host_std3[1], host_std3[2], (float*)out);
-    else if (dtype == CS_BF16)
-        hipLaunchKernelGGL(tile_gather_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, images, tile_img, tile_rc, n_tiles, H, W, size,
-                           host_mean3[0], host_mean3[1], host_mean3[2], host_std3[0], host_std3[1], host_std3[2], (bf16_t*)out);
-    else
-        CS_CHECK_ARG(false, "tile_gather: bad dtype");
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return cs_launch_typed(dtype, "tile_gather", [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        hipLaunchKernelGGL(tile_gather_kernel<T>, dim3(grid), dim3(256), 0, st, images, tile_img, tile_rc, n_tiles, H, W, size,
+                           host_mean3[0], host_mean3[1], host_mean3[2], host_std3[0], host_std3[1], host_std3[2], (T*)out);
+    });
 }

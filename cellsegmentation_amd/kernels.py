@@ -856,8 +856,7 @@ def se_scale_bwd_ds(dy, x):
 def se_scale_bwd_dx(dy, s, davg):
     N, H, W, C = dy.shape
     dx = torch.empty_like(dy)
-    _lib.check(_lib.load().cs_se_scale_bwd(_p(dy), None, _code(dy.dtype), _p(s), _p(davg), None, _p(dx), N, H * W, C, 1, _stream()),
-               "se_scale_bwd(dx)")
+    _lib.check(_lib.load().cs_se_scale_bwd_dx(_p(dy), _code(dy.dtype), _p(s), _p(davg), _p(dx), N, H * W, C, _stream()), "se_scale_bwd_dx")
     return dx
 
 

@@ -353,9 +353,8 @@ typedef struct { const float* src; float* dst; long long C; long long RS; long l
 int cs_dw_weights_hwc_multi(const CsDwStageDesc* desc_dev, int n, long long total, void* stream);
 /* y[n][p][c] = x[n][p][c]*s[n][c] */
 int cs_se_scale(const void* x, int dtype, const float* s, void* y, int N, int HW, int C, void* stream);
-/* phase 0: ds[n][c] = sum_p dy*x ; phase 1: dx = dy*s + davg[n][c]/HW (davg nullable) */
-int cs_se_scale_bwd(const void* dy, const void* x, int dtype, const float* s, const float* davg, float* ds, void* dx, int N,
-                    int HW, int C, int phase, void* stream);
+/* dx = dy*s + davg[n][c]/HW (davg nullable); the other half, ds[n][c] = sum_p dy*x, is cs_sample_sum(dy, x) */
+int cs_se_scale_bwd_dx(const void* dy, int dtype, const float* s, const float* davg, void* dx, int N, int HW, int C, void* stream);
 /* y = a*row_scale[n] + b over N rows of per_row elements (row_scale, b nullable) */
 int cs_rowscale_add(const void* a, int dtype, const float* row_scale, const void* b, void* y, int N, long long per_row,
                     void* stream);

@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/cellseg_hip.h declares; host-side
 logic of the model mirror (setmode groups, error behaviour, state_dict names, selection plan)."""
+import ctypes
 import os
 import re
 
@@ -67,6 +68,14 @@ def test_argument_checks_without_gpu():
     assert rc == -1 and b"chunk" in lib.cs_last_error()
     assert lib.cs_igemm_tile(64 * 75 * 75, 64) == 128064
     assert lib.cs_segmented_topk_workspace(1000) >= 8000
+    # a dtype code other than CS_F32 / CS_BF16 is refused by every depthwise entry point before anything is launched
+    buf = ctypes.create_string_buffer(64)
+    ptr = ctypes.c_void_p(ctypes.addressof(buf))
+    dg = _lib.CsConvGeom(1, 8, 8, 8, 8, 3, 3, 1, 1, 8, 8)
+    for code in (2, -1):
+        assert lib.cs_dwconv_fwd(dg, code, ptr, ptr, None, None, 0, ptr, None) == -1 and lib.cs_last_error() == b"dwconv_fwd: bad dtype"
+        assert lib.cs_dwconv_dgrad(dg, code, ptr, ptr, ptr, None) == -1 and lib.cs_last_error() == b"dwconv_dgrad: bad dtype"
+        assert lib.cs_dwconv_wgrad(dg, code, ptr, ptr, ptr, ptr, None) == -1 and lib.cs_last_error() == b"dwconv_wgrad: bad dtype"
 
 
 def test_setmode_groups_match_reference():

@@ -239,7 +239,7 @@ def test_depthwise_tiled_kernels_everywhere_the_geometry_allows(dev):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cfg", [(3, 19, 19, 144), (2, 10, 10, 2304), (4, 75, 38, 40), (2, 8, 8, 24), (1, 30, 31, 2136)])
 def test_per_sample_reductions_of_the_se_block(cfg, dtype, dev):
-    """cs_sample_rowsum_ behind cs_gap_avgmax_fwd(with_max = 0) and cs_se_scale_bwd(phase 0): average pool and ds = sum_p dy * x per
+    """cs_sample_sum behind kernels.gap_fwd(with_max=False) and kernels.se_scale_bwd_ds: average pool and ds = sum_p dy * x per
     (sample, channel), for channel-group counts below / above one workgroup row (18, 288 > 256, 5, 3, 267)."""
     N, H, W, C = cfg
     torch.manual_seed(C + H)

@@ -55,8 +55,8 @@ def test_restatement_wrappers():
     assert R.label(s)[1] == 1 and int(s.sum()) == 5 * 6 + 4 and R.label(~s, 2)[1] == 4
 
 
-def test_abi_version_is_9():
-    assert _lib.load().cs_abi_version() == 9
+def test_abi_version_is_10():
+    assert _lib.load().cs_abi_version() == 10
 
 
 def test_argument_errors_come_before_device_work():

@@ -147,7 +147,7 @@ def test_new_symbols_are_declared_and_bound():
         assert name in _lib._SIGNATURES and name in _lib.exported_symbols()
     assert len(_lib._SIGNATURES["cs_score_points"][1]) == 13 and _lib._SIGNATURES["cs_score_workspace"][0] is _lib.c_size_t
     lib = _lib.load()
-    assert lib.cs_abi_version() == 9                                      # pure additions
+    assert lib.cs_abi_version() == 10
     assert lib.cs_score_workspace(0, 10) == 0 and lib.cs_score_workspace(65536, 10) == 0 and lib.cs_score_workspace(1, -1) == 0
     assert lib.cs_score_workspace(1, 0) == 16 and lib.cs_score_workspace(300, 1 << 20) >= ((1 << 20) // 32 + 300) * 4
     # refused before any launch (no GPU needed): N, a NULL offset table, a negative radius2, unknown flag bits
