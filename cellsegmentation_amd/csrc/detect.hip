@@ -8,6 +8,8 @@
 //   cluster   DBSCAN(eps, min_samples=1): connected components of dr^2 + dc^2 <= eps^2; root = lowest point index
 //   centroids rint(sum / n) of exact integer sums; weight = blurred[centroid]; order: weight desc, label desc
 //   stitch    patches written into a zeroed whole-image mask, the highest patch index winning where patches overlap
+//   streamed  the same mask built batch by batch: softmax channel + quantise of a batch of logits written in place in one launch,
+//             the owner of a pixel decided from the batch's corners (no per-pixel state); earlier batches are overwritten in stream order
 //   edt       method="distancetransform" in place of the blur: foreground = u8 > thr_for_dt; exact squared Euclidean distance to the
 //             nearest background pixel (int32; -1 everywhere in a map without background): column sweep, then per row the lower
 //             envelope of (x - x')^2 + g[x']^2 by an outward search that stops at dx^2 >= best; per-map maximum M by integer
@@ -15,6 +17,7 @@
 // Every step is integer arithmetic or one correctly rounded fp64 operation, so the result does not depend on launch order.
 #include "cs_common.h"
 #include "cs_block.h"
+#include "cs_softmax.h"
 
 namespace {
 
@@ -156,6 +159,58 @@ __global__ __launch_bounds__(256) void stitch_gather_kernel(const uint8_t* __res
             v = patches[((long long)m * ph + (r - corners[2 * m])) * pw + (c - corners[2 * m + 1])];
         }
         out[i] = v;
+    }
+}
+
+// ---- streamed stitching: a batch of segment logits written straight into the whole-image mask ---------------------------------
+// bits [lo, hi) of a four-pixel unit (either end may lie outside 0..4)
+__device__ __forceinline__ uint32_t unit_bits(int lo, int hi) {
+    lo = min(max(lo, 0), 4);
+    hi = min(max(hi, 0), 4);
+    return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+
+// mask[R][Cc] = quant(softmax over the channels of logits[b], channel ch) for every pixel of every patch b that no later patch of the
+// batch covers.  Ownership comes from the corners alone: a workgroup-uniform walk over the later corners skips the rectangles that
+// lie apart from patch b, the others cost a row test and a column interval per lane.  So a mask byte is written at most once per
+// launch, without atomics and whatever order the workgroups run in; bytes that no patch covers are not touched.
+// A workgroup takes 256 units of one patch at a time.  A unit is the four mask bytes of one aligned dword of a patch row (ng units
+// span a row at any alignment): a wholly owned unit is one dword store, a patch edge or a partly covered unit is byte stores.
+__global__ __launch_bounds__(256) void stitch_logits_kernel(const float* __restrict__ logits, const int32_t* __restrict__ corners, int B, int C,
+                                                            int ch, int ph, int pw, int H, int W, int ng, int chunks,
+                                                            uint8_t* __restrict__ mask) {
+    const long long items = (long long)B * chunks, plane = (long long)ph * pw;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        const int b = (int)(item / chunks);
+        const int u = (int)(item - (long long)b * chunks) * 256 + threadIdx.x;
+        const long long r0 = corners[2 * b], c0 = corners[2 * b + 1];
+        if (r0 >= H || r0 + ph <= 0 || c0 >= W || c0 + pw <= 0) continue;          // workgroup-uniform: the patch misses the mask
+        const int r = u / ng, g = u - r * ng;
+        const int R = (int)r0 + r;
+        if (r >= ph || R < 0 || R >= H) continue;
+        const long long row = (long long)R * W;
+        const int lead = (int)((reinterpret_cast<uintptr_t>(mask) + row + c0) & 3);   // bytes between the dword boundary and the patch row
+        const int p0 = 4 * g - lead, C0 = (int)c0 + p0;                              // the unit's first column in the patch / in the mask
+        uint32_t want = unit_bits(max(-p0, -C0), min(pw - p0, W - C0));              // inside the patch and inside the mask
+        if (!want) continue;
+        for (int m = b + 1; m < B; ++m) {
+            const long long mr = corners[2 * m], mc = corners[2 * m + 1];
+            if (mr >= r0 + ph || mr + ph <= r0 || mc >= c0 + pw || mc + pw <= c0) continue;      // workgroup-uniform: rectangles apart
+            if ((unsigned)(R - (int)mr) < (unsigned)ph) want &= ~unit_bits((int)mc - C0, (int)mc + pw - C0);
+        }
+        if (!want) continue;
+        const long long src = ((long long)b * C * ph + r) * pw + p0;                 // channel 0 of the unit's first pixel
+        const long long dst = row + C0;                                               // 64-bit: a slide mask may exceed 2^31 pixels
+        if (want == 0xfu) {
+            uint32_t o = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o |= (uint32_t)quant(softmax_channel_at(logits + (src + j), plane, C, ch)) << (8 * j);
+            *reinterpret_cast<uint32_t*>(mask + dst) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((want >> j) & 1u) mask[dst + j] = quant(softmax_channel_at(logits + (src + j), plane, C, ch));
+        }
     }
 }
 
@@ -682,6 +737,25 @@ extern "C" int cs_stitch_patches(const uint8_t* patches, int M, int ph, int pw, 
         CS_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(stitch_gather_kernel, dim3(grid_for(HW)), dim3(256), 0, st, patches, corners, ph, pw, H, W, owner, out);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_stitch_logits(const float* logits, int B, int C, int ph, int pw, int ch, const int32_t* corners, int H, int W,
+                                uint8_t* mask, void* stream) {
+    CS_CHECK_ARG(mask && H > 0 && W > 0 && B >= 0 && ph > 0 && pw > 0, "stitch_logits: bad arguments");
+    CS_CHECK_ARG(C >= 2 && ch >= 0 && ch < C, "stitch_logits: needs at least two channels and 0 <= ch < C");
+    CS_CHECK_ARG(B == 0 || (logits && corners), "stitch_logits: NULL logits or corners");
+    CS_CHECK_ARG(H < (1 << 29) && W < (1 << 29) && ph <= H && pw <= W, "stitch_logits: the patch must fit the mask, whose sides stay below 2^29");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3) == 0 && (reinterpret_cast<uintptr_t>(corners) & 3) == 0,
+                 "stitch_logits: misaligned buffers");
+    if (B == 0) return CS_OK;
+    const int ng = pw / 4 + 2;                                   // dword units that span a patch row at any alignment
+    const long long units = (long long)ph * ng;
+    CS_CHECK_ARG(units < (1LL << 30), "stitch_logits: patch too large");
+    const int chunks = cs_ceil_div(units, 256);
+    hipLaunchKernelGGL(stitch_logits_kernel, dim3(grid_for((long long)B * chunks * 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       logits, corners, B, C, ch, ph, pw, H, W, ng, chunks, mask);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

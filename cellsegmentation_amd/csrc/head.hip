@@ -3,6 +3,7 @@
 // (train/losses.py:5-29, metrics/metrics.py:23-33), Dice (train/losses.py:44-62,
 // metrics/metrics.py:36-53).
 #include "cs_common.h"
+#include "cs_softmax.h"
 
 namespace {
 
@@ -503,12 +504,7 @@ __global__ __launch_bounds__(256) void softmax_ch_fwd_kernel(const float* __rest
                                                              long long HW, long long total) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long n = idx / HW, i = idx - n * HW;
-        const float* r = logits + n * C * HW + i;
-        float mx = r[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c * HW]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(r[c * HW] - mx);
-        pc[idx] = expf(r[ch * HW] - mx) / se;
+        pc[idx] = softmax_channel_at(logits + n * C * HW + i, HW, C, ch);
     }
 }
 

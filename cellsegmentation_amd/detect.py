@@ -27,6 +27,10 @@ Steps, each integer arithmetic or one correctly rounded fp64 operation, so the r
              half to even, decided by the integer comparison ``4 255^2 D2 <> (2k + 1)^2 M``.  cv2 computes the distance in float32
              and normalises in floating point; agreement with cv2's own rounding is NOT pinned (cv2 is not a dependency).
 
+Whole slides: ``stitch_patches`` builds the whole-image mask from patches that are all resident; ``stitch_logits`` builds the same
+bytes batch by batch, straight from the segment logits (softmax channel, quantise and the overlap rule in one launch per batch, the
+owner of a pixel decided from the batch's corners, no per-pixel state).  ``inference.detect_slide`` is the loop around it.
+
 ``meanshift_cluster`` itself still refuses ``"distancetransform"``; ``detect_points(mask, cell_counts=c,
 method="distancetransform").per_image()[0]`` returns the pair it would.
 """
@@ -180,6 +184,53 @@ def stitch_patches(patches, images_grid, image_hw):
         raise ValueError("a patch does not lie inside the image")
     corners = torch.from_numpy(grid.astype(np.int32)).to(p.device)
     return K.stitch_patches(p, corners, H, W)
+
+
+def _check_stitch_logits(mask, logits, corners, ch):
+    """Argument checks of stitch_logits, all on the host -> int64 numpy corners [B, 2].  The device check comes last, so that every
+    other error is the same with host tensors."""
+    if not torch.is_tensor(logits) or not torch.is_tensor(mask):
+        raise TypeError("stitch_logits: expected torch tensors (the mask is written in place on the device)")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"stitch_logits: expected float32 logits, got {logits.dtype}")
+    if logits.dim() != 4:
+        raise ValueError(f"stitch_logits expects logits shaped [B, C, ph, pw], got shape {tuple(logits.shape)}")
+    if mask.dtype != torch.uint8:
+        raise TypeError(f"stitch_logits: expected a uint8 mask, got {mask.dtype}")
+    if mask.dim() != 2:
+        raise ValueError(f"stitch_logits expects a mask shaped [H, W], got shape {tuple(mask.shape)}")
+    B, C, ph, pw = logits.shape
+    H, W = mask.shape
+    if C < 2:
+        raise ValueError(f"stitch_logits: the softmax needs at least two channels, got {C}")
+    if int(ch) != ch or not 0 <= ch < C:
+        raise ValueError(f"stitch_logits: channel {ch!r} is not one of the {C} channels")
+    grid = np.asarray(corners.cpu() if torch.is_tensor(corners) else corners, dtype=np.int64).reshape(-1, 2)
+    if len(grid) != B:
+        raise ValueError(f"{B} patches but {len(grid)} corners")
+    if B and (grid.min() < 0 or (grid[:, 0] + ph).max() > H or (grid[:, 1] + pw).max() > W):
+        raise ValueError("a patch does not lie inside the image")
+    if not mask.is_cuda or not mask.is_contiguous():
+        raise ValueError("stitch_logits writes the mask in place: it must be a contiguous device tensor")
+    if logits.device != mask.device:
+        raise ValueError(f"stitch_logits: logits on {logits.device}, mask on {mask.device}")
+    return grid
+
+
+def stitch_logits(mask, logits, corners, ch=1):
+    """Write ``quantize(softmax_channel_fwd(logits, ch))`` of a batch of segment logits fp32 [B, C, ph, pw] into the whole-image mask
+    uint8 [H, W] (device) at upper-left corners [B, 2] (row, col), in place, in one launch -- ``cell_detect``'s
+    ``whole_image_mask[...] = mask`` per patch (test_seg.py:255-257), a batch at a time.
+
+    The mask is not cleared: pixels that no patch of the batch covers keep their value.  Inside the call a pixel covered by several
+    patches is written once, by the one with the highest index (decided from the corners alone: no owner map, no atomics, the same
+    bytes whatever order the workgroups run in); two patches may share a corner.  Across calls the stream orders the writes, so ALL
+    CALLS FOR ONE MASK MUST BE ISSUED ON THE SAME STREAM.  Batch after batch in index order on a zeroed mask gives exactly
+    ``stitch_patches(quantize(softmax_channel_fwd(all_logits, ch)), all_corners, (H, W))``, bit for bit, for any split into batches,
+    with the mask and one batch resident instead of every patch and a 4 H W byte owner map.  Every workgroup walks the corners
+    that follow its patch, so keep a batch at tens of patches (DESIGN.md has the figures).  Returns the mask."""
+    grid = _check_stitch_logits(mask, logits, corners, ch)
+    return K.stitch_logits(mask, logits.contiguous(), torch.from_numpy(grid.astype(np.int32)).to(mask.device), int(ch))
 
 
 @dataclass

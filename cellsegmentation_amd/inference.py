@@ -7,6 +7,8 @@
   ``trainset.tileIDX`` / ``trainset.labels``; sorting + selection run in the segmented top-k HIP
   kernel, bit-exact with ``np.lexsort`` + the reference's wrap-around predicate.
 """
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
@@ -171,6 +173,84 @@ def detect_cells(loader, model, device, eps=11, reg_limit=False, method="gaussia
                             opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
             out.extend(res.per_image())
     return out
+
+
+@dataclass
+class SlideResult:
+    """One slide of ``detect_slide``: ``points`` / ``discarded`` int64 [n, 2] (row, col) as ``meanshift_cluster`` returns them
+    (``discarded`` is ``[]`` without a cap), ``cell_count`` the summed per-patch counts, ``mask`` the stitched uint8 [H, W] device
+    tensor."""
+    points: np.ndarray
+    discarded: object
+    cell_count: int
+    mask: torch.Tensor
+
+
+def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, interval=None, eps=11, reg_limit=True,
+                 method="gaussianblur", thr_for_dt=10, **blur):
+    """The loop of ``cell_detect`` (test_seg.py:182-316) for one slide or ROI, streamed on the device -> SlideResult.
+
+    image_u8: uint8 [H, W, 3], numpy or torch; it is moved to the device once.  ``tiles.sample_patches`` gives the (row, col) patch
+    corners (the reference's ROI mode indexes ``image[x:x+ph, y:y+pw]``); per batch of ``batch_size`` corners ``tiles.gather_tiles``
+    stages the patches, the segment-mode forward's logits go through ``detect.stitch_logits`` into one zeroed uint8 [H, W] mask
+    (later patches overwrite earlier ones, as ``whole_image_mask[...] = mask`` does), and ``rint(reg)`` of the image-mode forward of
+    the same staged batch is added to a device accumulator.  Nothing inside the loop synchronises with the host.  The stitched mask
+    then goes through ``detect._detect`` with the summed count as the cap (reg_limit=True, as ``cell_detect`` always caps, :240,265;
+    False returns every point).  ``method``, ``thr_for_dt`` and the keyword arguments thr, window_size, ksize, sigmaX, sigmaY, max_iter are
+    those of ``detect_cells``; ``interval`` is the patch grid's here, so the seed grid keeps ``meanshift_cluster``'s default of 10, as
+    in ``cell_detect``.  ``patch_size`` must be square here (gather_tiles cuts square tiles; ``sample_patches`` itself is general).  The model is left in segment mode and ``eval()``.
+
+    Not done here: reading ``.svs`` / ``.png`` files (OpenSlide is not a dependency), writing the CSV and PNG files, and the
+    ``name-<xoffset>`` file-name convention -- the caller adds the offset to ``points[:, 1]``.  ``meanshift_cluster(...,
+    "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
+    from . import detect as D
+    from . import tiles as T
+    D._check_method(method)
+    unknown = set(blur) - {"thr", "window_size", "ksize", "sigmaX", "sigmaY", "max_iter"}
+    if unknown:
+        raise TypeError(f"detect_slide: unexpected arguments {sorted(unknown)}")
+    opts = {"ksize": (15, 15), "sigmaX": 3.}
+    opts.update(blur)
+    if method == "gaussianblur":
+        D._blur_taps(opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.))
+    ph, pw = T._pair(patch_size, "patch_size")
+    if ph != pw:
+        raise ValueError(f"detect_slide cuts square patches (tiles.gather_tiles), got patch_size {(ph, pw)}")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size!r}")
+    img = torch.from_numpy(np.ascontiguousarray(image_u8)) if isinstance(image_u8, np.ndarray) else image_u8
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
+        raise TypeError("detect_slide expects a uint8 image shaped [H, W, 3] (numpy or torch)")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    corners = np.asarray(T.sample_patches((H, W), (ph, pw), interval), dtype=np.int32).reshape(-1, 2)
+    if device is None:
+        device = img.device if img.is_cuda else D._device()
+    img = img.to(device).contiguous()[None]
+    rc = torch.from_numpy(corners).to(device)                              # every corner of the slide, uploaded once
+    ti = torch.zeros((len(corners),), dtype=torch.int32, device=device)
+    mask = torch.zeros((H, W), dtype=torch.uint8, device=device)
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    dtype = getattr(model, "compute_dtype", torch.float32)
+    model.eval()
+    with torch.no_grad():
+        for i in range(0, len(corners), int(batch_size)):
+            x = T.gather_tiles(img, ti[i:i + batch_size], rc[i:i + batch_size], ph, dtype)
+            model.setmode("segment")
+            K.stitch_logits(mask, model(x).float().contiguous(), rc[i:i + batch_size], 1)
+            model.setmode("image")
+            total += torch.round(model(x)[1].detach()[:, 0].float()).sum(dtype=torch.float64)
+    model.setmode("segment")
+    count = int(total.item())                                              # the first synchronisation of the slide
+    res = D._detect(mask[None], count if reg_limit else None, opts.get("thr", 0.2), opts.get("window_size", 16), 10, eps,
+                    opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
+    points, discarded = res.per_image()[0]
+    return SlideResult(points, discarded, count, mask)
+
+
+def detect_slides(slides, model, device=None, **kwargs):
+    """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order."""
+    for image_u8 in slides:
+        yield detect_slide(image_u8, model, device, **kwargs)
 
 
 def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):

@@ -1102,6 +1102,17 @@ def stitch_patches(patches, corners, H, W):
     return out
 
 
+def stitch_logits(mask, logits, corners, ch=1):
+    """logits fp32 [B,C,ph,pw], corners int32 [B,2] (device) -> mask uint8 [H,W] (device), in place: quantised softmax channel ch of
+    every patch, the highest patch index of the batch winning overlaps; one launch, no workspace, no synchronisation."""
+    _f32(logits)
+    B, C, ph, pw = logits.shape
+    H, W = mask.shape
+    if B:
+        _lib.check(_lib.load().cs_stitch_logits(_p(logits), B, C, ph, pw, int(ch), _p(corners), H, W, _p(mask), _stream()), "stitch_logits")
+    return mask
+
+
 def detect_grid_size(H, W, interval, window):
     return _lib.load().cs_detect_grid_size(int(H), int(W), int(interval), int(window))
 

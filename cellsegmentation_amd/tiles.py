@@ -27,6 +27,30 @@ def get_tiles(shape_hw, interval, size):
     return [(x, y) for x in _axis_origins(h, interval, size) for y in _axis_origins(w, interval, size)]
 
 
+def _pair(v, what):
+    try:
+        a, b = (v, v) if np.ndim(v) == 0 else v
+        a, b = int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be an integer or a pair of integers, got {v!r}") from None
+    if a <= 0 or b <= 0:
+        raise ValueError(f"{what} must be positive, got {v!r}")
+    return a, b
+
+
+def sample_patches(size_hw, patch_size=(299, 299), interval=None):
+    """[(x, y)] patch corners of a whole slide or ROI, in the order of the reference's ``MaskTestset.sample_patches``
+    (dataset/dataset.py:577-612; both of its modes walk the same grid): x outer, y inner, the last origin of an axis aligned to
+    the border.  ``size_hw[k]`` pairs with ``patch_size[k]`` and ``interval[k]``; interval=None is ``patch_size - 16``
+    (dataset/dataset.py:540,548).  A patch larger than the image raises ``ValueError`` (the reference dies with ``IndexError``)."""
+    ph, pw = _pair(patch_size, "patch_size")
+    ih, iw = (ph - 16, pw - 16) if interval is None else _pair(interval, "interval")
+    if ih <= 0 or iw <= 0:
+        raise ValueError(f"interval must be positive, got {(ih, iw)} for patch_size {(ph, pw)}")
+    h, w = int(size_hw[0]), int(size_hw[1])
+    return [(x, y) for x in _axis_origins(h, ih, ph) for y in _axis_origins(w, iw, pw)]
+
+
 def tile_index(n_images, shape_hw, interval, size):
     """tileIDX (image id per tile) and the (row, col) grid for n_images equally sized images (dataset/dataset.py:118-140)."""
     grid = np.asarray(get_tiles(shape_hw, interval, size), dtype=np.int32)

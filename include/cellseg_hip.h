@@ -526,6 +526,14 @@ int cs_prune_excess(const int32_t* labels, long long n, int flag, long long n_ex
  * cs_stitch_patches  : out[H][W] = 0, then patch m (patches[M][ph][pw]) written at corners[m] = (row, col) (device int32
  *                      [M][2]), the highest m winning where patches overlap (clipped at the borders);
  *                      workspace >= cs_stitch_workspace(H, W) bytes.
+ * cs_stitch_logits   : the same mask built batch by batch, without the resident patches and the owner map: for the B patches
+ *                      logits[B][C][ph][pw] (fp32, C >= 2) at corners[b] = (row, col) (device int32 [B][2]),
+ *                      mask[row + y][col + x] = trunc(255 softmax_c(logits[b])[ch]) -- the bits of cs_softmax_channel_fwd followed by
+ *                      cs_detect_quantize -- in place, one launch, no workspace.  Within the call the highest b covering a pixel
+ *                      writes it, exactly once (decided from the corners alone: no atomics, any launch order); pixels that no
+ *                      patch of the call covers keep their value; parts of a patch outside the mask are clipped.  Calls are
+ *                      ordered by the stream only: every call for one mask must go to the same stream.  Batches of a zeroed mask
+ *                      in index order give cs_stitch_patches of all patches, for any split.  H, W < 2^29.
  * cs_detect_grid_size: number G of windows of get_tiles((H, W), interval, window) (-1 when the window does not fit).
  * cs_detect_meanshift: per map n, the grid windows whose blurred centre is above thr255 (fp64 compare), in grid order, each run
  *                      through cv2.meanShift (TermCriteria(EPS, 0, 1e-5): max_iter steps, stopping early at a fixed point);
@@ -551,6 +559,8 @@ int cs_detect_blur(const void* src, int src_is_f32, int N, int H, int W, const i
 size_t cs_stitch_workspace(int H, int W);
 int cs_stitch_patches(const uint8_t* patches, int M, int ph, int pw, const int32_t* corners, int H, int W, uint8_t* out,
                       void* workspace, size_t workspace_bytes, void* stream);
+int cs_stitch_logits(const float* logits, int B, int C, int ph, int pw, int ch, const int32_t* corners, int H, int W, uint8_t* mask,
+                     void* stream);
 int cs_detect_grid_size(int H, int W, int interval, int window);
 int cs_detect_meanshift(const uint8_t* blurred, int N, int H, int W, int interval, int window, double thr255, int max_iter,
                         int32_t* pts, int32_t* n_pts, void* stream);

@@ -4,7 +4,10 @@ host for the same work.  Checks that the GPU outputs equal the restatement.  --m
 exact distance transform, or both on the same maps in one run (the blur is then the yardstick of the distance form); the distance
 form is also timed on its worst case, a 4096^2 map that is all foreground but one pixel (smoothing kernels alone).
 
-    python tools/detect_microbench.py [--method both] [--reps 5] [--host-maps 128] [--json PATH]
+The 4096^2 grid is also stitched from segment logits: detect.stitch_logits batch by batch next to softmax_channel_fwd + quantize +
+stitch_patches on the same logits, with the peak device memory either takes (--stitch-only runs nothing else).
+
+    python tools/detect_microbench.py [--method both] [--reps 5] [--host-maps 128] [--stitch-only] [--json PATH]
 """
 import argparse
 import json
@@ -64,14 +67,18 @@ def main():
     ap.add_argument("--method", choices=["gaussianblur", "distancetransform", "both"], default="gaussianblur")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-maps", type=int, default=128, help="maps of the batch also run (and checked) on the host")
+    ap.add_argument("--stitch-only", action="store_true", help="only the streamed / resident stitch of segment logits")
     ap.add_argument("--json", default=None, help="also write the results to this file")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {}
     methods = ["gaussianblur", "distancetransform"] if args.method == "both" else [args.method]
+    if args.stitch_only:
+        methods = []
     # ---- 128 maps of 299^2
-    probs = blob_probs(128, 299, 299, 1 / 1500, seed=1)
-    pd = torch.from_numpy(probs).to(dev)
+    if methods:
+        probs = blob_probs(128, 299, 299, 1 / 1500, seed=1)
+        pd = torch.from_numpy(probs).to(dev)
     taps = D.gaussian_taps(15, 3.)
 
     for method in methods:
@@ -100,12 +107,12 @@ def main():
     if origins[-1] != H - 299:
         origins.append(H - 299)
     grid = [(r, c) for r in origins for c in origins]
-    patches = blob_probs(len(grid), 299, 299, 1 / 1500, seed=2)
-    pq = D.quantize(torch.from_numpy(patches).to(dev))
-    whole = D.stitch_patches(pq, grid, (H, W))
-
-    mask = R.stitch(R.quantize(patches), grid, (H, W))
-    stitched_ok = bool(np.array_equal(whole.cpu().numpy(), mask))
+    if methods:
+        patches = blob_probs(len(grid), 299, 299, 1 / 1500, seed=2)
+        pq = D.quantize(torch.from_numpy(patches).to(dev))
+        whole = D.stitch_patches(pq, grid, (H, W))
+        mask = R.stitch(R.quantize(patches), grid, (H, W))
+        stitched_ok = bool(np.array_equal(whole.cpu().numpy(), mask))
     for method in methods:
         def gpu_whole():
             return D._detect(whole[None], None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False, method)
@@ -123,6 +130,44 @@ def main():
         res[key] = {"method": method, "device_ms": ms, "device_ms_all": ts, "smoothing_ms": sm_ms, "host_ms": host_ms, "patches": len(grid),
                     "cells": int(out.offsets[-1]), "windows_kept": int(out.n_kept.sum()), "equal_to_host": ok}
         print(json.dumps({key: res[key]}), flush=True)
+    # ---- the same 4096^2 grid from segment LOGITS: streamed stitch_logits (batches of 16, one launch each, the mask and the corner
+    # table resident) next to the resident path softmax_channel_fwd + quantize + stitch_patches on the same logits (every patch and
+    # the 4 H W byte owner map resident); peak = rise of torch.cuda.max_memory_allocated over what is allocated before the call
+    logits = (4 * torch.randn((len(grid), 2, 299, 299), generator=torch.Generator().manual_seed(3))).to(dev)
+    rc = torch.tensor(grid, dtype=torch.int32, device=dev)
+
+    def streamed():
+        m = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        for i in range(0, len(grid), 16):
+            K.stitch_logits(m, logits[i:i + 16], rc[i:i + 16], 1)
+        return m
+
+    def resident():
+        return K.stitch_patches(K.detect_quantize(K.softmax_channel_fwd(logits, 1)), rc, H, W)
+
+    def peak_rise(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        out = fn()
+        torch.cuda.synchronize()
+        del out
+        return int(torch.cuda.max_memory_allocated() - before)
+    def one_launch():                                                       # the kernel alone: every patch in one call
+        return K.stitch_logits(torch.zeros((H, W), dtype=torch.uint8, device=dev), logits, rc, 1)
+    same = bool(torch.equal(streamed(), resident())) and bool(torch.equal(one_launch(), resident()))
+    rounds = {name: time_dev(fn, args.reps) for name, fn in (("streamed", streamed), ("resident", resident))}   # time_dev warms up
+    again = {name: time_dev(fn, args.reps) for name, fn in (("resident", resident), ("streamed", streamed))}   # alternated order
+    res["stitch_logits_4096"] = {"patches": len(grid), "batch": 16, "launches_streamed": (len(grid) + 15) // 16,
+                                 "streamed_ms": min(rounds["streamed"][0], again["streamed"][0]),
+                                 "resident_ms": min(rounds["resident"][0], again["resident"][0]),
+                                 "streamed_ms_all": rounds["streamed"][1] + again["streamed"][1],
+                                 "resident_ms_all": rounds["resident"][1] + again["resident"][1],
+                                 "one_launch_ms": time_dev(one_launch, args.reps)[0],
+                                 "streamed_peak_bytes": peak_rise(streamed), "resident_peak_bytes": peak_rise(resident),
+                                 "logit_bytes": logits.numel() * 4, "mask_bytes": H * W, "equal_to_resident": same}
+    print(json.dumps({"stitch_logits_4096": res["stitch_logits_4096"]}), flush=True)
+    del logits
     if "distancetransform" in methods:
         # ---- the distance form's worst case: every pixel's row search runs to the one background pixel's column
         worst = torch.full((1, H, W), 255, dtype=torch.uint8, device=dev)
@@ -137,7 +182,7 @@ def main():
     if args.json:
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
-    if not all(v["equal_to_host"] for v in res.values()):
+    if not all(v.get("equal_to_host", True) and v.get("equal_to_resident", True) for v in res.values()):
         sys.exit(1)
 
 
