@@ -9,10 +9,13 @@
 //               flatten every pixel takes its root; a tile-local root that is no longer a root adds its count to the root's slot
 //   filter    out = the other value where the pixel has the wanted value and area[root] < threshold (strict), else the input
 //   number    scipy's numbering of the foreground: 1 + the number of foreground roots with a lower index in the same image
+//   measure   one table row per numbered component (area, bounding box, row / column / intensity sums, intensity maximum): integer
+//             atomics, one set per horizontal run of foreground pixels within a wave's 64 columns of one image row
 // Hooks only ever lower a label and a label is always an index of the same component, so the root of a component is its lowest
 // index whatever order the hooks land in; areas are integer sums.  The result does not depend on launch order.  Every union loop
 // lowers max(a, b) in each turn that does not end it, so it is bounded by the index range; nothing waits on another thread.
 // The number of launches depends on (N, H, W) only and nothing synchronises with the host.
+#include <limits.h>
 #include <stdio.h>
 #include "cs_common.h"
 #include "cs_block.h"
@@ -161,7 +164,8 @@ __global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __rest
 }
 
 // one workgroup per image: blk[n][0..B) -> its exclusive prefix sums, in place
-__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B) {
+// counts (or NULL): [n] = the number of foreground components of image n
+__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B, int32_t* __restrict__ counts) {
     __shared__ int part[1024];
     int32_t* blk = blk_all + (long long)blockIdx.x * B;
     const int seg = (B + 1023) / 1024;
@@ -170,6 +174,7 @@ __global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__
     for (int i = lo; i < hi; ++i) s += blk[i];
     int total;
     int run = block_scan_incl<1024>(s, part, total) - s;
+    if (counts && threadIdx.x == 0) counts[blockIdx.x] = total;
     for (int i = lo; i < hi; ++i) {
         const int v = blk[i];
         blk[i] = run;
@@ -187,6 +192,104 @@ __global__ __launch_bounds__(kNB) void number_assign_kernel(const uint8_t* __res
     const int before = block_rank<kNB>(root, wsum, total);
     if (!root) return;
     num[base + i] = blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] + before + 1;
+}
+
+// ---- one table row per component: row (n, k) of every table belongs to the component numbered k + 1 of image n ------------------
+struct Tables {
+    int32_t* area;       // [N][cap]
+    int32_t* bbox;       // [N][cap][4] = r0, c0, r1, c1 (half-open)
+    long long* sums;     // [N][cap][2] = sum of rows, sum of columns
+    long long* isum;     // [N][cap], with an intensity image
+    int32_t* imax;       // [N][cap], with an intensity image
+};
+
+// All zero, except that the lower bounds of the rows that will be written (k < count) start at INT_MAX: every such component has
+// a pixel, so none of them is left behind.
+__global__ __launch_bounds__(256) void measure_init_kernel(const int32_t* __restrict__ counts, int N, int cap, Tables t, int with_v) {
+    const long long rows = (long long)N * cap;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        const int lo = (int)(i % cap) < counts[i / cap] ? INT_MAX : 0;
+        t.area[i] = 0;
+        t.bbox[4 * i] = lo;
+        t.bbox[4 * i + 1] = lo;
+        t.bbox[4 * i + 2] = 0;
+        t.bbox[4 * i + 3] = 0;
+        t.sums[2 * i] = 0;
+        t.sums[2 * i + 1] = 0;
+        if (with_v) {
+            t.isum[i] = 0;
+            t.imax[i] = 0;
+        }
+    }
+}
+
+// min / max into a slot that only ever moves one way: a value read earlier in this launch is never beyond the current one, so an
+// update that the read value already covers is dropped without an atomic, however stale the read is.
+__device__ __forceinline__ void lower_to(int32_t* p, int x) {
+    if (__hip_atomic_load(p, __ATOMIC_RELAXED, kGlobal) > x) __hip_atomic_fetch_min(p, x, __ATOMIC_RELAXED, kGlobal);
+}
+__device__ __forceinline__ void raise_to(int32_t* p, int x) {
+    if (__hip_atomic_load(p, __ATOMIC_RELAXED, kGlobal) < x) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, kGlobal);
+}
+
+// A wave takes 64 consecutive columns of ONE image row (the walk is over (n, r, 64-column segment), so no wave straddles a row
+// end).  Horizontal neighbours in the foreground are one component, so a maximal run of foreground lanes has one table row: its
+// head lane looks the number up once and issues one set of atomics for the whole run -- length, closed-form column sum, and the
+// intensity sum / maximum from a segmented shuffle reduction.  REDUCE = false (A/B flavour only) is the per-pixel form: every
+// foreground lane is a run of one.  lab: the root of every pixel; num: the number of every foreground root.
+template <bool REDUCE>
+__global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict__ m, const uint8_t* __restrict__ v, int N, int H, int W,
+                                                      const int32_t* __restrict__ lab, const int32_t* __restrict__ num, int cap, Tables t) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned segs = (unsigned)(W + 63) >> 6;
+    const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
+    const long long total = (long long)N * H * W;
+    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
+        const unsigned row = (unsigned)it / segs;                      // n H + r
+        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
+        const int n = (int)(row / (unsigned)H), r = (int)(row - (unsigned)n * (unsigned)H);
+        const long long p = (long long)row * W + c;
+        const bool fg = c < W && m[p] != 0;
+        const unsigned long long bal = __ballot(fg);
+        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
+        int s = (v && fg) ? v[p] : 0, mx = s;
+        int len = 1;
+        bool head = fg;
+        if (REDUCE) {
+            const unsigned long long gap = ~bal >> lane;               // bit 0 = this lane; the first set bit ends the run
+            len = gap ? __builtin_ctzll(gap) : 64 - lane;              // foreground lanes from this one to its run's last
+            head = fg && !(((bal << 1) >> lane) & 1);                  // the lane to the left is background, or this is lane 0
+            if (v) {
+                const int last = fg ? lane + len - 1 : lane;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {               // lane i: the sum / maximum over [i, min(i + 2 off - 1, last)]
+                    const int os = __shfl_down(s, off), om = __shfl_down(mx, off);
+                    if (lane + off <= last) {
+                        s += os;
+                        mx = max(mx, om);
+                    }
+                }
+            }
+        }
+        if (!head) continue;
+        const int root = lab[p];
+        if ((unsigned)root >= (unsigned)total) continue;               // never with a workspace that label_into filled
+        const int k = num[root] - 1;
+        if ((unsigned)k >= (unsigned)cap) continue;
+        const long long q = (long long)n * cap + k;
+        __hip_atomic_fetch_add(t.area + q, len, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_add(t.sums + 2 * q, (long long)r * len, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_add(t.sums + 2 * q + 1, (long long)len * c + (long long)len * (len - 1) / 2, __ATOMIC_RELAXED, kGlobal);
+        lower_to(t.bbox + 4 * q, r);
+        lower_to(t.bbox + 4 * q + 1, c);
+        raise_to(t.bbox + 4 * q + 2, r + 1);
+        raise_to(t.bbox + 4 * q + 3, c + len);
+        if (v) {
+            __hip_atomic_fetch_add(t.isum + q, (long long)s, __ATOMIC_RELAXED, kGlobal);
+            raise_to(t.imax + q, mx);
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ p, long long n, float thr, uint8_t* __restrict__ out) {
@@ -236,6 +339,20 @@ int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws
     return CS_OK;
 }
 
+// scipy's number of every foreground root of ws.lab into its slot of ws.cnt (the areas there are spent); counts (or NULL): the
+// number of foreground components of every image
+int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st) {
+    const long long HW = (long long)H * W;
+    const int B = (int)blocks_per_image(H, W);
+    hipLaunchKernelGGL(number_count_kernel, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, HW, ws.blk);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(number_scan_kernel, dim3(N), dim3(1024), 0, st, ws.blk, B, counts);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(number_assign_kernel, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, HW, ws.blk, ws.cnt);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
 int carve(const char* what, int N, int H, int W, int connectivity, const void* in, const void* out, void* workspace, size_t bytes, Ws* ws) {
     static thread_local char msg[160];
     auto fail = [&](const char* why) {
@@ -272,15 +389,54 @@ extern "C" int cs_regions_label(const uint8_t* mask, int N, int H, int W, int co
     if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    if ((rc = number_into(mask, N, H, W, ws, nullptr, st)) != CS_OK) return rc;
     const long long HW = (long long)H * W;
-    const int B = (int)blocks_per_image(H, W);
-    hipLaunchKernelGGL(number_count_kernel, dim3(B, N), dim3(kNB), 0, st, mask, ws.lab, HW, ws.blk);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(number_scan_kernel, dim3(N), dim3(1024), 0, st, ws.blk, B);
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(number_assign_kernel, dim3(B, N), dim3(kNB), 0, st, mask, ws.lab, HW, ws.blk, ws.cnt);   // cnt: number of every root
-    CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(spread_kernel, dim3(grid_for(N * HW)), dim3(256), 0, st, mask, N * HW, ws.lab, ws.cnt, 1, labels);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_number(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* counts, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_number", N, H, W, connectivity, mask, counts, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    return number_into(mask, N, H, W, ws, counts, st);
+}
+
+extern "C" int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity, int N, int H, int W, int connectivity, int capacity,
+                                  int numbered, int32_t* counts, int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum,
+                                  int32_t* imax, void* workspace, size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_measure", N, H, W, connectivity, mask, counts, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    CS_CHECK_ARG(area && bbox && sums, "regions_measure: NULL table");
+    CS_CHECK_ARG(capacity >= 1 && capacity <= (long long)H * W, "regions_measure: need 1 <= capacity <= H W");
+    CS_CHECK_ARG(numbered == 0 || numbered == 1, "regions_measure: numbered must be 0 or 1");
+    CS_CHECK_ARG(!intensity || (isum && imax), "regions_measure: an intensity image needs both intensity tables");
+    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(isum)) & 7), "regions_measure: misaligned int64 table");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!numbered) {
+        if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+        if ((rc = number_into(mask, N, H, W, ws, counts, st)) != CS_OK) return rc;
+    }
+    const Tables t{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
+    hipLaunchKernelGGL(measure_init_kernel, dim3(grid_for((long long)N * capacity)), dim3(256), 0, st, counts, N, capacity, t,
+                       intensity ? 1 : 0);
+    CS_LAUNCH_CHECK();
+    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
+    const dim3 grid(grid_for(waves * 64));
+#ifdef CS_AB_SWITCHES
+    static const int per_pixel = cs_env_int_("CELLSEG_MEASURE_PER_PIXEL", 0);     // A/B flavour: what the in-wave run reduction buys
+    if (per_pixel) {
+        hipLaunchKernelGGL(measure_kernel<false>, grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t);
+        CS_LAUNCH_CHECK();
+        return CS_OK;
+    }
+#endif
+    hipLaunchKernelGGL(measure_kernel<true>, grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -253,6 +253,19 @@ def detect_slides(slides, model, device=None, **kwargs):
         yield detect_slide(image_u8, model, device, **kwargs)
 
 
+def _cleaned_batch(model, x, threshold, mo, ho, reg_limit):
+    """test_seg.py:515-527 for one batch on the device -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W])"""
+    from . import regions as Rg
+    probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+    if reg_limit:
+        model.setmode("image")
+        counts = torch.round(model(x)[1].detach()[:, 0].float())
+        model.setmode("segment")
+        probs = probs * (counts != 0).to(probs.dtype)[:, None, None]
+    classes = Rg.threshold(probs, threshold)
+    return probs, Rg.remove_small_regions(classes, mo, ho, out=classes)
+
+
 def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):
     """Cleaned binary masks per image (test_seg.py:515-527): segment-mode forward, softmax channel 1, ``> threshold`` (compared in
     float32, as numpy does for a float32 map), ``remove_small_regions(., 300, 100)``.  With reg_limit the map of an image whose
@@ -264,16 +277,43 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
     out = []
     with torch.no_grad():
         for i, data in enumerate(tqdm(loader, desc="image segmenting")):
-            x = data.to(device)
-            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
-            if reg_limit:
-                model.setmode("image")
-                counts = torch.round(model(x)[1].detach()[:, 0].float())
-                model.setmode("segment")
-                probs = probs * (counts != 0).to(probs.dtype)[:, None, None]
-            classes = Rg.threshold(probs, threshold)
-            out.append(Rg.remove_small_regions(classes, mo, ho, out=classes))
+            out.append(_cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit)[1])
     return torch.cat(out) if out else torch.zeros((0,), dtype=torch.bool, device=device)
+
+
+def measure_cells(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, connectivity=1,
+                  max_regions=None):
+    """One row per segmented cell: the per-batch body of ``segment_classes``, then ``regions.measure`` of the cleaned masks with
+    ``detect.quantize`` of the probabilities (uint8 ``trunc(255 p)``) as the intensity.  Returns the ``RegionTable.per_image``
+    dicts of all batches in dataset order (area, bbox, centroid, intensity_sum / _mean / _max per cell).  With ``max_regions``
+    given nothing synchronises inside the loop: the tables are read back after the last batch."""
+    from . import detect as D
+    from . import regions as Rg
+    mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
+    model.eval()
+    tables = []
+    with torch.no_grad():
+        for data in tqdm(loader, desc="cell measuring"):
+            probs, classes = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit)
+            tables.append(Rg.measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions))
+    return [d for t in tables for d in t.per_image()]
+
+
+def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None):
+    """One row per cell of a stitched uint8 [H, W] map such as ``SlideResult.mask``: foreground = ``mask_u8 > thr_u8``, cleaned by
+    ``remove_small_regions``, measured with the map itself as the intensity -> the one-image ``RegionTable`` (device tensors)."""
+    from . import regions as Rg
+    t = torch.from_numpy(np.ascontiguousarray(mask_u8)) if isinstance(mask_u8, np.ndarray) else mask_u8
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2:
+        raise TypeError("measure_slide: expected a uint8 [H, W] map")
+    if isinstance(thr_u8, bool) or int(thr_u8) != thr_u8 or not 0 <= thr_u8 <= 255:
+        raise ValueError(f"measure_slide: thr_u8 must be an integer in [0, 255], got {thr_u8!r}")
+    if not t.is_cuda:
+        t = t.to(Rg._device())
+    t = t.contiguous()
+    fg = t > int(thr_u8)
+    fg = Rg.remove_small_regions(fg, min_object_size, hole_area_threshold, connectivity, out=fg)
+    return Rg.measure(fg, intensity=t, connectivity=connectivity, max_regions=max_regions)
 
 
 def _batch_points(points, n):

@@ -1199,6 +1199,47 @@ def regions_label(mask, connectivity=1, out=None, ws=None):
     return out
 
 
+def regions_number(mask, connectivity=1, counts=None, ws=None):
+    """uint8 [N,H,W] -> counts int32 [N], the number of foreground components per image; ``ws`` keeps the roots and numbers for a
+    regions_measure(..., numbered=True) of the same mask"""
+    N, H, W, ws = _regions_args(mask, ws)
+    if counts is None:
+        counts = torch.empty((N,), dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().cs_regions_number(_p(mask), N, H, W, int(connectivity), _p(counts), _p(ws), ws.numel(), _stream()), "regions_number")
+    return counts
+
+
+def regions_measure(mask, capacity, intensity=None, connectivity=1, numbered=False, counts=None, area=None, bbox=None, sums=None,
+                    isum=None, imax=None, ws=None):
+    """uint8 [N,H,W] (and uint8 intensity [N,H,W] or None) -> (counts int32 [N], area int32 [N,cap], bbox int32 [N,cap,4],
+    sums int64 [N,cap,2], isum int64 [N,cap] | None, imax int32 [N,cap] | None); row k = component k + 1, zero from
+    min(count, cap) on.  Tables that are given are written in place (contiguous, of these shapes).  numbered=True: ``counts`` and
+    ``ws`` are what regions_number left for this mask."""
+    N, H, W, ws = _regions_args(mask, ws)
+    cap = int(capacity)
+    if numbered and counts is None:
+        raise ValueError("regions_measure: numbered=True needs the counts of regions_number")
+    if intensity is not None and (intensity.dtype != torch.uint8 or tuple(intensity.shape) != (N, H, W)):
+        raise TypeError("regions_measure: the intensity image is uint8 of the mask's shape")
+    want = {"counts": ((N,), torch.int32), "area": ((N, cap), torch.int32), "bbox": ((N, cap, 4), torch.int32),
+            "sums": ((N, cap, 2), torch.int64)}
+    if intensity is not None:
+        want.update(isum=((N, cap), torch.int64), imax=((N, cap), torch.int32))
+    given = {"counts": counts, "area": area, "bbox": bbox, "sums": sums, "isum": isum, "imax": imax}
+    t = {}
+    for name, (shape, dtype) in want.items():
+        x = given[name]
+        if x is None:
+            x = torch.empty(shape, dtype=dtype, device=mask.device)
+        elif x.dtype != dtype or tuple(x.shape) != shape:
+            raise TypeError(f"regions_measure: {name} must be {dtype} of shape {shape}, got {x.dtype} {tuple(x.shape)}")
+        t[name] = x
+    _lib.check(_lib.load().cs_regions_measure(_p(mask), _p(intensity), N, H, W, int(connectivity), cap, int(bool(numbered)), _p(t["counts"]),
+                                              _p(t["area"]), _p(t["bbox"]), _p(t["sums"]), _p(t.get("isum")), _p(t.get("imax")), _p(ws),
+                                              ws.numel(), _stream()), "regions_measure")
+    return t["counts"], t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
+
+
 def regions_areas(mask, connectivity=1, out=None, ws=None):
     """uint8 [N,H,W] -> int32 [N,H,W]: the area of the component of equal-valued pixels under every pixel"""
     N, H, W, ws = _regions_args(mask, ws)

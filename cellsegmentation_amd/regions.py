@@ -18,7 +18,15 @@ different operation, and that raises ``TypeError`` here.
 
 Every function takes ``[H, W]`` or ``[N, H, W]`` (numpy or torch; N independent images) and returns a device tensor of the same
 shape.  A call enqueues a number of launches fixed by the shape and never synchronises, so it can be captured into a graph.
+
+``measure`` turns the same labelling into one table row per foreground component (``RegionTable``: count, area, bounding box,
+centroid, intensity sum / mean / maximum), pinned to ``scipy.ndimage`` (sum, mean, maximum, center_of_mass, find_objects;
+tests/golden/props_vectors.npz).  With a fixed ``max_regions`` it keeps the contract above; with ``max_regions=None`` it reads the
+largest component count back once to size the tables.
 """
+import dataclasses
+import typing
+
 import numpy as np
 import torch
 
@@ -148,3 +156,96 @@ def threshold(probs, thr):
     if not t.is_cuda:
         t = t.to(_device())
     return K.regions_threshold(t.contiguous(), float(thr)).view(torch.bool)
+
+
+@dataclasses.dataclass
+class RegionTable:
+    """Per-component measurements of N masks as device tensors; row k of image n is scipy label k + 1 and rows from
+    min(count, capacity) on are zero.  ``counts`` int32 [N] is the true component count, also above the capacity; ``area`` int32
+    [N, cap]; ``bbox`` int32 [N, cap, 4] = (r0, c0, r1, c1), half-open (the ``find_objects`` slices); ``sum_rc`` int64 [N, cap, 2];
+    ``intensity_sum`` int64 [N, cap] and ``intensity_max`` int32 [N, cap], or None without an intensity image."""
+    counts: torch.Tensor
+    capacity: int
+    area: torch.Tensor
+    bbox: torch.Tensor
+    sum_rc: torch.Tensor
+    intensity_sum: typing.Optional[torch.Tensor] = None
+    intensity_max: typing.Optional[torch.Tensor] = None
+
+    def centroid(self):
+        """float64 [N, cap, 2] = ``scipy.ndimage.center_of_mass`` (sum_rc / area), NaN in unused rows; on the device."""
+        return self.sum_rc.to(torch.float64) / self.area.to(torch.float64).unsqueeze(-1)
+
+    def mean_intensity(self):
+        """float64 [N, cap] = ``scipy.ndimage.mean`` of the intensity (intensity_sum / area), NaN in unused rows; on the device."""
+        if self.intensity_sum is None:
+            raise ValueError("mean_intensity: the table was measured without an intensity image")
+        return self.intensity_sum.to(torch.float64) / self.area.to(torch.float64)
+
+    def overflowed(self):
+        """device bool [N]: the image has more components than the table has rows"""
+        return self.counts > self.capacity
+
+    def per_image(self):
+        """A host list of N dicts of numpy arrays trimmed to min(count, capacity) rows: ``area``, ``bbox``, ``centroid`` and, with
+        an intensity image, ``intensity_sum``, ``intensity_mean``, ``intensity_max``.  The one method that synchronises."""
+        cols = {"area": self.area, "bbox": self.bbox, "centroid": self.centroid()}
+        if self.intensity_sum is not None:
+            cols.update(intensity_sum=self.intensity_sum, intensity_mean=self.mean_intensity(), intensity_max=self.intensity_max)
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        counts = self.counts.cpu().numpy()
+        return [{k: v[n, :min(int(c), self.capacity)] for k, v in cols.items()} for n, c in enumerate(counts)]
+
+
+def _as_intensity(v, shape):
+    """uint8 numpy / torch of the mask's shape -> the tensor (not yet on the device); argument errors only"""
+    t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+    if not torch.is_tensor(t):
+        raise TypeError("measure: intensity must be a numpy array or a torch tensor")
+    if t.dtype != torch.uint8:
+        raise TypeError(f"measure: intensity must be uint8, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"measure: intensity of shape {tuple(t.shape)} for a mask of shape {tuple(shape)}")
+    return t
+
+
+def measure(m, intensity=None, connectivity=1, max_regions=None):
+    """One row per connected foreground component of every image -> ``RegionTable``.  ``intensity``: uint8 of the mask's shape, or
+    None.  ``max_regions=int`` fixes the rows per image (capped at H W; components numbered above it are counted, not measured):
+    nothing synchronises and the call can be captured into a graph.  ``max_regions=None`` numbers first, reads the largest count
+    back (the one synchronisation) and measures with exactly that capacity (1 when there is no component)."""
+    conn = _check_connectivity(connectivity)
+    if max_regions is not None and (isinstance(max_regions, bool) or int(max_regions) != max_regions or max_regions < 1):
+        raise ValueError(f"max_regions must be a positive integer or None, got {max_regions!r}")
+    v = None if intensity is None else _as_intensity(intensity, getattr(m, "shape", ()))
+    t, two_d = _as_masks(m, "measure")
+    N, H, W = t.shape
+    if v is not None:
+        v = v.to(t.device).contiguous().view(N, H, W)
+    chunks = _chunks(t)
+    counts = torch.empty((N,), dtype=torch.int32, device=t.device)
+    ws, ws_n, numbered = None, 0, False
+
+    def workspace(n):
+        nonlocal ws, ws_n
+        if ws_n != n:
+            ws, ws_n = K.regions_workspace(n, H, W, t.device), n
+        return ws
+
+    if max_regions is None:
+        for a, b in chunks:
+            K.regions_number(t[a:b], conn, counts=counts[a:b], ws=workspace(b - a))
+        cap = max(1, int(counts.max()))                                  # the one synchronisation
+        numbered = len(chunks) == 1                                      # one call: its workspace still holds the numbering
+    else:
+        cap = min(int(max_regions), H * W)
+    dev = t.device
+    area = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    bbox = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
+    sums = torch.empty((N, cap, 2), dtype=torch.int64, device=dev)
+    isum = None if v is None else torch.empty((N, cap), dtype=torch.int64, device=dev)
+    imax = None if v is None else torch.empty((N, cap), dtype=torch.int32, device=dev)
+    for a, b in chunks:
+        K.regions_measure(t[a:b], cap, None if v is None else v[a:b], conn, numbered, counts[a:b], area[a:b], bbox[a:b], sums[a:b],
+                          None if v is None else isum[a:b], None if v is None else imax[a:b], ws=workspace(b - a))
+    return RegionTable(counts, cap, area, bbox, sums, isum, imax)

@@ -589,7 +589,19 @@ int cs_detect_edt_smooth(const void* src, int src_is_f32, int N, int H, int W, i
  * cs_regions_remove_small: the filter with (1, min_object_size), then with (0, hole_area_threshold) on its result.  out may be mask.
  * cs_regions_threshold   : out[i] = probs[i] > threshold, compared in fp32 (numpy's compare of a float32 array with a Python float).
  * cs_regions_hsv_gate    : out[i] = mask[i] != 0 && max(images_hwc[i][0..3)) <= v_max -- the V-channel gate of preprocess_masks
- *                          (image_processing.py:117-120, v_max = 170) on uint8 [..][3] pixels.  out may be mask. */
+ *                          (image_processing.py:117-120, v_max = 170) on uint8 [..][3] pixels.  out may be mask.
+ * cs_regions_number      : the labelling and numbering of cs_regions_label without the label image -- counts int32 [N] = the number
+ *                          of foreground components of every image; the workspace keeps the root of every pixel and the number
+ *                          of every root for a cs_regions_measure call with numbered = 1.
+ * cs_regions_measure     : one table row per component, row k of image n = component number k + 1, for k < capacity (1 <= capacity
+ *                          <= H W); components numbered above capacity are counted in counts and measured nowhere.  area int32
+ *                          [N][capacity]; bbox int32 [N][capacity][4] = (r0, c0, r1, c1), half-open (scipy's find_objects);
+ *                          sums int64 [N][capacity][2] = the sums of the pixels' rows and columns (center_of_mass = sums / area);
+ *                          with intensity (uint8 [N][H][W], or NULL) also isum int64 [N][capacity] and imax int32 [N][capacity],
+ *                          the sum and the maximum of the intensity under the component (both required then, else ignored).
+ *                          Rows k >= min(counts[n], capacity) are all zero.  numbered = 0 labels and numbers first and writes
+ *                          counts; numbered = 1 reads counts and the workspace as cs_regions_number left them for the same mask,
+ *                          shape and connectivity, so nothing is labelled twice.  int64 tables are 8-byte aligned. */
 size_t cs_regions_workspace(int N, int H, int W);
 int cs_regions_label(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* labels, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -601,6 +613,11 @@ int cs_regions_remove_small(const uint8_t* mask, int N, int H, int W, int min_ob
                             uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 int cs_regions_threshold(const float* probs, long long n, float threshold, uint8_t* out, void* stream);
 int cs_regions_hsv_gate(const uint8_t* images_hwc, const uint8_t* mask, long long n_pixels, int v_max, uint8_t* out, void* stream);
+int cs_regions_number(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* counts, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity, int N, int H, int W, int connectivity, int capacity,
+                       int numbered, int32_t* counts, int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
  * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of

@@ -3,10 +3,18 @@ whole-image mask, device-event timed after warm-up, next to the numpy restatemen
 same work.  Checks that the GPU outputs equal the restatement.
 
     python tools/regions_microbench.py [--reps 5] [--host-maps 128] [--json PATH]
+
+--measure times ``regions.measure`` (uint8 intensity, a fixed ``max_regions``: no synchronisation) next to ``regions.label`` on the
+same two mask sets, checks the tables against tests/props_ref.py, and reports the masks' component statistics.  It then runs
+itself once more in a child process on the A/B flavour of the library (CELLSEG_LIB_FLAVOUR=ab) with CELLSEG_MEASURE_PER_PIXEL=1,
+where every foreground pixel issues its own atomics: what the in-wave run reduction buys.
+
+    python tools/regions_microbench.py --measure [--reps 5] [--host-maps 8] [--json PATH]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -53,22 +61,81 @@ def case(name, masks, reps, host_maps, dev):
     return res
 
 
+def mask_sets():
+    yield "batch128_299", R.blobs(128, 299, 299, seed=1)
+    # one whole-image mask: 299^2 blob patches tiled into 4096^2 (objects and holes cross the patch seams)
+    patches = R.blobs(14 * 14, 299, 299, seed=2)
+    whole = patches.reshape(14, 14, 299, 299).transpose(0, 2, 1, 3).reshape(14 * 299, 14 * 299)[:4096, :4096]
+    yield "whole_4096", np.ascontiguousarray(whole)[None]
+
+
+MAX_REGIONS = {"batch128_299": 256, "whole_4096": 16384}
+
+
+def measure_case(name, masks, reps, host_maps, dev, check):
+    import props_ref as P
+    d = torch.from_numpy(masks).to(dev)
+    v = np.random.RandomState(3).randint(0, 256, size=masks.shape).astype(np.uint8)
+    dv = torch.from_numpy(v).to(dev)
+    cap = MAX_REGIONS[name]
+    label_ms, _ = time_dev(lambda: G.label(d), reps)
+    measure_ms, ts = time_dev(lambda: G.measure(d, intensity=dv, max_regions=cap), reps)
+    res = {"label_ms": label_ms, "measure_ms": measure_ms, "measure_ms_all": ts, "max_regions": cap}
+    if check:
+        t = G.measure(d, intensity=dv, max_regions=cap)
+        counts, area = t.counts.cpu().numpy(), t.area.cpu().numpy()
+        used = area[area > 0]
+        runs = int((np.diff(np.pad(masks, ((0, 0), (0, 0), (1, 0))).astype(np.int8), axis=2) == 1).sum())
+        res.update(components_per_image_mean=float(counts.mean()), components_per_image_max=int(counts.max()),
+                   overflowed=int(t.overflowed().sum()), area_median=float(np.median(used)), area_mean=float(used.mean()),
+                   area_max=int(used.max()), foreground_fraction=float(masks.mean()), foreground_pixels=int(masks.sum()), row_runs=runs)
+        ok = True
+        for i in range(min(host_maps, len(masks))):
+            ref = P.measure(masks[i], v[i], 1, cap)
+            ok &= int(counts[i]) == int(ref["counts"][0])
+            for key in ("area", "bbox", "sum_rc", "intensity_sum", "intensity_max"):
+                ok &= bool(np.array_equal(getattr(t, key)[i].cpu().numpy(), ref[key][0]))
+        res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
+def measure_main(args):
+    """the production library here; the per-pixel form of the accumulation in a child process on the A/B flavour"""
+    dev = torch.device("cuda:0")
+    child = os.environ.get("CELLSEG_MEASURE_PER_PIXEL", "") not in ("", "0")
+    res = {name: measure_case(name, masks, args.reps, args.host_maps, dev, not child) for name, masks in mask_sets()}
+    if child:
+        return res
+    env = dict(os.environ, CELLSEG_LIB_FLAVOUR="ab", CELLSEG_MEASURE_PER_PIXEL="1")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--measure", "--reps", str(args.reps)], env=env, capture_output=True,
+                       text=True, timeout=600)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr)
+        sys.exit(r.returncode)
+    for line in (x for x in r.stdout.splitlines() if x.startswith("{")):
+        for name, v in json.loads(line).items():
+            res[name]["measure_per_pixel_ms"] = v["measure_ms"]
+    print(json.dumps({k: {x: v[x] for x in ("label_ms", "measure_ms", "measure_per_pixel_ms")} for k, v in res.items()}), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-maps", type=int, default=128, help="maps of the batch also run (and checked) on the host")
     ap.add_argument("--json", default=None, help="also write the results to this file")
+    ap.add_argument("--measure", action="store_true", help="time regions.measure next to regions.label instead")
     args = ap.parse_args()
-    dev = torch.device("cuda:0")
-    res = {"batch128_299": case("batch128_299", R.blobs(128, 299, 299, seed=1), args.reps, min(args.host_maps, 128), dev)}
-    # one whole-image mask: 299^2 blob patches tiled into 4096^2 (objects and holes cross the patch seams)
-    patches = R.blobs(14 * 14, 299, 299, seed=2)
-    whole = patches.reshape(14, 14, 299, 299).transpose(0, 2, 1, 3).reshape(14 * 299, 14 * 299)[:4096, :4096]
-    res["whole_4096"] = case("whole_4096", np.ascontiguousarray(whole)[None], args.reps, 1, dev)
+    if args.measure:
+        res = measure_main(args)
+    else:
+        dev = torch.device("cuda:0")
+        res = {name: case(name, masks, args.reps, min(args.host_maps, len(masks)), dev) for name, masks in mask_sets()}
     if args.json:
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
-    if not all(v["equal_to_host"] for v in res.values()):
+    if not all(v.get("equal_to_host", True) for v in res.values()):
         sys.exit(1)
 
 
