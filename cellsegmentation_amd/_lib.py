@@ -167,6 +167,9 @@ _SIGNATURES = {
     "cs_regions_hsv_gate": (c_int, [_P, _P, c_longlong, c_int, _P, _P]),
     "cs_regions_number": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_regions_measure": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cs_regions_split_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cs_regions_split": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cs_regions_measure_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "cs_score_workspace": (c_size_t, [c_int, c_longlong]),
     "cs_score_points": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }

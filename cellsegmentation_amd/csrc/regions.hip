@@ -10,11 +10,18 @@
 //   filter    out = the other value where the pixel has the wanted value and area[root] < threshold (strict), else the input
 //   number    scipy's numbering of the foreground: 1 + the number of foreground roots with a lower index in the same image
 //   measure   one table row per numbered component (area, bounding box, row / column / intensity sums, intensity maximum): integer
-//             atomics, one set per horizontal run of foreground pixels within a wave's 64 columns of one image row
+//             atomics, one set per horizontal run of foreground pixels within a wave's 64 columns of one image row; the same pass
+//             measures a label image (one row per label, a run = equal neighbouring labels)
+//   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
+//             component without a seed is numbered after the seeds:
+//               seeds   one thread per point hangs the live seeds on a chain at their component's root
+//               number  the numbering trio over the roots that have no seed
+//               assign  every pixel walks the chain of its root; a wave whose foreground lanes share a root walks it as one
 // Hooks only ever lower a label and a label is always an index of the same component, so the root of a component is its lowest
 // index whatever order the hooks land in; areas are integer sums.  The result does not depend on launch order.  Every union loop
 // lowers max(a, b) in each turn that does not end it, so it is bounded by the index range; nothing waits on another thread.
-// The number of launches depends on (N, H, W) only and nothing synchronises with the host.
+// The number of launches depends on (N, H, W) only (for a split also on whether there is any point) and nothing synchronises with
+// the host.
 #include <limits.h>
 #include <stdio.h>
 #include "cs_common.h"
@@ -149,23 +156,48 @@ __global__ __launch_bounds__(256) void spread_kernel(const uint8_t* __restrict__
         out[p] = (foreground_only && m[p] == 0) ? 0 : table[lab[p]];
 }
 
-// ---- scipy's numbering: grid (blocks per image, N), kNB pixels per block --------------------------------------------------------
-__device__ __forceinline__ bool is_fg_root(const uint8_t* m, const int32_t* lab, long long HW, long long i, long long base) {
-    return i < HW && m[base + i] != 0 && lab[base + i] == (int32_t)(base + i);
+// ---- the seed points of a split: pts int64 [P][2] (row, col), image n owns pts[off[n] .. off[n + 1]) -----------------------------
+struct Seeds {
+    const long long* pts;
+    const long long* off;     // [N + 1]; NULL = no seeds at all
+    const int32_t* lim;       // [N] or NULL: Python's slice [:lim[n]] of image n's points
+    int P;                    // rows of pts
+};
+
+// S'_n, the number of points of image n that are seeds: within [0, P] whatever the offsets hold
+__device__ __forceinline__ int seed_limit(const Seeds& s, int n) {
+    if (!s.off) return 0;
+    long long k = s.off[n + 1] - s.off[n];
+    k = k < 0 ? 0 : (k > s.P ? s.P : k);
+    if (s.lim) {
+        const long long c = s.lim[n];
+        k = c >= 0 ? (c < k ? c : k) : (k + c > 0 ? k + c : 0);
+    }
+    return (int)k;
 }
 
-__global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab, long long HW,
-                                                           int32_t* __restrict__ blk) {
+// ---- scipy's numbering: grid (blocks per image, N), kNB pixels per block --------------------------------------------------------
+// SEEDLESS = false: every foreground root.  SEEDLESS = true (split): the foreground roots whose slot of `cnt` still holds the area
+// that label_into left there (> 0); the seed pass has replaced it by a chain head (< 0) at every root that has a live seed.
+template <bool SEEDLESS>
+__device__ __forceinline__ bool is_fg_root(const uint8_t* m, const int32_t* lab, const int32_t* cnt, long long HW, long long i,
+                                           long long base) {
+    return i < HW && m[base + i] != 0 && lab[base + i] == (int32_t)(base + i) && (!SEEDLESS || cnt[base + i] > 0);
+}
+
+template <bool SEEDLESS>
+__global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab,
+                                                           const int32_t* __restrict__ cnt, long long HW, int32_t* __restrict__ blk) {
     __shared__ int wsum[kNB / 64];
     const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
     int total;
-    block_rank<kNB>(is_fg_root(m, lab, HW, i, blockIdx.y * HW), wsum, total);
+    block_rank<kNB>(is_fg_root<SEEDLESS>(m, lab, cnt, HW, i, blockIdx.y * HW), wsum, total);
     if (threadIdx.x == 0) blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 // one workgroup per image: blk[n][0..B) -> its exclusive prefix sums, in place
-// counts (or NULL): [n] = the number of foreground components of image n
-__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B, int32_t* __restrict__ counts) {
+// counts (or NULL): [n] = the number of counted roots of image n, after its seeds_n = S'_n seeds
+__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B, int32_t* __restrict__ counts, Seeds seeds) {
     __shared__ int part[1024];
     int32_t* blk = blk_all + (long long)blockIdx.x * B;
     const int seg = (B + 1023) / 1024;
@@ -174,7 +206,7 @@ __global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__
     for (int i = lo; i < hi; ++i) s += blk[i];
     int total;
     int run = block_scan_incl<1024>(s, part, total) - s;
-    if (counts && threadIdx.x == 0) counts[blockIdx.x] = total;
+    if (counts && threadIdx.x == 0) counts[blockIdx.x] = seed_limit(seeds, blockIdx.x) + total;
     for (int i = lo; i < hi; ++i) {
         const int v = blk[i];
         blk[i] = run;
@@ -182,16 +214,18 @@ __global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__
     }
 }
 
+// num: the cnt array itself -- a counted root reads its own slot (SEEDLESS) and then writes its number there, nobody else's
+template <bool SEEDLESS>
 __global__ __launch_bounds__(kNB) void number_assign_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab, long long HW,
-                                                            const int32_t* __restrict__ blk, int32_t* __restrict__ num) {
+                                                            const int32_t* __restrict__ blk, int32_t* num, Seeds seeds) {
     __shared__ int wsum[kNB / 64];
     const long long base = blockIdx.y * HW;
     const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
-    const bool root = is_fg_root(m, lab, HW, i, base);
+    const bool root = is_fg_root<SEEDLESS>(m, lab, num, HW, i, base);
     int total;
     const int before = block_rank<kNB>(root, wsum, total);
     if (!root) return;
-    num[base + i] = blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] + before + 1;
+    num[base + i] = seed_limit(seeds, blockIdx.y) + blk[(long long)blockIdx.y * gridDim.x + blockIdx.x] + before + 1;
 }
 
 // ---- one table row per component: row (n, k) of every table belongs to the component numbered k + 1 of image n ------------------
@@ -204,11 +238,15 @@ struct Tables {
 };
 
 // All zero, except that the lower bounds of the rows that will be written (k < count) start at INT_MAX: every such component has
-// a pixel, so none of them is left behind.
-__global__ __launch_bounds__(256) void measure_init_kernel(const int32_t* __restrict__ counts, int N, int cap, Tables t, int with_v) {
+// a pixel, so none of them is left behind.  counts = NULL (a label image: a label below the count may own no pixel): every lower
+// bound starts at INT_MAX and measure_empty_rows_kernel puts the rows that stayed empty right; maxlab [N] is then zeroed for the
+// label maxima.
+__global__ __launch_bounds__(256) void measure_init_kernel(const int32_t* __restrict__ counts, int N, int cap, Tables t, int with_v,
+                                                           int32_t* __restrict__ maxlab) {
     const long long rows = (long long)N * cap;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
-        const int lo = (int)(i % cap) < counts[i / cap] ? INT_MAX : 0;
+        const int lo = (!counts || (int)(i % cap) < counts[i / cap]) ? INT_MAX : 0;
+        if (maxlab && i < N) maxlab[i] = 0;
         t.area[i] = 0;
         t.bbox[4 * i] = lo;
         t.bbox[4 * i + 1] = lo;
@@ -232,14 +270,28 @@ __device__ __forceinline__ void raise_to(int32_t* p, int x) {
     if (__hip_atomic_load(p, __ATOMIC_RELAXED, kGlobal) < x) __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, kGlobal);
 }
 
+// the rows of a label image's tables that no pixel wrote (a label that owns nothing, e.g. the second of two seeds on one pixel):
+// all zero, as the rows beyond the count
+__global__ __launch_bounds__(256) void measure_empty_rows_kernel(long long rows, Tables t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        if (t.area[i] != 0) continue;
+        t.bbox[4 * i] = 0;
+        t.bbox[4 * i + 1] = 0;
+    }
+}
+
 // A wave takes 64 consecutive columns of ONE image row (the walk is over (n, r, 64-column segment), so no wave straddles a row
 // end).  Horizontal neighbours in the foreground are one component, so a maximal run of foreground lanes has one table row: its
 // head lane looks the number up once and issues one set of atomics for the whole run -- length, closed-form column sum, and the
 // intensity sum / maximum from a segmented shuffle reduction.  REDUCE = false (A/B flavour only) is the per-pixel form: every
 // foreground lane is a run of one.  lab: the root of every pixel; num: the number of every foreground root.
-template <bool REDUCE>
+// LABELS: lab is a label image instead (m and num are not read): foreground = a positive label, table row = label - 1, and a run
+// also starts where the label differs from the left neighbour's -- neighbouring foreground pixels may belong to different cells.
+// The head lanes also raise maxlab[n] (or NULL) to their label.
+template <bool REDUCE, bool LABELS>
 __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict__ m, const uint8_t* __restrict__ v, int N, int H, int W,
-                                                      const int32_t* __restrict__ lab, const int32_t* __restrict__ num, int cap, Tables t) {
+                                                      const int32_t* __restrict__ lab, const int32_t* __restrict__ num, int cap, Tables t,
+                                                      int32_t* __restrict__ maxlab) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned segs = (unsigned)(W + 63) >> 6;
@@ -250,16 +302,19 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
         const int c = (int)((unsigned)it - row * segs) * 64 + lane;
         const int n = (int)(row / (unsigned)H), r = (int)(row - (unsigned)n * (unsigned)H);
         const long long p = (long long)row * W + c;
-        const bool fg = c < W && m[p] != 0;
+        const int l = (LABELS && c < W) ? lab[p] : 0;
+        const bool fg = LABELS ? l > 0 : (c < W && m[p] != 0);
         const unsigned long long bal = __ballot(fg);
         if (bal == 0) continue;                                        // the whole wave: `it` is uniform
         int s = (v && fg) ? v[p] : 0, mx = s;
         int len = 1;
         bool head = fg;
         if (REDUCE) {
-            const unsigned long long gap = ~bal >> lane;               // bit 0 = this lane; the first set bit ends the run
-            len = gap ? __builtin_ctzll(gap) : 64 - lane;              // foreground lanes from this one to its run's last
-            head = fg && !(((bal << 1) >> lane) & 1);                  // the lane to the left is background, or this is lane 0
+            unsigned long long start = bal & ~(bal << 1);              // the lane to the left is background, or this is lane 0
+            if (LABELS) start |= __ballot(fg && l != __shfl_up(l, 1)); // ... or carries another label (lane 0 gets its own back)
+            const unsigned long long rest = ((~bal | start) >> lane) >> 1;   // bit i = lane + 1 + i is no part of this lane's run
+            len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;        // lanes from this one to its run's last
+            head = (start >> lane) & 1;
             if (v) {
                 const int last = fg ? lane + len - 1 : lane;
 #pragma unroll
@@ -273,9 +328,15 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
             }
         }
         if (!head) continue;
-        const int root = lab[p];
-        if ((unsigned)root >= (unsigned)total) continue;               // never with a workspace that label_into filled
-        const int k = num[root] - 1;
+        int k;
+        if (LABELS) {
+            k = l - 1;
+            if (maxlab) raise_to(maxlab + n, l);
+        } else {
+            const int root = lab[p];
+            if ((unsigned)root >= (unsigned)total) continue;           // never with a workspace that label_into filled
+            k = num[root] - 1;
+        }
         if ((unsigned)k >= (unsigned)cap) continue;
         const long long q = (long long)n * cap + k;
         __hip_atomic_fetch_add(t.area + q, len, __ATOMIC_RELAXED, kGlobal);
@@ -289,6 +350,89 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
             __hip_atomic_fetch_add(t.isum + q, (long long)s, __ATOMIC_RELAXED, kGlobal);
             raise_to(t.imax + q, mx);
         }
+    }
+}
+
+// ---- seeded split ------------------------------------------------------------------------------------------------------------------
+// One thread per point.  A point is a live seed when it is one of the first S'_n of its image, lies inside the image and on a
+// foreground pixel.  A live seed is pushed on the chain of its component: the root's slot of `head` (the spent cnt array) holds the
+// area (> 0) while the component has no seed and -(p + 1), p = the point on top of the chain, afterwards; rec[p] = (row, col, index
+// within the image, the next point of the chain or -1).  The order of a chain depends on the order the pushes land in; what the
+// assign pass takes from it, the minimum of (d2, index) over the chain, does not.
+__global__ __launch_bounds__(256) void seed_kernel(const uint8_t* __restrict__ m, int N, int H, int W, Seeds s,
+                                                   const int32_t* __restrict__ lab, int32_t* __restrict__ head, int4* __restrict__ rec,
+                                                   uint8_t* __restrict__ live) {
+    const long long HW = (long long)H * W, total = HW * N;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < s.P; p += (long long)gridDim.x * 256) {
+        int n = 0, hi = N;                                             // the last image whose first point is not after p; every
+        while (hi - n > 1) {                                           // read stays inside off[0 .. N] whatever the offsets hold
+            const int mid = (n + hi) >> 1;
+            if (s.off[mid] <= p) n = mid; else hi = mid;
+        }
+        const long long k = p - s.off[n];
+        bool ok = k >= 0 && p < s.off[n + 1] && k < seed_limit(s, n);
+        const long long r = s.pts[2 * p], c = s.pts[2 * p + 1];
+        ok = ok && r >= 0 && r < H && c >= 0 && c < W;
+        const long long q = ok ? n * HW + r * W + c : 0;
+        ok = ok && m[q] != 0;
+        live[p] = (uint8_t)ok;
+        if (!ok) continue;
+        const int root = lab[q];
+        if ((unsigned)root >= (unsigned)total) continue;               // never with a workspace that label_into filled
+        const int old = __hip_atomic_exchange(head + root, (int)(-(p + 1)), __ATOMIC_RELAXED, kGlobal);
+        rec[p] = make_int4((int)r, (int)c, (int)k, old < 0 ? -old - 1 : -1);
+    }
+}
+
+// 1 + the index of the seed of the chain from point q on that minimises (dr^2 + dc^2, index); d2 < 2^31 as H^2 + W^2 is.  A chain
+// holds every point at most once, so P steps bound the walk.
+__device__ __forceinline__ int nearest_seed(const int4* __restrict__ rec, int q, int P, int r, int c) {
+    unsigned long long best = ~0ull;
+    for (int step = 0; (unsigned)q < (unsigned)P && step < P; ++step) {
+        const int4 s = rec[q];
+        const int dr = r - s.x, dc = c - s.y;
+        const unsigned long long key = ((unsigned long long)(unsigned)(dr * dr + dc * dc) << 32) | (unsigned)s.z;
+        best = key < best ? key : best;
+        q = s.w;
+    }
+    return (int)(unsigned)best + 1;
+}
+
+// A wave takes 64 consecutive columns of one image row, as measure_kernel.  head[root] > 0 is the label itself (a component
+// without a seed, numbered by number_into<true>), < 0 the chain to walk.  Where every foreground lane of the wave has the same root
+// (the inside of a cell clump, most waves) the chain is read through wave-uniform addresses and no lane diverges; otherwise every
+// lane walks its own.  Background writes 0: the output needs no clearing.
+__global__ __launch_bounds__(256) void split_assign_kernel(const uint8_t* __restrict__ m, int N, int H, int W,
+                                                           const int32_t* __restrict__ lab, const int32_t* __restrict__ head,
+                                                           const int4* __restrict__ rec, int P, int32_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned segs = (unsigned)(W + 63) >> 6;
+    const long long items = (long long)N * H * segs;
+    const long long total = (long long)N * H * W;
+    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
+        const unsigned row = (unsigned)it / segs;                      // n H + r
+        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
+        const int r = (int)(row % (unsigned)H);
+        const long long p = (long long)row * W + c;
+        const bool fg = c < W && m[p] != 0;
+        const unsigned long long bal = __ballot(fg);
+        int label = 0;
+        if (bal != 0) {                                                // the whole wave: `it` is uniform
+            int root = fg ? lab[p] : -1;
+            if ((unsigned)root >= (unsigned)total) root = -1;          // never with a workspace that label_into filled
+            const int x = root >= 0 ? head[root] : 0;
+            const int lead = __builtin_amdgcn_readfirstlane(__builtin_ctzll(bal));
+            const int root0 = __builtin_amdgcn_readlane(root, lead);
+            if (__ballot(fg && root != root0) == 0) {
+                const int x0 = __builtin_amdgcn_readlane(x, lead);
+                const int l0 = x0 < 0 ? nearest_seed(rec, -x0 - 1, P, r, c) : x0;
+                label = fg ? l0 : 0;
+            } else if (fg) {
+                label = x < 0 ? nearest_seed(rec, -x - 1, P, r, c) : x;
+            }
+        }
+        if (c < W) out[p] = label;
     }
 }
 
@@ -340,17 +484,22 @@ int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws
 }
 
 // scipy's number of every foreground root of ws.lab into its slot of ws.cnt (the areas there are spent); counts (or NULL): the
-// number of foreground components of every image
-int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st) {
+// number of foreground components of every image.  SEEDLESS (split, after the seed pass): only the roots without a seed, numbered
+// from S'_n + 1, and counts = S'_n + their number.
+template <bool SEEDLESS>
+int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, const Seeds& seeds, hipStream_t st) {
     const long long HW = (long long)H * W;
     const int B = (int)blocks_per_image(H, W);
-    hipLaunchKernelGGL(number_count_kernel, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, HW, ws.blk);
+    hipLaunchKernelGGL(number_count_kernel<SEEDLESS>, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, ws.cnt, HW, ws.blk);
     CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(number_scan_kernel, dim3(N), dim3(1024), 0, st, ws.blk, B, counts);
+    hipLaunchKernelGGL(number_scan_kernel, dim3(N), dim3(1024), 0, st, ws.blk, B, counts, seeds);
     CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(number_assign_kernel, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, HW, ws.blk, ws.cnt);
+    hipLaunchKernelGGL(number_assign_kernel<SEEDLESS>, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, HW, ws.blk, ws.cnt, seeds);
     CS_LAUNCH_CHECK();
     return CS_OK;
+}
+int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st) {
+    return number_into<false>(m, N, H, W, ws, counts, Seeds{nullptr, nullptr, nullptr, 0}, st);
 }
 
 int carve(const char* what, int N, int H, int W, int connectivity, const void* in, const void* out, void* workspace, size_t bytes, Ws* ws) {
@@ -424,19 +573,80 @@ extern "C" int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity,
     }
     const Tables t{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
     hipLaunchKernelGGL(measure_init_kernel, dim3(grid_for((long long)N * capacity)), dim3(256), 0, st, counts, N, capacity, t,
-                       intensity ? 1 : 0);
+                       intensity ? 1 : 0, (int32_t*)nullptr);
     CS_LAUNCH_CHECK();
     const long long waves = (long long)N * H * cs_ceil_div(W, 64);
     const dim3 grid(grid_for(waves * 64));
 #ifdef CS_AB_SWITCHES
     static const int per_pixel = cs_env_int_("CELLSEG_MEASURE_PER_PIXEL", 0);     // A/B flavour: what the in-wave run reduction buys
     if (per_pixel) {
-        hipLaunchKernelGGL(measure_kernel<false>, grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t);
+        hipLaunchKernelGGL((measure_kernel<false, false>), grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t,
+                           (int32_t*)nullptr);
         CS_LAUNCH_CHECK();
         return CS_OK;
     }
 #endif
-    hipLaunchKernelGGL(measure_kernel<true>, grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t);
+    hipLaunchKernelGGL((measure_kernel<true, false>), grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t,
+                       (int32_t*)nullptr);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_measure_labels(const int32_t* labels, const uint8_t* intensity, int N, int H, int W, int capacity,
+                                         int32_t* counts, int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax,
+                                         void* stream) {
+    CS_CHECK_ARG(labels && area && bbox && sums, "regions_measure_labels: NULL argument");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_measure_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(capacity >= 1, "regions_measure_labels: need capacity >= 1");
+    CS_CHECK_ARG((long long)N * capacity < (1LL << 31), "regions_measure_labels: need N capacity < 2^31");
+    CS_CHECK_ARG(!intensity || (isum && imax), "regions_measure_labels: an intensity image needs both intensity tables");
+    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(isum)) & 7),
+                 "regions_measure_labels: misaligned int64 table");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Tables t{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
+    const long long rows = (long long)N * capacity;
+    hipLaunchKernelGGL(measure_init_kernel, dim3(grid_for(rows)), dim3(256), 0, st, (const int32_t*)nullptr, N, capacity, t,
+                       intensity ? 1 : 0, counts);
+    CS_LAUNCH_CHECK();
+    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
+    hipLaunchKernelGGL((measure_kernel<true, true>), dim3(grid_for(waves * 64)), dim3(256), 0, st, (const uint8_t*)nullptr, intensity, N,
+                       H, W, labels, (const int32_t*)nullptr, capacity, t, counts);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(measure_empty_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+// workspace: that of cs_regions_workspace, then rec (int4 P)
+extern "C" size_t cs_regions_split_workspace(int N, int H, int W, int P) {
+    const size_t base = cs_regions_workspace(N, H, W);
+    if (base == 0 || P < 0) return 0;
+    return base + align16((size_t)P * sizeof(int4));
+}
+
+extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity, const int64_t* points, const int64_t* offsets,
+                                const int32_t* limits, int P, int32_t* labels, int32_t* counts, uint8_t* live, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_split", N, H, W, connectivity, mask, labels, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    CS_CHECK_ARG(counts, "regions_split: NULL counts");
+    CS_CHECK_ARG(P >= 0 && (P == 0 || (points && offsets && live)), "regions_split: P points need points, offsets and live");
+    CS_CHECK_ARG((long long)H * H + (long long)W * W < (1LL << 31), "regions_split: need H^2 + W^2 < 2^31");
+    CS_CHECK_ARG((long long)P + (long long)H * W < (1LL << 31), "regions_split: need P + H W < 2^31");
+    CS_CHECK_ARG(workspace_bytes >= cs_regions_split_workspace(N, H, W, P), "regions_split: workspace too small");
+    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7), "regions_split: misaligned int64 array");
+    int4* rec = reinterpret_cast<int4*>(reinterpret_cast<unsigned char*>(workspace) + cs_regions_workspace(N, H, W));
+    const Seeds seeds{reinterpret_cast<const long long*>(points), P > 0 ? reinterpret_cast<const long long*>(offsets) : nullptr, limits, P};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+    if (P > 0) {
+        hipLaunchKernelGGL(seed_kernel, dim3(grid_for(P)), dim3(256), 0, st, mask, N, H, W, seeds, ws.lab, ws.cnt, rec, live);
+        CS_LAUNCH_CHECK();
+    }
+    if ((rc = number_into<true>(mask, N, H, W, ws, counts, seeds, st)) != CS_OK) return rc;
+    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
+    hipLaunchKernelGGL(split_assign_kernel, dim3(grid_for(waves * 64)), dim3(256), 0, st, mask, N, H, W, ws.lab, ws.cnt, rec, P, labels);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

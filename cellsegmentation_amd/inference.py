@@ -303,17 +303,38 @@ def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=
     """One row per cell of a stitched uint8 [H, W] map such as ``SlideResult.mask``: foreground = ``mask_u8 > thr_u8``, cleaned by
     ``remove_small_regions``, measured with the map itself as the intensity -> the one-image ``RegionTable`` (device tensors)."""
     from . import regions as Rg
+    t, fg = _slide_foreground("measure_slide", mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity)
+    return Rg.measure(fg, intensity=t, connectivity=connectivity, max_regions=max_regions)
+
+
+def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity):
+    """a stitched uint8 [H, W] map -> (the map on the device, its cleaned foreground ``map > thr_u8`` as device bool)"""
+    from . import regions as Rg
     t = torch.from_numpy(np.ascontiguousarray(mask_u8)) if isinstance(mask_u8, np.ndarray) else mask_u8
     if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2:
-        raise TypeError("measure_slide: expected a uint8 [H, W] map")
+        raise TypeError(f"{what}: expected a uint8 [H, W] map")
     if isinstance(thr_u8, bool) or int(thr_u8) != thr_u8 or not 0 <= thr_u8 <= 255:
-        raise ValueError(f"measure_slide: thr_u8 must be an integer in [0, 255], got {thr_u8!r}")
+        raise ValueError(f"{what}: thr_u8 must be an integer in [0, 255], got {thr_u8!r}")
     if not t.is_cuda:
         t = t.to(Rg._device())
     t = t.contiguous()
     fg = t > int(thr_u8)
-    fg = Rg.remove_small_regions(fg, min_object_size, hole_area_threshold, connectivity, out=fg)
-    return Rg.measure(fg, intensity=t, connectivity=connectivity, max_regions=max_regions)
+    return t, Rg.remove_small_regions(fg, min_object_size, hole_area_threshold, connectivity, out=fg)
+
+
+def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None):
+    """One row per DETECTED cell of a ``SlideResult``: ``measure_slide``'s thresholding and clean-up of ``result.mask``, then
+    ``regions.split`` of the foreground at ``result.points`` and ``regions.measure_labels`` with the map as the intensity ->
+    ``(RegionTable, SplitResult)`` of one image.  Row k is ``result.points[k]`` (all zero where the point is not live: on the
+    background after the clean-up, or a second point on one pixel); the rows from ``len(result.points)`` on are cells that no
+    detection claimed.  ``max_regions`` as in ``measure_slide``: an int means no synchronisation."""
+    from . import regions as Rg
+    if not isinstance(result, SlideResult):
+        raise TypeError("measure_slide_cells: expected the SlideResult of detect_slide")
+    t, fg = _slide_foreground("measure_slide_cells", result.mask, thr_u8, min_object_size, hole_area_threshold, connectivity)
+    pts = np.asarray(result.points, np.int64).reshape(-1, 2)
+    parts = Rg.split(fg, pts, connectivity=connectivity)
+    return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts
 
 
 def _batch_points(points, n):

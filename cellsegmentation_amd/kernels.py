@@ -1190,6 +1190,19 @@ def _regions_args(mask, ws):
     return N, H, W, ws
 
 
+def _regions_outputs(what, want, given, device):
+    """name -> tensor for every (shape, dtype) of ``want``: the one given (checked: written in place), else a new one"""
+    t = {}
+    for name, (shape, dtype) in want.items():
+        x = given.get(name)
+        if x is None:
+            x = torch.empty(shape, dtype=dtype, device=device)
+        elif x.dtype != dtype or tuple(x.shape) != shape:
+            raise TypeError(f"{what}: {name} must be {dtype} of shape {shape}, got {x.dtype} {tuple(x.shape)}")
+        t[name] = x
+    return t
+
+
 def regions_label(mask, connectivity=1, out=None, ws=None):
     """uint8 [N,H,W] -> int32 [N,H,W] scipy.ndimage.label per image"""
     N, H, W, ws = _regions_args(mask, ws)
@@ -1225,19 +1238,71 @@ def regions_measure(mask, capacity, intensity=None, connectivity=1, numbered=Fal
             "sums": ((N, cap, 2), torch.int64)}
     if intensity is not None:
         want.update(isum=((N, cap), torch.int64), imax=((N, cap), torch.int32))
-    given = {"counts": counts, "area": area, "bbox": bbox, "sums": sums, "isum": isum, "imax": imax}
-    t = {}
-    for name, (shape, dtype) in want.items():
-        x = given[name]
-        if x is None:
-            x = torch.empty(shape, dtype=dtype, device=mask.device)
-        elif x.dtype != dtype or tuple(x.shape) != shape:
-            raise TypeError(f"regions_measure: {name} must be {dtype} of shape {shape}, got {x.dtype} {tuple(x.shape)}")
-        t[name] = x
+    t = _regions_outputs("regions_measure", want, {"counts": counts, "area": area, "bbox": bbox, "sums": sums, "isum": isum, "imax": imax},
+                         mask.device)
     _lib.check(_lib.load().cs_regions_measure(_p(mask), _p(intensity), N, H, W, int(connectivity), cap, int(bool(numbered)), _p(t["counts"]),
                                               _p(t["area"]), _p(t["bbox"]), _p(t["sums"]), _p(t.get("isum")), _p(t.get("imax")), _p(ws),
                                               ws.numel(), _stream()), "regions_measure")
     return t["counts"], t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
+
+
+def regions_split_workspace(N, H, W, P, device):
+    """the caller-owned scratch of one cs_regions_split call on [N,H,W] with a points buffer of P rows"""
+    ws_bytes = _lib.load().cs_regions_split_workspace(N, H, W, int(P))
+    if ws_bytes == 0:
+        raise ValueError(f"regions_split: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels and P >= 0 points, got {(N, H, W, P)}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+
+
+def regions_split(mask, points, offsets, limits=None, connectivity=1, labels=None, counts=None, live=None, ws=None):
+    """uint8 [N,H,W], points int64 [P,2] (row, col), offsets int64 [N+1], limits int32 [N] | None -> (labels int32 [N,H,W],
+    counts int32 [N], live uint8 [P]): every foreground pixel labelled 1 + the index of the nearest live seed of its own component,
+    components without one numbered after the image's seeds (cs_regions_split in include/cellseg_hip.h)"""
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise TypeError("regions kernels read uint8 [N,H,W] masks")
+    N, H, W = mask.shape
+    if points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2:
+        raise TypeError("regions_split: points must be int64 [P, 2]")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (N + 1,):
+        raise TypeError(f"regions_split: offsets must be int64 [{N + 1}]")
+    if limits is not None and (limits.dtype != torch.int32 or tuple(limits.shape) != (N,)):
+        raise TypeError(f"regions_split: limits must be int32 [{N}]")
+    P = int(points.shape[0])
+    if P + H * W >= 1 << 31:
+        raise ValueError(f"regions_split: {P} points and {H}x{W} pixels do not leave room for int32 labels")
+    want = {"labels": ((N, H, W), torch.int32), "counts": ((N,), torch.int32), "live": ((P,), torch.uint8)}
+    t = _regions_outputs("regions_split", want, {"labels": labels, "counts": counts, "live": live}, mask.device)
+    if ws is None:
+        ws = regions_split_workspace(N, H, W, P, mask.device)
+    none_if_empty = lambda x: _p(x) if P else None  # noqa: E731  (an empty tensor has no storage to point at)
+    _lib.check(_lib.load().cs_regions_split(_p(mask), N, H, W, int(connectivity), none_if_empty(points), _p(offsets), _p(limits), P,
+                                            _p(t["labels"]), _p(t["counts"]), none_if_empty(t["live"]), _p(ws), ws.numel(), _stream()),
+               "regions_split")
+    return t["labels"], t["counts"], t["live"]
+
+
+def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=None, bbox=None, sums=None, isum=None, imax=None,
+                           want_counts=True):
+    """int32 label image [N,H,W] (and uint8 intensity [N,H,W] or None) -> the tuple of regions_measure with row k = label k + 1; a
+    label without a pixel leaves an all-zero row.  counts is written with the largest label of every image, or left out
+    (``want_counts=False`` -> None) by a caller that has the counts already."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_measure_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    cap = int(capacity)
+    if intensity is not None and (intensity.dtype != torch.uint8 or tuple(intensity.shape) != (N, H, W)):
+        raise TypeError("regions_measure_labels: the intensity image is uint8 of the label image's shape")
+    want = {"area": ((N, cap), torch.int32), "bbox": ((N, cap, 4), torch.int32), "sums": ((N, cap, 2), torch.int64)}
+    if want_counts:
+        want["counts"] = ((N,), torch.int32)
+    if intensity is not None:
+        want.update(isum=((N, cap), torch.int64), imax=((N, cap), torch.int32))
+    t = _regions_outputs("regions_measure_labels", want,
+                         {"counts": counts, "area": area, "bbox": bbox, "sums": sums, "isum": isum, "imax": imax}, labels.device)
+    _lib.check(_lib.load().cs_regions_measure_labels(_p(labels), _p(intensity), N, H, W, cap, _p(t.get("counts")), _p(t["area"]),
+                                                     _p(t["bbox"]), _p(t["sums"]), _p(t.get("isum")), _p(t.get("imax")), _stream()),
+               "regions_measure_labels")
+    return t.get("counts"), t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
 
 
 def regions_areas(mask, connectivity=1, out=None, ws=None):

@@ -23,6 +23,10 @@ shape.  A call enqueues a number of launches fixed by the shape and never synchr
 centroid, intensity sum / mean / maximum), pinned to ``scipy.ndimage`` (sum, mean, maximum, center_of_mass, find_objects;
 tests/golden/props_vectors.npz).  With a fixed ``max_regions`` it keeps the contract above; with ``max_regions=None`` it reads the
 largest component count back once to size the tables.
+
+``split`` cuts the components at seed points (one per cell, ``detect.detect_points``): every foreground pixel goes to the nearest
+seed of its own component and label k + 1 is point k, so that ``measure_labels`` -- the same tables for a label image -- gives one
+row per detection.  Exact integer rules, stated once in ``split``'s docstring and restated in numpy by tests/split_ref.py.
 """
 import dataclasses
 import typing
@@ -215,8 +219,7 @@ def measure(m, intensity=None, connectivity=1, max_regions=None):
     nothing synchronises and the call can be captured into a graph.  ``max_regions=None`` numbers first, reads the largest count
     back (the one synchronisation) and measures with exactly that capacity (1 when there is no component)."""
     conn = _check_connectivity(connectivity)
-    if max_regions is not None and (isinstance(max_regions, bool) or int(max_regions) != max_regions or max_regions < 1):
-        raise ValueError(f"max_regions must be a positive integer or None, got {max_regions!r}")
+    _check_max_regions(max_regions)
     v = None if intensity is None else _as_intensity(intensity, getattr(m, "shape", ()))
     t, two_d = _as_masks(m, "measure")
     N, H, W = t.shape
@@ -249,3 +252,158 @@ def measure(m, intensity=None, connectivity=1, max_regions=None):
         K.regions_measure(t[a:b], cap, None if v is None else v[a:b], conn, numbered, counts[a:b], area[a:b], bbox[a:b], sums[a:b],
                           None if v is None else isum[a:b], None if v is None else imax[a:b], ws=workspace(b - a))
     return RegionTable(counts, cap, area, bbox, sums, isum, imax)
+
+
+@dataclasses.dataclass
+class SplitResult:
+    """``split`` of N masks, device tensors: ``labels`` int32 of the mask's shape (0 = background; label k + 1 = seed k of the
+    image; labels above ``n_seeds[n]`` = components that hold no live seed); ``counts`` int32 [N] = n_seeds + the number of such
+    components, i.e. the rows ``measure_labels`` fills; ``n_seeds`` int32 [N] = the points of image n within its limit; ``live``
+    bool [P], one per row of the points buffer: the point is a seed that lies inside its image on a foreground pixel."""
+    labels: torch.Tensor
+    counts: torch.Tensor
+    n_seeds: torch.Tensor
+    live: torch.Tensor
+
+
+def _seeds(points, offsets, limits, N, H, W):
+    """the seed arguments of ``split`` -> (points [P, 2], offsets [N + 1], limits [N] or None), each a host numpy array or a device
+    tensor as given; argument errors only, no device work.  Host points are checked against the image, device points cannot be."""
+    from . import score as S
+    if isinstance(points, (list, tuple)) and offsets is None:
+        if len(points) != N:
+            raise ValueError(f"split: {N} images but {len(points)} point arrays")
+        pts, off, on_device = *S.ragged(points), False
+    else:
+        pts, is_torch = S._points(points, "points")
+        on_device = is_torch and pts.is_cuda
+        if is_torch and not on_device:
+            pts = pts.numpy()
+        if offsets is None:
+            if N != 1:
+                raise ValueError(f"split: {N} images: pass one point array per image, or offsets")
+            offsets = np.asarray([0, pts.shape[0]], np.int64)
+        off_host, off_dev = S._offsets(offsets, pts.shape[0], N, "offsets")
+        off = off_dev if off_host is None else off_host
+    if pts.shape[0] + H * W > _MAX_PIXELS:
+        raise ValueError(f"split: {pts.shape[0]} points and {H}x{W} pixels do not leave room for int32 labels")
+    if not on_device and pts.size:
+        if int(pts[:, 0].min()) < 0 or int(pts[:, 0].max()) >= H or int(pts[:, 1].min()) < 0 or int(pts[:, 1].max()) >= W:
+            raise ValueError(f"split: a point lies outside the {H}x{W} image")
+    return pts, off, S._limits(limits, N)
+
+
+def split(m, points, offsets=None, limits=None, connectivity=1):
+    """Split the connected components of boolean masks at seed points -> ``SplitResult``.
+
+    ``m``: bool [H, W] or [N, H, W] with ``H^2 + W^2 < 2^31``.  ``points``: integer (row, col) pairs -- one ``[k, 2]`` array for a
+    2-D mask, a list of N per-image arrays, or one concatenated ``[P, 2]`` array with ``offsets`` [N + 1] (image n owns
+    ``points[offsets[n]:offsets[n + 1]]``; with device offsets the buffer may be longer than ``offsets[-1]``: this is the layout of
+    ``DetectResult.device_points`` / ``device_offsets``).  ``limits``: None, one count or one per image, Python's ``[:c]`` of every
+    image's points as in ``score.score_points``: the S' points it keeps are the seeds.
+
+    * Seed k (0-based within its image) is live iff it lies inside the image and on a foreground pixel.  Dead seeds own nothing and
+      are reported in ``live``, not raised: device points cannot be checked without a synchronisation.  Host points outside the
+      image raise ``ValueError`` before any device work.
+    * A foreground pixel (r, c) of a component that holds a live seed gets label ``1 + k``, k minimising ``((r - r_k)^2 +
+      (c - c_k)^2, k)`` over the live seeds OF THAT COMPONENT: a nearer seed of another component never wins, ties go to the lower
+      index, and of two seeds on one pixel the lower owns everything (the other's cell is empty).
+    * The pixels of a component without a live seed get ``S' + 1 + j``, j = the component's rank among the image's seedless
+      components in ``label``'s order; the background is 0; ``counts = S' +`` the number of seedless components.
+
+    Without points the labels are ``label(m)`` bit for bit.  All of it is integer work: exact and independent of launch order, a
+    fixed number of launches, no synchronisation.  This is a Euclidean partition inside each component, NOT a watershed: a cell of
+    a strongly non-convex clump may come out in two pieces, and no parity with any watershed implementation is claimed.  Cost: the
+    labelling plus (foreground pixels) x (live seeds of their component) distance evaluations."""
+    from . import detect as D
+    conn = _check_connectivity(connectivity)
+    shape = tuple(getattr(m, "shape", ()))
+    if len(shape) in (2, 3) and min(shape) > 0:
+        D._check_dt_shape(shape)                                         # before the mask is copied anywhere
+        pts, off, lim = _seeds(points, offsets, limits, 1 if len(shape) == 2 else shape[0], shape[-2], shape[-1])
+    t, two_d = _as_masks(m, "split")
+    N, H, W = t.shape
+    dev = t.device
+
+    def up(x, dtype):
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return x.to(device=dev, dtype=dtype).contiguous()
+
+    pts, off = up(pts, torch.int64), up(off, torch.int64)
+    lim = None if lim is None else up(lim, torch.int32)
+    P = pts.shape[0]
+    n_seeds = (off[1:] - off[:-1]).clamp(0, P)                            # S' as the kernel forms it
+    if lim is not None:
+        n_seeds = torch.where(lim >= 0, torch.minimum(lim.to(torch.int64), n_seeds), (n_seeds + lim).clamp(min=0))
+    labels = _int32_like(t)
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    live = None
+    for a, b in _chunks(t):
+        # every call looks at the whole points buffer: the points of the other chunks' images come out dead in this one
+        part = torch.empty((P,), dtype=torch.uint8, device=dev)
+        K.regions_split(t[a:b], pts, off[a:b + 1], None if lim is None else lim[a:b], conn, labels=labels[a:b], counts=counts[a:b], live=part)
+        live = part if live is None else live | part
+    return SplitResult(labels[0] if two_d else labels, counts, n_seeds.to(torch.int32), live.view(torch.bool))
+
+
+def _check_max_regions(max_regions):
+    if max_regions is not None and (isinstance(max_regions, bool) or int(max_regions) != max_regions or max_regions < 1):
+        raise ValueError(f"max_regions must be a positive integer or None, got {max_regions!r}")
+
+
+def measure_labels(labels, intensity=None, max_regions=None, counts=None):
+    """``measure`` for a label image: int32 [H, W] or [N, H, W] (numpy or torch; 0 and below = background) -> ``RegionTable`` whose
+    row k belongs to label k + 1.  A label that owns no pixel (an empty cell of ``split``) leaves an all-zero row, its bounding box
+    (0, 0, 0, 0) included: the row where ``scipy.ndimage.find_objects`` gives ``None``.  ``counts``: int32 [N], the labels in use per
+    image (``SplitResult.counts``); None = the largest label of every image, found on the device.  ``max_regions=int`` fixes the
+    rows per image (larger labels are counted, not measured): nothing synchronises and the call can be captured into a graph.
+    ``max_regions=None`` reads the largest count back (the one synchronisation; without ``counts`` after a pass that finds them)
+    and measures with exactly that capacity (1 when there is no label).  Only int32 is taken; boolean masks go to ``measure``."""
+    _check_max_regions(max_regions)
+    t = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
+    if not torch.is_tensor(t):
+        raise TypeError("measure_labels: expected a numpy array or a torch tensor")
+    if t.dtype != torch.int32:
+        raise TypeError(f"measure_labels: expected an int32 label image, got {t.dtype} (boolean masks go to measure)")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"measure_labels: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"measure_labels: empty label image of shape {tuple(t.shape)}")
+    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
+        raise ValueError(f"measure_labels: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
+    v = None if intensity is None else _as_intensity(intensity, t.shape)
+    n_images = 1 if t.dim() == 2 else t.shape[0]
+    if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (n_images,)):
+        raise TypeError(f"measure_labels: counts must be an int32 tensor of shape ({n_images},)")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if not t.is_cuda:
+        t = t.to(_device())
+    t = t.contiguous()
+    N, H, W = t.shape
+    dev = t.device
+    if v is not None:
+        v = v.to(dev).contiguous().view(N, H, W)
+    chunks = _chunks(t)
+    own_counts = counts is None
+    if own_counts:
+        counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    else:
+        counts = counts.to(dev).contiguous()
+
+    def run(cap, want_counts):
+        area = torch.empty((N, cap), dtype=torch.int32, device=dev)
+        bbox = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
+        sums = torch.empty((N, cap, 2), dtype=torch.int64, device=dev)
+        isum = None if v is None else torch.empty((N, cap), dtype=torch.int64, device=dev)
+        imax = None if v is None else torch.empty((N, cap), dtype=torch.int32, device=dev)
+        for a, b in chunks:
+            K.regions_measure_labels(t[a:b], cap, None if v is None else v[a:b], counts[a:b] if want_counts else None, area[a:b], bbox[a:b],
+                                     sums[a:b], None if v is None else isum[a:b], None if v is None else imax[a:b], want_counts=want_counts)
+        return RegionTable(counts, cap, area, bbox, sums, isum, imax)
+
+    if max_regions is not None:
+        return run(int(max_regions), own_counts)
+    if own_counts:
+        run(1, True)                                                     # the pass that finds the largest labels
+    return run(max(1, int(counts.max())), False)                         # the one synchronisation

@@ -619,6 +619,36 @@ int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity, int N, int
                        int numbered, int32_t* counts, int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- touching cells split at detected points, and the tables of a label image (csrc/regions.hip) ---------------------------
+ * Masks, sizes, connectivity and the launch contract are those of the section above; in addition H^2 + W^2 < 2^31 (every squared
+ * distance fits int32) and P + H W < 2^31.
+ * cs_regions_split         : points int64 [P][2] = (row, col) with offsets int64 [N + 1] are out_pts / out_off of cs_detect_cluster as
+ *                            they are: image n owns points[offsets[n] .. offsets[n + 1]), and points may hold more rows than
+ *                            offsets[N].  limits (int32 [N], or NULL) applies Python's slice [:c] to image n's points as hat_limit of
+ *                            cs_score_points does; the S'_n points it keeps are the seeds.  Seed k (0-based within its image) is live
+ *                            when it lies inside the image on a foreground pixel; live uint8 [P] reports that for every row of
+ *                            points (0 for the rows that are no seed of any image), and a dead seed owns nothing.  labels int32
+ *                            [N][H][W]: 0 on the background; 1 + k on a foreground pixel whose component holds a live seed, k being
+ *                            the live seed OF THAT COMPONENT that minimises (dr^2 + dc^2, k) -- a nearer seed in another component
+ *                            does not count, ties go to the lower index; S'_n + 1 + j on the pixels of a component without a live
+ *                            seed, j = its rank among such components of the image in cs_regions_label's order.  counts int32 [N] =
+ *                            S'_n + the number of components without a live seed.  With P = 0 (points, offsets, live may be NULL)
+ *                            labels are those of cs_regions_label.  Integer comparisons only: bit-exact and independent of launch
+ *                            order.  A Euclidean partition inside each component, not a watershed.  Cost: the labelling, plus
+ *                            (foreground pixels) x (live seeds of their component) distance evaluations.  workspace: 16-byte
+ *                            aligned, >= cs_regions_split_workspace(N, H, W, P) bytes (0 for sizes a call would refuse).
+ * cs_regions_measure_labels: the tables of cs_regions_measure for a label image labels int32 [N][H][W] (<= 0 = background): row k of
+ *                            image n belongs to label k + 1, for k < capacity (>= 1, N capacity < 2^31); larger labels are measured
+ *                            nowhere.  A row whose label owns no pixel is all zero, bbox (0, 0, 0, 0) included (scipy's find_objects
+ *                            gives None there).  counts (int32 [N], or NULL) is WRITTEN: the largest label of every image, also
+ *                            above capacity; a caller that knows the counts (cs_regions_split's) passes NULL.  No workspace. */
+size_t cs_regions_split_workspace(int N, int H, int W, int P);
+int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity, const int64_t* points, const int64_t* offsets,
+                     const int32_t* limits, int P, int32_t* labels, int32_t* counts, uint8_t* live, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cs_regions_measure_labels(const int32_t* labels, const uint8_t* intensity, int N, int H, int W, int capacity, int32_t* counts,
+                              int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax, void* stream);
+
 /* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
  * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of
  * cs_detect_cluster as they are; gt int32 [G][2] with gt_off int64 [N + 1] are the annotations, in the same coordinate convention.

@@ -10,6 +10,14 @@ itself once more in a child process on the A/B flavour of the library (CELLSEG_L
 where every foreground pixel issues its own atomics: what the in-wave run reduction buys.
 
     python tools/regions_microbench.py --measure [--reps 5] [--host-maps 8] [--json PATH]
+
+--split times ``regions.split`` + ``regions.measure_labels`` next to ``regions.label`` + ``regions.measure`` on the same two mask
+sets, with about 1 and about 10 seeds in every component, and on all-foreground masks of the same shapes (one component, 40 seeds
+per 299^2 of area: the worst case of the seed walk).  It reports the distance evaluations of every case -- (foreground pixels) x
+(live seeds of their component), the cost bound of the assign pass -- and checks the first ``--host-maps`` maps against
+tests/split_ref.py (scipy).
+
+    python tools/regions_microbench.py --split [--reps 5] [--host-maps 2] [--json PATH]
 """
 import argparse
 import json
@@ -120,14 +128,92 @@ def measure_main(args):
     return res
 
 
+def seeds_in_components(lab, per_component, seed):
+    """lab int32 [N, H, W] -> (points int64 [P, 2], offsets [N + 1]): per_component random pixels of every component"""
+    rng = np.random.RandomState(seed)
+    pts, off = [], [0]
+    W = lab.shape[2]
+    for x in lab:
+        flat = np.flatnonzero(x)
+        order = flat[np.argsort(x.ravel()[flat], kind="stable")]           # the pixels of component 1, then of 2, ...
+        size = np.bincount(x.ravel()[flat])[1:]
+        start = np.concatenate([[0], np.cumsum(size)[:-1]])
+        pick = (start[:, None] + (rng.rand(len(size), per_component) * size[:, None]).astype(np.int64)).ravel()
+        pts.append(np.stack([order[pick] // W, order[pick] % W], axis=1))
+        off.append(off[-1] + len(pick))
+    return np.concatenate(pts).astype(np.int64).reshape(-1, 2), np.asarray(off, np.int64)
+
+
+def split_case(name, masks, pts, off, reps, host_maps, dev):
+    import split_ref as S
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    v = np.random.RandomState(3).randint(0, 256, size=masks.shape).astype(np.uint8)
+    dv = torch.from_numpy(v).to(dev)
+    parts = G.split(d, dp, doff)
+    cap = max(1, int(parts.counts.max()))                                  # sized once, outside the timed region
+    components = G.measure(d, max_regions=cap)
+    cap_mask = max(1, int(components.counts.max()))
+    label_ms, _ = time_dev(lambda: G.label(d), reps)
+    measure_ms, _ = time_dev(lambda: G.measure(d, intensity=dv, max_regions=cap_mask), reps)
+    split_ms, _ = time_dev(lambda: G.split(d, dp, doff), reps)
+    tables_ms, _ = time_dev(lambda: G.measure_labels(parts.labels, intensity=dv, max_regions=cap, counts=parts.counts), reps)
+
+    def both():
+        p = G.split(d, dp, doff)
+        return G.measure_labels(p.labels, intensity=dv, max_regions=cap, counts=p.counts)
+
+    both_ms, ts = time_dev(both, reps)
+    # the cost bound: every foreground pixel looks at every live seed of its component
+    root = G.label(d).to(torch.int64) + torch.arange(len(masks), device=dev)[:, None, None] * (int(components.counts.max()) + 1)
+    live = parts.live.nonzero()[:, 0]
+    image = torch.bucketize(live, doff[1:], right=True)
+    seeds_of = torch.bincount(root[image, dp[live, 0], dp[live, 1]], minlength=int(root.max()) + 1)
+    evaluations = int(seeds_of[root[d]].sum())
+    res = {"label_ms": label_ms, "measure_ms": measure_ms, "label_plus_measure_ms": label_ms + measure_ms, "split_ms": split_ms,
+           "measure_labels_ms": tables_ms, "split_plus_measure_labels_ms": both_ms, "split_plus_measure_labels_ms_all": ts,
+           "points": int(len(pts)), "live_seeds": int(parts.live.sum()), "rows_max": cap, "components_max": cap_mask,
+           "foreground_pixels": int(masks.sum()), "distance_evaluations": evaluations}
+    t = both()
+    ok = True
+    if evaluations / len(masks) > 2e8:                                     # the brute-force reference would take hours
+        host_maps = 0
+    for i in range(min(host_maps, len(masks))):
+        ref = S.split(masks[i], pts[off[i]:off[i + 1]])
+        ok &= bool(np.array_equal(parts.labels[i].cpu().numpy(), ref["labels"])) and int(parts.counts[i]) == int(ref["counts"][0])
+        tab = S.tables(ref["labels"], v[i], cap, ref["counts"])
+        for key in ("area", "bbox", "sum_rc", "intensity_sum", "intensity_max"):
+            ok &= bool(np.array_equal(getattr(t, key)[i].cpu().numpy(), tab[key][0]))
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
+def split_main(args):
+    dev = torch.device("cuda:0")
+    res = {}
+    for name, masks in mask_sets():
+        lab = G.label(torch.from_numpy(masks).to(dev)).cpu().numpy()
+        for per in (1, 10):
+            pts, off = seeds_in_components(lab, per, seed=per)
+            res[f"{name}.seeds{per}"] = split_case(f"{name}.seeds{per}", masks, pts, off, args.reps, args.host_maps, dev)
+        full = np.ones_like(masks)
+        n = max(1, int(round(40 * masks.shape[1] * masks.shape[2] / 299.0 ** 2)))
+        pts, off = seeds_in_components(full.astype(np.int32), n, seed=40)
+        res[f"{name}.all_foreground"] = split_case(f"{name}.all_foreground", full, pts, off, args.reps, min(args.host_maps, 1), dev)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-maps", type=int, default=128, help="maps of the batch also run (and checked) on the host")
     ap.add_argument("--json", default=None, help="also write the results to this file")
     ap.add_argument("--measure", action="store_true", help="time regions.measure next to regions.label instead")
+    ap.add_argument("--split", action="store_true", help="time regions.split + measure_labels next to label + measure instead")
     args = ap.parse_args()
-    if args.measure:
+    if args.split:
+        res = split_main(args)
+    elif args.measure:
         res = measure_main(args)
     else:
         dev = torch.device("cuda:0")
