@@ -12,6 +12,9 @@
 //   measure   one table row per numbered component (area, bounding box, row / column / intensity sums, intensity maximum): integer
 //             atomics, one set per horizontal run of foreground pixels within a wave's 64 columns of one image row; the same pass
 //             measures a label image (one row per label, a run = equal neighbouring labels)
+//   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
+//             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
+//             and an exact 64-bit integer test per pred label
 //   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
 //             component without a seed is numbered after the seeds:
 //               seeds   one thread per point hangs the live seeds on a chain at their component's root
@@ -280,6 +283,16 @@ __global__ __launch_bounds__(256) void measure_empty_rows_kernel(long long rows,
     }
 }
 
+// The runs of a wave's 64 lanes.  live: the lanes that belong to a run at all; breaks: live lanes that start a new run although
+// the lane to their left is live too.  A run also starts where the lane to the left is not live, and at lane 0.  Returns whether
+// this lane is the head of its run; len = the lanes from this one to its run's last (1 on a lane that is not live).
+__device__ __forceinline__ bool run_of(unsigned long long live, unsigned long long breaks, int lane, int& len) {
+    const unsigned long long start = (live & ~(live << 1)) | breaks;
+    const unsigned long long rest = ((~live | start) >> lane) >> 1;    // bit i = lane + 1 + i is no part of this lane's run
+    len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
+    return (start >> lane) & 1;
+}
+
 // A wave takes 64 consecutive columns of ONE image row (the walk is over (n, r, 64-column segment), so no wave straddles a row
 // end).  Horizontal neighbours in the foreground are one component, so a maximal run of foreground lanes has one table row: its
 // head lane looks the number up once and issues one set of atomics for the whole run -- length, closed-form column sum, and the
@@ -310,11 +323,8 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
         int len = 1;
         bool head = fg;
         if (REDUCE) {
-            unsigned long long start = bal & ~(bal << 1);              // the lane to the left is background, or this is lane 0
-            if (LABELS) start |= __ballot(fg && l != __shfl_up(l, 1)); // ... or carries another label (lane 0 gets its own back)
-            const unsigned long long rest = ((~bal | start) >> lane) >> 1;   // bit i = lane + 1 + i is no part of this lane's run
-            len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;        // lanes from this one to its run's last
-            head = (start >> lane) & 1;
+            // LABELS: a run also breaks where the lane carries another label than its left neighbour (lane 0 gets its own back)
+            head = run_of(bal, LABELS ? __ballot(fg && l != __shfl_up(l, 1)) : 0ull, lane, len);
             if (v) {
                 const int last = fg ? lane + len - 1 : lane;
 #pragma unroll
@@ -350,6 +360,117 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
             __hip_atomic_fetch_add(t.isum + q, (long long)s, __ATOMIC_RELAXED, kGlobal);
             raise_to(t.imax + q, mx);
         }
+    }
+}
+
+// ---- label image against label image: object matches at IoU > 1/2 -----------------------------------------------------------------
+// pred label p and truth label g match iff 2 I(p, g) > Ap + At - I.  Such a g covers more than half of p's pixels, so bit b of g is
+// set exactly where more than half of p's pixels carry a truth label with bit b set: B = bit_length(cap_truth) counters per pred
+// label spell the only possible partner, one more pass counts its intersection, and the test itself is made on exact integers.
+struct Match {
+    int32_t* area_pred;    // [N][cap_pred]
+    int32_t* area_truth;   // [N][cap_truth]
+    int32_t* match;        // [N][cap_pred]   the truth label matched, 0 = none
+    int32_t* inter;        // [N][cap_pred]   I(p, match)
+    int32_t* match_truth;  // [N][cap_truth]  the pred label matched, 0 = none
+    int32_t* vote;         // [N][cap_pred][B]
+    int32_t* cand;         // [N][cap_pred]
+    int32_t* maxp;         // [N] or NULL: the largest pred label
+    int32_t* maxt;         // [N] or NULL: the largest truth label
+    int cap_pred, cap_truth, B;
+};
+
+__global__ __launch_bounds__(256) void match_init_kernel(int N, Match t) {
+    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth, nv = np * t.B;
+    const long long all = nv > nt ? nv : nt;                           // >= np >= N
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        if (i < nv) t.vote[i] = 0;
+        if (i < np) {
+            t.area_pred[i] = 0;
+            t.inter[i] = 0;
+        }
+        if (i < nt) {
+            t.area_truth[i] = 0;
+            t.match_truth[i] = 0;
+        }
+        if (i < N) {
+            if (t.maxp) t.maxp[i] = 0;
+            if (t.maxt) t.maxt[i] = 0;
+        }
+    }
+}
+
+// The walk of measure_kernel over two label images at once.  A run is a stretch of lanes on which both labels are constant and at
+// least one is positive; its head lane issues the atomics for the whole run.  A label above its side's capacity counts towards
+// that side's maximum and is background otherwise.  VOTE: the areas of both sides and, for every set bit b of the truth label,
+// vote[p][b] += len.  Otherwise: inter[p] += len on the runs whose truth label is p's candidate.
+template <bool VOTE>
+__global__ __launch_bounds__(256) void match_walk_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int N, int H,
+                                                         int W, Match t) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned segs = (unsigned)(W + 63) >> 6;
+    const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
+    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
+        const unsigned row = (unsigned)it / segs;                      // n H + r
+        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
+        const int n = (int)(row / (unsigned)H);
+        const long long px = (long long)row * W + c;
+        const int p = c < W ? max(pred[px], 0) : 0, g = c < W ? max(truth[px], 0) : 0;
+        const bool live = (p | g) != 0;
+        const unsigned long long bal = __ballot(live);
+        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
+        const int pl = __shfl_up(p, 1), gl = __shfl_up(g, 1);          // (lane 0 gets its own back)
+        int len;
+        const bool head = run_of(bal, __ballot(live && (p != pl || g != gl)), lane, len);
+        if (!head) continue;
+        if (VOTE) {
+            if (t.maxp && p) raise_to(t.maxp + n, p);
+            if (t.maxt && g) raise_to(t.maxt + n, g);
+        }
+        const int pc = p <= t.cap_pred ? p : 0, gc = g <= t.cap_truth ? g : 0;
+        const long long q = (long long)n * t.cap_pred + pc - 1;        // p's row, where pc > 0
+        if (VOTE) {
+            if (gc) __hip_atomic_fetch_add(t.area_truth + (long long)n * t.cap_truth + gc - 1, len, __ATOMIC_RELAXED, kGlobal);
+            if (!pc) continue;
+            __hip_atomic_fetch_add(t.area_pred + q, len, __ATOMIC_RELAXED, kGlobal);
+            for (unsigned bits = (unsigned)gc; bits; bits &= bits - 1)   // gc <= cap_truth < 2^B: every set bit is below B
+                __hip_atomic_fetch_add(t.vote + q * t.B + __builtin_ctz(bits), len, __ATOMIC_RELAXED, kGlobal);
+        } else if (pc && gc && t.cand[q] == gc) {
+            __hip_atomic_fetch_add(t.inter + q, len, __ATOMIC_RELAXED, kGlobal);
+        }
+    }
+}
+
+// One thread per pred label: the truth label spelled by the bits that more than half of the label's pixels voted for.  Without a
+// majority partner the votes can spell any number, one above cap_truth included: that is no candidate.
+__global__ __launch_bounds__(256) void match_candidate_kernel(long long rows, Match t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        const long long area = t.area_pred[i];
+        int g = 0;
+        for (int b = 0; b < t.B; ++b)
+            if (2 * (long long)t.vote[i * t.B + b] > area) g |= 1 << b;
+        t.cand[i] = g <= t.cap_truth ? g : 0;
+    }
+}
+
+// One thread per pred label: the test itself, in 64-bit integers.  A truth label is matched by at most one pred label (two would
+// each hold more than half of its pixels), so the stores into match_truth never meet.
+__global__ __launch_bounds__(256) void match_decide_kernel(long long rows, Match t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        const int g = t.cand[i];
+        const long long n = i / t.cap_pred;
+        const long long in = t.inter[i];
+        bool ok = false;
+        if (g > 0) {
+            const long long uni = (long long)t.area_pred[i] + (long long)t.area_truth[n * t.cap_truth + g - 1] - in;
+            ok = 2 * in > uni;
+        }
+        t.match[i] = ok ? g : 0;
+        if (ok)
+            t.match_truth[n * t.cap_truth + g - 1] = (int)(i - n * t.cap_pred) + 1;
+        else
+            t.inter[i] = 0;
     }
 }
 
@@ -462,6 +583,17 @@ struct Ws {
 };
 
 bool sizes_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31); }
+
+// the vote counters per pred label: one per bit of the largest truth label
+inline int vote_bits(int cap_truth) {
+    int b = 1;
+    while (b < 31 && (cap_truth >> b)) ++b;
+    return b;
+}
+bool match_sizes_ok(int N, int cap_pred, int cap_truth) {
+    return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && (long long)N * cap_pred * vote_bits(cap_truth) < (1LL << 31) &&
+           (long long)N * cap_truth < (1LL << 31);
+}
 
 // labels and areas of `m` into ws.lab / ws.cnt (cnt holds the area at every root's slot)
 int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws& ws, hipStream_t st) {
@@ -613,6 +745,45 @@ extern "C" int cs_regions_measure_labels(const int32_t* labels, const uint8_t* i
                        H, W, labels, (const int32_t*)nullptr, capacity, t, counts);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(measure_empty_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+// workspace: vote (int32 N cap_pred B, B = max(1, bit_length(cap_truth))), cand (int32 N cap_pred)
+extern "C" size_t cs_regions_match_workspace(int N, int cap_pred, int cap_truth) {
+    if (!match_sizes_ok(N, cap_pred, cap_truth)) return 0;
+    const size_t rows = (size_t)N * cap_pred;
+    return align16(rows * vote_bits(cap_truth) * 4) + align16(rows * 4);
+}
+
+extern "C" int cs_regions_match_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                                       int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred, int32_t* area_truth,
+                                       int32_t* match, int32_t* inter, int32_t* match_truth, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    CS_CHECK_ARG(pred && truth && area_pred && area_truth && match && inter && match_truth && workspace,
+                 "regions_match_labels: NULL argument");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_match_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(match_sizes_ok(N, cap_pred, cap_truth),
+                 "regions_match_labels: need capacities >= 1, N cap_pred bit_length(cap_truth) < 2^31 and N cap_truth < 2^31");
+    CS_CHECK_ARG(workspace_bytes >= cs_regions_match_workspace(N, cap_pred, cap_truth), "regions_match_labels: workspace too small");
+    CS_CHECK_ARG(!(reinterpret_cast<uintptr_t>(workspace) & 15), "regions_match_labels: misaligned workspace");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int B = vote_bits(cap_truth);
+    const long long rows = (long long)N * cap_pred;
+    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+    const Match t{area_pred, area_truth, match, inter, match_truth, reinterpret_cast<int32_t*>(w),
+                  reinterpret_cast<int32_t*>(w + align16((size_t)rows * B * 4)), counts_pred, counts_truth, cap_pred, cap_truth, B};
+    const long long cells = rows * B > (long long)N * cap_truth ? rows * B : (long long)N * cap_truth;
+    hipLaunchKernelGGL(match_init_kernel, dim3(grid_for(cells)), dim3(256), 0, st, N, t);
+    CS_LAUNCH_CHECK();
+    const dim3 walk(grid_for((long long)N * H * cs_ceil_div(W, 64) * 64));
+    hipLaunchKernelGGL(match_walk_kernel<true>, walk, dim3(256), 0, st, pred, truth, N, H, W, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_candidate_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_walk_kernel<false>, walk, dim3(256), 0, st, pred, truth, N, H, W, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_decide_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -253,17 +253,20 @@ def detect_slides(slides, model, device=None, **kwargs):
         yield detect_slide(image_u8, model, device, **kwargs)
 
 
-def _cleaned_batch(model, x, threshold, mo, ho, reg_limit):
-    """test_seg.py:515-527 for one batch on the device -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W])"""
+def _cleaned_batch(model, x, threshold, mo, ho, reg_limit, with_counts=False):
+    """test_seg.py:515-527 for one batch on the device -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W]); with_counts:
+    also the image-mode counts rint(reg) as a device fp32 [n] tensor (None without reg_limit)"""
     from . import regions as Rg
     probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+    counts = None
     if reg_limit:
         model.setmode("image")
         counts = torch.round(model(x)[1].detach()[:, 0].float())
         model.setmode("segment")
         probs = probs * (counts != 0).to(probs.dtype)[:, None, None]
     classes = Rg.threshold(probs, threshold)
-    return probs, Rg.remove_small_regions(classes, mo, ho, out=classes)
+    classes = Rg.remove_small_regions(classes, mo, ho, out=classes)
+    return (probs, classes, counts) if with_counts else (probs, classes)
 
 
 def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):
@@ -398,4 +401,52 @@ def evaluate_detection(loader, model, device, threshold=0.5, eps=11, reg_limit=F
                 cols[k].append(v)
     out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
     out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "dice"))
+    return out
+
+
+def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, eps=11, reg_limit=False, method="gaussianblur",
+                       thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, **blur):
+    """The instance-level sibling of ``evaluate_detection``: every image's cells -- the cleaned segmentation split at the detected
+    points -- against ground-truth instances, matched by IoU on the device (``regions.match_labels``).  The loader yields ``(images,
+    masks, ...)``: masks uint8 0 / 255 [n, H, W], whose connected components (``regions.label(masks != 0, connectivity)``) are the
+    truth instances, or int32 label images [n, H, W], used as they are.  Per batch: the body of ``segment_classes`` (with reg_limit
+    a count of 0 zeroes the map); detect._detect on the probabilities (with reg_limit capped by the image-mode count, as in
+    ``evaluate_detection``); ``regions.split`` of the cleaned classes at the device-resident detections; ``match_labels`` and
+    ``MatchTable.score(iou_threshold)``.  Returns a dict of numpy arrays ``n_pred, n_truth, tp, fp, fn, p, r, f1, sq, pq`` (one
+    entry per image) and ``mean`` = the averages (p, r, f1, sq, pq).  The model is left in segment mode."""
+    from . import detect as D
+    from . import regions as Rg
+    from . import score as S
+    D._check_method(method)
+    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
+    if unknown:
+        raise TypeError(f"evaluate_instances: unexpected arguments {sorted(unknown)}")
+    opts = {"ksize": (15, 15), "sigmaX": 3.}
+    opts.update(blur)
+    mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
+    conn = Rg._check_connectivity(connectivity)
+    S.check_iou_threshold(iou_threshold)
+    model.setmode("segment")
+    model.eval()
+    names = {"n_pred": "n_pred", "n_truth": "n_truth", "tp": "tp", "fp": "fp", "fn": "fn", "p": "precision", "r": "recall", "f1": "f1",
+             "sq": "sq", "pq": "pq"}
+    cols = {k: [] for k in names}
+    with torch.no_grad():
+        for batch in tqdm(loader, desc="testing"):
+            images, masks = batch[0], batch[1]
+            probs, classes, reg = _cleaned_batch(model, images.to(device), threshold, mo, ho, reg_limit, with_counts=True)
+            counts = reg.cpu().numpy().astype(int) if reg_limit else None
+            res = D._detect(probs, counts, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10), eps, opts["ksize"],
+                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
+            parts = res.split(classes, connectivity=conn)
+            truth = torch.as_tensor(masks)
+            if truth.dtype == torch.uint8:
+                truth = Rg.label(truth.to(device).reshape(classes.shape) != 0, conn)
+            elif truth.dtype != torch.int32:
+                raise TypeError(f"evaluate_instances: masks must be uint8 0 / 255 or int32 label images, got {truth.dtype}")
+            sc = Rg.match_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score(iou_threshold)
+            for k, field in names.items():
+                cols[k].append(getattr(sc, field))
+    out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
+    out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "sq", "pq"))
     return out

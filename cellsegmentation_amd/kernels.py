@@ -1305,6 +1305,42 @@ def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=N
     return t.get("counts"), t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
 
 
+def regions_match_workspace(N, cap_pred, cap_truth, device):
+    """the caller-owned scratch of one cs_regions_match_labels call on N images with these capacities"""
+    ws_bytes = _lib.load().cs_regions_match_workspace(int(N), int(cap_pred), int(cap_truth))
+    if ws_bytes == 0:
+        raise ValueError("regions_match_labels: a call takes 0 < N <= 65535 images and capacities >= 1 with N cap_pred "
+                         f"bit_length(cap_truth) < 2^31 and N cap_truth < 2^31, got {(N, cap_pred, cap_truth)}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+
+
+def regions_match_labels(pred, truth, cap_pred, cap_truth, counts_pred=None, counts_truth=None, area_pred=None, area_truth=None,
+                         match=None, inter=None, match_truth=None, want_counts=(True, True), ws=None):
+    """int32 label images pred, truth [N,H,W] -> (counts_pred int32 [N] | None, counts_truth int32 [N] | None, area_pred int32
+    [N,cap_pred], area_truth int32 [N,cap_truth], match int32 [N,cap_pred], inter int32 [N,cap_pred], match_truth int32
+    [N,cap_truth]): the partner of every label at IoU > 1/2 (cs_regions_match_labels in include/cellseg_hip.h).  The counts of a
+    side are written with the largest label of every image, or left out (``want_counts`` False for that side -> None)."""
+    if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):
+        raise TypeError("regions_match_labels reads two int32 [N,H,W] label images of one shape")
+    N, H, W = pred.shape
+    cp, ct = int(cap_pred), int(cap_truth)
+    want = {"area_pred": ((N, cp), torch.int32), "area_truth": ((N, ct), torch.int32), "match": ((N, cp), torch.int32),
+            "inter": ((N, cp), torch.int32), "match_truth": ((N, ct), torch.int32)}
+    if want_counts[0]:
+        want["counts_pred"] = ((N,), torch.int32)
+    if want_counts[1]:
+        want["counts_truth"] = ((N,), torch.int32)
+    if ws is None:
+        ws = regions_match_workspace(N, cp, ct, pred.device)
+    t = _regions_outputs("regions_match_labels", want,
+                         {"counts_pred": counts_pred, "counts_truth": counts_truth, "area_pred": area_pred, "area_truth": area_truth,
+                          "match": match, "inter": inter, "match_truth": match_truth}, pred.device)
+    _lib.check(_lib.load().cs_regions_match_labels(_p(pred), _p(truth), N, H, W, cp, ct, _p(t.get("counts_pred")), _p(t.get("counts_truth")),
+                                                   _p(t["area_pred"]), _p(t["area_truth"]), _p(t["match"]), _p(t["inter"]),
+                                                   _p(t["match_truth"]), _p(ws), ws.numel(), _stream()), "regions_match_labels")
+    return (t.get("counts_pred"), t.get("counts_truth"), t["area_pred"], t["area_truth"], t["match"], t["inter"], t["match_truth"])
+
+
 def regions_areas(mask, connectivity=1, out=None, ws=None):
     """uint8 [N,H,W] -> int32 [N,H,W]: the area of the component of equal-valued pixels under every pixel"""
     N, H, W, ws = _regions_args(mask, ws)

@@ -27,6 +27,10 @@ largest component count back once to size the tables.
 ``split`` cuts the components at seed points (one per cell, ``detect.detect_points``): every foreground pixel goes to the nearest
 seed of its own component and label k + 1 is point k, so that ``measure_labels`` -- the same tables for a label image -- gives one
 row per detection.  Exact integer rules, stated once in ``split``'s docstring and restated in numpy by tests/split_ref.py.
+
+``match_labels`` scores one label image against another at the object level: the partner of every label at IoU > 1/2, in exact
+integers (``MatchTable``; the rule is in ``match_labels``'s docstring, restated in numpy by tests/match_ref.py), from which
+``MatchTable.score`` forms TP / FP / FN, segmentation quality and panoptic quality on the host (``score.label_score``).
 """
 import dataclasses
 import typing
@@ -407,3 +411,133 @@ def measure_labels(labels, intensity=None, max_regions=None, counts=None):
     if own_counts:
         run(1, True)                                                     # the pass that finds the largest labels
     return run(max(1, int(counts.max())), False)                         # the one synchronisation
+
+
+def _host_int(t):
+    return t.cpu().numpy().astype(np.int64)
+
+
+@dataclasses.dataclass
+class MatchTable:
+    """``match_labels`` of N image pairs as device tensors.  ``counts_pred`` / ``counts_truth`` int32 [N]: the largest label of
+    every image, also above the capacity; ``area_pred`` int32 [N, cap_pred] and ``area_truth`` int32 [N, cap_truth]: the pixel
+    count of label k + 1 in row k (0 = the label owns nothing: no object); ``match`` int32 [N, cap_pred]: the truth label matched,
+    0 = none; ``inter`` int32 [N, cap_pred]: the pixels shared with it, 0 where unmatched; ``match_truth`` int32 [N, cap_truth]:
+    the inverse, the pred label or 0."""
+    counts_pred: torch.Tensor
+    counts_truth: torch.Tensor
+    cap_pred: int
+    cap_truth: int
+    area_pred: torch.Tensor
+    area_truth: torch.Tensor
+    match: torch.Tensor
+    inter: torch.Tensor
+    match_truth: torch.Tensor
+    _host: typing.Optional[tuple] = dataclasses.field(default=None, repr=False, compare=False)
+
+    def overflowed(self):
+        """device bool [N]: a side of the image has labels above its capacity (they were taken for background)"""
+        return (self.counts_pred > self.cap_pred) | (self.counts_truth > self.cap_truth)
+
+    def iou(self):
+        """float64 [N, cap_pred] = inter / (area_pred + area_truth[match] - inter) where matched, 0 elsewhere; on the device."""
+        matched = self.match > 0
+        at = torch.gather(self.area_truth, 1, (self.match - 1).clamp(min=0).to(torch.int64))
+        union = self.area_pred.to(torch.int64) + at - self.inter
+        q = self.inter.to(torch.float64) / union.clamp(min=1).to(torch.float64)
+        return torch.where(matched, q, torch.zeros_like(q))
+
+    def score(self, iou_threshold=0.5):
+        """TP / FP / FN, precision, recall, F1, SQ and PQ per image -> ``score.LabelScore`` (``score.label_score`` has the
+        formulas).  The one method that synchronises: the integer tables are copied to the host once and kept, so a sweep over
+        thresholds costs no further transfer.  ``iou_threshold``: a float in [0.5, 1]."""
+        from . import score as S
+        S.check_iou_threshold(iou_threshold)                              # before any transfer
+        if self._host is None:
+            self._host = tuple(_host_int(t) for t in (self.area_pred, self.area_truth, self.match, self.inter))
+        return S.label_score(*self._host, iou_threshold=iou_threshold)
+
+
+def _as_labels(x, what):
+    """int32 numpy / torch [H, W] or [N, H, W] -> the tensor (not yet on the device); argument errors only"""
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{what}: expected an int32 label image, got {t.dtype} (boolean masks go to label first)")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: empty label image of shape {tuple(t.shape)}")
+    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
+        raise ValueError(f"{what}: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
+    return t
+
+
+def _match_capacities(max_regions):
+    """None, one capacity or a (pred, truth) pair -> None or the pair"""
+    if max_regions is None:
+        return None
+    pair = tuple(max_regions) if isinstance(max_regions, (tuple, list)) else (max_regions, max_regions)
+    if len(pair) != 2:
+        raise ValueError(f"max_regions must be a positive integer, a (pred, truth) pair of them or None, got {max_regions!r}")
+    for c in pair:
+        _check_max_regions(c)
+        if c is None:
+            raise ValueError(f"max_regions must be a positive integer, a (pred, truth) pair of them or None, got {max_regions!r}")
+    return int(pair[0]), int(pair[1])
+
+
+def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=None):
+    """Match the objects of two label images by intersection over union -> ``MatchTable``.
+
+    ``pred``, ``truth``: int32 [H, W] or [N, H, W] of one shape (numpy or torch; 0 and below = background), e.g. ``split(...).labels``
+    against ``label(truth_mask)``.  Per image, with Ap[p] / At[g] the pixel counts of pred label p / truth label g, I(p, g) the
+    pixels that carry both and U = Ap[p] + At[g] - I:
+
+    * p and g are matched iff ``2 I(p, g) > U``, strictly, in 64-bit integers: IoU > 1/2, the panoptic-quality condition.  Then a
+      label has at most one partner on the other side: there is no assignment problem and no float decides a match.  IoU exactly
+      1/2 is NO match -- the one difference from matchers that test ``>=``.
+    * An object is a label that owns at least one pixel.  A label without pixels (a dead or duplicate seed of ``split``) is no
+      object: never a false positive or a false negative.
+    * A pixel whose label exceeds its side's capacity is background on that side; the largest labels are still reported in
+      ``counts_pred`` / ``counts_truth`` and ``overflowed()`` flags the image.
+
+    ``max_regions``: an int or a ``(pred, truth)`` pair fixes the capacities: a fixed number of launches, no synchronisation, the
+    call can be captured into a graph.  None finds the largest labels on the device, reads them back once (the one synchronisation)
+    and uses exactly those capacities (1 where there is no label).  ``pred_counts`` / ``truth_counts``: int32 [N], the labels in use
+    per image where the caller has them (``SplitResult.counts``); None = found on the device.  Everything the device writes is
+    integer and independent of launch order.  Memory: 4 N cap_pred (bit_length(cap_truth) + 1) bytes of workspace besides the
+    tables -- never a cap_pred x cap_truth table."""
+    caps = _match_capacities(max_regions)
+    p, t = _as_labels(pred, "match_labels"), _as_labels(truth, "match_labels")
+    if tuple(p.shape) != tuple(t.shape):
+        raise ValueError(f"match_labels: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
+    n_images = 1 if p.dim() == 2 else p.shape[0]
+    for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
+        if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (n_images,)):
+            raise TypeError(f"match_labels: {name} must be an int32 tensor of shape ({n_images},)")
+    dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
+    p, t = (x.reshape((n_images,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
+    N = n_images
+    chunks = _chunks(p)
+    own = (pred_counts is None, truth_counts is None)
+    cp = torch.empty((N,), dtype=torch.int32, device=dev) if own[0] else pred_counts.to(dev).contiguous()
+    ct = torch.empty((N,), dtype=torch.int32, device=dev) if own[1] else truth_counts.to(dev).contiguous()
+
+    def run(cap_p, cap_t, want):
+        tabs = [torch.empty((N, c), dtype=torch.int32, device=dev) for c in (cap_p, cap_t, cap_p, cap_p, cap_t)]
+        ws, ws_n = None, 0
+        for a, b in chunks:
+            if ws_n != b - a:
+                ws, ws_n = K.regions_match_workspace(b - a, cap_p, cap_t, dev), b - a
+            K.regions_match_labels(p[a:b], t[a:b], cap_p, cap_t, cp[a:b] if want[0] else None, ct[a:b] if want[1] else None,
+                                   *(x[a:b] for x in tabs), want_counts=want, ws=ws)
+        return MatchTable(cp, ct, cap_p, cap_t, *tabs)
+
+    if caps is not None:
+        return run(caps[0], caps[1], own)
+    if own[0] or own[1]:
+        run(1, 1, own)                                                   # the pass that finds the largest labels
+    top = torch.stack([cp.max(), ct.max()]).cpu()                        # the one synchronisation
+    return run(max(1, int(top[0])), max(1, int(top[1])), (False, False))

@@ -9,6 +9,10 @@ and no float decides anything; the ratios are formed on the host in float64 exac
 
 The result depends on the order of the detections.  ``detect.detect_points`` fixes that order (weight descending, then label
 descending), and ``DetectResult.score`` scores the device-resident detections of a batch without copying them back.
+
+``label_score`` is the object-level counterpart for label images: from the integer tables of ``regions.match_labels`` (areas,
+partner at IoU > 1/2, intersection) it forms TP / FP / FN at an IoU threshold, the same precision / recall / F1, and segmentation
+and panoptic quality -- a few thousand rows of host float64 arithmetic.
 """
 import math
 from dataclasses import dataclass
@@ -211,3 +215,52 @@ def get_prf1(points_hat, points):
     the same coordinate convention; ``np.asarray([])`` is an empty list."""
     res = score_points(points_hat, points)
     return float(res.precision[0]), float(res.recall[0]), float(res.f1[0]), int(res.tp[0]), int(res.fp[0]), int(res.fn[0])
+
+
+@dataclass
+class LabelScore:
+    """Per image (arrays of length N): ``n_pred``, ``n_truth`` (objects: labels that own a pixel, within the capacity), ``tp``,
+    ``fp``, ``fn`` int64; ``precision``, ``recall``, ``f1``, ``sq``, ``pq`` float64."""
+    n_pred: np.ndarray
+    n_truth: np.ndarray
+    tp: np.ndarray
+    fp: np.ndarray
+    fn: np.ndarray
+    precision: np.ndarray
+    recall: np.ndarray
+    f1: np.ndarray
+    sq: np.ndarray
+    pq: np.ndarray
+
+
+def check_iou_threshold(iou_threshold):
+    """a float in [0.5, 1] -> float; anything else raises ValueError (below 1/2 a label may have several partners)"""
+    t = iou_threshold
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not 0.5 <= float(t) <= 1.0:
+        raise ValueError(f"iou_threshold must be a number in [0.5, 1], got {iou_threshold!r}")
+    return float(t)
+
+
+def label_score(area_pred, area_truth, match, inter, iou_threshold=0.5):
+    """The integer tables of ``regions.match_labels`` on the host ([N, cap_pred], [N, cap_truth], [N, cap_pred], [N, cap_pred]) ->
+    ``LabelScore``, in numpy float64.  Per image: row p is a TP iff it is matched and ``inter / union >= iou_threshold`` (union =
+    area_pred + area_truth[match] - inter, a float64 quotient of the two integers); ``fp = n_pred - tp``, ``fn = n_truth - tp``;
+    precision, recall and F1 are ``precision_recall``'s, conventions for empty sides included; ``sq`` = the sum of the TP rows'
+    IoU in ascending pred label / tp, 0.0 without a TP; ``pq = sq * f1`` -- F1 is panoptic quality's recognition quality."""
+    thr = check_iou_threshold(iou_threshold)
+    ap, at, m, it = (np.asarray(x).astype(np.int64) for x in (area_pred, area_truth, match, inter))
+    if ap.ndim != 2 or at.ndim != 2 or m.shape != ap.shape or it.shape != ap.shape or at.shape[0] != ap.shape[0]:
+        raise ValueError("label_score: expected area_pred, match, inter [N, cap_pred] and area_truth [N, cap_truth]")
+    if m.size and (int(m.min()) < 0 or int(m.max()) > at.shape[1]):
+        raise ValueError("label_score: match holds a label outside area_truth")
+    matched = m > 0
+    union = ap + np.take_along_axis(at, np.where(matched, m - 1, 0), axis=1) - it if at.shape[1] else ap
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = np.where(matched, it / union, 0.0)
+    hit = matched & (iou >= thr)
+    n_pred, n_truth, tp = (ap > 0).sum(axis=1), (at > 0).sum(axis=1), hit.sum(axis=1)
+    fp, fn = n_pred - tp, n_truth - tp
+    p, r, f1 = (np.atleast_1d(v) for v in precision_recall(tp, fp, fn, True))
+    sq = np.asarray([np.sum(iou[n][hit[n]]) / tp[n] if tp[n] else 0.0 for n in range(len(tp))], np.float64)
+    return LabelScore(n_pred.astype(np.int64), n_truth.astype(np.int64), tp.astype(np.int64), fp.astype(np.int64), fn.astype(np.int64),
+                      p.astype(np.float64), r.astype(np.float64), f1.astype(np.float64), sq, sq * f1)

@@ -649,6 +649,25 @@ int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity,
 int cs_regions_measure_labels(const int32_t* labels, const uint8_t* intensity, int N, int H, int W, int capacity, int32_t* counts,
                               int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax, void* stream);
 
+/* ---- a label image scored against another at the object level (csrc/regions.hip) --------------------------------------------
+ * pred, truth int32 [N][H][W], values <= 0 = background; sizes and the launch contract as above (a fixed number of launches for
+ * given (N, H, W, cap_pred, cap_truth), no synchronisation, capturable).  For image n let Ap[p] / At[g] be the pixel counts of
+ * pred label p / truth label g, I(p, g) the pixels that carry both and U = Ap[p] + At[g] - I.  p and g are MATCHED iff
+ * 2 I(p, g) > U, strictly, compared in 64-bit integers (IoU > 1/2; IoU exactly 1/2 is no match).  With the strict inequality a
+ * label has at most one partner on the other side, so there is no assignment problem and no float decides anything.  A pixel
+ * whose label exceeds its side's capacity is background on that side.  Outputs: area_pred int32 [N][cap_pred] (row p - 1 = Ap[p]);
+ * area_truth int32 [N][cap_truth]; match int32 [N][cap_pred] = the matched truth label, 0 = none; inter int32 [N][cap_pred] =
+ * I(p, match), 0 where unmatched; match_truth int32 [N][cap_truth] = the matched pred label, 0 = none.  counts_pred / counts_truth
+ * (int32 [N], or NULL) are WRITTEN: the largest label of every image on that side, also above the capacity.  A label that owns no
+ * pixel has area 0 and no match.  All integer and independent of launch order: two runs give the same bits.
+ * Need cap_pred, cap_truth >= 1, N cap_pred B < 2^31 with B = max(1, bit_length(cap_truth)), N cap_truth < 2^31.  workspace:
+ * 16-byte aligned, >= cs_regions_match_workspace(N, cap_pred, cap_truth) bytes (0 for sizes a call would refuse): 4 N cap_pred
+ * (B + 1) bytes and padding, never a cap_pred x cap_truth table. */
+size_t cs_regions_match_workspace(int N, int cap_pred, int cap_truth);
+int cs_regions_match_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                            int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred, int32_t* area_truth, int32_t* match,
+                            int32_t* inter, int32_t* match_truth, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
  * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of
  * cs_detect_cluster as they are; gt int32 [G][2] with gt_off int64 [N + 1] are the annotations, in the same coordinate convention.

@@ -5,6 +5,14 @@ region.  Checks that the GPU counts equal the restatement's.
 
     python tools/score_microbench.py --images 1024 --cells 32 --path wave
     python tools/score_microbench.py --images 1 --cells 4096 --path block [--reps 20] [--json PATH]
+
+--labels times ``regions.match_labels`` (object matching of two label images at IoU > 1/2) with a fixed ``max_regions`` on the blob
+batches of tools/regions_microbench.py (128 x 299^2, and one 4096^2): pred = ``split`` at one seed per component, truth = the same
+masks shifted by a few pixels and relabelled.  Device events around the whole call, the median of 7 after a warm-up, next to two
+``measure_labels`` calls (one per label image: the same walk done twice) on the same inputs.  Two images of the batch are checked
+against tests/match_ref.py, the whole-slide image against a sparse pair count.
+
+    python tools/score_microbench.py --labels [--json PATH]
 """
 import argparse
 import json
@@ -18,6 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import score_ref as R  # noqa: E402
 from cellsegmentation_amd import kernels as K  # noqa: E402
@@ -37,14 +46,66 @@ def time_dev(fn, reps):
     return float(np.median(ts)), ts
 
 
+def sparse_match(pred, truth, cap):
+    """one image pair -> (match, inter) int64 [cap] from the distinct (pred, truth) pairs: for label counts a dense table cannot hold"""
+    p, g = (np.where((x < 0) | (x > cap), 0, x).astype(np.int64).ravel() for x in (pred, truth))
+    ap, at = np.bincount(p, minlength=cap + 1), np.bincount(g, minlength=cap + 1)
+    keys, inter = np.unique(p * (cap + 1) + g, return_counts=True)
+    kp, kg = keys // (cap + 1), keys % (cap + 1)
+    hit = (kp > 0) & (kg > 0) & (2 * inter > ap[kp] + at[kg] - inter)
+    match, shared = np.zeros(cap + 1, np.int64), np.zeros(cap + 1, np.int64)
+    match[kp[hit]], shared[kp[hit]] = kg[hit], inter[hit]
+    return match[1:], shared[1:]
+
+
+def labels_main(args):
+    import match_ref as M
+    import regions_microbench as RM
+    from cellsegmentation_amd import regions as G
+    dev = torch.device("cuda:0")
+    res = {}
+    for name, masks in RM.mask_sets():
+        cap = RM.MAX_REGIONS[name]
+        d = torch.from_numpy(masks).to(dev)
+        pts, off = RM.seeds_in_components(G.label(d).cpu().numpy(), 1, seed=1)
+        pred = G.split(d, torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)).labels
+        truth = G.label(torch.from_numpy(np.roll(masks, (3, 2), axis=(1, 2))).to(dev))
+        match_ms, ts = time_dev(lambda: G.match_labels(pred, truth, max_regions=cap), 7)
+        twice_ms, _ = time_dev(lambda: (G.measure_labels(pred, max_regions=cap), G.measure_labels(truth, max_regions=cap)), 7)
+        t = G.match_labels(pred, truth, max_regions=cap)
+        ok = True
+        hp, ht = pred.cpu().numpy(), truth.cpu().numpy()
+        for i in range(min(2, len(masks))):
+            got = {k: getattr(t, k)[i].cpu().numpy() for k in ("area_pred", "area_truth", "match", "inter", "match_truth")}
+            if cap <= 1024:
+                ref = M.match(hp[i], ht[i], cap, cap)
+                ok &= all(np.array_equal(got[k], ref[k][0]) for k in got)
+            else:
+                match, shared = sparse_match(hp[i], ht[i], cap)
+                ok &= bool(np.array_equal(got["match"], match) and np.array_equal(got["inter"], shared))
+        s = t.score()
+        res[name] = {"match_labels_ms": match_ms, "match_labels_ms_all": ts, "two_measure_labels_ms": twice_ms, "max_regions": cap,
+                     "objects_pred": int(s.n_pred.sum()), "objects_truth": int(s.n_truth.sum()), "matched": int(s.tp.sum()),
+                     "pq_mean": float(s.pq.mean()), "overflowed": int(t.overflowed().sum()), "equal_to_host": bool(ok)}
+        print(json.dumps({name: res[name]}), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    if not all(v["equal_to_host"] for v in res.values()):
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--labels", action="store_true", help="time regions.match_labels next to two measure_labels calls instead")
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--cells", type=int, default=32, help="annotations and detections per image")
     ap.add_argument("--path", choices=("wave", "block"), default="wave", help="block: the 256-thread path at any size")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", default=None, help="also write the result to this file")
     args = ap.parse_args()
+    if args.labels:
+        return labels_main(args)
     if args.path == "wave" and args.cells > 64:
         ap.error("the wave path serves at most 64 annotations per image")
     dev = torch.device("cuda:0")
