@@ -172,6 +172,8 @@ _SIGNATURES = {
     "cs_regions_measure_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "cs_regions_match_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_match_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cs_regions_overlap_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cs_regions_overlap_labels": (c_int, [_P, _P] + [c_int] * 6 + [_P] * 13 + [c_size_t, _P]),
     "cs_score_workspace": (c_size_t, [c_int, c_longlong]),
     "cs_score_points": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }

@@ -15,6 +15,8 @@
 //   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
 //             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
 //             and an exact 64-bit integer test per pred label
+//   overlap   the same two images: every (pred, truth) pair that shares a pixel with its count, in a per-image hash table filled by
+//             one walk, and from it every label's partner of largest IoU / largest intersection (integer maxima under a total order)
 //   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
 //             component without a seed is numbered after the seeds:
 //               seeds   one thread per point hangs the live seeds on a chain at their component's root
@@ -474,8 +476,178 @@ __global__ __launch_bounds__(256) void match_decide_kernel(long long rows, Match
     }
 }
 
+// ---- label image against label image: every overlapping pair ----------------------------------------------------------------------
+// The sparse contingency table of two label images: every (p, g) that shares a pixel, with the count.  Per image an open-addressing
+// hash table of `slots` (a power of two) 64-bit keys, (p << 32) | g, 0 = empty, and as many int32 counts.  A key is written once, by
+// the CAS that takes the slot from empty, and never changes: a probe that reads a key other than 0 has read the slot's final key.
+// Which slot a pair lands in depends on the order of arrival; the set of (key, count) does not (integer sums), and everything
+// derived from the table is a maximum under a total order of the pairs, which does not depend on where they sit.
+struct Overlap {
+    int32_t* area_pred;             // [N][cap_pred]
+    int32_t* area_truth;            // [N][cap_truth]
+    int32_t* n_pairs;               // [N]  occupied slots
+    int32_t* dropped;               // [N]  runs that found no slot
+    int32_t* iou_partner;           // [N][cap_truth]  the pred label of largest IoU, 0 = none
+    int32_t* iou_inter;             // [N][cap_truth]  its intersection
+    int32_t* inter_partner_truth;   // [N][cap_truth]  the pred label of largest intersection
+    int32_t* inter_truth;           // [N][cap_truth]
+    int32_t* inter_partner_pred;    // [N][cap_pred]   the truth label of largest intersection
+    int32_t* inter_pred;            // [N][cap_pred]
+    unsigned long long* keys;       // [N][slots]
+    int32_t* cnt;                   // [N][slots]
+    unsigned long long* best_iou;   // [N][cap_truth]  (I << 32) | p, 0 = none
+    unsigned long long* best_it;    // [N][cap_truth]  (I << 32) | ~p: the largest I, then the lowest p
+    unsigned long long* best_ip;    // [N][cap_pred]   (I << 32) | ~g
+    int32_t* maxp;                  // [N] or NULL: the largest pred label
+    int32_t* maxt;                  // [N] or NULL: the largest truth label
+    int cap_pred, cap_truth, slots;
+};
+
+__global__ __launch_bounds__(256) void overlap_init_kernel(int N, Overlap t) {
+    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth, ns = (long long)N * t.slots;
+    const long long all = max(ns, max(np, nt));                        // >= N
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        if (i < ns) {
+            t.keys[i] = 0;
+            t.cnt[i] = 0;
+        }
+        if (i < np) {
+            t.area_pred[i] = 0;
+            t.best_ip[i] = 0;
+        }
+        if (i < nt) {
+            t.area_truth[i] = 0;
+            t.best_iou[i] = 0;
+            t.best_it[i] = 0;
+        }
+        if (i < N) {
+            t.n_pairs[i] = 0;
+            t.dropped[i] = 0;
+            if (t.maxp) t.maxp[i] = 0;
+            if (t.maxt) t.maxt[i] = 0;
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned overlap_hash(unsigned p, unsigned g) {
+    unsigned h = p * 0x9E3779B1u ^ g * 0x85EBCA77u;
+    h ^= h >> 15;
+    h *= 0x2C1B3C6Du;
+    return h ^ (h >> 13);
+}
+
+// len more pixels for pair (p, g) of one image's table.  At most `slots` probes: a slot is taken from empty by CAS, one that
+// holds this key (from this CAS or from another thread's) gets the add, any other key sends the probe on.  Nothing is waited for.
+// Returns false when every slot holds another key.  *fresh: this call took a slot.
+__device__ __forceinline__ bool overlap_insert(unsigned long long* keys, int32_t* cnt, unsigned mask, int p, int g, int len, bool* fresh) {
+    const unsigned long long key = ((unsigned long long)(unsigned)p << 32) | (unsigned)g;
+    unsigned s = overlap_hash((unsigned)p, (unsigned)g) & mask;
+    *fresh = false;
+    for (unsigned tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
+        unsigned long long seen = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, kGlobal);
+        if (seen == 0) {                                               // (on failure the CAS leaves the key it met in `seen`)
+            if (__hip_atomic_compare_exchange_strong(keys + s, &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, kGlobal)) {
+                *fresh = true;
+                seen = key;
+            }
+        }
+        if (seen == key) {
+            __hip_atomic_fetch_add(cnt + s, len, __ATOMIC_RELAXED, kGlobal);
+            return true;
+        }
+    }
+    return false;
+}
+
+// match_walk_kernel's walk: the areas and maxima of both sides, and every run on which both labels are positive (and within their
+// capacities) adds its length to its pair's slot.
+__global__ __launch_bounds__(256) void overlap_walk_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int N, int H,
+                                                           int W, Overlap t) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned segs = (unsigned)(W + 63) >> 6;
+    const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
+    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
+        const unsigned row = (unsigned)it / segs;                      // n H + r
+        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
+        const int n = (int)(row / (unsigned)H);
+        const long long px = (long long)row * W + c;
+        const int p = c < W ? max(pred[px], 0) : 0, g = c < W ? max(truth[px], 0) : 0;
+        const bool live = (p | g) != 0;
+        const unsigned long long bal = __ballot(live);
+        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
+        const int pl = __shfl_up(p, 1), gl = __shfl_up(g, 1);          // (lane 0 gets its own back)
+        int len;
+        const bool head = run_of(bal, __ballot(live && (p != pl || g != gl)), lane, len);
+        if (!head) continue;
+        if (t.maxp && p) raise_to(t.maxp + n, p);
+        if (t.maxt && g) raise_to(t.maxt + n, g);
+        const int pc = p <= t.cap_pred ? p : 0, gc = g <= t.cap_truth ? g : 0;
+        if (gc) __hip_atomic_fetch_add(t.area_truth + (long long)n * t.cap_truth + gc - 1, len, __ATOMIC_RELAXED, kGlobal);
+        if (pc) __hip_atomic_fetch_add(t.area_pred + (long long)n * t.cap_pred + pc - 1, len, __ATOMIC_RELAXED, kGlobal);
+        if (!pc || !gc) continue;
+        const long long base = (long long)n * t.slots;                 // < N slots < 2^31
+        bool fresh;
+        if (!overlap_insert(t.keys + base, t.cnt + base, (unsigned)t.slots - 1, pc, gc, len, &fresh))
+            __hip_atomic_fetch_add(t.dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
+        else if (fresh)
+            __hip_atomic_fetch_add(t.n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+    }
+}
+
+// One thread per slot, after the walk: the areas and counts are final.  Best intersection of either side: an atomic maximum of
+// (I << 32) | ~partner, i.e. the largest I and among equals the lowest partner.  Best IoU of a truth label: I / U > I' / U' is
+// I U' > I' U in 64-bit integers (all four below 2^31), equal quotients go to the lower pred label; the holder is replaced by
+// CAS only where this slot's pair is strictly better under that total order, so a failed CAS means that another thread improved
+// the holder, the comparison is made again against what it wrote, and the loop ends with the best pair of all whatever the order.
+__global__ __launch_bounds__(256) void overlap_reduce_kernel(long long n_slots, Overlap t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_slots; i += (long long)gridDim.x * 256) {
+        const unsigned long long key = t.keys[i];
+        if (key == 0) continue;
+        const long long n = i / t.slots;
+        const unsigned p = (unsigned)(key >> 32), g = (unsigned)key;
+        const unsigned long long I = (unsigned)t.cnt[i];
+        const long long qp = n * t.cap_pred + p - 1, qg = n * t.cap_truth + g - 1;
+        __hip_atomic_fetch_max(t.best_it + qg, (I << 32) | (unsigned)~p, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_max(t.best_ip + qp, (I << 32) | (unsigned)~g, __ATOMIC_RELAXED, kGlobal);
+        const long long at = t.area_truth[qg];
+        const unsigned long long U = (unsigned long long)(t.area_pred[qp] + at - (long long)I);
+        const unsigned long long mine = (I << 32) | p;
+        unsigned long long held = __hip_atomic_load(t.best_iou + qg, __ATOMIC_RELAXED, kGlobal);
+        for (;;) {
+            if (held != 0) {
+                const unsigned hp = (unsigned)held;
+                const unsigned long long hI = held >> 32;
+                const unsigned long long hU = (unsigned long long)(t.area_pred[n * t.cap_pred + hp - 1] + at - (long long)hI);
+                const unsigned long long a = I * hU, b = hI * U;
+                if (!(a > b || (a == b && p < hp))) break;             // the holder is as good or better
+            }
+            if (__hip_atomic_compare_exchange_strong(t.best_iou + qg, &held, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, kGlobal)) break;
+        }
+    }
+}
+
+// One thread per label of either side: the packed winners into the tables.
+__global__ __launch_bounds__(256) void overlap_finish_kernel(int N, Overlap t) {
+    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < max(np, nt); i += (long long)gridDim.x * 256) {
+        if (i < nt) {
+            const unsigned long long q = t.best_iou[i], b = t.best_it[i];
+            t.iou_partner[i] = (int)(unsigned)q;
+            t.iou_inter[i] = (int)(q >> 32);
+            t.inter_partner_truth[i] = b ? (int)~(unsigned)b : 0;
+            t.inter_truth[i] = (int)(b >> 32);
+        }
+        if (i < np) {
+            const unsigned long long b = t.best_ip[i];
+            t.inter_partner_pred[i] = b ? (int)~(unsigned)b : 0;
+            t.inter_pred[i] = (int)(b >> 32);
+        }
+    }
+}
+
 // ---- seeded split ------------------------------------------------------------------------------------------------------------------
-// One thread per point.  A point is a live seed when it is one of the first S'_n of its image, lies inside the image and on a
+// One thread per point. A point is a live seed when it is one of the first S'_n of its image, lies inside the image and on a
 // foreground pixel.  A live seed is pushed on the chain of its component: the root's slot of `head` (the spent cnt array) holds the
 // area (> 0) while the component has no seed and -(p + 1), p = the point on top of the chain, afterwards; rec[p] = (row, col, index
 // within the image, the next point of the chain or -1).  The order of a chain depends on the order the pushes land in; what the
@@ -593,6 +765,19 @@ inline int vote_bits(int cap_truth) {
 bool match_sizes_ok(int N, int cap_pred, int cap_truth) {
     return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && (long long)N * cap_pred * vote_bits(cap_truth) < (1LL << 31) &&
            (long long)N * cap_truth < (1LL << 31);
+}
+
+// the slots of one image's pair table: the smallest power of two >= 2 max_pairs; 0 for a max_pairs no call takes
+inline long long overlap_slots(int max_pairs) {
+    if (max_pairs < 1 || max_pairs > (1 << 29)) return 0;
+    long long s = 2;
+    while (s < 2LL * max_pairs) s <<= 1;
+    return s;
+}
+bool overlap_sizes_ok(int N, int cap_pred, int cap_truth, int max_pairs) {
+    const long long slots = overlap_slots(max_pairs);
+    return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && slots > 0 && (long long)N * cap_pred < (1LL << 31) &&
+           (long long)N * cap_truth < (1LL << 31) && N * slots < (1LL << 31);
 }
 
 // labels and areas of `m` into ws.lab / ws.cnt (cnt holds the area at every root's slot)
@@ -784,6 +969,53 @@ extern "C" int cs_regions_match_labels(const int32_t* pred, const int32_t* truth
     hipLaunchKernelGGL(match_walk_kernel<false>, walk, dim3(256), 0, st, pred, truth, N, H, W, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(match_decide_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+// workspace: keys (uint64 N slots), cnt (int32 N slots) -- the pair table, which the caller may read afterwards -- then best_iou,
+// best_it (uint64 N cap_truth each), best_ip (uint64 N cap_pred); slots = overlap_slots(max_pairs)
+extern "C" size_t cs_regions_overlap_workspace(int N, int cap_pred, int cap_truth, int max_pairs) {
+    if (!overlap_sizes_ok(N, cap_pred, cap_truth, max_pairs)) return 0;
+    const size_t ns = (size_t)N * overlap_slots(max_pairs);
+    return align16(ns * 8) + align16(ns * 4) + 2 * align16((size_t)N * cap_truth * 8) + align16((size_t)N * cap_pred * 8);
+}
+
+extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                                         int max_pairs, int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred,
+                                         int32_t* area_truth, int32_t* n_pairs, int32_t* dropped, int32_t* iou_partner, int32_t* iou_inter,
+                                         int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred,
+                                         int32_t* inter_pred, void* workspace, size_t workspace_bytes, void* stream) {
+    CS_CHECK_ARG(pred && truth && area_pred && area_truth && n_pairs && dropped && iou_partner && iou_inter && inter_partner_truth &&
+                     inter_truth && inter_partner_pred && inter_pred && workspace,
+                 "regions_overlap_labels: NULL argument");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_overlap_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(overlap_sizes_ok(N, cap_pred, cap_truth, max_pairs),
+                 "regions_overlap_labels: need capacities >= 1, 1 <= max_pairs <= 2^29, N cap_pred < 2^31, N cap_truth < 2^31 and "
+                 "N slots < 2^31");
+    CS_CHECK_ARG(workspace_bytes >= cs_regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs),
+                 "regions_overlap_labels: workspace too small");
+    CS_CHECK_ARG(!(reinterpret_cast<uintptr_t>(workspace) & 15), "regions_overlap_labels: misaligned workspace");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int slots = (int)overlap_slots(max_pairs);
+    const long long ns = (long long)N * slots, np = (long long)N * cap_pred, nt = (long long)N * cap_truth;
+    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+    Overlap t{area_pred, area_truth, n_pairs, dropped, iou_partner, iou_inter, inter_partner_truth, inter_truth, inter_partner_pred,
+              inter_pred, nullptr, nullptr, nullptr, nullptr, nullptr, counts_pred, counts_truth, cap_pred, cap_truth, slots};
+    t.keys = reinterpret_cast<unsigned long long*>(w);      w += align16((size_t)ns * 8);
+    t.cnt = reinterpret_cast<int32_t*>(w);                  w += align16((size_t)ns * 4);
+    t.best_iou = reinterpret_cast<unsigned long long*>(w);  w += align16((size_t)nt * 8);
+    t.best_it = reinterpret_cast<unsigned long long*>(w);   w += align16((size_t)nt * 8);
+    t.best_ip = reinterpret_cast<unsigned long long*>(w);
+    const long long labels = np > nt ? np : nt;
+    hipLaunchKernelGGL(overlap_init_kernel, dim3(grid_for(ns > labels ? ns : labels)), dim3(256), 0, st, N, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(overlap_walk_kernel, dim3(grid_for((long long)N * H * cs_ceil_div(W, 64) * 64)), dim3(256), 0, st, pred, truth, N,
+                       H, W, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(overlap_reduce_kernel, dim3(grid_for(ns)), dim3(256), 0, st, ns, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(overlap_finish_kernel, dim3(grid_for(labels)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -405,7 +405,7 @@ def evaluate_detection(loader, model, device, threshold=0.5, eps=11, reg_limit=F
 
 
 def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, eps=11, reg_limit=False, method="gaussianblur",
-                       thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, **blur):
+                       thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, overlap=False, **blur):
     """The instance-level sibling of ``evaluate_detection``: every image's cells -- the cleaned segmentation split at the detected
     points -- against ground-truth instances, matched by IoU on the device (``regions.match_labels``).  The loader yields ``(images,
     masks, ...)``: masks uint8 0 / 255 [n, H, W], whose connected components (``regions.label(masks != 0, connectivity)``) are the
@@ -413,7 +413,9 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     a count of 0 zeroes the map); detect._detect on the probabilities (with reg_limit capped by the image-mode count, as in
     ``evaluate_detection``); ``regions.split`` of the cleaned classes at the device-resident detections; ``match_labels`` and
     ``MatchTable.score(iou_threshold)``.  Returns a dict of numpy arrays ``n_pred, n_truth, tp, fp, fn, p, r, f1, sq, pq`` (one
-    entry per image) and ``mean`` = the averages (p, r, f1, sq, pq).  The model is left in segment mode."""
+    entry per image) and ``mean`` = the averages (p, r, f1, sq, pq).  ``overlap=True`` also runs ``regions.overlap_labels`` on the
+    same label pair and adds the columns ``aji`` and ``dice_obj`` (``score.overlap_score``) and ``mean_overlap`` = their averages
+    (aji, dice_obj); without it nothing more is launched and the keys are the ones above.  The model is left in segment mode."""
     from . import detect as D
     from . import regions as Rg
     from . import score as S
@@ -431,6 +433,8 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     names = {"n_pred": "n_pred", "n_truth": "n_truth", "tp": "tp", "fp": "fp", "fn": "fn", "p": "precision", "r": "recall", "f1": "f1",
              "sq": "sq", "pq": "pq"}
     cols = {k: [] for k in names}
+    if overlap:
+        cols.update(aji=[], dice_obj=[])
     with torch.no_grad():
         for batch in tqdm(loader, desc="testing"):
             images, masks = batch[0], batch[1]
@@ -447,6 +451,12 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
             sc = Rg.match_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score(iou_threshold)
             for k, field in names.items():
                 cols[k].append(getattr(sc, field))
+            if overlap:
+                ov = Rg.overlap_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score()
+                cols["aji"].append(ov.aji)
+                cols["dice_obj"].append(ov.dice_obj)
     out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
     out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "sq", "pq"))
+    if overlap:
+        out["mean_overlap"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("aji", "dice_obj"))
     return out

@@ -1341,6 +1341,63 @@ def regions_match_labels(pred, truth, cap_pred, cap_truth, counts_pred=None, cou
     return (t.get("counts_pred"), t.get("counts_truth"), t["area_pred"], t["area_truth"], t["match"], t["inter"], t["match_truth"])
 
 
+def regions_overlap_slots(max_pairs):
+    """the entries of one image's pair table: the smallest power of two >= 2 max_pairs"""
+    return 1 << max(1, (2 * int(max_pairs) - 1).bit_length())
+
+
+def regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs, device):
+    """the caller-owned scratch of one cs_regions_overlap_labels call on N images with these capacities; it starts with the pair
+    table, which the call's result views"""
+    mp = int(max_pairs)
+    ws_bytes = _lib.load().cs_regions_overlap_workspace(int(N), int(cap_pred), int(cap_truth), mp) if 1 <= mp < 1 << 31 else 0
+    if ws_bytes == 0:
+        raise ValueError("regions_overlap_labels: a call takes 0 < N <= 65535 images, capacities >= 1 and 1 <= max_pairs <= 2^29 with "
+                         f"N cap_pred, N cap_truth and N slots < 2^31, got {(N, cap_pred, cap_truth, max_pairs)}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+
+
+_OVERLAP_TABLES = (("area_pred", 0), ("area_truth", 1), ("iou_partner", 1), ("iou_inter", 1), ("inter_partner_truth", 1), ("inter_truth", 1),
+                   ("inter_partner_pred", 0), ("inter_pred", 0))
+
+
+def regions_overlap_labels(pred, truth, cap_pred, cap_truth, max_pairs, counts_pred=None, counts_truth=None, area_pred=None,
+                           area_truth=None, n_pairs=None, dropped=None, iou_partner=None, iou_inter=None, inter_partner_truth=None,
+                           inter_truth=None, inter_partner_pred=None, inter_pred=None, want_counts=(True, True), ws=None):
+    """int32 label images pred, truth [N,H,W] -> a dict of int32 tensors: counts_pred, counts_truth [N] (None where ``want_counts``
+    is False for that side), area_pred [N,cap_pred], area_truth [N,cap_truth], n_pairs, dropped [N], iou_partner, iou_inter,
+    inter_partner_truth, inter_truth [N,cap_truth], inter_partner_pred, inter_pred [N,cap_pred], and the pair table itself as views
+    of ``ws``: slot_keys int64 [N,slots] ((pred << 32) | truth, 0 = empty) and slot_counts int32 [N,slots]
+    (cs_regions_overlap_labels in include/cellseg_hip.h)."""
+    if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):
+        raise TypeError("regions_overlap_labels reads two int32 [N,H,W] label images of one shape")
+    N, H, W = pred.shape
+    cp, ct, mp = int(cap_pred), int(cap_truth), int(max_pairs)
+    caps = (cp, ct)
+    want = {name: ((N, caps[side]), torch.int32) for name, side in _OVERLAP_TABLES}
+    want.update(n_pairs=((N,), torch.int32), dropped=((N,), torch.int32))
+    if want_counts[0]:
+        want["counts_pred"] = ((N,), torch.int32)
+    if want_counts[1]:
+        want["counts_truth"] = ((N,), torch.int32)
+    if ws is None:
+        ws = regions_overlap_workspace(N, cp, ct, mp, pred.device)
+    given = {"counts_pred": counts_pred, "counts_truth": counts_truth, "area_pred": area_pred, "area_truth": area_truth, "n_pairs": n_pairs,
+             "dropped": dropped, "iou_partner": iou_partner, "iou_inter": iou_inter, "inter_partner_truth": inter_partner_truth,
+             "inter_truth": inter_truth, "inter_partner_pred": inter_partner_pred, "inter_pred": inter_pred}
+    t = _regions_outputs("regions_overlap_labels", want, given, pred.device)
+    _lib.check(_lib.load().cs_regions_overlap_labels(
+        _p(pred), _p(truth), N, H, W, cp, ct, mp, _p(t.get("counts_pred")), _p(t.get("counts_truth")), _p(t["area_pred"]),
+        _p(t["area_truth"]), _p(t["n_pairs"]), _p(t["dropped"]), _p(t["iou_partner"]), _p(t["iou_inter"]), _p(t["inter_partner_truth"]),
+        _p(t["inter_truth"]), _p(t["inter_partner_pred"]), _p(t["inter_pred"]), _p(ws), ws.numel(), _stream()), "regions_overlap_labels")
+    cells = N * regions_overlap_slots(mp)                              # the table leads the workspace: 8 then 4 bytes per slot
+    t["slot_keys"] = ws[:8 * cells].view(torch.int64).view(N, -1)
+    t["slot_counts"] = ws[8 * cells:12 * cells].view(torch.int32).view(N, -1)
+    t.setdefault("counts_pred", None)
+    t.setdefault("counts_truth", None)
+    return t
+
+
 def regions_areas(mask, connectivity=1, out=None, ws=None):
     """uint8 [N,H,W] -> int32 [N,H,W]: the area of the component of equal-valued pixels under every pixel"""
     N, H, W, ws = _regions_args(mask, ws)

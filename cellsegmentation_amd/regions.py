@@ -31,6 +31,10 @@ row per detection.  Exact integer rules, stated once in ``split``'s docstring an
 ``match_labels`` scores one label image against another at the object level: the partner of every label at IoU > 1/2, in exact
 integers (``MatchTable``; the rule is in ``match_labels``'s docstring, restated in numpy by tests/match_ref.py), from which
 ``MatchTable.score`` forms TP / FP / FN, segmentation quality and panoptic quality on the host (``score.label_score``).
+
+``overlap_labels`` lists every (pred, truth) pair of labels that shares a pixel, with the count, and gives every label its best
+partner by IoU and by intersection, however small the overlap (``OverlapTable``; restated in numpy by tests/overlap_ref.py), from
+which ``OverlapTable.score`` forms AJI and object-level Dice on the host (``score.overlap_score``).
 """
 import dataclasses
 import typing
@@ -541,3 +545,132 @@ def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=N
         run(1, 1, own)                                                   # the pass that finds the largest labels
     top = torch.stack([cp.max(), ct.max()]).cpu()                        # the one synchronisation
     return run(max(1, int(top[0])), max(1, int(top[1])), (False, False))
+
+
+_OVERLAP_HOST = ("area_pred", "area_truth", "iou_partner", "iou_inter", "inter_partner_truth", "inter_truth", "inter_partner_pred",
+                 "inter_pred", "n_pairs")
+
+
+@dataclasses.dataclass
+class OverlapTable:
+    """``overlap_labels`` of N image pairs as device tensors, all int32 but the keys.  ``counts_pred`` / ``counts_truth`` [N], the
+    capacities and ``area_pred`` [N, cap_pred] / ``area_truth`` [N, cap_truth] as in ``MatchTable``.  ``n_pairs`` [N]: the (pred,
+    truth) pairs that share a pixel; ``dropped`` [N]: the runs of pixels whose pair found no room (0 unless ``max_pairs`` was too
+    small).  Row g - 1 of ``iou_partner`` / ``iou_inter`` [N, cap_truth]: the pred label of largest IoU with truth label g (0 =
+    none) and the pixels shared with it; of ``inter_partner_truth`` / ``inter_truth``: the pred label of largest intersection and
+    that intersection.  Row p - 1 of ``inter_partner_pred`` / ``inter_pred`` [N, cap_pred]: the same for pred label p over the
+    truth labels.  ``slot_keys`` int64 [N, slots] and ``slot_counts`` [N, slots]: the raw pair table, key = (pred << 32) | truth,
+    0 = empty, in no particular order -- ``pairs()`` reads it."""
+    counts_pred: torch.Tensor
+    counts_truth: torch.Tensor
+    cap_pred: int
+    cap_truth: int
+    area_pred: torch.Tensor
+    area_truth: torch.Tensor
+    n_pairs: torch.Tensor
+    dropped: torch.Tensor
+    iou_partner: torch.Tensor
+    iou_inter: torch.Tensor
+    inter_partner_truth: torch.Tensor
+    inter_truth: torch.Tensor
+    inter_partner_pred: torch.Tensor
+    inter_pred: torch.Tensor
+    slot_keys: torch.Tensor
+    slot_counts: torch.Tensor
+    _host: typing.Optional[tuple] = dataclasses.field(default=None, repr=False, compare=False)
+
+    def overflowed(self):
+        """device bool [N]: a side of the image has labels above its capacity (they were taken for background), or pairs of it
+        found no room in the table (they are missing from the pair list and from the partners)"""
+        return (self.counts_pred > self.cap_pred) | (self.counts_truth > self.cap_truth) | (self.dropped > 0)
+
+    def pairs(self):
+        """The sparse contingency table on the host: int64 arrays ``(image, pred, truth, inter)``, one entry per pair that shares a
+        pixel, sorted by (image, pred, truth).  One copy from the device (it synchronises)."""
+        flat = torch.cat([self.slot_keys.reshape(-1), self.slot_counts.reshape(-1).to(torch.int64)]).cpu().numpy()
+        keys, inter = flat[:flat.size // 2], flat[flat.size // 2:]
+        at = np.nonzero(keys)[0]
+        image, keys, inter = at // self.slot_keys.shape[1], keys[at], inter[at]
+        order = np.lexsort((keys, image))                                # a key orders by pred, then truth
+        return image[order], keys[order] >> 32, keys[order] & 0xFFFFFFFF, inter[order]
+
+    def score(self):
+        """AJI and object-level Dice per image -> ``score.OverlapScore`` (``score.overlap_score`` has the formulas).  It
+        synchronises: the integer tables are copied to the host once and kept."""
+        from . import score as S
+        if self._host is None:
+            self._host = tuple(_host_int(getattr(self, k)) for k in _OVERLAP_HOST)
+        return S.overlap_score(*self._host)
+
+
+def _check_max_pairs(max_pairs):
+    if max_pairs is not None and (isinstance(max_pairs, bool) or int(max_pairs) != max_pairs or not 1 <= max_pairs <= 1 << 29):
+        raise ValueError(f"max_pairs must be an integer in [1, 2^29] or None, got {max_pairs!r}")
+
+
+def overlap_labels(pred, truth, max_regions=None, max_pairs=None, pred_counts=None, truth_counts=None):
+    """Every overlapping pair of objects of two label images, and each object's best partner -> ``OverlapTable``: what the scores
+    that look below IoU 1/2 need (``OverlapTable.score``: AJI and object-level Dice; ``OverlapTable.pairs``: the sparse contingency
+    table, for any other).
+
+    ``pred``, ``truth``, ``max_regions``, ``pred_counts`` / ``truth_counts`` and the treatment of labels (0 and below, and labels
+    above their side's capacity, are background) are those of ``match_labels``.  Per image, with Ap / At the areas and I(p, g) the
+    pixels that carry both labels:
+
+    * the best-IoU partner of truth label g is the pred label p with I > 0 that maximises ``I / (Ap + At - I)``, fractions compared
+      by cross-multiplication in 64-bit integers, ties to the lower p;
+    * the best-intersection partner of a label of either side is the label of the other side of largest I, ties to the lower.
+
+    The pairs are collected in a per-image hash table of ``slots`` = the smallest power of two >= 2 ``max_pairs`` entries.
+    ``max_pairs=int`` (with ``max_regions`` given) fixes it: four launches, no synchronisation, the call can be captured into a
+    graph; pairs that find no room are counted in ``dropped`` and ``overflowed()`` flags the image.  ``max_pairs=None`` starts from
+    4 (cap_pred + cap_truth) (at most H W), reads ``dropped.max()`` back and doubles while it is non-zero -- it ends because an image has at most
+    H W pairs -- so the table returned has lost no pair.  Everything the device writes is integer and independent of launch and
+    arrival order, except the position of a pair in the raw table.  Memory besides the tables: 12 N slots + 8 N (2 cap_truth +
+    cap_pred) bytes of workspace, whose first 12 N slots bytes the result keeps -- never a cap_pred x cap_truth table."""
+    caps = _match_capacities(max_regions)
+    _check_max_pairs(max_pairs)
+    p, t = _as_labels(pred, "overlap_labels"), _as_labels(truth, "overlap_labels")
+    if tuple(p.shape) != tuple(t.shape):
+        raise ValueError(f"overlap_labels: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
+    n_images = 1 if p.dim() == 2 else p.shape[0]
+    for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
+        if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (n_images,)):
+            raise TypeError(f"overlap_labels: {name} must be an int32 tensor of shape ({n_images},)")
+    dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
+    p, t = (x.reshape((n_images,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
+    N = n_images
+    chunks = _chunks(p)
+    own = (pred_counts is None, truth_counts is None)
+    cp = torch.empty((N,), dtype=torch.int32, device=dev) if own[0] else pred_counts.to(dev).contiguous()
+    ct = torch.empty((N,), dtype=torch.int32, device=dev) if own[1] else truth_counts.to(dev).contiguous()
+
+    def run(cap_p, cap_t, pairs, want):
+        names = [k for k, _ in K._OVERLAP_TABLES] + ["n_pairs", "dropped"]
+        tabs = {k: torch.empty((N, (cap_p, cap_t)[side]), dtype=torch.int32, device=dev) for k, side in K._OVERLAP_TABLES}
+        tabs.update(n_pairs=torch.empty((N,), dtype=torch.int32, device=dev), dropped=torch.empty((N,), dtype=torch.int32, device=dev))
+        slots = []
+        for a, b in chunks:                                              # a workspace per call: the result views its pair table
+            r = K.regions_overlap_labels(p[a:b], t[a:b], cap_p, cap_t, pairs, cp[a:b] if want[0] else None, ct[a:b] if want[1] else None,
+                                         **{k: tabs[k][a:b] for k in names}, want_counts=want)
+            slots.append((r["slot_keys"], r["slot_counts"]))
+        keys, counts = slots[0] if len(slots) == 1 else (torch.cat([s[i] for s in slots]) for i in (0, 1))
+        return OverlapTable(cp, ct, cap_p, cap_t, *(tabs[k] for k in ("area_pred", "area_truth", "n_pairs", "dropped", "iou_partner",
+                                                                      "iou_inter", "inter_partner_truth", "inter_truth",
+                                                                      "inter_partner_pred", "inter_pred")), keys, counts)
+
+    want = own
+    if caps is None:
+        if own[0] or own[1]:
+            run(1, 1, 1, own)                                            # the pass that finds the largest labels
+        top = torch.stack([cp.max(), ct.max()]).cpu()                    # one synchronisation
+        caps, want = (max(1, int(top[0])), max(1, int(top[1]))), (False, False)
+    if max_pairs is not None:
+        return run(caps[0], caps[1], int(max_pairs), want)
+    most = p.shape[1] * p.shape[2]                                       # an image has no more pairs than pixels
+    pairs = min(4 * (caps[0] + caps[1]), most)
+    while True:
+        table = run(caps[0], caps[1], pairs, want)
+        if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
+            return table
+        pairs = min(2 * pairs, most)

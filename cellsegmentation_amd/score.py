@@ -12,7 +12,8 @@ descending), and ``DetectResult.score`` scores the device-resident detections of
 
 ``label_score`` is the object-level counterpart for label images: from the integer tables of ``regions.match_labels`` (areas,
 partner at IoU > 1/2, intersection) it forms TP / FP / FN at an IoU threshold, the same precision / recall / F1, and segmentation
-and panoptic quality -- a few thousand rows of host float64 arithmetic.
+and panoptic quality -- a few thousand rows of host float64 arithmetic.  ``overlap_score`` does the same for the tables of
+``regions.overlap_labels`` (best partner by IoU and by intersection, below IoU 1/2 too): AJI and object-level Dice.
 """
 import math
 from dataclasses import dataclass
@@ -264,3 +265,71 @@ def label_score(area_pred, area_truth, match, inter, iou_threshold=0.5):
     sq = np.asarray([np.sum(iou[n][hit[n]]) / tp[n] if tp[n] else 0.0 for n in range(len(tp))], np.float64)
     return LabelScore(n_pred.astype(np.int64), n_truth.astype(np.int64), tp.astype(np.int64), fp.astype(np.int64), fn.astype(np.int64),
                       p.astype(np.float64), r.astype(np.float64), f1.astype(np.float64), sq, sq * f1)
+
+
+@dataclass
+class OverlapScore:
+    """Per image (arrays of length N): ``n_pred``, ``n_truth`` (objects: labels that own a pixel, within the capacity), ``n_pairs``
+    (the (pred, truth) pairs that share a pixel), ``aji_inter``, ``aji_union`` int64; ``aji``, ``dice_obj`` float64."""
+    n_pred: np.ndarray
+    n_truth: np.ndarray
+    n_pairs: np.ndarray
+    aji_inter: np.ndarray
+    aji_union: np.ndarray
+    aji: np.ndarray
+    dice_obj: np.ndarray
+
+
+def overlap_score(area_pred, area_truth, iou_partner, iou_inter, inter_partner_truth, inter_truth, inter_partner_pred, inter_pred,
+                  n_pairs):
+    """The integer tables of ``regions.overlap_labels`` on the host (``area_pred``, ``inter_partner_pred``, ``inter_pred`` [N,
+    cap_pred]; the others [N, cap_truth]; ``n_pairs`` [N]) -> ``OverlapScore``, in numpy float64.  An object is a label whose
+    area is positive.  Per image, with Ap / At the areas:
+
+    * AJI (aggregated Jaccard index).  Every truth object g with a best-IoU partner j = ``iou_partner`` adds ``I = iou_inter`` to C
+      and ``Ap[j] + At[g] - I`` to U and marks j used; one without a partner adds ``At[g]`` to U.  A pred object may serve several
+      truth objects and adds a union for each.  Every pred object never used adds ``Ap`` to U.  ``aji = C / U``, one float64
+      quotient of the two integers ``aji_inter`` / ``aji_union``; 1.0 when U = 0 (no object on either side, the convention of
+      ``precision_recall`` for empty sides).
+    * Object-level Dice.  ``dice_obj = (T + P) / 2`` with ``T = sum_g (At[g] / sum At) * 2 I / (Ap[s] + At[g])`` over the truth
+      objects in ascending label, s = ``inter_partner_truth`` and I = ``inter_truth`` (the term is 0 without a partner), and P the
+      same sum over the pred objects with ``inter_partner_pred`` / ``inter_pred``.  A side without objects contributes 0; 1.0 when
+      both sides have none.
+
+    Partners by IoU for AJI and by intersection for Dice, ties to the lower label: the rules of ``regions.overlap_labels``."""
+    ap, at, jp, ji, sp, si, gp, gi = (np.asarray(x).astype(np.int64) for x in (
+        area_pred, area_truth, iou_partner, iou_inter, inter_partner_truth, inter_truth, inter_partner_pred, inter_pred))
+    npairs = np.asarray(n_pairs).astype(np.int64)
+    if ap.ndim != 2 or at.ndim != 2 or at.shape[0] != ap.shape[0] or any(x.shape != at.shape for x in (jp, ji, sp, si)) or any(
+            x.shape != ap.shape for x in (gp, gi)) or npairs.shape != ap.shape[:1]:
+        raise ValueError("overlap_score: expected area_pred, inter_partner_pred, inter_pred [N, cap_pred], area_truth, iou_partner, "
+                         "iou_inter, inter_partner_truth, inter_truth [N, cap_truth] and n_pairs [N]")
+    for part, cap in ((jp, ap.shape[1]), (sp, ap.shape[1]), (gp, at.shape[1])):
+        if part.size and (int(part.min()) < 0 or int(part.max()) > cap):
+            raise ValueError("overlap_score: a partner table holds a label outside the other side's areas")
+    N = ap.shape[0]
+    out = OverlapScore(*(np.zeros((N,), np.int64) for _ in range(5)), *(np.zeros((N,), np.float64) for _ in range(2)))
+    for n in range(N):
+        used = np.zeros((ap.shape[1] + 1,), bool)
+        C = U = 0
+        for g in np.nonzero(at[n])[0]:
+            j = int(jp[n, g])
+            if j:
+                C += int(ji[n, g])
+                U += int(ap[n, j - 1]) + int(at[n, g]) - int(ji[n, g])
+                used[j] = True
+            else:
+                U += int(at[n, g])
+        U += int(ap[n][(ap[n] > 0) & ~used[1:]].sum())
+        sides = []
+        for own, other, partner, inter in ((at[n], ap[n], sp[n], si[n]), (ap[n], at[n], gp[n], gi[n])):
+            total, acc = np.float64(own.sum()), np.float64(0.0)
+            for k in np.nonzero(own)[0]:
+                if partner[k]:
+                    acc += (np.float64(own[k]) / total) * (np.float64(2 * inter[k]) / np.float64(other[partner[k] - 1] + own[k]))
+            sides.append(acc)
+        n_truth, n_pred = int((at[n] > 0).sum()), int((ap[n] > 0).sum())
+        out.n_pred[n], out.n_truth[n], out.n_pairs[n], out.aji_inter[n], out.aji_union[n] = n_pred, n_truth, npairs[n], C, U
+        out.aji[n] = np.float64(C) / np.float64(U) if U else 1.0
+        out.dice_obj[n] = 0.5 * (sides[0] + sides[1]) if n_pred or n_truth else 1.0
+    return out

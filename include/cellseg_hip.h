@@ -668,6 +668,31 @@ int cs_regions_match_labels(const int32_t* pred, const int32_t* truth, int N, in
                             int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred, int32_t* area_truth, int32_t* match,
                             int32_t* inter, int32_t* match_truth, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- every overlapping pair of two label images, and each label's best partner (csrc/regions.hip) ----------------------------
+ * pred, truth, the treatment of labels (<= 0 and above the side's capacity = background; counts_pred / counts_truth, int32 [N] or
+ * NULL, WRITTEN with the largest labels), area_pred, area_truth and the launch contract are those of cs_regions_match_labels.
+ * I(p, g) = the pixels of image n that carry pred label p and truth label g, both within capacity.  The pairs with I > 0 are held
+ * in a per-image open-addressing hash table of slots = the smallest power of two >= 2 max_pairs entries at the START of the
+ * workspace: keys uint64 [N][slots], key = (p << 32) | g, 0 = empty, then counts int32 [N][slots] = I(p, g); the caller may read
+ * both after the call (the rest of the workspace is scratch).  Which slot a pair occupies may differ from run to run; the set of
+ * (key, count) and every output below do not.  Probing is bounded by slots: a run of pixels whose pair finds no slot is left out
+ * and adds 1 to dropped[n] (int32 [N]) -- the pair list and the partners of image n are then incomplete; the areas are not.
+ * n_pairs int32 [N] = the occupied slots.  Per truth label g (row g - 1 of [N][cap_truth] int32 tables):
+ *   iou_partner / iou_inter: the pred label p with I(p, g) > 0 that maximises I / (Ap[p] + At[g] - I), fractions compared by
+ *     cross-multiplication in 64-bit integers, ties to the lower p; 0 = none; and I(p, g).
+ *   inter_partner_truth / inter_truth: the pred label of largest I(p, g), ties to the lower p; 0 = none; and that I.
+ * Per pred label p ([N][cap_pred]): inter_partner_pred / inter_pred: the truth label of largest I(p, g), ties to the lower g.
+ * All integer and independent of launch and arrival order.  Need cap_pred, cap_truth >= 1, 1 <= max_pairs <= 2^29, N cap_pred,
+ * N cap_truth, N slots < 2^31.  workspace: 16-byte aligned, >= cs_regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs)
+ * bytes (0 for sizes a call would refuse): 12 N slots + 8 N (2 cap_truth + cap_pred) bytes and padding, never a cap_pred x
+ * cap_truth table.  Four launches. */
+size_t cs_regions_overlap_workspace(int N, int cap_pred, int cap_truth, int max_pairs);
+int cs_regions_overlap_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                              int max_pairs, int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred, int32_t* area_truth,
+                              int32_t* n_pairs, int32_t* dropped, int32_t* iou_partner, int32_t* iou_inter,
+                              int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred, int32_t* inter_pred,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
  * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of
  * cs_detect_cluster as they are; gt int32 [G][2] with gt_off int64 [N + 1] are the annotations, in the same coordinate convention.

@@ -13,6 +13,12 @@ masks shifted by a few pixels and relabelled.  Device events around the whole ca
 against tests/match_ref.py, the whole-slide image against a sparse pair count.
 
     python tools/score_microbench.py --labels [--json PATH]
+
+--labels --overlap also times ``regions.overlap_labels`` (every overlapping pair and each label's best partner: the tables behind
+AJI and object-level Dice) on the same label pairs with the same ``max_regions`` and ``max_pairs = 4 max_regions``, timed the same
+way right after ``match_labels``; the pair list of two images is checked against a sparse pair count on the host.
+
+    python tools/score_microbench.py --labels --overlap [--json PATH]
 """
 import argparse
 import json
@@ -58,6 +64,14 @@ def sparse_match(pred, truth, cap):
     return match[1:], shared[1:]
 
 
+def sparse_pairs(pred, truth, cap):
+    """one image pair -> (pred, truth, inter) int64 of the distinct pairs of positive labels within cap, sorted"""
+    p, g = (np.where((x < 0) | (x > cap), 0, x).astype(np.int64).ravel() for x in (pred, truth))
+    both = (p > 0) & (g > 0)
+    keys, inter = np.unique(p[both] * (cap + 1) + g[both], return_counts=True)
+    return keys // (cap + 1), keys % (cap + 1), inter.astype(np.int64)
+
+
 def labels_main(args):
     import match_ref as M
     import regions_microbench as RM
@@ -83,10 +97,23 @@ def labels_main(args):
             else:
                 match, shared = sparse_match(hp[i], ht[i], cap)
                 ok &= bool(np.array_equal(got["match"], match) and np.array_equal(got["inter"], shared))
+        extra = {}
+        if args.overlap:
+            pairs = 4 * cap
+            over_ms, over_ts = time_dev(lambda: G.overlap_labels(pred, truth, max_regions=cap, max_pairs=pairs), 7)
+            o = G.overlap_labels(pred, truth, max_regions=cap, max_pairs=pairs)
+            image, op, og, oi = o.pairs()
+            for i in range(min(2, len(masks))):
+                want = sparse_pairs(hp[i], ht[i], cap)
+                ok &= all(np.array_equal(a[image == i], b) for a, b in zip((op, og, oi), want))
+            ok &= bool(torch.equal(o.area_pred, t.area_pred) and torch.equal(o.area_truth, t.area_truth))
+            os_ = o.score()
+            extra = {"overlap_labels_ms": over_ms, "overlap_labels_ms_all": over_ts, "max_pairs": pairs, "pairs": int(len(image)),
+                     "dropped": int(o.dropped.sum()), "aji_mean": float(os_.aji.mean()), "dice_obj_mean": float(os_.dice_obj.mean())}
         s = t.score()
         res[name] = {"match_labels_ms": match_ms, "match_labels_ms_all": ts, "two_measure_labels_ms": twice_ms, "max_regions": cap,
                      "objects_pred": int(s.n_pred.sum()), "objects_truth": int(s.n_truth.sum()), "matched": int(s.tp.sum()),
-                     "pq_mean": float(s.pq.mean()), "overflowed": int(t.overflowed().sum()), "equal_to_host": bool(ok)}
+                     "pq_mean": float(s.pq.mean()), "overflowed": int(t.overflowed().sum()), **extra, "equal_to_host": bool(ok)}
         print(json.dumps({name: res[name]}), flush=True)
     if args.json:
         with open(args.json, "w") as f:
@@ -98,12 +125,15 @@ def labels_main(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--labels", action="store_true", help="time regions.match_labels next to two measure_labels calls instead")
+    ap.add_argument("--overlap", action="store_true", help="with --labels: also time regions.overlap_labels on the same label pairs")
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--cells", type=int, default=32, help="annotations and detections per image")
     ap.add_argument("--path", choices=("wave", "block"), default="wave", help="block: the 256-thread path at any size")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", default=None, help="also write the result to this file")
     args = ap.parse_args()
+    if args.overlap and not args.labels:
+        ap.error("--overlap goes with --labels")
     if args.labels:
         return labels_main(args)
     if args.path == "wave" and args.cells > 64:
