@@ -295,61 +295,68 @@ __device__ __forceinline__ bool run_of(unsigned long long live, unsigned long lo
     return (start >> lane) & 1;
 }
 
-// A wave takes 64 consecutive columns of ONE image row (the walk is over (n, r, 64-column segment), so no wave straddles a row
-// end).  Horizontal neighbours in the foreground are one component, so a maximal run of foreground lanes has one table row: its
-// head lane looks the number up once and issues one set of atomics for the whole run -- length, closed-form column sum, and the
-// intensity sum / maximum from a segmented shuffle reduction.  REDUCE = false (A/B flavour only) is the per-pixel form: every
-// foreground lane is a run of one.  lab: the root of every pixel; num: the number of every foreground root.
-// LABELS: lab is a label image instead (m and num are not read): foreground = a positive label, table row = label - 1, and a run
-// also starts where the label differs from the left neighbour's -- neighbouring foreground pixels may belong to different cells.
-// The head lanes also raise maxlab[n] (or NULL) to their label.
-template <bool REDUCE, bool LABELS>
-__global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict__ m, const uint8_t* __restrict__ v, int N, int H, int W,
-                                                      const int32_t* __restrict__ lab, const int32_t* __restrict__ num, int cap, Tables t,
-                                                      int32_t* __restrict__ maxlab) {
+// The walk of every kernel that works on horizontal runs: over (image, row, 64-column segment) items, one wave per item, four per
+// workgroup of 256 threads (grid: walk_grid(N, H, W)).  body(n, r, c, p): image n, row r, column c = 64 segment + lane, pixel index
+// p = (n H + r) W + c.  A wave takes 64 consecutive columns of ONE image row, so it never straddles a row end; n and r are
+// wave-uniform, and the body is called with the WHOLE wave, the lanes with c >= W included (p is then no pixel of that row), so it
+// may ballot and shuffle.  `return` in the body ends the item (by the whole wave where a ballot or shuffle would still follow).
+template <typename Body>
+__device__ __forceinline__ void walk_row_segments(int N, int H, int W, Body body) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned segs = (unsigned)(W + 63) >> 6;
     const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
-    const long long total = (long long)N * H * W;
     for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
         const unsigned row = (unsigned)it / segs;                      // n H + r
         const int c = (int)((unsigned)it - row * segs) * 64 + lane;
         const int n = (int)(row / (unsigned)H), r = (int)(row - (unsigned)n * (unsigned)H);
-        const long long p = (long long)row * W + c;
+        body(n, r, c, (long long)row * W + c);
+    }
+}
+
+// Horizontal neighbours in the foreground are one component, so a maximal run of foreground lanes has one table row: its head
+// lane looks the number up once and issues one set of atomics for the whole run -- length, closed-form column sum, and the
+// intensity sum / maximum from a segmented shuffle reduction.  lab: every pixel's root; num: every foreground root's number.
+// LABELS: lab is a label image instead (m and num are not read): foreground = a positive label, table row = label - 1, and a run
+// also starts where the label differs from the left neighbour's -- neighbouring foreground pixels may belong to different cells.
+// The head lanes also raise maxlab[n] (or NULL) to their label.
+template <bool LABELS>
+__global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict__ m, const uint8_t* __restrict__ v, int N, int H, int W,
+                                                      const int32_t* __restrict__ lab, const int32_t* __restrict__ num, int cap, Tables t,
+                                                      int32_t* __restrict__ maxlab) {
+    const int lane = threadIdx.x & 63;
+    const long long total = (long long)N * H * W;
+    walk_row_segments(N, H, W, [&](int n, int r, int c, long long p) {
         const int l = (LABELS && c < W) ? lab[p] : 0;
         const bool fg = LABELS ? l > 0 : (c < W && m[p] != 0);
         const unsigned long long bal = __ballot(fg);
-        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
+        if (bal == 0) return;
         int s = (v && fg) ? v[p] : 0, mx = s;
-        int len = 1;
-        bool head = fg;
-        if (REDUCE) {
-            // LABELS: a run also breaks where the lane carries another label than its left neighbour (lane 0 gets its own back)
-            head = run_of(bal, LABELS ? __ballot(fg && l != __shfl_up(l, 1)) : 0ull, lane, len);
-            if (v) {
-                const int last = fg ? lane + len - 1 : lane;
+        int len;
+        // LABELS: a run also breaks where the lane carries another label than its left neighbour (lane 0 gets its own back)
+        const bool head = run_of(bal, LABELS ? __ballot(fg && l != __shfl_up(l, 1)) : 0ull, lane, len);
+        if (v) {
+            const int last = fg ? lane + len - 1 : lane;
 #pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {               // lane i: the sum / maximum over [i, min(i + 2 off - 1, last)]
-                    const int os = __shfl_down(s, off), om = __shfl_down(mx, off);
-                    if (lane + off <= last) {
-                        s += os;
-                        mx = max(mx, om);
-                    }
+            for (int off = 1; off < 64; off <<= 1) {                   // lane i: the sum / maximum over [i, min(i + 2 off - 1, last)]
+                const int os = __shfl_down(s, off), om = __shfl_down(mx, off);
+                if (lane + off <= last) {
+                    s += os;
+                    mx = max(mx, om);
                 }
             }
         }
-        if (!head) continue;
+        if (!head) return;
         int k;
         if (LABELS) {
             k = l - 1;
             if (maxlab) raise_to(maxlab + n, l);
         } else {
             const int root = lab[p];
-            if ((unsigned)root >= (unsigned)total) continue;           // never with a workspace that label_into filled
+            if ((unsigned)root >= (unsigned)total) return;             // never with a workspace that label_into filled
             k = num[root] - 1;
         }
-        if ((unsigned)k >= (unsigned)cap) continue;
+        if ((unsigned)k >= (unsigned)cap) return;
         const long long q = (long long)n * cap + k;
         __hip_atomic_fetch_add(t.area + q, len, __ATOMIC_RELAXED, kGlobal);
         __hip_atomic_fetch_add(t.sums + 2 * q, (long long)r * len, __ATOMIC_RELAXED, kGlobal);
@@ -362,7 +369,46 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
             __hip_atomic_fetch_add(t.isum + q, (long long)s, __ATOMIC_RELAXED, kGlobal);
             raise_to(t.imax + q, mx);
         }
-    }
+    });
+}
+
+// ---- two label images walked at once: what match and overlap share ---------------------------------------------------------------
+struct PairSides {
+    int32_t *area_pred, *area_truth;   // [N][cap_pred], [N][cap_truth]
+    int32_t *maxp, *maxt;              // [N] or NULL: the largest pred / truth label
+    int cap_pred, cap_truth;
+};
+
+// element i of an init launch over at least max(N cap_pred, N cap_truth) >= N elements
+__device__ __forceinline__ void pair_sides_init(const PairSides& s, int N, long long i) {
+    if (i < (long long)N * s.cap_pred) s.area_pred[i] = 0;
+    if (i < (long long)N * s.cap_truth) s.area_truth[i] = 0;
+    if (i < N && s.maxp) s.maxp[i] = 0;
+    if (i < N && s.maxt) s.maxt[i] = 0;
+}
+
+// A run is a stretch of a wave's lanes on which both labels are constant and at least one is positive (0 and below = background);
+// it starts where either label differs from the left neighbour's.  head: this lane acts for the whole run of len lanes with pred
+// label p and truth label g, both clamped: a label above its side's capacity is background.  ACCOUNT: a head lane first raises
+// image n's maxima to its labels as they are, and after the clamp adds the run to the areas.  Called by the whole wave.
+struct PairRun { bool head; int len, p, g; };
+template <bool ACCOUNT>
+__device__ __forceinline__ PairRun pair_run(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, const PairSides& s, int n,
+                                            int W, int c, long long px) {
+    PairRun u{false, 1, c < W ? max(pred[px], 0) : 0, c < W ? max(truth[px], 0) : 0};
+    const bool live = (u.p | u.g) != 0;
+    const unsigned long long bal = __ballot(live);
+    if (bal == 0) return u;
+    const int pl = __shfl_up(u.p, 1), gl = __shfl_up(u.g, 1);          // (lane 0 gets its own back)
+    u.head = run_of(bal, __ballot(live && (u.p != pl || u.g != gl)), threadIdx.x & 63, u.len);
+    if (!u.head) return u;
+    if (ACCOUNT && s.maxp && u.p) raise_to(s.maxp + n, u.p);
+    if (ACCOUNT && s.maxt && u.g) raise_to(s.maxt + n, u.g);
+    u.p = u.p <= s.cap_pred ? u.p : 0;
+    u.g = u.g <= s.cap_truth ? u.g : 0;
+    if (ACCOUNT && u.g) __hip_atomic_fetch_add(s.area_truth + (long long)n * s.cap_truth + u.g - 1, u.len, __ATOMIC_RELAXED, kGlobal);
+    if (ACCOUNT && u.p) __hip_atomic_fetch_add(s.area_pred + (long long)n * s.cap_pred + u.p - 1, u.len, __ATOMIC_RELAXED, kGlobal);
+    return u;
 }
 
 // ---- label image against label image: object matches at IoU > 1/2 -----------------------------------------------------------------
@@ -370,89 +416,53 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
 // set exactly where more than half of p's pixels carry a truth label with bit b set: B = bit_length(cap_truth) counters per pred
 // label spell the only possible partner, one more pass counts its intersection, and the test itself is made on exact integers.
 struct Match {
-    int32_t* area_pred;    // [N][cap_pred]
-    int32_t* area_truth;   // [N][cap_truth]
+    PairSides s;
     int32_t* match;        // [N][cap_pred]   the truth label matched, 0 = none
     int32_t* inter;        // [N][cap_pred]   I(p, match)
     int32_t* match_truth;  // [N][cap_truth]  the pred label matched, 0 = none
     int32_t* vote;         // [N][cap_pred][B]
     int32_t* cand;         // [N][cap_pred]
-    int32_t* maxp;         // [N] or NULL: the largest pred label
-    int32_t* maxt;         // [N] or NULL: the largest truth label
-    int cap_pred, cap_truth, B;
+    int B;
 };
 
 __global__ __launch_bounds__(256) void match_init_kernel(int N, Match t) {
-    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth, nv = np * t.B;
+    const long long np = (long long)N * t.s.cap_pred, nt = (long long)N * t.s.cap_truth, nv = np * t.B;
     const long long all = nv > nt ? nv : nt;                           // >= np >= N
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        pair_sides_init(t.s, N, i);
         if (i < nv) t.vote[i] = 0;
-        if (i < np) {
-            t.area_pred[i] = 0;
-            t.inter[i] = 0;
-        }
-        if (i < nt) {
-            t.area_truth[i] = 0;
-            t.match_truth[i] = 0;
-        }
-        if (i < N) {
-            if (t.maxp) t.maxp[i] = 0;
-            if (t.maxt) t.maxt[i] = 0;
-        }
+        if (i < np) t.inter[i] = 0;
+        if (i < nt) t.match_truth[i] = 0;
     }
 }
 
-// The walk of measure_kernel over two label images at once.  A run is a stretch of lanes on which both labels are constant and at
-// least one is positive; its head lane issues the atomics for the whole run.  A label above its side's capacity counts towards
-// that side's maximum and is background otherwise.  VOTE: the areas of both sides and, for every set bit b of the truth label,
-// vote[p][b] += len.  Otherwise: inter[p] += len on the runs whose truth label is p's candidate.
+// VOTE: the accounting of both sides and, for every set bit b of the truth label, vote[p][b] += len.  Otherwise: inter[p] += len
+// on the runs whose truth label is p's candidate.
 template <bool VOTE>
 __global__ __launch_bounds__(256) void match_walk_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int N, int H,
                                                          int W, Match t) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned segs = (unsigned)(W + 63) >> 6;
-    const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
-    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
-        const unsigned row = (unsigned)it / segs;                      // n H + r
-        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
-        const int n = (int)(row / (unsigned)H);
-        const long long px = (long long)row * W + c;
-        const int p = c < W ? max(pred[px], 0) : 0, g = c < W ? max(truth[px], 0) : 0;
-        const bool live = (p | g) != 0;
-        const unsigned long long bal = __ballot(live);
-        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
-        const int pl = __shfl_up(p, 1), gl = __shfl_up(g, 1);          // (lane 0 gets its own back)
-        int len;
-        const bool head = run_of(bal, __ballot(live && (p != pl || g != gl)), lane, len);
-        if (!head) continue;
+    walk_row_segments(N, H, W, [&](int n, int, int c, long long px) {
+        const PairRun u = pair_run<VOTE>(pred, truth, t.s, n, W, c, px);
+        if (!u.head || !u.p) return;
+        const long long q = (long long)n * t.s.cap_pred + u.p - 1;     // p's row
         if (VOTE) {
-            if (t.maxp && p) raise_to(t.maxp + n, p);
-            if (t.maxt && g) raise_to(t.maxt + n, g);
+            for (unsigned bits = (unsigned)u.g; bits; bits &= bits - 1)   // g <= cap_truth < 2^B: every set bit is below B
+                __hip_atomic_fetch_add(t.vote + q * t.B + __builtin_ctz(bits), u.len, __ATOMIC_RELAXED, kGlobal);
+        } else if (u.g && t.cand[q] == u.g) {
+            __hip_atomic_fetch_add(t.inter + q, u.len, __ATOMIC_RELAXED, kGlobal);
         }
-        const int pc = p <= t.cap_pred ? p : 0, gc = g <= t.cap_truth ? g : 0;
-        const long long q = (long long)n * t.cap_pred + pc - 1;        // p's row, where pc > 0
-        if (VOTE) {
-            if (gc) __hip_atomic_fetch_add(t.area_truth + (long long)n * t.cap_truth + gc - 1, len, __ATOMIC_RELAXED, kGlobal);
-            if (!pc) continue;
-            __hip_atomic_fetch_add(t.area_pred + q, len, __ATOMIC_RELAXED, kGlobal);
-            for (unsigned bits = (unsigned)gc; bits; bits &= bits - 1)   // gc <= cap_truth < 2^B: every set bit is below B
-                __hip_atomic_fetch_add(t.vote + q * t.B + __builtin_ctz(bits), len, __ATOMIC_RELAXED, kGlobal);
-        } else if (pc && gc && t.cand[q] == gc) {
-            __hip_atomic_fetch_add(t.inter + q, len, __ATOMIC_RELAXED, kGlobal);
-        }
-    }
+    });
 }
 
 // One thread per pred label: the truth label spelled by the bits that more than half of the label's pixels voted for.  Without a
 // majority partner the votes can spell any number, one above cap_truth included: that is no candidate.
 __global__ __launch_bounds__(256) void match_candidate_kernel(long long rows, Match t) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
-        const long long area = t.area_pred[i];
+        const long long area = t.s.area_pred[i];
         int g = 0;
         for (int b = 0; b < t.B; ++b)
             if (2 * (long long)t.vote[i * t.B + b] > area) g |= 1 << b;
-        t.cand[i] = g <= t.cap_truth ? g : 0;
+        t.cand[i] = g <= t.s.cap_truth ? g : 0;
     }
 }
 
@@ -461,16 +471,16 @@ __global__ __launch_bounds__(256) void match_candidate_kernel(long long rows, Ma
 __global__ __launch_bounds__(256) void match_decide_kernel(long long rows, Match t) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
         const int g = t.cand[i];
-        const long long n = i / t.cap_pred;
+        const long long n = i / t.s.cap_pred;
         const long long in = t.inter[i];
         bool ok = false;
         if (g > 0) {
-            const long long uni = (long long)t.area_pred[i] + (long long)t.area_truth[n * t.cap_truth + g - 1] - in;
+            const long long uni = (long long)t.s.area_pred[i] + (long long)t.s.area_truth[n * t.s.cap_truth + g - 1] - in;
             ok = 2 * in > uni;
         }
         t.match[i] = ok ? g : 0;
         if (ok)
-            t.match_truth[n * t.cap_truth + g - 1] = (int)(i - n * t.cap_pred) + 1;
+            t.match_truth[n * t.s.cap_truth + g - 1] = (int)(i - n * t.s.cap_pred) + 1;
         else
             t.inter[i] = 0;
     }
@@ -483,8 +493,7 @@ __global__ __launch_bounds__(256) void match_decide_kernel(long long rows, Match
 // Which slot a pair lands in depends on the order of arrival; the set of (key, count) does not (integer sums), and everything
 // derived from the table is a maximum under a total order of the pairs, which does not depend on where they sit.
 struct Overlap {
-    int32_t* area_pred;             // [N][cap_pred]
-    int32_t* area_truth;            // [N][cap_truth]
+    PairSides s;
     int32_t* n_pairs;               // [N]  occupied slots
     int32_t* dropped;               // [N]  runs that found no slot
     int32_t* iou_partner;           // [N][cap_truth]  the pred label of largest IoU, 0 = none
@@ -498,33 +507,26 @@ struct Overlap {
     unsigned long long* best_iou;   // [N][cap_truth]  (I << 32) | p, 0 = none
     unsigned long long* best_it;    // [N][cap_truth]  (I << 32) | ~p: the largest I, then the lowest p
     unsigned long long* best_ip;    // [N][cap_pred]   (I << 32) | ~g
-    int32_t* maxp;                  // [N] or NULL: the largest pred label
-    int32_t* maxt;                  // [N] or NULL: the largest truth label
-    int cap_pred, cap_truth, slots;
+    int slots;
 };
 
 __global__ __launch_bounds__(256) void overlap_init_kernel(int N, Overlap t) {
-    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth, ns = (long long)N * t.slots;
+    const long long np = (long long)N * t.s.cap_pred, nt = (long long)N * t.s.cap_truth, ns = (long long)N * t.slots;
     const long long all = max(ns, max(np, nt));                        // >= N
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        pair_sides_init(t.s, N, i);
         if (i < ns) {
             t.keys[i] = 0;
             t.cnt[i] = 0;
         }
-        if (i < np) {
-            t.area_pred[i] = 0;
-            t.best_ip[i] = 0;
-        }
+        if (i < np) t.best_ip[i] = 0;
         if (i < nt) {
-            t.area_truth[i] = 0;
             t.best_iou[i] = 0;
             t.best_it[i] = 0;
         }
         if (i < N) {
             t.n_pairs[i] = 0;
             t.dropped[i] = 0;
-            if (t.maxp) t.maxp[i] = 0;
-            if (t.maxt) t.maxt[i] = 0;
         }
     }
 }
@@ -559,40 +561,23 @@ __device__ __forceinline__ bool overlap_insert(unsigned long long* keys, int32_t
     return false;
 }
 
-// match_walk_kernel's walk: the areas and maxima of both sides, and every run on which both labels are positive (and within their
-// capacities) adds its length to its pair's slot.
+// The accounting of both sides, and every run on which both labels are positive (and within their capacities) adds its length to
+// its pair's slot.
 __global__ __launch_bounds__(256) void overlap_walk_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int N, int H,
                                                            int W, Overlap t) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned segs = (unsigned)(W + 63) >> 6;
-    const long long items = (long long)N * H * segs;                   // <= N H W < 2^31
-    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
-        const unsigned row = (unsigned)it / segs;                      // n H + r
-        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
-        const int n = (int)(row / (unsigned)H);
-        const long long px = (long long)row * W + c;
-        const int p = c < W ? max(pred[px], 0) : 0, g = c < W ? max(truth[px], 0) : 0;
-        const bool live = (p | g) != 0;
-        const unsigned long long bal = __ballot(live);
-        if (bal == 0) continue;                                        // the whole wave: `it` is uniform
-        const int pl = __shfl_up(p, 1), gl = __shfl_up(g, 1);          // (lane 0 gets its own back)
-        int len;
-        const bool head = run_of(bal, __ballot(live && (p != pl || g != gl)), lane, len);
-        if (!head) continue;
-        if (t.maxp && p) raise_to(t.maxp + n, p);
-        if (t.maxt && g) raise_to(t.maxt + n, g);
-        const int pc = p <= t.cap_pred ? p : 0, gc = g <= t.cap_truth ? g : 0;
-        if (gc) __hip_atomic_fetch_add(t.area_truth + (long long)n * t.cap_truth + gc - 1, len, __ATOMIC_RELAXED, kGlobal);
-        if (pc) __hip_atomic_fetch_add(t.area_pred + (long long)n * t.cap_pred + pc - 1, len, __ATOMIC_RELAXED, kGlobal);
-        if (!pc || !gc) continue;
+    // The two counters as locals: read through `t` inside the body, the compiler merges the two adds below into one whose pointer
+    // it picks from `t` by a run-time index, and that keeps a copy of those 16 bytes of `t` in scratch (24 bytes, hipcc of ROCm 7).
+    int32_t *const n_pairs = t.n_pairs, *const dropped = t.dropped;
+    walk_row_segments(N, H, W, [&](int n, int, int c, long long px) {
+        const PairRun u = pair_run<true>(pred, truth, t.s, n, W, c, px);
+        if (!u.head || !u.p || !u.g) return;
         const long long base = (long long)n * t.slots;                 // < N slots < 2^31
         bool fresh;
-        if (!overlap_insert(t.keys + base, t.cnt + base, (unsigned)t.slots - 1, pc, gc, len, &fresh))
-            __hip_atomic_fetch_add(t.dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
+        if (!overlap_insert(t.keys + base, t.cnt + base, (unsigned)t.slots - 1, u.p, u.g, u.len, &fresh))
+            __hip_atomic_fetch_add(dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
         else if (fresh)
-            __hip_atomic_fetch_add(t.n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
-    }
+            __hip_atomic_fetch_add(n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+    });
 }
 
 // One thread per slot, after the walk: the areas and counts are final.  Best intersection of either side: an atomic maximum of
@@ -607,18 +592,18 @@ __global__ __launch_bounds__(256) void overlap_reduce_kernel(long long n_slots, 
         const long long n = i / t.slots;
         const unsigned p = (unsigned)(key >> 32), g = (unsigned)key;
         const unsigned long long I = (unsigned)t.cnt[i];
-        const long long qp = n * t.cap_pred + p - 1, qg = n * t.cap_truth + g - 1;
+        const long long qp = n * t.s.cap_pred + p - 1, qg = n * t.s.cap_truth + g - 1;
         __hip_atomic_fetch_max(t.best_it + qg, (I << 32) | (unsigned)~p, __ATOMIC_RELAXED, kGlobal);
         __hip_atomic_fetch_max(t.best_ip + qp, (I << 32) | (unsigned)~g, __ATOMIC_RELAXED, kGlobal);
-        const long long at = t.area_truth[qg];
-        const unsigned long long U = (unsigned long long)(t.area_pred[qp] + at - (long long)I);
+        const long long at = t.s.area_truth[qg];
+        const unsigned long long U = (unsigned long long)(t.s.area_pred[qp] + at - (long long)I);
         const unsigned long long mine = (I << 32) | p;
         unsigned long long held = __hip_atomic_load(t.best_iou + qg, __ATOMIC_RELAXED, kGlobal);
         for (;;) {
             if (held != 0) {
                 const unsigned hp = (unsigned)held;
                 const unsigned long long hI = held >> 32;
-                const unsigned long long hU = (unsigned long long)(t.area_pred[n * t.cap_pred + hp - 1] + at - (long long)hI);
+                const unsigned long long hU = (unsigned long long)(t.s.area_pred[n * t.s.cap_pred + hp - 1] + at - (long long)hI);
                 const unsigned long long a = I * hU, b = hI * U;
                 if (!(a > b || (a == b && p < hp))) break;             // the holder is as good or better
             }
@@ -629,7 +614,7 @@ __global__ __launch_bounds__(256) void overlap_reduce_kernel(long long n_slots, 
 
 // One thread per label of either side: the packed winners into the tables.
 __global__ __launch_bounds__(256) void overlap_finish_kernel(int N, Overlap t) {
-    const long long np = (long long)N * t.cap_pred, nt = (long long)N * t.cap_truth;
+    const long long np = (long long)N * t.s.cap_pred, nt = (long long)N * t.s.cap_truth;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < max(np, nt); i += (long long)gridDim.x * 256) {
         if (i < nt) {
             const unsigned long long q = t.best_iou[i], b = t.best_it[i];
@@ -691,27 +676,19 @@ __device__ __forceinline__ int nearest_seed(const int4* __restrict__ rec, int q,
     return (int)(unsigned)best + 1;
 }
 
-// A wave takes 64 consecutive columns of one image row, as measure_kernel.  head[root] > 0 is the label itself (a component
-// without a seed, numbered by number_into<true>), < 0 the chain to walk.  Where every foreground lane of the wave has the same root
-// (the inside of a cell clump, most waves) the chain is read through wave-uniform addresses and no lane diverges; otherwise every
-// lane walks its own.  Background writes 0: the output needs no clearing.
+// head[root] > 0 is the label itself (a component without a seed, numbered by number_into<true>), < 0 the chain to walk.  Where
+// every foreground lane of the wave has the same root (the inside of a cell clump, most waves) the chain is read through
+// wave-uniform addresses and no lane diverges; otherwise every lane walks its own.  Background writes 0: the output needs no
+// clearing.
 __global__ __launch_bounds__(256) void split_assign_kernel(const uint8_t* __restrict__ m, int N, int H, int W,
                                                            const int32_t* __restrict__ lab, const int32_t* __restrict__ head,
                                                            const int4* __restrict__ rec, int P, int32_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned segs = (unsigned)(W + 63) >> 6;
-    const long long items = (long long)N * H * segs;
     const long long total = (long long)N * H * W;
-    for (long long it = (long long)blockIdx.x * 4 + wave; it < items; it += (long long)gridDim.x * 4) {
-        const unsigned row = (unsigned)it / segs;                      // n H + r
-        const int c = (int)((unsigned)it - row * segs) * 64 + lane;
-        const int r = (int)(row % (unsigned)H);
-        const long long p = (long long)row * W + c;
+    walk_row_segments(N, H, W, [&](int, int r, int c, long long p) {
         const bool fg = c < W && m[p] != 0;
         const unsigned long long bal = __ballot(fg);
         int label = 0;
-        if (bal != 0) {                                                // the whole wave: `it` is uniform
+        if (bal != 0) {
             int root = fg ? lab[p] : -1;
             if ((unsigned)root >= (unsigned)total) root = -1;          // never with a workspace that label_into filled
             const int x = root >= 0 ? head[root] : 0;
@@ -726,7 +703,7 @@ __global__ __launch_bounds__(256) void split_assign_kernel(const uint8_t* __rest
             }
         }
         if (c < W) out[p] = label;
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ p, long long n, float thr, uint8_t* __restrict__ out) {
@@ -747,14 +724,42 @@ inline unsigned grid_for(long long n) {
     if (b < 1) b = 1;
     return (unsigned)(b > 16384 ? 16384 : b);
 }
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+// the grid of a kernel that calls walk_row_segments(N, H, W, .)
+inline dim3 walk_grid(int N, int H, int W) { return dim3(grid_for((long long)N * H * cs_ceil_div(W, 64) * 64)); }
 inline long long blocks_per_image(int H, int W) { return ((long long)H * W + kNB - 1) / kNB; }
 
-struct Ws {
-    int32_t *lab, *cnt, *blk;
+bool sizes_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31); }
+
+int fail(const char* what, const char* why) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", what, why);
+    cs_set_error_(msg);
+    return CS_ERR_INVALID_ARG;
+}
+
+// A workspace is a row of arrays that each start on a 16-byte boundary.  A *_layout function takes the arrays of one workspace in
+// order, writes their addresses where the kernels want them and returns the bytes in all: the one description of that workspace.
+// The cs_regions_*_workspace entry calls it on a NULL base for the size, the entry point that runs on it on the caller's pointer.
+struct Carve {
+    uintptr_t base;
+    size_t end = 0;
+    template <typename T>
+    T* take(size_t count) {
+        T* at = reinterpret_cast<T*>(base + end);
+        end += (count * sizeof(T) + 15) & ~(size_t)15;
+        return at;
+    }
 };
 
-bool sizes_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31); }
+struct Ws { int32_t *lab, *cnt, *blk; };
+// lab, cnt (int32 N H W each), blk (int32 N ceil(H W / 1024)); with rec, for a split: then rec (int4 P)
+size_t regions_layout(void* w, int N, int H, int W, Ws* ws, int P = 0, int4** rec = nullptr) {
+    const size_t t = (size_t)N * H * W;
+    Carve c{reinterpret_cast<uintptr_t>(w)};
+    *ws = Ws{c.take<int32_t>(t), c.take<int32_t>(t), c.take<int32_t>((size_t)N * blocks_per_image(H, W))};
+    if (rec) *rec = c.take<int4>(P);
+    return c.end;
+}
 
 // the vote counters per pred label: one per bit of the largest truth label
 inline int vote_bits(int cap_truth) {
@@ -765,6 +770,16 @@ inline int vote_bits(int cap_truth) {
 bool match_sizes_ok(int N, int cap_pred, int cap_truth) {
     return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && (long long)N * cap_pred * vote_bits(cap_truth) < (1LL << 31) &&
            (long long)N * cap_truth < (1LL << 31);
+}
+// vote (int32 N cap_pred B), cand (int32 N cap_pred), for the capacities of t, whose B it sets; 0 for capacities no call takes
+size_t match_layout(void* w, int N, Match* t) {
+    if (!match_sizes_ok(N, t->s.cap_pred, t->s.cap_truth)) return 0;
+    t->B = vote_bits(t->s.cap_truth);
+    const size_t rows = (size_t)N * t->s.cap_pred;
+    Carve c{reinterpret_cast<uintptr_t>(w)};
+    t->vote = c.take<int32_t>(rows * t->B);
+    t->cand = c.take<int32_t>(rows);
+    return c.end;
 }
 
 // the slots of one image's pair table: the smallest power of two >= 2 max_pairs; 0 for a max_pairs no call takes
@@ -778,6 +793,22 @@ bool overlap_sizes_ok(int N, int cap_pred, int cap_truth, int max_pairs) {
     const long long slots = overlap_slots(max_pairs);
     return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && slots > 0 && (long long)N * cap_pred < (1LL << 31) &&
            (long long)N * cap_truth < (1LL << 31) && N * slots < (1LL << 31);
+}
+// keys (uint64 N slots), cnt (int32 N slots), then best_iou, best_it (uint64 N cap_truth each), best_ip (uint64 N cap_pred), for
+// the capacities of t, whose slots it sets; 0 for sizes no call takes.  The pair table leads and N slots is even, so keys and cnt
+// are the first 8 N slots and the next 4 N slots bytes with no padding between them: kernels.regions_overlap_labels (Python) views
+// these 12 N slots bytes as the result's slot_keys / slot_counts.
+size_t overlap_layout(void* w, int N, int max_pairs, Overlap* t) {
+    if (!overlap_sizes_ok(N, t->s.cap_pred, t->s.cap_truth, max_pairs)) return 0;
+    t->slots = (int)overlap_slots(max_pairs);
+    const size_t ns = (size_t)N * t->slots, nt = (size_t)N * t->s.cap_truth;
+    Carve c{reinterpret_cast<uintptr_t>(w)};
+    t->keys = c.take<unsigned long long>(ns);
+    t->cnt = c.take<int32_t>(ns);
+    t->best_iou = c.take<unsigned long long>(nt);
+    t->best_it = c.take<unsigned long long>(nt);
+    t->best_ip = c.take<unsigned long long>((size_t)N * t->s.cap_pred);
+    return c.end;
 }
 
 // labels and areas of `m` into ws.lab / ws.cnt (cnt holds the area at every root's slot)
@@ -803,8 +834,8 @@ int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws
 // scipy's number of every foreground root of ws.lab into its slot of ws.cnt (the areas there are spent); counts (or NULL): the
 // number of foreground components of every image.  SEEDLESS (split, after the seed pass): only the roots without a seed, numbered
 // from S'_n + 1, and counts = S'_n + their number.
-template <bool SEEDLESS>
-int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, const Seeds& seeds, hipStream_t st) {
+template <bool SEEDLESS = false>
+int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st, const Seeds& seeds = Seeds{}) {
     const long long HW = (long long)H * W;
     const int B = (int)blocks_per_image(H, W);
     hipLaunchKernelGGL(number_count_kernel<SEEDLESS>, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, ws.cnt, HW, ws.blk);
@@ -815,37 +846,42 @@ int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* co
     CS_LAUNCH_CHECK();
     return CS_OK;
 }
-int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st) {
-    return number_into<false>(m, N, H, W, ws, counts, Seeds{nullptr, nullptr, nullptr, 0}, st);
-}
 
 int carve(const char* what, int N, int H, int W, int connectivity, const void* in, const void* out, void* workspace, size_t bytes, Ws* ws) {
-    static thread_local char msg[160];
-    auto fail = [&](const char* why) {
-        snprintf(msg, sizeof(msg), "%s: %s", what, why);
-        cs_set_error_(msg);
-        return CS_ERR_INVALID_ARG;
-    };
-    if (!in || !out || !workspace) return fail("NULL argument");
-    if (!sizes_ok(N, H, W)) return fail("need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
-    if (connectivity != 1 && connectivity != 2) return fail("connectivity must be 1 or 2");
-    if (bytes < cs_regions_workspace(N, H, W)) return fail("workspace too small");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("misaligned workspace");
-    const size_t t = (size_t)N * H * W;
-    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-    ws->lab = reinterpret_cast<int32_t*>(w);  w += align16(t * 4);
-    ws->cnt = reinterpret_cast<int32_t*>(w);  w += align16(t * 4);
-    ws->blk = reinterpret_cast<int32_t*>(w);
+    if (!in || !out || !workspace) return fail(what, "NULL argument");
+    if (!sizes_ok(N, H, W)) return fail(what, "need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    if (connectivity != 1 && connectivity != 2) return fail(what, "connectivity must be 1 or 2");
+    if (bytes < regions_layout(workspace, N, H, W, ws)) return fail(what, "workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(what, "misaligned workspace");
+    return CS_OK;
+}
+
+// What the two measure entry points check alike, after their own checks, and the tables as the kernels take them.
+int tables_of(const char* what, const uint8_t* intensity, int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax,
+              Tables* t) {
+    if (intensity && !(isum && imax)) return fail(what, "an intensity image needs both intensity tables");
+    if ((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(isum)) & 7) return fail(what, "misaligned int64 table");
+    *t = Tables{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
+    return CS_OK;
+}
+
+// What the two label-pair entry points check alike.  given: every pointer of the entry is there; need: what its workspace layout
+// returned, 0 for capacities it does not take, which is then the error caps_why.
+int check_label_pair(const char* what, bool given, int N, int H, int W, size_t need, const char* caps_why, const void* workspace,
+                     size_t bytes) {
+    if (!given) return fail(what, "NULL argument");
+    if (!sizes_ok(N, H, W)) return fail(what, "need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    if (need == 0) return fail(what, caps_why);
+    if (bytes < need) return fail(what, "workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(what, "misaligned workspace");
     return CS_OK;
 }
 
 }  // namespace
 
-// workspace: lab, cnt (int32 N H W each), blk (int32 N ceil(H W / 1024))
 extern "C" size_t cs_regions_workspace(int N, int H, int W) {
-    if (!sizes_ok(N, H, W)) return 0;
-    const size_t t = (size_t)N * H * W;
-    return 2 * align16(t * 4) + align16((size_t)N * blocks_per_image(H, W) * 4);
+    Ws ws;
+    return sizes_ok(N, H, W) ? regions_layout(nullptr, N, H, W, &ws) : 0;
 }
 
 extern "C" int cs_regions_label(const uint8_t* mask, int N, int H, int W, int connectivity, int32_t* labels, void* workspace,
@@ -881,29 +917,17 @@ extern "C" int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity,
     CS_CHECK_ARG(area && bbox && sums, "regions_measure: NULL table");
     CS_CHECK_ARG(capacity >= 1 && capacity <= (long long)H * W, "regions_measure: need 1 <= capacity <= H W");
     CS_CHECK_ARG(numbered == 0 || numbered == 1, "regions_measure: numbered must be 0 or 1");
-    CS_CHECK_ARG(!intensity || (isum && imax), "regions_measure: an intensity image needs both intensity tables");
-    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(isum)) & 7), "regions_measure: misaligned int64 table");
+    Tables t;
+    if ((rc = tables_of("regions_measure", intensity, area, bbox, sums, isum, imax, &t)) != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (!numbered) {
         if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
         if ((rc = number_into(mask, N, H, W, ws, counts, st)) != CS_OK) return rc;
     }
-    const Tables t{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
     hipLaunchKernelGGL(measure_init_kernel, dim3(grid_for((long long)N * capacity)), dim3(256), 0, st, counts, N, capacity, t,
                        intensity ? 1 : 0, (int32_t*)nullptr);
     CS_LAUNCH_CHECK();
-    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
-    const dim3 grid(grid_for(waves * 64));
-#ifdef CS_AB_SWITCHES
-    static const int per_pixel = cs_env_int_("CELLSEG_MEASURE_PER_PIXEL", 0);     // A/B flavour: what the in-wave run reduction buys
-    if (per_pixel) {
-        hipLaunchKernelGGL((measure_kernel<false, false>), grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t,
-                           (int32_t*)nullptr);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-#endif
-    hipLaunchKernelGGL((measure_kernel<true, false>), grid, dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t,
+    hipLaunchKernelGGL(measure_kernel<false>, walk_grid(N, H, W), dim3(256), 0, st, mask, intensity, N, H, W, ws.lab, ws.cnt, capacity, t,
                        (int32_t*)nullptr);
     CS_LAUNCH_CHECK();
     return CS_OK;
@@ -916,69 +940,57 @@ extern "C" int cs_regions_measure_labels(const int32_t* labels, const uint8_t* i
     CS_CHECK_ARG(sizes_ok(N, H, W), "regions_measure_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
     CS_CHECK_ARG(capacity >= 1, "regions_measure_labels: need capacity >= 1");
     CS_CHECK_ARG((long long)N * capacity < (1LL << 31), "regions_measure_labels: need N capacity < 2^31");
-    CS_CHECK_ARG(!intensity || (isum && imax), "regions_measure_labels: an intensity image needs both intensity tables");
-    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(isum)) & 7),
-                 "regions_measure_labels: misaligned int64 table");
+    Tables t;
+    const int rc = tables_of("regions_measure_labels", intensity, area, bbox, sums, isum, imax, &t);
+    if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const Tables t{area, bbox, reinterpret_cast<long long*>(sums), reinterpret_cast<long long*>(isum), imax};
     const long long rows = (long long)N * capacity;
     hipLaunchKernelGGL(measure_init_kernel, dim3(grid_for(rows)), dim3(256), 0, st, (const int32_t*)nullptr, N, capacity, t,
                        intensity ? 1 : 0, counts);
     CS_LAUNCH_CHECK();
-    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
-    hipLaunchKernelGGL((measure_kernel<true, true>), dim3(grid_for(waves * 64)), dim3(256), 0, st, (const uint8_t*)nullptr, intensity, N,
-                       H, W, labels, (const int32_t*)nullptr, capacity, t, counts);
+    hipLaunchKernelGGL(measure_kernel<true>, walk_grid(N, H, W), dim3(256), 0, st, (const uint8_t*)nullptr, intensity, N, H, W, labels,
+                       (const int32_t*)nullptr, capacity, t, counts);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(measure_empty_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }
 
-// workspace: vote (int32 N cap_pred B, B = max(1, bit_length(cap_truth))), cand (int32 N cap_pred)
 extern "C" size_t cs_regions_match_workspace(int N, int cap_pred, int cap_truth) {
-    if (!match_sizes_ok(N, cap_pred, cap_truth)) return 0;
-    const size_t rows = (size_t)N * cap_pred;
-    return align16(rows * vote_bits(cap_truth) * 4) + align16(rows * 4);
+    Match t{{nullptr, nullptr, nullptr, nullptr, cap_pred, cap_truth}};
+    return match_layout(nullptr, N, &t);
 }
 
 extern "C" int cs_regions_match_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
                                        int32_t* counts_pred, int32_t* counts_truth, int32_t* area_pred, int32_t* area_truth,
                                        int32_t* match, int32_t* inter, int32_t* match_truth, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    CS_CHECK_ARG(pred && truth && area_pred && area_truth && match && inter && match_truth && workspace,
-                 "regions_match_labels: NULL argument");
-    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_match_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
-    CS_CHECK_ARG(match_sizes_ok(N, cap_pred, cap_truth),
-                 "regions_match_labels: need capacities >= 1, N cap_pred bit_length(cap_truth) < 2^31 and N cap_truth < 2^31");
-    CS_CHECK_ARG(workspace_bytes >= cs_regions_match_workspace(N, cap_pred, cap_truth), "regions_match_labels: workspace too small");
-    CS_CHECK_ARG(!(reinterpret_cast<uintptr_t>(workspace) & 15), "regions_match_labels: misaligned workspace");
+    Match t{{area_pred, area_truth, counts_pred, counts_truth, cap_pred, cap_truth}, match, inter, match_truth};
+    const int rc = check_label_pair("regions_match_labels",
+                                    pred && truth && area_pred && area_truth && match && inter && match_truth && workspace, N, H, W,
+                                    match_layout(workspace, N, &t),
+                                    "need capacities >= 1, N cap_pred bit_length(cap_truth) < 2^31 and N cap_truth < 2^31", workspace,
+                                    workspace_bytes);
+    if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int B = vote_bits(cap_truth);
     const long long rows = (long long)N * cap_pred;
-    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-    const Match t{area_pred, area_truth, match, inter, match_truth, reinterpret_cast<int32_t*>(w),
-                  reinterpret_cast<int32_t*>(w + align16((size_t)rows * B * 4)), counts_pred, counts_truth, cap_pred, cap_truth, B};
-    const long long cells = rows * B > (long long)N * cap_truth ? rows * B : (long long)N * cap_truth;
+    const long long cells = rows * t.B > (long long)N * cap_truth ? rows * t.B : (long long)N * cap_truth;
     hipLaunchKernelGGL(match_init_kernel, dim3(grid_for(cells)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
-    const dim3 walk(grid_for((long long)N * H * cs_ceil_div(W, 64) * 64));
-    hipLaunchKernelGGL(match_walk_kernel<true>, walk, dim3(256), 0, st, pred, truth, N, H, W, t);
+    hipLaunchKernelGGL(match_walk_kernel<true>, walk_grid(N, H, W), dim3(256), 0, st, pred, truth, N, H, W, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(match_candidate_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(match_walk_kernel<false>, walk, dim3(256), 0, st, pred, truth, N, H, W, t);
+    hipLaunchKernelGGL(match_walk_kernel<false>, walk_grid(N, H, W), dim3(256), 0, st, pred, truth, N, H, W, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(match_decide_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }
 
-// workspace: keys (uint64 N slots), cnt (int32 N slots) -- the pair table, which the caller may read afterwards -- then best_iou,
-// best_it (uint64 N cap_truth each), best_ip (uint64 N cap_pred); slots = overlap_slots(max_pairs)
 extern "C" size_t cs_regions_overlap_workspace(int N, int cap_pred, int cap_truth, int max_pairs) {
-    if (!overlap_sizes_ok(N, cap_pred, cap_truth, max_pairs)) return 0;
-    const size_t ns = (size_t)N * overlap_slots(max_pairs);
-    return align16(ns * 8) + align16(ns * 4) + 2 * align16((size_t)N * cap_truth * 8) + align16((size_t)N * cap_pred * 8);
+    Overlap t{{nullptr, nullptr, nullptr, nullptr, cap_pred, cap_truth}};
+    return overlap_layout(nullptr, N, max_pairs, &t);
 }
 
 extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
@@ -986,32 +998,21 @@ extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* tru
                                          int32_t* area_truth, int32_t* n_pairs, int32_t* dropped, int32_t* iou_partner, int32_t* iou_inter,
                                          int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred,
                                          int32_t* inter_pred, void* workspace, size_t workspace_bytes, void* stream) {
-    CS_CHECK_ARG(pred && truth && area_pred && area_truth && n_pairs && dropped && iou_partner && iou_inter && inter_partner_truth &&
-                     inter_truth && inter_partner_pred && inter_pred && workspace,
-                 "regions_overlap_labels: NULL argument");
-    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_overlap_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
-    CS_CHECK_ARG(overlap_sizes_ok(N, cap_pred, cap_truth, max_pairs),
-                 "regions_overlap_labels: need capacities >= 1, 1 <= max_pairs <= 2^29, N cap_pred < 2^31, N cap_truth < 2^31 and "
-                 "N slots < 2^31");
-    CS_CHECK_ARG(workspace_bytes >= cs_regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs),
-                 "regions_overlap_labels: workspace too small");
-    CS_CHECK_ARG(!(reinterpret_cast<uintptr_t>(workspace) & 15), "regions_overlap_labels: misaligned workspace");
+    Overlap t{{area_pred, area_truth, counts_pred, counts_truth, cap_pred, cap_truth}, n_pairs, dropped, iou_partner, iou_inter,
+              inter_partner_truth, inter_truth, inter_partner_pred, inter_pred};
+    const int rc = check_label_pair("regions_overlap_labels",
+                                    pred && truth && area_pred && area_truth && n_pairs && dropped && iou_partner && iou_inter &&
+                                        inter_partner_truth && inter_truth && inter_partner_pred && inter_pred && workspace,
+                                    N, H, W, overlap_layout(workspace, N, max_pairs, &t),
+                                    "need capacities >= 1, 1 <= max_pairs <= 2^29, N cap_pred < 2^31, N cap_truth < 2^31 and N slots < 2^31",
+                                    workspace, workspace_bytes);
+    if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int slots = (int)overlap_slots(max_pairs);
-    const long long ns = (long long)N * slots, np = (long long)N * cap_pred, nt = (long long)N * cap_truth;
-    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-    Overlap t{area_pred, area_truth, n_pairs, dropped, iou_partner, iou_inter, inter_partner_truth, inter_truth, inter_partner_pred,
-              inter_pred, nullptr, nullptr, nullptr, nullptr, nullptr, counts_pred, counts_truth, cap_pred, cap_truth, slots};
-    t.keys = reinterpret_cast<unsigned long long*>(w);      w += align16((size_t)ns * 8);
-    t.cnt = reinterpret_cast<int32_t*>(w);                  w += align16((size_t)ns * 4);
-    t.best_iou = reinterpret_cast<unsigned long long*>(w);  w += align16((size_t)nt * 8);
-    t.best_it = reinterpret_cast<unsigned long long*>(w);   w += align16((size_t)nt * 8);
-    t.best_ip = reinterpret_cast<unsigned long long*>(w);
+    const long long ns = (long long)N * t.slots, np = (long long)N * cap_pred, nt = (long long)N * cap_truth;
     const long long labels = np > nt ? np : nt;
     hipLaunchKernelGGL(overlap_init_kernel, dim3(grid_for(ns > labels ? ns : labels)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(overlap_walk_kernel, dim3(grid_for((long long)N * H * cs_ceil_div(W, 64) * 64)), dim3(256), 0, st, pred, truth, N,
-                       H, W, t);
+    hipLaunchKernelGGL(overlap_walk_kernel, walk_grid(N, H, W), dim3(256), 0, st, pred, truth, N, H, W, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(overlap_reduce_kernel, dim3(grid_for(ns)), dim3(256), 0, st, ns, t);
     CS_LAUNCH_CHECK();
@@ -1020,11 +1021,10 @@ extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* tru
     return CS_OK;
 }
 
-// workspace: that of cs_regions_workspace, then rec (int4 P)
 extern "C" size_t cs_regions_split_workspace(int N, int H, int W, int P) {
-    const size_t base = cs_regions_workspace(N, H, W);
-    if (base == 0 || P < 0) return 0;
-    return base + align16((size_t)P * sizeof(int4));
+    Ws ws;
+    int4* rec;
+    return sizes_ok(N, H, W) && P >= 0 ? regions_layout(nullptr, N, H, W, &ws, P, &rec) : 0;
 }
 
 extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity, const int64_t* points, const int64_t* offsets,
@@ -1037,9 +1037,9 @@ extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int co
     CS_CHECK_ARG(P >= 0 && (P == 0 || (points && offsets && live)), "regions_split: P points need points, offsets and live");
     CS_CHECK_ARG((long long)H * H + (long long)W * W < (1LL << 31), "regions_split: need H^2 + W^2 < 2^31");
     CS_CHECK_ARG((long long)P + (long long)H * W < (1LL << 31), "regions_split: need P + H W < 2^31");
-    CS_CHECK_ARG(workspace_bytes >= cs_regions_split_workspace(N, H, W, P), "regions_split: workspace too small");
+    int4* rec;
+    CS_CHECK_ARG(workspace_bytes >= regions_layout(workspace, N, H, W, &ws, P, &rec), "regions_split: workspace too small");
     CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7), "regions_split: misaligned int64 array");
-    int4* rec = reinterpret_cast<int4*>(reinterpret_cast<unsigned char*>(workspace) + cs_regions_workspace(N, H, W));
     const Seeds seeds{reinterpret_cast<const long long*>(points), P > 0 ? reinterpret_cast<const long long*>(offsets) : nullptr, limits, P};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
@@ -1047,9 +1047,8 @@ extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int co
         hipLaunchKernelGGL(seed_kernel, dim3(grid_for(P)), dim3(256), 0, st, mask, N, H, W, seeds, ws.lab, ws.cnt, rec, live);
         CS_LAUNCH_CHECK();
     }
-    if ((rc = number_into<true>(mask, N, H, W, ws, counts, seeds, st)) != CS_OK) return rc;
-    const long long waves = (long long)N * H * cs_ceil_div(W, 64);
-    hipLaunchKernelGGL(split_assign_kernel, dim3(grid_for(waves * 64)), dim3(256), 0, st, mask, N, H, W, ws.lab, ws.cnt, rec, P, labels);
+    if ((rc = number_into<true>(mask, N, H, W, ws, counts, st, seeds)) != CS_OK) return rc;
+    hipLaunchKernelGGL(split_assign_kernel, walk_grid(N, H, W), dim3(256), 0, st, mask, N, H, W, ws.lab, ws.cnt, rec, P, labels);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

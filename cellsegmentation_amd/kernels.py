@@ -1305,6 +1305,14 @@ def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=N
     return t.get("counts"), t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
 
 
+def _label_pair_args(what, pred, truth, want_counts):
+    """two int32 [N,H,W] label images of one shape -> (N, H, W, the ``_regions_outputs`` entries of the counts asked for)"""
+    if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):
+        raise TypeError(f"{what} reads two int32 [N,H,W] label images of one shape")
+    N, H, W = pred.shape
+    return N, H, W, {k: ((N,), torch.int32) for k, wanted in zip(("counts_pred", "counts_truth"), want_counts) if wanted}
+
+
 def regions_match_workspace(N, cap_pred, cap_truth, device):
     """the caller-owned scratch of one cs_regions_match_labels call on N images with these capacities"""
     ws_bytes = _lib.load().cs_regions_match_workspace(int(N), int(cap_pred), int(cap_truth))
@@ -1320,16 +1328,10 @@ def regions_match_labels(pred, truth, cap_pred, cap_truth, counts_pred=None, cou
     [N,cap_pred], area_truth int32 [N,cap_truth], match int32 [N,cap_pred], inter int32 [N,cap_pred], match_truth int32
     [N,cap_truth]): the partner of every label at IoU > 1/2 (cs_regions_match_labels in include/cellseg_hip.h).  The counts of a
     side are written with the largest label of every image, or left out (``want_counts`` False for that side -> None)."""
-    if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):
-        raise TypeError("regions_match_labels reads two int32 [N,H,W] label images of one shape")
-    N, H, W = pred.shape
+    N, H, W, counts = _label_pair_args("regions_match_labels", pred, truth, want_counts)
     cp, ct = int(cap_pred), int(cap_truth)
     want = {"area_pred": ((N, cp), torch.int32), "area_truth": ((N, ct), torch.int32), "match": ((N, cp), torch.int32),
-            "inter": ((N, cp), torch.int32), "match_truth": ((N, ct), torch.int32)}
-    if want_counts[0]:
-        want["counts_pred"] = ((N,), torch.int32)
-    if want_counts[1]:
-        want["counts_truth"] = ((N,), torch.int32)
+            "inter": ((N, cp), torch.int32), "match_truth": ((N, ct), torch.int32), **counts}
     if ws is None:
         ws = regions_match_workspace(N, cp, ct, pred.device)
     t = _regions_outputs("regions_match_labels", want,
@@ -1369,17 +1371,11 @@ def regions_overlap_labels(pred, truth, cap_pred, cap_truth, max_pairs, counts_p
     inter_partner_truth, inter_truth [N,cap_truth], inter_partner_pred, inter_pred [N,cap_pred], and the pair table itself as views
     of ``ws``: slot_keys int64 [N,slots] ((pred << 32) | truth, 0 = empty) and slot_counts int32 [N,slots]
     (cs_regions_overlap_labels in include/cellseg_hip.h)."""
-    if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):
-        raise TypeError("regions_overlap_labels reads two int32 [N,H,W] label images of one shape")
-    N, H, W = pred.shape
+    N, H, W, counts = _label_pair_args("regions_overlap_labels", pred, truth, want_counts)
     cp, ct, mp = int(cap_pred), int(cap_truth), int(max_pairs)
     caps = (cp, ct)
     want = {name: ((N, caps[side]), torch.int32) for name, side in _OVERLAP_TABLES}
-    want.update(n_pairs=((N,), torch.int32), dropped=((N,), torch.int32))
-    if want_counts[0]:
-        want["counts_pred"] = ((N,), torch.int32)
-    if want_counts[1]:
-        want["counts_truth"] = ((N,), torch.int32)
+    want.update(n_pairs=((N,), torch.int32), dropped=((N,), torch.int32), **counts)
     if ws is None:
         ws = regions_overlap_workspace(N, cp, ct, mp, pred.device)
     given = {"counts_pred": counts_pred, "counts_truth": counts_truth, "area_pred": area_pred, "area_truth": area_truth, "n_pairs": n_pairs,

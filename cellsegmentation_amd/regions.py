@@ -221,6 +221,17 @@ def _as_intensity(v, shape):
     return t
 
 
+def _tables(N, cap, with_intensity, dev):
+    """the five tensors of a ``RegionTable`` with ``cap`` rows per image: area, bbox, sums, isum, imax (the last two None without an
+    intensity image)"""
+    area = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    bbox = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
+    sums = torch.empty((N, cap, 2), dtype=torch.int64, device=dev)
+    isum = torch.empty((N, cap), dtype=torch.int64, device=dev) if with_intensity else None
+    imax = torch.empty((N, cap), dtype=torch.int32, device=dev) if with_intensity else None
+    return area, bbox, sums, isum, imax
+
+
 def measure(m, intensity=None, connectivity=1, max_regions=None):
     """One row per connected foreground component of every image -> ``RegionTable``.  ``intensity``: uint8 of the mask's shape, or
     None.  ``max_regions=int`` fixes the rows per image (capped at H W; components numbered above it are counted, not measured):
@@ -250,12 +261,7 @@ def measure(m, intensity=None, connectivity=1, max_regions=None):
         numbered = len(chunks) == 1                                      # one call: its workspace still holds the numbering
     else:
         cap = min(int(max_regions), H * W)
-    dev = t.device
-    area = torch.empty((N, cap), dtype=torch.int32, device=dev)
-    bbox = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
-    sums = torch.empty((N, cap, 2), dtype=torch.int64, device=dev)
-    isum = None if v is None else torch.empty((N, cap), dtype=torch.int64, device=dev)
-    imax = None if v is None else torch.empty((N, cap), dtype=torch.int32, device=dev)
+    area, bbox, sums, isum, imax = _tables(N, cap, v is not None, t.device)
     for a, b in chunks:
         K.regions_measure(t[a:b], cap, None if v is None else v[a:b], conn, numbered, counts[a:b], area[a:b], bbox[a:b], sums[a:b],
                           None if v is None else isum[a:b], None if v is None else imax[a:b], ws=workspace(b - a))
@@ -359,6 +365,23 @@ def _check_max_regions(max_regions):
         raise ValueError(f"max_regions must be a positive integer or None, got {max_regions!r}")
 
 
+def _as_labels(x, what, masks_go_to="label first"):
+    """int32 numpy / torch [H, W] or [N, H, W] -> the tensor (not yet on the device); argument errors only.  ``masks_go_to``: where
+    the message sends a caller who passed a boolean mask."""
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{what}: expected an int32 label image, got {t.dtype} (boolean masks go to {masks_go_to})")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: empty label image of shape {tuple(t.shape)}")
+    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
+        raise ValueError(f"{what}: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
+    return t
+
+
 def measure_labels(labels, intensity=None, max_regions=None, counts=None):
     """``measure`` for a label image: int32 [H, W] or [N, H, W] (numpy or torch; 0 and below = background) -> ``RegionTable`` whose
     row k belongs to label k + 1.  A label that owns no pixel (an empty cell of ``split``) leaves an all-zero row, its bounding box
@@ -368,17 +391,7 @@ def measure_labels(labels, intensity=None, max_regions=None, counts=None):
     ``max_regions=None`` reads the largest count back (the one synchronisation; without ``counts`` after a pass that finds them)
     and measures with exactly that capacity (1 when there is no label).  Only int32 is taken; boolean masks go to ``measure``."""
     _check_max_regions(max_regions)
-    t = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
-    if not torch.is_tensor(t):
-        raise TypeError("measure_labels: expected a numpy array or a torch tensor")
-    if t.dtype != torch.int32:
-        raise TypeError(f"measure_labels: expected an int32 label image, got {t.dtype} (boolean masks go to measure)")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"measure_labels: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
-    if t.numel() == 0:
-        raise ValueError(f"measure_labels: empty label image of shape {tuple(t.shape)}")
-    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
-        raise ValueError(f"measure_labels: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
+    t = _as_labels(labels, "measure_labels", masks_go_to="measure")
     v = None if intensity is None else _as_intensity(intensity, t.shape)
     n_images = 1 if t.dim() == 2 else t.shape[0]
     if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (n_images,)):
@@ -400,11 +413,7 @@ def measure_labels(labels, intensity=None, max_regions=None, counts=None):
         counts = counts.to(dev).contiguous()
 
     def run(cap, want_counts):
-        area = torch.empty((N, cap), dtype=torch.int32, device=dev)
-        bbox = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
-        sums = torch.empty((N, cap, 2), dtype=torch.int64, device=dev)
-        isum = None if v is None else torch.empty((N, cap), dtype=torch.int64, device=dev)
-        imax = None if v is None else torch.empty((N, cap), dtype=torch.int32, device=dev)
+        area, bbox, sums, isum, imax = _tables(N, cap, v is not None, dev)
         for a, b in chunks:
             K.regions_measure_labels(t[a:b], cap, None if v is None else v[a:b], counts[a:b] if want_counts else None, area[a:b], bbox[a:b],
                                      sums[a:b], None if v is None else isum[a:b], None if v is None else imax[a:b], want_counts=want_counts)
@@ -462,22 +471,6 @@ class MatchTable:
         return S.label_score(*self._host, iou_threshold=iou_threshold)
 
 
-def _as_labels(x, what):
-    """int32 numpy / torch [H, W] or [N, H, W] -> the tensor (not yet on the device); argument errors only"""
-    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
-    if t.dtype != torch.int32:
-        raise TypeError(f"{what}: expected an int32 label image, got {t.dtype} (boolean masks go to label first)")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
-    if t.numel() == 0:
-        raise ValueError(f"{what}: empty label image of shape {tuple(t.shape)}")
-    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
-        raise ValueError(f"{what}: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
-    return t
-
-
 def _match_capacities(max_regions):
     """None, one capacity or a (pred, truth) pair -> None or the pair"""
     if max_regions is None:
@@ -490,6 +483,40 @@ def _match_capacities(max_regions):
         if c is None:
             raise ValueError(f"max_regions must be a positive integer, a (pred, truth) pair of them or None, got {max_regions!r}")
     return int(pair[0]), int(pair[1])
+
+
+class _LabelPair:
+    """The front end that ``match_labels`` and ``overlap_labels`` share: argument errors first, then ``pred`` / ``truth`` as int32
+    [N, H, W] on one device, the ``chunks`` of whole images per kernel call, ``own`` = which side's counts the device has to find,
+    and ``counts`` = the two int32 [N] tensors (the caller's where given)."""
+
+    def __init__(self, what, pred, truth, pred_counts, truth_counts):
+        p, t = _as_labels(pred, what), _as_labels(truth, what)
+        if tuple(p.shape) != tuple(t.shape):
+            raise ValueError(f"{what}: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
+        N = 1 if p.dim() == 2 else p.shape[0]
+        for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
+            if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (N,)):
+                raise TypeError(f"{what}: {name} must be an int32 tensor of shape ({N},)")
+        dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
+        self.pred, self.truth = (x.reshape((N,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
+        self.N, self.dev, self.chunks = N, dev, _chunks(self.pred)
+        self.own = (pred_counts is None, truth_counts is None)
+        self.counts = tuple(torch.empty((N,), dtype=torch.int32, device=dev) if c is None else c.to(dev).contiguous()
+                            for c in (pred_counts, truth_counts))
+
+    def calls(self, want):
+        """per chunk: (slice of the images, pred, truth, counts_pred | None, counts_truth | None) as a kernel call takes them"""
+        for a, b in self.chunks:
+            yield slice(a, b), self.pred[a:b], self.truth[a:b], *(c[a:b] if w else None for c, w in zip(self.counts, want))
+
+    def largest_labels(self, probe):
+        """The capacities that hold every label of the batch (1 where a side has none).  ``probe``: the caller's run at capacity
+        1, which leaves the largest labels in ``counts``; made only if a side's counts were not given.  One synchronisation."""
+        if self.own[0] or self.own[1]:
+            probe()
+        top = torch.stack([c.max() for c in self.counts]).cpu()
+        return max(1, int(top[0])), max(1, int(top[1]))
 
 
 def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=None):
@@ -514,37 +541,20 @@ def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=N
     integer and independent of launch order.  Memory: 4 N cap_pred (bit_length(cap_truth) + 1) bytes of workspace besides the
     tables -- never a cap_pred x cap_truth table."""
     caps = _match_capacities(max_regions)
-    p, t = _as_labels(pred, "match_labels"), _as_labels(truth, "match_labels")
-    if tuple(p.shape) != tuple(t.shape):
-        raise ValueError(f"match_labels: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
-    n_images = 1 if p.dim() == 2 else p.shape[0]
-    for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
-        if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (n_images,)):
-            raise TypeError(f"match_labels: {name} must be an int32 tensor of shape ({n_images},)")
-    dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
-    p, t = (x.reshape((n_images,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
-    N = n_images
-    chunks = _chunks(p)
-    own = (pred_counts is None, truth_counts is None)
-    cp = torch.empty((N,), dtype=torch.int32, device=dev) if own[0] else pred_counts.to(dev).contiguous()
-    ct = torch.empty((N,), dtype=torch.int32, device=dev) if own[1] else truth_counts.to(dev).contiguous()
+    pair = _LabelPair("match_labels", pred, truth, pred_counts, truth_counts)
 
     def run(cap_p, cap_t, want):
-        tabs = [torch.empty((N, c), dtype=torch.int32, device=dev) for c in (cap_p, cap_t, cap_p, cap_p, cap_t)]
+        tabs = [torch.empty((pair.N, c), dtype=torch.int32, device=pair.dev) for c in (cap_p, cap_t, cap_p, cap_p, cap_t)]
         ws, ws_n = None, 0
-        for a, b in chunks:
-            if ws_n != b - a:
-                ws, ws_n = K.regions_match_workspace(b - a, cap_p, cap_t, dev), b - a
-            K.regions_match_labels(p[a:b], t[a:b], cap_p, cap_t, cp[a:b] if want[0] else None, ct[a:b] if want[1] else None,
-                                   *(x[a:b] for x in tabs), want_counts=want, ws=ws)
-        return MatchTable(cp, ct, cap_p, cap_t, *tabs)
+        for at, p, t, cp, ct in pair.calls(want):
+            if ws_n != len(p):
+                ws, ws_n = K.regions_match_workspace(len(p), cap_p, cap_t, pair.dev), len(p)
+            K.regions_match_labels(p, t, cap_p, cap_t, cp, ct, *(x[at] for x in tabs), want_counts=want, ws=ws)
+        return MatchTable(*pair.counts, cap_p, cap_t, *tabs)
 
     if caps is not None:
-        return run(caps[0], caps[1], own)
-    if own[0] or own[1]:
-        run(1, 1, own)                                                   # the pass that finds the largest labels
-    top = torch.stack([cp.max(), ct.max()]).cpu()                        # the one synchronisation
-    return run(max(1, int(top[0])), max(1, int(top[1])), (False, False))
+        return run(*caps, pair.own)
+    return run(*pair.largest_labels(lambda: run(1, 1, pair.own)), (False, False))
 
 
 _OVERLAP_HOST = ("area_pred", "area_truth", "iou_partner", "iou_inter", "inter_partner_truth", "inter_truth", "inter_partner_pred",
@@ -630,44 +640,27 @@ def overlap_labels(pred, truth, max_regions=None, max_pairs=None, pred_counts=No
     cap_pred) bytes of workspace, whose first 12 N slots bytes the result keeps -- never a cap_pred x cap_truth table."""
     caps = _match_capacities(max_regions)
     _check_max_pairs(max_pairs)
-    p, t = _as_labels(pred, "overlap_labels"), _as_labels(truth, "overlap_labels")
-    if tuple(p.shape) != tuple(t.shape):
-        raise ValueError(f"overlap_labels: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
-    n_images = 1 if p.dim() == 2 else p.shape[0]
-    for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
-        if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (n_images,)):
-            raise TypeError(f"overlap_labels: {name} must be an int32 tensor of shape ({n_images},)")
-    dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
-    p, t = (x.reshape((n_images,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
-    N = n_images
-    chunks = _chunks(p)
-    own = (pred_counts is None, truth_counts is None)
-    cp = torch.empty((N,), dtype=torch.int32, device=dev) if own[0] else pred_counts.to(dev).contiguous()
-    ct = torch.empty((N,), dtype=torch.int32, device=dev) if own[1] else truth_counts.to(dev).contiguous()
+    pair = _LabelPair("overlap_labels", pred, truth, pred_counts, truth_counts)
+    N, dev = pair.N, pair.dev
 
     def run(cap_p, cap_t, pairs, want):
-        names = [k for k, _ in K._OVERLAP_TABLES] + ["n_pairs", "dropped"]
         tabs = {k: torch.empty((N, (cap_p, cap_t)[side]), dtype=torch.int32, device=dev) for k, side in K._OVERLAP_TABLES}
         tabs.update(n_pairs=torch.empty((N,), dtype=torch.int32, device=dev), dropped=torch.empty((N,), dtype=torch.int32, device=dev))
         slots = []
-        for a, b in chunks:                                              # a workspace per call: the result views its pair table
-            r = K.regions_overlap_labels(p[a:b], t[a:b], cap_p, cap_t, pairs, cp[a:b] if want[0] else None, ct[a:b] if want[1] else None,
-                                         **{k: tabs[k][a:b] for k in names}, want_counts=want)
+        for at, p, t, cp, ct in pair.calls(want):                        # a workspace per call: the result views its pair table
+            r = K.regions_overlap_labels(p, t, cap_p, cap_t, pairs, cp, ct, **{k: x[at] for k, x in tabs.items()}, want_counts=want)
             slots.append((r["slot_keys"], r["slot_counts"]))
         keys, counts = slots[0] if len(slots) == 1 else (torch.cat([s[i] for s in slots]) for i in (0, 1))
-        return OverlapTable(cp, ct, cap_p, cap_t, *(tabs[k] for k in ("area_pred", "area_truth", "n_pairs", "dropped", "iou_partner",
-                                                                      "iou_inter", "inter_partner_truth", "inter_truth",
-                                                                      "inter_partner_pred", "inter_pred")), keys, counts)
+        return OverlapTable(*pair.counts, cap_p, cap_t, *(tabs[k] for k in ("area_pred", "area_truth", "n_pairs", "dropped", "iou_partner",
+                                                                            "iou_inter", "inter_partner_truth", "inter_truth",
+                                                                            "inter_partner_pred", "inter_pred")), keys, counts)
 
-    want = own
+    want = pair.own
     if caps is None:
-        if own[0] or own[1]:
-            run(1, 1, 1, own)                                            # the pass that finds the largest labels
-        top = torch.stack([cp.max(), ct.max()]).cpu()                    # one synchronisation
-        caps, want = (max(1, int(top[0])), max(1, int(top[1]))), (False, False)
+        caps, want = pair.largest_labels(lambda: run(1, 1, 1, pair.own)), (False, False)
     if max_pairs is not None:
         return run(caps[0], caps[1], int(max_pairs), want)
-    most = p.shape[1] * p.shape[2]                                       # an image has no more pairs than pixels
+    most = pair.pred.shape[1] * pair.pred.shape[2]                       # an image has no more pairs than pixels
     pairs = min(4 * (caps[0] + caps[1]), most)
     while True:
         table = run(caps[0], caps[1], pairs, want)

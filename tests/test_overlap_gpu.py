@@ -123,6 +123,26 @@ def test_runs_across_segments_and_rows_meet_in_one_slot(dev, shape):
     assert [c.tolist() for c in got.pairs()] == [[0], [1], [2], [H * W]]
 
 
+@pytest.mark.parametrize("W", [1, 63, 64, 65, 129])
+@pytest.mark.parametrize("H", [1, 3])
+def test_both_sides_accounted_alike_by_match_overlap_and_measure(dev, H, W):
+    """The accounting that match_labels and overlap_labels share (label maxima, clamp to the capacities, areas), at the widths
+    either side of a wave's 64-column segment, with labels below 1 and labels above both capacities, against measure_labels of each
+    side and the dense statement."""
+    rng = np.random.RandomState(1000 * H + W)
+    pred, truth = (rng.randint(-1, 10, size=(2, H, W)).astype(np.int32) for _ in range(2))
+    ref = O.overlap(pred, truth, 6, 7)
+    m = G.match_labels(pred, truth, max_regions=(6, 7))
+    o = G.overlap_labels(pred, truth, max_regions=(6, 7), max_pairs=64)     # at most 6 x 7 pairs: nothing is dropped
+    assert not _np(o.dropped).any()
+    for key in ("counts_pred", "counts_truth", "area_pred", "area_truth"):
+        a, b = getattr(m, key), getattr(o, key)
+        assert a.dtype == torch.int32 and torch.equal(a, b), key
+        assert np.array_equal(_np(a), ref[key]), key
+    assert torch.equal(G.measure_labels(pred, max_regions=6).area, m.area_pred)
+    assert torch.equal(G.measure_labels(truth, max_regions=7).area, m.area_truth)
+
+
 def blocks_ref():
     if "blocks" not in _REFS:
         truth = M.blocks(64, 64)

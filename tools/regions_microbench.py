@@ -5,9 +5,7 @@ same work.  Checks that the GPU outputs equal the restatement.
     python tools/regions_microbench.py [--reps 5] [--host-maps 128] [--json PATH]
 
 --measure times ``regions.measure`` (uint8 intensity, a fixed ``max_regions``: no synchronisation) next to ``regions.label`` on the
-same two mask sets, checks the tables against tests/props_ref.py, and reports the masks' component statistics.  It then runs
-itself once more in a child process on the A/B flavour of the library (CELLSEG_LIB_FLAVOUR=ab) with CELLSEG_MEASURE_PER_PIXEL=1,
-where every foreground pixel issues its own atomics: what the in-wave run reduction buys.
+same two mask sets, checks the tables against tests/props_ref.py, and reports the masks' component statistics.
 
     python tools/regions_microbench.py --measure [--reps 5] [--host-maps 8] [--json PATH]
 
@@ -22,7 +20,6 @@ tests/split_ref.py (scipy).
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -80,7 +77,7 @@ def mask_sets():
 MAX_REGIONS = {"batch128_299": 256, "whole_4096": 16384}
 
 
-def measure_case(name, masks, reps, host_maps, dev, check):
+def measure_case(name, masks, reps, host_maps, dev):
     import props_ref as P
     d = torch.from_numpy(masks).to(dev)
     v = np.random.RandomState(3).randint(0, 256, size=masks.shape).astype(np.uint8)
@@ -89,43 +86,27 @@ def measure_case(name, masks, reps, host_maps, dev, check):
     label_ms, _ = time_dev(lambda: G.label(d), reps)
     measure_ms, ts = time_dev(lambda: G.measure(d, intensity=dv, max_regions=cap), reps)
     res = {"label_ms": label_ms, "measure_ms": measure_ms, "measure_ms_all": ts, "max_regions": cap}
-    if check:
-        t = G.measure(d, intensity=dv, max_regions=cap)
-        counts, area = t.counts.cpu().numpy(), t.area.cpu().numpy()
-        used = area[area > 0]
-        runs = int((np.diff(np.pad(masks, ((0, 0), (0, 0), (1, 0))).astype(np.int8), axis=2) == 1).sum())
-        res.update(components_per_image_mean=float(counts.mean()), components_per_image_max=int(counts.max()),
-                   overflowed=int(t.overflowed().sum()), area_median=float(np.median(used)), area_mean=float(used.mean()),
-                   area_max=int(used.max()), foreground_fraction=float(masks.mean()), foreground_pixels=int(masks.sum()), row_runs=runs)
-        ok = True
-        for i in range(min(host_maps, len(masks))):
-            ref = P.measure(masks[i], v[i], 1, cap)
-            ok &= int(counts[i]) == int(ref["counts"][0])
-            for key in ("area", "bbox", "sum_rc", "intensity_sum", "intensity_max"):
-                ok &= bool(np.array_equal(getattr(t, key)[i].cpu().numpy(), ref[key][0]))
-        res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    t = G.measure(d, intensity=dv, max_regions=cap)
+    counts, area = t.counts.cpu().numpy(), t.area.cpu().numpy()
+    used = area[area > 0]
+    runs = int((np.diff(np.pad(masks, ((0, 0), (0, 0), (1, 0))).astype(np.int8), axis=2) == 1).sum())
+    res.update(components_per_image_mean=float(counts.mean()), components_per_image_max=int(counts.max()),
+               overflowed=int(t.overflowed().sum()), area_median=float(np.median(used)), area_mean=float(used.mean()),
+               area_max=int(used.max()), foreground_fraction=float(masks.mean()), foreground_pixels=int(masks.sum()), row_runs=runs)
+    ok = True
+    for i in range(min(host_maps, len(masks))):
+        ref = P.measure(masks[i], v[i], 1, cap)
+        ok &= int(counts[i]) == int(ref["counts"][0])
+        for key in ("area", "bbox", "sum_rc", "intensity_sum", "intensity_max"):
+            ok &= bool(np.array_equal(getattr(t, key)[i].cpu().numpy(), ref[key][0]))
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
     print(json.dumps({name: res}), flush=True)
     return res
 
 
 def measure_main(args):
-    """the production library here; the per-pixel form of the accumulation in a child process on the A/B flavour"""
     dev = torch.device("cuda:0")
-    child = os.environ.get("CELLSEG_MEASURE_PER_PIXEL", "") not in ("", "0")
-    res = {name: measure_case(name, masks, args.reps, args.host_maps, dev, not child) for name, masks in mask_sets()}
-    if child:
-        return res
-    env = dict(os.environ, CELLSEG_LIB_FLAVOUR="ab", CELLSEG_MEASURE_PER_PIXEL="1")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--measure", "--reps", str(args.reps)], env=env, capture_output=True,
-                       text=True, timeout=600)
-    if r.returncode != 0:
-        sys.stderr.write(r.stderr)
-        sys.exit(r.returncode)
-    for line in (x for x in r.stdout.splitlines() if x.startswith("{")):
-        for name, v in json.loads(line).items():
-            res[name]["measure_per_pixel_ms"] = v["measure_ms"]
-    print(json.dumps({k: {x: v[x] for x in ("label_ms", "measure_ms", "measure_per_pixel_ms")} for k, v in res.items()}), flush=True)
-    return res
+    return {name: measure_case(name, masks, args.reps, args.host_maps, dev) for name, masks in mask_sets()}
 
 
 def seeds_in_components(lab, per_component, seed):
