@@ -35,12 +35,13 @@ owner of a pixel decided from the batch's corners, no per-pixel state).  ``infer
 method="distancetransform").per_image()[0]`` returns the pair it would.
 """
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
 from . import kernels as K
+from ._args import _device, _images, _tensor
 
 _ONE = 1 << 14
 _MAX_KSIZE = 31
@@ -81,30 +82,15 @@ def _ndim(x):
     return x.dim() if torch.is_tensor(x) else np.ndim(x)
 
 
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _as_u8_maps(masks, what):
     """uint8 numpy / torch [H,W] or [N,H,W] -> (device tensor [N,H,W], was_2d)."""
-    t = torch.from_numpy(np.ascontiguousarray(masks)) if isinstance(masks, np.ndarray) else masks
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
-    if t.dtype != torch.uint8:
-        raise TypeError(f"{what}: expected a uint8 mask (quantise probabilities first), got {t.dtype}")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
-    two_d = t.dim() == 2
-    if two_d:
-        t = t.unsqueeze(0)
-    if not t.is_cuda:
-        t = t.to(_device())
-    return t.contiguous(), two_d
+    t = _images(masks, what, torch.uint8, "a uint8 mask (quantise probabilities first), got {}", lift=True, to_device=True)
+    return t.contiguous(), masks.ndim == 2
 
 
 def quantize(probs):
     """fp32 probabilities (numpy or torch, any shape) -> uint8 ``trunc(255 p)`` on the device, same shape."""
-    t = torch.from_numpy(np.ascontiguousarray(probs)) if isinstance(probs, np.ndarray) else probs
+    t = _tensor(probs)
     if t.dtype != torch.float32:
         raise TypeError(f"quantize expects float32 probabilities, got {t.dtype}")
     if not t.is_cuda:
@@ -143,19 +129,18 @@ def _check_dt_shape(shape):
         raise ValueError(f"distance transform: H^2 + W^2 must stay below 2^31, got a {H}x{W} map")
 
 
-def _dt_maps(mask_u8, thr_for_dt, what):
-    thr = _dt_threshold(thr_for_dt)
+def _dt_maps(mask_u8, what):
     if hasattr(mask_u8, "shape") and len(mask_u8.shape) >= 2:
         _check_dt_shape(mask_u8.shape)                                    # before the map is copied anywhere
-    t, two_d = _as_u8_maps(mask_u8, what)
-    return t, two_d, thr
+    return _as_u8_maps(mask_u8, what)
 
 
 def distance_transform_sq(mask_u8, thr_for_dt=10):
     """Exact squared Euclidean distance of every pixel with ``mask > thr_for_dt`` to the nearest pixel without (module docstring);
     ``-1`` everywhere in a map that has no such pixel.  mask_u8: uint8 [H, W] or [N, H, W] (numpy or torch); returns an int32
     device tensor of the same shape."""
-    t, two_d, thr = _dt_maps(mask_u8, thr_for_dt, "distance_transform_sq")
+    thr = _dt_threshold(thr_for_dt)
+    t, two_d = _dt_maps(mask_u8, "distance_transform_sq")
     out = K.detect_edt_sq(t, thr)
     return out[0] if two_d else out
 
@@ -164,7 +149,8 @@ def distance_smooth(mask_u8, thr_for_dt=10):
     """The ``"distancetransform"`` smoothing (test_seg.py:325-329): threshold, exact distance transform, min-max normalisation of
     every map to 0..255, rounded half to even in integer arithmetic (module docstring).  Returns a uint8 device tensor of the
     same shape as mask_u8."""
-    t, two_d, thr = _dt_maps(mask_u8, thr_for_dt, "distance_smooth")
+    thr = _dt_threshold(thr_for_dt)
+    t, two_d = _dt_maps(mask_u8, "distance_smooth")
     out = K.detect_edt_smooth(t, thr)
     return out[0] if two_d else out
 
@@ -300,25 +286,46 @@ class DetectResult:
         return Rg.split(masks, pts, off, limits=S._limits(self.cell_counts, N), connectivity=connectivity)
 
 
-def _detect(src, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, force_global, method="gaussianblur",
-            thr_for_dt=10):
-    """src: device [N,H,W] uint8 masks or fp32 probabilities (quantised inside the smoothing kernel)."""
-    _check_method(method)
-    if method == "gaussianblur":
-        tx, ty = _blur_taps(ksize, sigmaX, sigmaY)
-    else:
-        dt_thr = _dt_threshold(thr_for_dt)
+@dataclass(frozen=True)
+class DetectOptions:
+    """The parameters of ``detect_points``, checked once on the host as far as they can be without an image; ``taps`` (the blur's
+    two int32 tap arrays) or ``dt_thr`` (the distance method's integer threshold) keep what the checks computed."""
+    thr: float = 0.2
+    window_size: int = 16
+    interval: int = 10
+    eps: float = 15
+    ksize: tuple = (15, 15)
+    sigmaX: float = 3.
+    sigmaY: float = 0.
+    max_iter: int = 100
+    method: str = "gaussianblur"
+    thr_for_dt: float = 10
+    taps: object = field(default=None, init=False, repr=False, compare=False)
+    dt_thr: object = field(default=None, init=False, repr=False, compare=False)
+
+    def __post_init__(self):
+        _check_method(self.method)
+        if self.method == "gaussianblur":
+            object.__setattr__(self, "taps", _blur_taps(self.ksize, self.sigmaX, self.sigmaY))
+        else:                                                             # ksize and sigma are not consulted
+            object.__setattr__(self, "dt_thr", _dt_threshold(self.thr_for_dt))
+        if self.eps < 0 or not math.isfinite(self.eps):
+            raise ValueError("eps must be finite and non-negative")
+        if int(self.max_iter) < 0:
+            raise ValueError("max_iter must be non-negative")
+
+
+def _detect(src, cell_counts, opts, force_global=False):
+    """src: device [N,H,W] uint8 masks or fp32 probabilities (quantised inside the smoothing kernel); opts: DetectOptions."""
+    blur = opts.method == "gaussianblur"
+    if not blur:
         _check_dt_shape(src.shape)
-    if eps < 0 or not math.isfinite(eps):
-        raise ValueError("eps must be finite and non-negative")
-    if int(max_iter) < 0:
-        raise ValueError("max_iter must be non-negative")
     N, H, W = src.shape
-    if K.detect_grid_size(H, W, interval, window_size) <= 0:
-        raise ValueError(f"window_size {window_size} does not fit a {H}x{W} map (or interval {interval} is not positive)")
-    blurred = K.detect_blur(src, tx, ty) if method == "gaussianblur" else K.detect_edt_smooth(src, dt_thr)
-    pts, n_pts = K.detect_meanshift(blurred, int(interval), int(window_size), float(thr) * 255.0, int(max_iter))
-    out_pts, out_w, out_off = K.detect_cluster(pts, n_pts, float(eps), blurred, force_global=force_global)
+    if K.detect_grid_size(H, W, opts.interval, opts.window_size) <= 0:
+        raise ValueError(f"window_size {opts.window_size} does not fit a {H}x{W} map (or interval {opts.interval} is not positive)")
+    blurred = K.detect_blur(src, *opts.taps) if blur else K.detect_edt_smooth(src, opts.dt_thr)
+    pts, n_pts = K.detect_meanshift(blurred, int(opts.interval), int(opts.window_size), float(opts.thr) * 255.0, int(opts.max_iter))
+    out_pts, out_w, out_off = K.detect_cluster(pts, n_pts, float(opts.eps), blurred, force_global=force_global)
     head = torch.cat([out_off, n_pts.to(torch.int64)]).cpu().numpy()        # the one synchronisation of the batch
     offsets, n_kept = head[:N + 1], head[N + 1:]
     total = int(offsets[-1])
@@ -333,13 +340,10 @@ def detect_points(masks_u8, cell_counts=None, thr=0.2, window_size=16, interval=
     one count for every map, or one per map (applied by ``DetectResult.per_image``).  ``method="distancetransform"`` smooths by
     ``distance_smooth(., thr_for_dt)`` instead of the blur (ksize, sigmaX and sigmaY are then not consulted).  ``_force_global``
     (tests) takes the multi-launch clustering path at any size."""
-    _check_method(method)                                                 # argument errors before any device work
-    if method == "gaussianblur":
-        _blur_taps(ksize, sigmaX, sigmaY)
-        t, _ = _as_u8_maps(masks_u8, "detect_points")
-    else:
-        t, _, _ = _dt_maps(masks_u8, thr_for_dt, "detect_points")
-    return _detect(t, cell_counts, thr, window_size, interval, eps, ksize, sigmaX, sigmaY, max_iter, _force_global, method, thr_for_dt)
+    opts = DetectOptions(thr=thr, window_size=window_size, interval=interval, eps=eps, ksize=ksize, sigmaX=sigmaX, sigmaY=sigmaY,
+                         max_iter=max_iter, method=method, thr_for_dt=thr_for_dt)                    # argument errors before any upload
+    t, _ = _as_u8_maps(masks_u8, "detect_points") if method == "gaussianblur" else _dt_maps(masks_u8, "detect_points")
+    return _detect(t, cell_counts, opts, _force_global)
 
 
 _BLUR_KEYS = {"ksize", "sigmaX", "sigmaY", "borderType"}

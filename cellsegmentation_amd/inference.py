@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from ._args import _device, _images, _tensor
 
 try:
     from tqdm import tqdm
@@ -152,27 +153,44 @@ def detect_cells(loader, model, device, eps=11, reg_limit=False, method="gaussia
     sigma are then not consulted); either way the fp32 probabilities go straight into the smoothing kernel.  With reg_limit the
     image-mode count rint(reg) caps each image's list (test_seg.py:217-221; the model is set back to segment mode afterwards).  Returns [(points, discarded)] per image, as meanshift_cluster."""
     from . import detect as D
-    D._check_method(method)
-    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
-    if unknown:
-        raise TypeError(f"detect_cells: unexpected arguments {sorted(unknown)}")
-    opts = {"ksize": (15, 15), "sigmaX": 3.}
-    opts.update(blur)
+    opts = _detect_options("detect_cells", eps, method, thr_for_dt, **blur)
     model.eval()
     out = []
     with torch.no_grad():
         for i, data in enumerate(tqdm(loader, desc="cell detecting")):
-            x = data.to(device)
-            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
-            counts = None
-            if reg_limit:
-                model.setmode("image")
-                counts = np.round(model(x)[1].detach()[:, 0].float().cpu().numpy()).astype(int)
-                model.setmode("segment")
-            res = D._detect(probs, counts, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10), eps, opts["ksize"],
-                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
-            out.extend(res.per_image())
+            probs, reg = _segment_batch(model, data.to(device), reg_limit, False)     # the count only caps the list
+            out.extend(D._detect(probs, reg.cpu().numpy().astype(int) if reg_limit else None, opts).per_image())
     return out
+
+
+def _detect_options(what, eps, method, thr_for_dt, **blur):
+    """the detection arguments of a driver -> detect.DetectOptions: every argument error that needs no image, before the model is
+    touched.  ``blur``: the driver's remaining keyword arguments."""
+    from . import detect as D
+    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
+    if unknown:
+        raise TypeError(f"{what}: unexpected arguments {sorted(unknown)}")
+    return D.DetectOptions(eps=eps, method=method, thr_for_dt=thr_for_dt, **blur)
+
+
+def _rounded_counts(model, x):
+    """rint(reg) of an image-mode forward -> device fp32 [n]"""
+    return torch.round(model(x)[1].detach()[:, 0].float())
+
+
+def _segment_batch(model, x, want_counts, zero_empty):
+    """One batch through the model in segment mode -> (probs, reg): probs fp32 [n, H, W] = softmax channel 1; reg = the image-mode
+    counts rint(reg) of a second forward as a device fp32 [n] tensor, None without ``want_counts`` (the model is set back to
+    segment mode).  ``zero_empty``: the map of an image whose count is 0 is zeroed (test_seg.py:518-524)."""
+    probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
+    reg = None
+    if want_counts:
+        model.setmode("image")
+        reg = _rounded_counts(model, x)
+        model.setmode("segment")
+        if zero_empty:
+            probs = probs * (reg != 0).to(probs.dtype)[:, None, None]
+    return probs, reg
 
 
 @dataclass
@@ -205,26 +223,19 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
     from . import detect as D
     from . import tiles as T
-    D._check_method(method)
-    unknown = set(blur) - {"thr", "window_size", "ksize", "sigmaX", "sigmaY", "max_iter"}
-    if unknown:
-        raise TypeError(f"detect_slide: unexpected arguments {sorted(unknown)}")
-    opts = {"ksize": (15, 15), "sigmaX": 3.}
-    opts.update(blur)
-    if method == "gaussianblur":
-        D._blur_taps(opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.))
+    opts = _detect_options("detect_slide", eps, method, thr_for_dt, **blur)   # ``interval`` is the patch grid's: never in blur
     ph, pw = T._pair(patch_size, "patch_size")
     if ph != pw:
         raise ValueError(f"detect_slide cuts square patches (tiles.gather_tiles), got patch_size {(ph, pw)}")
     if int(batch_size) < 1:
         raise ValueError(f"batch_size must be positive, got {batch_size!r}")
-    img = torch.from_numpy(np.ascontiguousarray(image_u8)) if isinstance(image_u8, np.ndarray) else image_u8
+    img = _tensor(image_u8)
     if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
         raise TypeError("detect_slide expects a uint8 image shaped [H, W, 3] (numpy or torch)")
     H, W = int(img.shape[0]), int(img.shape[1])
     corners = np.asarray(T.sample_patches((H, W), (ph, pw), interval), dtype=np.int32).reshape(-1, 2)
     if device is None:
-        device = img.device if img.is_cuda else D._device()
+        device = _device(img)
     img = img.to(device).contiguous()[None]
     rc = torch.from_numpy(corners).to(device)                              # every corner of the slide, uploaded once
     ti = torch.zeros((len(corners),), dtype=torch.int32, device=device)
@@ -238,12 +249,10 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
             model.setmode("segment")
             K.stitch_logits(mask, model(x).float().contiguous(), rc[i:i + batch_size], 1)
             model.setmode("image")
-            total += torch.round(model(x)[1].detach()[:, 0].float()).sum(dtype=torch.float64)
+            total += _rounded_counts(model, x).sum(dtype=torch.float64)
     model.setmode("segment")
     count = int(total.item())                                              # the first synchronisation of the slide
-    res = D._detect(mask[None], count if reg_limit else None, opts.get("thr", 0.2), opts.get("window_size", 16), 10, eps,
-                    opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
-    points, discarded = res.per_image()[0]
+    points, discarded = D._detect(mask[None], count if reg_limit else None, opts).per_image()[0]
     return SlideResult(points, discarded, count, mask)
 
 
@@ -253,20 +262,13 @@ def detect_slides(slides, model, device=None, **kwargs):
         yield detect_slide(image_u8, model, device, **kwargs)
 
 
-def _cleaned_batch(model, x, threshold, mo, ho, reg_limit, with_counts=False):
-    """test_seg.py:515-527 for one batch on the device -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W]); with_counts:
-    also the image-mode counts rint(reg) as a device fp32 [n] tensor (None without reg_limit)"""
+def _cleaned_batch(model, x, threshold, mo, ho, want_counts, zero_empty):
+    """test_seg.py:515-527 for one batch on the device: ``_segment_batch`` -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W],
+    reg)"""
     from . import regions as Rg
-    probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
-    counts = None
-    if reg_limit:
-        model.setmode("image")
-        counts = torch.round(model(x)[1].detach()[:, 0].float())
-        model.setmode("segment")
-        probs = probs * (counts != 0).to(probs.dtype)[:, None, None]
+    probs, reg = _segment_batch(model, x, want_counts, zero_empty)
     classes = Rg.threshold(probs, threshold)
-    classes = Rg.remove_small_regions(classes, mo, ho, out=classes)
-    return (probs, classes, counts) if with_counts else (probs, classes)
+    return probs, Rg.remove_small_regions(classes, mo, ho, out=classes), reg
 
 
 def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):
@@ -280,7 +282,7 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
     out = []
     with torch.no_grad():
         for i, data in enumerate(tqdm(loader, desc="image segmenting")):
-            out.append(_cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit)[1])
+            out.append(_cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)[1])
     return torch.cat(out) if out else torch.zeros((0,), dtype=torch.bool, device=device)
 
 
@@ -297,7 +299,7 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     tables = []
     with torch.no_grad():
         for data in tqdm(loader, desc="cell measuring"):
-            probs, classes = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit)
+            probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)
             tables.append(Rg.measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions))
     return [d for t in tables for d in t.per_image()]
 
@@ -313,14 +315,12 @@ def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=
 def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity):
     """a stitched uint8 [H, W] map -> (the map on the device, its cleaned foreground ``map > thr_u8`` as device bool)"""
     from . import regions as Rg
-    t = torch.from_numpy(np.ascontiguousarray(mask_u8)) if isinstance(mask_u8, np.ndarray) else mask_u8
-    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2:
-        raise TypeError(f"{what}: expected a uint8 [H, W] map")
     if isinstance(thr_u8, bool) or int(thr_u8) != thr_u8 or not 0 <= thr_u8 <= 255:
         raise ValueError(f"{what}: thr_u8 must be an integer in [0, 255], got {thr_u8!r}")
-    if not t.is_cuda:
-        t = t.to(Rg._device())
-    t = t.contiguous()
+    try:
+        t = _images(mask_u8, what, torch.uint8, "a uint8 map, got {}", ranks=(2,), to_device=True).contiguous()
+    except (TypeError, ValueError):                                         # one message, one type, whatever is wrong with the map
+        raise TypeError(f"{what}: expected a uint8 [H, W] map") from None
     fg = t > int(thr_u8)
     return t, Rg.remove_small_regions(fg, min_object_size, hole_area_threshold, connectivity, out=fg)
 
@@ -368,12 +368,7 @@ def evaluate_detection(loader, model, device, threshold=0.5, eps=11, reg_limit=F
     from . import metrics as M
     from . import regions as Rg
     from . import score as S
-    D._check_method(method)
-    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
-    if unknown:
-        raise TypeError(f"evaluate_detection: unexpected arguments {sorted(unknown)}")
-    opts = {"ksize": (15, 15), "sigmaX": 3.}
-    opts.update(blur)
+    opts = _detect_options("evaluate_detection", eps, method, thr_for_dt, **blur)
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
     S.radius_squared(radius)
     model.setmode("segment")
@@ -383,24 +378,22 @@ def evaluate_detection(loader, model, device, threshold=0.5, eps=11, reg_limit=F
         for i, batch in enumerate(tqdm(loader, desc="testing")):
             images, masks, points = batch[0], batch[1], batch[2]
             x = images.to(device)
-            probs = K.softmax_channel_fwd(model(x).contiguous(), 1)
-            model.setmode("image")
-            reg = torch.round(model(x)[1].detach()[:, 0].float())
-            model.setmode("segment")
+            probs, classes, reg = _cleaned_batch(model, x, threshold, mo, ho, True, reg_limit)       # the count column: always
             counts = reg.cpu().numpy().astype(int)
-            if reg_limit:
-                probs = probs * (reg != 0).to(probs.dtype)[:, None, None]
-            res = D._detect(probs, counts if reg_limit else None, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10),
-                            eps, opts["ksize"], opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
-            sc = res.score(_batch_points(points, x.shape[0]), gt_xy=True, radius=radius)
-            classes = Rg.threshold(probs, threshold)
-            classes = Rg.remove_small_regions(classes, mo, ho, out=classes)
+            sc = D._detect(probs, counts if reg_limit else None, opts).score(_batch_points(points, x.shape[0]), gt_xy=True, radius=radius)
             truth = torch.as_tensor(masks).to(device=device, dtype=torch.float32) / 255
             dice = M.dice_coef(classes.float(), truth.reshape(classes.shape))
             for k, v in zip(cols, (counts, sc.tp, sc.fp, sc.fn, sc.precision, sc.recall, sc.f1, dice.cpu().numpy().astype(np.float64))):
                 cols[k].append(v)
+    return _columns(cols, mean=("p", "r", "f1", "dice"))
+
+
+def _columns(cols, **means):
+    """the tail of the ``evaluate_*`` drivers: per-batch column pieces -> a dict of numpy arrays (empty float64 for an empty loader),
+    plus under every name of ``means`` the tuple of the averages of the columns it lists (0.0 for an empty column)"""
     out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
-    out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "dice"))
+    for name, keys in means.items():
+        out[name] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in keys)
     return out
 
 
@@ -419,12 +412,7 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     from . import detect as D
     from . import regions as Rg
     from . import score as S
-    D._check_method(method)
-    unknown = set(blur) - {"thr", "window_size", "interval", "ksize", "sigmaX", "sigmaY", "max_iter"}
-    if unknown:
-        raise TypeError(f"evaluate_instances: unexpected arguments {sorted(unknown)}")
-    opts = {"ksize": (15, 15), "sigmaX": 3.}
-    opts.update(blur)
+    opts = _detect_options("evaluate_instances", eps, method, thr_for_dt, **blur)
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
     conn = Rg._check_connectivity(connectivity)
     S.check_iou_threshold(iou_threshold)
@@ -438,11 +426,8 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     with torch.no_grad():
         for batch in tqdm(loader, desc="testing"):
             images, masks = batch[0], batch[1]
-            probs, classes, reg = _cleaned_batch(model, images.to(device), threshold, mo, ho, reg_limit, with_counts=True)
-            counts = reg.cpu().numpy().astype(int) if reg_limit else None
-            res = D._detect(probs, counts, opts.get("thr", 0.2), opts.get("window_size", 16), opts.get("interval", 10), eps, opts["ksize"],
-                            opts["sigmaX"], opts.get("sigmaY", 0.), opts.get("max_iter", 100), False, method, thr_for_dt)
-            parts = res.split(classes, connectivity=conn)
+            probs, classes, reg = _cleaned_batch(model, images.to(device), threshold, mo, ho, reg_limit, reg_limit)
+            parts = D._detect(probs, reg.cpu().numpy().astype(int) if reg_limit else None, opts).split(classes, connectivity=conn)
             truth = torch.as_tensor(masks)
             if truth.dtype == torch.uint8:
                 truth = Rg.label(truth.to(device).reshape(classes.shape) != 0, conn)
@@ -455,8 +440,4 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
                 ov = Rg.overlap_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score()
                 cols["aji"].append(ov.aji)
                 cols["dice_obj"].append(ov.dice_obj)
-    out = {k: (np.concatenate(v) if v else np.zeros((0,), np.float64)) for k, v in cols.items()}
-    out["mean"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("p", "r", "f1", "sq", "pq"))
-    if overlap:
-        out["mean_overlap"] = tuple(float(out[k].mean()) if len(out[k]) else 0.0 for k in ("aji", "dice_obj"))
-    return out
+    return _columns(cols, mean=("p", "r", "f1", "sq", "pq"), **({"mean_overlap": ("aji", "dice_obj")} if overlap else {}))

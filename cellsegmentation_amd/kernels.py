@@ -1090,15 +1090,22 @@ def detect_blur(src, taps_x, taps_y):
     return out
 
 
+def _workspace(size_fn, device, why, *args):
+    """the caller-owned scratch of one library call: ``size_fn(*args)`` bytes as uint8; 0 = the library refuses these sizes (``why``)"""
+    nbytes = size_fn(*args)
+    if nbytes == 0:
+        raise ValueError(why)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
 def stitch_patches(patches, corners, H, W):
     """patches uint8 [M,ph,pw], corners int32 [M,2] (device) -> uint8 [H,W], the highest patch index winning overlaps."""
     M, ph, pw = patches.shape
     lib = _lib.load()
-    ws_bytes = lib.cs_stitch_workspace(H, W)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=patches.device)
+    ws = _workspace(lib.cs_stitch_workspace, patches.device, f"stitch_patches: a {H}x{W} image has no pixels", H, W)
     out = torch.empty((H, W), dtype=torch.uint8, device=patches.device)
     _lib.check(lib.cs_stitch_patches(_p(patches.contiguous()) if M else None, M, ph, pw, _p(corners.contiguous()) if M else None, H, W, _p(out),
-                                     _p(ws), ws_bytes, _stream()), "stitch_patches")
+                                     _p(ws), ws.numel(), _stream()), "stitch_patches")
     return out
 
 
@@ -1136,27 +1143,24 @@ def detect_cluster(pts, n_pts, eps, blurred, force_global=False):
     N, cap, _ = pts.shape
     _, H, W = blurred.shape
     lib = _lib.load()
-    ws_bytes = lib.cs_detect_cluster_workspace(N, cap)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=pts.device)
+    ws = _workspace(lib.cs_detect_cluster_workspace, pts.device, f"detect_cluster: no workspace for {(N, cap)}", N, cap)
     out_pts = torch.empty((N * cap, 2), dtype=torch.int64, device=pts.device)
     out_w = torch.empty((N * cap,), dtype=torch.int32, device=pts.device)
     out_off = torch.empty((N + 1,), dtype=torch.int64, device=pts.device)
     _lib.check(lib.cs_detect_cluster(_p(pts.contiguous()), _p(n_pts.contiguous()), N, cap, float(eps), _p(blurred.contiguous()), H, W,
-                                     int(bool(force_global)), _p(out_pts), _p(out_w), _p(out_off), _p(ws), ws_bytes, _stream()), "detect_cluster")
+                                     int(bool(force_global)), _p(out_pts), _p(out_w), _p(out_off), _p(ws), ws.numel(), _stream()), "detect_cluster")
     return out_pts, out_w, out_off
 
 
 def _detect_edt(src, thr, smooth):
     N, H, W = src.shape
     lib = _lib.load()
-    ws_bytes = lib.cs_detect_edt_workspace(N, H, W, int(smooth))
-    if ws_bytes == 0:
-        raise ValueError(f"distance transform: a call takes 0 < N <= 65535 maps with H^2 + W^2 < 2^31, got {(N, H, W)}")
+    ws = _workspace(lib.cs_detect_edt_workspace, src.device,
+                    f"distance transform: a call takes 0 < N <= 65535 maps with H^2 + W^2 < 2^31, got {(N, H, W)}", N, H, W, int(smooth))
     s = _aligned16(src)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=s.device)
     out = torch.empty((N, H, W), dtype=torch.uint8 if smooth else torch.int32, device=s.device)
     fn = lib.cs_detect_edt_smooth if smooth else lib.cs_detect_edt_sq
-    _lib.check(fn(_p(s), int(s.dtype == torch.float32), N, H, W, int(thr), _p(out), _p(ws), ws_bytes, _stream()),
+    _lib.check(fn(_p(s), int(s.dtype == torch.float32), N, H, W, int(thr), _p(out), _p(ws), ws.numel(), _stream()),
                "detect_edt_smooth" if smooth else "detect_edt_sq")
     return out
 
@@ -1175,10 +1179,8 @@ def detect_edt_smooth(src, thr=10):
 # ---------------------------------------------------------------- small-region clean-up (csrc/regions.hip; regions.py is the public API)
 def regions_workspace(N, H, W, device):
     """the caller-owned scratch of one cs_regions_* call on [N,H,W] (reusable by later calls of the same shape)"""
-    ws_bytes = _lib.load().cs_regions_workspace(N, H, W)
-    if ws_bytes == 0:
-        raise ValueError(f"regions: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels, got {(N, H, W)}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    return _workspace(_lib.load().cs_regions_workspace, device,
+                      f"regions: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels, got {(N, H, W)}", N, H, W)
 
 
 def _regions_args(mask, ws):
@@ -1248,10 +1250,8 @@ def regions_measure(mask, capacity, intensity=None, connectivity=1, numbered=Fal
 
 def regions_split_workspace(N, H, W, P, device):
     """the caller-owned scratch of one cs_regions_split call on [N,H,W] with a points buffer of P rows"""
-    ws_bytes = _lib.load().cs_regions_split_workspace(N, H, W, int(P))
-    if ws_bytes == 0:
-        raise ValueError(f"regions_split: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels and P >= 0 points, got {(N, H, W, P)}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    why = f"regions_split: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels and P >= 0 points, got {(N, H, W, P)}"
+    return _workspace(_lib.load().cs_regions_split_workspace, device, why, N, H, W, int(P))
 
 
 def regions_split(mask, points, offsets, limits=None, connectivity=1, labels=None, counts=None, live=None, ws=None):
@@ -1315,11 +1315,9 @@ def _label_pair_args(what, pred, truth, want_counts):
 
 def regions_match_workspace(N, cap_pred, cap_truth, device):
     """the caller-owned scratch of one cs_regions_match_labels call on N images with these capacities"""
-    ws_bytes = _lib.load().cs_regions_match_workspace(int(N), int(cap_pred), int(cap_truth))
-    if ws_bytes == 0:
-        raise ValueError("regions_match_labels: a call takes 0 < N <= 65535 images and capacities >= 1 with N cap_pred "
-                         f"bit_length(cap_truth) < 2^31 and N cap_truth < 2^31, got {(N, cap_pred, cap_truth)}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    why = ("regions_match_labels: a call takes 0 < N <= 65535 images and capacities >= 1 with N cap_pred "
+           f"bit_length(cap_truth) < 2^31 and N cap_truth < 2^31, got {(N, cap_pred, cap_truth)}")
+    return _workspace(_lib.load().cs_regions_match_workspace, device, why, int(N), int(cap_pred), int(cap_truth))
 
 
 def regions_match_labels(pred, truth, cap_pred, cap_truth, counts_pred=None, counts_truth=None, area_pred=None, area_truth=None,
@@ -1351,12 +1349,10 @@ def regions_overlap_slots(max_pairs):
 def regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs, device):
     """the caller-owned scratch of one cs_regions_overlap_labels call on N images with these capacities; it starts with the pair
     table, which the call's result views"""
-    mp = int(max_pairs)
-    ws_bytes = _lib.load().cs_regions_overlap_workspace(int(N), int(cap_pred), int(cap_truth), mp) if 1 <= mp < 1 << 31 else 0
-    if ws_bytes == 0:
-        raise ValueError("regions_overlap_labels: a call takes 0 < N <= 65535 images, capacities >= 1 and 1 <= max_pairs <= 2^29 with "
-                         f"N cap_pred, N cap_truth and N slots < 2^31, got {(N, cap_pred, cap_truth, max_pairs)}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    why = ("regions_overlap_labels: a call takes 0 < N <= 65535 images, capacities >= 1 and 1 <= max_pairs <= 2^29 with "
+           f"N cap_pred, N cap_truth and N slots < 2^31, got {(N, cap_pred, cap_truth, max_pairs)}")
+    size = lambda *a: _lib.load().cs_regions_overlap_workspace(*a) if 1 <= a[3] < 1 << 31 else 0  # noqa: E731  (an int argument)
+    return _workspace(size, device, why, int(N), int(cap_pred), int(cap_truth), int(max_pairs))
 
 
 _OVERLAP_TABLES = (("area_pred", 0), ("area_truth", 1), ("iou_partner", 1), ("iou_inter", 1), ("inter_partner_truth", 1), ("inter_truth", 1),
@@ -1445,10 +1441,8 @@ def regions_hsv_gate(images_hwc, mask, v_max=170):
 # ---------------------------------------------------------------- detections against annotations (csrc/score.hip; score.py is the public API)
 def score_workspace(N, total_gt, device):
     """the caller-owned scratch of one cs_score_points call on N images with total_gt annotations in all"""
-    ws_bytes = _lib.load().cs_score_workspace(int(N), int(total_gt))
-    if ws_bytes == 0:
-        raise ValueError(f"score_points: a call takes 0 < N <= 65535 images, got {N}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    return _workspace(_lib.load().cs_score_workspace, device, f"score_points: a call takes 0 < N <= 65535 images, got {N}",
+                      int(N), int(total_gt))
 
 
 def score_points(hat, hat_off, gt, gt_off, limits=None, radius2=256, want_match=False, force_block=False, ws=None):

@@ -43,13 +43,10 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from ._args import MAX_PIXELS as _MAX_PIXELS          # per kernel call; larger batches are cut into chunks of whole images
+from ._args import _device, _images, _tensor
 
-_MAX_PIXELS = (1 << 31) - 1           # per kernel call; larger batches are cut into chunks of whole images
 _MAX_IMAGES = 65535
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _check_connectivity(connectivity):
@@ -66,23 +63,9 @@ def _check_size(value, name):
 
 def _as_masks(m, what):
     """boolean numpy / torch [H,W] or [N,H,W] -> (uint8 device view [N,H,W], was_2d); argument errors before any device work."""
-    t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
-    if t.dtype != torch.bool:
-        raise TypeError(f"{what}: expected a boolean mask, got {t.dtype} (an integer array is a label image in scikit-image: not supported)")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
-    if t.numel() == 0:
-        raise ValueError(f"{what}: empty mask of shape {tuple(t.shape)}")
-    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
-        raise ValueError(f"{what}: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
-    two_d = t.dim() == 2
-    if two_d:
-        t = t.unsqueeze(0)
-    if not t.is_cuda:
-        t = t.to(_device())
-    return t.contiguous().view(torch.uint8), two_d
+    t = _images(m, what, torch.bool, "a boolean mask, got {} (an integer array is a label image in scikit-image: not supported)",
+                noun="mask", lift=True, to_device=True)
+    return t.contiguous().view(torch.uint8), m.ndim == 2
 
 
 def _chunks(t):
@@ -162,7 +145,7 @@ def remove_small_regions(img_bin, min_object_size, hole_area_threshold, connecti
 def threshold(probs, thr):
     """``probs > thr`` as numpy evaluates it for a float32 array and a Python float (``thr`` rounded to float32 first) -> device
     ``torch.bool``, same shape."""
-    t = torch.from_numpy(np.ascontiguousarray(probs)) if isinstance(probs, np.ndarray) else probs
+    t = _tensor(probs)
     if not torch.is_tensor(t) or t.dtype != torch.float32:
         raise TypeError(f"threshold expects float32 probabilities, got {getattr(t, 'dtype', type(t))}")
     if not t.is_cuda:
@@ -211,11 +194,7 @@ class RegionTable:
 
 def _as_intensity(v, shape):
     """uint8 numpy / torch of the mask's shape -> the tensor (not yet on the device); argument errors only"""
-    t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
-    if not torch.is_tensor(t):
-        raise TypeError("measure: intensity must be a numpy array or a torch tensor")
-    if t.dtype != torch.uint8:
-        raise TypeError(f"measure: intensity must be uint8, got {t.dtype}")
+    t = _images(v, "measure", torch.uint8, "uint8, got {}", ranks=None, subject="intensity must be")
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"measure: intensity of shape {tuple(t.shape)} for a mask of shape {tuple(shape)}")
     return t
@@ -368,18 +347,7 @@ def _check_max_regions(max_regions):
 def _as_labels(x, what, masks_go_to="label first"):
     """int32 numpy / torch [H, W] or [N, H, W] -> the tensor (not yet on the device); argument errors only.  ``masks_go_to``: where
     the message sends a caller who passed a boolean mask."""
-    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: expected a numpy array or a torch tensor")
-    if t.dtype != torch.int32:
-        raise TypeError(f"{what}: expected an int32 label image, got {t.dtype} (boolean masks go to {masks_go_to})")
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected [H, W] or [N, H, W], got shape {tuple(t.shape)}")
-    if t.numel() == 0:
-        raise ValueError(f"{what}: empty label image of shape {tuple(t.shape)}")
-    if t.shape[-1] * t.shape[-2] > _MAX_PIXELS:
-        raise ValueError(f"{what}: one image of {t.shape[-2]}x{t.shape[-1]} has 2^31 pixels or more")
-    return t
+    return _images(x, what, torch.int32, f"an int32 label image, got {{}} (boolean masks go to {masks_go_to})", noun="label image")
 
 
 def measure_labels(labels, intensity=None, max_regions=None, counts=None):

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from ._args import _device
 
 _I32 = (-(1 << 31), (1 << 31) - 1)
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
@@ -178,13 +179,6 @@ def _run(hat_dev, hat_off_dev, n_hat_rows, prepared, limits, radius2, return_mat
     p, r, f1 = precision_recall(c[:, 0], c[:, 1], c[:, 2], return_f1=True)
     m = match[:n_hat_rows].cpu().numpy() if return_match else None
     return ScoreResult(c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy(), p, r, f1, m)
-
-
-def _device(*xs):
-    for x in xs:
-        if torch.is_tensor(x) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def score_points(points_hat, points, hat_offsets=None, offsets=None, limits=None, radius=16, gt_xy=False, return_match=False,

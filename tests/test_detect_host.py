@@ -112,3 +112,77 @@ def test_argument_errors():
         D.meanshift_cluster(mask, "gaussianblur", ksize=(14, 15), sigmaX=3.)
     with pytest.raises(TypeError):
         D.detect_points(np.zeros((2, 64, 64), np.float64))
+
+
+def test_detect_options_defaults_are_those_of_detect_points():
+    import dataclasses
+    import inspect
+    sig = inspect.signature(D.detect_points).parameters
+    fields = [f for f in dataclasses.fields(D.DetectOptions) if f.init]
+    assert [f.name for f in fields] == ["thr", "window_size", "interval", "eps", "ksize", "sigmaX", "sigmaY", "max_iter", "method",
+                                        "thr_for_dt"]
+    for f in fields:
+        assert sig[f.name].default == f.default and type(sig[f.name].default) is type(f.default), f.name
+    assert set(sig) - {f.name for f in fields} == {"masks_u8", "cell_counts", "_force_global"}
+    opts = D.DetectOptions()
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        opts.eps = 3
+    assert all(np.array_equal(t, D.gaussian_taps(15, 3.)) for t in opts.taps) and opts.dt_thr is None
+    dt = D.DetectOptions(method="distancetransform", thr_for_dt=12.7, ksize=(0, 0), sigmaX=-1.)     # ksize / sigma: not consulted
+    assert dt.taps is None and dt.dt_thr == 12
+    assert D.DetectOptions(sigmaY=2.).taps[1].tolist() == D.gaussian_taps(15, 2.).tolist()
+
+
+_BAD_OPTIONS = [
+    (dict(method="median"), ValueError, "Smoothing method not found. "),
+    (dict(ksize=(0, 0)), ValueError, r"ksize \(0, 0\) \(size derived from sigma\) is not supported: pass odd kernel sizes"),
+    (dict(ksize=15), ValueError, r"ksize must be a pair \(kx, ky\), got 15"),
+    (dict(ksize=(14, 15)), ValueError, "ksize must be a positive odd integer, got 14"),
+    (dict(ksize=(33, 15)), ValueError, "ksize 33 > 31 is not supported"),
+    (dict(ksize=(5, 5), sigmaX=0.), ValueError, "cv2's fixed kernel tables"),
+    (dict(eps=-1), ValueError, "eps must be finite and non-negative"),
+    (dict(eps=float("inf")), ValueError, "eps must be finite and non-negative"),
+    (dict(eps=float("nan")), ValueError, "eps must be finite and non-negative"),
+    (dict(max_iter=-1), ValueError, "max_iter must be non-negative"),
+    (dict(method="distancetransform", thr_for_dt=float("nan")), ValueError, "thr_for_dt must be finite, got nan"),
+    (dict(method="distancetransform", thr_for_dt=float("inf")), ValueError, "thr_for_dt must be finite, got inf"),
+    (dict(method="distancetransform", eps=-2), ValueError, "eps must be finite and non-negative"),
+]
+
+
+@pytest.mark.parametrize("kw,exc,msg", _BAD_OPTIONS)
+def test_invalid_options_raise_alike_everywhere(kw, exc, msg):
+    """the same type and message from the record, from detect_points (before the mask is looked at) and from a driver (before the
+    model or the loader is touched)"""
+    from cellsegmentation_amd import inference as I
+    raised = []
+    for call in (lambda: D.DetectOptions(**kw), lambda: D.detect_points(None, **kw), lambda: I.detect_cells([], None, None, **kw)):
+        with pytest.raises(exc, match=msg) as e:
+            call()
+        raised.append((type(e.value), str(e.value)))
+    assert raised[0] == raised[1] == raised[2]
+
+
+def test_drivers_name_themselves_and_check_before_the_model():
+    from cellsegmentation_amd import inference as I
+    img = np.zeros((150, 170, 3), np.uint8)
+    drivers = {"detect_cells": lambda **kw: I.detect_cells([], None, None, **kw),
+               "detect_slide": lambda **kw: I.detect_slide(img, None, patch_size=64, **kw),
+               "evaluate_detection": lambda **kw: I.evaluate_detection([], None, None, **kw),
+               "evaluate_instances": lambda **kw: I.evaluate_instances([], None, None, **kw)}
+    for name, call in drivers.items():
+        with pytest.raises(TypeError, match=rf"^{name}: unexpected arguments \['bogus', 'sigma'\]$"):
+            call(sigma=3., bogus=1)
+        with pytest.raises(ValueError, match="Smoothing method not found. "):
+            call(method="median")
+        with pytest.raises(ValueError, match="pass odd kernel sizes"):
+            call(ksize=(0, 0))
+        with pytest.raises(ValueError, match="max_iter must be non-negative"):
+            call(max_iter=-5)
+    # detect_slide's ``interval`` is the patch grid's, never a blur keyword: the options are fine, the grid is refused
+    with pytest.raises(ValueError, match="^interval must be positive, got 0$"):
+        I.detect_slide(img, None, patch_size=64, interval=0)
+    with pytest.raises(ValueError, match="square"):                         # ... and a good interval reaches the next check
+        I.detect_slide(img, None, patch_size=(64, 48), interval=48)
+    assert I._detect_options("detect_slide", 11, "gaussianblur", 10, thr=0.3).interval == 10      # the seed grid's stays 10
+    assert I._detect_options("detect_cells", 11, "gaussianblur", 10, interval=7).interval == 7

@@ -82,8 +82,10 @@ def main():
     taps = D.gaussian_taps(15, 3.)
 
     for method in methods:
+        opts = D.DetectOptions(eps=11, method=method)
+
         def gpu_batch():
-            return D._detect(pd, None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False, method)
+            return D._detect(pd, None, opts)
 
         def gpu_smooth():
             return K.detect_blur(pd, taps, taps) if method == "gaussianblur" else K.detect_edt_smooth(pd, 10)
@@ -114,8 +116,10 @@ def main():
         mask = R.stitch(R.quantize(patches), grid, (H, W))
         stitched_ok = bool(np.array_equal(whole.cpu().numpy(), mask))
     for method in methods:
+        opts = D.DetectOptions(eps=11, method=method)
+
         def gpu_whole():
-            return D._detect(whole[None], None, 0.2, 16, 10, 11, (15, 15), 3., 0., 100, False, method)
+            return D._detect(whole[None], None, opts)
 
         def gpu_smooth():
             return K.detect_blur(whole[None], taps, taps) if method == "gaussianblur" else K.detect_edt_smooth(whole[None], 10)
