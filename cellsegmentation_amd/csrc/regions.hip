@@ -17,6 +17,8 @@
 //             and an exact 64-bit integer test per pred label
 //   overlap   the same two images: every (pred, truth) pair that shares a pixel with its count, in a per-image hash table filled by
 //             one walk, and from it every label's partner of largest IoU / largest intersection (integer maxima under a total order)
+//   hausdorff the same two images and overlap's partners: the squared Hausdorff distance of every object to its partner, one
+//             workgroup per pair, the target's horizontal runs staged in LDS and every pixel of the source held against them
 //   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
 //             component without a seed is numbered after the seeds:
 //               seeds   one thread per point hangs the live seeds on a chain at their component's root
@@ -631,6 +633,310 @@ __global__ __launch_bounds__(256) void overlap_finish_kernel(int N, Overlap t) {
     }
 }
 
+// ---- label image against label image: squared Hausdorff distance of every object to its partner ----------------------------------
+// d2(A -> B) = max over ALL pixels a of A of min over the pixels b of B of dr^2 + dc^2; H2 = max of the two directions.  A job is a
+// pair (object, partner or candidate) and one workgroup computes both of its directions.  For A -> B the workgroup walks B's
+// bounding box and stages B's horizontal runs (row, first column, last column) in LDS, kHausStage at a time; the threads share out
+// the pixels of A's bounding box, kHausPix each at a time, and every pixel of A takes the minimum over the staged runs of
+// dr^2 + max(c0 - c, 0, c - c1)^2 -- all lanes read the same run, an LDS broadcast.  A target with more runs than the stage is
+// staged in chunks, the minima staying in registers; a source with more pixels than one turn takes the target again per turn
+// (not when the target fits the stage: it then stays).  An object without a partner is held against every object of the other side
+// whose box does not rule it out.  Rows are numbered truth first: row = n cap_truth + g - 1, then
+// N cap_truth + n cap_pred + p - 1.  An object is a label whose bounding box the walk of THIS call filled, so every box read lies
+// inside the image whatever the partner tables hold.
+constexpr int kHausStage = 2048;       // runs per stage: 16 KiB of LDS
+constexpr int kHausPix = 4;            // pixels of the source per thread and turn
+
+struct Haus {
+    const int32_t *pred, *truth;
+    const int32_t *given_truth, *given_pred;   // [N][cap_truth], [N][cap_pred]: the best-intersection partner, 0 = none
+    int32_t *partner_truth, *d2_truth;         // [N][cap_truth]
+    int32_t *partner_pred, *d2_pred;           // [N][cap_pred]
+    int32_t *box_truth, *box_pred;             // [N][cap][4] = r0, c0, r1, c1 (half-open); r1 = 0: no object
+    unsigned long long* best;                  // [rows]  (H2 << 32) | candidate label, all ones = none
+    int32_t* list;                             // [rows]  the rows of the objects without a given partner, in no particular order
+    int32_t* bound;                            // [rows]  of a listed row: an upper bound of its smallest H2, from the boxes alone
+    int32_t* n_list;                           // [1]
+    int N, H, W, cap_pred, cap_truth;
+};
+
+struct HausSide {                              // one side of a job: the image, the label and its box
+    const int32_t* img;
+    int label, r0, c0, r1, c1;
+};
+
+__global__ __launch_bounds__(256) void hausdorff_init_kernel(Haus t) {
+    const long long nt = (long long)t.N * t.cap_truth, np = (long long)t.N * t.cap_pred;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nt + np; i += (long long)gridDim.x * 256) {
+        int32_t* box = i < nt ? t.box_truth + 4 * i : t.box_pred + 4 * (i - nt);
+        box[0] = INT_MAX;
+        box[1] = INT_MAX;
+        box[2] = 0;
+        box[3] = 0;
+        t.best[i] = ~0ull;
+        t.bound[i] = INT_MAX;
+        if (i == 0) *t.n_list = 0;
+    }
+}
+
+// the bounding box of every label of both images (labels above the side's capacity are background)
+__global__ __launch_bounds__(256) void hausdorff_box_kernel(Haus t) {
+    const PairSides s{nullptr, nullptr, nullptr, nullptr, t.cap_pred, t.cap_truth};
+    walk_row_segments(t.N, t.H, t.W, [&](int n, int r, int c, long long px) {
+        const PairRun u = pair_run<false>(t.pred, t.truth, s, n, t.W, c, px);
+        if (!u.head) return;
+        if (u.g) {
+            int32_t* box = t.box_truth + 4 * ((long long)n * t.cap_truth + u.g - 1);
+            lower_to(box, r);
+            lower_to(box + 1, c);
+            raise_to(box + 2, r + 1);
+            raise_to(box + 3, c + u.len);
+        }
+        if (u.p) {
+            int32_t* box = t.box_pred + 4 * ((long long)n * t.cap_pred + u.p - 1);
+            lower_to(box, r);
+            lower_to(box + 1, c);
+            raise_to(box + 2, r + 1);
+            raise_to(box + 3, c + u.len);
+        }
+    });
+}
+
+struct HausLds {
+    int2 run[kHausStage];              // (row, first column | last column << 16): columns are below 2^16 where d2 fits int32
+    int heads[2][4];                   // the runs each wave found in a staging turn, double-buffered over the turns
+    int red[4];
+};
+
+// side `label` of image n: 0 = truth, 1 = pred.  Called with block-uniform arguments.
+__device__ __forceinline__ HausSide haus_side(const Haus& t, int side, int n, int label) {
+    const int cap = side ? t.cap_pred : t.cap_truth;
+    const int32_t* box = (side ? t.box_pred : t.box_truth) + 4 * ((long long)n * cap + label - 1);
+    return HausSide{(side ? t.pred : t.truth) + (long long)n * t.H * t.W, label, box[0], box[1], box[2], box[3]};
+}
+
+// The runs of b from item `it` of its box on (an item = 64 columns of one row of the box, one wave each, four per turn) into the
+// stage, for as long as another turn is sure to fit (a wave finds at most 32 runs).  Returns the runs staged; `it` moves to the
+// first item not taken.  Every thread of the workgroup calls it with the same arguments; it ends with a barrier.
+__device__ __forceinline__ int haus_stage(const HausSide& b, int W, int& it, int items, int segs, HausLds& lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int count = 0, turn = 0;
+    __syncthreads();                                                   // nobody still reads the stage
+    for (; it < items && count + 4 * 32 <= kHausStage; it += 4, turn ^= 1) {
+        const int item = it + wave;
+        int row = 0, c = 0, len = 1;
+        bool head = false;
+        if (item < items) {
+            row = b.r0 + item / segs;
+            c = b.c0 + (item % segs) * 64 + lane;
+            const bool live = c < b.c1 && b.img[(long long)row * W + c] == b.label;
+            const unsigned long long bal = __ballot(live);
+            head = bal && run_of(bal, 0ull, lane, len) && live;
+        }
+        const unsigned long long hb = __ballot(head);
+        if (lane == 0) lds.heads[turn][wave] = __popcll(hb);
+        __syncthreads();
+        int at = count;
+        for (int w = 0; w < 4; ++w) {
+            const int k = lds.heads[turn][w];
+            if (w < wave) at += k;
+            count += k;
+        }
+        if (head) lds.run[at + __popcll(hb & ((1ull << lane) - 1))] = make_int2(row, (int)((unsigned)c | ((unsigned)(c + len - 1) << 16)));
+    }
+    __syncthreads();
+    return count;
+}
+
+// d2(a -> b), the same value in every thread.  Every thread of the workgroup calls it with the same arguments.
+__device__ int haus_directed(const HausSide& a, const HausSide& b, int W, HausLds& lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned aw = (unsigned)(a.c1 - a.c0), apix = aw * (unsigned)(a.r1 - a.r0);   // <= H W < 2^31: base below stays in 32 bits
+    const int segs = (b.c1 - b.c0 + 63) >> 6, items = segs * (b.r1 - b.r0);
+    int worst = 0, count = 0;
+    bool whole = false;                                                // the stage holds all of b
+    for (unsigned base = 0; base < apix; base += 256 * kHausPix) {
+        int pr[kHausPix], pc[kHausPix], m[kHausPix];
+        bool mine = false;
+#pragma unroll
+        for (int k = 0; k < kHausPix; ++k) {
+            const unsigned idx = base + k * 256 + threadIdx.x;
+            const bool in = idx < apix;
+            pr[k] = a.r0 + (in ? (int)(idx / aw) : 0);
+            pc[k] = a.c0 + (in ? (int)(idx % aw) : 0);
+            const bool own = in && a.img[(long long)pr[k] * W + pc[k]] == a.label;
+            m[k] = own ? INT_MAX : 0;                                  // a pixel that is not a's stays at 0: no part of the maximum
+            mine |= own;
+        }
+        if (!__syncthreads_or(mine)) continue;
+        const bool wave_mine = __ballot(mine) != 0;
+        int it = 0;
+        do {
+            if (!whole) {
+                const bool first = it == 0;
+                count = haus_stage(b, W, it, items, segs, lds);
+                whole = first && it >= items;
+            }
+            if (wave_mine) {
+                for (int j = 0; j < count; ++j) {
+                    const int2 u = lds.run[j];
+                    const int c0 = u.y & 0xFFFF, c1 = (int)((unsigned)u.y >> 16);
+#pragma unroll
+                    for (int k = 0; k < kHausPix; ++k) {
+                        const int dr = pr[k] - u.x, dc = max(max(c0 - pc[k], pc[k] - c1), 0);
+                        m[k] = min(m[k], dr * dr + dc * dc);
+                    }
+                }
+            }
+        } while (!whole && it < items);
+#pragma unroll
+        for (int k = 0; k < kHausPix; ++k) worst = max(worst, m[k]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) worst = max(worst, __shfl_xor(worst, off));
+    __syncthreads();                                                   // nobody still reads red from the call before
+    if (lane == 0) lds.red[wave] = worst;
+    __syncthreads();
+    return max(max(lds.red[0], lds.red[1]), max(lds.red[2], lds.red[3]));
+}
+
+__device__ __forceinline__ int haus_h2(const HausSide& a, const HausSide& b, int W, HausLds& lds) {
+    const int ab = haus_directed(a, b, W, lds);
+    return max(ab, haus_directed(b, a, W, lds));
+}
+
+// row -> side (0 = truth, 1 = pred), image and label
+__device__ __forceinline__ void haus_row(const Haus& t, long long row, int& side, int& n, int& label) {
+    const long long nt = (long long)t.N * t.cap_truth;
+    side = row >= nt;
+    const long long i = side ? row - nt : row;
+    const int cap = side ? t.cap_pred : t.cap_truth;
+    n = (int)(i / cap);
+    label = (int)(i - (long long)n * cap) + 1;
+}
+
+// One workgroup per row at a time.  No object: (0, -1).  An object whose given partner is an object of the other side: H2 with
+// it.  Any other object goes on the list and gets (0, -1) for the time being.
+__global__ __launch_bounds__(256) void hausdorff_partner_kernel(Haus t) {
+    __shared__ HausLds lds;
+    const long long rows = (long long)t.N * (t.cap_truth + t.cap_pred);
+    for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        int side, n, label;
+        haus_row(t, row, side, n, label);
+        const long long nt = (long long)t.N * t.cap_truth;
+        int32_t* partner = side ? t.partner_pred + (row - nt) : t.partner_truth + row;
+        int32_t* d2 = side ? t.d2_pred + (row - nt) : t.d2_truth + row;
+        const HausSide a = haus_side(t, side, n, label);
+        int with = 0, dist = -1;
+        if (a.r1 > 0) {
+            const int given = side ? t.given_pred[row - nt] : t.given_truth[row];
+            const int cap_other = side ? t.cap_truth : t.cap_pred;
+            HausSide b{};
+            if (given >= 1 && given <= cap_other) b = haus_side(t, side ^ 1, n, given);
+            if (b.r1 > 0) {
+                with = given;
+                dist = haus_h2(a, b, t.W, lds);
+            } else if (threadIdx.x == 0) {
+                t.list[__hip_atomic_fetch_add(t.n_list, 1, __ATOMIC_RELAXED, kGlobal)] = (int)row;
+            }
+        }
+        if (threadIdx.x == 0) {
+            *partner = with;
+            *d2 = dist;
+        }
+    }
+}
+
+// What the boxes alone say about H2(A, B).  Below: the topmost pixel of whichever object starts higher is at least the difference of
+// the two top rows away from every pixel of the other, and likewise at the other three edges.  Above: no two pixels of the two
+// objects are farther apart than the corners of the box that holds both.
+__device__ __forceinline__ int haus_box_below(const int32_t* a, const int32_t* b) {
+    const int dr = max(abs(a[0] - b[0]), abs(a[2] - b[2])), dc = max(abs(a[1] - b[1]), abs(a[3] - b[3]));
+    return max(dr * dr, dc * dc);
+}
+__device__ __forceinline__ int haus_box_above(const int32_t* a, const int32_t* b) {
+    const int dr = max(a[2], b[2]) - 1 - min(a[0], b[0]), dc = max(a[3], b[3]) - 1 - min(a[1], b[1]);
+    return dr * dr + dc * dc;                                          // <= (H - 1)^2 + (W - 1)^2
+}
+
+// the box of label `cand` of the side opposite to row's, or NULL where that is no object
+__device__ __forceinline__ const int32_t* haus_candidate_box(const Haus& t, int side, int n, int cand) {
+    const int cap = side ? t.cap_truth : t.cap_pred;
+    if (cand > cap) return nullptr;
+    const int32_t* box = (side ? t.box_truth : t.box_pred) + 4 * ((long long)n * cap + cand - 1);
+    return box[2] > 0 ? box : nullptr;
+}
+
+// One wave per (listed row, 64 labels of the other side) at a time: the smallest upper bound among the candidates into the row's
+// bound.  The candidate that attains it has an H2 no larger, so the row's smallest H2 is no larger either.
+__global__ __launch_bounds__(256) void hausdorff_bound_kernel(Haus t) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cap_most = max(t.cap_pred, t.cap_truth), chunks = (cap_most + 63) >> 6;
+    const long long jobs = (long long)*t.n_list * chunks;
+    for (long long job = (long long)blockIdx.x * 4 + wave; job < jobs; job += (long long)gridDim.x * 4) {
+        const long long row = t.list[job / chunks];
+        int side, n, label;
+        haus_row(t, row, side, n, label);
+        const int32_t* a = (side ? t.box_pred : t.box_truth) + 4 * ((long long)n * (side ? t.cap_pred : t.cap_truth) + label - 1);
+        const int32_t* b = haus_candidate_box(t, side, n, (int)(job % chunks) * 64 + lane + 1);
+        int above = b ? haus_box_above(a, b) : INT_MAX;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) above = min(above, __shfl_xor(above, off));
+        if (lane == 0 && above != INT_MAX) lower_to(t.bound + row, above);
+    }
+}
+
+// One workgroup per (listed row, 256 labels of the other side) at a time.  Every thread holds one label against the row's object
+// by their boxes: an object whose lower bound exceeds the row's bound, or the H2 of a candidate already done, cannot be the
+// nearest nor tie with it, and is left out -- which candidates that spares depends on the order the jobs end in, the minimum does
+// not.  The workgroup then takes the candidates that are left one by one: the H2 goes into the row's minimum of (H2 << 32) | label,
+// the smallest distance and among equals the lowest label, in whatever order the jobs end.
+__global__ __launch_bounds__(256) void hausdorff_candidate_kernel(Haus t) {
+    __shared__ HausLds lds;
+    __shared__ int left[256];
+    __shared__ int wsum[4];
+    const int cap_most = max(t.cap_pred, t.cap_truth), chunks = (cap_most + 255) >> 8;
+    const long long jobs = (long long)*t.n_list * chunks;
+    for (long long job = blockIdx.x; job < jobs; job += gridDim.x) {
+        const long long row = t.list[job / chunks];
+        const int cand = (int)(job % chunks) * 256 + (int)threadIdx.x + 1;
+        int side, n, label;
+        haus_row(t, row, side, n, label);
+        const int32_t* mine = (side ? t.box_pred : t.box_truth) + 4 * ((long long)n * (side ? t.cap_pred : t.cap_truth) + label - 1);
+        const int32_t* b = haus_candidate_box(t, side, n, cand);
+        bool keep = false;
+        if (b) {
+            const unsigned done = (unsigned)(__hip_atomic_load(t.best + row, __ATOMIC_RELAXED, kGlobal) >> 32);   // none: all ones
+            keep = (unsigned)haus_box_below(mine, b) <= min((unsigned)t.bound[row], done);
+        }
+        int n_left;
+        const int at = block_rank<256>(keep, wsum, n_left);
+        if (keep) left[at] = cand;
+        __syncthreads();
+        const HausSide a = haus_side(t, side, n, label);
+        for (int i = 0; i < n_left; ++i) {
+            const int c = left[i];
+            const int dist = haus_h2(a, haus_side(t, side ^ 1, n, c), t.W, lds);
+            if (threadIdx.x == 0)
+                __hip_atomic_fetch_min(t.best + row, ((unsigned long long)(unsigned)dist << 32) | (unsigned)c, __ATOMIC_RELAXED, kGlobal);
+        }
+        __syncthreads();                                               // nobody still reads `left`
+    }
+}
+
+// One thread per listed row: the winner into the tables (a row without a candidate keeps (0, -1)).
+__global__ __launch_bounds__(256) void hausdorff_finish_kernel(Haus t) {
+    const long long nt = (long long)t.N * t.cap_truth;
+    const int listed = *t.n_list;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < listed; i += (long long)gridDim.x * 256) {
+        const long long row = t.list[i];
+        const unsigned long long b = t.best[row];
+        if (b == ~0ull) continue;
+        (row >= nt ? t.partner_pred + (row - nt) : t.partner_truth + row)[0] = (int)(unsigned)b;
+        (row >= nt ? t.d2_pred + (row - nt) : t.d2_truth + row)[0] = (int)(b >> 32);
+    }
+}
+
 // ---- seeded split ------------------------------------------------------------------------------------------------------------------
 // One thread per point. A point is a live seed when it is one of the first S'_n of its image, lies inside the image and on a
 // foreground pixel.  A live seed is pushed on the chain of its component: the root's slot of `head` (the spent cnt array) holds the
@@ -808,6 +1114,24 @@ size_t overlap_layout(void* w, int N, int max_pairs, Overlap* t) {
     t->best_iou = c.take<unsigned long long>(nt);
     t->best_it = c.take<unsigned long long>(nt);
     t->best_ip = c.take<unsigned long long>((size_t)N * t->s.cap_pred);
+    return c.end;
+}
+
+bool hausdorff_sizes_ok(int N, int H, int W, int cap_pred, int cap_truth) {
+    return sizes_ok(N, H, W) && cap_pred >= 1 && cap_truth >= 1 && (long long)N * ((long long)cap_pred + cap_truth) < (1LL << 31) &&
+           (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1) < (1LL << 31);
+}
+// box_truth (int32 4 N cap_truth), box_pred (int32 4 N cap_pred), best (uint64 rows), list, bound (int32 rows each), n_list
+// (int32 1), rows = N (cap_truth + cap_pred), for the capacities of t: 32 bytes per row and padding
+size_t hausdorff_layout(void* w, Haus* t) {
+    const size_t rows = (size_t)t->N * ((size_t)t->cap_truth + t->cap_pred);
+    Carve c{reinterpret_cast<uintptr_t>(w)};
+    t->box_truth = c.take<int32_t>(4 * (size_t)t->N * t->cap_truth);
+    t->box_pred = c.take<int32_t>(4 * (size_t)t->N * t->cap_pred);
+    t->best = c.take<unsigned long long>(rows);
+    t->list = c.take<int32_t>(rows);
+    t->bound = c.take<int32_t>(rows);
+    t->n_list = c.take<int32_t>(1);
     return c.end;
 }
 
@@ -1017,6 +1341,47 @@ extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* tru
     hipLaunchKernelGGL(overlap_reduce_kernel, dim3(grid_for(ns)), dim3(256), 0, st, ns, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(overlap_finish_kernel, dim3(grid_for(labels)), dim3(256), 0, st, N, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_hausdorff_stage_runs(void) { return kHausStage; }
+
+extern "C" size_t cs_regions_hausdorff_workspace(int N, int cap_pred, int cap_truth) {
+    Haus t{};
+    t.N = N, t.cap_pred = cap_pred, t.cap_truth = cap_truth;
+    return hausdorff_sizes_ok(N, 1, 1, cap_pred, cap_truth) ? hausdorff_layout(nullptr, &t) : 0;
+}
+
+extern "C" int cs_regions_hausdorff_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                                           const int32_t* inter_partner_truth, const int32_t* inter_partner_pred, int32_t* partner_truth,
+                                           int32_t* d2_truth, int32_t* partner_pred, int32_t* d2_pred, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    Haus t{pred, truth, inter_partner_truth, inter_partner_pred, partner_truth, d2_truth, partner_pred, d2_pred};
+    t.N = N, t.H = H, t.W = W, t.cap_pred = cap_pred, t.cap_truth = cap_truth;
+    const bool ok = sizes_ok(N, H, W) && hausdorff_sizes_ok(N, H, W, cap_pred, cap_truth);
+    const int rc = check_label_pair("regions_hausdorff_labels",
+                                    pred && truth && inter_partner_truth && inter_partner_pred && partner_truth && d2_truth &&
+                                        partner_pred && d2_pred && workspace,
+                                    N, H, W, ok ? hausdorff_layout(workspace, &t) : 0,
+                                    "need capacities >= 1, N (cap_pred + cap_truth) < 2^31 and (H - 1)^2 + (W - 1)^2 < 2^31", workspace,
+                                    workspace_bytes);
+    if (rc != CS_OK) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long rows = (long long)N * ((long long)cap_pred + cap_truth);
+    const int cap_most = cap_pred > cap_truth ? cap_pred : cap_truth;
+    const long long by64 = rows * ((cap_most + 63) / 64), by256 = rows * ((cap_most + 255) / 256);
+    hipLaunchKernelGGL(hausdorff_init_kernel, dim3(grid_for(rows)), dim3(256), 0, st, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hausdorff_box_kernel, walk_grid(N, H, W), dim3(256), 0, st, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hausdorff_partner_kernel, dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, st, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hausdorff_bound_kernel, dim3(grid_for(by64 * 64)), dim3(256), 0, st, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hausdorff_candidate_kernel, dim3((unsigned)(by256 < 4096 ? by256 : 4096)), dim3(256), 0, st, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hausdorff_finish_kernel, dim3(grid_for(rows)), dim3(256), 0, st, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -398,7 +398,8 @@ def _columns(cols, **means):
 
 
 def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, eps=11, reg_limit=False, method="gaussianblur",
-                       thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, overlap=False, **blur):
+                       thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, overlap=False, hausdorff=False,
+                       **blur):
     """The instance-level sibling of ``evaluate_detection``: every image's cells -- the cleaned segmentation split at the detected
     points -- against ground-truth instances, matched by IoU on the device (``regions.match_labels``).  The loader yields ``(images,
     masks, ...)``: masks uint8 0 / 255 [n, H, W], whose connected components (``regions.label(masks != 0, connectivity)``) are the
@@ -408,7 +409,12 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     ``MatchTable.score(iou_threshold)``.  Returns a dict of numpy arrays ``n_pred, n_truth, tp, fp, fn, p, r, f1, sq, pq`` (one
     entry per image) and ``mean`` = the averages (p, r, f1, sq, pq).  ``overlap=True`` also runs ``regions.overlap_labels`` on the
     same label pair and adds the columns ``aji`` and ``dice_obj`` (``score.overlap_score``) and ``mean_overlap`` = their averages
-    (aji, dice_obj); without it nothing more is launched and the keys are the ones above.  The model is left in segment mode."""
+    (aji, dice_obj); without it nothing more is launched and the keys are the ones above.  ``hausdorff=True`` also runs
+    ``regions.hausdorff_labels`` on the same label pair -- on the overlap tables of ``overlap=True`` where both are asked for, which
+    are then made once -- and adds the column ``hausdorff_obj`` (``score.hausdorff_score``; ``inf`` for an image with objects on
+    one side only), ``mean_hausdorff`` = its average over the images where it is finite (0.0 without one) and
+    ``hausdorff_undefined`` = the number of the others; without it nothing more is launched either.  The model is left in segment
+    mode."""
     from . import detect as D
     from . import regions as Rg
     from . import score as S
@@ -423,6 +429,8 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     cols = {k: [] for k in names}
     if overlap:
         cols.update(aji=[], dice_obj=[])
+    if hausdorff:
+        cols.update(hausdorff_obj=[])
     with torch.no_grad():
         for batch in tqdm(loader, desc="testing"):
             images, masks = batch[0], batch[1]
@@ -436,8 +444,17 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
             sc = Rg.match_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score(iou_threshold)
             for k, field in names.items():
                 cols[k].append(getattr(sc, field))
+            if overlap or hausdorff:
+                table = Rg.overlap_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts)
             if overlap:
-                ov = Rg.overlap_labels(parts.labels, truth.reshape(classes.shape), pred_counts=parts.counts).score()
+                ov = table.score()
                 cols["aji"].append(ov.aji)
                 cols["dice_obj"].append(ov.dice_obj)
-    return _columns(cols, mean=("p", "r", "f1", "sq", "pq"), **({"mean_overlap": ("aji", "dice_obj")} if overlap else {}))
+            if hausdorff:
+                cols["hausdorff_obj"].append(Rg.hausdorff_labels(parts.labels, truth.reshape(classes.shape), overlap=table).score().hausdorff_obj)
+    out = _columns(cols, mean=("p", "r", "f1", "sq", "pq"), **({"mean_overlap": ("aji", "dice_obj")} if overlap else {}))
+    if hausdorff:
+        finite = out["hausdorff_obj"][np.isfinite(out["hausdorff_obj"])]
+        out["mean_hausdorff"] = float(finite.mean()) if len(finite) else 0.0
+        out["hausdorff_undefined"] = int(len(out["hausdorff_obj"]) - len(finite))
+    return out

@@ -1390,6 +1390,42 @@ def regions_overlap_labels(pred, truth, cap_pred, cap_truth, max_pairs, counts_p
     return t
 
 
+def regions_hausdorff_stage_runs():
+    """the horizontal runs of an object that one stage of cs_regions_hausdorff_labels holds; an object with more is taken in chunks"""
+    return int(_lib.load().cs_regions_hausdorff_stage_runs())
+
+
+def regions_hausdorff_workspace(N, cap_pred, cap_truth, device):
+    """the caller-owned scratch of one cs_regions_hausdorff_labels call on N images with these capacities"""
+    why = ("regions_hausdorff_labels: a call takes 0 < N <= 65535 images and capacities >= 1 with N (cap_pred + cap_truth) < 2^31, "
+           f"got {(N, cap_pred, cap_truth)}")
+    return _workspace(_lib.load().cs_regions_hausdorff_workspace, device, why, int(N), int(cap_pred), int(cap_truth))
+
+
+def regions_hausdorff_labels(pred, truth, cap_pred, cap_truth, inter_partner_truth, inter_partner_pred, partner_truth=None, d2_truth=None,
+                             partner_pred=None, d2_pred=None, ws=None):
+    """int32 label images pred, truth [N,H,W] and the best-intersection partners of regions_overlap_labels for the same pair
+    (inter_partner_truth int32 [N,cap_truth], inter_partner_pred int32 [N,cap_pred]) -> a dict of int32 tensors: partner_truth,
+    d2_truth [N,cap_truth], partner_pred, d2_pred [N,cap_pred] (cs_regions_hausdorff_labels in include/cellseg_hip.h)."""
+    N, H, W, _ = _label_pair_args("regions_hausdorff_labels", pred, truth, (False, False))
+    cp, ct = int(cap_pred), int(cap_truth)
+    if (H - 1) ** 2 + (W - 1) ** 2 >= 1 << 31:
+        raise ValueError(f"regions_hausdorff_labels: squared distances in a {H}x{W} image do not fit int32")
+    for x, cap, name in ((inter_partner_truth, ct, "inter_partner_truth"), (inter_partner_pred, cp, "inter_partner_pred")):
+        if x.dtype != torch.int32 or tuple(x.shape) != (N, cap):
+            raise TypeError(f"regions_hausdorff_labels: {name} must be torch.int32 of shape {(N, cap)}, got {x.dtype} {tuple(x.shape)}")
+    want = {"partner_truth": ((N, ct), torch.int32), "d2_truth": ((N, ct), torch.int32), "partner_pred": ((N, cp), torch.int32),
+            "d2_pred": ((N, cp), torch.int32)}
+    if ws is None:
+        ws = regions_hausdorff_workspace(N, cp, ct, pred.device)
+    t = _regions_outputs("regions_hausdorff_labels", want, {"partner_truth": partner_truth, "d2_truth": d2_truth,
+                                                            "partner_pred": partner_pred, "d2_pred": d2_pred}, pred.device)
+    _lib.check(_lib.load().cs_regions_hausdorff_labels(
+        _p(pred), _p(truth), N, H, W, cp, ct, _p(inter_partner_truth), _p(inter_partner_pred), _p(t["partner_truth"]), _p(t["d2_truth"]),
+        _p(t["partner_pred"]), _p(t["d2_pred"]), _p(ws), ws.numel(), _stream()), "regions_hausdorff_labels")
+    return t
+
+
 def regions_areas(mask, connectivity=1, out=None, ws=None):
     """uint8 [N,H,W] -> int32 [N,H,W]: the area of the component of equal-valued pixels under every pixel"""
     N, H, W, ws = _regions_args(mask, ws)

@@ -35,6 +35,11 @@ integers (``MatchTable``; the rule is in ``match_labels``'s docstring, restated 
 ``overlap_labels`` lists every (pred, truth) pair of labels that shares a pixel, with the count, and gives every label its best
 partner by IoU and by intersection, however small the overlap (``OverlapTable``; restated in numpy by tests/overlap_ref.py), from
 which ``OverlapTable.score`` forms AJI and object-level Dice on the host (``score.overlap_score``).
+
+``hausdorff_labels`` holds every object against its partner on the other side -- ``overlap_labels``' best-intersection partner, or
+the nearest object where it overlaps nothing -- by the squared Hausdorff distance of the two pixel sets, in exact integers
+(``HausdorffTable``; restated in numpy by tests/hausdorff_ref.py), from which ``HausdorffTable.score`` forms the object-level
+Hausdorff distance on the host (``score.hausdorff_score``).
 """
 import dataclasses
 import typing
@@ -635,3 +640,103 @@ def overlap_labels(pred, truth, max_regions=None, max_pairs=None, pred_counts=No
         if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
             return table
         pairs = min(2 * pairs, most)
+
+
+_HAUSDORFF_HOST = ("area_pred", "area_truth", "d2_truth", "d2_pred")
+
+
+@dataclasses.dataclass
+class HausdorffTable:
+    """``hausdorff_labels`` of N image pairs as device int32 tensors.  ``counts_pred`` / ``counts_truth`` [N], the capacities and
+    ``area_pred`` [N, cap_pred] / ``area_truth`` [N, cap_truth] are those of the ``OverlapTable`` it was made from, ``dropped`` [N]
+    too.  Row g - 1 of ``partner_truth`` / ``d2_truth`` [N, cap_truth]: the pred label that truth label g is held against and the
+    squared Hausdorff distance H2 between the two; row p - 1 of ``partner_pred`` / ``d2_pred`` [N, cap_pred]: the same for pred label
+    p over the truth labels.  ``partner = 0`` and ``d2 = -1`` where the row is no object or the other side has none."""
+    counts_pred: torch.Tensor
+    counts_truth: torch.Tensor
+    cap_pred: int
+    cap_truth: int
+    area_pred: torch.Tensor
+    area_truth: torch.Tensor
+    dropped: torch.Tensor
+    partner_truth: torch.Tensor
+    d2_truth: torch.Tensor
+    partner_pred: torch.Tensor
+    d2_pred: torch.Tensor
+    _host: typing.Optional[tuple] = dataclasses.field(default=None, repr=False, compare=False)
+
+    def overflowed(self):
+        """device bool [N]: as ``OverlapTable.overflowed`` -- a side of the image has labels above its capacity (they were taken
+        for background), or pairs of it found no room in the overlap table (an object may then have missed its partner)"""
+        return (self.counts_pred > self.cap_pred) | (self.counts_truth > self.cap_truth) | (self.dropped > 0)
+
+    def score(self):
+        """Object-level Hausdorff distance per image -> ``score.HausdorffScore`` (``score.hausdorff_score`` has the formulas).  It
+        synchronises: the integer tables are copied to the host once and kept."""
+        from . import score as S
+        if self._host is None:
+            self._host = tuple(_host_int(getattr(self, k)) for k in _HAUSDORFF_HOST)
+        return S.hausdorff_score(*self._host)
+
+
+def _check_hausdorff_shape(shape):
+    """squared distances are int32: (H - 1)^2 + (W - 1)^2 has to fit"""
+    H, W = int(shape[-2]), int(shape[-1])
+    if (H - 1) ** 2 + (W - 1) ** 2 > (1 << 31) - 1:
+        raise ValueError(f"hausdorff_labels: squared distances in a {H}x{W} image do not fit int32: need (H - 1)^2 + (W - 1)^2 < 2^31")
+
+
+def hausdorff_labels(pred, truth, overlap=None, max_regions=None, max_pairs=None, pred_counts=None, truth_counts=None):
+    """The squared Hausdorff distance of every object of two label images to its partner on the other side -> ``HausdorffTable``:
+    what the object-level Hausdorff distance of the GlaS challenge needs (``HausdorffTable.score``).
+
+    ``pred``, ``truth``, ``max_regions``, ``max_pairs``, ``pred_counts`` / ``truth_counts``, the objects (labels that own a pixel)
+    and the background (0 and below, and labels above their side's capacity) are those of ``overlap_labels``.  ``overlap``: the
+    ``OverlapTable`` of the same pair where the caller has it (``max_regions``, if given as well, has to agree with it); None runs
+    ``overlap_labels`` with the arguments given here.  Per image, for pixel sets A and B:
+
+    * ``d2(A -> B)`` = the maximum over ALL pixels a of A -- not its boundary: the farthest pixel may lie inside -- of the minimum
+      over the pixels b of B of ``dr^2 + dc^2``, and ``H2(A, B) = max(d2(A -> B), d2(B -> A))``, exact integers.
+    * The partner of an object is its best-intersection partner of ``overlap_labels`` (``inter_partner_truth`` /
+      ``inter_partner_pred``, ties to the lower label) where it has one.  An object that overlaps nothing takes the object of the
+      other side of smallest H2, ties to the lower label (the rule of the GlaS evaluation); 0 when the other side has no object.
+
+    Needs ``(H - 1)^2 + (W - 1)^2 < 2^31`` (``ValueError`` before any launch).  With ``max_regions`` and ``max_pairs`` (or an
+    ``OverlapTable``) given, six launches whose grids depend on the shape and the capacities alone follow the overlap's, nothing
+    synchronises and the call can be captured into a graph; everything written is integer and independent of launch and arrival
+    order.  Cost: one workgroup per (object, partner) computes both directions, each about ``|bounding box of A| runs(B)``
+    distance evaluations, runs(B) = the horizontal runs of B's pixels, staged in LDS a fixed number at a time
+    (``kernels.regions_hausdorff_stage_runs()``; an object with more is handled in chunks); an object that overlaps nothing costs
+    one bounding-box test per object of the other side and one such job per object that the boxes do not rule out (at worst every
+    one of them).  Measured once, on synthetic blobs: DESIGN.md.  Memory besides the tables: 32 bytes per label of either side --
+    never a cap_pred x cap_truth table."""
+    caps = _match_capacities(max_regions)
+    _check_max_pairs(max_pairs)
+    if overlap is not None:
+        if not isinstance(overlap, OverlapTable):
+            raise TypeError(f"hausdorff_labels: overlap must be an OverlapTable or None, got {type(overlap).__name__}")
+        if caps is not None and caps != (overlap.cap_pred, overlap.cap_truth):
+            raise ValueError(f"hausdorff_labels: max_regions {caps} against an OverlapTable of capacities "
+                             f"{(overlap.cap_pred, overlap.cap_truth)}")
+    for x in (pred, truth):
+        if len(getattr(x, "shape", ())) in (2, 3):
+            _check_hausdorff_shape(x.shape)                              # before anything is copied anywhere
+    pair = _LabelPair("hausdorff_labels", pred, truth, pred_counts, truth_counts)
+    N, dev = pair.N, pair.dev
+    if overlap is None:
+        overlap = overlap_labels(pair.pred, pair.truth, max_regions=max_regions, max_pairs=max_pairs,
+                                 pred_counts=None if pair.own[0] else pair.counts[0], truth_counts=None if pair.own[1] else pair.counts[1])
+    elif overlap.area_pred.shape[0] != N or overlap.area_pred.device != dev:
+        raise ValueError(f"hausdorff_labels: an OverlapTable of {overlap.area_pred.shape[0]} images on {overlap.area_pred.device} for "
+                         f"{N} images on {dev}")
+    cap_p, cap_t = overlap.cap_pred, overlap.cap_truth
+    tabs = {k: torch.empty((N, cap), dtype=torch.int32, device=dev)
+            for k, cap in (("partner_truth", cap_t), ("d2_truth", cap_t), ("partner_pred", cap_p), ("d2_pred", cap_p))}
+    ws, ws_n = None, 0
+    for at, p, t, _, _ in pair.calls((False, False)):
+        if ws_n != len(p):
+            ws, ws_n = K.regions_hausdorff_workspace(len(p), cap_p, cap_t, dev), len(p)
+        K.regions_hausdorff_labels(p, t, cap_p, cap_t, overlap.inter_partner_truth[at], overlap.inter_partner_pred[at],
+                                   **{k: x[at] for k, x in tabs.items()}, ws=ws)
+    return HausdorffTable(overlap.counts_pred, overlap.counts_truth, cap_p, cap_t, overlap.area_pred, overlap.area_truth, overlap.dropped,
+                          tabs["partner_truth"], tabs["d2_truth"], tabs["partner_pred"], tabs["d2_pred"])

@@ -327,3 +327,43 @@ def overlap_score(area_pred, area_truth, iou_partner, iou_inter, inter_partner_t
         out.aji[n] = np.float64(C) / np.float64(U) if U else 1.0
         out.dice_obj[n] = 0.5 * (sides[0] + sides[1]) if n_pred or n_truth else 1.0
     return out
+
+
+@dataclass
+class HausdorffScore:
+    """Per image (arrays of length N): ``n_pred``, ``n_truth`` (objects: labels that own a pixel, within the capacity) int64;
+    ``term_truth``, ``term_pred``, ``hausdorff_obj`` float64, in pixels."""
+    n_pred: np.ndarray
+    n_truth: np.ndarray
+    term_truth: np.ndarray
+    term_pred: np.ndarray
+    hausdorff_obj: np.ndarray
+
+
+def hausdorff_score(area_pred, area_truth, d2_truth, d2_pred):
+    """The integer tables of ``regions.hausdorff_labels`` on the host (``area_pred``, ``d2_pred`` [N, cap_pred]; ``area_truth``,
+    ``d2_truth`` [N, cap_truth]) -> ``HausdorffScore``, in numpy float64.  An object is a label whose area is positive; ``d2`` is
+    the squared Hausdorff distance of the object to its partner.  Per image, with Ap / At the areas:
+
+    * ``term_truth = sum_g (At[g] / sum At) * sqrt(d2_truth[g])`` over the truth objects in ascending label, ``term_pred`` the same
+      sum over the pred objects, and ``hausdorff_obj = (term_truth + term_pred) / 2``: the object-level Hausdorff distance of the
+      GlaS challenge, where lower is better.
+    * No object on either side: all three are 0.0.  Exactly one side without objects: the objects of the other have no partner, the
+      score is undefined and ``hausdorff_obj`` and that side's term are ``inf`` (the empty side's term is 0.0) -- a value that cannot
+      be taken for a good one."""
+    ap, at, dt, dp = (np.asarray(x).astype(np.int64) for x in (area_pred, area_truth, d2_truth, d2_pred))
+    if ap.ndim != 2 or at.ndim != 2 or at.shape[0] != ap.shape[0] or dt.shape != at.shape or dp.shape != ap.shape:
+        raise ValueError("hausdorff_score: expected area_pred, d2_pred [N, cap_pred] and area_truth, d2_truth [N, cap_truth]")
+    N = ap.shape[0]
+    out = HausdorffScore(*(np.zeros((N,), np.int64) for _ in range(2)), *(np.zeros((N,), np.float64) for _ in range(3)))
+    for n in range(N):
+        terms = []
+        for own, d2 in ((at[n], dt[n]), (ap[n], dp[n])):
+            total, acc = np.float64(own.sum()), np.float64(0.0)
+            for k in np.nonzero(own)[0]:
+                acc += (np.float64(own[k]) / total) * (np.sqrt(np.float64(d2[k])) if d2[k] >= 0 else np.inf)
+            terms.append(acc)
+        out.n_truth[n], out.n_pred[n] = int((at[n] > 0).sum()), int((ap[n] > 0).sum())
+        out.term_truth[n], out.term_pred[n] = terms
+        out.hausdorff_obj[n] = 0.5 * (terms[0] + terms[1])
+    return out

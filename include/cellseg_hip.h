@@ -693,6 +693,32 @@ int cs_regions_overlap_labels(const int32_t* pred, const int32_t* truth, int N, 
                               int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred, int32_t* inter_pred,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the squared Hausdorff distance of every object of two label images to its partner (csrc/regions.hip) -------------------
+ * pred, truth, the treatment of labels (<= 0 and above the side's capacity = background) and the launch contract are those of
+ * cs_regions_overlap_labels; an object is a label that owns a pixel.  For pixel sets A, B of image n: d2(A -> B) = the maximum over
+ * ALL pixels a of A (not its boundary) of the minimum over the pixels b of B of dr^2 + dc^2; H2(A, B) = max(d2(A -> B), d2(B -> A)).
+ * inter_partner_truth int32 [N][cap_truth] / inter_partner_pred int32 [N][cap_pred] are READ: the tables of that name written by
+ * cs_regions_overlap_labels for the same pair and capacities.  Per truth label g (row g - 1 of [N][cap_truth] int32 tables):
+ *   partner_truth: inter_partner_truth where that is an object of pred; otherwise the pred object of smallest H2(g, p), ties to the
+ *     lower p; 0 where g is no object or pred has none.   d2_truth: H2 with that partner, -1 where partner_truth is 0.
+ * Per pred label p ([N][cap_pred]): partner_pred / d2_pred, the same over the truth labels.  A partner value outside
+ * [1, capacity] or naming a label without a pixel counts as none.  All integer and independent of launch and arrival order.
+ * One workgroup per (object, partner or candidate) computes both directions: for A -> B the horizontal runs of B are staged in
+ * LDS, cs_regions_hausdorff_stage_runs() at a time (an object with more is taken in chunks), and every pixel of A's bounding box
+ * that is A's takes its minimum over them: about |box of A| runs(B) + |box of B| runs(A) distance evaluations per pair.  An
+ * object without a given partner is held against every object of the other side that the bounding boxes do not rule out (the
+ * edges of two boxes bound H2 from below, the box around both from above): one box test per object of the other side and one pair
+ * per object that passes -- which of them a finished pair spares depends on the order of arrival, the result does not.
+ * Need cap_pred, cap_truth >= 1, N (cap_pred + cap_truth) < 2^31 and (H - 1)^2 + (W - 1)^2 < 2^31 (d2 is int32).  workspace:
+ * 16-byte aligned, >= cs_regions_hausdorff_workspace(N, cap_pred, cap_truth) bytes (0 for sizes a call would refuse): 32 bytes per
+ * label of either side and padding, never a cap_pred x cap_truth table.  Six launches whose grids depend on the sizes alone. */
+int cs_regions_hausdorff_stage_runs(void);
+size_t cs_regions_hausdorff_workspace(int N, int cap_pred, int cap_truth);
+int cs_regions_hausdorff_labels(const int32_t* pred, const int32_t* truth, int N, int H, int W, int cap_pred, int cap_truth,
+                                const int32_t* inter_partner_truth, const int32_t* inter_partner_pred, int32_t* partner_truth,
+                                int32_t* d2_truth, int32_t* partner_pred, int32_t* d2_pred, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 /* ---- detected points against annotated points (test_seg.py:120-141 get_prf1, metrics/metrics.py:56-66; csrc/score.hip) ------
  * N images that share nothing, 0 < N <= 65535.  hat int64 [T][2] with hat_off int64 [N + 1] are out_pts / out_off of
  * cs_detect_cluster as they are; gt int32 [G][2] with gt_off int64 [N + 1] are the annotations, in the same coordinate convention.

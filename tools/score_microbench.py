@@ -19,6 +19,16 @@ AJI and object-level Dice) on the same label pairs with the same ``max_regions``
 way right after ``match_labels``; the pair list of two images is checked against a sparse pair count on the host.
 
     python tools/score_microbench.py --labels --overlap [--json PATH]
+
+--labels --overlap --hausdorff also times ``regions.hausdorff_labels`` (the squared Hausdorff distance of every object to its
+partner: the table behind the object-level Hausdorff distance) on the same label pairs WITH that overlap table given, so the time is
+the six launches of its own, next to ``overlap_labels_ms`` from the same run.  It reports the jobs at most (one per object with a
+partner, one per candidate for every other object: the bounding boxes spare most of the latter), the objects without a partner and
+the largest number of horizontal runs of one object
+(``kernels.regions_hausdorff_stage_runs()`` of them are staged at a time).  Up to 200 objects of the first image are checked
+against ``scipy.ndimage.distance_transform_edt`` on the box that holds the object and its partner.
+
+    python tools/score_microbench.py --labels --overlap --hausdorff [--json PATH]
 """
 import argparse
 import json
@@ -72,6 +82,54 @@ def sparse_pairs(pred, truth, cap):
     return keys // (cap + 1), keys % (cap + 1), inter.astype(np.int64)
 
 
+def most_runs(labels):
+    """int label images [N, H, W] -> the largest number of horizontal runs that one label of one image has"""
+    most = 0
+    for lab in labels:
+        starts = (lab > 0) & (lab != np.pad(lab, ((0, 0), (1, 0)))[:, :-1])
+        if starts.any():
+            most = max(most, int(np.bincount(lab[starts]).max()))
+    return most
+
+
+def edt_h2(pred, truth, p, g):
+    """one image pair -> the squared Hausdorff distance of pred label p and truth label g, by distance transforms on the box that
+    holds both"""
+    import scipy.ndimage
+    rows, cols = np.nonzero((pred == p) | (truth == g))
+    box = (slice(rows.min(), rows.max() + 1), slice(cols.min(), cols.max() + 1))
+    a, b = pred[box] == p, truth[box] == g
+    to_b, to_a = scipy.ndimage.distance_transform_edt(~b), scipy.ndimage.distance_transform_edt(~a)
+    return max(int(np.rint(to_b[a].max() ** 2)), int(np.rint(to_a[b].max() ** 2)))
+
+
+def hausdorff_part(G, pred, truth, hp, ht, o, cap, pairs):
+    """the --hausdorff columns of one label pair and whether the checked objects agree with the host"""
+    ms, ts = time_dev(lambda: G.hausdorff_labels(pred, truth, overlap=o), 7)
+    h = G.hausdorff_labels(pred, truth, overlap=o)
+    own = G.hausdorff_labels(pred, truth, max_regions=cap, max_pairs=pairs)
+    ok = all(torch.equal(getattr(h, k), getattr(own, k)) for k in ("partner_truth", "d2_truth", "partner_pred", "d2_pred"))
+    tabs = {k: getattr(h, k).cpu().numpy() for k in ("area_pred", "area_truth", "partner_truth", "d2_truth", "partner_pred", "d2_pred")}
+    given = {"truth": o.inter_partner_truth.cpu().numpy(), "pred": o.inter_partner_pred.cpu().numpy()}
+    jobs = lone = 0
+    for side, other in (("truth", "pred"), ("pred", "truth")):
+        obj = tabs[f"area_{side}"] > 0
+        alone = obj & (given[side] == 0)
+        lone += int(alone.sum())
+        jobs += int((obj & ~alone).sum()) + int((alone.sum(axis=1) * (tabs[f"area_{other}"] > 0).sum(axis=1)).sum())
+        ok &= bool(np.array_equal(tabs[f"partner_{side}"][~alone], given[side][~alone]))
+        ok &= bool(((tabs[f"d2_{side}"] >= 0) == (tabs[f"partner_{side}"] > 0)).all())
+    for g in np.nonzero(tabs["partner_truth"][0])[0][:100]:
+        ok &= edt_h2(hp[0], ht[0], tabs["partner_truth"][0, g], g + 1) == tabs["d2_truth"][0, g]
+    for p in np.nonzero(tabs["partner_pred"][0])[0][:100]:
+        ok &= edt_h2(hp[0], ht[0], p + 1, tabs["partner_pred"][0, p]) == tabs["d2_pred"][0, p]
+    sc = h.score().hausdorff_obj
+    fin = np.isfinite(sc)
+    return {"hausdorff_labels_ms": ms, "hausdorff_labels_ms_all": ts, "hausdorff_jobs": jobs, "objects_without_partner": lone,
+            "most_runs": max(most_runs(hp), most_runs(ht)), "stage_runs": K.regions_hausdorff_stage_runs(),
+            "hausdorff_obj_mean": float(sc[fin].mean()) if fin.any() else 0.0, "hausdorff_undefined": int((~fin).sum())}, bool(ok)
+
+
 def labels_main(args):
     import match_ref as M
     import regions_microbench as RM
@@ -110,6 +168,10 @@ def labels_main(args):
             os_ = o.score()
             extra = {"overlap_labels_ms": over_ms, "overlap_labels_ms_all": over_ts, "max_pairs": pairs, "pairs": int(len(image)),
                      "dropped": int(o.dropped.sum()), "aji_mean": float(os_.aji.mean()), "dice_obj_mean": float(os_.dice_obj.mean())}
+            if args.hausdorff:
+                more, same = hausdorff_part(G, pred, truth, hp, ht, o, cap, pairs)
+                extra.update(more)
+                ok &= same
         s = t.score()
         res[name] = {"match_labels_ms": match_ms, "match_labels_ms_all": ts, "two_measure_labels_ms": twice_ms, "max_regions": cap,
                      "objects_pred": int(s.n_pred.sum()), "objects_truth": int(s.n_truth.sum()), "matched": int(s.tp.sum()),
@@ -126,6 +188,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--labels", action="store_true", help="time regions.match_labels next to two measure_labels calls instead")
     ap.add_argument("--overlap", action="store_true", help="with --labels: also time regions.overlap_labels on the same label pairs")
+    ap.add_argument("--hausdorff", action="store_true", help="with --labels --overlap: also time regions.hausdorff_labels on that table")
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--cells", type=int, default=32, help="annotations and detections per image")
     ap.add_argument("--path", choices=("wave", "block"), default="wave", help="block: the 256-thread path at any size")
@@ -134,6 +197,8 @@ def main():
     args = ap.parse_args()
     if args.overlap and not args.labels:
         ap.error("--overlap goes with --labels")
+    if args.hausdorff and not args.overlap:
+        ap.error("--hausdorff goes with --labels --overlap")
     if args.labels:
         return labels_main(args)
     if args.path == "wave" and args.cells > 64:
