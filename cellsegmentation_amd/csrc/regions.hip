@@ -12,6 +12,9 @@
 //   measure   one table row per numbered component (area, bounding box, row / column / intensity sums, intensity maximum): integer
 //             atomics, one set per horizontal run of foreground pixels within a wave's 64 columns of one image row; the same pass
 //             measures a label image (one row per label, a run = equal neighbouring labels)
+//   shape     of a label image: the inner boundary of every object as a map, and per label the second moments about the corner of
+//             its bounding box and four tallies of its boundary pixels by neighbourhood class (the perimeter estimate's weights) --
+//             a walk of measure's kind, integer atomics per run
 //   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
 //             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
 //             and an exact 64-bit integer test per pred label
@@ -370,6 +373,112 @@ __global__ __launch_bounds__(256) void measure_kernel(const uint8_t* __restrict_
         if (v) {
             __hip_atomic_fetch_add(t.isum + q, (long long)s, __ATOMIC_RELAXED, kGlobal);
             raise_to(t.imax + q, mx);
+        }
+    });
+}
+
+// ---- the shape of every label: inner boundary, second moments, perimeter tallies --------------------------------------------------
+// A pixel's object id is max(label, 0).  An edge pixel has a positive id and a 4-neighbour of another id (outside the image: 0):
+// the object minus its erosion by the 4-neighbourhood, per object.  A wave reads its 64 columns of rows r - 1, r, r + 1; the ids
+// left and right come by shuffle, at lanes 0 and 63 from the columns across the segment's ends.
+__global__ __launch_bounds__(256) void edge_kernel(const int32_t* __restrict__ lab, int N, int H, int W, uint8_t* __restrict__ edges) {
+    const int lane = threadIdx.x & 63;
+    walk_row_segments(N, H, W, [&](int, int r, int c, long long p) {
+        const bool in = c < W;
+        const int l = in ? max(lab[p], 0) : 0;
+        int left = __shfl_up(l, 1), right = __shfl_down(l, 1);         // a lane with c >= W carries 0: the id outside the image
+        if (lane == 0) left = c > 0 ? max(lab[p - 1], 0) : 0;
+        if (lane == 63) right = c + 1 < W ? max(lab[p + 1], 0) : 0;
+        if (!in) return;
+        bool edge = false;
+        if (l > 0) {
+            const int up = r > 0 ? max(lab[p - W], 0) : 0, down = r < H - 1 ? max(lab[p + W], 0) : 0;
+            edge = left != l || right != l || up != l || down != l;
+        }
+        edges[p] = (uint8_t)edge;
+    });
+}
+
+struct ShapeTables {
+    const int32_t* bbox;     // [N][cap][4], read: the origin (r0, c0) of every label's moments
+    long long* moments;      // [N][cap][3] = Sxx, Syy, Sxy with x = r - r0, y = c - c0
+    int32_t* tallies;        // [N][cap][4] = edge pixels, straight, diagonal, mixed
+};
+
+__global__ __launch_bounds__(256) void shape_init_kernel(long long rows, ShapeTables t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < 4 * rows; i += (long long)gridDim.x * 256) {
+        t.tallies[i] = 0;
+        if (i < 3 * rows) t.moments[i] = 0;
+    }
+}
+
+// lane i: the sum of s over the lanes [i, last] of its run, last = the run's last lane (the lane itself where it is in no run)
+__device__ __forceinline__ int run_sum(int s, int lane, int last) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {                           // lane i: the sum over [i, min(i + 2 off - 1, last)]
+        const int o = __shfl_down(s, off);
+        if (lane + off <= last) s += o;
+    }
+    return s;
+}
+
+// An edge pixel of object l with n4 of its 4-neighbours and nd of its diagonal neighbours edge pixels of l too has the code
+// 1 + 2 n4 + 10 nd (< 64), and the code its class: bit `code` of these masks.
+constexpr unsigned long long kStraight = 1ull << 5 | 1ull << 7 | 1ull << 15 | 1ull << 17 | 1ull << 25 | 1ull << 27;
+constexpr unsigned long long kDiagonal = 1ull << 21 | 1ull << 33;
+constexpr unsigned long long kMixed = 1ull << 13 | 1ull << 23;
+
+// The runs of measure_kernel<true>: per run one set of int64 adds for the moments in closed form, and one add per tally that is
+// not zero.  el = the "edge id" of a pixel: its id where it is an edge pixel, else 0 -- a neighbour counts iff its edge id is l.
+// The four tallies of a lane travel through the segmented reduction as the bytes of one int (a run has at most 64 pixels).
+__global__ __launch_bounds__(256) void shape_kernel(const int32_t* __restrict__ lab, const uint8_t* __restrict__ edges, int N, int H, int W,
+                                                    int cap, ShapeTables t) {
+    const int lane = threadIdx.x & 63;
+    walk_row_segments(N, H, W, [&](int n, int r, int c, long long p) {
+        const bool in = c < W;
+        const int l = in ? max(lab[p], 0) : 0;
+        const unsigned long long bal = __ballot(l > 0);
+        if (bal == 0) return;
+        auto edge_id = [&](long long q) { return edges[q] ? max(lab[q], 0) : 0; };
+        const int el = (l > 0 && edges[p]) ? l : 0;
+        int packed = 0;
+        if (__ballot(el != 0)) {                                       // wave-uniform: the shuffles below are made by all lanes
+            const bool above = r > 0, below = r < H - 1;
+            const int eu = (in && above) ? edge_id(p - W) : 0, ed = (in && below) ? edge_id(p + W) : 0;
+            int lu = __shfl_up(eu, 1), lm = __shfl_up(el, 1), ld = __shfl_up(ed, 1);
+            int ru = __shfl_down(eu, 1), rm = __shfl_down(el, 1), rd = __shfl_down(ed, 1);
+            if (lane == 0) {
+                const bool has = c > 0;
+                lm = has ? edge_id(p - 1) : 0;
+                lu = (has && above) ? edge_id(p - W - 1) : 0;
+                ld = (has && below) ? edge_id(p + W - 1) : 0;
+            }
+            if (lane == 63) {
+                const bool has = c + 1 < W;
+                rm = has ? edge_id(p + 1) : 0;
+                ru = (has && above) ? edge_id(p - W + 1) : 0;
+                rd = (has && below) ? edge_id(p + W + 1) : 0;
+            }
+            if (el) {
+                const int n4 = (lm == l) + (rm == l) + (eu == l) + (ed == l), nd = (lu == l) + (ru == l) + (ld == l) + (rd == l);
+                const int code = 1 + 2 * n4 + 10 * nd;
+                packed = 1 | (int)((kStraight >> code) & 1) << 8 | (int)((kDiagonal >> code) & 1) << 16 | (int)((kMixed >> code) & 1) << 24;
+            }
+        }
+        int len;
+        const bool head = run_of(bal, __ballot(l > 0 && l != __shfl_up(l, 1)), lane, len);
+        packed = run_sum(packed, lane, l > 0 ? lane + len - 1 : lane);
+        if (!head || l > cap) return;
+        const long long q = (long long)n * cap + l - 1;
+        const long long x = r - t.bbox[4 * q], y = c - t.bbox[4 * q + 1], m = len;   // the run: row x, columns y .. y + m - 1
+        const long long tri = m * (m - 1) / 2;                         // sum of j, j < m; sum of j^2 = tri (2 m - 1) / 3
+        __hip_atomic_fetch_add(t.moments + 3 * q, m * x * x, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_add(t.moments + 3 * q + 1, m * y * y + 2 * y * tri + tri * (2 * m - 1) / 3, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_add(t.moments + 3 * q + 2, x * (m * y + tri), __ATOMIC_RELAXED, kGlobal);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int add = (packed >> (8 * k)) & 0xFF;
+            if (add) __hip_atomic_fetch_add(t.tallies + 4 * q + k, add, __ATOMIC_RELAXED, kGlobal);
         }
     });
 }
@@ -1276,6 +1385,32 @@ extern "C" int cs_regions_measure_labels(const int32_t* labels, const uint8_t* i
                        (const int32_t*)nullptr, capacity, t, counts);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(measure_empty_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_edges_labels(const int32_t* labels, int N, int H, int W, uint8_t* edges, void* stream) {
+    CS_CHECK_ARG(labels && edges, "regions_edges_labels: NULL argument");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_edges_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    hipLaunchKernelGGL(edge_kernel, walk_grid(N, H, W), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), labels, N, H, W, edges);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edges, int N, int H, int W, int capacity, const int32_t* bbox,
+                                       int64_t* moments, int32_t* tallies, void* stream) {
+    CS_CHECK_ARG(labels && edges, "regions_shape_labels: NULL argument");
+    CS_CHECK_ARG(bbox && moments && tallies, "regions_shape_labels: NULL table");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_shape_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(capacity >= 1, "regions_shape_labels: need capacity >= 1");
+    CS_CHECK_ARG((long long)N * capacity < (1LL << 31), "regions_shape_labels: need N capacity < 2^31");
+    CS_CHECK_ARG(H <= 32768 && W <= 32768, "regions_shape_labels: need H, W <= 32768 (the second moments are int64)");
+    const ShapeTables t{bbox, reinterpret_cast<long long*>(moments), tallies};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long rows = (long long)N * capacity;
+    hipLaunchKernelGGL(shape_init_kernel, dim3(grid_for(4 * rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(shape_kernel, walk_grid(N, H, W), dim3(256), 0, st, labels, edges, N, H, W, capacity, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -287,11 +287,14 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
 
 
 def measure_cells(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, connectivity=1,
-                  max_regions=None):
+                  max_regions=None, shape=False):
     """One row per segmented cell: the per-batch body of ``segment_classes``, then ``regions.measure`` of the cleaned masks with
     ``detect.quantize`` of the probabilities (uint8 ``trunc(255 p)``) as the intensity.  Returns the ``RegionTable.per_image``
     dicts of all batches in dataset order (area, bbox, centroid, intensity_sum / _mean / _max per cell).  With ``max_regions``
-    given nothing synchronises inside the loop: the tables are read back after the last batch."""
+    given nothing synchronises inside the loop: the tables are read back after the last batch.  ``shape=True`` runs
+    ``regions.shape`` on every batch instead and the dicts are those of ``ShapeTable.per_image``: the same keys with the same
+    values, plus moments, tallies, central_moments, axis_lengths, eccentricity, orientation, perimeter, equivalent_diameter, extent
+    and circularity per cell."""
     from . import detect as D
     from . import regions as Rg
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
@@ -300,7 +303,8 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     with torch.no_grad():
         for data in tqdm(loader, desc="cell measuring"):
             probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)
-            tables.append(Rg.measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions))
+            measure = Rg.shape if shape else Rg.measure
+            tables.append(measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions))
     return [d for t in tables for d in t.per_image()]
 
 

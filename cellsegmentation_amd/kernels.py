@@ -1305,6 +1305,41 @@ def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=N
     return t.get("counts"), t["area"], t["bbox"], t["sums"], t.get("isum"), t.get("imax")
 
 
+REGIONS_SHAPE_MAX_SIDE = 32768       # cs_regions_shape_labels: Sxx <= area (H - 1)^2 < 2^61 stays inside int64
+
+
+def regions_edges_labels(labels, edges=None):
+    """int32 label image [N,H,W] -> edges uint8 [N,H,W]: 1 where the pixel's object id max(label, 0) is positive and one of its four
+    neighbours (outside the image: id 0) has another id (cs_regions_edges_labels in include/cellseg_hip.h)."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_edges_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    t = _regions_outputs("regions_edges_labels", {"edges": ((N, H, W), torch.uint8)}, {"edges": edges}, labels.device)
+    _lib.check(_lib.load().cs_regions_edges_labels(_p(labels), N, H, W, _p(t["edges"]), _stream()), "regions_edges_labels")
+    return t["edges"]
+
+
+def regions_shape_labels(labels, edges, capacity, bbox, moments=None, tallies=None):
+    """int32 label image [N,H,W], its edges uint8 [N,H,W] (regions_edges_labels) and bbox int32 [N,cap,4] (regions_measure_labels of
+    the same image) -> (moments int64 [N,cap,3] = Sxx, Syy, Sxy about the box corner, tallies int32 [N,cap,4] = edge pixels,
+    straight, diagonal, mixed); row k = label k + 1 (cs_regions_shape_labels in include/cellseg_hip.h)."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_shape_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    cap = int(capacity)
+    if edges.dtype != torch.uint8 or tuple(edges.shape) != (N, H, W):
+        raise TypeError("regions_shape_labels: the edge map is uint8 of the label image's shape")
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
+        raise TypeError(f"regions_shape_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    if max(H, W) > REGIONS_SHAPE_MAX_SIDE:
+        raise ValueError(f"regions_shape_labels: a {H}x{W} image: H, W <= {REGIONS_SHAPE_MAX_SIDE} keep the second moments inside int64")
+    t = _regions_outputs("regions_shape_labels", {"moments": ((N, cap, 3), torch.int64), "tallies": ((N, cap, 4), torch.int32)},
+                         {"moments": moments, "tallies": tallies}, labels.device)
+    _lib.check(_lib.load().cs_regions_shape_labels(_p(labels), _p(edges), N, H, W, cap, _p(bbox), _p(t["moments"]), _p(t["tallies"]),
+                                                   _stream()), "regions_shape_labels")
+    return t["moments"], t["tallies"]
+
+
 def _label_pair_args(what, pred, truth, want_counts):
     """two int32 [N,H,W] label images of one shape -> (N, H, W, the ``_regions_outputs`` entries of the counts asked for)"""
     if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):

@@ -40,6 +40,12 @@ which ``OverlapTable.score`` forms AJI and object-level Dice on the host (``scor
 the nearest object where it overlaps nothing -- by the squared Hausdorff distance of the two pixel sets, in exact integers
 (``HausdorffTable``; restated in numpy by tests/hausdorff_ref.py), from which ``HausdorffTable.score`` forms the object-level
 Hausdorff distance on the host (``score.hausdorff_score``).
+
+``shape_labels`` (``shape`` for a boolean mask) adds what says how a cell is shaped to the table that says where it is: int64 second
+moments about the corner of the bounding box and four tallies of boundary pixels per label, in exact integers (``ShapeTable``; the
+rules are in ``shape_labels``'s docstring, restated in numpy by tests/shape_ref.py), from which ``ShapeTable`` forms central moments,
+axis lengths, eccentricity, orientation, perimeter, circularity, extent and equivalent diameter in float64 on the device.
+``boundaries`` gives the inner-boundary map alone, e.g. as outlines for an overlay.
 """
 import dataclasses
 import typing
@@ -740,3 +746,199 @@ def hausdorff_labels(pred, truth, overlap=None, max_regions=None, max_pairs=None
                                    **{k: x[at] for k, x in tabs.items()}, ws=ws)
     return HausdorffTable(overlap.counts_pred, overlap.counts_truth, cap_p, cap_t, overlap.area_pred, overlap.area_truth, overlap.dropped,
                           tabs["partner_truth"], tabs["d2_truth"], tabs["partner_pred"], tabs["d2_pred"])
+
+
+_SQRT2 = 2.0 ** 0.5
+_SHAPE_COLUMNS = ("central_moments", "axis_lengths", "eccentricity", "orientation", "perimeter", "equivalent_diameter", "extent",
+                  "circularity")
+
+
+@dataclasses.dataclass
+class ShapeTable:
+    """``shape_labels`` of N label images as device tensors.  ``table``: the ``RegionTable`` of the same images (row k = label
+    k + 1); ``moments`` int64 [N, cap, 3] = (Sxx, Syy, Sxy) about the corner (r0, c0) of the row's bounding box; ``tallies`` int32
+    [N, cap, 4] = (edge pixels, straight, diagonal, mixed); ``edges`` bool of the label image's shape, the inner boundary of every
+    object.  The rules are in ``shape_labels``' docstring.  Every method but ``per_image`` runs on the device in float64, is
+    computed from the integer tables only and gives NaN in unused rows, as ``RegionTable.centroid`` does."""
+    table: RegionTable
+    moments: torch.Tensor
+    tallies: torch.Tensor
+    edges: torch.Tensor
+
+    def _area(self):
+        return self.table.area.to(torch.float64)
+
+    def central_moments(self):
+        """float64 [N, cap, 3] = (mu20, mu02, mu11) = (Sxx / A - (Sx / A)^2, Syy / A - (Sy / A)^2, Sxy / A - Sx Sy / A^2) with x
+        along the rows and y along the columns, Sx = sum_rc[0] - A r0 and Sy = sum_rc[1] - A c0 formed in int64."""
+        t = self.table
+        a64 = t.area.to(torch.int64).unsqueeze(-1)
+        s = (t.sum_rc - a64 * t.bbox[..., :2].to(torch.int64)).to(torch.float64)
+        a = self._area()
+        mx, my = s[..., 0] / a, s[..., 1] / a
+        m = self.moments.to(torch.float64)
+        return torch.stack([m[..., 0] / a - mx * mx, m[..., 1] / a - my * my, m[..., 2] / a - mx * my], dim=-1)
+
+    def _eigen(self):
+        """(lambda1, lambda2 clamped at 0) of the matrix of central moments"""
+        mu = self.central_moments()
+        mean, half = (mu[..., 0] + mu[..., 1]) / 2, (mu[..., 0] - mu[..., 1]) / 2
+        root = torch.sqrt(half * half + mu[..., 2] * mu[..., 2])
+        return mean + root, (mean - root).clamp(min=0)               # (clamp keeps NaN)
+
+    def axis_lengths(self):
+        """float64 [N, cap, 2] = (4 sqrt(lambda1), 4 sqrt(lambda2)): the axes of the ellipse with the object's second moments,
+        lambda = (mu20 + mu02) / 2 +- sqrt(((mu20 - mu02) / 2)^2 + mu11^2), lambda2 clamped at 0."""
+        l1, l2 = self._eigen()
+        return torch.stack([4 * torch.sqrt(l1), 4 * torch.sqrt(l2)], dim=-1)
+
+    def eccentricity(self):
+        """float64 [N, cap] = sqrt(1 - lambda2 / lambda1), 0 where lambda1 == 0 (a single pixel)."""
+        l1, l2 = self._eigen()
+        return torch.where(l1 == 0, torch.zeros_like(l1), torch.sqrt(1 - l2 / l1))
+
+    def orientation(self):
+        """float64 [N, cap] = 0.5 atan2(2 mu11, mu20 - mu02): the angle of the major axis against the row axis, in (-pi/2, pi/2],
+        0 for an isotropic object.  scikit-image's special case for mu20 == mu02 (+-pi/4 by the sign of mu11 in its own axis
+        convention) is NOT reproduced, and no parity with its sign convention is claimed."""
+        mu = self.central_moments()
+        return 0.5 * torch.atan2(2 * mu[..., 2], mu[..., 0] - mu[..., 1])
+
+    def perimeter(self):
+        """float64 [N, cap] = straight + sqrt(2) diagonal + (1 + sqrt(2)) / 2 mixed: the 4-neighbourhood estimator that
+        scikit-image documents; 0 for objects of one or two pixels."""
+        t = self.tallies.to(torch.float64)
+        p = t[..., 1] + _SQRT2 * t[..., 2] + (1 + _SQRT2) / 2 * t[..., 3]
+        return torch.where(self.table.area > 0, p, torch.full_like(p, float("nan")))
+
+    def equivalent_diameter(self):
+        """float64 [N, cap] = sqrt(4 A / pi): the diameter of the disc of the object's area."""
+        a = self._area()
+        return torch.where(a > 0, torch.sqrt(4 * a / np.pi), torch.full_like(a, float("nan")))
+
+    def extent(self):
+        """float64 [N, cap] = A / ((r1 - r0) (c1 - c0)): the filled fraction of the bounding box."""
+        b = self.table.bbox.to(torch.int64)
+        return self._area() / ((b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])).to(torch.float64)
+
+    def circularity(self):
+        """float64 [N, cap] = 4 pi A / perimeter^2, inf where the perimeter is 0."""
+        p = self.perimeter()
+        return 4 * np.pi * self._area() / (p * p)
+
+    def per_image(self):
+        """``RegionTable.per_image`` with the columns ``moments``, ``tallies`` and one per method above added, trimmed alike.  The
+        one method that synchronises."""
+        out = self.table.per_image()
+        cols = {"moments": self.moments, "tallies": self.tallies, **{k: getattr(self, k)() for k in _SHAPE_COLUMNS}}
+        for k, v in cols.items():
+            v = v.cpu().numpy()
+            for n, d in enumerate(out):
+                d[k] = v[n, :len(d["area"])]
+        return out
+
+
+def _check_shape_size(what, shape):
+    """the second moments are int64: Sxx <= area (H - 1)^2 < 2^61 needs H, W <= 32768"""
+    if len(shape) in (2, 3) and max(int(shape[-2]), int(shape[-1])) > K.REGIONS_SHAPE_MAX_SIDE:
+        raise ValueError(f"{what}: a {shape[-2]}x{shape[-1]} image: H, W <= {K.REGIONS_SHAPE_MAX_SIDE} keep the second moments in int64")
+
+
+def _device_labels(t):
+    """a checked label image -> contiguous int32 [N, H, W] on the device"""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    return (t if t.is_cuda else t.to(_device())).contiguous()
+
+
+def boundaries(x, connectivity=1):
+    """The inner boundary of every object -> device ``torch.bool`` of the input's shape (the edge-pixel rule of ``shape_labels``).
+    ``x``: an int32 label image ([H, W] or [N, H, W], 0 and below = background), or a boolean mask, which goes through
+    ``label(x, connectivity)`` first: the components of that connectivity are the objects, so with connectivity 1 two diagonal
+    foreground pixels may be different objects, each the other's "not this object".  Never synchronises."""
+    t = _tensor(x)
+    if torch.is_tensor(t) and t.dtype == torch.bool:
+        lab = label(t, connectivity)
+    else:
+        _check_connectivity(connectivity)
+        lab = _as_labels(t, "boundaries", masks_go_to="label first, which boundaries does for them")
+    two_d = lab.dim() == 2
+    lab = _device_labels(lab)
+    edges = torch.empty(lab.shape, dtype=torch.uint8, device=lab.device)
+    for a, b in _chunks(lab):
+        K.regions_edges_labels(lab[a:b], edges=edges[a:b])
+    edges = edges.view(torch.bool)
+    return edges[0] if two_d else edges
+
+
+def shape_labels(labels, table=None, max_regions=None, counts=None):
+    """Second moments and perimeter tallies of every label of a label image, and the map of its boundaries -> ``ShapeTable``: what
+    elongation, axis lengths, orientation, perimeter and circularity are formed from, without a copy of the masks to the host.
+
+    ``labels``: int32 [H, W] or [N, H, W] (numpy or torch) with H, W <= 32768 (``ValueError`` before anything is copied).  All rules
+    are exact integers:
+
+    * Objects.  A pixel's object id is ``max(label, 0)``: 0 and below are background.  The images of a batch are independent: the
+      last row of one and the first row of the next are no neighbours.
+    * Edge pixel.  A pixel whose id is positive and at least one of whose four neighbours has a different id; a neighbour outside
+      the image has id 0.  Per object this is the object minus its erosion by the 4-neighbourhood with ``border_value=0``; another
+      positive label counts as "not this object".  The capacity plays no part in this rule.
+    * Second moments of label l, relative to the top-left corner (r0, c0) of its bounding box, x = r - r0, y = c - c0:
+      ``Sxx = sum x^2``, ``Syy = sum y^2``, ``Sxy = sum x y``, int64.  (Relative to the box so that the float64 formulas of
+      ``ShapeTable`` do not cancel on a slide-sized image; sum x and sum y follow exactly from ``sum_rc``, ``area`` and ``bbox``.)
+    * Perimeter tallies.  For every edge pixel of object l, n4 = how many of its 4 neighbours are edge pixels of the same object
+      l, nd = how many of its 4 diagonal neighbours are, code = ``1 + 2 n4 + 10 nd``.  Codes 5, 7, 15, 17, 25, 27 are *straight*,
+      21 and 33 *diagonal*, 13 and 23 *mixed*, every other code is uncounted.  Four int32 tallies per object: edge pixels, straight,
+      diagonal, mixed -- the weights of ``perimeter = straight + sqrt(2) diagonal + (1 + sqrt(2)) / 2 mixed``.  A filled 5 x 5 square
+      has (16, 16, 0, 0).
+
+    Rows of labels above the capacity are not written; a label without a pixel has an all-zero row.  The rules are restated in
+    numpy by tests/shape_ref.py and pinned to ``scipy.ndimage`` constructions (``binary_erosion``; ``convolve`` with
+    ``[[10, 2, 10], [2, 1, 2], [10, 2, 10]]`` and ``bincount``; ``sum_labels``; tests/golden/shape_vectors.npz).  Parity with
+    ``skimage.measure.regionprops`` itself is NOT pinned: scikit-image is not a dependency of this project.
+
+    ``table``: the ``RegionTable`` of the same label image where the caller has it (``measure_labels``; a table of another N,
+    capacity or device raises ``ValueError``, and so does a ``max_regions`` that disagrees with it); None runs ``measure_labels``
+    with ``max_regions`` and ``counts`` as given here.  With a table, or an int ``max_regions``, three launches whose grids depend
+    on the shape and the capacity alone follow, nothing synchronises and the call can be captured into a graph; all accumulation is
+    integer atomics, so the result does not depend on launch or arrival order."""
+    _check_max_regions(max_regions)
+    if table is not None and not isinstance(table, RegionTable):
+        raise TypeError(f"shape_labels: table must be a RegionTable or None, got {type(table).__name__}")
+    t = _as_labels(labels, "shape_labels", masks_go_to="shape")
+    _check_shape_size("shape_labels", tuple(t.shape))                     # before anything is copied anywhere
+    two_d = t.dim() == 2
+    N = 1 if two_d else t.shape[0]
+    if table is not None:
+        if max_regions is not None and int(max_regions) != table.capacity:
+            raise ValueError(f"shape_labels: max_regions {max_regions} against a RegionTable of capacity {table.capacity}")
+        if tuple(table.bbox.shape) != (N, table.capacity, 4):
+            raise ValueError(f"shape_labels: a RegionTable of {tuple(table.bbox.shape[:2])} (images, capacity) with capacity "
+                             f"{table.capacity} for {N} images")
+    t = _device_labels(t)
+    dev = t.device
+    if table is None:
+        table = measure_labels(t, max_regions=max_regions, counts=counts)
+    elif table.bbox.device != dev:
+        raise ValueError(f"shape_labels: a RegionTable on {table.bbox.device} for label images on {dev}")
+    cap = table.capacity
+    edges = torch.empty(t.shape, dtype=torch.uint8, device=dev)
+    moments = torch.empty((N, cap, 3), dtype=torch.int64, device=dev)
+    tallies = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
+    bbox = table.bbox.contiguous()
+    for a, b in _chunks(t):
+        K.regions_edges_labels(t[a:b], edges=edges[a:b])
+        K.regions_shape_labels(t[a:b], edges[a:b], cap, bbox[a:b], moments=moments[a:b], tallies=tallies[a:b])
+    edges = edges.view(torch.bool)
+    return ShapeTable(table, moments, tallies, edges[0] if two_d else edges)
+
+
+def shape(m, connectivity=1, max_regions=None, intensity=None):
+    """``shape_labels`` for a boolean mask: ``label(m, connectivity)``, ``measure_labels`` of the labels (with ``intensity``, uint8
+    of the mask's shape, or None) and ``shape_labels`` on that table -> ``ShapeTable``.  ``label`` numbers as
+    ``scipy.ndimage.label``, so row k is the same component as row k of ``measure(m)`` and ``ShapeTable.table`` holds what
+    ``measure`` gives.  ``max_regions`` as in ``measure_labels``: an int means no synchronisation."""
+    _check_max_regions(max_regions)
+    _check_shape_size("shape", tuple(getattr(m, "shape", ())))
+    lab = label(m, connectivity)
+    return shape_labels(lab, table=measure_labels(lab, intensity=intensity, max_regions=max_regions))

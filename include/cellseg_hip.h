@@ -649,6 +649,33 @@ int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity,
 int cs_regions_measure_labels(const int32_t* labels, const uint8_t* intensity, int N, int H, int W, int capacity, int32_t* counts,
                               int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax, void* stream);
 
+/* ---- the shape of every object of a label image: boundary map, second moments, perimeter tallies (csrc/regions.hip) ---------
+ * labels int32 [N][H][W]; a pixel's object id is max(label, 0), images are independent; sizes and the launch contract as above (the
+ * grids depend on (N, H, W, capacity) alone, no synchronisation, capturable); no workspace.  Additions to the ABI: cs_abi_version
+ * is unchanged.
+ * cs_regions_edges_labels: edges uint8 [N][H][W], 1 on the edge pixels, else 0.  An edge pixel has a positive id and at least one
+ *                          of its four neighbours has another id, a neighbour outside the image having id 0: per object, the object
+ *                          minus its erosion by the 4-neighbourhood with border value 0.  Another positive label is "not this
+ *                          object".  One launch.
+ * cs_regions_shape_labels: edges is READ, as cs_regions_edges_labels wrote it for the same labels; bbox int32 [N][capacity][4] is
+ *                          READ, as cs_regions_measure_labels wrote it for the same labels and capacity.  Row k of image n belongs
+ *                          to label k + 1, for k < capacity; larger labels are measured nowhere (they still are objects for the
+ *                          edge rule), and the row of a label without a pixel is all zero.
+ *                          moments int64 [N][capacity][3] = (Sxx, Syy, Sxy) = the sums of x^2, y^2 and x y over the label's pixels
+ *                          with x = r - bbox[0], y = c - bbox[1]: relative to the box so that the central moments formed from them
+ *                          in float64 do not cancel on a large image; the sums of x and y follow from cs_regions_measure_labels'
+ *                          sums, area and bbox.
+ *                          tallies int32 [N][capacity][4] = (edge pixels, straight, diagonal, mixed).  For an edge pixel of object
+ *                          l let n4 / nd be the number of its 4-neighbours / diagonal neighbours that are edge pixels of l too and
+ *                          code = 1 + 2 n4 + 10 nd: straight = codes 5, 7, 15, 17, 25, 27; diagonal = 21, 33; mixed = 13, 23; any
+ *                          other code is counted as an edge pixel only.  perimeter = straight + sqrt(2) diagonal + (1 + sqrt(2)) / 2
+ *                          mixed is the 4-neighbourhood perimeter estimate.
+ *                          Integer atomics only: independent of launch and arrival order.  Need capacity >= 1, N capacity < 2^31 and
+ *                          H, W <= 32768, so that Sxx <= area (H - 1)^2 < 2^61.  Two launches. */
+int cs_regions_edges_labels(const int32_t* labels, int N, int H, int W, uint8_t* edges, void* stream);
+int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edges, int N, int H, int W, int capacity, const int32_t* bbox,
+                            int64_t* moments, int32_t* tallies, void* stream);
+
 /* ---- a label image scored against another at the object level (csrc/regions.hip) --------------------------------------------
  * pred, truth int32 [N][H][W], values <= 0 = background; sizes and the launch contract as above (a fixed number of launches for
  * given (N, H, W, cap_pred, cap_truth), no synchronisation, capturable).  For image n let Ap[p] / At[g] be the pixel counts of

@@ -16,6 +16,13 @@ per 299^2 of area: the worst case of the seed walk).  It reports the distance ev
 tests/split_ref.py (scipy).
 
     python tools/regions_microbench.py --split [--reps 5] [--host-maps 2] [--json PATH]
+
+--shape times ``regions.shape_labels`` with the table given (the boundary map, the second moments and the perimeter tallies: three
+launches) next to ``regions.measure_labels`` on the same label images: ``regions.split`` of the same two mask sets at about 1 and
+about 10 seeds per component.  Both are captured into a graph once and the replays are timed, so the figures hold no launch
+overhead of the host.  The first ``--host-maps`` maps are checked against tests/shape_ref.py.
+
+    python tools/regions_microbench.py --shape [--reps 5] [--host-maps 2] [--json PATH]
 """
 import argparse
 import json
@@ -48,6 +55,19 @@ def time_dev(fn, reps):
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b))
     return float(np.median(ts)), ts
+
+
+def time_graph(fn, reps):
+    """fn captured into one graph after a warm-up on a side stream; the median replay time in ms, and all of them"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return time_dev(graph.replay, reps)
 
 
 def case(name, masks, reps, host_maps, dev):
@@ -184,6 +204,42 @@ def split_main(args):
     return res
 
 
+def shape_case(name, masks, pts, off, reps, host_maps, dev):
+    import shape_ref as SR
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    parts = G.split(d, dp, doff)
+    cap = max(1, int(parts.counts.max()))                                  # sized once, outside the timed region
+    table = G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts)
+    measure_ms, _ = time_graph(lambda: G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts), reps)
+    edges_ms, _ = time_graph(lambda: G.boundaries(parts.labels), reps)
+    shape_ms, ts = time_graph(lambda: G.shape_labels(parts.labels, table=table), reps)
+    st = G.shape_labels(parts.labels, table=table)
+    res = {"measure_labels_ms": measure_ms, "boundaries_ms": edges_ms, "shape_labels_ms": shape_ms, "shape_labels_ms_all": ts,
+           "shape_over_measure_labels": shape_ms / measure_ms, "rows_max": cap, "foreground_pixels": int(masks.sum()),
+           "edge_pixels": int(st.edges.sum())}
+    ok = True
+    labels = parts.labels.cpu().numpy()
+    for i in range(min(host_maps, len(masks))):
+        ref = SR.shape_labels(labels[i], cap)
+        ok &= bool(np.array_equal(st.edges[i].cpu().numpy(), ref["edges"]))
+        for key in ("moments", "tallies"):
+            ok &= bool(np.array_equal(getattr(st, key)[i].cpu().numpy(), ref[key][0]))
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
+def shape_main(args):
+    dev = torch.device("cuda:0")
+    res = {}
+    for name, masks in mask_sets():
+        lab = G.label(torch.from_numpy(masks).to(dev)).cpu().numpy()
+        for per in (1, 10):
+            pts, off = seeds_in_components(lab, per, seed=per)
+            res[f"{name}.seeds{per}"] = shape_case(f"{name}.seeds{per}", masks, pts, off, args.reps, args.host_maps, dev)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -191,8 +247,11 @@ def main():
     ap.add_argument("--json", default=None, help="also write the results to this file")
     ap.add_argument("--measure", action="store_true", help="time regions.measure next to regions.label instead")
     ap.add_argument("--split", action="store_true", help="time regions.split + measure_labels next to label + measure instead")
+    ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
     args = ap.parse_args()
-    if args.split:
+    if args.shape:
+        res = shape_main(args)
+    elif args.split:
         res = split_main(args)
     elif args.measure:
         res = measure_main(args)
