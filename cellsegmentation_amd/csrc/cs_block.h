@@ -69,3 +69,20 @@ __device__ __forceinline__ void uf_unite(int32_t* lab, int a, int b) {
         b = lo;
     }
 }
+
+// op(., .) folded over the values v of the NT threads of the workgroup: xor shuffles within a wave, one slot of LDS per wave
+// across; op is associative and commutative, V a type the shuffles move (int, long long).  Contract: EVERY thread of the
+// workgroup calls it (it holds barriers), with `slots` = NT / 64 elements of LDS owned by the caller; every thread gets the
+// result and `slots` may be written again on return.
+template <int NT, typename V, typename Op>
+__device__ __forceinline__ V block_reduce(V v, Op op, V* slots) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off));
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
+    __syncthreads();
+    V all = slots[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w) all = op(all, slots[w]);
+    __syncthreads();
+    return all;
+}

@@ -15,6 +15,9 @@
 //   shape     of a label image: the inner boundary of every object as a map, and per label the second moments about the corner of
 //             its bounding box and four tallies of its boundary pixels by neighbourhood class (the perimeter estimate's weights) --
 //             a walk of measure's kind, integer atomics per run
+//   hull      of a label image: per label the convex hull of its pixels' unit squares -- vertex count, twice the area, the largest
+//             squared vertex distance and the smallest width as an exact fraction; one workgroup per label, the row extents of its
+//             bounding box and the hull's vertices in LDS, no atomics and no workspace
 //   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
 //             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
 //             and an exact 64-bit integer test per pred label
@@ -481,6 +484,136 @@ __global__ __launch_bounds__(256) void shape_kernel(const int32_t* __restrict__ 
             if (add) __hip_atomic_fetch_add(t.tallies + 4 * q + k, add, __ATOMIC_RELAXED, kGlobal);
         }
     });
+}
+
+// ---- the convex hull of every label: vertex count, area, largest and smallest Feret diameter ---------------------------------------
+// An object is the union of the closed unit squares of its pixels; in lattice coordinates relative to the corner of its box,
+// pixel (i, j) has the corners (i, j), (i + 1, j), (i, j + 1), (i + 1, j + 1).  On lattice row r lie the corners of the pixel rows
+// r - 1 and r, and only the leftmost and the rightmost of them can be vertices of the hull: the left chain runs down the leftmost
+// points, the right chain down the rightmost, and the hull is the left chain followed by the right chain backwards.  The ends of
+// the chains are the ends of the top and the bottom edge, which are horizontal and at least one pixel long.
+constexpr int kHullSide = 1024;        // cs_regions_hull_max_side: coordinates <= 1024, cross products <= 2^21, squared ones <= 2^42
+constexpr int kHullNone = 0xFFFF;      // lo of a pixel row without a pixel of the label (its hi is 0)
+
+struct HullLds {
+    uint16_t lo[kHullSide], hi[kHullSide];   // per pixel row of the box: the leftmost column of the label, the rightmost + 1
+    // Every lattice row gives one candidate per chain, so a box of `rows` pixel rows has at most 2 (rows + 1) hull vertices:
+    // rows + 1 <= kHullSide + 1 per chain.  A vertex is r << 16 | c.  12.3 KiB with lo and hi.
+    int32_t chain[2][kHullSide + 1];
+    int n[2];
+    long long red[4];
+};
+
+// the narrower of two edges (cross << 32 | len2; below 0: none): the smaller cross^2 / len2, then the smaller len2.  The products
+// are below 2^42 2^21 = 2^63.
+__device__ __forceinline__ long long hull_narrower(long long a, long long b) {
+    if (a < 0 || b < 0) return a < 0 ? b : a;
+    const unsigned long long ca = (unsigned long long)a >> 32, la = (unsigned long long)a & 0xFFFFFFFFull;
+    const unsigned long long cb = (unsigned long long)b >> 32, lb = (unsigned long long)b & 0xFFFFFFFFull;
+    const unsigned long long wa = ca * ca * lb, wb = cb * cb * la;
+    if (wa != wb) return wa < wb ? a : b;
+    return la <= lb ? a : b;
+}
+
+// One workgroup per (image, label) at a time.  The box is cut to the image before anything is read, so whatever the table holds
+// no read leaves the label image.
+__global__ __launch_bounds__(256) void hull_kernel(const int32_t* __restrict__ lab, int N, int H, int W, int cap,
+                                                   const int32_t* __restrict__ bbox, int32_t* __restrict__ hull) {
+    __shared__ HullLds s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long objects = (long long)N * cap;
+    for (long long q = blockIdx.x; q < objects; q += gridDim.x) {
+        const int n = (int)(q / cap), l = (int)(q - (long long)n * cap) + 1;
+        const int r0 = max(bbox[4 * q], 0), c0 = max(bbox[4 * q + 1], 0);
+        const int rows = min(bbox[4 * q + 2], H) - r0, cols = min(bbox[4 * q + 3], W) - c0;
+        const bool none = rows <= 0 || cols <= 0;
+        if (none || rows > kHullSide || cols > kHullSide) {            // the same in every thread: no barrier is left out below
+            if (threadIdx.x < 5) hull[5 * q + threadIdx.x] = none ? 0 : -1;
+            continue;
+        }
+        // 1. the extents of every pixel row: a wave per row, its lanes stride over the columns of the box
+        const int32_t* img = lab + (long long)n * H * W + (long long)r0 * W + c0;
+        for (int i = wave; i < rows; i += 4) {
+            const int32_t* row = img + (long long)i * W;
+            int lo = kHullNone, hi = 0;
+            for (int c = lane; c < cols; c += 64) {
+                if (row[c] == l) {
+                    lo = min(lo, c);
+                    hi = c + 1;
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                lo = min(lo, __shfl_xor(lo, off));
+                hi = max(hi, __shfl_xor(hi, off));
+            }
+            if (lane == 0) {
+                s.lo[i] = (uint16_t)lo;
+                s.hi[i] = (uint16_t)hi;
+            }
+        }
+        __syncthreads();
+        // 2. the two chains, each by one thread of a wave of its own: a streaming stack over the lattice rows, top to bottom.  With
+        //    a the vertex below the top b and p the candidate, b stays while it lies strictly outside the line a -> p.
+        if (lane == 0 && wave < 2) {
+            const bool right = wave == 1;
+            int32_t* v = s.chain[wave];
+            int m = 0;
+            for (int r = 0; r <= rows; ++r) {
+                int c;
+                if (right) {
+                    c = max(r > 0 ? (int)s.hi[r - 1] : 0, r < rows ? (int)s.hi[r] : 0);
+                    if (c == 0) continue;
+                } else {
+                    c = min(r > 0 ? (int)s.lo[r - 1] : kHullNone, r < rows ? (int)s.lo[r] : kHullNone);
+                    if (c == kHullNone) continue;
+                }
+                while (m >= 2) {
+                    const int a = v[m - 2], b = v[m - 1];
+                    const int ar = a >> 16, ac = a & 0xFFFF;
+                    const int turn = ((b >> 16) - ar) * (c - ac) - ((b & 0xFFFF) - ac) * (r - ar);
+                    if (right ? turn < 0 : turn > 0) break;
+                    --m;
+                }
+                v[m++] = r << 16 | c;
+            }
+            s.n[wave] = m;
+        }
+        __syncthreads();
+        // 3. a thread per edge a -> b, every vertex held against it: the farthest from a, and the farthest from the edge's line
+        const int nl = s.n[0], nr = s.n[1], V = nl + nr;
+        auto vertex = [&](int k) { return k < nl ? s.chain[0][k] : s.chain[1][V - 1 - k]; };
+        long long area2 = 0, far2 = 0, narrow = -1;
+        for (int k = threadIdx.x; k < V; k += 256) {
+            const int a = vertex(k), b = vertex(k + 1 == V ? 0 : k + 1);
+            const int ar = a >> 16, ac = a & 0xFFFF, br = b >> 16, bc = b & 0xFFFF, er = br - ar, ec = bc - ac;
+            area2 += ar * bc - br * ac;
+            int cross = 0, d2 = 0;
+            for (int side = 0; side < 2; ++side) {
+                const int count = side ? nr : nl;
+                for (int j = 0; j < count; ++j) {
+                    const int p = s.chain[side][j];
+                    const int dr = (p >> 16) - ar, dc = (p & 0xFFFF) - ac;
+                    cross = max(cross, abs(er * dc - ec * dr));
+                    d2 = max(d2, dr * dr + dc * dc);
+                }
+            }
+            far2 = max(far2, (long long)d2);
+            narrow = hull_narrower(narrow, (long long)cross << 32 | (long long)(er * er + ec * ec));
+        }
+        area2 = block_reduce<256>(area2, [](long long x, long long y) { return x + y; }, s.red);
+        far2 = block_reduce<256>(far2, [](long long x, long long y) { return x > y ? x : y; }, s.red);
+        // (the last barrier of this call is the one after which the next object may overwrite s)
+        narrow = block_reduce<256>(narrow, [](long long x, long long y) { return hull_narrower(x, y); }, s.red);
+        if (threadIdx.x == 0) {
+            int32_t* out = hull + 5 * q;
+            out[0] = V;
+            out[1] = (int)(area2 < 0 ? -area2 : area2);
+            out[2] = (int)far2;
+            out[3] = narrow < 0 ? 0 : (int)(narrow >> 32);
+            out[4] = narrow < 0 ? 0 : (int)(narrow & 0xFFFFFFFFll);
+        }
+    }
 }
 
 // ---- two label images walked at once: what match and overlap share ---------------------------------------------------------------
@@ -1411,6 +1544,22 @@ extern "C" int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edg
     hipLaunchKernelGGL(shape_init_kernel, dim3(grid_for(4 * rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(shape_kernel, walk_grid(N, H, W), dim3(256), 0, st, labels, edges, N, H, W, capacity, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_hull_max_side(void) { return kHullSide; }
+
+extern "C" int cs_regions_hull_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int32_t* hull,
+                                      void* stream) {
+    CS_CHECK_ARG(labels, "regions_hull_labels: NULL argument");
+    CS_CHECK_ARG(bbox && hull, "regions_hull_labels: NULL table");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_hull_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(capacity >= 1, "regions_hull_labels: need capacity >= 1");
+    CS_CHECK_ARG((long long)N * capacity < (1LL << 31), "regions_hull_labels: need N capacity < 2^31");
+    const long long objects = (long long)N * capacity;
+    hipLaunchKernelGGL(hull_kernel, dim3((unsigned)(objects < 8192 ? objects : 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       labels, N, H, W, capacity, bbox, hull);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

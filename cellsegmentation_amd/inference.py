@@ -287,14 +287,16 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
 
 
 def measure_cells(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, connectivity=1,
-                  max_regions=None, shape=False):
+                  max_regions=None, shape=False, hull=False):
     """One row per segmented cell: the per-batch body of ``segment_classes``, then ``regions.measure`` of the cleaned masks with
     ``detect.quantize`` of the probabilities (uint8 ``trunc(255 p)``) as the intensity.  Returns the ``RegionTable.per_image``
     dicts of all batches in dataset order (area, bbox, centroid, intensity_sum / _mean / _max per cell).  With ``max_regions``
     given nothing synchronises inside the loop: the tables are read back after the last batch.  ``shape=True`` runs
     ``regions.shape`` on every batch instead and the dicts are those of ``ShapeTable.per_image``: the same keys with the same
     values, plus moments, tallies, central_moments, axis_lengths, eccentricity, orientation, perimeter, equivalent_diameter, extent
-    and circularity per cell."""
+    and circularity per cell.  ``hull=True`` adds the columns of ``HullTable.per_image`` (hull, convex_area, solidity,
+    feret_diameter_max, feret_diameter_min, n_vertices, too_large) in the same way; with both, every batch is labelled and measured
+    once and ``regions.shape_labels`` and ``regions.hull_labels`` share that one ``RegionTable``."""
     from . import detect as D
     from . import regions as Rg
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
@@ -303,9 +305,22 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     with torch.no_grad():
         for data in tqdm(loader, desc="cell measuring"):
             probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)
-            measure = Rg.shape if shape else Rg.measure
-            tables.append(measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions))
-    return [d for t in tables for d in t.per_image()]
+            if hull:                                                      # label and measure once; both tables hang on that one
+                lab = Rg.label(classes, connectivity)
+                table = Rg.measure_labels(lab, intensity=D.quantize(probs), max_regions=max_regions)
+                parts = ([Rg.shape_labels(lab, table=table)] if shape else []) + [Rg.hull_labels(lab, table=table)]
+            else:
+                measure = Rg.shape if shape else Rg.measure
+                parts = [measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions)]
+            tables.append(parts)
+    out = []
+    for parts in tables:
+        dicts = parts[0].per_image()
+        for more in parts[1:]:
+            for d, extra in zip(dicts, more.per_image()):
+                d.update(extra)
+        out += dicts
+    return out
 
 
 def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None):

@@ -1340,6 +1340,24 @@ def regions_shape_labels(labels, edges, capacity, bbox, moments=None, tallies=No
     return t["moments"], t["tallies"]
 
 
+REGIONS_HULL_MAX_SIDE = 1024         # cs_regions_hull_max_side: a larger bounding box is counted, not measured (its row is -1)
+
+
+def regions_hull_labels(labels, capacity, bbox, hull=None):
+    """int32 label image [N,H,W] and bbox int32 [N,cap,4] (regions_measure_labels of the same image) -> hull int32 [N,cap,5] =
+    n_vertices, area2, feret_max2, width_cross, width_len2 of the convex hull of every label's pixel squares; row k = label k + 1,
+    all -1 where the box has more than REGIONS_HULL_MAX_SIDE rows or columns (cs_regions_hull_labels in include/cellseg_hip.h)."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_hull_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    cap = int(capacity)
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
+        raise TypeError(f"regions_hull_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    t = _regions_outputs("regions_hull_labels", {"hull": ((N, cap, 5), torch.int32)}, {"hull": hull}, labels.device)
+    _lib.check(_lib.load().cs_regions_hull_labels(_p(labels), N, H, W, cap, _p(bbox), _p(t["hull"]), _stream()), "regions_hull_labels")
+    return t["hull"]
+
+
 def _label_pair_args(what, pred, truth, want_counts):
     """two int32 [N,H,W] label images of one shape -> (N, H, W, the ``_regions_outputs`` entries of the counts asked for)"""
     if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):

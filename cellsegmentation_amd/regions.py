@@ -46,6 +46,12 @@ moments about the corner of the bounding box and four tallies of boundary pixels
 rules are in ``shape_labels``'s docstring, restated in numpy by tests/shape_ref.py), from which ``ShapeTable`` forms central moments,
 axis lengths, eccentricity, orientation, perimeter, circularity, extent and equivalent diameter in float64 on the device.
 ``boundaries`` gives the inner-boundary map alone, e.g. as outlines for an overlay.
+
+``hull_labels`` (``hull`` for a boolean mask) adds the convex hull of every label's pixel squares: vertex count, twice the area,
+the largest squared vertex distance and the smallest width as an exact fraction, in exact integers (``HullTable``; the rules are in
+``hull_labels``'s docstring, restated in Python integers by tests/hull_ref.py), from which ``HullTable`` forms convex area, solidity
+and the largest and smallest Feret diameter in float64 on the device.  Objects whose bounding box exceeds 1024 rows or columns are
+counted, not measured.
 """
 import dataclasses
 import typing
@@ -851,6 +857,32 @@ def _device_labels(t):
     return (t if t.is_cuda else t.to(_device())).contiguous()
 
 
+def _labels_and_table(what, labels, table, max_regions, counts, masks_go_to, check_size=None):
+    """The arguments that ``shape_labels`` and ``hull_labels`` share -> (contiguous int32 [N, H, W] on the device, the
+    ``RegionTable`` of those images, whether ``labels`` was [H, W]).  Every argument error is raised before anything is copied; a
+    table of None runs ``measure_labels`` with ``max_regions`` and ``counts``."""
+    _check_max_regions(max_regions)
+    if table is not None and not isinstance(table, RegionTable):
+        raise TypeError(f"{what}: table must be a RegionTable or None, got {type(table).__name__}")
+    t = _as_labels(labels, what, masks_go_to=masks_go_to)
+    if check_size is not None:
+        check_size(what, tuple(t.shape))
+    two_d = t.dim() == 2
+    N = 1 if two_d else t.shape[0]
+    if table is not None:
+        if max_regions is not None and int(max_regions) != table.capacity:
+            raise ValueError(f"{what}: max_regions {max_regions} against a RegionTable of capacity {table.capacity}")
+        if tuple(table.bbox.shape) != (N, table.capacity, 4):
+            raise ValueError(f"{what}: a RegionTable of {tuple(table.bbox.shape[:2])} (images, capacity) with capacity "
+                             f"{table.capacity} for {N} images")
+    t = _device_labels(t)
+    if table is None:
+        table = measure_labels(t, max_regions=max_regions, counts=counts)
+    elif table.bbox.device != t.device:
+        raise ValueError(f"{what}: a RegionTable on {table.bbox.device} for label images on {t.device}")
+    return t, table, two_d
+
+
 def boundaries(x, connectivity=1):
     """The inner boundary of every object -> device ``torch.bool`` of the input's shape (the edge-pixel rule of ``shape_labels``).
     ``x``: an int32 label image ([H, W] or [N, H, W], 0 and below = background), or a boolean mask, which goes through
@@ -902,25 +934,8 @@ def shape_labels(labels, table=None, max_regions=None, counts=None):
     with ``max_regions`` and ``counts`` as given here.  With a table, or an int ``max_regions``, three launches whose grids depend
     on the shape and the capacity alone follow, nothing synchronises and the call can be captured into a graph; all accumulation is
     integer atomics, so the result does not depend on launch or arrival order."""
-    _check_max_regions(max_regions)
-    if table is not None and not isinstance(table, RegionTable):
-        raise TypeError(f"shape_labels: table must be a RegionTable or None, got {type(table).__name__}")
-    t = _as_labels(labels, "shape_labels", masks_go_to="shape")
-    _check_shape_size("shape_labels", tuple(t.shape))                     # before anything is copied anywhere
-    two_d = t.dim() == 2
-    N = 1 if two_d else t.shape[0]
-    if table is not None:
-        if max_regions is not None and int(max_regions) != table.capacity:
-            raise ValueError(f"shape_labels: max_regions {max_regions} against a RegionTable of capacity {table.capacity}")
-        if tuple(table.bbox.shape) != (N, table.capacity, 4):
-            raise ValueError(f"shape_labels: a RegionTable of {tuple(table.bbox.shape[:2])} (images, capacity) with capacity "
-                             f"{table.capacity} for {N} images")
-    t = _device_labels(t)
-    dev = t.device
-    if table is None:
-        table = measure_labels(t, max_regions=max_regions, counts=counts)
-    elif table.bbox.device != dev:
-        raise ValueError(f"shape_labels: a RegionTable on {table.bbox.device} for label images on {dev}")
+    t, table, two_d = _labels_and_table("shape_labels", labels, table, max_regions, counts, "shape", _check_shape_size)
+    N, dev = t.shape[0], t.device
     cap = table.capacity
     edges = torch.empty(t.shape, dtype=torch.uint8, device=dev)
     moments = torch.empty((N, cap, 3), dtype=torch.int64, device=dev)
@@ -942,3 +957,115 @@ def shape(m, connectivity=1, max_regions=None, intensity=None):
     _check_shape_size("shape", tuple(getattr(m, "shape", ())))
     lab = label(m, connectivity)
     return shape_labels(lab, table=measure_labels(lab, intensity=intensity, max_regions=max_regions))
+
+
+_HULL_COLUMNS = ("convex_area", "solidity", "feret_diameter_max", "feret_diameter_min", "n_vertices", "too_large")
+
+
+@dataclasses.dataclass
+class HullTable:
+    """``hull_labels`` of N label images as device tensors.  ``table``: the ``RegionTable`` of the same images (row k = label
+    k + 1); ``hull`` int32 [N, cap, 5] = (n_vertices, area2, feret_max2, width_cross, width_len2) of the convex hull of the label's
+    pixel squares: all zero for a label without a pixel, all -1 for one whose bounding box is too large.  The rules are in
+    ``hull_labels``' docstring.  Every method but ``per_image`` runs on the device, is computed from the integer tables only and,
+    but for ``too_large``, gives float64 with NaN in unused and in too-large rows."""
+    table: RegionTable
+    hull: torch.Tensor
+
+    def _measured(self, x):
+        ok = (self.table.area > 0) & (self.hull[..., 0] >= 0)
+        return torch.where(ok, x, torch.full_like(x, float("nan")))
+
+    def too_large(self):
+        """device bool [N, cap]: the label's bounding box has more than ``kernels.REGIONS_HULL_MAX_SIDE`` rows or columns, so the
+        object is counted (its ``table`` row is complete) but its hull is not measured."""
+        return self.hull[..., 0] < 0
+
+    def n_vertices(self):
+        """float64 [N, cap]: the strict vertices of the hull, at least 4."""
+        return self._measured(self.hull[..., 0].to(torch.float64))
+
+    def convex_area(self):
+        """float64 [N, cap] = area2 / 2: the area of the hull of the pixel squares, >= the pixel count.  NOT scikit-image's
+        ``area_convex``, which counts the pixels of a rasterised hull of the pixel centres' offsets."""
+        return self._measured(self.hull[..., 1].to(torch.float64) / 2)
+
+    def solidity(self):
+        """float64 [N, cap] = area / convex_area, in (0, 1], exactly 1 for a filled rectangle."""
+        return self.table.area.to(torch.float64) / self.convex_area()
+
+    def feret_diameter_max(self):
+        """float64 [N, cap] = sqrt(feret_max2): the largest distance between two points of the object's pixel squares (a single
+        pixel: sqrt 2).  NOT scikit-image's ``feret_diameter_max``, which measures a marching-squares contour at level 0.5."""
+        return self._measured(torch.sqrt(self.hull[..., 2].clamp(min=0).to(torch.float64)))
+
+    def feret_diameter_min(self):
+        """float64 [N, cap] = width_cross / sqrt(width_len2): the smallest distance between two parallel lines that hold the object
+        between them (one of them runs along a hull edge)."""
+        return self._measured(self.hull[..., 3].to(torch.float64) / torch.sqrt(self.hull[..., 4].clamp(min=0).to(torch.float64)))
+
+    def per_image(self):
+        """``RegionTable.per_image`` with the columns ``hull`` and one per method above added, trimmed alike.  The one method that
+        synchronises."""
+        out = self.table.per_image()
+        cols = {"hull": self.hull, **{k: getattr(self, k)() for k in _HULL_COLUMNS}}
+        for k, v in cols.items():
+            v = v.cpu().numpy()
+            for n, d in enumerate(out):
+                d[k] = v[n, :len(d["area"])]
+        return out
+
+
+def hull_labels(labels, table=None, max_regions=None, counts=None):
+    """The convex hull of every label of a label image, as integers -> ``HullTable``: what convex area, solidity (one cell or a
+    clump?) and the largest and smallest Feret diameter are formed from, without a copy of the masks to the host.
+
+    ``labels``: int32 [H, W] or [N, H, W] (numpy or torch).  Everything the device writes is an exact integer:
+
+    * Objects.  A pixel's object id is ``max(label, 0)``: 0 and below are background.  The images of a batch are independent.  A
+      label need not be connected: the hull is that of all its pixels.
+    * Point set.  An object is the union of the closed unit squares of its pixels: pixel (r, c) contributes the lattice points
+      (r, c), (r + 1, c), (r, c + 1), (r + 1, c + 1), and the hull is the convex hull of those points.  So every object, a single
+      pixel included, has a hull of at least 4 vertices and positive area: there is no degenerate case.
+    * Candidates.  Only the leftmost and the rightmost pixel of the object in each pixel row can contribute vertices; a row of the
+      bounding box without a pixel of the label contributes nothing.  Hence at most ``2 (rows + 1)`` vertices, ``rows`` being the
+      height of the bounding box.
+    * Per label, int32 ``hull[N, cap, 5]``: ``n_vertices``, the strict vertices (no three consecutive ones collinear); ``area2``,
+      twice the hull's area by the shoelace formula; ``feret_max2``, the largest squared distance between two vertices;
+      ``width_cross`` and ``width_len2``, the minimum width as an exact fraction.
+    * Minimum width.  For every hull edge e from a to b let ``len2(e) = |b - a|^2`` and ``cross(e)`` the maximum over the hull's
+      vertices v of ``|(b - a) x (v - a)|``; the width across e is ``cross(e) / sqrt(len2(e))``.  Stored is the edge that minimises
+      ``(cross^2 / len2, len2)``, the fractions compared by cross-multiplication in unsigned 64-bit integers; the second key makes
+      the pair unique (equal width and equal len2 give equal cross).
+    * Side limit.  A bounding box of more than ``kernels.REGIONS_HULL_MAX_SIDE`` = 1024 rows or columns is too large: all five
+      entries are -1 and ``HullTable.too_large()`` flags the row; the object is counted, not measured, as rows above a capacity are
+      elsewhere.  Within the limit cross <= 2^21, cross^2 <= 2^42 and len2 <= 2^21: every compared product is below 2^64 and every
+      output fits int32.
+    * A label without a pixel has an all-zero row; rows of labels above the capacity are not written.  No workspace.
+
+    A filled 5 x 5 square has (4, 50, 50, 25, 25), a single pixel (4, 2, 2, 1, 1).  The rules are restated in Python integers by
+    tests/hull_ref.py and pinned to ``scipy.spatial.ConvexHull`` over all corners of all pixels (tests/golden/hull_vectors.npz).
+    Parity with ``skimage.measure.regionprops`` is NOT claimed and scikit-image is not a dependency: its ``area_convex`` counts the
+    pixels of a rasterised hull (an integer, where ``convex_area`` here is the exact area of the polygon round the pixel squares),
+    and its ``feret_diameter_max`` measures a marching-squares contour through the pixel edges' midpoints (shorter than the
+    distance between pixel corners used here).
+
+    ``table``, ``max_regions`` and ``counts`` as in ``shape_labels``.  With a table, or an int ``max_regions``, one launch whose
+    grid depends on (N, capacity) alone follows, nothing synchronises and the call can be captured into a graph; there are no
+    atomics, so the result does not depend on launch order."""
+    t, table, _ = _labels_and_table("hull_labels", labels, table, max_regions, counts, "hull")
+    cap = table.capacity
+    hull = torch.empty((t.shape[0], cap, 5), dtype=torch.int32, device=t.device)
+    bbox = table.bbox.contiguous()
+    for a, b in _chunks(t):
+        K.regions_hull_labels(t[a:b], cap, bbox[a:b], hull=hull[a:b])
+    return HullTable(table, hull)
+
+
+def hull(m, connectivity=1, max_regions=None, intensity=None):
+    """``hull_labels`` for a boolean mask: ``label(m, connectivity)``, ``measure_labels`` of the labels (with ``intensity``, uint8
+    of the mask's shape, or None) and ``hull_labels`` on that table -> ``HullTable``.  Row k is the same component as row k of
+    ``measure(m)``.  ``max_regions`` as in ``measure_labels``: an int means no synchronisation."""
+    _check_max_regions(max_regions)
+    lab = label(m, connectivity)
+    return hull_labels(lab, table=measure_labels(lab, intensity=intensity, max_regions=max_regions))

@@ -676,6 +676,31 @@ int cs_regions_edges_labels(const int32_t* labels, int N, int H, int W, uint8_t*
 int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edges, int N, int H, int W, int capacity, const int32_t* bbox,
                             int64_t* moments, int32_t* tallies, void* stream);
 
+/* ---- the convex hull of every object of a label image: vertex count, area, Feret diameters (csrc/regions.hip) ----------------
+ * labels int32 [N][H][W]; a pixel's object id is max(label, 0), images are independent, a label need not be connected; sizes as
+ * above.  One launch whose grid depends on (N, capacity) alone, no synchronisation, capturable; no workspace and no atomics.
+ * Additions to the ABI: cs_abi_version is unchanged.
+ * cs_regions_hull_max_side: 1024, the largest number of rows or columns of a bounding box that is still measured.
+ * cs_regions_hull_labels:   bbox int32 [N][capacity][4] is READ, as cs_regions_measure_labels wrote it for the same labels and
+ *                           capacity (it is cut to the image before a pixel is read).  Row k of image n belongs to label k + 1,
+ *                           for k < capacity; larger labels are measured nowhere.  An object is the union of the closed unit
+ *                           squares of its pixels, pixel (r, c) having the corners (r, c), (r + 1, c), (r, c + 1), (r + 1, c + 1);
+ *                           the hull is the convex hull of those lattice points, so it has at least 4 vertices and positive area.
+ *                           hull int32 [N][capacity][5] = (n_vertices, area2, feret_max2, width_cross, width_len2):
+ *                             n_vertices  the strict vertices (no three consecutive ones collinear);
+ *                             area2       twice the area of the hull (shoelace formula);
+ *                             feret_max2  the largest squared distance between two vertices;
+ *                             width_*     of the hull edge e = a -> b that minimises (cross^2 / len2, len2), len2 = |b - a|^2 and
+ *                                         cross = the maximum over the vertices v of |(b - a) x (v - a)|, the fractions compared by
+ *                                         cross-multiplication in unsigned 64-bit integers: the minimum width is
+ *                                         width_cross / sqrt(width_len2).
+ *                           The row of a label without a pixel (box (0, 0, 0, 0)) is all zero; the row of a label whose box has
+ *                           more than cs_regions_hull_max_side rows or columns is all -1.  Within that limit cross <= 2^21 and
+ *                           len2 <= 2^21: every compared product is below 2^64 and every entry fits int32.
+ *                           Need capacity >= 1 and N capacity < 2^31. */
+int cs_regions_hull_max_side(void);
+int cs_regions_hull_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int32_t* hull, void* stream);
+
 /* ---- a label image scored against another at the object level (csrc/regions.hip) --------------------------------------------
  * pred, truth int32 [N][H][W], values <= 0 = background; sizes and the launch contract as above (a fixed number of launches for
  * given (N, H, W, cap_pred, cap_truth), no synchronisation, capturable).  For image n let Ap[p] / At[g] be the pixel counts of

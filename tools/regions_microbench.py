@@ -23,6 +23,13 @@ about 10 seeds per component.  Both are captured into a graph once and the repla
 overhead of the host.  The first ``--host-maps`` maps are checked against tests/shape_ref.py.
 
     python tools/regions_microbench.py --shape [--reps 5] [--host-maps 2] [--json PATH]
+
+--hull times ``regions.hull_labels`` with the table given (one launch, one workgroup per label) next to ``regions.measure_labels``
+and ``regions.shape_labels`` on the label images of ``--shape``, graph replays again.  It reports the two terms of the cost model --
+the sum of the bounding-box areas and the sum of the squared vertex counts -- and checks the first ``--host-maps`` maps against
+tests/hull_ref.py.
+
+    python tools/regions_microbench.py --hull [--reps 5] [--host-maps 2] [--json PATH]
 """
 import argparse
 import json
@@ -229,14 +236,41 @@ def shape_case(name, masks, pts, off, reps, host_maps, dev):
     return res
 
 
-def shape_main(args):
+def hull_case(name, masks, pts, off, reps, host_maps, dev):
+    import hull_ref as HR
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    parts = G.split(d, dp, doff)
+    cap = max(1, int(parts.counts.max()))                                  # sized once, outside the timed region
+    table = G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts)
+    measure_ms, _ = time_graph(lambda: G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts), reps)
+    shape_ms, _ = time_graph(lambda: G.shape_labels(parts.labels, table=table), reps)
+    hull_ms, ts = time_graph(lambda: G.hull_labels(parts.labels, table=table), reps)
+    ht = G.hull_labels(parts.labels, table=table)
+    box = table.bbox.to(torch.int64)
+    vertices = ht.hull[..., 0].clamp(min=0).to(torch.int64)
+    res = {"measure_labels_ms": measure_ms, "shape_labels_ms": shape_ms, "hull_labels_ms": hull_ms, "hull_labels_ms_all": ts,
+           "hull_over_measure_plus_shape": hull_ms / (measure_ms + shape_ms), "rows_max": cap, "objects": int((table.area > 0).sum()),
+           "too_large": int(ht.too_large().sum()), "foreground_pixels": int(masks.sum()),
+           "box_area_sum": int(((box[..., 2] - box[..., 0]) * (box[..., 3] - box[..., 1])).sum()),
+           "vertices_max": int(vertices.max()), "vertices_squared_sum": int((vertices * vertices).sum())}
+    ok = True
+    labels = parts.labels.cpu().numpy()
+    for i in range(min(host_maps, len(masks))):
+        ok &= bool(np.array_equal(ht.hull[i].cpu().numpy(), HR.hull_labels(labels[i], cap)["hull"][0]))
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
+def seeded_main(case_fn, args):
+    """case_fn on ``regions.split`` of both mask sets at about 1 and about 10 seeds per component"""
     dev = torch.device("cuda:0")
     res = {}
     for name, masks in mask_sets():
         lab = G.label(torch.from_numpy(masks).to(dev)).cpu().numpy()
         for per in (1, 10):
             pts, off = seeds_in_components(lab, per, seed=per)
-            res[f"{name}.seeds{per}"] = shape_case(f"{name}.seeds{per}", masks, pts, off, args.reps, args.host_maps, dev)
+            res[f"{name}.seeds{per}"] = case_fn(f"{name}.seeds{per}", masks, pts, off, args.reps, args.host_maps, dev)
     return res
 
 
@@ -248,9 +282,12 @@ def main():
     ap.add_argument("--measure", action="store_true", help="time regions.measure next to regions.label instead")
     ap.add_argument("--split", action="store_true", help="time regions.split + measure_labels next to label + measure instead")
     ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
+    ap.add_argument("--hull", action="store_true", help="time regions.hull_labels next to measure_labels + shape_labels instead")
     args = ap.parse_args()
-    if args.shape:
-        res = shape_main(args)
+    if args.hull:
+        res = seeded_main(hull_case, args)
+    elif args.shape:
+        res = seeded_main(shape_case, args)
     elif args.split:
         res = split_main(args)
     elif args.measure:
