@@ -158,6 +158,11 @@ _SIGNATURES = {
     "cs_detect_edt_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cs_detect_edt_sq": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_detect_edt_smooth": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "cs_morph_max_site_width": (c_int, []),
+    "cs_morph_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "cs_morph_nearest": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cs_morph_binary": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "cs_morph_expand_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_regions_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_label": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_regions_areas": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

@@ -262,32 +262,43 @@ def detect_slides(slides, model, device=None, **kwargs):
         yield detect_slide(image_u8, model, device, **kwargs)
 
 
-def _cleaned_batch(model, x, threshold, mo, ho, want_counts, zero_empty):
+def _opened(classes, opening_radius):
+    """``morph.binary_opening(classes, opening_radius, border_value=0)`` when the radius is positive, else ``classes`` itself"""
+    if not opening_radius:
+        return classes
+    from . import morph as M
+    return M.binary_opening(classes, opening_radius, border_value=0)
+
+
+def _cleaned_batch(model, x, threshold, mo, ho, want_counts, zero_empty, opening_radius=0):
     """test_seg.py:515-527 for one batch on the device: ``_segment_batch`` -> (probs fp32 [n, H, W], cleaned classes bool [n, H, W],
-    reg)"""
+    reg).  A positive ``opening_radius`` opens the thresholded masks by that disk before the clean-up."""
     from . import regions as Rg
     probs, reg = _segment_batch(model, x, want_counts, zero_empty)
-    classes = Rg.threshold(probs, threshold)
+    classes = _opened(Rg.threshold(probs, threshold), opening_radius)
     return probs, Rg.remove_small_regions(classes, mo, ho, out=classes), reg
 
 
-def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False):
+def segment_classes(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, opening_radius=0):
     """Cleaned binary masks per image (test_seg.py:515-527): segment-mode forward, softmax channel 1, ``> threshold`` (compared in
     float32, as numpy does for a float32 map), ``remove_small_regions(., 300, 100)``.  With reg_limit the map of an image whose
-    image-mode count rint(reg) is 0 is zeroed first (:518-524; the model is set back to segment mode afterwards).  Returns a device
-    ``torch.bool`` tensor [len(dataset), H, W], ready for ``metrics.dice_coef``."""
+    image-mode count rint(reg) is 0 is zeroed first (:518-524; the model is set back to segment mode afterwards).  A positive
+    ``opening_radius`` runs ``morph.binary_opening(., opening_radius, border_value=0)`` between the threshold and the clean-up (not
+    in the reference; 0, the default, reaches none of it).  Returns a device ``torch.bool`` tensor [len(dataset), H, W], ready for
+    ``metrics.dice_coef``."""
     from . import regions as Rg
+    _check_opening("segment_classes", opening_radius)
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
     model.eval()
     out = []
     with torch.no_grad():
         for i, data in enumerate(tqdm(loader, desc="image segmenting")):
-            out.append(_cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)[1])
+            out.append(_cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit, opening_radius)[1])
     return torch.cat(out) if out else torch.zeros((0,), dtype=torch.bool, device=device)
 
 
 def measure_cells(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, connectivity=1,
-                  max_regions=None, shape=False, hull=False):
+                  max_regions=None, shape=False, hull=False, opening_radius=0):
     """One row per segmented cell: the per-batch body of ``segment_classes``, then ``regions.measure`` of the cleaned masks with
     ``detect.quantize`` of the probabilities (uint8 ``trunc(255 p)``) as the intensity.  Returns the ``RegionTable.per_image``
     dicts of all batches in dataset order (area, bbox, centroid, intensity_sum / _mean / _max per cell).  With ``max_regions``
@@ -296,15 +307,17 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     values, plus moments, tallies, central_moments, axis_lengths, eccentricity, orientation, perimeter, equivalent_diameter, extent
     and circularity per cell.  ``hull=True`` adds the columns of ``HullTable.per_image`` (hull, convex_area, solidity,
     feret_diameter_max, feret_diameter_min, n_vertices, too_large) in the same way; with both, every batch is labelled and measured
-    once and ``regions.shape_labels`` and ``regions.hull_labels`` share that one ``RegionTable``."""
+    once and ``regions.shape_labels`` and ``regions.hull_labels`` share that one ``RegionTable``.  ``opening_radius`` as in
+    ``segment_classes``."""
     from . import detect as D
     from . import regions as Rg
+    _check_opening("measure_cells", opening_radius)
     mo, ho = Rg._check_size(min_object_size, "min_object_size"), Rg._check_size(hole_area_threshold, "hole_area_threshold")
     model.eval()
     tables = []
     with torch.no_grad():
         for data in tqdm(loader, desc="cell measuring"):
-            probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit)
+            probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit, opening_radius)
             if hull:                                                      # label and measure once; both tables hang on that one
                 lab = Rg.label(classes, connectivity)
                 table = Rg.measure_labels(lab, intensity=D.quantize(probs), max_regions=max_regions)
@@ -323,37 +336,52 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     return out
 
 
-def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None):
-    """One row per cell of a stitched uint8 [H, W] map such as ``SlideResult.mask``: foreground = ``mask_u8 > thr_u8``, cleaned by
+def measure_slide(mask_u8, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None, opening_radius=0):
+    """One row per cell of a stitched uint8 [H, W] map such as ``SlideResult.mask``: foreground = ``mask_u8 > thr_u8``, opened by the
+    disk of ``opening_radius`` when that is positive (``morph.binary_opening``, ``border_value=0``), cleaned by
     ``remove_small_regions``, measured with the map itself as the intensity -> the one-image ``RegionTable`` (device tensors)."""
     from . import regions as Rg
-    t, fg = _slide_foreground("measure_slide", mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity)
+    t, fg = _slide_foreground("measure_slide", mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity, opening_radius)
     return Rg.measure(fg, intensity=t, connectivity=connectivity, max_regions=max_regions)
 
 
-def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity):
-    """a stitched uint8 [H, W] map -> (the map on the device, its cleaned foreground ``map > thr_u8`` as device bool)"""
+def _check_opening(what, opening_radius):
+    """the argument errors of ``opening_radius`` under the caller's name, before the model runs"""
+    from .score import radius_squared
+    try:
+        radius_squared(opening_radius)
+    except (TypeError, ValueError) as e:
+        raise type(e)(f"{what}: opening_radius: {e}") from None
+
+
+def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshold, connectivity, opening_radius=0):
+    """a stitched uint8 [H, W] map -> (the map on the device, its cleaned foreground ``map > thr_u8`` as device bool, opened first
+    when ``opening_radius`` is positive)"""
     from . import regions as Rg
+    _check_opening(what, opening_radius)
     if isinstance(thr_u8, bool) or int(thr_u8) != thr_u8 or not 0 <= thr_u8 <= 255:
         raise ValueError(f"{what}: thr_u8 must be an integer in [0, 255], got {thr_u8!r}")
     try:
         t = _images(mask_u8, what, torch.uint8, "a uint8 map, got {}", ranks=(2,), to_device=True).contiguous()
     except (TypeError, ValueError):                                         # one message, one type, whatever is wrong with the map
         raise TypeError(f"{what}: expected a uint8 [H, W] map") from None
-    fg = t > int(thr_u8)
+    fg = _opened(t > int(thr_u8), opening_radius)
     return t, Rg.remove_small_regions(fg, min_object_size, hole_area_threshold, connectivity, out=fg)
 
 
-def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None):
+def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None,
+                        opening_radius=0):
     """One row per DETECTED cell of a ``SlideResult``: ``measure_slide``'s thresholding and clean-up of ``result.mask``, then
     ``regions.split`` of the foreground at ``result.points`` and ``regions.measure_labels`` with the map as the intensity ->
     ``(RegionTable, SplitResult)`` of one image.  Row k is ``result.points[k]`` (all zero where the point is not live: on the
     background after the clean-up, or a second point on one pixel); the rows from ``len(result.points)`` on are cells that no
-    detection claimed.  ``max_regions`` as in ``measure_slide``: an int means no synchronisation."""
+    detection claimed.  ``max_regions`` and ``opening_radius`` as in ``measure_slide``: an int ``max_regions`` means no
+    synchronisation."""
     from . import regions as Rg
     if not isinstance(result, SlideResult):
         raise TypeError("measure_slide_cells: expected the SlideResult of detect_slide")
-    t, fg = _slide_foreground("measure_slide_cells", result.mask, thr_u8, min_object_size, hole_area_threshold, connectivity)
+    t, fg = _slide_foreground("measure_slide_cells", result.mask, thr_u8, min_object_size, hole_area_threshold, connectivity,
+                              opening_radius)
     pts = np.asarray(result.points, np.int64).reshape(-1, 2)
     parts = Rg.split(fg, pts, connectivity=connectivity)
     return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts

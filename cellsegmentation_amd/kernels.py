@@ -1176,6 +1176,61 @@ def detect_edt_smooth(src, thr=10):
     return _detect_edt(src, thr, True)
 
 
+# ---------------------------------------------------------------- nearest-site transform and disk morphology (csrc/morph.hip; morph.py
+# is the public API)
+def morph_max_site_width():
+    """the widest row the calls that return or follow a site take (a row of packed words has to fit the LDS)"""
+    return _lib.load().cs_morph_max_site_width()
+
+
+def morph_workspace(N, H, W, device):
+    """the caller-owned scratch of one cs_morph_* call on [N,H,W] (reusable by later calls of the same shape)"""
+    return _workspace(_lib.load().cs_morph_workspace, device,
+                      f"morph: a call takes 0 < N <= 65535 images with H^2 + W^2 < 2^31, got {(N, H, W)}", N, H, W)
+
+
+def _morph_args(x, dtypes, ws):
+    if x.dtype not in dtypes or x.dim() != 3:
+        raise TypeError(f"morph kernels read [N,H,W] of {' or '.join(str(d) for d in dtypes)}, got {x.dtype} {tuple(x.shape)}")
+    N, H, W = x.shape
+    if ws is None:
+        ws = morph_workspace(N, H, W, x.device)
+    return N, H, W, ws
+
+
+def morph_nearest(src, background=False, d2=None, site=None, ws=None):
+    """src uint8 [N,H,W] (sites: != 0, or == 0 with ``background``) or int32 labels (sites: != 0) -> (d2, site) int32 [N,H,W]: the
+    exact squared distance to the nearest site and its flat index row W + col, the lowest index among equally near sites; both -1
+    in an image without a site."""
+    N, H, W, ws = _morph_args(src, (torch.uint8, torch.int32), ws)
+    t = _regions_outputs("morph_nearest", {"d2": ((N, H, W), torch.int32), "site": ((N, H, W), torch.int32)}, {"d2": d2, "site": site},
+                         src.device)
+    _lib.check(_lib.load().cs_morph_nearest(_p(src), int(src.dtype == torch.int32), int(bool(background)), N, H, W, _p(t["d2"]),
+                                            _p(t["site"]), _p(ws), ws.numel(), _stream()), "morph_nearest")
+    return t["d2"], t["site"]
+
+
+def morph_binary(mask, erode, r2, outside_is_site=False, out=None, ws=None):
+    """mask uint8 [N,H,W] -> uint8 0/1: ``D2 to the nearest nonzero pixel <= r2`` (dilation), or with ``erode`` ``mask != 0 and D2 to
+    the nearest zero pixel > r2``; with ``outside_is_site`` the pixels beyond the edge count as nonzero / zero respectively."""
+    N, H, W, ws = _morph_args(mask, (torch.uint8,), ws)
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=mask.device)
+    _lib.check(_lib.load().cs_morph_binary(_p(mask), N, H, W, int(bool(erode)), int(r2), int(bool(outside_is_site)), _p(out), _p(ws),
+                                           ws.numel(), _stream()), "morph_binary")
+    return out
+
+
+def morph_expand_labels(labels, r2, out=None, ws=None):
+    """labels int32 [N,H,W] -> int32: a zero pixel whose nearest nonzero pixel lies within r2 takes that pixel's label"""
+    N, H, W, ws = _morph_args(labels, (torch.int32,), ws)
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.int32, device=labels.device)
+    _lib.check(_lib.load().cs_morph_expand_labels(_p(labels), N, H, W, int(r2), _p(out), _p(ws), ws.numel(), _stream()),
+               "morph_expand_labels")
+    return out
+
+
 # ---------------------------------------------------------------- small-region clean-up (csrc/regions.hip; regions.py is the public API)
 def regions_workspace(N, H, W, device):
     """the caller-owned scratch of one cs_regions_* call on [N,H,W] (reusable by later calls of the same shape)"""

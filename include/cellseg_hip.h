@@ -574,6 +574,32 @@ int cs_detect_edt_sq(const void* src, int src_is_f32, int N, int H, int W, int t
 int cs_detect_edt_smooth(const void* src, int src_is_f32, int N, int H, int W, int thr, uint8_t* dst, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- nearest-site transform, exact disk morphology and label expansion (csrc/morph.hip) --------------------------------------
+ * N images [N][H][W] that share nothing; 0 < N <= 65535 and H^2 + W^2 < 2^31 per call.  A SITE is a pixel selected by a predicate
+ * on the input.  Every pixel is given THE NEAREST SITE, AND AMONG EQUALLY NEAR SITES THE ONE WITH THE LOWEST ROW-MAJOR INDEX; d2 is
+ * the exact squared Euclidean distance to it.  Integer work only: bit-exact and independent of launch order; three launches per
+ * call, fixed by the shape, no host synchronisation.  Every call takes a 16-byte aligned workspace of cs_morph_workspace(N, H, W)
+ * bytes (0 for sizes a call would refuse).  The calls that return or follow a site stage 4 bytes per pixel of a row in LDS and
+ * refuse W > cs_morph_max_site_width() = 40960; cs_morph_binary stages 2 bytes and takes every W.
+ * cs_morph_nearest      : sites = src != 0 (uint8 [N][H][W]; == 0 with background; int32 with src_is_labels, where background
+ *                         must be 0).  d2 int32 [N][H][W] and / or site int32 [N][H][W] = row W + col of the nearest site within
+ *                         the image (either may be NULL, not both); both -1 everywhere in an image without a site.  The search of
+ *                         a pixel runs over offsets up to sqrt(d2): sparse sites in a wide image are its worst case.
+ * cs_morph_binary       : erode = 0: out = (d2 to the nearest nonzero pixel) <= r2, the dilation by the disk dx^2 + dy^2 <= r2;
+ *                         erode = 1: out = mask != 0 && (d2 to the nearest zero pixel) > r2, the erosion by it.  With
+ *                         outside_is_site the pixels beyond the image edge count as sites (nonzero for the dilation, zero for the
+ *                         erosion).  uint8 0 / 1 [N][H][W]; out must not overlap mask.  O(sqrt(r2)) per pixel.
+ * cs_morph_expand_labels: out = labels != 0 ? labels : (d2 <= r2 ? labels[site] : 0) for the sites labels != 0, int32 [N][H][W];
+ *                         out must not overlap labels.  O(sqrt(r2)) per pixel. */
+int cs_morph_max_site_width(void);
+size_t cs_morph_workspace(int N, int H, int W);
+int cs_morph_nearest(const void* src, int src_is_labels, int background, int N, int H, int W, int32_t* d2, int32_t* site,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int cs_morph_binary(const uint8_t* mask, int N, int H, int W, int erode, int r2, int outside_is_site, uint8_t* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int cs_morph_expand_labels(const int32_t* labels, int N, int H, int W, int r2, int32_t* out, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- small-region clean-up of binary masks (utils/image_processing.py:14-17 remove_small_regions; csrc/regions.hip) ---------
  * Masks are uint8 [N][H][W], non-zero = foreground, N images that share nothing; 0 < N <= 65535 and N H W < 2^31 per call.
  * connectivity 1 = 4-neighbourhood, 2 = 8-neighbourhood, for the foreground and the background alike.  Integer work only:

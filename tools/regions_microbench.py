@@ -30,6 +30,14 @@ the sum of the bounding-box areas and the sum of the squared vertex counts -- an
 tests/hull_ref.py.
 
     python tools/regions_microbench.py --hull [--reps 5] [--host-maps 2] [--json PATH]
+
+--morph times ``morph.binary_opening`` at radii 1, 2 and 5, ``morph.expand_labels`` at 4 (of ``regions.label`` of the masks) and
+``morph.nearest_sites`` (towards the background) next to ``detect.distance_transform_sq`` on the same two mask sets, graph replays
+again, and checks the first ``--host-maps`` maps against scipy: ``binary_opening`` by the disk, the squared
+``distance_transform_edt``, and for the expansion the filled set from scipy's distances and the labels from tests/morph_ref.py
+(scipy fixes no tie rule).
+
+    python tools/regions_microbench.py --morph [--reps 5] [--host-maps 2] [--json PATH]
 """
 import argparse
 import json
@@ -262,6 +270,45 @@ def hull_case(name, masks, pts, off, reps, host_maps, dev):
     return res
 
 
+def morph_case(name, masks, reps, host_maps, dev):
+    from scipy import ndimage
+    import morph_ref as MR
+    from cellsegmentation_amd import detect as D
+    from cellsegmentation_amd import morph as M
+    d = torch.from_numpy(masks).to(dev)
+    u8 = d.to(torch.uint8) * 255                                          # the same maps as the EDT reads them: foreground = u8 > 10
+    lab = G.label(d)
+    res = {"foreground_fraction": float(masks.mean())}
+    for r in (1, 2, 5):
+        res[f"opening_r{r}_ms"], _ = time_graph(lambda: M.binary_opening(d, r), reps)
+    res["expand_labels_r4_ms"], _ = time_graph(lambda: M.expand_labels(lab, 4), reps)
+    res["nearest_sites_ms"], res["nearest_sites_ms_all"] = time_graph(lambda: M.nearest_sites(d, background=True), reps)
+    res["distance_transform_sq_ms"], _ = time_graph(lambda: D.distance_transform_sq(u8), reps)
+    opened = {r: M.binary_opening(d, r).cpu().numpy() for r in (1, 2, 5)}
+    grown = M.expand_labels(lab, 4).cpu().numpy()
+    d2 = M.nearest_sites(d, background=True)[0].cpu().numpy()
+    ok = bool(np.array_equal(np.where(d2 < 0, -1, d2), D.distance_transform_sq(u8).cpu().numpy()))
+    labels = lab.cpu().numpy()
+    t0 = time.perf_counter()
+    for i in range(min(host_maps, len(masks))):
+        for r in (1, 2, 5):
+            ok &= bool(np.array_equal(opened[r][i], ndimage.binary_opening(masks[i], structure=MR.disk(r * r))))
+        if not masks[i].all():
+            ok &= bool(np.array_equal(d2[i], np.rint(ndimage.distance_transform_edt(masks[i]) ** 2).astype(np.int32)))
+        if masks[i].any():
+            to_label = np.rint(ndimage.distance_transform_edt(~masks[i]) ** 2)
+            ok &= bool(np.array_equal(grown[i] != 0, to_label <= 16))
+        ok &= bool(np.array_equal(grown[i], MR.expand_labels(labels[i], 16)))
+    res.update(host_ms=(time.perf_counter() - t0) * 1e3, equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
+def morph_main(args):
+    dev = torch.device("cuda:0")
+    return {name: morph_case(name, masks, args.reps, args.host_maps, dev) for name, masks in mask_sets()}
+
+
 def seeded_main(case_fn, args):
     """case_fn on ``regions.split`` of both mask sets at about 1 and about 10 seeds per component"""
     dev = torch.device("cuda:0")
@@ -283,8 +330,11 @@ def main():
     ap.add_argument("--split", action="store_true", help="time regions.split + measure_labels next to label + measure instead")
     ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
     ap.add_argument("--hull", action="store_true", help="time regions.hull_labels next to measure_labels + shape_labels instead")
+    ap.add_argument("--morph", action="store_true", help="time morph.binary_opening / expand_labels / nearest_sites next to the EDT instead")
     args = ap.parse_args()
-    if args.hull:
+    if args.morph:
+        res = morph_main(args)
+    elif args.hull:
         res = seeded_main(hull_case, args)
     elif args.shape:
         res = seeded_main(shape_case, args)
