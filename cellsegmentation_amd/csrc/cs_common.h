@@ -196,6 +196,16 @@ template <typename F> static inline int cs_launch_typed(int dtype, const char* n
 }
 
 static inline int cs_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+// byte count rounded up to the 16-byte granule of the workspace carve-ups
+static inline size_t cs_align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// uint8 level of a probability: trunc(255 p) in fp32, clamped to [0, 255] (cs_detect_quantize; the blur, the stitching and the distance
+// transform quantise fp32 sources with it on the way in)
+__device__ __forceinline__ uint8_t quant(float p) {
+    float v = 255.0f * p;
+    v = fminf(fmaxf(v, 0.f), 255.f);
+    return (uint8_t)(int)v;
+}
 
 // Dynamic LDS beyond 64 KiB has to be allowed per kernel AND per device (hipFuncSetAttribute applies to the device that is current
 // at the call).  cs_api.cpp keeps the (device, function) table under a mutex; `limit` is the byte count to allow (<= 160 KiB).

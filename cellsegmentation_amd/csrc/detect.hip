@@ -10,10 +10,7 @@
 //   stitch    patches written into a zeroed whole-image mask, the highest patch index winning where patches overlap
 //   streamed  the same mask built batch by batch: softmax channel + quantise of a batch of logits written in place in one launch,
 //             the owner of a pixel decided from the batch's corners (no per-pixel state); earlier batches are overwritten in stream order
-//   edt       method="distancetransform" in place of the blur: foreground = u8 > thr_for_dt; exact squared Euclidean distance to the
-//             nearest background pixel (int32; -1 everywhere in a map without background): column sweep, then per row the lower
-//             envelope of (x - x')^2 + g[x']^2 by an outward search that stops at dx^2 >= best; per-map maximum M by integer
-//             atomicMax; smoothed = 255 sqrt(D2 / M) rounded half to even, decided by 4 255^2 D2 <> (2k + 1)^2 M in int64
+//   distance  method="distancetransform" puts the exact distance transform of morph.hip in the blur's place; the rest is unchanged
 // Every step is integer arithmetic or one correctly rounded fp64 operation, so the result does not depend on launch order.
 #include "cs_common.h"
 #include "cs_block.h"
@@ -38,12 +35,6 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     i %= p;
     if (i < 0) i += p;
     return i >= n ? p - i : i;
-}
-
-__device__ __forceinline__ uint8_t quant(float p) {
-    float v = 255.0f * p;
-    v = fminf(fmaxf(v, 0.f), 255.f);
-    return (uint8_t)(int)v;
 }
 
 __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__ p, long long n, uint8_t* __restrict__ out) {
@@ -540,144 +531,11 @@ __global__ __launch_bounds__(256) void cluster_emit_kernel(const int32_t* __rest
     }
 }
 
-// ---- exact Euclidean distance transform ---------------------------------------------------------------------------------------------
-constexpr int32_t kInfG = 0x7fffffff;   // vertical distance of a column without background
-constexpr int kInfG16 = 0xffff;         // the same in the LDS row (H < 46341, so every real distance fits 16 bits)
-
-// st[0..N) = per-map maximum of D2 (starts at -1), st[N..2N) = "the map has a background pixel"
-__global__ __launch_bounds__(256) void edt_init_kernel(int32_t* __restrict__ st, int N) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < N) {
-        st[i] = -1;
-        st[N + i] = 0;
-    }
-}
-
-// One thread per column (a wave reads 64 adjacent pixels of a row): g[y][x] = distance to the nearest background pixel of the column,
-// kInfG in a column without one.  Sweep down, then up over what the sweep down wrote.
-template <bool F32>
-__global__ __launch_bounds__(64) void edt_column_kernel(const void* __restrict__ src, int H, int W, int thr, int32_t* __restrict__ g,
-                                                        int32_t* __restrict__ has_bg) {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const long long img = (long long)blockIdx.y * H * W;
-    bool seen = false;
-    if (x < W) {
-        const float* sf = reinterpret_cast<const float*>(src) + img + x;
-        const uint8_t* su = reinterpret_cast<const uint8_t*>(src) + img + x;
-        int32_t* col = g + img + x;
-        int32_t d = kInfG;
-#pragma unroll 8
-        for (int y = 0; y < H; ++y) {
-            const int v = F32 ? (int)quant(sf[(long long)y * W]) : (int)su[(long long)y * W];
-            d = v > thr ? (d == kInfG ? kInfG : d + 1) : 0;
-            col[(long long)y * W] = d;
-        }
-        seen = d != kInfG;                                     // once a background pixel is met, d stays finite
-        int32_t u = kInfG;
-#pragma unroll 8
-        for (int y = H - 1; y >= 0; --y) {
-            const int32_t down = col[(long long)y * W];
-            u = down == 0 ? 0 : (u == kInfG ? kInfG : u + 1);
-            if (u < down) col[(long long)y * W] = u;
-        }
-    }
-    if (__any(seen) && threadIdx.x == 0) atomicOr(has_bg + blockIdx.y, 1);
-}
-
-// One workgroup per row, in place: the row of g goes to LDS as 16-bit values, then every pixel searches outwards for
-// min (x - x')^2 + g[x']^2 and stops once dx^2 >= best (at most max(x, W - 1 - x) steps).  Every sum stays below H^2 + W^2 < 2^31.
-// A map without background gets -1; its maximum stays -1.
-__global__ __launch_bounds__(256) void edt_row_kernel(int32_t* __restrict__ d2, int H, int W, const int32_t* __restrict__ has_bg,
-                                                      int32_t* __restrict__ map_max) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char edt_lds[];
-    uint16_t* grow = reinterpret_cast<uint16_t*>(edt_lds);
-    __shared__ int wmax[4];
-    const int n = blockIdx.y;
-    int32_t* row = d2 + ((long long)n * H + blockIdx.x) * W;
-    if (!has_bg[n]) {
-        for (int x = threadIdx.x; x < W; x += blockDim.x) row[x] = -1;
-        return;
-    }
-    for (int x = threadIdx.x; x < W; x += blockDim.x) {
-        const int32_t gv = row[x];
-        grow[x] = (uint16_t)(gv == kInfG ? kInfG16 : gv);
-    }
-    __syncthreads();
-    int lmax = 0;
-    for (int x = threadIdx.x; x < W; x += blockDim.x) {
-        const int g0 = grow[x];
-        int best = g0 == kInfG16 ? 0x7fffffff : g0 * g0;
-        const int dmax = max(x, W - 1 - x);
-        for (int d = 1; d <= dmax && d * d < best; ++d) {
-            const int dd = d * d;
-            if (x - d >= 0) {
-                const int gl = grow[x - d];
-                if (gl != kInfG16) best = min(best, dd + gl * gl);
-            }
-            if (x + d < W) {
-                const int gr = grow[x + d];
-                if (gr != kInfG16) best = min(best, dd + gr * gr);
-            }
-        }
-        row[x] = best;
-        lmax = max(lmax, best);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lmax = max(lmax, __shfl_xor(lmax, off, 64));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = lmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) lmax = max(lmax, wmax[w]);
-        atomicMax(map_max + n, lmax);
-    }
-}
-
-// 255 sqrt(D2 / M) rounded half to even: the float estimate is moved until (2k - 1)^2 M <= 4 255^2 D2 <= (2k + 1)^2 M holds in
-// int64 (all products < 2^50); equality on either side is a tie between two integers and goes to the even one.
-__device__ __forceinline__ uint8_t edt_norm(int32_t d2, int32_t M) {
-    if (M <= 0 || d2 <= 0) return 0;
-    const long long A = 4LL * 255 * 255 * d2;
-    int k = (int)(255.0f * sqrtf((float)d2 / (float)M) + 0.5f);
-    k = min(max(k, 0), 255);
-    while (k > 0 && A < (long long)(2 * k - 1) * (2 * k - 1) * M) --k;
-    while (A > (long long)(2 * k + 1) * (2 * k + 1) * M) ++k;
-    if (A == (long long)(2 * k + 1) * (2 * k + 1) * M) return (uint8_t)((k & 1) ? k + 1 : k);
-    if (k > 0 && A == (long long)(2 * k - 1) * (2 * k - 1) * M) return (uint8_t)((k & 1) ? k - 1 : k);
-    return (uint8_t)k;
-}
-
-// four consecutive pixels of the flat [N H W] range per thread; a group may straddle maps (H W need not be a multiple of 4)
-__global__ __launch_bounds__(256) void edt_normalise_kernel(const int32_t* __restrict__ d2, const int32_t* __restrict__ map_max, long long HW,
-                                                            long long total, uint8_t* __restrict__ out) {
-    const long long t4 = total >> 2;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < t4; i += (long long)gridDim.x * 256) {
-        const int4 v = reinterpret_cast<const int4*>(d2)[i];
-        long long n = (4 * i) / HW, rem = 4 * i - n * HW;
-        const int32_t dv[4] = {v.x, v.y, v.z, v.w};
-        uint32_t o = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            while (rem >= HW) {
-                rem -= HW;
-                ++n;
-            }
-            o |= (uint32_t)edt_norm(dv[q], map_max[n]) << (8 * q);
-            ++rem;
-        }
-        reinterpret_cast<uint32_t*>(out)[i] = o;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (total & 3)) {
-        const long long i = t4 * 4 + threadIdx.x;
-        out[i] = edt_norm(d2[i], map_max[i / HW]);
-    }
-}
-
 inline unsigned grid_for(long long n) {
     long long b = (n + 255) / 256;
     if (b < 1) b = 1;
     return (unsigned)(b > 8192 ? 8192 : b);
 }
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 bool taps_ok(const int32_t* t, int k) {
     if (!t || k < 1 || k > 2 * kMaxHalf + 1 || (k & 1) == 0) return false;
@@ -799,7 +657,7 @@ extern "C" int cs_detect_meanshift(const uint8_t* blurred, int N, int H, int W, 
 // n_clu (int32 N), state (int32 2)
 extern "C" size_t cs_detect_cluster_workspace(int N, int cap) {
     const size_t t = (size_t)N * cap;
-    return align16(t * 4) * 3 + align16(t * 8) + align16(t * 4) + align16(t * 8) + align16(t * 24) + align16((size_t)N * 4) + 16;
+    return cs_align16(t * 4) * 3 + cs_align16(t * 8) + cs_align16(t * 4) + cs_align16(t * 8) + cs_align16(t * 24) + cs_align16((size_t)N * 4) + 16;
 }
 
 extern "C" int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N, int cap, double eps, const uint8_t* blurred, int H, int W,
@@ -813,14 +671,14 @@ extern "C" int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t t = (size_t)N * cap;
     unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-    int32_t* lab = reinterpret_cast<int32_t*>(w);            w += align16(t * 4);
-    int32_t* cid = reinterpret_cast<int32_t*>(w);            w += align16(t * 4);
-    int32_t* wgt = reinterpret_cast<int32_t*>(w);            w += align16(t * 4);
-    int32_t* cent = reinterpret_cast<int32_t*>(w);           w += align16(t * 8);
-    float* key = reinterpret_cast<float*>(w);                w += align16(t * 4);
-    int64_t* order = reinterpret_cast<int64_t*>(w);          w += align16(t * 8);
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(w); w += align16(t * 24);
-    int32_t* n_clu = reinterpret_cast<int32_t*>(w);          w += align16((size_t)N * 4);
+    int32_t* lab = reinterpret_cast<int32_t*>(w);            w += cs_align16(t * 4);
+    int32_t* cid = reinterpret_cast<int32_t*>(w);            w += cs_align16(t * 4);
+    int32_t* wgt = reinterpret_cast<int32_t*>(w);            w += cs_align16(t * 4);
+    int32_t* cent = reinterpret_cast<int32_t*>(w);           w += cs_align16(t * 8);
+    float* key = reinterpret_cast<float*>(w);                w += cs_align16(t * 4);
+    int64_t* order = reinterpret_cast<int64_t*>(w);          w += cs_align16(t * 8);
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(w); w += cs_align16(t * 24);
+    int32_t* n_clu = reinterpret_cast<int32_t*>(w);          w += cs_align16((size_t)N * 4);
     int32_t* state = reinterpret_cast<int32_t*>(w);
     const double eps2 = eps * eps;
     if (cap <= kLdsPts && !force_global) {
@@ -867,61 +725,6 @@ extern "C" int cs_detect_cluster(const int32_t* pts, const int32_t* n_pts, int N
     if (rc != CS_OK) return rc;
     hipLaunchKernelGGL(cluster_emit_kernel, dim3(grid_for((long long)t)), dim3(256), 0, st, n_clu, N, cap, out_off, order, cent, wgt, out_pts,
                        out_w);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-
-// workspace: st (int32 2 N: per-map maximum, has-background flag), then for the smoothed form D2 (int32 N H W)
-extern "C" size_t cs_detect_edt_workspace(int N, int H, int W, int smooth) {
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || (long long)H * H + (long long)W * W >= (1LL << 31)) return 0;
-    return align16((size_t)N * 8) + (smooth ? align16((size_t)N * H * W * 4) : 0);
-}
-
-namespace {
-int edt_sq_launch(const void* src, int src_is_f32, int N, int H, int W, int thr, int32_t* d2, int32_t* st, hipStream_t s) {
-    hipLaunchKernelGGL(edt_init_kernel, dim3(cs_ceil_div(N, 256)), dim3(256), 0, s, st, N);
-    CS_LAUNCH_CHECK();
-    const dim3 cgrid(cs_ceil_div(W, 64), N);
-    if (src_is_f32)
-        hipLaunchKernelGGL(edt_column_kernel<true>, cgrid, dim3(64), 0, s, src, H, W, thr, d2, st + N);
-    else
-        hipLaunchKernelGGL(edt_column_kernel<false>, cgrid, dim3(64), 0, s, src, H, W, thr, d2, st + N);
-    CS_LAUNCH_CHECK();
-    const size_t lds = align16((size_t)W * 2);
-    if (!cs_allow_dynamic_lds_(reinterpret_cast<const void*>(edt_row_kernel), lds, 96 * 1024)) return CS_ERR_LAUNCH;
-    const int threads = W >= 256 ? 256 : cs_ceil_div(W, 64) * 64;
-    hipLaunchKernelGGL(edt_row_kernel, dim3(H, N), dim3(threads), lds, s, d2, H, W, st + N, st);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
-}
-}  // namespace
-
-extern "C" int cs_detect_edt_sq(const void* src, int src_is_f32, int N, int H, int W, int thr, int32_t* d2, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    CS_CHECK_ARG(src && d2 && workspace, "detect_edt_sq: NULL argument");
-    const size_t need = cs_detect_edt_workspace(N, H, W, 0);
-    CS_CHECK_ARG(need > 0, "detect_edt_sq: needs 0 < N <= 65535 maps with H^2 + W^2 < 2^31");
-    CS_CHECK_ARG(workspace_bytes >= need, "detect_edt_sq: workspace too small");
-    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(d2) & 3) == 0 &&
-                     (!src_is_f32 || (reinterpret_cast<uintptr_t>(src) & 3) == 0), "detect_edt_sq: misaligned buffers");
-    return edt_sq_launch(src, src_is_f32, N, H, W, thr, d2, reinterpret_cast<int32_t*>(workspace), reinterpret_cast<hipStream_t>(stream));
-}
-
-extern "C" int cs_detect_edt_smooth(const void* src, int src_is_f32, int N, int H, int W, int thr, uint8_t* dst, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-    CS_CHECK_ARG(src && dst && workspace, "detect_edt_smooth: NULL argument");
-    const size_t need = cs_detect_edt_workspace(N, H, W, 1);
-    CS_CHECK_ARG(need > 0, "detect_edt_smooth: needs 0 < N <= 65535 maps with H^2 + W^2 < 2^31");
-    CS_CHECK_ARG(workspace_bytes >= need, "detect_edt_smooth: workspace too small");
-    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0 &&
-                     (!src_is_f32 || (reinterpret_cast<uintptr_t>(src) & 3) == 0), "detect_edt_smooth: misaligned buffers");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int32_t* state = reinterpret_cast<int32_t*>(workspace);
-    int32_t* d2 = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(workspace) + align16((size_t)N * 8));
-    const int rc = edt_sq_launch(src, src_is_f32, N, H, W, thr, d2, state, st);
-    if (rc != CS_OK) return rc;
-    const long long HW = (long long)H * W, total = HW * N;
-    hipLaunchKernelGGL(edt_normalise_kernel, dim3(grid_for((total + 3) / 4)), dim3(256), 0, st, d2, state, HW, total, dst);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

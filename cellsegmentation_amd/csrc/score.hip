@@ -231,14 +231,12 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restri
     else block_path<false>(im, R, radius2, s_r, s_c, s_flag, s_key, s_sum, ws + flag0, counts);
 }
 
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace
 
 // workspace: the flag bits of the images with more than 4096 annotations, image n from word gt_off[n] / 32 + n on
 extern "C" size_t cs_score_workspace(int N, long long total_gt) {
     if (N <= 0 || N > 65535 || total_gt < 0) return 0;
-    return align16(((size_t)(total_gt >> 5) + (size_t)N + 1) * 4);
+    return cs_align16(((size_t)(total_gt >> 5) + (size_t)N + 1) * 4);
 }
 
 extern "C" int cs_score_points(const int64_t* hat, const int64_t* hat_off, const int32_t* hat_limit, const int32_t* gt,

@@ -1152,6 +1152,7 @@ def detect_cluster(pts, n_pts, eps, blurred, force_global=False):
     return out_pts, out_w, out_off
 
 
+# cs_detect_edt_* live in csrc/morph.hip: the distance transform shares the nearest-site transform's column pass and row search
 def _detect_edt(src, thr, smooth):
     N, H, W = src.shape
     lib = _lib.load()

@@ -516,7 +516,8 @@ int cs_paint_tile_masks(const int64_t* selected, long long n_selected, const int
 int cs_prune_excess(const int32_t* labels, long long n, int flag, long long n_excess, int64_t* kept, int64_t* kept_count,
                     void* stream);
 
-/* ---- cell localisation from segmentation probability maps (test_seg.py meanshift_cluster / cell_detect; csrc/detect.hip) ----
+/* ---- cell localisation from segmentation probability maps (test_seg.py meanshift_cluster / cell_detect; csrc/detect.hip;
+ * cs_detect_edt_*: csrc/morph.hip, on the column pass and row search of the nearest-site transform further down) ----
  * Every step is integer arithmetic or one correctly rounded fp64 operation: bit-exact and independent of launch order.
  * cs_detect_quantize : out[i] = (uint8) trunc(255.0f * probs[i]) (fp32, clamped to [0, 255]); probs 16-byte aligned.
  * cs_detect_blur     : separable integer Gaussian of N maps [N][H][W], BORDER_REFLECT_101.  src is fp32 probabilities

@@ -1,7 +1,7 @@
 """cellsegmentation_amd.morph on the GPU (csrc/morph.hip), bit-exact against the numpy restatement tests/morph_ref.py and the scipy
 vectors tests/golden/morph_vectors.npz: the nearest-site transform in both polarities, the four binary operations with both border
-values, label expansion, Pythagorean ties, adversarial maps, batching and input forms, repeatability, graph capture, and the
-``opening_radius`` option of the segmentation pipeline."""
+values, label expansion, the distance transform of detect on the same core, Pythagorean ties, adversarial maps, batching and input
+forms, repeatability, graph capture, and the ``opening_radius`` option of the segmentation pipeline."""
 import itertools
 import os
 import sys
@@ -13,11 +13,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import detect_ref as DR  # noqa: E402
 import edt_ref as E  # noqa: E402
 import morph_ref as MR  # noqa: E402
 import regions_ref as RR  # noqa: E402
+from cellsegmentation_amd import detect as D  # noqa: E402
+from cellsegmentation_amd import kernels as K  # noqa: E402
 from cellsegmentation_amd import morph as M  # noqa: E402
 from cellsegmentation_amd import regions as G  # noqa: E402
+from test_edt_gpu import three_maps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "morph_vectors.npz"), allow_pickle=False)
@@ -115,6 +119,39 @@ def test_expand_labels_bit_exact(dev, hw):
         assert np.array_equal(_np(got), want["expand", r2]), r2
     assert torch.equal(M.expand_labels(d, 5), M.expand_labels(d, radius_sq=25))
     assert torch.equal(M.expand_labels(d, 0), d)
+
+
+# ---- the distance transform of detect and the nearest-site transform share one core ---------------------------------------------------
+EDT_SHAPES = [(5, 3), (1, 70), (70, 1), (64, 16), (130, 97), (3, 33001)]
+_EDT_REF = {}
+
+
+def edt_ref(hw, thr):
+    """(uint8 maps: the three of test_edt_gpu and one all-foreground map, expected D2 by edt_ref alone), computed once"""
+    if (hw, thr) not in _EDT_REF:
+        maps = np.concatenate([three_maps(hw), np.full((1,) + hw, 255, np.uint8)])
+        want = np.stack([E.edt_sq(m, thr) for m in maps])
+        maps.setflags(write=False)
+        want.setflags(write=False)
+        _EDT_REF[hw, thr] = (maps, want)
+    return _EDT_REF[hw, thr]
+
+
+@pytest.mark.parametrize("thr", (10, 0, 254))
+@pytest.mark.parametrize("hw", EDT_SHAPES)
+def test_distance_transform_equals_nearest_sites_of_the_background(dev, hw, thr):
+    maps, want = edt_ref(hw, thr)
+    edt = _np(D.distance_transform_sq(torch.from_numpy(maps.copy()).to(dev), thr))
+    near = _np(M.nearest_sites(torch.from_numpy(maps > thr), background=True)[0])
+    assert np.array_equal(edt, near)
+    for n in range(len(maps)):
+        assert np.array_equal(edt[n], want[n]) and np.array_equal(near[n], want[n]), n
+    assert (edt[3] == -1).all() and (near[3] == -1).all()                               # all foreground: no site
+    if hw == (130, 97):                                                                 # the same maps as fp32 probabilities k / 255
+        p = maps.astype(np.float32) / np.float32(255)
+        assert np.array_equal(DR.quantize(p), maps)
+        f32 = _np(K.detect_edt_sq(torch.from_numpy(p).to(dev), thr))
+        assert np.array_equal(f32, edt) and np.array_equal(f32, want)
 
 
 # ---- Pythagorean ties ---------------------------------------------------------------------------------------------------------------
