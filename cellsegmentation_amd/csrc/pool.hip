@@ -189,8 +189,11 @@ __global__ __launch_bounds__(256) void gap_fwd_kernel(const T* __restrict__ x, f
                 const float mq = s_max[q][l][e];
                 const int iq = s_idx[q][l][e];
                 if (iq == 0x7fffffff) continue;
-                // first (smallest index) maximum wins ties, matching a sequential strict-> scan
-                if (bi == 0x7fffffff || mq > m || (mq == m && iq < bi)) { m = mq; bi = iq; }
+                // the result of ONE sequential scan under ATen's rule (take if strictly greater, or NaN), as the lanes scanned: a NaN
+                // maximum takes over from a finite one and among NaN maxima the last (largest index) wins; among finite maxima the
+                // first (smallest index) wins ties
+                const bool nq = mq != mq, nm = m != m;
+                if (bi == 0x7fffffff || (nq ? (!nm || iq > bi) : (!nm && (mq > m || (mq == m && iq < bi))))) { m = mq; bi = iq; }
             }
             feat[(long long)n * C + cg * 8 + e] = s / (float)HW + (with_max ? m : 0.f);
             if (amax) amax[(long long)n * C + cg * 8 + e] = bi;

@@ -296,7 +296,7 @@ int cs_colsum_partial(const void* g, int dtype, long long M, int C, float* parti
 /* ---- pooling --------------------------------------------------------------------------------
  * MaxPool2d(3, stride 2, pad 1) (resnet.py:114). */
 /* argmax (nullable, uint8 [N][P][Q][C]): window tap kh*3+kw of the first maximum in scan order
- * (ATen's max_pool2d_with_indices tie rule: strictly-greater replaces). */
+ * (ATen's max_pool2d_with_indices rule: strictly-greater replaces, and so does a NaN: the LAST NaN of a window). */
 int cs_maxpool3x3s2_fwd(const void* x, int dtype, void* y, uint8_t* argmax, int N, int H, int W, int C, int P, int Q,
                         void* stream);
 /* dx[n][iy][ix][c] = sum over the <=4 windows containing (iy,ix) whose argmax is this pixel of
@@ -305,7 +305,8 @@ int cs_maxpool3x3s2_fwd(const void* x, int dtype, void* y, uint8_t* argmax, int 
 int cs_maxpool3x3s2_bwd(const void* dy, const uint8_t* argmax, const void* y_mask, int dtype, void* dx, int N, int H,
                         int W, int C, int P, int Q, void* stream);
 /* AdaptiveAvgPool2d(1)+AdaptiveMaxPool2d(1) summed (resnet.py:266,274): feat[N][C] fp32,
- * argmax[N][C] int32 = first spatial index of the maximum.  with_max==0: average only (the squeeze of
+ * argmax[N][C] int32 = first spatial index of the maximum (of the LAST NaN where the map holds one: ATen's
+ * rule, as for the max pool above).  with_max==0: average only (the squeeze of
  * torchvision's SqueezeExcitation, efficientnet.py:107). */
 int cs_gap_avgmax_fwd(const void* x, int dtype, float* feat, int32_t* argmax, int N, int HW, int C, int with_max,
                       void* stream);
