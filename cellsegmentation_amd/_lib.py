@@ -174,6 +174,8 @@ _SIGNATURES = {
     "cs_regions_measure": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cs_regions_split_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cs_regions_split": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cs_regions_geodesic_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cs_regions_split_geodesic": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cs_regions_measure_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "cs_regions_edges_labels": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "cs_regions_shape_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -30,11 +30,15 @@
 //               seeds   one thread per point hangs the live seeds on a chain at their component's root
 //               number  the numbering trio over the roots that have no seed
 //               assign  every pixel walks the chain of its root; a wave whose foreground lanes share a root walks it as one
+//   geodesic  the same split with the distance measured along paths that stay inside the component (5-7 chamfer steps), so that
+//             every cell is connected: one 64-bit key (distance, seed) per pixel, lowered to its fixpoint by rounds of one launch
+//             each in which every 64 x 64 tile relaxes in LDS against a one-pixel halo; a byte per tile and round skips the tiles
+//             where nothing can change any more
 // Hooks only ever lower a label and a label is always an index of the same component, so the root of a component is its lowest
 // index whatever order the hooks land in; areas are integer sums.  The result does not depend on launch order.  Every union loop
 // lowers max(a, b) in each turn that does not end it, so it is bounded by the index range; nothing waits on another thread.
-// The number of launches depends on (N, H, W) only (for a split also on whether there is any point) and nothing synchronises with
-// the host.
+// The number of launches depends on (N, H, W) only (for a split also on whether there is any point, for a geodesic split also on
+// the number of rounds asked for) and nothing synchronises with the host.
 #include <limits.h>
 #include <stdio.h>
 #include "cs_common.h"
@@ -1184,10 +1188,11 @@ __global__ __launch_bounds__(256) void hausdorff_finish_kernel(Haus t) {
 // foreground pixel.  A live seed is pushed on the chain of its component: the root's slot of `head` (the spent cnt array) holds the
 // area (> 0) while the component has no seed and -(p + 1), p = the point on top of the chain, afterwards; rec[p] = (row, col, index
 // within the image, the next point of the chain or -1).  The order of a chain depends on the order the pushes land in; what the
-// assign pass takes from it, the minimum of (d2, index) over the chain, does not.
+// assign pass takes from it, the minimum of (d2, index) over the chain, does not.  keys (geodesic split, else NULL): a live seed also
+// lowers the key of its pixel to (0, index).
 __global__ __launch_bounds__(256) void seed_kernel(const uint8_t* __restrict__ m, int N, int H, int W, Seeds s,
                                                    const int32_t* __restrict__ lab, int32_t* __restrict__ head, int4* __restrict__ rec,
-                                                   uint8_t* __restrict__ live) {
+                                                   uint8_t* __restrict__ live, unsigned long long* __restrict__ keys) {
     const long long HW = (long long)H * W, total = HW * N;
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < s.P; p += (long long)gridDim.x * 256) {
         int n = 0, hi = N;                                             // the last image whose first point is not after p; every
@@ -1207,6 +1212,7 @@ __global__ __launch_bounds__(256) void seed_kernel(const uint8_t* __restrict__ m
         if ((unsigned)root >= (unsigned)total) continue;               // never with a workspace that label_into filled
         const int old = __hip_atomic_exchange(head + root, (int)(-(p + 1)), __ATOMIC_RELAXED, kGlobal);
         rec[p] = make_int4((int)r, (int)c, (int)k, old < 0 ? -old - 1 : -1);
+        if (keys) atomicMin(keys + q, (unsigned long long)k);
     }
 }
 
@@ -1251,6 +1257,162 @@ __global__ __launch_bounds__(256) void split_assign_kernel(const uint8_t* __rest
             }
         }
         if (c < W) out[p] = label;
+    });
+}
+
+// ---- geodesic seeded split -----------------------------------------------------------------------------------------------------------
+// Every foreground pixel holds one key, dist << 32 | k: the cheapest path found so far from a live seed to it (5 per axial and 7
+// per diagonal step between foreground pixels of the 8-neighbourhood; CONN == 1: a diagonal step needs one of the two pixels it
+// cuts between to be foreground, so that no step leaves a 4-component) and the index of that seed; all ones = not reached.  Keys
+// only ever decrease and every value is the cost of a real path, so the fixpoint -- the minimum of (dist, k) over the live seeds of
+// the pixel's component -- is the same whatever order the tiles run in.
+constexpr int kGT = kT + 2;                                    // a tile and its one-pixel halo
+constexpr unsigned long long kUnreached = ~0ull;
+constexpr unsigned long long kStepAxial = 5ull << 32, kStepDiagonal = 7ull << 32;
+
+__global__ __launch_bounds__(256) void geodesic_init_kernel(long long total, unsigned long long* __restrict__ keys) {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) keys[p] = kUnreached;
+}
+
+// One round: grid (tiles across, tiles down, N), one workgroup per 64 x 64 tile.  The tile takes its keys and a one-pixel halo into
+// LDS and sweeps until none of its keys changes: in a sweep every thread pulls, for each of its 16 pixels, the minimum over the
+// allowed neighbours of key + step; a pixel's key is written by its owner only, after the barrier that ends the sweep's reads.  The
+// halo stays as it was read.  Keys that fell go back with relaxed agent-scope atomic stores and the halo is read with the matching
+// loads: a neighbouring tile may be writing in the same launch, and whatever it has written so far is the cost of a real path.
+// A tile's byte of `next`: bit 0 = it lowered a key in this round, bit 1 = it holds foreground.  prev (NULL in the first round of
+// a call, which runs every tile): the bytes of the round before; a tile runs only if it holds foreground and it or one of its
+// eight neighbours lowered a key then -- otherwise its keys and its halo are what they were when it last found nothing to do.
+template <int CONN>
+__global__ __launch_bounds__(256) void geodesic_relax_kernel(const uint8_t* __restrict__ m, int H, int W, unsigned long long* keys,
+                                                             const uint8_t* __restrict__ prev, uint8_t* __restrict__ next) {
+    __shared__ unsigned long long key[kGT * kGT];
+    __shared__ uint8_t val[kGT * kGT];
+    const int tx = blockIdx.x, ty = blockIdx.y, nx = gridDim.x, ny = gridDim.y;
+    const long long tile0 = (long long)blockIdx.z * ny * nx, tile = tile0 + (long long)ty * nx + tx;
+    if (prev) {                                                // the same bytes for every thread: the whole workgroup leaves or stays
+        const int own = prev[tile];
+        int stirred = 0;
+        if (own & 2)
+            for (int y = max(ty - 1, 0); y <= min(ty + 1, ny - 1); ++y)
+                for (int x = max(tx - 1, 0); x <= min(tx + 1, nx - 1); ++x) stirred |= prev[tile0 + (long long)y * nx + x] & 1;
+        if (!stirred) {
+            if (threadIdx.x == 0) next[tile] = (uint8_t)(own & 2);
+            return;
+        }
+    }
+    const int c0 = tx * kT, r0 = ty * kT;
+    const long long img = (long long)blockIdx.z * H * W;
+    for (int i = threadIdx.x; i < kGT * kGT; i += 256) {
+        const int r = r0 - 1 + i / kGT, c = c0 - 1 + i % kGT;
+        const bool in = r >= 0 && r < H && c >= 0 && c < W;
+        const long long p = img + (long long)r * W + c;
+        const bool fg = in && m[p] != 0;
+        val[i] = (uint8_t)fg;
+        key[i] = fg ? __hip_atomic_load(keys + p, __ATOMIC_RELAXED, kGlobal) : kUnreached;
+    }
+    __syncthreads();
+    unsigned long long cur[kPer], loaded[kPer];
+    unsigned mine = 0;                                         // bit k: this thread's pixel k is foreground
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        const int j = ((i >> 6) + 1) * kGT + (i & 63) + 1;
+        cur[k] = loaded[k] = key[j];
+        mine |= (unsigned)val[j] << k;
+    }
+    if (!__syncthreads_or(mine != 0)) {                        // nothing to own here: never run again
+        if (threadIdx.x == 0) next[tile] = 0;
+        return;
+    }
+    // a path inside the tile and its halo has at most kTP steps, so kTP sweeps settle it; a tile that is cut short says it changed
+    for (int sweep = 0; sweep < kTP; ++sweep) {
+        unsigned fell = 0;
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            if (!((mine >> k) & 1)) continue;
+            const int i = threadIdx.x + 256 * k;
+            const int j = ((i >> 6) + 1) * kGT + (i & 63) + 1;
+            unsigned long long best = cur[k];
+            auto pull = [&](int q, unsigned long long step) {
+                const unsigned long long v = key[q];
+                if (v != kUnreached && v + step < best) best = v + step;
+            };
+            pull(j - 1, kStepAxial);
+            pull(j + 1, kStepAxial);
+            pull(j - kGT, kStepAxial);
+            pull(j + kGT, kStepAxial);
+            const bool up = CONN == 2 || val[j - kGT], down = CONN == 2 || val[j + kGT];
+            const bool left = CONN == 2 || val[j - 1], right = CONN == 2 || val[j + 1];
+            if (up || left) pull(j - kGT - 1, kStepDiagonal);
+            if (up || right) pull(j - kGT + 1, kStepDiagonal);
+            if (down || left) pull(j + kGT - 1, kStepDiagonal);
+            if (down || right) pull(j + kGT + 1, kStepDiagonal);
+            if (best < cur[k]) {
+                cur[k] = best;
+                fell |= 1u << k;
+            }
+        }
+        __syncthreads();                                       // every read of this sweep is done
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            const int i = threadIdx.x + 256 * k;
+            if ((fell >> k) & 1) key[((i >> 6) + 1) * kGT + (i & 63) + 1] = cur[k];
+        }
+        if (!__syncthreads_or(fell != 0)) break;
+    }
+    bool wrote = false;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        if (cur[k] >= loaded[k]) continue;                     // only a foreground pixel of the image ever falls
+        const int i = threadIdx.x + 256 * k;
+        __hip_atomic_store(keys + img + (long long)(r0 + (i >> 6)) * W + c0 + (i & 63), cur[k], __ATOMIC_RELAXED, kGlobal);
+        wrote = true;
+    }
+    const int changed = __syncthreads_or(wrote);
+    if (threadIdx.x == 0) next[tile] = (uint8_t)(changed ? 3 : 2);
+}
+
+// grid N.  last: the bytes of the last round run (NULL: no round was needed); converged[n] = no tile of image n lowered a key in it
+__global__ __launch_bounds__(256) void geodesic_converged_kernel(const uint8_t* __restrict__ last, int tiles, uint8_t* __restrict__ converged) {
+    int stirred = 0;
+    if (last)
+        for (int i = threadIdx.x; i < tiles; i += 256) stirred |= last[(long long)blockIdx.x * tiles + i] & 1;
+    stirred = __syncthreads_or(stirred);
+    if (threadIdx.x == 0) converged[blockIdx.x] = (uint8_t)(stirred == 0);
+}
+
+// head[root] > 0 is the label itself (a component without a live seed), < 0 the chain of a component that has one: its pixels take
+// 1 + the seed of their key and its distance.  A pixel that no round has reached yet takes the seed on top of its component's chain
+// and distance -1.  dist may be NULL.  Background writes 0 to both: the outputs need no clearing.
+__global__ __launch_bounds__(256) void geodesic_assign_kernel(const uint8_t* __restrict__ m, int N, int H, int W,
+                                                              const int32_t* __restrict__ lab, const int32_t* __restrict__ head,
+                                                              const int4* __restrict__ rec, int P,
+                                                              const unsigned long long* __restrict__ keys, int32_t* __restrict__ out,
+                                                              int32_t* __restrict__ dist) {
+    const long long total = (long long)N * H * W;
+    walk_row_segments(N, H, W, [&](int, int, int c, long long p) {
+        if (c >= W) return;
+        int label = 0, d = 0;
+        if (m[p] != 0) {
+            const int root = lab[p];
+            const int x = (unsigned)root < (unsigned)total ? head[root] : 0;       // in range with a workspace that label_into filled
+            if (x > 0) {
+                label = x;
+                d = -1;
+            } else if (x < 0) {
+                const unsigned long long key = keys[p];
+                const int q = -x - 1;
+                if (key != kUnreached) {
+                    label = (int)(unsigned)key + 1;
+                    d = (int)(key >> 32);
+                } else {
+                    label = (unsigned)q < (unsigned)P ? rec[q].z + 1 : 0;
+                    d = -1;
+                }
+            }
+        }
+        out[p] = label;
+        if (dist) dist[p] = d;
     });
 }
 
@@ -1306,6 +1468,17 @@ size_t regions_layout(void* w, int N, int H, int W, Ws* ws, int P = 0, int4** re
     Carve c{reinterpret_cast<uintptr_t>(w)};
     *ws = Ws{c.take<int32_t>(t), c.take<int32_t>(t), c.take<int32_t>((size_t)N * blocks_per_image(H, W))};
     if (rec) *rec = c.take<int4>(P);
+    return c.end;
+}
+
+// a geodesic split: the split's arrays, then keys (uint64 N H W) and flags (uint8 2 N tiles: the two byte maps of the rounds)
+struct Geo { unsigned long long* keys; uint8_t* flags; int tiles; };
+bool geodesic_sizes_ok(int N, int H, int W, int P) { return sizes_ok(N, H, W) && P >= 0 && 7LL * H * W < (1LL << 31); }
+size_t geodesic_layout(void* w, int N, int H, int W, int P, Ws* ws, int4** rec, Geo* g) {
+    Carve c{reinterpret_cast<uintptr_t>(w), regions_layout(w, N, H, W, ws, P, rec)};
+    g->tiles = cs_ceil_div(H, kT) * cs_ceil_div(W, kT);
+    g->keys = c.take<unsigned long long>((size_t)N * H * W);
+    g->flags = c.take<uint8_t>(2 * (size_t)N * g->tiles);
     return c.end;
 }
 
@@ -1693,11 +1866,67 @@ extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int co
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
     if (P > 0) {
-        hipLaunchKernelGGL(seed_kernel, dim3(grid_for(P)), dim3(256), 0, st, mask, N, H, W, seeds, ws.lab, ws.cnt, rec, live);
+        hipLaunchKernelGGL(seed_kernel, dim3(grid_for(P)), dim3(256), 0, st, mask, N, H, W, seeds, ws.lab, ws.cnt, rec, live, nullptr);
         CS_LAUNCH_CHECK();
     }
     if ((rc = number_into<true>(mask, N, H, W, ws, counts, st, seeds)) != CS_OK) return rc;
     hipLaunchKernelGGL(split_assign_kernel, walk_grid(N, H, W), dim3(256), 0, st, mask, N, H, W, ws.lab, ws.cnt, rec, P, labels);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" size_t cs_regions_geodesic_workspace(int N, int H, int W, int P) {
+    Ws ws;
+    int4* rec;
+    Geo g;
+    return geodesic_sizes_ok(N, H, W, P) ? geodesic_layout(nullptr, N, H, W, P, &ws, &rec, &g) : 0;
+}
+
+extern "C" int cs_regions_split_geodesic(const uint8_t* mask, int N, int H, int W, int connectivity, const int64_t* points,
+                                         const int64_t* offsets, const int32_t* limits, int P, int rounds, int resume, int32_t* labels,
+                                         int32_t* counts, uint8_t* live, int32_t* distance, uint8_t* converged, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    Ws ws;
+    int rc = carve("regions_split_geodesic", N, H, W, connectivity, mask, labels, workspace, workspace_bytes, &ws);
+    if (rc != CS_OK) return rc;
+    CS_CHECK_ARG(counts, "regions_split_geodesic: NULL counts");
+    CS_CHECK_ARG(converged, "regions_split_geodesic: NULL converged");
+    CS_CHECK_ARG(P >= 0 && (P == 0 || (points && offsets && live)), "regions_split_geodesic: P points need points, offsets and live");
+    CS_CHECK_ARG(rounds >= 1, "regions_split_geodesic: need rounds >= 1");
+    CS_CHECK_ARG(7LL * H * W < (1LL << 31), "regions_split_geodesic: need 7 H W < 2^31");
+    CS_CHECK_ARG((long long)P + (long long)H * W < (1LL << 31), "regions_split_geodesic: need P + H W < 2^31");
+    int4* rec;
+    Geo g;
+    CS_CHECK_ARG(workspace_bytes >= geodesic_layout(workspace, N, H, W, P, &ws, &rec, &g), "regions_split_geodesic: workspace too small");
+    CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7),
+                 "regions_split_geodesic: misaligned int64 array");
+    const Seeds seeds{reinterpret_cast<const long long*>(points), P > 0 ? reinterpret_cast<const long long*>(offsets) : nullptr, limits, P};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long total = (long long)N * H * W;
+    if (!resume) {
+        if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
+        hipLaunchKernelGGL(geodesic_init_kernel, dim3(grid_for(total)), dim3(256), 0, st, total, g.keys);
+        CS_LAUNCH_CHECK();
+        if (P > 0) {
+            hipLaunchKernelGGL(seed_kernel, dim3(grid_for(P)), dim3(256), 0, st, mask, N, H, W, seeds, ws.lab, ws.cnt, rec, live, g.keys);
+            CS_LAUNCH_CHECK();
+        }
+        if ((rc = number_into<true>(mask, N, H, W, ws, counts, st, seeds)) != CS_OK) return rc;
+    }
+    const dim3 tiles(cs_ceil_div(W, kT), cs_ceil_div(H, kT), N);
+    uint8_t* const map[2] = {g.flags, g.flags + (size_t)N * g.tiles};
+    for (int t = 0; P > 0 && t < rounds; ++t) {                // without a point no key is ever set: nothing to relax
+        const uint8_t* prev = t == 0 ? nullptr : map[(t - 1) & 1];
+        if (connectivity == 2)
+            hipLaunchKernelGGL(geodesic_relax_kernel<2>, tiles, dim3(256), 0, st, mask, H, W, g.keys, prev, map[t & 1]);
+        else
+            hipLaunchKernelGGL(geodesic_relax_kernel<1>, tiles, dim3(256), 0, st, mask, H, W, g.keys, prev, map[t & 1]);
+        CS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(geodesic_converged_kernel, dim3(N), dim3(256), 0, st, P > 0 ? map[(rounds - 1) & 1] : nullptr, g.tiles, converged);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(geodesic_assign_kernel, walk_grid(N, H, W), dim3(256), 0, st, mask, N, H, W, ws.lab, ws.cnt, rec, P, g.keys, labels,
+                       distance);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

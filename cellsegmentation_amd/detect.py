@@ -271,11 +271,12 @@ class DetectResult:
             hat, off = self.device_points, self.device_offsets
         return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
 
-    def split(self, masks, connectivity=1):
+    def split(self, masks, connectivity=1, geodesic=False):
         """Split the cells of ``masks`` (bool [N, H, W], or [H, W] for one map: the segmentation the detections belong to) at every
         map's kept detections -- ``per_image()[n][0]``, i.e. ``cell_counts`` applied as the limit, as in ``score`` -- ->
         regions.SplitResult: label k + 1 of map n is its detection k (regions.split has the rules).  The device-resident points
-        are read where they are."""
+        are read where they are.  ``geodesic``: ``regions.split_geodesic`` in its exact mode instead, whose cells are connected
+        (a regions.GeodesicSplitResult)."""
         from . import regions as Rg
         from . import score as S
         N = len(self.offsets) - 1
@@ -283,7 +284,7 @@ class DetectResult:
             pts, off = np.asarray(self.points, np.int64).reshape(-1, 2), np.asarray(self.offsets, np.int64)
         else:
             pts, off = self.device_points, self.device_offsets
-        return Rg.split(masks, pts, off, limits=S._limits(self.cell_counts, N), connectivity=connectivity)
+        return (Rg.split_geodesic if geodesic else Rg.split)(masks, pts, off, limits=S._limits(self.cell_counts, N), connectivity=connectivity)
 
 
 @dataclass(frozen=True)

@@ -370,20 +370,21 @@ def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshol
 
 
 def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None,
-                        opening_radius=0):
+                        opening_radius=0, geodesic=False):
     """One row per DETECTED cell of a ``SlideResult``: ``measure_slide``'s thresholding and clean-up of ``result.mask``, then
     ``regions.split`` of the foreground at ``result.points`` and ``regions.measure_labels`` with the map as the intensity ->
     ``(RegionTable, SplitResult)`` of one image.  Row k is ``result.points[k]`` (all zero where the point is not live: on the
     background after the clean-up, or a second point on one pixel); the rows from ``len(result.points)`` on are cells that no
     detection claimed.  ``max_regions`` and ``opening_radius`` as in ``measure_slide``: an int ``max_regions`` means no
-    synchronisation."""
+    synchronisation.  ``geodesic``: ``regions.split_geodesic`` in its exact mode instead of ``regions.split``, so that every cell is
+    one connected piece (it reads a flag back: a synchronisation of its own)."""
     from . import regions as Rg
     if not isinstance(result, SlideResult):
         raise TypeError("measure_slide_cells: expected the SlideResult of detect_slide")
     t, fg = _slide_foreground("measure_slide_cells", result.mask, thr_u8, min_object_size, hole_area_threshold, connectivity,
                               opening_radius)
     pts = np.asarray(result.points, np.int64).reshape(-1, 2)
-    parts = Rg.split(fg, pts, connectivity=connectivity)
+    parts = (Rg.split_geodesic if geodesic else Rg.split)(fg, pts, connectivity=connectivity)
     return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts
 
 
@@ -446,7 +447,7 @@ def _columns(cols, **means):
 
 def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, eps=11, reg_limit=False, method="gaussianblur",
                        thr_for_dt=10, min_object_size=300, hole_area_threshold=100, connectivity=1, overlap=False, hausdorff=False,
-                       **blur):
+                       geodesic=False, **blur):
     """The instance-level sibling of ``evaluate_detection``: every image's cells -- the cleaned segmentation split at the detected
     points -- against ground-truth instances, matched by IoU on the device (``regions.match_labels``).  The loader yields ``(images,
     masks, ...)``: masks uint8 0 / 255 [n, H, W], whose connected components (``regions.label(masks != 0, connectivity)``) are the
@@ -460,8 +461,9 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
     ``regions.hausdorff_labels`` on the same label pair -- on the overlap tables of ``overlap=True`` where both are asked for, which
     are then made once -- and adds the column ``hausdorff_obj`` (``score.hausdorff_score``; ``inf`` for an image with objects on
     one side only), ``mean_hausdorff`` = its average over the images where it is finite (0.0 without one) and
-    ``hausdorff_undefined`` = the number of the others; without it nothing more is launched either.  The model is left in segment
-    mode."""
+    ``hausdorff_undefined`` = the number of the others; without it nothing more is launched either.  ``geodesic=True`` splits with
+    ``regions.split_geodesic`` in its exact mode instead, so that every predicted cell is one connected piece; the keys are the
+    same.  The model is left in segment mode."""
     from . import detect as D
     from . import regions as Rg
     from . import score as S
@@ -482,7 +484,8 @@ def evaluate_instances(loader, model, device, threshold=0.5, iou_threshold=0.5, 
         for batch in tqdm(loader, desc="testing"):
             images, masks = batch[0], batch[1]
             probs, classes, reg = _cleaned_batch(model, images.to(device), threshold, mo, ho, reg_limit, reg_limit)
-            parts = D._detect(probs, reg.cpu().numpy().astype(int) if reg_limit else None, opts).split(classes, connectivity=conn)
+            parts = D._detect(probs, reg.cpu().numpy().astype(int) if reg_limit else None, opts).split(classes, connectivity=conn,
+                                                                                                          geodesic=geodesic)
             truth = torch.as_tensor(masks)
             if truth.dtype == torch.uint8:
                 truth = Rg.label(truth.to(device).reshape(classes.shape) != 0, conn)

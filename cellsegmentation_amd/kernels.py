@@ -1337,6 +1337,49 @@ def regions_split(mask, points, offsets, limits=None, connectivity=1, labels=Non
     return t["labels"], t["counts"], t["live"]
 
 
+def regions_geodesic_workspace(N, H, W, P, device):
+    """the caller-owned scratch of one cs_regions_split_geodesic call on [N,H,W] with a points buffer of P rows; a call with
+    ``resume`` takes the one its first call ran on"""
+    why = (f"regions_split_geodesic: a call takes 0 < N <= 65535 images with N H W < 2^31 and 7 H W < 2^31 pixels and P >= 0 points, "
+           f"got {(N, H, W, P)}")
+    return _workspace(_lib.load().cs_regions_geodesic_workspace, device, why, N, H, W, int(P))
+
+
+def regions_split_geodesic(mask, points, offsets, limits=None, connectivity=1, rounds=1, resume=False, labels=None, counts=None,
+                           live=None, distance=None, converged=None, want_distance=False, ws=None):
+    """regions_split's arguments -> (labels int32 [N,H,W], counts int32 [N], live uint8 [P], distance int32 [N,H,W] | None, converged
+    uint8 [N], ws): every foreground pixel labelled 1 + the index of the live seed of its component that is nearest along 5-7 chamfer
+    paths inside the component, after ``rounds`` relaxation rounds (cs_regions_split_geodesic in include/cellseg_hip.h).  ``resume``:
+    ``ws`` and the outputs are those of an earlier call with the same arguments; ``rounds`` more rounds run on them."""
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise TypeError("regions kernels read uint8 [N,H,W] masks")
+    N, H, W = mask.shape
+    if points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2:
+        raise TypeError("regions_split_geodesic: points must be int64 [P, 2]")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (N + 1,):
+        raise TypeError(f"regions_split_geodesic: offsets must be int64 [{N + 1}]")
+    if limits is not None and (limits.dtype != torch.int32 or tuple(limits.shape) != (N,)):
+        raise TypeError(f"regions_split_geodesic: limits must be int32 [{N}]")
+    P = int(points.shape[0])
+    if P + H * W >= 1 << 31:
+        raise ValueError(f"regions_split_geodesic: {P} points and {H}x{W} pixels do not leave room for int32 labels")
+    if resume and (ws is None or labels is None or counts is None or live is None):
+        raise ValueError("regions_split_geodesic: resume needs the workspace and the outputs of the call it resumes")
+    want = {"labels": ((N, H, W), torch.int32), "counts": ((N,), torch.int32), "live": ((P,), torch.uint8), "converged": ((N,), torch.uint8)}
+    if want_distance or distance is not None:
+        want["distance"] = ((N, H, W), torch.int32)
+    t = _regions_outputs("regions_split_geodesic", want, {"labels": labels, "counts": counts, "live": live, "distance": distance,
+                                                          "converged": converged}, mask.device)
+    if ws is None:
+        ws = regions_geodesic_workspace(N, H, W, P, mask.device)
+    none_if_empty = lambda x: _p(x) if P else None  # noqa: E731  (an empty tensor has no storage to point at)
+    _lib.check(_lib.load().cs_regions_split_geodesic(_p(mask), N, H, W, int(connectivity), none_if_empty(points), _p(offsets), _p(limits), P,
+                                                     int(rounds), int(bool(resume)), _p(t["labels"]), _p(t["counts"]),
+                                                     none_if_empty(t["live"]), _p(t.get("distance")), _p(t["converged"]), _p(ws), ws.numel(),
+                                                     _stream()), "regions_split_geodesic")
+    return t["labels"], t["counts"], t["live"], t.get("distance"), t["converged"], ws
+
+
 def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=None, bbox=None, sums=None, isum=None, imax=None,
                            want_counts=True):
     """int32 label image [N,H,W] (and uint8 intensity [N,H,W] or None) -> the tuple of regions_measure with row k = label k + 1; a

@@ -28,6 +28,12 @@ largest component count back once to size the tables.
 seed of its own component and label k + 1 is point k, so that ``measure_labels`` -- the same tables for a label image -- gives one
 row per detection.  Exact integer rules, stated once in ``split``'s docstring and restated in numpy by tests/split_ref.py.
 
+``split_geodesic`` is the same split with the distance measured along paths that stay inside the component (5-7 chamfer steps), so
+that every cell comes out connected, which ``measure_labels``, ``shape_labels``, ``hull_labels`` and the matching functions assume:
+exact integers again, the rule stated once in ``split_geodesic``'s docstring and restated in plain loops by tests/geodesic_ref.py
+(``GeodesicSplitResult``).  With a fixed ``max_rounds`` it keeps the contract above; with ``max_rounds=None`` it reads a flag per
+image back between batches of rounds until every image has converged.
+
 ``match_labels`` scores one label image against another at the object level: the partner of every label at IoU > 1/2, in exact
 integers (``MatchTable``; the rule is in ``match_labels``'s docstring, restated in numpy by tests/match_ref.py), from which
 ``MatchTable.score`` forms TP / FP / FN, segmentation quality and panoptic quality on the host (``score.label_score``).
@@ -323,28 +329,11 @@ def split(m, points, offsets=None, limits=None, connectivity=1):
 
     Without points the labels are ``label(m)`` bit for bit.  All of it is integer work: exact and independent of launch order, a
     fixed number of launches, no synchronisation.  This is a Euclidean partition inside each component, NOT a watershed: a cell of
-    a strongly non-convex clump may come out in two pieces, and no parity with any watershed implementation is claimed.  Cost: the
+    a strongly non-convex clump may come out in two pieces (``split_geodesic`` measures the distance inside the component instead
+    and leaves every cell connected), and no parity with any watershed implementation is claimed.  Cost: the
     labelling plus (foreground pixels) x (live seeds of their component) distance evaluations."""
-    from . import detect as D
-    conn = _check_connectivity(connectivity)
-    shape = tuple(getattr(m, "shape", ()))
-    if len(shape) in (2, 3) and min(shape) > 0:
-        D._check_dt_shape(shape)                                         # before the mask is copied anywhere
-        pts, off, lim = _seeds(points, offsets, limits, 1 if len(shape) == 2 else shape[0], shape[-2], shape[-1])
-    t, two_d = _as_masks(m, "split")
-    N, H, W = t.shape
-    dev = t.device
-
-    def up(x, dtype):
-        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(device=dev, dtype=dtype).contiguous()
-
-    pts, off = up(pts, torch.int64), up(off, torch.int64)
-    lim = None if lim is None else up(lim, torch.int32)
-    P = pts.shape[0]
-    n_seeds = (off[1:] - off[:-1]).clamp(0, P)                            # S' as the kernel forms it
-    if lim is not None:
-        n_seeds = torch.where(lim >= 0, torch.minimum(lim.to(torch.int64), n_seeds), (n_seeds + lim).clamp(min=0))
+    conn, t, two_d, pts, off, lim, n_seeds = _split_args(m, points, offsets, limits, connectivity, "split")
+    N, P, dev = t.shape[0], pts.shape[0], t.device
     labels = _int32_like(t)
     counts = torch.empty((N,), dtype=torch.int32, device=dev)
     live = None
@@ -353,7 +342,101 @@ def split(m, points, offsets=None, limits=None, connectivity=1):
         part = torch.empty((P,), dtype=torch.uint8, device=dev)
         K.regions_split(t[a:b], pts, off[a:b + 1], None if lim is None else lim[a:b], conn, labels=labels[a:b], counts=counts[a:b], live=part)
         live = part if live is None else live | part
-    return SplitResult(labels[0] if two_d else labels, counts, n_seeds.to(torch.int32), live.view(torch.bool))
+    return SplitResult(labels[0] if two_d else labels, counts, n_seeds, live.view(torch.bool))
+
+
+def _split_args(m, points, offsets, limits, connectivity, what):
+    """the arguments of ``split`` / ``split_geodesic``, argument errors before any device work -> (connectivity, uint8 masks [N,H,W],
+    was_2d, points int64 [P,2], offsets int64 [N+1], limits int32 [N] | None, n_seeds int32 [N]), all on the device"""
+    from . import detect as D
+    conn = _check_connectivity(connectivity)
+    shape = tuple(getattr(m, "shape", ()))
+    if len(shape) in (2, 3) and min(shape) > 0:
+        D._check_dt_shape(shape)                                         # before the mask is copied anywhere
+        pts, off, lim = _seeds(points, offsets, limits, 1 if len(shape) == 2 else shape[0], shape[-2], shape[-1])
+    t, two_d = _as_masks(m, what)
+    dev = t.device
+
+    def up(x, dtype):
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return x.to(device=dev, dtype=dtype).contiguous()
+
+    pts, off = up(pts, torch.int64), up(off, torch.int64)
+    lim = None if lim is None else up(lim, torch.int32)
+    n_seeds = (off[1:] - off[:-1]).clamp(0, pts.shape[0])                 # S' as the kernel forms it
+    if lim is not None:
+        n_seeds = torch.where(lim >= 0, torch.minimum(lim.to(torch.int64), n_seeds), (n_seeds + lim).clamp(min=0))
+    return conn, t, two_d, pts, off, lim, n_seeds.to(torch.int32)
+
+
+@dataclasses.dataclass
+class GeodesicSplitResult(SplitResult):
+    """``split_geodesic`` of N masks: a ``SplitResult`` plus ``converged`` bool [N] (device): the labels of image n are the rule's
+    (always true in the exact mode), and ``distance``: int32 of the mask's shape, the chamfer cost from every pixel to the seed that
+    owns it (0 on the background, -1 in a component without a live seed and on a pixel not reached yet), or None."""
+    converged: torch.Tensor
+    distance: typing.Optional[torch.Tensor] = None
+
+
+# The rounds of one batch in the exact mode.  A round after convergence costs one flag read per tile, a read-back costs a drained
+# queue and a resumed batch starts with one round over every tile, so a batch should nearly always be the only one.  The tiled
+# relaxation needs about one round per tile edge that the longest shortest path crosses, plus the quiet last one: 2 to 4 on clumps
+# a tile or two across (tests/geodesic_ref.py's model on the test masks), 6 to 10 on the two mask sets of
+# tools/regions_microbench.py, whose components wind through several tiles (measured, DESIGN.md).  12 covers those in one batch; a
+# maze takes more batches.
+_GEODESIC_BATCH = 12
+
+
+def split_geodesic(m, points, offsets=None, limits=None, connectivity=1, max_rounds=None, want_distance=False):
+    """``split`` with the distance measured inside the component, so that every cell is connected -> ``GeodesicSplitResult``.
+
+    The arguments, the seeds, ``live``, the components without a live seed, ``counts``, ``n_seeds``, limits, offsets, device points
+    and dead seeds are ``split``'s, unchanged.  Only the distance differs:
+
+    * A step goes from a foreground pixel to a foreground pixel of its 8-neighbourhood.  An axial step costs 5, a diagonal step 7
+      (the 5-7 chamfer).  With ``connectivity=2`` every such step is allowed; with ``connectivity=1`` a diagonal step from (r, c)
+      to (r + dr, c + dc) only if at least one of (r + dr, c) and (r, c + dc) is foreground.  So a step never leaves the component
+      of the chosen connectivity, and every pixel of a component that holds a live seed is reached.
+    * ``dist(p, k)`` is the cheapest path from the pixel of live seed k to p, and p gets label ``1 + k`` for the k that minimises
+      ``(dist(p, k), k)`` over the live seeds of its component.  Of two seeds on one pixel the lower index owns everything.
+    * ``7 H W < 2^31`` is required (a path visits a pixel at most once, so every distance fits int32); larger images raise
+      ``ValueError`` before any device work.
+
+    Every cell with a live seed is connected in the 8-neighbourhood and contains its seed pixel: for a pixel q on a shortest path
+    from p to its owner k, an owner j <= k of q at equal or smaller distance would reach p at most as far as k does.  This is NOT a
+    watershed either: the cut between two seeds lies where the geodesic distances are equal, not at the neck of the clump.  Nor is
+    it a refinement of ``split``: the chamfer bisector differs slightly from the Euclidean one even in a convex clump.
+
+    The keys (dist, k) are lowered to their fixpoint in rounds of one launch each (csrc/regions.hip).  ``max_rounds=int``: exactly
+    that many rounds, a fixed sequence of launches with no synchronisation, capturable into a graph; ``converged[n]`` says whether
+    image n reached the fixpoint, and of one that did not only this is promised: every label is 0, a live seed of that pixel's
+    component or a seedless number.  ``max_rounds=None`` (the default) is exact: it runs a batch of rounds, reads ``converged``
+    back, and resumes until every image has converged, as ``measure(max_regions=None)`` reads its count back.
+    ``want_distance``: also return the distance map.  Without points the labels are ``label(m)`` bit for bit.  Integer work only:
+    the converged result is exact and independent of launch order."""
+    if max_rounds is not None and (isinstance(max_rounds, bool) or int(max_rounds) != max_rounds or max_rounds < 1):
+        raise ValueError(f"max_rounds must be a positive integer or None, got {max_rounds!r}")
+    shape = tuple(getattr(m, "shape", ()))
+    if len(shape) in (2, 3) and 7 * shape[-2] * shape[-1] >= 1 << 31:
+        raise ValueError(f"split_geodesic: a {shape[-2]}x{shape[-1]} image does not keep 7 H W below 2^31")
+    conn, t, two_d, pts, off, lim, n_seeds = _split_args(m, points, offsets, limits, connectivity, "split_geodesic")
+    N, P, dev = t.shape[0], pts.shape[0], t.device
+    labels = _int32_like(t)
+    distance = _int32_like(t) if want_distance else None
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    converged = torch.empty((N,), dtype=torch.uint8, device=dev)
+    live = None
+    for a, b in _chunks(t):
+        part = torch.empty((P,), dtype=torch.uint8, device=dev)         # as in split: the other chunks' points come out dead
+        args = (t[a:b], pts, off[a:b + 1], None if lim is None else lim[a:b], conn)
+        out = dict(labels=labels[a:b], counts=counts[a:b], live=part, distance=None if distance is None else distance[a:b],
+                   converged=converged[a:b])
+        ws = K.regions_split_geodesic(*args, rounds=_GEODESIC_BATCH if max_rounds is None else int(max_rounds), **out)[-1]
+        while max_rounds is None and not bool(converged[a:b].all()):    # the synchronisation of the exact mode
+            K.regions_split_geodesic(*args, rounds=_GEODESIC_BATCH, resume=True, ws=ws, **out)
+        live = part if live is None else live | part
+    return GeodesicSplitResult(labels[0] if two_d else labels, counts, n_seeds, live.view(torch.bool), converged.view(torch.bool),
+                               None if distance is None else (distance[0] if two_d else distance))
 
 
 def _check_max_regions(max_regions):

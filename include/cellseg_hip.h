@@ -677,6 +677,34 @@ int cs_regions_split(const uint8_t* mask, int N, int H, int W, int connectivity,
 int cs_regions_measure_labels(const int32_t* labels, const uint8_t* intensity, int N, int H, int W, int capacity, int32_t* counts,
                               int32_t* area, int32_t* bbox, int64_t* sums, int64_t* isum, int32_t* imax, void* stream);
 
+/* ---- geodesic seeded split: connected cells for non-convex clumps (csrc/regions.hip) ---------------------------------------------
+ * cs_regions_split with the distance measured along paths that stay inside the component.  Masks, points, offsets, limits, seeds,
+ * live, the components without a live seed, counts and the launch contract are those of cs_regions_split; only the distance changes.
+ * Additions to the ABI: cs_abi_version is unchanged.
+ * cs_regions_split_geodesic: a step goes from a foreground pixel to a foreground pixel of its 8-neighbourhood; an axial step costs 5
+ *                            and a diagonal step 7.  With connectivity 2 every such step is allowed; with connectivity 1 a diagonal
+ *                            step (r, c) -> (r + dr, c + dc) only if (r + dr, c) or (r, c + dc) is foreground, so that no step leaves
+ *                            the component.  dist(p, k) = the cheapest path from the pixel of live seed k to p; p gets label 1 + k
+ *                            for the k that minimises (dist(p, k), k).  Every cell is therefore connected in the 8-neighbourhood and
+ *                            holds its seed pixel.  Need 7 H W < 2^31 (every distance fits int32).
+ *                            The keys (dist, k) of all pixels are lowered to that fixpoint by `rounds` (>= 1) rounds of one launch
+ *                            each; converged uint8 [N] = no key of image n changed in the last round run, i.e. the labels ARE the
+ *                            rule's.  Of an image that has not converged only this holds: every label is 0, a live seed of the
+ *                            pixel's component or the number of a component without one, and converged[n] = 0.  resume != 0: the
+ *                            workspace is as an earlier call with the same arguments left it; `rounds` more rounds run on it and
+ *                            labels, distance and converged are written again (counts and live are not).  The first round of a call
+ *                            visits every tile that holds foreground, a later one only the tiles near a change of the round before.
+ *                            distance (int32 [N][H][W], or NULL): the cost to the owner; 0 on the background, -1 in a component
+ *                            without a live seed and on a pixel no round has reached yet.  Integer comparisons only: the converged
+ *                            result is bit-exact and independent of launch order.  The number of launches depends on (N, H, W), on
+ *                            P > 0 and on rounds alone.  workspace: 16-byte aligned, >= cs_regions_geodesic_workspace(N, H, W, P)
+ *                            bytes (0 for sizes a call would refuse): cs_regions_split's plus 8 bytes per pixel and 2 per tile. */
+size_t cs_regions_geodesic_workspace(int N, int H, int W, int P);
+int cs_regions_split_geodesic(const uint8_t* mask, int N, int H, int W, int connectivity, const int64_t* points, const int64_t* offsets,
+                              const int32_t* limits, int P, int rounds, int resume, int32_t* labels, int32_t* counts, uint8_t* live,
+                              int32_t* distance /* may be NULL */, uint8_t* converged, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ---- the shape of every object of a label image: boundary map, second moments, perimeter tallies (csrc/regions.hip) ---------
  * labels int32 [N][H][W]; a pixel's object id is max(label, 0), images are independent; sizes and the launch contract as above (the
  * grids depend on (N, H, W, capacity) alone, no synchronisation, capturable); no workspace.  Additions to the ABI: cs_abi_version

@@ -17,6 +17,13 @@ tests/split_ref.py (scipy).
 
     python tools/regions_microbench.py --split [--reps 5] [--host-maps 2] [--json PATH]
 
+--split --geodesic times ``regions.split_geodesic`` next to ``regions.split`` on the same masks and seeds (about 1 and about 10 per
+component): with ``max_rounds`` fixed to the rounds the case needs (found once, a round at a time: the first round in which nothing
+changes included), with one round only -- the start, the finish and the round that does nearly all of the in-tile sweeps -- and in
+the exact mode, which reads the convergence flags back.  The first ``--host-maps`` maps are checked against tests/geodesic_ref.py.
+
+    python tools/regions_microbench.py --split --geodesic [--reps 5] [--host-maps 2] [--json PATH]
+
 --shape times ``regions.shape_labels`` with the table given (the boundary map, the second moments and the perimeter tallies: three
 launches) next to ``regions.measure_labels`` on the same label images: ``regions.split`` of the same two mask sets at about 1 and
 about 10 seeds per component.  Both are captured into a graph once and the replays are timed, so the figures hold no launch
@@ -219,6 +226,41 @@ def split_main(args):
     return res
 
 
+def geodesic_case(name, masks, pts, off, reps, host_maps, dev):
+    import geodesic_ref as GR
+    from cellsegmentation_amd import kernels as K
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    exact = G.split_geodesic(d, dp, doff, want_distance=True)
+    # the rounds this case needs: one round per call, resumed until the flags say that nothing changed
+    out = K.regions_split_geodesic(d.view(torch.uint8), dp, doff, rounds=1)
+    rounds = 1
+    while not bool(out[4].all()) and rounds < 4096:
+        K.regions_split_geodesic(d.view(torch.uint8), dp, doff, rounds=1, resume=True, labels=out[0], counts=out[1], live=out[2],
+                                 converged=out[4], ws=out[5])
+        rounds += 1
+    fixed = G.split_geodesic(d, dp, doff, max_rounds=rounds, want_distance=True)
+    ok = bool(fixed.converged.all()) and torch.equal(fixed.labels, exact.labels) and torch.equal(fixed.distance, exact.distance)
+    ok &= torch.equal(out[0], exact.labels)
+    split_ms, _ = time_dev(lambda: G.split(d, dp, doff), reps)
+    fixed_ms, ts = time_dev(lambda: G.split_geodesic(d, dp, doff, max_rounds=rounds), reps)
+    one_ms, _ = time_dev(lambda: G.split_geodesic(d, dp, doff, max_rounds=1), reps)
+    exact_ms, _ = time_dev(lambda: G.split_geodesic(d, dp, doff), reps)
+    euclid = G.split(d, dp, doff)
+    res = {"split_ms": split_ms, "geodesic_fixed_ms": fixed_ms, "geodesic_fixed_ms_all": ts, "geodesic_one_round_ms": one_ms,
+           "geodesic_exact_ms": exact_ms, "rounds": rounds, "points": int(len(pts)), "live_seeds": int(exact.live.sum()),
+           "foreground_pixels": int(masks.sum()), "distance_max": int(exact.distance.max()),
+           "pixels_unlike_split": int((euclid.labels != exact.labels).sum())}
+    if masks.shape[1] * masks.shape[2] > 1 << 20:                          # the plain-loop reference would take too long
+        host_maps = 0
+    for i in range(min(host_maps, len(masks))):
+        ref = GR.split(masks[i], pts[off[i]:off[i + 1]])
+        ok &= bool(np.array_equal(exact.labels[i].cpu().numpy(), ref["labels"])) and int(exact.counts[i]) == int(ref["counts"][0])
+        ok &= bool(np.array_equal(exact.distance[i].cpu().numpy(), ref["distance"]))
+    res.update(equal_to_host=bool(ok), host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
 def shape_case(name, masks, pts, off, reps, host_maps, dev):
     import shape_ref as SR
     d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
@@ -328,6 +370,7 @@ def main():
     ap.add_argument("--json", default=None, help="also write the results to this file")
     ap.add_argument("--measure", action="store_true", help="time regions.measure next to regions.label instead")
     ap.add_argument("--split", action="store_true", help="time regions.split + measure_labels next to label + measure instead")
+    ap.add_argument("--geodesic", action="store_true", help="with --split: time regions.split_geodesic next to regions.split instead")
     ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
     ap.add_argument("--hull", action="store_true", help="time regions.hull_labels next to measure_labels + shape_labels instead")
     ap.add_argument("--morph", action="store_true", help="time morph.binary_opening / expand_labels / nearest_sites next to the EDT instead")
@@ -339,7 +382,7 @@ def main():
     elif args.shape:
         res = seeded_main(shape_case, args)
     elif args.split:
-        res = split_main(args)
+        res = seeded_main(geodesic_case, args) if args.geodesic else split_main(args)
     elif args.measure:
         res = measure_main(args)
     else:
