@@ -99,6 +99,35 @@ __global__ void adam_prep_kernel(float* const* __restrict__ steps, int t0, int n
     coef[t0 + i] = make_float2((float)(l / bc1), (float)(1.0 / sqrt(bc2)));
 }
 
+// ---- host side.  What every entry point takes: device tables, a HOST array of gradient pointers, 1..320 tensors, a chunk list
+bool common_args_ok(const void* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks) {
+    return tensors_dev && grads_host && chunks_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1;
+}
+
+// the gradients' addresses into the by-value kernel argument; false at a NULL among them: nothing may be launched then
+bool pack_grads(const void* const* grads_host, int n_tensors, AdamGrads* gr) {
+    for (int i = 0; i < n_tensors; ++i)
+        if (!(gr->g[i] = reinterpret_cast<const float*>(grads_host[i]))) return false;
+    return true;
+}
+
+// `steps_dev` (capturable form): adam_prep_kernel leaves the coefficients in `coef` first; NULL: the two by-value coefficients
+int adam_launch(const char* who, const CsAdamTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
+                float* const* steps_dev, float2* coef, const double* lr_dev, double lr, float step_size, float inv_sqrt_bc2, double beta1, double beta2,
+                double eps, double weight_decay, void* stream) {
+    AdamGrads gr{};
+    CS_CHECK_ARG(pack_grads(grads_host, n_tensors, &gr), who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (steps_dev) {
+        hipLaunchKernelGGL(adam_prep_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, st, steps_dev, t0, n_tensors, lr_dev, lr, beta1, beta2, coef);
+        CS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, tensors_dev, gr, reinterpret_cast<const int2*>(chunks_dev), t0,
+                       step_size, inv_sqrt_bc2, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, coef);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
 }  // namespace
 
 extern "C" int cs_adam_chunk_elems(void) { return kAdamChunk; }
@@ -106,46 +135,23 @@ extern "C" int cs_adam_max_tensors(void) { return kAdamMaxTensors; }
 
 extern "C" int cs_adam_step(const CsAdamTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev,
                             int n_chunks, double lr, double beta1, double beta2, double eps, double weight_decay, double step, void* stream) {
-    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1,
+    CS_CHECK_ARG(common_args_ok(tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks),
                  "adam_step: 1..320 tensors per call, device tables, a HOST array of gradient pointers");
     CS_CHECK_ARG(step >= 1.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_step: step >= 1, betas in [0, 1)");
     // scalar arithmetic in double, like torch's fused kernel: only the results are rounded to fp32
     const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    AdamGrads gr{};
-    for (int i = 0; i < n_tensors; ++i) {
-        CS_CHECK_ARG(grads_host[i], "adam_step: NULL gradient");
-        gr.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    }
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tensors_dev, gr,
-                       reinterpret_cast<const int2*>(chunks_dev), t0, step_size, inv_sqrt_bc2, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                       (float)weight_decay, static_cast<const float2*>(nullptr));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return adam_launch("adam_step: NULL gradient", tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks, nullptr, nullptr, nullptr, lr,
+                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, weight_decay, stream);
 }
 
 extern "C" int cs_adam_step_dev(const CsAdamTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev,
                                 int n_chunks, float* const* steps_dev, float* coef_dev, const double* lr_dev, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, void* stream) {
-    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && steps_dev && coef_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors &&
-                     n_chunks >= 1,
-                 "adam_step_dev: 1..320 tensors per call, device tables (tensors, chunks, step pointers, coefficient scratch), a HOST array "
-                 "of gradient pointers");
+    CS_CHECK_ARG(common_args_ok(tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks) && steps_dev && coef_dev,
+                 "adam_step_dev: 1..320 tensors per call, device tables (tensors, chunks, step pointers, coefficient scratch), a HOST array of gradient pointers");
     CS_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_step_dev: betas in [0, 1)");
-    AdamGrads gr{};
-    for (int i = 0; i < n_tensors; ++i) {
-        CS_CHECK_ARG(grads_host[i], "adam_step_dev: NULL gradient");
-        gr.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_prep_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, st, steps_dev, t0, n_tensors, lr_dev, lr, beta1, beta2,
-                       reinterpret_cast<float2*>(coef_dev));
-    CS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, tensors_dev, gr, reinterpret_cast<const int2*>(chunks_dev), t0,
-                       0.0f, 0.0f, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay,
-                       reinterpret_cast<const float2*>(coef_dev));
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return adam_launch("adam_step_dev: NULL gradient", tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks, steps_dev,
+                       reinterpret_cast<float2*>(coef_dev), lr_dev, lr, 0.0f, 0.0f, beta1, beta2, eps, weight_decay, stream);
 }
 
 // ---- SGD (torch.optim.SGD, single-tensor form) -------------------------------------------------------------------------------
@@ -219,13 +225,7 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const CsSgdTensor* __res
 int sgd_launch(const char* who, const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
                double lr, double momentum, double dampening, double weight_decay, int nesterov, int first, const double* hyper_dev, void* stream) {
     AdamGrads gr{};
-    for (int i = 0; i < n_tensors; ++i) {
-        if (!grads_host[i]) {
-            cs_set_error_(who);
-            return CS_ERR_INVALID_ARG;
-        }
-        gr.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    }
+    CS_CHECK_ARG(pack_grads(grads_host, n_tensors, &gr), who);
     // the scalars as torch forms them: python doubles, 1 - dampening in double, each rounded to fp32 once
     hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tensors_dev, gr,
                        reinterpret_cast<const int2*>(chunks_dev), t0, (float)lr, (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov,
@@ -238,7 +238,7 @@ int sgd_launch(const char* who, const CsSgdTensor* tensors_dev, const void* cons
 
 extern "C" int cs_sgd_step(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
                            double lr, double momentum, double dampening, double weight_decay, int nesterov, int first, void* stream) {
-    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1,
+    CS_CHECK_ARG(common_args_ok(tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks),
                  "sgd_step: 1..320 tensors per call, device tables, a HOST array of gradient pointers");
     CS_CHECK_ARG(lr >= 0.0 && momentum >= 0.0 && weight_decay >= 0.0, "sgd_step: lr, momentum and weight_decay >= 0");
     CS_CHECK_ARG(!nesterov || (momentum > 0.0 && dampening == 0.0), "sgd_step: nesterov requires momentum > 0 and dampening == 0");
@@ -248,7 +248,7 @@ extern "C" int cs_sgd_step(const CsSgdTensor* tensors_dev, const void* const* gr
 
 extern "C" int cs_sgd_step_dev(const CsSgdTensor* tensors_dev, const void* const* grads_host, int t0, int n_tensors, const int* chunks_dev, int n_chunks,
                                const double* hyper_dev, double dampening, double weight_decay, int nesterov, int first, void* stream) {
-    CS_CHECK_ARG(tensors_dev && grads_host && chunks_dev && hyper_dev && t0 >= 0 && n_tensors >= 1 && n_tensors <= kAdamMaxTensors && n_chunks >= 1,
+    CS_CHECK_ARG(common_args_ok(tensors_dev, grads_host, t0, n_tensors, chunks_dev, n_chunks) && hyper_dev,
                  "sgd_step_dev: 1..320 tensors per call, device tables (tensors, chunks, the (lr, momentum) doubles), a HOST array of gradient "
                  "pointers");
     CS_CHECK_ARG(weight_decay >= 0.0, "sgd_step_dev: weight_decay >= 0");

@@ -214,3 +214,49 @@ def test_adam_capturable_replays_as_successive_steps(dev):
             with torch.cuda.graph(g2, stream=side):
                 a.step()
     torch.cuda.synchronize()
+
+
+def _stepped_once(dev):
+    """Two tensors, a full chunk plus a one-element tail, a scalar tail loop: Adam(capturable=True) after one eager step."""
+    ps = _params(dev, [(5,), (16385,)], 3)
+    a = O.Adam(ps, lr=5e-4, capturable=True)
+    for p in ps:
+        p.grad = torch.ones_like(p)
+    a.step()
+    torch.cuda.synchronize()
+    return ps, a
+
+
+def test_adam_plan_keeps_the_state_its_tables_point_at_alive(dev):
+    """A plan's device tables hold raw addresses of the moments and of the device step scalars, and a captured graph holds the plan
+    (_capture.keep): the plan must own that memory, or `opt.state.clear()` frees what a replay reads and writes."""
+    import gc
+    import weakref
+    ps, a = _stepped_once(dev)
+    refs = [weakref.ref(t) for p in ps for t in a.state[p].values()]
+    assert len(refs) == 6 and len(a._plans) == 1
+    plan = next(iter(a._plans.values()))
+    a.state.clear()
+    gc.collect()
+    assert all(r() is not None for r in refs)
+    del plan
+    a._plans.clear()
+    gc.collect()
+    assert all(r() is None for r in refs)
+
+
+def test_adam_capturable_refuses_a_capture_that_would_build_device_tables(dev):
+    """A set of parameters that has not been stepped eagerly has no plan, and building one copies tables from the host: refused on
+    the host before any device work, as SGD does."""
+    ps, a = _stepped_once(dev)
+    ps[1].grad = None                         # another parameter set: a cache miss
+    before = [p.detach().clone() for p in ps]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with pytest.raises(RuntimeError, match="one eager step"):
+            with torch.cuda.graph(torch.cuda.CUDAGraph(), stream=side):
+                a.step()
+    torch.cuda.synchronize()
+    assert len(a._plans) == 1 and all(torch.equal(p, b) for p, b in zip(ps, before))
+    assert [float(a.state[p]["step"]) for p in ps] == [1.0, 1.0]

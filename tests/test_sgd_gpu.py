@@ -322,3 +322,26 @@ def test_graphed_resnet18_tile_step_under_onecycle_sgd_equals_eager_steps_bit_fo
         stepped += 1
         assert torch.equal(o1.state[p]["momentum_buffer"], o2.state[q]["momentum_buffer"])
     assert stepped > 50
+
+
+def test_sgd_plans_keep_the_buffers_their_tables_point_at_alive(dev):
+    """A plan's device table holds raw addresses of the momentum buffers, and a captured graph holds the plan (_capture.keep): the
+    plan must own that memory, or `opt.state.clear()` frees what a replay reads and writes."""
+    import gc
+    import weakref
+    ps = _params(dev, [(5,), (16385,)], 3)
+    a = O.SGD(ps, lr=5e-4, momentum=0.9)
+    for p in ps:
+        p.grad = torch.ones_like(p)
+    a.step()
+    torch.cuda.synchronize()
+    refs = [weakref.ref(a.state[p]["momentum_buffer"]) for p in ps]
+    plans = list(a._plans.values())           # this step's (buffers created) and the next one's, built ahead
+    assert len(plans) == 2
+    a.state.clear()
+    gc.collect()
+    assert all(r() is not None for r in refs)
+    del plans
+    a._plans.clear()
+    gc.collect()
+    assert all(r() is None for r in refs)

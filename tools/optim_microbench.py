@@ -1,9 +1,11 @@
-"""SGD update timing on the ResNet-50 tile step's parameter set: cellsegmentation_amd.optim.SGD (one launch), its capturable form
-(lr and momentum read from device memory) and torch.optim.SGD (foreach), momentum 0.9 and weight decay 1e-4 as the reference's
-drivers construct it (train_tile.py:280-303).  Shapes from the model (tile mode, encoder unfrozen: the tensors that receive a
-gradient in that step), random values, static gradients; device-event time per step() after a warm-up (median over --reps; alone on an
-idle queue, and queued behind other device work so that the host's enqueue time is hidden) and the achieved bandwidth at 20 B per
-parameter (read p, g, buf; write p, buf) from the latter.  One process, one GPU.
+"""Optimizer update timing on the ResNet-50 tile step's parameter set: cellsegmentation_amd.optim.SGD and Adam (one launch), their
+capturable forms (SGD: lr and momentum read from device memory; Adam: step counts and lr on the device, one more tiny launch) and
+torch.optim.SGD / Adam (foreach), as the reference's drivers construct them (train_tile.py:280-303: SGD with momentum 0.9 and weight
+decay 1e-4; train_tile.py:282: Adam with weight decay 1e-4).  Shapes from the model (tile mode, encoder unfrozen: the tensors that
+receive a gradient in that step), random values, static gradients; device-event time per step() after a warm-up (median over --reps;
+alone on an idle queue, and queued behind other device work so that the host's enqueue time is hidden) and the achieved bandwidth
+from the latter, at 20 B per parameter for SGD (read p, g, buf; write p, buf) and 28 B for Adam (read p, g, m, v; write p, m, v).
+One process, one GPU.
 
     python tools/optim_microbench.py [--reps 50] [--warmup 10]
 """
@@ -71,16 +73,22 @@ def main():
     grads = [torch.randn(s, generator=gen).to(dev) for s in shapes]
     big = torch.randn(8192, 8192, device=dev)
     blocker = lambda: [torch.mm(big, big) for _ in range(8)]          # tens of ms of device work: `reps` step() calls enqueue behind it
-    res = {"tensors": len(shapes), "parameters": n_params, "bytes_per_step": 20 * n_params, "reps": args.reps, "warmup": args.warmup}
-    makers = {"hip_sgd": lambda ps: O.SGD(ps, lr=5e-4, momentum=0.9, weight_decay=1e-4),
-              "hip_sgd_capturable": lambda ps: O.SGD(ps, lr=5e-4, momentum=0.9, weight_decay=1e-4, capturable=True),
-              "torch_sgd": lambda ps: torch.optim.SGD(ps, lr=5e-4, momentum=0.9, weight_decay=1e-4)}
-    for name, make in makers.items():
+    res = {"tensors": len(shapes), "parameters": n_params, "reps": args.reps, "warmup": args.warmup}
+    sgd, adam = dict(lr=5e-4, momentum=0.9, weight_decay=1e-4), dict(lr=5e-4, weight_decay=1e-4)
+    # name -> (constructor, bytes moved per parameter and step)
+    makers = {"hip_sgd": (lambda ps: O.SGD(ps, **sgd), 20),
+              "hip_sgd_capturable": (lambda ps: O.SGD(ps, capturable=True, **sgd), 20),
+              "torch_sgd": (lambda ps: torch.optim.SGD(ps, **sgd), 20),
+              "hip_adam": (lambda ps: O.Adam(ps, **adam), 28),
+              "hip_adam_capturable": (lambda ps: O.Adam(ps, capturable=True, **adam), 28),
+              "torch_adam": (lambda ps: torch.optim.Adam(ps, **adam), 28)}
+    for name, (make, nbytes) in makers.items():
         ps = [(0.05 * torch.randn(s, generator=gen)).to(dev).requires_grad_() for s in shapes]
         for p, g in zip(ps, grads):
             p.grad = g
         step_ms, device_ms = time_steps(make(ps), args.warmup, args.reps, blocker)
-        res[name] = {"step_ms": step_ms, "device_ms": device_ms, "gb_per_s": 20 * n_params / (device_ms * 1e-3) / 1e9}
+        res[name] = {"step_ms": step_ms, "device_ms": device_ms, "bytes_per_step": nbytes * n_params,
+                     "gb_per_s": nbytes * n_params / (device_ms * 1e-3) / 1e9}
         del ps
     print(json.dumps(res), flush=True)
 
