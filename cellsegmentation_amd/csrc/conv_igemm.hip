@@ -1960,8 +1960,12 @@ int launch_wgrad(WgradParams p, hipStream_t st, int n_items = 1) {
     if constexpr (sizeof(T) == 2 && TR && BN == 128) {
         const unsigned long long x_bytes = (unsigned long long)(p.M / ((long long)p.P * p.Q)) * p.H * p.W * p.C * 2ull;
         const unsigned long long g_bytes = (unsigned long long)p.M * p.KO * 2ull;
-        if (!p.slab && x_bytes < 0x80000000ull && g_bytes < 0x80000000ull) {
-            const bool plain = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;
+        const bool plain = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;
+        // the pixel walk of the DMA kernels divides by Q and P with a 32-bit multiply-high magic, ceil(2^32 / d): d = 1 has none (2^32
+        // wraps to 0 and every quotient with it), so an output of one row or one column under a filter stays on the register-staged
+        // kernel, which divides for real (PLAIN walks no pixels)
+        const bool walk_ok = plain || (p.P > 1 && p.Q > 1);
+        if (!p.slab && walk_ok && x_bytes < 0x80000000ull && g_bytes < 0x80000000ull) {
             constexpr size_t stage_ = (size_t)32 * (BM + 128) * 2;
             // loader / consumer specialisation pays on the deep layers (tools/wgrad_ab.sh, 4 layers per launch: 256 -> 1024 @19x19 61 -> 52 us,
             // 2048 -> 512 @10x10 65 -> 56, strided 512 -> 1024 139 -> 107, 1024 -> 512 110 -> 93) and on the pixel-paired stem (106 -> 85 us);

@@ -20,7 +20,8 @@ csrc/conv_igemm.hip).  The strings are written BY HAND from the dispatcher's rul
   weight grad    BM = 128 for K > 64 (ungrouped) else 64, BN = 128.  f32 and use_tr_read = 0: wgrad_kernel<T,BM,128,false>.
                  bf16 transposing reads: grouped -> wgrad_kernel<bf16,64,128,true>; else PLAIN = 1x1 / stride 1 / pad 0, and
                  wgrad_spec_kernel<BM,4,PLAIN,32> when deep (BM = 128, Kp >= 256, taps * Cp >= 256) or stem-like (not PLAIN,
-                 Cp <= 8), else wgrad_dma_kernel<BM,3,PLAIN,32>
+                 Cp <= 8), else wgrad_dma_kernel<BM,3,PLAIN,32>; not PLAIN with an output of one row or one column (P = 1 or Q = 1):
+                 wgrad_kernel<bf16,BM,128,true> (the DMA kernels' pixel walk has no 32-bit magic divisor for 1)
 
 In the A/B flavour's children (test_wave_specialised_weight_gradient_on_every_shape) the expected string follows from the production
 one by `ab_variant`: the register-staged path turns igemm_dma_kernel<T,BM,BN,MODE,..> into igemm_kernel<T,BM,BN,MODE> (a stride-2
@@ -188,6 +189,8 @@ CASES = [
     C("s3-1x1-tapless-f32",   (2, 7, 7, 8, 8, 1, 3, 0, 1), F32, "dgrad+add+mask", D(F32, 64, 64, 1, 0, 0), "eight classes without taps"),
     # ------------------------------------------------------------------ weight gradient
     C("wg-3x3-dma64",         (2, 13, 13, 24, 40, 3, 1, 1, 1), BF, "wgrad+tr", WDMA(64, 0), "338 pixels, not a multiple of the slice"),
+    C("wg-3x3-one-row-reg128", (3, 1, 13, 24, 72, 3, 1, 1, 1), BF, "wgrad+tr", WG(BF, 128, 1), "P = 1: no 32-bit magic divisor for the DMA pixel walk: register-staged"),
+    C("wg-3x3-one-col-reg64", (3, 13, 1, 24, 40, 3, 1, 1, 1), BF, "wgrad+tr", WG(BF, 64, 1), "Q = 1: the same, BM = 64"),
     C("wg-3x3-reg64",         (2, 13, 13, 24, 40, 3, 1, 1, 1), BF, "wgrad", WG(BF, 64, 0)),
     C("wg-1x1-dma128",        (2, 19, 19, 64, 128, 1, 1, 0, 1), BF, "wgrad+tr", WDMA(128, 1), "K > 64"),
     C("wg-1x1-reg128",        (2, 19, 19, 64, 128, 1, 1, 0, 1), BF, "wgrad", WG(BF, 128, 0)),
@@ -247,8 +250,6 @@ NO_ENTRY = "no public entry point can produce these parameters"
 EXCLUSIONS = {
     **{REG(t, bm, bn, m): (GIB2, "the register-staged twin runs when src or weights reach 2^31 bytes; cs_set_igemm_path(1) forces it")
        for t in (BF, F32) for bm, bn in _TILES for m in (0, 1, 2)},
-    WG(BF, 128, 1): (GIB2, "bf16 transposing reads with BM = 128 leave the LDS-DMA kernels only when x or dy reaches 2^31 bytes (the grouped "
-                           "launch, the other way out, always has BM = 64); no switch forces it at test sizes"),
     WSPEC(64, 1): (NO_ENTRY, "PLAIN with BM = 64 is neither deep (BM = 128) nor stem-like (not PLAIN): only CELLSEG_WGRAD_SPEC = 1 selects it"),
 }
-AB_COLUMN_MISSING = {WG(BF, 128, 1)}          # excluded in both flavours (see its reason)
+AB_COLUMN_MISSING = set()                     # excluded in both flavours: nothing

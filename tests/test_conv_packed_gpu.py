@@ -262,14 +262,15 @@ def test_packed_kernels_are_exact_on_integer_data(shape, dev):
         assert torch.equal(_from_nhwc(dx2), ref_dx2)
         assert torch.equal(cs.cpu()[:Cin], ref_dx2.sum(dim=(0, 2, 3)))       # integer column sums below 2^24: exact too
     # weight gradients (first- and second-generation kernels; fp32 output, dense integer operands)
-    dyw = torch.randint(-3, 4, (N, Cout, P, Q), generator=g).float()
-    ref_dw = torch.nn.grad.conv2d_weight(x, (Cout, Cin, R, R), dyw, stride=stride, padding=pad)
-    assert float(ref_dw.abs().max()) < 2 ** 24
-    slabs = K.wgrad_batched(geom, [xd, xd], [_nhwc(dyw, dev)] * 2)
+    # (each item its own dy: an item that read another item's table row would give the other gradient)
+    dyw = [torch.randint(-3, 4, (N, Cout, P, Q), generator=g).float() for _ in range(2)]
+    ref_dw = [torch.nn.grad.conv2d_weight(x, (Cout, Cin, R, R), d, stride=stride, padding=pad) for d in dyw]
+    assert max(float(r.abs().max()) for r in ref_dw) < 2 ** 24 and not torch.equal(ref_dw[0], ref_dw[1])
+    slabs = K.wgrad_batched(geom, [xd, xd], [_nhwc(d, dev) for d in dyw])
     torch.cuda.synchronize()
     for i in range(2):
         got = slabs[i].double().sum(0).float().cpu().permute(0, 3, 1, 2)     # [K][R][S][C] -> [K][C][R][S]
-        assert torch.equal(got, ref_dw), f"wgrad item {i}: max diff {float((got - ref_dw).abs().max())}"
+        assert torch.equal(got, ref_dw[i]), f"wgrad item {i}: max diff {float((got - ref_dw[i]).abs().max())}"
 
 
 def test_wide_kernel_forced_on_every_shape(dev):

@@ -12,23 +12,23 @@ from cellsegmentation_amd import _lib, kernels as K  # noqa: E402
 
 BF = torch.bfloat16
 
-#        N   H   W   C    K   items
+#        N   H   W   C    K   items  instantiation <positions per stage, x rows per stage>, by Wp = W + 1 (csrc/wgrad_v2.hip plan)
 SHAPES = [
-    (2, 19, 19, 256, 256, 1),      # 128-position stages, Wp = 20
-    (3, 10, 10, 128, 64, 2),       # 128-position stages, Wp = 11; two layers in one launch
-    (2, 38, 38, 128, 128, 1),      # 64-position stages, Wp = 39
-    (2, 75, 75, 64, 64, 3),        # 64-position stages, Wp = 76; three layers (layer1 of ResNet-50)
-    (5, 7, 9, 64, 128, 1),         # non-square, tiny images: several images per stage
-    (1, 21, 17, 192, 64, 1),       # three source chunks, one image
-    (64, 10, 10, 512, 512, 1),     # layer4 at bench size: 64 tile pairs, few splits
-    (1, 150, 150, 128, 64, 1),     # the widest decoder layer (upconv8, resnet.py:163): Wp = 151, the 384-row x region (one workgroup per CU)
-    (2, 97, 131, 64, 128, 2),      # Wp = 132, non-square, two layers
+    (2, 19, 19, 256, 256, 1, "wgrad2_kernel<128,176>"),      # 128-position stages, Wp = 20
+    (3, 10, 10, 128, 64, 2, "wgrad2_kernel<128,152>"),       # 128-position stages, Wp = 11; two layers in one launch
+    (2, 38, 38, 128, 128, 1, "wgrad2_kernel<64,144>"),       # 64-position stages, Wp = 39
+    (2, 75, 75, 64, 64, 3, "wgrad2_kernel<64,224>"),         # 64-position stages, Wp = 76; three layers (layer1 of ResNet-50)
+    (5, 7, 9, 64, 128, 1, "wgrad2_kernel<128,152>"),         # non-square, tiny images: several images per stage
+    (1, 21, 17, 192, 64, 1, "wgrad2_kernel<128,176>"),       # three source chunks, one image
+    (64, 10, 10, 512, 512, 1, "wgrad2_kernel<128,152>"),     # layer4 at bench size: 64 tile pairs, few splits
+    (1, 150, 150, 128, 64, 1, "wgrad2_kernel<64,384>"),      # the widest decoder layer (upconv8, resnet.py:163): Wp = 151, the 384-row x region (one workgroup per CU)
+    (2, 97, 131, 64, 128, 2, "wgrad2_kernel<64,384>"),       # Wp = 132, non-square, two layers
 ]
 
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_wgrad_v2_matches_torch(shape, dev):
-    N, H, W, C, Kc, n = shape
+    N, H, W, C, Kc, n, variant = shape
     g = torch.Generator().manual_seed(5 + H + C + Kc)
     geom = K.make_geom(N, H, W, C, Kc, 3, 3, 1, 1)
     lib = _lib.load()
@@ -39,7 +39,7 @@ def test_wgrad_v2_matches_torch(shape, dev):
     dyd = [d.permute(0, 2, 3, 1).contiguous().to(BF).to(dev) for d in dys]
     slabs = K.wgrad_batched(geom, xd, dyd)
     torch.cuda.synchronize()
-    assert (lib.cs_last_conv_variant() or b"").decode().startswith("wgrad2_kernel"), "the second-generation kernel must have served this shape"
+    assert (lib.cs_last_conv_variant() or b"").decode() == variant, "the second-generation kernel must have served this shape, on its stage class"
     for i in range(n):
         ref = torch.nn.grad.conv2d_weight(xs[i], (Kc, C, 3, 3), dys[i], stride=1, padding=1)          # [K][C][3][3]
         got = slabs[i].sum(dim=0).cpu().permute(0, 3, 1, 2)                                          # [K][3][3][C] -> [K][C][3][3]
