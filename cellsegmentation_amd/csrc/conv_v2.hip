@@ -1376,22 +1376,40 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const uint4* __restri
     }
 }
 
-void magic(unsigned d, unsigned& mg, unsigned& sh) {
-    int l = 0;
-    while ((1u << l) < d) ++l;
-    const unsigned long long two_p = 1ull << (31 + l);
-    mg = (unsigned)(two_p / d + 1ull);
-    sh = (unsigned)(l - 1);
-}
+// the kernel family and wave layout of a packed-operand launch (plan_* returning false = not served)
+enum class C2Kind {
+    Halo14,        // halo kernel, 1 x 4 waves on linear pixel runs: (32 * tm) px x 128 ch
+    Halo14T2D,     // halo kernel, 1 x 4 waves of 4 tiles on 8 x 16-pixel tiles (wide images)
+    Halo22,        // halo kernel, 2 x 2 waves: 256 px x 64 ch
+    Wide3x3,       // wide kernel (one wave per SIMD), (32 * tm) px x 128 ch
+    Ring14,        // ring kernel, 1 x 4 waves of tm tiles: (32 * tm) px x 128 ch
+    Ring22,        // ring kernel, 2 x 2 waves of 2 tiles: 128 px x 64 ch
+    Wide1x1,       // wide kernel on two-plane stages, (32 * tm) px x 128 ch
+};
+bool is_1x1(C2Kind k) { return k == C2Kind::Ring14 || k == C2Kind::Ring22 || k == C2Kind::Wide1x1; }
+// wave rows WM of the layout: 1 x 4 waves cover 128 output channels, 2 x 2 waves 64
+int wave_rows(C2Kind k) { return k == C2Kind::Halo22 || k == C2Kind::Ring22 ? 2 : 1; }
 
-// geometry of the packed-operand launch; cfg: 0 = not served, 1 = 128 px x 128 ch (1x4 waves), 2 = 256 px x 64 ch (2x2 waves),
-// 3 = wide kernel (one wave per SIMD), (32 * tm) px x 128 ch
 struct C2Plan {
-    int cfg, nbw, ncc, rows;       // rows = partial column-sum rows
-    int tm;                        // pixel tiles (32 px) per wave: 1 x 4 configurations only
-    int t2d;                       // halo kernel on 8 x 16-pixel tiles (wide images)
+    C2Kind kind;
+    int tm, nbw;                   // the TM and NBW the kernel is instantiated with: pixel tiles (32 px) per wave, window blocks per wave (ring: 0)
+    int rows;                      // partial column-sum rows
     C2Params p;
 };
+
+// The tile height from a descending set with the least rounds-of-residency x height (the taller on ties); 0 unless all its tiles are
+// resident at once
+int resident_tm(long long M, int n_ntiles, std::initializer_list<int> heights) {
+    int best = 0;
+    const long long cus = cs_device_cus_();            // one workgroup per compute unit: `cus` run at once
+    long long best_cost = 1ll << 60, best_tiles = 0;
+    for (const int tm : heights) {
+        const long long tiles = ((M + 32 * tm - 1) / (32 * tm)) * n_ntiles;
+        const long long cost = ((tiles + cus - 1) / cus) * tm;
+        if (cost < best_cost) { best_cost = cost; best = tm; best_tiles = tiles; }
+    }
+    return best_tiles <= cus ? best : 0;
+}
 
 // Pixel-tile height of the wide kernel (one workgroup per compute unit: 256 run at once).  The busiest compute unit sets the time:
 // rounds-of-residency x tile height, the taller tile on ties (fewer weight passes).  0 = do not use the wide kernel.
@@ -1401,19 +1419,11 @@ int pick_wide_tm(long long M, int n_ntiles, int ncc) {
     if (knob == 1) return 0;
     if (knob == 4 || knob == 6 || knob == 8) return knob;
     if (ncc < 2) return 0;
-    int best = 0;
-    const long long cus = cs_device_cus_();            // one workgroup per compute unit: `cus` run at once
-    long long best_cost = 1ll << 60, best_tiles = 0;
-    for (int tm = 8; tm >= 4; tm -= 2) {
-        const long long tiles = ((M + 32 * tm - 1) / (32 * tm)) * n_ntiles;
-        const long long cost = ((tiles + cus - 1) / cus) * tm;
-        if (cost < best_cost) { best_cost = cost; best = tm; best_tiles = tiles; }
-    }
     // Measured (tools/wide_ab.sh, profiles/round4_notes.md): with every tile resident at once -- one round -- the wide kernel is ahead
     // of two 4-wave halo workgroups per compute unit (ResNet-50 layer3 34.2 -> 31.0 us, layer4 41.8 -> 33.9 us, decoder 1024 -> 512
     // 106 -> 96 us); with a second round its serial prologue and epilogue are paid twice with nothing to hide them behind
     // (layer2: 32.7 -> 40.2 us), and the halo kernel stays.
-    return best_tiles <= cus ? best : 0;
+    return resident_tm(M, n_ntiles, {8, 6, 4});
 }
 
 // Pixel-tile height of the 1 x 4 halo configuration.  Workgroups do not run in lock-step rounds, so a shorter tile only pays
@@ -1431,7 +1441,7 @@ int pick_tm(long long M, int n_ntiles) {
     return (wg4 > 256 && wg4 <= 512 && wg3 <= 512) ? 3 : 4;
 }
 
-// The same decision for the deep 1x1 convolutions (wide kernel on two-plane stages, cfg 8).  CELLSEG_WIDE1 (A/B flavour): 1 = never,
+// The same decision for the deep 1x1 convolutions (wide kernel on two-plane stages, Wide1x1).  CELLSEG_WIDE1 (A/B flavour): 1 = never,
 // 4 / 6 / 8 = force that height.  Only where the ring kernel is chain-bound: >= 8 chunks (512 contraction channels), all tiles resident
 // at once; the short contractions into wide outputs stay on the ring kernel (HBM-bound, many pixel tiles per workgroup).
 int pick_wide1_tm(long long M, int n_ntiles, int ncc) {
@@ -1439,15 +1449,44 @@ int pick_wide1_tm(long long M, int n_ntiles, int ncc) {
     if (knob == 1) return 0;
     if (knob == 4 || knob == 6) return knob;
     if (ncc < 8) return 0;
-    int best = 0;
-    const long long cus = cs_device_cus_();
-    long long best_cost = 1ll << 60, best_tiles = 0;
-    for (int tm = 6; tm >= 4; tm -= 2) {               // (three LDS stages: 3 x 8 KiB x tm per wave column -- 144 KiB at tm = 6)
-        const long long tiles = ((M + 32 * tm - 1) / (32 * tm)) * n_ntiles;
-        const long long cost = ((tiles + cus - 1) / cus) * tm;
-        if (cost < best_cost) { best_cost = cost; best = tm; best_tiles = tiles; }
+    return resident_tm(M, n_ntiles, {6, 4});           // (three LDS stages: 3 x 8 KiB x tm per wave column -- 144 KiB at tm = 6)
+}
+
+// bytes of the packed weights of a [rows][taps][cols] filter (pack_weights_kernel: the rows padded to whole 32-row tiles)
+unsigned long long packed_weight_bytes(int rows, int taps, int cols) {
+    return (unsigned long long)cs_ceil_div(rows, 32) * 32 * taps * (unsigned long long)cols * 2ull;
+}
+
+// What every plan sets the same way: p zeroed, then the source [NS][SH][SW] (pix_bytes per pixel, SC contraction channels), the
+// destination [NS][DH][DW][NOUT] and what follows from them and from pl.kind.  false = not served: a pixel index or a byte offset of
+// the source or of the packed weights would not fit in 31 bits.
+bool fill_params(C2Plan& pl, int NS, int SH, int SW, int SC, unsigned pix_bytes, int DH, int DW, int NOUT, int taps) {
+    const long long M = (long long)NS * DH * DW;
+    const unsigned long long src_bytes = (unsigned long long)NS * SH * SW * pix_bytes;
+    const unsigned long long wbytes = packed_weight_bytes(NOUT, taps, SC);
+    if (M >= (1ll << 31) - 512 || src_bytes >= 0x80000000ull || wbytes >= 0x80000000ull) return false;
+    C2Params& p = pl.p;
+    p = C2Params{};
+    p.SH = SH; p.SW = SW; p.SC = SC; p.NS = NS;
+    p.DH = DH; p.DW = DW; p.NOUT = NOUT;
+    if (DW >= 2 && DH >= 2) {               // (destination pixel -> (n, y, x): the halo kernels, the strided forward gather and the strided add operand)
+        cs_magic((unsigned)DW, p.mg_dw, p.sh_dw);
+        cs_magic((unsigned)DH, p.mg_dh, p.sh_dh);
     }
-    return best_tiles <= cus ? best : 0;
+    p.NCC = SC / 64;
+    p.M = (unsigned)M;
+    p.src_bytes = (unsigned)src_bytes;
+    p.pix_bytes = pix_bytes;
+    p.wpk_bytes = (unsigned)wbytes;
+    p.n_ntiles = cs_ceil_div(NOUT, wave_rows(pl.kind) == 2 ? 64 : 128);
+    return true;
+}
+
+// partial column-sum rows of a filled plan: one per wave row of every pixel tile
+int partial_rows(const C2Plan& pl) {
+    if (pl.kind == C2Kind::Halo14T2D) return (int)pl.p.n_tiles;
+    const int wm = wave_rows(pl.kind);
+    return cs_ceil_div(pl.p.M, 32 * pl.tm * wm) * wm;
 }
 
 bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
@@ -1460,8 +1499,7 @@ bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     const int PWH = dgrad ? g->R - 1 - g->pad : g->pad;
     if (PWH < 0) return false;
     const long long M = (long long)g->N * DH * DW;
-    const unsigned long long src_bytes = (unsigned long long)g->N * SH * SW * SC * 2ull;
-    if (M >= (1ll << 31) - 512 || src_bytes >= 0x80000000ull || (unsigned long long)M * NOUT * 2ull >= (1ull << 40)) return false;
+    if ((unsigned long long)M * NOUT * 2ull >= (1ull << 40)) return false;
     const int Wp = SW + PWH, Hp = SH + PWH;
     if (Wp < 2 || Hp < 2 || Wp < DW || Hp < DH) return false;
     if ((long long)g->N * Hp * Wp + 4096 >= (1ll << 31)) return false;
@@ -1471,44 +1509,42 @@ bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
         const long long rows = span + (long long)(g->R - 1) * Wp + (g->S - 1) + 1;
         return (int)((rows + 15) / 16);
     };
-    int cfg = 0, nbw = 0, tm = 4;
+    bool served = false;
     if (NOUT % 128 == 0) {
         // wide kernel first: window blocks per wave rounded up to an instantiated count (TM 4: 3 / 5, TM 6: 5 / 7, TM 8: 7 / 9)
         const int wtm = pick_wide_tm(M, NOUT / 128, ncc);
         if (wtm) {
             const int nb = (window_blocks(32 * wtm) + 3) / 4;
             const int lo = wtm == 4 ? 3 : wtm == 6 ? 5 : 7;
-            if (nb <= lo + 2) { cfg = 3; tm = wtm; nbw = nb <= lo ? lo : lo + 2; }
+            if (nb <= lo + 2) { served = true; pl.kind = C2Kind::Wide3x3; pl.tm = wtm; pl.nbw = nb <= lo ? lo : lo + 2; }
         }
     }
-    if (!cfg && NOUT % 128 == 0) {
-        tm = pick_tm(M, NOUT / 128);
-        for (; tm <= 4; ++tm) {              // a shorter tile has a smaller window; fall back to taller ones only if it somehow does not fit
+    if (!served && NOUT % 128 == 0) {
+        // a shorter tile has a smaller window; fall back to taller ones only if it somehow does not fit
+        for (int tm = pick_tm(M, NOUT / 128); tm <= 4 && !served; ++tm) {
             const int nb = (window_blocks(32 * tm) + 3) / 4;
-            if (ncc == 1 ? nb <= 8 : nb <= 5) { cfg = 1; nbw = nb < 3 ? 3 : nb; break; }
+            if (ncc == 1 ? nb <= 8 : nb <= 5) {
+                served = true; pl.kind = C2Kind::Halo14; pl.tm = tm;
+                pl.nbw = nb < 3 ? 3 : nb <= 5 ? nb : 8;         // (6..8: one chunk, one LDS stage of 8 blocks)
+            }
         }
     } else if (NOUT == 64 && ncc == 1) {
         const int nb = (window_blocks(256) + 3) / 4;
-        if (nb <= 8) { cfg = 2; nbw = 8; }
+        if (nb <= 8) { served = true; pl.kind = C2Kind::Halo22; pl.tm = 4; pl.nbw = 8; }
     }
     // wide images: 8 x 16-pixel tiles (see conv2_halo_kernel T2D); 1 x 4 waves of 4 pixel tiles, 180 window rows = 3 blocks per wave
-    int t2d = 0;
-    if (!cfg && NOUT % 128 == 0 && (8 + g->R - 1) * (16 + g->S - 1) <= 192) { cfg = 1; nbw = 3; tm = 4; t2d = 1; }
-    if (!cfg) return false;
-    if (cfg == 1 && ncc == 1 && nbw > 5) nbw = 8;
+    if (!served && NOUT % 128 == 0 && (8 + g->R - 1) * (16 + g->S - 1) <= 192) { served = true; pl.kind = C2Kind::Halo14T2D; pl.tm = 4; pl.nbw = 3; }
+    if (!served) return false;
+    const bool t2d = pl.kind == C2Kind::Halo14T2D;
+    if (!fill_params(pl, g->N, SH, SW, SC, (unsigned)SC * 2u, DH, DW, NOUT, g->R * g->S)) return false;
     C2Params& p = pl.p;
-    p = C2Params{};
-    p.SH = SH; p.SW = SW; p.SC = SC; p.NS = g->N;
-    p.DH = DH; p.DW = DW; p.NOUT = NOUT;
     p.Wp = Wp; p.Hp = Hp; p.PW = PWH; p.PH = PWH;
     p.stride = 1;
     p.LW = t2d ? 16 + g->S - 1 : Wp;
     for (int t = 0; t < 9; ++t) p.tap_sh[t] = (unsigned)((t / 3) * p.LW + t % 3);
     p.chunk_bytes = 128u;
-    magic((unsigned)DW, p.mg_dw, p.sh_dw);
-    magic((unsigned)DH, p.mg_dh, p.sh_dh);
-    magic((unsigned)p.LW, p.mg_wp, p.sh_wp);
-    magic((unsigned)Hp, p.mg_hp, p.sh_hp);
+    cs_magic((unsigned)p.LW, p.mg_wp, p.sh_wp);
+    cs_magic((unsigned)Hp, p.mg_hp, p.sh_hp);
     if (t2d) {
         p.TH = 8; p.TWl = 4;
         p.tiles_x = cs_ceil_div(DW, 16); p.tiles_y = cs_ceil_div(DH, 8);
@@ -1516,18 +1552,7 @@ bool plan_halo(const CsConvGeom* g, int dgrad, C2Plan& pl) {
         if (nt >= (1ll << 28)) return false;
         p.n_tiles = (unsigned)nt;
     }
-    p.NCC = ncc;
-    p.M = (unsigned)M;
-    p.src_bytes = (unsigned)src_bytes;
-    p.pix_bytes = (unsigned)SC * 2u;
-    const unsigned long long wbytes = (unsigned long long)cs_ceil_div(NOUT, 32) * 32 * g->R * g->S * (unsigned long long)SC * 2ull;
-    if (wbytes >= 0x80000000ull) return false;
-    p.wpk_bytes = (unsigned)wbytes;
-    const int BM = cfg != 2 ? 32 * tm : 256, BN = cfg != 2 ? 128 : 64;
-    p.n_ntiles = cs_ceil_div(NOUT, BN);
-    pl.cfg = cfg; pl.nbw = nbw; pl.ncc = ncc; pl.tm = cfg != 2 ? tm : 4;
-    pl.t2d = t2d;
-    pl.rows = t2d ? (int)p.n_tiles : cs_ceil_div(M, BM) * (cfg != 2 ? 1 : 2);
+    pl.rows = partial_rows(pl);
     return true;
 }
 // group count of a ring launch (a multiple of 8: one group per XCD slot): minimises rounds-of-residency x pixel tiles per workgroup;
@@ -1558,56 +1583,43 @@ bool plan_gemm(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     const int DH = dgrad ? (compact ? g->P : g->H) : g->P, DW = dgrad ? (compact ? g->Q : g->W) : g->Q;
     if (SC % 64 || NOUT % 64 || DH < 1 || DW < 1) return false;
     if (!dgrad && g->stride > 1 && (DH < 2 || DW < 2)) return false;
-    const int ncc = SC / 64;
     // (isolated, tools/conv_microbench.py shows the first-generation kernel ahead on >= 16 chunks -- 24.5 vs 29.1 us on 1024 -> 256 at
     // 19 x 19 -- but inside the training step the ring kernel wins on the family: 3.37 vs 3.43 ms per step)
-    const long long M = (long long)g->N * DH * DW;
-    const unsigned long long src_bytes = (unsigned long long)g->N * SH * SW * SC * 2ull;
-    if (M >= (1ll << 31) - 512 || src_bytes >= 0x80000000ull) return false;
-    int cfg = 0;
-    if (NOUT % 128 == 0) cfg = 6;                       // ring kernel, 128 px x 128 ch: 1 x 4 waves of 4 tiles
-    else if (NOUT == 64) cfg = 7;                       // ring kernel, 128 px x 64 ch: 2 x 2 waves of 2 tiles
-    if (!cfg) return false;
+    if (NOUT % 128 == 0) pl.kind = C2Kind::Ring14;
+    else if (NOUT == 64) pl.kind = C2Kind::Ring22;
+    else return false;
+    if (!fill_params(pl, g->N, SH, SW, SC, (unsigned)SC * 2u, DH, DW, NOUT, 1)) return false;
     C2Params& p = pl.p;
-    p = C2Params{};
-    p.SH = SH; p.SW = SW; p.SC = SC; p.NS = g->N;
-    p.DH = DH; p.DW = DW; p.NOUT = NOUT;
     p.stride = dgrad ? 1 : g->stride;
     p.add_stride = 1;
-    if (DW >= 2 && DH >= 2) {               // (destination pixel -> (n, y, x): the strided forward gather and the strided add operand)
-        magic((unsigned)DW, p.mg_dw, p.sh_dw);
-        magic((unsigned)DH, p.mg_dh, p.sh_dh);
-    }
-    p.NCC = ncc;
-    p.M = (unsigned)M;
-    p.src_bytes = (unsigned)src_bytes;
-    p.pix_bytes = (unsigned)SC * 2u;
-    const unsigned long long wbytes = (unsigned long long)cs_ceil_div(NOUT, 32) * 32 * (unsigned long long)SC * 2ull;
-    if (wbytes >= 0x80000000ull) return false;
-    p.wpk_bytes = (unsigned)wbytes;
-    const int BN = cfg == 6 ? 128 : 64;
-    p.n_ntiles = cs_ceil_div(NOUT, BN);
-    pl.cfg = cfg; pl.nbw = 0; pl.ncc = ncc;
     static const int ring_tm = cs_env_int_("CELLSEG_RING_TM", 0);      // A/B flavour: 2 / 3 / 4 forces the ring tile height
-    pl.tm = cfg != 6 ? 2 : (ring_tm >= 2 && ring_tm <= 4) ? ring_tm : pick_tm(M, p.n_ntiles);
-    pl.rows = cfg == 6 ? cs_ceil_div(M, 32 * pl.tm) : cs_ceil_div(M, 128) * 2;
-    pl.t2d = 0;
-    if (cfg == 6 && p.stride == 1 && !compact && ncc % 4 == 0) {      // (two chunks per stage, two stages per loop body)
-        const int wtm = pick_wide1_tm(M, p.n_ntiles, ncc);
+    pl.tm = pl.kind == C2Kind::Ring22 ? 2 : (ring_tm >= 2 && ring_tm <= 4) ? ring_tm : pick_tm(p.M, p.n_ntiles);
+    pl.nbw = 0;
+    if (pl.kind == C2Kind::Ring14 && p.stride == 1 && !compact && p.NCC % 4 == 0) {      // (two chunks per stage, two stages per loop body)
+        const int wtm = pick_wide1_tm(p.M, p.n_ntiles, p.NCC);
         if (wtm) {
-            pl.cfg = 8; pl.tm = wtm; pl.nbw = wtm;          // 2 planes x 32 * tm rows = 4 * tm blocks of 16 rows, tm per wave
-            pl.rows = cs_ceil_div(M, 32 * wtm);
+            pl.kind = C2Kind::Wide1x1; pl.tm = wtm; pl.nbw = wtm;          // 2 planes x 32 * tm rows = 4 * tm blocks of 16 rows, tm per wave
             p.lin = 1; p.chunk_bytes = 256u;
             p.tap_sh[0] = 0u; p.tap_sh[1] = 32u * (unsigned)wtm;
         }
     }
+    pl.rows = partial_rows(pl);
     return true;
 }
 
-// dynamic LDS beyond 64 KiB has to be allowed per (device, kernel): cs_api.cpp keeps the table
-template <typename F> bool allow_lds(F fn, size_t bytes) {
-    return cs_allow_dynamic_lds_(reinterpret_cast<const void*>(fn), bytes, bytes > 81920 ? 163840 : 81920) != 0;
+// The tail of every launch: 256 threads, `grid` workgroups, `lds` bytes of dynamic LDS -- beyond 64 KiB it has to be allowed per
+// (device, kernel): cs_api.cpp keeps the table --, `name` for cs_last_conv_variant()
+template <typename F, typename... Args>
+int launch_kernel(F fn, const char* name, unsigned grid, size_t lds, hipStream_t st, const Args&... args) {
+    if (!cs_allow_dynamic_lds_(reinterpret_cast<const void*>(fn), lds, lds > 81920 ? 163840 : 81920)) return CS_ERR_LAUNCH;
+    cs_set_variant_(name);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, args...);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
 }
+const char* tf(bool b) { return b ? "true" : "false"; }
+// one workgroup per (pixel tile, channel tile), the pixel tiles rounded up to whole rounds of the 8 XCDs
+unsigned xcd_grid(unsigned n_mt, int n_ntiles) { return ((n_mt + 7) / 8) * 8 * (unsigned)n_ntiles; }
 
 template <int TM, int WM, int WN, bool DG>
 int launch_ring_t(const C2Params& p, hipStream_t st) {
@@ -1616,123 +1628,76 @@ int launch_ring_t(const C2Params& p, hipStream_t st) {
     const unsigned n_mt = (unsigned)cs_ceil_div(p.M, 32 * TM * WM);
     const unsigned best = ring_groups(n_mt, (unsigned)p.n_ntiles, nullptr);
     const size_t lds = 3 * 16384 + 4 * (size_t)TM * 2048;
+    char name[64];
+    snprintf(name, sizeof(name), "conv2_ring_kernel<%d,%d,%d,%s,%s>", TM, WM, WN, tf(DG), tf(p.gather));
     if constexpr (TM == 2 && !DG) {
-        if (p.gather) {
-            if (!allow_lds(conv2_ring_kernel<TM, WM, WN, DG, true>, lds)) return CS_ERR_LAUNCH;
-            cs_set_variant_("conv2_ring_kernel<2,2,2,false,true>");
-            hipLaunchKernelGGL((conv2_ring_kernel<TM, WM, WN, DG, true>), dim3(best * (unsigned)p.n_ntiles), dim3(256), lds, st, p, (int)best);
-            CS_LAUNCH_CHECK();
-            return CS_OK;
-        }
+        if (p.gather) return launch_kernel(conv2_ring_kernel<TM, WM, WN, DG, true>, name, best * (unsigned)p.n_ntiles, lds, st, p, (int)best);
     }
     if (p.gather) {
         cs_set_error_("conv2: gathered operand rows are served for 64 output channels only");
         return CS_ERR_UNSUPPORTED;
     }
-    if (!allow_lds(conv2_ring_kernel<TM, WM, WN, DG>, lds)) return CS_ERR_LAUNCH;
-    char name[64];
-    snprintf(name, sizeof(name), "conv2_ring_kernel<%d,%d,%d,%s,false>", TM, WM, WN, DG ? "true" : "false");
-    cs_set_variant_(name);
-    hipLaunchKernelGGL((conv2_ring_kernel<TM, WM, WN, DG>), dim3(best * (unsigned)p.n_ntiles), dim3(256), lds, st, p, (int)best);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    return launch_kernel(conv2_ring_kernel<TM, WM, WN, DG>, name, best * (unsigned)p.n_ntiles, lds, st, p, (int)best);
 }
 
-template <int TM, int NBW, bool DG, int NTAP = 9> int launch_wide(const C2Params& p, hipStream_t st);
-
-template <bool DG>
-int launch_gemm(const C2Plan& pl, hipStream_t st) {
-    const C2Params& p = pl.p;
-    if (pl.cfg == 8) {
-        if (pl.tm == 4) return launch_wide<4, 4, DG, 2>(p, st);
-        return launch_wide<6, 6, DG, 2>(p, st);
-    }
-    if (pl.cfg == 6) {
-        if (pl.tm == 2) return launch_ring_t<2, 1, 4, DG>(p, st);
-        if (pl.tm == 3) return launch_ring_t<3, 1, 4, DG>(p, st);
-        return launch_ring_t<4, 1, 4, DG>(p, st);
-    }
-    return launch_ring_t<2, 2, 2, DG>(p, st);
-}
-
-template <int TM, int NBW, bool DG, bool T2D = false>
-int launch_cfg1(const C2Params& p, hipStream_t st, int two_stage) {
-    const unsigned n_mt = T2D ? p.n_tiles : (unsigned)cs_ceil_div(p.M, 32 * TM);
-    dim3 grid(((n_mt + 7) / 8) * 8 * (unsigned)p.n_ntiles);
-    // two stages: the epilogue borrows the idle one; one stage: its exchange scratch sits behind it
-    const size_t lds = two_stage ? (size_t)NBW * 8192 * 2 : (size_t)NBW * 8192 + EPI_LDS;
-    auto fn = conv2_halo_kernel<9, 3, TM, 1, 4, NBW, DG, T2D>;
-    if (!allow_lds(fn, lds)) return CS_ERR_LAUNCH;
+template <int TM, int WM, int WN, int NBW, bool DG, bool T2D = false>
+int launch_halo_t(const C2Params& p, hipStream_t st) {
+    const unsigned n_mt = T2D ? p.n_tiles : (unsigned)cs_ceil_div(p.M, 32 * TM * WM);
+    // two stages: the epilogue borrows the idle one; one stage (a single chunk, and always the 8-block window): its exchange scratch sits behind it
+    const size_t lds = NBW != 8 && p.NCC > 1 ? (size_t)NBW * 8192 * 2 : (size_t)NBW * 8192 + EPI_LDS;
     char name[64];
-    snprintf(name, sizeof(name), "conv2_halo_kernel<9,3,%d,1,4,%d,%s%s>", TM, NBW, DG ? "true" : "false", T2D ? ",true" : ",false");
-    cs_set_variant_(name);
-    hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, p);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    snprintf(name, sizeof(name), "conv2_halo_kernel<9,3,%d,%d,%d,%d,%s,%s>", TM, WM, WN, NBW, tf(DG), tf(T2D));
+    return launch_kernel(conv2_halo_kernel<9, 3, TM, WM, WN, NBW, DG, T2D>, name, xcd_grid(n_mt, p.n_ntiles), lds, st, p);
 }
 
 template <int TM, int NBW, bool DG, int NTAP>
-int launch_wide(const C2Params& p, hipStream_t st) {
+int launch_wide_t(const C2Params& p, hipStream_t st) {
     const unsigned n_mt = (unsigned)cs_ceil_div(p.M, 32 * TM);
-    dim3 grid(((n_mt + 7) / 8) * 8 * (unsigned)p.n_ntiles);
     const size_t lds = (size_t)NBW * 8192 * (NTAP == 9 ? 2 : 3);      // two stages (1x1 form: three); the epilogue's exchange scratch borrows an idle one
-    auto fn = conv2_wide_kernel<TM, NBW, DG, NTAP>;
-    if (!allow_lds(fn, lds)) return CS_ERR_LAUNCH;
     char name[64];
-    snprintf(name, sizeof(name), "conv2_wide_kernel<%d,%d,%s,%d>", TM, NBW, DG ? "true" : "false", NTAP);
-    cs_set_variant_(name);
-    hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, p);
-    CS_LAUNCH_CHECK();
-    return CS_OK;
+    snprintf(name, sizeof(name), "conv2_wide_kernel<%d,%d,%s,%d>", TM, NBW, tf(DG), NTAP);
+    return launch_kernel(conv2_wide_kernel<TM, NBW, DG, NTAP>, name, xcd_grid(n_mt, p.n_ntiles), lds, st, p);
 }
 
+// every instantiation there is, by (kind, TM, NBW)
+constexpr int plan_key(C2Kind kind, int tm, int nbw) { return ((int)kind * 16 + tm) * 16 + nbw; }
 template <bool DG>
-int launch_halo(const C2Plan& pl, hipStream_t st) {
+int launch_plan_t(const C2Plan& pl, hipStream_t st) {
+    using K = C2Kind;
     const C2Params& p = pl.p;
-    if (pl.cfg == 3) {
-        switch (pl.tm * 16 + pl.nbw) {
-            case 4 * 16 + 3: return launch_wide<4, 3, DG>(p, st);
-            case 4 * 16 + 5: return launch_wide<4, 5, DG>(p, st);
-            case 6 * 16 + 5: return launch_wide<6, 5, DG>(p, st);
-            case 6 * 16 + 7: return launch_wide<6, 7, DG>(p, st);
-            case 8 * 16 + 7: return launch_wide<8, 7, DG>(p, st);
-            case 8 * 16 + 9: return launch_wide<8, 9, DG>(p, st);
-        }
-        cs_set_error_("conv2: no wide-kernel instantiation for this plan");
-        return CS_ERR_UNSUPPORTED;
+    switch (plan_key(pl.kind, pl.tm, pl.nbw)) {
+        case plan_key(K::Halo14, 3, 3): return launch_halo_t<3, 1, 4, 3, DG>(p, st);
+        case plan_key(K::Halo14, 3, 4): return launch_halo_t<3, 1, 4, 4, DG>(p, st);
+        case plan_key(K::Halo14, 3, 5): return launch_halo_t<3, 1, 4, 5, DG>(p, st);
+        case plan_key(K::Halo14, 3, 8): return launch_halo_t<3, 1, 4, 8, DG>(p, st);
+        case plan_key(K::Halo14, 4, 3): return launch_halo_t<4, 1, 4, 3, DG>(p, st);
+        case plan_key(K::Halo14, 4, 4): return launch_halo_t<4, 1, 4, 4, DG>(p, st);
+        case plan_key(K::Halo14, 4, 5): return launch_halo_t<4, 1, 4, 5, DG>(p, st);
+        case plan_key(K::Halo14, 4, 8): return launch_halo_t<4, 1, 4, 8, DG>(p, st);
+        case plan_key(K::Halo14T2D, 4, 3): return launch_halo_t<4, 1, 4, 3, DG, true>(p, st);
+        case plan_key(K::Halo22, 4, 8): return launch_halo_t<4, 2, 2, 8, DG>(p, st);
+        case plan_key(K::Wide3x3, 4, 3): return launch_wide_t<4, 3, DG, 9>(p, st);
+        case plan_key(K::Wide3x3, 4, 5): return launch_wide_t<4, 5, DG, 9>(p, st);
+        case plan_key(K::Wide3x3, 6, 5): return launch_wide_t<6, 5, DG, 9>(p, st);
+        case plan_key(K::Wide3x3, 6, 7): return launch_wide_t<6, 7, DG, 9>(p, st);
+        case plan_key(K::Wide3x3, 8, 7): return launch_wide_t<8, 7, DG, 9>(p, st);
+        case plan_key(K::Wide3x3, 8, 9): return launch_wide_t<8, 9, DG, 9>(p, st);
+        case plan_key(K::Wide1x1, 4, 4): return launch_wide_t<4, 4, DG, 2>(p, st);
+        case plan_key(K::Wide1x1, 6, 6): return launch_wide_t<6, 6, DG, 2>(p, st);
+        case plan_key(K::Ring14, 2, 0): return launch_ring_t<2, 1, 4, DG>(p, st);       // (A/B flavour only: CELLSEG_RING_TM=2)
+        case plan_key(K::Ring14, 3, 0): return launch_ring_t<3, 1, 4, DG>(p, st);
+        case plan_key(K::Ring14, 4, 0): return launch_ring_t<4, 1, 4, DG>(p, st);
+        case plan_key(K::Ring22, 2, 0): return launch_ring_t<2, 2, 2, DG>(p, st);
     }
-    if (pl.cfg == 2) {
-        const unsigned n_mt = (unsigned)cs_ceil_div(p.M, 256);
-        dim3 grid(((n_mt + 7) / 8) * 8 * (unsigned)p.n_ntiles);
-        cs_set_variant_(DG ? "conv2_halo_kernel<9,3,4,2,2,8,true,false>" : "conv2_halo_kernel<9,3,4,2,2,8,false,false>");
-        if (!allow_lds(conv2_halo_kernel<9, 3, 4, 2, 2, 8, DG>, 8 * 8192 + EPI_LDS)) return CS_ERR_LAUNCH;
-        hipLaunchKernelGGL((conv2_halo_kernel<9, 3, 4, 2, 2, 8, DG>), grid, dim3(256), 8 * 8192 + EPI_LDS, st, p);
-        CS_LAUNCH_CHECK();
-        return CS_OK;
-    }
-    const int two = pl.ncc > 1;
-    if (pl.t2d) return launch_cfg1<4, 3, DG, true>(p, st, two);
-#define CS_HALO_TM(TM_)                                         \
-    switch (pl.nbw) {                                           \
-        case 3: return launch_cfg1<TM_, 3, DG>(p, st, two);     \
-        case 4: return launch_cfg1<TM_, 4, DG>(p, st, two);     \
-        case 5: return launch_cfg1<TM_, 5, DG>(p, st, two);     \
-        default: return launch_cfg1<TM_, 8, DG>(p, st, 0);      \
-    }
-    if (pl.tm == 2) { CS_HALO_TM(2) }
-    if (pl.tm == 3) { CS_HALO_TM(3) }
-    CS_HALO_TM(4)
-#undef CS_HALO_TM
+    cs_set_error_("conv2: no kernel instantiation for this plan");
+    return CS_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
 static bool plan_any(const CsConvGeom* g, int dgrad, C2Plan& pl) { return plan_halo(g, dgrad, pl) || plan_gemm(g, dgrad, pl); }
-static int launch_any(const C2Plan& pl, hipStream_t st, bool dg) {
-    if (dg) return pl.cfg <= 3 ? launch_halo<true>(pl, st) : launch_gemm<true>(pl, st);
-    return pl.cfg <= 3 ? launch_halo<false>(pl, st) : launch_gemm<false>(pl, st);
-}
+static int launch_plan(const C2Plan& pl, hipStream_t st, bool dg) { return dg ? launch_plan_t<true>(pl, st) : launch_plan_t<false>(pl, st); }
 
 extern "C" int cs_conv2d_packed_supported(const CsConvGeom* g, int dgrad) {
     if (!g) return 0;
@@ -1743,14 +1708,14 @@ extern "C" int cs_conv2d_packed_supported(const CsConvGeom* g, int dgrad) {
 extern "C" size_t cs_conv2d_packed_weight_bytes(const CsConvGeom* g, int dgrad) {
     if (!g) return 0;
     const int rows = dgrad ? g->C : g->K, cols = dgrad ? g->K : g->C;
-    return (size_t)cs_ceil_div(rows, 32) * 32 * g->R * g->S * (size_t)cols * 2;
+    return (size_t)packed_weight_bytes(rows, g->R * g->S, cols);
 }
 
 extern "C" int cs_pack_conv_weights(const CsConvGeom* g, int dgrad, const void* w_staged, void* w_packed, void* stream) {
     CS_CHECK_ARG(g && w_staged && w_packed, "pack_conv_weights: NULL argument");
     const int rows = dgrad ? g->C : g->K, cols = dgrad ? g->K : g->C;
     CS_CHECK_ARG(cols % 64 == 0 && rows % 8 == 0, "pack_conv_weights: contraction channels must be a multiple of 64");
-    const long long total = (long long)cs_ceil_div(rows, 32) * (cols / 64) * g->R * g->S * 4 * 64;
+    const long long total = (long long)(packed_weight_bytes(rows, g->R * g->S, cols) / 16);       // one thread per 16 bytes
     long long nb = (total + 255) / 256;
     if (nb > 8192) nb = 8192;
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint4*>(w_staged),
@@ -1777,7 +1742,7 @@ extern "C" int cs_conv2d_fwd_packed(const CsConvGeom* g, const void* x, const vo
     pl.p.src = x; pl.p.wpk = w_packed; pl.p.dst = y;
     pl.p.shift = shift; pl.p.residual = residual; pl.p.act = act;
     pl.p.bits_out = positive_bits;
-    return launch_any(pl, reinterpret_cast<hipStream_t>(stream), false);
+    return launch_plan(pl, reinterpret_cast<hipStream_t>(stream), false);
 }
 
 extern "C" int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const void* w_packed, const void* add, int add_stride,
@@ -1794,7 +1759,7 @@ extern "C" int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const
                      "conv2d_dgrad_packed: a strided 1x1 data gradient is written in compact [N][P][Q][C] form, without add / mask / column sums");
     if (add_stride == 2) {
         // (the SAME plan as cs_conv2d_packed_partial_rows reported: the caller sized the column-sum rows by it)
-        CS_CHECK_ARG(pl.cfg >= 6 && pl.p.DH >= 2 && pl.p.DW >= 2, "conv2d_dgrad_packed: a strided add operand is served by the 1x1 kernels only");
+        CS_CHECK_ARG(is_1x1(pl.kind) && pl.p.DH >= 2 && pl.p.DW >= 2, "conv2d_dgrad_packed: a strided add operand is served by the 1x1 kernels only");
         pl.p.add_stride = 2;
         pl.p.AH = (pl.p.DH + 1) / 2;
         pl.p.AW = (pl.p.DW + 1) / 2;
@@ -1803,7 +1768,7 @@ extern "C" int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const
     pl.p.residual = add; pl.p.act = CS_ACT_NONE;
     pl.p.bits_in = mask_bits;
     pl.p.slab = partial_rows;
-    return launch_any(pl, reinterpret_cast<hipStream_t>(stream), true);
+    return launch_plan(pl, reinterpret_cast<hipStream_t>(stream), true);
 }
 
 // Forward of the pixel-paired 7x7 / stride-2 stem (model/resnet.py:171, csrc/conv_igemm.hip cs_stem_*) on the ring kernel: the LDS row of
@@ -1816,27 +1781,14 @@ extern "C" int cs_stem_fwd_packed(int N, int H, int W, int K, const void* x_pair
     CS_CHECK_ARG(K == 64, "stem_fwd_packed: 64 output channels (the stem of every ResNet / ResNeXt of model/resnet.py)");
     CS_CHECK_ARG(act == CS_ACT_NONE || act == CS_ACT_RELU, "stem_fwd_packed: activation must be none or ReLU");
     const int P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1, Wh = (W + 1) / 2;
-    const long long M = (long long)N * P * Q;
-    const unsigned long long src_bytes = (unsigned long long)N * H * Wh * 16ull;
-    CS_CHECK_ARG(P >= 2 && Q >= 2 && M < (1ll << 31) - 512 && src_bytes < 0x80000000ull, "stem_fwd_packed: extents out of range");
     C2Plan pl;
+    pl.kind = C2Kind::Ring22; pl.tm = 2; pl.nbw = 0; pl.rows = 0;
+    // the source pixel is one 16-byte pair; the contraction runs over the 256 gathered channels of an output pixel's LDS row
+    CS_CHECK_ARG(P >= 2 && Q >= 2 && fill_params(pl, N, H, Wh, 256, 16u, P, Q, K, 1), "stem_fwd_packed: extents out of range");
     C2Params& p = pl.p;
-    p = C2Params{};
-    p.SH = H; p.SW = Wh; p.SC = 256; p.NS = N;
-    p.DH = P; p.DW = Q; p.NOUT = K;
     p.stride = 1; p.add_stride = 1;
     p.gather = 1; p.GH = H; p.GWp = Wh;
-    magic((unsigned)Q, p.mg_dw, p.sh_dw);
-    magic((unsigned)P, p.mg_dh, p.sh_dh);
-    p.NCC = 4;
-    p.M = (unsigned)M;
-    p.src_bytes = (unsigned)src_bytes;
-    p.pix_bytes = 16u;
-    p.wpk_bytes = (unsigned)(cs_ceil_div(K, 32) * 32 * 256 * 2);
-    pl.cfg = K == 64 ? 7 : 6;
-    p.n_ntiles = cs_ceil_div(K, K == 64 ? 64 : 128);
-    pl.nbw = 0; pl.ncc = 4; pl.rows = 0;
     p.src = x_pair; p.wpk = w_packed; p.dst = y;
     p.shift = shift; p.act = act; p.bits_out = positive_bits;
-    return launch_gemm<false>(pl, reinterpret_cast<hipStream_t>(stream));
+    return launch_plan(pl, reinterpret_cast<hipStream_t>(stream), false);
 }

@@ -196,6 +196,15 @@ template <typename F> static inline int cs_launch_typed(int dtype, const char* n
 }
 
 static inline int cs_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+// the constants of the kernels' division by a run-time d >= 2 (conv_v2.hip udivm, wgrad_v2.hip): n / d = umulhi(n, mg) >> sh for
+// n < 2^31, with mg = floor(2^(31+l) / d) + 1, sh = l - 1, l = ceil(log2 d).  d <= 1 has none: both 0, and the caller must not divide
+static inline void cs_magic(unsigned d, unsigned& mg, unsigned& sh) {
+    if (d <= 1) { mg = 0; sh = 0; return; }
+    unsigned l = 0;
+    while ((1ull << l) < d) ++l;
+    mg = (unsigned)(((1ull << (31 + l)) / d) + 1ull);
+    sh = l - 1;
+}
 // byte count rounded up to the 16-byte granule of the workspace carve-ups
 static inline size_t cs_align16(size_t b) { return (b + 15) & ~(size_t)15; }
 

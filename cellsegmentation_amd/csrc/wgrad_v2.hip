@@ -208,14 +208,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(41))) void w
     }(std::make_integer_sequence<int, 144>{});
 }
 
-void magic(unsigned d, unsigned& mg, unsigned& sh) {
-    if (d <= 1) { mg = 0; sh = 0; return; }
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    mg = (unsigned)(((1ull << (31 + l)) / d) + 1ull);
-    sh = l - 1;
-}
-
 struct W2Plan { int bl, xr; W2Params p; };
 
 bool plan(const CsConvGeom* g, int dtype, int n_items, W2Plan& pl) {
@@ -239,8 +231,8 @@ bool plan(const CsConvGeom* g, int dtype, int n_items, W2Plan& pl) {
     p = W2Params{};
     p.N = g->N; p.H = g->H; p.W = g->W; p.C = g->C; p.K = g->K;
     p.Wp = Wp; p.Hp = Hp;
-    magic((unsigned)Wp, p.mg_wp, p.sh_wp);
-    magic((unsigned)Hp, p.mg_hp, p.sh_hp);
+    cs_magic((unsigned)Wp, p.mg_wp, p.sh_wp);
+    cs_magic((unsigned)Hp, p.mg_hp, p.sh_hp);
     p.n_stages = (unsigned)((D + bl - 1) / bl);
     p.n_kt = g->K / 64; p.n_ct = g->C / 64;
     p.n_items = n_items;

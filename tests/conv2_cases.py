@@ -2,7 +2,7 @@
 tests/test_conv2_ledger_gpu.py and checked on the host by tests/test_conv2_cases_host.py).
 
 Every row names, for the forward and the data gradient, the kernel instantiation the production library must reach, as
-`cs_last_conv_variant()` reports it after the launch (launch_cfg1 / launch_wide / launch_ring_t / launch_halo in csrc/conv_v2.hip,
+`cs_last_conv_variant()` reports it after the launch (launch_plan and its launch_*_t in csrc/conv_v2.hip,
 launch_t in csrc/wgrad_v2.hip).  The names are written BY HAND from the dispatcher's rules, restated here so a reader can check a row.
 M = destination pixels, NOUT = destination channels, ncc = source channels / 64 (forward: N*P*Q, K, C/64; data gradient: N*H*W, C, K/64):
 
@@ -198,7 +198,7 @@ def plan_any(geom, dgrad, cus=CUS):
 
 
 def variant_of(pl, dgrad):
-    """the name launch_halo / launch_gemm report for a plan"""
+    """the name launch_plan reports for a plan"""
     dg = bool(dgrad)
     if pl["cfg"] == 3:
         return WIDE(pl["tm"], pl["nbw"], dg)

@@ -143,7 +143,7 @@ def test_ledger_names_every_reachable_instantiation():
     assert named - reachable == set(), "named by the ledger, not produced by the grid"
     # 20 halo (TM 3 / 4 x NBW 3 / 4 / 5 / 8, the 2-D tiles, the 64-channel form) + 12 wide 3x3 + 4 wide 1x1 + 6 ring, forward and gradient
     assert len(named) == 42
-    # what the dispatcher instantiates but production routing cannot reach (CS_HALO_TM(2): pick_tm answers 3 or 4; ring<2,1,4>: knob only)
+    # what production routing cannot reach: halo TM 2 is not instantiated (pick_tm answers 3 or 4); ring<2,1,4> is, for the A/B knob only
     assert not any(v.startswith("conv2_halo_kernel<9,3,2,") or v.startswith("conv2_ring_kernel<2,1,4,") for v in reachable)
 
 

@@ -230,7 +230,11 @@ def test_paired_stem_equals_the_generic_7x7_path(dev, dtype, hw):
         # the same forward on the ring kernel of conv_v2.hip (gathered operand rows, packed [K][256] weights), with sign bits
         assert K.stem_fwd_packed_supported(g, dtype)
         y2, bits = K.stem_fwd_packed(g, xp, K.stem_pack_weights(wp), shift, K.CS_ACT_RELU, want_bits=True)
+        from cellsegmentation_amd import _lib
+        variant = (_lib.load().cs_last_conv_variant() or b"").decode()
         torch.cuda.synchronize()
+        if _lib.FLAVOUR == "":
+            assert variant == "conv2_ring_kernel<2,2,2,false,true>"
         assert float((y2.float() - y_ref.float()).abs().max()) <= tol * max(1.0, float(y_ref.float().abs().max()))
         assert torch.equal(K.unpack_bits(bits, Kc), y2 > 0)
     # batch statistics through the same entry point
