@@ -190,6 +190,15 @@ _SIGNATURES = {
     "cs_regions_hausdorff_labels": (c_int, [_P, _P] + [c_int] * 5 + [_P] * 7 + [c_size_t, _P]),
     "cs_score_workspace": (c_size_t, [c_int, c_longlong]),
     "cs_score_points": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cs_spatial_threads": (c_int, []),
+    "cs_spatial_chunk": (c_int, []),
+    "cs_spatial_max_buckets": (c_longlong, []),
+    "cs_spatial_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_longlong, c_longlong]),
+    "cs_spatial_nearest": (c_int, [_P, _P, _P, c_longlong, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
+                                   c_size_t, _P]),
+    "cs_spatial_count_within": (c_int, [_P, _P, _P, c_longlong, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P,
+                                        _P, c_size_t, _P]),
+    "cs_spatial_bin_counts": (c_int, [_P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 _lib = None

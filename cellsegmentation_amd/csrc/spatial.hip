@@ -1,0 +1,471 @@
+// Neighbourhood queries over integer points: a bucket grid per image and three exact queries on top of it (spatial.py is the public
+// API).  Points are (row, col) int64 rows of a ragged batch, as cs_detect_cluster leaves them; a point is LIVE when its image's
+// limit keeps it (Python's [:c], as hat_limit of cs_score_points) and it lies inside [0, H) x [0, W).  Only live points ask or
+// answer.  With H^2 + W^2 < 2^31 every squared distance fits an int32 and the key (d2 << 32) | index fits 64 bits; every result is
+// a minimum of distinct keys or a sum of integers, so nothing depends on the order in which points arrive in a bucket.
+//
+// Build, per point set (the queries; in cross mode the targets too), on square buckets of side b, nbr x nbc per image:
+//   count    one thread per row of the buffer: the row's image by bisection of the offsets, one integer atomic per live point
+//   scan     one workgroup per image: exclusive scan of the bucket counts (block_scan_incl, looping over the buckets 256 at a time)
+//            into start[n][0 .. nb], start[n][nb] = the image's live points; the counts are zeroed again to serve as cursors
+//   scatter  the count pass again: slot = start + cursor++, one 16-byte record (row, col, index within the image, 0) per live point,
+//            image n's records from its first row on -- a bucket row-major, so a ROW of buckets is one contiguous span of records
+// Queries: one workgroup of 256 threads per bucket of query points (an empty bucket returns at once), thread t holding query t, t +
+// 256, ... of the bucket in turn; candidate spans are staged through LDS kChunk records at a time and read by every lane at once.
+//   nearest       square rings of buckets around the query's bucket.  After ring q the scanned region is the bucket rows and columns
+//                 within q of the query's; an unseen point is at least m away, m = the smallest gap from the query to the first row
+//                 or column outside the region (sides on the image's border have none).  The query is settled when its k-th key
+//                 has d2 < m^2 -- strictly: an unseen point AT m with a lower index would win the tie -- or when no side is left.
+//                 The ring loop is uniform: it goes on while any thread is unsettled (__syncthreads_or).
+//   count_within  the bucket rows and columns that cover [r - R, r + R] x [c - R, c + R] of every query of the bucket, R = isqrt of
+//                 the largest radius2; |dr| > R or |dc| > R is rejected before anything is squared.  Per-image sums by one 64-bit
+//                 integer atomic per workgroup and radius.
+// Launch geometry depends on (P, N, H, W, b, k) only; nothing synchronises with the host.
+#include <limits.h>
+#include "cs_common.h"
+#include "cs_block.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunk = 512;                        // candidate records staged in LDS at a time
+constexpr long long kMaxBuckets = 1LL << 22;       // N * nbr * nbc of one call
+constexpr int kMaxRadii = 8, kMaxK = 8;
+constexpr unsigned long long kNoKey = ~0ull;
+
+struct Grid {
+    int N, H, W, b, nbr, nbc, nb;                  // nb = nbr * nbc
+};
+struct Points {
+    const int64_t* pts;                            // [P][2]
+    const int64_t* off;                            // [N + 1]
+    const int32_t* limit;                          // [N] or NULL
+    long long P;
+    int xy;                                        // 1: the rows are (col, row)
+};
+struct Cells {
+    int32_t* cnt;                                  // [N][nb]   counts, then cursors
+    int32_t* start;                                // [N][nb + 1]
+    int4* rec;                                     // [P]
+};
+struct Radii {
+    int r2[kMaxRadii];
+};
+
+// rows [o0, o0 + n_eff) of the buffer are image n's points within its limit; offsets that do not describe rows of the buffer: none
+struct Span {
+    long long o0;
+    int n_eff;
+};
+__device__ __forceinline__ Span image_span(const Points& p, int n) {
+    const long long o0 = p.off[n], o1 = p.off[n + 1];
+    if (o0 < 0 || o1 < o0 || o1 > p.P || o1 - o0 > INT_MAX) return {0, 0};
+    const int cnt = (int)(o1 - o0);
+    int n_eff = cnt;
+    if (p.limit) {                                 // Python's [:c]
+        const int c = p.limit[n];
+        n_eff = c >= 0 ? min(c, cnt) : max(cnt + c, 0);
+    }
+    return {o0, n_eff};
+}
+
+// the live point in row i of the buffer: image, index within it, bucket; false = the row holds none
+struct Live {
+    int n, idx, r, c, bk;
+    long long o0;
+};
+__device__ __forceinline__ bool live_point(const Points& p, const Grid& g, long long i, Live& v) {
+    int lo = 0, hi = g.N;                          // the last n in [0, N] with off[n] <= i
+    if (p.off[0] > i) return false;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (p.off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    if (p.off[hi] <= i) return false;              // beyond the last image (lo == N - 1 here, or N == hi was never lowered)
+    const Span s = image_span(p, lo);
+    const long long idx = i - s.o0;
+    if (idx < 0 || idx >= s.n_eff) return false;
+    const long long r = p.pts[2 * i + p.xy], c = p.pts[2 * i + 1 - p.xy];
+    if (r < 0 || r >= g.H || c < 0 || c >= g.W) return false;
+    v.n = lo;
+    v.idx = (int)idx;
+    v.r = (int)r;
+    v.c = (int)c;
+    v.bk = ((int)r / g.b) * g.nbc + (int)c / g.b;
+    v.o0 = s.o0;
+    return true;
+}
+
+// grid-stride fill of n int32 words
+__global__ __launch_bounds__(kThreads) void spatial_fill_kernel(int32_t* __restrict__ p, long long n, int v) {
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) p[i] = v;
+}
+
+// grid (ceil(P / 256)).  SCATTER = false: cnt[n][bucket] += 1 per live point.  true: the record into its bucket's next free slot.
+template <bool SCATTER>
+__global__ __launch_bounds__(kThreads) void spatial_count_kernel(Points p, Grid g, Cells cells) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= p.P) return;
+    Live v;
+    if (!live_point(p, g, i, v)) return;
+    const int at = atomicAdd(cells.cnt + (long long)v.n * g.nb + v.bk, 1);
+    if (SCATTER) cells.rec[v.o0 + cells.start[(long long)v.n * (g.nb + 1) + v.bk] + at] = make_int4(v.r, v.c, v.idx, 0);
+}
+
+// grid (N): start[n][j] = the live points of image n in the buckets before j, start[n][nb] = all of them; cnt[n][*] = 0 again
+__global__ __launch_bounds__(kThreads) void spatial_scan_kernel(Grid g, Cells cells) {
+    __shared__ int s_scan[kThreads];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    int32_t* cnt = cells.cnt + (long long)n * g.nb;
+    int32_t* start = cells.start + (long long)n * (g.nb + 1);
+    int carry = 0;
+    for (int j0 = 0; j0 < g.nb; j0 += kThreads) {
+        const int j = j0 + tid;
+        const int v = j < g.nb ? cnt[j] : 0;
+        int total;
+        const int incl = block_scan_incl<kThreads, int>(v, s_scan, total);
+        if (j < g.nb) {
+            start[j] = carry + incl - v;
+            cnt[j] = 0;
+        }
+        carry += total;
+    }
+    if (tid == 0) start[g.nb] = carry;
+}
+
+// the records [s0, s1) of one image, kChunk at a time: every thread of the workgroup calls it (barriers); f(record) runs on the
+// threads with `have` for every record
+template <typename F>
+__device__ __forceinline__ void scan_records(const int4* __restrict__ rec, int s0, int s1, int4* s_rec, bool have, F f) {
+    for (int c0 = s0; c0 < s1; c0 += kChunk) {
+        const int m = min(kChunk, s1 - c0);
+        __syncthreads();                           // the chunk before this one has been read
+        for (int e = threadIdx.x; e < m; e += kThreads) s_rec[e] = rec[c0 + e];
+        __syncthreads();
+        if (have)
+            for (int e = 0; e < m; ++e) f(s_rec[e]);
+    }
+}
+
+// the records of buckets [j0, j1] (one row of buckets, or part of one) of a target image
+__device__ __forceinline__ void bucket_span(const int32_t* __restrict__ start, int j0, int j1, int& s0, int& s1) {
+    s0 = start[j0];
+    s1 = start[j1 + 1];
+}
+
+struct Query {
+    const int32_t* q_start;                        // the query image's start row
+    const int4* q_rec;                             // its records
+    const int32_t* t_start;                        // the target image's
+    const int4* t_rec;
+    long long q_row0;                              // first row of the query image in the buffer
+    int br, bc, q0, qn;                            // this workgroup's bucket and its records [q0, q0 + qn) of q_rec
+};
+__device__ __forceinline__ bool open_query(const Points& q, const Points& t, const Grid& g, const Cells& qc, const Cells& tc, Query& u) {
+    const int n = blockIdx.x / g.nb, bk = blockIdx.x - n * g.nb;
+    u.q_start = qc.start + (long long)n * (g.nb + 1);
+    u.q0 = u.q_start[bk];
+    u.qn = u.q_start[bk + 1] - u.q0;
+    if (u.qn <= 0) return false;
+    u.q_row0 = image_span(q, n).o0;
+    u.q_rec = qc.rec + u.q_row0;
+    u.t_start = tc.start + (long long)n * (g.nb + 1);
+    u.t_rec = tc.rec + image_span(t, n).o0;
+    u.br = bk / g.nbc;
+    u.bc = bk - u.br * g.nbc;
+    return true;
+}
+
+// grid (N * nb).  K in {1, 2, 4, 8} keys per thread, the first k written; SELF: queries and targets are one set, a row is never
+// its own neighbour.
+template <int K, bool SELF>
+__global__ __launch_bounds__(kThreads) void spatial_nearest_kernel(Points q, Points t, Grid g, Cells qc, Cells tc, int k,
+                                                                   int32_t* __restrict__ index, int32_t* __restrict__ d2_out) {
+    __shared__ int4 s_rec[kChunk];
+    Query u;
+    if (!open_query(q, t, g, qc, tc, u)) return;
+    const int b = g.b;
+    for (int p0 = 0; p0 < u.qn; p0 += kThreads) {
+        const bool have = p0 + (int)threadIdx.x < u.qn;
+        const int4 me = have ? u.q_rec[u.q0 + p0 + threadIdx.x] : make_int4(0, 0, -1, 0);
+        unsigned long long key[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) key[j] = kNoKey;
+        auto take = [&](const int4& c) {
+            if (SELF && c.z == me.z) return;
+            const int dr = c.x - me.x, dc = c.y - me.y;
+            const unsigned long long cand = ((unsigned long long)(uint32_t)(dr * dr + dc * dc) << 32) | (uint32_t)c.z;
+            if (cand >= key[K - 1]) return;
+            key[K - 1] = cand;
+#pragma unroll
+            for (int j = K - 1; j > 0; --j) {
+                const unsigned long long lo = key[j] < key[j - 1] ? key[j] : key[j - 1];
+                const unsigned long long hi = key[j] < key[j - 1] ? key[j - 1] : key[j];
+                key[j - 1] = lo;
+                key[j] = hi;
+            }
+        };
+        for (int ring = 0;; ++ring) {
+            const int r_lo = u.br - ring, r_hi = u.br + ring, c_lo = u.bc - ring, c_hi = u.bc + ring;
+            const int cc_lo = max(c_lo, 0), cc_hi = min(c_hi, g.nbc - 1);
+            int s0, s1;
+            if (r_lo >= 0) {                                               // the ring's top row (ring 0: the bucket itself)
+                bucket_span(u.t_start, r_lo * g.nbc + cc_lo, r_lo * g.nbc + cc_hi, s0, s1);
+                scan_records(u.t_rec, s0, s1, s_rec, have, take);
+            }
+            if (ring > 0 && r_hi < g.nbr) {                                // its bottom row
+                bucket_span(u.t_start, r_hi * g.nbc + cc_lo, r_hi * g.nbc + cc_hi, s0, s1);
+                scan_records(u.t_rec, s0, s1, s_rec, have, take);
+            }
+            for (int rr = max(r_lo + 1, 0); rr <= min(r_hi - 1, g.nbr - 1); ++rr) {     // its two columns in between
+                if (c_lo >= 0) {
+                    bucket_span(u.t_start, rr * g.nbc + c_lo, rr * g.nbc + c_lo, s0, s1);
+                    scan_records(u.t_rec, s0, s1, s_rec, have, take);
+                }
+                if (c_hi < g.nbc) {
+                    bucket_span(u.t_start, rr * g.nbc + c_hi, rr * g.nbc + c_hi, s0, s1);
+                    scan_records(u.t_rec, s0, s1, s_rec, have, take);
+                }
+            }
+            // m = the smallest gap to a row or column not scanned yet; sides on the border of the image have none
+            long long m = LLONG_MAX;
+            if (r_lo > 0) m = min(m, (long long)me.x - (long long)r_lo * b + 1);
+            if (r_hi < g.nbr - 1) m = min(m, (long long)(r_hi + 1) * b - me.x);
+            if (c_lo > 0) m = min(m, (long long)me.y - (long long)c_lo * b + 1);
+            if (c_hi < g.nbc - 1) m = min(m, (long long)(c_hi + 1) * b - me.y);
+            unsigned long long kth = key[K - 1];                           // selects, not an indexed read: the keys stay in registers
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j) kth = j == k - 1 ? key[j] : kth;
+            const bool settled = m == LLONG_MAX || (kth != kNoKey && (long long)(kth >> 32) < m * m);
+            if (!__syncthreads_or(have && !settled)) break;
+        }
+        if (have) {
+            const long long row = u.q_row0 + me.z;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j < k) {
+                    const bool found = key[j] != kNoKey;
+                    index[row * k + j] = found ? (int)(uint32_t)key[j] : -1;
+                    d2_out[row * k + j] = found ? (int)(key[j] >> 32) : -1;
+                }
+        }
+    }
+}
+
+// grid (N * nb).  R = isqrt(max radius2), box = min(R, max(H, W)): the reach in pixels that picks the bucket range.
+template <bool SELF>
+__global__ __launch_bounds__(kThreads) void spatial_within_kernel(Points q, Points t, Grid g, Cells qc, Cells tc, Radii radii, int n_r, int R,
+                                                                  int box, int32_t* __restrict__ counts,
+                                                                  unsigned long long* __restrict__ pair_counts) {
+    __shared__ int4 s_rec[kChunk];
+    __shared__ long long s_sum[kThreads / 64];
+    Query u;
+    if (!open_query(q, t, g, qc, tc, u)) return;
+    const int b = g.b;
+    const int br0 = max(u.br * b - box, 0) / b, br1 = (int)min(((long long)(u.br + 1) * b - 1 + box) / b, (long long)g.nbr - 1);
+    const int bc0 = max(u.bc * b - box, 0) / b, bc1 = (int)min(((long long)(u.bc + 1) * b - 1 + box) / b, (long long)g.nbc - 1);
+    long long sum[kMaxRadii];
+#pragma unroll
+    for (int j = 0; j < kMaxRadii; ++j) sum[j] = 0;
+    for (int p0 = 0; p0 < u.qn; p0 += kThreads) {
+        const bool have = p0 + (int)threadIdx.x < u.qn;
+        const int4 me = have ? u.q_rec[u.q0 + p0 + threadIdx.x] : make_int4(0, 0, -1, 0);
+        int cnt[kMaxRadii];
+#pragma unroll
+        for (int j = 0; j < kMaxRadii; ++j) cnt[j] = 0;
+        auto take = [&](const int4& c) {
+            if (SELF && c.z == me.z) return;
+            const int dr = c.x - me.x, dc = c.y - me.y;
+            if (dr > R || dr < -R || dc > R || dc < -R) return;
+            const int d2 = dr * dr + dc * dc;
+#pragma unroll
+            for (int j = 0; j < kMaxRadii; ++j) cnt[j] += (j < n_r && d2 <= radii.r2[j]) ? 1 : 0;
+        };
+        for (int rr = br0; rr <= br1; ++rr) {
+            int s0, s1;
+            bucket_span(u.t_start, rr * g.nbc + bc0, rr * g.nbc + bc1, s0, s1);
+            scan_records(u.t_rec, s0, s1, s_rec, have, take);
+        }
+        if (have) {
+            const long long row = u.q_row0 + me.z;
+#pragma unroll
+            for (int j = 0; j < kMaxRadii; ++j)
+                if (j < n_r) {
+                    counts[row * n_r + j] = cnt[j];
+                    sum[j] += cnt[j];
+                }
+        }
+    }
+    const int n = blockIdx.x / g.nb;
+#pragma unroll
+    for (int j = 0; j < kMaxRadii; ++j)
+        if (j < n_r) {                                                     // n_r is uniform: every thread reaches the barriers
+            const long long all = block_reduce<kThreads, long long>(sum[j], [](long long a, long long c) { return a + c; }, s_sum);
+            if (threadIdx.x == 0 && all) atomicAdd(pair_counts + (long long)n * n_r + j, (unsigned long long)all);
+        }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+bool make_grid(int N, int H, int W, int b, Grid& g) {
+    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || b <= 0) return false;
+    if ((long long)H * H + (long long)W * W >= (1LL << 31)) return false;
+    b = b < (H > W ? H : W) ? b : (H > W ? H : W);                        // a larger side describes the same one-bucket grid
+    const long long nbr = (H + (long long)b - 1) / b, nbc = (W + (long long)b - 1) / b;
+    if (nbr * nbc * N > kMaxBuckets) return false;
+    g = {N, H, W, b, (int)nbr, (int)nbc, (int)(nbr * nbc)};
+    return true;
+}
+size_t cells_bytes(const Grid& g, long long P) {
+    return cs_align16((size_t)g.N * g.nb * 4) + cs_align16((size_t)g.N * (g.nb + 1) * 4) + (size_t)(P > 0 ? P : 1) * 16;
+}
+Cells carve(const Grid& g, long long P, char*& at) {
+    Cells c;
+    c.cnt = reinterpret_cast<int32_t*>(at);
+    at += cs_align16((size_t)g.N * g.nb * 4);
+    c.start = reinterpret_cast<int32_t*>(at);
+    at += cs_align16((size_t)g.N * (g.nb + 1) * 4);
+    c.rec = reinterpret_cast<int4*>(at);
+    at += (size_t)(P > 0 ? P : 1) * 16;
+    return c;
+}
+void fill(int32_t* p, long long n, int v, hipStream_t st) {
+    if (n <= 0) return;
+    const long long blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(spatial_fill_kernel, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(kThreads), 0, st, p, n, v);
+}
+void build(const Points& p, const Grid& g, const Cells& c, hipStream_t st) {
+    fill(c.cnt, (long long)g.N * g.nb, 0, st);
+    const unsigned blocks = (unsigned)((p.P + kThreads - 1) / kThreads);
+    if (blocks) hipLaunchKernelGGL(spatial_count_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, p, g, c);
+    hipLaunchKernelGGL(spatial_scan_kernel, dim3(g.N), dim3(kThreads), 0, st, g, c);
+    if (blocks) hipLaunchKernelGGL(spatial_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, p, g, c);
+}
+
+// the arguments every query shares: checked, then both grids built
+struct Plan {
+    Grid g;
+    Points q, t;
+    Cells qc, tc;
+    bool self;
+};
+#define SPATIAL_CHECK_COMMON(name)                                                                                                    \
+    Plan plan;                                                                                                                        \
+    CS_CHECK_ARG(make_grid(N, H, W, bucket, plan.g), name ": need 0 < N <= 65535, H^2 + W^2 < 2^31, bucket >= 1 and at most 2^22 buckets"); \
+    CS_CHECK_ARG(P >= 0 && P < (1LL << 31) && P_other >= 0 && P_other < (1LL << 31), name ": need 0 <= P < 2^31 rows");               \
+    CS_CHECK_ARG(off && workspace && (pts || P == 0), name ": NULL argument");                                                        \
+    CS_CHECK_ARG(other_off || (!other && !other_limit && P_other == 0), name ": a target set needs its offsets");                    \
+    CS_CHECK_ARG(!other_off || other || P_other == 0, name ": NULL argument");                                                        \
+    CS_CHECK_ARG((flags & ~1) == 0, name ": unknown flag bits");                                                                      \
+    CS_CHECK_ARG(workspace_bytes >= cs_spatial_workspace(N, H, W, bucket, P, other_off ? P_other : -1), name ": workspace too small"); \
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(pts) & 7) == 0 &&                 \
+                 (reinterpret_cast<uintptr_t>(other) & 7) == 0 && (reinterpret_cast<uintptr_t>(off) & 7) == 0 &&                      \
+                 (reinterpret_cast<uintptr_t>(other_off) & 7) == 0, name ": misaligned argument")
+
+void plan_build(Plan& plan, const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, const int64_t* other,
+                const int64_t* other_off, const int32_t* other_limit, long long P_other, int flags, void* workspace, hipStream_t st) {
+    char* at = reinterpret_cast<char*>(workspace);
+    plan.self = other_off == nullptr;
+    plan.q = {pts, off, limit, P, 0};
+    plan.qc = carve(plan.g, P, at);
+    build(plan.q, plan.g, plan.qc, st);
+    if (plan.self) {
+        plan.t = plan.q;
+        plan.tc = plan.qc;
+    } else {
+        plan.t = {other, other_off, other_limit, P_other, flags & 1};
+        plan.tc = carve(plan.g, P_other, at);
+        build(plan.t, plan.g, plan.tc, st);
+    }
+}
+
+}  // namespace
+
+extern "C" int cs_spatial_threads(void) { return kThreads; }
+extern "C" int cs_spatial_chunk(void) { return kChunk; }
+extern "C" long long cs_spatial_max_buckets(void) { return kMaxBuckets; }
+
+extern "C" size_t cs_spatial_workspace(int N, int H, int W, int bucket, long long P, long long P_other) {
+    Grid g;
+    if (!make_grid(N, H, W, bucket, g) || P < 0 || P >= (1LL << 31) || P_other >= (1LL << 31)) return 0;
+    return cells_bytes(g, P) + (P_other >= 0 ? cells_bytes(g, P_other) : 0);
+}
+
+extern "C" int cs_spatial_nearest(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, const int64_t* other,
+                                  const int64_t* other_off, const int32_t* other_limit, long long P_other, int N, int H, int W, int bucket,
+                                  int k, int flags, int32_t* index, int32_t* d2, void* workspace, size_t workspace_bytes, void* stream) {
+    SPATIAL_CHECK_COMMON("spatial_nearest");
+    CS_CHECK_ARG(k >= 1 && k <= kMaxK, "spatial_nearest: need 1 <= k <= 8");
+    CS_CHECK_ARG((index && d2) || P == 0, "spatial_nearest: NULL argument");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(index) & 3) == 0 && (reinterpret_cast<uintptr_t>(d2) & 3) == 0, "spatial_nearest: misaligned argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    fill(index, P * k, -2, st);
+    fill(d2, P * k, -1, st);
+    plan_build(plan, pts, off, limit, P, other, other_off, other_limit, P_other, flags, workspace, st);
+    const dim3 grid((unsigned)(plan.g.N * plan.g.nb)), block(kThreads);
+#define SPATIAL_NEAREST(KK)                                                                                                              \
+    do {                                                                                                                                 \
+        if (plan.self) hipLaunchKernelGGL((spatial_nearest_kernel<KK, true>), grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, k, index, d2); \
+        else hipLaunchKernelGGL((spatial_nearest_kernel<KK, false>), grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, k, index, d2); \
+    } while (0)
+    if (P > 0) {
+        if (k == 1) SPATIAL_NEAREST(1);
+        else if (k == 2) SPATIAL_NEAREST(2);
+        else if (k <= 4) SPATIAL_NEAREST(4);
+        else SPATIAL_NEAREST(8);
+    }
+#undef SPATIAL_NEAREST
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_spatial_count_within(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, const int64_t* other,
+                                       const int64_t* other_off, const int32_t* other_limit, long long P_other, int N, int H, int W,
+                                       int bucket, const int32_t* radii2, int n_radii, int flags, int32_t* counts, int64_t* pair_counts,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    SPATIAL_CHECK_COMMON("spatial_count_within");
+    CS_CHECK_ARG(radii2 && n_radii >= 1 && n_radii <= kMaxRadii, "spatial_count_within: need 1 to 8 radii");
+    Radii radii = {};
+    int top = 0;
+    for (int j = 0; j < n_radii; ++j) {
+        CS_CHECK_ARG(radii2[j] >= 0, "spatial_count_within: radius2 must be non-negative and below 2^31");
+        radii.r2[j] = radii2[j];
+        top = radii2[j] > top ? radii2[j] : top;
+    }
+    CS_CHECK_ARG(pair_counts && (counts || P == 0), "spatial_count_within: NULL argument");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(counts) & 3) == 0 && (reinterpret_cast<uintptr_t>(pair_counts) & 7) == 0,
+                 "spatial_count_within: misaligned argument");
+    int R = 0;                                                            // isqrt(top)
+    while ((long long)(R + 1) * (R + 1) <= top) ++R;
+    const int box = R < (H > W ? H : W) ? R : (H > W ? H : W);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    fill(counts, P * n_radii, -1, st);
+    fill(reinterpret_cast<int32_t*>(pair_counts), 2LL * N * n_radii, 0, st);
+    plan_build(plan, pts, off, limit, P, other, other_off, other_limit, P_other, flags, workspace, st);
+    const dim3 grid((unsigned)(plan.g.N * plan.g.nb)), block(kThreads);
+    unsigned long long* pc = reinterpret_cast<unsigned long long*>(pair_counts);
+    if (P > 0) {
+        if (plan.self) hipLaunchKernelGGL(spatial_within_kernel<true>, grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, radii, n_radii, R, box, counts, pc);
+        else hipLaunchKernelGGL(spatial_within_kernel<false>, grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, radii, n_radii, R, box, counts, pc);
+    }
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_spatial_bin_counts(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bin,
+                                     int32_t* out, void* stream) {
+    Grid g;
+    CS_CHECK_ARG(make_grid(N, H, W, bin, g), "spatial_bin_counts: need 0 < N <= 65535, H^2 + W^2 < 2^31, bin >= 1 and at most 2^22 bins");
+    CS_CHECK_ARG(P >= 0 && P < (1LL << 31), "spatial_bin_counts: need 0 <= P < 2^31 rows");
+    CS_CHECK_ARG(off && out && (pts || P == 0), "spatial_bin_counts: NULL argument");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(pts) & 7) == 0 && (reinterpret_cast<uintptr_t>(off) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(out) & 3) == 0, "spatial_bin_counts: misaligned argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Points p = {pts, off, limit, P, 0};
+    const Cells c = {out, nullptr, nullptr};
+    fill(out, (long long)N * g.nb, 0, st);
+    const unsigned blocks = (unsigned)((P + kThreads - 1) / kThreads);
+    if (blocks) hipLaunchKernelGGL(spatial_count_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, p, g, c);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}

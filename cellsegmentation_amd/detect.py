@@ -250,6 +250,20 @@ class DetectResult:
         from . import score as S
         N = len(self.offsets) - 1
         radius2 = S.radius_squared(radius)
+        points, offsets = self._per_map(points, offsets)
+        prepared = S._prepare(points, offsets, N, gt_xy)
+        limits = S._limits(self.cell_counts, N)
+        if self.device_points is None:
+            hat, off = torch.from_numpy(np.ascontiguousarray(self.points, dtype=np.int64)), torch.from_numpy(np.ascontiguousarray(self.offsets, dtype=np.int64))
+            hat, off = hat.reshape(-1, 2).to(_device()), off.to(_device())
+        else:
+            hat, off = self.device_points, self.device_offsets
+        return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
+
+    def _per_map(self, points, offsets):
+        """a second point set in one of the forms ``score`` lists -> (points [G, 2], offsets [N + 1] or None for a single map)"""
+        from . import score as S
+        N = len(self.offsets) - 1
         if offsets is None:
             if isinstance(points, (list, tuple)):
                 if len(points) != N:
@@ -262,14 +276,41 @@ class DetectResult:
                 points = points.reshape(-1, 2)
             elif N != 1:
                 raise ValueError(f"{N} maps: pass one point array per map, or offsets")
-        prepared = S._prepare(points, offsets, N, gt_xy)
-        limits = S._limits(self.cell_counts, N)
+        return points, offsets
+
+    def _own_points(self):
+        """the detections where they are: the device buffers when ``_detect`` left them, else the host arrays"""
         if self.device_points is None:
-            hat, off = torch.from_numpy(np.ascontiguousarray(self.points, dtype=np.int64)), torch.from_numpy(np.ascontiguousarray(self.offsets, dtype=np.int64))
-            hat, off = hat.reshape(-1, 2).to(_device()), off.to(_device())
-        else:
-            hat, off = self.device_points, self.device_offsets
-        return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
+            return np.asarray(self.points, np.int64).reshape(-1, 2), np.asarray(self.offsets, np.int64)
+        return self.device_points, self.device_offsets
+
+    def _neighbours(self, fn, image_hw, arg, other, other_offsets, other_xy, _bucket):
+        from . import score as S
+        pts, off = self._own_points()
+        kw = {}
+        if other is not None:
+            kw["other"], kw["other_offsets"] = self._per_map(other, other_offsets)
+            kw["other_xy"] = other_xy
+        res = fn(pts, image_hw, arg, offsets=off, limits=S._limits(self.cell_counts, len(self.offsets) - 1), _bucket=_bucket, **kw)
+        rows = int(self.offsets[-1])                                       # the device buffer holds spare rows after the last map's
+        for name in ("index", "d2", "counts"):
+            if hasattr(res, name):
+                setattr(res, name, getattr(res, name)[:rows])
+        return res
+
+    def nearest(self, image_hw, k=1, other=None, other_offsets=None, other_xy=False, _bucket=None):
+        """The k nearest neighbours of every map's kept detections -- ``per_image()[n][0]``, i.e. ``cell_counts`` applied as the limit,
+        as in ``score`` -- among themselves, or among a second point set ``other`` given in one of the forms ``score`` takes its
+        annotations in (``other_xy`` as ``gt_xy`` there) -> spatial.NeighborTable, one row per row of ``points`` (spatial.nearest has
+        the rules).  ``image_hw``: the (H, W) of the maps.  The device-resident points are read where they are."""
+        from . import spatial as Sp
+        return self._neighbours(Sp.nearest, image_hw, k, other, other_offsets, other_xy, _bucket)
+
+    def count_within(self, image_hw, radii, other=None, other_offsets=None, other_xy=False, _bucket=None):
+        """The number of kept detections (or of points of ``other``) within each of ``radii`` of every kept detection, and the
+        per-map sums -> spatial.WithinCounts (spatial.count_within has the rules); the arguments are those of ``nearest``."""
+        from . import spatial as Sp
+        return self._neighbours(Sp.count_within, image_hw, radii, other, other_offsets, other_xy, _bucket)
 
     def split(self, masks, connectivity=1, geodesic=False):
         """Split the cells of ``masks`` (bool [N, H, W], or [H, W] for one map: the segmentation the detections belong to) at every

@@ -388,6 +388,29 @@ def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_thres
     return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts
 
 
+def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
+    """Neighbourhood statistics of the detected cells of a ``SlideResult``, on the device: ``result.points`` is uploaded once and
+    queried on the bucket grid of ``spatial`` with the mask's shape as the image -> ``(NeighborTable or None, WithinCounts or
+    None)``: the ``k`` nearest detections of every detection (``k=0``: not asked for) and the number of detections within each of
+    ``radii`` of it (empty: not asked for).  ``other``: an integer [m, 2] point set (annotations, another cell class; ``other_xy``
+    as in ``score.score_points``) to query against instead of the detections themselves.  Both tables stay device tensors, row i
+    being ``result.points[i]``; nothing synchronises."""
+    from . import spatial as Sp
+    from .score import _points
+    if not isinstance(result, SlideResult):
+        raise TypeError("slide_neighbors: expected the SlideResult of detect_slide")
+    hw = tuple(int(v) for v in result.mask.shape)
+    pts = np.asarray(result.points, np.int64).reshape(-1, 2)
+    kw = {}
+    if other is not None:
+        kw = {"other": _points(other, "slide_neighbors: other")[0], "other_xy": other_xy}
+    radii = [radii] if np.isscalar(radii) else list(radii)
+    dev_pts = torch.from_numpy(pts).to(result.mask.device)
+    near = Sp.nearest(dev_pts, hw, k, **kw) if k else None
+    within = Sp.count_within(dev_pts, hw, radii, **kw) if radii else None
+    return near, within
+
+
 def _batch_points(points, n):
     """the annotations of a batch as the loader yields them -> a list of n [k, 2] arrays: a list of per-image arrays, or the
     [n, k, 2] tensor the default collate makes of equally long lists (batch size 1 in the reference)"""

@@ -1677,6 +1677,116 @@ def score_points(hat, hat_off, gt, gt_off, limits=None, radius2=256, want_match=
     return counts, match
 
 
+# ---------------------------------------------------------------- neighbourhood queries over points (csrc/spatial.hip; spatial.py is the public API)
+def spatial_workspace(N, H, W, bucket, P, P_other, device):
+    """the caller-owned scratch of one cs_spatial_nearest / cs_spatial_count_within call; P_other = -1 without a second point set"""
+    why = (f"spatial: a call takes 0 < N <= 65535 images with H^2 + W^2 < 2^31 and at most 2^22 buckets, got "
+           f"{(N, H, W)} with buckets of side {bucket}")
+    return _workspace(_lib.load().cs_spatial_workspace, device, why, int(N), int(H), int(W), int(bucket), int(P), int(P_other))
+
+
+def _spatial_args(what, pts, off, limits, other, other_off, other_limits):
+    """the operand checks the two query wrappers share -> (pts, off, limits, other, other_off, other_limits) contiguous, N"""
+    def need(t, name, dtype, tail):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a torch tensor")
+        if t.dtype != dtype:
+            raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"{what}: {name} must be shaped [n{''.join(f', {v}' for v in tail)}], got {tuple(t.shape)}")
+        if not t.is_cuda or t.device != off.device:
+            raise ValueError(f"{what}: {name} must live on the device of off")
+        return t.contiguous()
+
+    if not torch.is_tensor(off) or not off.is_cuda:
+        raise ValueError(f"{what}: off must be a device tensor")
+    off = need(off, "off", torch.int64, ())
+    N = off.numel() - 1
+    if N < 1 or N > 65535:
+        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images, got {N}")
+    pts = need(pts, "pts", torch.int64, (2,))
+    if limits is not None:
+        limits = need(limits, "limits", torch.int32, ())
+        if limits.numel() != N:
+            raise ValueError(f"{what}: {N} images but {limits.numel()} limits")
+    if other_off is None:
+        if other is not None or other_limits is not None:
+            raise ValueError(f"{what}: a second point set needs its offsets")
+    else:
+        other_off = need(other_off, "other_off", torch.int64, ())
+        if other_off.numel() != N + 1:
+            raise ValueError(f"{what}: {N + 1} offsets but {other_off.numel()} offsets of the second point set")
+        other = need(other, "other", torch.int64, (2,))
+        if other_limits is not None:
+            other_limits = need(other_limits, "other_limits", torch.int32, ())
+            if other_limits.numel() != N:
+                raise ValueError(f"{what}: {N} images but {other_limits.numel()} limits of the second point set")
+    return pts, off, limits, other, other_off, other_limits, N
+
+
+def _spatial_common(a, H, W, bucket, ws):
+    """-> the leading arguments of both query entry points, the workspace"""
+    pts, off, limits, other, other_off, other_limits, N = a
+    P, Q = int(pts.shape[0]), -1 if other_off is None else int(other.shape[0])
+    if ws is None:
+        ws = spatial_workspace(N, H, W, bucket, P, Q, pts.device)
+    head = (_p(pts) if P else None, _p(off), _p(limits), P, _p(other) if Q > 0 else None, _p(other_off), _p(other_limits), max(Q, 0), N,
+            int(H), int(W), int(bucket))
+    return head, ws
+
+
+def spatial_nearest(pts, off, H, W, bucket, k=1, limits=None, other=None, other_off=None, other_limits=None, other_xy=False,
+                    index=None, d2=None, ws=None):
+    """pts int64 [P,2] (row, col) with off int64 [N+1] and limits int32 [N] | None; optionally a second set other / other_off /
+    other_limits of the same layout (other_xy: its rows are (col, row)) -> (index int32 [P,k], d2 int32 [P,k]) on the device: the
+    k smallest keys (d2, index within the image) among the live targets of every live point, (-1, -1) beyond their number, (-2, -1)
+    in the rows that are not live (cs_spatial_nearest in include/cellseg_hip.h)"""
+    a = _spatial_args("spatial_nearest", pts, off, limits, other, other_off, other_limits)
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError(f"spatial_nearest: k must be in 1..8, got {k}")
+    head, ws = _spatial_common(a, H, W, bucket, ws)
+    P = int(a[0].shape[0])
+    t = _regions_outputs("spatial_nearest", {"index": ((P, k), torch.int32), "d2": ((P, k), torch.int32)}, {"index": index, "d2": d2},
+                         a[0].device)
+    _lib.check(_lib.load().cs_spatial_nearest(*head, k, int(bool(other_xy)), _p(t["index"]) if P else None, _p(t["d2"]) if P else None,
+                                              _p(ws), ws.numel(), _stream()), "spatial_nearest")
+    return t["index"], t["d2"]
+
+
+def spatial_count_within(pts, off, H, W, bucket, radii2, limits=None, other=None, other_off=None, other_limits=None, other_xy=False,
+                         counts=None, pair_counts=None, ws=None):
+    """spatial_nearest's operands and radii2, 1 to 8 host integers in [0, 2^31) -> (counts int32 [P,R], pair_counts int64 [N,R]) on
+    the device: the live targets with d2 <= radii2[j] of every live point (-1 in the rows that are not live) and their per-image
+    sums (cs_spatial_count_within in include/cellseg_hip.h)"""
+    a = _spatial_args("spatial_count_within", pts, off, limits, other, other_off, other_limits)
+    r2 = [int(v) for v in radii2]
+    if not 1 <= len(r2) <= 8 or any(v < 0 or v >= 1 << 31 for v in r2):
+        raise ValueError(f"spatial_count_within: 1 to 8 radii2 in [0, 2^31), got {r2}")
+    head, ws = _spatial_common(a, H, W, bucket, ws)
+    P, N, R = int(a[0].shape[0]), a[6], len(r2)
+    t = _regions_outputs("spatial_count_within", {"counts": ((P, R), torch.int32), "pair_counts": ((N, R), torch.int64)},
+                         {"counts": counts, "pair_counts": pair_counts}, a[0].device)
+    _lib.check(_lib.load().cs_spatial_count_within(*head, (ctypes.c_int32 * R)(*r2), R, int(bool(other_xy)), _p(t["counts"]) if P else None,
+                                                   _p(t["pair_counts"]), _p(ws), ws.numel(), _stream()), "spatial_count_within")
+    return t["counts"], t["pair_counts"]
+
+
+def spatial_bin_counts(pts, off, H, W, bin, limits=None, out=None):
+    """pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None -> int32 [N, ceil(H/bin), ceil(W/bin)] on the device: the live
+    points per square bin (cs_spatial_bin_counts in include/cellseg_hip.h)"""
+    pts, off, limits, _, _, _, N = _spatial_args("spatial_bin_counts", pts, off, limits, None, None, None)
+    bin = int(bin)
+    if bin < 1:
+        raise ValueError(f"spatial_bin_counts: bin must be positive, got {bin}")
+    P = int(pts.shape[0])
+    shape = (N, -(-int(H) // bin), -(-int(W) // bin))
+    out = _regions_outputs("spatial_bin_counts", {"out": (shape, torch.int32)}, {"out": out}, pts.device)["out"]
+    _lib.check(_lib.load().cs_spatial_bin_counts(_p(pts) if P else None, _p(off), _p(limits), P, N, int(H), int(W), bin, _p(out), _stream()),
+               "spatial_bin_counts")
+    return out
+
+
 # ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
 def stage_augmented_workspace(n_tiles, device):
     """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""

@@ -1,0 +1,204 @@
+"""Neighbourhood statistics of detected cells on the HIP path (csrc/spatial.hip): the nearest neighbours of every point, the number
+of points within a radius of it, and the density map -- exact integer work on a bucket grid, for a ragged batch of images at once.
+
+Points are integer (row, col) rows; image n owns ``points[offsets[n]:offsets[n + 1]]`` (``offsets=None``: one image), numpy or
+torch, on the host or the device, as ``score.score_points`` takes them.  ``limits`` (None, one count or one per image) applies
+Python's slice ``[:c]`` to every image's points, which is what ``DetectResult.per_image`` does with a regression count.  A point
+is *live* when it is within its image's limit and inside ``[0, H) x [0, W)`` of ``image_hw = (H, W)``; ``H^2 + W^2 < 2^31``, so every
+squared distance fits an int32.  A point that is not live neither asks nor answers: its output rows hold -2 (index) and -1 (squared
+distance, count), the convention of ``ScoreResult.match``.
+
+The targets are the points themselves, or a second set ``other`` / ``other_offsets`` / ``other_limits`` per image (``other_xy``:
+its rows are (x, y), as ``gt_xy`` of ``score_points``).  Among themselves a point is never its own neighbour -- the same row of the
+buffer -- but another point at the same coordinates is a neighbour at distance 0; against a second set nothing is excluded.  Images
+share nothing.  An index is the target's index within its image.
+
+Every result is decided by integer comparisons: neighbours are ordered by the key (d2, index), so equal distances go to the lower
+index, and the counts are sums of integers.  Nothing depends on the bucket side, which is chosen on the host from the sizes alone
+(``choose_bucket``): launch grids and the workspace are independent of the data, nothing synchronises, and a call can be captured
+under ``torch.cuda.graph``.
+"""
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from ._args import _device
+from .score import _limits, _offsets, _points, radius_squared
+
+THREADS = 256                  # workgroup width of the query kernels           (cs_spatial_threads)
+CHUNK = 512                    # candidate records staged in LDS at a time       (cs_spatial_chunk)
+MAX_BUCKETS = 1 << 22          # buckets of one call, all images together        (cs_spatial_max_buckets)
+MAX_K = 8
+MAX_RADII = 8
+OCCUPANCY = 8                  # targets per bucket that choose_bucket aims at
+
+
+@dataclass
+class NeighborTable:
+    """``index``, ``d2`` int32 [P, k] on the device: column j of a live row holds the (j + 1)-th smallest key (d2, index within the
+    image) among the live targets of the row's image, (-1, -1) beyond their number; rows that are not live hold (-2, -1)."""
+    index: torch.Tensor
+    d2: torch.Tensor
+
+    def distance(self):
+        """float64 [P, k] on the device: sqrt(d2) in pixels, NaN where there is no neighbour"""
+        d = self.d2.to(torch.float64)
+        return torch.where(self.d2 >= 0, d.clamp(min=0).sqrt(), torch.full_like(d, float("nan")))
+
+
+@dataclass
+class WithinCounts:
+    """``counts`` int32 [P, R]: the live targets within each radius of every live point (-1 in the rows that are not live);
+    ``pair_counts`` int64 [N, R]: their per-image sums.  ``radii2``: the integer ``floor(r^2)`` the kernel compared against."""
+    counts: torch.Tensor
+    pair_counts: torch.Tensor
+    radii2: tuple
+
+
+def check_image_hw(image_hw):
+    """(H, W) positive integers with H^2 + W^2 < 2^31 (the rule of ``detect._check_dt_shape``) -> (H, W)"""
+    try:
+        H, W = image_hw
+    except (TypeError, ValueError):
+        raise TypeError(f"image_hw: expected (H, W), got {image_hw!r}") from None
+    for v in (H, W):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"image_hw: expected two integers, got {image_hw!r}")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"image_hw: expected positive sizes, got {(H, W)}")
+    if H * H + W * W >= 1 << 31:
+        raise ValueError(f"image_hw: H^2 + W^2 must stay below 2^31 (squared distances are int32), got {(H, W)}")
+    return H, W
+
+
+def n_buckets(H, W, b):
+    return -(-H // b) * -(-W // b)
+
+
+def choose_bucket(H, W, n_images, n_targets, reach=0):
+    """The side b of the square buckets, from sizes known on the host only: about ``OCCUPANCY`` targets per bucket were they spread
+    evenly (b = ceil(sqrt(OCCUPANCY N H W / n_targets))), at least half the largest radius ``reach`` (so that the box of a radius
+    query spans a handful of bucket rows, not dozens), at most max(H, W), then raised until the call's N ceil(H / b) ceil(W / b)
+    buckets fit ``MAX_BUCKETS``."""
+    b = math.isqrt(max(OCCUPANCY * n_images * H * W // max(int(n_targets), 1) - 1, 0)) + 1
+    b = max(b, -(-int(reach) // 2), 1)
+    b = min(b, max(H, W))
+    while n_images * n_buckets(H, W, b) > MAX_BUCKETS:
+        b += max(1, b // 8)
+    return min(b, max(H, W))
+
+
+def _check_bucket(_bucket, H, W, n_images):
+    if isinstance(_bucket, bool) or not isinstance(_bucket, (int, np.integer)) or _bucket < 1:
+        raise ValueError(f"_bucket must be a positive integer, got {_bucket!r}")
+    b = min(int(_bucket), max(H, W))
+    if n_images * n_buckets(H, W, b) > MAX_BUCKETS:
+        raise ValueError(f"_bucket={_bucket}: {n_images} images of {n_buckets(H, W, b)} buckets exceed the {MAX_BUCKETS} of one call")
+    return b
+
+
+class _PointSet:
+    """One checked point set: nothing here touches the device until ``upload``."""
+
+    def __init__(self, points, offsets, limits, n_images, what):
+        self.pts, self.is_torch = _points(points, what)
+        self.off, self.off_dev = _offsets(offsets, self.pts.shape[0], n_images, f"{what} offsets")
+        self.n_images = (len(self.off) if self.off is not None else self.off_dev.numel()) - 1
+        if self.n_images < 1 or self.n_images > 65535:
+            raise ValueError(f"{what}: a call takes 1 to 65535 images, got {self.n_images}")
+        self.lim = _limits(limits, self.n_images)
+        if not self.is_torch and self.pts.size and self.pts.dtype == np.uint64:
+            self.pts = self.pts.astype(np.int64)                           # _points has checked that it fits
+        self.rows = int(self.pts.shape[0])
+        if self.rows >= 1 << 31:
+            raise ValueError(f"{what}: a call takes fewer than 2^31 points")
+
+    def upload(self, dev):
+        pts = self.pts if self.is_torch else torch.from_numpy(np.ascontiguousarray(self.pts.astype(np.int64)))
+        self.pts_dev = pts.to(device=dev, dtype=torch.int64).contiguous()
+        self.off_dev = self.off_dev.to(dev) if self.off is None else torch.from_numpy(self.off).to(dev)
+        lim = self.lim
+        if lim is not None:
+            lim = (lim if torch.is_tensor(lim) else torch.from_numpy(lim)).to(device=dev, dtype=torch.int32).contiguous()
+        self.lim_dev = lim
+        return self
+
+
+def _sets(what, points, offsets, limits, other, other_offsets, other_limits, other_xy):
+    q = _PointSet(points, offsets, limits, None, f"{what}: points")
+    if other is None:
+        if other_offsets is not None or other_limits is not None or other_xy:
+            raise ValueError(f"{what}: other_offsets, other_limits and other_xy describe `other`, which was not given")
+        return q, None
+    return q, _PointSet(other, other_offsets, other_limits, q.n_images, f"{what}: other")
+
+
+def _bucket_for(_bucket, H, W, q, t, reach=0):
+    if _bucket is not None:
+        return _check_bucket(_bucket, H, W, q.n_images)
+    return choose_bucket(H, W, q.n_images, (t or q).rows, reach)
+
+
+def _upload(q, t, *args):
+    dev = _device(*args)
+    q.upload(dev)
+    if t is None:
+        return {}
+    t.upload(dev)
+    return {"other": t.pts_dev, "other_off": t.off_dev, "other_limits": t.lim_dev}
+
+
+def nearest(points, image_hw, k=1, offsets=None, limits=None, other=None, other_offsets=None, other_limits=None, other_xy=False,
+            _bucket=None):
+    """The k nearest live targets of every live point -> ``NeighborTable`` (module docstring: inputs, live points, targets).
+    Column j holds the (j + 1)-th smallest key (d2, index); equal distances go to the lower index; columns beyond the number of
+    candidates hold (-1, -1).  ``1 <= k <= 8``.  ``_bucket`` (tests, tools/spatial_microbench.py): the bucket side instead of
+    ``choose_bucket``'s; the result does not depend on it."""
+    H, W = check_image_hw(image_hw)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+        raise ValueError(f"nearest: k must be an integer in 1..{MAX_K}, got {k!r}")
+    q, t = _sets("nearest", points, offsets, limits, other, other_offsets, other_limits, other_xy)
+    b = _bucket_for(_bucket, H, W, q, t)
+    kw = _upload(q, t, points, offsets, other, other_offsets)
+    index, d2 = K.spatial_nearest(q.pts_dev, q.off_dev, H, W, b, int(k), limits=q.lim_dev, other_xy=other_xy, **kw)
+    return NeighborTable(index, d2)
+
+
+def count_within(points, image_hw, radii, offsets=None, limits=None, other=None, other_offsets=None, other_limits=None,
+                 other_xy=False, _bucket=None):
+    """The number of live targets within each radius of every live point -> ``WithinCounts``.  ``radii``: one non-negative number
+    or up to 8; a target counts when its integer ``d2 <= floor(r^2)`` (``score.radius_squared``), i.e. exactly where ``sqrt(d2) <=
+    r``, so radius 0 counts coincident points only.  Among the points themselves a point does not count itself and the counts
+    are ORDERED pairs: a pair of points within r of each other adds one to each of the two rows and two to ``pair_counts`` -- the
+    raw ingredient of Ripley's K, without edge correction.  All radii are served by one pass over the box of the largest."""
+    H, W = check_image_hw(image_hw)
+    rs = [radii] if isinstance(radii, (int, float, np.integer, np.floating)) and not isinstance(radii, bool) else radii
+    try:
+        rs = list(rs)
+    except TypeError:
+        raise TypeError(f"count_within: radii must be a number or a sequence of numbers, got {radii!r}") from None
+    if not 1 <= len(rs) <= MAX_RADII:
+        raise ValueError(f"count_within: 1 to {MAX_RADII} radii in one call, got {len(rs)}")
+    r2 = tuple(radius_squared(r) for r in rs)
+    q, t = _sets("count_within", points, offsets, limits, other, other_offsets, other_limits, other_xy)
+    b = _bucket_for(_bucket, H, W, q, t, reach=min(math.isqrt(max(r2)), max(H, W)))
+    kw = _upload(q, t, points, offsets, other, other_offsets)
+    counts, pairs = K.spatial_count_within(q.pts_dev, q.off_dev, H, W, b, r2, limits=q.lim_dev, other_xy=other_xy, **kw)
+    return WithinCounts(counts, pairs, r2)
+
+
+def bin_counts(points, image_hw, bin, offsets=None, limits=None):
+    """The number of live points per square bin of side ``bin`` pixels -> int32 [N, ceil(H / bin), ceil(W / bin)] on the device: the
+    density map, and the grid's own count pass.  At most ``MAX_BUCKETS`` bins in one call."""
+    H, W = check_image_hw(image_hw)
+    if isinstance(bin, bool) or not isinstance(bin, (int, np.integer)) or bin < 1:
+        raise ValueError(f"bin_counts: bin must be a positive integer, got {bin!r}")
+    q = _PointSet(points, offsets, limits, None, "bin_counts: points")
+    if q.n_images * n_buckets(H, W, int(bin)) > MAX_BUCKETS:
+        raise ValueError(f"bin_counts: {q.n_images} images of {n_buckets(H, W, int(bin))} bins exceed the {MAX_BUCKETS} of one call")
+    _upload(q, None, points, offsets)
+    return K.spatial_bin_counts(q.pts_dev, q.off_dev, H, W, int(bin), limits=q.lim_dev)

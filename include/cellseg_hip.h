@@ -846,6 +846,41 @@ size_t cs_score_workspace(int N, long long total_gt);
 int cs_score_points(const int64_t* hat, const int64_t* hat_off, const int32_t* hat_limit, const int32_t* gt, const int64_t* gt_off, int N,
                     int radius2, int flags, int32_t* counts, int32_t* match, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- neighbourhood queries over integer points on a bucket grid (csrc/spatial.hip) ------------------------------------------
+ * N images that share nothing, 0 < N <= 65535, all H x W with H^2 + W^2 < 2^31.  pts int64 [P][2] = (row, col) with off int64
+ * [N + 1] are out_pts / out_off of cs_detect_cluster as they are (the buffer may hold more rows than off[N]); limit (int32 [N], or
+ * NULL) applies Python's slice [:c] as hat_limit of cs_score_points does.  A point is LIVE when its limit keeps it and it lies
+ * inside [0, H) x [0, W); only live points ask or answer.  The targets are the points themselves (other_off NULL; then other and
+ * other_limit are NULL and P_other is 0: a row is never its own neighbour, another row at the same coordinates is one at
+ * distance 0) or a second set other / other_off / other_limit / P_other of the same layout (flags bit 0: its rows are (col, row));
+ * an index is the target's index within its image.  An image whose offsets do not describe rows of its buffer has no live point.
+ * bucket: the side in pixels of the square buckets, >= 1 (a side above max(H, W) means one bucket); N ceil(H / bucket)
+ * ceil(W / bucket) may not exceed cs_spatial_max_buckets().  No result depends on it.
+ * cs_spatial_nearest      : index, d2 int32 [P][k], 1 <= k <= 8: column j of a live row holds the (j + 1)-th smallest key (d2, index)
+ *                           among the live targets of its image, (-1, -1) beyond their number; every other row holds (-2, -1).
+ * cs_spatial_count_within : radii2 (host) int32 [n_radii], 1 <= n_radii <= 8, each >= 0.  counts int32 [P][n_radii]: the live
+ *                           targets with d2 <= radii2[j], the row itself excluded when the targets are the points; -1 in the rows
+ *                           that are not live.  pair_counts int64 [N][n_radii]: the sums of counts over the live rows of each image.
+ * cs_spatial_bin_counts   : out int32 [N][ceil(H / bin)][ceil(W / bin)]: the live points per square bin, the grid's own count pass
+ *                           (the same cap on the number of bins).  No workspace.
+ * A fixed sequence of launches on one stream for given (P, P_other, N, H, W, bucket, k), no host synchronisation: capturable.
+ * workspace: 16-byte aligned, >= cs_spatial_workspace(N, H, W, bucket, P, P_other) bytes, P_other = -1 without a second set
+ * (0 for sizes a call would refuse); its contents on entry do not matter.  cs_spatial_threads / cs_spatial_chunk: the workgroup
+ * width of the query kernels and the number of candidate records they stage in LDS at a time (the tests size their cases by them). */
+int cs_spatial_threads(void);
+int cs_spatial_chunk(void);
+long long cs_spatial_max_buckets(void);
+size_t cs_spatial_workspace(int N, int H, int W, int bucket, long long P, long long P_other);
+int cs_spatial_nearest(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, const int64_t* other,
+                       const int64_t* other_off, const int32_t* other_limit, long long P_other, int N, int H, int W, int bucket, int k,
+                       int flags, int32_t* index, int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
+int cs_spatial_count_within(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, const int64_t* other,
+                            const int64_t* other_off, const int32_t* other_limit, long long P_other, int N, int H, int W, int bucket,
+                            const int32_t* radii2, int n_radii, int flags, int32_t* counts, int64_t* pair_counts, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int cs_spatial_bin_counts(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bin,
+                          int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
