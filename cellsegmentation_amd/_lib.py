@@ -136,6 +136,8 @@ _SIGNATURES = {
     "cs_stem_pair_input": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "cs_stem_pair_from_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "cs_stem_fwd_packed": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "cs_stem_pool_fwd_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "cs_stem_pool_fwd": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "cs_stem_pair_weights": (c_int, [_P, c_int, c_int, _P, _P]),
     "cs_stem_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "cs_stem_wgrad_splits": (c_int, [c_int, c_int, c_int, c_int]),

@@ -33,6 +33,7 @@ ACT_NONE, ACT_RELU, ACT_SILU = K.CS_ACT_NONE, K.CS_ACT_RELU, K.CS_ACT_SILU
 
 PACKED = True              # packed-operand conv kernels (False: first-generation igemm everywhere; tests flip it for a reference path)
 PACKED_TRAIN_BN = True     # ... also for heavy 3x3 convolutions under batch-statistics BN
+FUSE_STEM_POOL = True      # eval-BN bf16 stem + ReLU + the max-pool behind it in one launch (False: the two launches; tests compare the two)
 
 
 class ConvUnit:
@@ -97,6 +98,16 @@ class ConvUnit:
             # one bit per output next to a ReLU output of a pass that will run backward: the data gradient that later masks with
             # this tensor reads 1 byte per 16 (the bf16 masks are ~1/8 of a training step's HBM traffic)
             want_bits = f.save and self.act == ACT_RELU
+            pool_ui = None
+            if stem and PACKED and FUSE_STEM_POOL and self.act == ACT_RELU and K.stem_pool_fwd_supported(geom, f.dtype):
+                pool_ui = _sole_pool_consumer(f.plan, self)
+            if pool_ui is not None:
+                # stem + max-pool in one launch: the pool's slot and aux are stored here, this unit's own slot is never materialised
+                # (backward needs the pooled gradient, the tap plane and xp only); the PoolUnit finds its work done
+                f.t[f.plan.units[pool_ui].dst], am = K.stem_pool_fwd(geom, xp, wp, st.shift, want_argmax=f.save)
+                f.aux[pool_ui] = SimpleNamespace(argmax=am, in_hw=(geom.P, geom.Q))
+                f.aux[ui] = SimpleNamespace(geom=geom, st=st, train=False, xp=xp)
+                return
             if stem and PACKED and K.stem_fwd_packed_supported(geom, f.dtype):
                 y = K.stem_fwd_packed(geom, xp, K.stem_pack_weights(wp), st.shift, self.act)       # ring kernel, gathered rows
             elif stem:
@@ -262,6 +273,8 @@ class PoolUnit:
         return [self.src]
 
     def fwd(self, f, ui):
+        if f.aux[ui] is not None:
+            return          # the stem in front pooled its own output (ConvUnit.fwd, FUSE_STEM_POOL)
         x = f.t[self.src]
         f.t[self.dst], am = K.maxpool_fwd(x, want_argmax=f.save)
         f.aux[ui] = SimpleNamespace(argmax=am, in_hw=tuple(x.shape[1:3]))
@@ -362,6 +375,16 @@ def _is_paired_stem(u):
     c = u.conv
     return (not u.grouped and u.res is None and c.in_channels <= 3 and c.kernel_size == (7, 7)
             and c.stride == (2, 2) and c.padding == (3, 3))
+
+
+def _sole_pool_consumer(plan, u):
+    """Index of the PoolUnit that is the ONLY reader of conv unit u's output (which is no plan output either), else None."""
+    if plan.consumers.get(u.dst, 0) != 1 or u.dst in plan.outputs:
+        return None
+    for vi, v in enumerate(plan.units):
+        if u.dst in v.inputs():
+            return vi if v.kind == "pool" else None
+    return None
 
 
 def _stem_takes_nchw(plan, dtype):

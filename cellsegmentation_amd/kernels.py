@@ -420,6 +420,24 @@ def stem_fwd_packed(geom, x_pair, w_packed, shift=None, act=CS_ACT_NONE, want_bi
     return (y, bits) if want_bits else y
 
 
+def stem_pool_fwd_supported(geom, dtype):
+    """Does cs_stem_pool_fwd (stem forward + ReLU + MaxPool2d(3, 2, 1) in one launch) serve this stem geometry?"""
+    return (dtype == torch.bfloat16 and is_stem_geom(geom)
+            and bool(_lib.load().cs_stem_pool_fwd_supported(geom.N, geom.H, geom.W, geom.K)))
+
+
+def stem_pool_fwd(geom, x_pair, w_pair, shift, want_argmax=True):
+    """max_pool(relu(stem(x) + shift)) of the stem geometry `geom` without the stem map in between: (y_pool, argmax or None), the
+    values maxpool_fwd(stem_fwd_packed(...)) returns.  w_pair: the paired weights [K,7,4,8] of stem_pair_weights."""
+    PP, PQ = (geom.P - 1) // 2 + 1, (geom.Q - 1) // 2 + 1
+    y = torch.empty((geom.N, PP, PQ, geom.K), dtype=x_pair.dtype, device=x_pair.device)
+    am = torch.empty((geom.N, PP, PQ, geom.K), dtype=torch.uint8, device=x_pair.device) if want_argmax else None
+    lib = _lib.load()
+    _lib.check(_timed("fwd", geom, x_pair.dtype, lambda: lib.cs_stem_pool_fwd(
+        geom.N, geom.H, geom.W, geom.K, _p(x_pair), _p(w_pair), _p(shift), _p(y), _p(am), _stream())), "stem_pool_fwd")
+    return y, am
+
+
 def stem_wgrad(geom, x_pair, dy, use_tr_read=True):
     """Raw weight gradient of the stem in the ORDINARY slab layout [1, K, 7, 7, 8] (one slab: the paired split-K slabs are summed
     while they are un-paired), ready for wgrad_finalize / wgrad_finalize_batched."""

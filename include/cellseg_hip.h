@@ -490,6 +490,13 @@ int cs_stem_fwd(int N, int H, int W, int K, int dtype, const void* x_pair, const
  * (C = 256, K) applied to w_pair padded to [K][8][4][8] with one zero filter row; epilogue as cs_conv2d_fwd_packed. */
 int cs_stem_fwd_packed(int N, int H, int W, int K, const void* x_pair, const void* w_packed, const float* shift, int act, void* y,
                        uint8_t* positive_bits, void* stream);
+/* The bf16 stem forward (shift, ReLU) and the MaxPool2d(3, 2, 1) behind it in one launch (stem_pool.hip): the [N][P][Q][K] stem map is
+ * never written.  w_pair as cs_stem_pair_weights leaves it; y_pool[N][PP][PQ][K] with PP = (P - 1) / 2 + 1, PQ = (Q - 1) / 2 + 1;
+ * argmax (nullable) as cs_maxpool3x3s2_fwd writes it.  The values are those of cs_stem_fwd_packed + cs_maxpool3x3s2_fwd, bit for bit.
+ * cs_stem_pool_fwd_supported: 1 where the launch is served (K == 64, H, W >= 7, 32-bit offsets inside one image), else 0. */
+int cs_stem_pool_fwd_supported(int N, int H, int W, int K);
+int cs_stem_pool_fwd(int N, int H, int W, int K, const void* x_pair, const void* w_pair, const float* shift, void* y_pool,
+                     uint8_t* argmax, void* stream);
 int cs_stem_wgrad_splits(int N, int H, int W, int K);
 int cs_stem_wgrad(int N, int H, int W, int K, int dtype, const void* x_pair, const void* dy, float* dw_pair_slabs, int use_tr_read,
                   void* stream);
