@@ -197,15 +197,16 @@ def _segment_batch(model, x, want_counts, zero_empty):
 class SlideResult:
     """One slide of ``detect_slide``: ``points`` / ``discarded`` int64 [n, 2] (row, col) as ``meanshift_cluster`` returns them
     (``discarded`` is ``[]`` without a cap), ``cell_count`` the summed per-patch counts, ``mask`` the stitched uint8 [H, W] device
-    tensor."""
+    tensor, ``tissue`` the ``tissue.TissueResult`` of a run with ``tissue=`` (None without)."""
     points: np.ndarray
     discarded: object
     cell_count: int
     mask: torch.Tensor
+    tissue: object = None
 
 
 def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, interval=None, eps=11, reg_limit=True,
-                 method="gaussianblur", thr_for_dt=10, **blur):
+                 method="gaussianblur", thr_for_dt=10, tissue=None, **blur):
     """The loop of ``cell_detect`` (test_seg.py:182-316) for one slide or ROI, streamed on the device -> SlideResult.
 
     image_u8: uint8 [H, W, 3], numpy or torch; it is moved to the device once.  ``tiles.sample_patches`` gives the (row, col) patch
@@ -218,12 +219,22 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     those of ``detect_cells``; ``interval`` is the patch grid's here, so the seed grid keeps ``meanshift_cluster``'s default of 10, as
     in ``cell_detect``.  ``patch_size`` must be square here (gather_tiles cuts square tiles; ``sample_patches`` itself is general).  The model is left in segment mode and ``eval()``.
 
+    ``tissue`` (not in the reference, which runs every patch): None, the default, reaches none of it.  ``True`` or a
+    ``tissue.TissueOptions`` first decides on the device which patches hold tissue (``tissue.select_patches``: a tissue mask by
+    Otsu's threshold, the tissue pixels under every patch, the patches with enough of them) and runs the loop over those only, in
+    the order of ``sample_patches`` and in batches of ``batch_size`` of the kept list.  Mask pixels that no kept patch covers stay
+    0, the count sums over the kept patches, and ``SlideResult.tissue`` holds the ``TissueResult``.  That costs two small
+    synchronisations before the loop and none inside it; with no patch kept the loop does not run.
+
     Not done here: reading ``.svs`` / ``.png`` files (OpenSlide is not a dependency), writing the CSV and PNG files, and the
     ``name-<xoffset>`` file-name convention -- the caller adds the offset to ``points[:, 1]``.  ``meanshift_cluster(...,
     "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
     from . import detect as D
     from . import tiles as T
     opts = _detect_options("detect_slide", eps, method, thr_for_dt, **blur)   # ``interval`` is the patch grid's: never in blur
+    if tissue is not None:
+        from . import tissue as Ts
+        tissue = Ts._check_options(tissue, "detect_slide: tissue")
     ph, pw = T._pair(patch_size, "patch_size")
     if ph != pw:
         raise ValueError(f"detect_slide cuts square patches (tiles.gather_tiles), got patch_size {(ph, pw)}")
@@ -239,25 +250,30 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     img = img.to(device).contiguous()[None]
     rc = torch.from_numpy(corners).to(device)                              # every corner of the slide, uploaded once
     ti = torch.zeros((len(corners),), dtype=torch.int32, device=device)
+    kept = None
+    if tissue is not None:                                                 # the patches that hold tissue, in the order of the grid
+        kept = Ts._select(img, corners, ti, rc, ph, pw, tissue)
+        rc, ti = rc.index_select(0, kept.selected.long()), ti[:kept.n_selected]
     mask = torch.zeros((H, W), dtype=torch.uint8, device=device)
     total = torch.zeros((), dtype=torch.float64, device=device)
     dtype = getattr(model, "compute_dtype", torch.float32)
     model.eval()
     with torch.no_grad():
-        for i in range(0, len(corners), int(batch_size)):
+        for i in range(0, len(rc), int(batch_size)):
             x = T.gather_tiles(img, ti[i:i + batch_size], rc[i:i + batch_size], ph, dtype)
             model.setmode("segment")
             K.stitch_logits(mask, model(x).float().contiguous(), rc[i:i + batch_size], 1)
             model.setmode("image")
             total += _rounded_counts(model, x).sum(dtype=torch.float64)
     model.setmode("segment")
-    count = int(total.item())                                              # the first synchronisation of the slide
+    count = int(total.item())                                              # the first synchronisation of the slide's loop
     points, discarded = D._detect(mask[None], count if reg_limit else None, opts).per_image()[0]
-    return SlideResult(points, discarded, count, mask)
+    return SlideResult(points, discarded, count, mask, kept)
 
 
 def detect_slides(slides, model, device=None, **kwargs):
-    """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order."""
+    """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order.  ``kwargs`` are
+    ``detect_slide``'s, ``tissue=`` among them."""
     for image_u8 in slides:
         yield detect_slide(image_u8, model, device, **kwargs)
 

@@ -1805,6 +1805,69 @@ def spatial_bin_counts(pts, off, H, W, bin, limits=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------- tissue detection (csrc/tissue.hip; tissue.py is the public API)
+CS_TISSUE_CHROMA, CS_TISSUE_DARKNESS = 0, 1
+
+
+def _tissue_images(what, images_u8):
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise TypeError(f"{what}: images must be a uint8 tensor shaped [N, H, W, 3]")
+    N, H, W, _ = images_u8.shape
+    if not 1 <= N <= 65535 or H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images of 0 < H W < 2^31 pixels, got {(N, H, W)}")
+    return N, H, W
+
+
+def tissue_histogram(images_u8, channel=CS_TISSUE_CHROMA, hist=None):
+    """images uint8 [N,H,W,3] (device) -> int64 [N,256] on the device: the pixels of every image per value of the feature
+    ``channel``.  ``hist``: an int64 [N,256] device tensor to ADD into instead of a zeroed one (cs_tissue_histogram)."""
+    N, H, W = _tissue_images("tissue_histogram", images_u8)
+    if hist is None:
+        hist = torch.zeros((N, 256), dtype=torch.int64, device=images_u8.device)
+    elif not torch.is_tensor(hist) or hist.dtype != torch.int64 or tuple(hist.shape) != (N, 256):
+        raise ValueError(f"tissue_histogram: hist must be an int64 tensor shaped {(N, 256)}")
+    _lib.check(_lib.load().cs_tissue_histogram(_p(images_u8), N, H, W, int(channel), _p(hist), _stream()), "tissue_histogram")
+    return hist
+
+
+def tissue_mask(images_u8, thr, channel=CS_TISSUE_CHROMA, out=None):
+    """images uint8 [N,H,W,3], thr int32 [N] (both on the device) -> uint8 [N,H,W]: feature > thr[n] as 0 / 1 (cs_tissue_mask)"""
+    N, H, W = _tissue_images("tissue_mask", images_u8)
+    if not torch.is_tensor(thr) or thr.dtype != torch.int32 or tuple(thr.shape) != (N,):
+        raise ValueError(f"tissue_mask: thr must be an int32 tensor shaped {(N,)}")
+    out = _regions_outputs("tissue_mask", {"out": ((N, H, W), torch.uint8)}, {"out": out}, images_u8.device)["out"]
+    _lib.check(_lib.load().cs_tissue_mask(_p(images_u8), N, H, W, int(channel), _p(thr), _p(out), _stream()), "tissue_mask")
+    return out
+
+
+def tissue_coverage(mask, tile_img, tile_rc, ph, pw):
+    """mask uint8 [N,H,W], tile_img int32 [T], tile_rc int32 [T,2] (device) -> int32 [T]: the non-zero mask pixels under every
+    ph x pw window, clamped to the image (cs_tissue_coverage)"""
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise TypeError("tissue_coverage: mask must be a uint8 tensor shaped [N, H, W]")
+    N, H, W = mask.shape
+    T = int(tile_img.numel())
+    if tile_img.dtype != torch.int32 or tile_rc.dtype != torch.int32 or tuple(tile_rc.shape) != (T, 2):
+        raise ValueError(f"tissue_coverage: tile_img int32 [T] and tile_rc int32 [T, 2], got {tuple(tile_img.shape)} and {tuple(tile_rc.shape)}")
+    cover = torch.empty((T,), dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().cs_tissue_coverage(_p(mask), N, H, W, _p(tile_img) if T else None, _p(tile_rc) if T else None, T, int(ph), int(pw),
+                                              _p(cover) if T else None, _stream()), "tissue_coverage")
+    return cover
+
+
+def tissue_select(cover, min_pixels):
+    """cover int32 [T] (device) -> (selected int32 [T], n_selected int32 [1]) on the device: the indices with cover >= min_pixels
+    in rising order, -1 from their number on (cs_tissue_select)"""
+    if not torch.is_tensor(cover) or cover.dtype != torch.int32 or cover.dim() != 1:
+        raise TypeError("tissue_select: cover must be an int32 tensor shaped [T]")
+    T = int(cover.numel())
+    selected = torch.empty((T,), dtype=torch.int32, device=cover.device)
+    n_selected = torch.empty((1,), dtype=torch.int32, device=cover.device)
+    _lib.check(_lib.load().cs_tissue_select(_p(cover) if T else None, T, int(min_pixels), _p(selected) if T else None, _p(n_selected), _stream()),
+               "tissue_select")
+    return selected, n_selected
+
+
 # ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
 def stage_augmented_workspace(n_tiles, device):
     """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""

@@ -888,6 +888,29 @@ int cs_spatial_count_within(const int64_t* pts, const int64_t* off, const int32_
 int cs_spatial_bin_counts(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bin,
                           int32_t* out, void* stream);
 
+/* ---- tissue detection for whole-slide streaming (csrc/tissue.hip) -----------------------------------------------------------
+ * images_hwc uint8 [N][H][W][3] (RGB), 0 < N <= 65535, 0 < H W < 2^31; pixel offsets are 64-bit, N H W 3 may pass 2^31.  No
+ * alignment is asked of the images or the masks.  The pixel feature f(r, g, b) in [0, 255] is selected by `channel`:
+ *   CS_TISSUE_CHROMA    max(r, g, b) - min(r, g, b)                      white glass, grey shadow and black pen all score low
+ *   CS_TISSUE_DARKNESS  255 - ((77 r + 150 g + 29 b + 128) >> 8)
+ * All arithmetic is integer and every result is a sum or a comparison of integers: nothing depends on the launch geometry.
+ * cs_tissue_histogram : hist int64 [N][256] += the number of pixels of image n with f = v.  It ADDS: the caller zeroes hist.
+ * cs_tissue_mask      : mask uint8 [N][H][W] = f > thr[n] as 0 / 1; thr int32 [N] is a DEVICE array (a threshold computed on the
+ *                       device needs no round trip); the feature channel is never written anywhere.
+ * cs_tissue_coverage  : cover int32 [T] = the non-zero pixels of mask uint8 [N][H][W] in the window [r, r + ph) x [c, c + pw) of image
+ *                       tile_img[t], (r, c) = tile_rc[t] (int32 [T] and [T][2] on the device, the convention of cs_tile_gather);
+ *                       the window is clamped to the image and an image index outside [0, N) counts 0.  ph, pw > 0, 0 <= T < 2^31.
+ * cs_tissue_select    : selected int32 [T] = the indices t with cover[t] >= min_pixels in rising order, -1 from their number on;
+ *                       n_selected int32 [1] = their number.  One workgroup; T is a number of patches.
+ * One launch each on `stream`, no workspace, no host synchronisation: capturable. */
+#define CS_TISSUE_CHROMA 0
+#define CS_TISSUE_DARKNESS 1
+int cs_tissue_histogram(const uint8_t* images_hwc, int N, int H, int W, int channel, int64_t* hist, void* stream);
+int cs_tissue_mask(const uint8_t* images_hwc, int N, int H, int W, int channel, const int32_t* thr, uint8_t* mask, void* stream);
+int cs_tissue_coverage(const uint8_t* mask, int N, int H, int W, const int32_t* tile_img, const int32_t* tile_rc, long long T, int ph,
+                       int pw, int32_t* cover, void* stream);
+int cs_tissue_select(const int32_t* cover, long long T, int min_pixels, int32_t* selected, int32_t* n_selected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
