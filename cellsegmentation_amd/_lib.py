@@ -205,6 +205,11 @@ _SIGNATURES = {
     "cs_tissue_mask": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "cs_tissue_coverage": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_longlong, c_int, c_int, _P, _P]),
     "cs_tissue_select": (c_int, [_P, c_longlong, c_int, _P, _P, _P]),
+    "cs_stain_moments": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "cs_stain_angle_hist": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
+    "cs_stain_conc_hist": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_float, _P, _P]),
+    "cs_stain_apply": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P]),
+    "cs_stain_separate": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_float, _P, _P]),
 }
 
 _lib = None

@@ -197,16 +197,19 @@ def _segment_batch(model, x, want_counts, zero_empty):
 class SlideResult:
     """One slide of ``detect_slide``: ``points`` / ``discarded`` int64 [n, 2] (row, col) as ``meanshift_cluster`` returns them
     (``discarded`` is ``[]`` without a cap), ``cell_count`` the summed per-patch counts, ``mask`` the stitched uint8 [H, W] device
-    tensor, ``tissue`` the ``tissue.TissueResult`` of a run with ``tissue=`` (None without)."""
+    tensor, ``tissue`` the ``tissue.TissueResult`` of a run with ``tissue=`` (None without).  ``stain``: the slide's own
+    ``stain.StainEstimate`` of a run with ``stain=`` (None without); an attribute that ``detect_slide`` sets, not an argument of
+    the constructor, so that the record's positional fields stay the five they were."""
     points: np.ndarray
     discarded: object
     cell_count: int
     mask: torch.Tensor
     tissue: object = None
+    stain = None
 
 
 def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, interval=None, eps=11, reg_limit=True,
-                 method="gaussianblur", thr_for_dt=10, tissue=None, **blur):
+                 method="gaussianblur", thr_for_dt=10, tissue=None, stain=None, **blur):
     """The loop of ``cell_detect`` (test_seg.py:182-316) for one slide or ROI, streamed on the device -> SlideResult.
 
     image_u8: uint8 [H, W, 3], numpy or torch; it is moved to the device once.  ``tiles.sample_patches`` gives the (row, col) patch
@@ -226,6 +229,13 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     0, the count sums over the kept patches, and ``SlideResult.tissue`` holds the ``TissueResult``.  That costs two small
     synchronisations before the loop and none inside it; with no patch kept the loop does not run.
 
+    ``stain`` (not in the reference either): None, the default, reaches none of it.  ``True``, a ``stain.StainOptions`` or an
+    ``(options, target)`` pair estimates the slide's stain vectors once (``stain.estimate``, over the tissue mask when ``tissue`` is
+    given as well -- the tissue decision itself is taken on the slide as scanned) and writes a Macenko-normalised copy of the slide
+    on the device (``stain.normalize`` towards ``target``, by default ``stain.TARGET_HDAB``); ``gather_tiles`` then reads that copy.
+    ``SlideResult.stain`` holds the slide's own ``StainEstimate``.  The estimate's three small copies to the host happen before
+    the loop; there is none inside it.
+
     Not done here: reading ``.svs`` / ``.png`` files (OpenSlide is not a dependency), writing the CSV and PNG files, and the
     ``name-<xoffset>`` file-name convention -- the caller adds the offset to ``points[:, 1]``.  ``meanshift_cluster(...,
     "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
@@ -235,6 +245,9 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     if tissue is not None:
         from . import tissue as Ts
         tissue = Ts._check_options(tissue, "detect_slide: tissue")
+    if stain is not None:
+        from . import stain as St
+        stain = St._check_slide_argument(stain, "detect_slide: stain")
     ph, pw = T._pair(patch_size, "patch_size")
     if ph != pw:
         raise ValueError(f"detect_slide cuts square patches (tiles.gather_tiles), got patch_size {(ph, pw)}")
@@ -254,6 +267,9 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     if tissue is not None:                                                 # the patches that hold tissue, in the order of the grid
         kept = Ts._select(img, corners, ti, rc, ph, pw, tissue)
         rc, ti = rc.index_select(0, kept.selected.long()), ti[:kept.n_selected]
+    source = None
+    if stain is not None:                                                  # the loop reads the normalised copy from here on
+        img, source = St._normalize_slide(img, None if kept is None else kept.mask[None], *stain)
     mask = torch.zeros((H, W), dtype=torch.uint8, device=device)
     total = torch.zeros((), dtype=torch.float64, device=device)
     dtype = getattr(model, "compute_dtype", torch.float32)
@@ -268,12 +284,14 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     model.setmode("segment")
     count = int(total.item())                                              # the first synchronisation of the slide's loop
     points, discarded = D._detect(mask[None], count if reg_limit else None, opts).per_image()[0]
-    return SlideResult(points, discarded, count, mask, kept)
+    result = SlideResult(points, discarded, count, mask, kept)
+    result.stain = source
+    return result
 
 
 def detect_slides(slides, model, device=None, **kwargs):
     """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order.  ``kwargs`` are
-    ``detect_slide``'s, ``tissue=`` among them."""
+    ``detect_slide``'s, ``tissue=`` and ``stain=`` among them."""
     for image_u8 in slides:
         yield detect_slide(image_u8, model, device, **kwargs)
 
@@ -386,21 +404,29 @@ def _slide_foreground(what, mask_u8, thr_u8, min_object_size, hole_area_threshol
 
 
 def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_threshold=100, connectivity=1, max_regions=None,
-                        opening_radius=0, geodesic=False):
+                        opening_radius=0, geodesic=False, intensity=None):
     """One row per DETECTED cell of a ``SlideResult``: ``measure_slide``'s thresholding and clean-up of ``result.mask``, then
     ``regions.split`` of the foreground at ``result.points`` and ``regions.measure_labels`` with the map as the intensity ->
     ``(RegionTable, SplitResult)`` of one image.  Row k is ``result.points[k]`` (all zero where the point is not live: on the
     background after the clean-up, or a second point on one pixel); the rows from ``len(result.points)`` on are cells that no
     detection claimed.  ``max_regions`` and ``opening_radius`` as in ``measure_slide``: an int ``max_regions`` means no
     synchronisation.  ``geodesic``: ``regions.split_geodesic`` in its exact mode instead of ``regions.split``, so that every cell is
-    one connected piece (it reads a flag back: a synchronisation of its own)."""
+    one connected piece (it reads a flag back: a synchronisation of its own).  ``intensity``: a uint8 ``[H, W]`` map of the mask's
+    shape that takes the place of ``result.mask`` as the intensity of ``measure_labels`` -- the labels still come from the mask --,
+    for example the DAB concentration ``stain.separate(slide, dtype="u8")[..., 1]``."""
     from . import regions as Rg
     if not isinstance(result, SlideResult):
         raise TypeError("measure_slide_cells: expected the SlideResult of detect_slide")
+    if intensity is not None:
+        intensity = _tensor(intensity)
+        if not torch.is_tensor(intensity) or intensity.dtype != torch.uint8 or tuple(intensity.shape) != tuple(result.mask.shape):
+            raise TypeError(f"measure_slide_cells: intensity must be a uint8 map shaped {tuple(result.mask.shape)}")
     t, fg = _slide_foreground("measure_slide_cells", result.mask, thr_u8, min_object_size, hole_area_threshold, connectivity,
                               opening_radius)
     pts = np.asarray(result.points, np.int64).reshape(-1, 2)
     parts = (Rg.split_geodesic if geodesic else Rg.split)(fg, pts, connectivity=connectivity)
+    if intensity is not None:
+        t = intensity.to(t.device).contiguous()
     return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts
 
 

@@ -1868,6 +1868,83 @@ def tissue_select(cover, min_pixels):
     return selected, n_selected
 
 
+# ---------------------------------------------------------------- stain separation and normalisation (csrc/stain.hip; stain.py is the public API)
+def _stain_args(what, images_u8, od_q, mask=None, **mats):
+    """the checks every stain wrapper shares; ``mats``: name -> (fp32 device tensor, its shape after N)"""
+    N, H, W = _tissue_images(what, images_u8)
+    if not torch.is_tensor(od_q) or od_q.dtype != torch.int32 or tuple(od_q.shape) != (256,):
+        raise ValueError(f"{what}: od_q must be an int32 tensor shaped (256,) (stain.od_table)")
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W)):
+        raise ValueError(f"{what}: mask must be a uint8 tensor shaped {(N, H, W)}")
+    for name, (m, shape) in mats.items():
+        if not torch.is_tensor(m) or m.dtype != torch.float32 or tuple(m.shape) != (N,) + shape:
+            raise ValueError(f"{what}: {name} must be a float32 tensor shaped {(N,) + shape}")
+    return N, H, W
+
+
+def _stain_sums(what, given, shape, device):
+    if given is None:
+        return torch.zeros(shape, dtype=torch.int64, device=device)
+    if not torch.is_tensor(given) or given.dtype != torch.int64 or tuple(given.shape) != shape:
+        raise ValueError(f"{what}: out must be an int64 tensor shaped {shape}")
+    return given
+
+
+def stain_moments(images_u8, od_q, beta_q, mask=None, out=None):
+    """images uint8 [N,H,W,3], od_q int32 [256], mask uint8 [N,H,W] or None (device) -> int64 [N,10]: over the kept pixels their
+    number and the sums of od_q r, g, b, rr, rg, rb, gg, gb, bb.  ``out``: an int64 [N,10] tensor to ADD into instead of a zeroed
+    one (cs_stain_moments)."""
+    N, H, W = _stain_args("stain_moments", images_u8, od_q, mask)
+    out = _stain_sums("stain_moments", out, (N, 10), images_u8.device)
+    _lib.check(_lib.load().cs_stain_moments(_p(images_u8), N, H, W, _p(od_q), int(beta_q), _p(mask), _p(out), _stream()), "stain_moments")
+    return out
+
+
+def stain_angle_hist(images_u8, od_q, beta_q, V, bins, mask=None, out=None):
+    """V fp32 [N,3,2] -> int64 [N,bins]: the kept pixels by the angle atan2f(p1, p0) of p = od V over [-pi/2, pi/2); ADDS into
+    ``out`` where given (cs_stain_angle_hist)"""
+    N, H, W = _stain_args("stain_angle_hist", images_u8, od_q, mask, V=(V, (3, 2)))
+    out = _stain_sums("stain_angle_hist", out, (N, int(bins)), images_u8.device)
+    _lib.check(_lib.load().cs_stain_angle_hist(_p(images_u8), N, H, W, _p(od_q), int(beta_q), _p(mask), _p(V), int(bins), _p(out), _stream()),
+               "stain_angle_hist")
+    return out
+
+
+def stain_conc_hist(images_u8, od_q, beta_q, P, bins, conc_max, mask=None, out=None):
+    """P fp32 [N,2,3] -> int64 [N,2,bins]: the kept pixels by each concentration of c = P od over [0, conc_max); ADDS into ``out``
+    where given (cs_stain_conc_hist)"""
+    N, H, W = _stain_args("stain_conc_hist", images_u8, od_q, mask, P=(P, (2, 3)))
+    out = _stain_sums("stain_conc_hist", out, (N, 2, int(bins)), images_u8.device)
+    _lib.check(_lib.load().cs_stain_conc_hist(_p(images_u8), N, H, W, _p(od_q), int(beta_q), _p(mask), _p(P), int(bins), float(conc_max),
+                                              _p(out), _stream()), "stain_conc_hist")
+    return out
+
+
+def stain_apply(images_u8, od_q, A, Io, out=None):
+    """A fp32 [N,3,3] -> uint8 [N,H,W,3]: clamp(rint(Io expf(-(A od))), 0, 255) for every pixel; ``out`` must not be the images
+    (cs_stain_apply)"""
+    N, H, W = _stain_args("stain_apply", images_u8, od_q, A=(A, (3, 3)))
+    out = _regions_outputs("stain_apply", {"out": ((N, H, W, 3), torch.uint8)}, {"out": out}, images_u8.device)["out"]
+    if out.data_ptr() == images_u8.data_ptr():
+        raise ValueError("stain_apply: out must not be the images")
+    _lib.check(_lib.load().cs_stain_apply(_p(images_u8), N, H, W, _p(od_q), _p(A), float(Io), _p(out), _stream()), "stain_apply")
+    return out
+
+
+def stain_separate(images_u8, od_q, P, as_u8=False, conc_max=1.0, out=None):
+    """P fp32 [N,K,3], K = 2 or 3 -> the concentrations P od of every pixel: fp32 [N,H,W,K], or with ``as_u8`` uint8
+    clamp(rint(255 c / conc_max), 0, 255) (cs_stain_separate)"""
+    if not torch.is_tensor(P) or P.dim() != 3 or P.shape[1] not in (2, 3):
+        raise ValueError("stain_separate: P must be a float32 tensor shaped [N, K, 3] with K = 2 or 3")
+    Kn = int(P.shape[1])
+    N, H, W = _stain_args("stain_separate", images_u8, od_q, P=(P, (Kn, 3)))
+    out = _regions_outputs("stain_separate", {"out": ((N, H, W, Kn), torch.uint8 if as_u8 else torch.float32)}, {"out": out},
+                           images_u8.device)["out"]
+    _lib.check(_lib.load().cs_stain_separate(_p(images_u8), N, H, W, _p(od_q), _p(P), Kn, int(bool(as_u8)), float(conc_max), _p(out),
+                                             _stream()), "stain_separate")
+    return out
+
+
 # ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
 def stage_augmented_workspace(n_tiles, device):
     """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""

@@ -911,6 +911,36 @@ int cs_tissue_coverage(const uint8_t* mask, int N, int H, int W, const int32_t* 
                        int pw, int32_t* cover, void* stream);
 int cs_tissue_select(const int32_t* cover, long long T, int min_pixels, int32_t* selected, int32_t* n_selected, void* stream);
 
+/* ---- stain separation and Macenko stain normalisation (csrc/stain.hip) --------------------------------------------------------
+ * images_hwc uint8 [N][H][W][3] (RGB) as for the tissue entry points: 0 < N <= 65535, 0 < H W < 2^31, 64-bit pixel offsets, no
+ * alignment asked of the images, the mask or the uint8 outputs.  All arrays are DEVICE arrays.
+ * od_q int32 [256] is the quantised optical density of a byte, made once on the host: od_q[v] = max(0, rint(4096 ln(Io / (v + 1))))
+ * with 0 < Io <= 256, so 0 <= od_q[v] <= 22713; the float optical density is od = od_q / 4096, exact in fp32.  No kernel calls log.
+ * A pixel is KEPT when none of its three od_q is below beta_q and, with `mask` uint8 [N][H][W] not NULL, its mask byte is non-zero.
+ * cs_stain_moments    : moments int64 [N][10] += over the kept pixels of image n: their number, the sums of od_q r, g, b and of
+ *                       the products rr, rg, rb, gg, gb, bb.  Integer only (22713^2 2^31 < 2^63): the bits do not depend on the
+ *                       launch geometry.  It ADDS: the caller zeroes moments.
+ * cs_stain_angle_hist : hist int64 [N][bins] += the kept pixels by clamp(floor((phi + pi/2) bins / pi), 0, bins - 1) with
+ *                       p = od V (V fp32 [N][3][2]), phi = atan2f(p1, p0).  0 < bins <= 8192.  It ADDS.
+ * cs_stain_conc_hist  : hist int64 [N][2][bins] += the kept pixels by clamp(floor(c_k bins / conc_max), 0, bins - 1) for each of the
+ *                       two concentrations c = P od (P fp32 [N][2][3]).  0 < bins <= 4096, conc_max > 0.  It ADDS.
+ * cs_stain_apply      : out uint8 [N][H][W][3] = clamp(rint(Io exp(-(A od))), 0, 255) for EVERY pixel, A fp32 [N][3][3], 0 < Io <= 256;
+ *                       evaluated in fp32 as exp2(log2 Io - (A od) log2 e), within 10^-3 levels of the exact value.  out must
+ *                       not overlap the images.
+ * cs_stain_separate   : the concentrations c = P od of EVERY pixel, P fp32 [N][K][3], K = 2 or 3: out fp32 [N][H][W][K] (as_u8 = 0) or
+ *                       uint8 [N][H][W][K] = clamp(rint(255 c_k / conc_max), 0, 255) (as_u8 = 1).
+ * Every product of a matrix row with od is fmaf(b, a2, fmaf(g, a1, r a0)) in fp32; a NaN result lands in bin 0 or as level 0.
+ * One launch each on `stream`, no workspace, no host synchronisation: capturable. */
+int cs_stain_moments(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask, int64_t* moments,
+                     void* stream);
+int cs_stain_angle_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask, const float* V,
+                        int bins, int64_t* hist, void* stream);
+int cs_stain_conc_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask, const float* P,
+                       int bins, float conc_max, int64_t* hist, void* stream);
+int cs_stain_apply(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, const float* A, float Io, uint8_t* out, void* stream);
+int cs_stain_separate(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, const float* P, int K, int as_u8, float conc_max,
+                      void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

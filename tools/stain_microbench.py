@@ -1,0 +1,110 @@
+"""Times the five launches of cellsegmentation_amd.stain (csrc/stain.hip) on an MI355X, and ``estimate`` and ``normalize`` end to
+end: device events around each launch, outputs preallocated, 20 launches back to back between two events, median of 9 such
+repetitions after a warm-up, with their spread (max - min) beside it.  ``estimate`` and ``normalize`` hold copies to the host, so
+they are timed by the wall clock around the synchronised call, median of 5 after a warm-up.
+
+    python tools/stain_microbench.py [--size 4096 16384] [--json PATH]
+
+Synthetic slides of ``size`` x ``size`` RGB pixels, made on the device (those of tools/tissue_microbench.py):
+
+    near_constant   glass: one colour plus 0..2 per channel; no pixel is kept, the histograms stay empty
+    half_tissue     the upper half glass, the lower half stained noise, most of it kept
+    noise           uniform noise in every channel: about half of the pixels is kept and the bins are hit widely
+
+``n_kept`` of every row says how many pixels the estimation passes did work for.
+
+The yardstick is a device-to-device copy of the same image, timed in the same process: it reads and writes 3 bytes per pixel.
+``moments`` and the two histograms read 3, ``apply`` reads 3 and writes 3 as the copy does, ``separate`` writes 2 (uint8) or 8
+(fp32) bytes per pixel for two stains.  A 4096^2 image (50 MB) stays in the 256 MiB Infinity Cache between launches, a 16384^2
+image (805 MB) cannot."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from cellsegmentation_amd import kernels as K  # noqa: E402
+from cellsegmentation_amd import stain  # noqa: E402
+from tissue_microbench import slides, time_dev  # noqa: E402
+
+
+def time_wall(fn, reps=5):
+    """-> (median ms, max - min ms) of a call that synchronises with the host itself"""
+    fn()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(ts)), float(max(ts) - min(ts))
+
+
+def bench(name, x, opts):
+    dev = x.device
+    _, H, W, _ = x.shape
+    row = {"slide": name, "size": [H, W]}
+    od, beta_q = torch.from_numpy(stain.od_table(opts.Io)).to(dev), opts.beta_q
+    est = stain.estimate(x[0], options=opts)
+    row["n_kept"], row["ok"] = est.n_kept, est.ok
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a[None], dtype=np.float32)).to(dev)  # noqa: E731
+    V = f32(np.linalg.svd(est.vectors)[0][:, :2])                          # a plane that holds the vectors
+    P, A = f32(np.linalg.pinv(est.vectors)), f32(stain.normalizer(est, stain.TARGET_HDAB))
+    dst = torch.empty_like(x)
+    timed = {"copy": lambda: dst.copy_(x)}
+    mom = torch.zeros((1, 10), dtype=torch.int64, device=dev)
+    timed["moments"] = lambda: K.stain_moments(x, od, beta_q, out=mom)
+    ah = torch.zeros((1, opts.angle_bins), dtype=torch.int64, device=dev)
+    timed["angle_hist"] = lambda: K.stain_angle_hist(x, od, beta_q, V, opts.angle_bins, out=ah)
+    ch = torch.zeros((1, 2, opts.conc_bins), dtype=torch.int64, device=dev)
+    timed["conc_hist"] = lambda: K.stain_conc_hist(x, od, beta_q, P, opts.conc_bins, opts.conc_max, out=ch)
+    timed["apply"] = lambda: K.stain_apply(x, od, A, opts.Io, out=dst)
+    for key, fn in timed.items():
+        row[f"{key}_ms"], row[f"{key}_spread_ms"] = time_dev(fn)
+    del dst
+    for key, as_u8, dtype in (("separate_u8", True, torch.uint8), ("separate_f32", False, torch.float32)):
+        out = torch.empty((1, H, W, 2), dtype=dtype, device=dev)
+        row[f"{key}_ms"], row[f"{key}_spread_ms"] = time_dev(lambda: K.stain_separate(x, od, P, as_u8, opts.conc_max, out=out))
+        del out
+    for key in ("moments", "angle_hist", "conc_hist", "apply", "separate_u8", "separate_f32"):
+        row[f"{key}_over_copy"] = row[f"{key}_ms"] / row["copy_ms"]
+    px = H * W
+    row["copy_GBps"] = 6 * px / row["copy_ms"] / 1e6
+    row["moments_GBps"] = 3 * px / row["moments_ms"] / 1e6
+    row["apply_GBps"] = 6 * px / row["apply_ms"] / 1e6
+    row["estimate_ms"], row["estimate_spread_ms"] = time_wall(lambda: stain.estimate(x[0], options=opts))
+    out = torch.empty_like(x)
+    row["normalize_ms"], row["normalize_spread_ms"] = time_wall(lambda: stain.normalize(x[0], options=opts, out=out))
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, nargs="+", default=[4096, 16384])
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    opts = stain.StainOptions()
+    rows = []
+    for size in args.size:
+        imgs = slides(size, dev)
+        for name in list(imgs):
+            rows.append(bench(name, imgs.pop(name), opts))
+            print(json.dumps(rows[-1]), flush=True)
+            torch.cuda.empty_cache()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
