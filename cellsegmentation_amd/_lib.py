@@ -183,6 +183,8 @@ _SIGNATURES = {
     "cs_regions_shape_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "cs_regions_hull_max_side": (c_int, []),
     "cs_regions_hull_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "cs_regions_contour_max_side": (c_int, []),
+    "cs_regions_contour_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
     "cs_regions_match_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_match_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cs_regions_overlap_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -18,6 +18,9 @@
 //   hull      of a label image: per label the convex hull of its pixels' unit squares -- vertex count, twice the area, the largest
 //             squared vertex distance and the smallest width as an exact fraction; one workgroup per label, the row extents of its
 //             bounding box and the hull's vertices in LDS, no atomics and no workspace
+//   contour   of a label image: per label the outer boundary of its first component as an ordered ring of lattice vertices, with
+//             the ring's crack count and enclosed area and the crack count of the whole label; one workgroup per label, its
+//             bounding box as a bitmap in LDS, which one thread walks
 //   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
 //             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
 //             and an exact 64-bit integer test per pred label
@@ -617,6 +620,148 @@ __global__ __launch_bounds__(256) void hull_kernel(const int32_t* __restrict__ l
             out[3] = narrow < 0 ? 0 : (int)(narrow >> 32);
             out[4] = narrow < 0 ? 0 : (int)(narrow & 0xFFFFFFFFll);
         }
+    }
+}
+
+// ---- the outer boundary ring of every label: an ordered polygon of lattice vertices ---------------------------------------------
+// The object of label l is the pixels with id l inside its box, pixel (i, j) of the box being the closed unit square with the
+// lattice corners (i, j) and (i + 1, j + 1).  A crack is one unit side of a pixel of the object whose neighbour across it is not in
+// the object; walked with the object on the right hand, every crack has exactly one successor (the rule is at `contour_walk`), so
+// the cracks fall into closed rings.  Traced is the ring through the top side of the object's first pixel in row-major order.
+constexpr int kContourSide = 512;                              // cs_regions_contour_max_side
+constexpr int kContourWords = (kContourSide + 2 + 31) / 32;    // words of a bitmap row at the side limit: 514 bits in 17 words
+
+struct ContourLds {
+    // One bit per pixel of the box inside a border of one zero bit all round: pixel (i, j) is bit (j + 1) & 31 of word
+    // (i + 1) * wpr + ((j + 1) >> 5), wpr = ceil((cols + 2) / 32) words per row.  34.1 KiB at the side limit.
+    uint32_t bits[(kContourSide + 2) * kContourWords];
+    int red[4];
+    int walked[3];                                             // n_vertices, n_cracks, area2: thread 0 to the others
+};
+
+// pixel (i, j) of the box, -1 <= i <= rows and -1 <= j <= cols: the border reads as "not the object"
+__device__ __forceinline__ bool contour_in(const uint32_t* bits, int wpr, int i, int j) {
+    return (bits[(i + 1) * wpr + ((j + 1) >> 5)] >> ((j + 1) & 31)) & 1u;
+}
+
+// The ring from lattice vertex (pr, pc), heading east along the top side of the first pixel (pr, pc), by one thread.  Headings
+// 0 = E, 1 = S, 2 = W, 3 = N; a step moves one crack along the heading, and at the vertex (r, c) it reaches R is the pixel ahead on
+// the right and L the one ahead on the left:
+//     E: R = (r, c),         L = (r - 1, c)         S: R = (r, c - 1),     L = (r, c)
+//     W: R = (r - 1, c - 1), L = (r, c - 1)         N: R = (r - 1, c),     L = (r - 1, c - 1)           (L of h is R of h - 1)
+// R out: turn right (with CONN 2 and L in: turn left, across to the diagonal pixel); R and L in: turn left; R in, L out: straight.
+// Either way the crack that follows has a pixel of the object on its right, so every vertex reached is a corner of such a pixel,
+// 0 <= r <= rows and 0 <= c <= cols, and R and L lie inside the bordered bitmap.  The walk ends on arriving at (pr, pc) with the
+// new heading east; the successor rule permutes the cracks of the bitmap, so that happens after at most `bound` steps, and the
+// loop stops there whatever the bitmap holds.  A vertex is written where the heading changes, (pr, pc) first.
+template <int CONN>
+__device__ __forceinline__ void contour_walk(const uint32_t* bits, int wpr, int pr, int pc, int bound, int r0, int c0, int maxv,
+                                             int32_t* __restrict__ verts, int* walked) {
+    int r = pr, c = pc, h = 0, n = 1, cracks = 0;
+    int vr = pr, vc = pc;                                      // the last vertex written
+    long long area2 = 0;
+    if (maxv > 0) {
+        verts[0] = r0 + pr;
+        verts[1] = c0 + pc;
+    }
+    while (cracks < bound) {
+        r += h == 1 ? 1 : h == 3 ? -1 : 0;
+        c += h == 0 ? 1 : h == 2 ? -1 : 0;
+        ++cracks;
+        const int rr = r - (h >= 2), rc = c - (h == 1 || h == 2);                // R of h
+        const int lr = r - (h == 0 || h == 3), lc = c - (h >= 2);                // L of h = R of h - 1
+        const bool R = contour_in(bits, wpr, rr, rc), L = contour_in(bits, wpr, lr, lc);
+        int nh = h;
+        if (!R) nh = (CONN == 2 && L) ? (h + 3) & 3 : (h + 1) & 3;
+        else if (L) nh = (h + 3) & 3;
+        if (r == pr && c == pc && nh == 0) break;
+        if (nh != h) {
+            area2 += (long long)vc * r - (long long)c * vr;
+            if (n < maxv) {
+                verts[2 * n] = r0 + r;
+                verts[2 * n + 1] = c0 + c;
+            }
+            ++n;
+            vr = r;
+            vc = c;
+            h = nh;
+        }
+    }
+    area2 += (long long)vc * pr - (long long)pc * vr;
+    walked[0] = n;
+    walked[1] = cracks;
+    walked[2] = (int)area2;
+}
+
+// (-1, -1) into the vertex slots from `from` on, by the workgroup; unsigned, since 2 maxv may come close to 2^31
+__device__ __forceinline__ void contour_fill(int32_t* __restrict__ verts, int from, int maxv) {
+    for (unsigned k = 2u * from + threadIdx.x; k < 2u * maxv; k += 256) verts[k] = -1;
+}
+
+// One workgroup per (image, label) at a time.  The box is cut to the image before anything is read, so whatever the table holds
+// no read leaves the label image; after the staging no step reads global memory or leaves the bitmap.
+template <int CONN>
+__global__ __launch_bounds__(256) void contour_kernel(const int32_t* __restrict__ lab, int N, int H, int W, int cap,
+                                                      const int32_t* __restrict__ bbox, int maxv, int32_t* __restrict__ contour,
+                                                      int32_t* __restrict__ vertices) {
+    __shared__ ContourLds s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long objects = (long long)N * cap;
+    for (long long q = blockIdx.x; q < objects; q += gridDim.x) {
+        const int n = (int)(q / cap), l = (int)(q - (long long)n * cap) + 1;
+        const int r0 = max(bbox[4 * q], 0), c0 = max(bbox[4 * q + 1], 0);
+        const int rows = min(bbox[4 * q + 2], H) - r0, cols = min(bbox[4 * q + 3], W) - c0;
+        int32_t* verts = vertices + 2 * q * maxv;              // never dereferenced where maxv == 0
+        const bool none = rows <= 0 || cols <= 0;
+        if (none || rows > kContourSide || cols > kContourSide) {      // the same in every thread: no barrier is left out below
+            if (threadIdx.x < 4) contour[4 * q + threadIdx.x] = none ? 0 : -1;
+            contour_fill(verts, 0, maxv);
+            continue;
+        }
+        // 1. the bitmap: a wave per bitmap row, its lanes over 64 bitmap columns at a time; a ballot is two words of the row
+        const int wpr = (cols + 2 + 31) >> 5;
+        const int32_t* img = lab + (long long)n * H * W + (long long)r0 * W + c0;
+        for (int i = wave; i < rows + 2; i += 4) {
+            const bool inside = i >= 1 && i <= rows;
+            const int32_t* row = img + (long long)(i - 1) * W;        // read where `inside` only
+            for (int j0 = 0; j0 < cols + 2; j0 += 64) {
+                const int j = j0 + lane - 1;                           // the box column of bitmap column j0 + lane
+                const unsigned long long bal = __ballot(inside && j >= 0 && j < cols && row[j] == l);
+                const int w = (j0 >> 5) + lane;
+                if (lane < 2 && w < wpr) s.bits[i * wpr + w] = (uint32_t)(bal >> (32 * lane));
+            }
+        }
+        __syncthreads();
+        // 2. all boundary cracks of the label, a word of 32 pixels at a time, and its first pixel in row-major order
+        int cracks_all = 0, first = INT_MAX;
+        for (int k = threadIdx.x; k < rows * wpr; k += 256) {
+            const int i = k / wpr + 1, w = k - (i - 1) * wpr;
+            const uint32_t* p = s.bits + i * wpr + w;
+            const uint32_t x = *p;
+            if (x == 0) continue;
+            const uint32_t west = x << 1 | (w > 0 ? p[-1] >> 31 : 0u), east = x >> 1 | (w + 1 < wpr ? p[1] << 31 : 0u);
+            cracks_all += __popc(x & ~p[-wpr]) + __popc(x & ~p[wpr]) + __popc(x & ~west) + __popc(x & ~east);
+            first = min(first, (k << 5) + __ffs(x) - 1);
+        }
+        cracks_all = block_reduce<256>(cracks_all, [](int x, int y) { return x + y; }, s.red);
+        first = block_reduce<256>(first, [](int x, int y) { return min(x, y); }, s.red);
+        if (first == INT_MAX) {                                        // the same in every thread; the bitmap is free again
+            if (threadIdx.x < 4) contour[4 * q + threadIdx.x] = 0;
+            contour_fill(verts, 0, maxv);
+            continue;
+        }
+        // 3. the walk, by one thread; the others wait for the vertex count
+        if (threadIdx.x == 0) {
+            const int k = first >> 5;
+            const int pr = k / wpr, pc = ((k - pr * wpr) << 5) + (first & 31) - 1;
+            contour_walk<CONN>(s.bits, wpr, pr, pc, 2 * rows * cols + rows + cols, r0, c0, maxv, verts, s.walked);
+        }
+        __syncthreads();
+        // (thread 0 writes `walked` again only behind the next object's barriers, which every thread reaches after this read)
+        const int nv = s.walked[0];
+        if (threadIdx.x < 3) contour[4 * q + threadIdx.x] = s.walked[threadIdx.x];
+        if (threadIdx.x == 3) contour[4 * q + 3] = cracks_all;
+        contour_fill(verts, min(nv, maxv), maxv);
     }
 }
 
@@ -1733,6 +1878,30 @@ extern "C" int cs_regions_hull_labels(const int32_t* labels, int N, int H, int W
     const long long objects = (long long)N * capacity;
     hipLaunchKernelGGL(hull_kernel, dim3((unsigned)(objects < 8192 ? objects : 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        labels, N, H, W, capacity, bbox, hull);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_contour_max_side(void) { return kContourSide; }
+
+extern "C" int cs_regions_contour_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int connectivity,
+                                         int max_vertices, int32_t* contour, int32_t* vertices, void* stream) {
+    CS_CHECK_ARG(labels, "regions_contour_labels: NULL argument");
+    CS_CHECK_ARG(bbox && contour, "regions_contour_labels: NULL table");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_contour_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(capacity >= 1, "regions_contour_labels: need capacity >= 1");
+    CS_CHECK_ARG((long long)N * capacity < (1LL << 31), "regions_contour_labels: need N capacity < 2^31");
+    CS_CHECK_ARG(connectivity == 1 || connectivity == 2, "regions_contour_labels: connectivity must be 1 or 2");
+    CS_CHECK_ARG(max_vertices >= 0, "regions_contour_labels: need max_vertices >= 0");
+    CS_CHECK_ARG(vertices || max_vertices == 0, "regions_contour_labels: NULL vertices with max_vertices > 0");
+    const long long objects = (long long)N * capacity;
+    CS_CHECK_ARG(2 * objects * max_vertices < (1LL << 31), "regions_contour_labels: need 2 N capacity max_vertices < 2^31");
+    const dim3 grid((unsigned)(objects < 8192 ? objects : 8192));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (connectivity == 1)
+        hipLaunchKernelGGL(contour_kernel<1>, grid, dim3(256), 0, st, labels, N, H, W, capacity, bbox, max_vertices, contour, vertices);
+    else
+        hipLaunchKernelGGL(contour_kernel<2>, grid, dim3(256), 0, st, labels, N, H, W, capacity, bbox, max_vertices, contour, vertices);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

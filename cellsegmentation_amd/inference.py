@@ -332,7 +332,7 @@ def segment_classes(loader, model, device, threshold, min_object_size=300, hole_
 
 
 def measure_cells(loader, model, device, threshold, min_object_size=300, hole_area_threshold=100, reg_limit=False, connectivity=1,
-                  max_regions=None, shape=False, hull=False, opening_radius=0):
+                  max_regions=None, shape=False, hull=False, opening_radius=0, contours=False, max_vertices=None):
     """One row per segmented cell: the per-batch body of ``segment_classes``, then ``regions.measure`` of the cleaned masks with
     ``detect.quantize`` of the probabilities (uint8 ``trunc(255 p)``) as the intensity.  Returns the ``RegionTable.per_image``
     dicts of all batches in dataset order (area, bbox, centroid, intensity_sum / _mean / _max per cell).  With ``max_regions``
@@ -342,7 +342,11 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     and circularity per cell.  ``hull=True`` adds the columns of ``HullTable.per_image`` (hull, convex_area, solidity,
     feret_diameter_max, feret_diameter_min, n_vertices, too_large) in the same way; with both, every batch is labelled and measured
     once and ``regions.shape_labels`` and ``regions.hull_labels`` share that one ``RegionTable``.  ``opening_radius`` as in
-    ``segment_classes``."""
+    ``segment_classes``.  ``contours=True`` takes that label-once path too and adds the columns of ``ContourTable.per_image``
+    (contour, polygon, n_vertices, too_large, truncated, is_simple, crack_perimeter, enclosed_area, hole_area) from
+    ``regions.contour_labels`` with this ``connectivity`` and ``max_vertices`` (None: every batch reads its largest vertex count
+    back, so that no polygon is truncated); together with ``hull=True`` the hull keeps ``n_vertices`` and ``too_large`` and the
+    contour's two go by ``contour_n_vertices`` and ``contour_too_large``."""
     from . import detect as D
     from . import regions as Rg
     _check_opening("measure_cells", opening_radius)
@@ -352,19 +356,30 @@ def measure_cells(loader, model, device, threshold, min_object_size=300, hole_ar
     with torch.no_grad():
         for data in tqdm(loader, desc="cell measuring"):
             probs, classes, _ = _cleaned_batch(model, data.to(device), threshold, mo, ho, reg_limit, reg_limit, opening_radius)
-            if hull:                                                      # label and measure once; both tables hang on that one
+            if hull or contours:                                          # label and measure once; the tables hang on that one
                 lab = Rg.label(classes, connectivity)
                 table = Rg.measure_labels(lab, intensity=D.quantize(probs), max_regions=max_regions)
-                parts = ([Rg.shape_labels(lab, table=table)] if shape else []) + [Rg.hull_labels(lab, table=table)]
+                parts = [Rg.shape_labels(lab, table=table)] if shape else []
+                if contours:
+                    parts.append(Rg.contour_labels(lab, table=table, connectivity=connectivity, max_vertices=max_vertices))
+                if hull:
+                    parts.append(Rg.hull_labels(lab, table=table))
             else:
                 measure = Rg.shape if shape else Rg.measure
                 parts = [measure(classes, intensity=D.quantize(probs), connectivity=connectivity, max_regions=max_regions)]
             tables.append(parts)
+    def per_image(part):
+        dicts = part.per_image()
+        if hull and isinstance(part, Rg.ContourTable):                    # the two names that HullTable.per_image has as well
+            for d in dicts:
+                d.update(contour_n_vertices=d.pop("n_vertices"), contour_too_large=d.pop("too_large"))
+        return dicts
+
     out = []
     for parts in tables:
-        dicts = parts[0].per_image()
+        dicts = per_image(parts[0])
         for more in parts[1:]:
-            for d, extra in zip(dicts, more.per_image()):
+            for d, extra in zip(dicts, per_image(more)):
                 d.update(extra)
         out += dicts
     return out

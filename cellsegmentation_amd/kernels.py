@@ -1475,6 +1475,34 @@ def regions_hull_labels(labels, capacity, bbox, hull=None):
     return t["hull"]
 
 
+REGIONS_CONTOUR_MAX_SIDE = 512       # cs_regions_contour_max_side: a larger bounding box is counted, not traced (its row is -1)
+
+
+def regions_contour_labels(labels, capacity, bbox, connectivity, max_vertices, contour=None, vertices=None):
+    """int32 label image [N,H,W] and bbox int32 [N,cap,4] (regions_measure_labels of the same image) -> (contour int32 [N,cap,4] =
+    n_vertices, n_cracks, area2, cracks_all of the outer boundary ring of every label, vertices int32 [N,cap,max_vertices,2] = the
+    ring's first vertices as (row, col), then (-1, -1)); row k = label k + 1, all -1 where the box has more than
+    REGIONS_CONTOUR_MAX_SIDE rows or columns.  ``max_vertices=0`` only counts: vertices is None
+    (cs_regions_contour_labels in include/cellseg_hip.h)."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_contour_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    cap, maxv = int(capacity), int(max_vertices)
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
+        raise TypeError(f"regions_contour_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    if maxv < 0:
+        raise ValueError(f"regions_contour_labels: max_vertices must be >= 0, got {max_vertices!r}")
+    want = {"contour": ((N, cap, 4), torch.int32)}
+    if maxv > 0:
+        want["vertices"] = ((N, cap, maxv, 2), torch.int32)
+    elif vertices is not None:
+        raise TypeError("regions_contour_labels: max_vertices=0 only counts and takes no vertices")
+    t = _regions_outputs("regions_contour_labels", want, {"contour": contour, "vertices": vertices}, labels.device)
+    _lib.check(_lib.load().cs_regions_contour_labels(_p(labels), N, H, W, cap, _p(bbox), int(connectivity), maxv, _p(t["contour"]),
+                                                     _p(t.get("vertices")), _stream()), "regions_contour_labels")
+    return t["contour"], t.get("vertices")
+
+
 def _label_pair_args(what, pred, truth, want_counts):
     """two int32 [N,H,W] label images of one shape -> (N, H, W, the ``_regions_outputs`` entries of the counts asked for)"""
     if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):

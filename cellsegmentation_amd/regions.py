@@ -58,6 +58,13 @@ the largest squared vertex distance and the smallest width as an exact fraction,
 ``hull_labels``'s docstring, restated in Python integers by tests/hull_ref.py), from which ``HullTable`` forms convex area, solidity
 and the largest and smallest Feret diameter in float64 on the device.  Objects whose bounding box exceeds 1024 rows or columns are
 counted, not measured.
+
+``contour_labels`` (``contours`` for a boolean mask) adds the outline of every label as an ordered polygon: the ring of lattice
+vertices round the component of the label's first pixel, walked along the pixel sides with the object on the right hand, with its
+vertex count, length, enclosed area and the length of all of the label's boundary, in exact integers (``ContourTable``; the rule is
+in ``contour_labels``'s docstring, restated in plain loops by tests/contour_ref.py), from which ``ContourTable`` tells one-piece
+labels without holes from the others and writes GeoJSON polygons for QuPath or shapely on the host.  Holes are not traced, and
+objects whose bounding box exceeds 512 rows or columns are counted, not traced.
 """
 import dataclasses
 import typing
@@ -1152,3 +1159,189 @@ def hull(m, connectivity=1, max_regions=None, intensity=None):
     _check_max_regions(max_regions)
     lab = label(m, connectivity)
     return hull_labels(lab, table=measure_labels(lab, intensity=intensity, max_regions=max_regions))
+
+
+_CONTOUR_COLUMNS = ("n_vertices", "too_large", "truncated", "is_simple", "crack_perimeter", "enclosed_area", "hole_area")
+
+
+@dataclasses.dataclass
+class ContourTable:
+    """``contour_labels`` of N label images as device tensors.  ``table``: the ``RegionTable`` of the same images (row k = label
+    k + 1); ``contour`` int32 [N, cap, 4] = (n_vertices, n_cracks, area2, cracks_all) of the label's outer boundary ring: all zero
+    for a label without a pixel in its box, all -1 for one whose bounding box is too large; ``vertices`` int32
+    [N, cap, max_vertices, 2] = the ring's first ``min(n_vertices, max_vertices)`` lattice vertices as (row, col), (-1, -1) after
+    them; ``connectivity`` as traced.  The rules are in ``contour_labels``' docstring.  Every method but ``per_image`` and
+    ``geojson`` runs where the tensors are, is computed from the integer tables only and gives either bool or float64 with NaN in
+    unused and in too-large rows."""
+    table: RegionTable
+    contour: torch.Tensor
+    vertices: torch.Tensor
+    connectivity: int = 1
+
+    def _ok(self):
+        return (self.table.area > 0) & (self.contour[..., 0] > 0)
+
+    def _measured(self, x):
+        return torch.where(self._ok(), x, torch.full_like(x, float("nan")))
+
+    @property
+    def max_vertices(self):
+        return int(self.vertices.shape[2])
+
+    def too_large(self):
+        """bool [N, cap]: the label's bounding box has more than ``kernels.REGIONS_CONTOUR_MAX_SIDE`` rows or columns, so the object
+        is counted (its ``table`` row is complete) but not traced."""
+        return self.contour[..., 0] < 0
+
+    def truncated(self):
+        """bool [N, cap]: the ring has more vertices than ``vertices`` has slots; ``n_vertices`` is still the true count."""
+        return self.contour[..., 0] > self.max_vertices
+
+    def is_simple(self):
+        """bool [N, cap]: ``n_cracks == cracks_all`` in a traced row, i.e. every boundary crack of the label lies on the traced
+        ring: the label is one piece (of the connectivity traced) without a hole, and the ring is all of its boundary."""
+        return self._ok() & (self.contour[..., 1] == self.contour[..., 3])
+
+    def n_vertices(self):
+        """float64 [N, cap]: the vertices of the ring, even and at least 4, also where the ring is truncated."""
+        return self._measured(self.contour[..., 0].to(torch.float64))
+
+    def crack_perimeter(self):
+        """float64 [N, cap] = n_cracks: the length of the ring along the pixel sides (the city-block perimeter of the outline)."""
+        return self._measured(self.contour[..., 1].to(torch.float64))
+
+    def enclosed_area(self):
+        """float64 [N, cap] = area2 / 2: the area inside the ring, holes included; for a one-piece label >= its pixel count."""
+        return self._measured(self.contour[..., 2].to(torch.float64) / 2)
+
+    def hole_area(self):
+        """float64 [N, cap] = area2 / 2 - area: for a one-piece label the pixels the ring encloses that are not the label's (its
+        holes and whatever lies in them); negative where further pieces of the label lie outside the ring."""
+        return self.enclosed_area() - self.table.area.to(torch.float64)
+
+    def per_image(self):
+        """``RegionTable.per_image`` with the columns ``contour``, one per method above and ``polygon`` added, trimmed alike;
+        ``polygon`` is a list of int32 [n, 2] arrays (row, col), n = min(n_vertices, max_vertices), 0 for a row that is not
+        traced.  Synchronises."""
+        out = self.table.per_image()
+        cols = {"contour": self.contour, **{k: getattr(self, k)() for k in _CONTOUR_COLUMNS}}
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        verts = self.vertices.cpu().numpy()
+        for n, d in enumerate(out):
+            rows = len(d["area"])
+            for k, v in cols.items():
+                d[k] = v[n, :rows]
+            kept = np.clip(cols["contour"][n, :rows, 0], 0, self.max_vertices)
+            d["polygon"] = [verts[n, k, :kept[k]].copy() for k in range(rows)]
+        return out
+
+    def geojson(self, image=0, origin=(0, 0), scale=1.0, properties=None):
+        """The rings of one image as a GeoJSON ``FeatureCollection`` (a host ``dict``, ready for ``json.dump``; QuPath, shapely
+        and geopandas read it): one ``Polygon`` feature per traced row whose ring is complete -- unused, too-large and truncated
+        rows are left out.  A lattice vertex (row, col) becomes ``[origin[0] + scale * col, origin[1] + scale * row]`` (x, y), so
+        ``origin`` is the (x, y) of the image's top-left corner in the target frame and ``scale`` its pixel size there; the ring
+        is closed (the first point is repeated last) and, y pointing down, runs clockwise on screen.  ``properties`` of a
+        feature: ``row`` (k; the label is k + 1), ``area`` (the pixel count), and one entry per item of ``properties``, a dict
+        name -> a sequence with one value per row of this image.  Synchronises."""
+        n = int(image)
+        if not 0 <= n < self.contour.shape[0]:
+            raise IndexError(f"geojson: image {image} of {self.contour.shape[0]}")
+        extra = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in (properties or {}).items()}
+        rows = self.contour.shape[1]
+        for k, v in extra.items():
+            if v.ndim < 1 or len(v) < rows:
+                raise ValueError(f"geojson: properties[{k!r}] needs one value per row ({rows}), got shape {v.shape}")
+        contour, verts, area = self.contour[n].cpu().numpy(), self.vertices[n].cpu().numpy(), self.table.area[n].cpu().numpy()
+        ox, oy, scale = float(origin[0]), float(origin[1]), float(scale)
+        features = []
+        for k in range(rows):
+            nv = int(contour[k, 0])
+            if area[k] <= 0 or nv <= 0 or nv > self.max_vertices:
+                continue
+            ring = [[ox + scale * int(c), oy + scale * int(r)] for r, c in verts[k, :nv].tolist()]
+            props = {"row": k, "area": int(area[k]), **{name: v[k].tolist() for name, v in extra.items()}}
+            features.append({"type": "Feature", "properties": props,
+                             "geometry": {"type": "Polygon", "coordinates": [ring + [ring[0]]]}})
+        return {"type": "FeatureCollection", "features": features}
+
+
+def _check_max_vertices(max_vertices):
+    if max_vertices is not None and (isinstance(max_vertices, bool) or int(max_vertices) != max_vertices or max_vertices < 0):
+        raise ValueError(f"max_vertices must be a non-negative integer or None, got {max_vertices!r}")
+
+
+def contour_labels(labels, table=None, max_regions=None, counts=None, connectivity=1, max_vertices=None):
+    """The outer boundary of every label of a label image as an ordered polygon of lattice vertices -> ``ContourTable``: what a
+    GeoJSON or QuPath export, shapely, or a comparison with polygon annotations needs, without a copy of the label image to the
+    host.
+
+    ``labels``: int32 [H, W] or [N, H, W] (numpy or torch).  Everything the device writes is an exact integer:
+
+    * Objects.  A pixel's object id is ``max(label, 0)``: 0 and below are background.  The images of a batch are independent.
+      Pixel (r, c) is the closed unit square with the lattice corners (r, c) and (r + 1, c + 1), as in ``hull_labels``.  For
+      label l the object is the pixels with id l inside the label's box from the ``RegionTable``, the box cut to the image first;
+      a pixel outside the box is "not the object" whatever it holds, and so is every other positive label.
+    * Crack.  A unit side of a pixel of the object whose neighbour across that side is not in the object.
+    * Start.  (pr, pc) is the first pixel of the object in row-major order.  The ring starts at lattice vertex (pr, pc), heading
+      east along that pixel's top side, the object on the right hand: with rows pointing down that is clockwise on screen, and
+      the shoelace sum ``sum(c_i r_{i+1} - c_{i+1} r_i)`` over the ring, twice its area, comes out positive.
+    * Step.  Move one lattice unit, one crack, along the heading.  At the vertex (r, c) reached look at the pixel ahead on the
+      right, R, and the one ahead on the left, L: heading E, R = (r, c) and L = (r - 1, c); S, R = (r, c - 1) and L = (r, c);
+      W, R = (r - 1, c - 1) and L = (r, c - 1); N, R = (r - 1, c) and L = (r - 1, c - 1).  R not in the object: turn right --
+      but with ``connectivity=2`` and L in the object turn left, across to the diagonal pixel.  R and L both in: turn left.  R
+      in and L out: straight on.
+    * Stop on arriving at (pr, pc) with the new heading east.  The successor rule permutes the cracks of a finite bitmap, so the
+      walk returns to its first crack; the kernel's loop is bounded by ``2 rows cols + rows + cols`` steps, the cracks of the box,
+      all the same.
+    * Vertices.  A lattice vertex is emitted where the heading changes; the start vertex is such a corner and comes first.  So the
+      ring is strict (no three consecutive vertices collinear), its edges alternate horizontal and vertical, ``n_vertices`` is
+      even and at least 4, and a lattice point may occur twice in a ring, at a pinch point.
+    * What is traced.  Only the ring through the start crack: the outer boundary of the component that holds the label's first
+      pixel, 4-connected at connectivity 1 and 8-connected at 2.  Holes and further pieces of a disconnected label are not
+      traced; ``cracks_all``, the number of all cracks of the label, tells: it equals ``n_cracks`` exactly when there are none.
+    * Per label, int32 ``contour[N, cap, 4]`` = ``n_vertices`` (the true count, also above ``max_vertices``), ``n_cracks`` (the
+      ring's length), ``area2`` (twice the area the ring encloses), ``cracks_all``; and int32 ``vertices[N, cap, max_vertices, 2]``
+      = the first ``min(n_vertices, max_vertices)`` vertices as absolute (row, col), every slot after them (-1, -1).
+    * Side limit.  A bounding box of more than ``kernels.REGIONS_CONTOUR_MAX_SIDE`` = 512 rows or columns is too large: the four
+      entries are -1, there is no vertex and ``ContourTable.too_large()`` flags the row; the object is counted, not traced.
+    * A label without a pixel in its box has an all-zero row and no vertex; rows of labels above the capacity are not written.
+
+    A single pixel at (0, 0) has the ring (0, 0), (0, 1), (1, 1), (1, 0) and the row (4, 4, 2, 4); a filled 5 x 5 square (4, 20,
+    50, 20); a 3 x 3 square without its centre (4, 12, 18, 16).  The rule is restated in plain loops by tests/contour_ref.py and
+    pinned to ``scipy.ndimage.binary_fill_holes`` of the first component with the complementary structure
+    (tests/golden/contour_vectors.npz).  Parity with ``cv2.findContours`` (which joins pixel centres) or
+    ``skimage.measure.find_contours`` (marching squares at half-pixel positions) is NOT claimed: neither is a dependency.
+
+    ``table``, ``max_regions`` and ``counts`` as in ``shape_labels``; ``connectivity`` 1 or 2 as above.  ``max_vertices=int`` fixes
+    the vertex slots per label (0: count only): with a table, or an int ``max_regions``, one launch whose grid depends on (N,
+    capacity) alone follows, nothing synchronises and the call can be captured into a graph.  ``max_vertices=None`` makes a
+    counting-only launch first, reads the largest ``n_vertices`` back (the one synchronisation) and runs with ``max(4, that)``, so
+    that no ring is truncated.  There are no atomics: the result does not depend on launch order."""
+    conn = _check_connectivity(connectivity)
+    _check_max_vertices(max_vertices)
+    t, table, _ = _labels_and_table("contour_labels", labels, table, max_regions, counts, "contours")
+    N, cap = t.shape[0], table.capacity
+    bbox = table.bbox.contiguous()
+    contour = torch.empty((N, cap, 4), dtype=torch.int32, device=t.device)
+    chunks = _chunks(t)
+    if max_vertices is None:
+        for a, b in chunks:
+            K.regions_contour_labels(t[a:b], cap, bbox[a:b], conn, 0, contour=contour[a:b])
+        maxv = max(4, int(contour[..., 0].max()))                        # the one synchronisation
+    else:
+        maxv = int(max_vertices)
+    vertices = torch.empty((N, cap, maxv, 2), dtype=torch.int32, device=t.device)
+    for a, b in chunks:
+        K.regions_contour_labels(t[a:b], cap, bbox[a:b], conn, maxv, contour=contour[a:b], vertices=vertices[a:b] if maxv else None)
+    return ContourTable(table, contour, vertices, conn)
+
+
+def contours(m, connectivity=1, max_regions=None, max_vertices=None):
+    """``contour_labels`` for a boolean mask: ``label(m, connectivity)``, ``measure_labels`` of the labels and ``contour_labels`` on
+    that table with the same connectivity -> ``ContourTable``.  Row k is the same component as row k of ``measure(m)``; every
+    component is one piece, so ``is_simple()`` says whether it has a hole.  ``max_regions`` as in ``measure_labels`` and
+    ``max_vertices`` as in ``contour_labels``: ints mean no synchronisation."""
+    _check_max_regions(max_regions)
+    _check_max_vertices(max_vertices)
+    lab = label(m, connectivity)
+    return contour_labels(lab, table=measure_labels(lab, max_regions=max_regions), connectivity=connectivity, max_vertices=max_vertices)

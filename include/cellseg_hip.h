@@ -764,6 +764,41 @@ int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edges, int N, 
 int cs_regions_hull_max_side(void);
 int cs_regions_hull_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int32_t* hull, void* stream);
 
+/* ---- the outer boundary of every object of a label image as an ordered polygon (csrc/regions.hip) ----------------------------
+ * labels int32 [N][H][W]; a pixel's object id is max(label, 0), images are independent; sizes as above.  One launch whose grid
+ * depends on (N, capacity) alone, no synchronisation, capturable; no workspace and no atomics, every element of both outputs is
+ * written.  Additions to the ABI: cs_abi_version is unchanged.
+ * cs_regions_contour_max_side: 512, the largest number of rows or columns of a bounding box that is still traced.
+ * cs_regions_contour_labels:   bbox int32 [N][capacity][4] is READ, as cs_regions_measure_labels wrote it for the same labels
+ *                              and capacity (it is cut to the image before a pixel is read).  Row k of image n belongs to label
+ *                              k + 1.  The object of label l is the pixels with id l INSIDE its box; pixel (r, c) is the closed
+ *                              unit square with the lattice corners (r, c) and (r + 1, c + 1).  A crack is a unit side of a pixel
+ *                              of the object whose neighbour across it is not in the object.  The ring starts at the lattice
+ *                              vertex (pr, pc) of the object's first pixel in row-major order, heading east along that pixel's top
+ *                              side with the object on the right hand, and moves one crack at a time.  At the vertex reached, with
+ *                              R the pixel ahead on the right and L the one ahead on the left: R out -> turn right (connectivity
+ *                              2 and L in -> turn left instead); R and L in -> turn left; R in, L out -> straight.  It ends on
+ *                              arriving at (pr, pc) with the new heading east, or after 2 rows cols + rows + cols steps (the
+ *                              cracks of the box), which a consistent walk never needs.  A vertex is emitted where the heading
+ *                              changes, (pr, pc) first: edges alternate horizontal and vertical, n_vertices is even and >= 4.
+ *                              Only this ring -- the outer boundary of the 4- (connectivity 1) or 8-connected (2) component
+ *                              of the first pixel -- is traced: no holes, no further pieces of the label.
+ *                              contour int32 [N][capacity][4] = (n_vertices, n_cracks, area2, cracks_all):
+ *                                n_vertices  the ring's vertices, the true count also above max_vertices;
+ *                                n_cracks    the ring's length;
+ *                                area2       twice the area the ring encloses (shoelace sum, positive);
+ *                                cracks_all  all cracks of the label: == n_cracks iff the label is one piece without a hole.
+ *                              vertices int32 [N][capacity][max_vertices][2] = (row, col), absolute lattice coordinates: the
+ *                              first min(n_vertices, max_vertices) vertices of the ring, then (-1, -1).  vertices == NULL with
+ *                              max_vertices == 0 only counts.
+ *                              The row of a label without a pixel in its box is all zero; the row of a label whose box has more
+ *                              than cs_regions_contour_max_side rows or columns is all -1; both have no vertex.
+ *                              Need capacity >= 1, N capacity < 2^31, connectivity 1 or 2, max_vertices >= 0 and
+ *                              2 N capacity max_vertices < 2^31. */
+int cs_regions_contour_max_side(void);
+int cs_regions_contour_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int connectivity,
+                              int max_vertices, int32_t* contour, int32_t* vertices, void* stream);
+
 /* ---- a label image scored against another at the object level (csrc/regions.hip) --------------------------------------------
  * pred, truth int32 [N][H][W], values <= 0 = background; sizes and the launch contract as above (a fixed number of launches for
  * given (N, H, W, cap_pred, cap_truth), no synchronisation, capturable).  For image n let Ap[p] / At[g] be the pixel counts of

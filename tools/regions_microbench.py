@@ -38,6 +38,16 @@ tests/hull_ref.py.
 
     python tools/regions_microbench.py --hull [--reps 5] [--host-maps 2] [--json PATH]
 
+--contours times ``regions.contour_labels`` with the table and an int ``max_vertices`` given (one launch, one workgroup per label,
+the ring walked by one thread in an LDS bitmap) and its counting-only form, next to ``regions.measure_labels`` and
+``regions.shape_labels`` on the label images of ``--shape``, graph replays again, and next to the copy of the int32 label image into
+pinned host memory: the floor of any route that traces the outlines on the host.  It reports the terms of the cost model -- the sum
+of the bounding-box areas (staging and counting) and the sum of the ring lengths (the walk), with the longest ring, which bounds the
+launch from below -- and checks the first ``--host-maps`` maps against tests/contour_ref.py, both connectivities, the first 512
+labels of every map (the restatement is plain Python loops).
+
+    python tools/regions_microbench.py --contours [--reps 5] [--host-maps 2] [--json PATH]
+
 --morph times ``morph.binary_opening`` at radii 1, 2 and 5, ``morph.expand_labels`` at 4 (of ``regions.label`` of the masks) and
 ``morph.nearest_sites`` (towards the background) next to ``detect.distance_transform_sq`` on the same two mask sets, graph replays
 again, and checks the first ``--host-maps`` maps against scipy: ``binary_opening`` by the disk, the squared
@@ -312,6 +322,42 @@ def hull_case(name, masks, pts, off, reps, host_maps, dev):
     return res
 
 
+def contour_case(name, masks, pts, off, reps, host_maps, dev):
+    import contour_ref as CR
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    parts = G.split(d, dp, doff)
+    cap = max(1, int(parts.counts.max()))                                  # sized once, outside the timed region
+    table = G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts)
+    both = {conn: G.contour_labels(parts.labels, table=table, connectivity=conn) for conn in (1, 2)}   # max_vertices sized here
+    ct = both[1]
+    maxv = ct.max_vertices
+    measure_ms, _ = time_graph(lambda: G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts), reps)
+    shape_ms, _ = time_graph(lambda: G.shape_labels(parts.labels, table=table), reps)
+    contour_ms, ts = time_graph(lambda: G.contour_labels(parts.labels, table=table, max_vertices=maxv), reps)
+    count_ms, _ = time_graph(lambda: G.contour_labels(parts.labels, table=table, max_vertices=0), reps)
+    host = torch.empty(parts.labels.shape, dtype=torch.int32, pin_memory=True)
+    copy_ms, _ = time_dev(lambda: host.copy_(parts.labels, non_blocking=True), reps)
+    box = table.bbox.to(torch.int64)
+    cracks = ct.contour[..., 1].clamp(min=0).to(torch.int64)
+    res = {"measure_labels_ms": measure_ms, "shape_labels_ms": shape_ms, "contour_labels_ms": contour_ms, "contour_labels_ms_all": ts,
+           "contour_count_only_ms": count_ms, "labels_to_pinned_host_ms": copy_ms, "label_image_bytes": parts.labels.numel() * 4,
+           "contour_over_measure_plus_shape": contour_ms / (measure_ms + shape_ms), "rows_max": cap, "max_vertices": maxv,
+           "objects": int((table.area > 0).sum()), "too_large": int(ct.too_large().sum()), "simple": int(ct.is_simple().sum()),
+           "foreground_pixels": int(masks.sum()), "box_area_sum": int(((box[..., 2] - box[..., 0]) * (box[..., 3] - box[..., 1])).sum()),
+           "ring_cracks_sum": int(cracks.sum()), "ring_cracks_max": int(cracks.max()), "vertices_sum": int(ct.contour[..., 0].clamp(min=0).sum())}
+    ok = True
+    labels = parts.labels.cpu().numpy()
+    rows = min(cap, 512)
+    for i in range(min(host_maps, len(masks))):
+        for conn, got in both.items():
+            ref = CR.contour_labels(labels[i], rows, conn, got.max_vertices)
+            ok &= bool(np.array_equal(got.contour[i, :rows].cpu().numpy(), ref["contour"][0]))
+            ok &= bool(np.array_equal(got.vertices[i, :rows].cpu().numpy(), ref["vertices"][0]))
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)), host_rows=rows)
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
 def morph_case(name, masks, reps, host_maps, dev):
     from scipy import ndimage
     import morph_ref as MR
@@ -373,10 +419,13 @@ def main():
     ap.add_argument("--geodesic", action="store_true", help="with --split: time regions.split_geodesic next to regions.split instead")
     ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
     ap.add_argument("--hull", action="store_true", help="time regions.hull_labels next to measure_labels + shape_labels instead")
+    ap.add_argument("--contours", action="store_true", help="time regions.contour_labels next to measure_labels + shape_labels instead")
     ap.add_argument("--morph", action="store_true", help="time morph.binary_opening / expand_labels / nearest_sites next to the EDT instead")
     args = ap.parse_args()
     if args.morph:
         res = morph_main(args)
+    elif args.contours:
+        res = seeded_main(contour_case, args)
     elif args.hull:
         res = seeded_main(hull_case, args)
     elif args.shape:
