@@ -212,6 +212,8 @@ _SIGNATURES = {
     "cs_stain_conc_hist": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_float, _P, _P]),
     "cs_stain_apply": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P]),
     "cs_stain_separate": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_float, _P, _P]),
+    "cs_render_compose": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_float, c_int, _P, _P, c_int, _P, c_int, _P, _P]),
+    "cs_render_points": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P]),
 }
 
 _lib = None

@@ -260,6 +260,13 @@ class DetectResult:
             hat, off = self.device_points, self.device_offsets
         return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
 
+    def render(self, images_u8, **compose):
+        """The maps' images annotated on the device -> uint8 of the images' shape: ``render.compose(images_u8, **compose)`` (mask=,
+        heat=, outlines=, ... as there), then every map's kept detections -- ``per_image()[n][0]`` -- as red dots of radius 4 and
+        its discarded ones as blue dots on top, straight from the device points and offsets: no host round trip."""
+        from . import render as Rd
+        return Rd.render_detections(self, images_u8, **compose)
+
     def _per_map(self, points, offsets):
         """a second point set in one of the forms ``score`` lists -> (points [G, 2], offsets [N + 1] or None for a single map)"""
         from . import score as S

@@ -296,6 +296,32 @@ def detect_slides(slides, model, device=None, **kwargs):
         yield detect_slide(image_u8, model, device, **kwargs)
 
 
+def render_slide(image_u8, result, fill="mask", thr_u8=127, outlines=None, **compose):
+    """The annotated slide of a ``SlideResult`` -> device uint8 [H, W, 3]: ``render.compose`` of ``image_u8`` (uint8 [H, W, 3], numpy or
+    torch) over ``result.mask``, then the dots of ``render.locate_cells``: red at ``result.points``, blue at ``result.discarded``.
+    ``fill``: ``"mask"`` is the half-white overlay of ``result.mask > thr_u8``; ``"heat"`` takes ``result.mask`` itself as the uint8 heat
+    map; ``None`` skips the fill.  ``outlines`` and the other keyword arguments (colormap, invert, outline_color, palette,
+    connectivity, out) are ``compose``'s.  The image is not written to unless it is ``out``."""
+    from . import render as Rd
+    from .tissue import _check_threshold
+    if not isinstance(result, SlideResult):
+        raise TypeError(f"render_slide: expected a SlideResult, got {type(result).__name__}")
+    if fill not in ("mask", "heat", None):
+        raise ValueError(f"render_slide: fill must be 'mask', 'heat' or None, got {fill!r}")
+    for name in ("mask", "heat", "threshold"):
+        if name in compose:
+            raise TypeError(f"render_slide: {name} is not an argument here: the fill comes from result.mask")
+    thr_u8 = _check_threshold(thr_u8, "thr_u8")
+    t, one = Rd._images_arg(image_u8, "render_slide")
+    if not one or tuple(t.shape[1:3]) != tuple(result.mask.shape):
+        raise ValueError(f"render_slide: expected one image shaped {tuple(result.mask.shape) + (3,)}, got shape {tuple(np.shape(image_u8))}")
+    if fill == "mask":
+        compose["mask"] = result.mask > thr_u8
+    elif fill == "heat":
+        compose["heat"] = result.mask
+    return Rd._dots(Rd.compose(image_u8, outlines=outlines, **compose), result.points, result.discarded)
+
+
 def _opened(classes, opening_radius):
     """``morph.binary_opening(classes, opening_radius, border_value=0)`` when the radius is positive, else ``classes`` itself"""
     if not opening_radius:

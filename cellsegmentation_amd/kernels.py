@@ -1973,6 +1973,100 @@ def stain_separate(images_u8, od_q, P, as_u8=False, conc_max=1.0, out=None):
     return out
 
 
+# ---------------------------------------------------------------- annotated images (csrc/render.hip; render.py is the public API)
+CS_RENDER_FILL_NONE, CS_RENDER_FILL_MASK, CS_RENDER_FILL_HEAT_U8, CS_RENDER_FILL_HEAT_F32 = 0, 1, 2, 3
+CS_RENDER_POINTS_XY, CS_RENDER_POINTS_TAIL = 1, 2
+RENDER_MAX_RADIUS = 64
+
+
+def _render_images(what, images_u8, name="images"):
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise TypeError(f"{what}: {name} must be a uint8 tensor shaped [N, H, W, 3]")
+    N, H, W, _ = images_u8.shape
+    if not 1 <= N <= 65535 or H < 1 or W < 1 or N * H * W >= 1 << 31:
+        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels, got {(N, H, W)}")
+    return N, H, W
+
+
+def _render_rgb(what, name, rgb):
+    """three integers in [0, 255] -> r | g << 8 | b << 16"""
+    try:
+        r, g, b = (int(v) for v in rgb)
+        ok = all(not isinstance(v, bool) and int(v) == v for v in rgb)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError(f"{what}: {name} must be three integers in [0, 255], got {rgb!r}")
+    return r | g << 8 | b << 16
+
+
+def render_compose(images_u8, fill=CS_RENDER_FILL_NONE, fill_map=None, threshold=0.0, invert=True, colormap=None, labels=None,
+                   outline_color=(255, 255, 0), palette=None, out=None):
+    """images uint8 [N,H,W,3] -> uint8 [N,H,W,3], one launch: the fill ``fill`` from ``fill_map`` (uint8 [N,H,W]; fp32 for
+    CS_RENDER_FILL_HEAT_F32, with ``threshold``) through ``colormap`` uint8 [256,3], then the outline of ``labels`` int32 [N,H,W] in
+    ``outline_color`` or ``palette`` uint8 [P,3]; ``out`` may be the images (cs_render_compose in include/cellseg_hip.h)"""
+    N, H, W = _render_images("render_compose", images_u8)
+    if fill not in (CS_RENDER_FILL_NONE, CS_RENDER_FILL_MASK, CS_RENDER_FILL_HEAT_U8, CS_RENDER_FILL_HEAT_F32):
+        raise ValueError(f"render_compose: unknown fill {fill!r}")
+    if (fill == CS_RENDER_FILL_NONE) != (fill_map is None):
+        raise ValueError("render_compose: a fill needs its map, no fill takes none")
+    heat = fill in (CS_RENDER_FILL_HEAT_U8, CS_RENDER_FILL_HEAT_F32)
+    if fill_map is not None:
+        want = torch.float32 if fill == CS_RENDER_FILL_HEAT_F32 else torch.uint8
+        if not torch.is_tensor(fill_map) or fill_map.dtype != want or tuple(fill_map.shape) != (N, H, W):
+            raise TypeError(f"render_compose: the map of this fill must be a {want} tensor shaped {(N, H, W)}")
+    if heat and (not torch.is_tensor(colormap) or colormap.dtype != torch.uint8 or tuple(colormap.shape) != (256, 3)):
+        raise TypeError("render_compose: a heat fill needs a uint8 colour table shaped (256, 3)")
+    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (N, H, W)):
+        raise TypeError(f"render_compose: labels must be an int32 tensor shaped {(N, H, W)}")
+    rows = 0
+    if palette is not None:
+        if labels is None:
+            raise ValueError("render_compose: a palette needs the labels")
+        if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3:
+            raise TypeError("render_compose: palette must be a uint8 tensor shaped [P, 3]")
+        rows = int(palette.shape[0])
+        if not 1 <= rows <= 256:
+            raise ValueError(f"render_compose: a palette has 1 to 256 rows, got {rows}")
+    rgb = _render_rgb("render_compose", "outline_color", outline_color)
+    out = _regions_outputs("render_compose", {"out": ((N, H, W, 3), torch.uint8)}, {"out": out}, images_u8.device)["out"]
+    a, b, n = images_u8.data_ptr(), out.data_ptr(), 3 * N * H * W
+    if a != b and a < b + n and b < a + n:
+        raise ValueError("render_compose: out may be the images themselves, or must not overlap them")
+    _lib.check(_lib.load().cs_render_compose(_p(images_u8), N, H, W, int(fill), _p(fill_map), float(threshold), int(bool(invert)),
+                                             _p(colormap) if heat else None, _p(labels), rgb, _p(palette), rows, _p(out), _stream()),
+               "render_compose")
+    return out
+
+
+def render_points(canvas_u8, pts, off, limits=None, radius=4, color=(255, 0, 0), thickness=-1, xy=False, tail=False):
+    """draws into canvas uint8 [N,H,W,3] in place and returns it: pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None
+    (the triple of spatial_bin_counts), every kept row -- with ``tail`` every row that limits does not keep -- as a disc of
+    ``radius`` (thickness < 0) or a ring of that thickness (cs_render_points in include/cellseg_hip.h)"""
+    N, H, W = _render_images("render_points", canvas_u8, "canvas")
+    radius, thickness = int(radius), int(thickness)
+    if not 0 <= radius <= RENDER_MAX_RADIUS:
+        raise ValueError(f"render_points: radius must be in [0, {RENDER_MAX_RADIUS}], got {radius}")
+    if thickness == 0 or thickness > 2 * radius:
+        raise ValueError(f"render_points: thickness must be negative (filled) or in [1, 2 radius = {2 * radius}], got {thickness}")
+    rgb = _render_rgb("render_points", "color", color)
+    if not canvas_u8.is_cuda:
+        raise ValueError("render_points: the canvas must be a device tensor")
+    pts, off, limits, _, _, _, n = _spatial_args("render_points", pts, off, limits, None, None, None)
+    if off.device != canvas_u8.device:
+        raise ValueError("render_points: off must live on the device of the canvas")
+    if n != N:
+        raise ValueError(f"render_points: {N} images but {n + 1} offsets")
+    if tail and limits is None:
+        raise ValueError("render_points: tail draws the points from limits[n] on: it needs limits")
+    P = int(pts.shape[0])
+    flags = (CS_RENDER_POINTS_XY if xy else 0) | (CS_RENDER_POINTS_TAIL if tail else 0)
+    if P:
+        _lib.check(_lib.load().cs_render_points(_p(canvas_u8), N, H, W, _p(pts), _p(off), _p(limits), P, radius, max(thickness, -1), rgb, flags,
+                                                _stream()), "render_points")
+    return canvas_u8
+
+
 # ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
 def stage_augmented_workspace(n_tiles, device):
     """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""

@@ -976,6 +976,44 @@ int cs_stain_apply(const uint8_t* images_hwc, int N, int H, int W, const int32_t
 int cs_stain_separate(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, const float* P, int K, int as_u8, float conc_max,
                       void* out, void* stream);
 
+/* ---- annotated images: overlays, heat maps, outlines and cell dots (csrc/render.hip) -------------------------------------------
+ * images uint8 [N][H][W][3], 0 < N <= 65535, N H W < 2^31 (the sizes of the regions entry points); all arrays are DEVICE arrays and
+ * no alignment is asked of the images, the uint8 maps or the outputs.  Integer arithmetic throughout: the bits do not depend on
+ * the launch geometry.  One launch each on `stream` (none without work), no workspace, no host synchronisation: capturable.
+ * cs_render_compose : out uint8 [N][H][W][3] = per pixel and channel value c, in this order:
+ *                       fill  CS_RENDER_FILL_NONE      nothing, fill_map == NULL
+ *                             CS_RENDER_FILL_MASK      fill_map uint8 [N][H][W]: c = (c + 255 (m != 0)) >> 1
+ *                             CS_RENDER_FILL_HEAT_U8   fill_map uint8 [N][H][W] = h
+ *                             CS_RENDER_FILL_HEAT_F32  fill_map fp32 [N][H][W] = p (4-byte aligned): h = p > threshold ?
+ *                                                      (uint8)(255.0f * p) : 0, for p in [0, 1]
+ *                             heat: k = colormap[invert ? 255 - h : h][channel] (colormap uint8 [256][3]), s = c + k,
+ *                             c = (s >> 1) + ((s & 1) & ((s >> 1) & 1)): the mean rounded half to even
+ *                       outlines  labels int32 [N][H][W] or NULL: a pixel whose id = max(label, 0) is positive and one of whose
+ *                             four neighbours has another id (outside the image: id 0) -- the rule of cs_regions_edges_labels,
+ *                             evaluated here from the labels -- gets outline_rgb = r | g << 8 | b << 16, or, with palette uint8
+ *                             [palette_rows][3] (1 <= palette_rows <= 256, else NULL and 0), palette[(id - 1) % palette_rows].
+ *                     The image reads are pointwise: out may be the images themselves (any other overlap is not allowed).
+ * cs_render_points  : draws into canvas uint8 [N][H][W][3].  pts int64 [P][2], off int64 [N + 1] and limit int32 [N] or NULL are
+ *                     the triple of cs_spatial_bin_counts: image n owns the rows [off[n], off[n + 1]) of pts, of which limit keeps
+ *                     the first limit[n] (Python's [:c]); offsets that do not describe rows of the buffer own none.  flags:
+ *                     CS_RENDER_POINTS_XY = the rows are (col, row) instead of (row, col); CS_RENDER_POINTS_TAIL = the rows
+ *                     that limit does NOT keep are drawn instead (it needs limit).  With d2 = dr^2 + dc^2 from the point,
+ *                     thickness < 0 writes the pixels with d2 <= radius^2, thickness = t in [1, 2 radius] those with
+ *                     (2 radius - t)^2 <= 4 d2 <= (2 radius + t)^2; 0 <= radius <= 64.  Pixels outside the image are skipped and
+ *                     a point may lie anywhere.  Every write of a call stores the same rgb = r | g << 8 | b << 16, so overlapping
+ *                     marks do not depend on any order.  P == 0 launches nothing. */
+#define CS_RENDER_FILL_NONE 0
+#define CS_RENDER_FILL_MASK 1
+#define CS_RENDER_FILL_HEAT_U8 2
+#define CS_RENDER_FILL_HEAT_F32 3
+#define CS_RENDER_POINTS_XY 1
+#define CS_RENDER_POINTS_TAIL 2
+int cs_render_compose(const uint8_t* images_hwc, int N, int H, int W, int fill, const void* fill_map, float threshold, int invert,
+                      const uint8_t* colormap, const int32_t* labels, int outline_rgb, const uint8_t* palette, int palette_rows,
+                      uint8_t* out, void* stream);
+int cs_render_points(uint8_t* canvas_hwc, int N, int H, int W, const int64_t* pts, const int64_t* off, const int32_t* limit, long long P,
+                     int radius, int thickness, int rgb, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,310 @@
+"""Rendering on the GPU (csrc/render.hip): compose and draw_points bit for bit against the numpy restatement tests/render_ref.py on
+the pinned vectors, at every kind of address and in place, on sizes that take more than one workgroup and the strided grid, and the
+reference-named front ends, DetectResult.render and inference.render_slide against the composition of the restatement's steps."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import render_ref as R  # noqa: E402
+from cellsegmentation_amd import detect as D  # noqa: E402
+from cellsegmentation_amd import inference, regions, render  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLD = np.load(os.path.join(ROOT, "tests", "golden", "render_vectors.npz"), allow_pickle=False)
+COMPOSE = [str(n) for n in GOLD["compose_names"]]
+POINTS = [str(n) for n in GOLD["points_names"]]
+SHIFTS = ((1, 0), (7, 4), (12, 3), (0, 9),            # (inputs, output) bytes past a 16-byte boundary: byte loads and stores
+          (0, 4), (4, 8))                             # and the dword paths of the map and of the output
+GUARD = 0xA5
+
+
+def _shifted(a, shift, dev, fill=None):
+    """the array on the device, its first byte `shift` bytes past a 16-byte boundary (4-byte types: the next multiple of 4), inside a
+    buffer of GUARD bytes -> (the view, the buffer, the view's byte range in it); fill: a constant instead of the array's values"""
+    item = a.dtype.itemsize
+    shift = shift if item == 1 else 4 * (shift % 4)
+    flat = torch.full((a.nbytes + 64,), GUARD, dtype=torch.uint8, device=dev)
+    lead = (-flat.data_ptr()) % 16 + 16 + shift
+    view = flat[lead:lead + a.nbytes].view(torch.from_numpy(a[:0].copy()).dtype).view(a.shape)
+    if fill is None:
+        view.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    else:
+        view.fill_(fill)
+    assert view.data_ptr() % 16 == shift % 16 and view.is_contiguous()
+    return view, flat, (lead, lead + a.nbytes)
+
+
+def _guards_intact(flat, span):
+    f = flat.cpu().numpy()
+    return (f[:span[0]] == GUARD).all() and (f[span[1]:] == GUARD).all()
+
+
+def _package_kwargs(kw):
+    kw = dict(kw)
+    if "labels" in kw:
+        kw["outlines"] = kw.pop("labels")
+    if "outline_color" in kw:
+        kw["outline_color"] = tuple(int(v) for v in kw["outline_color"])
+    return kw
+
+
+@pytest.mark.parametrize("name", COMPOSE)
+def test_compose_pinned_cases_bit_equal_at_every_address_and_in_place(dev, name):
+    kw, want = R.golden_case(GOLD, name, R.COMPOSE_KEYS)
+    kw = _package_kwargs(kw)
+    images = GOLD[f"{name}.images"]
+    got = render.compose(images, **kw)                                     # host arrays in
+    assert got.is_cuda and got.dtype == torch.uint8 and tuple(got.shape) == images.shape and np.array_equal(got.cpu().numpy(), want)
+    if images.shape[0] == 1:                                               # one image in, one image out
+        one = {k: v[0] if k in ("mask", "heat", "outlines") else v for k, v in kw.items()}
+        got = render.compose(images[0], **one)
+        assert tuple(got.shape) == images.shape[1:] and np.array_equal(got.cpu().numpy(), want[0])
+    for shift_in, shift_out in SHIFTS:
+        x, _, _ = _shifted(images, shift_in, dev)
+        on_dev = dict(kw)
+        for k in ("mask", "heat", "outlines"):
+            if k in on_dev:
+                on_dev[k] = _shifted(on_dev[k], shift_in, dev)[0]
+        out, flat, span = _shifted(images, shift_out, dev, fill=7)         # prefilled: a pixel written outside the view shows
+        assert render.compose(x, out=out, **on_dev) is out
+        assert np.array_equal(out.cpu().numpy(), want) and _guards_intact(flat, span)
+        assert np.array_equal(x.cpu().numpy(), images)                     # the input is read only
+        x, flat, span = _shifted(images, shift_out, dev)
+        assert render.compose(x, out=x, **on_dev) is x                     # out is the input itself
+        assert np.array_equal(x.cpu().numpy(), want) and _guards_intact(flat, span)
+
+
+def test_outlined_pixels_are_those_of_boundaries(dev):
+    for name in ("outline_37x53", "outline_batch2_12x13"):
+        lab = GOLD[f"{name}.labels"]
+        grey = np.full(lab.shape + (3,), 7, np.uint8)
+        got = render.compose(grey, outlines=lab, outline_color=(255, 254, 253)).cpu().numpy()
+        edges = regions.boundaries(lab).cpu().numpy()
+        assert edges.any() and not edges.all() and np.array_equal(edges, R.boundaries(lab))
+        assert (got[edges] == (255, 254, 253)).all() and (got[~edges] == 7).all()
+        pal = np.asarray([(1, 2, 3), (4, 5, 6)], np.uint8)
+        got = render.compose(grey, outlines=lab, palette=pal).cpu().numpy()
+        ids = np.maximum(lab, 0)[edges]
+        assert np.array_equal(got[edges], pal[(ids - 1) % 2]) and (got[~edges] == 7).all()
+
+
+@pytest.mark.parametrize("connectivity", (1, 2))
+def test_boolean_outlines_are_labelled_first(dev, connectivity):
+    m = np.zeros((19, 23), bool)
+    m[2:6, 2:6] = True
+    m[6:9, 6:9] = True                                                     # touches the first at a corner only
+    m[12:18, 10:20] = True
+    m[14, 14] = False
+    img = np.random.RandomState(3).randint(0, 256, size=(19, 23, 3)).astype(np.uint8)
+    lab = regions.label(m, connectivity).cpu().numpy()
+    assert lab.max() == (3 if connectivity == 1 else 2)
+    pal = np.asarray([(255, 0, 0), (0, 255, 0), (0, 0, 255)], np.uint8)
+    got = render.compose(img, mask=m, outlines=m, palette=pal, connectivity=connectivity)
+    want = R.compose(img[None], mask=m[None], labels=lab[None], palette=pal)[0]
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+def _fast_compose(images, mask=None, heat=None, colormap=None, invert=True, labels=None, outline_color=(255, 255, 0)):
+    """the rules in whole-array numpy, for sizes the loops of render_ref are too slow for (checked against them below)"""
+    v = images.astype(np.int32)
+    if mask is not None:
+        v = (v + 255 * (mask != 0)[..., None]) >> 1
+    if heat is not None:
+        s = v + colormap.astype(np.int32)[255 - heat.astype(np.int32) if invert else heat.astype(np.int32)]
+        v = (s >> 1) + ((s & 1) & ((s >> 1) & 1))
+    if labels is not None:
+        ids = np.pad(np.maximum(labels, 0), ((0, 0), (1, 1), (1, 1)))
+        c = ids[:, 1:-1, 1:-1]
+        edge = (c > 0) & ((ids[:, :-2, 1:-1] != c) | (ids[:, 2:, 1:-1] != c) | (ids[:, 1:-1, :-2] != c) | (ids[:, 1:-1, 2:] != c))
+        v[edge] = outline_color
+    return v.astype(np.uint8)
+
+
+def _big(h, w, seed, block=8):
+    rng = np.random.RandomState(seed)
+    img = rng.randint(0, 256, size=(1, h, w, 3), dtype=np.uint8)
+    heat = rng.randint(0, 256, size=(1, h, w), dtype=np.uint8)
+    lab = (rng.randint(0, 40, size=(1, h // block + 1, w // block + 1)).astype(np.int32) - 8).repeat(block, 1).repeat(block, 2)[:, :h, :w]
+    return img, heat, np.ascontiguousarray(lab)
+
+
+def test_fast_restatement_is_the_loop_restatement():
+    img, heat, lab = _big(23, 31, 5)
+    table = R.jet()
+    assert np.array_equal(_fast_compose(img, mask=heat & 1, labels=lab), R.compose(img, mask=heat & 1, labels=lab))
+    for invert in (True, False):
+        assert np.array_equal(_fast_compose(img, heat=heat, colormap=table, invert=invert), R.compose(img, heat=heat, invert=invert))
+
+
+def test_several_workgroups_301x517(dev):
+    img, heat, lab = _big(301, 517, 6)
+    x = torch.from_numpy(img).to(dev)
+    table = R.jet()
+    assert np.array_equal(render.compose(x, mask=heat & 1, outlines=lab).cpu().numpy(), _fast_compose(img, mask=heat & 1, labels=lab))
+    assert np.array_equal(render.compose(x, heat=heat).cpu().numpy(), _fast_compose(img, heat=heat, colormap=table))
+    p = (heat.astype(np.float32) / np.float32(255.0)).astype(np.float32)
+    level = np.where(p > np.float32(0.25), (np.float32(255.0) * p).astype(np.int64) & 255, 0).astype(np.uint8)
+    assert np.array_equal(render.compose(x, heat=p, threshold=0.25, invert=False).cpu().numpy(),
+                          _fast_compose(img, heat=level, colormap=table, invert=False))
+    assert np.array_equal(render.compose(x).cpu().numpy(), img)            # no fill, no outlines: a copy
+
+
+@pytest.mark.parametrize("shape", ((40, 64), (3, 16), (33, 20), (2, 5)))
+def test_outline_runs_rows_a_multiple_of_4_and_shorter_than_a_run(dev, shape):
+    """W % 4 == 0 takes the rows above and below as vectors; W < 16 lets one run of 16 pixels cross several rows (and images)"""
+    img, heat, lab = _big(*shape, 8, block=2)
+    img, heat, lab = np.concatenate([img, img[:, ::-1]]), np.concatenate([heat, heat]), np.concatenate([lab, lab[:, ::-1]])
+    want = _fast_compose(img, mask=heat & 1, labels=lab)
+    assert np.array_equal(want, R.compose(img, mask=heat & 1, labels=lab))
+    assert np.array_equal(render.compose(img, mask=heat & 1, outlines=lab).cpu().numpy(), want)
+    x, flat, span = _shifted(img, 3, dev)
+    assert render.compose(x, mask=_shifted(heat & 1, 2, dev)[0], outlines=_shifted(lab, 1, dev)[0], out=x) is x
+    assert np.array_equal(x.cpu().numpy(), want) and _guards_intact(flat, span)
+
+
+def test_grid_cap_strides_over_a_large_image(dev):
+    """2912 x 2903 pixels are more runs of 16 than the capped grid has threads: some threads take two"""
+    img, heat, lab = _big(2912, 2903, 7)
+    assert img.size // 3 // 16 > 2048 * 256
+    x = torch.from_numpy(img).to(dev)
+    want = _fast_compose(img, mask=heat & 1, labels=lab)
+    got = render.compose(x, mask=torch.from_numpy(heat & 1).to(dev), outlines=torch.from_numpy(lab).to(dev))
+    assert np.array_equal(got.cpu().numpy(), want)
+    assert render.compose(x, mask=torch.from_numpy(heat & 1).to(dev), outlines=torch.from_numpy(lab).to(dev), out=x) is x
+    assert np.array_equal(x.cpu().numpy(), want)
+
+
+def _points_kwargs(kw):
+    kw = dict(kw)
+    if "color" in kw:
+        kw["color"] = tuple(int(v) for v in kw["color"])
+    return kw
+
+
+@pytest.mark.parametrize("name", POINTS)
+def test_points_pinned_cases_bit_equal(dev, name):
+    kw, want = R.golden_case(GOLD, name, R.POINTS_KEYS)
+    kw = _points_kwargs(kw)
+    canvas, pts = GOLD[f"{name}.canvas"], GOLD[f"{name}.points"]
+    c, flat, span = _shifted(canvas, 5, dev)
+    assert render.draw_points(c, pts, **kw) is c                           # in place; host points
+    first = c.cpu().numpy()
+    assert np.array_equal(first, want) and _guards_intact(flat, span)
+    on_dev = {k: torch.from_numpy(np.asarray(v)).to(dev) if k in ("offsets", "limits") else v for k, v in kw.items()}
+    if "offsets" not in on_dev:
+        on_dev["offsets"] = torch.tensor([0, len(pts)], dtype=torch.int64, device=dev)
+    spare = torch.cat([torch.from_numpy(pts), torch.full((3, 2), 5, dtype=torch.int64)]).to(dev)       # rows no image owns
+    c2 = torch.from_numpy(canvas).to(dev)
+    render.draw_points(c2, spare, **on_dev)                                # device points: the same bits in a second call
+    assert np.array_equal(c2.cpu().numpy(), first)
+    if canvas.shape[0] == 1 and "offsets" not in kw:
+        c3 = torch.from_numpy(canvas[0]).to(dev)                           # one [H, W, 3] canvas, points as a list of pairs
+        assert render.draw_points(c3, [tuple(int(v) for v in p) for p in pts], **kw) is c3
+        assert np.array_equal(c3.cpu().numpy(), want[0])
+
+
+def test_layers_are_calls_in_stream_order_and_the_later_wins(dev):
+    canvas = GOLD["dots_16x20_r4.canvas"]
+    a, b = [(5, 5), (8, 9)], [(6, 7), (20, 3)]
+    c = torch.from_numpy(canvas).to(dev)
+    render.draw_points(c, a, radius=4, color=(255, 0, 0))
+    render.draw_points(c, b, radius=3, color=(0, 0, 255))
+    want = R.draw_points(R.draw_points(canvas, a, radius=4, color=(255, 0, 0)), b, radius=3, color=(0, 0, 255))
+    assert np.array_equal(c.cpu().numpy(), want)
+    assert (want[0, 6, 7] == (0, 0, 255)).all() and (want[0, 5, 2] == (255, 0, 0)).all()
+    c = torch.from_numpy(canvas).to(dev)
+    for empty in ([], np.zeros((0, 2), np.int64), torch.zeros((0, 2), dtype=torch.int64, device=dev)):
+        assert render.draw_points(c, empty) is c
+    assert np.array_equal(c.cpu().numpy(), canvas)                          # no points: the canvas is as it was
+
+
+# ---- the front ends on hand-built results: no model is involved --------------------------------------------------------------------
+def _slide():
+    rng = np.random.RandomState(11)
+    H, W = 64, 80
+    img = rng.randint(0, 256, size=(H, W, 3)).astype(np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    mask = np.zeros((H, W), np.uint8)
+    for cy, cx, r in ((15, 20, 9), (40, 55, 12), (50, 12, 6)):
+        mask = np.maximum(mask, np.clip(255 - 14 * np.hypot(yy - cy, xx - cx) * 9 / r, 0, 255).astype(np.uint8))
+    pts = np.asarray([(15, 20), (40, 55), (50, 12), (2, 78), (63, 0), (30, 30), (0, 0), (44, 60)], np.int64)      # 5 kept, 3 discarded
+    return img, mask, pts
+
+
+def _dotted(img4, pts):
+    return R.draw_points(R.draw_points(img4, pts[:5], radius=4, color=(255, 0, 0)), pts[5:], radius=4, color=(0, 0, 255))
+
+
+def test_detect_result_render(dev):
+    img, mask, pts = _slide()
+    spare = torch.cat([torch.from_numpy(pts), torch.zeros((4, 2), dtype=torch.int64)]).to(dev)
+    res = D.DetectResult(pts, np.ones(8), np.asarray([0, 8], np.int64), np.asarray([8]), cell_counts=np.asarray([5]),
+                         device_points=spare, device_offsets=torch.tensor([0, 8], dtype=torch.int64, device=dev))
+    lab = regions.label(mask > 127).cpu().numpy()
+    got = res.render(img[None], mask=(mask > 127)[None], outlines=lab[None])
+    want = _dotted(R.compose(img[None], mask=(mask > 127)[None], labels=lab[None]), pts)
+    assert got.is_cuda and np.array_equal(got.cpu().numpy(), want)
+    host = D.DetectResult(pts, np.ones(8), np.asarray([0, 8], np.int64), np.asarray([8]), cell_counts=5)      # no device points
+    assert np.array_equal(host.render(img, heat=mask).cpu().numpy(), _dotted(R.compose(img[None], heat=mask[None]), pts)[0])
+    every = D.DetectResult(pts, np.ones(8), np.asarray([0, 8], np.int64), np.asarray([8]))                    # no cap: all kept
+    assert np.array_equal(every.render(img).cpu().numpy(), R.draw_points(img[None], pts, radius=4, color=(255, 0, 0))[0])
+
+
+def test_render_slide(dev):
+    img, mask, pts = _slide()
+    res = inference.SlideResult(pts[:5], pts[5:], 5, torch.from_numpy(mask).to(dev))
+    got = inference.render_slide(img, res)
+    assert got.is_cuda and tuple(got.shape) == img.shape
+    assert np.array_equal(got.cpu().numpy(), _dotted(R.compose(img[None], mask=(mask > 127)[None]), pts)[0])
+    got = inference.render_slide(torch.from_numpy(img).to(dev), res, thr_u8=30)
+    assert np.array_equal(got.cpu().numpy(), _dotted(R.compose(img[None], mask=(mask > 30)[None]), pts)[0])
+    table = R.jet()[:, ::-1].copy()
+    got = inference.render_slide(img, res, fill="heat", colormap=table, invert=False)
+    assert np.array_equal(got.cpu().numpy(), _dotted(R.compose(img[None], heat=mask[None], colormap=table, invert=False), pts)[0])
+    lab = regions.label(mask > 127).cpu().numpy()
+    got = inference.render_slide(img, res, fill=None, outlines=mask > 127, outline_color=(0, 255, 0))
+    assert np.array_equal(got.cpu().numpy(), _dotted(R.compose(img[None], labels=lab[None], outline_color=(0, 255, 0)), pts)[0])
+    none = inference.SlideResult(pts[:5], [], 5, torch.from_numpy(mask).to(dev))                              # nothing discarded
+    got = inference.render_slide(img, none, fill=None)
+    assert np.array_equal(got.cpu().numpy(), R.draw_points(img[None], pts[:5], radius=4, color=(255, 0, 0))[0])
+
+
+def test_reference_named_front_ends_24x31(dev):
+    rng = np.random.RandomState(12)
+    img = rng.randint(0, 256, size=(24, 31, 3)).astype(np.uint8)
+    grids = np.asarray([(3, 4), (23, 30), (10, 15), (0, 29)], np.int64)
+    gone = np.asarray([(11, 16), (26, 2)], np.int64)
+    got = render.locate_cells(img, grids, gone)
+    want = R.draw_points(R.draw_points(img[None], grids, radius=4, color=(255, 0, 0)), gone, radius=4, color=(0, 0, 255))[0]
+    assert got.is_cuda and np.array_equal(got.cpu().numpy(), want)
+    x = torch.from_numpy(img).to(dev)
+    assert np.array_equal(render.locate_cells(x, grids).cpu().numpy(), R.draw_points(img[None], grids, radius=4, color=(255, 0, 0))[0])
+    assert np.array_equal(x.cpu().numpy(), img)                            # drawn on a copy
+    xy = grids[:, ::-1].copy()
+    assert np.array_equal(render.dotting(img, xy).cpu().numpy(), R.draw_points(img[None], xy, xy=True)[0])
+    got = render.dotting(x, [tuple(int(v) for v in p) for p in xy], radius=5, color=(0, 255, 0), thickness=2)
+    assert got is x                                                        # a device image is drawn on, as cv2.circle does
+    assert np.array_equal(x.cpu().numpy(), R.draw_points(img[None], xy, radius=5, color=(0, 255, 0), thickness=2, xy=True)[0])
+    m = rng.randint(0, 4, size=(24, 31)) > 0                               # specks and pinholes for the clean-up to remove
+    assert np.array_equal(render.overlap_mask(img, m, postprocess=False).cpu().numpy(), R.compose(img[None], mask=m[None])[0])
+    clean = regions.remove_small_regions(m, 20, 3).cpu().numpy()
+    assert (clean != m).any()
+    assert np.array_equal(render.overlap_mask(img, m, min_object_size=20, hole_area_threshold=3).cpu().numpy(),
+                          R.compose(img[None], mask=clean[None])[0])
+    imgs = rng.randint(0, 256, size=(2, 24, 31, 3)).astype(np.uint8)
+    p = rng.uniform(0, 1, size=(2, 24, 31)).astype(np.float32)
+    p[0, 0, :2] = (0.5, 1.0)
+    hard = render.save_images_with_masks(imgs, p, 0.5)
+    assert np.array_equal(hard.cpu().numpy(), R.compose(imgs, mask=p > np.float32(0.5)))
+    blended, soft = render.save_images_with_masks([imgs[0], imgs[1]], [p[0], p[1]], 0.5, soft=True)
+    want_soft = np.asarray([[[R.heat_level(v, 0.5) for v in row] for row in plane] for plane in p], np.uint8)
+    assert soft.is_cuda and soft.dtype == torch.uint8 and np.array_equal(soft.cpu().numpy(), want_soft)
+    assert np.array_equal(blended.cpu().numpy(), R.compose(imgs, heat=p, threshold=0.5))
+    assert np.array_equal(render.compose(imgs, heat=p, threshold=0.5).cpu().numpy(), blended.cpu().numpy())  # the kernel's own float path
