@@ -153,6 +153,8 @@ _SIGNATURES = {
     "cs_stitch_workspace": (c_size_t, [c_int, c_int]),
     "cs_stitch_patches": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "cs_stitch_logits": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P]),
+    "cs_stitch_blend_add": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P, _P]),
+    "cs_stitch_blend_finish": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "cs_detect_grid_size": (c_int, [c_int, c_int, c_int, c_int]),
     "cs_detect_meanshift": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _P, _P, _P]),
     "cs_detect_cluster_workspace": (c_size_t, [c_int, c_int]),

@@ -10,6 +10,8 @@
 //   stitch    patches written into a zeroed whole-image mask, the highest patch index winning where patches overlap
 //   streamed  the same mask built batch by batch: softmax channel + quantise of a batch of logits written in place in one launch,
 //             the owner of a pixel decided from the batch's corners (no per-pixel state); earlier batches are overwritten in stream order
+//   blended   overlaps averaged instead of overwritten: per pixel the integer sums of w * level and of w over every covering patch
+//             (flipped views included), mask = floor(sum / (256 sum of w)); the lowest covering index of a batch owns the update
 //   distance  method="distancetransform" puts the exact distance transform of morph.hip in the blur's place; the rest is unchanged
 // Every step is integer arithmetic or one correctly rounded fp64 operation, so the result does not depend on launch order.
 #include "cs_common.h"
@@ -203,6 +205,109 @@ __global__ __launch_bounds__(256) void stitch_logits_kernel(const float* __restr
                 if ((want >> j) & 1u) mask[dst + j] = quant(softmax_channel_at(logits + (src + j), plane, C, ch));
         }
     }
+}
+
+// ---- blended stitching: every patch that covers a pixel adds its weighted level to two whole-image accumulators ------------------
+// The level of a probability: quant()'s clamp, then 256 steps per mask level.  The product by 256 is exact in fp32, so
+// blend_level(p) >> 8 == quant(p); a NaN gives 0, as in quant.
+__device__ __forceinline__ uint32_t blend_level(float p) {
+    const float v = fminf(fmaxf(255.0f * p, 0.f), 255.f);
+    return (uint32_t)(256.0f * v);
+}
+
+// num[R][Cc] += sum of w q, den[R][Cc] += sum of w over the patches m of the batch that cover slide pixel (R, Cc): q = blend_level of
+// the softmax of patch m at that pixel, w = tr[i] tc[j] with (i, j) the pixel's position inside patch m ON THE SLIDE.  flips[m]
+// (1 horizontal, 2 vertical, 3 both) says that logits[m] are those of the flipped tile: slide position (i, j) reads logit pixel
+// (ph-1-i if code & 2 else i, pw-1-j if code & 1 else j).
+// Ownership comes from the corners alone, as in stitch_logits_kernel, with the LOWEST covering index as the owner: a
+// workgroup-uniform walk over the earlier corners strips the pixels that an earlier patch covers, a second walk over the patches
+// from b on sums every contribution in registers, and the owner does one plain read-modify-write.  So an accumulator element is
+// updated at most once per launch, without atomics and whatever order the workgroups run in; integer sums make the result
+// independent of how the patches are split into launches.  Units are four slide pixels at a 4-element boundary of the
+// accumulators (16 bytes of den, 32 of num): a wholly owned unit is vector loads and stores, the rest element by element.
+__global__ __launch_bounds__(256) void stitch_blend_add_kernel(const float* __restrict__ logits, const int32_t* __restrict__ corners,
+                                                               const uint8_t* __restrict__ flips, const int32_t* __restrict__ tr,
+                                                               const int32_t* __restrict__ tc, int B, int C, int ch, int ph, int pw, int H,
+                                                               int W, int ng, int chunks, unsigned long long* __restrict__ num,
+                                                               uint32_t* __restrict__ den) {
+    const long long items = (long long)B * chunks, plane = (long long)ph * pw;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        const int b = (int)(item / chunks);
+        const int u = (int)(item - (long long)b * chunks) * 256 + threadIdx.x;
+        const long long r0 = corners[2 * b], c0 = corners[2 * b + 1];
+        if (r0 >= H || r0 + ph <= 0 || c0 >= W || c0 + pw <= 0) continue;          // workgroup-uniform: the patch misses the slide
+        const int r = u / ng, g = u - r * ng;
+        const int R = (int)r0 + r;
+        if (r >= ph || R < 0 || R >= H) continue;
+        const long long row = (long long)R * W;
+        const int lead = (int)((row + c0) & 3);                                      // elements between the unit boundary and the patch row
+        const int p0 = 4 * g - lead, C0 = (int)c0 + p0;                              // the unit's first column in the patch / on the slide
+        uint32_t want = unit_bits(max(-p0, -C0), min(pw - p0, W - C0));              // inside the patch and inside the slide
+        if (!want) continue;
+        for (int m = 0; m < b; ++m) {                                                // an earlier patch that covers a pixel owns it
+            const long long mr = corners[2 * m], mc = corners[2 * m + 1];
+            if (mr >= r0 + ph || mr + ph <= r0 || mc >= c0 + pw || mc + pw <= c0) continue;      // workgroup-uniform: rectangles apart
+            if ((unsigned)(R - (int)mr) < (unsigned)ph) want &= ~unit_bits((int)mc - C0, (int)mc + pw - C0);
+        }
+        if (!want) continue;
+        unsigned long long sn[4] = {0, 0, 0, 0};
+        uint32_t sd[4] = {0, 0, 0, 0};
+        for (int m = b; m < B; ++m) {                                                // patch b itself, then the later ones that reach it
+            const long long mr = corners[2 * m], mc = corners[2 * m + 1];
+            if (mr >= r0 + ph || mr + ph <= r0 || mc >= c0 + pw || mc + pw <= c0) continue;      // workgroup-uniform
+            const int i = R - (int)mr;
+            if ((unsigned)i >= (unsigned)ph) continue;
+            const uint32_t cover = want & unit_bits((int)mc - C0, (int)mc + pw - C0);
+            if (!cover) continue;
+            const int code = flips ? flips[m] : 0;
+            const long long base = ((long long)m * C * ph + ((code & 2) ? ph - 1 - i : i)) * pw;     // channel 0 of the logit row
+            const uint32_t wr = (uint32_t)tr[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((cover >> j) & 1u)) continue;
+                const int jj = C0 + j - (int)mc;
+                const uint32_t w = wr * (uint32_t)tc[jj];
+                const uint32_t q = blend_level(softmax_channel_at(logits + (base + ((code & 1) ? pw - 1 - jj : jj)), plane, C, ch));
+                sn[j] += (unsigned long long)w * q;
+                sd[j] += w;
+            }
+        }
+        const long long dst = row + C0;                                               // 64-bit: a slide may exceed 2^31 pixels
+        if (want == 0xfu) {
+            ulonglong2* n2 = reinterpret_cast<ulonglong2*>(num + dst);
+            uint4* d4 = reinterpret_cast<uint4*>(den + dst);
+            ulonglong2 lo = n2[0], hi = n2[1];
+            uint4 d = *d4;
+            lo.x += sn[0]; lo.y += sn[1]; hi.x += sn[2]; hi.y += sn[3];
+            d.x += sd[0]; d.y += sd[1]; d.z += sd[2]; d.w += sd[3];
+            n2[0] = lo; n2[1] = hi;
+            *d4 = d;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((want >> j) & 1u) {
+                    num[dst + j] += sn[j];
+                    den[dst + j] += sd[j];
+                }
+        }
+    }
+}
+
+// mask = den ? floor(num / (256 den)) : 0.  num <= 255 * 256 * den for sums that stitch_blend_add_kernel made, so the byte holds it.
+__device__ __forceinline__ uint32_t blend_byte(unsigned long long n, uint32_t d) {
+    return d ? (uint32_t)(n / (256ull * d)) & 0xffu : 0u;
+}
+// n4 four-pixel units with vector loads and one dword store (0 when a buffer is not aligned for them), the rest element by element.
+__global__ __launch_bounds__(256) void stitch_blend_finish_kernel(const unsigned long long* __restrict__ num, const uint32_t* __restrict__ den,
+                                                                  long long n, long long n4, uint8_t* __restrict__ mask) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+    for (long long i = t; i < n4; i += step) {
+        const ulonglong2 lo = reinterpret_cast<const ulonglong2*>(num)[2 * i], hi = reinterpret_cast<const ulonglong2*>(num)[2 * i + 1];
+        const uint4 d = reinterpret_cast<const uint4*>(den)[i];
+        reinterpret_cast<uint32_t*>(mask)[i] =
+            blend_byte(lo.x, d.x) | (blend_byte(lo.y, d.y) << 8) | (blend_byte(hi.x, d.z) << 16) | (blend_byte(hi.y, d.w) << 24);
+    }
+    for (long long i = 4 * n4 + t; i < n; i += step) mask[i] = (uint8_t)blend_byte(num[i], den[i]);
 }
 
 // ---- seeds + mean shift -------------------------------------------------------------------------------------------------------
@@ -614,6 +719,42 @@ extern "C" int cs_stitch_logits(const float* logits, int B, int C, int ph, int p
     const int chunks = cs_ceil_div(units, 256);
     hipLaunchKernelGGL(stitch_logits_kernel, dim3(grid_for((long long)B * chunks * 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        logits, corners, B, C, ch, ph, pw, H, W, ng, chunks, mask);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_stitch_blend_add(const float* logits, int B, int C, int ph, int pw, int ch, const int32_t* corners, const uint8_t* flips,
+                                   const int32_t* taps_r, const int32_t* taps_c, int H, int W, int64_t* num, int32_t* den, void* stream) {
+    CS_CHECK_ARG(num && den && taps_r && taps_c && H > 0 && W > 0 && B >= 0 && ph > 0 && pw > 0, "stitch_blend_add: bad arguments");
+    CS_CHECK_ARG(C >= 2 && ch >= 0 && ch < C, "stitch_blend_add: needs at least two channels and 0 <= ch < C");
+    CS_CHECK_ARG(B == 0 || (logits && corners), "stitch_blend_add: NULL logits or corners");
+    CS_CHECK_ARG(H < (1 << 29) && W < (1 << 29) && ph <= H && pw <= W, "stitch_blend_add: the patch must fit the slide, whose sides stay below 2^29");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3) == 0 && (reinterpret_cast<uintptr_t>(corners) & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(taps_r) & 3) == 0 && (reinterpret_cast<uintptr_t>(taps_c) & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(num) & 15) == 0 && (reinterpret_cast<uintptr_t>(den) & 15) == 0,
+                 "stitch_blend_add: misaligned buffers (the accumulators need 16 bytes)");
+    CS_CHECK_ARG(B <= 32768, "stitch_blend_add: at most 32768 patches in one call (the sum of their weights stays below 2^31)");
+    if (B == 0) return CS_OK;
+    const int ng = pw / 4 + 2;                                   // four-pixel units that span a patch row at any alignment
+    const long long units = (long long)ph * ng;
+    CS_CHECK_ARG(units < (1LL << 30), "stitch_blend_add: patch too large");
+    const int chunks = cs_ceil_div(units, 256);
+    hipLaunchKernelGGL(stitch_blend_add_kernel, dim3(grid_for((long long)B * chunks * 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       logits, corners, flips, taps_r, taps_c, B, C, ch, ph, pw, H, W, ng, chunks, reinterpret_cast<unsigned long long*>(num),
+                       reinterpret_cast<uint32_t*>(den));
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_stitch_blend_finish(const int64_t* num, const int32_t* den, int H, int W, uint8_t* mask, void* stream) {
+    CS_CHECK_ARG(num && den && mask && H > 0 && W > 0, "stitch_blend_finish: bad arguments");
+    CS_CHECK_ARG(H < (1 << 29) && W < (1 << 29), "stitch_blend_finish: the slide's sides stay below 2^29");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(num) & 7) == 0 && (reinterpret_cast<uintptr_t>(den) & 3) == 0, "stitch_blend_finish: misaligned buffers");
+    const long long n = (long long)H * W;
+    const bool vec = (reinterpret_cast<uintptr_t>(num) & 15) == 0 && (reinterpret_cast<uintptr_t>(den) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+    hipLaunchKernelGGL(stitch_blend_finish_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const unsigned long long*>(num), reinterpret_cast<const uint32_t*>(den), n, vec ? n >> 2 : 0LL, mask);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -30,6 +30,8 @@ Steps, each integer arithmetic or one correctly rounded fp64 operation, so the r
 Whole slides: ``stitch_patches`` builds the whole-image mask from patches that are all resident; ``stitch_logits`` builds the same
 bytes batch by batch, straight from the segment logits (softmax channel, quantise and the overlap rule in one launch per batch, the
 owner of a pixel decided from the batch's corners, no per-pixel state).  ``inference.detect_slide`` is the loop around it.
+``StitchBlend`` / ``stitch_blend`` (not in the reference) average the overlaps instead: integer weighted sums of every covering
+patch, flipped views included, in two whole-image accumulators (``detect_slide(blend=, tta=)``).
 
 ``meanshift_cluster`` itself still refuses ``"distancetransform"``; ``detect_points(mask, cell_counts=c,
 method="distancetransform").per_image()[0]`` returns the pair it would.
@@ -217,6 +219,180 @@ def stitch_logits(mask, logits, corners, ch=1):
     that follow its patch, so keep a batch at tens of patches (DESIGN.md has the figures).  Returns the mask."""
     grid = _check_stitch_logits(mask, logits, corners, ch)
     return K.stitch_logits(mask, logits.contiguous(), torch.from_numpy(grid.astype(np.int32)).to(mask.device), int(ch))
+
+
+_MAX_TAP = 255
+_WINDOWS = ("linear", "uniform")
+
+
+def _check_ramp(ramp):
+    if ramp is None:
+        return _MAX_TAP
+    if isinstance(ramp, bool) or not isinstance(ramp, (int, np.integer)) or not 1 <= ramp <= _MAX_TAP:
+        raise ValueError(f"blend: ramp must be an integer in 1..{_MAX_TAP} (None: {_MAX_TAP}), got {ramp!r}")
+    return int(ramp)
+
+
+def blend_taps(n, window="linear", ramp=None):
+    """The weights of one patch axis of ``n`` pixels for ``StitchBlend`` -> int32 numpy [n], every tap in 1..255.  ``"linear"``:
+    ``min(i + 1, n - i, ramp)``, a ramp from 1 at either edge to ``ramp`` (None: 255) and flat between -- a patch's edge, where a
+    zero-padded CNN is least reliable, counts least.  ``"uniform"``: all ones, the plain mean of the covering patches."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"blend_taps: n must be a positive integer, got {n!r}")
+    if not isinstance(window, str) or window not in _WINDOWS:
+        raise ValueError(f"blend_taps: window must be one of {_WINDOWS}, got {window!r}")
+    ramp = _check_ramp(ramp)
+    if window == "uniform":
+        return np.ones((int(n),), np.int32)
+    i = np.arange(int(n), dtype=np.int64)
+    return np.minimum(np.minimum(i + 1, int(n) - i), ramp).astype(np.int32)
+
+
+def _blend_windows(window, ramp, ph, pw):
+    """``window`` / ``ramp`` of StitchBlend -> the (row taps [ph], column taps [pw]) int32 numpy pair"""
+    if isinstance(window, str):
+        return blend_taps(ph, window, ramp), blend_taps(pw, window, ramp)
+    if ramp is not None:
+        raise ValueError("blend: ramp goes with a named window, not with explicit taps")
+    try:
+        tr, tc = (np.asarray(t) for t in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"blend: window must be one of {_WINDOWS} or a pair (row taps, column taps), got {window!r}") from None
+    for t, n, axis in ((tr, ph, "row"), (tc, pw, "column")):
+        if t.dtype.kind not in "iu" or t.shape != (n,):
+            raise ValueError(f"blend: expected {n} integer {axis} taps, got {t.dtype} of shape {tuple(t.shape)}")
+        if t.min() < 1 or t.max() > _MAX_TAP:
+            raise ValueError(f"blend: every {axis} tap lies in 1..{_MAX_TAP}")
+    return tr.astype(np.int32), tc.astype(np.int32)
+
+
+class StitchBlend:
+    """A whole-image mask in which overlapping patches are blended instead of overwritten, and to which flipped views of a patch
+    (test-time augmentation) contribute like any other patch.  Integer arithmetic throughout (csrc/detect.hip):
+
+    * level   ``q = uint32(256 * clamp(255 p, 0, 255))`` of the fp32 probability ``p = softmax_channel_fwd(logits, ch)``: 0..65280,
+              ``q >> 8`` is the byte ``quantize`` makes of ``p``, a NaN gives 0.
+    * weight  ``w = tr[i] * tc[j]`` for the pixel at row i, column j of its patch ON THE SLIDE; ``tr`` / ``tc`` are ``blend_taps`` of
+              the patch sides (``window`` "linear" or "uniform", ``ramp``) or the explicit pair ``window=(row taps, column taps)``
+              of integers in 1..255.
+    * sums    per slide pixel ``num += w q`` (int64 [H, W]) and ``den += w`` (int32 [H, W]): 12 bytes per pixel, owned by this
+              object and zeroed at the start.
+    * finish  ``mask = num // (256 den)``, 0 where ``den == 0``.  A pixel that one patch covers holds exactly the byte
+              ``stitch_logits`` writes; a patch added twice changes nothing.
+
+    Being integer sums, the accumulators do not depend on how the patches are split into ``add`` calls or on their order.  ``add``
+    is one launch without atomics; as with ``stitch_logits``, ALL CALLS FOR ONE ACCUMULATOR MUST BE ISSUED ON THE SAME STREAM."""
+
+    def __init__(self, image_hw, patch_hw, window="linear", ramp=None, device=None):
+        try:
+            H, W = (int(v) for v in image_hw)
+            ph, pw = (int(v) for v in patch_hw)
+        except (TypeError, ValueError):
+            raise ValueError(f"StitchBlend: image_hw and patch_hw are pairs of integers, got {image_hw!r} and {patch_hw!r}") from None
+        if not (0 < ph <= H < 1 << 29 and 0 < pw <= W < 1 << 29):
+            raise ValueError(f"StitchBlend: a {ph}x{pw} patch does not fit a {H}x{W} image (sides below 2^29)")
+        tr, tc = _blend_windows(window, ramp, ph, pw)
+        self.image_hw, self.patch_hw, self.taps = (H, W), (ph, pw), (tr, tc)
+        self._wmax = int(tr.max()) * int(tc.max())
+        self.n_added = 0                                                   # patches added since the last reset: the den bound
+        device = _device() if device is None else torch.device(device)
+        self.num = torch.zeros((H, W), dtype=torch.int64, device=device)
+        self.den = torch.zeros((H, W), dtype=torch.int32, device=device)
+        self._tr, self._tc = torch.from_numpy(tr).to(device), torch.from_numpy(tc).to(device)
+
+    def _check_add(self, logits, corners, flips, ch):
+        """Argument checks of add, all on the host -> (corners, flips) as device operands.  Corners and flips that are host data are
+        checked by value and uploaded; device tensors are taken as they are, without a copy back (the kernel clips a patch that
+        leaves the slide and reads the two low bits of a flip code).  The device check comes last, so that every other error is
+        the same with host tensors."""
+        if not torch.is_tensor(logits):
+            raise TypeError("stitch_blend: expected the logits as a torch tensor")
+        if logits.dtype != torch.float32:
+            raise TypeError(f"stitch_blend: expected float32 logits, got {logits.dtype}")
+        if logits.dim() != 4:
+            raise ValueError(f"stitch_blend expects logits shaped [B, C, ph, pw], got shape {tuple(logits.shape)}")
+        B, C, ph, pw = logits.shape
+        (H, W), dev = self.image_hw, self.num.device
+        if (ph, pw) != self.patch_hw:
+            raise ValueError(f"stitch_blend: the taps are those of {self.patch_hw} patches, got {(ph, pw)}")
+        if C < 2:
+            raise ValueError(f"stitch_blend: the softmax needs at least two channels, got {C}")
+        if int(ch) != ch or not 0 <= ch < C:
+            raise ValueError(f"stitch_blend: channel {ch!r} is not one of the {C} channels")
+        if torch.is_tensor(corners) and corners.is_cuda:
+            if corners.dtype != torch.int32 or tuple(corners.shape) != (B, 2):
+                raise ValueError(f"stitch_blend: device corners are int32 [{B}, 2], got {corners.dtype} {tuple(corners.shape)}")
+            rc = corners.contiguous()
+        else:
+            grid = np.asarray(corners, dtype=np.int64).reshape(-1, 2)
+            if len(grid) != B:
+                raise ValueError(f"{B} patches but {len(grid)} corners")
+            if B and (grid.min() < 0 or (grid[:, 0] + ph).max() > H or (grid[:, 1] + pw).max() > W):
+                raise ValueError("a patch does not lie inside the image")
+            rc = grid.astype(np.int32)
+        if flips is None:
+            fl = None
+        elif torch.is_tensor(flips) and flips.is_cuda:
+            if flips.dtype not in (torch.uint8, torch.int8) or tuple(flips.shape) != (B,):
+                raise ValueError(f"stitch_blend: device flips are uint8 [{B}], got {flips.dtype} {tuple(flips.shape)}")
+            fl = flips.contiguous().view(torch.uint8)
+        else:
+            fl = np.asarray(flips)
+            if fl.dtype.kind not in "iu" or fl.shape != (B,):
+                raise ValueError(f"stitch_blend: expected {B} integer flip codes, got {fl.dtype} of shape {tuple(fl.shape)}")
+            if B and (fl.min() < 0 or fl.max() > 3):
+                raise ValueError("stitch_blend: a flip code is 0 (none), 1 (horizontal), 2 (vertical) or 3 (both)")
+            fl = fl.astype(np.uint8)
+        if (self.n_added + B) * self._wmax >= 1 << 31:
+            raise OverflowError(f"stitch_blend: {self.n_added} + {B} patches of weight up to {self._wmax} could overflow the int32 "
+                                "weight sum; finish and reset, or use smaller taps")
+        if not dev.type == "cuda":
+            raise ValueError("stitch_blend adds in place on the device: the accumulators must be device tensors")
+        if logits.device != dev:
+            raise ValueError(f"stitch_blend: logits on {logits.device}, accumulators on {dev}")
+        for t in (rc, fl):
+            if torch.is_tensor(t) and t.device != dev:
+                raise ValueError(f"stitch_blend: corners or flips on {t.device}, accumulators on {dev}")
+        if isinstance(rc, np.ndarray):
+            rc = torch.from_numpy(rc).to(dev)
+        if isinstance(fl, np.ndarray):
+            fl = torch.from_numpy(fl).to(dev)
+        return rc, fl
+
+    def add(self, logits, corners, flips=None, ch=1):
+        """Add a batch of segment logits fp32 [B, C, ph, pw] at upper-left corners [B, 2] (row, col) in one launch -> self.
+        ``flips``: B of ``augment``'s codes (0 none, 1 horizontal, 2 vertical, 3 both) saying that ``logits[b]`` are those of the
+        flipped tile; logit pixel (i, j) then belongs to slide pixel ``(r + (ph-1-i if code & 2 else i), c + (pw-1-j if code & 1 else
+        j))`` and is weighted by the taps of that position.  Corners, and (corner, flip) pairs, may repeat within a batch.  With
+        corners and flips already int32 / uint8 device tensors nothing here synchronises with the host.  Raises OverflowError,
+        before anything is enqueued, once ``patches added * max(tr) * max(tc)`` would reach 2^31 (the int32 weight sum)."""
+        rc, fl = self._check_add(logits, corners, flips, ch)
+        K.stitch_blend_add(self.num, self.den, logits.contiguous(), rc, self._tr, self._tc, fl, int(ch))
+        self.n_added += int(logits.shape[0])
+        return self
+
+    def finish(self, out=None):
+        """The blended uint8 [H, W] device mask of everything added so far (into ``out`` when given).  The accumulators are only
+        read: ``finish`` may be called again, and more ``add`` calls may follow."""
+        if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != self.image_hw
+                                or not out.is_contiguous() or out.device != self.num.device):
+            raise ValueError(f"stitch_blend: out must be a contiguous uint8 {list(self.image_hw)} tensor on {self.num.device}")
+        return K.stitch_blend_finish(self.num, self.den, out)
+
+    def reset(self):
+        """Zero the accumulators -> self."""
+        self.num.zero_()
+        self.den.zero_()
+        self.n_added = 0
+        return self
+
+
+def stitch_blend(logits, corners, image_hw, flips=None, ch=1, window="linear", ramp=None):
+    """``StitchBlend`` in one shot: the blended uint8 [H, W] device mask of one batch of logits fp32 [B, C, ph, pw] at ``corners``."""
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise ValueError("stitch_blend expects logits shaped [B, C, ph, pw] as a torch tensor")
+    sb = StitchBlend(image_hw, logits.shape[-2:], window, ramp, logits.device)
+    return sb.add(logits, corners, flips, ch).finish()
 
 
 @dataclass

@@ -208,8 +208,64 @@ class SlideResult:
     stain = None
 
 
+def _check_blend(blend, tta, ph, pw):
+    """``blend=`` / ``tta=`` of detect_slide -> (taps, codes): the ``(row taps, column taps)`` pair of ``detect.StitchBlend`` and the
+    flip codes of the views, un-flipped first; every error on the host."""
+    from . import detect as D
+    codes = (0,)
+    if tta is not None:
+        try:
+            codes = tuple(tta)
+        except TypeError:
+            raise TypeError(f"detect_slide: tta must be a sequence of flip codes, got {tta!r}") from None
+        if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= 3 for c in codes):
+            raise ValueError(f"detect_slide: a tta flip code is 0 (none), 1 (horizontal), 2 (vertical) or 3 (both), got {tta!r}")
+        if len(set(codes)) != len(codes) or 0 not in codes:
+            raise ValueError(f"detect_slide: tta must hold distinct flip codes, the un-flipped view 0 among them, got {tta!r}")
+        codes = (0,) + tuple(int(c) for c in codes if c != 0)
+        if blend is None:
+            blend = True
+    if blend is True:
+        blend = {}
+    elif isinstance(blend, str):
+        blend = {"window": blend}
+    elif not isinstance(blend, dict):
+        raise TypeError(f"detect_slide: blend must be None, True, 'linear', 'uniform' or a dict with window and ramp, got {blend!r}")
+    unknown = set(blend) - {"window", "ramp"}
+    if unknown:
+        raise TypeError(f"detect_slide: blend has no entries {sorted(unknown)}")
+    return D._blend_windows(blend.get("window", "linear"), blend.get("ramp"), ph, pw), codes
+
+
+def _blended_loop(model, img, ti, rc, size, batch_size, dtype, total, taps, codes):
+    """detect_slide's loop with blending on -> the blended uint8 [H, W] mask.  Per batch of corners and per view of ``codes``: stage
+    (view 0 by ``tiles.gather_tiles`` as in the plain loop, a flipped view by ``augment.stage_tiles``' kernel with that flip code
+    for every tile), segment forward, ``StitchBlend.add`` with the view's code; the image-mode counts of view 0 alone are added to
+    ``total``.  Every operand is a device tensor made before the loop, so nothing in it synchronises; ``finish`` runs once after
+    it."""
+    from . import detect as D
+    from . import tiles as T
+    sb = D.StitchBlend(img.shape[1:3], (size, size), taps, device=img.device)
+    if len(rc) * len(codes) * sb._wmax >= 1 << 31:                         # add would raise part of the way through the slide
+        raise OverflowError(f"detect_slide: {len(rc)} patches in {len(codes)} views of weight up to {sb._wmax} could overflow the "
+                            "int32 weight sum of the blend; pass a smaller ramp (blend={'ramp': 16})")
+    flips = {c: torch.full((batch_size,), c, dtype=torch.int8, device=img.device) for c in codes if c}
+    with torch.no_grad():
+        for i in range(0, len(rc), batch_size):
+            bi, brc = ti[i:i + batch_size], rc[i:i + batch_size]
+            for code in codes:
+                fl = flips[code][:len(brc)] if code else None
+                x = K.stage_augmented(img, bi, brc, size, size, flips=fl, dtype=dtype) if code else T.gather_tiles(img, bi, brc, size, dtype)
+                model.setmode("segment")
+                sb.add(model(x).float().contiguous(), brc, fl, 1)
+                if not code:
+                    model.setmode("image")
+                    total += _rounded_counts(model, x).sum(dtype=torch.float64)
+    return sb.finish()
+
+
 def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, interval=None, eps=11, reg_limit=True,
-                 method="gaussianblur", thr_for_dt=10, tissue=None, stain=None, **blur):
+                 method="gaussianblur", thr_for_dt=10, tissue=None, stain=None, blend=None, tta=None, **blur):
     """The loop of ``cell_detect`` (test_seg.py:182-316) for one slide or ROI, streamed on the device -> SlideResult.
 
     image_u8: uint8 [H, W, 3], numpy or torch; it is moved to the device once.  ``tiles.sample_patches`` gives the (row, col) patch
@@ -236,6 +292,21 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     ``SlideResult.stain`` holds the slide's own ``StainEstimate``.  The estimate's three small copies to the host happen before
     the loop; there is none inside it.
 
+    ``blend`` (not in the reference, whose last writer wins every overlap): None, the default, reaches none of it.  ``True``
+    (linear window, full ramp), ``"linear"``, ``"uniform"`` or a dict with ``window`` and ``ramp`` (``detect.blend_taps``; ``window``
+    may also be an explicit pair of tap sequences) feeds the logits of every batch to a ``detect.StitchBlend`` instead: per pixel
+    the weighted integer mean of every patch that covers it, the weight falling towards a patch's edge, so that no seam is left
+    where patches meet and a smaller ``interval`` buys a smoother mask.  The mask is its ``finish()``, taken once after the loop,
+    and does not depend on ``batch_size``; a pixel that one patch covers holds the byte it holds without ``blend``.  The two
+    accumulators take 12 bytes per slide pixel while the loop runs.
+
+    ``tta``: None, or a sequence of distinct flip codes with 0 among them, e.g. ``(0, 1, 2, 3)`` (``augment``'s codes: 1 horizontal,
+    2 vertical, 3 both): every batch also runs through the segment forward once per flipped view, staged by
+    ``augment.stage_tiles``' kernel, and the view's logits are added to the same ``StitchBlend`` with its code, which puts every
+    pixel back where it belongs on the slide.  ``tta`` alone turns on ``blend=True``.  ``cell_count`` still sums ``rint(reg)`` of
+    the un-flipped view only, so the count and the cap it puts on the points do not depend on ``tta``.  Both compose with
+    ``tissue`` and ``stain`` unchanged; pixels that no kept patch covers are 0.
+
     Not done here: reading ``.svs`` / ``.png`` files (OpenSlide is not a dependency), writing the CSV and PNG files, and the
     ``name-<xoffset>`` file-name convention -- the caller adds the offset to ``points[:, 1]``.  ``meanshift_cluster(...,
     "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
@@ -253,6 +324,7 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
         raise ValueError(f"detect_slide cuts square patches (tiles.gather_tiles), got patch_size {(ph, pw)}")
     if int(batch_size) < 1:
         raise ValueError(f"batch_size must be positive, got {batch_size!r}")
+    blended = None if blend is None and tta is None else _check_blend(blend, tta, ph, pw)
     img = _tensor(image_u8)
     if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
         raise TypeError("detect_slide expects a uint8 image shaped [H, W, 3] (numpy or torch)")
@@ -270,17 +342,20 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     source = None
     if stain is not None:                                                  # the loop reads the normalised copy from here on
         img, source = St._normalize_slide(img, None if kept is None else kept.mask[None], *stain)
-    mask = torch.zeros((H, W), dtype=torch.uint8, device=device)
     total = torch.zeros((), dtype=torch.float64, device=device)
     dtype = getattr(model, "compute_dtype", torch.float32)
     model.eval()
-    with torch.no_grad():
-        for i in range(0, len(rc), int(batch_size)):
-            x = T.gather_tiles(img, ti[i:i + batch_size], rc[i:i + batch_size], ph, dtype)
-            model.setmode("segment")
-            K.stitch_logits(mask, model(x).float().contiguous(), rc[i:i + batch_size], 1)
-            model.setmode("image")
-            total += _rounded_counts(model, x).sum(dtype=torch.float64)
+    if blended is None:
+        mask = torch.zeros((H, W), dtype=torch.uint8, device=device)
+        with torch.no_grad():
+            for i in range(0, len(rc), int(batch_size)):
+                x = T.gather_tiles(img, ti[i:i + batch_size], rc[i:i + batch_size], ph, dtype)
+                model.setmode("segment")
+                K.stitch_logits(mask, model(x).float().contiguous(), rc[i:i + batch_size], 1)
+                model.setmode("image")
+                total += _rounded_counts(model, x).sum(dtype=torch.float64)
+    else:
+        mask = _blended_loop(model, img, ti, rc, ph, int(batch_size), dtype, total, *blended)
     model.setmode("segment")
     count = int(total.item())                                              # the first synchronisation of the slide's loop
     points, discarded = D._detect(mask[None], count if reg_limit else None, opts).per_image()[0]
@@ -289,11 +364,12 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     return result
 
 
-def detect_slides(slides, model, device=None, **kwargs):
-    """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order.  ``kwargs`` are
-    ``detect_slide``'s, ``tissue=`` and ``stain=`` among them."""
+def detect_slides(slides, model, device=None, blend=None, tta=None, **kwargs):
+    """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order.  ``blend`` and ``tta``
+    (blended overlaps, flip test-time augmentation) and the ``kwargs`` are ``detect_slide``'s, ``tissue=`` and ``stain=`` among
+    them."""
     for image_u8 in slides:
-        yield detect_slide(image_u8, model, device, **kwargs)
+        yield detect_slide(image_u8, model, device, blend=blend, tta=tta, **kwargs)
 
 
 def render_slide(image_u8, result, fill="mask", thr_u8=127, outlines=None, **compose):

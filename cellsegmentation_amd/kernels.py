@@ -1138,6 +1138,28 @@ def stitch_logits(mask, logits, corners, ch=1):
     return mask
 
 
+def stitch_blend_add(num, den, logits, corners, taps_r, taps_c, flips=None, ch=1):
+    """logits fp32 [B,C,ph,pw], corners int32 [B,2], flips uint8 [B] or None, taps int32 [ph] / [pw] (all device) -> num int64 [H,W]
+    += w q and den int32 [H,W] += w in place, for every patch that covers a pixel (csrc/detect.hip); one launch, no workspace, no
+    synchronisation."""
+    _f32(logits)
+    B, C, ph, pw = logits.shape
+    H, W = num.shape
+    if B:
+        _lib.check(_lib.load().cs_stitch_blend_add(_p(logits), B, C, ph, pw, int(ch), _p(corners), _p(flips), _p(taps_r), _p(taps_c), H, W,
+                                                   _p(num), _p(den), _stream()), "stitch_blend_add")
+    return num, den
+
+
+def stitch_blend_finish(num, den, out=None):
+    """num int64 [H,W], den int32 [H,W] -> uint8 [H,W] = den ? num // (256 den) : 0 (into ``out`` when given); one launch."""
+    H, W = num.shape
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=num.device)
+    _lib.check(_lib.load().cs_stitch_blend_finish(_p(num), _p(den), H, W, _p(out), _stream()), "stitch_blend_finish")
+    return out
+
+
 def detect_grid_size(H, W, interval, window):
     return _lib.load().cs_detect_grid_size(int(H), int(W), int(interval), int(window))
 

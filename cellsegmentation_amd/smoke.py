@@ -59,9 +59,25 @@ def run():
                                 torch.from_numpy(kpt).to(dev), torch.tensor([0, 32, 64], device=dev), 32)
     got = out[: int(cnt.item())].cpu().numpy().tolist()
     assert got == orc.sample_indices(pr, groups, lab, 1, 10).tolist()
+    # blended stitch: two overlapping 8x8 patches, the second given flipped horizontally with its code, against the integer formula
+    from cellsegmentation_amd import detect as D
+    logits = torch.randn((2, 2, 8, 8), generator=torch.Generator().manual_seed(4))
+    corners = [(0, 0), (3, 5)]
+    got = D.stitch_blend(logits.to(dev), corners, (12, 14), flips=[0, 1]).cpu()
+    p = K.softmax_channel_fwd(logits.to(dev), 1).cpu()
+    q = (256.0 * (255.0 * p).clamp(0, 255)).to(torch.int64)
+    q[1] = q[1].flip(-1)                                                    # back to where its pixels lie on the slide
+    t = torch.from_numpy(D.blend_taps(8).astype(np.int64))
+    w = t[:, None] * t[None, :]
+    num, den = torch.zeros((12, 14), dtype=torch.int64), torch.zeros((12, 14), dtype=torch.int64)
+    for b, (r, c) in enumerate(corners):
+        num[r:r + 8, c:c + 8] += w * q[b]
+        den[r:r + 8, c:c + 8] += w
+    want = torch.where(den > 0, num // (256 * den.clamp(min=1)), 0).to(torch.uint8)
+    assert torch.equal(got, want) and int(got[3:8, 5:8].max()) > 0, "blended stitch differs from the integer formula"
     # bf16 throughput mode runs
     m.set_compute_dtype(torch.bfloat16)
     with torch.no_grad():
         m(x.to(dev))
     torch.cuda.synchronize()
-    print(f"smoke ok: loss rel err {e_loss:.2e}, prob abs err {e_prob:.2e}, conv1 grad rel err {e_grad:.2e}, top-k exact")
+    print(f"smoke ok: loss rel err {e_loss:.2e}, prob abs err {e_prob:.2e}, conv1 grad rel err {e_grad:.2e}, top-k exact, blend exact")

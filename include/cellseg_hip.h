@@ -543,6 +543,19 @@ int cs_prune_excess(const int32_t* labels, long long n, int flag, long long n_ex
  *                      patch of the call covers keep their value; parts of a patch outside the mask are clipped.  Calls are
  *                      ordered by the stream only: every call for one mask must go to the same stream.  Batches of a zeroed mask
  *                      in index order give cs_stitch_patches of all patches, for any split.  H, W < 2^29.
+ * cs_stitch_blend_add: overlaps blended instead of overwritten.  Per patch pixel q = (uint32)(256 clamp(255 p, 0, 255)) with p the fp32
+ *                      softmax channel ch of cs_softmax_channel_fwd (q >> 8 is the byte of cs_detect_quantize; a NaN gives 0) and
+ *                      w = taps_r[i] * taps_c[j] (device int32 [ph], [pw], values 1..255; (i, j) = the pixel's position inside the
+ *                      patch on the slide); num[H][W] (int64) += w q and den[H][W] (int32) += w, in place, for the B patches
+ *                      logits[B][C][ph][pw] at corners[b] = (row, col) (device int32 [B][2]).  flips (device uint8 [B], or NULL for
+ *                      none): 1 horizontal, 2 vertical, 3 both -- logits[b] are those of the flipped tile, so slide position
+ *                      (i, j) reads logit pixel (code & 2 ? ph-1-i : i, code & 1 ? pw-1-j : j).  One launch, no workspace, no
+ *                      atomics: the lowest b covering a pixel sums every covering patch of the call in registers and updates
+ *                      the pixel once; corners and (corner, flip) pairs may repeat.  Integer sums: any split into calls and any
+ *                      patch order give the same accumulators.  Calls are ordered by the stream only.  num and den 16-byte
+ *                      aligned, H, W < 2^29, B <= 32768; the caller keeps the total of w per pixel below 2^31.
+ * cs_stitch_blend_finish: mask[i] = den[i] ? floor(num[i] / (256 den[i])) : 0 (uint8 [H][W]); a pixel covered once holds the byte
+ *                      cs_stitch_logits writes.  Reads the accumulators only: more cs_stitch_blend_add calls may follow.
  * cs_detect_grid_size: number G of windows of get_tiles((H, W), interval, window) (-1 when the window does not fit).
  * cs_detect_meanshift: per map n, the grid windows whose blurred centre is above thr255 (fp64 compare), in grid order, each run
  *                      through cv2.meanShift (TermCriteria(EPS, 0, 1e-5): max_iter steps, stopping early at a fixed point);
@@ -570,6 +583,9 @@ int cs_stitch_patches(const uint8_t* patches, int M, int ph, int pw, const int32
                       void* workspace, size_t workspace_bytes, void* stream);
 int cs_stitch_logits(const float* logits, int B, int C, int ph, int pw, int ch, const int32_t* corners, int H, int W, uint8_t* mask,
                      void* stream);
+int cs_stitch_blend_add(const float* logits, int B, int C, int ph, int pw, int ch, const int32_t* corners, const uint8_t* flips,
+                        const int32_t* taps_r, const int32_t* taps_c, int H, int W, int64_t* num, int32_t* den, void* stream);
+int cs_stitch_blend_finish(const int64_t* num, const int32_t* den, int H, int W, uint8_t* mask, void* stream);
 int cs_detect_grid_size(int H, int W, int interval, int window);
 int cs_detect_meanshift(const uint8_t* blurred, int N, int H, int W, int interval, int window, double thr255, int max_iter,
                         int32_t* pts, int32_t* n_pts, void* stream);

@@ -5,7 +5,9 @@ exact distance transform, or both on the same maps in one run (the blur is then 
 form is also timed on its worst case, a 4096^2 map that is all foreground but one pixel (smoothing kernels alone).
 
 The 4096^2 grid is also stitched from segment logits: detect.stitch_logits batch by batch next to softmax_channel_fwd + quantize +
-stitch_patches on the same logits, with the peak device memory either takes (--stitch-only runs nothing else).
+stitch_patches on the same logits, with the peak device memory either takes (--stitch-only runs nothing else), and blended
+(detect.StitchBlend, batches of 16, with and without the four flip views of test-time augmentation) next to the streamed stitch and
+to the two forward passes that detect_slide runs per batch.
 
     python tools/detect_microbench.py [--method both] [--reps 5] [--host-maps 128] [--stitch-only] [--json PATH]
 """
@@ -171,7 +173,69 @@ def main():
                                  "streamed_peak_bytes": peak_rise(streamed), "resident_peak_bytes": peak_rise(resident),
                                  "logit_bytes": logits.numel() * 4, "mask_bytes": H * W, "equal_to_resident": same}
     print(json.dumps({"stitch_logits_4096": res["stitch_logits_4096"]}), flush=True)
-    del logits
+    # ---- the same grid and logits BLENDED (detect.StitchBlend: zeroed accumulators, one add per batch of 16, one finish), without
+    # and with the four flip views of test-time augmentation (the views are the flipped logits, so the mask must not change)
+    views = {0: logits, 1: logits.flip(-1).contiguous(), 2: logits.flip(-2).contiguous(), 3: logits.flip(-2, -1).contiguous()}
+    codes = {c: torch.full((16,), c, dtype=torch.uint8, device=dev) for c in views}
+
+    def blended(tta=(0,)):
+        sb = D.StitchBlend((H, W), (299, 299), device=dev)
+        for i in range(0, len(grid), 16):
+            for c in tta:
+                sb.add(views[c][i:i + 16], rc[i:i + 16], codes[c][:len(rc[i:i + 16])], 1)
+        return sb.finish()
+
+    def blended_tta():
+        return blended((0, 1, 2, 3))
+    plain, mask_b = streamed().cpu().numpy(), blended().cpu().numpy()
+    cover = np.zeros((H, W), np.int32)
+    for r, c in grid:
+        cover[r:r + 299, c:c + 299] += 1
+    same = bool(np.array_equal(mask_b[cover == 1], plain[cover == 1])) and bool(np.array_equal(blended_tta().cpu().numpy(), mask_b))
+    rounds = {name: time_dev(fn, args.reps) for name, fn in (("streamed", streamed), ("blended", blended), ("tta", blended_tta))}
+    again = {name: time_dev(fn, args.reps) for name, fn in (("tta", blended_tta), ("blended", blended), ("streamed", streamed))}
+    sb = D.StitchBlend((H, W), (299, 299), device=dev).add(logits[:16], rc[:16])
+    # the yardstick of the loop: what detect_slide runs per batch of 16 next to one stitch call (ResNet-18, its default compute
+    # dtype: gather_tiles, the segment forward, the image forward for the count)
+    from cellsegmentation_amd import synth, tiles
+    from cellsegmentation_amd.model import resnet as RN
+    model = RN.MILresnet18()
+    sd = model.state_dict()
+    synth.fill_state_dict(sd)
+    model.load_state_dict(sd)
+    model = model.to(dev).eval()
+    slide = torch.randint(0, 256, (1, H, W, 3), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(4))
+    ti = torch.zeros((16,), dtype=torch.int32, device=dev)
+
+    def forwards():
+        with torch.no_grad():
+            x = tiles.gather_tiles(slide, ti, rc[:16], 299, model.compute_dtype)
+            model.setmode("segment")
+            out = model(x).float().contiguous()
+            model.setmode("image")
+            return out, model(x)[1]
+    forward_ms = time_dev(forwards, args.reps)[0]
+    del model, slide
+    px =len(grid) * 299 * 299                                             # patch pixels of one view
+    res["stitch_blend_4096"] = {"patches": len(grid), "batch": 16, "adds": (len(grid) + 15) // 16, "adds_tta": 4 * ((len(grid) + 15) // 16),
+                                "streamed_ms": min(rounds["streamed"][0], again["streamed"][0]),
+                                "blended_ms": min(rounds["blended"][0], again["blended"][0]),
+                                "blended_tta_ms": min(rounds["tta"][0], again["tta"][0]),
+                                "blended_ms_all": rounds["blended"][1] + again["blended"][1],
+                                "blended_tta_ms_all": rounds["tta"][1] + again["tta"][1],
+                                "finish_ms": time_dev(sb.finish, args.reps)[0],
+                                "forwards_ms_per_batch": forward_ms, "batches": (len(grid) + 15) // 16,
+                                "blended_peak_bytes": peak_rise(blended), "blended_tta_peak_bytes": peak_rise(blended_tta),
+                                "streamed_peak_bytes": peak_rise(streamed),
+                                "accumulator_bytes": 12 * H * W,
+                                # zeroing; per patch pixel 12 accumulator bytes read, 12 written and 8 logit bytes; finish 12 + 1
+                                "bytes_moved_blended": 12 * H * W + px * (24 + 8) + 13 * H * W,
+                                "bytes_moved_tta": 12 * H * W + 4 * px * (24 + 8) + 13 * H * W,
+                                "bytes_moved_streamed": H * W + px * (1 + 8),
+                                "single_cover_fraction": float((cover == 1).mean()),
+                                "equal_to_resident": same}
+    print(json.dumps({"stitch_blend_4096": res["stitch_blend_4096"]}), flush=True)
+    del logits, views
     if "distancetransform" in methods:
         # ---- the distance form's worst case: every pixel's row search runs to the one background pixel's column
         worst = torch.full((1, H, W), 255, dtype=torch.uint8, device=dev)
