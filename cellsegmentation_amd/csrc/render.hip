@@ -6,11 +6,8 @@
 //            that no edge map is ever stored.  The image is read once and written once.  The batch is one flat run of N H W pixels
 //            (only the outline rule needs rows and columns).  The unit of work is 4 pixels = 12 bytes = three dwords: the fills are
 //            byte-parallel dword arithmetic on those three words, the per-pixel operands (mask flag, table colour, outline colour)
-//            being spread over them by pack4.  A thread takes kRun = 16 consecutive pixels = 48 bytes as three 16-byte loads from the
-//            first pixel boundary of the images that is also a 16-byte boundary (one exists within the first 16 pixels: 3 is
-//            invertible mod 16), so no alignment is asked of anything: the fewer than 16 pixels before it and after the last whole
-//            run go one by one through the same arithmetic in the first workgroup, and the loads of the map and the stores pick
-//            16-byte, dword or byte accesses by the address they meet, uniformly over the launch.  The outline of a run reads its
+//            being spread over them by pack4.  The pixels are walked by cs_pixels.h, a run of 16 being four units; the single pixels
+//            on either side go through the same arithmetic, and no alignment is asked of anything.  The outline of a run reads its
 //            own 16 labels and the 16 above and below once each (the neighbours left and right are its own), with one division
 //            per run; a first version that asked label by label -- a division and four loads per labelled pixel, in divergent
 //            code -- ran at 18 times the copy.  The colour table and the palette sit in LDS as packed words.  The grid is capped and
@@ -19,12 +16,11 @@
 //            of a launch carries the same colour, so marks that overlap do not depend on the order of arrival.
 #include <limits.h>
 #include "cs_common.h"
+#include "cs_pixels.h"
 
 namespace {
 
 constexpr int kThreads = 256;                      // also the rows of the colour table: thread v stages entry v
-constexpr int kRun = 16;                           // pixels per thread and step: four units of 4 pixels
-constexpr int kMaxBlocks = 2048;
 constexpr int kMaxRadius = 64;
 
 struct ComposeArgs {
@@ -106,8 +102,8 @@ __device__ __forceinline__ void outline4(uint32_t* w, const ComposeArgs& a, uint
     for (int d = 0; d < 3; ++d) w[d] = C[d] | (w[d] & ~M[d]);
 }
 
-// the ids max(label, 0) of the kRun pixels at q; vec: q is 16-byte aligned
-__device__ __forceinline__ void ids16(const int32_t* q, bool vec, int (&v)[kRun]) {
+// the ids max(label, 0) of the kPixelRun pixels at q; vec: q is 16-byte aligned
+__device__ __forceinline__ void ids16(const int32_t* q, bool vec, int (&v)[kPixelRun]) {
     if (vec) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -116,42 +112,42 @@ __device__ __forceinline__ void ids16(const int32_t* q, bool vec, int (&v)[kRun]
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < kRun; ++i) v[i] = max(q[i], 0);
+        for (int i = 0; i < kPixelRun; ++i) v[i] = max(q[i], 0);
     }
 }
 
-// the outline over the kRun pixels from p on, in the dwords w[0..11]: the rule of edge_id with the run's own labels and the runs
+// the outline over the kPixelRun pixels from p on, in the dwords w[0..11]: the rule of edge_id with the run's own labels and the runs
 // above and below it loaded once -- as vectors where they are aligned (vec_c: this run; vec_ud: W is a multiple of 4 as well) --
 // and one division for the run, the row and column stepping from pixel to pixel.  A run may cross rows and images.
 __device__ __forceinline__ void outline16(uint32_t* w, const ComposeArgs& a, long long p, bool vec_c, bool vec_ud, const uint32_t* s_pal) {
-    int ctr[kRun], up[kRun], dn[kRun];
+    int ctr[kPixelRun], up[kPixelRun], dn[kPixelRun];
     ids16(a.lab + p, vec_c, ctr);
     int any = 0;
 #pragma unroll
-    for (int i = 0; i < kRun; ++i) any |= ctr[i];
+    for (int i = 0; i < kPixelRun; ++i) any |= ctr[i];
     if (!any) return;                              // background only, as most of a slide is: no neighbour is looked at
     if (p >= a.W) {                             // the whole run above lies in the buffer (a first row's is not used)
         ids16(a.lab + p - a.W, vec_ud, up);
     } else {
 #pragma unroll
-        for (int i = 0; i < kRun; ++i) up[i] = p + i >= a.W ? max(a.lab[p + i - a.W], 0) : 0;
+        for (int i = 0; i < kPixelRun; ++i) up[i] = p + i >= a.W ? max(a.lab[p + i - a.W], 0) : 0;
     }
-    if (p + a.W + kRun <= a.T) {
+    if (p + a.W + kPixelRun <= a.T) {
         ids16(a.lab + p + a.W, vec_ud, dn);
     } else {
 #pragma unroll
-        for (int i = 0; i < kRun; ++i) dn[i] = p + i + a.W < a.T ? max(a.lab[p + i + a.W], 0) : 0;
+        for (int i = 0; i < kPixelRun; ++i) dn[i] = p + i + a.W < a.T ? max(a.lab[p + i + a.W], 0) : 0;
     }
     const uint32_t q = (uint32_t)p / (uint32_t)a.W;
     int c = (int)((uint32_t)p - q * (uint32_t)a.W), r = (int)(q % (uint32_t)a.H);
     const int before = c > 0 ? max(a.lab[p - 1], 0) : 0;
-    uint32_t e[kRun], col[kRun];
+    uint32_t e[kPixelRun], col[kPixelRun];
 #pragma unroll
-    for (int i = 0; i < kRun; ++i) {
+    for (int i = 0; i < kPixelRun; ++i) {
         const int l = ctr[i];
         const int left = c == 0 ? 0 : i ? ctr[i ? i - 1 : 0] : before;
         int right = 0;
-        if (c + 1 < a.W) right = i + 1 < kRun ? ctr[i + 1 < kRun ? i + 1 : i] : max(a.lab[p + kRun], 0);      // the same row: inside the buffer
+        if (c + 1 < a.W) right = i + 1 < kPixelRun ? ctr[i + 1 < kPixelRun ? i + 1 : i] : max(a.lab[p + kPixelRun], 0);      // the same row: inside the buffer
         const int above = r > 0 ? up[i] : 0, below = r + 1 < a.H ? dn[i] : 0;
         const bool edge = l > 0 && (left != l || right != l || above != l || below != l);
         e[i] = edge ? 0xffffffu : 0u;
@@ -180,13 +176,13 @@ __device__ __forceinline__ uint32_t fill_at(const ComposeArgs& a, long long p) {
     return static_cast<const uint8_t*>(a.fill)[p];
 }
 
-// the fill operands of the kRun pixels from p on; align: what the address of the first divides, uniform over the launch
+// the fill operands of the kPixelRun pixels from p on; width: the access_width of the map's first run
 template <int FILL>
-__device__ __forceinline__ void fill16(const ComposeArgs& a, long long p, int align, uint32_t (&f)[kRun]) {
+__device__ __forceinline__ void fill16(const ComposeArgs& a, long long p, int width, uint32_t (&f)[kPixelRun]) {
     if (FILL == CS_RENDER_FILL_NONE) return;
     if (FILL == CS_RENDER_FILL_HEAT_F32) {
         const float* q = static_cast<const float*>(a.fill) + p;
-        if (align == 16) {
+        if (width == 16) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float4 v = reinterpret_cast<const float4*>(q)[j];
@@ -195,31 +191,14 @@ __device__ __forceinline__ void fill16(const ComposeArgs& a, long long p, int al
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < kRun; ++i) f[i] = heat_level(q[i], a.thr);
+            for (int i = 0; i < kPixelRun; ++i) f[i] = heat_level(q[i], a.thr);
         }
         return;
     }
-    const uint8_t* q = static_cast<const uint8_t*>(a.fill) + p;
-    if (align == 1) {
-#pragma unroll
-        for (int i = 0; i < kRun; ++i) f[i] = q[i];
-        return;
-    }
     uint32_t m[4];
-    if (align == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(q);
-        m[0] = v.x, m[1] = v.y, m[2] = v.z, m[3] = v.w;
-    } else {
+    load_bytes16(static_cast<const uint8_t*>(a.fill) + p, width, m);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) m[j] = reinterpret_cast<const uint32_t*>(q)[j];
-    }
-#pragma unroll
-    for (int i = 0; i < kRun; ++i) f[i] = (m[i >> 2] >> (8 * (i & 3))) & 255u;
-}
-
-__device__ __forceinline__ int align_of(const void* p) {
-    const uintptr_t at = reinterpret_cast<uintptr_t>(p);
-    return (at & 15) == 0 ? 16 : (at & 3) == 0 ? 4 : 1;
+    for (int i = 0; i < kPixelRun; ++i) f[i] = byte_of(m, i);
 }
 
 // pixel p alone, through the arithmetic of a unit whose other three pixels are not stored
@@ -233,8 +212,7 @@ __device__ __forceinline__ void compose_one(const ComposeArgs& a, long long p, c
     q[0] = (uint8_t)w[0], q[1] = (uint8_t)(w[0] >> 8), q[2] = (uint8_t)(w[0] >> 16);
 }
 
-// grid (capped): the batch as [0, head) single pixels, `runs` runs of kRun pixels from the 16-byte boundary of the images at pixel
-// `head` on, [tail_at, T) single pixels
+// grid (capped): the batch as one span of T pixels
 template <int FILL>
 __global__ __launch_bounds__(kThreads) void render_compose_kernel(const ComposeArgs a) {
     __shared__ uint32_t s_cmap[256], s_pal[256];
@@ -242,40 +220,24 @@ __global__ __launch_bounds__(kThreads) void render_compose_kernel(const ComposeA
     if (FILL == CS_RENDER_FILL_HEAT_U8 || FILL == CS_RENDER_FILL_HEAT_F32) s_cmap[tid] = rgb_at(a.cmap + 3 * tid);
     if (tid < a.pal_rows) s_pal[tid] = rgb_at(a.pal + 3 * tid);
     __syncthreads();
-    // the smallest k with (img + 3 k) % 16 == 0: 3 * 11 = 33 = 1 (mod 16), so k = 11 * (-img) (mod 16)
-    const long long k = (11 * ((16 - (int)(reinterpret_cast<uintptr_t>(a.img) & 15)) & 15)) & 15;
-    const long long head = k < a.T ? k : a.T, runs = (a.T - head) / kRun, tail_at = head + runs * kRun;
-    const int out_align = align_of(a.out + 3 * head);
-    const bool lab_vec = a.lab && align_of(a.lab + head) == 16;
-    const int fill_align = FILL == CS_RENDER_FILL_NONE           ? 1
-                           : FILL == CS_RENDER_FILL_HEAT_F32     ? align_of(static_cast<const float*>(a.fill) + head)
-                                                                 : align_of(static_cast<const uint8_t*>(a.fill) + head);
-    for (long long g = (long long)blockIdx.x * kThreads + tid; g < runs; g += (long long)gridDim.x * kThreads) {
-        const long long p = head + kRun * g;
-        const uint4* src = reinterpret_cast<const uint4*>(a.img + 3 * p);
-        const uint4 x = src[0], y = src[1], z = src[2];
-        uint32_t w[12] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y, z.z, z.w};
-        uint32_t f[kRun];
-        fill16<FILL>(a, p, fill_align, f);
+    const PixelSpan s = pixel_span(a.img, a.T);
+    const int out_width = access_width(a.out + 3 * s.head);
+    const bool lab_vec = a.lab && access_width(a.lab + s.head) == 16;
+    const int fill_width = FILL == CS_RENDER_FILL_NONE           ? 1
+                           : FILL == CS_RENDER_FILL_HEAT_F32     ? access_width(static_cast<const float*>(a.fill) + s.head)
+                                                                 : access_width(static_cast<const uint8_t*>(a.fill) + s.head);
+    for_pixels<kThreads>(
+        s,
+        [&](long long g, uint32_t(&w)[12]) {
+            const long long p = s.head + kPixelRun * g;
+            uint32_t f[kPixelRun];
+            fill16<FILL>(a, p, fill_width, f);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) shade4<FILL>(w + 3 * j, f + 4 * j, a, s_cmap);
-        if (a.lab) outline16(w, a, p, lab_vec, lab_vec && (a.W & 3) == 0, s_pal);
-        uint8_t* q = a.out + 3 * p;
-        if (out_align == 16) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) reinterpret_cast<uint4*>(q)[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-        } else if (out_align == 4) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) reinterpret_cast<uint32_t*>(q)[j] = w[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 48; ++j) q[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-        }
-    }
-    if (blockIdx.x == 0) {                         // fewer than kRun pixels on either side
-        if (tid < head) compose_one<FILL>(a, tid, s_cmap, s_pal);
-        if (tid < a.T - tail_at) compose_one<FILL>(a, tail_at + tid, s_cmap, s_pal);
-    }
+            for (int j = 0; j < 4; ++j) shade4<FILL>(w + 3 * j, f + 4 * j, a, s_cmap);
+            if (a.lab) outline16(w, a, p, lab_vec, lab_vec && (a.W & 3) == 0, s_pal);
+            store_words(a.out + 3 * p, out_width, w);
+        },
+        [&](long long p) { compose_one<FILL>(a, p, s_cmap, s_pal); });
 }
 
 struct PointArgs {
@@ -327,13 +289,9 @@ __global__ __launch_bounds__(kThreads) void render_points_kernel(const PointArgs
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-bool sizes_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31); }
-
 template <int FILL>
 void launch_compose(const ComposeArgs& a, hipStream_t st) {
-    const long long want = (a.T / kRun + kThreads - 1) / kThreads;
-    const unsigned blocks = (unsigned)(want < 1 ? 1 : want < kMaxBlocks ? want : kMaxBlocks);
-    hipLaunchKernelGGL(render_compose_kernel<FILL>, dim3(blocks), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(render_compose_kernel<FILL>, pixel_grid(1, a.T, kThreads), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace
@@ -341,7 +299,7 @@ void launch_compose(const ComposeArgs& a, hipStream_t st) {
 extern "C" int cs_render_compose(const uint8_t* images_hwc, int N, int H, int W, int fill, const void* fill_map, float threshold, int invert,
                                  const uint8_t* colormap, const int32_t* labels, int outline_rgb, const uint8_t* palette, int palette_rows,
                                  uint8_t* out, void* stream) {
-    CS_CHECK_ARG(sizes_ok(N, H, W), "render_compose: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(pixel_batch_ok(N, H, W), "render_compose: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
     CS_CHECK_ARG(fill >= CS_RENDER_FILL_NONE && fill <= CS_RENDER_FILL_HEAT_F32, "render_compose: unknown fill");
     CS_CHECK_ARG(images_hwc && out, "render_compose: NULL argument");
     CS_CHECK_ARG((fill == CS_RENDER_FILL_NONE) == (fill_map == nullptr), "render_compose: a fill needs its map, no fill takes none");
@@ -351,8 +309,7 @@ extern "C" int cs_render_compose(const uint8_t* images_hwc, int N, int H, int W,
                  "render_compose: need a palette of 1 to 256 rows, or none and 0 rows");
     CS_CHECK_ARG(labels || !palette, "render_compose: a palette needs the labels");
     CS_CHECK_ARG(outline_rgb >= 0 && outline_rgb < (1 << 24), "render_compose: outline_rgb is r | g << 8 | b << 16");
-    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 3) == 0 &&
-                 (fill != CS_RENDER_FILL_HEAT_F32 || (reinterpret_cast<uintptr_t>(fill_map) & 3) == 0), "render_compose: misaligned argument");
+    CS_CHECK_ARG(aligned(labels, 4) && (fill != CS_RENDER_FILL_HEAT_F32 || aligned(fill_map, 4)), "render_compose: misaligned argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const ComposeArgs a{images_hwc, out, fill_map, colormap, labels, palette, (long long)N * H * W, H, W, invert != 0, palette_rows,
                         threshold, (uint32_t)outline_rgb};
@@ -366,7 +323,7 @@ extern "C" int cs_render_compose(const uint8_t* images_hwc, int N, int H, int W,
 
 extern "C" int cs_render_points(uint8_t* canvas_hwc, int N, int H, int W, const int64_t* pts, const int64_t* off, const int32_t* limit,
                                 long long P, int radius, int thickness, int rgb, int flags, void* stream) {
-    CS_CHECK_ARG(sizes_ok(N, H, W), "render_points: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(pixel_batch_ok(N, H, W), "render_points: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
     CS_CHECK_ARG(P >= 0 && P < (1LL << 31), "render_points: need 0 <= P < 2^31 rows");
     CS_CHECK_ARG(radius >= 0 && radius <= kMaxRadius, "render_points: need 0 <= radius <= 64");
     CS_CHECK_ARG(thickness < 0 || (thickness >= 1 && thickness <= 2 * radius), "render_points: need thickness < 0 or 1 <= thickness <= 2 radius");
@@ -374,8 +331,7 @@ extern "C" int cs_render_points(uint8_t* canvas_hwc, int N, int H, int W, const 
     CS_CHECK_ARG(flags >= 0 && flags <= (CS_RENDER_POINTS_XY | CS_RENDER_POINTS_TAIL), "render_points: unknown flags");
     CS_CHECK_ARG(limit || !(flags & CS_RENDER_POINTS_TAIL), "render_points: the tail needs the limits");
     CS_CHECK_ARG(canvas_hwc && off && (pts || P == 0), "render_points: NULL argument");
-    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(pts) & 7) == 0 && (reinterpret_cast<uintptr_t>(off) & 7) == 0 &&
-                 (reinterpret_cast<uintptr_t>(limit) & 3) == 0, "render_points: misaligned argument");
+    CS_CHECK_ARG(aligned(pts, 8) && aligned(off, 8) && aligned(limit, 4), "render_points: misaligned argument");
     if (P == 0) return CS_OK;
     const PointArgs a{canvas_hwc, pts, off, limit, P, N, H, W, radius, thickness, flags & CS_RENDER_POINTS_XY ? 1 : 0,
                       flags & CS_RENDER_POINTS_TAIL ? 1 : 0, (uint32_t)rgb};

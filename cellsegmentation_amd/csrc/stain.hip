@@ -6,92 +6,29 @@
 //              LDS, and ten 64-bit integer atomics per workgroup reach memory.  The bits do not depend on the launch geometry.
 //   angle_hist int64 [B] per image: kept pixels by the angle of their projection on a plane, phi = atan2f(od.V1, od.V0).
 //   conc_hist  int64 [2][Bc] per image: kept pixels by each of two concentrations c = P od.
-//              Both keep sub-histograms in LDS (lane & (copies - 1) picks the copy, a stride of bins + 1 words spreads one bin of
-//              the copies over the banks) and flush the non-zero sums with 64-bit integer atomics, as tissue.hip does.
+//              Both count into the sub-histograms of cs_pixels.h, as many copies as kMaxBins words of LDS hold.
 //   apply      uint8 RGB out = clamp(rint(Io exp(-(A od))), 0, 255) for every pixel, as exp2(log2 Io - (A od) log2 e) with log2 Io
 //              from the host and log2 e folded into A: one v_exp_f32 per channel.  Its error stays below 10^-3 levels.
 //   separate   c = P od for every pixel, K = 2 or 3 stains, as fp32 or as uint8 clamp(rint(255 c / conc_max), 0, 255).
 // The optical density is a table of 256 integers made once on the host, od_q[v] = rint(4096 ln(Io / (v + 1))), kept in LDS; the
 // float od is od_q / 4096, exact in fp32, and no kernel calls log.  A pixel is KEPT when none of its three od_q is below beta_q
 // and, with a mask, its mask byte is non-zero.
-// The pixel loader is tissue.hip's: 16 pixels = 48 bytes per thread and step as three 16-byte loads from the first pixel boundary
-// that is also a 16-byte boundary (one exists within the first 16 pixels of any image), the fewer than 16 pixels on either side
-// taken singly by the image's first workgroup; nothing is asked of the alignment of the images, the mask or the outputs.  Outputs
-// and the mask move as 16-byte words where their address allows, as dwords or bytes where it does not.
+// The pixels are walked by cs_pixels.h (runs of 16 pixels as three 16-byte loads, single pixels on either side), which also keeps the
+// sub-histograms of the two histogram kernels; nothing is asked of the alignment of the images, the mask or the outputs.
 #include <cmath>
 
 #include "cs_common.h"
+#include "cs_pixels.h"
 
 namespace {
 
 constexpr int kThreads = 256;                      // also the entries of the od table: thread v loads entry v
-constexpr int kRun = 16;                           // pixels per thread and step
-constexpr int kMaxBlocks = 2048;                   // of one pixel pass, all images together (an image has at least one)
 constexpr int kMaxBins = 8192;                     // histogram words of one copy in LDS: B, or 2 Bc
 constexpr int kMaxCopies = 16;
 constexpr int kMoments = 10;
 constexpr float kOdUnit = 1.0f / 4096.0f;
 constexpr float kHalfPi = 1.57079632679489661923f;
 constexpr float kLog2e = 1.44269504088896340736f;
-
-// image n as [0, head) single pixels, `runs` runs of kRun pixels from the 16-byte boundary at pixel `head` on, [tail_at, HW) singles
-struct Span {
-    const uint8_t* px;
-    long long head, runs, tail_at, HW;
-};
-__device__ __forceinline__ Span image_span(const uint8_t* __restrict__ images, int n, long long HW) {
-    Span s;
-    s.px = images + (long long)n * HW * 3;
-    s.HW = HW;
-    // the smallest k with (px + 3 k) % 16 == 0: 3 * 11 = 33 = 1 (mod 16), so k = 11 * (-px) (mod 16)
-    const long long k = (11 * ((16 - (int)(reinterpret_cast<uintptr_t>(s.px) & 15)) & 15)) & 15;
-    s.head = k < HW ? k : HW;
-    s.runs = (HW - s.head) / kRun;
-    s.tail_at = s.head + s.runs * kRun;
-    return s;
-}
-
-// the widest access every run of an image allows when its first run starts at p: 16, 4 or 1 bytes (uniform over the image)
-__device__ __forceinline__ int access_width(const void* p) {
-    const uintptr_t at = reinterpret_cast<uintptr_t>(p);
-    return (at & 15) == 0 ? 16 : (at & 3) == 0 ? 4 : 1;
-}
-// byte o of a run of words
-template <int NW>
-__device__ __forceinline__ int byte_of(const uint32_t (&w)[NW], int o) { return (w[o >> 2] >> (8 * (o & 3))) & 255; }
-
-// the 16 pixels in the 48 bytes at p (16-byte aligned)
-__device__ __forceinline__ void load_pixels(const uint8_t* __restrict__ p, uint32_t (&w)[12]) {
-    const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1], c = reinterpret_cast<const uint4*>(p)[2];
-    w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w, w[8] = c.x, w[9] = c.y, w[10] = c.z, w[11] = c.w;
-}
-// the 16 mask bytes at q
-__device__ __forceinline__ void load_mask(const uint8_t* __restrict__ q, int width, uint32_t (&w)[4]) {
-    if (width == 16) {
-        const uint4 a = *reinterpret_cast<const uint4*>(q);
-        w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w;
-    } else if (width == 4) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = reinterpret_cast<const uint32_t*>(q)[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = q[4 * j] | (uint32_t)q[4 * j + 1] << 8 | (uint32_t)q[4 * j + 2] << 16 | (uint32_t)q[4 * j + 3] << 24;
-    }
-}
-// NW words (a multiple of 4) to q
-template <int NW>
-__device__ __forceinline__ void store_words(uint8_t* __restrict__ q, int width, const uint32_t (&w)[NW]) {
-    if (width == 16) {
-#pragma unroll
-        for (int j = 0; j < NW / 4; ++j) reinterpret_cast<uint4*>(q)[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-    } else if (width == 4) {
-#pragma unroll
-        for (int j = 0; j < NW; ++j) reinterpret_cast<uint32_t*>(q)[j] = w[j];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4 * NW; ++i) q[i] = (uint8_t)byte_of(w, i);
-    }
-}
 
 // a row of a 3-column matrix times the float optical density of a pixel, in this order everywhere
 __device__ __forceinline__ float dot3(const float* __restrict__ a, float r, float g, float b) { return fmaf(b, a[2], fmaf(g, a[1], r * a[0])); }
@@ -100,46 +37,30 @@ __device__ __forceinline__ uint32_t level(float v) { return (uint32_t)fminf(fmax
 // floor(x) as a bin of `bins`, clamped: NaN becomes bin 0
 __device__ __forceinline__ int bin_of(float x, int bins) { return (int)fminf(fmaxf(floorf(x), 0.0f), (float)(bins - 1)); }
 
-// Walks the pixels of image blockIdx.y: run(g, w) for the runs of this thread, with the 12 words loaded; single(i) for the pixels
-// before the first and after the last run, which the image's first workgroup takes, a pixel per thread.
-template <typename Run, typename Single>
-__device__ __forceinline__ void for_pixels(const Span& s, Run run, Single single) {
-    for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < s.runs; g += (long long)gridDim.x * kThreads) {
-        uint32_t w[12];
-        load_pixels(s.px + 3 * (s.head + kRun * g), w);
-        run(g, w);
-    }
-    if (blockIdx.x == 0) {
-        const long long t = threadIdx.x;
-        if (t < s.head) single(t);
-        if (t < s.HW - s.tail_at) single(s.tail_at + t);
-    }
-}
-
 // The kept pixels of the image: keep(qr, qg, qb) for each, with its three quantised optical densities.  `flush(i)` follows pixel
-// i of a run (and every single pixel, as i = kRun - 1), kept or not.
+// i of a run (and every single pixel, as i = kPixelRun - 1), kept or not.
 template <typename Keep, typename Flush>
-__device__ __forceinline__ void for_kept_pixels(const Span& s, const int32_t* __restrict__ od, int beta_q, const uint8_t* __restrict__ mask,
+__device__ __forceinline__ void for_kept_pixels(const PixelSpan& s, const int32_t* __restrict__ od, int beta_q, const uint8_t* __restrict__ mask,
                                                 Keep keep, Flush flush) {
     const int width = mask ? access_width(mask + s.head) : 0;
     auto take = [&](int r, int g, int b, bool on) {
         const int qr = od[r], qg = od[g], qb = od[b];
         if (on && min(qr, min(qg, qb)) >= beta_q) keep(qr, qg, qb);
     };
-    for_pixels(
+    for_pixels<kThreads>(
         s,
         [&](long long g, const uint32_t(&w)[12]) {
             uint32_t m[4] = {~0u, ~0u, ~0u, ~0u};
-            if (mask) load_mask(mask + s.head + kRun * g, width, m);
+            if (mask) load_bytes16(mask + s.head + kPixelRun * g, width, m);
 #pragma unroll
-            for (int i = 0; i < kRun; ++i) {
+            for (int i = 0; i < kPixelRun; ++i) {
                 take(byte_of(w, 3 * i), byte_of(w, 3 * i + 1), byte_of(w, 3 * i + 2), byte_of(m, i) != 0);
                 flush(i);
             }
         },
         [&](long long i) {
             take(s.px[3 * i], s.px[3 * i + 1], s.px[3 * i + 2], !mask || mask[i] != 0);
-            flush(kRun - 1);
+            flush(kPixelRun - 1);
         });
 }
 
@@ -152,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void stain_moments_kernel(const uint8_t* 
     const int n = blockIdx.y, tid = threadIdx.x;
     s_od[tid] = od_q[tid];
     __syncthreads();
-    const Span s = image_span(images, n, HW);
+    const PixelSpan s = pixel_span(images + (long long)n * HW * 3, HW);
     unsigned long long acc[kMoments] = {};
     uint32_t lin[4] = {}, quad[6] = {};             // of the pixels since the last flush: at most 16 and 8 of them
     for_kept_pixels(
@@ -167,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void stain_moments_kernel(const uint8_t* 
 #pragma unroll
                 for (int k = 0; k < 6; ++k) acc[4 + k] += quad[k], quad[k] = 0;
             }
-            if (i == kRun - 1) {
+            if (i == kPixelRun - 1) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[k] += lin[k], lin[k] = 0;
             }
@@ -199,16 +120,16 @@ __global__ __launch_bounds__(kThreads) void stain_hist_kernel(const uint8_t* __r
     const int n = blockIdx.y, tid = threadIdx.x;
     const int TB = CONC ? 2 * bins : bins, stride = TB + 1;
     s_od[tid] = od_q[tid];
-    for (int i = tid; i < copies * stride; i += kThreads) s_hist[i] = 0;
+    hist_zero<kThreads>(s_hist, copies, stride);
     __syncthreads();
-    uint32_t* mine = s_hist + (tid & (copies - 1)) * stride;
+    uint32_t* mine = hist_mine(s_hist, copies, stride);
     float a0[3], a1[3];                            // the two rows that meet the od of a pixel
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         a0[j] = M[6 * n + (CONC ? j : 2 * j)];
         a1[j] = M[6 * n + (CONC ? 3 + j : 2 * j + 1)];
     }
-    const Span s = image_span(images, n, HW);
+    const PixelSpan s = pixel_span(images + (long long)n * HW * 3, HW);
     for_kept_pixels(
         s, s_od, beta_q, mask ? mask + (long long)n * HW : nullptr,
         [&](int qr, int qg, int qb) {
@@ -222,12 +143,7 @@ __global__ __launch_bounds__(kThreads) void stain_hist_kernel(const uint8_t* __r
             }
         },
         [](int) {});
-    __syncthreads();
-    for (int b = tid; b < TB; b += kThreads) {
-        uint32_t sum = 0;                          // the workgroup's pixels: below 2^31
-        for (int c = 0; c < copies; ++c) sum += s_hist[c * stride + b];
-        if (sum) atomicAdd(hist + (long long)n * TB + b, (unsigned long long)sum);
-    }
+    hist_flush<kThreads>(s_hist, copies, stride, hist + (long long)n * TB);
 }
 
 // grid (blocks per image, N)
@@ -240,24 +156,24 @@ __global__ __launch_bounds__(kThreads) void stain_apply_kernel(const uint8_t* __
     float a[9];                                    // Io exp(-x) = exp2(log2 Io - x log2 e): one v_exp_f32 per channel, no multiply by Io
 #pragma unroll
     for (int j = 0; j < 9; ++j) a[j] = -kLog2e * A[9 * n + j];
-    const Span s = image_span(images, n, HW);
+    const PixelSpan s = pixel_span(images + (long long)n * HW * 3, HW);
     uint8_t* o = out + (long long)n * HW * 3;
     const int width = access_width(o + 3 * s.head);
     auto pixel = [&](int r8, int g8, int b8, int c) {
         const float* row = a + 3 * c;
         return level(__builtin_amdgcn_exp2f(fmaf(s_od[b8], row[2], fmaf(s_od[g8], row[1], fmaf(s_od[r8], row[0], lg_Io)))));
     };
-    for_pixels(
+    for_pixels<kThreads>(
         s,
         [&](long long g, const uint32_t(&w)[12]) {
             uint32_t v[12] = {};
 #pragma unroll
-            for (int i = 0; i < kRun; ++i) {
+            for (int i = 0; i < kPixelRun; ++i) {
                 const int r8 = byte_of(w, 3 * i), g8 = byte_of(w, 3 * i + 1), b8 = byte_of(w, 3 * i + 2);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) v[(3 * i + c) >> 2] |= pixel(r8, g8, b8, c) << (8 * ((3 * i + c) & 3));
             }
-            store_words(o + 3 * (s.head + kRun * g), width, v);
+            store_words(o + 3 * (s.head + kPixelRun * g), width, v);
         },
         [&](long long i) {
             const int r8 = s.px[3 * i], g8 = s.px[3 * i + 1], b8 = s.px[3 * i + 2];
@@ -277,19 +193,19 @@ __global__ __launch_bounds__(kThreads) void stain_separate_kernel(const uint8_t*
     float p[3 * K];
 #pragma unroll
     for (int j = 0; j < 3 * K; ++j) p[j] = P[3 * K * n + j];
-    const Span s = image_span(images, n, HW);
+    const PixelSpan s = pixel_span(images + (long long)n * HW * 3, HW);
     constexpr int kItem = U8 ? 1 : 4;              // bytes per value
     uint8_t* o = static_cast<uint8_t*>(out) + (long long)n * HW * K * kItem;
     const int width = access_width(o + (long long)K * kItem * s.head);
     auto conc = [&](int r8, int g8, int b8, int k) {
         return dot3(p + 3 * k, s_od[r8], s_od[g8], s_od[b8]);
     };
-    for_pixels(
+    for_pixels<kThreads>(
         s,
         [&](long long g, const uint32_t(&w)[12]) {
-            uint32_t v[kRun * K * kItem / 4] = {};
+            uint32_t v[kPixelRun * K * kItem / 4] = {};
 #pragma unroll
-            for (int i = 0; i < kRun; ++i) {
+            for (int i = 0; i < kPixelRun; ++i) {
                 const int r8 = byte_of(w, 3 * i), g8 = byte_of(w, 3 * i + 1), b8 = byte_of(w, 3 * i + 2);
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
@@ -298,7 +214,7 @@ __global__ __launch_bounds__(kThreads) void stain_separate_kernel(const uint8_t*
                     else v[K * i + k] = __float_as_uint(c);
                 }
             }
-            store_words(o + (long long)K * kItem * (s.head + kRun * g), width, v);
+            store_words(o + (long long)K * kItem * (s.head + kPixelRun * g), width, v);
         },
         [&](long long i) {
             const int r8 = s.px[3 * i], g8 = s.px[3 * i + 1], b8 = s.px[3 * i + 2];
@@ -312,13 +228,6 @@ __global__ __launch_bounds__(kThreads) void stain_separate_kernel(const uint8_t*
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-bool images_ok(int N, int H, int W) { return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)H * W < (1LL << 31); }
-bool aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-dim3 pixel_grid(int N, long long HW) {
-    const long long want = (HW / kRun + kThreads - 1) / kThreads, cap = kMaxBlocks / N;
-    const long long per = want < cap ? want : cap;
-    return dim3((unsigned)(per > 1 ? per : 1), (unsigned)N);
-}
 // the sub-histograms of a workgroup with TB bins each: a power of two, as many as kMaxBins words hold
 int hist_copies(int TB) {
     int c = 1;
@@ -331,7 +240,7 @@ int launch_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* o
                 float scale, int64_t* hist, void* stream) {
     const int TB = CONC ? 2 * bins : bins, copies = hist_copies(TB);
     const long long HW = (long long)H * W;
-    hipLaunchKernelGGL(stain_hist_kernel<CONC>, pixel_grid(N, HW), dim3(kThreads), (size_t)copies * (TB + 1) * sizeof(uint32_t),
+    hipLaunchKernelGGL(stain_hist_kernel<CONC>, pixel_grid(N, HW, kThreads), dim3(kThreads), (size_t)copies * (TB + 1) * sizeof(uint32_t),
                        reinterpret_cast<hipStream_t>(stream), images_hwc, HW, od_q, beta_q, mask, M, bins, copies, scale,
                        reinterpret_cast<unsigned long long*>(hist));
     CS_LAUNCH_CHECK();
@@ -342,11 +251,11 @@ int launch_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* o
 
 extern "C" int cs_stain_moments(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask,
                                 int64_t* moments, void* stream) {
-    CS_CHECK_ARG(images_ok(N, H, W), "stain_moments: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
+    CS_CHECK_ARG(pixel_images_ok(N, H, W), "stain_moments: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
     CS_CHECK_ARG(images_hwc && od_q && moments, "stain_moments: NULL argument");
     CS_CHECK_ARG(aligned(od_q, 4) && aligned(moments, 8), "stain_moments: misaligned argument");
     const long long HW = (long long)H * W;
-    hipLaunchKernelGGL(stain_moments_kernel, pixel_grid(N, HW), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), images_hwc, HW, od_q,
+    hipLaunchKernelGGL(stain_moments_kernel, pixel_grid(N, HW, kThreads), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), images_hwc, HW, od_q,
                        beta_q, mask, reinterpret_cast<unsigned long long*>(moments));
     CS_LAUNCH_CHECK();
     return CS_OK;
@@ -354,7 +263,7 @@ extern "C" int cs_stain_moments(const uint8_t* images_hwc, int N, int H, int W, 
 
 extern "C" int cs_stain_angle_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask,
                                    const float* V, int bins, int64_t* hist, void* stream) {
-    CS_CHECK_ARG(images_ok(N, H, W), "stain_angle_hist: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
+    CS_CHECK_ARG(pixel_images_ok(N, H, W), "stain_angle_hist: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
     CS_CHECK_ARG(bins > 0 && bins <= kMaxBins, "stain_angle_hist: need 0 < bins <= 8192");
     CS_CHECK_ARG(images_hwc && od_q && V && hist, "stain_angle_hist: NULL argument");
     CS_CHECK_ARG(aligned(od_q, 4) && aligned(V, 4) && aligned(hist, 8), "stain_angle_hist: misaligned argument");
@@ -363,7 +272,7 @@ extern "C" int cs_stain_angle_hist(const uint8_t* images_hwc, int N, int H, int 
 
 extern "C" int cs_stain_conc_hist(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, int beta_q, const uint8_t* mask,
                                   const float* P, int bins, float conc_max, int64_t* hist, void* stream) {
-    CS_CHECK_ARG(images_ok(N, H, W), "stain_conc_hist: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
+    CS_CHECK_ARG(pixel_images_ok(N, H, W), "stain_conc_hist: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
     CS_CHECK_ARG(bins > 0 && 2 * bins <= kMaxBins, "stain_conc_hist: need 0 < bins <= 4096");
     CS_CHECK_ARG(conc_max > 0 && conc_max <= 3.0e38f, "stain_conc_hist: conc_max must be positive and finite");
     CS_CHECK_ARG(images_hwc && od_q && P && hist, "stain_conc_hist: NULL argument");
@@ -373,12 +282,12 @@ extern "C" int cs_stain_conc_hist(const uint8_t* images_hwc, int N, int H, int W
 
 extern "C" int cs_stain_apply(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, const float* A, float Io, uint8_t* out,
                               void* stream) {
-    CS_CHECK_ARG(images_ok(N, H, W), "stain_apply: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
+    CS_CHECK_ARG(pixel_images_ok(N, H, W), "stain_apply: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
     CS_CHECK_ARG(Io > 0 && Io <= 256.0f, "stain_apply: need 0 < Io <= 256");
     CS_CHECK_ARG(images_hwc && od_q && A && out, "stain_apply: NULL argument");
     CS_CHECK_ARG(aligned(od_q, 4) && aligned(A, 4), "stain_apply: misaligned argument");
     const long long HW = (long long)H * W;
-    hipLaunchKernelGGL(stain_apply_kernel, pixel_grid(N, HW), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), images_hwc, HW, od_q, A,
+    hipLaunchKernelGGL(stain_apply_kernel, pixel_grid(N, HW, kThreads), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), images_hwc, HW, od_q, A,
                        (float)std::log2((double)Io), out);
     CS_LAUNCH_CHECK();
     return CS_OK;
@@ -386,7 +295,7 @@ extern "C" int cs_stain_apply(const uint8_t* images_hwc, int N, int H, int W, co
 
 extern "C" int cs_stain_separate(const uint8_t* images_hwc, int N, int H, int W, const int32_t* od_q, const float* P, int K, int as_u8,
                                  float conc_max, void* out, void* stream) {
-    CS_CHECK_ARG(images_ok(N, H, W), "stain_separate: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
+    CS_CHECK_ARG(pixel_images_ok(N, H, W), "stain_separate: need 0 < N <= 65535 images of 0 < H W < 2^31 pixels");
     CS_CHECK_ARG(K == 2 || K == 3, "stain_separate: need K = 2 or 3 stains");
     CS_CHECK_ARG(as_u8 == 0 || as_u8 == 1, "stain_separate: as_u8 is 0 (fp32 out) or 1 (uint8 out)");
     CS_CHECK_ARG(!as_u8 || (conc_max > 0 && conc_max <= 3.0e38f), "stain_separate: conc_max must be positive and finite");
@@ -394,7 +303,7 @@ extern "C" int cs_stain_separate(const uint8_t* images_hwc, int N, int H, int W,
     CS_CHECK_ARG(aligned(od_q, 4) && aligned(P, 4) && (as_u8 || aligned(out, 4)), "stain_separate: misaligned argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long HW = (long long)H * W;
-    const dim3 grid = pixel_grid(N, HW);
+    const dim3 grid = pixel_grid(N, HW, kThreads);
     const float scale = as_u8 ? (float)(255.0 / conc_max) : 0.0f;
     if (K == 2 && as_u8) hipLaunchKernelGGL((stain_separate_kernel<2, true>), grid, dim3(kThreads), 0, st, images_hwc, HW, od_q, P, scale, out);
     else if (K == 2) hipLaunchKernelGGL((stain_separate_kernel<2, false>), grid, dim3(kThreads), 0, st, images_hwc, HW, od_q, P, scale, out);

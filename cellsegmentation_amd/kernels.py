@@ -1859,19 +1859,22 @@ def spatial_bin_counts(pts, off, H, W, bin, limits=None, out=None):
 CS_TISSUE_CHROMA, CS_TISSUE_DARKNESS = 0, 1
 
 
-def _tissue_images(what, images_u8):
+def _rgb_images(what, images_u8, name="images", whole_batch=False):
+    """the check of every pass over uint8 RGB images (csrc/cs_pixels.h) -> (N, H, W); ``whole_batch``: the pass walks the batch as
+    one run of pixels, so all of them together stay below 2^31"""
     if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise TypeError(f"{what}: images must be a uint8 tensor shaped [N, H, W, 3]")
+        raise TypeError(f"{what}: {name} must be a uint8 tensor shaped [N, H, W, 3]")
     N, H, W, _ = images_u8.shape
-    if not 1 <= N <= 65535 or H < 1 or W < 1 or H * W >= 1 << 31:
-        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images of 0 < H W < 2^31 pixels, got {(N, H, W)}")
+    if not 1 <= N <= 65535 or H < 1 or W < 1 or (N if whole_batch else 1) * H * W >= 1 << 31:
+        limit = "with N H W < 2^31" if whole_batch else "of 0 < H W < 2^31"
+        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images {limit} pixels, got {(N, H, W)}")
     return N, H, W
 
 
 def tissue_histogram(images_u8, channel=CS_TISSUE_CHROMA, hist=None):
     """images uint8 [N,H,W,3] (device) -> int64 [N,256] on the device: the pixels of every image per value of the feature
     ``channel``.  ``hist``: an int64 [N,256] device tensor to ADD into instead of a zeroed one (cs_tissue_histogram)."""
-    N, H, W = _tissue_images("tissue_histogram", images_u8)
+    N, H, W = _rgb_images("tissue_histogram", images_u8)
     if hist is None:
         hist = torch.zeros((N, 256), dtype=torch.int64, device=images_u8.device)
     elif not torch.is_tensor(hist) or hist.dtype != torch.int64 or tuple(hist.shape) != (N, 256):
@@ -1882,7 +1885,7 @@ def tissue_histogram(images_u8, channel=CS_TISSUE_CHROMA, hist=None):
 
 def tissue_mask(images_u8, thr, channel=CS_TISSUE_CHROMA, out=None):
     """images uint8 [N,H,W,3], thr int32 [N] (both on the device) -> uint8 [N,H,W]: feature > thr[n] as 0 / 1 (cs_tissue_mask)"""
-    N, H, W = _tissue_images("tissue_mask", images_u8)
+    N, H, W = _rgb_images("tissue_mask", images_u8)
     if not torch.is_tensor(thr) or thr.dtype != torch.int32 or tuple(thr.shape) != (N,):
         raise ValueError(f"tissue_mask: thr must be an int32 tensor shaped {(N,)}")
     out = _regions_outputs("tissue_mask", {"out": ((N, H, W), torch.uint8)}, {"out": out}, images_u8.device)["out"]
@@ -1921,7 +1924,7 @@ def tissue_select(cover, min_pixels):
 # ---------------------------------------------------------------- stain separation and normalisation (csrc/stain.hip; stain.py is the public API)
 def _stain_args(what, images_u8, od_q, mask=None, **mats):
     """the checks every stain wrapper shares; ``mats``: name -> (fp32 device tensor, its shape after N)"""
-    N, H, W = _tissue_images(what, images_u8)
+    N, H, W = _rgb_images(what, images_u8)
     if not torch.is_tensor(od_q) or od_q.dtype != torch.int32 or tuple(od_q.shape) != (256,):
         raise ValueError(f"{what}: od_q must be an int32 tensor shaped (256,) (stain.od_table)")
     if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W)):
@@ -2001,15 +2004,6 @@ CS_RENDER_POINTS_XY, CS_RENDER_POINTS_TAIL = 1, 2
 RENDER_MAX_RADIUS = 64
 
 
-def _render_images(what, images_u8, name="images"):
-    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise TypeError(f"{what}: {name} must be a uint8 tensor shaped [N, H, W, 3]")
-    N, H, W, _ = images_u8.shape
-    if not 1 <= N <= 65535 or H < 1 or W < 1 or N * H * W >= 1 << 31:
-        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images with N H W < 2^31 pixels, got {(N, H, W)}")
-    return N, H, W
-
-
 def _render_rgb(what, name, rgb):
     """three integers in [0, 255] -> r | g << 8 | b << 16"""
     try:
@@ -2027,7 +2021,7 @@ def render_compose(images_u8, fill=CS_RENDER_FILL_NONE, fill_map=None, threshold
     """images uint8 [N,H,W,3] -> uint8 [N,H,W,3], one launch: the fill ``fill`` from ``fill_map`` (uint8 [N,H,W]; fp32 for
     CS_RENDER_FILL_HEAT_F32, with ``threshold``) through ``colormap`` uint8 [256,3], then the outline of ``labels`` int32 [N,H,W] in
     ``outline_color`` or ``palette`` uint8 [P,3]; ``out`` may be the images (cs_render_compose in include/cellseg_hip.h)"""
-    N, H, W = _render_images("render_compose", images_u8)
+    N, H, W = _rgb_images("render_compose", images_u8, whole_batch=True)
     if fill not in (CS_RENDER_FILL_NONE, CS_RENDER_FILL_MASK, CS_RENDER_FILL_HEAT_U8, CS_RENDER_FILL_HEAT_F32):
         raise ValueError(f"render_compose: unknown fill {fill!r}")
     if (fill == CS_RENDER_FILL_NONE) != (fill_map is None):
@@ -2065,7 +2059,7 @@ def render_points(canvas_u8, pts, off, limits=None, radius=4, color=(255, 0, 0),
     """draws into canvas uint8 [N,H,W,3] in place and returns it: pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None
     (the triple of spatial_bin_counts), every kept row -- with ``tail`` every row that limits does not keep -- as a disc of
     ``radius`` (thickness < 0) or a ring of that thickness (cs_render_points in include/cellseg_hip.h)"""
-    N, H, W = _render_images("render_points", canvas_u8, "canvas")
+    N, H, W = _rgb_images("render_points", canvas_u8, "canvas", whole_batch=True)
     radius, thickness = int(radius), int(thickness)
     if not 0 <= radius <= RENDER_MAX_RADIUS:
         raise ValueError(f"render_points: radius must be in [0, {RENDER_MAX_RADIUS}], got {radius}")

@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import render_ref as R  # noqa: E402
+from shifted import guards_intact as _guards_intact, shifted  # noqa: E402
 from cellsegmentation_amd import detect as D  # noqa: E402
 from cellsegmentation_amd import inference, regions, render  # noqa: E402
 
@@ -22,28 +23,11 @@ COMPOSE = [str(n) for n in GOLD["compose_names"]]
 POINTS = [str(n) for n in GOLD["points_names"]]
 SHIFTS = ((1, 0), (7, 4), (12, 3), (0, 9),            # (inputs, output) bytes past a 16-byte boundary: byte loads and stores
           (0, 4), (4, 8))                             # and the dword paths of the map and of the output
-GUARD = 0xA5
 
 
 def _shifted(a, shift, dev, fill=None):
-    """the array on the device, its first byte `shift` bytes past a 16-byte boundary (4-byte types: the next multiple of 4), inside a
-    buffer of GUARD bytes -> (the view, the buffer, the view's byte range in it); fill: a constant instead of the array's values"""
-    item = a.dtype.itemsize
-    shift = shift if item == 1 else 4 * (shift % 4)
-    flat = torch.full((a.nbytes + 64,), GUARD, dtype=torch.uint8, device=dev)
-    lead = (-flat.data_ptr()) % 16 + 16 + shift
-    view = flat[lead:lead + a.nbytes].view(torch.from_numpy(a[:0].copy()).dtype).view(a.shape)
-    if fill is None:
-        view.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-    else:
-        view.fill_(fill)
-    assert view.data_ptr() % 16 == shift % 16 and view.is_contiguous()
-    return view, flat, (lead, lead + a.nbytes)
-
-
-def _guards_intact(flat, span):
-    f = flat.cpu().numpy()
-    return (f[:span[0]] == GUARD).all() and (f[span[1]:] == GUARD).all()
+    """shifted(), with the shift of a 4-byte type taken as words: 4 (shift % 4) bytes"""
+    return shifted(a, shift if a.dtype.itemsize == 1 else 4 * (shift % 4), dev, fill)
 
 
 def _package_kwargs(kw):

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import stain_ref as R  # noqa: E402
 import tissue_ref as TR  # noqa: E402
+from shifted import shifted  # noqa: E402
 from cellsegmentation_amd import detect as D  # noqa: E402
 from cellsegmentation_amd import kernels as K  # noqa: E402
 from cellsegmentation_amd import stain, tiles, tissue  # noqa: E402
@@ -48,16 +49,8 @@ def _f32(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 
 
-def _shifted(a, shift, dev, align=16):
-    """the array on the device, its first byte `shift` bytes past a 16-byte boundary"""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    nbytes = t.numel() * t.element_size()
-    flat = torch.zeros((nbytes + 48,), dtype=torch.uint8, device=dev)
-    lead = (-flat.data_ptr()) % 16 + shift
-    view = flat[lead:lead + nbytes].view(t.dtype).view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == shift % 16 and view.is_contiguous()
-    return view
+def _shifted(a, shift, dev):
+    return shifted(a, shift, dev)[0]
 
 
 def _mask_for(shape, seed):
