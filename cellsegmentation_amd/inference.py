@@ -199,13 +199,16 @@ class SlideResult:
     (``discarded`` is ``[]`` without a cap), ``cell_count`` the summed per-patch counts, ``mask`` the stitched uint8 [H, W] device
     tensor, ``tissue`` the ``tissue.TissueResult`` of a run with ``tissue=`` (None without).  ``stain``: the slide's own
     ``stain.StainEstimate`` of a run with ``stain=`` (None without); an attribute that ``detect_slide`` sets, not an argument of
-    the constructor, so that the record's positional fields stay the five they were."""
+    the constructor, so that the record's positional fields stay the five they were.  ``roi``: the device uint8 [H, W] mask of 0 / 1
+    of a run with ``roi=`` (None without), an attribute set the same way; with ``tissue=`` as well, ``tissue.mask`` is the tissue mask
+    cut to the ROI and ``tissue.coverage`` counts that."""
     points: np.ndarray
     discarded: object
     cell_count: int
     mask: torch.Tensor
     tissue: object = None
     stain = None
+    roi = None
 
 
 def _check_blend(blend, tta, ph, pw):
@@ -265,7 +268,7 @@ def _blended_loop(model, img, ti, rc, size, batch_size, dtype, total, taps, code
 
 
 def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, interval=None, eps=11, reg_limit=True,
-                 method="gaussianblur", thr_for_dt=10, tissue=None, stain=None, blend=None, tta=None, **blur):
+                 method="gaussianblur", thr_for_dt=10, tissue=None, stain=None, blend=None, tta=None, roi=None, **blur):
     """The loop of ``cell_detect`` (test_seg.py:182-316) for one slide or ROI, streamed on the device -> SlideResult.
 
     image_u8: uint8 [H, W, 3], numpy or torch; it is moved to the device once.  ``tiles.sample_patches`` gives the (row, col) patch
@@ -307,6 +310,16 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     the un-flipped view only, so the count and the cap it puts on the points do not depend on ``tta``.  Both compose with
     ``tissue`` and ``stain`` unchanged; pixels that no kept patch covers are 0.
 
+    ``roi`` (the reference's QuPath flow crops the region on the host): None, the default, reaches none of it.  A
+    ``polygons.PolygonSet`` of one image, a GeoJSON object (read by ``polygons.from_geojson`` with its defaults) or a uint8 / bool
+    [H, W] mask (non-zero = inside) restricts the run to the region a pathologist drew.  The ROI becomes a device mask once
+    (``polygons.rasterize``); the patches with at least one ROI pixel under them are kept, in the order of ``sample_patches``
+    (``tissue_coverage`` and ``tissue_select``, one small synchronisation); with ``tissue`` as well the tissue mask is ANDed with
+    the ROI before the windows are counted.  After the loop the stitched mask is zeroed outside the ROI, so no point lies outside
+    it; inside it every patch that covers a pixel has run, in the same order, so the mask there is the mask of the run without
+    ``roi``.  ``cell_count`` sums the kept patches whole and therefore over-counts at the ROI's border, where a patch reaches
+    beyond it.  ``SlideResult.roi`` holds the mask.  It composes with ``stain``, ``blend`` and ``tta`` unchanged.
+
     Not done here: reading ``.svs`` / ``.png`` files (OpenSlide is not a dependency), writing the CSV and PNG files, and the
     ``name-<xoffset>`` file-name convention -- the caller adds the offset to ``points[:, 1]``.  ``meanshift_cluster(...,
     "distancetransform")`` keeps raising ``NotImplementedError``; method="distancetransform" here goes through ``detect._detect``."""
@@ -330,15 +343,24 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
         raise TypeError("detect_slide expects a uint8 image shaped [H, W, 3] (numpy or torch)")
     H, W = int(img.shape[0]), int(img.shape[1])
     corners = np.asarray(T.sample_patches((H, W), (ph, pw), interval), dtype=np.int32).reshape(-1, 2)
+    if roi is not None:                                                    # checked here, made on the device below
+        from . import polygons as Pg
+        roi = Pg.roi_mask(roi, (H, W))
     if device is None:
         device = _device(img)
     img = img.to(device).contiguous()[None]
     rc = torch.from_numpy(corners).to(device)                              # every corner of the slide, uploaded once
     ti = torch.zeros((len(corners),), dtype=torch.int32, device=device)
     kept = None
+    if roi is not None:
+        roi = roi(device)
     if tissue is not None:                                                 # the patches that hold tissue, in the order of the grid
-        kept = Ts._select(img, corners, ti, rc, ph, pw, tissue)
+        kept = Ts._select(img, corners, ti, rc, ph, pw, tissue, roi)
         rc, ti = rc.index_select(0, kept.selected.long()), ti[:kept.n_selected]
+    elif roi is not None:                                                  # the patches over at least one pixel of the ROI
+        selected, n_selected = K.tissue_select(K.tissue_coverage(roi[None], ti, rc, ph, pw), 1)
+        n = int(n_selected.item())
+        rc, ti = rc.index_select(0, selected[:n].long()), ti[:n]
     source = None
     if stain is not None:                                                  # the loop reads the normalised copy from here on
         img, source = St._normalize_slide(img, None if kept is None else kept.mask[None], *stain)
@@ -357,19 +379,22 @@ def detect_slide(image_u8, model, device=None, batch_size=16, patch_size=299, in
     else:
         mask = _blended_loop(model, img, ti, rc, ph, int(batch_size), dtype, total, *blended)
     model.setmode("segment")
+    if roi is not None:
+        mask *= roi                                                        # 0 / 1: nothing is left outside the ROI
     count = int(total.item())                                              # the first synchronisation of the slide's loop
     points, discarded = D._detect(mask[None], count if reg_limit else None, opts).per_image()[0]
     result = SlideResult(points, discarded, count, mask, kept)
     result.stain = source
+    result.roi = roi
     return result
 
 
-def detect_slides(slides, model, device=None, blend=None, tta=None, **kwargs):
+def detect_slides(slides, model, device=None, blend=None, tta=None, roi=None, **kwargs):
     """``detect_slide`` for every image of an iterable -> a generator of SlideResult, one per slide, in order.  ``blend`` and ``tta``
-    (blended overlaps, flip test-time augmentation) and the ``kwargs`` are ``detect_slide``'s, ``tissue=`` and ``stain=`` among
-    them."""
+    (blended overlaps, flip test-time augmentation), ``roi`` (one region for every slide) and the ``kwargs`` are ``detect_slide``'s,
+    ``tissue=`` and ``stain=`` among them."""
     for image_u8 in slides:
-        yield detect_slide(image_u8, model, device, blend=blend, tta=tta, **kwargs)
+        yield detect_slide(image_u8, model, device, blend=blend, tta=tta, roi=roi, **kwargs)
 
 
 def render_slide(image_u8, result, fill="mask", thr_u8=127, outlines=None, **compose):

@@ -2083,6 +2083,55 @@ def render_points(canvas_u8, pts, off, limits=None, radius=4, color=(255, 0, 0),
     return canvas_u8
 
 
+# ---------------------------------------------------------------- polygons to pixels (csrc/polygons.hip; polygons.py is the public API)
+CS_POLYGON_EVENODD, CS_POLYGON_NONZERO = 0, 1
+CS_POLYGON_LABELS, CS_POLYGON_MASK = 0, 1
+POLYGON_MAX_SUB = 8
+POLYGON_MAX_COORD = 1 << 28           # of a quantised vertex coordinate, either sign
+
+
+def polygons_check_size(what, N, H, W, sub):
+    """the sizes cs_polygons_rasterize takes, checked without the library"""
+    if isinstance(sub, bool) or not isinstance(sub, int) or not 0 <= sub <= POLYGON_MAX_SUB:
+        raise ValueError(f"{what}: sub must be an integer in [0, {POLYGON_MAX_SUB}], got {sub!r}")
+    if not 1 <= N <= 65535 or H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError(f"{what}: a call takes 0 < N <= 65535 images of 0 < H W < 2^31 pixels, got {(N, H, W)}")
+    if max(H, W) << (sub + 1) >= 1 << 30:
+        raise ValueError(f"{what}: max(H, W) << (sub + 1) must stay below 2^30, got {(H, W)} at sub={sub}")
+
+
+def polygons_rasterize(vertices, ring_start, ring_count, shape_rings, image_shapes, out, sub, rule=CS_POLYGON_EVENODD, items=None):
+    """paints into ``out`` (int32 [N,H,W]: labels by maximum; uint8 [N,H,W]: 1 where covered) and returns it.  vertices int32 [V,2],
+    ring_start / ring_count int32 [R], shape_rings int32 [S+1], image_shapes int32 [N+1], items int32 [I,3] | None, all on the device
+    of ``out``; pixels that no shape takes are not written (cs_polygons_rasterize in include/cellseg_hip.h)."""
+    if not torch.is_tensor(out) or out.dim() != 3 or out.dtype not in (torch.int32, torch.uint8):
+        raise TypeError("polygons_rasterize: out must be an int32 (labels) or uint8 (mask) tensor shaped [N, H, W]")
+    N, H, W = (int(v) for v in out.shape)
+    polygons_check_size("polygons_rasterize", N, H, W, sub)
+    if rule not in (CS_POLYGON_EVENODD, CS_POLYGON_NONZERO):
+        raise ValueError(f"polygons_rasterize: unknown rule {rule!r}")
+    tabs = {"vertices": vertices, "ring_start": ring_start, "ring_count": ring_count, "shape_rings": shape_rings,
+            "image_shapes": image_shapes}
+    if items is not None:
+        tabs["items"] = items
+    for name, t in tabs.items():
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise TypeError(f"polygons_rasterize: {name} must be an int32 tensor")
+    V, R, S = int(vertices.numel()) // 2, int(ring_start.numel()), int(shape_rings.numel()) - 1
+    I = 0 if items is None else int(items.numel()) // 3
+    if (vertices.numel() % 2 or int(ring_count.numel()) != R or S < 0 or int(image_shapes.numel()) != N + 1
+            or (items is not None and items.numel() % 3)):
+        raise ValueError("polygons_rasterize: vertices [V,2], ring_start and ring_count [R], shape_rings [S+1], image_shapes [N+1], "
+                         f"items [I,3]; got {[tuple(t.shape) for t in tabs.values()]} for {N} images")
+    if items is not None and I == 0:
+        return out
+    mode = CS_POLYGON_LABELS if out.dtype == torch.int32 else CS_POLYGON_MASK
+    _lib.check(_lib.load().cs_polygons_rasterize(_p(vertices) if V else None, V, _p(ring_start) if R else None, _p(ring_count) if R else None,
+                                                 R, _p(shape_rings), S, _p(image_shapes), _p(items), I, N, H, W, sub, rule, mode, _p(out),
+                                                 _stream()), "polygons_rasterize")
+    return out
+
+
 # ---------------------------------------------------------------- augmented input staging (csrc/augment.hip; augment.py is the public API)
 def stage_augmented_workspace(n_tiles, device):
     """the caller-owned scratch of one cs_stage_augmented call whose records hold a contrast op"""

@@ -239,9 +239,10 @@ def _check_options(options, what):
     return options
 
 
-def _select(dev_image, corners, tile_img, tile_rc, ph, pw, options):
+def _select(dev_image, corners, tile_img, tile_rc, ph, pw, options, roi=None):
     """the device half of ``select_patches``: dev_image uint8 [1, H, W, 3]; corners int32 [T, 2] on the host, tile_img / tile_rc the
-    same table on the device"""
+    same table on the device; ``roi``: None, or a device uint8 [H, W] mask of 0 / 1 that the cleaned tissue mask is ANDed with
+    before the windows are counted (``detect_slide(roi=...)``)"""
     m, thr = _mask(dev_image, CHANNELS[options.channel], None if options.threshold is None else [int(options.threshold)])
     if options.opening_radius or options.min_object_size or options.hole_area_threshold:
         from . import morph as M
@@ -250,6 +251,8 @@ def _select(dev_image, corners, tile_img, tile_rc, ph, pw, options):
         if options.opening_radius:
             fg = M.binary_opening(fg, options.opening_radius, border_value=0)
         m = Rg.remove_small_regions(fg, options.min_object_size, options.hole_area_threshold, out=fg).view(torch.uint8)
+    if roi is not None:
+        m = m & roi[None]
     need = options.pixels(ph, pw)
     cover = K.tissue_coverage(m, tile_img, tile_rc, ph, pw)
     selected, n_selected = K.tissue_select(cover, need)

@@ -1030,6 +1030,40 @@ int cs_render_compose(const uint8_t* images_hwc, int N, int H, int W, int fill, 
 int cs_render_points(uint8_t* canvas_hwc, int N, int H, int W, const int64_t* pts, const int64_t* off, const int32_t* limit, long long P,
                      int radius, int thickness, int rgb, int flags, void* stream);
 
+/* ---- polygons to pixels: label images and masks from vertex rings (csrc/polygons.hip) -----------------------------------------
+ * The inverse of cs_regions_contour_labels, for any closed rings.  All arrays are DEVICE arrays, all arithmetic is integer.
+ * Vertices are fixed-point: vertices int32 [V][2] = (row, col) in units of 1 / S pixel, S = 2^sub, 0 <= sub <= 8; sub = 0 is the
+ * lattice of cs_regions_contour_labels.  Pixel (i, j) is the closed unit square with the corners (i, j) and (i + 1, j + 1); its
+ * centre decides.  In units of 1 / (2 S) the centre is Y = (2 i + 1) S, X = (2 j + 1) S and a vertex (R, C) is y = 2 R, x = 2 C.
+ * For every edge a -> b of every ring of a shape, the closing edge last -> first included, let d = yb - ya and
+ * cross = (xb - xa)(Y - ya) - (X - xa) d in 64-bit integers.  The edge COUNTS for the pixel when (ya <= Y) != (yb <= Y) and
+ * (d > 0 and cross <= 0, or d < 0 and cross >= 0): the ray from the centre towards smaller columns.  A counting edge weighs +1 if
+ * d > 0, else -1; the winding number of the pixel is the sum over all rings of the shape.  rule CS_POLYGON_EVENODD takes the pixel
+ * when the winding number is odd, CS_POLYGON_NONZERO when it is not 0.  A centre exactly on an edge or a vertex belongs to the side
+ * towards larger columns or rows (top and left in, bottom and right out), so shapes that share an edge neither overlap nor leave
+ * a gap; rings of fewer than 3 vertices, zero-area rings, repeated vertices and horizontal edges contribute nothing by the rule
+ * itself; vertices may lie outside the image, only pixels of the image are written.
+ * Layout: ring r is the rows ring_start[r] .. ring_start[r] + ring_count[r] of vertices (ring_start, ring_count int32 [R]; a count
+ * <= 0, or a ring that does not lie within the V rows, draws nothing) -- a packed CSR table and the padded vertices of
+ * cs_regions_contour_labels are both served.  Shape s owns the rings shape_rings[s] .. shape_rings[s + 1] (int32 [S + 1]); image n
+ * owns the shapes image_shapes[n] .. image_shapes[n + 1] (int32 [N + 1], rising).  items int32 [I][3] = (shape, first row, rows):
+ * one workgroup paints those rows of that shape; the items of a shape must cover every row it reaches.  items == NULL (I ignored):
+ * one item per shape, and the workgroup works out the shape's rows itself.
+ * Output: mode CS_POLYGON_LABELS: out int32 [N][H][W], shape s of image n RAISES the pixels it takes to s - image_shapes[n] + 1 by
+ * an integer maximum -- the highest label wins, whatever the order of arrival, and what out held stays where it is larger;
+ * mode CS_POLYGON_MASK: out uint8 [N][H][W], 1 is stored where any shape takes the pixel.  Other pixels are not written: the caller
+ * clears out, or paints onto what it holds.
+ * Need 0 < N <= 65535, 0 < H W < 2^31, max(H, W) << (sub + 1) < 2^30, every coordinate in [-2^28, 2^28] (not checked on the
+ * device: every product then stays below 2^62), V, R, S, I < 2^31, vertices 8-byte aligned.  One launch whose grid depends on
+ * I (or S) alone, no workspace, no environment, no host synchronisation: capturable. */
+#define CS_POLYGON_EVENODD 0
+#define CS_POLYGON_NONZERO 1
+#define CS_POLYGON_LABELS 0
+#define CS_POLYGON_MASK 1
+int cs_polygons_rasterize(const int32_t* vertices, long long V, const int32_t* ring_start, const int32_t* ring_count, int R,
+                          const int32_t* shape_rings, int S, const int32_t* image_shapes, const int32_t* items, long long I, int N,
+                          int H, int W, int sub, int rule, int mode, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
