@@ -205,6 +205,8 @@ _SIGNATURES = {
     "cs_spatial_count_within": (c_int, [_P, _P, _P, c_longlong, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P,
                                         _P, c_size_t, _P]),
     "cs_spatial_bin_counts": (c_int, [_P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P, _P]),
+    "cs_spatial_cluster_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_longlong]),
+    "cs_spatial_cluster": (c_int, [_P, _P, _P, c_longlong] + [c_int] * 6 + [_P] * 8 + [c_size_t, _P]),
     "cs_tissue_histogram": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "cs_tissue_mask": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "cs_tissue_coverage": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_longlong, c_int, c_int, _P, _P]),

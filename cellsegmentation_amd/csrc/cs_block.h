@@ -55,6 +55,20 @@ __device__ __forceinline__ int uf_find(const int32_t* lab, int x) {
     while ((q = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, SCOPE)) != x) x = q;
     return x;
 }
+// uf_find that halves the path it walks: every label on it is lowered to its grandparent, with an atomic minimum, so a label still
+// only decreases and still names a member of its own set, and a root is never written.  Concurrent uf_unite / uf_find stay
+// correct; the forest is the same partition with shorter paths.  For passes that may write the labels.
+template <int SCOPE>
+__device__ __forceinline__ int uf_find_halving(int32_t* lab, int x) {
+    for (;;) {
+        const int p = __hip_atomic_load(lab + x, __ATOMIC_RELAXED, SCOPE);
+        if (p == x) return x;
+        const int g = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, SCOPE);
+        if (g == p) return p;
+        __hip_atomic_fetch_min(lab + x, g, __ATOMIC_RELAXED, SCOPE);
+        x = g;
+    }
+}
 // Hangs the larger root below the smaller.  Every turn that does not end the loop lowers max(a, b): bounded by the index range.
 template <int SCOPE>
 __device__ __forceinline__ void uf_unite(int32_t* lab, int a, int b) {

@@ -20,6 +20,7 @@
 //   count_within  the bucket rows and columns that cover [r - R, r + R] x [c - R, c + R] of every query of the bucket, R = isqrt of
 //                 the largest radius2; |dr| > R or |dc| > R is rejected before anything is squared.  Per-image sums by one 64-bit
 //                 integer atomic per workgroup and radius.
+//   cluster       DBSCAN on the same box walk (walk_box), three times at the one radius: the passes are listed at the kernels.
 // Launch geometry depends on (P, N, H, W, b, k) only; nothing synchronises with the host.
 #include <limits.h>
 #include "cs_common.h"
@@ -253,6 +254,27 @@ __global__ __launch_bounds__(kThreads) void spatial_nearest_kernel(Points q, Poi
     }
 }
 
+// The box walk of the radius queries: every query `me` of the workgroup's bucket, 256 at a time, meets every target record of the
+// bucket rows and columns that cover the reach `box` (pixels) around the bucket.  Every thread of the workgroup calls it (barriers);
+// on the threads that hold a query, begin(me), then take(me, record) for every record of the box, then done(me, buffer row of me).
+template <typename Begin, typename Take, typename Done>
+__device__ __forceinline__ void walk_box(const Query& u, const Grid& g, int box, int4* s_rec, Begin begin, Take take, Done done) {
+    const int b = g.b;
+    const int br0 = max(u.br * b - box, 0) / b, br1 = (int)min(((long long)(u.br + 1) * b - 1 + box) / b, (long long)g.nbr - 1);
+    const int bc0 = max(u.bc * b - box, 0) / b, bc1 = (int)min(((long long)(u.bc + 1) * b - 1 + box) / b, (long long)g.nbc - 1);
+    for (int p0 = 0; p0 < u.qn; p0 += kThreads) {
+        const bool have = p0 + (int)threadIdx.x < u.qn;
+        const int4 me = have ? u.q_rec[u.q0 + p0 + threadIdx.x] : make_int4(0, 0, -1, 0);
+        if (have) begin(me);
+        for (int rr = br0; rr <= br1; ++rr) {
+            int s0, s1;
+            bucket_span(u.t_start, rr * g.nbc + bc0, rr * g.nbc + bc1, s0, s1);
+            scan_records(u.t_rec, s0, s1, s_rec, have, [&](const int4& c) { take(me, c); });
+        }
+        if (have) done(me, u.q_row0 + me.z);
+    }
+}
+
 // grid (N * nb).  R = isqrt(max radius2), box = min(R, max(H, W)): the reach in pixels that picks the bucket range.
 template <bool SELF>
 __global__ __launch_bounds__(kThreads) void spatial_within_kernel(Points q, Points t, Grid g, Cells qc, Cells tc, Radii radii, int n_r, int R,
@@ -262,41 +284,32 @@ __global__ __launch_bounds__(kThreads) void spatial_within_kernel(Points q, Poin
     __shared__ long long s_sum[kThreads / 64];
     Query u;
     if (!open_query(q, t, g, qc, tc, u)) return;
-    const int b = g.b;
-    const int br0 = max(u.br * b - box, 0) / b, br1 = (int)min(((long long)(u.br + 1) * b - 1 + box) / b, (long long)g.nbr - 1);
-    const int bc0 = max(u.bc * b - box, 0) / b, bc1 = (int)min(((long long)(u.bc + 1) * b - 1 + box) / b, (long long)g.nbc - 1);
     long long sum[kMaxRadii];
 #pragma unroll
     for (int j = 0; j < kMaxRadii; ++j) sum[j] = 0;
-    for (int p0 = 0; p0 < u.qn; p0 += kThreads) {
-        const bool have = p0 + (int)threadIdx.x < u.qn;
-        const int4 me = have ? u.q_rec[u.q0 + p0 + threadIdx.x] : make_int4(0, 0, -1, 0);
-        int cnt[kMaxRadii];
+    int cnt[kMaxRadii];
+    walk_box(
+        u, g, box, s_rec,
+        [&](const int4&) {
 #pragma unroll
-        for (int j = 0; j < kMaxRadii; ++j) cnt[j] = 0;
-        auto take = [&](const int4& c) {
+            for (int j = 0; j < kMaxRadii; ++j) cnt[j] = 0;
+        },
+        [&](const int4& me, const int4& c) {
             if (SELF && c.z == me.z) return;
             const int dr = c.x - me.x, dc = c.y - me.y;
             if (dr > R || dr < -R || dc > R || dc < -R) return;
             const int d2 = dr * dr + dc * dc;
 #pragma unroll
             for (int j = 0; j < kMaxRadii; ++j) cnt[j] += (j < n_r && d2 <= radii.r2[j]) ? 1 : 0;
-        };
-        for (int rr = br0; rr <= br1; ++rr) {
-            int s0, s1;
-            bucket_span(u.t_start, rr * g.nbc + bc0, rr * g.nbc + bc1, s0, s1);
-            scan_records(u.t_rec, s0, s1, s_rec, have, take);
-        }
-        if (have) {
-            const long long row = u.q_row0 + me.z;
+        },
+        [&](const int4&, long long row) {
 #pragma unroll
             for (int j = 0; j < kMaxRadii; ++j)
                 if (j < n_r) {
                     counts[row * n_r + j] = cnt[j];
                     sum[j] += cnt[j];
                 }
-        }
-    }
+        });
     const int n = blockIdx.x / g.nb;
 #pragma unroll
     for (int j = 0; j < kMaxRadii; ++j)
@@ -304,6 +317,212 @@ __global__ __launch_bounds__(kThreads) void spatial_within_kernel(Points q, Poin
             const long long all = block_reduce<kThreads, long long>(sum[j], [](long long a, long long c) { return a + c; }, s_sum);
             if (threadIdx.x == 0 && all) atomicAdd(pair_counts + (long long)n * n_r + j, (unsigned long long)all);
         }
+}
+
+// ---- density-based clustering (DBSCAN) of every image's live points -------------------------------------------------------------
+// Three box walks at the one radius, then a numbering and a table pass; union-find parents are buffer rows (P < 2^31).
+//   core      a point with at least `need` = min_samples - 1 other live points within r2 is a core point; lab[row] = row
+//   stamp     one thread per record: the core flag of its point into the record's spare word, so that the next two walks read a
+//             candidate's flag from LDS with the candidate
+//   unite     every core point with every core neighbour of a lower row: uf_unite hangs the larger root below the smaller, so a
+//             cluster's root ends as its smallest core row whatever the order of the unions.  The finds halve their paths
+//             (uf_find_halving), a query remembers the root it was last seen under and a candidate is hung straight below the
+//             root found for it, so most pairs of a dense clump cost the one load that shows they are united already
+//   resolve   lab is only read: root[row] = uf_find for a core point, the smallest root among the core neighbours of another live
+//             point, -1 when it has none (noise); the rows that are not live keep the -1 of the fill
+//   number    a row with root[row] == row is its cluster's first core point.  G[i] = the number of such rows below i, in two levels:
+//             per chunk of 256 rows (block_rank), one workgroup scanning the chunk counts, then chunk base + rank within the chunk.
+//             Images are contiguous row ranges and clusters never cross them: cluster id = G[root] - G[off[n]], in the order of the
+//             roots, and the image has G[off[n + 1]] - G[off[n]] clusters.
+//   table     one thread per row: the label, and integer atomics into row off[n] + id of the tables
+// Every value is a count, a minimum or a sum of integers over a set that the definition fixes: nothing depends on the bucket side,
+// the launch order or thread timing.  No kernel waits for another workgroup.
+constexpr int kCorePass = 0, kUnitePass = 1, kResolvePass = 2;
+constexpr int kAgent = __HIP_MEMORY_SCOPE_AGENT;
+
+struct ClusterWork {
+    int32_t* lab;                                  // [P]       union-find parents
+    int32_t* root;                                 // [P]       the cluster's smallest core row, -1: none
+    int32_t* G;                                    // [P + 1]   cluster roots in the rows below
+    int32_t* chunk;                                // [P / 256 + 1]
+};
+struct ClusterTables {
+    int32_t* size;                                 // [P]       row off[n] + c: cluster c of image n
+    int32_t* n_core;                               // [P]
+    unsigned long long* sums;                      // [P][2] = sum of rows, sum of columns
+    int32_t* bbox;                                 // [P][4] = r0, c0, r1, c1 (half-open)
+};
+
+// grid (N * nb)
+template <int PASS>
+__global__ __launch_bounds__(kThreads) void spatial_cluster_walk_kernel(Points p, Grid g, Cells cells, int r2, int R, int box, int need,
+                                                                        uint8_t* __restrict__ core, ClusterWork w) {
+    __shared__ int4 s_rec[kChunk];
+    Query u;
+    if (!open_query(p, p, g, cells, cells, u)) return;
+    // core: the neighbours within r2; unite: the root the query was last seen under; resolve: the smallest root among the core ones
+    int acc = 0;
+    walk_box(
+        u, g, box, s_rec,
+        [&](const int4& me) { acc = PASS == kCorePass ? 0 : PASS == kUnitePass ? (int)(u.q_row0 + me.z) : INT_MAX; },
+        [&](const int4& me, const int4& c) {
+            if (c.z == me.z) return;
+            if (PASS != kCorePass && !c.w) return;                         // only core points unite or adopt
+            if (PASS == kUnitePass && (!me.w || c.z > me.z)) return;       // every core pair once, from its higher row
+            if (PASS == kResolvePass && me.w) return;
+            const int dr = c.x - me.x, dc = c.y - me.y;
+            if (dr > R || dr < -R || dc > R || dc < -R) return;
+            if (dr * dr + dc * dc > r2) return;
+            if (PASS == kCorePass) ++acc;
+            if (PASS == kUnitePass) {
+                // in a dense clump the candidate hangs below the query's root already: one load settles such a pair
+                const int up = __hip_atomic_load(w.lab + u.q_row0 + c.z, __ATOMIC_RELAXED, kAgent);
+                if (up == acc) return;
+                const int a = uf_find_halving<kAgent>(w.lab, acc), b = uf_find_halving<kAgent>(w.lab, up);
+                if (b != up) __hip_atomic_fetch_min(w.lab + u.q_row0 + c.z, b, __ATOMIC_RELAXED, kAgent);     // an ancestor, as the halving writes
+                if (a != b) uf_unite<kAgent>(w.lab, a, b);
+                acc = min(a, b);
+            }
+            if (PASS == kResolvePass) acc = min(acc, uf_find<kAgent>(w.lab, (int)(u.q_row0 + c.z)));
+        },
+        [&](const int4& me, long long row) {
+            if (PASS == kCorePass) {
+                core[row] = acc >= need ? 1 : 0;
+                w.lab[row] = (int)row;
+            }
+            if (PASS == kResolvePass) w.root[row] = me.w ? uf_find<kAgent>(w.lab, (int)row) : (acc == INT_MAX ? -1 : acc);
+        });
+}
+
+// grid (ceil(P / 256)): slot i of the record buffer belongs to the image whose rows hold it; its first start[n][nb] slots are records
+__global__ __launch_bounds__(kThreads) void spatial_cluster_stamp_kernel(Points p, Grid g, Cells cells, const uint8_t* __restrict__ core) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= p.P || p.off[0] > i) return;
+    int lo = 0, hi = g.N;                          // as live_point
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (p.off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    if (p.off[hi] <= i) return;
+    const Span s = image_span(p, lo);
+    const long long slot = i - s.o0;
+    if (slot < 0 || slot >= s.n_eff || slot >= cells.start[(long long)lo * (g.nb + 1) + g.nb]) return;
+    cells.rec[i].w = core[s.o0 + cells.rec[i].z];
+}
+
+// grid (P / 256 + 1), rows 0 .. P.  WRITE = false: chunk[block] = the cluster roots among the block's rows.  true, after the scan:
+// G[i] = chunk[block] + the roots of the block below i, and the table row i is cleared (lower bounds at INT_MAX: table_kernel lowers
+// them, empty_rows_kernel puts the unused rows right).
+template <bool WRITE>
+__global__ __launch_bounds__(kThreads) void spatial_cluster_rank_kernel(long long P, ClusterWork w, ClusterTables t) {
+    __shared__ int s_wsum[kThreads / 64];
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    int total;
+    const int before = block_rank<kThreads>(i < P && w.root[i] == i, s_wsum, total);
+    if (!WRITE) {
+        if (threadIdx.x == 0) w.chunk[blockIdx.x] = total;
+        return;
+    }
+    if (i <= P) w.G[i] = w.chunk[blockIdx.x] + before;
+    if (i < P) {
+        t.size[i] = 0;
+        t.n_core[i] = 0;
+        t.sums[2 * i] = 0;
+        t.sums[2 * i + 1] = 0;
+        t.bbox[4 * i] = INT_MAX;
+        t.bbox[4 * i + 1] = INT_MAX;
+        t.bbox[4 * i + 2] = 0;
+        t.bbox[4 * i + 3] = 0;
+    }
+}
+
+// grid (1): chunk[0 .. n) -> its exclusive prefix sums, 256 at a time
+__global__ __launch_bounds__(kThreads) void spatial_cluster_scan_kernel(int32_t* __restrict__ chunk, int n) {
+    __shared__ int s_scan[kThreads];
+    int carry = 0;
+    for (int j0 = 0; j0 < n; j0 += kThreads) {
+        const int j = j0 + threadIdx.x;
+        const int v = j < n ? chunk[j] : 0;
+        int total;
+        const int incl = block_scan_incl<kThreads, int>(v, s_scan, total);
+        if (j < n) chunk[j] = carry + incl - v;
+        carry += total;
+    }
+}
+
+constexpr int kTableRounds = 4;
+
+// n points, n_core of them core, with these coordinate sums and bounds (r1, c1 inclusive) into table row `at`
+__device__ __forceinline__ void table_add(const ClusterTables& t, long long at, int n, int n_core, int sr, int sc, int r0, int c0, int r1, int c1) {
+    atomicAdd(t.size + at, n);
+    if (n_core) atomicAdd(t.n_core + at, n_core);
+    atomicAdd(t.sums + 2 * at, (unsigned long long)sr);
+    atomicAdd(t.sums + 2 * at + 1, (unsigned long long)sc);
+    atomicMin(t.bbox + 4 * at, r0);
+    atomicMin(t.bbox + 4 * at + 1, c0);
+    atomicMax(t.bbox + 4 * at + 2, r1 + 1);
+    atomicMax(t.bbox + 4 * at + 3, c1 + 1);
+}
+
+// grid (ceil(max(P, N) / 256)): thread i < N writes n_clusters[i], thread i < P the label of row i and its share of the tables
+__global__ __launch_bounds__(kThreads) void spatial_cluster_table_kernel(Points p, Grid g, ClusterWork w, int32_t* __restrict__ labels,
+                                                                         uint8_t* __restrict__ core, int32_t* __restrict__ n_clusters,
+                                                                         ClusterTables t) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i < g.N) {
+        const long long o0 = p.off[i], o1 = p.off[i + 1];
+        n_clusters[i] = (o0 < 0 || o1 < o0 || o1 > p.P || o1 - o0 > INT_MAX) ? 0 : w.G[o1] - w.G[o0];      // image_span's rule
+    }
+    Live v = {};
+    long long at = -1;                                                     // the table row this thread's point adds to, -1: none
+    bool is_core = false;
+    if (i < p.P) {
+        if (!live_point(p, g, i, v)) {
+            labels[i] = -2;
+            core[i] = 0;
+        } else {
+            const int root = w.root[i];
+            const int id = root < 0 ? -1 : w.G[root] - w.G[v.o0];
+            labels[i] = id;
+            if (id >= 0) {
+                at = v.o0 + id;
+                is_core = core[i] != 0;
+            }
+        }
+    }
+    // Lanes of a wave that feed one table row add up first and one of them goes to memory: a slide that is a single aggregate would
+    // otherwise queue every point on the same eight addresses.  A few rounds, each for the row of the first lane still waiting; the
+    // lanes left after them go on their own.  Sums of integers, minima and maxima: the grouping does not show in the result.
+    const int lane = threadIdx.x & 63;
+    for (int round = 0; round < kTableRounds; ++round) {
+        const unsigned long long waiting = __ballot(at >= 0);
+        if (!waiting) break;                                               // uniform over the wave
+        const int lead = __builtin_ctzll(waiting);
+        const bool in = at >= 0 && at == __shfl(at, lead);
+        const unsigned long long group = __ballot(in), cores = __ballot(in && is_core);
+        int sr = in ? v.r : 0, sc = in ? v.c : 0, r0 = in ? v.r : INT_MAX, c0 = in ? v.c : INT_MAX, r1 = in ? v.r : -1, c1 = in ? v.c : -1;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off);
+            sc += __shfl_xor(sc, off);
+            r0 = min(r0, __shfl_xor(r0, off));
+            c0 = min(c0, __shfl_xor(c0, off));
+            r1 = max(r1, __shfl_xor(r1, off));
+            c1 = max(c1, __shfl_xor(c1, off));
+        }
+        if (lane == lead) table_add(t, at, __popcll(group), __popcll(cores), sr, sc, r0, c0, r1, c1);
+        if (in) at = -1;
+    }
+    if (at >= 0) table_add(t, at, 1, is_core ? 1 : 0, v.r, v.c, v.r, v.c, v.r, v.c);
+}
+
+// grid (ceil(P / 256)): the table rows that no cluster owns hold the empty bounding box (0, 0, 0, 0)
+__global__ __launch_bounds__(kThreads) void spatial_cluster_empty_rows_kernel(long long P, ClusterTables t) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= P || t.size[i] != 0) return;
+    t.bbox[4 * i] = 0;
+    t.bbox[4 * i + 1] = 0;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
@@ -448,6 +667,69 @@ extern "C" int cs_spatial_count_within(const int64_t* pts, const int64_t* off, c
         if (plan.self) hipLaunchKernelGGL(spatial_within_kernel<true>, grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, radii, n_radii, R, box, counts, pc);
         else hipLaunchKernelGGL(spatial_within_kernel<false>, grid, block, 0, st, plan.q, plan.t, plan.g, plan.qc, plan.tc, radii, n_radii, R, box, counts, pc);
     }
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" size_t cs_spatial_cluster_workspace(int N, int H, int W, int bucket, long long P) {
+    Grid g;
+    if (!make_grid(N, H, W, bucket, g) || P < 0 || P >= (1LL << 31)) return 0;
+    const size_t rows = (size_t)P;
+    return cells_bytes(g, P) + 2 * cs_align16((rows > 0 ? rows : 1) * 4) + cs_align16((rows + 1) * 4) + cs_align16((rows / kThreads + 1) * 4);
+}
+
+extern "C" int cs_spatial_cluster(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bucket,
+                                  int radius2, int min_samples, int32_t* labels, uint8_t* core, int32_t* n_clusters, int32_t* size,
+                                  int32_t* n_core, int64_t* sums, int32_t* bbox, void* workspace, size_t workspace_bytes, void* stream) {
+    Grid g;
+    CS_CHECK_ARG(make_grid(N, H, W, bucket, g), "spatial_cluster: need 0 < N <= 65535, H^2 + W^2 < 2^31, bucket >= 1 and at most 2^22 buckets");
+    CS_CHECK_ARG(P >= 0 && P < (1LL << 31), "spatial_cluster: need 0 <= P < 2^31 rows");
+    CS_CHECK_ARG(radius2 >= 0, "spatial_cluster: radius2 must be non-negative and below 2^31");
+    CS_CHECK_ARG(min_samples >= 1, "spatial_cluster: min_samples must be at least 1");
+    CS_CHECK_ARG(off && workspace && n_clusters && (pts || P == 0), "spatial_cluster: NULL argument");
+    CS_CHECK_ARG((labels && core && size && n_core && sums && bbox) || P == 0, "spatial_cluster: NULL argument");
+    CS_CHECK_ARG(workspace_bytes >= cs_spatial_cluster_workspace(N, H, W, bucket, P), "spatial_cluster: workspace too small");
+    CS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(pts) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(off) & 7) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(labels) & 3) == 0 && (reinterpret_cast<uintptr_t>(n_clusters) & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(size) & 3) == 0 && (reinterpret_cast<uintptr_t>(n_core) & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(bbox) & 3) == 0, "spatial_cluster: misaligned argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        fill(n_clusters, N, 0, st);
+        CS_LAUNCH_CHECK();
+        return CS_OK;
+    }
+    char* at = reinterpret_cast<char*>(workspace);
+    const Points p = {pts, off, limit, P, 0};
+    const Cells cells = carve(g, P, at);
+    ClusterWork w;
+    w.lab = reinterpret_cast<int32_t*>(at);
+    at += cs_align16((size_t)P * 4);
+    w.root = reinterpret_cast<int32_t*>(at);
+    at += cs_align16((size_t)P * 4);
+    w.G = reinterpret_cast<int32_t*>(at);
+    at += cs_align16(((size_t)P + 1) * 4);
+    w.chunk = reinterpret_cast<int32_t*>(at);
+    const ClusterTables t = {size, n_core, reinterpret_cast<unsigned long long*>(sums), bbox};
+    int R = 0;                                                            // isqrt(radius2)
+    while ((long long)(R + 1) * (R + 1) <= radius2) ++R;
+    const int box = R < (H > W ? H : W) ? R : (H > W ? H : W);
+    fill(w.root, P, -1, st);
+    build(p, g, cells, st);
+    const dim3 walk((unsigned)(g.N * g.nb)), block(kThreads), rows((unsigned)((P + kThreads - 1) / kThreads));
+    const unsigned chunks = (unsigned)(P / kThreads + 1);
+    const long long most = P > N ? P : N;
+    hipLaunchKernelGGL(spatial_cluster_walk_kernel<kCorePass>, walk, block, 0, st, p, g, cells, radius2, R, box, min_samples - 1, core, w);
+    hipLaunchKernelGGL(spatial_cluster_stamp_kernel, rows, block, 0, st, p, g, cells, core);
+    hipLaunchKernelGGL(spatial_cluster_walk_kernel<kUnitePass>, walk, block, 0, st, p, g, cells, radius2, R, box, 0, core, w);
+    hipLaunchKernelGGL(spatial_cluster_walk_kernel<kResolvePass>, walk, block, 0, st, p, g, cells, radius2, R, box, 0, core, w);
+    hipLaunchKernelGGL(spatial_cluster_rank_kernel<false>, dim3(chunks), block, 0, st, P, w, t);
+    hipLaunchKernelGGL(spatial_cluster_scan_kernel, dim3(1), block, 0, st, w.chunk, (int)chunks);
+    hipLaunchKernelGGL(spatial_cluster_rank_kernel<true>, dim3(chunks), block, 0, st, P, w, t);
+    hipLaunchKernelGGL(spatial_cluster_table_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads)), block, 0, st, p, g, w, labels, core,
+                       n_clusters, t);
+    hipLaunchKernelGGL(spatial_cluster_empty_rows_kernel, rows, block, 0, st, P, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -476,7 +476,7 @@ class DetectResult:
             kw["other_xy"] = other_xy
         res = fn(pts, image_hw, arg, offsets=off, limits=S._limits(self.cell_counts, len(self.offsets) - 1), _bucket=_bucket, **kw)
         rows = int(self.offsets[-1])                                       # the device buffer holds spare rows after the last map's
-        for name in ("index", "d2", "counts"):
+        for name in ("index", "d2", "counts", "labels", "core", "size", "n_core", "sums", "bbox"):
             if hasattr(res, name):
                 setattr(res, name, getattr(res, name)[:rows])
         return res
@@ -494,6 +494,16 @@ class DetectResult:
         per-map sums -> spatial.WithinCounts (spatial.count_within has the rules); the arguments are those of ``nearest``."""
         from . import spatial as Sp
         return self._neighbours(Sp.count_within, image_hw, radii, other, other_offsets, other_xy, _bucket)
+
+    def cluster(self, image_hw, eps, min_samples=5, _bucket=None):
+        """The DBSCAN clusters of every map's kept detections -- ``per_image()[n][0]``, as in ``nearest`` -- -> spatial.ClusterTable,
+        one row per row of ``points`` (spatial.cluster has the rules); cluster c of map n is row ``offsets[n] + c`` of its tables.
+        ``image_hw``: the (H, W) of the maps.  The device-resident points are read where they are."""
+        from . import spatial as Sp
+
+        def fn(pts, hw, eps, **kw):
+            return Sp.cluster(pts, hw, eps, min_samples, **kw)
+        return self._neighbours(fn, image_hw, eps, None, None, False, _bucket)
 
     def split(self, masks, connectivity=1, geodesic=False):
         """Split the cells of ``masks`` (bool [N, H, W], or [H, W] for one map: the segmentation the detections belong to) at every

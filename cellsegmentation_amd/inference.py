@@ -595,6 +595,19 @@ def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
     return near, within
 
 
+def slide_clusters(result, eps, min_samples=5):
+    """The aggregates of the detected cells of a ``SlideResult``, on the device: ``result.points`` is uploaded once and clustered by
+    ``spatial.cluster`` (DBSCAN; its docstring has the rules) with the mask's shape as the image -> ``spatial.ClusterTable``: the
+    cluster number of every detection (-1: noise), ``n_clusters`` [1], and size, core count, centroid sums and bounding box of
+    cluster c in row c of the tables.  Everything stays a device tensor, row i being ``result.points[i]``; nothing synchronises."""
+    from . import spatial as Sp
+    if not isinstance(result, SlideResult):
+        raise TypeError("slide_clusters: expected the SlideResult of detect_slide")
+    hw = tuple(int(v) for v in result.mask.shape)
+    pts = np.asarray(result.points, np.int64).reshape(-1, 2)
+    return Sp.cluster(torch.from_numpy(pts).to(result.mask.device), hw, eps, min_samples)
+
+
 def _batch_points(points, n):
     """the annotations of a batch as the loader yields them -> a list of n [k, 2] arrays: a list of per-image arrays, or the
     [n, k, 2] tensor the default collate makes of equally long lists (batch size 1 in the reference)"""

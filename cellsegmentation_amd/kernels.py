@@ -1840,6 +1840,38 @@ def spatial_count_within(pts, off, H, W, bucket, radii2, limits=None, other=None
     return t["counts"], t["pair_counts"]
 
 
+def spatial_cluster_workspace(N, H, W, bucket, P, device):
+    """the caller-owned scratch of one cs_spatial_cluster call"""
+    why = (f"spatial: a call takes 0 < N <= 65535 images with H^2 + W^2 < 2^31 and at most 2^22 buckets, got "
+           f"{(N, H, W)} with buckets of side {bucket}")
+    return _workspace(_lib.load().cs_spatial_cluster_workspace, device, why, int(N), int(H), int(W), int(bucket), int(P))
+
+
+def spatial_cluster(pts, off, H, W, bucket, radius2, min_samples, limits=None, labels=None, core=None, n_clusters=None, size=None,
+                    n_core=None, sums=None, bbox=None, ws=None):
+    """pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None, radius2 in [0, 2^31) and min_samples >= 1 host integers ->
+    (labels int32 [P], core uint8 [P], n_clusters int32 [N], size int32 [P], n_core int32 [P], sums int64 [P,2], bbox int32 [P,4])
+    on the device: DBSCAN of every image's live points; cluster c of image n is row off[n] + c of the four tables
+    (cs_spatial_cluster in include/cellseg_hip.h)"""
+    pts, off, limits, _, _, _, N = _spatial_args("spatial_cluster", pts, off, limits, None, None, None)
+    radius2, min_samples = int(radius2), int(min_samples)
+    if not 0 <= radius2 < 1 << 31:
+        raise ValueError(f"spatial_cluster: radius2 must be in [0, 2^31), got {radius2}")
+    if not 1 <= min_samples < 1 << 31:
+        raise ValueError(f"spatial_cluster: min_samples must be in [1, 2^31), got {min_samples}")
+    P = int(pts.shape[0])
+    if ws is None:
+        ws = spatial_cluster_workspace(N, H, W, bucket, P, pts.device)
+    want = {"labels": ((P,), torch.int32), "core": ((P,), torch.uint8), "n_clusters": ((N,), torch.int32), "size": ((P,), torch.int32),
+            "n_core": ((P,), torch.int32), "sums": ((P, 2), torch.int64), "bbox": ((P, 4), torch.int32)}
+    t = _regions_outputs("spatial_cluster", want, {"labels": labels, "core": core, "n_clusters": n_clusters, "size": size, "n_core": n_core,
+                                                   "sums": sums, "bbox": bbox}, pts.device)
+    out = [_p(t[name]) if P or name == "n_clusters" else None for name in want]
+    _lib.check(_lib.load().cs_spatial_cluster(_p(pts) if P else None, _p(off), _p(limits), P, N, int(H), int(W), int(bucket), radius2,
+                                              min_samples, *out, _p(ws), ws.numel(), _stream()), "spatial_cluster")
+    return tuple(t[name] for name in want)
+
+
 def spatial_bin_counts(pts, off, H, W, bin, limits=None, out=None):
     """pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None -> int32 [N, ceil(H/bin), ceil(W/bin)] on the device: the live
     points per square bin (cs_spatial_bin_counts in include/cellseg_hip.h)"""

@@ -1,5 +1,6 @@
 """Neighbourhood statistics of detected cells on the HIP path (csrc/spatial.hip): the nearest neighbours of every point, the number
-of points within a radius of it, and the density map -- exact integer work on a bucket grid, for a ragged batch of images at once.
+of points within a radius of it, the density map, and the density-based clusters (DBSCAN) of the points with their per-cluster
+tables -- exact integer work on a bucket grid, for a ragged batch of images at once.
 
 Points are integer (row, col) rows; image n owns ``points[offsets[n]:offsets[n + 1]]`` (``offsets=None``: one image), numpy or
 torch, on the host or the device, as ``score.score_points`` takes them.  ``limits`` (None, one count or one per image) applies
@@ -56,6 +57,53 @@ class WithinCounts:
     counts: torch.Tensor
     pair_counts: torch.Tensor
     radii2: tuple
+
+
+@dataclass
+class ClusterTable:
+    """The DBSCAN clusters of every image's live points (``cluster``), all device tensors.  Per row of ``points``: ``labels`` int32
+    [P], the cluster number within the row's image, -1 for noise, -2 in the rows that are not live; ``core`` uint8 [P], 1 on core
+    points.  ``n_clusters`` int32 [N].  The cluster tables have P rows too and use the points' own ``offsets``: cluster c of image n
+    is row ``offsets[n] + c`` -- an image never has more clusters than points, so nothing overflows.  ``size`` int32 [P] (core plus
+    border points), ``n_core`` int32 [P], ``sums`` int64 [P, 2] (sum of rows, sum of columns), ``bbox`` int32 [P, 4] = r0, c0, r1, c1
+    half-open, as ``RegionTable.bbox``; every other table row is all zero.  ``radius2``, ``min_samples``: the integers the kernels
+    compared against."""
+    labels: torch.Tensor
+    core: torch.Tensor
+    n_clusters: torch.Tensor
+    size: torch.Tensor
+    n_core: torch.Tensor
+    sums: torch.Tensor
+    bbox: torch.Tensor
+    radius2: int
+    min_samples: int
+    offsets: torch.Tensor
+
+    @property
+    def centroid(self):
+        """float64 [P, 2] on the device: (row, col) = sums / size, NaN in the table rows that no cluster owns"""
+        return self.sums.to(torch.float64) / self.size.to(torch.float64)[:, None]
+
+    @property
+    def n_noise(self):
+        """int64 [N] on the device: the live points of every image that belong to no cluster; nothing synchronises"""
+        seen = torch.cat([self.labels.new_zeros(1, dtype=torch.int64), (self.labels == -1).to(torch.int64).cumsum(0)])
+        at = self.offsets.clamp(0, self.labels.numel())
+        return seen[at[1:]] - seen[at[:-1]]
+
+    def per_image(self):
+        """A host list of N dicts of numpy arrays: ``labels`` and ``core`` of the image's rows, and ``size``, ``n_core``, ``bbox``,
+        ``centroid`` trimmed to its ``n_clusters`` rows.  The one method that synchronises."""
+        cols = {"size": self.size, "n_core": self.n_core, "bbox": self.bbox, "centroid": self.centroid}
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        labels, core = self.labels.cpu().numpy(), self.core.cpu().numpy()
+        off, counts = self.offsets.cpu().numpy(), self.n_clusters.cpu().numpy()
+        out = []
+        for n, c in enumerate(counts):
+            d = {"labels": labels[off[n]:off[n + 1]], "core": core[off[n]:off[n + 1]]}
+            d.update({k: v[off[n]:off[n] + int(c)] for k, v in cols.items()})
+            out.append(d)
+        return out
 
 
 def check_image_hw(image_hw):
@@ -189,6 +237,33 @@ def count_within(points, image_hw, radii, offsets=None, limits=None, other=None,
     kw = _upload(q, t, points, offsets, other, other_offsets)
     counts, pairs = K.spatial_count_within(q.pts_dev, q.off_dev, H, W, b, r2, limits=q.lim_dev, other_xy=other_xy, **kw)
     return WithinCounts(counts, pairs, r2)
+
+
+def cluster(points, image_hw, eps, min_samples=5, offsets=None, limits=None, _bucket=None):
+    """Density-based clustering (DBSCAN) of every image's live points -> ``ClusterTable``: which cells form an aggregate, how many
+    aggregates there are, how large each one is and where it lies.  The labels and core flags equal
+    ``sklearn.cluster.DBSCAN(eps, min_samples)`` image by image, with ``d2 <= floor(eps^2)`` (``score.radius_squared``) for
+    ``distance <= eps``:
+
+    * a live point is a *core point* when at least ``min_samples`` live points of its image lie within ``eps`` of it, itself
+      included; another row at the same coordinates is a neighbour at distance 0;
+    * two core points share a cluster when a chain of core points joins them whose steps are all within ``eps``; an image's
+      clusters are numbered from 0 in increasing order of the smallest index that a core point of the cluster has;
+    * a live point that is not core but has a core point within ``eps`` is a *border point* of the lowest-numbered cluster among
+      those core points' -- it never joins two clusters; every other live point is noise, label -1; rows that are not live hold -2.
+
+    ``min_samples`` is an integer >= 1.  ``min_samples=1`` makes every live point a core point: single-linkage ("friends of
+    friends") grouping at distance ``eps``, the connected components of the graph of pairs within ``eps``.  Nothing depends on the
+    bucket side, the launch order or thread timing; the launches follow from the sizes alone, so a call can be captured."""
+    H, W = check_image_hw(image_hw)
+    r2 = radius_squared(eps)
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 1 <= min_samples < 1 << 31:
+        raise ValueError(f"cluster: min_samples must be an integer in 1..2^31 - 1, got {min_samples!r}")
+    q = _PointSet(points, offsets, limits, None, "cluster: points")
+    b = _bucket_for(_bucket, H, W, q, None, reach=min(math.isqrt(r2), max(H, W)))
+    _upload(q, None, points, offsets)
+    out = K.spatial_cluster(q.pts_dev, q.off_dev, H, W, b, r2, int(min_samples), limits=q.lim_dev)
+    return ClusterTable(*out, r2, int(min_samples), q.off_dev)
 
 
 def bin_counts(points, image_hw, bin, offsets=None, limits=None):

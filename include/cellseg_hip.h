@@ -939,6 +939,29 @@ int cs_spatial_count_within(const int64_t* pts, const int64_t* off, const int32_
 int cs_spatial_bin_counts(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bin,
                           int32_t* out, void* stream);
 
+/* ---- density-based clustering (DBSCAN) of the live points of every image, on the same grid (csrc/spatial.hip) -----------------
+ * pts / off / limit / P / N / H / W / bucket and LIVE as above; the result equals sklearn.cluster.DBSCAN(eps, min_samples) with
+ * radius2 = floor(eps^2) >= 0 and min_samples >= 1, image by image:
+ *   core point : a live point i with 1 + #(live points j != i of its image with d2(i, j) <= radius2) >= min_samples -- it counts
+ *                itself, and another row at the same coordinates is a neighbour at distance 0;
+ *   cluster    : core points joined by a chain of core points whose steps all have d2 <= radius2; the clusters of an image are
+ *                numbered 0 .. C - 1 in increasing order of the smallest index that a core point of the cluster has;
+ *   border     : a live point that is not core but has a core point within radius2 takes the lowest cluster number among those
+ *                core points' clusters (it never joins two clusters); every other live point is noise.
+ * labels int32 [P]: the cluster number, -1 noise, -2 in the rows that are not live.  core uint8 [P]: 1 on core points, else 0.
+ * n_clusters int32 [N].  The tables have P rows and use the points' own offsets: cluster c of image n is row off[n] + c (an image
+ * never has more clusters than points, so there is no capacity and no overflow).  size int32 [P]: core plus border points; n_core
+ * int32 [P]; sums int64 [P][2] = (sum of rows, sum of columns); bbox int32 [P][4] = r0, c0, r1, c1 (half-open, as
+ * cs_regions_measure).  Every other table row is all zero.  Nothing depends on bucket, the launch order or thread timing.
+ * A fixed sequence of launches on one stream for given (P, N, H, W, bucket), no host synchronisation: capturable.  pts, off and
+ * sums 8-byte, the int32 outputs 4-byte aligned; pts and every output but n_clusters may be NULL when P == 0.  workspace: 16-byte
+ * aligned, >= cs_spatial_cluster_workspace(N, H, W, bucket, P) bytes (0 for sizes a call would refuse); its contents on entry do
+ * not matter. */
+size_t cs_spatial_cluster_workspace(int N, int H, int W, int bucket, long long P);
+int cs_spatial_cluster(const int64_t* pts, const int64_t* off, const int32_t* limit, long long P, int N, int H, int W, int bucket,
+                       int radius2, int min_samples, int32_t* labels, uint8_t* core, int32_t* n_clusters, int32_t* size, int32_t* n_core,
+                       int64_t* sums, int32_t* bbox, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- tissue detection for whole-slide streaming (csrc/tissue.hip) -----------------------------------------------------------
  * images_hwc uint8 [N][H][W][3] (RGB), 0 < N <= 65535, 0 < H W < 2^31; pixel offsets are 64-bit, N H W 3 may pass 2^31.  No
  * alignment is asked of the images or the masks.  The pixel feature f(r, g, b) in [0, 255] is selected by `channel`:

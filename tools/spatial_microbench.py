@@ -2,6 +2,7 @@
 call -- uploads excluded, the points are device tensors -- median of 7 after a warm-up.
 
     python tools/spatial_microbench.py [--json PATH] [--quick]
+    python tools/spatial_microbench.py --cluster [--json PATH]
 
 Workloads: 128 images of 299^2 with about 80 points each (the workload of the ``regions.split`` table), one 4096^2 image with 10^4
 and 10^5 uniformly placed points, and the same 10^5 points in 100 tight clumps.  Each runs ``nearest`` (k = 1 and 8) and
@@ -13,7 +14,15 @@ and 10^5 uniformly placed points, and the same 10^5 points in 100 tight clumps. 
     kdtree   ``scipy.spatial.cKDTree`` on the host, the copy of the points to the host included
 
 Every row reports the bucket side, the buckets per image and the largest bucket occupancy, and whether grid and single agree bit
-for bit (and, for the distances and counts, with the tree).  ``--quick`` leaves out the single-bucket runs of the 10^5-point rows."""
+for bit (and, for the distances and counts, with the tree).  ``--quick`` leaves out the single-bucket runs of the 10^5-point rows.
+
+``--cluster`` times ``spatial.cluster`` (DBSCAN, min_samples 5, eps 16 and 64) on the same point sets instead, next to two
+yardsticks: ``spatial.count_within`` at the same radius on the same points -- the cost of one box walk, of which the cluster call
+makes three plus the grid build, the numbering and the table pass -- and the host library on the same box, the copy of the points
+to the host included: ``sklearn.cluster.DBSCAN`` image by image, or, where scikit-learn is absent, ``scipy.spatial.cKDTree`` pairs
+and ``scipy.sparse.csgraph.connected_components`` over the core points (the clusters without their border points).  The host run
+is left out where the pairs within eps, which ``count_within`` has just counted, pass 5 x 10^7: its neighbour lists would not fit.
+Every row says whether the labels equal the host library's."""
 import argparse
 import json
 import os
@@ -82,12 +91,79 @@ def kdtree(dev_pts, off, k=None, radius=None):
     return (np.concatenate(d2s), None) if k is not None else (None, np.concatenate(cnts))
 
 
+MAX_HOST_PAIRS = 5 * 10 ** 7
+
+
+def host_dbscan(dev_pts, off, eps, min_samples):
+    """the host yardstick: copy, then image by image -> (labels int64 [P] | None, core bool [P], library name).  Without
+    scikit-learn the labels are None: the components of the core points are timed, border points are not assigned."""
+    pts = dev_pts.cpu().numpy().astype(np.float64)
+    labels, core = np.full(len(pts), -1, np.int64), np.zeros(len(pts), bool)
+    try:
+        from sklearn.cluster import DBSCAN
+    except ImportError:
+        DBSCAN = None
+    for n in range(len(off) - 1):
+        p = pts[off[n]:off[n + 1]]
+        if not len(p):
+            continue
+        if DBSCAN is not None:
+            fit = DBSCAN(eps=np.sqrt(eps * eps + 0.5), min_samples=min_samples).fit(p)
+            labels[off[n]:off[n + 1]] = fit.labels_
+            core[off[n] + fit.core_sample_indices_] = True
+            continue
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        from scipy.spatial import cKDTree
+        pairs = cKDTree(p).query_pairs(np.sqrt(eps * eps + 0.5), output_type="ndarray")
+        c = np.bincount(pairs.ravel(), minlength=len(p)) + 1 >= min_samples
+        keep = pairs[c[pairs[:, 0]] & c[pairs[:, 1]]]
+        connected_components(coo_matrix((np.ones(len(keep), bool), (keep[:, 0], keep[:, 1])), shape=(len(p), len(p))), directed=False)
+        core[off[n]:off[n + 1]] = c
+    return (labels if DBSCAN is not None else None), core, "sklearn.cluster.DBSCAN" if DBSCAN is not None else "scipy cKDTree + connected_components"
+
+
+def cluster_rows(dev, min_samples=5):
+    rows = []
+    for name, pts, off, (H, W) in workloads():
+        d_pts, d_off = torch.from_numpy(pts.astype(np.int64)).to(dev), torch.from_numpy(off).to(dev)
+        N, P = len(off) - 1, len(pts)
+        for eps in (16, 64):
+            b = S.choose_bucket(H, W, N, P, eps)
+            row = {"workload": name, "eps": eps, "min_samples": min_samples, "bucket": b, "buckets_per_image": S.n_buckets(H, W, b),
+                   "max_occupancy": int(S.bin_counts(d_pts, (H, W), b, offsets=d_off).max())}
+            row["cluster_ms"] = time_dev(lambda: S.cluster(d_pts, (H, W), eps, min_samples, offsets=d_off), 7)
+            row["count_within_ms"] = time_dev(lambda: S.count_within(d_pts, (H, W), eps, offsets=d_off), 7)
+            row["walks"] = row["cluster_ms"] / row["count_within_ms"]
+            got = S.cluster(d_pts, (H, W), eps, min_samples, offsets=d_off)
+            row["pairs_within_eps"] = int(S.count_within(d_pts, (H, W), eps, offsets=d_off).pair_counts.sum())
+            row.update(clusters=int(got.n_clusters.sum()), core=int(got.core.sum()), noise=int(got.n_noise.sum()))
+            if row["pairs_within_eps"] <= MAX_HOST_PAIRS:
+                row["host_ms"], (labels, core, row["host"]) = time_host(lambda: host_dbscan(d_pts, off, eps, min_samples), 3 if P < 10 ** 5 else 1)
+                row["host_agrees"] = bool(np.array_equal(got.core.cpu().numpy().astype(bool), core) and
+                                          (labels is None or np.array_equal(got.labels.cpu().numpy(), labels)))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--cluster", action="store_true", help="time spatial.cluster against count_within and the host library instead")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.cluster:
+        rows = cluster_rows(dev)
+        ok = all(r.get("host_agrees", True) for r in rows)
+        out = {"device": torch.cuda.get_device_name(0), "threads": S.THREADS, "chunk": S.CHUNK, "occupancy_target": S.OCCUPANCY, "rows": rows,
+               "all_agree": ok}
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({"all_agree": ok, "rows": len(rows)}))
+        return 0 if ok else 1
     rows = []
     for name, pts, off, (H, W) in workloads():
         d_pts, d_off = torch.from_numpy(pts.astype(np.int64)).to(dev), torch.from_numpy(off).to(dev)
