@@ -30,7 +30,8 @@
 //             workgroup per pair, the target's horizontal runs staged in LDS and every pixel of the source held against them
 //   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
 //             component without a seed is numbered after the seeds:
-//               seeds   one thread per point hangs the live seeds on a chain at their component's root
+//               seeds   one thread per row of the ragged point set (cs_points.h) hangs the live seeds on a chain at their
+//                       component's root
 //               number  the numbering trio over the roots that have no seed
 //               assign  every pixel walks the chain of its root; a wave whose foreground lanes share a root walks it as one
 //   geodesic  the same split with the distance measured along paths that stay inside the component (5-7 chamfer steps), so that
@@ -46,6 +47,7 @@
 #include <stdio.h>
 #include "cs_common.h"
 #include "cs_block.h"
+#include "cs_points.h"
 
 namespace {
 
@@ -176,25 +178,9 @@ __global__ __launch_bounds__(256) void spread_kernel(const uint8_t* __restrict__
         out[p] = (foreground_only && m[p] == 0) ? 0 : table[lab[p]];
 }
 
-// ---- the seed points of a split: pts int64 [P][2] (row, col), image n owns pts[off[n] .. off[n + 1]) -----------------------------
-struct Seeds {
-    const long long* pts;
-    const long long* off;     // [N + 1]; NULL = no seeds at all
-    const int32_t* lim;       // [N] or NULL: Python's slice [:lim[n]] of image n's points
-    int P;                    // rows of pts
-};
-
-// S'_n, the number of points of image n that are seeds: within [0, P] whatever the offsets hold
-__device__ __forceinline__ int seed_limit(const Seeds& s, int n) {
-    if (!s.off) return 0;
-    long long k = s.off[n + 1] - s.off[n];
-    k = k < 0 ? 0 : (k > s.P ? s.P : k);
-    if (s.lim) {
-        const long long c = s.lim[n];
-        k = c >= 0 ? (c < k ? c : k) : (k + c > 0 ? k + c : 0);
-    }
-    return (int)k;
-}
+// ---- the seed points of a split: the ragged point set of cs_points.h, rows (row, col); off == NULL (P == 0) = no seeds at all ------
+// S'_n, the number of points of image n that are seeds: the rows its window keeps
+__device__ __forceinline__ int seed_limit(const PointSet& s, int n) { return s.off ? point_window(s, n).kept : 0; }
 
 // ---- scipy's numbering: grid (blocks per image, N), kNB pixels per block --------------------------------------------------------
 // SEEDLESS = false: every foreground root.  SEEDLESS = true (split): the foreground roots whose slot of `cnt` still holds the area
@@ -217,7 +203,7 @@ __global__ __launch_bounds__(kNB) void number_count_kernel(const uint8_t* __rest
 
 // one workgroup per image: blk[n][0..B) -> its exclusive prefix sums, in place
 // counts (or NULL): [n] = the number of counted roots of image n, after its seeds_n = S'_n seeds
-__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B, int32_t* __restrict__ counts, Seeds seeds) {
+__global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__ blk_all, int B, int32_t* __restrict__ counts, PointSet seeds) {
     __shared__ int part[1024];
     int32_t* blk = blk_all + (long long)blockIdx.x * B;
     const int seg = (B + 1023) / 1024;
@@ -237,7 +223,7 @@ __global__ __launch_bounds__(1024) void number_scan_kernel(int32_t* __restrict__
 // num: the cnt array itself -- a counted root reads its own slot (SEEDLESS) and then writes its number there, nobody else's
 template <bool SEEDLESS>
 __global__ __launch_bounds__(kNB) void number_assign_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ lab, long long HW,
-                                                            const int32_t* __restrict__ blk, int32_t* num, Seeds seeds) {
+                                                            const int32_t* __restrict__ blk, int32_t* num, PointSet seeds) {
     __shared__ int wsum[kNB / 64];
     const long long base = blockIdx.y * HW;
     const long long i = (long long)blockIdx.x * kNB + threadIdx.x;
@@ -1335,18 +1321,19 @@ __global__ __launch_bounds__(256) void hausdorff_finish_kernel(Haus t) {
 // within the image, the next point of the chain or -1).  The order of a chain depends on the order the pushes land in; what the
 // assign pass takes from it, the minimum of (d2, index) over the chain, does not.  keys (geodesic split, else NULL): a live seed also
 // lowers the key of its pixel to (0, index).
-__global__ __launch_bounds__(256) void seed_kernel(const uint8_t* __restrict__ m, int N, int H, int W, Seeds s,
+__global__ __launch_bounds__(256) void seed_kernel(const uint8_t* __restrict__ m, int N, int H, int W, PointSet s,
                                                    const int32_t* __restrict__ lab, int32_t* __restrict__ head, int4* __restrict__ rec,
                                                    uint8_t* __restrict__ live, unsigned long long* __restrict__ keys) {
     const long long HW = (long long)H * W, total = HW * N;
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < s.P; p += (long long)gridDim.x * 256) {
-        int n = 0, hi = N;                                             // the last image whose first point is not after p; every
-        while (hi - n > 1) {                                           // read stays inside off[0 .. N] whatever the offsets hold
-            const int mid = (n + hi) >> 1;
-            if (s.off[mid] <= p) n = mid; else hi = mid;
+        const int n = point_image(s, N, p);
+        bool ok = n >= 0;
+        long long k = 0;                                               // the point's index within its image
+        if (ok) {
+            const PointWindow w = point_window(s, n);
+            k = p - w.o0;
+            ok = k < w.kept;
         }
-        const long long k = p - s.off[n];
-        bool ok = k >= 0 && p < s.off[n + 1] && k < seed_limit(s, n);
         const long long r = s.pts[2 * p], c = s.pts[2 * p + 1];
         ok = ok && r >= 0 && r < H && c >= 0 && c < W;
         const long long q = ok ? n * HW + r * W + c : 0;
@@ -1719,7 +1706,7 @@ int label_into(const uint8_t* m, int N, int H, int W, int connectivity, const Ws
 // number of foreground components of every image.  SEEDLESS (split, after the seed pass): only the roots without a seed, numbered
 // from S'_n + 1, and counts = S'_n + their number.
 template <bool SEEDLESS = false>
-int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st, const Seeds& seeds = Seeds{}) {
+int number_into(const uint8_t* m, int N, int H, int W, const Ws& ws, int32_t* counts, hipStream_t st, const PointSet& seeds = PointSet{}) {
     const long long HW = (long long)H * W;
     const int B = (int)blocks_per_image(H, W);
     hipLaunchKernelGGL(number_count_kernel<SEEDLESS>, dim3(B, N), dim3(kNB), 0, st, m, ws.lab, ws.cnt, HW, ws.blk);
@@ -2031,7 +2018,7 @@ extern "C" int cs_regions_split(const uint8_t* mask, int N, int H, int W, int co
     int4* rec;
     CS_CHECK_ARG(workspace_bytes >= regions_layout(workspace, N, H, W, &ws, P, &rec), "regions_split: workspace too small");
     CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7), "regions_split: misaligned int64 array");
-    const Seeds seeds{reinterpret_cast<const long long*>(points), P > 0 ? reinterpret_cast<const long long*>(offsets) : nullptr, limits, P};
+    const PointSet seeds{points, P > 0 ? offsets : nullptr, limits, P, 0};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if ((rc = label_into(mask, N, H, W, connectivity, ws, st)) != CS_OK) return rc;
     if (P > 0) {
@@ -2069,7 +2056,7 @@ extern "C" int cs_regions_split_geodesic(const uint8_t* mask, int N, int H, int 
     CS_CHECK_ARG(workspace_bytes >= geodesic_layout(workspace, N, H, W, P, &ws, &rec, &g), "regions_split_geodesic: workspace too small");
     CS_CHECK_ARG(!((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7),
                  "regions_split_geodesic: misaligned int64 array");
-    const Seeds seeds{reinterpret_cast<const long long*>(points), P > 0 ? reinterpret_cast<const long long*>(offsets) : nullptr, limits, P};
+    const PointSet seeds{points, P > 0 ? offsets : nullptr, limits, P, 0};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long total = (long long)N * H * W;
     if (!resume) {

@@ -12,11 +12,13 @@
 //            per run; a first version that asked label by label -- a division and four loads per labelled pixel, in divergent
 //            code -- ran at 18 times the copy.  The colour table and the palette sit in LDS as packed words.  The grid is capped and
 //            strides; every pixel depends on its own inputs alone.
-//   points   a scatter: one wave per row of the points buffer, its lanes over the box of the disc or ring, byte stores.  Every store
-//            of a launch carries the same colour, so marks that overlap do not depend on the order of arrival.
+//   points   a scatter: one wave per row of the points buffer (the ragged point set of cs_points.h: the rows its windows keep, or
+//            with `tail` the rows of a window that its limit does not keep), its lanes over the box of the disc or ring, byte
+//            stores.  Every store of a launch carries the same colour, so marks that overlap do not depend on the order of arrival.
 #include <limits.h>
 #include "cs_common.h"
 #include "cs_pixels.h"
+#include "cs_points.h"
 
 namespace {
 
@@ -242,11 +244,8 @@ __global__ __launch_bounds__(kThreads) void render_compose_kernel(const ComposeA
 
 struct PointArgs {
     uint8_t* canvas;                               // [N][H][W][3]
-    const int64_t* pts;                            // [P][2]
-    const int64_t* off;                            // [N + 1]
-    const int32_t* limit;                          // [N] or NULL
-    long long P;
-    int N, H, W, radius, thickness, xy, tail;
+    PointSet p;
+    int N, H, W, radius, thickness, tail;
     uint32_t rgb;
 };
 
@@ -254,26 +253,11 @@ struct PointArgs {
 __global__ __launch_bounds__(kThreads) void render_points_kernel(const PointArgs a) {
     const long long i = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (i >= a.P || a.off[0] > i) return;
-    int lo = 0, hi = a.N;                          // the last n in [0, N] with off[n] <= i, as live_point of spatial.hip
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.off[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    if (a.off[hi] <= i) return;                    // beyond the last image
-    const long long o0 = a.off[lo], o1 = a.off[lo + 1];
-    if (o0 < 0 || o1 < o0 || o1 > a.P || o1 - o0 > INT_MAX) return;        // offsets that do not describe rows of the buffer
-    const long long idx = i - o0;
-    if (idx < 0 || idx >= o1 - o0) return;
-    const int cnt = (int)(o1 - o0);
-    int kept = cnt;
-    if (a.limit) {                                 // Python's [:c]
-        const int c = a.limit[lo];
-        kept = c >= 0 ? min(c, cnt) : max(cnt + c, 0);
-    }
-    if ((idx < kept) == (a.tail != 0)) return;
-    const long long pr = a.pts[2 * i + a.xy], pc = a.pts[2 * i + 1 - a.xy];
+    const int n = i < a.p.P ? point_image(a.p, a.N, i) : -1;
+    if (n < 0) return;
+    const PointWindow w = point_window(a.p, n);
+    if (!w.ok || (i - w.o0 < w.kept) == (a.tail != 0)) return;
+    const long long pr = a.p.pts[2 * i + a.p.xy], pc = a.p.pts[2 * i + 1 - a.p.xy];
     const int t = a.thickness, R = t < 0 ? a.radius : a.radius + (t + 1) / 2;      // the box holds every pixel of the mark
     if (pr < -R || pr >= (long long)a.H + R || pc < -R || pc >= (long long)a.W + R) return;
     const int side = 2 * R + 1, r2 = a.radius * a.radius;
@@ -283,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void render_points_kernel(const PointArgs
         const bool on = t < 0 ? d2 <= r2 : (in2 <= 4 * d2 && 4 * d2 <= out2);
         const int r = (int)pr + dr, c = (int)pc + dc;
         if (!on || r < 0 || r >= a.H || c < 0 || c >= a.W) continue;
-        uint8_t* q = a.canvas + (((long long)lo * a.H + r) * a.W + c) * 3;
+        uint8_t* q = a.canvas + (((long long)n * a.H + r) * a.W + c) * 3;
         q[0] = (uint8_t)a.rgb, q[1] = (uint8_t)(a.rgb >> 8), q[2] = (uint8_t)(a.rgb >> 16);
     }
 }
@@ -333,7 +317,7 @@ extern "C" int cs_render_points(uint8_t* canvas_hwc, int N, int H, int W, const 
     CS_CHECK_ARG(canvas_hwc && off && (pts || P == 0), "render_points: NULL argument");
     CS_CHECK_ARG(aligned(pts, 8) && aligned(off, 8) && aligned(limit, 4), "render_points: misaligned argument");
     if (P == 0) return CS_OK;
-    const PointArgs a{canvas_hwc, pts, off, limit, P, N, H, W, radius, thickness, flags & CS_RENDER_POINTS_XY ? 1 : 0,
+    const PointArgs a{canvas_hwc, {pts, off, limit, P, flags & CS_RENDER_POINTS_XY ? 1 : 0}, N, H, W, radius, thickness,
                       flags & CS_RENDER_POINTS_TAIL ? 1 : 0, (uint32_t)rgb};
     const unsigned blocks = (unsigned)((P + kThreads / 64 - 1) / (kThreads / 64));
     hipLaunchKernelGGL(render_points_kernel, dim3(blocks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);

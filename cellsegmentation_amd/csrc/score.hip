@@ -18,6 +18,7 @@
 // Images share nothing and every reduction is a minimum of distinct integers: the result does not depend on scheduling.
 #include <limits.h>
 #include "cs_common.h"
+#include "cs_points.h"
 
 namespace {
 
@@ -180,8 +181,9 @@ __device__ __forceinline__ void block_path(const Image& im, int R, uint32_t radi
     }
 }
 
-// grid (N), kThreads threads.  An image whose offsets do not describe 0 <= n < 2^31 points, or whose flag words would not fit the
-// workspace, reports counts (-1, -1, -1) and touches nothing else.
+// grid (N), kThreads threads.  The detections scored are a window of the ragged point set of cs_points.h, the annotations a window
+// without limits.  An image with a window that is not ok, or whose flag words would not fit the workspace, reports counts
+// (-1, -1, -1) and touches nothing else.
 __global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restrict__ hat, const int64_t* __restrict__ hat_off,
                                                          const int32_t* __restrict__ hat_limit, const int32_t* __restrict__ gt,
                                                          const int64_t* __restrict__ gt_off, int R, uint32_t radius2, int force_block,
@@ -194,26 +196,21 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const int64_t* __restri
     __shared__ int s_sum[kWaves];
     const int n = blockIdx.x, tid = threadIdx.x;
     int32_t* counts = counts_all + 3 * (long long)n;
-    const long long h0 = hat_off[n], nh = hat_off[n + 1] - h0, g0 = gt_off[n], ng = gt_off[n + 1] - g0;
-    const long long flag0 = (g0 >> 5) + n;                                // first flag word of the image in the workspace
-    const bool bad = h0 < 0 || g0 < 0 || nh < 0 || nh > INT_MAX || ng < 0 || ng > INT_MAX ||
-                     (ng > kLdsGt && flag0 + ((ng + 31) >> 5) > ws_words);
-    if (bad) {
+    // the entry point knows the rows of neither buffer: any window of 0 <= n < 2^31 rows from a row >= 0 on is taken
+    const PointWindow hw = point_window(hat_off[n], hat_off[n + 1], LLONG_MAX, hat_limit, n);
+    const PointWindow gw = point_window(gt_off[n], gt_off[n + 1], LLONG_MAX, nullptr, n);
+    const long long flag0 = (gw.o0 >> 5) + n;                             // first flag word of the image in the workspace
+    if (!hw.ok || !gw.ok || (gw.count > kLdsGt && flag0 + (((long long)gw.count + 31) >> 5) > ws_words)) {
         if (tid < 3) counts[tid] = -1;
         return;
     }
-    const int n_hat = (int)nh;
-    int n_eff = n_hat;
-    if (hat_limit) {                                                      // Python's [:c]
-        const int c = hat_limit[n];
-        n_eff = c >= 0 ? min(c, n_hat) : max(n_hat + c, 0);
-    }
+    const int n_hat = hw.count, n_eff = hw.kept;
     Image im;
-    im.hat = hat + 2 * h0;
-    im.gt = gt + 2 * g0;
-    im.match = match ? match + h0 : nullptr;
+    im.hat = hat + 2 * hw.o0;
+    im.gt = gt + 2 * gw.o0;
+    im.match = match ? match + hw.o0 : nullptr;
     im.n_eff = n_eff;
-    im.n_gt = (int)ng;
+    im.n_gt = gw.count;
     if (match)
         for (int i = n_eff + tid; i < n_hat; i += kThreads) im.match[i] = -2;
     if (im.n_gt <= 64 && !force_block) {

@@ -1,8 +1,8 @@
 // Neighbourhood queries over integer points: a bucket grid per image and three exact queries on top of it (spatial.py is the public
-// API).  Points are (row, col) int64 rows of a ragged batch, as cs_detect_cluster leaves them; a point is LIVE when its image's
-// limit keeps it (Python's [:c], as hat_limit of cs_score_points) and it lies inside [0, H) x [0, W).  Only live points ask or
-// answer.  With H^2 + W^2 < 2^31 every squared distance fits an int32 and the key (d2 << 32) | index fits 64 bits; every result is
-// a minimum of distinct keys or a sum of integers, so nothing depends on the order in which points arrive in a bucket.
+// API).  Points are the ragged point set of cs_points.h; a point is LIVE when its image's window keeps it (point_window) and it
+// lies inside [0, H) x [0, W).  Only live points ask or answer.  With H^2 + W^2 < 2^31 every squared distance fits an int32 and the
+// key (d2 << 32) | index fits 64 bits; every result is a minimum of distinct keys or a sum of integers, so nothing depends on the
+// order in which points arrive in a bucket.
 //
 // Build, per point set (the queries; in cross mode the targets too), on square buckets of side b, nbr x nbc per image:
 //   count    one thread per row of the buffer: the row's image by bisection of the offsets, one integer atomic per live point
@@ -25,6 +25,7 @@
 #include <limits.h>
 #include "cs_common.h"
 #include "cs_block.h"
+#include "cs_points.h"
 
 namespace {
 
@@ -37,13 +38,6 @@ constexpr unsigned long long kNoKey = ~0ull;
 struct Grid {
     int N, H, W, b, nbr, nbc, nb;                  // nb = nbr * nbc
 };
-struct Points {
-    const int64_t* pts;                            // [P][2]
-    const int64_t* off;                            // [N + 1]
-    const int32_t* limit;                          // [N] or NULL
-    long long P;
-    int xy;                                        // 1: the rows are (col, row)
-};
 struct Cells {
     int32_t* cnt;                                  // [N][nb]   counts, then cursors
     int32_t* start;                                // [N][nb + 1]
@@ -53,48 +47,24 @@ struct Radii {
     int r2[kMaxRadii];
 };
 
-// rows [o0, o0 + n_eff) of the buffer are image n's points within its limit; offsets that do not describe rows of the buffer: none
-struct Span {
-    long long o0;
-    int n_eff;
-};
-__device__ __forceinline__ Span image_span(const Points& p, int n) {
-    const long long o0 = p.off[n], o1 = p.off[n + 1];
-    if (o0 < 0 || o1 < o0 || o1 > p.P || o1 - o0 > INT_MAX) return {0, 0};
-    const int cnt = (int)(o1 - o0);
-    int n_eff = cnt;
-    if (p.limit) {                                 // Python's [:c]
-        const int c = p.limit[n];
-        n_eff = c >= 0 ? min(c, cnt) : max(cnt + c, 0);
-    }
-    return {o0, n_eff};
-}
-
 // the live point in row i of the buffer: image, index within it, bucket; false = the row holds none
 struct Live {
     int n, idx, r, c, bk;
     long long o0;
 };
-__device__ __forceinline__ bool live_point(const Points& p, const Grid& g, long long i, Live& v) {
-    int lo = 0, hi = g.N;                          // the last n in [0, N] with off[n] <= i
-    if (p.off[0] > i) return false;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (p.off[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    if (p.off[hi] <= i) return false;              // beyond the last image (lo == N - 1 here, or N == hi was never lowered)
-    const Span s = image_span(p, lo);
-    const long long idx = i - s.o0;
-    if (idx < 0 || idx >= s.n_eff) return false;
+__device__ __forceinline__ bool live_point(const PointSet& p, const Grid& g, long long i, Live& v) {
+    const int n = point_image(p, g.N, i);
+    if (n < 0) return false;
+    const PointWindow w = point_window(p, n);
+    if (i - w.o0 >= w.kept) return false;
     const long long r = p.pts[2 * i + p.xy], c = p.pts[2 * i + 1 - p.xy];
     if (r < 0 || r >= g.H || c < 0 || c >= g.W) return false;
-    v.n = lo;
-    v.idx = (int)idx;
+    v.n = n;
+    v.idx = (int)(i - w.o0);
     v.r = (int)r;
     v.c = (int)c;
     v.bk = ((int)r / g.b) * g.nbc + (int)c / g.b;
-    v.o0 = s.o0;
+    v.o0 = w.o0;
     return true;
 }
 
@@ -105,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void spatial_fill_kernel(int32_t* __restr
 
 // grid (ceil(P / 256)).  SCATTER = false: cnt[n][bucket] += 1 per live point.  true: the record into its bucket's next free slot.
 template <bool SCATTER>
-__global__ __launch_bounds__(kThreads) void spatial_count_kernel(Points p, Grid g, Cells cells) {
+__global__ __launch_bounds__(kThreads) void spatial_count_kernel(PointSet p, Grid g, Cells cells) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= p.P) return;
     Live v;
@@ -163,16 +133,16 @@ struct Query {
     long long q_row0;                              // first row of the query image in the buffer
     int br, bc, q0, qn;                            // this workgroup's bucket and its records [q0, q0 + qn) of q_rec
 };
-__device__ __forceinline__ bool open_query(const Points& q, const Points& t, const Grid& g, const Cells& qc, const Cells& tc, Query& u) {
+__device__ __forceinline__ bool open_query(const PointSet& q, const PointSet& t, const Grid& g, const Cells& qc, const Cells& tc, Query& u) {
     const int n = blockIdx.x / g.nb, bk = blockIdx.x - n * g.nb;
     u.q_start = qc.start + (long long)n * (g.nb + 1);
     u.q0 = u.q_start[bk];
     u.qn = u.q_start[bk + 1] - u.q0;
     if (u.qn <= 0) return false;
-    u.q_row0 = image_span(q, n).o0;
+    u.q_row0 = point_window(q, n).o0;
     u.q_rec = qc.rec + u.q_row0;
     u.t_start = tc.start + (long long)n * (g.nb + 1);
-    u.t_rec = tc.rec + image_span(t, n).o0;
+    u.t_rec = tc.rec + point_window(t, n).o0;
     u.br = bk / g.nbc;
     u.bc = bk - u.br * g.nbc;
     return true;
@@ -181,7 +151,7 @@ __device__ __forceinline__ bool open_query(const Points& q, const Points& t, con
 // grid (N * nb).  K in {1, 2, 4, 8} keys per thread, the first k written; SELF: queries and targets are one set, a row is never
 // its own neighbour.
 template <int K, bool SELF>
-__global__ __launch_bounds__(kThreads) void spatial_nearest_kernel(Points q, Points t, Grid g, Cells qc, Cells tc, int k,
+__global__ __launch_bounds__(kThreads) void spatial_nearest_kernel(PointSet q, PointSet t, Grid g, Cells qc, Cells tc, int k,
                                                                    int32_t* __restrict__ index, int32_t* __restrict__ d2_out) {
     __shared__ int4 s_rec[kChunk];
     Query u;
@@ -277,7 +247,7 @@ __device__ __forceinline__ void walk_box(const Query& u, const Grid& g, int box,
 
 // grid (N * nb).  R = isqrt(max radius2), box = min(R, max(H, W)): the reach in pixels that picks the bucket range.
 template <bool SELF>
-__global__ __launch_bounds__(kThreads) void spatial_within_kernel(Points q, Points t, Grid g, Cells qc, Cells tc, Radii radii, int n_r, int R,
+__global__ __launch_bounds__(kThreads) void spatial_within_kernel(PointSet q, PointSet t, Grid g, Cells qc, Cells tc, Radii radii, int n_r, int R,
                                                                   int box, int32_t* __restrict__ counts,
                                                                   unsigned long long* __restrict__ pair_counts) {
     __shared__ int4 s_rec[kChunk];
@@ -355,7 +325,7 @@ struct ClusterTables {
 
 // grid (N * nb)
 template <int PASS>
-__global__ __launch_bounds__(kThreads) void spatial_cluster_walk_kernel(Points p, Grid g, Cells cells, int r2, int R, int box, int need,
+__global__ __launch_bounds__(kThreads) void spatial_cluster_walk_kernel(PointSet p, Grid g, Cells cells, int r2, int R, int box, int need,
                                                                         uint8_t* __restrict__ core, ClusterWork w) {
     __shared__ int4 s_rec[kChunk];
     Query u;
@@ -395,20 +365,14 @@ __global__ __launch_bounds__(kThreads) void spatial_cluster_walk_kernel(Points p
 }
 
 // grid (ceil(P / 256)): slot i of the record buffer belongs to the image whose rows hold it; its first start[n][nb] slots are records
-__global__ __launch_bounds__(kThreads) void spatial_cluster_stamp_kernel(Points p, Grid g, Cells cells, const uint8_t* __restrict__ core) {
+__global__ __launch_bounds__(kThreads) void spatial_cluster_stamp_kernel(PointSet p, Grid g, Cells cells, const uint8_t* __restrict__ core) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= p.P || p.off[0] > i) return;
-    int lo = 0, hi = g.N;                          // as live_point
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (p.off[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    if (p.off[hi] <= i) return;
-    const Span s = image_span(p, lo);
-    const long long slot = i - s.o0;
-    if (slot < 0 || slot >= s.n_eff || slot >= cells.start[(long long)lo * (g.nb + 1) + g.nb]) return;
-    cells.rec[i].w = core[s.o0 + cells.rec[i].z];
+    const int n = i < p.P ? point_image(p, g.N, i) : -1;
+    if (n < 0) return;
+    const PointWindow w = point_window(p, n);
+    const long long slot = i - w.o0;
+    if (slot >= w.kept || slot >= cells.start[(long long)n * (g.nb + 1) + g.nb]) return;
+    cells.rec[i].w = core[w.o0 + cells.rec[i].z];
 }
 
 // grid (P / 256 + 1), rows 0 .. P.  WRITE = false: chunk[block] = the cluster roots among the block's rows.  true, after the scan:
@@ -466,13 +430,13 @@ __device__ __forceinline__ void table_add(const ClusterTables& t, long long at, 
 }
 
 // grid (ceil(max(P, N) / 256)): thread i < N writes n_clusters[i], thread i < P the label of row i and its share of the tables
-__global__ __launch_bounds__(kThreads) void spatial_cluster_table_kernel(Points p, Grid g, ClusterWork w, int32_t* __restrict__ labels,
+__global__ __launch_bounds__(kThreads) void spatial_cluster_table_kernel(PointSet p, Grid g, ClusterWork w, int32_t* __restrict__ labels,
                                                                          uint8_t* __restrict__ core, int32_t* __restrict__ n_clusters,
                                                                          ClusterTables t) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i < g.N) {
-        const long long o0 = p.off[i], o1 = p.off[i + 1];
-        n_clusters[i] = (o0 < 0 || o1 < o0 || o1 > p.P || o1 - o0 > INT_MAX) ? 0 : w.G[o1] - w.G[o0];      // image_span's rule
+        const PointWindow win = point_window(p, (int)i);                   // not ok: o0 = count = 0
+        n_clusters[i] = w.G[win.o0 + win.count] - w.G[win.o0];
     }
     Live v = {};
     long long at = -1;                                                     // the table row this thread's point adds to, -1: none
@@ -553,7 +517,7 @@ void fill(int32_t* p, long long n, int v, hipStream_t st) {
     const long long blocks = (n + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(spatial_fill_kernel, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(kThreads), 0, st, p, n, v);
 }
-void build(const Points& p, const Grid& g, const Cells& c, hipStream_t st) {
+void build(const PointSet& p, const Grid& g, const Cells& c, hipStream_t st) {
     fill(c.cnt, (long long)g.N * g.nb, 0, st);
     const unsigned blocks = (unsigned)((p.P + kThreads - 1) / kThreads);
     if (blocks) hipLaunchKernelGGL(spatial_count_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, p, g, c);
@@ -564,7 +528,7 @@ void build(const Points& p, const Grid& g, const Cells& c, hipStream_t st) {
 // the arguments every query shares: checked, then both grids built
 struct Plan {
     Grid g;
-    Points q, t;
+    PointSet q, t;
     Cells qc, tc;
     bool self;
 };
@@ -701,7 +665,7 @@ extern "C" int cs_spatial_cluster(const int64_t* pts, const int64_t* off, const 
         return CS_OK;
     }
     char* at = reinterpret_cast<char*>(workspace);
-    const Points p = {pts, off, limit, P, 0};
+    const PointSet p = {pts, off, limit, P, 0};
     const Cells cells = carve(g, P, at);
     ClusterWork w;
     w.lab = reinterpret_cast<int32_t*>(at);
@@ -743,7 +707,7 @@ extern "C" int cs_spatial_bin_counts(const int64_t* pts, const int64_t* off, con
     CS_CHECK_ARG((reinterpret_cast<uintptr_t>(pts) & 7) == 0 && (reinterpret_cast<uintptr_t>(off) & 7) == 0 &&
                  (reinterpret_cast<uintptr_t>(out) & 3) == 0, "spatial_bin_counts: misaligned argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const Points p = {pts, off, limit, P, 0};
+    const PointSet p = {pts, off, limit, P, 0};
     const Cells c = {out, nullptr, nullptr};
     fill(out, (long long)N * g.nb, 0, st);
     const unsigned blocks = (unsigned)((P + kThreads - 1) / kThreads);

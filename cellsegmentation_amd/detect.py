@@ -44,6 +44,7 @@ import torch
 
 from . import kernels as K
 from ._args import _device, _images, _tensor
+from ._points import PointSet, ragged
 
 _ONE = 1 << 14
 _MAX_KSIZE = 31
@@ -427,14 +428,10 @@ class DetectResult:
         N = len(self.offsets) - 1
         radius2 = S.radius_squared(radius)
         points, offsets = self._per_map(points, offsets)
-        prepared = S._prepare(points, offsets, N, gt_xy)
-        limits = S._limits(self.cell_counts, N)
-        if self.device_points is None:
-            hat, off = torch.from_numpy(np.ascontiguousarray(self.points, dtype=np.int64)), torch.from_numpy(np.ascontiguousarray(self.offsets, dtype=np.int64))
-            hat, off = hat.reshape(-1, 2).to(_device()), off.to(_device())
-        else:
-            hat, off = self.device_points, self.device_offsets
-        return S._run(hat, off, int(self.offsets[-1]), prepared, limits, radius2, return_match)
+        gt = S._prepare(points, offsets, N, gt_xy)
+        pts, off = self._own_points()
+        hat = PointSet(pts, off, self.cell_counts, N, "detections").upload(_device(pts))
+        return S._run(hat, int(self.offsets[-1]), gt, radius2, return_match)
 
     def render(self, images_u8, **compose):
         """The maps' images annotated on the device -> uint8 of the images' shape: ``render.compose(images_u8, **compose)`` (mask=,
@@ -445,13 +442,12 @@ class DetectResult:
 
     def _per_map(self, points, offsets):
         """a second point set in one of the forms ``score`` lists -> (points [G, 2], offsets [N + 1] or None for a single map)"""
-        from . import score as S
         N = len(self.offsets) - 1
         if offsets is None:
             if isinstance(points, (list, tuple)):
                 if len(points) != N:
                     raise ValueError(f"{N} maps but {len(points)} point arrays")
-                points, offsets = S.ragged(points)
+                points, offsets = ragged(points)
             elif _ndim(points) == 3:
                 if points.shape[0] != N or points.shape[2] != 2:
                     raise ValueError(f"expected annotations shaped [{N}, k, 2], got {tuple(points.shape)}")
@@ -468,13 +464,12 @@ class DetectResult:
         return self.device_points, self.device_offsets
 
     def _neighbours(self, fn, image_hw, arg, other, other_offsets, other_xy, _bucket):
-        from . import score as S
         pts, off = self._own_points()
         kw = {}
         if other is not None:
             kw["other"], kw["other_offsets"] = self._per_map(other, other_offsets)
             kw["other_xy"] = other_xy
-        res = fn(pts, image_hw, arg, offsets=off, limits=S._limits(self.cell_counts, len(self.offsets) - 1), _bucket=_bucket, **kw)
+        res = fn(pts, image_hw, arg, offsets=off, limits=self.cell_counts, _bucket=_bucket, **kw)
         rows = int(self.offsets[-1])                                       # the device buffer holds spare rows after the last map's
         for name in ("index", "d2", "counts", "labels", "core", "size", "n_core", "sums", "bbox"):
             if hasattr(res, name):
@@ -512,13 +507,8 @@ class DetectResult:
         are read where they are.  ``geodesic``: ``regions.split_geodesic`` in its exact mode instead, whose cells are connected
         (a regions.GeodesicSplitResult)."""
         from . import regions as Rg
-        from . import score as S
-        N = len(self.offsets) - 1
-        if self.device_points is None:
-            pts, off = np.asarray(self.points, np.int64).reshape(-1, 2), np.asarray(self.offsets, np.int64)
-        else:
-            pts, off = self.device_points, self.device_offsets
-        return (Rg.split_geodesic if geodesic else Rg.split)(masks, pts, off, limits=S._limits(self.cell_counts, N), connectivity=connectivity)
+        pts, off = self._own_points()
+        return (Rg.split_geodesic if geodesic else Rg.split)(masks, pts, off, limits=self.cell_counts, connectivity=connectivity)
 
 
 @dataclass(frozen=True)

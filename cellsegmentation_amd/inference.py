@@ -580,7 +580,7 @@ def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
     as in ``score.score_points``) to query against instead of the detections themselves.  Both tables stay device tensors, row i
     being ``result.points[i]``; nothing synchronises."""
     from . import spatial as Sp
-    from .score import _points
+    from ._points import points as _points
     if not isinstance(result, SlideResult):
         raise TypeError("slide_neighbors: expected the SlideResult of detect_slide")
     hw = tuple(int(v) for v in result.mask.shape)

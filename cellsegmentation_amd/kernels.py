@@ -1350,27 +1350,28 @@ def regions_split_workspace(N, H, W, P, device):
     return _workspace(_lib.load().cs_regions_split_workspace, device, why, N, H, W, int(P))
 
 
+def _split_operands(what, mask, points, offsets, limits):
+    """the operand checks the two split wrappers share -> N, H, W, the contiguous point set, P, and none_if_empty: the pointer of a
+    tensor of P rows, None when P == 0 (an empty tensor has no storage to point at)"""
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise TypeError("regions kernels read uint8 [N,H,W] masks")
+    N, H, W = mask.shape
+    points, offsets, limits, _ = _point_operands(what, points, offsets, limits, N, "points", device=mask.device)
+    P = int(points.shape[0])
+    if P + H * W >= 1 << 31:
+        raise ValueError(f"{what}: {P} points and {H}x{W} pixels do not leave room for int32 labels")
+    return N, H, W, points, offsets, limits, P, (lambda x: _p(x) if P else None)
+
+
 def regions_split(mask, points, offsets, limits=None, connectivity=1, labels=None, counts=None, live=None, ws=None):
     """uint8 [N,H,W], points int64 [P,2] (row, col), offsets int64 [N+1], limits int32 [N] | None -> (labels int32 [N,H,W],
     counts int32 [N], live uint8 [P]): every foreground pixel labelled 1 + the index of the nearest live seed of its own component,
     components without one numbered after the image's seeds (cs_regions_split in include/cellseg_hip.h)"""
-    if mask.dtype != torch.uint8 or mask.dim() != 3:
-        raise TypeError("regions kernels read uint8 [N,H,W] masks")
-    N, H, W = mask.shape
-    if points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2:
-        raise TypeError("regions_split: points must be int64 [P, 2]")
-    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (N + 1,):
-        raise TypeError(f"regions_split: offsets must be int64 [{N + 1}]")
-    if limits is not None and (limits.dtype != torch.int32 or tuple(limits.shape) != (N,)):
-        raise TypeError(f"regions_split: limits must be int32 [{N}]")
-    P = int(points.shape[0])
-    if P + H * W >= 1 << 31:
-        raise ValueError(f"regions_split: {P} points and {H}x{W} pixels do not leave room for int32 labels")
+    N, H, W, points, offsets, limits, P, none_if_empty = _split_operands("regions_split", mask, points, offsets, limits)
     want = {"labels": ((N, H, W), torch.int32), "counts": ((N,), torch.int32), "live": ((P,), torch.uint8)}
     t = _regions_outputs("regions_split", want, {"labels": labels, "counts": counts, "live": live}, mask.device)
     if ws is None:
         ws = regions_split_workspace(N, H, W, P, mask.device)
-    none_if_empty = lambda x: _p(x) if P else None  # noqa: E731  (an empty tensor has no storage to point at)
     _lib.check(_lib.load().cs_regions_split(_p(mask), N, H, W, int(connectivity), none_if_empty(points), _p(offsets), _p(limits), P,
                                             _p(t["labels"]), _p(t["counts"]), none_if_empty(t["live"]), _p(ws), ws.numel(), _stream()),
                "regions_split")
@@ -1391,18 +1392,7 @@ def regions_split_geodesic(mask, points, offsets, limits=None, connectivity=1, r
     uint8 [N], ws): every foreground pixel labelled 1 + the index of the live seed of its component that is nearest along 5-7 chamfer
     paths inside the component, after ``rounds`` relaxation rounds (cs_regions_split_geodesic in include/cellseg_hip.h).  ``resume``:
     ``ws`` and the outputs are those of an earlier call with the same arguments; ``rounds`` more rounds run on them."""
-    if mask.dtype != torch.uint8 or mask.dim() != 3:
-        raise TypeError("regions kernels read uint8 [N,H,W] masks")
-    N, H, W = mask.shape
-    if points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2:
-        raise TypeError("regions_split_geodesic: points must be int64 [P, 2]")
-    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (N + 1,):
-        raise TypeError(f"regions_split_geodesic: offsets must be int64 [{N + 1}]")
-    if limits is not None and (limits.dtype != torch.int32 or tuple(limits.shape) != (N,)):
-        raise TypeError(f"regions_split_geodesic: limits must be int32 [{N}]")
-    P = int(points.shape[0])
-    if P + H * W >= 1 << 31:
-        raise ValueError(f"regions_split_geodesic: {P} points and {H}x{W} pixels do not leave room for int32 labels")
+    N, H, W, points, offsets, limits, P, none_if_empty = _split_operands("regions_split_geodesic", mask, points, offsets, limits)
     if resume and (ws is None or labels is None or counts is None or live is None):
         raise ValueError("regions_split_geodesic: resume needs the workspace and the outputs of the call it resumes")
     want = {"labels": ((N, H, W), torch.int32), "counts": ((N,), torch.int32), "live": ((P,), torch.uint8), "converged": ((N,), torch.uint8)}
@@ -1412,7 +1402,6 @@ def regions_split_geodesic(mask, points, offsets, limits=None, connectivity=1, r
                                                           "converged": converged}, mask.device)
     if ws is None:
         ws = regions_geodesic_workspace(N, H, W, P, mask.device)
-    none_if_empty = lambda x: _p(x) if P else None  # noqa: E731  (an empty tensor has no storage to point at)
     _lib.check(_lib.load().cs_regions_split_geodesic(_p(mask), N, H, W, int(connectivity), none_if_empty(points), _p(offsets), _p(limits), P,
                                                      int(rounds), int(bool(resume)), _p(t["labels"]), _p(t["counts"]),
                                                      none_if_empty(t["live"]), _p(t.get("distance")), _p(t["converged"]), _p(ws), ws.numel(),
@@ -1706,32 +1695,8 @@ def score_points(hat, hat_off, gt, gt_off, limits=None, radius2=256, want_match=
     [N+1], limits int32 [N] or None (Python's [:c] per image) -> (counts int32 [N,3] = tp, fp, fn; match int32 [T] or None) on the
     device.  match: the annotation index within the image, -1 = false positive, -2 = not scored (beyond the limit, or a row of hat
     that hat_off does not cover).  force_block (tests): the 256-thread path for images of at most 64 annotations too."""
-    def need(t, what, dtype, tail):
-        if not torch.is_tensor(t):
-            raise TypeError(f"score_points: {what} must be a torch tensor")
-        if t.dtype != dtype:
-            raise TypeError(f"score_points: {what} must be {dtype}, got {t.dtype}")
-        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
-            raise ValueError(f"score_points: {what} must be shaped [n{''.join(f', {v}' for v in tail)}], got {tuple(t.shape)}")
-        if not t.is_cuda or t.device != hat_off.device:
-            raise ValueError(f"score_points: {what} must live on the device of hat_off")
-        return t.contiguous()
-
-    if not torch.is_tensor(hat_off) or not hat_off.is_cuda:
-        raise ValueError("score_points: hat_off must be a device tensor")
-    hat_off = need(hat_off, "hat_off", torch.int64, ())
-    N = hat_off.numel() - 1
-    if N < 1 or N > 65535:
-        raise ValueError(f"score_points: a call takes 0 < N <= 65535 images, got {N}")
-    hat = need(hat, "hat", torch.int64, (2,))
-    gt = need(gt, "gt", torch.int32, (2,))
-    gt_off = need(gt_off, "gt_off", torch.int64, ())
-    if gt_off.numel() != N + 1:
-        raise ValueError(f"score_points: {N + 1} detection offsets but {gt_off.numel()} annotation offsets")
-    if limits is not None:
-        limits = need(limits, "limits", torch.int32, ())
-        if limits.numel() != N:
-            raise ValueError(f"score_points: {N} images but {limits.numel()} limits")
+    hat, hat_off, limits, N = _point_operands("score_points", hat, hat_off, limits, name="hat")
+    gt, gt_off, _, _ = _point_operands("score_points", gt, gt_off, None, N, "gt", torch.int32, hat_off.device)
     radius2 = int(radius2)
     if radius2 < 0 or radius2 >= 1 << 31:
         raise ValueError(f"score_points: radius2 must be in [0, 2^31), got {radius2}")
@@ -1753,8 +1718,12 @@ def spatial_workspace(N, H, W, bucket, P, P_other, device):
     return _workspace(_lib.load().cs_spatial_workspace, device, why, int(N), int(H), int(W), int(bucket), int(P), int(P_other))
 
 
-def _spatial_args(what, pts, off, limits, other, other_off, other_limits):
-    """the operand checks the two query wrappers share -> (pts, off, limits, other, other_off, other_limits) contiguous, N"""
+def _point_operands(what, pts, off, limits, n_images=None, name="pts", dtype=torch.int64, device=None):
+    """the operand check of one ragged point set (csrc/cs_points.h): ``pts`` dtype [P,2], ``off`` int64 [N+1], ``limits`` int32 [N] |
+    None, device tensors on the device of ``off`` -> (pts, off, limits) contiguous, N; ``n_images``, ``device``: the N it must
+    have and the device it must live on (those of the call's first set)"""
+    names = (name, "off", "limits") if name == "pts" else (name, f"{name}_off", f"{name}_limits")
+
     def need(t, name, dtype, tail):
         if not torch.is_tensor(t):
             raise TypeError(f"{what}: {name} must be a torch tensor")
@@ -1763,32 +1732,33 @@ def _spatial_args(what, pts, off, limits, other, other_off, other_limits):
         if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
             raise ValueError(f"{what}: {name} must be shaped [n{''.join(f', {v}' for v in tail)}], got {tuple(t.shape)}")
         if not t.is_cuda or t.device != off.device:
-            raise ValueError(f"{what}: {name} must live on the device of off")
+            raise ValueError(f"{what}: {name} must live on the device of {names[1]}")
         return t.contiguous()
 
-    if not torch.is_tensor(off) or not off.is_cuda:
-        raise ValueError(f"{what}: off must be a device tensor")
-    off = need(off, "off", torch.int64, ())
+    if not torch.is_tensor(off) or not off.is_cuda or (device is not None and off.device != device):
+        raise ValueError(f"{what}: {names[1]} must be a device tensor{'' if device is None else f' on {device}'}")
+    off = need(off, names[1], torch.int64, ())
     N = off.numel() - 1
     if N < 1 or N > 65535:
         raise ValueError(f"{what}: a call takes 0 < N <= 65535 images, got {N}")
-    pts = need(pts, "pts", torch.int64, (2,))
+    if n_images is not None and N != n_images:
+        raise ValueError(f"{what}: {n_images} images but {N + 1} offsets of {name}")
+    pts = need(pts, name, dtype, (2,))
     if limits is not None:
-        limits = need(limits, "limits", torch.int32, ())
+        limits = need(limits, names[2], torch.int32, ())
         if limits.numel() != N:
-            raise ValueError(f"{what}: {N} images but {limits.numel()} limits")
+            raise ValueError(f"{what}: {N} images but {limits.numel()} limits of {name}")
+    return pts, off, limits, N
+
+
+def _spatial_args(what, pts, off, limits, other, other_off, other_limits):
+    """the operand checks the two query wrappers share -> (pts, off, limits, other, other_off, other_limits) contiguous, N"""
+    pts, off, limits, N = _point_operands(what, pts, off, limits)
     if other_off is None:
         if other is not None or other_limits is not None:
             raise ValueError(f"{what}: a second point set needs its offsets")
     else:
-        other_off = need(other_off, "other_off", torch.int64, ())
-        if other_off.numel() != N + 1:
-            raise ValueError(f"{what}: {N + 1} offsets but {other_off.numel()} offsets of the second point set")
-        other = need(other, "other", torch.int64, (2,))
-        if other_limits is not None:
-            other_limits = need(other_limits, "other_limits", torch.int32, ())
-            if other_limits.numel() != N:
-                raise ValueError(f"{what}: {N} images but {other_limits.numel()} limits of the second point set")
+        other, other_off, other_limits, _ = _point_operands(what, other, other_off, other_limits, N, "other", device=off.device)
     return pts, off, limits, other, other_off, other_limits, N
 
 
@@ -1853,7 +1823,7 @@ def spatial_cluster(pts, off, H, W, bucket, radius2, min_samples, limits=None, l
     (labels int32 [P], core uint8 [P], n_clusters int32 [N], size int32 [P], n_core int32 [P], sums int64 [P,2], bbox int32 [P,4])
     on the device: DBSCAN of every image's live points; cluster c of image n is row off[n] + c of the four tables
     (cs_spatial_cluster in include/cellseg_hip.h)"""
-    pts, off, limits, _, _, _, N = _spatial_args("spatial_cluster", pts, off, limits, None, None, None)
+    pts, off, limits, N = _point_operands("spatial_cluster", pts, off, limits)
     radius2, min_samples = int(radius2), int(min_samples)
     if not 0 <= radius2 < 1 << 31:
         raise ValueError(f"spatial_cluster: radius2 must be in [0, 2^31), got {radius2}")
@@ -1875,7 +1845,7 @@ def spatial_cluster(pts, off, H, W, bucket, radius2, min_samples, limits=None, l
 def spatial_bin_counts(pts, off, H, W, bin, limits=None, out=None):
     """pts int64 [P,2] with off int64 [N+1] and limits int32 [N] | None -> int32 [N, ceil(H/bin), ceil(W/bin)] on the device: the live
     points per square bin (cs_spatial_bin_counts in include/cellseg_hip.h)"""
-    pts, off, limits, _, _, _, N = _spatial_args("spatial_bin_counts", pts, off, limits, None, None, None)
+    pts, off, limits, N = _point_operands("spatial_bin_counts", pts, off, limits)
     bin = int(bin)
     if bin < 1:
         raise ValueError(f"spatial_bin_counts: bin must be positive, got {bin}")
@@ -2100,11 +2070,7 @@ def render_points(canvas_u8, pts, off, limits=None, radius=4, color=(255, 0, 0),
     rgb = _render_rgb("render_points", "color", color)
     if not canvas_u8.is_cuda:
         raise ValueError("render_points: the canvas must be a device tensor")
-    pts, off, limits, _, _, _, n = _spatial_args("render_points", pts, off, limits, None, None, None)
-    if off.device != canvas_u8.device:
-        raise ValueError("render_points: off must live on the device of the canvas")
-    if n != N:
-        raise ValueError(f"render_points: {N} images but {n + 1} offsets")
+    pts, off, limits, _ = _point_operands("render_points", pts, off, limits, N, device=canvas_u8.device)
     if tail and limits is None:
         raise ValueError("render_points: tail draws the points from limits[n] on: it needs limits")
     P = int(pts.shape[0])

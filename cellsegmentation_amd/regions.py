@@ -290,30 +290,18 @@ class SplitResult:
 
 
 def _seeds(points, offsets, limits, N, H, W):
-    """the seed arguments of ``split`` -> (points [P, 2], offsets [N + 1], limits [N] or None), each a host numpy array or a device
-    tensor as given; argument errors only, no device work.  Host points are checked against the image, device points cannot be."""
-    from . import score as S
-    if isinstance(points, (list, tuple)) and offsets is None:
-        if len(points) != N:
-            raise ValueError(f"split: {N} images but {len(points)} point arrays")
-        pts, off, on_device = *S.ragged(points), False
-    else:
-        pts, is_torch = S._points(points, "points")
-        on_device = is_torch and pts.is_cuda
-        if is_torch and not on_device:
-            pts = pts.numpy()
-        if offsets is None:
-            if N != 1:
-                raise ValueError(f"split: {N} images: pass one point array per image, or offsets")
-            offsets = np.asarray([0, pts.shape[0]], np.int64)
-        off_host, off_dev = S._offsets(offsets, pts.shape[0], N, "offsets")
-        off = off_dev if off_host is None else off_host
-    if pts.shape[0] + H * W > _MAX_PIXELS:
-        raise ValueError(f"split: {pts.shape[0]} points and {H}x{W} pixels do not leave room for int32 labels")
-    if not on_device and pts.size:
+    """the seed arguments of ``split`` -> their PointSet; argument errors only, no device work.  Host points are checked against the
+    image, device points cannot be."""
+    from ._points import PointSet
+    seeds = PointSet(points, offsets, limits, N, "split", per_image=isinstance(points, (list, tuple)) and offsets is None,
+                     max_images=N)                                        # any N: split serves the batch in chunks
+    pts = seeds.pts
+    if seeds.rows + H * W > _MAX_PIXELS:
+        raise ValueError(f"split: {seeds.rows} points and {H}x{W} pixels do not leave room for int32 labels")
+    if not seeds.on_device and pts.size:
         if int(pts[:, 0].min()) < 0 or int(pts[:, 0].max()) >= H or int(pts[:, 1].min()) < 0 or int(pts[:, 1].max()) >= W:
             raise ValueError(f"split: a point lies outside the {H}x{W} image")
-    return pts, off, S._limits(limits, N)
+    return seeds
 
 
 def split(m, points, offsets=None, limits=None, connectivity=1):
@@ -360,17 +348,14 @@ def _split_args(m, points, offsets, limits, connectivity, what):
     shape = tuple(getattr(m, "shape", ()))
     if len(shape) in (2, 3) and min(shape) > 0:
         D._check_dt_shape(shape)                                         # before the mask is copied anywhere
-        pts, off, lim = _seeds(points, offsets, limits, 1 if len(shape) == 2 else shape[0], shape[-2], shape[-1])
+        seeds = _seeds(points, offsets, limits, 1 if len(shape) == 2 else shape[0], shape[-2], shape[-1])
     t, two_d = _as_masks(m, what)
-    dev = t.device
-
-    def up(x, dtype):
-        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(device=dev, dtype=dtype).contiguous()
-
-    pts, off = up(pts, torch.int64), up(off, torch.int64)
-    lim = None if lim is None else up(lim, torch.int32)
-    n_seeds = (off[1:] - off[:-1]).clamp(0, pts.shape[0])                 # S' as the kernel forms it
+    seeds.upload(t.device)
+    pts, off, lim = seeds.pts_dev, seeds.off_dev, seeds.lim_dev
+    # S' as the kernel forms it (point_window of csrc/cs_points.h): offsets that do not describe rows of the buffer leave no seeds
+    lo, hi = off[:-1], off[1:]
+    n_seeds = hi - lo
+    n_seeds = n_seeds.masked_fill((lo | n_seeds | (pts.shape[0] - hi)) < 0, 0)     # any of lo, hi - lo, P - hi negative: none
     if lim is not None:
         n_seeds = torch.where(lim >= 0, torch.minimum(lim.to(torch.int64), n_seeds), (n_seeds + lim).clamp(min=0))
     return conn, t, two_d, pts, off, lim, n_seeds.to(torch.int32)

@@ -33,6 +33,7 @@ import torch
 
 from . import kernels as K
 from ._args import _device, _tensor
+from ._points import PointSet
 from .tissue import _rgb
 
 MAX_RADIUS = K.RENDER_MAX_RADIUS
@@ -142,28 +143,13 @@ def compose(images_u8, mask=None, heat=None, threshold=None, colormap=None, inve
 
 
 def _point_args(what, points, offsets, limits, N, tail):
-    """the points of N images in the forms ``regions.split`` takes them (its own host checks, minus the one that keeps points
-    inside the image) -> (points, offsets, limits or None), host numpy arrays or device tensors as given"""
-    from . import score as S
+    """the points of N images in the forms ``regions.split`` takes them -> their PointSet (nothing keeps them inside the image)"""
     # a sequence is one point array per image, as in regions.split; for ONE image it may also be that image's (row, col) pairs
-    if isinstance(points, (list, tuple)) and offsets is None and (N != 1 or (len(points) and np.ndim(points[0]) == 2)):
-        if len(points) != N:
-            raise ValueError(f"{what}: {N} images but {len(points)} point arrays")
-        pts, off = S.ragged(points)
-    else:
-        pts, is_torch = S._points(points, "points")
-        if is_torch and not pts.is_cuda:
-            pts = pts.numpy()
-        if offsets is None and N != 1:
-            raise ValueError(f"{what}: {N} images: pass one point array per image, or offsets")
-        off_host, off_dev = S._offsets(offsets, pts.shape[0], N, "offsets")
-        off = off_dev if off_host is None else off_host
-    if pts.shape[0] >= 1 << 31:
-        raise ValueError(f"{what}: a call takes fewer than 2^31 points")
-    lim = S._limits(limits, N)
-    if tail and lim is None:
+    per_image = isinstance(points, (list, tuple)) and offsets is None and (N != 1 or (len(points) and np.ndim(points[0]) == 2))
+    ps = PointSet(points, offsets, limits, N, what, per_image=per_image)
+    if tail and ps.lim is None:
         raise ValueError(f"{what}: tail draws the points from limits[n] on: it needs limits")
-    return pts, off, lim
+    return ps
 
 
 def _check_mark(what, radius, thickness):
@@ -195,18 +181,12 @@ def draw_points(canvas_u8, points, offsets=None, limits=None, radius=4, color=(2
         raise ValueError(f"draw_points: a call takes up to 65535 images of fewer than 2^31 pixels in all, got {(N, H, W)}")
     _check_mark(what, radius, thickness)
     K._render_rgb(what, "color", color)
-    pts, off, lim = _point_args(what, points, offsets, limits, N, tail)
+    ps = _point_args(what, points, offsets, limits, N, tail)
     if not canvas_u8.is_cuda or not canvas_u8.is_contiguous():
         raise ValueError("draw_points: the canvas must be a contiguous device tensor")
-    dev = canvas_u8.device
-
-    def up(x, dtype):
-        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(device=dev, dtype=dtype).contiguous()
-
-    if pts.shape[0]:
-        K.render_points(c4, up(pts, torch.int64), up(off, torch.int64), None if lim is None else up(lim, torch.int32), int(radius), color,
-                        int(thickness), xy=bool(xy), tail=bool(tail))
+    if ps.rows:
+        ps.upload(canvas_u8.device)
+        K.render_points(c4, ps.pts_dev, ps.off_dev, ps.lim_dev, int(radius), color, int(thickness), xy=bool(xy), tail=bool(tail))
     return canvas_u8
 
 
@@ -266,8 +246,8 @@ def dotting(img, points, radius=4, color=(255, 0, 0), thickness=-1):
     ``img`` is drawn on in place, as ``cv2.circle`` draws on its argument; a host image is copied to the device first."""
     _check_mark("dotting", radius, thickness)
     K._render_rgb("dotting", "color", color)
-    pts, off, _ = _point_args("dotting", points, None, None, 1, False)
-    return draw_points(_canvas(img, "dotting", copy=False), pts, off, radius=radius, color=color, thickness=thickness, xy=True)
+    pts = _point_args("dotting", points, None, None, 1, False).pts
+    return draw_points(_canvas(img, "dotting", copy=False), pts, radius=radius, color=color, thickness=thickness, xy=True)
 
 
 def _dots(canvas, grids, discarded):
@@ -281,22 +261,21 @@ def _dots(canvas, grids, discarded):
 def locate_cells(image, grids, discarded_grids=None):
     """utils/image_processing.py:37-49 for an image already in memory -> device uint8 ``[H, W, 3]``, a copy of ``image`` with a red
     filled dot of radius 4 at every (row, col) of ``grids``, then a blue one at every discarded point, in that order."""
-    g = _point_args("locate_cells", grids, None, None, 1, False)[0]
-    d = None if discarded_grids is None else _point_args("locate_cells", discarded_grids, None, None, 1, False)[0]
+    g = _point_args("locate_cells", grids, None, None, 1, False).pts
+    d = None if discarded_grids is None else _point_args("locate_cells", discarded_grids, None, None, 1, False).pts
     return _dots(_canvas(image, "locate_cells", copy=True), g, d)
 
 
 def render_detections(result, images_u8, **compose_args):
     """``DetectResult.render``: ``compose(images_u8, **compose_args)``, then the kept points of every map (``cell_counts`` as the
     limit) as red dots and the discarded ones as blue dots, read from the result's device points where it has them."""
-    from . import score as S
     N = len(result.offsets) - 1
     t, one = _images_arg(images_u8, "render")
     if t.shape[0] != N:
         raise ValueError(f"render: {N} maps but {t.shape[0]} images")
     canvas = compose(images_u8, **compose_args)
     pts, off = result._own_points()
-    limits = S._limits(result.cell_counts, N)
+    limits = result.cell_counts
     draw_points(canvas, pts, off, limits, radius=4, color=RED)
     if limits is not None:
         draw_points(canvas, pts, off, limits, radius=4, color=BLUE, tail=True)

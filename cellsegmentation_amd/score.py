@@ -23,9 +23,7 @@ import torch
 
 from . import kernels as K
 from ._args import _device
-
-_I32 = (-(1 << 31), (1 << 31) - 1)
-_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+from ._points import _I32, PointSet, ragged  # noqa: F401  (ragged: the tools build their batches with score.ragged)
 
 
 def precision_recall(tp, fp, fn, return_f1=False):
@@ -74,104 +72,24 @@ def radius_squared(radius):
     return int(r2)
 
 
-def _points(x, what):
-    """-> ([n, 2] integer numpy array or torch tensor, is_torch); an empty 1-D array (``np.asarray([])``) is no points."""
-    if not torch.is_tensor(x):
-        x = np.asarray(x)
-        if x.size == 0 and x.ndim <= 2:
-            return np.zeros((0, 2), np.int64), False
-    if x.ndim != 2 or x.shape[1] != 2:
-        raise ValueError(f"{what}: expected points shaped [n, 2], got shape {tuple(x.shape)}")
-    if torch.is_tensor(x):
-        if x.dtype not in _INT_DTYPES:
-            raise TypeError(f"{what}: expected integer coordinates, got {x.dtype}")
-        return x, True
-    if x.dtype.kind not in "iu":
-        raise TypeError(f"{what}: expected integer coordinates, got {x.dtype}")
-    if x.dtype == np.uint64 and x.size and int(x.max()) > np.iinfo(np.int64).max:
-        raise ValueError(f"{what}: a coordinate does not fit int64")
-    return x, False
-
-
-def _offsets(off, n_points, n_images, what):
-    """offsets (None = one image; numpy / sequence / torch, host or device) -> (host int64 array or None, device tensor or None)"""
-    if off is None:
-        return np.asarray([0, n_points], np.int64), None
-    if torch.is_tensor(off):
-        if off.dtype not in _INT_DTYPES or off.dim() != 1:
-            raise TypeError(f"{what}: expected a 1-D integer tensor")
-        if off.is_cuda:
-            if n_images is not None and off.numel() != n_images + 1:
-                raise ValueError(f"{what}: expected {n_images + 1} offsets, got {off.numel()}")
-            return None, off.to(torch.int64)
-        off = off.numpy()
-    off = np.asarray(off)
-    if off.ndim != 1 or off.dtype.kind not in "iu" or len(off) < 2:
-        raise ValueError(f"{what}: expected a 1-D integer sequence of N + 1 offsets")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != n_points or np.any(np.diff(off) < 0):
-        raise ValueError(f"{what}: offsets must rise from 0 to the number of points ({n_points})")
-    if n_images is not None and len(off) != n_images + 1:
-        raise ValueError(f"{what}: expected {n_images + 1} offsets, got {len(off)}")
-    return off, None
-
-
-def ragged(per_image):
-    """a sequence of N per-image point arrays ([k, 2], or empty) -> (points [sum k, 2], offsets int64 [N + 1]), on the host"""
-    arrs = []
-    for i, a in enumerate(per_image):
-        a, is_torch = _points(a, f"points of image {i}")
-        arrs.append(a.cpu().numpy() if is_torch else a)
-    off = np.zeros(len(arrs) + 1, np.int64)
-    if arrs:
-        np.cumsum([len(a) for a in arrs], out=off[1:])
-    pts = np.concatenate([a.astype(np.int64) for a in arrs]) if arrs else np.zeros((0, 2), np.int64)
-    return pts, off
-
-
-def _limits(limits, n_images):
-    """None, one count or one per image -> host int32 [N] (or a device tensor as given) with Python's [:c] meaning kept"""
-    if limits is None:
-        return None
-    if torch.is_tensor(limits) and limits.is_cuda:
-        if limits.dtype not in _INT_DTYPES or limits.dim() != 1 or limits.numel() != n_images:
-            raise ValueError(f"limits: expected {n_images} integers")
-        return limits
-    lim = np.asarray(limits.numpy() if torch.is_tensor(limits) else limits)
-    if lim.dtype.kind not in "iu":
-        raise TypeError(f"limits: expected integers, got {lim.dtype}")
-    if lim.ndim == 0:
-        lim = np.full(n_images, int(lim))
-    if lim.shape != (n_images,):
-        raise ValueError(f"limits: expected one count or {n_images} counts, got shape {lim.shape}")
-    return np.clip(lim.astype(np.int64), *_I32).astype(np.int32)          # clipping keeps the slice's meaning: n_hat < 2^31
-
-
 def _prepare(points, offsets, n_images, gt_xy):
-    """annotations -> (gt host int32 array or device tensor [G, 2] (row, col), offsets host / device); no device work"""
-    gt, gt_torch = _points(points, "points")
-    gt_off, gt_off_dev = _offsets(offsets, gt.shape[0], n_images, "offsets")
-    if gt_torch and gt.is_cuda:
-        gt = gt.flip(1) if gt_xy else gt
-        return gt, gt_off, gt_off_dev
-    g = gt.numpy() if gt_torch else gt
+    """annotations -> their PointSet with (row, col) rows, host rows as int32; no device work"""
+    gt = PointSet(points, offsets, None, n_images, "points")
+    if gt.on_device:
+        gt.pts = gt.pts.flip(1) if gt_xy else gt.pts
+        return gt
+    g = gt.pts
     if g.size and (int(g.min()) < _I32[0] or int(g.max()) > _I32[1]):
         raise ValueError("points: an annotation coordinate does not fit int32")
     g = g.astype(np.int32)
-    return np.ascontiguousarray(g[:, ::-1] if gt_xy else g), gt_off, gt_off_dev
+    gt.pts = np.ascontiguousarray(g[:, ::-1] if gt_xy else g)
+    return gt
 
 
-def _run(hat_dev, hat_off_dev, n_hat_rows, prepared, limits, radius2, return_match, force_block=False):
-    """device detections + prepared annotations -> ScoreResult (one copy of the counts to the host, one of match if asked for)"""
-    dev = hat_dev.device
-    gt, gt_off, gt_off_dev = prepared
-
-    def up(x, dtype):
-        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        return t.to(device=dev, dtype=dtype).contiguous()
-
-    counts, match = K.score_points(hat_dev, hat_off_dev, up(gt, torch.int32), gt_off_dev.to(dev) if gt_off is None else up(gt_off, torch.int64),
-                                   None if limits is None else up(limits, torch.int32), radius2, want_match=return_match,
+def _run(hat, n_hat_rows, gt, radius2, return_match, force_block=False):
+    """uploaded detections + prepared annotations -> ScoreResult (one copy of the counts to the host, one of match if asked for)"""
+    gt.upload(hat.pts_dev.device, torch.int32)
+    counts, match = K.score_points(hat.pts_dev, hat.off_dev, gt.pts_dev, gt.off_dev, hat.lim_dev, radius2, want_match=return_match,
                                    force_block=force_block)
     c = counts.cpu().numpy().astype(np.int64)
     if c.min(initial=0) < 0:
@@ -192,17 +110,10 @@ def score_points(points_hat, points, hat_offsets=None, offsets=None, limits=None
     (what ``DetectResult.per_image`` does with a regression count); detections beyond it are not scored.  ``radius``: a
     non-negative number, the reference's CELL_RADIUS_PXS = 16.  ``_force_block`` (tests) takes the 256-thread path at any size."""
     radius2 = radius_squared(radius)
-    hat, hat_torch = _points(points_hat, "points_hat")
-    hat_off, hat_off_dev = _offsets(hat_offsets, hat.shape[0], None, "hat_offsets")
-    n_images = (len(hat_off) if hat_off is not None else hat_off_dev.numel()) - 1
-    if n_images > 65535:
-        raise ValueError(f"score_points: a call takes at most 65535 images, got {n_images}")
-    prepared = _prepare(points, offsets, n_images, gt_xy)
-    lim = _limits(limits, n_images)
-    dev = _device(points_hat, points, hat_offsets, offsets)
-    hat_dev = (hat if hat_torch else torch.from_numpy(np.ascontiguousarray(hat.astype(np.int64)))).to(device=dev, dtype=torch.int64).contiguous()
-    off_dev = hat_off_dev.to(dev) if hat_off is None else torch.from_numpy(hat_off).to(dev)
-    return _run(hat_dev, off_dev, hat.shape[0], prepared, lim, radius2, return_match, _force_block)
+    hat = PointSet(points_hat, hat_offsets, limits, None, "points_hat")
+    gt = _prepare(points, offsets, hat.n_images, gt_xy)
+    hat.upload(_device(points_hat, points, hat_offsets, offsets))
+    return _run(hat, hat.rows, gt, radius2, return_match, _force_block)
 
 
 def get_prf1(points_hat, points):

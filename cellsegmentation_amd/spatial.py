@@ -27,7 +27,8 @@ import torch
 
 from . import kernels as K
 from ._args import _device
-from .score import _limits, _offsets, _points, radius_squared
+from ._points import PointSet
+from .score import radius_squared
 
 THREADS = 256                  # workgroup width of the query kernels           (cs_spatial_threads)
 CHUNK = 512                    # candidate records staged in LDS at a time       (cs_spatial_chunk)
@@ -149,40 +150,13 @@ def _check_bucket(_bucket, H, W, n_images):
     return b
 
 
-class _PointSet:
-    """One checked point set: nothing here touches the device until ``upload``."""
-
-    def __init__(self, points, offsets, limits, n_images, what):
-        self.pts, self.is_torch = _points(points, what)
-        self.off, self.off_dev = _offsets(offsets, self.pts.shape[0], n_images, f"{what} offsets")
-        self.n_images = (len(self.off) if self.off is not None else self.off_dev.numel()) - 1
-        if self.n_images < 1 or self.n_images > 65535:
-            raise ValueError(f"{what}: a call takes 1 to 65535 images, got {self.n_images}")
-        self.lim = _limits(limits, self.n_images)
-        if not self.is_torch and self.pts.size and self.pts.dtype == np.uint64:
-            self.pts = self.pts.astype(np.int64)                           # _points has checked that it fits
-        self.rows = int(self.pts.shape[0])
-        if self.rows >= 1 << 31:
-            raise ValueError(f"{what}: a call takes fewer than 2^31 points")
-
-    def upload(self, dev):
-        pts = self.pts if self.is_torch else torch.from_numpy(np.ascontiguousarray(self.pts.astype(np.int64)))
-        self.pts_dev = pts.to(device=dev, dtype=torch.int64).contiguous()
-        self.off_dev = self.off_dev.to(dev) if self.off is None else torch.from_numpy(self.off).to(dev)
-        lim = self.lim
-        if lim is not None:
-            lim = (lim if torch.is_tensor(lim) else torch.from_numpy(lim)).to(device=dev, dtype=torch.int32).contiguous()
-        self.lim_dev = lim
-        return self
-
-
 def _sets(what, points, offsets, limits, other, other_offsets, other_limits, other_xy):
-    q = _PointSet(points, offsets, limits, None, f"{what}: points")
+    q = PointSet(points, offsets, limits, None, f"{what}: points")
     if other is None:
         if other_offsets is not None or other_limits is not None or other_xy:
             raise ValueError(f"{what}: other_offsets, other_limits and other_xy describe `other`, which was not given")
         return q, None
-    return q, _PointSet(other, other_offsets, other_limits, q.n_images, f"{what}: other")
+    return q, PointSet(other, other_offsets, other_limits, q.n_images, f"{what}: other")
 
 
 def _bucket_for(_bucket, H, W, q, t, reach=0):
@@ -259,7 +233,7 @@ def cluster(points, image_hw, eps, min_samples=5, offsets=None, limits=None, _bu
     r2 = radius_squared(eps)
     if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 1 <= min_samples < 1 << 31:
         raise ValueError(f"cluster: min_samples must be an integer in 1..2^31 - 1, got {min_samples!r}")
-    q = _PointSet(points, offsets, limits, None, "cluster: points")
+    q = PointSet(points, offsets, limits, None, "cluster: points")
     b = _bucket_for(_bucket, H, W, q, None, reach=min(math.isqrt(r2), max(H, W)))
     _upload(q, None, points, offsets)
     out = K.spatial_cluster(q.pts_dev, q.off_dev, H, W, b, r2, int(min_samples), limits=q.lim_dev)
@@ -272,7 +246,7 @@ def bin_counts(points, image_hw, bin, offsets=None, limits=None):
     H, W = check_image_hw(image_hw)
     if isinstance(bin, bool) or not isinstance(bin, (int, np.integer)) or bin < 1:
         raise ValueError(f"bin_counts: bin must be a positive integer, got {bin!r}")
-    q = _PointSet(points, offsets, limits, None, "bin_counts: points")
+    q = PointSet(points, offsets, limits, None, "bin_counts: points")
     if q.n_images * n_buckets(H, W, int(bin)) > MAX_BUCKETS:
         raise ValueError(f"bin_counts: {q.n_images} images of {n_buckets(H, W, int(bin))} bins exceed the {MAX_BUCKETS} of one call")
     _upload(q, None, points, offsets)

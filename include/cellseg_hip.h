@@ -676,7 +676,9 @@ int cs_regions_measure(const uint8_t* mask, const uint8_t* intensity, int N, int
  * cs_regions_split         : points int64 [P][2] = (row, col) with offsets int64 [N + 1] are out_pts / out_off of cs_detect_cluster as
  *                            they are: image n owns points[offsets[n] .. offsets[n + 1]), and points may hold more rows than
  *                            offsets[N].  limits (int32 [N], or NULL) applies Python's slice [:c] to image n's points as hat_limit of
- *                            cs_score_points does; the S'_n points it keeps are the seeds.  Seed k (0-based within its image) is live
+ *                            cs_score_points does; the S'_n points it keeps are the seeds.  An image whose offsets do not describe
+ *                            rows of the buffer (offsets[n] < 0, a negative count, offsets[n + 1] > P) has no seeds: S'_n = 0, as
+ *                            such an image has no live point for the spatial entry points.  Seed k (0-based within its image) is live
  *                            when it lies inside the image on a foreground pixel; live uint8 [P] reports that for every row of
  *                            points (0 for the rows that are no seed of any image), and a dead seed owns nothing.  labels int32
  *                            [N][H][W]: 0 on the background; 1 + k on a foreground pixel whose component holds a live seed, k being
