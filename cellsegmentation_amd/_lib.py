@@ -191,6 +191,9 @@ _SIGNATURES = {
     "cs_regions_match_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cs_regions_overlap_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cs_regions_overlap_labels": (c_int, [_P, _P] + [c_int] * 6 + [_P] * 13 + [c_size_t, _P]),
+    "cs_regions_adjacency_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "cs_regions_adjacency_labels": (c_int, [_P] + [c_int] * 6 + [_P] * 10 + [c_size_t, _P]),
+    "cs_regions_seed_labels": (c_int, [_P, _P, _P, c_longlong, c_int, c_int, c_int, _P, _P]),
     "cs_regions_hausdorff_stage_runs": (c_int, []),
     "cs_regions_hausdorff_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_hausdorff_labels": (c_int, [_P, _P] + [c_int] * 5 + [_P] * 7 + [c_size_t, _P]),

@@ -26,6 +26,10 @@
 //             and an exact 64-bit integer test per pred label
 //   overlap   the same two images: every (pred, truth) pair that shares a pixel with its count, in a per-image hash table filled by
 //             one walk, and from it every label's partner of largest IoU / largest intersection (integer maxima under a total order)
+//   adjacency one label image against its own shifted self: every pair of labels that shares a pixel side (or corner) with the
+//             counts, in overlap's hash table filled by one walk over three rows at a time, per label the sides shared with other
+//             labels, with the background and with the image edge, and the neighbour of longest contact; seed_labels paints a
+//             ragged point set into the label image that the Voronoi graph of the points is read from
 //   hausdorff the same two images and overlap's partners: the squared Hausdorff distance of every object to its partner, one
 //             workgroup per pair, the target's horizontal runs staged in LDS and every pixel of the source held against them
 //   split     every foreground pixel goes to the nearest seed point of ITS OWN component (squared distance, then seed index), a
@@ -1010,6 +1014,179 @@ __global__ __launch_bounds__(256) void overlap_finish_kernel(int N, Overlap t) {
     }
 }
 
+// ---- one label image against its own shifted self: which labels touch which -------------------------------------------------------
+// A pixel's id is its label where 1 <= label <= cap, else 0.  An interior side is an unordered pair of 4-adjacent pixels, an
+// exterior side a pixel side on the image edge.  sides(a, b), a < b both positive: the interior sides with ids {a, b}; corners(a, b)
+// (CONN 2 only): the diagonal pixel pairs {(r, c), (r + 1, c + 1)} and {(r, c + 1), (r + 1, c)} with ids {a, b}.  The pairs live in
+// overlap's hash table, key (a << 32) | b, with two count arrays; a slot exists iff one of its two counts is positive.  Per label:
+// background = interior sides with ids {a, 0}, outside = exterior sides of a's pixels, contact = the sum of sides over a's pairs,
+// n_neighbors = a's pairs, partner = the pair of largest sides, ties to the lower label.
+struct Adjacency {
+    int32_t* maxlab;                // [N] or NULL: the largest label, also above cap
+    int32_t* n_pairs;               // [N]  occupied slots
+    int32_t* dropped;               // [N]  runs that found no slot
+    int32_t* n_neighbors;           // [N][cap]
+    int32_t* contact;               // [N][cap]
+    int32_t* background;            // [N][cap]
+    int32_t* outside;               // [N][cap]
+    int32_t* partner;               // [N][cap]
+    int32_t* partner_sides;         // [N][cap]
+    unsigned long long* keys;       // [N][slots]
+    int32_t* sides;                 // [N][slots]
+    int32_t* corners;               // [N][slots]
+    unsigned long long* best;       // [N][cap]  (sides << 32) | ~partner, 0 = no neighbour
+    int cap, slots;
+};
+
+__global__ __launch_bounds__(256) void adjacency_init_kernel(int N, Adjacency t) {
+    const long long nl = (long long)N * t.cap, ns = (long long)N * t.slots;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < max(nl, ns); i += (long long)gridDim.x * 256) {
+        if (i < ns) {
+            t.keys[i] = 0;
+            t.sides[i] = 0;
+            t.corners[i] = 0;
+        }
+        if (i < nl) {
+            t.n_neighbors[i] = 0;
+            t.contact[i] = 0;
+            t.background[i] = 0;
+            t.outside[i] = 0;
+            t.best[i] = 0;
+        }
+        if (i < N) {                                                   // N <= nl
+            t.n_pairs[i] = 0;
+            t.dropped[i] = 0;
+            if (t.maxlab) t.maxlab[i] = 0;
+        }
+    }
+}
+
+// A wave holds its 64 columns of rows r - 1, r, r + 1 (edge_kernel's access pattern).  Every interior side and every diagonal pair
+// is counted by exactly one pixel: the left one of a horizontal side, the upper one of a vertical side, and pixel (r, c) for the two
+// diagonals of the 2 x 2 block whose top left corner it is.  What a row adds to a pair goes out per run of lanes on which the two
+// ids are constant, one insert with the run's length; the background / outside tallies of a pixel are summed over the runs of
+// constant id and added once per run.
+template <int CONN>
+__global__ __launch_bounds__(256) void adjacency_walk_kernel(const int32_t* __restrict__ lab, int N, int H, int W, Adjacency t) {
+    const int lane = threadIdx.x & 63;
+    const int cap = t.cap;
+    int32_t *const n_pairs = t.n_pairs, *const dropped = t.dropped;    // (locals: see overlap_walk_kernel)
+    auto id_of = [cap](int l) { return (l >= 1 && l <= cap) ? l : 0; };
+    walk_row_segments(N, H, W, [&](int n, int r, int c, long long p) {
+        const bool in = c < W, above = r > 0, below = r < H - 1;
+        const int raw = in ? lab[p] : 0;
+        const int m = id_of(raw);
+        const int u = (in && above) ? id_of(lab[p - W]) : 0, d = (in && below) ? id_of(lab[p + W]) : 0;
+        const int raw_left = __shfl_up(raw, 1);                        // (lane 0 gets its own back)
+        if (t.maxlab && raw > 0 && (lane == 0 || raw != raw_left)) raise_to(t.maxlab + n, raw);
+        int left = __shfl_up(m, 1), right = __shfl_down(m, 1), dr = __shfl_down(d, 1);   // a lane with c >= W carries 0
+        if (lane == 0) left = c > 0 ? id_of(lab[p - 1]) : 0;
+        if (lane == 63) {
+            const bool has = c + 1 < W;
+            right = has ? id_of(lab[p + 1]) : 0;
+            dr = (has && below) ? id_of(lab[p + W + 1]) : 0;
+        }
+        if (__ballot((m | right) != 0) == 0) return;                    // every side and corner counted here has m or right in it
+        const bool has_right = c + 1 < W;                              // (then c < W too)
+
+        int tally = 0;                                                 // outside | background << 16, at most 4 each per pixel
+        if (m > 0) {
+            tally = (int)!above + (int)!below + (int)(c == 0) + (int)!has_right;
+            tally += ((int)(c > 0 && left == 0) + (int)(has_right && right == 0) + (int)(above && u == 0) + (int)(below && d == 0)) << 16;
+        }
+        const int m_left = __shfl_up(m, 1);
+        int len;
+        const bool head = run_of(__ballot(m > 0), __ballot(m > 0 && m != m_left), lane, len);
+        tally = run_sum(tally, lane, m > 0 ? lane + len - 1 : lane);
+        if (head) {
+            const long long q = (long long)n * cap + m - 1;
+            if (tally & 0xFFFF) __hip_atomic_fetch_add(t.outside + q, tally & 0xFFFF, __ATOMIC_RELAXED, kGlobal);
+            if (tally >> 16) __hip_atomic_fetch_add(t.background + q, tally >> 16, __ATOMIC_RELAXED, kGlobal);
+        }
+
+        const long long base = (long long)n * t.slots;                 // < N slots < 2^31
+        // the runs of constant (a, b) among the lanes where `ok` and the two ids are positive and differ: one insert each
+        auto emit = [&](int a, int b, bool ok, int32_t* cnt) {
+            const bool live = ok && a > 0 && b > 0 && a != b;
+            const unsigned long long bal = __ballot(live);
+            if (bal == 0) return;
+            const int al = __shfl_up(a, 1), bl = __shfl_up(b, 1);
+            int n_run;
+            if (!run_of(bal, __ballot(live && (a != al || b != bl)), lane, n_run)) return;
+            bool fresh;
+            if (!overlap_insert(t.keys + base, cnt + base, (unsigned)t.slots - 1, min(a, b), max(a, b), n_run, &fresh))
+                __hip_atomic_fetch_add(dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
+            else if (fresh)
+                __hip_atomic_fetch_add(n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+        };
+        emit(m, d, below, t.sides);                                    // (d is 0 where c >= W)
+        emit(m, right, has_right, t.sides);
+        if (CONN == 2) {
+            emit(m, dr, has_right && below, t.corners);
+            emit(right, d, has_right && below, t.corners);
+        }
+    });
+}
+
+// One thread per slot, after the walk: both labels of the pair get a neighbour, its sides, and the atomic maximum of
+// (sides << 32) | ~other, i.e. the largest sides and among equals the lowest label.
+__global__ __launch_bounds__(256) void adjacency_reduce_kernel(long long n_slots, Adjacency t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_slots; i += (long long)gridDim.x * 256) {
+        const unsigned long long key = t.keys[i];
+        if (key == 0) continue;
+        const long long n = i / t.slots;
+        const unsigned a = (unsigned)(key >> 32), b = (unsigned)key;
+        const int s = t.sides[i];
+        const long long qa = n * t.cap + a - 1, qb = n * t.cap + b - 1;
+        __hip_atomic_fetch_add(t.n_neighbors + qa, 1, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_add(t.n_neighbors + qb, 1, __ATOMIC_RELAXED, kGlobal);
+        if (s) {
+            __hip_atomic_fetch_add(t.contact + qa, s, __ATOMIC_RELAXED, kGlobal);
+            __hip_atomic_fetch_add(t.contact + qb, s, __ATOMIC_RELAXED, kGlobal);
+        }
+        const unsigned long long hi = (unsigned long long)(unsigned)s << 32;
+        __hip_atomic_fetch_max(t.best + qa, hi | (unsigned)~b, __ATOMIC_RELAXED, kGlobal);
+        __hip_atomic_fetch_max(t.best + qb, hi | (unsigned)~a, __ATOMIC_RELAXED, kGlobal);
+    }
+}
+
+// One thread per label: the packed winner into the tables.
+__global__ __launch_bounds__(256) void adjacency_finish_kernel(long long rows, Adjacency t) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        const unsigned long long b = t.best[i];
+        t.partner[i] = b ? (int)~(unsigned)b : 0;
+        t.partner_sides[i] = (int)(b >> 32);
+    }
+}
+
+// ---- the seed label image of a point set: 0 everywhere, k + 1 at the pixel of live point k, the lowest k of a pixel -------------
+// A point is live when it is within its image's limit and inside the image.  CLAIM: the pixel is raised to ~k as an unsigned
+// number (the largest for the lowest k, never 0).  Otherwise, in a later launch: the point whose ~k the pixel holds writes k + 1.
+// k + 1 is never another point's ~k' (k + k' + 1 < 2^32 - 1), so whichever order the writes land in, only the owner writes.
+template <bool CLAIM>
+__global__ __launch_bounds__(256) void seed_labels_kernel(PointSet s, int N, int H, int W, int32_t* __restrict__ out) {
+    const long long HW = (long long)H * W;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < s.P; p += (long long)gridDim.x * 256) {
+        const int n = point_image(s, N, p);
+        if (n < 0) continue;
+        const PointWindow w = point_window(s, n);
+        const long long k = p - w.o0;
+        if (k >= w.kept) continue;
+        const long long r = s.pts[2 * p], c = s.pts[2 * p + 1];
+        if (r < 0 || r >= H || c < 0 || c >= W) continue;
+        unsigned* at = reinterpret_cast<unsigned*>(out) + (n * HW + r * W + c);
+        const unsigned mine = ~(unsigned)k;
+        if (CLAIM)
+            __hip_atomic_fetch_max(at, mine, __ATOMIC_RELAXED, kGlobal);
+        else if (__hip_atomic_load(at, __ATOMIC_RELAXED, kGlobal) == mine)
+            __hip_atomic_store(at, (unsigned)k + 1u, __ATOMIC_RELAXED, kGlobal);
+    }
+}
+
+__global__ __launch_bounds__(256) void zero_labels_kernel(long long total, int32_t* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) out[i] = 0;
+}
+
 // ---- label image against label image: squared Hausdorff distance of every object to its partner ----------------------------------
 // d2(A -> B) = max over ALL pixels a of A of min over the pixels b of B of dr^2 + dc^2; H2 = max of the two directions.  A job is a
 // pair (object, partner or candidate) and one workgroup computes both of its directions.  For A -> B the workgroup walks B's
@@ -1664,6 +1841,23 @@ size_t overlap_layout(void* w, int N, int max_pairs, Overlap* t) {
     return c.end;
 }
 
+// keys (uint64 N slots), sides, corners (int32 N slots each), then best (uint64 N cap), for the capacity of t, whose slots it sets;
+// 0 for sizes no call takes.  The pair table leads and N slots is even, so its three arrays are the first 8, the next 4 and the next
+// 4 N slots bytes with no padding between them: kernels.regions_adjacency_labels (Python) views these 16 N slots bytes as the
+// result's slot_keys / slot_sides / slot_corners.
+size_t adjacency_layout(void* w, int N, int max_pairs, Adjacency* t) {
+    const long long slots = overlap_slots(max_pairs);
+    if (!(N > 0 && N <= 65535 && t->cap >= 1 && slots > 0 && (long long)N * t->cap < (1LL << 31) && N * slots < (1LL << 31))) return 0;
+    t->slots = (int)slots;
+    const size_t ns = (size_t)N * t->slots;
+    Carve c{reinterpret_cast<uintptr_t>(w)};
+    t->keys = c.take<unsigned long long>(ns);
+    t->sides = c.take<int32_t>(2 * ns);                                // one array for the two counts: 4 N slots need not be 16-byte
+    t->corners = t->sides + ns;                                        // aligned, 8 N slots is
+    t->best = c.take<unsigned long long>((size_t)N * t->cap);
+    return c.end;
+}
+
 bool hausdorff_sizes_ok(int N, int H, int W, int cap_pred, int cap_truth) {
     return sizes_ok(N, H, W) && cap_pred >= 1 && cap_truth >= 1 && (long long)N * ((long long)cap_pred + cap_truth) < (1LL << 31) &&
            (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1) < (1LL << 31);
@@ -1955,6 +2149,63 @@ extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* tru
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(overlap_finish_kernel, dim3(grid_for(labels)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" size_t cs_regions_adjacency_workspace(int N, int capacity, int max_pairs) {
+    Adjacency t{};
+    t.cap = capacity;
+    return adjacency_layout(nullptr, N, max_pairs, &t);
+}
+
+extern "C" int cs_regions_adjacency_labels(const int32_t* labels, int N, int H, int W, int capacity, int max_pairs, int connectivity,
+                                           int32_t* counts, int32_t* n_pairs, int32_t* dropped, int32_t* n_neighbors, int32_t* contact,
+                                           int32_t* background, int32_t* outside, int32_t* partner, int32_t* partner_sides,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    Adjacency t{counts, n_pairs, dropped, n_neighbors, contact, background, outside, partner, partner_sides};
+    t.cap = capacity;
+    const int rc = check_label_pair("regions_adjacency_labels",
+                                    labels && n_pairs && dropped && n_neighbors && contact && background && outside && partner &&
+                                        partner_sides && workspace,
+                                    N, H, W, adjacency_layout(workspace, N, max_pairs, &t),
+                                    "need capacity >= 1, 1 <= max_pairs <= 2^29, N capacity < 2^31 and N slots < 2^31", workspace,
+                                    workspace_bytes);
+    if (rc != CS_OK) return rc;
+    if (connectivity != 1 && connectivity != 2) return fail("regions_adjacency_labels", "connectivity must be 1 or 2");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long ns = (long long)N * t.slots, rows = (long long)N * capacity;
+    hipLaunchKernelGGL(adjacency_init_kernel, dim3(grid_for(ns > rows ? ns : rows)), dim3(256), 0, st, N, t);
+    CS_LAUNCH_CHECK();
+    if (connectivity == 2)
+        hipLaunchKernelGGL(adjacency_walk_kernel<2>, walk_grid(N, H, W), dim3(256), 0, st, labels, N, H, W, t);
+    else
+        hipLaunchKernelGGL(adjacency_walk_kernel<1>, walk_grid(N, H, W), dim3(256), 0, st, labels, N, H, W, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(adjacency_reduce_kernel, dim3(grid_for(ns)), dim3(256), 0, st, ns, t);
+    CS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(adjacency_finish_kernel, dim3(grid_for(rows)), dim3(256), 0, st, rows, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_seed_labels(const int64_t* points, const int64_t* offsets, const int32_t* limits, long long P, int N, int H,
+                                      int W, int32_t* labels, void* stream) {
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_seed_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(P >= 0 && P < (1LL << 31), "regions_seed_labels: need 0 <= P < 2^31 rows");
+    CS_CHECK_ARG(offsets && labels && (points || P == 0), "regions_seed_labels: NULL argument");
+    CS_CHECK_ARG(((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(offsets)) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(labels) & 3) == 0, "regions_seed_labels: misaligned argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const PointSet s = {points, offsets, limits, P, 0};
+    const long long total = (long long)N * H * W;
+    hipLaunchKernelGGL(zero_labels_kernel, dim3(grid_for(total)), dim3(256), 0, st, total, labels);
+    CS_LAUNCH_CHECK();
+    if (P > 0) {
+        hipLaunchKernelGGL(seed_labels_kernel<true>, dim3(grid_for(P)), dim3(256), 0, st, s, N, H, W, labels);
+        CS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(seed_labels_kernel<false>, dim3(grid_for(P)), dim3(256), 0, st, s, N, H, W, labels);
+        CS_LAUNCH_CHECK();
+    }
     return CS_OK;
 }
 

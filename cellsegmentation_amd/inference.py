@@ -572,6 +572,28 @@ def measure_slide_cells(result, thr_u8=127, min_object_size=300, hole_area_thres
     return Rg.measure_labels(parts.labels, intensity=t, max_regions=max_regions, counts=parts.counts), parts
 
 
+def slide_contacts(result, distance=None, connectivity=1, max_pairs=None, **measure_kwargs):
+    """Which DETECTED cells of a ``SlideResult`` touch which, on the device: ``measure_slide_cells(result, connectivity=connectivity,
+    **measure_kwargs)``, whose split labels go to ``regions.adjacency_labels`` with ``counts=parts.counts`` and the region table's
+    capacity -> ``(AdjacencyTable, RegionTable, SplitResult)`` of one image.  Row k of every table is ``result.points[k]``.
+    ``distance``: cells whose gap ``morph.expand_labels`` closes at that distance count as touching (the adjacency table then
+    describes the expanded labels, the region table the cells as split).  ``connectivity`` serves the clean-up, the split and the
+    adjacency alike: with 2, cells that meet at a pixel corner are neighbours.  ``max_pairs`` as in ``adjacency_labels``; with it
+    and ``max_regions`` both integers nothing synchronises."""
+    from . import regions as Rg
+    if not isinstance(result, SlideResult):
+        raise TypeError("slide_contacts: expected the SlideResult of detect_slide")
+    conn = Rg._check_connectivity(connectivity)
+    Rg._check_max_pairs(max_pairs)
+    if distance is not None:
+        from .score import radius_squared
+        radius_squared(distance)
+    table, parts = measure_slide_cells(result, connectivity=conn, **measure_kwargs)
+    contacts = Rg.adjacency_labels(parts.labels, conn, distance=distance, max_regions=table.capacity, max_pairs=max_pairs,
+                                   counts=parts.counts)
+    return contacts, table, parts
+
+
 def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
     """Neighbourhood statistics of the detected cells of a ``SlideResult``, on the device: ``result.points`` is uploaded once and
     queried on the bucket grid of ``spatial`` with the mask's shape as the image -> ``(NeighborTable or None, WithinCounts or

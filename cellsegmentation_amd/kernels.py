@@ -1599,6 +1599,62 @@ def regions_overlap_labels(pred, truth, cap_pred, cap_truth, max_pairs, counts_p
     return t
 
 
+def regions_adjacency_workspace(N, capacity, max_pairs, device):
+    """the caller-owned scratch of one cs_regions_adjacency_labels call on N images with this capacity; it starts with the pair
+    table, which the call's result views"""
+    why = ("regions_adjacency_labels: a call takes 0 < N <= 65535 images, a capacity >= 1 and 1 <= max_pairs <= 2^29 with "
+           f"N capacity and N slots < 2^31, got {(N, capacity, max_pairs)}")
+    size = lambda *a: _lib.load().cs_regions_adjacency_workspace(*a) if 1 <= a[2] < 1 << 31 else 0  # noqa: E731  (an int argument)
+    return _workspace(size, device, why, int(N), int(capacity), int(max_pairs))
+
+
+_ADJACENCY_TABLES = ("n_neighbors", "contact", "background", "outside", "partner", "partner_sides")
+
+
+def regions_adjacency_labels(labels, capacity, max_pairs, connectivity=1, counts=None, n_pairs=None, dropped=None, n_neighbors=None,
+                             contact=None, background=None, outside=None, partner=None, partner_sides=None, want_counts=True, ws=None):
+    """int32 label image [N,H,W] -> a dict of int32 tensors: counts [N] (the largest label of every image; None with
+    ``want_counts=False``), n_pairs, dropped [N], n_neighbors, contact, background, outside, partner, partner_sides [N,capacity], and
+    the pair table itself as views of ``ws``: slot_keys int64 [N,slots] ((a << 32) | b with a < b, 0 = empty), slot_sides and
+    slot_corners int32 [N,slots] (cs_regions_adjacency_labels in include/cellseg_hip.h)."""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("regions_adjacency_labels reads int32 [N,H,W] label images")
+    N, H, W = labels.shape
+    cap, mp = int(capacity), int(max_pairs)
+    want = {name: ((N, cap), torch.int32) for name in _ADJACENCY_TABLES}
+    want.update(n_pairs=((N,), torch.int32), dropped=((N,), torch.int32))
+    if want_counts:
+        want["counts"] = ((N,), torch.int32)
+    if ws is None:
+        ws = regions_adjacency_workspace(N, cap, mp, labels.device)
+    given = {"counts": counts, "n_pairs": n_pairs, "dropped": dropped, "n_neighbors": n_neighbors, "contact": contact,
+             "background": background, "outside": outside, "partner": partner, "partner_sides": partner_sides}
+    t = _regions_outputs("regions_adjacency_labels", want, given, labels.device)
+    _lib.check(_lib.load().cs_regions_adjacency_labels(
+        _p(labels), N, H, W, cap, mp, int(connectivity), _p(t.get("counts")), _p(t["n_pairs"]), _p(t["dropped"]), _p(t["n_neighbors"]),
+        _p(t["contact"]), _p(t["background"]), _p(t["outside"]), _p(t["partner"]), _p(t["partner_sides"]), _p(ws), ws.numel(), _stream()),
+        "regions_adjacency_labels")
+    cells = N * regions_overlap_slots(mp)                              # the table leads the workspace: 8, 4 and 4 bytes per slot
+    t["slot_keys"] = ws[:8 * cells].view(torch.int64).view(N, -1)
+    t["slot_sides"] = ws[8 * cells:12 * cells].view(torch.int32).view(N, -1)
+    t["slot_corners"] = ws[12 * cells:16 * cells].view(torch.int32).view(N, -1)
+    t.setdefault("counts", None)
+    return t
+
+
+def regions_seed_labels(points, offsets, H, W, limits=None, labels=None):
+    """points int64 [P,2] (row, col) with offsets int64 [N+1] and limits int32 [N] | None -> labels int32 [N,H,W]: 0 everywhere and
+    k + 1 at the pixel of point k of its image (within the limit, inside the image), the lowest k of a pixel
+    (cs_regions_seed_labels in include/cellseg_hip.h)"""
+    points, offsets, limits, N = _point_operands("regions_seed_labels", points, offsets, limits, name="points")
+    P = int(points.shape[0])
+    labels = _regions_outputs("regions_seed_labels", {"labels": ((N, int(H), int(W)), torch.int32)}, {"labels": labels},
+                              points.device)["labels"]
+    _lib.check(_lib.load().cs_regions_seed_labels(_p(points) if P else None, _p(offsets), _p(limits), P, N, int(H), int(W), _p(labels),
+                                                  _stream()), "regions_seed_labels")
+    return labels
+
+
 def regions_hausdorff_stage_runs():
     """the horizontal runs of an object that one stage of cs_regions_hausdorff_labels holds; an object with more is taken in chunks"""
     return int(_lib.load().cs_regions_hausdorff_stage_runs())

@@ -65,6 +65,13 @@ vertex count, length, enclosed area and the length of all of the label's boundar
 in ``contour_labels``'s docstring, restated in plain loops by tests/contour_ref.py), from which ``ContourTable`` tells one-piece
 labels without holes from the others and writes GeoJSON polygons for QuPath or shapely on the host.  Holes are not traced, and
 objects whose bounding box exceeds 512 rows or columns are counted, not traced.
+
+``adjacency_labels`` (``adjacency`` for a boolean mask) relates the cells of ONE label image to each other: every pair of labels
+that shares a pixel side (with ``connectivity=2`` also a pixel corner) with the number of shared sides and corners, and per label the
+number of neighbours, the sides shared with other cells, with the background and with the image edge, and the neighbour of longest
+contact, in exact integers (``AdjacencyTable``; the rules are in ``adjacency_labels``'s docstring, restated in numpy by
+tests/adjacency_ref.py), from which ``AdjacencyTable`` forms the touching fraction in float64 and the cell graph as a COO edge list
+on the device.  ``distance=`` expands the labels first (``morph.expand_labels``), so that cells within a gap count as neighbours.
 """
 import dataclasses
 import typing
@@ -727,6 +734,193 @@ def overlap_labels(pred, truth, max_regions=None, max_pairs=None, pred_counts=No
         if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
             return table
         pairs = min(2 * pairs, most)
+
+
+@dataclasses.dataclass
+class AdjacencyTable:
+    """``adjacency_labels`` of N label images as device tensors, all int32 but the keys.  ``counts`` [N]: the largest label of every
+    image, also above ``capacity``; ``connectivity``: 1 or 2, as asked for.  ``n_pairs`` [N]: the listed pairs; ``dropped`` [N]: the
+    runs of sides or corners whose pair found no room (0 unless ``max_pairs`` was too small).  Row a - 1 of the [N, capacity] tables
+    belongs to label a: ``n_neighbors``, ``contact``, ``background``, ``outside``, ``partner``, ``partner_sides``
+    (``adjacency_labels`` has the rules).  ``slot_keys`` int64 [N, slots], ``slot_sides`` and ``slot_corners`` [N, slots]: the raw
+    pair table, key = (a << 32) | b with a < b, 0 = empty, in no particular order -- ``pairs()`` and ``edge_index()`` read it."""
+    counts: torch.Tensor
+    capacity: int
+    connectivity: int
+    n_pairs: torch.Tensor
+    dropped: torch.Tensor
+    n_neighbors: torch.Tensor
+    contact: torch.Tensor
+    background: torch.Tensor
+    outside: torch.Tensor
+    partner: torch.Tensor
+    partner_sides: torch.Tensor
+    slot_keys: torch.Tensor
+    slot_sides: torch.Tensor
+    slot_corners: torch.Tensor
+
+    def overflowed(self):
+        """device bool [N]: the image has labels above the capacity (they were taken for background), or pairs of it found no room
+        in the table (they are missing from the pair list, and n_neighbors / contact / partner are incomplete)"""
+        return (self.counts > self.capacity) | (self.dropped > 0)
+
+    def boundary(self):
+        """int32 [N, capacity] on the device: ``contact + background + outside``, the crack length of every label
+        (``ContourTable``'s ``cracks_all``)"""
+        return self.contact + self.background + self.outside
+
+    def touching_fraction(self):
+        """float64 [N, capacity] on the device: ``contact / boundary()``, the share of a cell's outline that it has in common with
+        other cells (CellProfiler's PercentTouching as a fraction); NaN where the boundary is 0 (a label without pixels)."""
+        b = self.boundary().to(torch.float64)
+        return torch.where(b > 0, self.contact.to(torch.float64) / b.clamp(min=1), torch.full_like(b, float("nan")))
+
+    def pairs(self):
+        """The listed pairs on the host: int64 arrays ``(image, a, b, sides, corners)`` with a < b, sorted by (image, a, b).  One
+        copy from the device (it synchronises)."""
+        flat = torch.cat([self.slot_keys.reshape(-1), self.slot_sides.reshape(-1).to(torch.int64),
+                          self.slot_corners.reshape(-1).to(torch.int64)]).cpu().numpy()
+        keys, sides, corners = flat.reshape(3, -1)
+        at = np.nonzero(keys)[0]
+        image, keys = at // self.slot_keys.shape[1], keys[at]
+        order = np.lexsort((keys, image))                                # a key orders by a, then b
+        return image[order], keys[order] >> 32, keys[order] & 0xFFFFFFFF, sides[at][order], corners[at][order]
+
+    def edge_index(self):
+        """The cell graph in COO form, on the device: ``(edge_index, image, sides, corners)``, int64 [2, E] = the 0-based rows
+        (a - 1, b - 1) of every listed pair, and int64 [E] each, in the order of ``pairs()``.  Made with torch ops whose output size
+        depends on the data: it may synchronise and cannot be captured into a graph."""
+        keys = self.slot_keys.reshape(-1)
+        at = torch.nonzero(keys).reshape(-1)
+        keys, image = keys[at], at // self.slot_keys.shape[1]
+        order = torch.sort(keys, stable=True).indices
+        order = order[torch.sort(image[order], stable=True).indices]
+        keys, at = keys[order], at[order]
+        edges = torch.stack([(keys >> 32) - 1, (keys & 0xFFFFFFFF) - 1])
+        return (edges, image[order], self.slot_sides.reshape(-1)[at].to(torch.int64), self.slot_corners.reshape(-1)[at].to(torch.int64))
+
+    def per_image(self):
+        """A host list of N dicts of numpy arrays: the six label tables and ``boundary`` trimmed to min(count, capacity) rows, and
+        ``pairs`` = int64 [n_pairs, 4] rows (a, b, sides, corners) sorted by (a, b).  It synchronises."""
+        cols = {k: getattr(self, k) for k in ("n_neighbors", "contact", "background", "outside", "partner", "partner_sides")}
+        cols["boundary"] = self.boundary()
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        counts = self.counts.cpu().numpy()
+        image, *rest = self.pairs()
+        listed = np.stack(rest, axis=1) if len(image) else np.zeros((0, 4), np.int64)
+        out = []
+        for n, c in enumerate(counts):
+            d = {k: v[n, :min(int(c), self.capacity)] for k, v in cols.items()}
+            d["pairs"] = listed[image == n]
+            out.append(d)
+        return out
+
+
+def adjacency_labels(labels, connectivity=1, distance=None, radius_sq=None, max_regions=None, max_pairs=None, counts=None):
+    """Which cells of a label image touch which, and what every cell's outline faces -> ``AdjacencyTable``: neighbour counts and
+    the share of the outline in contact with other cells (CellProfiler's MeasureObjectNeighbors: NumberOfNeighbors,
+    PercentTouching), and the list of touching pairs, i.e. the cell graph.
+
+    ``labels``: int32 [H, W] or [N, H, W] (numpy or torch), independent images, e.g. ``split(...).labels``.  All rules are exact
+    integers, per image:
+
+    * A pixel's id is its label when ``1 <= label <= capacity``, else 0: a label above the capacity is background here, as in
+      ``overlap_labels``; the largest label is still reported in ``counts`` and ``overflowed()`` flags the image.
+    * Every unordered pair of 4-adjacent pixels of the image is one *interior side*; a pixel side that lies on the image edge is an
+      *exterior side* of that pixel.
+    * Per pair of labels a < b, both positive: ``sides(a, b)`` is the number of interior sides whose two ids are {a, b}.
+      ``corners(a, b)`` is counted with ``connectivity=2`` only (0 otherwise): the number of unordered diagonal pixel pairs
+      {(r, c), (r + 1, c + 1)} and {(r, c + 1), (r + 1, c)} whose ids are {a, b}, whether or not the two labels also share a side.
+      A pair is *listed* iff ``sides > 0`` (connectivity 1) or ``sides + corners > 0`` (connectivity 2).
+    * Per label a (row a - 1 of the int32 [N, capacity] tables): ``n_neighbors`` = the listed pairs that contain a; ``contact`` = the
+      sum of ``sides`` over them; ``background`` = the interior sides with ids {a, 0}; ``outside`` = the exterior sides of a's pixels;
+      ``partner`` / ``partner_sides`` = the listed neighbour of largest ``sides``, ties going to the lower label, and that count (a
+      neighbour met at corners only has 0 sides); ``partner`` is 0 without a neighbour.  A label without pixels has an all-zero row.
+    * ``contact + background + outside = 4 area - 2 (interior sides with both ids a)``: ``boundary()``, which is ``cracks_all`` of
+      ``contour_labels`` for the same label.
+
+    By hand::
+
+        1 1 2      sides   (1,2)=1 (1,3)=2 (2,3)=2          background  [1, 0, 1]    n_neighbors [2, 2, 2]
+        1 3 2      corners (1,2)=1 (1,3)=2 (2,3)=2 (conn 2) outside     [4, 3, 3]    partner     [3, 3, 1]
+        0 3 3                                               contact     [3, 3, 4]    (label 3: a tie at 2 sides, the lower label)
+
+    ``distance=`` / ``radius_sq=`` (one of them, as ``morph.expand_labels`` takes them): the label image goes through
+    ``morph.expand_labels`` first, so that two cells whose gap the expansion closes touch -- CellProfiler's neighbours within a
+    distance.  ``background``, ``outside`` and the identity then refer to the EXPANDED image, not to the cells as given.
+
+    The pairs are collected as ``overlap_labels`` collects them, in a per-image hash table of ``slots`` = the smallest power of two
+    >= 2 ``max_pairs`` entries.  With ``max_regions`` and ``max_pairs`` both integers the call is four launches that depend on shape
+    and capacities alone (after those of the expansion, which are fixed by the shape too): nothing synchronises and the call can be
+    captured into a graph; pairs that find no room are counted in ``dropped``.  ``max_pairs=None`` starts from min(4 capacity,
+    4 H W), reads ``dropped.max()`` back and doubles while it is non-zero (an image has fewer than 4 H W pairs), so the table returned
+    has lost no pair.  ``max_regions=None`` finds the largest label first and reads it back (the one synchronisation); ``counts``:
+    int32 [N], the labels in use per image where the caller has them (``SplitResult.counts``).  Everything the device writes is
+    integer and independent of launch and arrival order, except the position of a pair in the raw table.  Memory besides the
+    tables: 16 N slots + 8 N capacity bytes of workspace, whose first 16 N slots bytes the result keeps."""
+    conn = _check_connectivity(connectivity)
+    _check_max_regions(max_regions)
+    _check_max_pairs(max_pairs)
+    r2 = None
+    if distance is not None or radius_sq is not None:
+        from . import morph as M
+        r2 = M._r2("adjacency_labels", distance, radius_sq, name="distance")
+    t = _as_labels(labels, "adjacency_labels")
+    n_images = 1 if t.dim() == 2 else t.shape[0]
+    if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (n_images,)):
+        raise TypeError(f"adjacency_labels: counts must be an int32 tensor of shape ({n_images},)")
+    if r2 is not None:
+        t = M.expand_labels(t, radius_sq=r2)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if not t.is_cuda:
+        t = t.to(_device())
+    t = t.contiguous()
+    N, H, W = t.shape
+    dev = t.device
+    chunks = _chunks(t)
+    own = counts is None
+    counts = torch.empty((N,), dtype=torch.int32, device=dev) if own else counts.to(dev).contiguous()
+
+    def run(cap, pairs, want):
+        tabs = {k: torch.empty((N, cap), dtype=torch.int32, device=dev) for k in K._ADJACENCY_TABLES}
+        tabs.update(n_pairs=torch.empty((N,), dtype=torch.int32, device=dev), dropped=torch.empty((N,), dtype=torch.int32, device=dev))
+        slots = []
+        for a, b in chunks:                                              # a workspace per call: the result views its pair table
+            r = K.regions_adjacency_labels(t[a:b], cap, pairs, conn, counts[a:b] if want else None,
+                                           **{k: x[a:b] for k, x in tabs.items()}, want_counts=want)
+            slots.append(tuple(r[k] for k in ("slot_keys", "slot_sides", "slot_corners")))
+        table = slots[0] if len(slots) == 1 else tuple(torch.cat([s[i] for s in slots]) for i in range(3))
+        return AdjacencyTable(counts, cap, conn, tabs["n_pairs"], tabs["dropped"], *(tabs[k] for k in K._ADJACENCY_TABLES), *table)
+
+    if max_regions is not None:
+        cap, want = int(max_regions), own
+    else:
+        if own:
+            run(1, 1, True)                                              # the pass that finds the largest labels
+        cap, want = max(1, int(counts.max())), False                     # the one synchronisation
+    if max_pairs is not None:
+        return run(cap, int(max_pairs), want)
+    most = min(4 * H * W, 1 << 29)                                       # an image has fewer pairs than sides and diagonals
+    pairs = min(4 * cap, most)
+    while True:
+        table = run(cap, pairs, want)
+        if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
+            return table
+        pairs = min(2 * pairs, most)
+
+
+def adjacency(m, connectivity=1, distance=None, radius_sq=None, max_regions=None, max_pairs=None):
+    """``adjacency_labels`` for a boolean mask: ``label(m, connectivity)`` first, then the above with the same ``connectivity``.
+    The components of a mask never touch each other, so this is of use with ``distance=`` / ``radius_sq=``: components closer than
+    twice that distance become neighbours."""
+    conn = _check_connectivity(connectivity)
+    _check_max_regions(max_regions)
+    _check_max_pairs(max_pairs)
+    if distance is not None or radius_sq is not None:
+        from . import morph as M
+        M._r2("adjacency", distance, radius_sq, name="distance")
+    return adjacency_labels(label(m, conn), conn, distance, radius_sq, max_regions, max_pairs)
 
 
 _HAUSDORFF_HOST = ("area_pred", "area_truth", "d2_truth", "d2_pred")

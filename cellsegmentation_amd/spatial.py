@@ -18,6 +18,12 @@ Every result is decided by integer comparisons: neighbours are ordered by the ke
 index, and the counts are sums of integers.  Nothing depends on the bucket side, which is chosen on the host from the sizes alone
 (``choose_bucket``): launch grids and the workspace are independent of the data, nothing synchronises, and a call can be captured
 under ``torch.cuda.graph``.
+
+``voronoi_graph`` is the one function here that works on pixels: it paints the live points into a seed label image
+(``cs_regions_seed_labels``), lets every pixel take its nearest seed (``morph.nearest_sites``, or ``morph.expand_labels`` for
+territories bounded by a distance) and reads the neighbour graph off that label image with ``regions.adjacency_labels`` -- the raster
+Voronoi graph of the detections, row k = point k.  Exact integers again, but its launches and read-backs are those of the functions
+it is made of (its docstring says which).
 """
 import math
 from dataclasses import dataclass
@@ -238,6 +244,49 @@ def cluster(points, image_hw, eps, min_samples=5, offsets=None, limits=None, _bu
     _upload(q, None, points, offsets)
     out = K.spatial_cluster(q.pts_dev, q.off_dev, H, W, b, r2, int(min_samples), limits=q.lim_dev)
     return ClusterTable(*out, r2, int(min_samples), q.off_dev)
+
+
+def voronoi_graph(points, image_hw, offsets=None, limits=None, max_distance=None, connectivity=1, max_pairs=None):
+    """The raster Voronoi neighbour graph of every image's live points -> ``(regions.AdjacencyTable, labels)``: which detections
+    are neighbours, the cell graph that graph-based tissue analysis starts from.
+
+    Point k of an image is label k + 1.  The seed label image holds k + 1 at the pixel of live point k (of several live points on
+    one pixel the lowest k owns it; the others own nothing and have no neighbours) and 0 elsewhere.  With ``max_distance=None``
+    every pixel takes the label of its nearest seed, among equally near seeds the one with the lowest row-major pixel index
+    (``morph.nearest_sites``): the raster Voronoi diagram.  With a number, ``morph.expand_labels(seeds, max_distance)``: the
+    territories are bounded by that distance, and two points are neighbours only if their territories meet.  ``labels`` is that
+    int32 [N, H, W] device image, and the table is ``regions.adjacency_labels(labels, connectivity)`` with capacity = the largest
+    point count of an image, so that row k of image n is point k: ``sides`` is the length in pixel sides of the border two
+    territories share.  ``max_pairs`` as in ``adjacency_labels``: None reads a counter back and doubles the pair table until every
+    pair fits.  Offsets given as a device tensor cost one more read-back, for the capacity.
+
+    This is the RASTER Voronoi graph.  Parity with ``scipy.spatial.Delaunay`` is not claimed: a thin raster cell can be cut where
+    the exact one is connected, and co-circular integer points, whose exact Voronoi cells meet in a single vertex, come out as
+    neighbours by a pixel side or corner or not at all.  Memory on a whole slide: the seed image and the label image, two int32
+    images of N H W pixels, are held at once; ``max_distance=None`` holds two more (the squared distances and the site indices)
+    during the call, and its search is as far as the nearest seed lies -- bound it with ``max_distance`` where seeds are sparse."""
+    from . import morph as M
+    from . import regions as Rg
+    H, W = check_image_hw(image_hw)
+    conn = Rg._check_connectivity(connectivity)
+    Rg._check_max_pairs(max_pairs)
+    r2 = None if max_distance is None else radius_squared(max_distance)
+    if W > M.MAX_SITE_WIDTH:
+        raise ValueError(f"voronoi_graph: rows wider than {M.MAX_SITE_WIDTH} pixels are not supported, got {H}x{W}")
+    q = PointSet(points, offsets, limits, None, "voronoi_graph: points")
+    if q.n_images * H * W >= 1 << 31:
+        raise ValueError(f"voronoi_graph: a call takes fewer than 2^31 pixels, got {q.n_images} images of {H}x{W}")
+    _upload(q, None, points, offsets)
+    seeds = K.regions_seed_labels(q.pts_dev, q.off_dev, H, W, limits=q.lim_dev)
+    if r2 is None:
+        _, site = M.nearest_sites(seeds)
+        flat = seeds.flatten(-2).gather(-1, site.flatten(-2).clamp(min=0).to(torch.int64)).view_as(seeds)
+        labels = torch.where(site >= 0, flat, torch.zeros_like(flat))    # an image without a seed has no site
+    else:
+        labels = M.expand_labels(seeds, radius_sq=r2)
+    per_image = np.diff(q.off) if q.off is not None else (q.off_dev[1:] - q.off_dev[:-1]).cpu().numpy()
+    cap = max(1, int(per_image.max()))
+    return Rg.adjacency_labels(labels, conn, max_regions=cap, max_pairs=max_pairs), labels
 
 
 def bin_counts(points, image_hw, bin, offsets=None, limits=None):

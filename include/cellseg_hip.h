@@ -861,6 +861,45 @@ int cs_regions_overlap_labels(const int32_t* pred, const int32_t* truth, int N, 
                               int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred, int32_t* inter_pred,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- which labels of one label image touch which: adjacency tables (csrc/regions.hip) ------------------------------------------
+ * labels int32 [N][H][W], images independent; sizes and the launch contract are those of cs_regions_measure_labels.  All rules are
+ * exact integers:
+ *   id        a pixel's id is its label where 1 <= label <= capacity, else 0: a label above the capacity is background here.  counts
+ *             (int32 [N] or NULL) is WRITTEN with the largest label of every image, also above the capacity.
+ *   sides     every unordered pair of 4-adjacent pixels of the image is one interior side; a pixel side on the image edge is an
+ *             exterior side of that pixel.
+ *   per pair of labels a < b, both positive: sides(a, b) = the interior sides whose two ids are {a, b}; corners(a, b), counted with
+ *             connectivity 2 only (else 0), = the unordered diagonal pixel pairs {(r, c), (r + 1, c + 1)} and {(r, c + 1), (r + 1, c)}
+ *             whose ids are {a, b}, whether or not the two labels also share a side.  A pair is listed iff sides > 0 (connectivity 1)
+ *             or sides + corners > 0 (connectivity 2).
+ *   per label a (row a - 1 of the int32 [N][capacity] tables): n_neighbors = the listed pairs that contain a; contact = the sum of
+ *             sides over them; background = the interior sides with ids {a, 0}; outside = the exterior sides of a's pixels; partner /
+ *             partner_sides = the listed neighbour of largest sides, ties to the lower label, and that count (a neighbour met at
+ *             corners only has 0 sides); partner 0 = no neighbour.  A label without pixels has an all-zero row.
+ *   identity  contact + background + outside = 4 area - 2 (interior sides with both ids a): the crack length of the label.
+ * The listed pairs are held as cs_regions_overlap_labels holds its pairs, in a per-image open-addressing table of slots = the smallest
+ * power of two >= 2 max_pairs entries at the START of the workspace: keys uint64 [N][slots], key = (a << 32) | b, 0 = empty, then
+ * sides int32 [N][slots], then corners int32 [N][slots]; the caller may read the three after the call.  n_pairs int32 [N] = the
+ * occupied slots; a run of sides or corners whose pair finds no slot is left out and adds 1 to dropped[n] (int32 [N]) -- the pair
+ * list, n_neighbors, contact and partner of image n are then incomplete (never too large); background and outside are not.  Which
+ * slot a pair occupies may differ from run to run; everything else is integer sums and maxima under a total order, independent of
+ * launch and arrival order.  The counts are int32: an image of fewer than 2^29 pixels cannot overflow them.  Need capacity >= 1,
+ * 1 <= max_pairs <= 2^29, connectivity 1 or 2, N capacity < 2^31 and N slots < 2^31.  workspace: 16-byte aligned, >=
+ * cs_regions_adjacency_workspace(N, capacity, max_pairs) bytes (0 for sizes a call would refuse): 16 N slots + 8 N capacity bytes
+ * and padding.  Four launches. */
+size_t cs_regions_adjacency_workspace(int N, int capacity, int max_pairs);
+int cs_regions_adjacency_labels(const int32_t* labels, int N, int H, int W, int capacity, int max_pairs, int connectivity,
+                                int32_t* counts, int32_t* n_pairs, int32_t* dropped, int32_t* n_neighbors, int32_t* contact,
+                                int32_t* background, int32_t* outside, int32_t* partner, int32_t* partner_sides, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* ---- the seed label image of a ragged point set (csrc/regions.hip, csrc/cs_points.h) -----------------------------------------
+ * points int64 [P][2] (row, col), offsets int64 [N + 1], limits int32 [N] or NULL as cs_regions_split takes them.  labels int32
+ * [N][H][W] is WRITTEN: 0 everywhere, and k + 1 at the pixel of point k of its image where that point is within its image's limit and
+ * inside the image; of several such points on one pixel the lowest k.  Three launches (one without points), nothing synchronises. */
+int cs_regions_seed_labels(const int64_t* points, const int64_t* offsets, const int32_t* limits, long long P, int N, int H, int W,
+                           int32_t* labels, void* stream);
+
 /* ---- the squared Hausdorff distance of every object of two label images to its partner (csrc/regions.hip) -------------------
  * pred, truth, the treatment of labels (<= 0 and above the side's capacity = background) and the launch contract are those of
  * cs_regions_overlap_labels; an object is a label that owns a pixel.  For pixel sets A, B of image n: d2(A -> B) = the maximum over

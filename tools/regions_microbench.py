@@ -48,6 +48,13 @@ labels of every map (the restatement is plain Python loops).
 
     python tools/regions_microbench.py --contours [--reps 5] [--host-maps 2] [--json PATH]
 
+--adjacency times ``regions.adjacency_labels`` with ``max_regions``, ``max_pairs`` and ``counts`` given (four launches, nothing
+synchronises) at both connectivities, next to ``regions.measure_labels`` and ``regions.shape_labels`` on the label images of
+``--shape``, graph replays again.  It reports the pairs found and the table size, and checks the pair list and the contact column of
+the first ``--host-maps`` maps against numpy's ``unique`` over the id pairs of adjacent pixels.
+
+    python tools/regions_microbench.py --adjacency [--reps 5] [--host-maps 2] [--json PATH]
+
 --morph times ``morph.binary_opening`` at radii 1, 2 and 5, ``morph.expand_labels`` at 4 (of ``regions.label`` of the masks) and
 ``morph.nearest_sites`` (towards the background) next to ``detect.distance_transform_sq`` on the same two mask sets, graph replays
 again, and checks the first ``--host-maps`` maps against scipy: ``binary_opening`` by the disk, the squared
@@ -358,6 +365,62 @@ def contour_case(name, masks, pts, off, reps, host_maps, dev):
     return res
 
 
+def host_pairs(lab, conn):
+    """lab int [H, W] -> int64 [n, 4] rows (a, b, sides, corners), a < b both positive, sorted: numpy's unique over the id pairs of
+    the adjacent pixels (no dense table: a whole-image mask has thousands of labels)"""
+    lab = np.maximum(lab.astype(np.int64), 0)
+
+    def counted(x, y):
+        x, y = x.ravel(), y.ravel()
+        keep = (x > 0) & (y > 0) & (x != y)
+        keys, n = np.unique(np.minimum(x, y)[keep] << 32 | np.maximum(x, y)[keep], return_counts=True)
+        return dict(zip(keys.tolist(), n.tolist()))
+
+    sides = counted(np.concatenate([lab[:, :-1].ravel(), lab[:-1, :].ravel()]), np.concatenate([lab[:, 1:].ravel(), lab[1:, :].ravel()]))
+    corners = {}
+    if conn == 2:
+        corners = counted(np.concatenate([lab[:-1, :-1].ravel(), lab[:-1, 1:].ravel()]),
+                          np.concatenate([lab[1:, 1:].ravel(), lab[1:, :-1].ravel()]))
+    keys = sorted(set(sides) | set(corners))
+    return np.asarray([(k >> 32, k & 0xFFFFFFFF, sides.get(k, 0), corners.get(k, 0)) for k in keys], np.int64).reshape(-1, 4)
+
+
+def adjacency_case(name, masks, pts, off, reps, host_maps, dev):
+    d, dp, doff = torch.from_numpy(masks).to(dev), torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev)
+    parts = G.split(d, dp, doff)
+    cap = max(1, int(parts.counts.max()))                                  # sized once, outside the timed region
+    table = G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts)
+    sized = {conn: G.adjacency_labels(parts.labels, conn, max_regions=cap, counts=parts.counts) for conn in (1, 2)}   # max_pairs sized here
+    max_pairs = {conn: t.slot_keys.shape[1] // 2 for conn, t in sized.items()}
+    measure_ms, _ = time_graph(lambda: G.measure_labels(parts.labels, max_regions=cap, counts=parts.counts), reps)
+    shape_ms, _ = time_graph(lambda: G.shape_labels(parts.labels, table=table), reps)
+    res = {"measure_labels_ms": measure_ms, "shape_labels_ms": shape_ms, "rows_max": cap, "objects": int((table.area > 0).sum()),
+           "foreground_pixels": int(masks.sum())}
+    ok = True
+    labels = parts.labels.cpu().numpy()
+    for conn in (1, 2):
+        ms, ts = time_graph(lambda: G.adjacency_labels(parts.labels, conn, max_regions=cap, max_pairs=max_pairs[conn],
+                                                       counts=parts.counts), reps)
+        t = sized[conn]
+        res.update({f"adjacency_c{conn}_ms": ms, f"adjacency_c{conn}_ms_all": ts,
+                    f"adjacency_c{conn}_over_measure_plus_shape": ms / (measure_ms + shape_ms), f"max_pairs_c{conn}": max_pairs[conn],
+                    f"pairs_c{conn}": int(t.n_pairs.sum()), f"pairs_per_image_max_c{conn}": int(t.n_pairs.max())})
+        image, a, b, sides, corners = t.pairs()
+        contact = t.contact.cpu().numpy()
+        for i in range(min(host_maps, len(masks))):
+            ref = host_pairs(labels[i], conn)
+            ok &= bool(np.array_equal(np.stack([a, b, sides, corners], axis=1)[image == i], ref))
+            want = np.zeros(cap, np.int64)
+            np.add.at(want, ref[:, 0] - 1, ref[:, 2])
+            np.add.at(want, ref[:, 1] - 1, ref[:, 2])
+            ok &= bool(np.array_equal(contact[i], want))
+    res["contact_sides"] = int(sized[1].contact.sum())
+    res["background_sides"] = int(sized[1].background.sum())
+    res.update(equal_to_host=ok, host_maps=min(host_maps, len(masks)))
+    print(json.dumps({name: res}), flush=True)
+    return res
+
+
 def morph_case(name, masks, reps, host_maps, dev):
     from scipy import ndimage
     import morph_ref as MR
@@ -420,10 +483,13 @@ def main():
     ap.add_argument("--shape", action="store_true", help="time regions.shape_labels next to regions.measure_labels instead")
     ap.add_argument("--hull", action="store_true", help="time regions.hull_labels next to measure_labels + shape_labels instead")
     ap.add_argument("--contours", action="store_true", help="time regions.contour_labels next to measure_labels + shape_labels instead")
+    ap.add_argument("--adjacency", action="store_true", help="time regions.adjacency_labels next to measure_labels + shape_labels instead")
     ap.add_argument("--morph", action="store_true", help="time morph.binary_opening / expand_labels / nearest_sites next to the EDT instead")
     args = ap.parse_args()
     if args.morph:
         res = morph_main(args)
+    elif args.adjacency:
+        res = seeded_main(adjacency_case, args)
     elif args.contours:
         res = seeded_main(contour_case, args)
     elif args.hull:
