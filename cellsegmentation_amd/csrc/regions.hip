@@ -869,64 +869,40 @@ __global__ __launch_bounds__(256) void match_decide_kernel(long long rows, Match
     }
 }
 
-// ---- label image against label image: every overlapping pair ----------------------------------------------------------------------
-// The sparse contingency table of two label images: every (p, g) that shares a pixel, with the count.  Per image an open-addressing
-// hash table of `slots` (a power of two) 64-bit keys, (p << 32) | g, 0 = empty, and as many int32 counts.  A key is written once, by
-// the CAS that takes the slot from empty, and never changes: a probe that reads a key other than 0 has read the slot's final key.
-// Which slot a pair lands in depends on the order of arrival; the set of (key, count) does not (integer sums), and everything
-// derived from the table is a maximum under a total order of the pairs, which does not depend on where they sit.
-struct Overlap {
-    PairSides s;
+// ---- a sparse table of label pairs: what overlap and adjacency share --------------------------------------------------------------
+// Per image an open-addressing hash table of `slots` (a power of two) 64-bit keys, (hi << 32) | lo, 0 = empty, and one or more
+// arrays of as many int32 counts, which the owner of the table holds.  A key is written once, by the CAS that takes the slot from
+// empty, and never changes: a probe that reads a key other than 0 has read the slot's final key.  Which slot a pair lands in depends
+// on the order of arrival; the set of (key, counts) does not (integer sums).
+struct PairTable {
     int32_t* n_pairs;               // [N]  occupied slots
     int32_t* dropped;               // [N]  runs that found no slot
-    int32_t* iou_partner;           // [N][cap_truth]  the pred label of largest IoU, 0 = none
-    int32_t* iou_inter;             // [N][cap_truth]  its intersection
-    int32_t* inter_partner_truth;   // [N][cap_truth]  the pred label of largest intersection
-    int32_t* inter_truth;           // [N][cap_truth]
-    int32_t* inter_partner_pred;    // [N][cap_pred]   the truth label of largest intersection
-    int32_t* inter_pred;            // [N][cap_pred]
     unsigned long long* keys;       // [N][slots]
-    int32_t* cnt;                   // [N][slots]
-    unsigned long long* best_iou;   // [N][cap_truth]  (I << 32) | p, 0 = none
-    unsigned long long* best_it;    // [N][cap_truth]  (I << 32) | ~p: the largest I, then the lowest p
-    unsigned long long* best_ip;    // [N][cap_pred]   (I << 32) | ~g
     int slots;
 };
 
-__global__ __launch_bounds__(256) void overlap_init_kernel(int N, Overlap t) {
-    const long long np = (long long)N * t.s.cap_pred, nt = (long long)N * t.s.cap_truth, ns = (long long)N * t.slots;
-    const long long all = max(ns, max(np, nt));                        // >= N
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
-        pair_sides_init(t.s, N, i);
-        if (i < ns) {
-            t.keys[i] = 0;
-            t.cnt[i] = 0;
-        }
-        if (i < np) t.best_ip[i] = 0;
-        if (i < nt) {
-            t.best_iou[i] = 0;
-            t.best_it[i] = 0;
-        }
-        if (i < N) {
-            t.n_pairs[i] = 0;
-            t.dropped[i] = 0;
-        }
+// element i of an init launch over at least N slots >= N elements (the count arrays are their owner's to clear)
+__device__ __forceinline__ void pair_table_init(const PairTable& p, int N, long long i) {
+    if (i < (long long)N * p.slots) p.keys[i] = 0;
+    if (i < N) {
+        p.n_pairs[i] = 0;
+        p.dropped[i] = 0;
     }
 }
 
-__device__ __forceinline__ unsigned overlap_hash(unsigned p, unsigned g) {
+__device__ __forceinline__ unsigned pair_hash(unsigned p, unsigned g) {
     unsigned h = p * 0x9E3779B1u ^ g * 0x85EBCA77u;
     h ^= h >> 15;
     h *= 0x2C1B3C6Du;
     return h ^ (h >> 13);
 }
 
-// len more pixels for pair (p, g) of one image's table.  At most `slots` probes: a slot is taken from empty by CAS, one that
+// len more for pair (p, g) of one image's table.  At most `slots` probes: a slot is taken from empty by CAS, one that
 // holds this key (from this CAS or from another thread's) gets the add, any other key sends the probe on.  Nothing is waited for.
 // Returns false when every slot holds another key.  *fresh: this call took a slot.
-__device__ __forceinline__ bool overlap_insert(unsigned long long* keys, int32_t* cnt, unsigned mask, int p, int g, int len, bool* fresh) {
+__device__ __forceinline__ bool pair_insert(unsigned long long* keys, int32_t* cnt, unsigned mask, int p, int g, int len, bool* fresh) {
     const unsigned long long key = ((unsigned long long)(unsigned)p << 32) | (unsigned)g;
-    unsigned s = overlap_hash((unsigned)p, (unsigned)g) & mask;
+    unsigned s = pair_hash((unsigned)p, (unsigned)g) & mask;
     *fresh = false;
     for (unsigned tries = 0; tries <= mask; ++tries, s = (s + 1) & mask) {
         unsigned long long seen = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, kGlobal);
@@ -944,22 +920,61 @@ __device__ __forceinline__ bool overlap_insert(unsigned long long* keys, int32_t
     return false;
 }
 
+// A run of len for pair (p, g) of image n into the count array cnt [N][slots] of the table: a run that finds no slot is counted in
+// dropped[n], one that takes a slot in n_pairs[n].  `p` must be a copy of the table in a local of the kernel: with the two counters
+// read through the kernel's argument inside a walker's body, the compiler merges the two adds below into one whose pointer it picks
+// from the argument by a run-time index, and that keeps a copy of those 16 bytes of it in scratch (24 bytes, hipcc of ROCm 7).
+__device__ __forceinline__ void pair_add(const PairTable& p, int32_t* cnt, int n, int hi, int lo, int len) {
+    const long long base = (long long)n * p.slots;                     // < N slots < 2^31
+    bool fresh;
+    if (!pair_insert(p.keys + base, cnt + base, (unsigned)p.slots - 1, hi, lo, len, &fresh))
+        __hip_atomic_fetch_add(p.dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
+    else if (fresh)
+        __hip_atomic_fetch_add(p.n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+}
+
+// ---- label image against label image: every overlapping pair ----------------------------------------------------------------------
+// The sparse contingency table of two label images: every (p, g) that shares a pixel, with the count, in a PairTable with key
+// (p << 32) | g and one count array.  Everything derived from the table is a maximum under a total order of the pairs, which does
+// not depend on where they sit.
+struct Overlap {
+    PairSides s;
+    PairTable pairs;
+    int32_t* iou_partner;           // [N][cap_truth]  the pred label of largest IoU, 0 = none
+    int32_t* iou_inter;             // [N][cap_truth]  its intersection
+    int32_t* inter_partner_truth;   // [N][cap_truth]  the pred label of largest intersection
+    int32_t* inter_truth;           // [N][cap_truth]
+    int32_t* inter_partner_pred;    // [N][cap_pred]   the truth label of largest intersection
+    int32_t* inter_pred;            // [N][cap_pred]
+    int32_t* cnt;                   // [N][slots]
+    unsigned long long* best_iou;   // [N][cap_truth]  (I << 32) | p, 0 = none
+    unsigned long long* best_it;    // [N][cap_truth]  (I << 32) | ~p: the largest I, then the lowest p
+    unsigned long long* best_ip;    // [N][cap_pred]   (I << 32) | ~g
+};
+
+__global__ __launch_bounds__(256) void overlap_init_kernel(int N, Overlap t) {
+    const long long np = (long long)N * t.s.cap_pred, nt = (long long)N * t.s.cap_truth, ns = (long long)N * t.pairs.slots;
+    const long long all = max(ns, max(np, nt));                        // >= N
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        pair_sides_init(t.s, N, i);
+        pair_table_init(t.pairs, N, i);
+        if (i < ns) t.cnt[i] = 0;
+        if (i < np) t.best_ip[i] = 0;
+        if (i < nt) {
+            t.best_iou[i] = 0;
+            t.best_it[i] = 0;
+        }
+    }
+}
+
 // The accounting of both sides, and every run on which both labels are positive (and within their capacities) adds its length to
 // its pair's slot.
 __global__ __launch_bounds__(256) void overlap_walk_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int N, int H,
                                                            int W, Overlap t) {
-    // The two counters as locals: read through `t` inside the body, the compiler merges the two adds below into one whose pointer
-    // it picks from `t` by a run-time index, and that keeps a copy of those 16 bytes of `t` in scratch (24 bytes, hipcc of ROCm 7).
-    int32_t *const n_pairs = t.n_pairs, *const dropped = t.dropped;
+    const PairTable pairs = t.pairs;                                   // (a local: see pair_add)
     walk_row_segments(N, H, W, [&](int n, int, int c, long long px) {
         const PairRun u = pair_run<true>(pred, truth, t.s, n, W, c, px);
-        if (!u.head || !u.p || !u.g) return;
-        const long long base = (long long)n * t.slots;                 // < N slots < 2^31
-        bool fresh;
-        if (!overlap_insert(t.keys + base, t.cnt + base, (unsigned)t.slots - 1, u.p, u.g, u.len, &fresh))
-            __hip_atomic_fetch_add(dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
-        else if (fresh)
-            __hip_atomic_fetch_add(n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+        if (u.head && u.p && u.g) pair_add(pairs, t.cnt, n, u.p, u.g, u.len);
     });
 }
 
@@ -970,9 +985,9 @@ __global__ __launch_bounds__(256) void overlap_walk_kernel(const int32_t* __rest
 // the holder, the comparison is made again against what it wrote, and the loop ends with the best pair of all whatever the order.
 __global__ __launch_bounds__(256) void overlap_reduce_kernel(long long n_slots, Overlap t) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_slots; i += (long long)gridDim.x * 256) {
-        const unsigned long long key = t.keys[i];
+        const unsigned long long key = t.pairs.keys[i];
         if (key == 0) continue;
-        const long long n = i / t.slots;
+        const long long n = i / t.pairs.slots;
         const unsigned p = (unsigned)(key >> 32), g = (unsigned)key;
         const unsigned long long I = (unsigned)t.cnt[i];
         const long long qp = n * t.s.cap_pred + p - 1, qg = n * t.s.cap_truth + g - 1;
@@ -1018,31 +1033,29 @@ __global__ __launch_bounds__(256) void overlap_finish_kernel(int N, Overlap t) {
 // A pixel's id is its label where 1 <= label <= cap, else 0.  An interior side is an unordered pair of 4-adjacent pixels, an
 // exterior side a pixel side on the image edge.  sides(a, b), a < b both positive: the interior sides with ids {a, b}; corners(a, b)
 // (CONN 2 only): the diagonal pixel pairs {(r, c), (r + 1, c + 1)} and {(r, c + 1), (r + 1, c)} with ids {a, b}.  The pairs live in
-// overlap's hash table, key (a << 32) | b, with two count arrays; a slot exists iff one of its two counts is positive.  Per label:
+// a PairTable, key (a << 32) | b, with two count arrays; a slot exists iff one of its two counts is positive.  Per label:
 // background = interior sides with ids {a, 0}, outside = exterior sides of a's pixels, contact = the sum of sides over a's pairs,
 // n_neighbors = a's pairs, partner = the pair of largest sides, ties to the lower label.
 struct Adjacency {
     int32_t* maxlab;                // [N] or NULL: the largest label, also above cap
-    int32_t* n_pairs;               // [N]  occupied slots
-    int32_t* dropped;               // [N]  runs that found no slot
+    PairTable pairs;
     int32_t* n_neighbors;           // [N][cap]
     int32_t* contact;               // [N][cap]
     int32_t* background;            // [N][cap]
     int32_t* outside;               // [N][cap]
     int32_t* partner;               // [N][cap]
     int32_t* partner_sides;         // [N][cap]
-    unsigned long long* keys;       // [N][slots]
     int32_t* sides;                 // [N][slots]
     int32_t* corners;               // [N][slots]
     unsigned long long* best;       // [N][cap]  (sides << 32) | ~partner, 0 = no neighbour
-    int cap, slots;
+    int cap;
 };
 
 __global__ __launch_bounds__(256) void adjacency_init_kernel(int N, Adjacency t) {
-    const long long nl = (long long)N * t.cap, ns = (long long)N * t.slots;
+    const long long nl = (long long)N * t.cap, ns = (long long)N * t.pairs.slots;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < max(nl, ns); i += (long long)gridDim.x * 256) {
+        pair_table_init(t.pairs, N, i);                                // (N <= ns)
         if (i < ns) {
-            t.keys[i] = 0;
             t.sides[i] = 0;
             t.corners[i] = 0;
         }
@@ -1053,11 +1066,7 @@ __global__ __launch_bounds__(256) void adjacency_init_kernel(int N, Adjacency t)
             t.outside[i] = 0;
             t.best[i] = 0;
         }
-        if (i < N) {                                                   // N <= nl
-            t.n_pairs[i] = 0;
-            t.dropped[i] = 0;
-            if (t.maxlab) t.maxlab[i] = 0;
-        }
+        if (i < N && t.maxlab) t.maxlab[i] = 0;                        // N <= nl
     }
 }
 
@@ -1070,7 +1079,7 @@ template <int CONN>
 __global__ __launch_bounds__(256) void adjacency_walk_kernel(const int32_t* __restrict__ lab, int N, int H, int W, Adjacency t) {
     const int lane = threadIdx.x & 63;
     const int cap = t.cap;
-    int32_t *const n_pairs = t.n_pairs, *const dropped = t.dropped;    // (locals: see overlap_walk_kernel)
+    const PairTable pairs = t.pairs;                                   // (a local: see pair_add)
     auto id_of = [cap](int l) { return (l >= 1 && l <= cap) ? l : 0; };
     walk_row_segments(N, H, W, [&](int n, int r, int c, long long p) {
         const bool in = c < W, above = r > 0, below = r < H - 1;
@@ -1104,7 +1113,6 @@ __global__ __launch_bounds__(256) void adjacency_walk_kernel(const int32_t* __re
             if (tally >> 16) __hip_atomic_fetch_add(t.background + q, tally >> 16, __ATOMIC_RELAXED, kGlobal);
         }
 
-        const long long base = (long long)n * t.slots;                 // < N slots < 2^31
         // the runs of constant (a, b) among the lanes where `ok` and the two ids are positive and differ: one insert each
         auto emit = [&](int a, int b, bool ok, int32_t* cnt) {
             const bool live = ok && a > 0 && b > 0 && a != b;
@@ -1112,12 +1120,7 @@ __global__ __launch_bounds__(256) void adjacency_walk_kernel(const int32_t* __re
             if (bal == 0) return;
             const int al = __shfl_up(a, 1), bl = __shfl_up(b, 1);
             int n_run;
-            if (!run_of(bal, __ballot(live && (a != al || b != bl)), lane, n_run)) return;
-            bool fresh;
-            if (!overlap_insert(t.keys + base, cnt + base, (unsigned)t.slots - 1, min(a, b), max(a, b), n_run, &fresh))
-                __hip_atomic_fetch_add(dropped + n, 1, __ATOMIC_RELAXED, kGlobal);
-            else if (fresh)
-                __hip_atomic_fetch_add(n_pairs + n, 1, __ATOMIC_RELAXED, kGlobal);
+            if (run_of(bal, __ballot(live && (a != al || b != bl)), lane, n_run)) pair_add(pairs, cnt, n, min(a, b), max(a, b), n_run);
         };
         emit(m, d, below, t.sides);                                    // (d is 0 where c >= W)
         emit(m, right, has_right, t.sides);
@@ -1132,9 +1135,9 @@ __global__ __launch_bounds__(256) void adjacency_walk_kernel(const int32_t* __re
 // (sides << 32) | ~other, i.e. the largest sides and among equals the lowest label.
 __global__ __launch_bounds__(256) void adjacency_reduce_kernel(long long n_slots, Adjacency t) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_slots; i += (long long)gridDim.x * 256) {
-        const unsigned long long key = t.keys[i];
+        const unsigned long long key = t.pairs.keys[i];
         if (key == 0) continue;
-        const long long n = i / t.slots;
+        const long long n = i / t.pairs.slots;
         const unsigned a = (unsigned)(key >> 32), b = (unsigned)key;
         const int s = t.sides[i];
         const long long qa = n * t.cap + a - 1, qb = n * t.cap + b - 1;
@@ -1813,47 +1816,44 @@ size_t match_layout(void* w, int N, Match* t) {
 }
 
 // the slots of one image's pair table: the smallest power of two >= 2 max_pairs; 0 for a max_pairs no call takes
-inline long long overlap_slots(int max_pairs) {
+inline long long pair_slots(int max_pairs) {
     if (max_pairs < 1 || max_pairs > (1 << 29)) return 0;
     long long s = 2;
     while (s < 2LL * max_pairs) s <<= 1;
     return s;
 }
-bool overlap_sizes_ok(int N, int cap_pred, int cap_truth, int max_pairs) {
-    const long long slots = overlap_slots(max_pairs);
-    return N > 0 && N <= 65535 && cap_pred >= 1 && cap_truth >= 1 && slots > 0 && (long long)N * cap_pred < (1LL << 31) &&
-           (long long)N * cap_truth < (1LL << 31) && N * slots < (1LL << 31);
+// The pair table at the head of a workspace: keys (uint64 N slots), then k int32 count arrays of N slots each, taken as one array
+// at *counts (4 N slots need not be 16-byte aligned, 8 N slots is); sets p's slots.  false for sizes no call takes.  N slots is even,
+// so the arrays are the first 8 N slots bytes and k times the next 4 N slots with no padding between them:
+// kernels._pair_table_views (Python) views these (8 + 4 k) N slots bytes as the result's slot_keys / slot_<count>.
+bool pair_table_layout(Carve* c, int N, int max_pairs, int k, PairTable* p, int32_t** counts) {
+    const long long slots = pair_slots(max_pairs);
+    if (!(N > 0 && N <= 65535 && slots > 0 && N * slots < (1LL << 31))) return false;
+    p->slots = (int)slots;
+    p->keys = c->take<unsigned long long>((size_t)N * slots);
+    *counts = c->take<int32_t>((size_t)k * N * slots);
+    return true;
 }
-// keys (uint64 N slots), cnt (int32 N slots), then best_iou, best_it (uint64 N cap_truth each), best_ip (uint64 N cap_pred), for
-// the capacities of t, whose slots it sets; 0 for sizes no call takes.  The pair table leads and N slots is even, so keys and cnt
-// are the first 8 N slots and the next 4 N slots bytes with no padding between them: kernels.regions_overlap_labels (Python) views
-// these 12 N slots bytes as the result's slot_keys / slot_counts.
+
+// the pair table with cnt, then best_iou, best_it (uint64 N cap_truth each), best_ip (uint64 N cap_pred), for the capacities of t;
+// 0 for sizes no call takes
 size_t overlap_layout(void* w, int N, int max_pairs, Overlap* t) {
-    if (!overlap_sizes_ok(N, t->s.cap_pred, t->s.cap_truth, max_pairs)) return 0;
-    t->slots = (int)overlap_slots(max_pairs);
-    const size_t ns = (size_t)N * t->slots, nt = (size_t)N * t->s.cap_truth;
     Carve c{reinterpret_cast<uintptr_t>(w)};
-    t->keys = c.take<unsigned long long>(ns);
-    t->cnt = c.take<int32_t>(ns);
+    if (!pair_table_layout(&c, N, max_pairs, 1, &t->pairs, &t->cnt) || t->s.cap_pred < 1 || t->s.cap_truth < 1 ||
+        (long long)N * t->s.cap_pred >= (1LL << 31) || (long long)N * t->s.cap_truth >= (1LL << 31))
+        return 0;
+    const size_t nt = (size_t)N * t->s.cap_truth;
     t->best_iou = c.take<unsigned long long>(nt);
     t->best_it = c.take<unsigned long long>(nt);
     t->best_ip = c.take<unsigned long long>((size_t)N * t->s.cap_pred);
     return c.end;
 }
 
-// keys (uint64 N slots), sides, corners (int32 N slots each), then best (uint64 N cap), for the capacity of t, whose slots it sets;
-// 0 for sizes no call takes.  The pair table leads and N slots is even, so its three arrays are the first 8, the next 4 and the next
-// 4 N slots bytes with no padding between them: kernels.regions_adjacency_labels (Python) views these 16 N slots bytes as the
-// result's slot_keys / slot_sides / slot_corners.
+// the pair table with sides and corners, then best (uint64 N cap), for the capacity of t; 0 for sizes no call takes
 size_t adjacency_layout(void* w, int N, int max_pairs, Adjacency* t) {
-    const long long slots = overlap_slots(max_pairs);
-    if (!(N > 0 && N <= 65535 && t->cap >= 1 && slots > 0 && (long long)N * t->cap < (1LL << 31) && N * slots < (1LL << 31))) return 0;
-    t->slots = (int)slots;
-    const size_t ns = (size_t)N * t->slots;
     Carve c{reinterpret_cast<uintptr_t>(w)};
-    t->keys = c.take<unsigned long long>(ns);
-    t->sides = c.take<int32_t>(2 * ns);                                // one array for the two counts: 4 N slots need not be 16-byte
-    t->corners = t->sides + ns;                                        // aligned, 8 N slots is
+    if (!pair_table_layout(&c, N, max_pairs, 2, &t->pairs, &t->sides) || t->cap < 1 || (long long)N * t->cap >= (1LL << 31)) return 0;
+    t->corners = t->sides + (size_t)N * t->pairs.slots;
     t->best = c.take<unsigned long long>((size_t)N * t->cap);
     return c.end;
 }
@@ -1930,10 +1930,10 @@ int tables_of(const char* what, const uint8_t* intensity, int32_t* area, int32_t
     return CS_OK;
 }
 
-// What the two label-pair entry points check alike.  given: every pointer of the entry is there; need: what its workspace layout
-// returned, 0 for capacities it does not take, which is then the error caps_why.
-int check_label_pair(const char* what, bool given, int N, int H, int W, size_t need, const char* caps_why, const void* workspace,
-                     size_t bytes) {
+// What the entry points that take one or two label images and a workspace check alike.  given: every pointer of the entry is there;
+// need: what its workspace layout returned, 0 for capacities it does not take, which is then the error caps_why.
+int check_label_images(const char* what, bool given, int N, int H, int W, size_t need, const char* caps_why, const void* workspace,
+                       size_t bytes) {
     if (!given) return fail(what, "NULL argument");
     if (!sizes_ok(N, H, W)) return fail(what, "need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
     if (need == 0) return fail(what, caps_why);
@@ -2097,11 +2097,11 @@ extern "C" int cs_regions_match_labels(const int32_t* pred, const int32_t* truth
                                        int32_t* match, int32_t* inter, int32_t* match_truth, void* workspace, size_t workspace_bytes,
                                        void* stream) {
     Match t{{area_pred, area_truth, counts_pred, counts_truth, cap_pred, cap_truth}, match, inter, match_truth};
-    const int rc = check_label_pair("regions_match_labels",
-                                    pred && truth && area_pred && area_truth && match && inter && match_truth && workspace, N, H, W,
-                                    match_layout(workspace, N, &t),
-                                    "need capacities >= 1, N cap_pred bit_length(cap_truth) < 2^31 and N cap_truth < 2^31", workspace,
-                                    workspace_bytes);
+    const int rc = check_label_images("regions_match_labels",
+                                      pred && truth && area_pred && area_truth && match && inter && match_truth && workspace, N, H, W,
+                                      match_layout(workspace, N, &t),
+                                      "need capacities >= 1, N cap_pred bit_length(cap_truth) < 2^31 and N cap_truth < 2^31", workspace,
+                                      workspace_bytes);
     if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long rows = (long long)N * cap_pred;
@@ -2129,17 +2129,17 @@ extern "C" int cs_regions_overlap_labels(const int32_t* pred, const int32_t* tru
                                          int32_t* area_truth, int32_t* n_pairs, int32_t* dropped, int32_t* iou_partner, int32_t* iou_inter,
                                          int32_t* inter_partner_truth, int32_t* inter_truth, int32_t* inter_partner_pred,
                                          int32_t* inter_pred, void* workspace, size_t workspace_bytes, void* stream) {
-    Overlap t{{area_pred, area_truth, counts_pred, counts_truth, cap_pred, cap_truth}, n_pairs, dropped, iou_partner, iou_inter,
+    Overlap t{{area_pred, area_truth, counts_pred, counts_truth, cap_pred, cap_truth}, {n_pairs, dropped}, iou_partner, iou_inter,
               inter_partner_truth, inter_truth, inter_partner_pred, inter_pred};
-    const int rc = check_label_pair("regions_overlap_labels",
-                                    pred && truth && area_pred && area_truth && n_pairs && dropped && iou_partner && iou_inter &&
-                                        inter_partner_truth && inter_truth && inter_partner_pred && inter_pred && workspace,
-                                    N, H, W, overlap_layout(workspace, N, max_pairs, &t),
-                                    "need capacities >= 1, 1 <= max_pairs <= 2^29, N cap_pred < 2^31, N cap_truth < 2^31 and N slots < 2^31",
-                                    workspace, workspace_bytes);
+    const int rc = check_label_images("regions_overlap_labels",
+                                      pred && truth && area_pred && area_truth && n_pairs && dropped && iou_partner && iou_inter &&
+                                          inter_partner_truth && inter_truth && inter_partner_pred && inter_pred && workspace,
+                                      N, H, W, overlap_layout(workspace, N, max_pairs, &t),
+                                      "need capacities >= 1, 1 <= max_pairs <= 2^29, N cap_pred < 2^31, N cap_truth < 2^31 and N slots < 2^31",
+                                      workspace, workspace_bytes);
     if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long ns = (long long)N * t.slots, np = (long long)N * cap_pred, nt = (long long)N * cap_truth;
+    const long long ns = (long long)N * t.pairs.slots, np = (long long)N * cap_pred, nt = (long long)N * cap_truth;
     const long long labels = np > nt ? np : nt;
     hipLaunchKernelGGL(overlap_init_kernel, dim3(grid_for(ns > labels ? ns : labels)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
@@ -2162,18 +2162,18 @@ extern "C" int cs_regions_adjacency_labels(const int32_t* labels, int N, int H, 
                                            int32_t* counts, int32_t* n_pairs, int32_t* dropped, int32_t* n_neighbors, int32_t* contact,
                                            int32_t* background, int32_t* outside, int32_t* partner, int32_t* partner_sides,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-    Adjacency t{counts, n_pairs, dropped, n_neighbors, contact, background, outside, partner, partner_sides};
+    Adjacency t{counts, {n_pairs, dropped}, n_neighbors, contact, background, outside, partner, partner_sides};
     t.cap = capacity;
-    const int rc = check_label_pair("regions_adjacency_labels",
-                                    labels && n_pairs && dropped && n_neighbors && contact && background && outside && partner &&
-                                        partner_sides && workspace,
-                                    N, H, W, adjacency_layout(workspace, N, max_pairs, &t),
-                                    "need capacity >= 1, 1 <= max_pairs <= 2^29, N capacity < 2^31 and N slots < 2^31", workspace,
-                                    workspace_bytes);
+    const int rc = check_label_images("regions_adjacency_labels",
+                                      labels && n_pairs && dropped && n_neighbors && contact && background && outside && partner &&
+                                          partner_sides && workspace,
+                                      N, H, W, adjacency_layout(workspace, N, max_pairs, &t),
+                                      "need capacity >= 1, 1 <= max_pairs <= 2^29, N capacity < 2^31 and N slots < 2^31", workspace,
+                                      workspace_bytes);
     if (rc != CS_OK) return rc;
     if (connectivity != 1 && connectivity != 2) return fail("regions_adjacency_labels", "connectivity must be 1 or 2");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long ns = (long long)N * t.slots, rows = (long long)N * capacity;
+    const long long ns = (long long)N * t.pairs.slots, rows = (long long)N * capacity;
     hipLaunchKernelGGL(adjacency_init_kernel, dim3(grid_for(ns > rows ? ns : rows)), dim3(256), 0, st, N, t);
     CS_LAUNCH_CHECK();
     if (connectivity == 2)
@@ -2224,12 +2224,12 @@ extern "C" int cs_regions_hausdorff_labels(const int32_t* pred, const int32_t* t
     Haus t{pred, truth, inter_partner_truth, inter_partner_pred, partner_truth, d2_truth, partner_pred, d2_pred};
     t.N = N, t.H = H, t.W = W, t.cap_pred = cap_pred, t.cap_truth = cap_truth;
     const bool ok = sizes_ok(N, H, W) && hausdorff_sizes_ok(N, H, W, cap_pred, cap_truth);
-    const int rc = check_label_pair("regions_hausdorff_labels",
-                                    pred && truth && inter_partner_truth && inter_partner_pred && partner_truth && d2_truth &&
-                                        partner_pred && d2_pred && workspace,
-                                    N, H, W, ok ? hausdorff_layout(workspace, &t) : 0,
-                                    "need capacities >= 1, N (cap_pred + cap_truth) < 2^31 and (H - 1)^2 + (W - 1)^2 < 2^31", workspace,
-                                    workspace_bytes);
+    const int rc = check_label_images("regions_hausdorff_labels",
+                                      pred && truth && inter_partner_truth && inter_partner_pred && partner_truth && d2_truth &&
+                                          partner_pred && d2_pred && workspace,
+                                      N, H, W, ok ? hausdorff_layout(workspace, &t) : 0,
+                                      "need capacities >= 1, N (cap_pred + cap_truth) < 2^31 and (H - 1)^2 + (W - 1)^2 < 2^31", workspace,
+                                      workspace_bytes);
     if (rc != CS_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long rows = (long long)N * ((long long)cap_pred + cap_truth);

@@ -1409,14 +1409,25 @@ def regions_split_geodesic(mask, points, offsets, limits=None, connectivity=1, r
     return t["labels"], t["counts"], t["live"], t.get("distance"), t["converged"], ws
 
 
+def _label_images(what, labels):
+    """the label-image operand of the wrapper ``what`` -> N, H, W"""
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError(f"{what} reads int32 [N,H,W] label images")
+    return labels.shape
+
+
+def _bbox_operand(what, bbox, N, cap):
+    """the bounding boxes of regions_measure_labels for the same image, as the wrapper ``what`` takes them"""
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
+        raise TypeError(f"{what}: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+
+
 def regions_measure_labels(labels, capacity, intensity=None, counts=None, area=None, bbox=None, sums=None, isum=None, imax=None,
                            want_counts=True):
     """int32 label image [N,H,W] (and uint8 intensity [N,H,W] or None) -> the tuple of regions_measure with row k = label k + 1; a
     label without a pixel leaves an all-zero row.  counts is written with the largest label of every image, or left out
     (``want_counts=False`` -> None) by a caller that has the counts already."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_measure_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_measure_labels", labels)
     cap = int(capacity)
     if intensity is not None and (intensity.dtype != torch.uint8 or tuple(intensity.shape) != (N, H, W)):
         raise TypeError("regions_measure_labels: the intensity image is uint8 of the label image's shape")
@@ -1439,9 +1450,7 @@ REGIONS_SHAPE_MAX_SIDE = 32768       # cs_regions_shape_labels: Sxx <= area (H -
 def regions_edges_labels(labels, edges=None):
     """int32 label image [N,H,W] -> edges uint8 [N,H,W]: 1 where the pixel's object id max(label, 0) is positive and one of its four
     neighbours (outside the image: id 0) has another id (cs_regions_edges_labels in include/cellseg_hip.h)."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_edges_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_edges_labels", labels)
     t = _regions_outputs("regions_edges_labels", {"edges": ((N, H, W), torch.uint8)}, {"edges": edges}, labels.device)
     _lib.check(_lib.load().cs_regions_edges_labels(_p(labels), N, H, W, _p(t["edges"]), _stream()), "regions_edges_labels")
     return t["edges"]
@@ -1451,14 +1460,11 @@ def regions_shape_labels(labels, edges, capacity, bbox, moments=None, tallies=No
     """int32 label image [N,H,W], its edges uint8 [N,H,W] (regions_edges_labels) and bbox int32 [N,cap,4] (regions_measure_labels of
     the same image) -> (moments int64 [N,cap,3] = Sxx, Syy, Sxy about the box corner, tallies int32 [N,cap,4] = edge pixels,
     straight, diagonal, mixed); row k = label k + 1 (cs_regions_shape_labels in include/cellseg_hip.h)."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_shape_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_shape_labels", labels)
     cap = int(capacity)
     if edges.dtype != torch.uint8 or tuple(edges.shape) != (N, H, W):
         raise TypeError("regions_shape_labels: the edge map is uint8 of the label image's shape")
-    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
-        raise TypeError(f"regions_shape_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    _bbox_operand("regions_shape_labels", bbox, N, cap)
     if max(H, W) > REGIONS_SHAPE_MAX_SIDE:
         raise ValueError(f"regions_shape_labels: a {H}x{W} image: H, W <= {REGIONS_SHAPE_MAX_SIDE} keep the second moments inside int64")
     t = _regions_outputs("regions_shape_labels", {"moments": ((N, cap, 3), torch.int64), "tallies": ((N, cap, 4), torch.int32)},
@@ -1475,12 +1481,9 @@ def regions_hull_labels(labels, capacity, bbox, hull=None):
     """int32 label image [N,H,W] and bbox int32 [N,cap,4] (regions_measure_labels of the same image) -> hull int32 [N,cap,5] =
     n_vertices, area2, feret_max2, width_cross, width_len2 of the convex hull of every label's pixel squares; row k = label k + 1,
     all -1 where the box has more than REGIONS_HULL_MAX_SIDE rows or columns (cs_regions_hull_labels in include/cellseg_hip.h)."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_hull_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_hull_labels", labels)
     cap = int(capacity)
-    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
-        raise TypeError(f"regions_hull_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    _bbox_operand("regions_hull_labels", bbox, N, cap)
     t = _regions_outputs("regions_hull_labels", {"hull": ((N, cap, 5), torch.int32)}, {"hull": hull}, labels.device)
     _lib.check(_lib.load().cs_regions_hull_labels(_p(labels), N, H, W, cap, _p(bbox), _p(t["hull"]), _stream()), "regions_hull_labels")
     return t["hull"]
@@ -1495,12 +1498,9 @@ def regions_contour_labels(labels, capacity, bbox, connectivity, max_vertices, c
     ring's first vertices as (row, col), then (-1, -1)); row k = label k + 1, all -1 where the box has more than
     REGIONS_CONTOUR_MAX_SIDE rows or columns.  ``max_vertices=0`` only counts: vertices is None
     (cs_regions_contour_labels in include/cellseg_hip.h)."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_contour_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_contour_labels", labels)
     cap, maxv = int(capacity), int(max_vertices)
-    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (N, cap, 4):
-        raise TypeError(f"regions_contour_labels: bbox must be torch.int32 of shape {(N, cap, 4)}, got {bbox.dtype} {tuple(bbox.shape)}")
+    _bbox_operand("regions_contour_labels", bbox, N, cap)
     if maxv < 0:
         raise ValueError(f"regions_contour_labels: max_vertices must be >= 0, got {max_vertices!r}")
     want = {"contour": ((N, cap, 4), torch.int32)}
@@ -1555,13 +1555,27 @@ def regions_overlap_slots(max_pairs):
     return 1 << max(1, (2 * int(max_pairs) - 1).bit_length())
 
 
+def _int_max_pairs(size_fn, at):
+    """``size_fn`` with its ``max_pairs``, argument ``at``, kept to what the library's int holds: any other is refused here (0)"""
+    return lambda *a: size_fn(*a) if 1 <= a[at] < 1 << 31 else 0
+
+
+def _pair_table_views(ws, N, max_pairs, n_counts):
+    """The pair table of a call as views of its workspace ``ws``: (slot_keys int64 [N,slots], then ``n_counts`` int32 [N,slots] count
+    arrays).  The table leads the workspace, 8 bytes per slot of keys and then 4 per slot of every count array, and N slots is even,
+    so nothing pads them apart (pair_table_layout in csrc/regions.hip)."""
+    cells = N * regions_overlap_slots(max_pairs)
+    keys = ws[:8 * cells].view(torch.int64).view(N, -1)
+    return (keys, *(ws[(8 + 4 * k) * cells:(12 + 4 * k) * cells].view(torch.int32).view(N, -1) for k in range(n_counts)))
+
+
 def regions_overlap_workspace(N, cap_pred, cap_truth, max_pairs, device):
     """the caller-owned scratch of one cs_regions_overlap_labels call on N images with these capacities; it starts with the pair
     table, which the call's result views"""
     why = ("regions_overlap_labels: a call takes 0 < N <= 65535 images, capacities >= 1 and 1 <= max_pairs <= 2^29 with "
            f"N cap_pred, N cap_truth and N slots < 2^31, got {(N, cap_pred, cap_truth, max_pairs)}")
-    size = lambda *a: _lib.load().cs_regions_overlap_workspace(*a) if 1 <= a[3] < 1 << 31 else 0  # noqa: E731  (an int argument)
-    return _workspace(size, device, why, int(N), int(cap_pred), int(cap_truth), int(max_pairs))
+    return _workspace(_int_max_pairs(_lib.load().cs_regions_overlap_workspace, 3), device, why, int(N), int(cap_pred), int(cap_truth),
+                      int(max_pairs))
 
 
 _OVERLAP_TABLES = (("area_pred", 0), ("area_truth", 1), ("iou_partner", 1), ("iou_inter", 1), ("inter_partner_truth", 1), ("inter_truth", 1),
@@ -1591,9 +1605,7 @@ def regions_overlap_labels(pred, truth, cap_pred, cap_truth, max_pairs, counts_p
         _p(pred), _p(truth), N, H, W, cp, ct, mp, _p(t.get("counts_pred")), _p(t.get("counts_truth")), _p(t["area_pred"]),
         _p(t["area_truth"]), _p(t["n_pairs"]), _p(t["dropped"]), _p(t["iou_partner"]), _p(t["iou_inter"]), _p(t["inter_partner_truth"]),
         _p(t["inter_truth"]), _p(t["inter_partner_pred"]), _p(t["inter_pred"]), _p(ws), ws.numel(), _stream()), "regions_overlap_labels")
-    cells = N * regions_overlap_slots(mp)                              # the table leads the workspace: 8 then 4 bytes per slot
-    t["slot_keys"] = ws[:8 * cells].view(torch.int64).view(N, -1)
-    t["slot_counts"] = ws[8 * cells:12 * cells].view(torch.int32).view(N, -1)
+    t["slot_keys"], t["slot_counts"] = _pair_table_views(ws, N, mp, 1)
     t.setdefault("counts_pred", None)
     t.setdefault("counts_truth", None)
     return t
@@ -1604,8 +1616,7 @@ def regions_adjacency_workspace(N, capacity, max_pairs, device):
     table, which the call's result views"""
     why = ("regions_adjacency_labels: a call takes 0 < N <= 65535 images, a capacity >= 1 and 1 <= max_pairs <= 2^29 with "
            f"N capacity and N slots < 2^31, got {(N, capacity, max_pairs)}")
-    size = lambda *a: _lib.load().cs_regions_adjacency_workspace(*a) if 1 <= a[2] < 1 << 31 else 0  # noqa: E731  (an int argument)
-    return _workspace(size, device, why, int(N), int(capacity), int(max_pairs))
+    return _workspace(_int_max_pairs(_lib.load().cs_regions_adjacency_workspace, 2), device, why, int(N), int(capacity), int(max_pairs))
 
 
 _ADJACENCY_TABLES = ("n_neighbors", "contact", "background", "outside", "partner", "partner_sides")
@@ -1617,9 +1628,7 @@ def regions_adjacency_labels(labels, capacity, max_pairs, connectivity=1, counts
     ``want_counts=False``), n_pairs, dropped [N], n_neighbors, contact, background, outside, partner, partner_sides [N,capacity], and
     the pair table itself as views of ``ws``: slot_keys int64 [N,slots] ((a << 32) | b with a < b, 0 = empty), slot_sides and
     slot_corners int32 [N,slots] (cs_regions_adjacency_labels in include/cellseg_hip.h)."""
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("regions_adjacency_labels reads int32 [N,H,W] label images")
-    N, H, W = labels.shape
+    N, H, W = _label_images("regions_adjacency_labels", labels)
     cap, mp = int(capacity), int(max_pairs)
     want = {name: ((N, cap), torch.int32) for name in _ADJACENCY_TABLES}
     want.update(n_pairs=((N,), torch.int32), dropped=((N,), torch.int32))
@@ -1634,10 +1643,7 @@ def regions_adjacency_labels(labels, capacity, max_pairs, connectivity=1, counts
         _p(labels), N, H, W, cap, mp, int(connectivity), _p(t.get("counts")), _p(t["n_pairs"]), _p(t["dropped"]), _p(t["n_neighbors"]),
         _p(t["contact"]), _p(t["background"]), _p(t["outside"]), _p(t["partner"]), _p(t["partner_sides"]), _p(ws), ws.numel(), _stream()),
         "regions_adjacency_labels")
-    cells = N * regions_overlap_slots(mp)                              # the table leads the workspace: 8, 4 and 4 bytes per slot
-    t["slot_keys"] = ws[:8 * cells].view(torch.int64).view(N, -1)
-    t["slot_sides"] = ws[8 * cells:12 * cells].view(torch.int32).view(N, -1)
-    t["slot_corners"] = ws[12 * cells:16 * cells].view(torch.int32).view(N, -1)
+    t["slot_keys"], t["slot_sides"], t["slot_corners"] = _pair_table_views(ws, N, mp, 2)
     t.setdefault("counts", None)
     return t
 

@@ -74,6 +74,7 @@ tests/adjacency_ref.py), from which ``AdjacencyTable`` forms the touching fracti
 on the device.  ``distance=`` expands the labels first (``morph.expand_labels``), so that cells within a gap count as neighbours.
 """
 import dataclasses
+import functools
 import typing
 
 import numpy as np
@@ -112,13 +113,16 @@ def _chunks(t):
     return [(i, min(i + per, N)) for i in range(0, N, per)]
 
 
+# the workspace of the kernel calls of one batch: ``_Workspace(make)(n)`` is ``make(n)``, the workspace of a chunk of n images, kept
+# for as long as n stays the same (the chunks of a batch are equal but for the last)
+_Workspace = functools.lru_cache(maxsize=1)
+
+
 def _run(t, fn, out):
     """fn(chunk, out_chunk, workspace) over the chunks of t [N,H,W]; out: a tensor of t's shape"""
-    ws, ws_n = None, 0
+    workspace = _Workspace(lambda n: K.regions_workspace(n, t.shape[1], t.shape[2], t.device))
     for a, b in _chunks(t):
-        if ws_n != b - a:
-            ws, ws_n = K.regions_workspace(b - a, t.shape[1], t.shape[2], t.device), b - a
-        fn(t[a:b], out[a:b], ws)
+        fn(t[a:b], out[a:b], workspace(b - a))
     return out
 
 
@@ -262,14 +266,7 @@ def measure(m, intensity=None, connectivity=1, max_regions=None):
         v = v.to(t.device).contiguous().view(N, H, W)
     chunks = _chunks(t)
     counts = torch.empty((N,), dtype=torch.int32, device=t.device)
-    ws, ws_n, numbered = None, 0, False
-
-    def workspace(n):
-        nonlocal ws, ws_n
-        if ws_n != n:
-            ws, ws_n = K.regions_workspace(n, H, W, t.device), n
-        return ws
-
+    workspace, numbered = _Workspace(lambda n: K.regions_workspace(n, H, W, t.device)), False
     if max_regions is None:
         for a, b in chunks:
             K.regions_number(t[a:b], conn, counts=counts[a:b], ws=workspace(b - a))
@@ -449,6 +446,53 @@ def _as_labels(x, what, masks_go_to="label first"):
     return _images(x, what, torch.int32, f"an int32 label image, got {{}} (boolean masks go to {masks_go_to})", noun="label image")
 
 
+class _LabelImage:
+    """The front end of one label-image argument of the call ``what``, in two phases so that every argument error of a call can
+    come before its first copy.  The check, on the host: ``_as_labels``, then ``check_size(what, shape)`` where given, ``two_d`` =
+    the argument was [H, W], ``N``, and in ``with_counts`` the check of the caller's ``counts``.  ``place``: ``labels`` as
+    contiguous int32 [N, H, W] on a device, the ``chunks`` of whole images per kernel call, and for a call with counts ``own`` = the
+    device has to find them and ``counts`` = the int32 [N] tensor (the caller's where given)."""
+    own = counts = None
+
+    def __init__(self, what, x, masks_go_to="label first", check_size=None):
+        self.what, self.labels = what, _as_labels(x, what, masks_go_to)
+        if check_size is not None:
+            check_size(what, tuple(self.labels.shape))
+        self.two_d = self.labels.dim() == 2
+        self.N = 1 if self.two_d else self.labels.shape[0]
+
+    def with_counts(self, counts, name="counts", what=None):
+        """``what``: the call the message names, where it is not this one's"""
+        if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (self.N,)):
+            raise TypeError(f"{what or self.what}: {name} must be an int32 tensor of shape ({self.N},)")
+        self.own, self.counts = counts is None, counts
+        return self
+
+    @functools.cached_property
+    def chunks(self):
+        return _chunks(self.labels)                                      # (of the placed labels)
+
+    def place(self, dev=None):
+        """``dev``: None = the labels' own device, for host labels the current one -> (labels, counts)"""
+        t = self.labels.unsqueeze(0) if self.two_d else self.labels
+        dev = dev or (t.device if t.is_cuda else _device())
+        self.labels = (t if t.device == dev else t.to(dev)).contiguous()
+        if self.own is not None:
+            self.counts = torch.empty((self.N,), dtype=torch.int32, device=dev) if self.own else self.counts.to(dev).contiguous()
+        return self.labels, self.counts
+
+
+def _largest_labels(probe, *sides):
+    """The capacities that hold every label of the batch, one per placed ``_LabelImage`` of ``sides`` (1 where a side has no label).
+    ``probe``: the caller's run at capacity 1, which leaves the largest labels in the sides' ``counts``; made only if a side's counts
+    were not given.  One synchronisation."""
+    if any(s.own for s in sides):
+        probe()
+    top = [s.counts.max() for s in sides]
+    top = (top[0] if len(top) == 1 else torch.stack(top)).cpu().reshape(-1)
+    return tuple(max(1, int(x)) for x in top)
+
+
 def measure_labels(labels, intensity=None, max_regions=None, counts=None):
     """``measure`` for a label image: int32 [H, W] or [N, H, W] (numpy or torch; 0 and below = background) -> ``RegionTable`` whose
     row k belongs to label k + 1.  A label that owns no pixel (an empty cell of ``split``) leaves an all-zero row, its bounding box
@@ -458,43 +502,60 @@ def measure_labels(labels, intensity=None, max_regions=None, counts=None):
     ``max_regions=None`` reads the largest count back (the one synchronisation; without ``counts`` after a pass that finds them)
     and measures with exactly that capacity (1 when there is no label).  Only int32 is taken; boolean masks go to ``measure``."""
     _check_max_regions(max_regions)
-    t = _as_labels(labels, "measure_labels", masks_go_to="measure")
-    v = None if intensity is None else _as_intensity(intensity, t.shape)
-    n_images = 1 if t.dim() == 2 else t.shape[0]
-    if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (n_images,)):
-        raise TypeError(f"measure_labels: counts must be an int32 tensor of shape ({n_images},)")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if not t.is_cuda:
-        t = t.to(_device())
-    t = t.contiguous()
+    img = _LabelImage("measure_labels", labels, masks_go_to="measure")
+    v = None if intensity is None else _as_intensity(intensity, img.labels.shape)
+    t, counts = img.with_counts(counts).place()
     N, H, W = t.shape
     dev = t.device
     if v is not None:
         v = v.to(dev).contiguous().view(N, H, W)
-    chunks = _chunks(t)
-    own_counts = counts is None
-    if own_counts:
-        counts = torch.empty((N,), dtype=torch.int32, device=dev)
-    else:
-        counts = counts.to(dev).contiguous()
 
     def run(cap, want_counts):
         area, bbox, sums, isum, imax = _tables(N, cap, v is not None, dev)
-        for a, b in chunks:
+        for a, b in img.chunks:
             K.regions_measure_labels(t[a:b], cap, None if v is None else v[a:b], counts[a:b] if want_counts else None, area[a:b], bbox[a:b],
                                      sums[a:b], None if v is None else isum[a:b], None if v is None else imax[a:b], want_counts=want_counts)
         return RegionTable(counts, cap, area, bbox, sums, isum, imax)
 
     if max_regions is not None:
-        return run(int(max_regions), own_counts)
-    if own_counts:
-        run(1, True)                                                     # the pass that finds the largest labels
-    return run(max(1, int(counts.max())), False)                         # the one synchronisation
+        return run(int(max_regions), img.own)
+    return run(*_largest_labels(lambda: run(1, True), img), False)      # (the pass that finds the largest labels; one synchronisation)
 
 
-def _host_int(t):
-    return t.cpu().numpy().astype(np.int64)
+def _host_tables(table, names):
+    """the named device tables of a result as int64 numpy arrays: copied once, then kept in the result's ``_host``"""
+    if table._host is None:
+        table._host = tuple(getattr(table, k).cpu().numpy().astype(np.int64) for k in names)
+    return table._host
+
+
+def _grow_pairs(run, start, most):
+    """``run(pairs)`` -> a table, from ``min(start, most)`` pairs on and with twice as many (at most ``most``) for as long as the
+    table's ``dropped.max()``, read back after every run (a synchronisation per turn), is non-zero: with a ``most`` that holds every
+    pair the table returned has lost none."""
+    pairs = min(start, most)
+    while True:
+        table = run(pairs)
+        if int(table.dropped.max()) == 0 or pairs >= most:
+            return table
+        pairs = min(2 * pairs, most)
+
+
+def _gather_slots(calls, names):
+    """the results of the chunks' kernel calls -> name: the raw pair table's [N, slots] array of that name for the batch; one chunk:
+    the call's own views, which go on viewing its workspace"""
+    return {k: calls[0][k] if len(calls) == 1 else torch.cat([r[k] for r in calls]) for k in names}
+
+
+def _read_pairs(slot_keys, *columns):
+    """A raw pair table (``slot_keys`` int64 [N, slots], 0 = empty, and int32 count ``columns`` of that shape) -> the int64 host
+    arrays ``(image, hi, lo, *columns)`` of the occupied slots, sorted by (image, hi, lo).  One copy from the device."""
+    flat = torch.cat([slot_keys.reshape(-1), *(c.reshape(-1).to(torch.int64) for c in columns)]).cpu().numpy()
+    keys, *columns = flat.reshape(1 + len(columns), -1)
+    at = np.nonzero(keys)[0]
+    image, keys = at // slot_keys.shape[1], keys[at]
+    order = np.lexsort((keys, image))                                    # a key orders by its high, then its low label
+    return (image[order], keys[order] >> 32, keys[order] & 0xFFFFFFFF, *(c[at][order] for c in columns))
 
 
 @dataclasses.dataclass
@@ -533,9 +594,7 @@ class MatchTable:
         thresholds costs no further transfer.  ``iou_threshold``: a float in [0.5, 1]."""
         from . import score as S
         S.check_iou_threshold(iou_threshold)                              # before any transfer
-        if self._host is None:
-            self._host = tuple(_host_int(t) for t in (self.area_pred, self.area_truth, self.match, self.inter))
-        return S.label_score(*self._host, iou_threshold=iou_threshold)
+        return S.label_score(*_host_tables(self, ("area_pred", "area_truth", "match", "inter")), iou_threshold=iou_threshold)
 
 
 def _match_capacities(max_regions):
@@ -553,37 +612,25 @@ def _match_capacities(max_regions):
 
 
 class _LabelPair:
-    """The front end that ``match_labels`` and ``overlap_labels`` share: argument errors first, then ``pred`` / ``truth`` as int32
-    [N, H, W] on one device, the ``chunks`` of whole images per kernel call, ``own`` = which side's counts the device has to find,
-    and ``counts`` = the two int32 [N] tensors (the caller's where given)."""
+    """The front end that ``match_labels``, ``overlap_labels`` and ``hausdorff_labels`` share, two ``_LabelImage`` (``sides``) that
+    agree in shape: argument errors first, then ``pred`` / ``truth`` as int32 [N, H, W] on one device (pred's if it is on one, else
+    truth's, else the current one), the ``chunks`` of whole images per kernel call, ``own`` = which side's counts the device has to
+    find, and ``counts`` = the two int32 [N] tensors (the caller's where given)."""
 
     def __init__(self, what, pred, truth, pred_counts, truth_counts):
-        p, t = _as_labels(pred, what), _as_labels(truth, what)
-        if tuple(p.shape) != tuple(t.shape):
-            raise ValueError(f"{what}: pred of shape {tuple(p.shape)} against truth of shape {tuple(t.shape)}")
-        N = 1 if p.dim() == 2 else p.shape[0]
-        for c, name in ((pred_counts, "pred_counts"), (truth_counts, "truth_counts")):
-            if c is not None and not (torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == (N,)):
-                raise TypeError(f"{what}: {name} must be an int32 tensor of shape ({N},)")
-        dev = p.device if p.is_cuda else t.device if t.is_cuda else _device()
-        self.pred, self.truth = (x.reshape((N,) + tuple(x.shape[-2:])).to(dev).contiguous() for x in (p, t))
-        self.N, self.dev, self.chunks = N, dev, _chunks(self.pred)
-        self.own = (pred_counts is None, truth_counts is None)
-        self.counts = tuple(torch.empty((N,), dtype=torch.int32, device=dev) if c is None else c.to(dev).contiguous()
-                            for c in (pred_counts, truth_counts))
+        self.sides = p, t = _LabelImage(what, pred), _LabelImage(what, truth)
+        if tuple(p.labels.shape) != tuple(t.labels.shape):
+            raise ValueError(f"{what}: pred of shape {tuple(p.labels.shape)} against truth of shape {tuple(t.labels.shape)}")
+        p.with_counts(pred_counts, "pred_counts"), t.with_counts(truth_counts, "truth_counts")
+        dev = p.labels.device if p.labels.is_cuda else t.labels.device if t.labels.is_cuda else _device()
+        (self.pred, _), (self.truth, _) = p.place(dev), t.place(dev)
+        self.N, self.dev, self.chunks = p.N, dev, p.chunks
+        self.own, self.counts = (p.own, t.own), (p.counts, t.counts)
 
     def calls(self, want):
         """per chunk: (slice of the images, pred, truth, counts_pred | None, counts_truth | None) as a kernel call takes them"""
         for a, b in self.chunks:
             yield slice(a, b), self.pred[a:b], self.truth[a:b], *(c[a:b] if w else None for c, w in zip(self.counts, want))
-
-    def largest_labels(self, probe):
-        """The capacities that hold every label of the batch (1 where a side has none).  ``probe``: the caller's run at capacity
-        1, which leaves the largest labels in ``counts``; made only if a side's counts were not given.  One synchronisation."""
-        if self.own[0] or self.own[1]:
-            probe()
-        top = torch.stack([c.max() for c in self.counts]).cpu()
-        return max(1, int(top[0])), max(1, int(top[1]))
 
 
 def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=None):
@@ -612,16 +659,14 @@ def match_labels(pred, truth, max_regions=None, pred_counts=None, truth_counts=N
 
     def run(cap_p, cap_t, want):
         tabs = [torch.empty((pair.N, c), dtype=torch.int32, device=pair.dev) for c in (cap_p, cap_t, cap_p, cap_p, cap_t)]
-        ws, ws_n = None, 0
+        workspace = _Workspace(lambda n: K.regions_match_workspace(n, cap_p, cap_t, pair.dev))
         for at, p, t, cp, ct in pair.calls(want):
-            if ws_n != len(p):
-                ws, ws_n = K.regions_match_workspace(len(p), cap_p, cap_t, pair.dev), len(p)
-            K.regions_match_labels(p, t, cap_p, cap_t, cp, ct, *(x[at] for x in tabs), want_counts=want, ws=ws)
+            K.regions_match_labels(p, t, cap_p, cap_t, cp, ct, *(x[at] for x in tabs), want_counts=want, ws=workspace(len(p)))
         return MatchTable(*pair.counts, cap_p, cap_t, *tabs)
 
     if caps is not None:
         return run(*caps, pair.own)
-    return run(*pair.largest_labels(lambda: run(1, 1, pair.own)), (False, False))
+    return run(*_largest_labels(lambda: run(1, 1, pair.own), *pair.sides), (False, False))
 
 
 _OVERLAP_HOST = ("area_pred", "area_truth", "iou_partner", "iou_inter", "inter_partner_truth", "inter_truth", "inter_partner_pred",
@@ -664,20 +709,13 @@ class OverlapTable:
     def pairs(self):
         """The sparse contingency table on the host: int64 arrays ``(image, pred, truth, inter)``, one entry per pair that shares a
         pixel, sorted by (image, pred, truth).  One copy from the device (it synchronises)."""
-        flat = torch.cat([self.slot_keys.reshape(-1), self.slot_counts.reshape(-1).to(torch.int64)]).cpu().numpy()
-        keys, inter = flat[:flat.size // 2], flat[flat.size // 2:]
-        at = np.nonzero(keys)[0]
-        image, keys, inter = at // self.slot_keys.shape[1], keys[at], inter[at]
-        order = np.lexsort((keys, image))                                # a key orders by pred, then truth
-        return image[order], keys[order] >> 32, keys[order] & 0xFFFFFFFF, inter[order]
+        return _read_pairs(self.slot_keys, self.slot_counts)
 
     def score(self):
         """AJI and object-level Dice per image -> ``score.OverlapScore`` (``score.overlap_score`` has the formulas).  It
         synchronises: the integer tables are copied to the host once and kept."""
         from . import score as S
-        if self._host is None:
-            self._host = tuple(_host_int(getattr(self, k)) for k in _OVERLAP_HOST)
-        return S.overlap_score(*self._host)
+        return S.overlap_score(*_host_tables(self, _OVERLAP_HOST))
 
 
 def _check_max_pairs(max_pairs):
@@ -713,27 +751,18 @@ def overlap_labels(pred, truth, max_regions=None, max_pairs=None, pred_counts=No
     def run(cap_p, cap_t, pairs, want):
         tabs = {k: torch.empty((N, (cap_p, cap_t)[side]), dtype=torch.int32, device=dev) for k, side in K._OVERLAP_TABLES}
         tabs.update(n_pairs=torch.empty((N,), dtype=torch.int32, device=dev), dropped=torch.empty((N,), dtype=torch.int32, device=dev))
-        slots = []
-        for at, p, t, cp, ct in pair.calls(want):                        # a workspace per call: the result views its pair table
-            r = K.regions_overlap_labels(p, t, cap_p, cap_t, pairs, cp, ct, **{k: x[at] for k, x in tabs.items()}, want_counts=want)
-            slots.append((r["slot_keys"], r["slot_counts"]))
-        keys, counts = slots[0] if len(slots) == 1 else (torch.cat([s[i] for s in slots]) for i in (0, 1))
-        return OverlapTable(*pair.counts, cap_p, cap_t, *(tabs[k] for k in ("area_pred", "area_truth", "n_pairs", "dropped", "iou_partner",
-                                                                            "iou_inter", "inter_partner_truth", "inter_truth",
-                                                                            "inter_partner_pred", "inter_pred")), keys, counts)
+        # (a workspace per call: the result views its pair table)
+        calls = [K.regions_overlap_labels(p, t, cap_p, cap_t, pairs, cp, ct, **{k: x[at] for k, x in tabs.items()}, want_counts=want)
+                 for at, p, t, cp, ct in pair.calls(want)]
+        return OverlapTable(*pair.counts, cap_p, cap_t, **tabs, **_gather_slots(calls, ("slot_keys", "slot_counts")))
 
     want = pair.own
     if caps is None:
-        caps, want = pair.largest_labels(lambda: run(1, 1, 1, pair.own)), (False, False)
+        caps, want = _largest_labels(lambda: run(1, 1, 1, pair.own), *pair.sides), (False, False)
     if max_pairs is not None:
         return run(caps[0], caps[1], int(max_pairs), want)
     most = pair.pred.shape[1] * pair.pred.shape[2]                       # an image has no more pairs than pixels
-    pairs = min(4 * (caps[0] + caps[1]), most)
-    while True:
-        table = run(caps[0], caps[1], pairs, want)
-        if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
-            return table
-        pairs = min(2 * pairs, most)
+    return _grow_pairs(lambda pairs: run(caps[0], caps[1], pairs, want), 4 * (caps[0] + caps[1]), most)
 
 
 @dataclasses.dataclass
@@ -778,13 +807,7 @@ class AdjacencyTable:
     def pairs(self):
         """The listed pairs on the host: int64 arrays ``(image, a, b, sides, corners)`` with a < b, sorted by (image, a, b).  One
         copy from the device (it synchronises)."""
-        flat = torch.cat([self.slot_keys.reshape(-1), self.slot_sides.reshape(-1).to(torch.int64),
-                          self.slot_corners.reshape(-1).to(torch.int64)]).cpu().numpy()
-        keys, sides, corners = flat.reshape(3, -1)
-        at = np.nonzero(keys)[0]
-        image, keys = at // self.slot_keys.shape[1], keys[at]
-        order = np.lexsort((keys, image))                                # a key orders by a, then b
-        return image[order], keys[order] >> 32, keys[order] & 0xFFFFFFFF, sides[at][order], corners[at][order]
+        return _read_pairs(self.slot_keys, self.slot_sides, self.slot_corners)
 
     def edge_index(self):
         """The cell graph in COO form, on the device: ``(edge_index, image, sides, corners)``, int64 [2, E] = the 0-based rows
@@ -865,49 +888,29 @@ def adjacency_labels(labels, connectivity=1, distance=None, radius_sq=None, max_
     if distance is not None or radius_sq is not None:
         from . import morph as M
         r2 = M._r2("adjacency_labels", distance, radius_sq, name="distance")
-    t = _as_labels(labels, "adjacency_labels")
-    n_images = 1 if t.dim() == 2 else t.shape[0]
-    if counts is not None and not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (n_images,)):
-        raise TypeError(f"adjacency_labels: counts must be an int32 tensor of shape ({n_images},)")
+    img = _LabelImage("adjacency_labels", labels).with_counts(counts)
     if r2 is not None:
-        t = M.expand_labels(t, radius_sq=r2)
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if not t.is_cuda:
-        t = t.to(_device())
-    t = t.contiguous()
+        img.labels = M.expand_labels(img.labels, radius_sq=r2)
+    t, counts = img.place()
     N, H, W = t.shape
     dev = t.device
-    chunks = _chunks(t)
-    own = counts is None
-    counts = torch.empty((N,), dtype=torch.int32, device=dev) if own else counts.to(dev).contiguous()
 
     def run(cap, pairs, want):
         tabs = {k: torch.empty((N, cap), dtype=torch.int32, device=dev) for k in K._ADJACENCY_TABLES}
         tabs.update(n_pairs=torch.empty((N,), dtype=torch.int32, device=dev), dropped=torch.empty((N,), dtype=torch.int32, device=dev))
-        slots = []
-        for a, b in chunks:                                              # a workspace per call: the result views its pair table
-            r = K.regions_adjacency_labels(t[a:b], cap, pairs, conn, counts[a:b] if want else None,
-                                           **{k: x[a:b] for k, x in tabs.items()}, want_counts=want)
-            slots.append(tuple(r[k] for k in ("slot_keys", "slot_sides", "slot_corners")))
-        table = slots[0] if len(slots) == 1 else tuple(torch.cat([s[i] for s in slots]) for i in range(3))
-        return AdjacencyTable(counts, cap, conn, tabs["n_pairs"], tabs["dropped"], *(tabs[k] for k in K._ADJACENCY_TABLES), *table)
+        # (a workspace per call: the result views its pair table)
+        calls = [K.regions_adjacency_labels(t[a:b], cap, pairs, conn, counts[a:b] if want else None,
+                                            **{k: x[a:b] for k, x in tabs.items()}, want_counts=want) for a, b in img.chunks]
+        return AdjacencyTable(counts, cap, conn, **tabs, **_gather_slots(calls, ("slot_keys", "slot_sides", "slot_corners")))
 
     if max_regions is not None:
-        cap, want = int(max_regions), own
+        cap, want = int(max_regions), img.own
     else:
-        if own:
-            run(1, 1, True)                                              # the pass that finds the largest labels
-        cap, want = max(1, int(counts.max())), False                     # the one synchronisation
+        (cap,), want = _largest_labels(lambda: run(1, 1, True), img), False      # (the pass that finds the largest labels)
     if max_pairs is not None:
         return run(cap, int(max_pairs), want)
     most = min(4 * H * W, 1 << 29)                                       # an image has fewer pairs than sides and diagonals
-    pairs = min(4 * cap, most)
-    while True:
-        table = run(cap, pairs, want)
-        if int(table.dropped.max()) == 0 or pairs >= most:               # (a synchronisation per turn)
-            return table
-        pairs = min(2 * pairs, most)
+    return _grow_pairs(lambda pairs: run(cap, pairs, want), 4 * cap, most)
 
 
 def adjacency(m, connectivity=1, distance=None, radius_sq=None, max_regions=None, max_pairs=None):
@@ -955,9 +958,7 @@ class HausdorffTable:
         """Object-level Hausdorff distance per image -> ``score.HausdorffScore`` (``score.hausdorff_score`` has the formulas).  It
         synchronises: the integer tables are copied to the host once and kept."""
         from . import score as S
-        if self._host is None:
-            self._host = tuple(_host_int(getattr(self, k)) for k in _HAUSDORFF_HOST)
-        return S.hausdorff_score(*self._host)
+        return S.hausdorff_score(*_host_tables(self, _HAUSDORFF_HOST))
 
 
 def _check_hausdorff_shape(shape):
@@ -1013,14 +1014,12 @@ def hausdorff_labels(pred, truth, overlap=None, max_regions=None, max_pairs=None
     cap_p, cap_t = overlap.cap_pred, overlap.cap_truth
     tabs = {k: torch.empty((N, cap), dtype=torch.int32, device=dev)
             for k, cap in (("partner_truth", cap_t), ("d2_truth", cap_t), ("partner_pred", cap_p), ("d2_pred", cap_p))}
-    ws, ws_n = None, 0
+    workspace = _Workspace(lambda n: K.regions_hausdorff_workspace(n, cap_p, cap_t, dev))
     for at, p, t, _, _ in pair.calls((False, False)):
-        if ws_n != len(p):
-            ws, ws_n = K.regions_hausdorff_workspace(len(p), cap_p, cap_t, dev), len(p)
         K.regions_hausdorff_labels(p, t, cap_p, cap_t, overlap.inter_partner_truth[at], overlap.inter_partner_pred[at],
-                                   **{k: x[at] for k, x in tabs.items()}, ws=ws)
+                                   **{k: x[at] for k, x in tabs.items()}, ws=workspace(len(p)))
     return HausdorffTable(overlap.counts_pred, overlap.counts_truth, cap_p, cap_t, overlap.area_pred, overlap.area_truth, overlap.dropped,
-                          tabs["partner_truth"], tabs["d2_truth"], tabs["partner_pred"], tabs["d2_pred"])
+                          **tabs)
 
 
 _SQRT2 = 2.0 ** 0.5
@@ -1119,37 +1118,29 @@ def _check_shape_size(what, shape):
         raise ValueError(f"{what}: a {shape[-2]}x{shape[-1]} image: H, W <= {K.REGIONS_SHAPE_MAX_SIDE} keep the second moments in int64")
 
 
-def _device_labels(t):
-    """a checked label image -> contiguous int32 [N, H, W] on the device"""
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    return (t if t.is_cuda else t.to(_device())).contiguous()
-
-
 def _labels_and_table(what, labels, table, max_regions, counts, masks_go_to, check_size=None):
-    """The arguments that ``shape_labels`` and ``hull_labels`` share -> (contiguous int32 [N, H, W] on the device, the
-    ``RegionTable`` of those images, whether ``labels`` was [H, W]).  Every argument error is raised before anything is copied; a
-    table of None runs ``measure_labels`` with ``max_regions`` and ``counts``."""
+    """The arguments that ``shape_labels``, ``hull_labels`` and ``contour_labels`` share -> (the placed ``_LabelImage``, the
+    ``RegionTable`` of those images).  Every argument error is raised before anything is copied; a table of None runs
+    ``measure_labels`` with ``max_regions`` and ``counts``."""
     _check_max_regions(max_regions)
     if table is not None and not isinstance(table, RegionTable):
         raise TypeError(f"{what}: table must be a RegionTable or None, got {type(table).__name__}")
-    t = _as_labels(labels, what, masks_go_to=masks_go_to)
-    if check_size is not None:
-        check_size(what, tuple(t.shape))
-    two_d = t.dim() == 2
-    N = 1 if two_d else t.shape[0]
+    img = _LabelImage(what, labels, masks_go_to, check_size)
+    N = img.N
     if table is not None:
         if max_regions is not None and int(max_regions) != table.capacity:
             raise ValueError(f"{what}: max_regions {max_regions} against a RegionTable of capacity {table.capacity}")
         if tuple(table.bbox.shape) != (N, table.capacity, 4):
             raise ValueError(f"{what}: a RegionTable of {tuple(table.bbox.shape[:2])} (images, capacity) with capacity "
                              f"{table.capacity} for {N} images")
-    t = _device_labels(t)
+    if table is None:
+        img.with_counts(counts, what="measure_labels")                   # (read by measure_labels below, and refused in its name)
+    t, _ = img.place()
     if table is None:
         table = measure_labels(t, max_regions=max_regions, counts=counts)
     elif table.bbox.device != t.device:
         raise ValueError(f"{what}: a RegionTable on {table.bbox.device} for label images on {t.device}")
-    return t, table, two_d
+    return img, table
 
 
 def boundaries(x, connectivity=1):
@@ -1159,17 +1150,16 @@ def boundaries(x, connectivity=1):
     foreground pixels may be different objects, each the other's "not this object".  Never synchronises."""
     t = _tensor(x)
     if torch.is_tensor(t) and t.dtype == torch.bool:
-        lab = label(t, connectivity)
+        t = label(t, connectivity)
     else:
         _check_connectivity(connectivity)
-        lab = _as_labels(t, "boundaries", masks_go_to="label first, which boundaries does for them")
-    two_d = lab.dim() == 2
-    lab = _device_labels(lab)
+    img = _LabelImage("boundaries", t, masks_go_to="label first, which boundaries does for them")
+    lab, _ = img.place()
     edges = torch.empty(lab.shape, dtype=torch.uint8, device=lab.device)
-    for a, b in _chunks(lab):
+    for a, b in img.chunks:
         K.regions_edges_labels(lab[a:b], edges=edges[a:b])
     edges = edges.view(torch.bool)
-    return edges[0] if two_d else edges
+    return edges[0] if img.two_d else edges
 
 
 def shape_labels(labels, table=None, max_regions=None, counts=None):
@@ -1203,18 +1193,18 @@ def shape_labels(labels, table=None, max_regions=None, counts=None):
     with ``max_regions`` and ``counts`` as given here.  With a table, or an int ``max_regions``, three launches whose grids depend
     on the shape and the capacity alone follow, nothing synchronises and the call can be captured into a graph; all accumulation is
     integer atomics, so the result does not depend on launch or arrival order."""
-    t, table, two_d = _labels_and_table("shape_labels", labels, table, max_regions, counts, "shape", _check_shape_size)
-    N, dev = t.shape[0], t.device
+    img, table = _labels_and_table("shape_labels", labels, table, max_regions, counts, "shape", _check_shape_size)
+    t, N, dev = img.labels, img.N, img.labels.device
     cap = table.capacity
     edges = torch.empty(t.shape, dtype=torch.uint8, device=dev)
     moments = torch.empty((N, cap, 3), dtype=torch.int64, device=dev)
     tallies = torch.empty((N, cap, 4), dtype=torch.int32, device=dev)
     bbox = table.bbox.contiguous()
-    for a, b in _chunks(t):
+    for a, b in img.chunks:
         K.regions_edges_labels(t[a:b], edges=edges[a:b])
         K.regions_shape_labels(t[a:b], edges[a:b], cap, bbox[a:b], moments=moments[a:b], tallies=tallies[a:b])
     edges = edges.view(torch.bool)
-    return ShapeTable(table, moments, tallies, edges[0] if two_d else edges)
+    return ShapeTable(table, moments, tallies, edges[0] if img.two_d else edges)
 
 
 def shape(m, connectivity=1, max_regions=None, intensity=None):
@@ -1322,11 +1312,11 @@ def hull_labels(labels, table=None, max_regions=None, counts=None):
     ``table``, ``max_regions`` and ``counts`` as in ``shape_labels``.  With a table, or an int ``max_regions``, one launch whose
     grid depends on (N, capacity) alone follows, nothing synchronises and the call can be captured into a graph; there are no
     atomics, so the result does not depend on launch order."""
-    t, table, _ = _labels_and_table("hull_labels", labels, table, max_regions, counts, "hull")
-    cap = table.capacity
-    hull = torch.empty((t.shape[0], cap, 5), dtype=torch.int32, device=t.device)
+    img, table = _labels_and_table("hull_labels", labels, table, max_regions, counts, "hull")
+    t, cap = img.labels, table.capacity
+    hull = torch.empty((img.N, cap, 5), dtype=torch.int32, device=t.device)
     bbox = table.bbox.contiguous()
-    for a, b in _chunks(t):
+    for a, b in img.chunks:
         K.regions_hull_labels(t[a:b], cap, bbox[a:b], hull=hull[a:b])
     return HullTable(table, hull)
 
@@ -1498,11 +1488,10 @@ def contour_labels(labels, table=None, max_regions=None, counts=None, connectivi
     that no ring is truncated.  There are no atomics: the result does not depend on launch order."""
     conn = _check_connectivity(connectivity)
     _check_max_vertices(max_vertices)
-    t, table, _ = _labels_and_table("contour_labels", labels, table, max_regions, counts, "contours")
-    N, cap = t.shape[0], table.capacity
+    img, table = _labels_and_table("contour_labels", labels, table, max_regions, counts, "contours")
+    t, N, cap, chunks = img.labels, img.N, table.capacity, img.chunks
     bbox = table.bbox.contiguous()
     contour = torch.empty((N, cap, 4), dtype=torch.int32, device=t.device)
-    chunks = _chunks(t)
     if max_vertices is None:
         for a, b in chunks:
             K.regions_contour_labels(t[a:b], cap, bbox[a:b], conn, 0, contour=contour[a:b])
