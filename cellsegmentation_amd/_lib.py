@@ -219,6 +219,7 @@ _SIGNATURES = {
     "cs_stain_conc_hist": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_float, _P, _P]),
     "cs_stain_apply": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P]),
     "cs_stain_separate": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_float, _P, _P]),
+    "cs_stain_quantify_labels": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cs_render_compose": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_float, c_int, _P, _P, c_int, _P, c_int, _P, _P]),
     "cs_render_points": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, _P]),
     "cs_polygons_rasterize": (c_int, [_P, c_longlong, _P, _P, c_int, _P, c_int, _P, _P, c_longlong] + [c_int] * 6 + [_P, _P]),

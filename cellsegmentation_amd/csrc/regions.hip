@@ -15,6 +15,8 @@
 //   shape     of a label image: the inner boundary of every object as a map, and per label the second moments about the corner of
 //             its bounding box and four tallies of its boundary pixels by neighbourhood class (the perimeter estimate's weights) --
 //             a walk of measure's kind, integer atomics per run
+//   quantify  of a label image over an RGB image: per label (and per ring of an expanded label image) the integer stain levels of
+//             its pixels -- count, sum, sum of squares, maximum, positive pixels, histogram; the same walk again
 //   hull      of a label image: per label the convex hull of its pixels' unit squares -- vertex count, twice the area, the largest
 //             squared vertex distance and the smallest width as an exact fraction; one workgroup per label, the row extents of its
 //             bounding box and the hull's vertices in LDS, no atomics and no workspace
@@ -479,6 +481,110 @@ __global__ __launch_bounds__(256) void shape_kernel(const int32_t* __restrict__ 
         for (int k = 0; k < 4; ++k) {
             const int add = (packed >> (8 * k)) & 0xFF;
             if (add) __hip_atomic_fetch_add(t.tallies + 4 * q + k, add, __ATOMIC_RELAXED, kGlobal);
+        }
+    });
+}
+
+// ---- how strongly every label is stained: integer stain levels of an RGB image, tabulated per (label, compartment) -----------------
+// A pixel belongs to (row labels[p] - 1, compartment 0) where labels[p] > 0, else to (row expanded[p] - 1, compartment 1) where
+// there is an expanded image and expanded[p] > 0, else to nothing.  Its level of stain s is
+//   clamp((Mq[n][s][0] od_q[R] + Mq[n][s][1] od_q[G] + Mq[n][s][2] od_q[B] + 2^23) >> 24, 0, 255)      (int64, arithmetic shift),
+// at most 2^31 * 22713 * 3 + 2^23 < 2^48 in magnitude.  Per (image, row, compartment) n, and per stain the sum, the sum of squares,
+// the maximum of the level, the pixels with level >= pos_level[s], and with bins > 0 the pixels per bin = level * bins >> 8.
+struct QuantTables {
+    int32_t* n;          // [N][cap][C]
+    long long* sum;      // [N][cap][C][K]
+    long long* sumsq;    // [N][cap][C][K]
+    int32_t* mx;         // [N][cap][C][K]
+    int32_t* pos;        // [N][cap][C][K]
+    int32_t* hist;       // [N][cap][C][K][bins], bins > 0
+    int32_t* maxlab;     // [N] or NULL
+    int C, bins;
+    int pos_level[3];    // 256 = no pixel is positive
+};
+
+__global__ __launch_bounds__(256) void quantify_init_kernel(long long slots, int K, int N, QuantTables t) {
+    const long long cells = slots * K, all = t.bins ? cells * t.bins : cells;      // >= slots >= N
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+        if (t.bins) t.hist[i] = 0;
+        if (i < cells) {
+            t.sum[i] = 0;
+            t.sumsq[i] = 0;
+            t.mx[i] = 0;
+            t.pos[i] = 0;
+        }
+        if (i < slots) t.n[i] = 0;
+        if (i < N && t.maxlab) t.maxlab[i] = 0;
+    }
+}
+
+// The runs of measure_kernel<true>, a run being a stretch of lanes with the same (row, compartment): id = the label for
+// compartment 0, minus the label for compartment 1, 0 where the pixel belongs to nothing.  Every lane reads the three bytes of its
+// own pixel, so nothing is asked of the image's alignment; a wave's loads cover 192 consecutive bytes.  Per stain three ints go
+// through the segmented reduction: sum | positives << 16 (a run has at most 64 pixels: 64 * 255 < 2^16), the sum of squares
+// (64 * 255^2 < 2^23) and the maximum.  The head lane adds them with one atomic each; the histogram is added per pixel.
+template <int K>
+__global__ __launch_bounds__(256) void quantify_kernel(const uint8_t* __restrict__ rgb, const int32_t* __restrict__ lab,
+                                                       const int32_t* __restrict__ expd, int N, int H, int W,
+                                                       const int32_t* __restrict__ od_q, const int32_t* __restrict__ Mq, int cap, QuantTables t) {
+    __shared__ int32_t s_od[256];
+    s_od[threadIdx.x] = od_q[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    walk_row_segments(N, H, W, [&](int n, int r, int c, long long p) {
+        const bool in = c < W;
+        int id = in ? max(lab[p], 0) : 0;
+        if (expd && in && id == 0) id = -max(expd[p], 0);
+        const unsigned long long bal = __ballot(id != 0);
+        if (bal == 0) return;
+        const int l = id < 0 ? -id : id, comp = id < 0;
+        const bool measured = id != 0 && l <= cap;
+        const long long slot = ((long long)n * cap + l - 1) * t.C + comp;  // used where `measured` only
+        int a[K], b[K], m[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) a[s] = b[s] = m[s] = 0;
+        if (measured) {
+            const uint8_t* px = rgb + 3 * p;
+            const long long qr = s_od[px[0]], qg = s_od[px[1]], qb = s_od[px[2]];
+            const int32_t* mq = Mq + (long long)n * K * 3;
+#pragma unroll
+            for (int s = 0; s < K; ++s) {
+                const long long acc = mq[3 * s] * qr + mq[3 * s + 1] * qg + mq[3 * s + 2] * qb + (1LL << 23);
+                const long long sh = acc >> 24;
+                const int lv = (int)(sh < 0 ? 0 : sh > 255 ? 255 : sh);
+                a[s] = lv | (int)(lv >= t.pos_level[s]) << 16;
+                b[s] = lv * lv;
+                m[s] = lv;
+                if (t.bins) __hip_atomic_fetch_add(t.hist + ((slot * K + s) * t.bins + ((lv * t.bins) >> 8)), 1, __ATOMIC_RELAXED, kGlobal);
+            }
+        }
+        int len;
+        const bool head = run_of(bal, __ballot(id != 0 && id != __shfl_up(id, 1)), lane, len);
+        const int last = id != 0 ? lane + len - 1 : lane;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {                       // lane i: over [i, min(i + 2 off - 1, last)]
+#pragma unroll
+            for (int s = 0; s < K; ++s) {
+                const int oa = __shfl_down(a[s], off), ob = __shfl_down(b[s], off), om = __shfl_down(m[s], off);
+                if (lane + off <= last) {
+                    a[s] += oa;
+                    b[s] += ob;
+                    m[s] = max(m[s], om);
+                }
+            }
+        }
+        if (!head) return;
+        if (t.maxlab) raise_to(t.maxlab + n, l);
+        if (!measured) return;
+        __hip_atomic_fetch_add(t.n + slot, len, __ATOMIC_RELAXED, kGlobal);
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const long long q = slot * K + s;
+            const int sum = a[s] & 0xFFFF, pos = a[s] >> 16;
+            if (sum) __hip_atomic_fetch_add(t.sum + q, (long long)sum, __ATOMIC_RELAXED, kGlobal);
+            if (b[s]) __hip_atomic_fetch_add(t.sumsq + q, (long long)b[s], __ATOMIC_RELAXED, kGlobal);
+            if (pos) __hip_atomic_fetch_add(t.pos + q, pos, __ATOMIC_RELAXED, kGlobal);
+            raise_to(t.mx + q, m[s]);
         }
     });
 }
@@ -2043,6 +2149,40 @@ extern "C" int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edg
     hipLaunchKernelGGL(shape_init_kernel, dim3(grid_for(4 * rows)), dim3(256), 0, st, rows, t);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(shape_kernel, walk_grid(N, H, W), dim3(256), 0, st, labels, edges, N, H, W, capacity, t);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_stain_quantify_labels(const uint8_t* images_hwc, const int32_t* labels, const int32_t* expanded, int N, int H, int W,
+                                        const int32_t* od_q, const int32_t* Mq, int K, const int32_t* pos_levels, int bins, int capacity,
+                                        int32_t* counts, int32_t* n, int64_t* sum, int64_t* sumsq, int32_t* vmax, int32_t* pos,
+                                        int32_t* hist, void* stream) {
+    CS_CHECK_ARG(images_hwc && labels && od_q && Mq, "stain_quantify_labels: NULL argument");
+    CS_CHECK_ARG(n && sum && sumsq && vmax && pos, "stain_quantify_labels: NULL table");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "stain_quantify_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG(K == 2 || K == 3, "stain_quantify_labels: need K = 2 or 3 stains");
+    CS_CHECK_ARG(bins == 0 || bins == 16 || bins == 32 || bins == 64 || bins == 128 || bins == 256,
+                 "stain_quantify_labels: bins must be 0, 16, 32, 64, 128 or 256");
+    CS_CHECK_ARG((bins == 0) == (hist == nullptr), "stain_quantify_labels: hist goes with bins > 0");
+    CS_CHECK_ARG(capacity >= 1, "stain_quantify_labels: need capacity >= 1");
+    const int C = expanded ? 2 : 1;
+    CS_CHECK_ARG((long long)N * capacity * C * K * (bins ? bins : 1) < (1LL << 31), "stain_quantify_labels: need N capacity C K bins < 2^31");
+    CS_CHECK_ARG(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(expanded) | reinterpret_cast<uintptr_t>(od_q) |
+                   reinterpret_cast<uintptr_t>(Mq)) & 3) == 0 && ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(sumsq)) & 7) == 0,
+                 "stain_quantify_labels: misaligned argument");
+    QuantTables t{n, reinterpret_cast<long long*>(sum), reinterpret_cast<long long*>(sumsq), vmax, pos, hist, counts, C, bins, {256, 256, 256}};
+    for (int s = 0; s < K && pos_levels; ++s) {
+        CS_CHECK_ARG(pos_levels[s] >= 0 && pos_levels[s] <= 256, "stain_quantify_labels: a positive level lies in [0, 256]");
+        t.pos_level[s] = pos_levels[s];
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long slots = (long long)N * capacity * C;
+    hipLaunchKernelGGL(quantify_init_kernel, dim3(grid_for(slots * K * (bins ? bins : 1))), dim3(256), 0, st, slots, K, N, t);
+    CS_LAUNCH_CHECK();
+    if (K == 2)
+        hipLaunchKernelGGL(quantify_kernel<2>, walk_grid(N, H, W), dim3(256), 0, st, images_hwc, labels, expanded, N, H, W, od_q, Mq, capacity, t);
+    else
+        hipLaunchKernelGGL(quantify_kernel<3>, walk_grid(N, H, W), dim3(256), 0, st, images_hwc, labels, expanded, N, H, W, od_q, Mq, capacity, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

@@ -594,6 +594,41 @@ def slide_contacts(result, distance=None, connectivity=1, max_pairs=None, **meas
     return contacts, table, parts
 
 
+def slide_positivity(result, image_u8, stains=None, thresholds=(0.2, 0.4, 0.6), distance=None, stain=1, options=None, **measure_kwargs):
+    """Which DETECTED cells of a ``SlideResult`` are stained and how strongly, on the device: ``measure_slide_cells(result,
+    **measure_kwargs)``, whose split labels go to ``stain.quantify_labels`` over ``image_u8`` (uint8 RGB ``[H, W, 3]`` of the mask's
+    shape) with ``counts=parts.counts`` and the region table's capacity -> ``(PositivityScore, StainTable, RegionTable,
+    SplitResult)`` of one image.  Row k of every table is ``result.points[k]``.  ``stains``: a [3, 2] matrix or a ``StainEstimate``;
+    None estimates the slide (``stain.estimate``).  ``thresholds``: 1 to 3 increasing concentrations of stain ``stain`` (1 = DAB)
+    that a cell's mean level must reach for the classes 1+, 2+, 3+ (``StainTable.classify``).  ``distance``: the cells are grown by
+    ``morph.expand_labels`` at that distance and the ring is tabulated as compartment 1 (it is then also the compartment that is
+    classified, as a cytoplasmic stain asks for); None classifies the cells as split.  The score is read back; with an int
+    ``max_regions`` and given ``stains`` nothing else synchronises."""
+    from . import stain as St
+    if not isinstance(result, SlideResult):
+        raise TypeError("slide_positivity: expected the SlideResult of detect_slide")
+    opts = St._options(options, "slide_positivity")
+    St.class_thresholds(thresholds, opts.conc_max)
+    img = _tensor(image_u8)
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or tuple(img.shape) != tuple(result.mask.shape) + (3,):
+        raise TypeError(f"slide_positivity: image_u8 must be a uint8 RGB image shaped {tuple(result.mask.shape) + (3,)}")
+    if stains is not None:
+        St.quantised_matrix(stains, False, opts.conc_max)
+    if distance is not None:
+        from .score import radius_squared
+        radius_squared(distance)
+    table, parts = measure_slide_cells(result, **measure_kwargs)
+    img = img.to(parts.labels.device)
+    if stains is None:
+        stains = St.estimate(img, options=opts)
+    ring = None
+    if distance is not None:
+        from . import morph
+        ring = morph.expand_labels(parts.labels, distance)
+    cells = St.quantify_labels(img, parts.labels, stains, expanded=ring, table=table, options=opts)
+    return cells.score(thresholds, stain, 0 if ring is None else 1), cells, table, parts
+
+
 def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
     """Neighbourhood statistics of the detected cells of a ``SlideResult``, on the device: ``result.points`` is uploaded once and
     queried on the bucket grid of ``spatial`` with the mask's shape as the image -> ``(NeighborTable or None, WithinCounts or

@@ -2062,6 +2062,47 @@ def stain_separate(images_u8, od_q, P, as_u8=False, conc_max=1.0, out=None):
     return out
 
 
+STAIN_QUANTIFY_BINS = (0, 16, 32, 64, 128, 256)
+
+
+def stain_quantify_labels(images_u8, labels, od_q, Mq, capacity, expanded=None, pos_levels=None, bins=0, counts=None, want_counts=True,
+                          **tables):
+    """images uint8 [N,H,W,3], labels (and expanded or None) int32 [N,H,W], od_q int32 [256], Mq int32 [N,K,3] (device) -> dict of
+    n int32 [N,cap,C]; sum, sumsq int64 and max, pos int32 [N,cap,C,K]; hist int32 [N,cap,C,K,bins] (with bins) and counts int32 [N]
+    (with ``want_counts``): the integer stain levels of every (label, compartment), C = 2 with ``expanded``.  ``pos_levels``: K host
+    integers in [0, 256] or None; ``tables``: tensors to write instead of new ones (cs_stain_quantify_labels in
+    include/cellseg_hip.h)."""
+    what = "stain_quantify_labels"
+    N, H, W = _rgb_images(what, images_u8, whole_batch=True)
+    if not torch.is_tensor(od_q) or od_q.dtype != torch.int32 or tuple(od_q.shape) != (256,):
+        raise ValueError(f"{what}: od_q must be an int32 tensor shaped (256,) (stain.od_table)")
+    if not torch.is_tensor(Mq) or Mq.dtype != torch.int32 or Mq.dim() != 3 or tuple(Mq.shape) not in ((N, 2, 3), (N, 3, 3)):
+        raise ValueError(f"{what}: Mq must be an int32 tensor shaped [{N}, K, 3] with K = 2 or 3")
+    Kn, cap, bins = int(Mq.shape[1]), int(capacity), int(bins)
+    for name, x in (("labels", labels), ("expanded", expanded)):
+        if x is not None and (tuple(_label_images(what, x)) != (N, H, W)):
+            raise ValueError(f"{what}: {name} of shape {tuple(x.shape)} for images of {(N, H, W)}")
+    if bins not in STAIN_QUANTIFY_BINS:
+        raise ValueError(f"{what}: bins must be one of {STAIN_QUANTIFY_BINS}, got {bins}")
+    levels = None
+    if pos_levels is not None:
+        if len(pos_levels) != Kn:
+            raise ValueError(f"{what}: {Kn} stains but {len(pos_levels)} positive levels")
+        levels = (ctypes.c_int32 * Kn)(*[int(v) for v in pos_levels])
+    C = 1 if expanded is None else 2
+    want = {"n": ((N, cap, C), torch.int32), "sum": ((N, cap, C, Kn), torch.int64), "sumsq": ((N, cap, C, Kn), torch.int64),
+            "max": ((N, cap, C, Kn), torch.int32), "pos": ((N, cap, C, Kn), torch.int32)}
+    if bins:
+        want["hist"] = ((N, cap, C, Kn, bins), torch.int32)
+    if want_counts:
+        want["counts"] = ((N,), torch.int32)
+    t = _regions_outputs(what, want, dict(tables, counts=counts), images_u8.device)
+    _lib.check(_lib.load().cs_stain_quantify_labels(_p(images_u8), _p(labels), _p(expanded), N, H, W, _p(od_q), _p(Mq), Kn, levels, bins,
+                                                    cap, _p(t.get("counts")), _p(t["n"]), _p(t["sum"]), _p(t["sumsq"]), _p(t["max"]),
+                                                    _p(t["pos"]), _p(t.get("hist")), _stream()), what)
+    return t
+
+
 # ---------------------------------------------------------------- annotated images (csrc/render.hip; render.py is the public API)
 CS_RENDER_FILL_NONE, CS_RENDER_FILL_MASK, CS_RENDER_FILL_HEAT_U8, CS_RENDER_FILL_HEAT_F32 = 0, 1, 2, 3
 CS_RENDER_POINTS_XY, CS_RENDER_POINTS_TAIL = 1, 2

@@ -124,6 +124,33 @@ def get_prf1(points_hat, points):
 
 
 @dataclass
+class PositivityScore:
+    """Per image (arrays of length N): ``class_counts`` int64 [N, 4], the cells of class 0 (negative), 1+, 2+ and 3+; ``n_cells``
+    int64; ``labelling_index`` float64, the positive cells (class >= 1) per cell in percent; ``h_score`` float64 =
+    ``100 sum_k k f_k`` with ``f_k`` the fraction of cells in class k, from 0 to 300.  Both are NaN for an image without cells."""
+    class_counts: np.ndarray
+    n_cells: np.ndarray
+    labelling_index: np.ndarray
+    h_score: np.ndarray
+
+
+def positivity_score(class_counts):
+    """The cells per intensity class ([m] or [N, m] non-negative integers, 2 <= m <= 4: class 0 = negative, then 1+, 2+, 3+; for
+    example the classes of ``stain.StainTable.classify`` counted per image) -> ``PositivityScore``, in numpy float64: the labelling
+    index ``100 (n - n_0) / n`` and the H-score ``100 (n_1 + 2 n_2 + 3 n_3) / n``, NaN where ``n = 0``."""
+    c = np.asarray(class_counts)
+    if c.dtype.kind not in "iu" or c.ndim not in (1, 2) or not 2 <= c.shape[-1] <= 4 or (c.size and int(c.min()) < 0):
+        raise ValueError("positivity_score: expected non-negative integer cell counts shaped [m] or [N, m] with 2 <= m <= 4 classes")
+    c = np.atleast_2d(c).astype(np.int64)
+    c = np.concatenate([c, np.zeros((c.shape[0], 4 - c.shape[1]), np.int64)], axis=1)
+    n = c.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        li = 100.0 * (n - c[:, 0]).astype(np.float64) / n.astype(np.float64)
+        hs = 100.0 * (c[:, 1] + 2 * c[:, 2] + 3 * c[:, 3]).astype(np.float64) / n.astype(np.float64)
+    return PositivityScore(c, n, li, hs)
+
+
+@dataclass
 class LabelScore:
     """Per image (arrays of length N): ``n_pred``, ``n_truth`` (objects: labels that own a pixel, within the capacity), ``tp``,
     ``fp``, ``fn`` int64; ``precision``, ``recall``, ``f1``, ``sq``, ``pq`` float64."""

@@ -14,6 +14,11 @@ float64 numpy on a few KB read back three times (the moments, the angle histogra
 itself never leaves the device.  ``normalize`` re-expresses every pixel with a target's vectors and intensity range, ``separate``
 writes the concentrations themselves -- as uint8 they are ready to be the ``intensity=`` of the per-cell tables.
 
+``quantify_labels`` answers what the slide was stained for without a concentration image in between: one pass over the RGB image
+and a label image (csrc/regions.hip) leaves, per cell and per compartment (the cell, and the ring an expansion adds around it),
+exact integer tables of an integer stain level -- ``StainTable``, whose ``classify`` and ``score`` give the intensity classes, the
+labelling index and the H-score.
+
 Argument errors are raised before the library is loaded or the device is touched.
 """
 import math
@@ -290,6 +295,238 @@ def separate(images, stains=HDAB, dtype="float", residual=False, options=None):
     x = t.to(dev).contiguous()
     y = K.stain_separate(x, _od(opts, dev), _upload(P, dev), dtype == "u8", float(opts.conc_max))
     return y[0] if one else y
+
+
+# ---- per-cell stain quantification: integer levels tabulated per (label, compartment) ------------------------------------------------
+QUANTIFY_BINS = K.STAIN_QUANTIFY_BINS
+LEVEL_SHIFT = 24
+
+
+def quantised_matrix(stains, residual=False, conc_max=8.0):
+    """``Mq`` int32 [K, 3] of one image: ``rint(2^24 255 pinv(S) / (4096 conc_max))`` in float64; ``ValueError`` where an entry
+    leaves int32."""
+    _number(conc_max, "conc_max", 0, 1e30, lo_open=True)
+    M = np.rint(np.linalg.pinv(stain_matrix(stains, bool(residual))) * (float(1 << LEVEL_SHIFT) * 255.0) / (float(OD_UNIT) * float(conc_max)))
+    if not np.isfinite(M).all() or np.abs(M).max() > 2 ** 31 - 1:
+        raise ValueError(f"stains: the quantised matrix leaves int32 (largest entry {np.abs(M).max():.3g}): conc_max {conc_max} is too "
+                         "small for these stain vectors")
+    return M.astype(np.int32)
+
+
+def positive_levels(pixel_threshold, n_stains, conc_max):
+    """None | one concentration per stain -> None | the K levels ``clamp(ceil(255 t / conc_max), 0, 256)``"""
+    if pixel_threshold is None:
+        return None
+    if isinstance(pixel_threshold, (str, bytes)) or not hasattr(pixel_threshold, "__len__") or len(pixel_threshold) != n_stains:
+        raise ValueError(f"pixel_threshold must be None or {n_stains} concentrations, one per stain, got {pixel_threshold!r}")
+    for t in pixel_threshold:
+        _number(t, "pixel_threshold", -1e30, 1e30)
+    return tuple(int(min(max(math.ceil(255.0 * float(t) / float(conc_max)), 0), 256)) for t in pixel_threshold)
+
+
+def class_thresholds(thresholds, conc_max):
+    """1 to 3 increasing concentrations -> the integers ``T = rint(256 255 t / conc_max)``, each in [0, 2^31)"""
+    if isinstance(thresholds, (int, float, np.integer, np.floating)) and not isinstance(thresholds, bool):
+        thresholds = (thresholds,)
+    if isinstance(thresholds, (str, bytes)) or not hasattr(thresholds, "__len__") or not 1 <= len(thresholds) <= 3:
+        raise ValueError(f"thresholds must be 1 to 3 increasing concentrations, got {thresholds!r}")
+    for t in thresholds:
+        _number(t, "thresholds", 0, 1e30)
+    if any(b <= a for a, b in zip(thresholds, thresholds[1:])):
+        raise ValueError(f"thresholds must increase, got {thresholds!r}")
+    T = [int(np.rint(256.0 * 255.0 * float(t) / float(conc_max))) for t in thresholds]
+    if T[-1] >= 1 << 31:
+        raise ValueError(f"thresholds: {thresholds[-1]!r} is beyond 2^31 / 65280 of conc_max {conc_max}")
+    return T
+
+
+@dataclass(eq=False)
+class StainTable:
+    """``quantify_labels`` of N images as device tensors; row k belongs to label k + 1, compartment 0 is the label itself and
+    compartment 1 (only with ``expanded``) the ring around it.  ``counts`` int32 [N]: the labels in use, also above the capacity;
+    ``n`` int32 [N, cap, C] pixels; ``sum``, ``sumsq`` int64 and ``max``, ``pos`` int32 [N, cap, C, K] of the integer stain level
+    (``pos`` None without a ``pixel_threshold``); ``hist`` int32 [N, cap, C, K, bins] or None.  ``Mq`` int32 numpy [N, K, 3],
+    ``options`` and ``pos_levels`` are what it was made with.  The rules are in ``quantify_labels``' docstring.  Every method but
+    ``per_image`` and ``score`` runs on the device in float64, is computed from the integer tables only and gives NaN where
+    ``n == 0``."""
+    counts: torch.Tensor
+    capacity: int
+    n: torch.Tensor
+    sum: torch.Tensor
+    sumsq: torch.Tensor
+    max: torch.Tensor
+    pos: object
+    hist: object
+    Mq: np.ndarray
+    options: StainOptions
+    pos_levels: object = None
+
+    def _n(self):
+        return self.n.to(torch.float64).unsqueeze(-1)
+
+    def mean(self):
+        """float64 [N, cap, C, K] = sum / n, in levels"""
+        return self.sum.to(torch.float64) / self._n()
+
+    def std(self):
+        """float64 [N, cap, C, K] = sqrt(n sumsq - sum^2) / n, the population standard deviation in levels.  The numerator is an
+        exact int64 where n < 2^23 (2^23 2^23 255^2 < 2^62); a larger region forms it in float64."""
+        n64 = self.n.to(torch.int64).unsqueeze(-1)
+        exact = (n64 * self.sumsq - self.sum * self.sum).to(torch.float64)
+        s = self.sum.to(torch.float64)
+        num = torch.where(n64 < (1 << 23), exact, (self._n() * self.sumsq.to(torch.float64) - s * s).clamp(min=0))
+        return torch.sqrt(num) / self._n()
+
+    def positive_fraction(self):
+        """float64 [N, cap, C, K] = pos / n: the fraction of pixels at or above the stain's ``pixel_threshold``"""
+        if self.pos is None:
+            raise ValueError("positive_fraction: the table was made without a pixel_threshold")
+        return self.pos.to(torch.float64) / self._n()
+
+    def quantile(self, q):
+        """float64 [N, cap, C, K]: the centre, in levels, of the histogram bin that holds order statistic ``ceil(q (n - 1))`` of the
+        region's levels (``order_bin``): ``(bin + 1/2) 256 / bins - 1/2``, the level itself with 256 bins."""
+        if self.hist is None:
+            raise ValueError("quantile: the table was made without a histogram (bins=0)")
+        _number(q, "q", 0, 1)
+        bins = int(self.hist.shape[-1])
+        k = torch.ceil(float(q) * (self._n() - 1)).to(torch.int64)
+        b = (torch.cumsum(self.hist.to(torch.int64), dim=-1) <= k.unsqueeze(-1)).sum(dim=-1).to(torch.float64)
+        centre = (b + 0.5) * (256.0 / bins) - 0.5
+        return torch.where(self.n.unsqueeze(-1) > 0, centre, torch.full_like(centre, float("nan")))
+
+    def concentration(self, levels):
+        """levels (a tensor or a number) -> ``levels conc_max / 255``: the concentration a level stands for"""
+        return levels * float(self.options.conc_max) / 255.0
+
+    def overflowed(self):
+        """device bool [N]: the image has labels above the table's rows"""
+        return self.counts > self.capacity
+
+    def classify(self, thresholds, stain=1, compartment=0):
+        """int8 [N, cap] on the device: the number of ``thresholds`` (1 to 3 increasing concentrations) that the mean level of
+        ``stain`` in ``compartment`` reaches, -1 where ``n == 0``.  Exact: threshold t is ``T = rint(256 255 t / conc_max)`` and
+        reached iff ``256 sum >= T n`` in int64."""
+        T = class_thresholds(thresholds, self.options.conc_max)
+        s, c = self._pick(stain, compartment)
+        n64, lhs = self.n[:, :, c].to(torch.int64), 256 * self.sum[:, :, c, s]
+        cls = torch.zeros_like(n64)
+        for t in T:
+            cls += (lhs >= t * n64).to(torch.int64)
+        return torch.where(n64 > 0, cls, torch.full_like(cls, -1)).to(torch.int8)
+
+    def _pick(self, stain, compartment):
+        Kn, C = int(self.sum.shape[3]), int(self.sum.shape[2])
+        for v, hi, name in ((stain, Kn, "stain"), (compartment, C, "compartment")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < hi:
+                raise ValueError(f"{name} must be an integer in [0, {hi}), got {v!r}")
+        return int(stain), int(compartment)
+
+    def score(self, thresholds, stain=1, compartment=0):
+        """``score.positivity_score`` of the cells per class of ``classify`` -> ``PositivityScore``; one small copy to the host."""
+        from .score import positivity_score
+        cls = self.classify(thresholds, stain, compartment).to(torch.int64)
+        per = torch.stack([(cls == k).sum(dim=1) for k in range(4)], dim=1)
+        return positivity_score(per.cpu().numpy())
+
+    def per_image(self):
+        """A host list of N dicts of numpy arrays trimmed to min(count, capacity) rows: the integer tables that the table has, and
+        ``mean`` and ``std``.  The one method that synchronises besides ``score``."""
+        cols = {"n": self.n, "sum": self.sum, "sumsq": self.sumsq, "max": self.max, "mean": self.mean(), "std": self.std()}
+        if self.pos is not None:
+            cols["pos"] = self.pos
+        if self.hist is not None:
+            cols["hist"] = self.hist
+        cols = {k: v.cpu().numpy() for k, v in cols.items()}
+        counts = self.counts.cpu().numpy()
+        return [{k: v[i, :min(int(c), self.capacity)] for k, v in cols.items()} for i, c in enumerate(counts)]
+
+
+def quantify_labels(images, labels, stains=HDAB, residual=False, expanded=None, pixel_threshold=None, bins=0, table=None,
+                    max_regions=None, counts=None, options=None):
+    """How strongly every cell of a label image is stained -> ``StainTable``: one pass over the RGB image and the labels, no
+    concentration image in between.
+
+    ``images``: uint8 RGB [H, W, 3] or [N, H, W, 3]; ``labels`` (and ``expanded``, for example ``morph.expand_labels(labels, d)``, or
+    None): int32 [H, W] or [N, H, W] of the same size.  ``stains``: a [3, 2] matrix of optical-density vectors or a ``StainEstimate``,
+    or a list of N of them, one per image; ``residual`` adds the third stain as in ``separate``.  All rules are exact integers:
+
+    * Quantised matrix.  With ``S`` the image's [3, K] stain matrix and ``P = pinv(S)``: ``Mq[s][j] = rint(2^24 255 P[s][j] /
+      (4096 conc_max))``, float64 on the host, stored as int32 (``ValueError`` where an entry leaves int32).
+    * Level.  Stain s of a pixel (R, G, B) has the level ``clamp((Mq[s][0] od_q[R] + Mq[s][1] od_q[G] + Mq[s][2] od_q[B] + 2^23) >>
+      24, 0, 255)``, the sum in int64 and the shift arithmetic, ``od_q = od_table(options.Io)``: the uint8 concentration of
+      ``separate(dtype="u8")`` to within one level, free of float rounding and of the order of evaluation.
+    * Owner.  A pixel belongs to (row ``labels - 1``, compartment 0) where ``labels > 0``; else, with ``expanded``, to (row
+      ``expanded - 1``, compartment 1) where ``expanded > 0``; else to nothing.  Compartment 0 is the cell as segmented (the
+      nucleus), compartment 1 the ring that the expansion adds around it.
+    * Tables.  Per (image, row, compartment): ``n`` pixels; per stain the ``sum``, the sum of squares ``sumsq`` and the ``max`` of
+      the level, ``pos`` = the pixels with level >= ``L_s = clamp(ceil(255 t_s / conc_max), 0, 256)`` for ``pixel_threshold = (t_0,
+      ..)``, one concentration per stain, and with ``bins`` (16, 32, 64, 128 or 256) ``hist`` = the pixels per ``bin = level bins
+      >> 8``.  A row without a pixel is all zero.
+
+    The rules are restated in numpy by tests/quantify_ref.py (tests/golden/quantify_vectors.npz).  ``table``: the ``RegionTable`` of
+    the same labels where the caller has it: its capacity and counts are taken; otherwise ``max_regions`` and ``counts`` as in
+    ``regions.measure_labels``: an int ``max_regions`` fixes the rows per image (larger labels are counted, not measured), two
+    launches follow and nothing synchronises; None reads the largest label back first (the one synchronisation).  All accumulation
+    is integer atomics: the result does not depend on launch or arrival order.  Argument errors are raised before the library is
+    loaded."""
+    from . import regions as Rg
+    what = "quantify_labels"
+    opts = _options(options, what)
+    x, _ = _rgb(images, what)
+    N, H, W, _ = x.shape
+    Rg._check_max_regions(max_regions)
+    if table is not None and not isinstance(table, Rg.RegionTable):
+        raise TypeError(f"{what}: table must be a RegionTable or None, got {type(table).__name__}")
+    if bins not in QUANTIFY_BINS or isinstance(bins, bool):
+        raise ValueError(f"bins must be one of {QUANTIFY_BINS}, got {bins!r}")
+    img = Rg._LabelImage(what, labels, masks_go_to="regions.label first")
+    ring = None if expanded is None else Rg._LabelImage(what, expanded, masks_go_to="regions.label first")
+    for name, side in (("labels", img), ("expanded", ring)):
+        if side is not None and (side.N, tuple(side.labels.shape[-2:])) != (N, (H, W)):
+            raise ValueError(f"{what}: {name} of shape {tuple(side.labels.shape)} for images of shape {tuple(x.shape)}")
+    per = stains if isinstance(stains, (list, tuple)) else [stains] * N
+    if len(per) != N:
+        raise ValueError(f"{what}: {len(per)} stain matrices for {N} images")
+    Mq = np.stack([quantised_matrix(s, residual, opts.conc_max) for s in per])
+    levels = positive_levels(pixel_threshold, Mq.shape[1], opts.conc_max)
+    if table is not None:
+        if max_regions is not None and int(max_regions) != table.capacity:
+            raise ValueError(f"{what}: max_regions {max_regions} against a RegionTable of capacity {table.capacity}")
+        if tuple(table.counts.shape) != (N,):
+            raise ValueError(f"{what}: a RegionTable of {tuple(table.counts.shape)[0]} images for {N} images")
+        if counts is not None:
+            raise ValueError(f"{what}: counts come with the table")
+    else:
+        img.with_counts(counts)
+    dev = _device(x, img.labels)
+    x = x.to(dev).contiguous()
+    lab, counts = img.place(dev)
+    ring = None if ring is None else ring.place(dev)[0]
+    if table is not None:
+        if table.counts.device != dev:
+            raise ValueError(f"{what}: a RegionTable on {table.counts.device} for images on {dev}")
+        counts = table.counts
+    od, mq = _od(opts, dev), torch.from_numpy(Mq).to(dev)
+    Kn, C = int(Mq.shape[1]), 1 if ring is None else 2
+
+    def run(cap, want_counts):
+        new = lambda dtype, *tail: torch.empty((N, cap, C) + tail, dtype=dtype, device=dev)  # noqa: E731
+        t = {"n": new(torch.int32), "sum": new(torch.int64, Kn), "sumsq": new(torch.int64, Kn), "max": new(torch.int32, Kn),
+             "pos": new(torch.int32, Kn)}
+        if bins:
+            t["hist"] = new(torch.int32, Kn, int(bins))
+        for a, b in img.chunks:
+            K.stain_quantify_labels(x[a:b], lab[a:b], od, mq[a:b], cap, None if ring is None else ring[a:b], levels, int(bins),
+                                    counts[a:b] if want_counts else None, want_counts, **{k: v[a:b] for k, v in t.items()})
+        return StainTable(counts, cap, t["n"], t["sum"], t["sumsq"], t["max"], t["pos"] if levels is not None else None, t.get("hist"),
+                          Mq, opts, levels)
+
+    if table is not None:
+        return run(table.capacity, False)
+    if max_regions is not None:
+        return run(int(max_regions), img.own)
+    return run(*Rg._largest_labels(lambda: run(1, True), img), False)   # (the pass that finds the largest labels; one synchronisation)
 
 
 # ---- inference.detect_slide(..., stain=...) ------------------------------------------------------------------------------------------

@@ -757,6 +757,30 @@ int cs_regions_edges_labels(const int32_t* labels, int N, int H, int W, uint8_t*
 int cs_regions_shape_labels(const int32_t* labels, const uint8_t* edges, int N, int H, int W, int capacity, const int32_t* bbox,
                             int64_t* moments, int32_t* tallies, void* stream);
 
+/* ---- how strongly every object of a label image is stained: per-cell tables of integer stain levels (csrc/regions.hip) ------
+ * One pass over images uint8 [N][H][W][3] (RGB, any alignment), labels int32 [N][H][W] and, where not NULL, expanded int32
+ * [N][H][W] (cs_morph_expand_labels of the labels); sizes and the launch contract are those of cs_regions_measure_labels (two
+ * launches whose grids depend on (N, H, W, capacity, K, bins) alone, no synchronisation, capturable); no workspace.  Additions to
+ * the ABI: cs_abi_version is unchanged.  All rules are exact integers:
+ *   owner     a pixel belongs to (row labels - 1, compartment 0) where labels > 0, else to (row expanded - 1, compartment 1)
+ *             where expanded is given and > 0, else to nothing.  C = 1 compartment without expanded, 2 with it.
+ *   level     of stain s < K (K = 2 or 3) at a pixel of image n with the bytes (R, G, B):
+ *             clamp((Mq[n][s][0] od_q[R] + Mq[n][s][1] od_q[G] + Mq[n][s][2] od_q[B] + 2^23) >> 24, 0, 255), the sum in int64,
+ *             the shift arithmetic; od_q int32 [256] (device), Mq int32 [N][K][3] (device).
+ *   tables    n int32 [N][capacity][C]; sum, sumsq int64 and max, pos int32 [N][capacity][C][K]: over the pixels of (row,
+ *             compartment) their number and per stain the sum, the sum of squares and the maximum of the level and the number
+ *             of pixels with level >= pos_levels[s] (HOST int32 [K], each in [0, 256]; NULL = 256 everywhere: pos stays 0);
+ *             hist int32 [N][capacity][C][K][bins], the pixels per bin = level * bins >> 8, with bins in {16, 32, 64, 128,
+ *             256}; bins = 0 goes with hist = NULL.  Every table is zeroed by the call.
+ *   counts    (int32 [N], or NULL) is WRITTEN: the largest label that owns a pixel of the image, also above the capacity; rows
+ *             at or above the capacity are measured nowhere.
+ * Integer atomics only: independent of launch and arrival order.  Need capacity >= 1 and N capacity C K max(bins, 1) < 2^31;
+ * labels, expanded, od_q, Mq on 4-byte and sum, sumsq on 8-byte boundaries. */
+int cs_stain_quantify_labels(const uint8_t* images_hwc, const int32_t* labels, const int32_t* expanded /* may be NULL */, int N, int H,
+                             int W, const int32_t* od_q, const int32_t* Mq, int K, const int32_t* pos_levels /* host, may be NULL */,
+                             int bins, int capacity, int32_t* counts /* may be NULL */, int32_t* n, int64_t* sum, int64_t* sumsq,
+                             int32_t* max, int32_t* pos, int32_t* hist /* NULL iff bins == 0 */, void* stream);
+
 /* ---- the convex hull of every object of a label image: vertex count, area, Feret diameters (csrc/regions.hip) ----------------
  * labels int32 [N][H][W]; a pixel's object id is max(label, 0), images are independent, a label need not be connected; sizes as
  * above.  One launch whose grid depends on (N, capacity) alone, no synchronisation, capturable; no workspace and no atomics.

@@ -4,6 +4,7 @@ repetitions after a warm-up, with their spread (max - min) beside it.  ``estimat
 they are timed by the wall clock around the synchronised call, median of 5 after a warm-up.
 
     python tools/stain_microbench.py [--size 4096 16384] [--json PATH]
+    python tools/stain_microbench.py --quantify [--size 4096] [--json PATH]
 
 Synthetic slides of ``size`` x ``size`` RGB pixels, made on the device (those of tools/tissue_microbench.py):
 
@@ -16,7 +17,12 @@ Synthetic slides of ``size`` x ``size`` RGB pixels, made on the device (those of
 The yardstick is a device-to-device copy of the same image, timed in the same process: it reads and writes 3 bytes per pixel.
 ``moments`` and the two histograms read 3, ``apply`` reads 3 and writes 3 as the copy does, ``separate`` writes 2 (uint8) or 8
 (fp32) bytes per pixel for two stains.  A 4096^2 image (50 MB) stays in the 256 MiB Infinity Cache between launches, a 16384^2
-image (805 MB) cannot."""
+image (805 MB) cannot.
+
+``--quantify`` times the per-cell stain tables instead: ``stain.quantify_labels``' one launch pair (cs_stain_quantify_labels) on a
+synthetic H-DAB slide of about 10^4 labelled cells (discs on a grid, a DAB amplitude per cell), next to the path it replaces on the
+same inputs -- ``separate(dtype="u8")``, then per stain the contiguous copy of its channel and ``measure_labels(intensity=)`` -- and
+next to the device-to-device copy of the image; timed the same way, in one process."""
 import argparse
 import json
 import os
@@ -86,14 +92,89 @@ def bench(name, x, opts):
     return row
 
 
+def hdab_cells(size, dev, pitch=40, radius=12, seed=0):
+    """-> (uint8 [1, size, size, 3] slide, int32 [1, size, size] labels, cells): discs of haematoxylin on a grid of ``pitch``
+    pixels, label k + 1 = disc k, a DAB amplitude per cell in [0, 1.5] over the disc and a little beyond it, noise on top"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    per = size // pitch
+    yy = torch.arange(size, device=dev)
+    cell, off = torch.clamp(yy // pitch, max=per - 1), yy - (torch.clamp(yy // pitch, max=per - 1) * pitch + pitch // 2)
+    d2 = off[:, None] ** 2 + off[None, :] ** 2
+    index = cell[:, None] * per + cell[None, :]
+    labels = torch.where(d2 <= radius * radius, index + 1, torch.zeros_like(index)).to(torch.int32)
+    amp = torch.rand((per * per,), generator=g, device=dev) * 1.5
+    S = torch.from_numpy(np.asarray(stain.HDAB, np.float32)).to(dev)       # [3, 2]
+    x = torch.empty((size, size, 3), dtype=torch.uint8, device=dev)
+    for r0 in range(0, size, 512):                                        # in bands: the float image of a 16384^2 slide is 3 GB
+        rows = slice(r0, min(r0 + 512, size))
+        c = torch.rand((rows.stop - r0, size, 2), generator=g, device=dev) * 0.05
+        c[..., 0] += 1.2 * (d2[rows] <= radius * radius)
+        c[..., 1] += amp[index[rows]] * (d2[rows] <= (radius + 4) ** 2)
+        rgb = 240.0 * torch.exp(-(c @ S.T)) + 1.5 * torch.randn((rows.stop - r0, size, 3), generator=g, device=dev)
+        x[rows] = rgb.round().clamp(0, 255).to(torch.uint8)
+    return x[None].contiguous(), labels[None].contiguous(), per * per
+
+
+def bench_quantify(size, opts, dev):
+    from cellsegmentation_amd import morph
+    x, lab, cells = hdab_cells(size, dev)
+    _, H, W, _ = x.shape
+    row = {"slide": "hdab_cells", "size": [H, W], "cells": cells, "labelled_fraction": float((lab > 0).float().mean())}
+    od = torch.from_numpy(stain.od_table(opts.Io)).to(dev)
+    Mq = torch.from_numpy(stain.quantised_matrix(stain.HDAB, False, opts.conc_max)[None]).to(dev)
+    P = torch.from_numpy(np.ascontiguousarray(np.linalg.pinv(stain.HDAB)[None], dtype=np.float32)).to(dev)
+    levels = stain.positive_levels((0.2, 0.2), 2, opts.conc_max)
+    ring = morph.expand_labels(lab, 4)
+    dst = torch.empty_like(x)
+    timed = {"copy": lambda: dst.copy_(x)}
+    for key, kw in (("quantify", {}), ("quantify_pos", {"pos_levels": levels}), ("quantify_ring", {"expanded": ring}),
+                    ("quantify_hist256", {"bins": 256}), ("quantify_ring_pos_hist64", {"expanded": ring, "pos_levels": levels, "bins": 64})):
+        t = K.stain_quantify_labels(x, lab, od, Mq, cells, **kw)
+        timed[key] = lambda kw=kw, t=t: K.stain_quantify_labels(x, lab, od, Mq, cells, **kw, **t)
+    conc = torch.empty((1, H, W, 2), dtype=torch.uint8, device=dev)
+    chan = [torch.empty((1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
+    m = dict(zip(("counts", "area", "bbox", "sums", "isum", "imax"), K.regions_measure_labels(lab, cells, chan[0])))
+    timed["separate_u8"] = lambda: K.stain_separate(x, od, P, True, opts.conc_max, out=conc)
+    timed["channel_copy"] = lambda: chan[0].copy_(conc[..., 0])
+    timed["measure_labels"] = lambda: K.regions_measure_labels(lab, cells, chan[0], **m)
+
+    def two_pass():
+        K.stain_separate(x, od, P, True, opts.conc_max, out=conc)
+        for k in range(2):
+            chan[k].copy_(conc[..., k])
+            K.regions_measure_labels(lab, cells, chan[k], **m)
+
+    timed["two_pass"] = two_pass
+    for key, fn in timed.items():
+        row[f"{key}_ms"], row[f"{key}_spread_ms"] = time_dev(fn)
+    for key in timed:
+        if key != "copy":
+            row[f"{key}_over_copy"] = row[f"{key}_ms"] / row["copy_ms"]
+    row["two_pass_over_quantify"] = row["two_pass_ms"] / row["quantify_ms"]
+    # the fused table against the path it replaces, on the values both have: the sums agree to one level per pixel
+    t = K.stain_quantify_labels(x, lab, od, Mq, cells)
+    two_pass()
+    row["max_abs_mean_difference_levels"] = float(((t["sum"][0, :, 0, 1] - m["isum"][0]).abs().double() / m["area"][0].clamp(min=1)).max())
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, nargs="+", default=[4096, 16384])
+    ap.add_argument("--size", type=int, nargs="+", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--quantify", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     opts = stain.StainOptions()
     rows = []
+    if args.quantify:
+        for size in args.size or [4096]:
+            rows.append(bench_quantify(size, opts, dev))
+            print(json.dumps(rows[-1]), flush=True)
+            torch.cuda.empty_cache()
+        args.size = []
+    elif args.size is None:
+        args.size = [4096, 16384]
     for size in args.size:
         imgs = slides(size, dev)
         for name in list(imgs):
