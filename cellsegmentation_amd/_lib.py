@@ -187,6 +187,7 @@ _SIGNATURES = {
     "cs_regions_hull_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "cs_regions_contour_max_side": (c_int, []),
     "cs_regions_contour_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
+    "cs_regions_texture_labels": (c_int, [_P] * 5 + [c_int] * 4 + [_P, c_int, c_int] + [_P] * 8),
     "cs_regions_match_workspace": (c_size_t, [c_int, c_int, c_int]),
     "cs_regions_match_labels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cs_regions_overlap_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),

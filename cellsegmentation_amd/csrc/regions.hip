@@ -23,6 +23,10 @@
 //   contour   of a label image: per label the outer boundary of its first component as an ordered ring of lattice vertices, with
 //             the ring's crack count and enclosed area and the crack count of the whole label; one workgroup per label, its
 //             bounding box as a bitmap in LDS, which one thread walks
+//   texture   of a label image over a uint8 plane or one stain of an RGB image: per label and per direction (0, 45, 90, 135
+//             degrees at one distance) the grey-level co-occurrence matrix of the pixel pairs inside the label, folded to its pair
+//             count, difference, sum and marginal histograms, sum of squares and cross moment; one workgroup per label, four
+//             L x L tables of counters in LDS, no global atomics and no workspace
 //   match     a label image against another: per-label areas of both, and for every pred label the one truth label with
 //             IoU > 1/2, if any -- two walks of measure's kind (bit votes spell the candidate, then its intersection is counted)
 //             and an exact 64-bit integer test per pred label
@@ -858,6 +862,131 @@ __global__ __launch_bounds__(256) void contour_kernel(const int32_t* __restrict_
         if (threadIdx.x < 3) contour[4 * q + threadIdx.x] = s.walked[threadIdx.x];
         if (threadIdx.x == 3) contour[4 * q + 3] = cracks_all;
         contour_fill(verts, min(nv, maxv), maxv);
+    }
+}
+
+// ---- how a stain is arranged inside every label: grey-level co-occurrence per direction, folded to Haralick's tables --------------
+// A pixel's level is the byte of a plane, or the level of one stain of an RGB pixel by quantify's rule with ONE row of Mq per
+// image; its grey level is g = level * L >> 8, L in {8, 16, 32}.  Direction k = 0 .. 3 has the offset (0, d), (d, d), (d, 0),
+// (d, -d).  A pixel p of label l pairs with q = p + offset where q lies inside the image and has the label l too: C_k[g(p)][g(q)]
+// += 1.  S_k = C_k + C_k^T; written per (image, row, direction) are the pair count, diff[x] = sum over |i - j| = x of S_ij,
+// sum[x] = the same over i + j = x, marg[i] = sum over j of S_ij, sq = sum of S_ij^2, cross = sum of i j S_ij and, where asked
+// for, S itself.  With H W <= 2^30 a direction has fewer than 2^30 pairs: every S_ij < 2^31, sq < 2^62, cross < 2^41.
+constexpr int kTexLevels = 32;                                 // the largest L: four tables of 32 x 32 counters are 16 KiB
+
+enum TextureSrc { kTexPlane, kTexRgb };
+
+struct TextureTables {
+    int32_t* pairs;      // [N][cap][4]
+    int32_t* diff;       // [N][cap][4][L]
+    int32_t* sum;        // [N][cap][4][2L - 1]
+    int32_t* marg;       // [N][cap][4][L]
+    long long* sq;       // [N][cap][4]
+    long long* cross;    // [N][cap][4]
+    int32_t* matrix;     // [N][cap][4][L][L] or NULL
+};
+
+struct TextureLds {
+    // C_k as [k][i][j] with the row length L of the call, and the three histograms laid out as a row of their output tables
+    uint32_t c[4 * kTexLevels * kTexLevels];
+    uint32_t diff[4 * kTexLevels], sum[4 * (2 * kTexLevels - 1)], marg[4 * kTexLevels], pairs[4];
+    long long red[4];
+    int32_t od[256];                                           // od_q, read on the RGB route only
+};
+
+// One workgroup per (image, label) at a time.  The box is cut to the image before anything is read and every partner is held
+// against the image's own sides, so whatever the table holds no read leaves the label image or the source.  A wave walks a row of
+// the box with its lanes along the columns; every add to LDS is one that returns nothing.  After the walk the workgroup folds its
+// four tables and writes its own output row with plain stores, zeros included: nothing is zeroed beforehand, nothing is added to
+// global memory, and the result does not depend on launch or arrival order.
+template <TextureSrc SRC>
+__global__ __launch_bounds__(256) void texture_kernel(const int32_t* __restrict__ lab, const uint8_t* __restrict__ src, int N, int H, int W,
+                                                      const int32_t* __restrict__ od_q, const int32_t* __restrict__ Mq, int cap,
+                                                      const int32_t* __restrict__ bbox, int L, int d, TextureTables t) {
+    __shared__ TextureLds s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int LL = L * L, S2 = 2 * L - 1, shift = L == 8 ? 3 : L == 16 ? 4 : 5;
+    if (SRC == kTexRgb) s.od[tid] = od_q[tid];                  // (the first barrier of the first object publishes it)
+    const long long objects = (long long)N * cap;
+    for (long long q = blockIdx.x; q < objects; q += gridDim.x) {
+        const int n = (int)(q / cap), l = (int)(q - (long long)n * cap) + 1;
+        const int r0 = max(bbox[4 * q], 0), c0 = max(bbox[4 * q + 1], 0), r1 = min(bbox[4 * q + 2], H), c1 = min(bbox[4 * q + 3], W);
+        const bool none = r1 <= r0 || c1 <= c0;                        // the same in every thread: no barrier is left out below
+        for (int i = tid; i < 4 * LL; i += 256) {
+            s.c[i] = 0;
+            if (none && t.matrix) t.matrix[q * 4 * LL + i] = 0;
+        }
+        for (int i = tid; i < 4 * S2; i += 256) {
+            s.sum[i] = 0;
+            if (i < 4 * L) s.diff[i] = s.marg[i] = 0;
+            if (i < 4) s.pairs[i] = 0;
+        }
+        __syncthreads();
+        if (!none) {
+            // 1. the ordered counts: a wave per row of the box, every pixel of the label looks at its four partners
+            const long long base = (long long)n * H * W;
+            long long m0 = 0, m1 = 0, m2 = 0;
+            if (SRC == kTexRgb) m0 = Mq[3 * n], m1 = Mq[3 * n + 1], m2 = Mq[3 * n + 2];
+            auto grey = [&](long long p) {
+                if (SRC == kTexPlane) return (int)src[p] * L >> 8;
+                const uint8_t* px = src + 3 * p;
+                const long long sh = (m0 * s.od[px[0]] + m1 * s.od[px[1]] + m2 * s.od[px[2]] + (1LL << 23)) >> 24;
+                return (int)(sh < 0 ? 0 : sh > 255 ? 255 : sh) * L >> 8;
+            };
+            for (int r = r0 + wave; r < r1; r += 4) {
+                const long long row = base + (long long)r * W;
+                for (int c = c0 + lane; c < c1; c += 64) {
+                    if (lab[row + c] != l) continue;
+                    const int gp = grey(row + c);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int rr = r + (k == 0 ? 0 : d), cc = c + (k < 2 ? d : k == 2 ? 0 : -d);
+                        if (rr >= H || cc < 0 || cc >= W) continue;
+                        const long long pq = base + (long long)rr * W + cc;
+                        if (lab[pq] != l) continue;
+                        __hip_atomic_fetch_add(s.c + k * LL + (gp << shift) + grey(pq), 1u, __ATOMIC_RELAXED, kLds);
+                    }
+                }
+            }
+            __syncthreads();
+            // 2. S = C + C^T of every direction, folded into the histograms (adds to LDS) and the two sums (block_reduce)
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t* ck = s.c + k * LL;
+                long long sq = 0, cross = 0;
+                for (int e = tid; e < LL; e += 256) {
+                    const int i = e >> shift, j = e & (L - 1);
+                    const uint32_t cij = ck[e], sij = cij + ck[j * L + i];
+                    if (t.matrix) t.matrix[(q * 4 + k) * LL + e] = (int32_t)sij;
+                    if (sij == 0) continue;
+                    __hip_atomic_fetch_add(s.diff + k * L + abs(i - j), sij, __ATOMIC_RELAXED, kLds);
+                    __hip_atomic_fetch_add(s.sum + k * S2 + i + j, sij, __ATOMIC_RELAXED, kLds);
+                    __hip_atomic_fetch_add(s.marg + k * L + i, sij, __ATOMIC_RELAXED, kLds);
+                    if (cij) __hip_atomic_fetch_add(s.pairs + k, cij, __ATOMIC_RELAXED, kLds);
+                    sq += (long long)sij * sij;
+                    cross += (long long)(i * j) * sij;
+                }
+                sq = block_reduce<256>(sq, [](long long x, long long y) { return x + y; }, s.red);
+                cross = block_reduce<256>(cross, [](long long x, long long y) { return x + y; }, s.red);
+                if (tid == 0) {
+                    t.sq[q * 4 + k] = sq;
+                    t.cross[q * 4 + k] = cross;
+                }
+            }
+            // (the last barrier of block_reduce is behind every add above)
+        } else if (tid < 4) {
+            t.sq[q * 4 + tid] = 0;
+            t.cross[q * 4 + tid] = 0;
+        }
+        // 3. the row of this label: the histograms as they lie in LDS
+        for (int i = tid; i < 4 * S2; i += 256) {
+            t.sum[q * 4 * S2 + i] = (int32_t)s.sum[i];
+            if (i < 4 * L) {
+                t.diff[q * 4 * L + i] = (int32_t)s.diff[i];
+                t.marg[q * 4 * L + i] = (int32_t)s.marg[i];
+            }
+            if (i < 4) t.pairs[q * 4 + i] = (int32_t)s.pairs[i];
+        }
+        __syncthreads();                                               // the next object zeroes the tables
     }
 }
 
@@ -2223,6 +2352,41 @@ extern "C" int cs_regions_contour_labels(const int32_t* labels, int N, int H, in
         hipLaunchKernelGGL(contour_kernel<1>, grid, dim3(256), 0, st, labels, N, H, W, capacity, bbox, max_vertices, contour, vertices);
     else
         hipLaunchKernelGGL(contour_kernel<2>, grid, dim3(256), 0, st, labels, N, H, W, capacity, bbox, max_vertices, contour, vertices);
+    CS_LAUNCH_CHECK();
+    return CS_OK;
+}
+
+extern "C" int cs_regions_texture_labels(const int32_t* labels, const uint8_t* plane, const uint8_t* images_hwc, const int32_t* od_q,
+                                         const int32_t* Mq, int N, int H, int W, int capacity, const int32_t* bbox, int levels, int distance,
+                                         int32_t* pairs, int32_t* diff, int32_t* sum, int32_t* marg, int64_t* sq, int64_t* cross,
+                                         int32_t* matrix, void* stream) {
+    CS_CHECK_ARG(labels, "regions_texture_labels: NULL argument");
+    CS_CHECK_ARG((plane != nullptr) != (images_hwc != nullptr), "regions_texture_labels: exactly one of the plane and the RGB image is given");
+    CS_CHECK_ARG((od_q != nullptr) == (images_hwc != nullptr) && (Mq != nullptr) == (images_hwc != nullptr),
+                 "regions_texture_labels: od_q and Mq go with the RGB image");
+    CS_CHECK_ARG(bbox && pairs && diff && sum && marg && sq && cross, "regions_texture_labels: NULL table");
+    CS_CHECK_ARG(sizes_ok(N, H, W), "regions_texture_labels: need 0 < N <= 65535, H, W > 0 and N H W < 2^31");
+    CS_CHECK_ARG((long long)H * W <= (1LL << 30), "regions_texture_labels: need H W <= 2^30 (the counts are int32)");
+    CS_CHECK_ARG(levels == 8 || levels == 16 || levels == 32, "regions_texture_labels: levels must be 8, 16 or 32");
+    CS_CHECK_ARG(distance >= 1 && distance <= 8, "regions_texture_labels: distance must lie in [1, 8]");
+    CS_CHECK_ARG(capacity >= 1, "regions_texture_labels: need capacity >= 1");
+    const long long objects = (long long)N * capacity;
+    CS_CHECK_ARG(objects * 4 * (2 * levels - 1) < (1LL << 31), "regions_texture_labels: need N capacity 4 (2 levels - 1) < 2^31");
+    CS_CHECK_ARG(!matrix || objects * 4 * levels * levels < (1LL << 31), "regions_texture_labels: need N capacity 4 levels^2 < 2^31");
+    CS_CHECK_ARG(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(od_q) | reinterpret_cast<uintptr_t>(Mq) |
+                   reinterpret_cast<uintptr_t>(bbox) | reinterpret_cast<uintptr_t>(pairs) | reinterpret_cast<uintptr_t>(diff) |
+                   reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(marg) | reinterpret_cast<uintptr_t>(matrix)) & 3) == 0 &&
+                 ((reinterpret_cast<uintptr_t>(sq) | reinterpret_cast<uintptr_t>(cross)) & 7) == 0,
+                 "regions_texture_labels: misaligned argument");
+    const TextureTables t{pairs, diff, sum, marg, reinterpret_cast<long long*>(sq), reinterpret_cast<long long*>(cross), matrix};
+    const dim3 grid((unsigned)(objects < 8192 ? objects : 8192));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (plane)
+        hipLaunchKernelGGL(texture_kernel<kTexPlane>, grid, dim3(256), 0, st, labels, plane, N, H, W, od_q, Mq, capacity, bbox, levels,
+                           distance, t);
+    else
+        hipLaunchKernelGGL(texture_kernel<kTexRgb>, grid, dim3(256), 0, st, labels, images_hwc, N, H, W, od_q, Mq, capacity, bbox, levels,
+                           distance, t);
     CS_LAUNCH_CHECK();
     return CS_OK;
 }

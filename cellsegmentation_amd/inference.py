@@ -629,6 +629,35 @@ def slide_positivity(result, image_u8, stains=None, thresholds=(0.2, 0.4, 0.6), 
     return cells.score(thresholds, stain, 0 if ring is None else 1), cells, table, parts
 
 
+def slide_texture(result, image_u8, stains=None, stain=0, levels=16, distance=1, options=None, **measure_kwargs):
+    """How a stain is arranged inside the DETECTED cells of a ``SlideResult``, on the device: ``measure_slide_cells(result,
+    **measure_kwargs)``, whose split labels go to ``stain.texture_labels`` over ``image_u8`` (uint8 RGB ``[H, W, 3]`` of the mask's
+    shape) with the region table -> ``(TextureTable, RegionTable, SplitResult)`` of one image.  Row k of every table is
+    ``result.points[k]``.  ``stains``: a [3, 2] matrix or a ``StainEstimate``; None estimates the slide (``stain.estimate``).
+    ``stain``: the stain whose level is the grey value (0 = haematoxylin: chromatin texture); ``levels`` and ``distance`` as in
+    ``regions.texture_labels``.  With an int ``max_regions`` and given ``stains`` nothing synchronises."""
+    from . import regions as Rg
+    from . import stain as St
+    if not isinstance(result, SlideResult):
+        raise TypeError("slide_texture: expected the SlideResult of detect_slide")
+    opts = St._options(options, "slide_texture")
+    Rg._check_texture(levels, distance)
+    if isinstance(stain, bool) or not isinstance(stain, (int, np.integer)) or not 0 <= stain < 2:
+        raise ValueError(f"stain must be an integer in [0, 2), got {stain!r}")
+    img = _tensor(image_u8)
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or tuple(img.shape) != tuple(result.mask.shape) + (3,):
+        raise TypeError(f"slide_texture: image_u8 must be a uint8 RGB image shaped {tuple(result.mask.shape) + (3,)}")
+    if stains is not None:
+        St.quantised_matrix(stains, False, opts.conc_max)
+    Rg._check_texture_size("slide_texture", tuple(result.mask.shape))
+    table, parts = measure_slide_cells(result, **measure_kwargs)
+    img = img.to(parts.labels.device)
+    if stains is None:
+        stains = St.estimate(img, options=opts)
+    cells = St.texture_labels(img, parts.labels, stains, stain=stain, levels=levels, distance=distance, table=table, options=opts)
+    return cells, table, parts
+
+
 def slide_neighbors(result, k=1, radii=(), other=None, other_xy=False):
     """Neighbourhood statistics of the detected cells of a ``SlideResult``, on the device: ``result.points`` is uploaded once and
     queried on the bucket grid of ``spatial`` with the mask's shape as the image -> ``(NeighborTable or None, WithinCounts or

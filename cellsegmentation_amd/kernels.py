@@ -1514,6 +1514,57 @@ def regions_contour_labels(labels, capacity, bbox, connectivity, max_vertices, c
     return t["contour"], t.get("vertices")
 
 
+TEXTURE_LEVELS = (8, 16, 32)         # cs_regions_texture_labels: the grey levels L of a co-occurrence matrix
+TEXTURE_MAX_DISTANCE = 8
+TEXTURE_MAX_PIXELS = 1 << 30         # H W per image: every direction then has fewer than 2^30 pairs and the int32 counts hold
+
+
+def texture_labels(labels, capacity, bbox, plane=None, images_u8=None, od_q=None, Mq=None, levels=16, distance=1, want_matrix=False,
+                   **tables):
+    """int32 label image [N,H,W], bbox int32 [N,cap,4] (regions_measure_labels of the same image) and either ``plane`` uint8 [N,H,W]
+    or ``images_u8`` uint8 [N,H,W,3] with od_q int32 [256] and Mq int32 [N,3] (one stain row per image) -> dict of pairs int32
+    [N,cap,4]; diff, marg int32 [N,cap,4,L]; sum int32 [N,cap,4,2L-1]; sq, cross int64 [N,cap,4] and, with ``want_matrix``, matrix
+    int32 [N,cap,4,L,L]: the symmetric grey-level co-occurrence of every label at ``distance`` in the four directions, L =
+    ``levels``; row k = label k + 1.  ``tables``: tensors to write instead of new ones (cs_regions_texture_labels in
+    include/cellseg_hip.h)."""
+    what = "texture_labels"
+    N, H, W = _label_images(what, labels)
+    cap, L, d = int(capacity), int(levels), int(distance)
+    _bbox_operand(what, bbox, N, cap)
+    if (plane is None) == (images_u8 is None):
+        raise ValueError(f"{what}: exactly one of plane and images_u8 is given")
+    if L not in TEXTURE_LEVELS:
+        raise ValueError(f"{what}: levels must be one of {TEXTURE_LEVELS}, got {levels}")
+    if not 1 <= d <= TEXTURE_MAX_DISTANCE:
+        raise ValueError(f"{what}: distance must lie in [1, {TEXTURE_MAX_DISTANCE}], got {distance}")
+    if H * W > TEXTURE_MAX_PIXELS:
+        raise ValueError(f"{what}: a {H}x{W} image: H W <= 2^30 keeps the pair counts inside int32")
+    if plane is not None:
+        if not torch.is_tensor(plane) or plane.dtype != torch.uint8 or tuple(plane.shape) != (N, H, W):
+            raise TypeError(f"{what}: the plane is uint8 of the label image's shape")
+        if od_q is not None or Mq is not None:
+            raise ValueError(f"{what}: od_q and Mq go with images_u8")
+    else:
+        if tuple(_rgb_images(what, images_u8, whole_batch=True)) != (N, H, W):
+            raise ValueError(f"{what}: images of shape {tuple(images_u8.shape)} for labels of {(N, H, W)}")
+        if not torch.is_tensor(od_q) or od_q.dtype != torch.int32 or tuple(od_q.shape) != (256,):
+            raise ValueError(f"{what}: od_q must be an int32 tensor shaped (256,) (stain.od_table)")
+        if not torch.is_tensor(Mq) or Mq.dtype != torch.int32 or tuple(Mq.shape) != (N, 3):
+            raise ValueError(f"{what}: Mq must be an int32 tensor shaped {(N, 3)}: one stain row per image")
+    want = {"pairs": ((N, cap, 4), torch.int32), "diff": ((N, cap, 4, L), torch.int32), "sum": ((N, cap, 4, 2 * L - 1), torch.int32),
+            "marg": ((N, cap, 4, L), torch.int32), "sq": ((N, cap, 4), torch.int64), "cross": ((N, cap, 4), torch.int64)}
+    if want_matrix or tables.get("matrix") is not None:
+        want["matrix"] = ((N, cap, 4, L, L), torch.int32)
+    unknown = sorted(set(tables) - set(want) - {"matrix"})
+    if unknown:
+        raise TypeError(f"{what}: no table named {unknown[0]!r}")
+    t = _regions_outputs(what, want, tables, labels.device)
+    _lib.check(_lib.load().cs_regions_texture_labels(_p(labels), _p(plane), _p(images_u8), _p(od_q), _p(Mq), N, H, W, cap, _p(bbox), L, d,
+                                                     _p(t["pairs"]), _p(t["diff"]), _p(t["sum"]), _p(t["marg"]), _p(t["sq"]),
+                                                     _p(t["cross"]), _p(t.get("matrix")), _stream()), what)
+    return t
+
+
 def _label_pair_args(what, pred, truth, want_counts):
     """two int32 [N,H,W] label images of one shape -> (N, H, W, the ``_regions_outputs`` entries of the counts asked for)"""
     if pred.dtype != torch.int32 or pred.dim() != 3 or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(pred.shape):

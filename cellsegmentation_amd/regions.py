@@ -72,6 +72,13 @@ number of neighbours, the sides shared with other cells, with the background and
 contact, in exact integers (``AdjacencyTable``; the rules are in ``adjacency_labels``'s docstring, restated in numpy by
 tests/adjacency_ref.py), from which ``AdjacencyTable`` forms the touching fraction in float64 and the cell graph as a COO edge list
 on the device.  ``distance=`` expands the labels first (``morph.expand_labels``), so that cells within a gap count as neighbours.
+
+``texture_labels`` adds how the grey values of a uint8 plane are arranged inside every label: the grey-level co-occurrence matrix of
+the pixel pairs inside the label at one distance in four directions, folded to its pair count, its difference, sum and marginal
+histograms, its sum of squares and its cross moment, in exact integers (``TextureTable``; the rules are in ``texture_labels``'s
+docstring, restated in numpy by tests/texture_ref.py), from which ``TextureTable`` forms Haralick's features -- contrast,
+homogeneity, energy, correlation, the entropies -- in float64 on the device.  ``stain.texture_labels`` is the same over one stain
+of an RGB image.
 """
 import dataclasses
 import functools
@@ -1513,3 +1520,225 @@ def contours(m, connectivity=1, max_regions=None, max_vertices=None):
     _check_max_vertices(max_vertices)
     lab = label(m, connectivity)
     return contour_labels(lab, table=measure_labels(lab, max_regions=max_regions), connectivity=connectivity, max_vertices=max_vertices)
+
+
+TEXTURE_LEVELS = K.TEXTURE_LEVELS
+_TEXTURE_COLUMNS = ("contrast", "dissimilarity", "homogeneity", "asm", "energy", "mean", "variance", "correlation",
+                    "difference_entropy", "sum_entropy", "sum_average")
+
+
+def _check_texture(levels, distance):
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels not in TEXTURE_LEVELS:
+        raise ValueError(f"levels must be one of {TEXTURE_LEVELS}, got {levels!r}")
+    if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)) or not 1 <= distance <= K.TEXTURE_MAX_DISTANCE:
+        raise ValueError(f"distance must be an integer in [1, {K.TEXTURE_MAX_DISTANCE}], got {distance!r}")
+    return int(levels), int(distance)
+
+
+def _check_texture_size(what, shape):
+    """the pair counts are int32: a direction has fewer than H W <= 2^30 pairs"""
+    if len(shape) in (2, 3) and int(shape[-2]) * int(shape[-1]) > K.TEXTURE_MAX_PIXELS:
+        raise ValueError(f"{what}: a {shape[-2]}x{shape[-1]} image: H W <= 2^30 keeps the pair counts in int32")
+
+
+def _entropy(counts, total, dims):
+    """-sum q log2 q over ``dims`` of q = counts / total, 0 log 0 = 0"""
+    q = counts.to(torch.float64) / total
+    return -torch.where(q > 0, q * torch.log2(q), torch.zeros_like(q)).sum(dim=dims)
+
+
+@dataclasses.dataclass(eq=False)
+class TextureTable:
+    """``texture_labels`` of N label images as device tensors.  ``table``: the ``RegionTable`` of the same images (row k = label
+    k + 1).  Per (image, row, direction), the directions being 0, 45, 90 and 135 degrees at ``distance``, of the symmetric grey-level
+    co-occurrence matrix S of the pixel pairs inside the label at ``levels`` = L grey levels: ``pairs`` int32 [N, cap, 4]; ``diff``
+    and ``marg`` int32 [N, cap, 4, L]; ``sum`` int32 [N, cap, 4, 2L - 1]; ``sq`` and ``cross`` int64 [N, cap, 4]; ``matrix`` int32
+    [N, cap, 4, L, L] = S, or None.  ``Mq`` int32 numpy [N, 3] and ``options`` are what ``stain.texture_labels`` made it with, None
+    for a plane.  The rules are in ``texture_labels``' docstring.  With T = 2 pairs, M1 = sum i marg[i] and M2 = sum i^2 marg[i],
+    every method but ``per_image`` runs on the device in float64, is computed from the integer tables only and returns [N, cap, 4]
+    with NaN where ``pairs == 0``; ``average=True`` returns [N, cap]: the mean over the directions that are not NaN, NaN where none
+    is."""
+    table: RegionTable
+    pairs: torch.Tensor
+    diff: torch.Tensor
+    sum: torch.Tensor
+    marg: torch.Tensor
+    sq: torch.Tensor
+    cross: torch.Tensor
+    matrix: typing.Optional[torch.Tensor]
+    levels: int
+    distance: int
+    Mq: typing.Optional[np.ndarray] = None
+    options: object = None
+
+    def _total(self):
+        """T = 2 pairs in float64, NaN where there is no pair"""
+        t = 2.0 * self.pairs.to(torch.float64)
+        return torch.where(self.pairs > 0, t, torch.full_like(t, float("nan")))
+
+    def _out(self, x, average):
+        x = torch.where(self.pairs > 0, x, torch.full_like(x, float("nan")))
+        if not average:
+            return x
+        ok = ~torch.isnan(x)
+        return torch.where(ok, x, torch.zeros_like(x)).sum(dim=-1) / ok.sum(dim=-1).to(torch.float64)
+
+    def _weighted(self, hist, weight):
+        """sum_k weight(k) hist[k] in float64"""
+        k = torch.arange(hist.shape[-1], dtype=torch.float64, device=hist.device)
+        return (hist.to(torch.float64) * weight(k)).sum(dim=-1)
+
+    def _moments(self):
+        """M1 = sum i marg[i] and M2 = sum i^2 marg[i], int64"""
+        i = torch.arange(self.levels, dtype=torch.int64, device=self.marg.device)
+        m = self.marg.to(torch.int64)
+        return (m * i).sum(dim=-1), (m * i * i).sum(dim=-1)
+
+    def _central(self, raw):
+        """T raw - M1^2 in float64 (raw: int64 M2 or cross) and T: an exact int64 product where pairs < 2^20 (T < 2^21, raw and
+        M1 <= 31^2 T: every product below 2^62), float64 beyond"""
+        M1, _ = self._moments()
+        T = 2 * self.pairs.to(torch.int64)
+        exact = (T * raw - M1 * M1).to(torch.float64)
+        Tf, M1f = T.to(torch.float64), M1.to(torch.float64)
+        return torch.where(self.pairs < (1 << 20), exact, Tf * raw.to(torch.float64) - M1f * M1f)
+
+    def contrast(self, average=False):
+        """sum k^2 diff[k] / T"""
+        return self._out(self._weighted(self.diff, lambda k: k * k) / self._total(), average)
+
+    def dissimilarity(self, average=False):
+        """sum k diff[k] / T"""
+        return self._out(self._weighted(self.diff, lambda k: k) / self._total(), average)
+
+    def homogeneity(self, average=False):
+        """sum diff[k] / (1 + k^2) / T: the inverse difference moment"""
+        return self._out(self._weighted(self.diff, lambda k: 1.0 / (1.0 + k * k)) / self._total(), average)
+
+    def asm(self, average=False):
+        """sq / T^2: the angular second moment"""
+        T = self._total()
+        return self._out(self.sq.to(torch.float64) / (T * T), average)
+
+    def energy(self, average=False):
+        """sqrt(asm)"""
+        T = self._total()
+        return self._out(torch.sqrt(self.sq.to(torch.float64) / (T * T)), average)
+
+    def mean(self, average=False):
+        """M1 / T: the mean grey level of the pixels that pair"""
+        return self._out(self._moments()[0].to(torch.float64) / self._total(), average)
+
+    def variance(self, average=False):
+        """(T M2 - M1^2) / T^2"""
+        T = self._total()
+        return self._out(self._central(self._moments()[1]) / (T * T), average)
+
+    def correlation(self, average=False):
+        """(T cross - M1^2) / (T M2 - M1^2), NaN where the denominator is 0 (one grey level only)"""
+        num, den = self._central(self.cross), self._central(self._moments()[1])
+        return self._out(torch.where(den != 0, num / den, torch.full_like(den, float("nan"))), average)
+
+    def difference_entropy(self, average=False):
+        """-sum q log2 q over q = diff / T"""
+        return self._out(_entropy(self.diff, self._total().unsqueeze(-1), -1), average)
+
+    def sum_entropy(self, average=False):
+        """-sum q log2 q over q = sum / T"""
+        return self._out(_entropy(self.sum, self._total().unsqueeze(-1), -1), average)
+
+    def sum_average(self, average=False):
+        """sum k sum[k] / T"""
+        return self._out(self._weighted(self.sum, lambda k: k) / self._total(), average)
+
+    def entropy(self, average=False):
+        """-sum p log2 p over p = matrix / T; the table must have been made with ``want_matrix=True``"""
+        if self.matrix is None:
+            raise ValueError("entropy: the table was made without the matrix (want_matrix=False)")
+        return self._out(_entropy(self.matrix, self._total().unsqueeze(-1).unsqueeze(-1), (-2, -1)), average)
+
+    def overflowed(self):
+        """device bool [N]: the image has labels above the table's rows"""
+        return self.table.overflowed()
+
+    def per_image(self):
+        """``RegionTable.per_image`` with the integer tables that the table has and one column per method above (``entropy`` with
+        the matrix) added, trimmed alike.  The one method that synchronises."""
+        out = self.table.per_image()
+        cols = {k: getattr(self, k) for k in ("pairs", "diff", "sum", "marg", "sq", "cross")}
+        cols.update({k: getattr(self, k)() for k in _TEXTURE_COLUMNS})
+        if self.matrix is not None:
+            cols.update(matrix=self.matrix, entropy=self.entropy())
+        for k, v in cols.items():
+            v = v.cpu().numpy()
+            for n, d in enumerate(out):
+                d[k] = v[n, :len(d["area"])]
+        return out
+
+
+def _texture(img, table, levels, distance, want_matrix, plane=None, images=None, od_q=None, mq=None, Mq=None, options=None):
+    """the launches of ``texture_labels`` and ``stain.texture_labels`` on placed operands -> ``TextureTable``"""
+    t, N, cap, dev, L = img.labels, img.N, table.capacity, img.labels.device, levels
+    new = lambda dtype, *tail: torch.empty((N, cap, 4) + tail, dtype=dtype, device=dev)  # noqa: E731
+    out = {"pairs": new(torch.int32), "diff": new(torch.int32, L), "sum": new(torch.int32, 2 * L - 1), "marg": new(torch.int32, L),
+           "sq": new(torch.int64), "cross": new(torch.int64)}
+    if want_matrix:
+        out["matrix"] = new(torch.int32, L, L)
+    bbox = table.bbox.contiguous()
+    for a, b in img.chunks:
+        K.texture_labels(t[a:b], cap, bbox[a:b], None if plane is None else plane[a:b], None if images is None else images[a:b], od_q,
+                         None if mq is None else mq[a:b], L, distance, want_matrix, **{k: v[a:b] for k, v in out.items()})
+    return TextureTable(table, out["pairs"], out["diff"], out["sum"], out["marg"], out["sq"], out["cross"], out.get("matrix"), L,
+                        distance, Mq, options)
+
+
+def texture_labels(labels, intensity, levels=16, distance=1, table=None, max_regions=None, counts=None, want_matrix=False):
+    """How the grey values of ``intensity`` are arranged inside every label of a label image -> ``TextureTable``: the grey-level
+    co-occurrence matrices that Haralick's texture features are formed from (QuPath's "Haralick features", CellProfiler's
+    ``MeasureTexture``), without a copy of the image to the host.
+
+    ``labels``: int32 [H, W] or [N, H, W] (numpy or torch) with H W <= 2^30; ``intensity``: uint8 of the same shape, for example
+    a plane of ``stain.separate(dtype="u8")`` (``stain.texture_labels`` reads an RGB image instead).  Everything the device writes
+    is an exact integer:
+
+    * Level.  Every pixel has a level in 0 .. 255: the byte of ``intensity``.
+    * Grey level.  ``g = (level * L) >> 8`` with L = ``levels`` in {8, 16, 32}: the bin rule of ``stain.quantify_labels``' ``hist``.
+    * Offsets.  For ``distance`` d in 1 .. 8 the four directions k = 0 .. 3 are ``(dr, dc)`` = ``(0, d)``, ``(d, d)``, ``(d, 0)``,
+      ``(d, -d)``: 0, 45, 90 and 135 degrees with the row axis downwards.
+    * Pairs.  A pixel p = (r, c) with ``0 < labels[p] = l <= capacity`` forms a pair with q = (r + dr, c + dc) when q lies inside
+      the image and ``labels[q] == l``; nothing else forms a pair.  The ordered count is ``C_k[g(p)][g(q)] += 1``.  A label need not
+      be connected: two of its pieces exactly an offset apart do pair.  Pixels of another label, of the background (``<= 0``) or
+      outside the image never pair.  The images of a batch are independent.
+    * Symmetric matrix.  ``S_k = C_k + C_k^T``; its total is ``T_k = 2 pairs_k``.
+    * Tables, per (image, row = label - 1, direction): ``pairs`` int32 [N, cap, 4], the number of pairs; ``diff`` int32
+      [N, cap, 4, L], ``diff[k]`` = the sum of ``S_ij`` over ``abs(i - j) = k``; ``sum`` int32 [N, cap, 4, 2L - 1], ``sum[k]`` = the
+      same over ``i + j = k``; ``marg`` int32 [N, cap, 4, L], ``marg[i]`` = the sum of ``S_ij`` over j; ``sq`` int64 [N, cap, 4] =
+      the sum of ``S_ij^2``; ``cross`` int64 [N, cap, 4] = the sum of ``i j S_ij``; and only with ``want_matrix=True`` ``matrix``
+      int32 [N, cap, 4, L, L] = S itself.
+    * Empty rows.  A label without a pixel, or without a pair in a direction, has all zeros there (and NaN in every method of the
+      table).  Rows of labels above the capacity are not written; they are counted in ``table.counts`` as elsewhere.
+    * Bounds.  With H W <= 2^30, ``2 pairs < 2^31``: every int32 entry fits, ``sq < 2^62`` and ``cross < 2^41``.  ``N cap 4
+      (2L - 1)`` and, with the matrix, ``N cap 4 L^2`` per kernel call stay below 2^31.
+
+    Hand case: labels ``[[1,1,1,2],[1,1,2,2],[0,1,2,-3]]`` over the plane ``[[0,40,40,255],[100,40,255,200],[7,250,31,9]]`` with
+    L = 8 and d = 1 have the grey levels ``[[0,1,1,7],[3,1,7,6],[0,7,0,0]]``.  Label 1 has in direction 0 three pairs, ``diff`` =
+    (2, 2, 2, 0, ..), ``marg`` = (1, 4, 0, 1, 0, 0, 0, 0), ``sq`` = 8 and ``cross`` = 8, and in direction 1 two pairs, ``diff`` =
+    (0, 2, 0, 0, 2, 0, ..), ``sq`` = 4 and ``cross`` = 42.  Label 2 has in direction 0 one pair, ``sq`` = 2 and ``cross`` = 84, in
+    direction 1 none (all zero), and in direction 3 two pairs, ``marg`` = (1, 0, 0, 0, 0, 0, 1, 2), ``sq`` = 6 and ``cross`` = 98.
+
+    The rules are restated in numpy by tests/texture_ref.py (tests/golden/texture_vectors.npz) and, on a full rectangle, held
+    against an independent ``scipy.sparse`` construction.  Parity with ``skimage.feature.graycomatrix`` is claimed for d = 1 only,
+    with ``symmetric=True`` and its angles 0, pi/4, pi/2 and 3 pi/4 matched to the offsets above: scikit-image rounds its diagonal
+    offsets ``d cos``, ``d sin`` differently for d > 1, where the offsets here stay ``(d, d)``.  scikit-image is not a dependency
+    of this project and was not run.
+
+    ``table``, ``max_regions`` and ``counts`` as in ``hull_labels``.  With a table, or an int ``max_regions``, one launch whose grid
+    depends on (N, capacity) alone follows, nothing synchronises and the call can be captured into a graph: one workgroup per label
+    walks the label's bounding box and counts into tables in its own local memory, there are no global atomics and no workspace,
+    so the result does not depend on launch or arrival order.  Argument errors are raised before the library is loaded."""
+    what = "texture_labels"
+    L, d = _check_texture(levels, distance)
+    v = _as_intensity(intensity, _as_labels(labels, what).shape)
+    img, table = _labels_and_table(what, labels, table, max_regions, counts, "label first", _check_texture_size)
+    N, H, W = img.labels.shape
+    return _texture(img, table, L, d, bool(want_matrix), plane=v.to(img.labels.device).contiguous().view(N, H, W))

@@ -17,7 +17,8 @@ writes the concentrations themselves -- as uint8 they are ready to be the ``inte
 ``quantify_labels`` answers what the slide was stained for without a concentration image in between: one pass over the RGB image
 and a label image (csrc/regions.hip) leaves, per cell and per compartment (the cell, and the ring an expansion adds around it),
 exact integer tables of an integer stain level -- ``StainTable``, whose ``classify`` and ``score`` give the intensity classes, the
-labelling index and the H-score.
+labelling index and the H-score.  ``texture_labels`` tabulates how that level is arranged inside every cell instead: the grey-level
+co-occurrence tables of ``regions.texture_labels`` over one stain (``regions.TextureTable``, Haralick's features).
 
 Argument errors are raised before the library is loaded or the device is touched.
 """
@@ -527,6 +528,42 @@ def quantify_labels(images, labels, stains=HDAB, residual=False, expanded=None, 
     if max_regions is not None:
         return run(int(max_regions), img.own)
     return run(*Rg._largest_labels(lambda: run(1, True), img), False)   # (the pass that finds the largest labels; one synchronisation)
+
+
+def texture_labels(images, labels, stains=HDAB, stain=0, residual=False, levels=16, distance=1, table=None, max_regions=None, counts=None,
+                   want_matrix=False, options=None):
+    """How one stain is arranged inside every cell of a label image -> ``regions.TextureTable``: ``regions.texture_labels`` over an
+    RGB image, the level of a pixel being the integer level of stain ``stain`` by the rule of ``quantify_labels``, ``clamp((Mq[0]
+    od_q[R] + Mq[1] od_q[G] + Mq[2] od_q[B] + 2^23) >> 24, 0, 255)`` with ``Mq`` = row ``stain`` of the image's
+    ``quantised_matrix(stains, residual, options.conc_max)``; no concentration image lies in between.  ``stain=0`` is the first
+    stain, haematoxylin under ``HDAB``: the default is chromatin texture.
+
+    ``images``: uint8 RGB [H, W, 3] or [N, H, W, 3]; ``labels``: int32 [H, W] or [N, H, W] of the same size with H W <= 2^30;
+    ``stains``: a [3, 2] matrix or a ``StainEstimate``, or a list of N of them; ``stain`` in [0, K), K = 3 with ``residual``.
+    ``levels``, ``distance``, ``want_matrix`` and every rule of the tables as in ``regions.texture_labels``; ``table``,
+    ``max_regions`` and ``counts`` as in ``regions.hull_labels``.  The table keeps ``Mq`` int32 [N, 3] and the options.  Every
+    lane reads the three bytes of its own pixel: nothing is asked of the image's alignment.  Argument errors are raised before the
+    library is loaded."""
+    from . import regions as Rg
+    what = "texture_labels"
+    opts = _options(options, what)
+    x, _ = _rgb(images, what)
+    N, H, W, _ = x.shape
+    L, d = Rg._check_texture(levels, distance)
+    shape = tuple(Rg._as_labels(labels, what, "regions.label first").shape)
+    if (1 if len(shape) == 2 else shape[0], shape[-2:]) != (N, (H, W)):
+        raise ValueError(f"{what}: labels of shape {shape} for images of shape {tuple(x.shape)}")
+    per = stains if isinstance(stains, (list, tuple)) else [stains] * N
+    if len(per) != N:
+        raise ValueError(f"{what}: {len(per)} stain matrices for {N} images")
+    Mq = np.stack([quantised_matrix(s, residual, opts.conc_max) for s in per])
+    if isinstance(stain, bool) or not isinstance(stain, (int, np.integer)) or not 0 <= stain < Mq.shape[1]:
+        raise ValueError(f"stain must be an integer in [0, {Mq.shape[1]}), got {stain!r}")
+    Mq = np.ascontiguousarray(Mq[:, int(stain)])
+    img, table = Rg._labels_and_table(what, labels, table, max_regions, counts, "regions.label first", Rg._check_texture_size)
+    dev = img.labels.device
+    return Rg._texture(img, table, L, d, bool(want_matrix), images=x.to(dev).contiguous(), od_q=_od(opts, dev),
+                       mq=torch.from_numpy(Mq).to(dev), Mq=Mq, options=opts)
 
 
 # ---- inference.detect_slide(..., stain=...) ------------------------------------------------------------------------------------------

@@ -841,6 +841,31 @@ int cs_regions_contour_max_side(void);
 int cs_regions_contour_labels(const int32_t* labels, int N, int H, int W, int capacity, const int32_t* bbox, int connectivity,
                               int max_vertices, int32_t* contour, int32_t* vertices, void* stream);
 
+/* ---- how a stain is arranged inside every object of a label image: grey-level co-occurrence tables (csrc/regions.hip) --------
+ * labels int32 [N][H][W] and bbox int32 [N][capacity][4] as for cs_regions_hull_labels (the box is READ and cut to the image; every
+ * read stays inside the image whatever it holds).  One launch whose grid depends on (N, capacity) alone, no synchronisation,
+ * capturable; no workspace, no global atomics, every element of every table is written.  An addition to the ABI: cs_abi_version
+ * is unchanged.  All rules are exact integers:
+ *   level     of a pixel, in 0 .. 255.  Exactly one of plane and images_hwc is not NULL: plane uint8 [N][H][W] gives the byte;
+ *             images_hwc uint8 [N][H][W][3] (RGB, any alignment) comes with od_q int32 [256] and Mq int32 [N][3] (ONE stain row
+ *             per image, both on the device; NULL with a plane) and gives clamp((Mq[n][0] od_q[R] + Mq[n][1] od_q[G] +
+ *             Mq[n][2] od_q[B] + 2^23) >> 24, 0, 255), the sum in int64, the shift arithmetic (cs_stain_quantify_labels' level).
+ *   grey      g = level * levels >> 8 with levels = L in {8, 16, 32}.
+ *   offsets   direction k = 0 .. 3 is (dr, dc) = (0, d), (d, d), (d, 0), (d, -d) with d = distance in 1 .. 8.
+ *   pairs     a pixel p with 0 < labels[p] = l <= capacity pairs with q = p + (dr, dc) where q lies inside the image and
+ *             labels[q] == l: C_k[g(p)][g(q)] += 1.  A label need not be connected.  S_k = C_k + C_k^T.
+ *   tables    per (image, row = l - 1, direction): pairs int32 [N][capacity][4] the number of pairs; diff int32
+ *             [N][capacity][4][L], diff[x] = the sum of S_ij over |i - j| = x; sum int32 [N][capacity][4][2L - 1], sum[x] = the
+ *             same over i + j = x; marg int32 [N][capacity][4][L], marg[i] = the sum of S_ij over j; sq int64 [N][capacity][4]
+ *             = the sum of S_ij^2; cross int64 [N][capacity][4] = the sum of i j S_ij; matrix (may be NULL) int32
+ *             [N][capacity][4][L][L] = S.  A label without a pixel, or a direction without a pair, is all zero.
+ * Need capacity >= 1, H W <= 2^30 (then every count is below 2^31, sq < 2^62, cross < 2^41), N capacity 4 (2L - 1) < 2^31 and with
+ * the matrix N capacity 4 L^2 < 2^31; the int32 operands on 4-byte and sq, cross on 8-byte boundaries. */
+int cs_regions_texture_labels(const int32_t* labels, const uint8_t* plane, const uint8_t* images_hwc, const int32_t* od_q,
+                              const int32_t* Mq, int N, int H, int W, int capacity, const int32_t* bbox, int levels, int distance,
+                              int32_t* pairs, int32_t* diff, int32_t* sum, int32_t* marg, int64_t* sq, int64_t* cross,
+                              int32_t* matrix /* may be NULL */, void* stream);
+
 /* ---- a label image scored against another at the object level (csrc/regions.hip) --------------------------------------------
  * pred, truth int32 [N][H][W], values <= 0 = background; sizes and the launch contract as above (a fixed number of launches for
  * given (N, H, W, cap_pred, cap_truth), no synchronisation, capturable).  For image n let Ap[p] / At[g] be the pixel counts of

@@ -5,6 +5,7 @@ they are timed by the wall clock around the synchronised call, median of 5 after
 
     python tools/stain_microbench.py [--size 4096 16384] [--json PATH]
     python tools/stain_microbench.py --quantify [--size 4096] [--json PATH]
+    python tools/stain_microbench.py --texture [--size 4096] [--json PATH]
 
 Synthetic slides of ``size`` x ``size`` RGB pixels, made on the device (those of tools/tissue_microbench.py):
 
@@ -22,7 +23,13 @@ image (805 MB) cannot.
 ``--quantify`` times the per-cell stain tables instead: ``stain.quantify_labels``' one launch pair (cs_stain_quantify_labels) on a
 synthetic H-DAB slide of about 10^4 labelled cells (discs on a grid, a DAB amplitude per cell), next to the path it replaces on the
 same inputs -- ``separate(dtype="u8")``, then per stain the contiguous copy of its channel and ``measure_labels(intensity=)`` -- and
-next to the device-to-device copy of the image; timed the same way, in one process."""
+next to the device-to-device copy of the image; timed the same way, in one process.
+
+``--texture`` times the per-cell co-occurrence tables (cs_regions_texture_labels, one launch) on the same slide and labels: the
+plane route over the slide's haematoxylin plane at 16 and 32 grey levels, with the matrix, and at distance 4, and the stain route
+over the RGB slide, next to ``quantify_labels``, ``measure_labels`` and the copy on the same inputs; and the same launches over a
+uniform plane / slide, where every pixel has one level and all adds of a wave meet in one counter: the gap between the two is what
+that hot spot costs."""
 import argparse
 import json
 import os
@@ -158,18 +165,55 @@ def bench_quantify(size, opts, dev):
     return row
 
 
+def bench_texture(size, opts, dev):
+    x, lab, cells = hdab_cells(size, dev)
+    _, H, W, _ = x.shape
+    row = {"slide": "hdab_cells", "size": [H, W], "cells": cells, "labelled_fraction": float((lab > 0).float().mean())}
+    od = torch.from_numpy(stain.od_table(opts.Io)).to(dev)
+    Mq = torch.from_numpy(stain.quantised_matrix(stain.HDAB, False, opts.conc_max)[None]).to(dev)
+    P = torch.from_numpy(np.ascontiguousarray(np.linalg.pinv(stain.HDAB)[None], dtype=np.float32)).to(dev)
+    m = dict(zip(("counts", "area", "bbox", "sums", "isum", "imax"), K.regions_measure_labels(lab, cells)))
+    bbox, mq0 = m["bbox"], Mq[:, 0].contiguous()
+    plane = K.stain_separate(x, od, P, True, opts.conc_max)[..., 0].contiguous()        # the haematoxylin plane of the noisy slide
+    flat_plane, flat_x = torch.full_like(plane, 100), torch.full_like(x, 120)           # every level equal: all adds of a wave meet
+    dst = torch.empty_like(x)
+    q = K.stain_quantify_labels(x, lab, od, Mq, cells)
+    timed = {"copy": lambda: dst.copy_(x), "quantify": lambda: K.stain_quantify_labels(x, lab, od, Mq, cells, **q),
+             "measure_labels": lambda: K.regions_measure_labels(lab, cells, **{k: v for k, v in m.items() if v is not None})}
+    cases = (("plane_L16", dict(plane=plane, levels=16)), ("plane_L32", dict(plane=plane, levels=32)),
+             ("plane_L16_matrix", dict(plane=plane, levels=16, want_matrix=True)),
+             ("stain_L16", dict(images_u8=x, od_q=od, Mq=mq0, levels=16)),
+             ("plane_L16_d4", dict(plane=plane, levels=16, distance=4)),
+             ("uniform_plane_L16", dict(plane=flat_plane, levels=16)), ("uniform_plane_L32", dict(plane=flat_plane, levels=32)),
+             ("uniform_stain_L16", dict(images_u8=flat_x, od_q=od, Mq=mq0, levels=16)))
+    for key, kw in cases:
+        t = K.texture_labels(lab, cells, bbox, **kw)
+        row[f"{key}_pairs"] = int(t["pairs"].sum())
+        kw = {k: v for k, v in kw.items() if k != "want_matrix"}
+        timed[f"texture_{key}"] = lambda kw=kw, t=t: K.texture_labels(lab, cells, bbox, **kw, **t)
+    for key, fn in timed.items():
+        row[f"{key}_ms"], row[f"{key}_spread_ms"] = time_dev(fn)
+    for key in timed:
+        if key != "copy":
+            row[f"{key}_over_copy"] = row[f"{key}_ms"] / row["copy_ms"]
+    for key in ("plane_L16", "plane_L32", "stain_L16"):
+        row[f"uniform_over_noise_{key}"] = row[f"texture_uniform_{key}_ms"] / row[f"texture_{key}_ms"]
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, nargs="+", default=None)
     ap.add_argument("--json", default=None)
     ap.add_argument("--quantify", action="store_true")
+    ap.add_argument("--texture", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     opts = stain.StainOptions()
     rows = []
-    if args.quantify:
+    if args.quantify or args.texture:
         for size in args.size or [4096]:
-            rows.append(bench_quantify(size, opts, dev))
+            rows.append((bench_texture if args.texture else bench_quantify)(size, opts, dev))
             print(json.dumps(rows[-1]), flush=True)
             torch.cuda.empty_cache()
         args.size = []
