@@ -17,7 +17,11 @@
 //    v_permlane32_swap per dword pair every lane owns 16 contiguous bytes of its pixel's row.  The epilogue exchanges that
 //    arrangement for a row arrangement (4 consecutive lanes = 64 contiguous bytes of one pixel) through a wave-private LDS
 //    scratch -- no workgroup barrier -- because 64 lanes x 64 different rows is address-rate-bound (struct Epilogue).
-//  * 1x1 convolutions: a persistent ring kernel (conv2_ring_kernel) instead of one-shot workgroups.
+//  * 1x1 convolutions: a persistent ring kernel (conv2_ring_kernel) instead of one-shot workgroups.  Its two-source form (template
+//    flag S2, cs_conv2d_fwd_shortcut_packed) multiplies a bottleneck's last 1x1 convolution and the block's 1x1 projection shortcut
+//    in ONE launch: the shortcut's K-channel output -- written once, read back once as the residual, the widest tensor of the block --
+//    lives in the epilogue's LDS scratch instead of HBM, rounded to bf16 as the stored tensor was, so the values are those of the two
+//    launches bit for bit (profiles/shortcut_fusion_notes.md).
 //  * All global->LDS and global->register traffic of the main loop is inline asm with hand-counted s_waitcnt vmcnt(N)
 //    (hipcc drains the queue at every use otherwise, see conv_igemm.hip).
 #include "cs_common.h"
@@ -61,6 +65,15 @@ struct C2Params {
     unsigned src_bytes;
     unsigned pix_bytes;            // SC * 2
     unsigned wpk_bytes;            // whole packed weight tensor (the range check of a raw buffer covers voffset + soffset)
+    // two-source ring forward (conv2_ring_kernel S2, cs_conv2d_fwd_shortcut_packed): a pixel tile walks NCC = NCC_a + NCC_b chunks,
+    // chunks c < NCC_a from src / wpk (the projection shortcut: SH, SW, stride as above), chunks c >= NCC_a from src2 / wpk2 (the main
+    // convolution, stride 1, destination-shaped) -- ALWAYS in that order.  Appended, so that every other kernel finds its fields where
+    // they were.
+    int NCC_a;
+    unsigned src2_bytes, pix2_bytes, wpk2_bytes;
+    const void* src2;
+    const void* wpk2;              // its own packed buffer: row-tile stride NCC_b * 4096
+    const float* shift2;           // nullable: the shift of the FIRST product (the shortcut's folded BN); `shift` is the main convolution's
 };
 
 // n / d for n < 2^31, d >= 2: q = umulhi(n, mg) >> sh with mg = floor(2^(31+l) / d) + 1, sh = l - 1, l = ceil(log2 d)
@@ -1034,7 +1047,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(50))) void c
 // =================================================================================================
 constexpr int R_MB = 96;
 
-template <int TM, bool DG> struct RingEpilogue {
+// S2: the two-source forward.  stash() ends the FIRST product of a pixel tile (the shortcut): accumulator + shift2, rounded to bf16 and
+// written where a residual would have landed by DMA -- the words and the arrangement operator() reads back -- so the second product's
+// epilogue adds it exactly as it added the stored tensor.  shift2 is held like shift, in 16 registers (not in LDS:
+// 80 KiB is what lets two workgroups share a compute unit).
+struct NoShift2 {};
+struct Shift2 { float v[16]; };
+template <int TM, bool DG, bool S2 = false> struct RingEpilogue {
     static constexpr int E_OPS = 5 * TM + (DG ? 2 : 0);
     const C2Params& p;
     unsigned m0w = 0, m0w_next = 0xffffffffu, slab_row = 0;
@@ -1042,6 +1061,7 @@ template <int TM, bool DG> struct RingEpilogue {
     bool alive;
     unsigned region;           // LDS byte address of this wave's TM x 2 KiB
     float sh[16];
+    [[no_unique_address]] std::conditional_t<S2, Shift2, NoShift2> sh2;      // S2: the shortcut's shift of accumulator register r, as sh
     float s1[8];
     i32x4 q_res, q_bin;
     __amdgpu_buffer_rsrc_t r_dst, r_bout, r_slab;
@@ -1108,6 +1128,16 @@ template <int TM, bool DG> struct RingEpilogue {
             if (!DG && p.shift && alive) s = *reinterpret_cast<const float4*>(p.shift + n_w + 8 * g + 4 * hh);
             sh[4 * g] = s.x; sh[4 * g + 1] = s.y; sh[4 * g + 2] = s.z; sh[4 * g + 3] = s.w;
         }
+        if constexpr (S2) {                  // the shortcut's shifts, arranged like sh
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (p.shift2 && alive) s = *reinterpret_cast<const float4*>(p.shift2 + n_w + 8 * g + 4 * hh);
+                sh2.v[4 * g] = s.x; sh2.v[4 * g + 1] = s.y; sh2.v[4 * g + 2] = s.z; sh2.v[4 * g + 3] = s.w;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(sh2.v[r]));
+        }
         // the only compiler-visible loads of the kernel: complete before the loop, so hipcc places no vmcnt wait inside it
 #pragma unroll
         for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(sh[r]));
@@ -1116,13 +1146,24 @@ template <int TM, bool DG> struct RingEpilogue {
         arm_all(first, std::make_integer_sequence<int, TM>{});
     }
 
+    template <int I> __device__ __forceinline__ void stash(const f32x16& acc) {
+        float v[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = acc[r] + sh2.v[r];
+        unsigned pk[8];
+        pack_tile(v, false, pk);
+        lds_put(acc_lds(I, 0), make_uint4(pk[0], pk[1], pk[2], pk[3]));
+        lds_put(acc_lds(I, 1), make_uint4(pk[4], pk[5], pk[6], pk[7]));
+        __builtin_amdgcn_wave_barrier();
+    }
+
     template <int I> __device__ __forceinline__ void operator()(const f32x16& acc) {
         const int lane = threadIdx.x & 63;
         const unsigned pc = piece();
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = DG ? acc[r] : acc[r] + sh[r];
-        if (p.residual) {
+        if (S2 || p.residual) {
             const uint4 xa = lds_get(acc_lds(I, 0)), xb = lds_get(acc_lds(I, 1));
             __builtin_amdgcn_wave_barrier();
             add_residual(v, xa, xb);
@@ -1181,14 +1222,26 @@ template <int TM, bool DG> struct RingEpilogue {
 };
 
 // GA: gathered operand rows (the pixel-paired stem, cs_stem_fwd_packed); a template flag because its per-tile state costs registers
-template <int TM, int WM, int WN, bool DG, bool GA = false>
+// S2: TWO sources (cs_conv2d_fwd_shortcut_packed: a bottleneck's 1x1 projection shortcut and its last 1x1 convolution in one launch,
+// y = act(z . W3 + shift + bf16(x_s . Wd + shift2))).  For every pixel tile the fetch cursor walks NCC_a chunks of the first source
+// (the block input: p.src, stride 1 or 2, weight pack p.wpk), then NCC_b chunks of the second (conv3's input: p.src2, stride 1, its own
+// pack p.wpk2), in that fixed order.  After the first source's last chunk the accumulators are the shortcut's output: RingEpilogue::
+// stash rounds them to bf16 into the LDS rows a residual would have been DMA-ed into and the accumulators restart from zero, so the
+// tile's epilogue adds the very words the separate launch would have stored and read back.  Which source a step reads is
+// wave-uniform (f_c is), so a step still issues one bload4 and two dma_blocks, and the stash issues no memory operation: the counts
+// behind every vmcnt immediate, and the out-of-range tail, are those of the one-source kernel.  The residual buffer stays
+// zero-sized, its DMA (armed one tile ahead, E_OPS holds) writes zeros into those rows BEFORE the stash: for NCC_a >= 3 the step's own
+// wait covers it, for NCC_a = 1, 2 the stash of 32-pixel tile i waits for vmcnt(8 * NCC_a + 5 * (TM - 1 - i)).  The pixel offsets of the other source are recomputed when
+// the cursor crosses NCC_a (one tile_voff per pixel tile and source) instead of holding a second f_vo[2] across the loop.
+template <int TM, int WM, int WN, bool DG, bool GA = false, bool S2 = false>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void conv2_ring_kernel(C2Params p, int n_groups) {
     static_assert(WM * WN == 4 && WM * TM <= 4 && TM >= 2, "a ring slot holds up to 128 pixel rows");
+    static_assert(!S2 || (!DG && !GA && WM == 1), "two sources: forward, 1 x 4 waves, plain operand rows");
     // BM < 128 (1 x 4 waves of 2 or 3 pixel tiles, round 3): the slot keeps its 16 KiB stride, its tail is never read; the DMA
     // blocks past the tile are issued out of range (they count in vmcnt, and write their zeros into that tail)
     constexpr int BM = WM * TM * 32, BN = WN * 32;
     constexpr unsigned SLOT = 16384u, NSLOT = 3u, SLOT_ROWS = 128u;
-    using Epi = RingEpilogue<TM, DG>;
+    using Epi = RingEpilogue<TM, DG, S2>;
     constexpr int E = Epi::E_OPS;
     static_assert(12 + 2 * E <= 63, "vmcnt field");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1213,13 +1266,17 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
     const unsigned smem_base = lds_off(smem);
     const unsigned hhb = (unsigned)hh * 256u;
     const unsigned cf0 = 0xf0u;
-    const unsigned w_base = (unsigned)(n_w >> 5) * (unsigned)NCC * 4096u;
+    const int NCC_a = S2 ? p.NCC_a : NCC;               // chunks of the first source (every pack has its own row-tile stride)
+    const unsigned w_base = (unsigned)(n_w >> 5) * (unsigned)NCC_a * 4096u;
+    const i32x4 rsrc_a2 = S2 ? make_rsrc(p.src2, p.src2_bytes) : rsrc_a;
+    const i32x4 rsrc_b2 = S2 ? make_rsrc(p.wpk2, p.wpk2_bytes) : rsrc_b;
+    const unsigned w_base2 = S2 ? (unsigned)(n_w >> 5) * (unsigned)(NCC - NCC_a) * 4096u : 0u;
 
     // this wave's two 16-row blocks (wave, wave + 4) of pixel tile mt: byte offset of (row, chunk column) or out of range
     // gathered rows (the pixel-paired stem: 7 x 4 taps of 16 bytes, stride 2 rows / 1 pair, pad 3 rows / 2 pairs): per block the byte
     // base of the row's image (~0: no such row) and its first tap's source row / pair; slot (kh, pw) adds (kh * GWp + pw) * 16 bytes
     int f_gy[2] = {0, 0}, f_gx[2] = {0, 0};
-    auto tile_voff = [&](unsigned mt, unsigned (&vo)[2]) {
+    auto tile_voff = [&](unsigned mt, unsigned (&vo)[2], bool src_b = false) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const unsigned m = mt * BM + 16u * (unsigned)(wave + 4 * j) + (unsigned)(lane & 15);
@@ -1235,6 +1292,12 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
                 continue;
             }
             unsigned pix = m;
+            if constexpr (S2) {
+                if (src_b) {             // (wave-uniform) the second source: destination-shaped, its own pixel size
+                    vo[j] = (m < p.M && mt != 0xffffffffu) ? m * p.pix2_bytes + (unsigned)(lane >> 4) * 16u : OOB;
+                    continue;
+                }
+            }
             if (p.stride > 1) {
                 const unsigned yall = udivm(m, p.mg_dw, p.sh_dw);
                 const unsigned x = m - yall * (unsigned)p.DW;
@@ -1259,6 +1322,13 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
     tile_voff(f_mt, f_vo);
     auto advance_fetch = [&]() {
         f_slot = f_slot == NSLOT - 1 ? 0u : f_slot + 1u;
+        if constexpr (S2) {
+            if (f_c + 1 == NCC_a) {                      // first -> second source inside the pixel tile (1 <= NCC_a < NCC)
+                ++f_c;
+                tile_voff(f_mt, f_vo, true);
+                return;
+            }
+        }
         if (++f_c == NCC) {
             f_c = 0;
             if (f_mt != 0xffffffffu) {
@@ -1270,6 +1340,12 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
     };
     auto issue_b = [&]<int J>() {
         const unsigned bv = (alive && f_mt != 0xffffffffu) ? (unsigned)lane * 16u : OOB;
+        if constexpr (S2) {
+            if (f_c >= NCC_a) {
+                bload4<J>(rsrc_b2, bv, w_base2 + (unsigned)(f_c - NCC_a) * 4096u);
+                return;
+            }
+        }
         bload4<J>(rsrc_b, bv, w_base + (unsigned)f_c * 4096u);
     };
     auto issue_a = [&]() {
@@ -1287,6 +1363,13 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
                 dma_block2(rsrc_a, dst + (unsigned)(wave + 4 * j) * 2048u, slot_off(s0), slot_off(s0 + 4));
             }
             return;
+        }
+        if constexpr (S2) {
+            if (f_c >= NCC_a) {
+                dma_block(rsrc_a2, dst + (unsigned)wave * 2048u, f_vo[0], (unsigned)(f_c - NCC_a) * 128u);
+                dma_block(rsrc_a2, dst + (unsigned)(wave + 4) * 2048u, f_vo[1], (unsigned)(f_c - NCC_a) * 128u);
+                return;
+            }
         }
         dma_block(rsrc_a, dst + (unsigned)wave * 2048u, f_vo[0], (unsigned)f_c * 128u);
         dma_block(rsrc_a, dst + (unsigned)(wave + 4) * 2048u, f_vo[1], (unsigned)f_c * 128u);
@@ -1320,7 +1403,23 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(48))) void c
         const unsigned sh_cur = slot * SLOT_ROWS;          // the slot, in LDS rows
         const bool fin = c == NCC - 1;
         bool more = true;
-        if (!fin) {
+        if (S2 && c == NCC_a - 1) {
+            if constexpr (S2) {
+                // the first product of the pixel tile is complete: round it into the residual rows, restart the accumulators.  The
+                // zeros E(s - NCC_a) armed for the rows of 32-pixel tile i must have landed.  Issued behind them: the 5 operations
+                // of each later 32-pixel tile of that epilogue and the 8 loads of each of the NCC_a steps since (this one's
+                // included) -- for NCC_a >= 3 the step's own wait covered them.  No memory operation is issued here, and the step
+                // is no epilogue for fin1 / fin2.
+                auto on_stash = [&]<int i>(const f32x16& d) {
+                    if (NCC_a == 1) wait_vm_mem<8 + 5 * (TM - 1 - i)>();
+                    else if (NCC_a == 2) wait_vm_mem<16 + 5 * (TM - 1 - i)>();
+                    epi.template stash<i>(d);
+                };
+                tap_mfma<TM, CUR, 0, 0u, 0u, true, false, true, true>(qb[0], qb[1], qb[2], qb[3], sh_cur, 0u, hhb, cf0, on_stash);
+                vzero_seq(std::make_integer_sequence<int, 16 * TM>{});
+                ++c;
+            }
+        } else if (!fin) {
             tap_mfma<TM, CUR, 0, 0u, 0u, true, false, true, false>(qb[0], qb[1], qb[2], qb[3], sh_cur, 0u, hhb, cf0);
             ++c;
         } else {
@@ -1607,6 +1706,38 @@ bool plan_gemm(const CsConvGeom* g, int dgrad, C2Plan& pl) {
     return true;
 }
 
+// The two-source ring forward (conv2_ring_kernel S2): `a` is the main 1x1 convolution (stride 1, pad 0), `b` the 1x1 projection shortcut
+// (pad 0, stride 1 or 2) whose output would have been a's residual.  Same N, P, Q, K on both; K in whole 128-channel tiles (1 x 4
+// waves), both contractions in whole 64-channel chunks; pixel indices and the byte offsets of both sources and both weight packs in
+// 31 bits.  The SHORTCUT is the kernel's first source (p.src, p.wpk, p.stride; p.shift2), the main convolution its second (p.src2,
+// p.wpk2; p.shift).  Tile height and group count as for the one-source launch (pick_tm, ring_groups).
+bool plan_shortcut(const CsConvGeom* a, const CsConvGeom* b, C2Plan& pl) {
+    for (const CsConvGeom* g : {a, b}) {
+        if (g->groups > 1 || g->R != 1 || g->S != 1 || g->pad != 0 || g->N < 1 || g->H < 1 || g->W < 1 || g->C < 64 || g->C % 64) return false;
+        if (g->stride < 1 || g->P != (g->H - 1) / g->stride + 1 || g->Q != (g->W - 1) / g->stride + 1) return false;
+    }
+    if (a->stride != 1 || (b->stride != 1 && b->stride != 2)) return false;
+    if (a->N != b->N || a->P != b->P || a->Q != b->Q || a->K != b->K) return false;
+    if (a->K < 128 || a->K % 128) return false;
+    if (b->stride > 1 && (a->P < 2 || a->Q < 2)) return false;          // (destination pixel -> (n, y, x) by the magic numbers of fill_params)
+    pl.kind = C2Kind::Ring14;
+    if (!fill_params(pl, b->N, b->H, b->W, b->C, (unsigned)b->C * 2u, b->P, b->Q, b->K, 1)) return false;
+    const unsigned long long src2_bytes = (unsigned long long)a->N * a->H * a->W * (unsigned long long)a->C * 2ull;
+    const unsigned long long wbytes2 = packed_weight_bytes(a->K, 1, a->C);
+    if (src2_bytes >= 0x80000000ull || wbytes2 >= 0x80000000ull) return false;
+    C2Params& p = pl.p;
+    p.stride = b->stride; p.add_stride = 1;
+    p.NCC_a = p.NCC;
+    p.NCC = p.NCC_a + a->C / 64;
+    p.src2_bytes = (unsigned)src2_bytes;
+    p.pix2_bytes = (unsigned)a->C * 2u;
+    p.wpk2_bytes = (unsigned)wbytes2;
+    pl.tm = pick_tm(p.M, p.n_ntiles);
+    pl.nbw = 0;
+    pl.rows = partial_rows(pl);
+    return true;
+}
+
 // The tail of every launch: 256 threads, `grid` workgroups, `lds` bytes of dynamic LDS -- beyond 64 KiB it has to be allowed per
 // (device, kernel): cs_api.cpp keeps the table --, `name` for cs_last_conv_variant()
 template <typename F, typename... Args>
@@ -1638,6 +1769,17 @@ int launch_ring_t(const C2Params& p, hipStream_t st) {
         return CS_ERR_UNSUPPORTED;
     }
     return launch_kernel(conv2_ring_kernel<TM, WM, WN, DG>, name, best * (unsigned)p.n_ntiles, lds, st, p, (int)best);
+}
+
+// the two-source forward (plan_shortcut): grid and LDS as launch_ring_t<TM, 1, 4, false>; the sixth template argument names the form
+template <int TM>
+int launch_ring2_t(const C2Params& p, hipStream_t st) {
+    const unsigned n_mt = (unsigned)cs_ceil_div(p.M, 32 * TM);
+    const unsigned best = ring_groups(n_mt, (unsigned)p.n_ntiles, nullptr);
+    const size_t lds = 3 * 16384 + 4 * (size_t)TM * 2048;
+    char name[64];
+    snprintf(name, sizeof(name), "conv2_ring_kernel<%d,1,4,false,false,true>", TM);
+    return launch_kernel(conv2_ring_kernel<TM, 1, 4, false, false, true>, name, best * (unsigned)p.n_ntiles, lds, st, p, (int)best);
 }
 
 template <int TM, int WM, int WN, int NBW, bool DG, bool T2D = false>
@@ -1743,6 +1885,32 @@ extern "C" int cs_conv2d_fwd_packed(const CsConvGeom* g, const void* x, const vo
     pl.p.shift = shift; pl.p.residual = residual; pl.p.act = act;
     pl.p.bits_out = positive_bits;
     return launch_plan(pl, reinterpret_cast<hipStream_t>(stream), false);
+}
+
+extern "C" int cs_conv2d_fwd_shortcut_supported(const CsConvGeom* main, const CsConvGeom* shortcut) {
+    if (!main || !shortcut) return 0;
+    C2Plan pl;
+    return plan_shortcut(main, shortcut, pl) ? 1 : 0;
+}
+
+extern "C" int cs_conv2d_fwd_shortcut_packed(const CsConvGeom* main, const void* x, const void* w_packed, const float* shift,
+                                             const CsConvGeom* shortcut, const void* x_in, const void* w_packed_sc, const float* shift_sc, int act,
+                                             void* y, uint8_t* positive_bits, void* stream) {
+    CS_CHECK_ARG(main && shortcut, "conv2d_fwd_shortcut_packed: NULL geometry");
+    CS_CHECK_ARG(x && w_packed && x_in && w_packed_sc && y, "conv2d_fwd_shortcut_packed: NULL tensor");
+    CS_CHECK_ARG(act == CS_ACT_NONE || act == CS_ACT_RELU, "conv2d_fwd_shortcut_packed: activation must be none or ReLU");
+    C2Plan pl;
+    if (!plan_shortcut(main, shortcut, pl)) {
+        cs_set_error_("conv2d_fwd_shortcut_packed: geometry pair not served (ask cs_conv2d_fwd_shortcut_supported first)");
+        return CS_ERR_UNSUPPORTED;
+    }
+    C2Params& p = pl.p;
+    p.src = x_in; p.wpk = w_packed_sc; p.shift2 = shift_sc;
+    p.src2 = x; p.wpk2 = w_packed; p.shift = shift;
+    p.dst = y; p.act = act; p.bits_out = positive_bits;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (pl.tm == 3) return launch_ring2_t<3>(p, st);
+    return launch_ring2_t<4>(p, st);
 }
 
 extern "C" int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const void* w_packed, const void* add, int add_stride,

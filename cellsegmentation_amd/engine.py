@@ -34,6 +34,7 @@ ACT_NONE, ACT_RELU, ACT_SILU = K.CS_ACT_NONE, K.CS_ACT_RELU, K.CS_ACT_SILU
 PACKED = True              # packed-operand conv kernels (False: first-generation igemm everywhere; tests flip it for a reference path)
 PACKED_TRAIN_BN = True     # ... also for heavy 3x3 convolutions under batch-statistics BN
 FUSE_STEM_POOL = True      # eval-BN bf16 stem + ReLU + the max-pool behind it in one launch (False: the two launches; tests compare the two)
+FUSE_SHORTCUT = True       # eval-BN bf16 1x1 projection shortcut inside the block's last 1x1 forward (False: the two launches; tests compare the two)
 
 
 class ConvUnit:
@@ -68,7 +69,9 @@ class ConvUnit:
         Kp = K.pad_channels(conv.out_channels)
         R, S = conv.kernel_size
         geom = K.make_geom(N, H, W, Cp, Kp, R, S, conv.stride[0], conv.padding[0])
-        res = f.t[self.res] if self.res is not None else None
+        # (a projection shortcut fused into this launch left its operands instead of a residual tensor: see below)
+        sc = f.fused_sc.pop(ui, None)
+        res = f.t[self.res] if (self.res is not None and sc is None) else None
         batch_stats = _bn_uses_batch_stats(self.bn, f.bn_train)
         st = f.staged(ui, self, geom, batch_stats)
         # the stem runs on a pixel-paired image (kernels.stem_*): 28 instead of 49 K chunks
@@ -98,6 +101,31 @@ class ConvUnit:
             # one bit per output next to a ReLU output of a pass that will run backward: the data gradient that later masks with
             # this tensor reads 1 byte per 16 (the bf16 masks are ~1/8 of a training step's HBM traffic)
             want_bits = f.save and self.act == ACT_RELU
+            main_ui = f.sc_pairs.get(ui)
+            if main_ui is not None and st.fwd_packed:
+                # this unit is the 1x1 projection shortcut of a block whose last 1x1 convolution (unit main_ui) is its only reader:
+                # that launch multiplies both (kernels.conv_fwd_shortcut_packed).  Staged here, aux recorded for backward (which
+                # needs the block input and the incoming gradient only), the slot never materialised.  The operands travel in
+                # fused_sc, so the block input outlives its release in a no-grad pass until the main unit has run.
+                um = f.plan.units[main_ui]
+                zN, zH, zW, zC = f.t[um.src].shape
+                gm = K.make_geom(zN, zH, zW, zC, K.pad_channels(um.conv.out_channels), 1, 1, 1, 0)
+                # (both operands staged packed -- the main unit's flag is the one its own f.staged() will compute -- and the pair served)
+                main_packed = _packed_flags(f.plan, um, gm, f.dtype, False, False, f.bits, f.bn_train)[0]
+                if main_packed and K.conv_fwd_shortcut_supported(gm, geom, f.dtype):
+                    f.fused_sc[main_ui] = (geom, st, x)
+                    f.aux[ui] = SimpleNamespace(geom=geom, st=st, train=False, xp=None)
+                    return
+            if sc is not None:
+                if not st.fwd_packed:
+                    raise RuntimeError(f"{self.name}: a shortcut was left for this launch but its operand is not staged packed")
+                gv, stv, x_in = sc
+                y = K.conv_fwd_shortcut_packed(geom, x, st.w_khwc, st.shift, gv, x_in, stv.w_khwc, stv.shift, self.act, want_bits=want_bits)
+                if want_bits:
+                    y, f.bits[self.dst] = y
+                f.aux[ui] = SimpleNamespace(geom=geom, st=st, train=False, xp=None)
+                f.t[self.dst] = y
+                return
             pool_ui = None
             if stem and PACKED and FUSE_STEM_POOL and self.act == ACT_RELU and K.stem_pool_fwd_supported(geom, f.dtype):
                 pool_ui = _sole_pool_consumer(f.plan, self)
@@ -387,6 +415,48 @@ def _sole_pool_consumer(plan, u):
     return None
 
 
+def shortcut_pairs(plan, bn_train):
+    """{index of a projection-shortcut unit v: index of the unit u that takes v's output as its residual} for every pair one launch can
+    serve (FUSE_SHORTCUT): both ungrouped 1x1 convolutions without padding, u of stride 1 and v of stride 1 or 2, v without
+    activation or residual of its own, v's output read by u alone and no plan output, u's input already there when v runs, a folded
+    (not batch-statistics) BN or none on both.  What depends on the pass -- bf16, packed staging, the extents the library serves --
+    is asked in ConvUnit.fwd.  Decided once per plan and BN mode (cached on the plan)."""
+    if not (PACKED and FUSE_SHORTCUT):
+        return {}
+    key = (bool(bn_train), tuple(u.bn.training for u in plan.units if u.kind == "conv" and u.bn is not None))
+    cache = plan.__dict__.setdefault("_shortcut_pairs", {})
+    if key not in cache:
+        cache[key] = _find_shortcut_pairs(plan, bn_train)
+    return cache[key]
+
+
+def _find_shortcut_pairs(plan, bn_train):
+    producer = {v.dst: vi for vi, v in enumerate(plan.units) if v.kind == "conv"}
+    made_by = {w.dst: wi for wi, w in enumerate(plan.units)}
+    pairs = {}
+    for ui, u in enumerate(plan.units):
+        vi = producer.get(u.res) if u.kind == "conv" and u.res is not None else None
+        if vi is None or vi >= ui:
+            continue
+        v = plan.units[vi]
+
+        def one_by_one(w, strides):
+            c = w.conv
+            return not w.grouped and c.kernel_size == (1, 1) and c.padding == (0, 0) and c.stride in strides
+        if not (one_by_one(u, ((1, 1),)) and one_by_one(v, ((1, 1), (2, 2)))):
+            continue
+        if v.act != ACT_NONE or v.res is not None or u.act not in (ACT_NONE, ACT_RELU):
+            continue
+        if plan.consumers.get(v.dst, 0) != 1 or v.dst in plan.outputs:
+            continue
+        if u.src not in plan.inputs and made_by.get(u.src, len(plan.units)) >= vi:
+            continue          # (v asks the library with u's input extents, and hands its operands to the NEXT launch of u)
+        if _bn_uses_batch_stats(u.bn, bn_train) or _bn_uses_batch_stats(v.bn, bn_train):
+            continue
+        pairs[vi] = ui
+    return pairs
+
+
 def _stem_takes_nchw(plan, dtype):
     """True when the plan's input feeds exactly one unit and that unit is the pixel-paired bf16 stem: the fp32 NCHW image can go
     straight to the paired operand (cs_stem_pair_from_nchw) and the NHWC8 tensor is never made."""
@@ -564,6 +634,10 @@ class _Forward:
         if bn_train and save:
             K.begin_pass(dev)
         self.bits = {}       # slot -> uint8 "output > 0" bit tensor (folded Conv+BN+ReLU outputs of a pass that will run backward)
+        # projection shortcuts that ride in their block's last 1x1 launch (shortcut_pairs: cached on the plan), and the operands a
+        # shortcut unit left for that launch {main unit index: (geometry, staged set, block input)}
+        self.sc_pairs = shortcut_pairs(plan, bn_train) if dtype == torch.bfloat16 else {}
+        self.fused_sc = {}
         n_stats = sum(K.accum_words(K.pad_channels(u.conv.out_channels)) for u in plan.units
                       if u.kind == "conv" and _bn_uses_batch_stats(u.bn, bn_train)) if bn_train else 0
         self.stats = _Arena(n_stats, torch.float64, dev, 1)

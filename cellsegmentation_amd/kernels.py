@@ -315,6 +315,25 @@ def conv_fwd_packed(geom, x, w_packed, shift=None, residual=None, act=CS_ACT_NON
     return (y, bits) if want_bits else y
 
 
+def conv_fwd_shortcut_supported(geom, geom_sc, dtype):
+    """Does one launch serve the 1x1 convolution `geom` together with the 1x1 projection shortcut `geom_sc` that feeds its residual
+    (conv_fwd_shortcut_packed; bf16 only)?"""
+    return dtype == torch.bfloat16 and bool(_lib.load().cs_conv2d_fwd_shortcut_supported(ctypes.byref(geom), ctypes.byref(geom_sc)))
+
+
+def conv_fwd_shortcut_packed(geom, x, w_packed, shift, geom_sc, x_in, w_packed_sc, shift_sc, act=CS_ACT_NONE, want_bits=False, out=None):
+    """y = act(conv(x, w) + shift + bf16(conv(x_in, w_sc) + shift_sc)): the two 1x1 convolutions in one launch -- the shortcut's
+    output never reaches memory, the values are those of the two launches.  Timed under the main geometry: the row's byte and FLOP
+    model (that of a one-source forward) does not count the second source."""
+    y = out if out is not None else torch.empty((geom.N, geom.P, geom.Q, geom.K), dtype=x.dtype, device=x.device)
+    bits = torch.empty((geom.N, geom.P, geom.Q, geom.K // 8), dtype=torch.uint8, device=x.device) if want_bits else None
+    lib = _lib.load()
+    _lib.check(_timed("fwd", geom, x.dtype, lambda: lib.cs_conv2d_fwd_shortcut_packed(
+        ctypes.byref(geom), _p(x), _p(w_packed), _p(shift), ctypes.byref(geom_sc), _p(x_in), _p(w_packed_sc), _p(shift_sc), act, _p(y), _p(bits),
+        _stream()), extra_tensors=1.0 / 16 if want_bits else 0.0), "conv2d_fwd_shortcut_packed")
+    return (y, bits) if want_bits else y
+
+
 class CompactGrad:
     """The data gradient of a stride-2 1x1 convolution in compact form: `t` [N][P][Q][C] holds the values of the destination pixels
     (2y, 2x); every other pixel of that gradient is zero and was never written.  Only a packed 1x1 data gradient can consume it

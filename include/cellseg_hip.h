@@ -470,6 +470,17 @@ int cs_conv2d_fwd_packed(const CsConvGeom* g, const void* x, const void* w_packe
                          void* y, uint8_t* positive_bits, void* stream);
 int cs_conv2d_dgrad_packed(const CsConvGeom* g, const void* dy, const void* w_packed, const void* add, int add_stride,
                            const uint8_t* mask_bits, void* dx, float* partial_rows, void* stream);
+/* The last 1x1 convolution of a bottleneck block and the block's 1x1 projection shortcut (model/resnet.py:58) in ONE launch of the
+ * ring kernel: y = act(conv(x, w) + shift + bf16(conv(x_in, w_sc) + shift_sc)) -- the shortcut's output, which cs_conv2d_fwd_packed
+ * would read back as `residual`, is rounded to bf16 into LDS instead of being written to memory, so y holds the bits of the two ring
+ * launches it replaces.  main: 1x1, stride 1,
+ * pad 0; shortcut: 1x1, pad 0, stride 1 or 2; both with the same N, P, Q, K, K a multiple of 128, both C multiples of 64.  Each
+ * operand as cs_conv2d_fwd_packed takes it for its own geometry (two packed weight buffers, two nullable shift vectors);
+ * positive_bits as there.  cs_conv2d_fwd_shortcut_supported: 1 where the pair is served, else 0 (two launches then). */
+int cs_conv2d_fwd_shortcut_supported(const CsConvGeom* main, const CsConvGeom* shortcut);
+int cs_conv2d_fwd_shortcut_packed(const CsConvGeom* main, const void* x, const void* w_packed, const float* shift,
+                                  const CsConvGeom* shortcut, const void* x_in, const void* w_packed_sc, const float* shift_sc, int act,
+                                  void* y, uint8_t* positive_bits, void* stream);
 
 /* ---- stem on a pixel-paired image (Conv2d(3, 64, 7, stride 2, padding 3), model/resnet.py:111) ---------------------------
  * With 3 channels padded to one 16-byte chunk per pixel the implicit GEMM walks 49 chunks of which 147/392 elements are real.

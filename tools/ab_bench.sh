@@ -8,11 +8,15 @@ for d in $other .; do
   f=$(find $out/prof_$tag -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $out/stats_$tag.csv; rm -rf $out/prof_$tag
 done
 python - <<EOF
-import csv, glob
+import csv, glob, re
+def ring(n):
+    # conv2_ring_kernel's sixth template flag (two sources) is spelled only where it is set, so that the one-source rows of a tree
+    # from before the flag and of this one carry the same name (tools/summarize_profile.py ring_variant)
+    return re.sub(r'(conv2_ring_kernel<(?:[^,<>]+,){4}[^,<>]+),\s*false>', r'\1>', n)
 def load(p):
     d={}
     for r in csv.DictReader(open(p)):
-        d[r['Name']]=(int(r['Calls']), float(r['TotalDurationNs'])/1e6/25)
+        c,t=d.get(ring(r['Name']),(0,0.0)); d[ring(r['Name'])]=(c+int(r['Calls']), t+float(r['TotalDurationNs'])/1e6/25)
     return d
 fs=sorted(glob.glob('$out/stats_*.csv')); a,b=load(fs[0]),load(fs[1]); print(fs)
 rows=[]

@@ -33,10 +33,17 @@ def _pretty_local(n):
     return f"{name}<{','.join(args)}>"
 
 
+def ring_variant(name):
+    """conv2_ring_kernel's sixth template flag (two sources: the projection shortcut inside the block's last 1x1 forward) is spelled
+    only where it is set: `<4,1,4,false,false,true>` is the two-source form, `<...,false>` is written without it -- the variant
+    strings of cs_last_conv_variant(), and the rows of profiles taken before the flag existed."""
+    return re.sub(r"(conv2_ring_kernel<(?:[^,<>]+,){4}[^,<>]+),\s*false>", r"\1>", name)
+
+
 def demangle(n):
     loc = _pretty_local(n)
     if loc:
-        return loc
+        return ring_variant(loc)
     try:
         out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt", n], capture_output=True, text=True).stdout.strip() or n
     except OSError:
@@ -44,7 +51,7 @@ def demangle(n):
     out = out.replace("(anonymous namespace)::", "").replace("__bf16", "bf16")
     out = re.sub(r"\((?:[^()]|\([^()]*\))*\)$", "", out)          # drop the parameter list
     out = re.sub(r"^void ", "", out)
-    return out[:110]
+    return ring_variant(out)[:110]
 
 
 def main():
